@@ -32,6 +32,12 @@ The JSON line also carries
                  k-means objective of both) and next to the committed full-size golden made by the reference itself
                  (tests/golden/ref_goldens_25m.json, read as data: device == oracle mode B bit for bit; the reference's n_iter).
 
+    python bench.py ... --dump-outputs DIR
+
+writes what the last timed step returned to its caller (rank 0's part) as DIR/<name>.npy, float32 / float64, about 42 MB: per tensor
+the centres, index histogram, Huffman code lengths and scalars; per weight the quantized values, indices and prune mask at 2^21
+positions drawn with a fixed seed.  The inputs are seeded, so two builds given the same arguments can be compared array by array.
+
     python bench.py --config 4 [--gpus N] ...
 
 BASELINE.json configs[4] instead: the 122 tensors of a GPT-2-small-sized model (124.4 M weights), per tensor prune -> 4-bit
@@ -94,7 +100,66 @@ def parse():
     ap.add_argument("--backend", default="nccl", help="torch.distributed backend for N > 1 (nccl = RCCL; gloo only to rehearse "
                                                       "the multi-rank path with all ranks on one GPU: --one-device)")
     ap.add_argument("--one-device", action="store_true", help="rehearsal: every rank uses cuda:0")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", help="after the timed steps: write what the last timed step returned (rank 0's part) as "
+                                                          "DIR/<name>.npy, float32 / float64; per-weight outputs at a fixed, seeded sample of positions")
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    return args
+
+
+DUMP_SAMPLE = 1 << 21   # positions of the per-weight outputs --dump-outputs writes (values, indices, mask: 8 MB each, positions 16 MB)
+DUMP_SEED = 1234
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, results):
+    """--dump-outputs: what the last timed step handed its caller, one LayerResult per tensor (None: a tensor this rank does not
+    hold).  Per tensor (one row each): centres, index histogram, Huffman code lengths, iterations, relocations, sigma, threshold,
+    zeroed weights, total Huffman bits.  Per weight: the quantized values, the centroid indices and the prune mask of the held
+    tensors laid end to end, at DUMP_SAMPLE positions drawn with a fixed seed (all of them when there are fewer).  NaN: no value."""
+    import torch
+
+    held = [r for r in results if r is not None]
+    k = max([r.model.cluster_centers_.size for r in held if r.model is not None], default=0)
+    t = len(results)
+    rows = {"centers": np.full((t, k), np.nan, np.float32), "counts": np.full((t, k), np.nan), "code_lengths": np.full((t, k), np.nan, np.float32)}
+    scal = {nm: np.full(t, np.nan) for nm in ("n_iter", "n_relocations", "sigma", "threshold", "nzeroed", "total_bits")}
+    for i, r in enumerate(results):
+        if r is None:
+            continue
+        for nm, v in (("sigma", r.sigma), ("threshold", r.threshold), ("nzeroed", r.nzeroed), ("total_bits", r.total_bits)):
+            if v is not None:
+                scal[nm][i] = v
+        if r.model is not None:
+            c = r.model.cluster_centers_.ravel()
+            rows["centers"][i, :c.size] = c
+            if r.counts is not None:
+                rows["counts"][i, :c.size] = r.counts
+                rows["code_lengths"][i, :c.size] = r.code_lengths
+            scal["n_iter"][i], scal["n_relocations"][i] = r.model.n_iter_, r.model.n_relocations_
+    sizes = [int(r.values.numel()) for r in held]
+    n = sum(sizes)
+    pos = np.sort(np.random.default_rng(DUMP_SEED).choice(n, DUMP_SAMPLE, replace=False)) if n > DUMP_SAMPLE else np.arange(n)
+    per_weight = {nm: np.full(pos.size, np.nan, np.float32) for nm in ("values", "labels", "mask")}
+    lo = 0
+    for r, sz in zip(held, sizes):
+        a, b = np.searchsorted(pos, [lo, lo + sz])
+        if b > a:
+            at = torch.from_numpy(pos[a:b] - lo).to(r.values.device)
+            per_weight["values"][a:b] = r.values.reshape(-1)[at].float().cpu().numpy()
+            if r.model is not None:
+                per_weight["labels"][a:b] = r.model.labels_device()[at].float().cpu().numpy()
+            if r.mask is not None:
+                per_weight["mask"][a:b] = r.mask.reshape(-1)[at].float().cpu().numpy()
+        lo += sz
+    arrays = {**rows, **scal, **per_weight, "positions": pos.astype(np.float64)}
+    total = sum(v.nbytes for v in arrays.values())
+    assert total <= DUMP_MAX_BYTES, f"--dump-outputs: {total} bytes"
+    os.makedirs(out_dir, exist_ok=True)
+    for nm, v in arrays.items():
+        np.save(os.path.join(out_dir, nm + ".npy"), v)
+    print(f"[bench] {len(arrays)} arrays ({total / 1e6:.1f} MB) written to {out_dir}", file=sys.stderr)
 
 
 def cpu_baseline(args, w_full: np.ndarray):
@@ -392,6 +457,8 @@ def main_config4(args):
         }
         if world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline_config4(args, layers)
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, res if group is None else [rec.result for rec in res])
         print(json.dumps(out))
     if comm is not None:
         comm.close()
@@ -672,6 +739,8 @@ def main():
             out["parity"] = parity_record(args, res, None, None, 0, 0)
         if agreement is not None:
             out["config"]["ranks_agree"] = agreement
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, [res])
         print(json.dumps(out))
     if comm is not None:
         comm.close()

@@ -5,6 +5,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -46,3 +47,34 @@ def test_bench_line_contract_configs3_reduced():
 def test_bench_input_pool_fallback_says_so():
     d = _run(["--n", "1000000", "--no-cpu-baseline", "--no-streaming-leg", "--input-pool-gb", "0"])
     assert d["config"]["input"].startswith("one resident vector, copied")
+
+
+@pytest.mark.gpu
+def test_bench_dump_outputs_are_the_last_steps_results_and_repeat(tmp_path):
+    """--dump-outputs: the same arguments give the same arrays run after run; they are the step's results (decoded value = centre of
+    the index, the index histogram over every weight, the prune mask of the seeded input at the sampled positions)."""
+    from neural_network_compression_amd import synth
+    from oracle import oracle as orc
+
+    n = 3_000_000
+    dumps = []
+    for name in ("a", "b"):
+        d = _run(["--n", str(n), "--no-cpu-baseline", "--no-streaming-leg", "--dump-outputs", str(tmp_path / name)])
+        assert d["steps"] == 3
+        dumps.append({f[:-4]: np.load(tmp_path / name / f) for f in os.listdir(tmp_path / name)})
+    a, b = dumps
+    assert a.keys() == b.keys() and all(np.array_equal(a[k], b[k]) for k in a)
+    assert all(v.dtype in (np.float32, np.float64) for v in a.values()) and sum(v.nbytes for v in a.values()) <= 64 << 20
+    pos = a["positions"].astype(np.int64)
+    assert pos.size == 1 << 21 and np.all(np.diff(pos) > 0) and pos[-1] < n
+    lab = a["labels"].astype(np.int64)
+    assert np.array_equal(a["values"], a["centers"][0][lab])
+    assert a["counts"].shape == (1, 257) and a["counts"].sum() == n and a["n_iter"][0] >= 1
+    w = synth.weights((n,), 4000)
+    mask = orc.prune_weigth(w, 1, True)
+    assert np.array_equal(a["mask"].astype(bool), mask[pos]) and a["nzeroed"][0] == mask.sum()
+
+
+def test_bench_refuses_zero_steps():
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "0"], cwd=ROOT, capture_output=True, text=True, timeout=120)
+    assert out.returncode == 2 and "--steps" in out.stderr
