@@ -535,6 +535,21 @@ int nnc_centroid_grad_f32(const float *grad, const void *labels, int label_bytes
 int nnc_gather_f32(const float *centers_dev, int32_t k, const void *labels, int label_bytes, int64_t n, float *out, void *stream);
 
 /* ------------------------------------------------------------------------------------
+ * The quantized layer run from its stored form (csrc/nnc_cbmm.hip): y[m, ncols] = x[m, kdim] @ W + bias, then ReLU if relu != 0,
+ * with W[i, o] = centers_dev[labels[i * ncols + o]] never written out in float32.  labels = the flattened quantized tensor in the
+ * order the fit saw it (Keras Dense kernel (in, out): kdim = in; Conv2D kernel (h, w, in, out): kdim = h * w * in; ncols = out),
+ * uint8 (label_bytes 1, k <= 256) or uint16 (label_bytes 2), any alignment; x, y contiguous float32 on the device; bias_dev
+ * float32[ncols] or NULL.  An index >= k reads 0 (as nnc_gather_f32).  m <= 16 streams the indices (k_cbmm_stream), larger m
+ * dequantizes W tiles into LDS (k_cbmm_tiled); split-K partials go to the workspace and are summed in split order by
+ * k_cbmm_reduce: no float atomics, the same call gives the same bits.  m or ncols = 0 is a no-op; kdim = 0 writes y = bias (or 0).
+ * nnc_cbmm_workspace_bytes: what nnc_cbmm_f32 needs for that shape (0 for none; host arithmetic only, no device query).
+ * Argument errors (NNC_EINVAL; NNC_ENOSPACE for a short workspace) are returned before any HIP call.
+ * ---------------------------------------------------------------------------------- */
+int64_t nnc_cbmm_workspace_bytes(int64_t m, int64_t kdim, int64_t ncols, int label_bytes);
+int nnc_cbmm_f32(const float *x, int64_t m, int64_t kdim, const void *labels, int label_bytes, int64_t ncols, const float *centers_dev, int32_t k,
+                 const float *bias_dev, int32_t relu, float *y, void *workspace, int64_t workspace_bytes, void *stream);
+
+/* ------------------------------------------------------------------------------------
  * Multi-GPU: the vector is sharded across one process per GPU (contiguous shards starting on multiples of
  * NNC_CHUNK elements); the exchange per Lloyd iteration is one all-reduce (SUM) of the 2K int64 sums / counts over
  * RCCL / xGMI, enqueued by the library on the caller's stream between its own kernels.  The reference has no

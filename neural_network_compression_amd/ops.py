@@ -285,6 +285,41 @@ def gather(centers: torch.Tensor, labels: torch.Tensor) -> torch.Tensor:
     return out
 
 
+def codebook_matmul(x: torch.Tensor, labels: torch.Tensor, centers: torch.Tensor, kdim: int, ncols: int,
+                    bias: torch.Tensor | None = None, relu: bool = False) -> torch.Tensor:
+    """y = x @ W + bias (then ReLU) with W[i, o] = centers[labels[i * ncols + o]] read from the indices, never decoded to float32
+    (include/nnc.h, nnc_cbmm_f32).  x: float32 (..., kdim); labels: the kdim * ncols uint8 / 16-bit indices (QuantizedModel.
+    labels_compact_, any storage offset); centers: float32[K]; bias: float32[ncols] or None.  Returns float32 (..., ncols).
+    Inference only: with autograd recording a tensor that needs a gradient it raises instead of returning a result without one."""
+    _require_cuda(x, "x", torch.float32)
+    _require_cuda(labels, "labels")
+    _require_cuda(centers, "centers", torch.float32)
+    if bias is not None:
+        _require_cuda(bias, "bias", torch.float32)
+    kdim, ncols = int(kdim), int(ncols)
+    if torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (x, centers, bias)):
+        raise RuntimeError("codebook_matmul is inference only: it computes no gradient (run it under torch.no_grad())")
+    devs = {t.device for t in (x, labels, centers, bias) if t is not None}
+    if len(devs) != 1:
+        raise ValueError("x, labels, centers and bias must be on one device")
+    if x.dim() < 1 or x.shape[-1] != kdim:
+        raise ValueError(f"x must have shape (..., {kdim}), got {tuple(x.shape)}")
+    if labels.numel() != kdim * ncols:
+        raise ValueError(f"labels must hold kdim * ncols = {kdim * ncols} indices, got {labels.numel()}")
+    if bias is not None and bias.numel() != ncols:
+        raise ValueError(f"bias must hold ncols = {ncols} values, got {bias.numel()}")
+    L = nat.load()
+    lead = tuple(x.shape[:-1])
+    m = int(np.prod(lead)) if lead else 1
+    y = torch.empty(lead + (ncols,), dtype=torch.float32, device=x.device)
+    lb = _label_bytes(labels)
+    ws_bytes = int(L.nnc_cbmm_workspace_bytes(m, kdim, ncols, lb))
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=x.device) if ws_bytes else None
+    nat.check(L.nnc_cbmm_f32(_ptr(x), m, kdim, _ptr(labels), lb, ncols, _ptr(centers), centers.numel(), _ptr(bias), 1 if relu else 0,
+                             _ptr(y), _ptr(ws), ws_bytes, _stream(x)))
+    return y
+
+
 def huffman_lengths(counts) -> tuple:
     """Host: (lengths uint8[k], hist int64[max_len+1], total_bits) from an index histogram."""
     L = nat.load()

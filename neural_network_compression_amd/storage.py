@@ -255,16 +255,15 @@ def save_compressed(path: str, tensors: Dict[str, Tuple[tuple, object, torch.Ten
     return len(blob)
 
 
-def load_compressed(path: str, device=None) -> Dict[str, torch.Tensor]:
-    """name -> decoded float32 tensor on the device: cluster_centers_[labels_] in the stored shape."""
-    device = torch.device("cuda", torch.cuda.current_device()) if device is None else device
+def _records(path: str, device):
+    """(name, shape, value) per stored tensor: value = the raw float32 device tensor (K = 0) or (centers float32[K] host array,
+    indices device tensor) decoded by the device decoders."""
     with open(path, "rb") as f:
         blob = f.read()
     if blob[:4] != MAGIC:
         raise ValueError("not an NNC2 file")
     (nt,) = struct.unpack_from("<I", blob, 4)
     pos = 8
-    out = {}
     for _ in range(nt):
         (ln,) = struct.unpack_from("<H", blob, pos); pos += 2
         name = blob[pos: pos + ln].decode("utf-8"); pos += ln
@@ -273,9 +272,37 @@ def load_compressed(path: str, device=None) -> Dict[str, torch.Tensor]:
         k, lb, n, total_bits = struct.unpack_from("<IBQQ", blob, pos); pos += 21
         if k == 0:
             data = np.frombuffer(blob, dtype=np.float32, count=n, offset=pos); pos += 4 * n
-            out[name] = torch.from_numpy(data.copy()).to(device).reshape(shape)
+            yield name, shape, torch.from_numpy(data.copy()).to(device).reshape(shape)
             continue
         centers = np.frombuffer(blob, dtype=np.float32, count=k, offset=pos); pos += 4 * k
         labels, pos = unpack_indices(blob, pos, k, n, lb, device)
-        out[name] = ops.gather(torch.from_numpy(centers.copy()).to(device), labels).reshape(shape)
+        yield name, shape, (centers, labels)
+
+
+def _device(device):
+    return torch.device("cuda", torch.cuda.current_device()) if device is None else device
+
+
+def load_compressed(path: str, device=None) -> Dict[str, torch.Tensor]:
+    """name -> decoded float32 tensor on the device: cluster_centers_[labels_] in the stored shape."""
+    device = _device(device)
+    out = {}
+    for name, shape, value in _records(path, device):
+        if isinstance(value, tuple):
+            centers, labels = value
+            value = ops.gather(torch.from_numpy(centers.copy()).to(device), labels).reshape(shape)
+        out[name] = value
+    return out
+
+
+def load_compressed_codes(path: str, device=None) -> Dict[str, object]:
+    """name -> (shape, centers float32[K] on the device, centroid indices uint8 / 16-bit on the device) without decoding the
+    weights (what compressed.load_network runs from), or the raw float32 tensor of a record stored unquantized (K = 0)."""
+    device = _device(device)
+    out = {}
+    for name, shape, value in _records(path, device):
+        if isinstance(value, tuple):
+            centers, labels = value
+            value = (tuple(int(d) for d in shape), torch.from_numpy(centers.copy()).to(device), labels)
+        out[name] = value
     return out

@@ -1,0 +1,334 @@
+"""The quantized layers run from codebook + indices on the GPU (ops.codebook_matmul, compressed.py; run with -m gpu):
+exact on exact data, within the float32 bound on fitted data, deterministic, no float32 weight matrix, and the LeNets through
+the Trainer and through the stored form."""
+import numpy as np
+import pytest
+
+pytestmark = pytest.mark.gpu
+
+torch = pytest.importorskip("torch")
+
+from neural_network_compression_amd import synth  # noqa: E402
+
+
+@pytest.fixture(scope="module")
+def mods():
+    assert torch.cuda.is_available()
+    from neural_network_compression_amd import _native, compressed, ops, pipeline, storage
+
+    _native.load()
+    return ops, compressed, pipeline, storage
+
+
+def _labels_dev(lab: np.ndarray, k: int, offset: bool) -> torch.Tensor:
+    dt = np.uint8 if k <= 256 else np.int16
+    host = lab.astype(np.uint16).view(np.int16) if dt is np.int16 else lab.astype(np.uint8)
+    if not offset:
+        return torch.from_numpy(np.ascontiguousarray(host)).cuda()
+    buf = torch.empty(host.size + 1, dtype=torch.uint8 if dt is np.uint8 else torch.int16, device="cuda")
+    buf[1:] = torch.from_numpy(np.ascontiguousarray(host)).cuda()
+    v = buf[1:]
+    assert v.storage_offset() == 1
+    return v
+
+
+SHAPES = [(1, 1, 1), (2, 3, 10), (7, 100, 15), (16, 784, 300), (1, 5003, 4097), (17, 2450, 16), (64, 784, 256), (300, 100, 100),
+          (4099, 3, 4097), (16, 5003, 10), (2, 2450, 4097), (4099, 784, 15), (4, 784, 300), (8, 100, 4097), (1, 2450, 256)]
+KS = [1, 2, 17, 256, 257, 1040]
+
+
+@pytest.mark.parametrize("k", KS)
+@pytest.mark.parametrize("si", range(len(SHAPES)))
+def test_bit_exact_on_exact_data(mods, k, si):
+    """Integer x in [-8, 8], dyadic centres, integer bias: every partial sum is exact in float32 (|sum| * 4 < 2^24), so the
+    result equals the exact product whatever the summation order."""
+    ops = mods[0]
+    m, kdim, ncols = SHAPES[si]
+    rng = np.random.RandomState(1000 * si + k)
+    use_bias, relu, offset = si % 2 == 0, (si // 2) % 2 == 0, (si + k) % 3 != 1
+    x = rng.randint(-8, 9, size=(m, kdim)).astype(np.float32)
+    cen = (rng.randint(-16, 17, size=k) / 4.0).astype(np.float32)
+    lab = rng.randint(0, k, size=kdim * ncols)
+    bias = rng.randint(-50, 51, size=ncols).astype(np.float32) if use_bias else None
+    y = ops.codebook_matmul(torch.from_numpy(x).cuda(), _labels_dev(lab, k, offset), torch.from_numpy(cen).cuda(), kdim, ncols,
+                            bias=None if bias is None else torch.from_numpy(bias).cuda(), relu=relu).cpu().numpy()
+    want = x.astype(np.float64) @ cen[lab].astype(np.float64).reshape(kdim, ncols)
+    if bias is not None:
+        want += bias
+    if relu:
+        want = np.maximum(want, 0)
+    assert y.shape == (m, ncols)
+    assert np.array_equal(y, want.astype(np.float32))
+
+
+def test_out_of_range_indices_read_zero_as_the_gather_does(mods):
+    ops = mods[0]
+    rng = np.random.RandomState(5)
+    for m, k, lb_k in ((3, 17, 17), (40, 17, 17), (2, 300, 300)):
+        kdim, ncols = 300, 77
+        x = rng.randint(-8, 9, size=(m, kdim)).astype(np.float32)
+        cen = rng.randint(-16, 17, size=k).astype(np.float32)
+        hi = 256 if lb_k <= 256 else 2000
+        lab_t = _labels_dev(rng.randint(0, hi, size=kdim * ncols), 1040 if hi > 256 else 256, False)
+        cen_t = torch.from_numpy(cen).cuda()
+        y = ops.codebook_matmul(torch.from_numpy(x).cuda(), lab_t, cen_t, kdim, ncols).cpu().numpy()
+        w = ops.gather(cen_t, lab_t).cpu().numpy().astype(np.float64).reshape(kdim, ncols)
+        assert np.array_equal(y, (x.astype(np.float64) @ w).astype(np.float32))
+
+
+def test_edge_sizes(mods):
+    ops = mods[0]
+    cen = torch.arange(4, dtype=torch.float32, device="cuda")
+    bias = torch.tensor([1.0, -2.0, 3.0], device="cuda")
+    y = ops.codebook_matmul(torch.empty(5, 0, device="cuda"), torch.empty(0, dtype=torch.uint8, device="cuda"), cen, 0, 3, bias=bias)
+    assert torch.equal(y, bias.expand(5, 3))
+    y = ops.codebook_matmul(torch.empty(5, 0, device="cuda"), torch.empty(0, dtype=torch.uint8, device="cuda"), cen, 0, 3)
+    assert torch.equal(y, torch.zeros(5, 3, device="cuda"))
+    assert ops.codebook_matmul(torch.empty(0, 7, device="cuda"), torch.zeros(21, dtype=torch.uint8, device="cuda"), cen, 7, 3).shape == (0, 3)
+    assert ops.codebook_matmul(torch.ones(4, 7, device="cuda"), torch.zeros(0, dtype=torch.uint8, device="cuda"), cen, 7, 0).shape == (4, 0)
+    # leading dimensions
+    x = torch.randint(-8, 9, (2, 3, 7), device="cuda").float()
+    lab = torch.randint(0, 4, (21,), device="cuda").to(torch.uint8)
+    y = ops.codebook_matmul(x, lab, cen, 7, 3)
+    assert y.shape == (2, 3, 3) and torch.equal(y, x @ cen[lab.long()].view(7, 3))
+
+
+def test_inference_only(mods):
+    ops, compressed = mods[0], mods[1]
+    x = torch.ones(2, 4, device="cuda", requires_grad=True)
+    with pytest.raises(RuntimeError, match="inference only"):
+        ops.codebook_matmul(x, torch.zeros(8, dtype=torch.uint8, device="cuda"), torch.ones(1, device="cuda"), 4, 2)
+    with torch.no_grad():
+        assert torch.equal(ops.codebook_matmul(x, torch.zeros(8, dtype=torch.uint8, device="cuda"), torch.ones(1, device="cuda"), 4, 2),
+                           torch.full((2, 2), 4.0, device="cuda"))
+
+
+_FITS = {}
+
+
+def _fitted(pipeline, shape, bits, mode, seed):
+    key = (shape, bits, mode, seed)
+    if key not in _FITS:
+        w = torch.from_numpy(synth.weights(shape, seed)).cuda()
+        res = pipeline.compress_layer(w, q=1, bits=bits, mode=mode)
+        _FITS[key] = (res.model, shape)
+    return _FITS[key]
+
+
+def _check_bound(y, x, w, bias=None):
+    """|y - y64| <= 2 kdim 2^-24 (|x| @ |W| + |bias|) + 1e-30, elementwise."""
+    x64, w64 = x.astype(np.float64), w.astype(np.float64)
+    y64 = x64 @ w64
+    mag = np.abs(x64) @ np.abs(w64)
+    if bias is not None:
+        y64 = y64 + bias.astype(np.float64)
+        mag = mag + np.abs(bias.astype(np.float64))
+    kdim = x.shape[-1]
+    err = np.abs(y.astype(np.float64) - y64)
+    bound = 2.0 * kdim * 2.0 ** -24 * mag + 1e-30
+    assert np.all(err <= bound), float((err / bound).max())
+
+
+REAL = [((784, 300), 4, "linear"), ((300, 100), 4, "linear"), ((100, 10), 4, "linear"), ((2450, 256), 4, "linear"),
+        ((784, 300), 8, "density"), ((4096, 4096), 8, "linear"), ((5000, 5000), 8, "linear"), ((5000, 5000), 8, "density")]
+
+
+@pytest.mark.parametrize("shape,bits,mode", REAL)
+def test_fitted_weights_within_the_float32_bound_and_deterministic(mods, shape, bits, mode):
+    ops, _, pipeline, _ = mods
+    model, _ = _fitted(pipeline, shape, bits, mode, 4242 + shape[0])
+    kdim, ncols = shape
+    cen = torch.from_numpy(np.ascontiguousarray(model.cluster_centers_.ravel())).cuda()
+    lab = model.labels_compact_
+    assert (lab.dtype == torch.uint8) == (cen.numel() <= 256)
+    w = ops.gather(cen, lab).cpu().numpy().reshape(kdim, ncols)
+    rng = np.random.RandomState(kdim)
+    for m in (1, 16, 256):
+        x = rng.rand(m, kdim).astype(np.float32)
+        xt = torch.from_numpy(x).cuda()
+        y = ops.codebook_matmul(xt, lab, cen, kdim, ncols)
+        _check_bound(y.cpu().numpy(), x, w)
+        y2 = ops.codebook_matmul(xt, lab, cen, kdim, ncols)
+        assert torch.equal(y.view(torch.int32), y2.view(torch.int32))   # the same bits, twice
+
+
+@pytest.mark.parametrize("mode", ["linear", "density"])
+def test_no_float32_weight_matrix_is_materialized(mods, mode):
+    ops, _, pipeline, _ = mods
+    model, (kdim, ncols) = _fitted(pipeline, (5000, 5000), 8, mode, 4242 + 5000)
+    cen = torch.from_numpy(np.ascontiguousarray(model.cluster_centers_.ravel())).cuda()
+    for m in (1, 16):
+        x = torch.rand(m, kdim, device="cuda")
+        torch.cuda.synchronize()
+        torch.cuda.reset_peak_memory_stats()
+        base = torch.cuda.memory_allocated()
+        y = ops.codebook_matmul(x, model.labels_compact_, cen, kdim, ncols)
+        torch.cuda.synchronize()
+        grown = torch.cuda.max_memory_allocated() - base
+        assert grown < 2 * kdim * ncols, grown
+        del y
+
+
+# ------------------------------------------------------------------ the LeNets through the Trainer
+def _trainer(kind):
+    from neural_network_compression_amd.common import trainer as tr
+
+    tr.Trainer.pruned_indexes_by_layer.clear()
+    torch.manual_seed(0)
+    if kind == "lenet300":
+        from neural_network_compression_amd.le_net_300_100_trainer import LeNet300100Trainer
+
+        t = LeNet300100Trainer()
+        specs = synth.LENET_300_100
+    else:
+        from neural_network_compression_amd.le_net_5_trainer import LeNet5Trainer
+
+        t = LeNet5Trainer()
+        specs = synth.LENET_5
+    layers = [layer for layer in t.neural_network.get_config().values() if layer.get_weights()]
+    for li, ((_, wshape, bshape), layer) in enumerate(zip(specs, layers)):
+        assert tuple(layer.kernel.shape) == wshape
+        layer.set_weights([torch.from_numpy(synth.weights(wshape, 2000 + 2 * li)).cuda(), torch.from_numpy(synth.weights(bshape, 2001 + 2 * li)).cuda()])
+    return t
+
+
+def _inputs(kind, n, seed):
+    rng = np.random.RandomState(seed)
+    return rng.rand(n, 784).astype(np.float32) if kind == "lenet300" else rng.rand(n, 28, 28, 1).astype(np.float32)
+
+
+def _layer_checks(mods, t, cnet, x):
+    """Each compressed layer, fed what the decoded network feeds that layer, against a float64 product."""
+    _, compressed, _, _ = mods
+    seen = {}
+    hooks = [layer.register_forward_hook(lambda mod, inp, out, name=name: seen.__setitem__(name, inp[0].detach().clone()))
+             for name, layer in t.neural_network.get_config().items()]
+    with torch.no_grad():
+        t.neural_network(x)
+    for h in hooks:
+        h.remove()
+    checked = 0
+    for name, layer in cnet.get_config().items():
+        if not isinstance(layer, compressed._CodebookLayer):
+            continue
+        inp = seen[name]
+        with torch.no_grad():
+            y = layer(inp).cpu().numpy()
+        orig = t.neural_network.get_config()[name]
+        w_dec = orig.kernel.detach().cpu().numpy()
+        b = orig.bias.detach().cpu().numpy()
+        if isinstance(layer, compressed.CompressedConv2D):
+            ks = w_dec.shape[0]
+            rows = compressed.keras_rows_for_unfold(ks, ks, w_dec.shape[2])
+            p = compressed.conv_patches(inp.cpu().double(), ks, layer.pad).numpy()
+            xin, w = p.reshape(-1, p.shape[-1]), w_dec.reshape(-1, w_dec.shape[-1])[rows]
+            y = y.reshape(-1, y.shape[-1])
+        else:
+            xin, w = inp.cpu().numpy(), w_dec
+        if orig.activation is torch.relu:
+            x64, w64 = xin.astype(np.float64), w.astype(np.float64)
+            pre = x64 @ w64 + b
+            err = np.abs(y.astype(np.float64) - np.maximum(pre, 0))
+            bound = 2.0 * xin.shape[-1] * 2.0 ** -24 * (np.abs(x64) @ np.abs(w64) + np.abs(b)) + 1e-30
+            assert np.all(err <= bound), (name, float((err / bound).max()))
+        else:
+            _check_bound(y, xin, w, b)
+        checked += 1
+    assert checked >= 2
+    # end to end: the same argmax wherever the decoded logits' top-2 margin is not a rounding matter
+    with torch.no_grad():
+        ref = t.neural_network(x).cpu().numpy()
+        got = cnet(x).cpu().numpy()
+    top2 = np.sort(ref, axis=1)[:, -2:]
+    margin = top2[:, 1] - top2[:, 0]
+    clear = margin > 1e-4 * np.abs(ref).max()
+    assert clear.sum() > 0.5 * len(ref)
+    assert np.array_equal(ref.argmax(1)[clear], got.argmax(1)[clear])
+
+
+@pytest.mark.parametrize("kind", ["lenet300", "lenet5"])
+@pytest.mark.parametrize("bits,mode,cdf", [(4, "linear", False), (8, "density", True)])
+def test_lenets_through_the_trainer(mods, kind, bits, mode, cdf):
+    from neural_network_compression_amd.common import trainer as tr
+
+    t = _trainer(kind)
+    n = 2048 if kind == "lenet300" else 512
+    x = _inputs(kind, n, 7)
+    y = np.eye(10, dtype=np.float32)[np.random.RandomState(8).randint(0, 10, size=n)]
+    data = tr.LeNetDataset(x, y)
+    test = tr.LeNetDataset(x[:256], y[:256].argmax(1))
+    with pytest.raises(RuntimeError, match="quantize"):
+        t.compressed_network()
+    t._prune_parameters(True)
+    t.quantize(test, cdf, bits, mode)
+    want_k = 2 ** bits + (1 if mode == "density" else 0)
+    ks = [m.cluster_centers_.size for ms in t.quantized_models_by_layer.values() for m in ms if m is not None]
+    assert ks and all(k <= want_k for k in ks) and max(ks) == want_k
+    xt = torch.from_numpy(x[:256]).cuda()
+    cnet = t.compressed_network()
+    assert any(isinstance(l, mods[1]._CodebookLayer) for l in cnet.get_config().values())
+    _layer_checks(mods, t, cnet, xt)
+    # after centroid fine-tuning the compressed network carries the tuned centres
+    t.fine_tune_centroids(data, test, epochs=1)
+    cnet2 = t.compressed_network()
+    _layer_checks(mods, t, cnet2, xt)
+
+
+@pytest.mark.parametrize("kind", ["lenet300", "lenet5"])
+def test_round_trip_through_storage_is_bitwise(mods, kind, tmp_path):
+    _, compressed, _, storage = mods
+    from neural_network_compression_amd.common import trainer as tr
+
+    t = _trainer(kind)
+    x = _inputs(kind, 256, 9)
+    t._prune_parameters(True)
+    t.quantize(tr.LeNetDataset(x, np.zeros(256, dtype=np.int64)), False, 4, "linear")
+    xt = torch.from_numpy(x).cuda()
+    with torch.no_grad():
+        want = t.compressed_network()(xt)
+    t.store_report(str(tmp_path / "rep"))
+    with torch.no_grad():
+        got = compressed.load_network(str(tmp_path / "rep" / "weights.nnc"), t.neural_network)(xt)
+    assert torch.equal(got.view(torch.int32), want.view(torch.int32))
+    for form in ("dense", "sparse8"):
+        stored = {}
+        for name, layer in t.neural_network.get_config().items():
+            if layer not in t.quantized_models_by_layer:
+                continue
+            for kind_, tens, m in zip(("weights", "biases"), layer.get_weights(), t.quantized_models_by_layer[layer]):
+                stored[f"{name}.{kind_}"] = (tuple(tens.shape), m, tens if m is None else None)
+        path = str(tmp_path / f"{form}.nnc")
+        storage.save_compressed(path, stored, form=form)
+        codes = storage.load_compressed_codes(path)
+        dec = storage.load_compressed(path)
+        for nm, v in codes.items():
+            if isinstance(v, tuple):
+                assert torch.equal(mods[0].gather(v[1], v[2]).reshape(v[0]), dec[nm])
+            else:
+                assert torch.equal(v, dec[nm])
+        with torch.no_grad():
+            got = compressed.load_network(path, t.neural_network)(xt)
+        assert torch.equal(got.view(torch.int32), want.view(torch.int32)), form
+
+
+def test_footprint(mods):
+    _, compressed, _, _ = mods
+    from neural_network_compression_amd.common import trainer as tr
+
+    t = _trainer("lenet300")
+    x = _inputs("lenet300", 64, 3)
+    t._prune_parameters(True)
+    t.quantize(tr.LeNetDataset(x, np.zeros(64, dtype=np.int64)), False, 4, "linear")
+    cnet = t.compressed_network()
+    fp32 = 0
+    for name, layer in t.neural_network.get_config().items():
+        w, b = layer.get_weights()
+        fp32 += 4 * (w.numel() + b.numel())
+        wm = t.quantized_models_by_layer[layer][0]
+        c = cnet.get_config()[name]
+        assert isinstance(c, compressed.CompressedDense)
+        assert compressed.compressed_nbytes(c) == w.numel() * wm.labels_compact_.element_size() + 4 * wm.cluster_centers_.size + 4 * b.numel()
+    total = compressed.compressed_nbytes(cnet)
+    assert total == sum(compressed.compressed_nbytes(c) for c in cnet.get_config().values())
+    assert total <= 0.26 * fp32, (total, fp32)
+    assert compressed.compressed_nbytes(t.neural_network) == fp32
