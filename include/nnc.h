@@ -546,6 +546,35 @@ int nnc_gather_f32(const float *centers_dev, int32_t k, const void *labels, int 
  * Argument errors (NNC_EINVAL; NNC_ENOSPACE for a short workspace) are returned before any HIP call.
  * ---------------------------------------------------------------------------------- */
 int64_t nnc_cbmm_workspace_bytes(int64_t m, int64_t kdim, int64_t ncols, int label_bytes);
+/* The plan nnc_cbmm_f32 follows for these arguments on a device with `cus` compute units and labels at `labels_addr` (only its
+ * alignment matters): host arithmetic only, no HIP call.  Writes NNC_CBMM_PLAN_LEN values to out[], indexed by NNC_CBMM_P_*:
+ *   PATH       NNC_CBMM_NONE (m or ncols = 0: nothing is written), _STREAM (k_cbmm_stream), _TILED (k_cbmm_tiled), _BIAS (kdim = 0)
+ *   VB, MT     stream: label bytes per lane per row, rows of x per launch (0 otherwise)
+ *   COPIES     copies of the codebook in LDS, ENTRIES its entries (centres, then zeros; 0 for NONE / BIAS)
+ *   SPLITS     K splits (1: the main kernel writes y; more: partials + k_cbmm_reduce), RPS rows of K per split
+ *   ALIGNED    stream: 1 if every label row starts on a VB-byte boundary (no funnel shift)
+ *   LDS        dynamic LDS bytes of the main kernel
+ *   COL_TILES, ROW_TILES   the main kernel's tiles (grid = COL_TILES * ROW_TILES x SPLITS)
+ *   WORKSPACE  workspace bytes the call uses on this device (<= nnc_cbmm_workspace_bytes, which plans for 256 CUs)
+ * NNC_EINVAL for the argument errors nnc_cbmm_f32 reports, cus < 1, out NULL, or a plan with no kernel instantiation. */
+#define NNC_CBMM_NONE 0
+#define NNC_CBMM_STREAM 1
+#define NNC_CBMM_TILED 2
+#define NNC_CBMM_BIAS 3
+#define NNC_CBMM_P_PATH 0
+#define NNC_CBMM_P_VB 1
+#define NNC_CBMM_P_MT 2
+#define NNC_CBMM_P_COPIES 3
+#define NNC_CBMM_P_ENTRIES 4
+#define NNC_CBMM_P_SPLITS 5
+#define NNC_CBMM_P_RPS 6
+#define NNC_CBMM_P_ALIGNED 7
+#define NNC_CBMM_P_LDS 8
+#define NNC_CBMM_P_COL_TILES 9
+#define NNC_CBMM_P_ROW_TILES 10
+#define NNC_CBMM_P_WORKSPACE 11
+#define NNC_CBMM_PLAN_LEN 12
+int nnc_cbmm_plan(int64_t m, int64_t kdim, int64_t ncols, int label_bytes, int32_t k, int32_t cus, uint64_t labels_addr, int64_t *out);
 int nnc_cbmm_f32(const float *x, int64_t m, int64_t kdim, const void *labels, int label_bytes, int64_t ncols, const float *centers_dev, int32_t k,
                  const float *bias_dev, int32_t relu, float *y, void *workspace, int64_t workspace_bytes, void *stream);
 

@@ -25,6 +25,9 @@ NNC_KM_TWO_LAUNCH = 1   # nnc_kmeans_params.flags: iterate launch by launch (inc
 NNC_KM_LOOP = 2         # ... inside one resident workgroup whatever K
 NNC_KM_MASS_IN_PLACE = 4  # ... nnc_kmeans_fit: mass empty-cluster events settled by the finalize step (experiment; include/nnc.h)
 NNC_KM_LOOP_KMAX = 64  # up to here the library takes the loop by itself
+CBMM_NONE, CBMM_STREAM, CBMM_TILED, CBMM_BIAS = 0, 1, 2, 3   # nnc_cbmm_plan: the path a call takes (include/nnc.h)
+CBMM_PLAN_LEN = 12
+CBMM_PLAN_FIELDS = ("path", "vb", "mt", "copies", "entries", "splits", "rps", "aligned", "lds", "col_tiles", "row_tiles", "workspace")
 
 
 class NativeLibraryError(RuntimeError):
@@ -149,6 +152,7 @@ SIGNATURES = {
     "nnc_centroid_grad_f32": (c_int, [c_void_p, c_void_p, c_int, c_i64, c_i32, c_i32, c_void_p, c_void_p, c_void_p]),
     "nnc_gather_f32": (c_int, [c_void_p, c_i32, c_void_p, c_int, c_i64, c_void_p, c_void_p]),
     "nnc_cbmm_workspace_bytes": (c_i64, [c_i64, c_i64, c_i64, c_int]),
+    "nnc_cbmm_plan": (c_int, [c_i64, c_i64, c_i64, c_int, c_i32, c_i32, ctypes.c_uint64, ctypes.POINTER(c_i64)]),
     "nnc_cbmm_f32": (c_int, [c_void_p, c_i64, c_i64, c_void_p, c_int, c_i64, c_void_p, c_i32, c_void_p, c_i32, c_void_p, c_void_p, c_i64, c_void_p]),
     "nnc_huffman_codes": (c_int, [ctypes.POINTER(ctypes.c_uint8), c_i32, ctypes.POINTER(ctypes.c_uint32)]),
     "nnc_codec_chunks": (c_size, [c_i64]),

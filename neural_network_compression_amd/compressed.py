@@ -127,6 +127,8 @@ class CompressedConv2D(_CodebookLayer):
         ho, wo = hh + 2 * self.pad - self.kernel_size + 1, ww + 2 * self.pad - self.kernel_size + 1
         per = max(1, _PATCH_BYTES // max(1, ho * wo * self.kdim * 4))
         outs = [self._matmul(conv_patches(x[i: i + per], self.kernel_size, self.pad).contiguous()) for i in range(0, n, per)]
+        if not outs:   # an empty batch: the (0, kdim) product, as F.conv2d gives an empty result
+            outs = [self._matmul(x.new_empty((0, self.kdim)))]
         y = outs[0] if len(outs) == 1 else torch.cat(outs)
         return y.reshape(n, ho, wo, self.ncols)
 

@@ -30,22 +30,27 @@
 #define TB_K 8
 
 // ------------------------------------------------------------------ the plan (host)
+// Every decision nnc_cbmm_f32 takes before it launches: which kernel, its instantiation, the LDS table, the grid and the K
+// splits.  nnc_cbmm_plan reports it (include/nnc.h), so the tests can see which regime a call hits.
 struct CbPlan {
-    int skinny;
-    int vb, mt;              // skinny: bytes per lane per row, rows of x per launch (a power of two >= m)
+    int path;                // NNC_CBMM_NONE / _STREAM / _TILED / _BIAS
+    int vb, mt;              // stream: bytes per lane per row, rows of x per launch (a power of two >= m)
+    int entries, cshift;     // the LDS codebook: entries (centres, then zeros) x (1 << cshift) copies
+    int aligned;             // stream: every label row starts on a VB-byte boundary (no funnel shift)
     long long col_tiles, row_tiles;
     long long splits, rows_per_split;
+    long long lds;           // dynamic LDS bytes of the main kernel
 };
 
 static long long cdiv(long long a, long long b) { return (a + b - 1) / b; }
 
-static CbPlan cb_plan(long long m, long long kdim, long long ncols, int lb, int cus)
+// the splits and tiles (m >= 1, kdim >= 1, ncols >= 1)
+static void cb_grid(CbPlan &p, long long m, long long kdim, long long ncols, int lb, int cus)
 {
-    CbPlan p{};
     cus = std::max(1, std::min(cus, CB_PLAN_CUS));
     long long s;
     if (m <= CB_SKINNY_M) {
-        p.skinny = 1;
+        p.path = NNC_CBMM_STREAM;
         p.mt = m <= 1 ? 1 : (m <= 2 ? 2 : (m <= 4 ? 4 : (m <= 8 ? 8 : 16)));
         const int e_max = 64 / p.mt;                                 // accumulators per lane <= 64
         p.vb = std::min(16, e_max * lb);
@@ -55,13 +60,39 @@ static CbPlan cb_plan(long long m, long long kdim, long long ncols, int lb, int 
         // stay within a quarter of the index stream
         s = std::min({cdiv(2LL * cus, p.col_tiles), kdim / (CB_WAVES * CB_UNROLL), kdim * lb / (16 * m)});
     } else {
+        p.path = NNC_CBMM_TILED;
         p.col_tiles = cdiv(ncols, TB_N);
         p.row_tiles = cdiv(m, TB_M);
         s = std::min({cdiv(2LL * cus, p.col_tiles * p.row_tiles), kdim / (16 * TB_K), 16LL});
     }
     s = std::max(1LL, s);
-    p.rows_per_split = std::max(1LL, cdiv(kdim, s));
-    p.splits = kdim > 0 ? cdiv(kdim, p.rows_per_split) : 0;
+    p.rows_per_split = cdiv(kdim, s);
+    p.splits = cdiv(kdim, p.rows_per_split);
+}
+
+static CbPlan cb_plan(long long m, long long kdim, long long ncols, int lb, int k, int cus, uintptr_t labels)
+{
+    CbPlan p{};
+    if (m == 0 || ncols == 0) return p;                              // NNC_CBMM_NONE: nothing to write
+    if (kdim == 0) {                                                 // y = bias (zeros without one), by k_cbmm_reduce
+        p.path = NNC_CBMM_BIAS;
+        return p;
+    }
+    cb_grid(p, m, kdim, ncols, lb, cus);
+    if (p.path == NNC_CBMM_STREAM) {
+        if (lb == 1) {
+            p.entries = 256;
+            p.cshift = __builtin_ctz(CB_U8_COPIES);
+        } else {
+            p.entries = k + 1;
+            while ((1 << p.cshift) < CB_U8_COPIES && (long long)p.entries << (p.cshift + 1) <= CB_U16_WORDS) ++p.cshift;
+        }
+        p.aligned = labels % p.vb == 0 && (ncols * lb) % p.vb == 0;
+        p.lds = ((long long)p.entries << p.cshift) * 4 + (long long)p.mt * (p.vb / lb) * 64 * 4 + (long long)p.entries * 4;
+    } else {
+        p.entries = k + 1;
+        p.lds = (long long)(TB_K * TB_M + TB_K * TB_N + k + 1) * 4;
+    }
     return p;
 }
 
@@ -245,7 +276,7 @@ __global__ __launch_bounds__(CB_THREADS) void k_cbmm_stream(const float *__restr
             float v = acc[r][e];
             if (direct) {
                 if (bias) v += bias[c];
-                if (relu) v = v > 0.0f ? v : 0.0f;
+                if (relu) v = v < 0.0f ? 0.0f : v;   // NaN stays NaN, as torch.relu
                 out[(long long)r * ncols + c] = v;
             } else {
                 out[((long long)blockIdx.y * m + r) * ncols + c] = v;
@@ -322,7 +353,7 @@ __global__ __launch_bounds__(256) void k_cbmm_tiled(const float *__restrict__ x,
             float v = acc[a][b];
             if (direct) {
                 if (bias) v += bias[c];
-                if (relu) v = v > 0.0f ? v : 0.0f;
+                if (relu) v = v < 0.0f ? 0.0f : v;   // NaN stays NaN, as torch.relu
                 out[r * ncols + c] = v;
             } else {
                 out[((long long)blockIdx.y * m + r) * ncols + c] = v;
@@ -356,7 +387,7 @@ __global__ __launch_bounds__(256) void k_cbmm_reduce(const float *__restrict__ p
 #pragma unroll
             for (int j = 0; j < RED_Q - 1; ++j) v += qs[j][o];
             if (bias) v += bias[idx % ncols];
-            if (relu) v = v > 0.0f ? v : 0.0f;
+            if (relu) v = v < 0.0f ? 0.0f : v;   // NaN stays NaN, as torch.relu
             y[idx] = v;
         }
     }
@@ -376,7 +407,7 @@ static int cb_check(int64_t m, int64_t kdim, int64_t ncols, int label_bytes, int
 extern "C" int64_t nnc_cbmm_workspace_bytes(int64_t m, int64_t kdim, int64_t ncols, int label_bytes)
 {
     if (m <= 0 || kdim <= 0 || ncols <= 0 || (label_bytes != 1 && label_bytes != 2) || cb_check(m, kdim, ncols, label_bytes, 1) != NNC_OK) return 0;
-    return cb_ws_bytes(cb_plan(m, kdim, ncols, label_bytes, CB_PLAN_CUS), m, ncols);
+    return cb_ws_bytes(cb_plan(m, kdim, ncols, label_bytes, 1, CB_PLAN_CUS, 0), m, ncols);
 }
 
 template <typename LT, int VB, int MT>
@@ -390,19 +421,54 @@ static void launch_stream(bool aligned, dim3 grid, size_t lds, hipStream_t s, co
         hipLaunchKernelGGL((k_cbmm_stream<LT, VB, MT, false>), grid, dim3(CB_THREADS), lds, s, x, m, kdim, lab, ncols, centers, k, entries, cshift, rps, bias, relu, direct, out);
 }
 
-template <typename LT>
-static void dispatch_stream(int vb, int mt, bool aligned, dim3 grid, size_t lds, hipStream_t s, const float *x, int m, long long kdim, const void *labels,
-                            long long ncols, const float *centers, int k, int entries, int cshift, long long rps, const float *bias, int relu, int direct, float *out)
+// every k_cbmm_stream instantiation there is; the plan is checked against this table, and the launch goes through it
+using StreamLaunch = void (*)(bool, dim3, size_t, hipStream_t, const float *, int, long long, const void *, long long, const float *, int, int, int,
+                              long long, const float *, int, int, float *);
+struct StreamCase {
+    int lb, vb, mt;
+    StreamLaunch fn;
+};
+static const StreamCase kStreamCases[] = {
+    {1, 16, 1, launch_stream<uint8_t, 16, 1>},  {1, 16, 2, launch_stream<uint8_t, 16, 2>},  {1, 16, 4, launch_stream<uint8_t, 16, 4>},
+    {1, 8, 8, launch_stream<uint8_t, 8, 8>},    {1, 4, 16, launch_stream<uint8_t, 4, 16>},
+    {2, 16, 1, launch_stream<uint16_t, 16, 1>}, {2, 16, 2, launch_stream<uint16_t, 16, 2>}, {2, 16, 4, launch_stream<uint16_t, 16, 4>},
+    {2, 16, 8, launch_stream<uint16_t, 16, 8>}, {2, 8, 16, launch_stream<uint16_t, 8, 16>},
+};
+
+static StreamLaunch find_stream(int lb, int vb, int mt)
 {
-#define CB_CASE(VB_, MT_)                                                                                                                  \
-    if (vb == VB_ && mt == MT_) {                                                                                                          \
-        launch_stream<LT, VB_, MT_>(aligned, grid, lds, s, x, m, kdim, labels, ncols, centers, k, entries, cshift, rps, bias, relu, direct, out); \
-        return;                                                                                                                            \
-    }
-    CB_CASE(16, 1) CB_CASE(16, 2) CB_CASE(16, 4)
-    if constexpr (sizeof(LT) == 1) { CB_CASE(8, 8) CB_CASE(4, 16) }
-    else { CB_CASE(16, 8) CB_CASE(8, 16) }
-#undef CB_CASE
+    for (const StreamCase &c : kStreamCases)
+        if (c.lb == lb && c.vb == vb && c.mt == mt) return c.fn;
+    return nullptr;
+}
+
+static int no_stream_case(int lb, int vb, int mt)
+{
+    return fail(NNC_EINVAL, "nnc_cbmm: no k_cbmm_stream instantiation for label_bytes " + std::to_string(lb) + ", vb " + std::to_string(vb) +
+                                ", mt " + std::to_string(mt));
+}
+
+static int dispatch_stream(const CbPlan &p, int lb, dim3 grid, hipStream_t s, const float *x, int m, long long kdim, const void *labels, long long ncols,
+                           const float *centers, int k, const float *bias, int relu, int direct, float *out)
+{
+    const StreamLaunch fn = find_stream(lb, p.vb, p.mt);
+    if (!fn) return no_stream_case(lb, p.vb, p.mt);
+    fn(p.aligned != 0, grid, (size_t)p.lds, s, x, m, kdim, labels, ncols, centers, k, p.entries, p.cshift, p.rows_per_split, bias, relu, direct, out);
+    return NNC_OK;
+}
+
+extern "C" int nnc_cbmm_plan(int64_t m, int64_t kdim, int64_t ncols, int label_bytes, int32_t k, int32_t cus, uint64_t labels_addr, int64_t *out)
+{
+    const int rc = cb_check(m, kdim, ncols, label_bytes, k);
+    if (rc != NNC_OK) return rc;
+    if (cus < 1) return nnc_set_error_(NNC_EINVAL, "nnc_cbmm_plan: cus < 1");
+    if (!out) return nnc_set_error_(NNC_EINVAL, "nnc_cbmm_plan: out is NULL");
+    const CbPlan p = cb_plan(m, kdim, ncols, label_bytes, k, cus, (uintptr_t)labels_addr);
+    if (p.path == NNC_CBMM_STREAM && !find_stream(label_bytes, p.vb, p.mt)) return no_stream_case(label_bytes, p.vb, p.mt);
+    const int64_t v[NNC_CBMM_PLAN_LEN] = {p.path, p.vb, p.mt, p.path == NNC_CBMM_STREAM ? 1LL << p.cshift : (p.entries ? 1 : 0), p.entries,
+                                          p.splits, p.rows_per_split, p.aligned, p.lds, p.col_tiles, p.row_tiles, cb_ws_bytes(p, m, ncols)};
+    for (int i = 0; i < NNC_CBMM_PLAN_LEN; ++i) out[i] = v[i];
+    return NNC_OK;
 }
 
 extern "C" int nnc_cbmm_f32(const float *x, int64_t m, int64_t kdim, const void *labels, int label_bytes, int64_t ncols, const float *centers_dev,
@@ -422,43 +488,26 @@ extern "C" int nnc_cbmm_f32(const float *x, int64_t m, int64_t kdim, const void 
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     const long long mn = m * ncols;
     const int rgrid = (int)std::max(1LL, std::min(cdiv(mn, 64), 8192LL));
-    if (kdim == 0) {   // y = bias (zeros without one)
+    const CbPlan p = cb_plan(m, kdim, ncols, label_bytes, k, cu_count(), reinterpret_cast<uintptr_t>(labels));
+    if (p.path == NNC_CBMM_BIAS) {   // kdim = 0: y = bias (zeros without one)
         hipLaunchKernelGGL(k_cbmm_reduce, dim3(rgrid), dim3(256), 0, s, (const float *)nullptr, 0LL, mn, (long long)ncols, bias_dev, (int)relu, y);
         LAUNCHCHK("k_cbmm_reduce");
         return NNC_OK;
     }
-    const CbPlan p = cb_plan(m, kdim, ncols, label_bytes, cu_count());
     const int direct = p.splits == 1;
     float *out = direct ? y : reinterpret_cast<float *>(workspace);
-    if (p.skinny) {
-        int entries, cshift;
-        if (label_bytes == 1) {
-            entries = 256;
-            cshift = __builtin_ctz(CB_U8_COPIES);
-        } else {
-            entries = k + 1;
-            cshift = 0;
-            while ((1 << cshift) < CB_U8_COPIES && (long long)entries << (cshift + 1) <= CB_U16_WORDS) ++cshift;
-        }
-        const int e = p.vb / label_bytes;
-        const size_t lds = ((size_t)entries << cshift) * 4 + (size_t)p.mt * e * 64 * 4 + (size_t)entries * 4;
-        const bool aligned = (reinterpret_cast<uintptr_t>(labels) % p.vb) == 0 && (ncols * label_bytes) % p.vb == 0;
+    if (p.path == NNC_CBMM_STREAM) {
         const dim3 grid((unsigned)p.col_tiles, (unsigned)p.splits);
-        if (label_bytes == 1)
-            dispatch_stream<uint8_t>(p.vb, p.mt, aligned, grid, lds, s, x, (int)m, kdim, labels, ncols, centers_dev, k, entries, cshift, p.rows_per_split,
-                                     bias_dev, relu, direct, out);
-        else
-            dispatch_stream<uint16_t>(p.vb, p.mt, aligned, grid, lds, s, x, (int)m, kdim, labels, ncols, centers_dev, k, entries, cshift, p.rows_per_split,
-                                      bias_dev, relu, direct, out);
+        rc = dispatch_stream(p, label_bytes, grid, s, x, (int)m, kdim, labels, ncols, centers_dev, k, bias_dev, relu, direct, out);
+        if (rc != NNC_OK) return rc;
         LAUNCHCHK("k_cbmm_stream");
     } else {
-        const size_t lds = (size_t)(TB_K * TB_M + TB_K * TB_N + k + 1) * 4;
         const dim3 grid((unsigned)(p.col_tiles * p.row_tiles), (unsigned)p.splits);
         if (label_bytes == 1)
-            hipLaunchKernelGGL(k_cbmm_tiled<uint8_t>, grid, dim3(256), lds, s, x, (long long)m, (long long)kdim, reinterpret_cast<const uint8_t *>(labels),
+            hipLaunchKernelGGL(k_cbmm_tiled<uint8_t>, grid, dim3(256), (size_t)p.lds, s, x, (long long)m, (long long)kdim, reinterpret_cast<const uint8_t *>(labels),
                                (long long)ncols, centers_dev, (int)k, p.col_tiles, p.rows_per_split, bias_dev, (int)relu, direct, out);
         else
-            hipLaunchKernelGGL(k_cbmm_tiled<uint16_t>, grid, dim3(256), lds, s, x, (long long)m, (long long)kdim, reinterpret_cast<const uint16_t *>(labels),
+            hipLaunchKernelGGL(k_cbmm_tiled<uint16_t>, grid, dim3(256), (size_t)p.lds, s, x, (long long)m, (long long)kdim, reinterpret_cast<const uint16_t *>(labels),
                                (long long)ncols, centers_dev, (int)k, p.col_tiles, p.rows_per_split, bias_dev, (int)relu, direct, out);
         LAUNCHCHK("k_cbmm_tiled");
     }

@@ -320,6 +320,15 @@ def codebook_matmul(x: torch.Tensor, labels: torch.Tensor, centers: torch.Tensor
     return y
 
 
+def cbmm_plan(m: int, kdim: int, ncols: int, label_bytes: int, k: int, cus: int, labels_addr: int = 0) -> dict:
+    """Host: the plan nnc_cbmm_f32 follows for this call on a device with ``cus`` compute units (include/nnc.h, nnc_cbmm_plan),
+    as a dict keyed by _native.CBMM_PLAN_FIELDS.  No device needed."""
+    L = nat.load()
+    out = (ctypes.c_int64 * nat.CBMM_PLAN_LEN)()
+    nat.check(L.nnc_cbmm_plan(int(m), int(kdim), int(ncols), int(label_bytes), int(k), int(cus), int(labels_addr), out))
+    return dict(zip(nat.CBMM_PLAN_FIELDS, (int(v) for v in out)))
+
+
 def huffman_lengths(counts) -> tuple:
     """Host: (lengths uint8[k], hist int64[max_len+1], total_bits) from an index histogram."""
     L = nat.load()

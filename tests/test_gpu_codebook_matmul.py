@@ -1,6 +1,8 @@
 """The quantized layers run from codebook + indices on the GPU (ops.codebook_matmul, compressed.py; run with -m gpu):
 exact on exact data, within the float32 bound on fitted data, deterministic, no float32 weight matrix, and the LeNets through
 the Trainer and through the stored form."""
+from types import SimpleNamespace
+
 import numpy as np
 import pytest
 
@@ -9,6 +11,7 @@ pytestmark = pytest.mark.gpu
 torch = pytest.importorskip("torch")
 
 from neural_network_compression_amd import synth  # noqa: E402
+from tests.helpers.cbmm_ref import assert_exact, conv_nhwc, exact_grid_bits  # noqa: E402
 
 
 @pytest.fixture(scope="module")
@@ -332,3 +335,160 @@ def test_footprint(mods):
     assert total == sum(compressed.compressed_nbytes(c) for c in cnet.get_config().values())
     assert total <= 0.26 * fp32, (total, fp32)
     assert compressed.compressed_nbytes(t.neural_network) == fp32
+
+
+# ------------------------------------------------------------------ CompressedConv2D against a float64 convolution
+def _exact_conv_layer(compressed, ks, cin, cout, pad, act, rng, k=17):
+    """A CompressedConv2D from random codes on exact data (quarter-integer centres, integer bias) and its decoded kernel."""
+    cen = (rng.randint(-16, 17, size=k) / 4.0).astype(np.float32)
+    lab = rng.randint(0, k, size=ks * ks * cin * cout)
+    bias = rng.randint(-50, 51, size=cout).astype(np.float32)
+    layer = compressed.CompressedConv2D.from_codes(ks, cin, cout, pad, torch.from_numpy(lab.astype(np.uint8)).cuda(), torch.from_numpy(cen).cuda(),
+                                                   torch.from_numpy(bias).cuda(), act)
+    return layer, cen[lab].reshape(ks, ks, cin, cout), bias
+
+
+def _conv_ref(x, kernel, bias, pad, act):
+    """float64 convolution + bias (+ ReLU), after asserting every float32 partial sum of it is exact."""
+    mag = conv_nhwc(np.abs(x), np.abs(kernel), pad) + np.abs(bias)
+    g = max(exact_grid_bits(x) + exact_grid_bits(kernel), exact_grid_bits(bias))
+    assert mag.max(initial=0.0) * 2.0 ** g < 2.0 ** 24
+    out = conv_nhwc(x, kernel, pad) + bias
+    return np.maximum(out, 0) if act is torch.relu else out
+
+
+@pytest.mark.parametrize("ks", [1, 3, 5])
+@pytest.mark.parametrize("padding", ["valid", "same"])
+@pytest.mark.parametrize("cin", [1, 3, 20])
+def test_conv2d_bit_exact_against_a_float64_convolution(mods, ks, padding, cin):
+    """H != W; N * Ho * Wo <= 16 (the stream kernel) and > 16 (the tiled one); cout 1, 16, 50; with and without the fused ReLU."""
+    ops, compressed = mods[0], mods[1]
+    _, cus = ops.device_info()
+    pad = ks // 2 if padding == "same" else 0
+    rng = np.random.RandomState(ks * 100 + cin * 3 + pad)
+    for cout in (1, 16, 50):
+        for n, (ho, wo), path in ((2, (2, 3), 1), (3, (5, 4), 2)):
+            hh, ww = ho + ks - 1 - 2 * pad, wo + ks - 1 - 2 * pad
+            assert hh != ww
+            act = torch.relu if cout != 16 else None
+            layer, kernel, bias = _exact_conv_layer(compressed, ks, cin, cout, pad, act, rng)
+            assert ops.cbmm_plan(n * ho * wo, ks * ks * cin, cout, 1, 17, cus)["path"] == path
+            x = rng.randint(-8, 9, size=(n, hh, ww, cin)).astype(np.float32)
+            with torch.no_grad():
+                got = layer(torch.from_numpy(x).cuda()).cpu().numpy()
+            want = _conv_ref(x, kernel, bias, pad, act)
+            assert got.shape == (n, ho, wo, cout)
+            assert np.array_equal(got, want.astype(np.float32)), (cout, n)
+
+
+def test_conv2d_patch_chunks_and_the_empty_batch(mods, monkeypatch):
+    """The patch-chunking branch (several products concatenated) with 1 and 3 images per chunk at N = 7 (an uneven last chunk)
+    is bitwise the unchunked result and the float64 convolution; an empty batch gives an empty (0, Ho, Wo, cout) result."""
+    ops, compressed = mods[0], mods[1]
+    rng = np.random.RandomState(77)
+    ks, cin, cout, pad = 3, 4, 16, 1
+    layer, kernel, bias = _exact_conv_layer(compressed, ks, cin, cout, pad, torch.relu, rng)
+    x = rng.randint(-8, 9, size=(7, 6, 5, cin)).astype(np.float32)
+    xt = torch.from_numpy(x).cuda()
+    with torch.no_grad():
+        whole = layer(xt)
+    assert torch.equal(whole.cpu(), torch.from_numpy(_conv_ref(x, kernel, bias, pad, torch.relu).astype(np.float32)))
+    per_image = 6 * 5 * ks * ks * cin * 4
+    for per, calls in ((1, 7), (3, 3)):
+        monkeypatch.setattr(compressed, "_PATCH_BYTES", per * per_image)
+        seen = []
+        matmul = layer._matmul
+        monkeypatch.setattr(layer, "_matmul", lambda p: seen.append(p.shape[0]) or matmul(p))
+        with torch.no_grad():
+            got = layer(xt)
+        assert seen == [per] * (7 // per) + ([7 % per] if 7 % per else []) and len(seen) == calls
+        assert torch.equal(got.view(torch.int32), whole.view(torch.int32)), per
+        monkeypatch.undo()
+    with torch.no_grad():
+        empty = layer(torch.empty(0, 6, 5, cin, device="cuda"))
+    assert empty.shape == (0, 6, 5, cout) and empty.dtype == torch.float32
+
+
+# ------------------------------------------------------------------ whole networks on exact data
+def _codes_model(centers, labels):
+    """The two attributes compress_network reads of a fitted model."""
+    return SimpleNamespace(cluster_centers_=np.asarray(centers, dtype=np.float32).reshape(-1, 1), labels_compact_=labels)
+
+
+def _exact_codes(net, rng):
+    """Pruned-looking codebooks for every layer of ``net``: centres {0, +-1/2, +-1} with the 0 centre for most weights; the float
+    layers get centers[labels].  Returns models_by_layer for compress_network."""
+    cen = np.array([0.0, 0.5, -0.5, 1.0, -1.0], dtype=np.float32)
+    p = [0.86, 0.035, 0.035, 0.035, 0.035]
+    models = {}
+    for layer in net.get_config().values():
+        if not layer.get_weights():
+            continue
+        kl = rng.choice(5, size=layer.kernel.numel(), p=p)
+        bl = rng.choice(5, size=layer.bias.numel(), p=[0.4, 0.15, 0.15, 0.15, 0.15])
+        kt, bt = torch.from_numpy(kl.astype(np.uint8)).cuda(), torch.from_numpy(bl.astype(np.uint8)).cuda()
+        layer.set_weights([torch.from_numpy(cen[kl]).cuda().view(layer.kernel.shape), torch.from_numpy(cen[bl]).cuda()])
+        models[layer] = [_codes_model(cen, kt), _codes_model(cen, bt)]
+    return models
+
+
+def _np(t):
+    return t.detach().cpu().numpy().astype(np.float64)
+
+
+def test_lenet_300_100_bit_exact_against_the_decoded_network(mods):
+    from neural_network_compression_amd.neural_networks.le_net_300_100 import LeNet300100
+
+    compressed = mods[1]
+    rng = np.random.RandomState(300)
+    net = LeNet300100().cuda()
+    cnet = compressed.compress_network(net, _exact_codes(net, rng))
+    assert all(isinstance(layer, compressed.CompressedDense) for layer in cnet.get_config().values())
+    for n in (5, 64):
+        x = rng.randint(0, 2, size=(n, 784)).astype(np.float32)
+        h = x.astype(np.float64)
+        for layer in net.get_config().values():   # the float64 forward, each layer's exactness asserted
+            w, b = _np(layer.kernel), _np(layer.bias)
+            assert_exact(h, w, b)
+            h = h @ w + b
+            h = np.maximum(h, 0) if layer.activation is torch.relu else h
+        xt = torch.from_numpy(x).cuda()
+        with torch.no_grad():
+            got, dec = cnet(xt), net(xt)
+        assert torch.equal(got.view(torch.int32), dec.view(torch.int32)), n
+        assert np.array_equal(got.cpu().numpy(), h.astype(np.float32)), n
+
+
+def test_lenet_5_bit_exact_against_a_float64_forward(mods):
+    from neural_network_compression_amd.neural_networks.le_net_5 import LeNet5
+
+    compressed = mods[1]
+    rng = np.random.RandomState(5)
+    net = LeNet5().cuda()
+    cnet = compressed.compress_network(net, _exact_codes(net, rng))
+    conf = net.get_config()
+    for name in ("conv1", "conv2"):
+        assert isinstance(cnet.get_config()[name], compressed.CompressedConv2D)
+    for name in ("dense", "logits"):
+        assert isinstance(cnet.get_config()[name], compressed.CompressedDense)
+    n = 3
+    x = rng.randint(0, 2, size=(n, 28, 28, 1)).astype(np.float32)
+
+    def pool(a):   # 2 x 2 max-pool, stride 2, NHWC
+        nn_, hh, ww, c = a.shape
+        return a.reshape(nn_, hh // 2, 2, ww // 2, 2, c).max(axis=(2, 4))
+
+    h = x.astype(np.float64)
+    for name in ("conv1", "conv2"):
+        layer = conf[name]
+        h = pool(np.maximum(_conv_ref(h, _np(layer.kernel), _np(layer.bias), layer.pad, None), 0))
+    h = h.reshape(n, -1)
+    for name in ("dense", "logits"):
+        w, b = _np(conf[name].kernel), _np(conf[name].bias)
+        assert_exact(h, w, b)
+        h = h @ w + b
+        h = np.maximum(h, 0) if conf[name].activation is torch.relu else h
+    with torch.no_grad():
+        got = cnet(torch.from_numpy(x).cuda()).cpu().numpy()
+    assert got.shape == (n, 10)
+    assert np.array_equal(got, h.astype(np.float32))
