@@ -579,6 +579,62 @@ int nnc_cbmm_f32(const float *x, int64_t m, int64_t kdim, const void *labels, in
                  const float *bias_dev, int32_t relu, float *y, void *workspace, int64_t workspace_bytes, void *stream);
 
 /* ------------------------------------------------------------------------------------
+ * The pruned quantized layer run from a bitmap-sparse form of its indices (csrc/nnc_cbsp.hip).  The
+ * (kdim, ncols) index matrix, row-major as nnc_cbmm_f32 reads it, and a skipped symbol z (by default the most frequent index)
+ * are packed into one 256-byte aligned buffer of nnc_cbsp_pack_bytes(kdim, ncols, label_bytes, nnz) bytes, S = ceil(ncols / 64):
+ *   bitmap  uint64[kdim * S]  bit b of word (i, s) set iff labels[i, 64 s + b] != z; bits past ncols are 0
+ *   lo      uint32[kdim * S]  low word of the exclusive count of stored symbols at the start of segment (i, s)
+ *   hi      uint32[kdim]      high word of that count at the start of row i; the count at (i, s) is
+ *                             (hi[i] << 32 | lo[i, s]) + (lo[i, s] < lo[i, 0] ? 2^32 : 0)
+ *   symbols                   the nnz labels != z in row-major order, label_bytes each, from byte align256(12 kdim S + 4 kdim)
+ * The structure is 96 bits per segment + 32 per row: at most 2 bits per weight of the (kdim, 64 S) padded matrix.  Limits:
+ * ncols < 2^32, kdim * S <= 2^40; nnz may exceed 2^32.
+ * nnc_cbsp_pack_bytes   host: the buffer size (0 for bad arguments).
+ * nnc_cbsp_pack         labels (any storage offset; 2-byte aligned for uint16) -> bitmap, counts and the symbols that fit in
+ *                       packed_bytes (pass nnc_cbsp_pack_bytes(.., 0) bytes to get the structure and the count alone);
+ *                       *nnz_dev (device int64, may be NULL) = the number of labels != z.  No per-weight temporary.
+ * nnc_cbsp_unpack       the inverse: labels_out[kdim * ncols].
+ * nnc_cbsp_f32          y[m, ncols] = c_z * sum_i x[r, i] + sum over stored (i, o) of x[r, i] * d[labels[i, o]] (+ bias[o], then
+ *                       ReLU if relu != 0), d[s] = float32(c[s] - c_z) for s < k, d[s] = -c_z for s >= k, c_z = centers[z] (0 if
+ *                       z >= k).  If c_z == 0 exactly the rank-1 term is dropped and d == c: a skipped weight is absent, so an
+ *                       Inf in x at a skipped position gives no Inf * 0 NaN -- the one departure from nnc_cbmm_f32 on the same
+ *                       labels.  ReLU keeps NaN.  m <= 16: k_cbsp_stream (row sums fused); m > 16: k_cbsp_rowsum + k_cbsp_tiled;
+ *                       split-K partials summed in split order by k_cbsp_reduce: no float atomics, the same call gives the same
+ *                       bits.  m or ncols = 0 is a no-op; kdim = 0 writes y = bias (or 0).
+ * nnc_cbsp_workspace_bytes  what nnc_cbsp_f32 needs for that shape (host arithmetic, plans for 256 CUs).
+ * nnc_cbsp_plan         host: the plan nnc_cbsp_f32 follows on a device with `cus` CUs, NNC_CBSP_PLAN_LEN values indexed by
+ *                       NNC_CBSP_P_*: PATH (NNC_CBMM_NONE / _STREAM / _TILED / _BIAS), MT, COPIES and ENTRIES of the LDS d
+ *                       table, SPLITS, RPS, ROWSUM (NNC_CBSP_ROWSUM_*), LDS, COL_TILES, ROW_TILES, WORKSPACE (this device).
+ * Argument errors (NNC_EINVAL; NNC_ENOSPACE for a short pack buffer or workspace) are returned before any HIP call; a plan
+ * with no kernel instantiation is NNC_EINVAL.
+ * ---------------------------------------------------------------------------------- */
+#define NNC_CBSP_ROWSUM_NONE 0
+#define NNC_CBSP_ROWSUM_FUSED 1
+#define NNC_CBSP_ROWSUM_PASS 2
+#define NNC_CBSP_P_PATH 0
+#define NNC_CBSP_P_MT 1
+#define NNC_CBSP_P_COPIES 2
+#define NNC_CBSP_P_ENTRIES 3
+#define NNC_CBSP_P_SPLITS 4
+#define NNC_CBSP_P_RPS 5
+#define NNC_CBSP_P_ROWSUM 6
+#define NNC_CBSP_P_LDS 7
+#define NNC_CBSP_P_COL_TILES 8
+#define NNC_CBSP_P_ROW_TILES 9
+#define NNC_CBSP_P_WORKSPACE 10
+#define NNC_CBSP_PLAN_LEN 11
+int64_t nnc_cbsp_pack_bytes(int64_t kdim, int64_t ncols, int label_bytes, int64_t nnz);
+int nnc_cbsp_pack(const void *labels, int label_bytes, int64_t kdim, int64_t ncols, int32_t zero_symbol, void *packed, int64_t packed_bytes,
+                  int64_t *nnz_dev, void *stream);
+int nnc_cbsp_unpack(const void *packed, int64_t packed_bytes, int label_bytes, int64_t kdim, int64_t ncols, int32_t zero_symbol, int64_t nnz,
+                    void *labels_out, void *stream);
+int64_t nnc_cbsp_workspace_bytes(int64_t m, int64_t kdim, int64_t ncols, int label_bytes);
+int nnc_cbsp_plan(int64_t m, int64_t kdim, int64_t ncols, int label_bytes, int32_t k, int32_t cus, int64_t *out);
+int nnc_cbsp_f32(const float *x, int64_t m, int64_t kdim, const void *packed, int64_t packed_bytes, int label_bytes, int64_t ncols, int32_t zero_symbol,
+                 int64_t nnz, const float *centers_dev, int32_t k, const float *bias_dev, int32_t relu, float *y, void *workspace,
+                 int64_t workspace_bytes, void *stream);
+
+/* ------------------------------------------------------------------------------------
  * Multi-GPU: the vector is sharded across one process per GPU (contiguous shards starting on multiples of
  * NNC_CHUNK elements); the exchange per Lloyd iteration is one all-reduce (SUM) of the 2K int64 sums / counts over
  * RCCL / xGMI, enqueued by the library on the caller's stream between its own kernels.  The reference has no

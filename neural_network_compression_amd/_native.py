@@ -28,6 +28,9 @@ NNC_KM_LOOP_KMAX = 64  # up to here the library takes the loop by itself
 CBMM_NONE, CBMM_STREAM, CBMM_TILED, CBMM_BIAS = 0, 1, 2, 3   # nnc_cbmm_plan: the path a call takes (include/nnc.h)
 CBMM_PLAN_LEN = 12
 CBMM_PLAN_FIELDS = ("path", "vb", "mt", "copies", "entries", "splits", "rps", "aligned", "lds", "col_tiles", "row_tiles", "workspace")
+CBSP_ROWSUM_NONE, CBSP_ROWSUM_FUSED, CBSP_ROWSUM_PASS = 0, 1, 2   # nnc_cbsp_plan: how the row sums of x are formed (include/nnc.h)
+CBSP_PLAN_LEN = 11
+CBSP_PLAN_FIELDS = ("path", "mt", "copies", "entries", "splits", "rps", "rowsum", "lds", "col_tiles", "row_tiles", "workspace")
 
 
 class NativeLibraryError(RuntimeError):
@@ -154,6 +157,13 @@ SIGNATURES = {
     "nnc_cbmm_workspace_bytes": (c_i64, [c_i64, c_i64, c_i64, c_int]),
     "nnc_cbmm_plan": (c_int, [c_i64, c_i64, c_i64, c_int, c_i32, c_i32, ctypes.c_uint64, ctypes.POINTER(c_i64)]),
     "nnc_cbmm_f32": (c_int, [c_void_p, c_i64, c_i64, c_void_p, c_int, c_i64, c_void_p, c_i32, c_void_p, c_i32, c_void_p, c_void_p, c_i64, c_void_p]),
+    "nnc_cbsp_pack_bytes": (c_i64, [c_i64, c_i64, c_int, c_i64]),
+    "nnc_cbsp_pack": (c_int, [c_void_p, c_int, c_i64, c_i64, c_i32, c_void_p, c_i64, c_void_p, c_void_p]),
+    "nnc_cbsp_unpack": (c_int, [c_void_p, c_i64, c_int, c_i64, c_i64, c_i32, c_i64, c_void_p, c_void_p]),
+    "nnc_cbsp_workspace_bytes": (c_i64, [c_i64, c_i64, c_i64, c_int]),
+    "nnc_cbsp_plan": (c_int, [c_i64, c_i64, c_i64, c_int, c_i32, c_i32, ctypes.POINTER(c_i64)]),
+    "nnc_cbsp_f32": (c_int, [c_void_p, c_i64, c_i64, c_void_p, c_i64, c_int, c_i64, c_i32, c_i64, c_void_p, c_i32, c_void_p, c_i32, c_void_p,
+                             c_void_p, c_i64, c_void_p]),
     "nnc_huffman_codes": (c_int, [ctypes.POINTER(ctypes.c_uint8), c_i32, ctypes.POINTER(ctypes.c_uint32)]),
     "nnc_codec_chunks": (c_size, [c_i64]),
     "nnc_huffman_chunk_offsets": (c_int, [c_void_p, c_int, c_i64, c_void_p, c_i32, c_void_p, c_void_p]),

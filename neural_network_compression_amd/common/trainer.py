@@ -161,15 +161,16 @@ class Trainer(ABC):
             models[layer][ti].cluster_centers_ = c.cpu().numpy().reshape(-1, 1)
         return accuracies
 
-    def compressed_network(self) -> torch.nn.Module:
+    def compressed_network(self, sparse=False) -> torch.nn.Module:
         """A copy of the network whose quantized layers run from their codebooks and centroid indices (compressed.py; the
-        float32 weights are never rebuilt), with the centres as they stand (after fine_tune_centroids, the tuned ones)."""
+        float32 weights are never rebuilt), with the centres as they stand (after fine_tune_centroids, the tuned ones).
+        ``sparse``: False, True (the indices in the bitmap-sparse form) or "auto" (per layer, the smaller form)."""
         models = getattr(self, "quantized_models_by_layer", None)
         if not models:
             raise RuntimeError("compressed_network needs a quantized network: call quantize first")
         from .. import compressed
 
-        return compressed.compress_network(self.neural_network, models)
+        return compressed.compress_network(self.neural_network, models, sparse=sparse)
 
     def _prune_parameters(self, with_standard_deviation_smoothing: bool) -> None:
         for layer, (weight_threshold, bias_threshold) in self._layers_to_prune_with_threshold.items():

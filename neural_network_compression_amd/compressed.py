@@ -7,9 +7,14 @@ tensor is never rebuilt.  Biases (one value per output column) are decoded once 
 
     CompressedDense.from_dense(dense, weight_model, bias_model)
     CompressedConv2D.from_conv(conv, weight_model, bias_model)     stride 1, padding "valid" | "same", NHWC in and out
-    compress_network(network, models_by_layer)                     a deep copy with the quantized layers replaced
-    load_network(path, network)                                    the same from a ``weights.nnc`` (Trainer.store_report)
+    compress_network(network, models_by_layer, sparse=False)       a deep copy with the quantized layers replaced
+    load_network(path, network, sparse=False)                      the same from a ``weights.nnc`` (Trainer.store_report)
     compressed_nbytes(network)                                     resident bytes of the layers' tensors
+
+A pruned layer can instead keep its indices in the bitmap-sparse form (ops.pack_sparse_codes, csrc/nnc_cbsp.hip, DESIGN.md
+section 11): one bit per weight, a count per 64 columns, and only the indices that are not the skipped (pruned) cluster's.
+``SparseCompressedDense`` / ``SparseCompressedConv2D``; ``sparse=True`` in compress_network / load_network /
+Trainer.compressed_network takes it for every quantized layer, ``sparse="auto"`` for each layer whose sparse form is smaller.
 
 Inference only: under autograd, with an input that needs a gradient, the layers raise instead of returning a result that
 silently has none (fine-tuning stays ``Trainer.fine_tune_centroids``).
@@ -119,50 +124,182 @@ class CompressedConv2D(_CodebookLayer):
     @classmethod
     def from_codes(cls, kernel_size, cin, cout, pad, labels, centers, bias, activation) -> "CompressedConv2D":
         """labels in the Keras order of the (h, w, in, out) kernel."""
-        rows = torch.from_numpy(keras_rows_for_unfold(kernel_size, kernel_size, cin)).to(labels.device)
-        return cls(kernel_size, cin, cout, pad, labels.reshape(-1, cout)[rows].contiguous(), centers, bias, activation)
+        return cls(kernel_size, cin, cout, pad, _unfold_labels(kernel_size, cin, cout, labels), centers, bias, activation)
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:   # x: (N, H, W, C)
-        n, hh, ww, _ = x.shape
-        ho, wo = hh + 2 * self.pad - self.kernel_size + 1, ww + 2 * self.pad - self.kernel_size + 1
-        per = max(1, _PATCH_BYTES // max(1, ho * wo * self.kdim * 4))
-        outs = [self._matmul(conv_patches(x[i: i + per], self.kernel_size, self.pad).contiguous()) for i in range(0, n, per)]
-        if not outs:   # an empty batch: the (0, kdim) product, as F.conv2d gives an empty result
-            outs = [self._matmul(x.new_empty((0, self.kdim)))]
-        y = outs[0] if len(outs) == 1 else torch.cat(outs)
-        return y.reshape(n, ho, wo, self.ncols)
+        return _conv_forward(self, x)
 
 
-def _replace(layer, weight_model, bias_model):
+def _conv_forward(layer, x: torch.Tensor) -> torch.Tensor:
+    """The patches of NHWC x, at most _PATCH_BYTES of them at a time, through layer._matmul -> (N, Ho, Wo, ncols)."""
+    n, hh, ww, _ = x.shape
+    ho, wo = hh + 2 * layer.pad - layer.kernel_size + 1, ww + 2 * layer.pad - layer.kernel_size + 1
+    per = max(1, _PATCH_BYTES // max(1, ho * wo * layer.kdim * 4))
+    outs = [layer._matmul(conv_patches(x[i: i + per], layer.kernel_size, layer.pad).contiguous()) for i in range(0, n, per)]
+    if not outs:   # an empty batch: the (0, kdim) product, as F.conv2d gives an empty result
+        outs = [layer._matmul(x.new_empty((0, layer.kdim)))]
+    y = outs[0] if len(outs) == 1 else torch.cat(outs)
+    return y.reshape(n, ho, wo, layer.ncols)
+
+
+def _unfold_labels(kernel_size: int, cin: int, cout: int, labels: torch.Tensor) -> torch.Tensor:
+    """Labels of a Keras (h, w, in, out) kernel -> the same labels with their rows in unfold order (keras_rows_for_unfold)."""
+    rows = torch.from_numpy(keras_rows_for_unfold(kernel_size, kernel_size, cin)).to(labels.device)
+    return labels.reshape(-1, cout)[rows].contiguous()
+
+
+class _SparseCodebookLayer(nn.Module):
+    """The indices in the bitmap-sparse form (ops.SparseCodes: its buffer is the module's ``packed`` buffer), centers float32[K],
+    bias float32[ncols] or None.  No kdim * ncols tensor stays resident."""
+
+    def __init__(self, codes: ops.SparseCodes, centers: torch.Tensor, bias: torch.Tensor | None, activation=None):
+        super().__init__()
+        self.kdim, self.ncols = codes.kdim, codes.ncols
+        self.k, self.zero_symbol, self.label_bytes, self.nnz = codes.k, codes.zero_symbol, codes.label_bytes, codes.nnz
+        if centers.numel() != codes.k:
+            raise ValueError(f"{centers.numel()} centres for indices into a codebook of {codes.k}")
+        self.register_buffer("packed", codes.buf)
+        self.register_buffer("centers", centers.reshape(-1).to(torch.float32).contiguous())
+        self.register_buffer("bias", None if bias is None else bias.reshape(-1).to(torch.float32).contiguous())
+        self.activation = activation
+        self._fused_relu = activation is torch.relu
+
+    @property
+    def codes(self) -> ops.SparseCodes:
+        return ops.SparseCodes(self.packed, self.kdim, self.ncols, self.k, self.zero_symbol, self.label_bytes, self.nnz)
+
+    def _matmul(self, x: torch.Tensor) -> torch.Tensor:
+        y = ops.sparse_codebook_matmul(x, self.codes, self.centers, bias=self.bias, relu=self._fused_relu)
+        if self.activation is not None and not self._fused_relu:
+            y = self.activation(y)
+        return y
+
+    def get_weights(self):
+        return []
+
+    def nbytes(self) -> int:
+        return sum(t.numel() * t.element_size() for t in (self.packed, self.centers, self.bias) if t is not None)
+
+
+class SparseCompressedDense(_SparseCodebookLayer):
+    """Dense run from its codebook and the bitmap-sparse form of its (in, out) indices."""
+
+    @classmethod
+    def from_dense(cls, dense, weight_model, bias_model=None, zero_symbol=None) -> "SparseCompressedDense":
+        if weight_model is None:
+            raise ValueError("the kernel was not quantized (no fitted model): keep the float32 layer")
+        kin, kout = dense.kernel.shape
+        centers, labels = _codes(weight_model, dense.kernel.device)
+        return cls.from_codes(kin, kout, labels, centers, _decoded_bias(dense.bias, bias_model), dense.activation, zero_symbol)
+
+    @classmethod
+    def from_codes(cls, kdim, ncols, labels, centers, bias, activation, zero_symbol=None) -> "SparseCompressedDense":
+        return cls(ops.pack_sparse_codes(labels, kdim, ncols, centers.numel(), zero_symbol), centers, bias, activation)
+
+    def forward(self, x: torch.Tensor) -> torch.Tensor:
+        return self._matmul(x.contiguous())
+
+
+class SparseCompressedConv2D(_SparseCodebookLayer):
+    """Conv2D (stride 1, NHWC) run from its codebook and the bitmap-sparse form of its indices, packed after the rows were put
+    in unfold order (keras_rows_for_unfold); patch chunking and the empty batch as CompressedConv2D."""
+
+    def __init__(self, kernel_size: int, cin: int, pad: int, codes: ops.SparseCodes, centers: torch.Tensor, bias: torch.Tensor | None,
+                 activation=None):
+        if codes.kdim != kernel_size * kernel_size * cin:
+            raise ValueError(f"{codes.kdim} index rows for a {kernel_size} x {kernel_size} x {cin} kernel")
+        super().__init__(codes, centers, bias, activation)
+        self.kernel_size, self.cin, self.pad = int(kernel_size), int(cin), int(pad)
+
+    @classmethod
+    def from_conv(cls, conv, weight_model, bias_model=None, zero_symbol=None) -> "SparseCompressedConv2D":
+        if weight_model is None:
+            raise ValueError("the kernel was not quantized (no fitted model): keep the float32 layer")
+        h, w, cin, cout = conv.kernel.shape
+        if h != w:
+            raise ValueError("square kernels only (as layers.Conv2D)")
+        centers, labels = _codes(weight_model, conv.kernel.device)
+        return cls.from_codes(h, cin, cout, conv.pad, labels, centers, _decoded_bias(conv.bias, bias_model), conv.activation, zero_symbol)
+
+    @classmethod
+    def from_codes(cls, kernel_size, cin, cout, pad, labels, centers, bias, activation, zero_symbol=None) -> "SparseCompressedConv2D":
+        """labels in the Keras order of the (h, w, in, out) kernel."""
+        unf = _unfold_labels(kernel_size, cin, cout, labels)
+        codes = ops.pack_sparse_codes(unf, kernel_size * kernel_size * cin, cout, centers.numel(), zero_symbol)
+        del unf
+        return cls(kernel_size, cin, pad, codes, centers, bias, activation)
+
+    def forward(self, x: torch.Tensor) -> torch.Tensor:   # x: (N, H, W, C)
+        return _conv_forward(self, x)
+
+
+def _check_sparse(sparse):
+    if sparse not in (False, True, "auto"):
+        raise ValueError(f"sparse must be False, True or 'auto', got {sparse!r}")
+
+
+def _pick(dense_layer, make_sparse, sparse):
+    """The dense form, the sparse one, or (``"auto"``) whichever holds fewer resident bytes."""
+    if sparse is False:
+        return dense_layer()
+    sp = make_sparse()
+    if sparse is True:
+        return sp
+    de = dense_layer()
+    return sp if sp.nbytes() < de.nbytes() else de
+
+
+def _from_codes(layer, shape, labels, centers, bias, sparse):
     from .neural_networks.layers import Conv2D, Dense
 
     if isinstance(layer, Dense):
-        return CompressedDense.from_dense(layer, weight_model, bias_model)
+        return _pick(lambda: CompressedDense(shape[0], shape[1], labels, centers, bias, layer.activation),
+                     lambda: SparseCompressedDense.from_codes(shape[0], shape[1], labels, centers, bias, layer.activation), sparse)
     if isinstance(layer, Conv2D):
-        return CompressedConv2D.from_conv(layer, weight_model, bias_model)
+        return _pick(lambda: CompressedConv2D.from_codes(shape[0], shape[2], shape[3], layer.pad, labels, centers, bias, layer.activation),
+                     lambda: SparseCompressedConv2D.from_codes(shape[0], shape[2], shape[3], layer.pad, labels, centers, bias, layer.activation),
+                     sparse)
     raise TypeError(f"no compressed form of {type(layer).__name__}")
 
 
-def compress_network(network: nn.Module, models_by_layer) -> nn.Module:
+def _replace(layer, weight_model, bias_model, sparse=False):
+    from .neural_networks.layers import Conv2D, Dense
+
+    if sparse is False:
+        if isinstance(layer, Dense):
+            return CompressedDense.from_dense(layer, weight_model, bias_model)
+        if isinstance(layer, Conv2D):
+            return CompressedConv2D.from_conv(layer, weight_model, bias_model)
+        raise TypeError(f"no compressed form of {type(layer).__name__}")
+    if not isinstance(layer, (Dense, Conv2D)):
+        raise TypeError(f"no compressed form of {type(layer).__name__}")
+    centers, labels = _codes(weight_model, layer.kernel.device)
+    return _from_codes(layer, tuple(layer.kernel.shape), labels, centers, _decoded_bias(layer.bias, bias_model), sparse)
+
+
+def compress_network(network: nn.Module, models_by_layer, sparse=False) -> nn.Module:
     """A deep copy of ``network`` whose quantized layers (``models_by_layer``: layer -> [kernel model, bias model], as
     Trainer.quantized_models_by_layer) run from their codebooks.  Layers are replaced by the attribute names of
-    ``get_config()``; a layer whose kernel passed through unquantized (model None) stays float32."""
+    ``get_config()``; a layer whose kernel passed through unquantized (model None) stays float32.  ``sparse``: False (the
+    indices as they are), True (the bitmap-sparse form, skipping the most frequent index), "auto" (per layer, the smaller)."""
+    _check_sparse(sparse)
     out = copy.deepcopy(network)
     for name, layer in network.get_config().items():
         models = models_by_layer.get(layer)
         if not models or models[0] is None:
             continue
         bias_model = models[1] if len(models) > 1 else None
-        setattr(out, name, _replace(layer, models[0], bias_model))
+        setattr(out, name, _replace(layer, models[0], bias_model, sparse))
     return out
 
 
-def load_network(path: str, network: nn.Module, device=None) -> nn.Module:
+def load_network(path: str, network: nn.Module, device=None, sparse=False) -> nn.Module:
     """``compress_network`` from a stored network (storage.save_compressed, as Trainer.store_report writes it: records
-    "{layer}.weights" / "{layer}.biases").  ``network`` gives the architecture; layers stored raw get the stored float32 values."""
+    "{layer}.weights" / "{layer}.biases").  ``network`` gives the architecture; layers stored raw get the stored float32 values.
+    ``sparse`` as in compress_network."""
     from . import storage
-    from .neural_networks.layers import Conv2D, Dense
 
+    _check_sparse(sparse)
     device = next(network.parameters()).device if device is None else device
     codes = storage.load_compressed_codes(path, device)
     out = copy.deepcopy(network)
@@ -184,23 +321,17 @@ def load_network(path: str, network: nn.Module, device=None) -> nn.Module:
             target.set_weights([went.reshape(target.kernel.shape)] + ([bias.reshape(target.bias.shape)] if bias is not None else []))
             continue
         shape, centers, labels = went
-        if isinstance(layer, Dense):
-            new = CompressedDense(shape[0], shape[1], labels, centers, bias, layer.activation)
-        elif isinstance(layer, Conv2D):
-            new = CompressedConv2D.from_codes(shape[0], shape[2], shape[3], layer.pad, labels, centers, bias, layer.activation)
-        else:
-            raise TypeError(f"no compressed form of {type(layer).__name__}")
-        setattr(out, name, new)
+        setattr(out, name, _from_codes(layer, tuple(shape), labels, centers, bias, sparse))
     return out
 
 
 def compressed_nbytes(network: nn.Module) -> int:
-    """Resident bytes of the tensors of ``network``'s layers (or of one layer): indices + codebook + decoded bias for the
-    compressed ones, the float32 parameters for the others."""
+    """Resident bytes of the tensors of ``network``'s layers (or of one layer): indices (or their bitmap-sparse form) + codebook +
+    decoded bias for the compressed ones, the float32 parameters for the others."""
     layers = network.get_config().values() if hasattr(network, "get_config") else [network]
     total = 0
     for layer in layers:
-        if isinstance(layer, _CodebookLayer):
+        if isinstance(layer, (_CodebookLayer, _SparseCodebookLayer)):
             total += layer.nbytes()
         else:
             total += sum(p.numel() * p.element_size() for p in layer.parameters())

@@ -16,18 +16,7 @@
 // and funnel-shifts them (v_alignbyte) by the row's misalignment, which is uniform over the wave.  An aligned chunk that holds
 // one byte of the tensor lies in the tensor's page, so no load leaves the allocation; lanes past the last column load their
 // row's first chunk and store nothing.  An index >= K reads 0, as nnc_gather_f32 does.
-#include "nnc_common.hpp"
-
-#define CB_WAVES 4
-#define CB_THREADS (CB_WAVES * WAVE)
-#define CB_UNROLL 8               // label rows in flight per wave
-#define CB_SKINNY_M 16
-#define CB_U8_COPIES 32           // K <= 256 (uint8): 32 copies of a 256-entry table (zero-padded: no bounds test) = 32 KiB
-#define CB_U16_WORDS 8448         // K > 256 (uint16): copies = the largest power of two with (K + 1) * copies <= this (33 KiB)
-#define CB_PLAN_CUS 256           // the workspace query plans for this many CUs (the plan's splits never shrink with more)
-#define TB_M 128
-#define TB_N 128
-#define TB_K 8
+#include "nnc_cbmm.hpp"
 
 // ------------------------------------------------------------------ the plan (host)
 // Every decision nnc_cbmm_f32 takes before it launches: which kernel, its instantiation, the LDS table, the grid and the K
@@ -41,8 +30,6 @@ struct CbPlan {
     long long splits, rows_per_split;
     long long lds;           // dynamic LDS bytes of the main kernel
 };
-
-static long long cdiv(long long a, long long b) { return (a + b - 1) / b; }
 
 // the splits and tiles (m >= 1, kdim >= 1, ncols >= 1)
 static void cb_grid(CbPlan &p, long long m, long long kdim, long long ncols, int lb, int cus)
@@ -99,17 +86,6 @@ static CbPlan cb_plan(long long m, long long kdim, long long ncols, int lb, int 
 static int64_t cb_ws_bytes(const CbPlan &p, long long m, long long ncols) { return p.splits > 1 ? (int64_t)p.splits * m * ncols * 4 : 0; }
 
 // ------------------------------------------------------------------ device helpers
-template <typename LT> struct CbTable;
-template <> struct CbTable<uint8_t> {
-    __device__ static __forceinline__ int index(uint32_t l, int, int cshift, int lane) { return (int)((l << cshift) | (lane & ((1 << cshift) - 1))); }
-};
-template <> struct CbTable<uint16_t> {
-    __device__ static __forceinline__ int index(uint32_t l, int k, int cshift, int lane)
-    {
-        return (int)((std::min(l, (uint32_t)k) << cshift) | (lane & ((1 << cshift) - 1)));   // entry k holds 0
-    }
-};
-
 // the table: `entries` values (centers, then zeros), `1 << cshift` copies of each, copy c of entry j at j * copies + c.  The
 // centres come from global memory once per workgroup into `stage`; the copies are made from LDS (a loop of global loads per copy
 // was a chain of L2 round trips in front of every workgroup).
@@ -329,19 +305,7 @@ __global__ __launch_bounds__(256) void k_cbmm_tiled(const float *__restrict__ x,
             }
         }
         __syncthreads();
-#pragma unroll
-        for (int kk = 0; kk < TB_K; ++kk) {
-            const float4 a0 = *reinterpret_cast<const float4 *>(xs + kk * TB_M + ty * 8);
-            const float4 a1 = *reinterpret_cast<const float4 *>(xs + kk * TB_M + ty * 8 + 4);
-            const float4 b0 = *reinterpret_cast<const float4 *>(ws + kk * TB_N + tx * 8);
-            const float4 b1 = *reinterpret_cast<const float4 *>(ws + kk * TB_N + tx * 8 + 4);
-            const float av[8] = {a0.x, a0.y, a0.z, a0.w, a1.x, a1.y, a1.z, a1.w};
-            const float bv[8] = {b0.x, b0.y, b0.z, b0.w, b1.x, b1.y, b1.z, b1.w};
-#pragma unroll
-            for (int a = 0; a < 8; ++a)
-#pragma unroll
-                for (int b = 0; b < 8; ++b) acc[a][b] = __builtin_fmaf(av[a], bv[b], acc[a][b]);
-        }
+        tb_tile_fma(xs, ws, tx, ty, acc);
     }
 #pragma unroll
     for (int a = 0; a < 8; ++a) {

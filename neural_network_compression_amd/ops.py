@@ -329,6 +329,122 @@ def cbmm_plan(m: int, kdim: int, ncols: int, label_bytes: int, k: int, cus: int,
     return dict(zip(nat.CBMM_PLAN_FIELDS, (int(v) for v in out)))
 
 
+class SparseCodes:
+    """The bitmap-sparse form of one (kdim, ncols) index matrix (include/nnc.h, nnc_cbsp_*): one 256-byte aligned uint8 device
+    buffer holding the bitmap, the symbol counts and the ``nnz`` stored symbols, plus the metadata a product needs.  ``k`` is the
+    codebook size the labels index; ``zero_symbol`` the skipped index."""
+
+    def __init__(self, buf: torch.Tensor, kdim: int, ncols: int, k: int, zero_symbol: int, label_bytes: int, nnz: int):
+        self.buf, self.kdim, self.ncols, self.k = buf, int(kdim), int(ncols), int(k)
+        self.zero_symbol, self.label_bytes, self.nnz = int(zero_symbol), int(label_bytes), int(nnz)
+
+    @property
+    def device(self):
+        return self.buf.device
+
+    def density(self) -> float:
+        n = self.kdim * self.ncols
+        return self.nnz / n if n else 0.0
+
+    def nbytes(self) -> int:
+        """Resident bytes of the form (the buffer)."""
+        return self.buf.numel() * self.buf.element_size()
+
+    def to_dense(self) -> torch.Tensor:
+        """The kdim * ncols labels again (uint8, or int16 storage for 2-byte labels), by nnc_cbsp_unpack."""
+        L = nat.load()
+        dt = torch.uint8 if self.label_bytes == 1 else torch.int16
+        out = torch.empty(self.kdim * self.ncols, dtype=dt, device=self.buf.device)
+        nat.check(L.nnc_cbsp_unpack(_ptr(self.buf), self.nbytes(), self.label_bytes, self.kdim, self.ncols, self.zero_symbol, self.nnz,
+                                    _ptr(out), _stream(self.buf)))
+        return out
+
+    def __repr__(self):
+        return (f"SparseCodes(kdim={self.kdim}, ncols={self.ncols}, k={self.k}, zero_symbol={self.zero_symbol}, "
+                f"label_bytes={self.label_bytes}, nnz={self.nnz}, nbytes={self.nbytes()})")
+
+
+def _aligned_bytes(nbytes: int, dev) -> torch.Tensor:
+    """A uint8 device buffer of ``nbytes`` starting on a 256-byte boundary (the caching allocator gives at least 512)."""
+    buf = torch.empty(max(1, int(nbytes)), dtype=torch.uint8, device=dev)
+    assert buf.data_ptr() % 256 == 0
+    return buf[: int(nbytes)]
+
+
+def pack_sparse_codes(labels: torch.Tensor, kdim: int, ncols: int, k: int, zero_symbol: int | None = None) -> SparseCodes:
+    """The (kdim, ncols) labels (uint8 / 16-bit, any storage offset) -> SparseCodes on their device (nnc_cbsp_pack: bitmap,
+    counts, symbols; no per-weight temporary).  ``zero_symbol``: the skipped index, by default the most frequent one (ties:
+    the lowest), as storage.pack_indices chooses it.  Two passes: the first returns the count of stored symbols (one host read)."""
+    _require_cuda(labels, "labels")
+    kdim, ncols, k = int(kdim), int(ncols), int(k)
+    lb = _label_bytes(labels)
+    if labels.numel() != kdim * ncols:
+        raise ValueError(f"labels must hold kdim * ncols = {kdim * ncols} indices, got {labels.numel()}")
+    if not 1 <= k <= nat.NNC_KMAX or (lb == 1 and k > 256):
+        raise ValueError(f"k = {k} outside 1..{256 if lb == 1 else nat.NNC_KMAX}")
+    labels = labels.reshape(-1)
+    if zero_symbol is None:
+        zero_symbol = int(torch.argmax(bincount(labels, k)).item()) if labels.numel() else 0
+    L = nat.load()
+    st = _stream(labels)
+    struct_bytes = int(L.nnc_cbsp_pack_bytes(kdim, ncols, lb, 0))
+    if struct_bytes == 0 and kdim * ncols > 0:
+        raise ValueError(f"no sparse form for a {kdim} x {ncols} matrix (ncols < 2^32, kdim * ceil(ncols / 64) <= 2^40)")
+    nnz_dev = torch.zeros(1, dtype=torch.int64, device=labels.device)
+    probe = _aligned_bytes(struct_bytes, labels.device)
+    nat.check(L.nnc_cbsp_pack(_ptr(labels), lb, kdim, ncols, int(zero_symbol), _ptr(probe), struct_bytes, _ptr(nnz_dev), st))
+    nnz = int(nnz_dev.item())
+    del probe
+    total = int(L.nnc_cbsp_pack_bytes(kdim, ncols, lb, nnz))
+    buf = _aligned_bytes(total, labels.device)
+    nat.check(L.nnc_cbsp_pack(_ptr(labels), lb, kdim, ncols, int(zero_symbol), _ptr(buf), total, None, st))
+    return SparseCodes(buf, kdim, ncols, k, int(zero_symbol), lb, nnz)
+
+
+def sparse_codebook_matmul(x: torch.Tensor, codes: SparseCodes, centers: torch.Tensor, bias: torch.Tensor | None = None,
+                           relu: bool = False) -> torch.Tensor:
+    """y = c_z * sum_i x[., i] + the stored weights' x[., i] * (centers[label] - c_z) (+ bias, then ReLU): x @ W for W[i, o] =
+    centers[labels[i, o]] read from the bitmap-sparse form (include/nnc.h, nnc_cbsp_f32).  With centers[zero_symbol] == 0 the
+    skipped weights are absent (an Inf in x meets no 0).  x: float32 (..., kdim); centers: float32[codes.k]; bias: float32[ncols]
+    or None.  Returns float32 (..., ncols).  Inference only, as codebook_matmul."""
+    _require_cuda(x, "x", torch.float32)
+    _require_cuda(centers, "centers", torch.float32)
+    if bias is not None:
+        _require_cuda(bias, "bias", torch.float32)
+    if not isinstance(codes, SparseCodes):
+        raise TypeError("codes must be a SparseCodes (ops.pack_sparse_codes)")
+    if torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (x, centers, bias)):
+        raise RuntimeError("sparse_codebook_matmul is inference only: it computes no gradient (run it under torch.no_grad())")
+    devs = {t.device for t in (x, codes.buf, centers, bias) if t is not None}
+    if len(devs) != 1:
+        raise ValueError("x, codes, centers and bias must be on one device")
+    kdim, ncols = codes.kdim, codes.ncols
+    if x.dim() < 1 or x.shape[-1] != kdim:
+        raise ValueError(f"x must have shape (..., {kdim}), got {tuple(x.shape)}")
+    if centers.numel() != codes.k:
+        raise ValueError(f"centers must hold k = {codes.k} values, got {centers.numel()}")
+    if bias is not None and bias.numel() != ncols:
+        raise ValueError(f"bias must hold ncols = {ncols} values, got {bias.numel()}")
+    L = nat.load()
+    lead = tuple(x.shape[:-1])
+    m = int(np.prod(lead)) if lead else 1
+    y = torch.empty(lead + (ncols,), dtype=torch.float32, device=x.device)
+    ws_bytes = int(L.nnc_cbsp_workspace_bytes(m, kdim, ncols, codes.label_bytes))
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=x.device) if ws_bytes else None
+    nat.check(L.nnc_cbsp_f32(_ptr(x), m, kdim, _ptr(codes.buf), codes.nbytes(), codes.label_bytes, ncols, codes.zero_symbol, codes.nnz,
+                             _ptr(centers), centers.numel(), _ptr(bias), 1 if relu else 0, _ptr(y), _ptr(ws), ws_bytes, _stream(x)))
+    return y
+
+
+def cbsp_plan(m: int, kdim: int, ncols: int, label_bytes: int, k: int, cus: int) -> dict:
+    """Host: the plan nnc_cbsp_f32 follows on a device with ``cus`` compute units (include/nnc.h, nnc_cbsp_plan), as a dict keyed
+    by _native.CBSP_PLAN_FIELDS.  No device needed."""
+    L = nat.load()
+    out = (ctypes.c_int64 * nat.CBSP_PLAN_LEN)()
+    nat.check(L.nnc_cbsp_plan(int(m), int(kdim), int(ncols), int(label_bytes), int(k), int(cus), out))
+    return dict(zip(nat.CBSP_PLAN_FIELDS, (int(v) for v in out)))
+
+
 def huffman_lengths(counts) -> tuple:
     """Host: (lengths uint8[k], hist int64[max_len+1], total_bits) from an index histogram."""
     L = nat.load()
