@@ -744,7 +744,12 @@ int nnc_huffman_lengths(const int64_t *counts, int32_t k, uint8_t *lengths_out, 
  *   nnc_huffman_encode               words_dev[nwords] (uint32, zeroed here; nwords >= total_bits / 32 + 2), MSB first
  *   nnc_huffman_decode_tables (host) first-code / count / first-index per length + symbols by (length, symbol), packed into
  *                                    nnc_huffman_decode_tables_bytes() bytes; copy them to the device for
- *   nnc_huffman_decode               one thread per chunk; *bad_dev = 1 if a chunk does not parse to its recorded length
+ *   nnc_huffman_decode               one thread per chunk; *bad_dev = 1 if a chunk does not parse to its recorded length.
+ *                                    words_dev must hold the stream, ceil(total_bits / 32) words, plus ONE look-ahead word behind
+ *                                    it: a chunk that ends on a word boundary loads the next word, so the last chunk may read word
+ *                                    total_bits / 32.  The decoder has no length argument and cannot check this itself.  It trusts
+ *                                    chunk_off_dev (each chunk <= 32 * NNC_CODEC_CHUNK bits, rising to total_bits) and the tables:
+ *                                    check both on the host first, as storage.py does for a stored file.
  * The pruned zeros share one centroid, so their index is the most frequent symbol and costs one bit in the dense stream.
  *
  * Relative-index sparse form (Deep Compression section 3; the format the reference's report cites, papers/lat/report.tex:327,
@@ -753,7 +758,10 @@ int nnc_huffman_lengths(const int64_t *counts, int32_t k, uint8_t *lengths_out, 
  * Distances restart at every chunk of NNC_CODEC_CHUNK positions.  The two entry streams are Huffman coded with the functions above.
  *   nnc_sparse_entry_offsets         entries_off_dev[nchunks + 1] uint64: entries in front of every chunk, [nchunks] = all entries
  *   nnc_sparse_emit                  delta_out_dev[entries] uint8, sym_out_dev[entries] (width of the labels)
- *   nnc_sparse_expand                the inverse; *bad_dev = 1 if an entry points outside its chunk
+ *   nnc_sparse_expand                the inverse; *bad_dev = 1 if an entry points outside its chunk.  zero_symbol is only checked
+ *                                    against NNC_KMAX: the caller checks it against its own K (storage.py does).
+ * The encoders give an index >= k no bits and no entry count of its own; the caller checks that the histogram adds up to n
+ * (storage.encode_indices / encode_sparse raise ValueError otherwise).
  * storage.py stores whichever of the dense stream and the sparse form (delta_bits 4 or 8) is smaller, per tensor.
  * ---------------------------------------------------------------------------------- */
 #define NNC_CODEC_CHUNK 1024

@@ -172,7 +172,13 @@ class Trainer(ABC):
 
         return compressed.compress_network(self.neural_network, models, sparse=sparse)
 
+    def _discard_quantization(self) -> None:
+        """The weights are about to change: the centroid indices of ``quantize`` no longer describe them, so nothing may store, run
+        or fine-tune from them any more."""
+        self.quantized_models_by_layer = {}
+
     def _prune_parameters(self, with_standard_deviation_smoothing: bool) -> None:
+        self._discard_quantization()
         for layer, (weight_threshold, bias_threshold) in self._layers_to_prune_with_threshold.items():
             weights, biases = layer.get_weights()
             zero_weight = utility.prune_weigth(weights, threshold=weight_threshold,
@@ -202,6 +208,7 @@ class Trainer(ABC):
                             smoothing=with_standard_deviation_smoothing)
 
     def _epochs(self, train_dataset, test_dataset, epochs, prune, reset, smoothing=True) -> List[float]:
+        self._discard_quantization()
         x = self._to_device(train_dataset.input_data).float()
         y = self._to_device(train_dataset.output_data).float()
         accuracies = []
@@ -217,9 +224,7 @@ class Trainer(ABC):
 
     def store_report(self, directory: str) -> None:
         """Zero counts per layer, as the reference's report.txt (common/trainer.py:154-175; its plots are out of scope).  After
-        ``quantize`` the network is also written in its stored form (storage.save_compressed: codebook + Huffman-coded centroid
-        indices, dense or relative-index sparse, whichever is smaller per tensor -> ``weights.nnc``) and the report gains what Deep
-        Compression reports: bits per weight of every tensor and the compression ratio against 32-bit weights."""
+        ``quantize`` (and no retraining since) also ``store_compressed``: the stored network and its ratio."""
         pathlib.Path(directory).mkdir(parents=True, exist_ok=True)
         report = ""
         for layer_name, layer in self.neural_network.get_config().items():
@@ -230,27 +235,41 @@ class Trainer(ABC):
             report += f"layer: {layer_name}\n"
             report += f"zeroed weights: {int((weight_layer == 0).sum())}\ntotal weights: {weight_layer.numel()}\n"
             report += f"zeroed biases: {int((bias_layer == 0).sum())}\ntotal weights: {bias_layer.numel()}\n\n"
-        models = getattr(self, "quantized_models_by_layer", None)
-        if models:
-            from .. import storage
-
-            stored = {}
-            for layer_name, layer in self.neural_network.get_config().items():
-                if layer not in models:
-                    continue
-                for kind, t, m in zip(("weights", "biases"), layer.get_weights(), models[layer]):
-                    stored[f"{layer_name}.{kind}"] = (tuple(t.shape), m, t if m is None else None)
-            rep = {}
-            storage.save_compressed(f"{directory}/weights.nnc", stored, report=rep)
-            self.compression_report = rep
-            for name, r in rep.items():
-                if name != "total":
-                    report += f"stored {name}: {r['bytes']} bytes, {r['bits_per_weight']:.3f} bits per weight ({r['form']}, {r['k']} centroids)\n"
-            t = rep["total"]
-            report += (f"stored network: {t['bytes']} bytes for {t['n']} weights = {t['bits_per_weight']:.3f} bits per weight; "
-                       f"compression ratio {t['compression_ratio']:.1f}x against float32\n")
         with open(f"{directory}/report.txt", "w") as f:
             f.write(report)
+        if getattr(self, "quantized_models_by_layer", None):
+            self.store_compressed(directory)
+
+    def store_compressed(self, directory: str) -> dict:
+        """The quantized network in its stored form (storage.save_compressed: codebook + Huffman-coded centroid indices, dense or
+        relative-index sparse, whichever is smaller per tensor -> ``weights.nnc``); appends to ``report.txt`` what Deep Compression
+        reports: bits per weight of every tensor and the compression ratio against 32-bit weights.  Needs ``quantize`` with no
+        retraining since (the indices must describe the weights).  Returns storage.save_compressed's report."""
+        models = getattr(self, "quantized_models_by_layer", None)
+        if not models:
+            raise RuntimeError("store_compressed needs a quantized network: call quantize first (retraining discards it)")
+        from .. import storage
+
+        pathlib.Path(directory).mkdir(parents=True, exist_ok=True)
+        stored = {}
+        for layer_name, layer in self.neural_network.get_config().items():
+            if layer not in models:
+                continue
+            for kind, t, m in zip(("weights", "biases"), layer.get_weights(), models[layer]):
+                stored[f"{layer_name}.{kind}"] = (tuple(t.shape), m, t if m is None else None)
+        rep = {}
+        storage.save_compressed(f"{directory}/weights.nnc", stored, report=rep)
+        self.compression_report = rep
+        report = ""
+        for name, r in rep.items():
+            if name != "total":
+                report += f"stored {name}: {r['bytes']} bytes, {r['bits_per_weight']:.3f} bits per weight ({r['form']}, {r['k']} centroids)\n"
+        t = rep["total"]
+        report += (f"stored network: {t['bytes']} bytes for {t['n']} weights = {t['bits_per_weight']:.3f} bits per weight; "
+                   f"compression ratio {t['compression_ratio']:.1f}x against float32\n")
+        with open(f"{directory}/report.txt", "a") as f:
+            f.write(report)
+        return rep
 
     def _get_gradient(self, input_data: torch.Tensor, expected_output: torch.Tensor):
         self.optimizer.zero_grad(set_to_none=True)

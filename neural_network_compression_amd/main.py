@@ -1,6 +1,6 @@
 """Experiment driver with the reference's entry point
 (neural_network_compression/main.py:31-93): train -> prune while training -> train with the masks
-held -> report -> quantize.  MNIST is fetched by the reference over the network
+held -> report -> quantize -> stored form.  MNIST is fetched by the reference over the network
 (common/utility.py:59); without the files this driver falls back to a synthetic 10-class problem of
 the same shape so that the whole surface still runs."""
 from __future__ import annotations
@@ -92,11 +92,12 @@ def _run_experiment(trainer, train_dataset, test_dataset, train_epochs, prune_tr
                                                    epochs=prune_train_epochs, with_standard_deviation_smoothing=True)
     semi_pruned_train_accuracies = trainer.semi_pruned_train(train_dataset=train_dataset, test_dataset=test_dataset,
                                                              epochs=semi_prune_train_epochs)
-    trainer.store_report(report_directory)
+    trainer.store_report(report_directory)        # the reference's zero counts, before quantization
     after_quantization_accuracy = trainer.quantize(
         test_dataset=test_dataset, with_cumulative_weight_distribution=with_cumulative_weight_distribution,
         maximum_centroid_bits=maximum_centroid_bits, k_means_initialization_mode=k_means_initialization_mode,
         arith=arith, reloc=reloc)
+    trainer.store_compressed(report_directory)    # weights.nnc + bits per weight and compression ratio in report.txt
 
     pathlib.Path(report_directory).mkdir(parents=True, exist_ok=True)
     with open(f"{report_directory}/accuracies.txt", "w") as f:

@@ -23,10 +23,14 @@ File layout (little endian), one record per tensor:
       STREAM(k, n) = u64 bits | u8 code_length[k] | u32 chunk_bits[ceil(n / 1024)] | u32 words[ceil(bits / 32)]  (MSB-first)
     total_bits = all stream bits of the record (what the compression ratio counts besides the tables).
     a tensor that passed through unquantized ("not enough bits") is stored raw: K = 0, then f32 data[N].
+
+A file is checked field by field on the host before anything reaches the device (_parse_records): a malformed
+or truncated one raises ValueError naming the field.  Files of the older NNC1 layout are not read.
 """
 from __future__ import annotations
 
 import ctypes
+import math
 import struct
 from typing import Dict, Tuple
 
@@ -38,6 +42,7 @@ from . import ops
 
 MAGIC = b"NNC2"
 CHUNK = 1024
+NNC_KMAX = nat.NNC_KMAX
 
 
 def _flatten_lengths(lengths: np.ndarray, counts: np.ndarray) -> np.ndarray:
@@ -52,6 +57,13 @@ def _flatten_lengths(lengths: np.ndarray, counts: np.ndarray) -> np.ndarray:
     return out
 
 
+def _check_histogram(counts: np.ndarray, k: int, n: int) -> None:
+    """The encoders give an index >= k no bits and the histogram does not count it, so the stream would silently lose it: a
+    histogram of k bins that does not add up to n means such an index is there."""
+    if counts.size != k or int(counts.sum()) != n:
+        raise ValueError(f"an index is >= k = {k} (the histogram of {n} indices over {k} symbols adds up to {int(counts.sum())})")
+
+
 def encode_indices(labels: torch.Tensor, k: int, counts: np.ndarray | None = None):
     """labels: device uint8 / int16-storage centroid indices.  Returns (words uint32 device tensor, chunk_bits np.uint32[nchunks],
     lengths np.uint8[k], total_bits)."""
@@ -61,6 +73,7 @@ def encode_indices(labels: torch.Tensor, k: int, counts: np.ndarray | None = Non
     if counts is None:
         counts = ops.bincount(labels, k).cpu().numpy()
     counts = np.asarray(counts, dtype=np.int64)
+    _check_histogram(counts, k, n)
     lengths, _, _ = ops.huffman_lengths(counts)
     lengths = _flatten_lengths(np.ascontiguousarray(lengths, dtype=np.uint8), counts)
     codes = np.zeros(k, dtype=np.uint32)
@@ -105,11 +118,20 @@ def decode_indices(words: torch.Tensor, chunk_bits: np.ndarray, n: int, lengths:
     return out
 
 
-def encode_sparse(labels: torch.Tensor, zero_symbol: int, delta_bits: int):
-    """The relative-index entries of ``labels`` (device) -> (delta uint8 device tensor [distance - 1], sym device tensor [indices, the
-    labels' width], entries_in_chunk np.uint16[nchunks])."""
+def encode_sparse(labels: torch.Tensor, zero_symbol: int, delta_bits: int, k: int | None = None, counts: np.ndarray | None = None):
+    """The relative-index entries of ``labels`` (device, indices < k; ``counts`` their histogram over k if known) -> (delta uint8
+    device tensor [distance - 1], sym device tensor [indices, the labels' width], entries_in_chunk np.uint16[nchunks]).  Without
+    ``k`` the bound is the codec's own, NNC_KMAX; pack_indices passes the tensor's K.  ValueError for an index or zero_symbol
+    >= k."""
     L = nat.load()
     n = labels.numel()
+    if k is None:
+        k, counts = NNC_KMAX, None
+    if not 0 <= int(zero_symbol) < k:
+        raise ValueError(f"zero_symbol {zero_symbol} is not an index below k = {k}")
+    if counts is None:
+        counts = ops.bincount(labels, k).cpu().numpy()
+    _check_histogram(np.asarray(counts, dtype=np.int64), k, n)
     lb = ops._label_bytes(labels)
     dev = labels.device
     stream = ops._stream(labels)
@@ -146,18 +168,55 @@ def _stream_bytes(words, chunk_bits, lengths, total_bits) -> bytes:
     return struct.pack("<Q", int(total_bits)) + lengths.tobytes() + chunk_bits.tobytes() + words.cpu().numpy().tobytes()
 
 
-def _read_stream(blob, pos, k, n, device, label_bytes):
-    (total_bits,) = struct.unpack_from("<Q", blob, pos); pos += 8
-    lengths = np.frombuffer(blob, dtype=np.uint8, count=k, offset=pos); pos += k
+class _Reader:
+    """Bounds-checked reads from a stored blob: running past its end is a ValueError, not a struct.error or a short array."""
+
+    def __init__(self, blob, pos=0):
+        self.blob, self.pos = blob, pos
+
+    def take(self, fmt):
+        size = struct.calcsize(fmt)
+        if self.pos + size > len(self.blob):
+            raise ValueError(f"truncated file: {size} bytes needed at offset {self.pos}, {len(self.blob)} in all")
+        out = struct.unpack_from(fmt, self.blob, self.pos)
+        self.pos += size
+        return out
+
+    def array(self, dtype, count):
+        size = np.dtype(dtype).itemsize * count
+        if self.pos + size > len(self.blob):
+            raise ValueError(f"truncated file: {size} bytes needed at offset {self.pos}, {len(self.blob)} in all")
+        out = np.frombuffer(self.blob, dtype=dtype, count=count, offset=self.pos)
+        self.pos += size
+        return out
+
+
+def _parse_stream(r: _Reader, k: int, n: int, what: str):
+    """STREAM(k, n) checked on the host -> (words int32, chunk_bits uint32, lengths uint8, total_bits).  The device decoder trusts
+    its tables and chunk table, so everything it indexes by is checked here."""
+    (total_bits,) = r.take("<Q")
+    lengths = r.array(np.uint8, k)
+    if int(lengths.max(initial=0)) > 32:
+        raise ValueError(f"{what}: code_length {int(lengths.max())} > 32")
+    used = lengths[lengths > 0].astype(np.int64)
+    if int(np.sum(np.left_shift(1, 32 - used, dtype=np.int64))) > 1 << 32:
+        raise ValueError(f"{what}: code_length violates Kraft's inequality")
     nchunks = (n + CHUNK - 1) // CHUNK
-    chunk_bits = np.frombuffer(blob, dtype=np.uint32, count=nchunks, offset=pos); pos += 4 * nchunks
-    nwords = (total_bits + 31) // 32
-    words = np.frombuffer(blob, dtype=np.int32, count=nwords, offset=pos); pos += 4 * nwords
+    chunk_bits = r.array(np.uint32, nchunks)
+    if nchunks and int(chunk_bits.max()) > 32 * CHUNK:
+        raise ValueError(f"{what}: chunk_bits {int(chunk_bits.max())} > {32 * CHUNK}")
     if int(chunk_bits.astype(np.int64).sum()) != total_bits:
-        raise ValueError("corrupt chunk table")
+        raise ValueError(f"{what}: chunk_bits do not add up to the stream's bits")
+    words = r.array(np.int32, (total_bits + 31) // 32)
+    return words, chunk_bits, lengths, total_bits
+
+
+def _decode_stream(parsed, n, device, label_bytes):
+    words, chunk_bits, lengths, total_bits = parsed
     if n == 0:
-        return torch.empty(0, dtype=torch.uint8 if label_bytes == 1 else torch.int16, device=device), pos
-    return decode_indices(torch.from_numpy(words.copy()).to(device), chunk_bits, n, lengths.copy(), k, label_bytes), pos
+        return torch.empty(0, dtype=torch.uint8 if label_bytes == 1 else torch.int16, device=device)
+    k = lengths.size
+    return decode_indices(torch.from_numpy(words.copy()).to(device), chunk_bits, n, lengths.copy(), k, label_bytes)
 
 
 SPARSE_MIN_ZERO_SHARE = 0.5     # below this share of zero-cluster indices the sparse form cannot win: it is not even tried
@@ -178,7 +237,7 @@ def pack_indices(labels: torch.Tensor, k: int, counts: np.ndarray | None = None,
     for name, db in (("sparse4", 4), ("sparse8", 8)):
         if form != name and not (form == "auto" and n > 0 and counts[zero] >= SPARSE_MIN_ZERO_SHARE * n):
             continue
-        delta, sym, per_chunk = encode_sparse(labels, zero, db)
+        delta, sym, per_chunk = encode_sparse(labels, zero, db, k, counts)
         e = delta.numel()
         body = struct.pack("<BBIQ", 1, db, zero, e) + per_chunk.tobytes()
         bits = 0
@@ -196,18 +255,44 @@ def pack_indices(labels: torch.Tensor, k: int, counts: np.ndarray | None = None,
     return cands[best][0], cands[best][1], best
 
 
-def unpack_indices(blob, pos, k, n, lb, device):
-    (form,) = struct.unpack_from("<B", blob, pos); pos += 1
+def _parse_indices(r: _Reader, k: int, n: int, lb: int):
+    """The index part of a record (from the form byte on), checked on the host."""
+    (form,) = r.take("<B")
     if form == 0:
-        return _read_stream(blob, pos, k, n, device, lb)
+        return ("dense", _parse_stream(r, k, n, "dense stream"))
     if form != 1:
-        raise ValueError("unknown index form")
-    db, zero, e = struct.unpack_from("<BIQ", blob, pos); pos += 13
+        raise ValueError(f"form {form} is neither 0 (dense) nor 1 (sparse)")
+    db, zero, e = r.take("<BIQ")
+    if db not in (4, 8):
+        raise ValueError(f"delta_bits {db} is neither 4 nor 8")
+    if zero >= k:
+        raise ValueError(f"zero_symbol {zero} >= K = {k}")
+    if e > n:
+        raise ValueError(f"entries {e} > N = {n}")
     nchunks = (n + CHUNK - 1) // CHUNK
-    per_chunk = np.frombuffer(blob, dtype=np.uint16, count=nchunks, offset=pos); pos += 2 * nchunks
-    delta, pos = _read_stream(blob, pos, 1 << db, e, device, 1)
-    sym, pos = _read_stream(blob, pos, k, e, device, lb)
-    return decode_sparse(delta, sym, per_chunk, n, zero), pos
+    per_chunk = r.array(np.uint16, nchunks)
+    if nchunks and int(per_chunk.max()) > CHUNK:
+        raise ValueError(f"entries_in_chunk {int(per_chunk.max())} > {CHUNK}")
+    if int(per_chunk.astype(np.int64).sum()) != e:
+        raise ValueError("entries_in_chunk do not add up to the entries")
+    delta = _parse_stream(r, 1 << db, e, "distance stream")
+    sym = _parse_stream(r, k, e, "index stream")
+    return ("sparse", zero, e, per_chunk, delta, sym)
+
+
+def _decode_parsed_indices(parsed, n, lb, device):
+    if parsed[0] == "dense":
+        return _decode_stream(parsed[1], n, device, lb)
+    _, zero, e, per_chunk, delta, sym = parsed
+    return decode_sparse(_decode_stream(delta, e, device, 1), _decode_stream(sym, e, device, lb), per_chunk, n, zero)
+
+
+def unpack_indices(blob, pos, k, n, lb, device):
+    """The inverse of pack_indices: (indices device tensor, position behind them).  The header fields are checked before any
+    device call (ValueError)."""
+    r = _Reader(blob, pos)
+    parsed = _parse_indices(r, k, n, lb)
+    return _decode_parsed_indices(parsed, n, lb, device), r.pos
 
 
 def pack_tensor(name: str, shape, model, raw: torch.Tensor | None = None, form: str = "auto", info: dict | None = None) -> bytes:
@@ -255,28 +340,55 @@ def save_compressed(path: str, tensors: Dict[str, Tuple[tuple, object, torch.Ten
     return len(blob)
 
 
+def _parse_records(blob):
+    """Every record of a stored blob, checked on the host before anything reaches the device: (name, shape, k, lb, n, payload)
+    with payload the raw float32 array (K = 0) or (centers float32[K], parsed indices).  ValueError names the field at fault."""
+    if blob[:4] != MAGIC:
+        raise ValueError(f"magic {bytes(blob[:4])!r} is not {MAGIC!r} (files of the older NNC1 layout are not read)")
+    r = _Reader(blob, 4)
+    (nt,) = r.take("<I")
+    out = []
+    for _ in range(nt):
+        (ln,) = r.take("<H")
+        name = bytes(r.array(np.uint8, ln)).decode("utf-8")
+        (nd,) = r.take("<B")
+        shape = r.take("<" + "Q" * nd)
+        k, lb, n, total_bits = r.take("<IBQQ")
+        if n != math.prod(shape):
+            raise ValueError(f"{name}: N = {n} is not the product of the shape {shape}")
+        if k == 0:
+            if lb != 0 or total_bits != 0:
+                raise ValueError(f"{name}: a raw record (K = 0) has label_bytes {lb} and total_bits {total_bits}, not 0 and 0")
+            out.append((name, shape, k, lb, n, r.array(np.float32, n)))
+            continue
+        if k > NNC_KMAX:
+            raise ValueError(f"{name}: K = {k} is not in 1 .. {NNC_KMAX}")
+        if lb not in (1, 2):
+            raise ValueError(f"{name}: label_bytes {lb} is neither 1 nor 2")
+        if lb == 1 and k > 256:
+            raise ValueError(f"{name}: label_bytes 1 cannot hold the indices of K = {k} > 256")
+        centers = r.array(np.float32, k)
+        parsed = _parse_indices(r, k, n, lb)
+        bits = parsed[1][3] if parsed[0] == "dense" else parsed[4][3] + parsed[5][3]
+        if bits != total_bits:
+            raise ValueError(f"{name}: total_bits {total_bits} is not the {bits} bits of its streams")
+        out.append((name, shape, k, lb, n, (centers, parsed)))
+    if r.pos != len(blob):
+        raise ValueError(f"{len(blob) - r.pos} trailing bytes after the last record")
+    return out
+
+
 def _records(path: str, device):
     """(name, shape, value) per stored tensor: value = the raw float32 device tensor (K = 0) or (centers float32[K] host array,
-    indices device tensor) decoded by the device decoders."""
+    indices device tensor) decoded by the device decoders.  The whole file is checked before the first device call."""
     with open(path, "rb") as f:
         blob = f.read()
-    if blob[:4] != MAGIC:
-        raise ValueError("not an NNC2 file")
-    (nt,) = struct.unpack_from("<I", blob, 4)
-    pos = 8
-    for _ in range(nt):
-        (ln,) = struct.unpack_from("<H", blob, pos); pos += 2
-        name = blob[pos: pos + ln].decode("utf-8"); pos += ln
-        (nd,) = struct.unpack_from("<B", blob, pos); pos += 1
-        shape = struct.unpack_from("<" + "Q" * nd, blob, pos); pos += 8 * nd
-        k, lb, n, total_bits = struct.unpack_from("<IBQQ", blob, pos); pos += 21
+    for name, shape, k, lb, n, payload in _parse_records(blob):
         if k == 0:
-            data = np.frombuffer(blob, dtype=np.float32, count=n, offset=pos); pos += 4 * n
-            yield name, shape, torch.from_numpy(data.copy()).to(device).reshape(shape)
+            yield name, shape, torch.from_numpy(payload.copy()).to(device).reshape(shape)
             continue
-        centers = np.frombuffer(blob, dtype=np.float32, count=k, offset=pos); pos += 4 * k
-        labels, pos = unpack_indices(blob, pos, k, n, lb, device)
-        yield name, shape, (centers, labels)
+        centers, parsed = payload
+        yield name, shape, (centers, _decode_parsed_indices(parsed, n, lb, device))
 
 
 def _device(device):

@@ -9,6 +9,7 @@ pytestmark = pytest.mark.gpu
 torch = pytest.importorskip("torch")
 
 from neural_network_compression_amd import synth  # noqa: E402
+from tests.helpers import codec_ref  # noqa: E402
 
 
 @pytest.fixture(scope="module")
@@ -105,25 +106,6 @@ def test_save_and_load_a_compressed_network(mods, tmp_path):
 
 
 # ------------------------------------------------------------------ relative-index sparse form (Deep Compression section 3)
-def _host_sparse_entries(lab, zero, dbits):
-    """The entries position by position in plain Python: (distance - 1, index) per stored position, filler entries
-    (distance 2^dbits, index = zero) for longer gaps, distances restarting at every chunk of 1024 positions."""
-    D = 1 << dbits
-    deltas, syms, per_chunk = [], [], []
-    for base in range(0, len(lab), 1024):
-        prev, cnt = base - 1, 0
-        for i in range(base, min(base + 1024, len(lab))):
-            if lab[i] == zero:
-                continue
-            gap = i - prev
-            while gap > D:
-                deltas.append(D - 1); syms.append(zero); gap -= D; cnt += 1
-            deltas.append(gap - 1); syms.append(int(lab[i])); cnt += 1
-            prev = i
-        per_chunk.append(cnt)
-    return np.array(deltas, dtype=np.int64), np.array(syms, dtype=np.int64), np.array(per_chunk, dtype=np.int64)
-
-
 @pytest.mark.parametrize("n,k,density,dbits", [(1, 4, 1.0, 4), (7, 4, 0.0, 4), (1023, 16, 0.3, 4), (1024, 16, 0.05, 4), (1025, 16, 0.01, 4),
                                                (5000, 16, 0.001, 4), (40_000, 257, 0.1, 8), (40_000, 257, 0.002, 8), (70_001, 33, 0.5, 4),
                                                (3000, 16, 0.0, 8), (66_000, 5, 0.02, 1)])
@@ -134,8 +116,8 @@ def test_sparse_entries_against_host_construction(mods, n, k, density, dbits):
     lab = np.where(rng.rand(n) < density, rng.randint(0, k, size=n), zero)
     dt = np.uint8 if k <= 256 else np.int16
     lab_d = torch.from_numpy(lab.astype(dt)).cuda()
-    delta, sym, per_chunk = storage.encode_sparse(lab_d, zero, dbits)
-    wd, ws, wc = _host_sparse_entries(lab, zero, dbits)
+    delta, sym, per_chunk = storage.encode_sparse(lab_d, zero, dbits, k)
+    wd, ws, wc = codec_ref.sparse_entries(lab, zero, dbits)
     assert np.array_equal(per_chunk.astype(np.int64), wc)
     assert np.array_equal(delta.cpu().numpy().astype(np.int64), wd)
     assert np.array_equal(sym.cpu().numpy().astype(np.int64) & 0xFFFF, ws)
@@ -200,3 +182,60 @@ def test_store_report_writes_the_stored_network_and_its_ratio(mods, tmp_path):
     for layer_name, layer in tr.neural_network.get_config().items():
         for kind, t in zip(("weights", "biases"), layer.get_weights()):
             assert torch.equal(got[f"{layer_name}.{kind}"], t), (layer_name, kind)
+
+
+@pytest.mark.parametrize("phase", ["train", "pruned_train", "semi_pruned_train"])
+def test_retraining_after_quantize_discards_the_indices(mods, tmp_path, phase):
+    """Once the weights are trained again the centroid indices of quantize no longer describe them: nothing may be stored, run or
+    fine-tuned from them."""
+    ops, pipeline, storage = mods
+    from neural_network_compression_amd import main
+    from neural_network_compression_amd.common.trainer import Trainer
+    from neural_network_compression_amd.le_net_300_100_trainer import LeNet300100Trainer
+
+    Trainer.pruned_indexes_by_layer.clear()
+    torch.manual_seed(0)
+    train, test = main._synthetic(n_train=512, n_test=64)
+    tr = LeNet300100Trainer()
+    tr.pruned_train(train, test, 1, with_standard_deviation_smoothing=True)
+    tr.quantize(test, True, 2, "density")
+    assert tr.quantized_models_by_layer
+    kw = {"with_standard_deviation_smoothing": True} if phase == "pruned_train" else {}
+    getattr(tr, phase)(train, test, 1, **kw)
+    assert not tr.quantized_models_by_layer
+    with pytest.raises(RuntimeError):
+        tr.compressed_network()
+    with pytest.raises(RuntimeError):
+        tr.fine_tune_centroids(train, test, 1)
+    with pytest.raises(RuntimeError):
+        tr.store_compressed(str(tmp_path / "rep"))
+    tr.store_report(str(tmp_path / "rep"))
+    assert (tmp_path / "rep" / "report.txt").exists() and not (tmp_path / "rep" / "weights.nnc").exists()
+    assert "compression ratio" not in (tmp_path / "rep" / "report.txt").read_text()
+
+
+def test_run_experiment_stores_the_final_network(mods, tmp_path, monkeypatch):
+    """_run_experiment writes weights.nnc after quantize (the reference's order kept its report before quantize, so nothing was
+    stored): it decodes to the network's final tensors bit for bit, and report.txt keeps the pre-quantize zero counts first."""
+    ops, pipeline, storage = mods
+    from neural_network_compression_amd import main
+    from neural_network_compression_amd.common.trainer import Trainer
+    from neural_network_compression_amd.le_net_300_100_trainer import LeNet300100Trainer
+
+    Trainer.pruned_indexes_by_layer.clear()
+    monkeypatch.chdir(tmp_path)
+    main.reset_seed()
+    train, test = main._synthetic(n_train=1024, n_test=128)
+    tr = LeNet300100Trainer()
+    main._run_experiment(tr, train, test, 1, 1, 1, 2, "density", True, "stored")
+    d = tmp_path / "LeNet300100_stored"
+    text = (d / "report.txt").read_text()
+    assert text.startswith("layer: dense1") and text.index("zeroed weights:") < text.index("stored network:")
+    assert "compression ratio" in text
+    got = storage.load_compressed(str(d / "weights.nnc"))
+    n = 0
+    for layer_name, layer in tr.neural_network.get_config().items():
+        for kind, t in zip(("weights", "biases"), layer.get_weights()):
+            assert torch.equal(got[f"{layer_name}.{kind}"], t), (layer_name, kind)
+            n += 1
+    assert n == len(got) == 6

@@ -134,6 +134,8 @@ def test_run_experiment_surface(trainer_mod, tmp_path, monkeypatch):
     d = tmp_path / "LeNet300100_smoke"
     rep = (d / "report.txt").read_text()
     assert "layer: dense1" in rep and "zeroed weights:" in rep
+    assert (d / "weights.nnc").exists()
+    assert "compression ratio" in rep
     acc = (d / "accuracies.txt").read_text()
     assert "after quantization" in acc
 
@@ -298,3 +300,5 @@ def test_run_experiment_lenet5_surface(trainer_mod, tmp_path, monkeypatch):
                                     with_cumulative_weight_distribution=False, experiment_name="smoke")
     rep = (tmp_path / "LeNet5_smoke" / "report.txt").read_text()
     assert "layer: conv1" in rep and "layer: dense" in rep and "layer: logits" in rep
+    assert (tmp_path / "LeNet5_smoke" / "weights.nnc").exists()
+    assert "compression ratio" in rep
