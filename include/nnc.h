@@ -579,6 +579,72 @@ int nnc_cbmm_f32(const float *x, int64_t m, int64_t kdim, const void *labels, in
                  const float *bias_dev, int32_t relu, float *y, void *workspace, int64_t workspace_bytes, void *stream);
 
 /* ------------------------------------------------------------------------------------
+ * The backward pass of nnc_cbmm_f32 from the same codebook and indices, W never decoded (csrc/nnc_cbgrad.hip, DESIGN.md section
+ * 12).  W[i, o] = centers[labels[i * ncols + o]] as above (same label widths, any storage offset); g = dL/dy float32[m, ncols].
+ * nnc_cbmm_dx_f32   dx[m, kdim] = g @ W^T: dx[r, i] = sum_o g[r, o] * W[i, o].  m <= 16 streams the index rows (k_cbdx_stream: a
+ *                   wave per row, a fixed-order wave reduction, one split per block of 64 * VB / label_bytes columns), larger m
+ *                   decodes W^T tiles into LDS (k_cbdx_tiled, ncols split by a count that depends on the shape alone); the split
+ *                   partials are summed in split order (k_cbgrad_reduce).  An index >= k reads 0.
+ * nnc_cbmm_dc_f32   dc[k] = sum over (i, o) with labels[i, o] = k of dW[i, o], dW = x^T g (x float32[m, kdim]), written as
+ *                   float64[k] (out_f64 != 0) or float32[k]; dW itself is never stored.  dW[i, o] is formed in float32 (r
+ *                   ascending; for m > 16 one value per split of m, k_cbdc_tiled) and binned as the exact integer
+ *                       rint(dW * 2^S),   S = 62 - T - P,   T = ceil(log2(kdim * ncols * splits)),   2^P > m * max|x| * max|g|
+ *                   (max|x|, max|g| reduced on the device; the kernel derives S itself and keeps it in the workspace): every
+ *                   image is at most 2^(62 - T) (1 + 2^-24)^m in magnitude, so the int64 sum stays below 2^63 for m <= 2^23; it is exact and
+ *                   independent of order -- the result depends on the shape and the data only.  dc = ldexp(sum, -S): each term
+ *                   is off by at most 2^(-S-1).  dc is all NaN if x or g holds Inf / NaN or P > 127; an index >= k falls into
+ *                   no bin.  splits is NNC_CBDC_P_SPLITS of the plan (1 for m <= 16).
+ * No host read and no float atomics in either; the same call gives the same bits.  m = 0 or kdim = 0: dx is empty (a no-op);
+ * ncols = 0: dx = 0.  No terms (m, kdim or ncols = 0): dc = 0.
+ * *_workspace_bytes: what the call needs for that shape (0 for none; host arithmetic only); the dc workspace must be 8-byte
+ * aligned.  Argument errors (NNC_EINVAL; NNC_ENOSPACE for a short workspace) are returned before any HIP call.
+ * *_plan: host arithmetic only, the plan the call follows on a device with `cus` compute units and labels at `labels_addr`.  The
+ * splits depend on the shape alone (planned for 256 CUs); `cus` changes only the grid.  NNC_EINVAL as the call, for cus < 1, out
+ * NULL, or a plan with no kernel instantiation.
+ *   dx (NNC_CBDX_P_*): PATH (NNC_CBMM_NONE: nothing written, _STREAM, _TILED, _ZERO: dx = 0), VB, MT, COPIES and ENTRIES of the
+ *       LDS codebook, SPLITS of ncols and CPS columns per split, ALIGNED, LDS, COL_TILES x ROW_TILES (stream: column blocks x
+ *       row groups; tiled: kdim tiles x m tiles), WORKSPACE.
+ *   dc (NNC_CBDC_P_*): PATH (_STREAM, _TILED, _ZERO: dc = 0), VB, MT, COPIES of every LDS bin, SPLITS of m and RPS rows of m per
+ *       split, ALIGNED, LDS, COL_TILES x ROW_TILES (stream: column blocks x row groups; tiled: ncols tiles x kdim tiles),
+ *       TERMS_LOG2 (T above), WORKSPACE.
+ * ---------------------------------------------------------------------------------- */
+#define NNC_CBMM_ZERO 4
+#define NNC_CBDX_P_PATH 0
+#define NNC_CBDX_P_VB 1
+#define NNC_CBDX_P_MT 2
+#define NNC_CBDX_P_COPIES 3
+#define NNC_CBDX_P_ENTRIES 4
+#define NNC_CBDX_P_SPLITS 5
+#define NNC_CBDX_P_CPS 6
+#define NNC_CBDX_P_ALIGNED 7
+#define NNC_CBDX_P_LDS 8
+#define NNC_CBDX_P_COL_TILES 9
+#define NNC_CBDX_P_ROW_TILES 10
+#define NNC_CBDX_P_WORKSPACE 11
+#define NNC_CBDX_PLAN_LEN 12
+#define NNC_CBDC_P_PATH 0
+#define NNC_CBDC_P_VB 1
+#define NNC_CBDC_P_MT 2
+#define NNC_CBDC_P_COPIES 3
+#define NNC_CBDC_P_SPLITS 4
+#define NNC_CBDC_P_RPS 5
+#define NNC_CBDC_P_ALIGNED 6
+#define NNC_CBDC_P_LDS 7
+#define NNC_CBDC_P_COL_TILES 8
+#define NNC_CBDC_P_ROW_TILES 9
+#define NNC_CBDC_P_TERMS_LOG2 10
+#define NNC_CBDC_P_WORKSPACE 11
+#define NNC_CBDC_PLAN_LEN 12
+int64_t nnc_cbmm_dx_workspace_bytes(int64_t m, int64_t kdim, int64_t ncols, int label_bytes);
+int nnc_cbmm_dx_plan(int64_t m, int64_t kdim, int64_t ncols, int label_bytes, int32_t k, int32_t cus, uint64_t labels_addr, int64_t *out);
+int nnc_cbmm_dx_f32(const float *g, int64_t m, int64_t kdim, const void *labels, int label_bytes, int64_t ncols, const float *centers_dev, int32_t k,
+                    float *dx, void *workspace, int64_t workspace_bytes, void *stream);
+int64_t nnc_cbmm_dc_workspace_bytes(int64_t m, int64_t kdim, int64_t ncols, int label_bytes, int32_t k);
+int nnc_cbmm_dc_plan(int64_t m, int64_t kdim, int64_t ncols, int label_bytes, int32_t k, int32_t cus, uint64_t labels_addr, int64_t *out);
+int nnc_cbmm_dc_f32(const float *x, const float *g, int64_t m, int64_t kdim, const void *labels, int label_bytes, int64_t ncols, int32_t k, void *dc,
+                    int32_t out_f64, void *workspace, int64_t workspace_bytes, void *stream);
+
+/* ------------------------------------------------------------------------------------
  * The pruned quantized layer run from a bitmap-sparse form of its indices (csrc/nnc_cbsp.hip).  The
  * (kdim, ncols) index matrix, row-major as nnc_cbmm_f32 reads it, and a skipped symbol z (by default the most frequent index)
  * are packed into one 256-byte aligned buffer of nnc_cbsp_pack_bytes(kdim, ncols, label_bytes, nnz) bytes, S = ceil(ncols / 64):

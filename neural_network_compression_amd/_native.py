@@ -28,6 +28,11 @@ NNC_KM_LOOP_KMAX = 64  # up to here the library takes the loop by itself
 CBMM_NONE, CBMM_STREAM, CBMM_TILED, CBMM_BIAS = 0, 1, 2, 3   # nnc_cbmm_plan: the path a call takes (include/nnc.h)
 CBMM_PLAN_LEN = 12
 CBMM_PLAN_FIELDS = ("path", "vb", "mt", "copies", "entries", "splits", "rps", "aligned", "lds", "col_tiles", "row_tiles", "workspace")
+CBMM_ZERO = 4   # nnc_cbmm_dx_plan / nnc_cbmm_dc_plan: the output is zero-filled (include/nnc.h)
+CBDX_PLAN_LEN = 12
+CBDX_PLAN_FIELDS = ("path", "vb", "mt", "copies", "entries", "splits", "cps", "aligned", "lds", "col_tiles", "row_tiles", "workspace")
+CBDC_PLAN_LEN = 12
+CBDC_PLAN_FIELDS = ("path", "vb", "mt", "copies", "splits", "rps", "aligned", "lds", "col_tiles", "row_tiles", "terms_log2", "workspace")
 CBSP_ROWSUM_NONE, CBSP_ROWSUM_FUSED, CBSP_ROWSUM_PASS = 0, 1, 2   # nnc_cbsp_plan: how the row sums of x are formed (include/nnc.h)
 CBSP_PLAN_LEN = 11
 CBSP_PLAN_FIELDS = ("path", "mt", "copies", "entries", "splits", "rps", "rowsum", "lds", "col_tiles", "row_tiles", "workspace")
@@ -157,6 +162,12 @@ SIGNATURES = {
     "nnc_cbmm_workspace_bytes": (c_i64, [c_i64, c_i64, c_i64, c_int]),
     "nnc_cbmm_plan": (c_int, [c_i64, c_i64, c_i64, c_int, c_i32, c_i32, ctypes.c_uint64, ctypes.POINTER(c_i64)]),
     "nnc_cbmm_f32": (c_int, [c_void_p, c_i64, c_i64, c_void_p, c_int, c_i64, c_void_p, c_i32, c_void_p, c_i32, c_void_p, c_void_p, c_i64, c_void_p]),
+    "nnc_cbmm_dx_workspace_bytes": (c_i64, [c_i64, c_i64, c_i64, c_int]),
+    "nnc_cbmm_dx_plan": (c_int, [c_i64, c_i64, c_i64, c_int, c_i32, c_i32, ctypes.c_uint64, ctypes.POINTER(c_i64)]),
+    "nnc_cbmm_dx_f32": (c_int, [c_void_p, c_i64, c_i64, c_void_p, c_int, c_i64, c_void_p, c_i32, c_void_p, c_void_p, c_i64, c_void_p]),
+    "nnc_cbmm_dc_workspace_bytes": (c_i64, [c_i64, c_i64, c_i64, c_int, c_i32]),
+    "nnc_cbmm_dc_plan": (c_int, [c_i64, c_i64, c_i64, c_int, c_i32, c_i32, ctypes.c_uint64, ctypes.POINTER(c_i64)]),
+    "nnc_cbmm_dc_f32": (c_int, [c_void_p, c_void_p, c_i64, c_i64, c_void_p, c_int, c_i64, c_i32, c_void_p, c_i32, c_void_p, c_i64, c_void_p]),
     "nnc_cbsp_pack_bytes": (c_i64, [c_i64, c_i64, c_int, c_i64]),
     "nnc_cbsp_pack": (c_int, [c_void_p, c_int, c_i64, c_i64, c_i32, c_void_p, c_i64, c_void_p, c_void_p]),
     "nnc_cbsp_unpack": (c_int, [c_void_p, c_i64, c_int, c_i64, c_i64, c_i32, c_i64, c_void_p, c_void_p]),

@@ -43,6 +43,14 @@ def _batches(x: torch.Tensor, y: torch.Tensor, batch: int = 512, shuffle_buffer:
         yield x[idx], y[idx]
 
 
+def kernel_l2(layer) -> torch.Tensor:
+    """tf.nn.l2_loss of a layer's kernel, sum(kernel^2) / 2: from the float32 kernel, or for a trainable codebook layer from its
+    codebook and index counts (kernel_sq_sum, compressed.py) without the kernel."""
+    if hasattr(layer, "kernel_sq_sum"):
+        return layer.kernel_sq_sum() / 2
+    return (layer.kernel ** 2).sum() / 2
+
+
 class Trainer(ABC):
     neural_network: torch.nn.Module
     optimizer: torch.optim.Optimizer
@@ -61,8 +69,8 @@ class Trainer(ABC):
         """layer -> (weight threshold, bias threshold)."""
 
     @abstractmethod
-    def _get_error(self, input_data: torch.Tensor, expected_output: torch.Tensor) -> torch.Tensor:
-        """The loss."""
+    def _get_error(self, input_data: torch.Tensor, expected_output: torch.Tensor, network: torch.nn.Module | None = None) -> torch.Tensor:
+        """The loss of ``network`` (by default the float network; fine_tune_compressed passes its trainable codebook copy)."""
 
     # ------------------------------------------------------------------ device plumbing
     @property
@@ -161,16 +169,71 @@ class Trainer(ABC):
             models[layer][ti].cluster_centers_ = c.cpu().numpy().reshape(-1, 1)
         return accuracies
 
-    def compressed_network(self, sparse=False) -> torch.nn.Module:
+    def fine_tune_compressed(self, train_dataset: LeNetDataset, test_dataset: LeNetDataset, epochs: int,
+                             learning_rate: float = 1e-3) -> List[float]:
+        """fine_tune_centroids' algorithm run on ``compressed_network(trainable=True)``: the indices stay fixed and per batch every
+        quantized tensor's centres take the plain step c -= learning_rate * dc, dc formed from the codebook and the indices by
+        ops.codebook_linear's backward (neither W nor dW is built).  Tensors that passed through
+        unquantized stay frozen.  At the end the tuned centres go into ``quantized_models_by_layer`` and the float layers are
+        re-decoded from them (ops.gather), as after fine_tune_centroids.  Returns the accuracy per epoch (of the trainable
+        network)."""
+        models = getattr(self, "quantized_models_by_layer", None)
+        if not models:
+            raise RuntimeError("fine_tune_compressed needs a quantized network: call quantize first")
+        from .. import compressed
+
+        net = self.compressed_network(trainable=True)
+        for p in net.parameters():
+            p.requires_grad_(False)
+        tuned = {}   # layer name -> trainable layer
+        params = []
+        for name, layer in net.get_config().items():
+            if isinstance(layer, compressed._TrainableCodebookLayer):
+                tuned[name] = layer
+                for p in (layer.centers, layer.bias_centers):
+                    if p is not None:
+                        p.requires_grad_(True)
+                        params.append(p)
+        x = self._to_device(train_dataset.input_data).float()
+        y = self._to_device(train_dataset.output_data).float()
+        accuracies = []
+        for _ in range(epochs):
+            for xb, yb in _batches(x, y):
+                for p in params:
+                    p.grad = None
+                self._get_error(xb, yb, net).backward()
+                with torch.no_grad():
+                    for p in params:
+                        if p.grad is not None:
+                            p.sub_(learning_rate * p.grad)
+            accuracies.append(self._get_accuracy(test_dataset, net))
+        with torch.no_grad():
+            for name, layer in self.neural_network.get_config().items():
+                t = tuned.get(name)
+                if t is None:
+                    continue
+                ms = models[layer]
+                tensors = layer.get_weights()
+                for ti, c in ((0, t.centers), (1, t.bias_centers)):
+                    if c is None or ti >= len(ms) or ms[ti] is None:
+                        continue
+                    c = c.detach().contiguous()
+                    ms[ti].cluster_centers_ = c.cpu().numpy().reshape(-1, 1)
+                    tensors[ti] = ops.gather(c, ms[ti].labels_compact_).view(tensors[ti].shape)
+                layer.set_weights(tensors)
+        return accuracies
+
+    def compressed_network(self, sparse=False, trainable=False) -> torch.nn.Module:
         """A copy of the network whose quantized layers run from their codebooks and centroid indices (compressed.py; the
         float32 weights are never rebuilt), with the centres as they stand (after fine_tune_centroids, the tuned ones).
-        ``sparse``: False, True (the indices in the bitmap-sparse form) or "auto" (per layer, the smaller form)."""
+        ``sparse``: False, True (the indices in the bitmap-sparse form) or "auto" (per layer, the smaller form).
+        ``trainable=True`` (with sparse=False only): the layers' centres are parameters with a backward pass."""
         models = getattr(self, "quantized_models_by_layer", None)
         if not models:
             raise RuntimeError("compressed_network needs a quantized network: call quantize first")
         from .. import compressed
 
-        return compressed.compress_network(self.neural_network, models, sparse=sparse)
+        return compressed.compress_network(self.neural_network, models, sparse=sparse, trainable=trainable)
 
     def _discard_quantization(self) -> None:
         """The weights are about to change: the centroid indices of ``quantize`` no longer describe them, so nothing may store, run
@@ -283,8 +346,9 @@ class Trainer(ABC):
         self.optimizer.step()
 
     @torch.no_grad()
-    def _get_accuracy(self, dataset: LeNetDataset) -> float:
+    def _get_accuracy(self, dataset: LeNetDataset, network: torch.nn.Module | None = None) -> float:
         x = self._to_device(dataset.input_data).float()
         y = self._to_device(dataset.output_data)
-        pred = torch.argmax(torch.softmax(self.neural_network(x), dim=1), dim=1)
+        net = self.neural_network if network is None else network
+        pred = torch.argmax(torch.softmax(net(x), dim=1), dim=1)
         return float((pred == y.to(pred.dtype)).float().mean().item())

@@ -7,7 +7,7 @@ tensor is never rebuilt.  Biases (one value per output column) are decoded once 
 
     CompressedDense.from_dense(dense, weight_model, bias_model)
     CompressedConv2D.from_conv(conv, weight_model, bias_model)     stride 1, padding "valid" | "same", NHWC in and out
-    compress_network(network, models_by_layer, sparse=False)       a deep copy with the quantized layers replaced
+    compress_network(network, models_by_layer, sparse=False, trainable=False)   a deep copy with the quantized layers replaced
     load_network(path, network, sparse=False)                      the same from a ``weights.nnc`` (Trainer.store_report)
     compressed_nbytes(network)                                     resident bytes of the layers' tensors
 
@@ -16,8 +16,13 @@ section 11): one bit per weight, a count per 64 columns, and only the indices th
 ``SparseCompressedDense`` / ``SparseCompressedConv2D``; ``sparse=True`` in compress_network / load_network /
 Trainer.compressed_network takes it for every quantized layer, ``sparse="auto"`` for each layer whose sparse form is smaller.
 
-Inference only: under autograd, with an input that needs a gradient, the layers raise instead of returning a result that
-silently has none (fine-tuning stays ``Trainer.fine_tune_centroids``).
+These layers are inference only: under autograd, with an input that needs a gradient, they raise instead of returning a result
+that silently has none.  ``trainable=True`` in compress_network / Trainer.compressed_network gives the trainable variants instead
+(``TrainableCompressedDense`` / ``TrainableCompressedConv2D``): their ``centers`` is an nn.Parameter and the
+forward goes through ops.codebook_linear, whose backward forms dx and the centroid gradient from the codebook and the indices
+(csrc/nnc_cbgrad.hip) -- W and dW are never built.  A quantized bias keeps its indices and a ``bias_centers`` parameter; a raw bias
+stays frozen.  ``kernel_sq_sum()`` gives the trainers' L2 term without W.  Trainer.fine_tune_compressed trains them.  The
+bitmap-sparse layers have no backward pass.
 """
 from __future__ import annotations
 
@@ -146,6 +151,111 @@ def _unfold_labels(kernel_size: int, cin: int, cout: int, labels: torch.Tensor) 
     """Labels of a Keras (h, w, in, out) kernel -> the same labels with their rows in unfold order (keras_rows_for_unfold)."""
     rows = torch.from_numpy(keras_rows_for_unfold(kernel_size, kernel_size, cin)).to(labels.device)
     return labels.reshape(-1, cout)[rows].contiguous()
+
+
+class _GatherCenters(torch.autograd.Function):
+    """centers[labels] (ops.gather) with the centroid gradient of the result (ops.centroid_gradient) as the backward."""
+
+    @staticmethod
+    def forward(ctx, centers, labels):
+        ctx.save_for_backward(labels)
+        ctx.k = centers.numel()
+        return ops.gather(centers.detach().contiguous(), labels)
+
+    @staticmethod
+    def backward(ctx, grad):
+        (labels,) = ctx.saved_tensors
+        return ops.centroid_gradient(grad.contiguous(), labels, ctx.k).to(torch.float32), None
+
+
+class _TrainableCodebookLayer(nn.Module):
+    """labels (kdim * ncols indices, row-major (kdim, ncols)) and counts (their histogram, for kernel_sq_sum) as buffers, centers a
+    float32[K] nn.Parameter.  The bias is a quantized one (bias_labels buffer + bias_centers parameter), a frozen raw one (bias
+    buffer) or None."""
+
+    def __init__(self, kdim: int, ncols: int, labels: torch.Tensor, centers: torch.Tensor, bias: torch.Tensor | None = None,
+                 bias_codes=None, activation=None):
+        super().__init__()
+        if labels.numel() != kdim * ncols:
+            raise ValueError(f"{labels.numel()} indices for a {kdim} x {ncols} weight matrix")
+        self.kdim, self.ncols = int(kdim), int(ncols)
+        self.register_buffer("labels", labels.reshape(-1))
+        self.centers = nn.Parameter(centers.detach().reshape(-1).to(torch.float32).clone())
+        self.register_buffer("counts", ops.bincount(self.labels, self.centers.numel()))
+        if bias_codes is not None:
+            bcenters, blabels = bias_codes
+            if blabels.numel() != ncols:
+                raise ValueError(f"{blabels.numel()} bias indices for {ncols} columns")
+            self.register_buffer("bias_labels", blabels.reshape(-1))
+            self.bias_centers = nn.Parameter(bcenters.detach().reshape(-1).to(torch.float32).clone())
+            self.register_buffer("bias", None)
+        else:
+            self.register_buffer("bias_labels", None)
+            self.bias_centers = None
+            self.register_buffer("bias", None if bias is None else bias.detach().reshape(-1).to(torch.float32).clone())
+        self.activation = activation
+        self._fused_relu = activation is torch.relu
+
+    def current_bias(self) -> torch.Tensor | None:
+        if self.bias_centers is not None:
+            return _GatherCenters.apply(self.bias_centers, self.bias_labels)
+        return self.bias
+
+    def _matmul(self, x: torch.Tensor) -> torch.Tensor:
+        y = ops.codebook_linear(x, self.labels, self.centers, self.kdim, self.ncols, bias=self.current_bias(), relu=self._fused_relu)
+        if self.activation is not None and not self._fused_relu:
+            y = self.activation(y)
+        return y
+
+    def kernel_sq_sum(self) -> torch.Tensor:
+        """sum of kernel^2 = sum_k count_k * c_k^2, differentiable in the centres, without W."""
+        return (self.counts.to(torch.float32) * self.centers ** 2).sum()
+
+    def get_weights(self):
+        return []
+
+    def nbytes(self) -> int:
+        ts = (self.labels, self.centers, self.bias, self.bias_labels, self.bias_centers)
+        return sum(t.numel() * t.element_size() for t in ts if t is not None)
+
+
+class TrainableCompressedDense(_TrainableCodebookLayer):
+    """CompressedDense with trainable centres (ops.codebook_linear)."""
+
+    def forward(self, x: torch.Tensor) -> torch.Tensor:
+        return self._matmul(x.contiguous())
+
+
+class TrainableCompressedConv2D(_TrainableCodebookLayer):
+    """CompressedConv2D with trainable centres: the patches (F.unfold, chunked as CompressedConv2D) through ops.codebook_linear;
+    autograd carries the patch gradients back through the unfold."""
+
+    def __init__(self, kernel_size: int, cin: int, cout: int, pad: int, labels_unfold: torch.Tensor, centers: torch.Tensor, bias=None,
+                 bias_codes=None, activation=None):
+        super().__init__(kernel_size * kernel_size * cin, cout, labels_unfold, centers, bias, bias_codes, activation)
+        self.kernel_size, self.cin, self.pad = int(kernel_size), int(cin), int(pad)
+
+    def forward(self, x: torch.Tensor) -> torch.Tensor:   # x: (N, H, W, C)
+        return _conv_forward(self, x)
+
+
+def _trainable(layer, weight_model, bias_model):
+    from .neural_networks.layers import Conv2D, Dense
+
+    if weight_model is None:
+        raise ValueError("the kernel was not quantized (no fitted model): keep the float32 layer")
+    centers, labels = _codes(weight_model, layer.kernel.device)
+    bias, bias_codes = (None, _codes(bias_model, layer.kernel.device)) if bias_model is not None else (layer.bias, None)
+    if isinstance(layer, Dense):
+        kin, kout = layer.kernel.shape
+        return TrainableCompressedDense(kin, kout, labels, centers, bias, bias_codes, layer.activation)
+    if isinstance(layer, Conv2D):
+        h, w, cin, cout = layer.kernel.shape
+        if h != w:
+            raise ValueError("square kernels only (as layers.Conv2D)")
+        return TrainableCompressedConv2D(h, cin, cout, layer.pad, _unfold_labels(h, cin, cout, labels), centers, bias, bias_codes,
+                                         layer.activation)
+    raise TypeError(f"no compressed form of {type(layer).__name__}")
 
 
 class _SparseCodebookLayer(nn.Module):
@@ -277,19 +387,22 @@ def _replace(layer, weight_model, bias_model, sparse=False):
     return _from_codes(layer, tuple(layer.kernel.shape), labels, centers, _decoded_bias(layer.bias, bias_model), sparse)
 
 
-def compress_network(network: nn.Module, models_by_layer, sparse=False) -> nn.Module:
+def compress_network(network: nn.Module, models_by_layer, sparse=False, trainable=False) -> nn.Module:
     """A deep copy of ``network`` whose quantized layers (``models_by_layer``: layer -> [kernel model, bias model], as
     Trainer.quantized_models_by_layer) run from their codebooks.  Layers are replaced by the attribute names of
     ``get_config()``; a layer whose kernel passed through unquantized (model None) stays float32.  ``sparse``: False (the
-    indices as they are), True (the bitmap-sparse form, skipping the most frequent index), "auto" (per layer, the smaller)."""
+    indices as they are), True (the bitmap-sparse form, skipping the most frequent index), "auto" (per layer, the smaller).
+    ``trainable=True`` (dense indices only): TrainableCompressedDense / TrainableCompressedConv2D, centres as parameters."""
     _check_sparse(sparse)
+    if trainable and sparse is not False:
+        raise ValueError("trainable=True needs sparse=False: the bitmap-sparse layers have no backward pass")
     out = copy.deepcopy(network)
     for name, layer in network.get_config().items():
         models = models_by_layer.get(layer)
         if not models or models[0] is None:
             continue
         bias_model = models[1] if len(models) > 1 else None
-        setattr(out, name, _replace(layer, models[0], bias_model, sparse))
+        setattr(out, name, _trainable(layer, models[0], bias_model) if trainable else _replace(layer, models[0], bias_model, sparse))
     return out
 
 
@@ -331,7 +444,7 @@ def compressed_nbytes(network: nn.Module) -> int:
     layers = network.get_config().values() if hasattr(network, "get_config") else [network]
     total = 0
     for layer in layers:
-        if isinstance(layer, (_CodebookLayer, _SparseCodebookLayer)):
+        if isinstance(layer, (_CodebookLayer, _SparseCodebookLayer, _TrainableCodebookLayer)):
             total += layer.nbytes()
         else:
             total += sum(p.numel() * p.element_size() for p in layer.parameters())

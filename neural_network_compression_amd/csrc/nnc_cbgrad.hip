@@ -1,0 +1,755 @@
+// nnc_cbgrad.hip -- the backward pass of the codebook matmul (nnc_cbmm.hip) from the codebook and the indices, W never decoded
+// (include/nnc.h, nnc_cbmm_dx_f32 / nnc_cbmm_dc_f32).  W[i, o] = c[L[i, o]], y = x @ W, g = dL/dy:
+//
+//   dx[r, i] = sum_o g[r, o] * c[L[i, o]]                      a codebook matmul against W^T, read from the same row-major indices
+//   dc[k]    = sum_{(i, o): L[i, o] = k} sum_r x[r, i] * g[r, o]  x^T g binned by index as it is formed; no kdim x ncols dW is written
+//
+//   k_cbdx_stream  m <= 16.  A workgroup owns 64 lanes x E columns of g (held in registers) and a group of label rows; a wave takes one
+//                  row i at a time (CB_UNROLL rows in flight, the loads of k_cbmm_stream), looks the centres up in the per-bank LDS
+//                  table and reduces its m partials over the 64 lanes in a fixed order.  Column blocks are the splits: their partials
+//                  are summed in block order by k_cbgrad_reduce.
+//   k_cbdx_tiled   m > 16.  128 (r) x 128 (i) output tiles; the W^T tile (128 rows i x TB_K columns o) is decoded into LDS from the
+//                  row-major indices, then the register-blocked FMA of k_cbmm_tiled.  ncols is split by a count that depends on the
+//                  shape alone; the partials go through k_cbgrad_reduce.
+//   k_cbdc_stream  m <= 16.  A lane holds g[0..m-1, o] for its columns; x[r, i] is broadcast by v_readlane; dW[i, o] is formed in
+//                  float32 with r ascending and binned at once.
+//   k_cbdc_tiled   m > 16.  128 (i) x 128 (o) tiles of x^T g, the reduction over m split by a count that depends on the shape alone.
+//   Binning: every dW (or every m-split's partial) becomes rint(v * 2^S) in int64 and is added into K LDS bins (replicated across
+//   banks) with integer atomics, then into a global int64[K] with integer atomics: exact, so the result depends on the shape and the
+//   data only.  S = 62 - ceil(log2(terms)) - P, 2^P > m * max|x| * max|g|, terms = kdim * ncols * splits; max|x| and max|g| come
+//   from k_cbgrad_absmax on the device, the dc kernel derives S itself and writes it next to the sums, and k_cbdc_finish writes
+//   dc = ldexp(sum, -S).  No host read anywhere.
+// An index >= K reads 0 in dx and falls into no bin in dc, as in the forward pass.  No float atomics.
+#include "nnc_cbmm.hpp"
+
+#define CBG_FLAG_OK 0
+#define CBG_FLAG_NONFINITE 1   // x or g holds Inf / NaN, or m * max|x| * max|g| >= 2^127: dc is NaN
+#define CBG_FLAG_ZERO 2        // max|x| or max|g| is 0: every dW is 0
+#define CBG_HDR_BYTES 64       // dc workspace: {max|x| bits, max|g| bits, S, flag} then int64 sums[K] at byte 64
+
+// ------------------------------------------------------------------ plans (host)
+struct CgPlan {
+    int path;                 // NNC_CBMM_NONE / _STREAM / _TILED / _ZERO
+    int vb, mt;               // stream: bytes per lane per row, rows of m per launch (a power of two >= m)
+    int entries, cshift;      // dx stream: the LDS codebook (entries x (1 << cshift) copies); tiled: k + 1 entries
+    int rlog2;                // dc: 1 << rlog2 copies of every LDS bin
+    int aligned;
+    long long col_tiles, row_tiles;   // stream: column blocks x row groups; tiled: tiles
+    long long splits, per_split;      // dx: splits of ncols (columns per split); dc: splits of m (rows of m per split)
+    long long rows_per_group;         // stream: label rows per workgroup
+    int terms_log2;                   // dc: ceil(log2(kdim * ncols * splits))
+    long long lds;
+};
+
+static int mt_of(long long m) { return m <= 1 ? 1 : (m <= 2 ? 2 : (m <= 4 ? 4 : (m <= 8 ? 8 : 16))); }
+
+static int ceil_log2(long long v)
+{
+    int l = 0;
+    while (l < 62 && (1LL << l) < v) ++l;
+    return l;
+}
+
+// the stream geometry both directions share: a column block of 64 lanes x E labels, row groups for two workgroups per CU
+static void cg_stream_grid(CgPlan &p, long long m, long long kdim, long long ncols, int lb, int cus, uintptr_t labels)
+{
+    cus = std::max(1, std::min(cus, CB_PLAN_CUS));
+    p.path = NNC_CBMM_STREAM;
+    p.mt = mt_of(m);
+    p.vb = std::min(16, (64 / p.mt) * lb);
+    p.col_tiles = cdiv(ncols, 64LL * (p.vb / lb));
+    const long long groups = std::max(1LL, std::min(cdiv(2LL * cus, p.col_tiles), cdiv(kdim, (long long)CB_WAVES * CB_UNROLL)));
+    p.rows_per_group = cdiv(kdim, groups);
+    p.row_tiles = cdiv(kdim, p.rows_per_group);
+    p.aligned = labels % p.vb == 0 && (ncols * lb) % p.vb == 0;
+}
+
+static CgPlan dx_plan(long long m, long long kdim, long long ncols, int lb, int k, int cus, uintptr_t labels)
+{
+    CgPlan p{};
+    if (m == 0 || kdim == 0) return p;                       // NNC_CBMM_NONE: dx is empty
+    if (ncols == 0) {                                        // dx = 0
+        p.path = NNC_CBMM_ZERO;
+        return p;
+    }
+    if (m <= CB_SKINNY_M) {
+        cg_stream_grid(p, m, kdim, ncols, lb, cus, labels);
+        p.splits = p.col_tiles;                              // one split per column block
+        p.per_split = 64LL * (p.vb / lb);
+        if (lb == 1) {
+            p.entries = 256;
+            p.cshift = __builtin_ctz(CB_U8_COPIES);
+        } else {
+            p.entries = k + 1;
+            while ((1 << p.cshift) < CB_U8_COPIES && (long long)p.entries << (p.cshift + 1) <= CB_U16_WORDS) ++p.cshift;
+        }
+        p.lds = ((long long)p.entries << p.cshift) * 4 + (long long)p.entries * 4;
+    } else {
+        p.path = NNC_CBMM_TILED;
+        p.col_tiles = cdiv(kdim, TB_N);
+        p.row_tiles = cdiv(m, TB_M);
+        long long s = std::min({cdiv(2LL * CB_PLAN_CUS, p.col_tiles * p.row_tiles), ncols / (16 * TB_K), 16LL});
+        s = std::max(1LL, s);
+        p.per_split = cdiv(ncols, s);
+        p.splits = cdiv(ncols, p.per_split);
+        p.entries = k + 1;
+        p.lds = (long long)(TB_K * TB_M + TB_K * TB_N + k + 1) * 4;
+    }
+    return p;
+}
+
+static int dc_rlog2(int k) { return k <= 64 ? 5 : (k <= 256 ? 3 : 1); }   // as k_centroid_grad: K x copies x 8 B <= 16.3 KiB
+
+static CgPlan dc_plan(long long m, long long kdim, long long ncols, int lb, int k, int cus, uintptr_t labels)
+{
+    CgPlan p{};
+    if (m == 0 || kdim == 0 || ncols == 0) {                 // no terms: dc = 0
+        p.path = NNC_CBMM_ZERO;
+        return p;
+    }
+    p.rlog2 = dc_rlog2(k);
+    const long long bins = ((long long)k << p.rlog2) * 8;
+    if (m <= CB_SKINNY_M) {
+        cg_stream_grid(p, m, kdim, ncols, lb, cus, labels);
+        p.splits = 1;
+        p.per_split = m;
+        p.lds = bins;
+    } else {
+        p.path = NNC_CBMM_TILED;
+        p.col_tiles = cdiv(ncols, TB_N);
+        p.row_tiles = cdiv(kdim, TB_M);
+        long long s = std::min({cdiv(2LL * CB_PLAN_CUS, p.col_tiles * p.row_tiles), m / (16 * TB_K), 16LL});
+        s = std::max(1LL, s);
+        p.per_split = cdiv(m, s);
+        p.splits = cdiv(m, p.per_split);
+        p.lds = (long long)(TB_K * TB_M + TB_K * TB_N) * 4 + bins;
+    }
+    p.terms_log2 = ceil_log2(kdim * ncols * p.splits);
+    return p;
+}
+
+static int64_t dx_ws_bytes(const CgPlan &p, long long m, long long kdim) { return p.splits > 1 ? (int64_t)p.splits * m * kdim * 4 : 0; }
+static int64_t dc_ws_bytes(const CgPlan &p, int k) { return p.path == NNC_CBMM_STREAM || p.path == NNC_CBMM_TILED ? CBG_HDR_BYTES + 8LL * k : 0; }
+
+// ------------------------------------------------------------------ device helpers
+// The m partials of every lane summed over the wave: a reduce-scatter (at lane bit 32 >> t the lanes with the bit set keep the upper
+// half of the rows they hold and take their partner's; then the rest of the butterfly on one value).  N + log2(64 / N) shuffles
+// instead of 6 N; every pair adds in a fixed order, so the sum depends on the data only.  Returns the total of row `row`, the
+// same on every lane of a group of 64 / N lanes.
+template <int N>
+__device__ __forceinline__ float wave_reduce_rows(float (&v)[N], int lane, int &row)
+{
+    row = 0;
+#pragma unroll
+    for (int t = 0; (N >> t) > 1; ++t) {
+        const int half = N >> (t + 1), bit = 32 >> t;
+        const bool up = (lane & bit) != 0;
+#pragma unroll
+        for (int j = 0; j < half; ++j) {
+            const float send = up ? v[j] : v[j + half];
+            const float keep = up ? v[j + half] : v[j];
+            v[j] = keep + __shfl_xor(send, bit);
+        }
+        row += up ? half : 0;
+    }
+    float s = v[0];
+#pragma unroll
+    for (int bit = 64 / N / 2; bit >= 1; bit >>= 1) s += __shfl_xor(s, bit);
+    return s;
+}
+
+// S of the dc sums from the maxima k_cbgrad_absmax left (uniform over the launch); flag as CBG_FLAG_*
+__device__ __forceinline__ int cbdc_shift(const uint32_t *amax, long long m, int terms_log2, int &flag)
+{
+    const uint32_t ux = amax[0], ug = amax[1];
+    flag = CBG_FLAG_OK;
+    if (ux >= 0x7F800000u || ug >= 0x7F800000u) {
+        flag = CBG_FLAG_NONFINITE;
+        return 0;
+    }
+    const double bound = (double)m * (double)__uint_as_float(ux) * (double)__uint_as_float(ug);
+    if (!(bound > 0.0)) {
+        flag = CBG_FLAG_ZERO;
+        return 0;
+    }
+    int P = 0;
+    (void)frexp(bound, &P);   // bound = f * 2^P, f in [0.5, 1): 2^P > bound
+    if (P > 127) {
+        flag = CBG_FLAG_NONFINITE;
+        return 0;
+    }
+    return 62 - terms_log2 - P;
+}
+
+// the fixed-point image of one dW: exact scaling by 2^S (|v * 2^S| < 2^63), nearest integer, ties to even
+__device__ __forceinline__ unsigned long long cbdc_fix(float v, int S) { return (unsigned long long)(long long)rintf(ldexpf(v, S)); }
+
+// the workgroup's bins into the global sums (integer atomics), copies summed in order; zero bins are skipped
+__device__ __forceinline__ void cbdc_flush(const unsigned long long *bins, int k, int rlog2, unsigned long long *__restrict__ sums)
+{
+    __syncthreads();
+    const int R = 1 << rlog2;
+    for (int j = threadIdx.x; j < k; j += blockDim.x) {
+        unsigned long long s = 0;
+        for (int r = 0; r < R; ++r) s += bins[(j << rlog2) + r];
+        if (s) atomicAdd(&sums[j], s);
+    }
+}
+
+// ------------------------------------------------------------------ max |x|, max |g|
+// amax[0] = bits of max |x|, amax[1] = bits of max |g| (zeroed by the caller).  |v| as a bit pattern orders as the value; a NaN
+// orders above Inf, so amax >= 0x7F800000 means "not finite".
+__global__ __launch_bounds__(256) void k_cbgrad_absmax(const float *__restrict__ x, long long nx, const float *__restrict__ g, long long ng,
+                                                       uint32_t *__restrict__ amax)
+{
+    __shared__ uint32_t wmax[2][4];
+    uint32_t a = 0, b = 0;
+    const long long tid = (long long)blockIdx.x * blockDim.x + threadIdx.x, nth = (long long)gridDim.x * blockDim.x;
+    for (long long i = tid; i < nx; i += nth) a = std::max(a, __float_as_uint(x[i]) & 0x7FFFFFFFu);
+    for (long long i = tid; i < ng; i += nth) b = std::max(b, __float_as_uint(g[i]) & 0x7FFFFFFFu);
+#pragma unroll
+    for (int bit = 32; bit >= 1; bit >>= 1) {
+        a = std::max(a, (uint32_t)__shfl_xor((int)a, bit));
+        b = std::max(b, (uint32_t)__shfl_xor((int)b, bit));
+    }
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    if (lane == 0) {
+        wmax[0][wave] = a;
+        wmax[1][wave] = b;
+    }
+    __syncthreads();
+    if (threadIdx.x < 2) {
+        uint32_t v = 0;
+        for (int w = 0; w < (int)(blockDim.x >> 6); ++w) v = std::max(v, wmax[threadIdx.x][w]);
+        if (v) atomicMax(&amax[threadIdx.x], v);
+    }
+}
+
+// ------------------------------------------------------------------ dx, m <= 16
+// grid (column blocks, row groups), CB_THREADS threads.  out: dx (one column block) or the partials [block][m][kdim].
+template <typename LT, int VB, int MT, bool ALIGNED>
+__global__ __launch_bounds__(CB_THREADS) void k_cbdx_stream(const float *__restrict__ g, int m, long long kdim, const unsigned char *__restrict__ labels,
+                                                            long long ncols, const float *__restrict__ centers, int k, int entries, int cshift,
+                                                            long long rows_per_group, int direct, float *__restrict__ out)
+{
+    constexpr int LB = sizeof(LT), E = VB / LB, N = VB / 4, PER = 32 / (8 * LB);
+    extern __shared__ float smem[];
+    float *cb = smem;
+    float *stage = smem + (entries << cshift);
+    cb_fill(cb, stage, centers, k, entries, cshift);
+
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const long long c0 = (long long)blockIdx.x * (64 * E) + lane * E;
+    const bool active = c0 < ncols;
+    const int ne = (int)std::max(0LL, std::min((long long)E, ncols - c0));   // the lane's columns inside the matrix
+    float gv[MT][E];
+#pragma unroll
+    for (int r = 0; r < MT; ++r)
+#pragma unroll
+        for (int e = 0; e < E; ++e) gv[r][e] = (r < m && e < ne) ? g[(long long)r * ncols + c0 + e] : 0.0f;
+
+    const long long g_lo = (long long)blockIdx.y * rows_per_group, g_hi = std::min(kdim, g_lo + rows_per_group);
+    const long long per_wave = (g_hi - g_lo + CB_WAVES - 1) / CB_WAVES;
+    const long long i0 = std::min(g_hi, g_lo + wave * per_wave), i1 = std::min(g_hi, i0 + per_wave);
+    const uintptr_t base = reinterpret_cast<uintptr_t>(labels);
+    const long long row_bytes = ncols * LB;
+    const long long lane_off = (long long)blockIdx.x * (64 * VB) + lane * VB;
+    float *dst = direct ? out : out + (long long)blockIdx.x * m * kdim;
+    __syncthreads();
+
+    auto row_words = [&](long long i, uint32_t *w, uint32_t &s) {
+        const uintptr_t row = base + (uintptr_t)(i * row_bytes);
+        if constexpr (ALIGNED) {
+            s = 0;
+            load_chunk<VB>(reinterpret_cast<const unsigned char *>(active ? row + lane_off : row), w);
+        } else {
+            const uintptr_t first = row & ~(uintptr_t)(VB - 1);
+            s = (uint32_t)(__builtin_amdgcn_readfirstlane((uint32_t)((row + blockIdx.x * (64 * VB)) & (VB - 1))));
+            const uintptr_t a = ((row + lane_off) & ~(uintptr_t)(VB - 1));
+            const uintptr_t a0 = active ? a : first;
+            const uintptr_t a1 = (active && a + VB < row + row_bytes) ? a + VB : a0;
+            load_chunk<VB>(reinterpret_cast<const unsigned char *>(a0), w);
+            load_chunk<VB>(reinterpret_cast<const unsigned char *>(a1), w + N);
+        }
+    };
+    auto consume = [&](const uint32_t *w, uint32_t s, long long i) {
+        uint32_t o[N];
+        if constexpr (ALIGNED) {
+#pragma unroll
+            for (int d = 0; d < N; ++d) o[d] = w[d];
+        } else {
+            funnel<N>(w, s, o);
+        }
+        float p[MT];
+#pragma unroll
+        for (int r = 0; r < MT; ++r) p[r] = 0.0f;
+#pragma unroll
+        for (int e = 0; e < E; ++e) {
+            const uint32_t l = (o[e / PER] >> (8 * LB * (e % PER))) & (LB == 1 ? 0xFFu : 0xFFFFu);
+            const float wv = e < ne ? cb[CbTable<LT>::index(l, k, cshift, lane)] : 0.0f;   // (columns past the row: no Inf * 0)
+#pragma unroll
+            for (int r = 0; r < MT; ++r) p[r] = __builtin_fmaf(gv[r][e], wv, p[r]);
+        }
+        int row;
+        const float v = wave_reduce_rows<MT>(p, lane, row);
+        if ((lane & (64 / MT - 1)) == 0 && row < m) dst[(long long)row * kdim + i] = v;
+    };
+
+    constexpr int WN = ALIGNED ? N : 2 * N;
+    long long i = i0;
+    for (; i + CB_UNROLL <= i1; i += CB_UNROLL) {
+        uint32_t w[CB_UNROLL][WN], s[CB_UNROLL];
+#pragma unroll
+        for (int u = 0; u < CB_UNROLL; ++u) row_words(i + u, w[u], s[u]);
+#pragma unroll
+        for (int u = 0; u < CB_UNROLL; ++u) consume(w[u], s[u], i + u);
+    }
+    for (; i < i1; ++i) {
+        uint32_t w[WN], s;
+        row_words(i, w, s);
+        consume(w, s, i);
+    }
+}
+
+// ------------------------------------------------------------------ dx, m > 16
+// grid (kdim tiles * m tiles, splits of ncols), 256 threads; thread (tx, ty) owns rows ty*8.. (of g) and columns tx*8.. (i) of the tile.
+template <typename LT>
+__global__ __launch_bounds__(256) void k_cbdx_tiled(const float *__restrict__ g, long long m, long long kdim, const LT *__restrict__ labels, long long ncols,
+                                                    const float *__restrict__ centers, int k, long long col_tiles, long long cols_per_split, int direct,
+                                                    float *__restrict__ out)
+{
+    extern __shared__ float smem[];
+    float *gs = smem;                      // [TB_K][TB_M]: g[m0 + r, o]
+    float *ws = gs + TB_K * TB_M;          // [TB_K][TB_N]: W^T[o, n0 + i] = c[L[n0 + i, o]]
+    float *cb = ws + TB_K * TB_N;          // k + 1 entries (entry k = 0)
+    for (int j = threadIdx.x; j <= k; j += 256) cb[j] = j < k ? centers[j] : 0.0f;
+
+    const int t = threadIdx.x, tx = t & 15, ty = t >> 4;
+    const long long n0 = (blockIdx.x % col_tiles) * TB_N, m0 = (blockIdx.x / col_tiles) * TB_M;
+    const long long o_lo = (long long)blockIdx.y * cols_per_split, o_hi = std::min(ncols, o_lo + cols_per_split);
+    float acc[8][8];
+#pragma unroll
+    for (int a = 0; a < 8; ++a)
+#pragma unroll
+        for (int b = 0; b < 8; ++b) acc[a][b] = 0.0f;
+
+    const int lr = t >> 1, lo = (t & 1) * 4;   // g tile: row lr, o lo..lo+3; W^T tile: index row n0 + lr, o lo..lo+3
+    for (long long ob = o_lo; ob < o_hi; ob += TB_K) {
+        __syncthreads();
+        {
+            const long long gr = m0 + lr, wi = n0 + lr;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const long long go = ob + lo + j;
+                const bool in_o = go < o_hi;
+                gs[(lo + j) * TB_M + lr] = (gr < m && in_o) ? g[gr * ncols + go] : 0.0f;
+                ws[(lo + j) * TB_N + lr] = (wi < kdim && in_o) ? cb[std::min((uint32_t)labels[wi * ncols + go], (uint32_t)k)] : 0.0f;
+            }
+        }
+        __syncthreads();
+        tb_tile_fma(gs, ws, tx, ty, acc);
+    }
+    float *dst = direct ? out : out + (long long)blockIdx.y * m * kdim;
+#pragma unroll
+    for (int a = 0; a < 8; ++a) {
+        const long long r = m0 + ty * 8 + a;
+#pragma unroll
+        for (int b = 0; b < 8; ++b) {
+            const long long c = n0 + tx * 8 + b;
+            if (r < m && c < kdim) dst[r * kdim + c] = acc[a][b];
+        }
+    }
+}
+
+// ------------------------------------------------------------------ the split partials, summed in split order
+__global__ __launch_bounds__(256) void k_cbgrad_reduce(const float *__restrict__ part, long long splits, long long mn, float *__restrict__ out)
+{
+    for (long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x; idx < mn; idx += (long long)gridDim.x * blockDim.x) {
+        float v = part[idx];
+        for (long long s = 1; s < splits; ++s) v += part[s * mn + idx];
+        out[idx] = v;
+    }
+}
+
+// ------------------------------------------------------------------ dc, m <= 16
+// grid (column blocks, row groups), CB_THREADS threads.  LDS: the bins, [k][1 << rlog2] int64.
+template <typename LT, int VB, int MT, bool ALIGNED>
+__global__ __launch_bounds__(CB_THREADS) void k_cbdc_stream(const float *__restrict__ x, const float *__restrict__ g, int m, long long kdim,
+                                                            const unsigned char *__restrict__ labels, long long ncols, int k, int rlog2, int terms_log2,
+                                                            long long rows_per_group, uint32_t *__restrict__ hdr, unsigned long long *__restrict__ sums)
+{
+    constexpr int LB = sizeof(LT), E = VB / LB, N = VB / 4, PER = 32 / (8 * LB);
+    extern __shared__ unsigned long long bins[];
+    int flag;
+    const int S = cbdc_shift(hdr, m, terms_log2, flag);
+    if (blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0) {
+        hdr[2] = (uint32_t)S;
+        hdr[3] = (uint32_t)flag;
+    }
+    if (flag != CBG_FLAG_OK) return;   // (uniform over the launch)
+    for (int j = threadIdx.x; j < (k << rlog2); j += CB_THREADS) bins[j] = 0ull;
+
+    const int lane = threadIdx.x & 63;
+    const int rep = lane & ((1 << rlog2) - 1);
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const long long c0 = (long long)blockIdx.x * (64 * E) + lane * E;
+    const bool active = c0 < ncols;
+    const int ne = (int)std::max(0LL, std::min((long long)E, ncols - c0));
+    float gv[MT][E];
+#pragma unroll
+    for (int r = 0; r < MT; ++r)
+#pragma unroll
+        for (int e = 0; e < E; ++e) gv[r][e] = (r < m && e < ne) ? g[(long long)r * ncols + c0 + e] : 0.0f;
+
+    const long long g_lo = (long long)blockIdx.y * rows_per_group, g_hi = std::min(kdim, g_lo + rows_per_group);
+    const long long per_wave = (g_hi - g_lo + CB_WAVES - 1) / CB_WAVES;
+    const long long i0 = std::min(g_hi, g_lo + wave * per_wave), i1 = std::min(g_hi, i0 + per_wave);
+    const uintptr_t base = reinterpret_cast<uintptr_t>(labels);
+    const long long row_bytes = ncols * LB;
+    const long long lane_off = (long long)blockIdx.x * (64 * VB) + lane * VB;
+    __syncthreads();
+
+    auto row_words = [&](long long i, uint32_t *w, uint32_t &s) {
+        const uintptr_t row = base + (uintptr_t)(i * row_bytes);
+        if constexpr (ALIGNED) {
+            s = 0;
+            load_chunk<VB>(reinterpret_cast<const unsigned char *>(active ? row + lane_off : row), w);
+        } else {
+            const uintptr_t first = row & ~(uintptr_t)(VB - 1);
+            s = (uint32_t)(__builtin_amdgcn_readfirstlane((uint32_t)((row + blockIdx.x * (64 * VB)) & (VB - 1))));
+            const uintptr_t a = ((row + lane_off) & ~(uintptr_t)(VB - 1));
+            const uintptr_t a0 = active ? a : first;
+            const uintptr_t a1 = (active && a + VB < row + row_bytes) ? a + VB : a0;
+            load_chunk<VB>(reinterpret_cast<const unsigned char *>(a0), w);
+            load_chunk<VB>(reinterpret_cast<const unsigned char *>(a1), w + N);
+        }
+    };
+    // x[r, i + u] of a batch of U rows: lane f holds value f = r * U + u (and f + 64), broadcast by v_readlane (as k_cbmm_stream)
+    auto load_x = [&](long long i, int U, float &xa, float &xb) {
+        const int f0 = lane, f1 = lane + 64;
+        const int r0 = f0 / U, r1 = f1 / U;
+        xa = r0 < m ? x[(long long)r0 * kdim + i + f0 % U] : 0.0f;
+        xb = (MT * CB_UNROLL > 64 && r1 < m) ? x[(long long)r1 * kdim + i + f1 % U] : 0.0f;
+    };
+    auto consume = [&](const uint32_t *w, uint32_t s, float xa, float xb, int u, int U) {
+        float xv[MT];
+#pragma unroll
+        for (int r = 0; r < MT; ++r) {
+            const int f = r * U + u;
+            xv[r] = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, f < 64 ? xa : xb), f & 63));
+        }
+        uint32_t o[N];
+        if constexpr (ALIGNED) {
+#pragma unroll
+            for (int d = 0; d < N; ++d) o[d] = w[d];
+        } else {
+            funnel<N>(w, s, o);
+        }
+#pragma unroll
+        for (int e = 0; e < E; ++e) {
+            const uint32_t l = (o[e / PER] >> (8 * LB * (e % PER))) & (LB == 1 ? 0xFFu : 0xFFFFu);
+            float d = 0.0f;
+#pragma unroll
+            for (int r = 0; r < MT; ++r) d = __builtin_fmaf(xv[r], gv[r][e], d);   // dW[i, o], r ascending
+            if (e < ne && l < (uint32_t)k) atomicAdd(&bins[(l << rlog2) + rep], cbdc_fix(d, S));
+        }
+    };
+
+    constexpr int WN = ALIGNED ? N : 2 * N;
+    long long i = i0;
+    for (; i + CB_UNROLL <= i1; i += CB_UNROLL) {
+        uint32_t w[CB_UNROLL][WN], s[CB_UNROLL];
+        float xa, xb;
+#pragma unroll
+        for (int u = 0; u < CB_UNROLL; ++u) row_words(i + u, w[u], s[u]);
+        load_x(i, CB_UNROLL, xa, xb);
+#pragma unroll
+        for (int u = 0; u < CB_UNROLL; ++u) consume(w[u], s[u], xa, xb, u, CB_UNROLL);
+    }
+    for (; i < i1; ++i) {
+        uint32_t w[WN], s;
+        float xa, xb;
+        row_words(i, w, s);
+        load_x(i, 1, xa, xb);
+        consume(w, s, xa, xb, 0, 1);
+    }
+    cbdc_flush(bins, k, rlog2, sums);
+}
+
+// ------------------------------------------------------------------ dc, m > 16
+// grid (ncols tiles * kdim tiles, splits of m), 256 threads; thread (tx, ty) forms dW for index rows ty*8.. and columns tx*8.. of the
+// 128 x 128 tile over its split's rows of m, then bins the 64 values.
+template <typename LT>
+__global__ __launch_bounds__(256) void k_cbdc_tiled(const float *__restrict__ x, const float *__restrict__ g, long long m, long long kdim,
+                                                    const LT *__restrict__ labels, long long ncols, int k, int rlog2, int terms_log2, long long col_tiles,
+                                                    long long rows_per_split, uint32_t *__restrict__ hdr, unsigned long long *__restrict__ sums)
+{
+    extern __shared__ float smem[];
+    float *xs = smem;                      // [TB_K][TB_M]: x[r, i0 + i]
+    float *gs = xs + TB_K * TB_M;          // [TB_K][TB_N]: g[r, o0 + o]
+    unsigned long long *bins = reinterpret_cast<unsigned long long *>(gs + TB_K * TB_N);
+    int flag;
+    const int S = cbdc_shift(hdr, m, terms_log2, flag);
+    if (blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0) {
+        hdr[2] = (uint32_t)S;
+        hdr[3] = (uint32_t)flag;
+    }
+    if (flag != CBG_FLAG_OK) return;
+    for (int j = threadIdx.x; j < (k << rlog2); j += 256) bins[j] = 0ull;
+
+    const int t = threadIdx.x, tx = t & 15, ty = t >> 4;
+    const long long o0 = (blockIdx.x % col_tiles) * TB_N, i0 = (blockIdx.x / col_tiles) * TB_M;
+    const long long r_lo = (long long)blockIdx.y * rows_per_split, r_hi = std::min(m, r_lo + rows_per_split);
+    float acc[8][8];
+#pragma unroll
+    for (int a = 0; a < 8; ++a)
+#pragma unroll
+        for (int b = 0; b < 8; ++b) acc[a][b] = 0.0f;
+
+    const int lk = t >> 5, lc = (t & 31) * 4;   // both tiles: row r = rb + lk, columns lc..lc+3 (coalesced)
+    for (long long rb = r_lo; rb < r_hi; rb += TB_K) {
+        __syncthreads();
+        {
+            const long long r = rb + lk;
+            const bool in_r = r < r_hi;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const long long ii = i0 + lc + j, oo = o0 + lc + j;
+                xs[lk * TB_M + lc + j] = (in_r && ii < kdim) ? x[r * kdim + ii] : 0.0f;
+                gs[lk * TB_N + lc + j] = (in_r && oo < ncols) ? g[r * ncols + oo] : 0.0f;
+            }
+        }
+        __syncthreads();
+        tb_tile_fma(xs, gs, tx, ty, acc);
+    }
+    const int rep = t & ((1 << rlog2) - 1);
+#pragma unroll
+    for (int a = 0; a < 8; ++a) {
+        const long long i = i0 + ty * 8 + a;
+#pragma unroll
+        for (int b = 0; b < 8; ++b) {
+            const long long o = o0 + tx * 8 + b;
+            if (i >= kdim || o >= ncols) continue;
+            const uint32_t l = (uint32_t)labels[i * ncols + o];
+            if (l < (uint32_t)k) atomicAdd(&bins[(l << rlog2) + rep], cbdc_fix(acc[a][b], S));
+        }
+    }
+    cbdc_flush(bins, k, rlog2, sums);
+}
+
+// ------------------------------------------------------------------ dc = ldexp(sum, -S)
+__global__ __launch_bounds__(256) void k_cbdc_finish(const uint32_t *__restrict__ hdr, const long long *__restrict__ sums, int k, int f64, void *__restrict__ out)
+{
+    const int S = (int)hdr[2], flag = (int)hdr[3];
+    for (int j = blockIdx.x * blockDim.x + threadIdx.x; j < k; j += gridDim.x * blockDim.x) {
+        const double v = flag == CBG_FLAG_NONFINITE ? __builtin_nan("") : ldexp((double)sums[j], -S);
+        if (f64) reinterpret_cast<double *>(out)[j] = v;
+        else reinterpret_cast<float *>(out)[j] = (float)v;
+    }
+}
+
+// ------------------------------------------------------------------ C ABI
+static int cg_check(const char *fn, int64_t m, int64_t kdim, int64_t ncols, int label_bytes, int32_t k)
+{
+    const std::string f(fn);
+    if (m < 0 || kdim < 0 || ncols < 0) return fail(NNC_EINVAL, f + ": negative size");
+    if (label_bytes != 1 && label_bytes != 2) return fail(NNC_EINVAL, f + ": label_bytes must be 1 or 2");
+    if (k < 1 || k > NNC_KMAX) return fail(NNC_EINVAL, f + ": k outside 1..NNC_KMAX");
+    if (label_bytes == 1 && k > 256) return fail(NNC_EINVAL, f + ": k > 256 needs 2-byte labels");
+    if (m > (1LL << 40) || kdim > (1LL << 40) || ncols > (1LL << 40)) return fail(NNC_EINVAL, f + ": size too large");
+    if (m > 0 && kdim > 0 && ncols > 0 && (kdim > (1LL << 62) / ncols || kdim * ncols > (1LL << 62) / (16 * TB_K)))
+        return fail(NNC_EINVAL, f + ": kdim * ncols too large");
+    return NNC_OK;
+}
+
+template <typename LT, int VB, int MT>
+static void launch_dx_stream(bool aligned, dim3 grid, size_t lds, hipStream_t s, const float *g, int m, long long kdim, const void *labels, long long ncols,
+                             const float *centers, int k, int entries, int cshift, long long rpg, int direct, float *out)
+{
+    const unsigned char *lab = reinterpret_cast<const unsigned char *>(labels);
+    if (aligned)
+        hipLaunchKernelGGL((k_cbdx_stream<LT, VB, MT, true>), grid, dim3(CB_THREADS), lds, s, g, m, kdim, lab, ncols, centers, k, entries, cshift, rpg, direct, out);
+    else
+        hipLaunchKernelGGL((k_cbdx_stream<LT, VB, MT, false>), grid, dim3(CB_THREADS), lds, s, g, m, kdim, lab, ncols, centers, k, entries, cshift, rpg, direct, out);
+}
+
+template <typename LT, int VB, int MT>
+static void launch_dc_stream(bool aligned, dim3 grid, size_t lds, hipStream_t s, const float *x, const float *g, int m, long long kdim, const void *labels,
+                             long long ncols, int k, int rlog2, int tl, long long rpg, uint32_t *hdr, unsigned long long *sums)
+{
+    const unsigned char *lab = reinterpret_cast<const unsigned char *>(labels);
+    if (aligned)
+        hipLaunchKernelGGL((k_cbdc_stream<LT, VB, MT, true>), grid, dim3(CB_THREADS), lds, s, x, g, m, kdim, lab, ncols, k, rlog2, tl, rpg, hdr, sums);
+    else
+        hipLaunchKernelGGL((k_cbdc_stream<LT, VB, MT, false>), grid, dim3(CB_THREADS), lds, s, x, g, m, kdim, lab, ncols, k, rlog2, tl, rpg, hdr, sums);
+}
+
+// every stream instantiation there is; the plans are checked against this table, and the launches go through it
+using DxLaunch = void (*)(bool, dim3, size_t, hipStream_t, const float *, int, long long, const void *, long long, const float *, int, int, int, long long,
+                          int, float *);
+using DcLaunch = void (*)(bool, dim3, size_t, hipStream_t, const float *, const float *, int, long long, const void *, long long, int, int, int, long long,
+                          uint32_t *, unsigned long long *);
+struct GradCase {
+    int lb, vb, mt;
+    DxLaunch dx;
+    DcLaunch dc;
+};
+#define GRAD_CASE(LT, LB, VB, MT) {LB, VB, MT, launch_dx_stream<LT, VB, MT>, launch_dc_stream<LT, VB, MT>}
+static const GradCase kGradCases[] = {
+    GRAD_CASE(uint8_t, 1, 16, 1),  GRAD_CASE(uint8_t, 1, 16, 2),  GRAD_CASE(uint8_t, 1, 16, 4),  GRAD_CASE(uint8_t, 1, 8, 8),   GRAD_CASE(uint8_t, 1, 4, 16),
+    GRAD_CASE(uint16_t, 2, 16, 1), GRAD_CASE(uint16_t, 2, 16, 2), GRAD_CASE(uint16_t, 2, 16, 4), GRAD_CASE(uint16_t, 2, 16, 8), GRAD_CASE(uint16_t, 2, 8, 16),
+};
+#undef GRAD_CASE
+
+static const GradCase *find_grad_case(int lb, int vb, int mt)
+{
+    for (const GradCase &c : kGradCases)
+        if (c.lb == lb && c.vb == vb && c.mt == mt) return &c;
+    return nullptr;
+}
+
+static int no_grad_case(const char *fn, int lb, int vb, int mt)
+{
+    return fail(NNC_EINVAL, std::string(fn) + ": no stream instantiation for label_bytes " + std::to_string(lb) + ", vb " + std::to_string(vb) + ", mt " +
+                                std::to_string(mt));
+}
+
+static int plan_out(const char *fn, const CgPlan &p, int lb, int32_t cus, int64_t *out)
+{
+    if (cus < 1) return fail(NNC_EINVAL, std::string(fn) + ": cus < 1");
+    if (!out) return fail(NNC_EINVAL, std::string(fn) + ": out is NULL");
+    if (p.path == NNC_CBMM_STREAM && !find_grad_case(lb, p.vb, p.mt)) return no_grad_case(fn, lb, p.vb, p.mt);
+    return NNC_OK;
+}
+
+extern "C" int64_t nnc_cbmm_dx_workspace_bytes(int64_t m, int64_t kdim, int64_t ncols, int label_bytes)
+{
+    if (cg_check("nnc_cbmm_dx_workspace_bytes", m, kdim, ncols, label_bytes, 1) != NNC_OK) return 0;
+    return dx_ws_bytes(dx_plan(m, kdim, ncols, label_bytes, 1, CB_PLAN_CUS, 0), m, kdim);
+}
+
+extern "C" int nnc_cbmm_dx_plan(int64_t m, int64_t kdim, int64_t ncols, int label_bytes, int32_t k, int32_t cus, uint64_t labels_addr, int64_t *out)
+{
+    int rc = cg_check("nnc_cbmm_dx_plan", m, kdim, ncols, label_bytes, k);
+    if (rc != NNC_OK) return rc;
+    const CgPlan p = dx_plan(m, kdim, ncols, label_bytes, k, cus, (uintptr_t)labels_addr);
+    if ((rc = plan_out("nnc_cbmm_dx_plan", p, label_bytes, cus, out)) != NNC_OK) return rc;
+    const int64_t v[NNC_CBDX_PLAN_LEN] = {p.path, p.vb, p.mt, p.path == NNC_CBMM_STREAM ? 1LL << p.cshift : (p.entries ? 1 : 0), p.entries, p.splits,
+                                          p.per_split, p.aligned, p.lds, p.col_tiles, p.row_tiles, dx_ws_bytes(p, m, kdim)};
+    for (int i = 0; i < NNC_CBDX_PLAN_LEN; ++i) out[i] = v[i];
+    return NNC_OK;
+}
+
+extern "C" int nnc_cbmm_dx_f32(const float *g, int64_t m, int64_t kdim, const void *labels, int label_bytes, int64_t ncols, const float *centers_dev,
+                               int32_t k, float *dx, void *workspace, int64_t workspace_bytes, void *stream)
+{
+    int rc = cg_check("nnc_cbmm_dx_f32", m, kdim, ncols, label_bytes, k);
+    if (rc != NNC_OK) return rc;
+    if (!centers_dev) return fail(NNC_EINVAL, "nnc_cbmm_dx_f32: centers is NULL");
+    if (m > 0 && kdim > 0 && !dx) return fail(NNC_EINVAL, "nnc_cbmm_dx_f32: dx is NULL");
+    if (m > 0 && kdim > 0 && ncols > 0 && (!g || !labels)) return fail(NNC_EINVAL, "nnc_cbmm_dx_f32: g or labels is NULL");
+    if (workspace_bytes < 0) return fail(NNC_EINVAL, "nnc_cbmm_dx_f32: negative workspace size");
+    const int64_t need = nnc_cbmm_dx_workspace_bytes(m, kdim, ncols, label_bytes);
+    if (workspace_bytes < need) return fail(NNC_ENOSPACE, "nnc_cbmm_dx_f32: workspace smaller than nnc_cbmm_dx_workspace_bytes()");
+    if (need > 0 && !workspace) return fail(NNC_EINVAL, "nnc_cbmm_dx_f32: workspace is NULL");
+    const CgPlan p = dx_plan(m, kdim, ncols, label_bytes, k, cu_count(), reinterpret_cast<uintptr_t>(labels));
+    const GradCase *gc = p.path == NNC_CBMM_STREAM ? find_grad_case(label_bytes, p.vb, p.mt) : nullptr;
+    if (p.path == NNC_CBMM_STREAM && !gc) return no_grad_case("nnc_cbmm_dx_f32", label_bytes, p.vb, p.mt);
+    if (p.path == NNC_CBMM_NONE) return NNC_OK;
+
+    hipStream_t s = S(stream);
+    if (p.path == NNC_CBMM_ZERO) {
+        HIPCHK(hipMemsetAsync(dx, 0, (size_t)(m * kdim) * 4, s));
+        return NNC_OK;
+    }
+    const int direct = p.splits == 1;
+    float *out = direct ? dx : reinterpret_cast<float *>(workspace);
+    if (p.path == NNC_CBMM_STREAM) {
+        gc->dx(p.aligned != 0, dim3((unsigned)p.col_tiles, (unsigned)p.row_tiles), (size_t)p.lds, s, g, (int)m, kdim, labels, ncols, centers_dev, k, p.entries,
+               p.cshift, p.rows_per_group, direct, out);
+        LAUNCHCHK("k_cbdx_stream");
+    } else {
+        const dim3 grid((unsigned)(p.col_tiles * p.row_tiles), (unsigned)p.splits);
+        if (label_bytes == 1)
+            hipLaunchKernelGGL(k_cbdx_tiled<uint8_t>, grid, dim3(256), (size_t)p.lds, s, g, (long long)m, (long long)kdim, reinterpret_cast<const uint8_t *>(labels),
+                               (long long)ncols, centers_dev, (int)k, p.col_tiles, p.per_split, direct, out);
+        else
+            hipLaunchKernelGGL(k_cbdx_tiled<uint16_t>, grid, dim3(256), (size_t)p.lds, s, g, (long long)m, (long long)kdim, reinterpret_cast<const uint16_t *>(labels),
+                               (long long)ncols, centers_dev, (int)k, p.col_tiles, p.per_split, direct, out);
+        LAUNCHCHK("k_cbdx_tiled");
+    }
+    if (!direct) {
+        const long long mn = m * kdim;
+        const int rgrid = (int)std::max(1LL, std::min(cdiv(mn, 256), 8192LL));
+        hipLaunchKernelGGL(k_cbgrad_reduce, dim3(rgrid), dim3(256), 0, s, reinterpret_cast<const float *>(workspace), (long long)p.splits, mn, dx);
+        LAUNCHCHK("k_cbgrad_reduce");
+    }
+    return NNC_OK;
+}
+
+extern "C" int64_t nnc_cbmm_dc_workspace_bytes(int64_t m, int64_t kdim, int64_t ncols, int label_bytes, int32_t k)
+{
+    if (cg_check("nnc_cbmm_dc_workspace_bytes", m, kdim, ncols, label_bytes, k) != NNC_OK) return 0;
+    return dc_ws_bytes(dc_plan(m, kdim, ncols, label_bytes, k, CB_PLAN_CUS, 0), k);
+}
+
+extern "C" int nnc_cbmm_dc_plan(int64_t m, int64_t kdim, int64_t ncols, int label_bytes, int32_t k, int32_t cus, uint64_t labels_addr, int64_t *out)
+{
+    int rc = cg_check("nnc_cbmm_dc_plan", m, kdim, ncols, label_bytes, k);
+    if (rc != NNC_OK) return rc;
+    const CgPlan p = dc_plan(m, kdim, ncols, label_bytes, k, cus, (uintptr_t)labels_addr);
+    if ((rc = plan_out("nnc_cbmm_dc_plan", p, label_bytes, cus, out)) != NNC_OK) return rc;
+    const int64_t v[NNC_CBDC_PLAN_LEN] = {p.path, p.vb, p.mt, p.path == NNC_CBMM_ZERO ? 0 : 1LL << p.rlog2, p.splits, p.per_split, p.aligned, p.lds,
+                                          p.col_tiles, p.row_tiles, p.terms_log2, dc_ws_bytes(p, k)};
+    for (int i = 0; i < NNC_CBDC_PLAN_LEN; ++i) out[i] = v[i];
+    return NNC_OK;
+}
+
+extern "C" int nnc_cbmm_dc_f32(const float *x, const float *g, int64_t m, int64_t kdim, const void *labels, int label_bytes, int64_t ncols, int32_t k,
+                               void *dc, int32_t out_f64, void *workspace, int64_t workspace_bytes, void *stream)
+{
+    int rc = cg_check("nnc_cbmm_dc_f32", m, kdim, ncols, label_bytes, k);
+    if (rc != NNC_OK) return rc;
+    if (!dc) return fail(NNC_EINVAL, "nnc_cbmm_dc_f32: dc is NULL");
+    if (m > 0 && kdim > 0 && ncols > 0 && (!x || !g || !labels)) return fail(NNC_EINVAL, "nnc_cbmm_dc_f32: x, g or labels is NULL");
+    if (workspace_bytes < 0) return fail(NNC_EINVAL, "nnc_cbmm_dc_f32: negative workspace size");
+    const int64_t need = nnc_cbmm_dc_workspace_bytes(m, kdim, ncols, label_bytes, k);
+    if (workspace_bytes < need) return fail(NNC_ENOSPACE, "nnc_cbmm_dc_f32: workspace smaller than nnc_cbmm_dc_workspace_bytes()");
+    if (need > 0 && !workspace) return fail(NNC_EINVAL, "nnc_cbmm_dc_f32: workspace is NULL");
+    if (need > 0 && reinterpret_cast<uintptr_t>(workspace) % 8 != 0) return fail(NNC_EINVAL, "nnc_cbmm_dc_f32: workspace not 8-byte aligned");
+    const CgPlan p = dc_plan(m, kdim, ncols, label_bytes, k, cu_count(), reinterpret_cast<uintptr_t>(labels));
+    const GradCase *gc = p.path == NNC_CBMM_STREAM ? find_grad_case(label_bytes, p.vb, p.mt) : nullptr;
+    if (p.path == NNC_CBMM_STREAM && !gc) return no_grad_case("nnc_cbmm_dc_f32", label_bytes, p.vb, p.mt);
+
+    hipStream_t s = S(stream);
+    const size_t esz = out_f64 ? 8 : 4;
+    if (p.path == NNC_CBMM_ZERO) {
+        HIPCHK(hipMemsetAsync(dc, 0, (size_t)k * esz, s));
+        return NNC_OK;
+    }
+    uint32_t *hdr = reinterpret_cast<uint32_t *>(workspace);
+    unsigned long long *sums = reinterpret_cast<unsigned long long *>(reinterpret_cast<char *>(workspace) + CBG_HDR_BYTES);
+    HIPCHK(hipMemsetAsync(workspace, 0, (size_t)need, s));
+    const long long nx = m * kdim, ng = m * ncols;
+    const int agrid = (int)std::max(1LL, std::min(cdiv(std::max(nx, ng), 256 * 8), 4LL * cu_count()));
+    hipLaunchKernelGGL(k_cbgrad_absmax, dim3(agrid), dim3(256), 0, s, x, nx, g, ng, hdr);
+    LAUNCHCHK("k_cbgrad_absmax");
+    if (p.path == NNC_CBMM_STREAM) {
+        gc->dc(p.aligned != 0, dim3((unsigned)p.col_tiles, (unsigned)p.row_tiles), (size_t)p.lds, s, x, g, (int)m, kdim, labels, ncols, k, p.rlog2,
+               p.terms_log2, p.rows_per_group, hdr, sums);
+        LAUNCHCHK("k_cbdc_stream");
+    } else {
+        const dim3 grid((unsigned)(p.col_tiles * p.row_tiles), (unsigned)p.splits);
+        if (label_bytes == 1)
+            hipLaunchKernelGGL(k_cbdc_tiled<uint8_t>, grid, dim3(256), (size_t)p.lds, s, x, g, (long long)m, (long long)kdim,
+                               reinterpret_cast<const uint8_t *>(labels), (long long)ncols, (int)k, p.rlog2, p.terms_log2, p.col_tiles, p.per_split, hdr, sums);
+        else
+            hipLaunchKernelGGL(k_cbdc_tiled<uint16_t>, grid, dim3(256), (size_t)p.lds, s, x, g, (long long)m, (long long)kdim,
+                               reinterpret_cast<const uint16_t *>(labels), (long long)ncols, (int)k, p.rlog2, p.terms_log2, p.col_tiles, p.per_split, hdr, sums);
+        LAUNCHCHK("k_cbdc_tiled");
+    }
+    hipLaunchKernelGGL(k_cbdc_finish, dim3((unsigned)cdiv(k, 256)), dim3(256), 0, s, hdr, reinterpret_cast<const long long *>(sums), (int)k, (int)(out_f64 != 0), dc);
+    LAUNCHCHK("k_cbdc_finish");
+    return NNC_OK;
+}

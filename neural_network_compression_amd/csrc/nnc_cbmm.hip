@@ -85,48 +85,6 @@ static CbPlan cb_plan(long long m, long long kdim, long long ncols, int lb, int 
 
 static int64_t cb_ws_bytes(const CbPlan &p, long long m, long long ncols) { return p.splits > 1 ? (int64_t)p.splits * m * ncols * 4 : 0; }
 
-// ------------------------------------------------------------------ device helpers
-// the table: `entries` values (centers, then zeros), `1 << cshift` copies of each, copy c of entry j at j * copies + c.  The
-// centres come from global memory once per workgroup into `stage`; the copies are made from LDS (a loop of global loads per copy
-// was a chain of L2 round trips in front of every workgroup).
-__device__ __forceinline__ void cb_fill(float *cb, float *stage, const float *__restrict__ centers, int k, int entries, int cshift)
-{
-    for (int j = threadIdx.x; j < entries; j += blockDim.x) stage[j] = j < k ? centers[j] : 0.0f;
-    __syncthreads();
-    const int words = entries << cshift;
-#pragma unroll 8
-    for (int w = threadIdx.x; w < words; w += blockDim.x) cb[w] = stage[w >> cshift];
-}
-
-template <int VB> struct Chunk;
-template <> struct Chunk<4> { using T = uint32_t; };
-template <> struct Chunk<8> { using T = uint2; };
-template <> struct Chunk<16> { using T = uint4; };
-
-template <int VB>
-__device__ __forceinline__ void load_chunk(const unsigned char *p, uint32_t *w)
-{
-    const typename Chunk<VB>::T v = *reinterpret_cast<const typename Chunk<VB>::T *>(p);
-    __builtin_memcpy(w, &v, VB);
-}
-
-// o[d] = bytes [s + 4d, s + 4d + 4) of the 2N-dword window w (s < 4N, uniform over the wave)
-template <int N>
-__device__ __forceinline__ void funnel(const uint32_t *w, uint32_t s, uint32_t *o)
-{
-    const uint32_t q = s >> 2, r = s & 3;
-    uint32_t v[N + 1];
-#pragma unroll
-    for (int d = 0; d <= N; ++d) {
-        uint32_t t = w[d];
-#pragma unroll
-        for (int qq = 1; qq < N; ++qq) t = q == (uint32_t)qq ? w[d + qq] : t;
-        v[d] = t;
-    }
-#pragma unroll
-    for (int d = 0; d < N; ++d) o[d] = __builtin_amdgcn_alignbyte(v[d + 1], v[d], r);
-}
-
 // ------------------------------------------------------------------ skinny: m <= 16
 // grid (col_tiles, splits), CB_THREADS threads.  `out` is y (splits == 1: + bias, ReLU here) or the partials [split][m][ncols].
 template <typename LT, int VB, int MT, bool ALIGNED>

@@ -1,5 +1,6 @@
-// nnc_cbmm.hpp -- what the codebook matmul (nnc_cbmm.hip) and its bitmap-sparse sibling (nnc_cbsp.hip) share: the launch
-// constants, the per-bank LDS codebook layout and the register-blocked FMA step of the tiled kernels.
+// nnc_cbmm.hpp -- what the codebook matmul (nnc_cbmm.hip), its bitmap-sparse sibling (nnc_cbsp.hip) and its backward pass
+// (nnc_cbgrad.hip) share: the launch constants, the per-bank LDS codebook layout, the label-row loads of the stream kernels and the
+// register-blocked FMA step of the tiled kernels.
 #pragma once
 #include "nnc_common.hpp"
 
@@ -44,4 +45,46 @@ __device__ __forceinline__ void tb_tile_fma(const float *xs, const float *ws, in
 #pragma unroll
             for (int b = 0; b < 8; ++b) acc[a][b] = __builtin_fmaf(av[a], bv[b], acc[a][b]);
     }
+}
+
+// ------------------------------------------------------------------ device helpers
+// the table: `entries` values (centers, then zeros), `1 << cshift` copies of each, copy c of entry j at j * copies + c.  The
+// centres come from global memory once per workgroup into `stage`; the copies are made from LDS (a loop of global loads per copy
+// was a chain of L2 round trips in front of every workgroup).
+__device__ __forceinline__ void cb_fill(float *cb, float *stage, const float *__restrict__ centers, int k, int entries, int cshift)
+{
+    for (int j = threadIdx.x; j < entries; j += blockDim.x) stage[j] = j < k ? centers[j] : 0.0f;
+    __syncthreads();
+    const int words = entries << cshift;
+#pragma unroll 8
+    for (int w = threadIdx.x; w < words; w += blockDim.x) cb[w] = stage[w >> cshift];
+}
+
+template <int VB> struct Chunk;
+template <> struct Chunk<4> { using T = uint32_t; };
+template <> struct Chunk<8> { using T = uint2; };
+template <> struct Chunk<16> { using T = uint4; };
+
+template <int VB>
+__device__ __forceinline__ void load_chunk(const unsigned char *p, uint32_t *w)
+{
+    const typename Chunk<VB>::T v = *reinterpret_cast<const typename Chunk<VB>::T *>(p);
+    __builtin_memcpy(w, &v, VB);
+}
+
+// o[d] = bytes [s + 4d, s + 4d + 4) of the 2N-dword window w (s < 4N, uniform over the wave)
+template <int N>
+__device__ __forceinline__ void funnel(const uint32_t *w, uint32_t s, uint32_t *o)
+{
+    const uint32_t q = s >> 2, r = s & 3;
+    uint32_t v[N + 1];
+#pragma unroll
+    for (int d = 0; d <= N; ++d) {
+        uint32_t t = w[d];
+#pragma unroll
+        for (int qq = 1; qq < N; ++qq) t = q == (uint32_t)qq ? w[d + qq] : t;
+        v[d] = t;
+    }
+#pragma unroll
+    for (int d = 0; d < N; ++d) o[d] = __builtin_amdgcn_alignbyte(v[d + 1], v[d], r);
 }

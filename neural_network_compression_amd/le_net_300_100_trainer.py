@@ -6,7 +6,7 @@ from typing import Dict, Tuple
 
 import torch
 
-from .common.trainer import Trainer
+from .common.trainer import Trainer, kernel_l2
 from .neural_networks import LeNet300100
 
 
@@ -26,10 +26,10 @@ class LeNet300100Trainer(Trainer):
         net = self.neural_network
         return {net.dense1: (1, 0.1), net.dense2: (1, 0.1), net.out: (0.5, 0)}
 
-    def _get_error(self, input_data: torch.Tensor, expected_output: torch.Tensor) -> torch.Tensor:
-        logits = self.neural_network(input_data)
+    def _get_error(self, input_data: torch.Tensor, expected_output: torch.Tensor, network: torch.nn.Module | None = None) -> torch.Tensor:
+        net = self.neural_network if network is None else network
+        logits = net(input_data)
         cross_entropy = torch.nn.functional.binary_cross_entropy_with_logits(logits, expected_output)
-        net = self.neural_network
         # tf.nn.l2_loss(w) = sum(w^2) / 2 over the three kernels, weighted 0.01
-        l2 = sum((layer.kernel ** 2).sum() / 2 for layer in (net.dense1, net.dense2, net.out))
+        l2 = sum(kernel_l2(layer) for layer in (net.dense1, net.dense2, net.out))
         return cross_entropy + 0.01 * l2

@@ -329,6 +329,137 @@ def cbmm_plan(m: int, kdim: int, ncols: int, label_bytes: int, k: int, cus: int,
     return dict(zip(nat.CBMM_PLAN_FIELDS, (int(v) for v in out)))
 
 
+def _grad_args(g: torch.Tensor, labels: torch.Tensor, kdim: int, ncols: int, k: int):
+    _require_cuda(g, "g", torch.float32)
+    _require_cuda(labels, "labels")
+    if labels.numel() != kdim * ncols:
+        raise ValueError(f"labels must hold kdim * ncols = {kdim * ncols} indices, got {labels.numel()}")
+    if g.dim() < 1 or g.shape[-1] != ncols:
+        raise ValueError(f"g must have shape (..., {ncols}), got {tuple(g.shape)}")
+    if not 1 <= k <= nat.NNC_KMAX:
+        raise ValueError(f"k = {k} outside 1..{nat.NNC_KMAX}")
+    lead = tuple(g.shape[:-1])
+    return lead, (int(np.prod(lead)) if lead else 1)
+
+
+def codebook_matmul_dx(g: torch.Tensor, labels: torch.Tensor, centers: torch.Tensor, kdim: int, ncols: int) -> torch.Tensor:
+    """dx = g @ W^T with W[i, o] = centers[labels[i * ncols + o]] read from the indices (include/nnc.h, nnc_cbmm_dx_f32): the input
+    gradient of codebook_matmul.  g: float32 (..., ncols); labels, centers as codebook_matmul.  Returns float32 (..., kdim).  Split
+    partials are summed in a fixed order: the same call gives the same bits.  No host read."""
+    kdim, ncols = int(kdim), int(ncols)
+    _require_cuda(centers, "centers", torch.float32)
+    lead, m = _grad_args(g, labels, kdim, ncols, centers.numel())
+    if len({g.device, labels.device, centers.device}) != 1:
+        raise ValueError("g, labels and centers must be on one device")
+    L = nat.load()
+    dx = torch.empty(lead + (kdim,), dtype=torch.float32, device=g.device)
+    lb = _label_bytes(labels)
+    ws_bytes = int(L.nnc_cbmm_dx_workspace_bytes(m, kdim, ncols, lb))
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=g.device) if ws_bytes else None
+    nat.check(L.nnc_cbmm_dx_f32(_ptr(g), m, kdim, _ptr(labels), lb, ncols, _ptr(centers), centers.numel(), _ptr(dx), _ptr(ws), ws_bytes, _stream(g)))
+    return dx
+
+
+def codebook_centroid_grad(x: torch.Tensor, g: torch.Tensor, labels: torch.Tensor, k: int, kdim: int, ncols: int,
+                           dtype=torch.float64) -> torch.Tensor:
+    """dc[j] = sum over the (i, o) with labels[i * ncols + o] = j of (x^T g)[i, o] (include/nnc.h, nnc_cbmm_dc_f32): the centroid
+    gradient of codebook_matmul, the kdim x ncols dW never written.  x: float32 (..., kdim), g: float32 (..., ncols) with the same
+    leading shape.  Exact fixed-point sums (S from max|x| and max|g| on the device, cbgrad_shift): the result depends on the shape
+    and the data only.  Returns ``dtype`` (float64 or float32) [k].  No host read."""
+    kdim, ncols, k = int(kdim), int(ncols), int(k)
+    _require_cuda(x, "x", torch.float32)
+    lead, m = _grad_args(g, labels, kdim, ncols, k)
+    if x.dim() < 1 or x.shape[-1] != kdim or tuple(x.shape[:-1]) != lead:
+        raise ValueError(f"x must have shape {lead + (kdim,)}, got {tuple(x.shape)}")
+    if len({x.device, g.device, labels.device}) != 1:
+        raise ValueError("x, g and labels must be on one device")
+    if dtype not in (torch.float64, torch.float32):
+        raise TypeError("dtype must be torch.float64 or torch.float32")
+    L = nat.load()
+    lb = _label_bytes(labels)
+    if lb == 1 and k > 256:
+        raise ValueError("k > 256 needs 16-bit labels")
+    dc = torch.empty(k, dtype=dtype, device=x.device)
+    ws_bytes = int(L.nnc_cbmm_dc_workspace_bytes(m, kdim, ncols, lb, k))
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=x.device) if ws_bytes else None
+    nat.check(L.nnc_cbmm_dc_f32(_ptr(x), _ptr(g), m, kdim, _ptr(labels), lb, ncols, k, _ptr(dc), 1 if dtype == torch.float64 else 0,
+                                _ptr(ws), ws_bytes, _stream(x)))
+    return dc
+
+
+def cbmm_dx_plan(m: int, kdim: int, ncols: int, label_bytes: int, k: int, cus: int, labels_addr: int = 0) -> dict:
+    """Host: the plan nnc_cbmm_dx_f32 follows on a device with ``cus`` compute units (include/nnc.h, nnc_cbmm_dx_plan), as a dict
+    keyed by _native.CBDX_PLAN_FIELDS.  No device needed."""
+    L = nat.load()
+    out = (ctypes.c_int64 * nat.CBDX_PLAN_LEN)()
+    nat.check(L.nnc_cbmm_dx_plan(int(m), int(kdim), int(ncols), int(label_bytes), int(k), int(cus), int(labels_addr), out))
+    return dict(zip(nat.CBDX_PLAN_FIELDS, (int(v) for v in out)))
+
+
+def cbmm_dc_plan(m: int, kdim: int, ncols: int, label_bytes: int, k: int, cus: int, labels_addr: int = 0) -> dict:
+    """Host: the plan nnc_cbmm_dc_f32 follows on a device with ``cus`` compute units (include/nnc.h, nnc_cbmm_dc_plan), as a dict
+    keyed by _native.CBDC_PLAN_FIELDS.  No device needed."""
+    L = nat.load()
+    out = (ctypes.c_int64 * nat.CBDC_PLAN_LEN)()
+    nat.check(L.nnc_cbmm_dc_plan(int(m), int(kdim), int(ncols), int(label_bytes), int(k), int(cus), int(labels_addr), out))
+    return dict(zip(nat.CBDC_PLAN_FIELDS, (int(v) for v in out)))
+
+
+CBGRAD_OK, CBGRAD_NONFINITE, CBGRAD_ZERO = 0, 1, 2
+
+
+def cbgrad_shift(m: int, absmax_x: float, absmax_g: float, terms_log2: int):
+    """Host mirror of the shift rule of nnc_cbmm_dc_f32 (include/nnc.h): (S, flag) with S = 62 - T - P, 2^P > m * max|x| * max|g|
+    (float64, in that order), T = terms_log2.  flag CBGRAD_NONFINITE (dc is NaN) for a non-finite maximum or P > 127,
+    CBGRAD_ZERO (dc = 0) for a zero one; S is 0 then."""
+    ax, ag = float(np.float32(absmax_x)), float(np.float32(absmax_g))
+    if not (math.isfinite(ax) and math.isfinite(ag)):
+        return 0, CBGRAD_NONFINITE
+    bound = float(m) * ax * ag
+    if not bound > 0:
+        return 0, CBGRAD_ZERO
+    _, P = math.frexp(bound)
+    if P > 127:
+        return 0, CBGRAD_NONFINITE
+    return 62 - int(terms_log2) - P, CBGRAD_OK
+
+
+class _CodebookLinear(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, labels, centers, kdim, ncols, bias, relu):
+        with torch.no_grad():
+            y = codebook_matmul(x.contiguous(), labels, centers, kdim, ncols, bias=bias, relu=relu)
+        ctx.kdim, ctx.ncols, ctx.relu = kdim, ncols, relu
+        ctx.save_for_backward(x, labels, centers, y if relu else None)
+        return y
+
+    @staticmethod
+    def backward(ctx, gy):
+        x, labels, centers, y = ctx.saved_tensors
+        kdim, ncols = ctx.kdim, ctx.ncols
+        g = gy.contiguous()
+        if ctx.relu:   # as torch.relu's backward: the gradient passes where y > 0 only (a NaN or negative output gets 0)
+            g = torch.where(y > 0, g, torch.zeros((), dtype=g.dtype, device=g.device))
+        g2 = g.reshape(-1, ncols)
+        dx = dc = db = None
+        if ctx.needs_input_grad[0]:
+            dx = codebook_matmul_dx(g2, labels, centers, kdim, ncols).view(x.shape)
+        if ctx.needs_input_grad[2]:
+            dc = codebook_centroid_grad(x.contiguous().reshape(-1, kdim), g2, labels, centers.numel(), kdim, ncols, dtype=torch.float32)
+        if ctx.needs_input_grad[5]:
+            db = g2.sum(0)
+        return dx, None, dc, None, None, db, None
+
+
+def codebook_linear(x: torch.Tensor, labels: torch.Tensor, centers: torch.Tensor, kdim: int, ncols: int, bias: torch.Tensor | None = None,
+                    relu: bool = False) -> torch.Tensor:
+    """codebook_matmul with gradients for x, centers and bias (an autograd Function).  The forward is the same nnc_cbmm_f32 call
+    (under no_grad the bits of codebook_matmul); the backward runs codebook_matmul_dx only if x needs a gradient and
+    codebook_centroid_grad (float32) only if centers does, masks a fused ReLU as torch does and sums the bias gradient over the
+    rows.  The indices get no gradient.  No host read."""
+    return _CodebookLinear.apply(x, labels, centers, int(kdim), int(ncols), bias, bool(relu))
+
+
 class SparseCodes:
     """The bitmap-sparse form of one (kdim, ncols) index matrix (include/nnc.h, nnc_cbsp_*): one 256-byte aligned uint8 device
     buffer holding the bitmap, the symbol counts and the ``nnz`` stored symbols, plus the metadata a product needs.  ``k`` is the
