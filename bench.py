@@ -22,15 +22,21 @@ The JSON line also carries
   roofline     : the k-means assignment pass over the vector, k_assign<labels> (4 B read + centroid index + 4 B decoded
                  value written per weight), against the 8 TB/s HBM peak; its duration is measured with HIP events
                  around the launch inside the timed region (in-library, on the launching stream);
-  kernels      : the same for every data-touching kernel of the step (durations, launches per step, and -- for passes
-                 over the vector -- algorithmic bytes and achieved GB/s);
+  kernels      : the same for every data-touching kernel of the timed region (durations, launches per step, and -- for passes
+                 over the vector -- algorithmic bytes and achieved GB/s).
+
+    python bench.py ... --full
+
+also measures and checks what the headline figure does not need, after the timed region (a plain run does none of it):
+  kernels      : + the K-sized kernels of the Lloyd loop, timed with events in one extra step (and --dump-durations);
   roofline_streaming_accumulate : the streaming form of the Lloyd pass (4 B read per weight per launch), which the
-                 iterations on a sorted vector no longer need, timed on its own after the timed region;
+                 iterations on a sorted vector no longer need, timed on its own;
   cpu_baseline : the same pipeline through NumPy / scikit-learn on the host cores (rank 0, N = 1
-                 only) on a bounded sample of the same vector;
+                 only) on a bounded sample of the same vector (about 20 s at the default size);
   parity       : the GPU fit of the timed region next to that CPU fit (n_iter, centres, index histogram, differing indices, the
                  k-means objective of both) and next to the committed full-size golden made by the reference itself
-                 (tests/golden/ref_goldens_25m.json, read as data: device == oracle mode B bit for bit; the reference's n_iter).
+                 (tests/golden/ref_goldens_25m.json, read as data: device == oracle mode B bit for bit; the reference's n_iter);
+  config.ranks_agree : N > 1, every rank ran the same fit (gathered and asserted).
 
     python bench.py ... --dump-outputs DIR
 
@@ -43,7 +49,8 @@ positions drawn with a fixed seed.  The inputs are seeded, so two builds given t
 BASELINE.json configs[4] instead: the 122 tensors of a GPT-2-small-sized model (124.4 M weights), per tensor prune -> 4-bit
 linear-init k-means (K = 16) -> labels + values -> index histogram -> Huffman lengths; the tensors are dealt out to the GPUs
 (pipeline.compress_layers(group=...): replicas, no data-path collective; --shard-above shards the longest ones instead).  The total
-work is fixed ("scaling": "strong").  The driver's default invocation (no --config) stays configs[3], the headline.
+work is fixed ("scaling": "strong").  The driver's default invocation (no --config) stays configs[3], the headline.  With --full the
+line adds the roofline of the assignment passes (one extra step, one tensor after the other) and the CPU baseline on block 0.
 """
 from __future__ import annotations
 
@@ -86,11 +93,14 @@ def parse():
                          "(BASELINE configs[3] read literally: one 25 M vector across 8 GPUs)")
     ap.add_argument("--python-exchange", action="store_true", help="N > 1: issue the per-iteration all-reduce from torch.distributed "
                                                                    "instead of inside the C library (nnc_kmeans_iterate_sharded)")
-    ap.add_argument("--dump-durations", action="store_true", help="stderr: the per-launch durations (us) of the iteration kernels of the last step")
-    ap.add_argument("--no-streaming-leg", action="store_true", help="skip the separate timing of the streaming Lloyd pass")
+    ap.add_argument("--full", action="store_true", help="after the timed steps, also measure and check what the headline figure does not need: "
+                                                        "the K-sized kernels in one extra step, the streaming Lloyd pass, the CPU baseline, parity, "
+                                                        "the ranks' agreement (configs[3]); the assignment roofline and the CPU baseline (configs[4])")
+    ap.add_argument("--dump-durations", action="store_true", help="--full: stderr: the per-launch durations (us) of the iteration kernels of the extra step")
+    ap.add_argument("--no-streaming-leg", action="store_true", help="--full: skip the separate timing of the streaming Lloyd pass")
     ap.add_argument("--input-pool-gb", type=float, default=64.0,
                     help="configs[3]: room for the per-step input batches (100 MB each at 25 M weights); beyond it the steps copy one resident vector instead")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
     ap.add_argument("--step-by-step", action="store_true", help="drive the layer's steps from Python (pipeline.compress_layer(native=False)) instead of "
                                                                 "the one-call form (nnc_compress_layer_f32): for comparison")
     ap.add_argument("--two-launch", action="store_true", help="Lloyd iterations launch by launch (k_bounds + k_finalize) instead of inside one resident "
@@ -105,6 +115,8 @@ def parse():
     args = ap.parse_args()
     if args.steps < 1 or args.warmup < 0:
         ap.error("--steps must be at least 1 and --warmup at least 0")
+    if args.dump_durations and not args.full:
+        ap.error("--dump-durations needs --full (the iteration kernels are timed in the extra step it runs)")
     return args
 
 
@@ -403,15 +415,17 @@ def main_config4(args):
 
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX, group=group)
     dt = float(tmax.item())
-    # one more step, one tensor after the other, with HIP events around the assignment pass of every tensor (outside the timed region)
-    nat.check(L.nnc_profile_tags(1 << 2))
-    nat.check(L.nnc_profile_begin(256))
-    step(workers=1)
-    torch.cuda.synchronize(dev)
-    ms_buf, tag_buf, cnt = (ctypes.c_float * 256)(), (ctypes.c_int32 * 256)(), ctypes.c_int64(0)
-    nat.check(L.nnc_profile_end(ms_buf, tag_buf, 256, ctypes.byref(cnt)))
-    nat.check(L.nnc_profile_tags(0xFFFFFFFF))
-    lab_ms = np.array(ms_buf[:min(cnt.value, 256)], dtype=np.float64)
+    lab_ms = np.zeros(0)
+    if args.full:
+        # one more step, one tensor after the other, with HIP events around the assignment pass of every tensor (outside the timed region)
+        nat.check(L.nnc_profile_tags(1 << 2))
+        nat.check(L.nnc_profile_begin(256))
+        step(workers=1)
+        torch.cuda.synchronize(dev)
+        ms_buf, tag_buf, cnt = (ctypes.c_float * 256)(), (ctypes.c_int32 * 256)(), ctypes.c_int64(0)
+        nat.check(L.nnc_profile_end(ms_buf, tag_buf, 256, ctypes.byref(cnt)))
+        nat.check(L.nnc_profile_tags(0xFFFFFFFF))
+        lab_ms = np.array(ms_buf[:min(cnt.value, 256)], dtype=np.float64)
     if rank == 0:
         if group is None:
             n_iter = sum(r.model.n_iter_ for r in res if r.model is not None)
@@ -422,16 +436,6 @@ def main_config4(args):
             bits = sum(int(r.total_bits or 0) for r in res)
             passed = sum(1 for r in res if r.centers is None)
         per_rank = [sum(1 for o in owner if o == r) for r in range(world)]
-        mine_long = [sizes[i] for i, o in enumerate(owner) if o in (0, -1) and sizes[i] > 4096]
-        lab_bytes = sum((4 + 1 + 4) * (n if owner[i] >= 0 else -(-n // world)) for i, n in enumerate(sizes) if owner[i] in (0, -1) and n > 4096)
-        roof = {"bound": "hbm", "kernel": "k_assign<labels> over rank 0's tensors of more than 4096 weights (final E-step: 4 B read + 1 B centroid index + 4 B decoded "
-                                         "value per weight), one tensor after the other in one extra step",
-                "peak": HBM_PEAK_GBS, "unit": "GB/s", "traffic": None, "launches_timed": int(lab_ms.size), "achieved": None, "frac": None}
-        if lab_ms.size == len(mine_long) and lab_ms.size:
-            roof["achieved"] = lab_bytes / (lab_ms.sum() * 1e-3) / 1e9
-            roof["frac"] = roof["achieved"] / HBM_PEAK_GBS
-            roof["algorithmic_bytes"] = int(lab_bytes)
-            roof["kernel_ms_total"] = float(lab_ms.sum())
         # the bytes no implementation could avoid (see the configs[3] line): per weight 8+8+9+8 + 4+1+4, per surviving weight 12; short tensors as one read + write
         step_bytes = n_total * (8 + 8 + 9 + 8 + 4 + 1 + 4) + int(0.32 * n_total) * 12
         out = {
@@ -450,13 +454,24 @@ def main_config4(args):
                 "rccl_world": (int(L.nnc_comm_world(comm.handle)) if comm is not None else None),
                 "backend": (args.backend if world > 1 else None),
             },
-            "roofline": roof,
             "roofline_step": {"bound": "hbm", "unavoidable_bytes_per_step": int(step_bytes), "achieved": step_bytes / (dt / args.steps) / 1e9, "peak": HBM_PEAK_GBS * world,
                               "unit": "GB/s", "frac": step_bytes / (dt / args.steps) / 1e9 / (HBM_PEAK_GBS * world),
                               "note": "122 chains of short dependent launches: latency, not bandwidth, bounds this configuration"},
         }
-        if world == 1 and not args.no_cpu_baseline:
-            out["cpu_baseline"] = cpu_baseline_config4(args, layers)
+        if args.full:
+            mine_long = [sizes[i] for i, o in enumerate(owner) if o in (0, -1) and sizes[i] > 4096]
+            lab_bytes = sum((4 + 1 + 4) * (n if owner[i] >= 0 else -(-n // world)) for i, n in enumerate(sizes) if owner[i] in (0, -1) and n > 4096)
+            roof = {"bound": "hbm", "kernel": "k_assign<labels> over rank 0's tensors of more than 4096 weights (final E-step: 4 B read + 1 B centroid index + 4 B decoded "
+                                             "value per weight), one tensor after the other in one extra step",
+                    "peak": HBM_PEAK_GBS, "unit": "GB/s", "traffic": None, "launches_timed": int(lab_ms.size), "achieved": None, "frac": None}
+            if lab_ms.size == len(mine_long) and lab_ms.size:
+                roof["achieved"] = lab_bytes / (lab_ms.sum() * 1e-3) / 1e9
+                roof["frac"] = roof["achieved"] / HBM_PEAK_GBS
+                roof["algorithmic_bytes"] = int(lab_bytes)
+                roof["kernel_ms_total"] = float(lab_ms.sum())
+            out["roofline"] = roof
+            if world == 1 and not args.no_cpu_baseline:
+                out["cpu_baseline"] = cpu_baseline_config4(args, layers)
         if args.dump_outputs:
             dump_outputs(args.dump_outputs, res if group is None else [rec.result for rec in res])
         print(json.dumps(out))
@@ -526,9 +541,10 @@ def main():
 
     # Every step gets a batch of its own, resident in HBM before the timed region starts (prune_weigth works in place, so a batch
     # is spent once it has been through a step): 1 set-up + W warm-up + K timed + 1 step for the K-sized kernels' events, 100 MB
-    # each.  Until round 4 a device-to-device copy of the one resident vector sat at the head of every timed step (2 x 22 us of copy
-    # kernels that are not on the path; it also left the step's input warm in the Infinity Cache, which a layer coming from
-    # elsewhere is not).  Beyond `--input-pool-gb` the old form is used and the line says so (config.input).
+    # each; a plain run leaves the last one unspent, so that its timed steps see the same pool as a --full run's.  Until round 4 a
+    # device-to-device copy of the one resident vector sat at the head of every timed step (2 x 22 us of copy kernels that are not
+    # on the path; it also left the step's input warm in the Infinity Cache, which a layer coming from elsewhere is not).  Beyond
+    # `--input-pool-gb` the old form is used and the line says so (config.input).
     n_batches = 1 + args.warmup + args.steps + 1
     pooled = n_batches * w0.numel() * 4 <= args.input_pool_gb * (1 << 30)
     pool = [w0.clone() for _ in range(n_batches)] if pooled else []
@@ -570,17 +586,19 @@ def main():
         return dt, np.array(ms_buf[:m], dtype=np.float64), np.array(tag_buf[:m], dtype=np.int64), r
 
     # THE timed region: exactly K steps; events only around the passes over the vector (ten launches a step).  The K-sized
-    # kernels of the Lloyd loop (some 110 launches a step) are timed in one more step afterwards, outside the timed region.
+    # kernels of the Lloyd loop (some 110 launches a step) are timed in one more step afterwards (--full), outside the timed region.
     STREAM_TAGS = (1 << 0) | (1 << 2) | (1 << 3) | (1 << 4) | (1 << 6) | (1 << 7)
     dt, all_ms, all_tags, res = profiled(args.steps, STREAM_TAGS)
-    _, ms_k, tags_k, _ = profiled(1, (1 << 1) | (1 << 5) | (1 << 8) | (1 << 9))
+    ms_k, tags_k = np.zeros(0), np.zeros(0, dtype=np.int64)
+    if args.full:
+        _, ms_k, tags_k, _ = profiled(1, (1 << 1) | (1 << 5) | (1 << 8) | (1 << 9))
     per_step_scale = {1: 1.0, 5: 1.0, 8: 1.0, 9: 1.0}
 
     # The streaming form of the Lloyd pass (k_assign<accumulate>: what an iteration costs on a vector that is NOT sorted, and
-    # the fallback of the rank-boundary form) timed on its own, outside the timed region: 30 launches on the same sorted
+    # the fallback of the rank-boundary form) timed on its own, outside the timed region (--full): 30 launches on the same sorted
     # 25 M vector with the converged centres.
     stream_ms = np.zeros(0)
-    if rank == 0 and res.model is not None and not args.no_streaming_leg:
+    if args.full and rank == 0 and res.model is not None and not args.no_streaming_leg:
         from neural_network_compression_amd import kmeans as _km
 
         xq = w0.clone()
@@ -605,9 +623,9 @@ def main():
 
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX, group=group)
     dt = float(tmax.item())
-    # N > 1: every rank must have run the same fit (the status is replicated: same iterations, events, centres); checked, not assumed
+    # N > 1: every rank must have run the same fit (the status is replicated: same iterations, events, centres); --full checks it
     agreement = None
-    if group is not None and res.model is not None:
+    if args.full and group is not None and res.model is not None:
         import hashlib
         import torch.distributed as dist
 
@@ -716,13 +734,14 @@ def main():
         if res.model is not None and res.nzeroed is not None:
             nnz = n_loc - int(res.nzeroed)
             step_bytes = n_loc * (8 + 8 + 9 + 8 + 4 + label_bytes + 4) + nnz * (8 + 4)
-            ksz = sum(kernels[nm]["ms_per_step"] for nm in ("k_bounds", "k_finalize", "k_lloyd", "k_reloc_*") if nm in kernels)
             out["roofline_step"] = {
                 "bound": "hbm", "unavoidable_bytes_per_step": int(step_bytes), "achieved": step_bytes / (dt / args.steps) / 1e9, "peak": HBM_PEAK_GBS,
                 "unit": "GB/s", "frac": step_bytes / (dt / args.steps) / 1e9 / HBM_PEAK_GBS,
-                "k_sized_kernel_ms_per_step": ksz, "k_sized_share_of_step": ksz / (dt / args.steps * 1e3),
                 "note": "roofline.frac describes one kernel (the assignment pass over the vector); this is the whole step",
             }
+            if args.full:   # the K-sized kernels are timed in the extra step
+                ksz = sum(kernels[nm]["ms_per_step"] for nm in ("k_bounds", "k_finalize", "k_lloyd", "k_reloc_*") if nm in kernels)
+                out["roofline_step"].update({"k_sized_kernel_ms_per_step": ksz, "k_sized_share_of_step": ksz / (dt / args.steps * 1e3)})
         if stream_ms.size:
             a = 4.0 * n_loc / (stream_ms.mean() * 1e-3) / 1e9
             out["roofline_streaming_accumulate"] = {
@@ -731,11 +750,11 @@ def main():
                 "avg_kernel_ms": float(stream_ms.mean()), "median_kernel_ms": float(np.median(stream_ms)), "launches_timed": int(stream_ms.size),
                 "algorithmic_bytes_per_launch": 4 * n_loc,
             }
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"], km_cpu, w_cpu, thr_cpu = cpu_baseline(args, w_host)
             if res.model is not None:
                 out["parity"] = parity_record(args, res, km_cpu, w_cpu, w_cpu.size, thr_cpu, w_host)
-        elif world == 1 and res.model is not None:
+        elif args.full and world == 1 and res.model is not None:
             out["parity"] = parity_record(args, res, None, None, 0, 0)
         if agreement is not None:
             out["config"]["ranks_agree"] = agreement

@@ -1,5 +1,5 @@
 """The line bench.py prints: run as the driver runs it (a child process, rank 0 prints ONE JSON line), at a reduced size so that the
-CPU leg takes seconds; the keys the driver and the judge read are there and consistent with each other."""
+CPU leg of --full takes seconds; the keys the driver and the judge read are there and consistent with each other."""
 import json
 import os
 import subprocess
@@ -22,7 +22,7 @@ def _run(extra):
 
 @pytest.mark.gpu
 def test_bench_line_contract_configs3_reduced():
-    d = _run(["--n", "2000000", "--cpu-sample", "2000000"])
+    d = _run(["--full", "--n", "2000000", "--cpu-sample", "2000000"])
     for key in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline", "dtype", "data",
                 "config", "roofline", "cpu_baseline", "parity"):
         assert key in d, key
@@ -41,6 +41,24 @@ def test_bench_line_contract_configs3_reduced():
     assert c["kind"] == "port" and c["unit"] == "weights/s" and c["cores"] >= 1 and c["value"] > 0 and "sample" in c
     p = d["parity"]
     assert p["mask_equal"] is True and p["n_iter_gpu"] >= 1 and p["n_iter_cpu"] >= 1
+    assert "roofline_streaming_accumulate" in d and "k_sized_kernel_ms_per_step" in d["roofline_step"]
+    assert any(k["timed"] == "one extra step" for k in d["kernels"].values())    # the K-sized kernels of the extra step
+
+
+@pytest.mark.gpu
+def test_bench_plain_run_is_the_headline_alone():
+    """Without --full the line is the timed region's: the headline and the events inside it, nothing that needs a run of its own."""
+    d = _run(["--n", "2000000"])
+    assert d["n_gpus"] == 1 and d["steps"] == 3 and d["warmup"] == 1 and d["higher_is_better"] is True
+    assert d["unit"] == "weights/s" and d["dtype"] == "f32" and d["metric"] == "weights/sec through prune+k-means (K=256)"
+    assert abs(d["value"] - 2_000_000 / (d["ms_per_step"] * 1e-3)) <= 1e-6 * d["value"]
+    assert d["config"]["k"] == 257 and d["config"]["lloyd_iterations"] >= 1
+    r = d["roofline"]
+    assert 0.0 < r["frac"] < 1.0 and r["launches_timed"] >= 3
+    assert d["kernels"] and all(k["timed"] == "timed region" for k in d["kernels"].values())
+    for key in ("cpu_baseline", "parity", "roofline_streaming_accumulate"):
+        assert key not in d, key
+    assert "k_sized_kernel_ms_per_step" not in d["roofline_step"] and "ranks_agree" not in d["config"]
 
 
 @pytest.mark.gpu
@@ -78,3 +96,8 @@ def test_bench_dump_outputs_are_the_last_steps_results_and_repeat(tmp_path):
 def test_bench_refuses_zero_steps():
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "0"], cwd=ROOT, capture_output=True, text=True, timeout=120)
     assert out.returncode == 2 and "--steps" in out.stderr
+
+
+def test_bench_dump_durations_needs_full():
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--dump-durations"], cwd=ROOT, capture_output=True, text=True, timeout=120)
+    assert out.returncode == 2 and "--full" in out.stderr

@@ -7,7 +7,7 @@ while read -r flags; do
   touch neural_network_compression_amd/csrc/*.hip
   NNC_EXTRA_CXXFLAGS="$flags" python -m neural_network_compression_amd.build > $out/build.log 2>&1 || { tail -5 $out/build.log | tee -a $out/variant.log; continue; }
   for i in 1 2; do
-  python bench.py --steps 20 --warmup 3 --no-cpu-baseline --no-streaming-leg --dump-durations 2> $out/dump.txt | python -c "
+  python bench.py --steps 20 --warmup 3 --full --no-cpu-baseline --no-streaming-leg --dump-durations 2> $out/dump.txt | python -c "
 import json,sys,re,statistics as st
 d=json.loads(sys.stdin.read().strip().splitlines()[-1]); k=d['kernels']
 line=[l for l in open('$out/dump.txt') if l.startswith('iteration kernels')][-1]

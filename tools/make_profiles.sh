@@ -5,9 +5,9 @@
 export TMPDIR=/tmp
 out=$PWD/gpurun_out/profiles
 rm -rf $out; mkdir -p $out
-CMD="python bench.py --steps 3 --warmup 1 --no-cpu-baseline"
-python bench.py --steps 10 --warmup 2 > $out/bench_plain.json 2> $out/bench_plain.err
-python bench.py --config 4 --steps 10 --warmup 3 > $out/bench_config4.json 2> $out/bench_config4.err
+CMD="python bench.py --steps 3 --warmup 1 --full --no-cpu-baseline"
+python bench.py --steps 10 --warmup 2 --full > $out/bench_plain.json 2> $out/bench_plain.err
+python bench.py --config 4 --steps 10 --warmup 3 --full > $out/bench_config4.json 2> $out/bench_config4.err
 python tools/time_sort.py > $out/sort_times.txt 2>&1
 python tools/time_assign.py > $out/assign_times.txt 2>&1
 rocprofv3 --kernel-trace --stats --output-format csv -d $out/trace -- $CMD > $out/bench_under_trace.json 2>/dev/null
@@ -61,7 +61,7 @@ json.dump({"k_assign_labels_hbm_bytes_per_launch": traffic,
            "k_assign_accumulate_hbm_bytes_per_launch": hbm("k_assign<0"),
            "k_bounds_hbm_bytes_per_launch": hbm("k_bounds"),
            "k_threshold_hbm_bytes_per_launch": hbm("k_threshold"),
-           "how": "rocprofv3 --pmc FETCH_SIZE and --pmc WRITE_SIZE in separate passes over `python bench.py --steps 3 --warmup 1 --no-cpu-baseline`; "
+           "how": "rocprofv3 --pmc FETCH_SIZE and --pmc WRITE_SIZE in separate passes over `python bench.py --steps 3 --warmup 1 --full --no-cpu-baseline`; "
                   "bytes = 2 * FETCH_SIZE_KB * 1024 (gfx950 half-count correction for 16 B/lane streaming reads) + WRITE_SIZE_KB * 1024; mean over the live launches"},
           open(os.path.join(out, "traffic.json"), "w"), indent=1)
 print(json.dumps(summ, indent=1)[:1500])
