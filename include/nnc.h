@@ -701,6 +701,70 @@ int nnc_cbsp_f32(const float *x, int64_t m, int64_t kdim, const void *packed, in
                  int64_t workspace_bytes, void *stream);
 
 /* ------------------------------------------------------------------------------------
+ * The backward pass of nnc_cbsp_f32 from the same packed form, the indices never unpacked and W never decoded
+ * (csrc/nnc_cbspgrad.hip).  The form, z, c_z and d are nnc_cbsp_f32's; g = dL/dy float32[m, ncols].
+ * nnc_cbsp_dx_f32   dx[m, kdim] = c_z * sum_o g[r, o] + sum over the stored (i, o) of g[r, o] * d[labels[i, o]]: the Jacobian of
+ *                   the forward with its conventions -- with c_z == 0 exactly the rank-1 term is dropped and a skipped weight forms no
+ *                   product (an Inf in g meets no 0); a stored index >= k reads d = -c_z.  m <= 16 streams the bitmap
+ *                   (k_cbspdx_stream: a block of SEGS segments per workgroup, a wave reduction in a fixed order per index row, one
+ *                   split per block), larger m decodes W^T tiles into LDS (k_cbspdx_tiled, ncols split into whole segments by a
+ *                   count that depends on the shape alone); the split partials are summed in split order (k_cbgrad_reduce), then
+ *                   c_z times the fixed-order row sums of g is added.
+ * nnc_cbsp_dc_f32   dc[k] as nnc_cbmm_dc_f32 on the unpacked labels, bit for bit: every dW[i, o] is formed in float32 as that call
+ *                   forms it and binned as rint(dW * 2^S) with the same S (SPLITS and TERMS_LOG2 are nnc_cbmm_dc_plan's for the
+ *                   shape); a skipped (i, o) falls into bin z (none if z >= k), a stored index >= k into none.  A stored
+ *                   weight's image goes into LDS bins, a skipped one's into a register flushed once per thread.  The all-NaN rule,
+ *                   dc = 0 for a zero maximum, float64 / float32 output: as nnc_cbmm_dc_f32.
+ * No host read and no float atomics in either; the same call gives the same bits.  m = 0 or kdim = 0: dx is empty (a no-op);
+ * ncols = 0: dx = 0.  No terms (m, kdim or ncols = 0): dc = 0.  Limits as nnc_cbsp_f32 (m <= 2^40).
+ * *_workspace_bytes: what the call needs for that shape (0 for none; host arithmetic only): dx the split partials (256-byte
+ * aligned) and m floats of row sums, 4-byte aligned; dc 64 bytes of header and k int64 sums, 8-byte aligned.  Argument errors
+ * (NNC_EINVAL; NNC_ENOSPACE for a short workspace) are returned before any HIP call.
+ * *_plan: host arithmetic only, the plan the call follows on a device with `cus` compute units.  The splits depend on the shape
+ * alone (planned for 256 CUs); `cus` changes only the grid.  NNC_EINVAL as the call, for cus < 1, out NULL, or a plan with no
+ * kernel instantiation.
+ *   dx (NNC_CBSPDX_P_*): PATH (NNC_CBMM_NONE: nothing written, _STREAM, _TILED, _ZERO: dx = 0), MT, SEGS (stream: segments per
+ *       column block), COPIES and ENTRIES of the LDS d table, SPLITS of ncols and CPS columns per split, LDS, COL_TILES x ROW_TILES
+ *       (stream: column blocks x row groups; tiled: kdim tiles x m tiles), WORKSPACE.
+ *   dc (NNC_CBSPDC_P_*): PATH (_STREAM, _TILED, _ZERO: dc = 0), MT, SEGS, COPIES of every LDS bin, SPLITS of m and RPS rows of m
+ *       per split, LDS, COL_TILES x ROW_TILES (stream: column blocks x row groups; tiled: ncols tiles x kdim tiles), TERMS_LOG2,
+ *       WORKSPACE.
+ * ---------------------------------------------------------------------------------- */
+#define NNC_CBSPDX_P_PATH 0
+#define NNC_CBSPDX_P_MT 1
+#define NNC_CBSPDX_P_SEGS 2
+#define NNC_CBSPDX_P_COPIES 3
+#define NNC_CBSPDX_P_ENTRIES 4
+#define NNC_CBSPDX_P_SPLITS 5
+#define NNC_CBSPDX_P_CPS 6
+#define NNC_CBSPDX_P_LDS 7
+#define NNC_CBSPDX_P_COL_TILES 8
+#define NNC_CBSPDX_P_ROW_TILES 9
+#define NNC_CBSPDX_P_WORKSPACE 10
+#define NNC_CBSPDX_PLAN_LEN 11
+#define NNC_CBSPDC_P_PATH 0
+#define NNC_CBSPDC_P_MT 1
+#define NNC_CBSPDC_P_SEGS 2
+#define NNC_CBSPDC_P_COPIES 3
+#define NNC_CBSPDC_P_SPLITS 4
+#define NNC_CBSPDC_P_RPS 5
+#define NNC_CBSPDC_P_LDS 6
+#define NNC_CBSPDC_P_COL_TILES 7
+#define NNC_CBSPDC_P_ROW_TILES 8
+#define NNC_CBSPDC_P_TERMS_LOG2 9
+#define NNC_CBSPDC_P_WORKSPACE 10
+#define NNC_CBSPDC_PLAN_LEN 11
+int64_t nnc_cbsp_dx_workspace_bytes(int64_t m, int64_t kdim, int64_t ncols, int label_bytes);
+int nnc_cbsp_dx_plan(int64_t m, int64_t kdim, int64_t ncols, int label_bytes, int32_t k, int32_t cus, int64_t *out);
+int nnc_cbsp_dx_f32(const float *g, int64_t m, int64_t kdim, const void *packed, int64_t packed_bytes, int label_bytes, int64_t ncols,
+                    int32_t zero_symbol, int64_t nnz, const float *centers_dev, int32_t k, float *dx, void *workspace, int64_t workspace_bytes,
+                    void *stream);
+int64_t nnc_cbsp_dc_workspace_bytes(int64_t m, int64_t kdim, int64_t ncols, int label_bytes, int32_t k);
+int nnc_cbsp_dc_plan(int64_t m, int64_t kdim, int64_t ncols, int label_bytes, int32_t k, int32_t cus, int64_t *out);
+int nnc_cbsp_dc_f32(const float *x, const float *g, int64_t m, int64_t kdim, const void *packed, int64_t packed_bytes, int label_bytes, int64_t ncols,
+                    int32_t zero_symbol, int64_t nnz, int32_t k, void *dc, int32_t out_f64, void *workspace, int64_t workspace_bytes, void *stream);
+
+/* ------------------------------------------------------------------------------------
  * Multi-GPU: the vector is sharded across one process per GPU (contiguous shards starting on multiples of
  * NNC_CHUNK elements); the exchange per Lloyd iteration is one all-reduce (SUM) of the 2K int64 sums / counts over
  * RCCL / xGMI, enqueued by the library on the caller's stream between its own kernels.  The reference has no

@@ -170,25 +170,27 @@ class Trainer(ABC):
         return accuracies
 
     def fine_tune_compressed(self, train_dataset: LeNetDataset, test_dataset: LeNetDataset, epochs: int,
-                             learning_rate: float = 1e-3) -> List[float]:
-        """fine_tune_centroids' algorithm run on ``compressed_network(trainable=True)``: the indices stay fixed and per batch every
-        quantized tensor's centres take the plain step c -= learning_rate * dc, dc formed from the codebook and the indices by
-        ops.codebook_linear's backward (neither W nor dW is built).  Tensors that passed through
-        unquantized stay frozen.  At the end the tuned centres go into ``quantized_models_by_layer`` and the float layers are
-        re-decoded from them (ops.gather), as after fine_tune_centroids.  Returns the accuracy per epoch (of the trainable
-        network)."""
+                             learning_rate: float = 1e-3, sparse=False) -> List[float]:
+        """fine_tune_centroids' algorithm run on ``compressed.compress_network_trainable(..., sparse=sparse)`` (sparse=False: the
+        network of ``compressed_network(trainable=True)``; True or "auto": the bitmap-sparse trainable layers, for every
+        quantized layer or where that form is smaller): the indices stay fixed and per batch every quantized tensor's centres
+        take the plain step c -= learning_rate * dc, dc formed from the codebook and the indices (dense or packed) by the
+        backward of ops.codebook_linear / ops.sparse_codebook_linear (DESIGN.md sections 12, 13; neither W nor dW is built).
+        Tensors that passed through unquantized stay frozen.  At the end the tuned centres go into ``quantized_models_by_layer``
+        and the float layers are re-decoded from them (ops.gather), as after fine_tune_centroids.  Returns the accuracy per epoch
+        (of the trainable network)."""
         models = getattr(self, "quantized_models_by_layer", None)
         if not models:
             raise RuntimeError("fine_tune_compressed needs a quantized network: call quantize first")
         from .. import compressed
 
-        net = self.compressed_network(trainable=True)
+        net = compressed.compress_network_trainable(self.neural_network, models, sparse=sparse)
         for p in net.parameters():
             p.requires_grad_(False)
         tuned = {}   # layer name -> trainable layer
         params = []
         for name, layer in net.get_config().items():
-            if isinstance(layer, compressed._TrainableCodebookLayer):
+            if isinstance(layer, compressed._TrainableCentres):
                 tuned[name] = layer
                 for p in (layer.centers, layer.bias_centers):
                     if p is not None:

@@ -21,8 +21,15 @@ that silently has none.  ``trainable=True`` in compress_network / Trainer.compre
 (``TrainableCompressedDense`` / ``TrainableCompressedConv2D``): their ``centers`` is an nn.Parameter and the
 forward goes through ops.codebook_linear, whose backward forms dx and the centroid gradient from the codebook and the indices
 (csrc/nnc_cbgrad.hip) -- W and dW are never built.  A quantized bias keeps its indices and a ``bias_centers`` parameter; a raw bias
-stays frozen.  ``kernel_sq_sum()`` gives the trainers' L2 term without W.  Trainer.fine_tune_compressed trains them.  The
-bitmap-sparse layers have no backward pass.
+stays frozen.  ``kernel_sq_sum()`` gives the trainers' L2 term without W.  Trainer.fine_tune_compressed trains them.
+
+    compress_network_trainable(network, models_by_layer, sparse=False)   the trainable layers, dense, bitmap-sparse or per layer
+
+The bitmap-sparse layers train too (``TrainableSparseCompressedDense`` / ``TrainableSparseCompressedConv2D``, DESIGN.md section
+13): ops.sparse_codebook_linear's backward forms dx and the centroid gradient from the packed form (csrc/nnc_cbspgrad.hip), and
+the centroid gradient is the dense trainable layer's bit for bit -- the same function, stored differently.
+compress_network_trainable(..., sparse=True | "auto") and Trainer.fine_tune_compressed(..., sparse=...) give them;
+compress_network(..., trainable=True) stays the dense form.
 """
 from __future__ import annotations
 
@@ -168,20 +175,14 @@ class _GatherCenters(torch.autograd.Function):
         return ops.centroid_gradient(grad.contiguous(), labels, ctx.k).to(torch.float32), None
 
 
-class _TrainableCodebookLayer(nn.Module):
-    """labels (kdim * ncols indices, row-major (kdim, ncols)) and counts (their histogram, for kernel_sq_sum) as buffers, centers a
-    float32[K] nn.Parameter.  The bias is a quantized one (bias_labels buffer + bias_centers parameter), a frozen raw one (bias
+class _TrainableCentres(nn.Module):
+    """What the trainable layers share: centers a float32[K] nn.Parameter, counts (the histogram of the kdim * ncols indices, for
+    kernel_sq_sum) a buffer, and the bias: a quantized one (bias_labels buffer + bias_centers parameter), a frozen raw one (bias
     buffer) or None."""
 
-    def __init__(self, kdim: int, ncols: int, labels: torch.Tensor, centers: torch.Tensor, bias: torch.Tensor | None = None,
-                 bias_codes=None, activation=None):
-        super().__init__()
-        if labels.numel() != kdim * ncols:
-            raise ValueError(f"{labels.numel()} indices for a {kdim} x {ncols} weight matrix")
-        self.kdim, self.ncols = int(kdim), int(ncols)
-        self.register_buffer("labels", labels.reshape(-1))
+    def _init_centres(self, labels: torch.Tensor, centers: torch.Tensor, ncols: int, bias, bias_codes, activation):
         self.centers = nn.Parameter(centers.detach().reshape(-1).to(torch.float32).clone())
-        self.register_buffer("counts", ops.bincount(self.labels, self.centers.numel()))
+        self.register_buffer("counts", ops.bincount(labels, self.centers.numel()))
         if bias_codes is not None:
             bcenters, blabels = bias_codes
             if blabels.numel() != ncols:
@@ -201,8 +202,7 @@ class _TrainableCodebookLayer(nn.Module):
             return _GatherCenters.apply(self.bias_centers, self.bias_labels)
         return self.bias
 
-    def _matmul(self, x: torch.Tensor) -> torch.Tensor:
-        y = ops.codebook_linear(x, self.labels, self.centers, self.kdim, self.ncols, bias=self.current_bias(), relu=self._fused_relu)
+    def _activate(self, y: torch.Tensor) -> torch.Tensor:
         if self.activation is not None and not self._fused_relu:
             y = self.activation(y)
         return y
@@ -214,9 +214,29 @@ class _TrainableCodebookLayer(nn.Module):
     def get_weights(self):
         return []
 
-    def nbytes(self) -> int:
-        ts = (self.labels, self.centers, self.bias, self.bias_labels, self.bias_centers)
+    def _nbytes(self, indices: torch.Tensor) -> int:
+        ts = (indices, self.centers, self.bias, self.bias_labels, self.bias_centers)
         return sum(t.numel() * t.element_size() for t in ts if t is not None)
+
+
+class _TrainableCodebookLayer(_TrainableCentres):
+    """labels (kdim * ncols indices, row-major (kdim, ncols)) a buffer; the centres, counts and bias of _TrainableCentres."""
+
+    def __init__(self, kdim: int, ncols: int, labels: torch.Tensor, centers: torch.Tensor, bias: torch.Tensor | None = None,
+                 bias_codes=None, activation=None):
+        super().__init__()
+        if labels.numel() != kdim * ncols:
+            raise ValueError(f"{labels.numel()} indices for a {kdim} x {ncols} weight matrix")
+        self.kdim, self.ncols = int(kdim), int(ncols)
+        self.register_buffer("labels", labels.reshape(-1))
+        self._init_centres(self.labels, centers, ncols, bias, bias_codes, activation)
+
+    def _matmul(self, x: torch.Tensor) -> torch.Tensor:
+        return self._activate(ops.codebook_linear(x, self.labels, self.centers, self.kdim, self.ncols, bias=self.current_bias(),
+                                                  relu=self._fused_relu))
+
+    def nbytes(self) -> int:
+        return self._nbytes(self.labels)
 
 
 class TrainableCompressedDense(_TrainableCodebookLayer):
@@ -239,13 +259,19 @@ class TrainableCompressedConv2D(_TrainableCodebookLayer):
         return _conv_forward(self, x)
 
 
-def _trainable(layer, weight_model, bias_model):
-    from .neural_networks.layers import Conv2D, Dense
-
+def _trainable_codes(layer, weight_model, bias_model):
+    """(centers, labels, raw bias, bias codes) of a trainable layer: a quantized bias keeps its codes, a raw one stays frozen."""
     if weight_model is None:
         raise ValueError("the kernel was not quantized (no fitted model): keep the float32 layer")
     centers, labels = _codes(weight_model, layer.kernel.device)
     bias, bias_codes = (None, _codes(bias_model, layer.kernel.device)) if bias_model is not None else (layer.bias, None)
+    return centers, labels, bias, bias_codes
+
+
+def _trainable(layer, weight_model, bias_model):
+    from .neural_networks.layers import Conv2D, Dense
+
+    centers, labels, bias, bias_codes = _trainable_codes(layer, weight_model, bias_model)
     if isinstance(layer, Dense):
         kin, kout = layer.kernel.shape
         return TrainableCompressedDense(kin, kout, labels, centers, bias, bias_codes, layer.activation)
@@ -343,6 +369,93 @@ class SparseCompressedConv2D(_SparseCodebookLayer):
         return _conv_forward(self, x)
 
 
+class _TrainableSparseCodebookLayer(_TrainableCentres):
+    """The indices in the bitmap-sparse form (the ``packed`` buffer, as _SparseCodebookLayer) with the centres, counts and bias of
+    _TrainableCentres; the forward goes through ops.sparse_codebook_linear, whose backward forms dx and the centroid gradient
+    from the packed form (csrc/nnc_cbspgrad.hip).  ``counts`` is taken from the labels before packing, so kernel_sq_sum() is the
+    dense trainable layer's bit for bit.  No kdim * ncols tensor stays resident."""
+
+    def __init__(self, codes: ops.SparseCodes, labels: torch.Tensor, centers: torch.Tensor, bias: torch.Tensor | None = None,
+                 bias_codes=None, activation=None):
+        super().__init__()
+        if centers.numel() != codes.k:
+            raise ValueError(f"{centers.numel()} centres for indices into a codebook of {codes.k}")
+        if labels.numel() != codes.kdim * codes.ncols:
+            raise ValueError(f"{labels.numel()} indices for a {codes.kdim} x {codes.ncols} weight matrix")
+        self.kdim, self.ncols = codes.kdim, codes.ncols
+        self.k, self.zero_symbol, self.label_bytes, self.nnz = codes.k, codes.zero_symbol, codes.label_bytes, codes.nnz
+        self.register_buffer("packed", codes.buf)
+        self._init_centres(labels.reshape(-1), centers, codes.ncols, bias, bias_codes, activation)
+
+    codes = _SparseCodebookLayer.codes
+
+    def _matmul(self, x: torch.Tensor) -> torch.Tensor:
+        return self._activate(ops.sparse_codebook_linear(x, self.codes, self.centers, bias=self.current_bias(), relu=self._fused_relu))
+
+    def nbytes(self) -> int:
+        return self._nbytes(self.packed)
+
+
+class TrainableSparseCompressedDense(_TrainableSparseCodebookLayer):
+    """SparseCompressedDense with trainable centres (ops.sparse_codebook_linear)."""
+
+    @classmethod
+    def from_dense(cls, dense, weight_model, bias_model=None, zero_symbol=None) -> "TrainableSparseCompressedDense":
+        centers, labels, bias, bias_codes = _trainable_codes(dense, weight_model, bias_model)
+        kin, kout = dense.kernel.shape
+        return cls.from_codes(kin, kout, labels, centers, bias, bias_codes, dense.activation, zero_symbol)
+
+    @classmethod
+    def from_codes(cls, kdim, ncols, labels, centers, bias=None, bias_codes=None, activation=None,
+                   zero_symbol=None) -> "TrainableSparseCompressedDense":
+        return cls(ops.pack_sparse_codes(labels, kdim, ncols, centers.numel(), zero_symbol), labels, centers, bias, bias_codes, activation)
+
+    def forward(self, x: torch.Tensor) -> torch.Tensor:
+        return self._matmul(x.contiguous())
+
+
+class TrainableSparseCompressedConv2D(_TrainableSparseCodebookLayer):
+    """SparseCompressedConv2D with trainable centres: the patches (chunked as CompressedConv2D) through
+    ops.sparse_codebook_linear; autograd carries the patch gradients back through the unfold."""
+
+    def __init__(self, kernel_size: int, cin: int, pad: int, codes: ops.SparseCodes, labels: torch.Tensor, centers: torch.Tensor, bias=None,
+                 bias_codes=None, activation=None):
+        if codes.kdim != kernel_size * kernel_size * cin:
+            raise ValueError(f"{codes.kdim} index rows for a {kernel_size} x {kernel_size} x {cin} kernel")
+        super().__init__(codes, labels, centers, bias, bias_codes, activation)
+        self.kernel_size, self.cin, self.pad = int(kernel_size), int(cin), int(pad)
+
+    @classmethod
+    def from_conv(cls, conv, weight_model, bias_model=None, zero_symbol=None) -> "TrainableSparseCompressedConv2D":
+        h, w, cin, cout = conv.kernel.shape
+        if h != w:
+            raise ValueError("square kernels only (as layers.Conv2D)")
+        centers, labels, bias, bias_codes = _trainable_codes(conv, weight_model, bias_model)
+        return cls.from_codes(h, cin, cout, conv.pad, labels, centers, bias, bias_codes, conv.activation, zero_symbol)
+
+    @classmethod
+    def from_codes(cls, kernel_size, cin, cout, pad, labels, centers, bias=None, bias_codes=None, activation=None,
+                   zero_symbol=None) -> "TrainableSparseCompressedConv2D":
+        """labels in the Keras order of the (h, w, in, out) kernel (the counts are the same in either order)."""
+        unf = _unfold_labels(kernel_size, cin, cout, labels)
+        codes = ops.pack_sparse_codes(unf, kernel_size * kernel_size * cin, cout, centers.numel(), zero_symbol)
+        del unf
+        return cls(kernel_size, cin, pad, codes, labels, centers, bias, bias_codes, activation)
+
+    def forward(self, x: torch.Tensor) -> torch.Tensor:   # x: (N, H, W, C)
+        return _conv_forward(self, x)
+
+
+def _trainable_sparse(layer, weight_model, bias_model):
+    from .neural_networks.layers import Conv2D, Dense
+
+    if isinstance(layer, Dense):
+        return TrainableSparseCompressedDense.from_dense(layer, weight_model, bias_model)
+    if isinstance(layer, Conv2D):
+        return TrainableSparseCompressedConv2D.from_conv(layer, weight_model, bias_model)
+    raise TypeError(f"no compressed form of {type(layer).__name__}")
+
+
 def _check_sparse(sparse):
     if sparse not in (False, True, "auto"):
         raise ValueError(f"sparse must be False, True or 'auto', got {sparse!r}")
@@ -392,17 +505,37 @@ def compress_network(network: nn.Module, models_by_layer, sparse=False, trainabl
     Trainer.quantized_models_by_layer) run from their codebooks.  Layers are replaced by the attribute names of
     ``get_config()``; a layer whose kernel passed through unquantized (model None) stays float32.  ``sparse``: False (the
     indices as they are), True (the bitmap-sparse form, skipping the most frequent index), "auto" (per layer, the smaller).
-    ``trainable=True`` (dense indices only): TrainableCompressedDense / TrainableCompressedConv2D, centres as parameters."""
+    ``trainable=True`` (dense indices only): TrainableCompressedDense / TrainableCompressedConv2D, centres as parameters;
+    compress_network_trainable gives the bitmap-sparse trainable layers too."""
     _check_sparse(sparse)
     if trainable and sparse is not False:
-        raise ValueError("trainable=True needs sparse=False: the bitmap-sparse layers have no backward pass")
+        raise ValueError("trainable=True needs sparse=False here: use compress_network_trainable(..., sparse=...) for trainable "
+                         "bitmap-sparse layers")
+    if trainable:
+        return compress_network_trainable(network, models_by_layer)
+    return _compress_each(network, models_by_layer, lambda layer, wm, bm: _replace(layer, wm, bm, sparse))
+
+
+def compress_network_trainable(network: nn.Module, models_by_layer, sparse=False) -> nn.Module:
+    """compress_network with the centres (and quantized biases' centres) as nn.Parameters.  ``sparse``: False
+    (TrainableCompressedDense / TrainableCompressedConv2D, the layers of compress_network(..., trainable=True)), True
+    (TrainableSparseCompressedDense / TrainableSparseCompressedConv2D: the indices in the bitmap-sparse form, skipping the most
+    frequent one) or "auto" (per layer, the form with fewer resident bytes).  Both train the same function: the sparse layer's
+    centroid gradient is the dense one's bit for bit."""
+    _check_sparse(sparse)
+    return _compress_each(network, models_by_layer,
+                          lambda layer, wm, bm: _pick(lambda: _trainable(layer, wm, bm), lambda: _trainable_sparse(layer, wm, bm), sparse))
+
+
+def _compress_each(network: nn.Module, models_by_layer, make) -> nn.Module:
+    """A deep copy of ``network`` with every quantized layer replaced by make(layer, kernel model, bias model)."""
     out = copy.deepcopy(network)
     for name, layer in network.get_config().items():
         models = models_by_layer.get(layer)
         if not models or models[0] is None:
             continue
         bias_model = models[1] if len(models) > 1 else None
-        setattr(out, name, _trainable(layer, models[0], bias_model) if trainable else _replace(layer, models[0], bias_model, sparse))
+        setattr(out, name, make(layer, models[0], bias_model))
     return out
 
 
@@ -444,7 +577,7 @@ def compressed_nbytes(network: nn.Module) -> int:
     layers = network.get_config().values() if hasattr(network, "get_config") else [network]
     total = 0
     for layer in layers:
-        if isinstance(layer, (_CodebookLayer, _SparseCodebookLayer, _TrainableCodebookLayer)):
+        if isinstance(layer, (_CodebookLayer, _SparseCodebookLayer, _TrainableCentres)):
             total += layer.nbytes()
         else:
             total += sum(p.numel() * p.element_size() for p in layer.parameters())

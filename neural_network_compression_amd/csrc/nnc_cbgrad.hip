@@ -20,12 +20,7 @@
 //   from k_cbgrad_absmax on the device, the dc kernel derives S itself and writes it next to the sums, and k_cbdc_finish writes
 //   dc = ldexp(sum, -S).  No host read anywhere.
 // An index >= K reads 0 in dx and falls into no bin in dc, as in the forward pass.  No float atomics.
-#include "nnc_cbmm.hpp"
-
-#define CBG_FLAG_OK 0
-#define CBG_FLAG_NONFINITE 1   // x or g holds Inf / NaN, or m * max|x| * max|g| >= 2^127: dc is NaN
-#define CBG_FLAG_ZERO 2        // max|x| or max|g| is 0: every dW is 0
-#define CBG_HDR_BYTES 64       // dc workspace: {max|x| bits, max|g| bits, S, flag} then int64 sums[K] at byte 64
+#include "nnc_cbgrad.hpp"
 
 // ------------------------------------------------------------------ plans (host)
 struct CgPlan {
@@ -130,71 +125,6 @@ static CgPlan dc_plan(long long m, long long kdim, long long ncols, int lb, int 
 
 static int64_t dx_ws_bytes(const CgPlan &p, long long m, long long kdim) { return p.splits > 1 ? (int64_t)p.splits * m * kdim * 4 : 0; }
 static int64_t dc_ws_bytes(const CgPlan &p, int k) { return p.path == NNC_CBMM_STREAM || p.path == NNC_CBMM_TILED ? CBG_HDR_BYTES + 8LL * k : 0; }
-
-// ------------------------------------------------------------------ device helpers
-// The m partials of every lane summed over the wave: a reduce-scatter (at lane bit 32 >> t the lanes with the bit set keep the upper
-// half of the rows they hold and take their partner's; then the rest of the butterfly on one value).  N + log2(64 / N) shuffles
-// instead of 6 N; every pair adds in a fixed order, so the sum depends on the data only.  Returns the total of row `row`, the
-// same on every lane of a group of 64 / N lanes.
-template <int N>
-__device__ __forceinline__ float wave_reduce_rows(float (&v)[N], int lane, int &row)
-{
-    row = 0;
-#pragma unroll
-    for (int t = 0; (N >> t) > 1; ++t) {
-        const int half = N >> (t + 1), bit = 32 >> t;
-        const bool up = (lane & bit) != 0;
-#pragma unroll
-        for (int j = 0; j < half; ++j) {
-            const float send = up ? v[j] : v[j + half];
-            const float keep = up ? v[j + half] : v[j];
-            v[j] = keep + __shfl_xor(send, bit);
-        }
-        row += up ? half : 0;
-    }
-    float s = v[0];
-#pragma unroll
-    for (int bit = 64 / N / 2; bit >= 1; bit >>= 1) s += __shfl_xor(s, bit);
-    return s;
-}
-
-// S of the dc sums from the maxima k_cbgrad_absmax left (uniform over the launch); flag as CBG_FLAG_*
-__device__ __forceinline__ int cbdc_shift(const uint32_t *amax, long long m, int terms_log2, int &flag)
-{
-    const uint32_t ux = amax[0], ug = amax[1];
-    flag = CBG_FLAG_OK;
-    if (ux >= 0x7F800000u || ug >= 0x7F800000u) {
-        flag = CBG_FLAG_NONFINITE;
-        return 0;
-    }
-    const double bound = (double)m * (double)__uint_as_float(ux) * (double)__uint_as_float(ug);
-    if (!(bound > 0.0)) {
-        flag = CBG_FLAG_ZERO;
-        return 0;
-    }
-    int P = 0;
-    (void)frexp(bound, &P);   // bound = f * 2^P, f in [0.5, 1): 2^P > bound
-    if (P > 127) {
-        flag = CBG_FLAG_NONFINITE;
-        return 0;
-    }
-    return 62 - terms_log2 - P;
-}
-
-// the fixed-point image of one dW: exact scaling by 2^S (|v * 2^S| < 2^63), nearest integer, ties to even
-__device__ __forceinline__ unsigned long long cbdc_fix(float v, int S) { return (unsigned long long)(long long)rintf(ldexpf(v, S)); }
-
-// the workgroup's bins into the global sums (integer atomics), copies summed in order; zero bins are skipped
-__device__ __forceinline__ void cbdc_flush(const unsigned long long *bins, int k, int rlog2, unsigned long long *__restrict__ sums)
-{
-    __syncthreads();
-    const int R = 1 << rlog2;
-    for (int j = threadIdx.x; j < k; j += blockDim.x) {
-        unsigned long long s = 0;
-        for (int r = 0; r < R; ++r) s += bins[(j << rlog2) + r];
-        if (s) atomicAdd(&sums[j], s);
-    }
-}
 
 // ------------------------------------------------------------------ max |x|, max |g|
 // amax[0] = bits of max |x|, amax[1] = bits of max |g| (zeroed by the caller).  |v| as a bit pattern orders as the value; a NaN
@@ -549,6 +479,30 @@ __global__ __launch_bounds__(256) void k_cbdc_finish(const uint32_t *__restrict_
     }
 }
 
+// ------------------------------------------------------------------ the launches nnc_cbspgrad.hip shares (nnc_cbgrad.hpp)
+int cbgrad_absmax(const float *x, long long nx, const float *g, long long ng, uint32_t *amax, hipStream_t s)
+{
+    const int agrid = (int)std::max(1LL, std::min(cdiv(std::max(nx, ng), 256 * 8), 4LL * cu_count()));
+    hipLaunchKernelGGL(k_cbgrad_absmax, dim3(agrid), dim3(256), 0, s, x, nx, g, ng, amax);
+    LAUNCHCHK("k_cbgrad_absmax");
+    return NNC_OK;
+}
+
+int cbgrad_reduce(const float *part, long long splits, long long mn, float *out, hipStream_t s)
+{
+    const int rgrid = (int)std::max(1LL, std::min(cdiv(mn, 256), 8192LL));
+    hipLaunchKernelGGL(k_cbgrad_reduce, dim3(rgrid), dim3(256), 0, s, part, splits, mn, out);
+    LAUNCHCHK("k_cbgrad_reduce");
+    return NNC_OK;
+}
+
+int cbdc_finish(const uint32_t *hdr, const long long *sums, int k, int f64, void *out, hipStream_t s)
+{
+    hipLaunchKernelGGL(k_cbdc_finish, dim3((unsigned)cdiv(k, 256)), dim3(256), 0, s, hdr, sums, k, f64, out);
+    LAUNCHCHK("k_cbdc_finish");
+    return NNC_OK;
+}
+
 // ------------------------------------------------------------------ C ABI
 static int cg_check(const char *fn, int64_t m, int64_t kdim, int64_t ncols, int label_bytes, int32_t k)
 {
@@ -679,12 +633,7 @@ extern "C" int nnc_cbmm_dx_f32(const float *g, int64_t m, int64_t kdim, const vo
                                (long long)ncols, centers_dev, (int)k, p.col_tiles, p.per_split, direct, out);
         LAUNCHCHK("k_cbdx_tiled");
     }
-    if (!direct) {
-        const long long mn = m * kdim;
-        const int rgrid = (int)std::max(1LL, std::min(cdiv(mn, 256), 8192LL));
-        hipLaunchKernelGGL(k_cbgrad_reduce, dim3(rgrid), dim3(256), 0, s, reinterpret_cast<const float *>(workspace), (long long)p.splits, mn, dx);
-        LAUNCHCHK("k_cbgrad_reduce");
-    }
+    if (!direct) return cbgrad_reduce(reinterpret_cast<const float *>(workspace), p.splits, m * kdim, dx, s);
     return NNC_OK;
 }
 
@@ -731,10 +680,7 @@ extern "C" int nnc_cbmm_dc_f32(const float *x, const float *g, int64_t m, int64_
     uint32_t *hdr = reinterpret_cast<uint32_t *>(workspace);
     unsigned long long *sums = reinterpret_cast<unsigned long long *>(reinterpret_cast<char *>(workspace) + CBG_HDR_BYTES);
     HIPCHK(hipMemsetAsync(workspace, 0, (size_t)need, s));
-    const long long nx = m * kdim, ng = m * ncols;
-    const int agrid = (int)std::max(1LL, std::min(cdiv(std::max(nx, ng), 256 * 8), 4LL * cu_count()));
-    hipLaunchKernelGGL(k_cbgrad_absmax, dim3(agrid), dim3(256), 0, s, x, nx, g, ng, hdr);
-    LAUNCHCHK("k_cbgrad_absmax");
+    if ((rc = cbgrad_absmax(x, m * kdim, g, m * ncols, hdr, s)) != NNC_OK) return rc;
     if (p.path == NNC_CBMM_STREAM) {
         gc->dc(p.aligned != 0, dim3((unsigned)p.col_tiles, (unsigned)p.row_tiles), (size_t)p.lds, s, x, g, (int)m, kdim, labels, ncols, k, p.rlog2,
                p.terms_log2, p.rows_per_group, hdr, sums);
@@ -749,7 +695,5 @@ extern "C" int nnc_cbmm_dc_f32(const float *x, const float *g, int64_t m, int64_
                                reinterpret_cast<const uint16_t *>(labels), (long long)ncols, (int)k, p.rlog2, p.terms_log2, p.col_tiles, p.per_split, hdr, sums);
         LAUNCHCHK("k_cbdc_tiled");
     }
-    hipLaunchKernelGGL(k_cbdc_finish, dim3((unsigned)cdiv(k, 256)), dim3(256), 0, s, hdr, reinterpret_cast<const long long *>(sums), (int)k, (int)(out_f64 != 0), dc);
-    LAUNCHCHK("k_cbdc_finish");
-    return NNC_OK;
+    return cbdc_finish(hdr, reinterpret_cast<const long long *>(sums), (int)k, (int)(out_f64 != 0), dc, s);
 }

@@ -1,0 +1,82 @@
+// nnc_cbgrad.hpp -- what the backward pass of the codebook matmul (nnc_cbgrad.hip) shares with that of its bitmap-sparse sibling
+// (nnc_cbspgrad.hip): the fixed-order wave reduction of the dx stream kernels, the fixed-point binning of dc (DESIGN.md section
+// 12) and the launches of the kernels both use (defined in nnc_cbgrad.hip).
+#pragma once
+#include "nnc_cbmm.hpp"
+
+#define CBG_FLAG_OK 0
+#define CBG_FLAG_NONFINITE 1   // x or g holds Inf / NaN, or m * max|x| * max|g| >= 2^127: dc is NaN
+#define CBG_FLAG_ZERO 2        // max|x| or max|g| is 0: every dW is 0
+#define CBG_HDR_BYTES 64       // dc workspace: {max|x| bits, max|g| bits, S, flag} then int64 sums[K] at byte 64
+
+// The m partials of every lane summed over the wave: a reduce-scatter (at lane bit 32 >> t the lanes with the bit set keep the upper
+// half of the rows they hold and take their partner's; then the rest of the butterfly on one value).  N + log2(64 / N) shuffles
+// instead of 6 N; every pair adds in a fixed order, so the sum depends on the data only.  Returns the total of row `row`, the
+// same on every lane of a group of 64 / N lanes.
+template <int N>
+__device__ __forceinline__ float wave_reduce_rows(float (&v)[N], int lane, int &row)
+{
+    row = 0;
+#pragma unroll
+    for (int t = 0; (N >> t) > 1; ++t) {
+        const int half = N >> (t + 1), bit = 32 >> t;
+        const bool up = (lane & bit) != 0;
+#pragma unroll
+        for (int j = 0; j < half; ++j) {
+            const float send = up ? v[j] : v[j + half];
+            const float keep = up ? v[j + half] : v[j];
+            v[j] = keep + __shfl_xor(send, bit);
+        }
+        row += up ? half : 0;
+    }
+    float s = v[0];
+#pragma unroll
+    for (int bit = 64 / N / 2; bit >= 1; bit >>= 1) s += __shfl_xor(s, bit);
+    return s;
+}
+
+// S of the dc sums from the maxima k_cbgrad_absmax left (uniform over the launch); flag as CBG_FLAG_*
+__device__ __forceinline__ int cbdc_shift(const uint32_t *amax, long long m, int terms_log2, int &flag)
+{
+    const uint32_t ux = amax[0], ug = amax[1];
+    flag = CBG_FLAG_OK;
+    if (ux >= 0x7F800000u || ug >= 0x7F800000u) {
+        flag = CBG_FLAG_NONFINITE;
+        return 0;
+    }
+    const double bound = (double)m * (double)__uint_as_float(ux) * (double)__uint_as_float(ug);
+    if (!(bound > 0.0)) {
+        flag = CBG_FLAG_ZERO;
+        return 0;
+    }
+    int P = 0;
+    (void)frexp(bound, &P);   // bound = f * 2^P, f in [0.5, 1): 2^P > bound
+    if (P > 127) {
+        flag = CBG_FLAG_NONFINITE;
+        return 0;
+    }
+    return 62 - terms_log2 - P;
+}
+
+// the fixed-point image of one dW: exact scaling by 2^S (|v * 2^S| < 2^63), nearest integer, ties to even
+__device__ __forceinline__ unsigned long long cbdc_fix(float v, int S) { return (unsigned long long)(long long)rintf(ldexpf(v, S)); }
+
+// the workgroup's bins into the global sums (integer atomics), copies summed in order; zero bins are skipped
+__device__ __forceinline__ void cbdc_flush(const unsigned long long *bins, int k, int rlog2, unsigned long long *__restrict__ sums)
+{
+    __syncthreads();
+    const int R = 1 << rlog2;
+    for (int j = threadIdx.x; j < k; j += blockDim.x) {
+        unsigned long long s = 0;
+        for (int r = 0; r < R; ++r) s += bins[(j << rlog2) + r];
+        if (s) atomicAdd(&sums[j], s);
+    }
+}
+
+// the shared kernels of nnc_cbgrad.hip, launched on `s` (NNC_OK, or the launch error):
+//   cbgrad_absmax  amax[0..1] = bits of max |x[0, nx)|, max |g[0, ng)| (amax zeroed by the caller)   k_cbgrad_absmax
+//   cbgrad_reduce  out[idx] = sum over s < splits of part[s * mn + idx], in split order                k_cbgrad_reduce
+//   cbdc_finish    dc[j] = ldexp(sums[j], -S), float64 or float32; NaN on CBG_FLAG_NONFINITE          k_cbdc_finish
+int cbgrad_absmax(const float *x, long long nx, const float *g, long long ng, uint32_t *amax, hipStream_t s);
+int cbgrad_reduce(const float *part, long long splits, long long mn, float *out, hipStream_t s);
+int cbdc_finish(const uint32_t *hdr, const long long *sums, int k, int f64, void *out, hipStream_t s);

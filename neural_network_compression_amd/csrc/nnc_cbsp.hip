@@ -25,40 +25,10 @@
 //   k_cbsp_tiled   m > 16: the W tile decoded from bitmap and symbols into LDS, then the FMA step of k_cbmm_tiled.
 //   k_cbsp_rowsum  m > 16: sum_i x[r, i], one workgroup per row, in a fixed order.
 //   k_cbsp_reduce  the split-K partials in split order, + c_z * row sum, + bias, ReLU.  No float atomics anywhere.
-#include "nnc_cbmm.hpp"
+#include "nnc_cbsp.hpp"
 
 #define SP_ROWS 64                // rows whose bitmap words one vector load brings to a wave
 #define SP_PLAN_LEN NNC_CBSP_PLAN_LEN
-
-// ------------------------------------------------------------------ the layout (host and device)
-struct SpLayout {
-    long long segs, g;            // segments per row, kdim * segs
-    long long off_lo, off_hi, off_sym, bytes;
-};
-
-static SpLayout sp_layout(long long kdim, long long ncols, int lb, long long nnz)
-{
-    SpLayout L{};
-    L.segs = cdiv(ncols, 64);
-    L.g = kdim * L.segs;
-    L.off_lo = 8 * L.g;
-    L.off_hi = L.off_lo + 4 * L.g;
-    L.off_sym = (L.off_hi + 4 * kdim + 255) / 256 * 256;
-    L.bytes = L.off_sym + nnz * lb;
-    return L;
-}
-
-// the exclusive count of stored symbols at segment g of row i (lo0 = lo[i * segs], h = hi[i])
-__device__ __forceinline__ long long sp_count(uint32_t lo, uint32_t lo0, uint32_t h)
-{
-    return (long long)(((uint64_t)h << 32) | lo) + (lo < lo0 ? (1LL << 32) : 0LL);
-}
-
-// bits of `word` below this lane (v_mbcnt_lo / v_mbcnt_hi)
-__device__ __forceinline__ uint32_t sp_rank(uint64_t word)
-{
-    return __builtin_amdgcn_mbcnt_hi((uint32_t)(word >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)word, 0u));
-}
 
 __device__ __forceinline__ uint32_t sp_label(const unsigned char *labels, int lb, long long idx)
 {
@@ -246,18 +216,6 @@ static long long sp_part_bytes(const SpPlan &p, long long m, long long ncols)
 static int64_t sp_ws_bytes(const SpPlan &p, long long m, long long ncols) { return sp_part_bytes(p, m, ncols) + sp_rsplits(p) * m * 4; }
 
 // ------------------------------------------------------------------ device helpers
-// the d table: stage[j] = c[j] - c_z (j < k), -c_z past k; then `1 << cshift` copies of each entry as in k_cbmm_stream
-__device__ __forceinline__ float sp_cz(const float *__restrict__ centers, int k, int z) { return z < k ? centers[z] : 0.0f; }
-
-__device__ __forceinline__ void sp_fill(float *tab, float *stage, const float *__restrict__ centers, int k, float cz, int entries, int cshift)
-{
-    for (int j = threadIdx.x; j < entries; j += blockDim.x) stage[j] = (j < k ? centers[j] : 0.0f) - cz;
-    __syncthreads();
-    const int words = entries << cshift;
-#pragma unroll 8
-    for (int w = threadIdx.x; w < words; w += blockDim.x) tab[w] = stage[w >> cshift];
-}
-
 __device__ __forceinline__ float sp_epilogue(float acc, float cz, float rs, const float *__restrict__ bias, long long c, int relu)
 {
     float v = cz != 0.0f ? cz * rs + acc : acc;
@@ -384,20 +342,6 @@ __global__ __launch_bounds__(CB_THREADS) void k_cbsp_stream(const float *__restr
         if (r >= m) continue;
         if (direct) out[(long long)r * ncols + col] = sp_epilogue(acc[r], cz, rs[r], bias, col, relu);
         else out[((long long)blockIdx.y * m + r) * ncols + col] = acc[r];
-    }
-}
-
-// tb_tile_fma with the products of skipped weights (kept[kk][n] == 0) left out
-__device__ __forceinline__ void tb_tile_fma_masked(const float *xs, const float *ws, const unsigned char *kept, int tx, int ty, float (&acc)[8][8])
-{
-    for (int kk = 0; kk < TB_K; ++kk) {
-#pragma unroll
-        for (int a = 0; a < 8; ++a) {
-            const float av = xs[kk * TB_M + ty * 8 + a];
-#pragma unroll
-            for (int b = 0; b < 8; ++b)
-                if (kept[kk * TB_N + tx * 8 + b]) acc[a][b] = __builtin_fmaf(av, ws[kk * TB_N + tx * 8 + b], acc[a][b]);
-        }
     }
 }
 
@@ -542,9 +486,11 @@ __global__ __launch_bounds__(256) void k_cbsp_reduce(const float *__restrict__ p
 }
 
 // ------------------------------------------------------------------ C ABI
-static bool sp_size_ok(int64_t kdim, int64_t ncols)
+int cbsp_rowsum(const float *x, long long m, long long kdim, float *rs, hipStream_t s)
 {
-    return kdim <= (1LL << 40) && ncols < (1LL << 32) && (ncols == 0 || kdim <= (1LL << 40) / cdiv(ncols, 64));
+    hipLaunchKernelGGL(k_cbsp_rowsum, dim3((unsigned)std::min<long long>(m, 65536)), dim3(256), 0, s, x, m, kdim, rs);
+    LAUNCHCHK("k_cbsp_rowsum");
+    return NNC_OK;
 }
 
 static int sp_check_shape(const char *fn, int64_t kdim, int64_t ncols, int label_bytes)
@@ -552,12 +498,6 @@ static int sp_check_shape(const char *fn, int64_t kdim, int64_t ncols, int label
     if (kdim < 0 || ncols < 0) return fail(NNC_EINVAL, std::string(fn) + ": negative size");
     if (label_bytes != 1 && label_bytes != 2) return fail(NNC_EINVAL, std::string(fn) + ": label_bytes must be 1 or 2");
     if (!sp_size_ok(kdim, ncols)) return fail(NNC_EINVAL, std::string(fn) + ": size too large (ncols < 2^32, kdim * ceil(ncols / 64) <= 2^40)");
-    return NNC_OK;
-}
-
-static int sp_check_z(const char *fn, int32_t z, int label_bytes)
-{
-    if (z < 0 || z >= (label_bytes == 1 ? 256 : 65536)) return fail(NNC_EINVAL, std::string(fn) + ": zero_symbol outside the label range");
     return NNC_OK;
 }
 
@@ -741,8 +681,7 @@ extern "C" int nnc_cbsp_f32(const float *x, int64_t m, int64_t kdim, const void 
            bias_dev, relu, direct, out, direct ? nullptr : rsp);
         LAUNCHCHK("k_cbsp_stream");
     } else {
-        hipLaunchKernelGGL(k_cbsp_rowsum, dim3((unsigned)std::min<long long>(m, 65536)), dim3(256), 0, s, x, (long long)m, (long long)kdim, rsp);
-        LAUNCHCHK("k_cbsp_rowsum");
+        if ((rc = cbsp_rowsum(x, m, kdim, rsp, s)) != NNC_OK) return rc;
         const dim3 grid((unsigned)(p.col_tiles * p.row_tiles), (unsigned)p.splits);
         const uint64_t *bm = reinterpret_cast<const uint64_t *>(base);
         const uint32_t *lo = reinterpret_cast<const uint32_t *>(base + L.off_lo), *hi = reinterpret_cast<const uint32_t *>(base + L.off_hi);

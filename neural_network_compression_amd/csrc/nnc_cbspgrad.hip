@@ -1,0 +1,717 @@
+// nnc_cbspgrad.hip -- the backward pass of the bitmap-sparse codebook matmul (nnc_cbsp.hip) from the packed form: the indices are
+// never unpacked and W is never decoded (include/nnc.h, nnc_cbsp_dx_f32 / nnc_cbsp_dc_f32).  With the
+// skipped symbol z, c_z = c[z] (0 if z >= K), d[s] = float32(c[s] - c_z) (-c_z for s >= K) and g = dL/dy:
+//
+//   dx[r, i] = c_z * sum_o g[r, o] + sum over the stored (i, o) of g[r, o] * d[L[i, o]]   the Jacobian of nnc_cbsp_f32; with
+//                                                                                        c_z == 0 the rank-1 term is dropped
+//   dc[k]    = nnc_cbmm_dc_f32 on the unpacked labels, bit for bit: every dW[i, o] is formed in float32 as k_cbdc_stream /
+//              k_cbdc_tiled form it and binned as rint(dW * 2^S) with the same S (the same splits of m and T); a skipped (i, o)
+//              falls into bin z (none if z >= K).  Integer sums do not depend on order.
+//
+//   k_cbspdx_stream  m <= 16.  A workgroup owns a block of E segments (64 lanes x E columns of g in registers, E * MT <= 32) and
+//                    a group of index rows.  A wave takes its rows in batches of 64 / E: the bitmap words and counts of a batch come
+//                    in one vector load (lane = row x segment; the next batch's are in flight while this one is consumed) and are
+//                    broadcast by v_readlane; a lane's symbol is at count + v_mbcnt(word), its d from the per-bank LDS table; the m
+//                    partials of a row are reduced over the wave in a fixed order (wave_reduce_rows).  A skipped weight forms no
+//                    product.  Column blocks are the splits, summed in block order by k_cbgrad_reduce.
+//   k_cbspdx_tiled   m > 16.  128 (r) x 128 (i) output tiles; the W^T tile is decoded into LDS from bitmap and symbols (d where
+//                    stored, 0 where skipped), then tb_tile_fma (the masked step for a g tile holding Inf / NaN).  ncols is split
+//                    into whole segments by a count that depends on the shape alone.
+//   k_cbspdx_rank1   dx += c_z * sum_o g[r, o], the row sums of g in a fixed order (k_cbsp_rowsum); nothing when c_z == 0.
+//   k_cbspdc_stream  m <= 16.  The grid and loads of k_cbspdx_stream; x[r, i] by v_readlane; dW[i, o] as k_cbdc_stream forms it.
+//                    A stored weight's image goes into the replicated LDS bins (64-bit integer atomics), a skipped one's into a
+//                    per-lane int64 register for bin z, flushed once per lane at the end.
+//   k_cbspdc_tiled   m > 16.  k_cbdc_tiled's tiles and splits of m; each of a thread's 64 values takes its label from the bitmap
+//                    word, the count and the popcount; the skipped ones are summed in a register.
+// k_cbgrad_absmax, k_cbdc_finish and k_cbgrad_reduce are nnc_cbgrad.hip's.  No float atomics; no host read.
+#include "nnc_cbgrad.hpp"
+#include "nnc_cbsp.hpp"
+
+// ------------------------------------------------------------------ plans (host)
+struct SgPlan {
+    int path;                 // NNC_CBMM_NONE / _STREAM / _TILED / _ZERO
+    int mt, segs;             // stream: rows of m per launch (a power of two >= m), segments per column block
+    int entries, cshift;      // dx: the LDS d table (entries x (1 << cshift) copies); tiled: k + 1 entries
+    int rlog2;                // dc: 1 << rlog2 copies of every LDS bin
+    long long col_tiles, row_tiles;   // stream: column blocks x row groups; tiled: tiles
+    long long splits, per_split;      // dx: splits of ncols (columns per split); dc: splits of m (rows of m per split)
+    long long rows_per_group;         // stream: index rows per workgroup
+    int terms_log2;                   // dc: T of nnc_cbmm_dc_plan
+    long long lds;
+};
+
+static int sg_mt(long long m) { return m <= 1 ? 1 : (m <= 2 ? 2 : (m <= 4 ? 4 : (m <= 8 ? 8 : 16))); }
+
+// segments per column block: at most 32 g values per lane (the MT = 16 instantiation of k_cbdx_stream keeps 64 and spills)
+__host__ __device__ constexpr int sg_segs(int mt) { return mt <= 4 ? 8 : 32 / mt; }
+
+static void sg_stream_grid(SgPlan &p, long long m, long long kdim, long long ncols, int cus)
+{
+    cus = std::max(1, std::min(cus, CB_PLAN_CUS));
+    p.path = NNC_CBMM_STREAM;
+    p.mt = sg_mt(m);
+    p.segs = sg_segs(p.mt);
+    p.col_tiles = cdiv(cdiv(ncols, 64), p.segs);
+    const long long batch = 64 / p.segs;   // index rows per batch of a wave
+    const long long groups = std::max(1LL, std::min(cdiv(2LL * cus, p.col_tiles), cdiv(kdim, (long long)CB_WAVES * batch)));
+    p.rows_per_group = cdiv(kdim, groups);
+    p.row_tiles = cdiv(kdim, p.rows_per_group);
+}
+
+static SgPlan sg_dx_plan(long long m, long long kdim, long long ncols, int lb, int k, int cus)
+{
+    SgPlan p{};
+    if (m == 0 || kdim == 0) return p;                       // NNC_CBMM_NONE: dx is empty
+    if (ncols == 0) {                                        // dx = 0
+        p.path = NNC_CBMM_ZERO;
+        return p;
+    }
+    if (m <= CB_SKINNY_M) {
+        sg_stream_grid(p, m, kdim, ncols, cus);
+        p.splits = p.col_tiles;                              // one split per column block
+        p.per_split = 64LL * p.segs;
+        if (lb == 1) {
+            p.entries = 256;
+            p.cshift = __builtin_ctz(CB_U8_COPIES);
+        } else {
+            p.entries = k + 1;
+            while ((1 << p.cshift) < CB_U8_COPIES && (long long)p.entries << (p.cshift + 1) <= CB_U16_WORDS) ++p.cshift;
+        }
+        p.lds = ((long long)p.entries << p.cshift) * 4 + (long long)p.entries * 4;
+    } else {
+        p.path = NNC_CBMM_TILED;
+        p.col_tiles = cdiv(kdim, TB_N);
+        p.row_tiles = cdiv(m, TB_M);
+        long long s = std::min({cdiv(2LL * CB_PLAN_CUS, p.col_tiles * p.row_tiles), ncols / (16 * TB_K), 16LL});
+        s = std::max(1LL, s);
+        p.per_split = cdiv(cdiv(ncols, s), 64) * 64;         // whole segments: a thread's 4 columns never straddle two words
+        p.splits = cdiv(ncols, p.per_split);
+        p.entries = k + 1;
+        p.lds = (long long)(TB_K * TB_M + TB_K * TB_N + k + 1) * 4 + TB_K * TB_N;
+    }
+    return p;
+}
+
+// the dx workspace: [partials: splits x m x kdim floats, when split, 256-byte aligned][row sums of g: m floats]
+static long long sg_part_bytes(const SgPlan &p, long long m, long long kdim) { return p.splits > 1 ? (p.splits * m * kdim * 4 + 255) / 256 * 256 : 0; }
+static int64_t sg_dx_ws_bytes(const SgPlan &p, long long m, long long kdim)
+{
+    return p.path == NNC_CBMM_STREAM || p.path == NNC_CBMM_TILED ? sg_part_bytes(p, m, kdim) + m * 4 : 0;
+}
+
+// The splits of m, the bin copies and T are nnc_cbmm_dc_plan's for the same shape (so S, every image and every sum are the dense
+// call's).  NNC_OK, or that plan's error.
+static int sg_dc_plan(long long m, long long kdim, long long ncols, int lb, int k, int cus, SgPlan &p)
+{
+    p = SgPlan{};
+    if (m == 0 || kdim == 0 || ncols == 0) {                 // no terms: dc = 0
+        p.path = NNC_CBMM_ZERO;
+        return NNC_OK;
+    }
+    int64_t d[NNC_CBDC_PLAN_LEN];
+    const int rc = nnc_cbmm_dc_plan(m, kdim, ncols, lb, k, CB_PLAN_CUS, 0, d);
+    if (rc != NNC_OK) return rc;
+    p.splits = d[NNC_CBDC_P_SPLITS];
+    p.per_split = d[NNC_CBDC_P_RPS];
+    p.terms_log2 = (int)d[NNC_CBDC_P_TERMS_LOG2];
+    p.rlog2 = __builtin_ctzll((unsigned long long)d[NNC_CBDC_P_COPIES]);
+    const long long bins = ((long long)k << p.rlog2) * 8;
+    if (m <= CB_SKINNY_M) {
+        sg_stream_grid(p, m, kdim, ncols, cus);
+        p.lds = bins;
+    } else {
+        p.path = NNC_CBMM_TILED;
+        p.col_tiles = cdiv(ncols, TB_N);
+        p.row_tiles = cdiv(kdim, TB_M);
+        p.lds = (long long)(TB_K * TB_M + TB_K * TB_N) * 4 + bins;
+    }
+    return NNC_OK;
+}
+
+static int64_t sg_dc_ws_bytes(const SgPlan &p, int k) { return p.path == NNC_CBMM_STREAM || p.path == NNC_CBMM_TILED ? CBG_HDR_BYTES + 8LL * k : 0; }
+
+// ------------------------------------------------------------------ device helpers
+// The words and counts of a batch of 64 / E rows x E segments: lane l holds those of row ib + l / E, segment blk * E + l % E
+// (0 past the wave's rows or the matrix), broadcast later by v_readlane.
+template <int E>
+__device__ __forceinline__ void sg_batch(const uint64_t *__restrict__ bitmap, const uint32_t *__restrict__ lo, const uint32_t *__restrict__ hi,
+                                         long long segs, long long blk, long long ib, long long i1, int lane, uint64_t &word, long long &cnt)
+{
+    const long long i = ib + lane / E, sg = blk * E + lane % E;
+    word = 0;
+    cnt = 0;
+    if (i < i1 && sg < segs) {
+        const long long gi = i * segs;
+        word = bitmap[gi + sg];
+        cnt = sp_count(lo[gi + sg], lo[gi], hi[i]);
+    }
+}
+
+// lane `src`'s 64-bit value, on every lane
+__device__ __forceinline__ uint64_t sg_bcast(uint64_t v, int src)
+{
+    return ((uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(v >> 32), src) << 32) | (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)v, src);
+}
+
+// The UR rows u0 .. u0 + UR - 1 of a batch: per row and segment the lane's bit and its symbol (0 where the bit is clear).  A
+// symbol past the nnz stored ones (a malformed form) counts as skipped, as nnc_cbsp_unpack reads it.  The symbol loads of the
+// UR x E (row, segment) pairs are in flight together.
+template <typename LT, int E, int UR>
+__device__ __forceinline__ void sg_symbols(uint64_t wl, long long cl, int u0, int lane, const LT *__restrict__ sym, long long nnz, uint32_t (&bits)[UR][E],
+                                           uint32_t (&sv)[UR][E])
+{
+#pragma unroll
+    for (int u = 0; u < UR; ++u)
+#pragma unroll
+        for (int e = 0; e < E; ++e) {
+            const int src = (u0 + u) * E + e;
+            const uint64_t word = sg_bcast(wl, src);
+            const long long pos = (long long)sg_bcast((uint64_t)cl, src) + sp_rank(word);
+            bits[u][e] = (uint32_t)(word >> lane) & 1u;
+            sv[u][e] = 0;
+            if (bits[u][e] && pos < nnz) sv[u][e] = sym[pos];
+            else bits[u][e] = 0;
+        }
+}
+
+// ------------------------------------------------------------------ dx, m <= 16
+// grid (column blocks, row groups), CB_THREADS threads.  out: dx (one column block) or the partials [block][m][kdim].
+template <typename LT, int MT>
+__global__ __launch_bounds__(CB_THREADS) void k_cbspdx_stream(const float *__restrict__ g, int m, long long kdim, const uint64_t *__restrict__ bitmap,
+                                                              const uint32_t *__restrict__ lo, const uint32_t *__restrict__ hi, const LT *__restrict__ sym,
+                                                              long long nnz, long long ncols, long long segs, const float *__restrict__ centers, int k,
+                                                              int z, int entries, int cshift, long long rows_per_group, int direct, float *__restrict__ out)
+{
+    constexpr int E = sg_segs(MT), RB = 64 / E, UR = E >= 8 ? 1 : 8 / E;   // segments per block, rows per batch, rows per step
+    extern __shared__ float smem[];
+    float *tab = smem;
+    float *stage = smem + (entries << cshift);
+    sp_fill(tab, stage, centers, k, sp_cz(centers, k, z), entries, cshift);
+
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const long long blk = blockIdx.x;
+    float gv[MT][E];
+#pragma unroll
+    for (int e = 0; e < E; ++e) {
+        const long long col = (blk * E + e) * 64 + lane;
+#pragma unroll
+        for (int r = 0; r < MT; ++r) gv[r][e] = (r < m && col < ncols) ? g[(long long)r * ncols + col] : 0.0f;
+    }
+
+    const long long g_lo = (long long)blockIdx.y * rows_per_group, g_hi = std::min(kdim, g_lo + rows_per_group);
+    const long long per_wave = (g_hi - g_lo + CB_WAVES - 1) / CB_WAVES;
+    const long long i0 = std::min(g_hi, g_lo + wave * per_wave), i1 = std::min(g_hi, i0 + per_wave);
+    float *dst = direct ? out : out + blk * m * kdim;
+    __syncthreads();
+
+    uint64_t wn;
+    long long cn;
+    sg_batch<E>(bitmap, lo, hi, segs, blk, i0, i1, lane, wn, cn);
+    for (long long ib = i0; ib < i1; ib += RB) {
+        const uint64_t wl = wn;
+        const long long cl = cn;
+        if (ib + RB < i1) sg_batch<E>(bitmap, lo, hi, segs, blk, ib + RB, i1, lane, wn, cn);   // the next batch in flight
+        const int nb = (int)std::min((long long)RB, i1 - ib);
+        for (int u0 = 0; u0 < nb; u0 += UR) {
+            uint32_t bits[UR][E], sv[UR][E];
+            sg_symbols<LT, E, UR>(wl, cl, u0, lane, sym, nnz, bits, sv);
+#pragma unroll
+            for (int u = 0; u < UR; ++u) {
+                float p[MT];
+#pragma unroll
+                for (int r = 0; r < MT; ++r) p[r] = 0.0f;
+#pragma unroll
+                for (int e = 0; e < E; ++e) {
+                    const float dv = tab[CbTable<LT>::index(sv[u][e], k, cshift, lane)];
+#pragma unroll
+                    for (int r = 0; r < MT; ++r) p[r] = bits[u][e] ? __builtin_fmaf(gv[r][e], dv, p[r]) : p[r];   // skipped: no product
+                }
+                int row;
+                const float v = wave_reduce_rows<MT>(p, lane, row);
+                if (u0 + u < nb && (lane & (64 / MT - 1)) == 0 && row < m) dst[(long long)row * kdim + ib + u0 + u] = v;
+            }
+        }
+    }
+}
+
+// ------------------------------------------------------------------ dx, m > 16
+// grid (kdim tiles * m tiles, splits of ncols), 256 threads; thread (tx, ty) owns rows ty*8.. (of g) and columns tx*8.. (i) of the tile.
+template <typename LT>
+__global__ __launch_bounds__(256) void k_cbspdx_tiled(const float *__restrict__ g, long long m, long long kdim, const uint64_t *__restrict__ bitmap,
+                                                      const uint32_t *__restrict__ lo, const uint32_t *__restrict__ hi, const LT *__restrict__ sym,
+                                                      long long nnz, long long ncols, long long segs, const float *__restrict__ centers, int k, int z,
+                                                      long long col_tiles, long long cols_per_split, int direct, float *__restrict__ out)
+{
+    extern __shared__ float smem[];
+    float *gs = smem;                      // [TB_K][TB_M]: g[m0 + r, o]
+    float *ws = gs + TB_K * TB_M;          // [TB_K][TB_N]: d of the stored W[n0 + i, o], 0 where skipped
+    float *tab = ws + TB_K * TB_N;         // k + 1 entries: d, then -c_z
+    unsigned char *kept = reinterpret_cast<unsigned char *>(tab + k + 1);   // [TB_K][TB_N]: 1 where the weight is stored
+    const float cz = sp_cz(centers, k, z);
+    for (int j = threadIdx.x; j <= k; j += 256) tab[j] = (j < k ? centers[j] : 0.0f) - cz;
+
+    const int t = threadIdx.x, tx = t & 15, ty = t >> 4;
+    const long long n0 = (blockIdx.x % col_tiles) * TB_N, m0 = (blockIdx.x / col_tiles) * TB_M;
+    const long long o_lo = (long long)blockIdx.y * cols_per_split, o_hi = std::min(ncols, o_lo + cols_per_split);
+    float acc[8][8];
+#pragma unroll
+    for (int a = 0; a < 8; ++a)
+#pragma unroll
+        for (int b = 0; b < 8; ++b) acc[a][b] = 0.0f;
+
+    const int lr = t >> 1, lq = (t & 1) * 4;   // g tile: row lr, o lq..lq+3; W^T tile: index row n0 + lr, o lq..lq+3 (one segment)
+    int nonfinite = 0;
+    for (long long ob = o_lo; ob < o_hi; ob += TB_K) {
+        __syncthreads();
+        {
+            const long long gr = m0 + lr, wi = n0 + lr, go = ob + lq;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const float gv = (gr < m && go + j < o_hi) ? g[gr * ncols + go + j] : 0.0f;
+                nonfinite |= !__builtin_isfinite(gv);
+                gs[(lq + j) * TB_M + lr] = gv;
+            }
+            float v[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+            uint32_t keep = 0;
+            if (wi < kdim && go < o_hi) {   // (bits past ncols are 0; a split ends on a segment boundary)
+                const long long gi = wi * segs, sg = go >> 6;
+                const int b0 = (int)(go & 63);
+                const uint64_t word = bitmap[gi + sg];
+                long long pos = sp_count(lo[gi + sg], lo[gi], hi[wi]) + __popcll(word & ((1ULL << b0) - 1));
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    if ((word >> (b0 + j)) & 1) {
+                        if (pos < nnz) {
+                            v[j] = tab[std::min((uint32_t)sym[pos], (uint32_t)k)];
+                            keep |= 1u << j;
+                        }
+                        ++pos;
+                    }
+                }
+            }
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                ws[(lq + j) * TB_N + lr] = v[j];
+                kept[(lq + j) * TB_N + lr] = (unsigned char)((keep >> j) & 1);
+            }
+        }
+        // a skipped weight is absent: where the g tile holds an Inf or NaN the FMA must not form g * 0 at a skipped position
+        if (__syncthreads_or(nonfinite)) tb_tile_fma_masked(gs, ws, kept, tx, ty, acc);
+        else tb_tile_fma(gs, ws, tx, ty, acc);
+        nonfinite = 0;
+    }
+    float *dst = direct ? out : out + (long long)blockIdx.y * m * kdim;
+#pragma unroll
+    for (int a = 0; a < 8; ++a) {
+        const long long r = m0 + ty * 8 + a;
+#pragma unroll
+        for (int b = 0; b < 8; ++b) {
+            const long long c = n0 + tx * 8 + b;
+            if (r < m && c < kdim) dst[r * kdim + c] = acc[a][b];
+        }
+    }
+}
+
+// ------------------------------------------------------------------ dx += c_z * row sums of g (as sp_epilogue adds its rank-1 term)
+__global__ __launch_bounds__(256) void k_cbspdx_rank1(float *__restrict__ dx, long long m, long long kdim, const float *__restrict__ rs,
+                                                      const float *__restrict__ centers, int k, int z)
+{
+    const float cz = sp_cz(centers, k, z);
+    if (cz == 0.0f) return;   // the rank-1 term is dropped (uniform over the launch)
+    const long long mn = m * kdim;
+    for (long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x; idx < mn; idx += (long long)gridDim.x * blockDim.x)
+        dx[idx] = cz * rs[idx / kdim] + dx[idx];
+}
+
+// ------------------------------------------------------------------ dc, m <= 16
+// grid (column blocks, row groups), CB_THREADS threads.  LDS: the bins, [k][1 << rlog2] int64.
+template <typename LT, int MT>
+__global__ __launch_bounds__(CB_THREADS) void k_cbspdc_stream(const float *__restrict__ x, const float *__restrict__ g, int m, long long kdim,
+                                                              const uint64_t *__restrict__ bitmap, const uint32_t *__restrict__ lo,
+                                                              const uint32_t *__restrict__ hi, const LT *__restrict__ sym, long long nnz, long long ncols,
+                                                              long long segs, int k, int z, int rlog2, int terms_log2, long long rows_per_group,
+                                                              uint32_t *__restrict__ hdr, unsigned long long *__restrict__ sums)
+{
+    constexpr int E = sg_segs(MT), RB = 64 / E, UR = E >= 8 ? 1 : 8 / E;
+    extern __shared__ unsigned long long bins[];
+    int flag;
+    const int S = cbdc_shift(hdr, m, terms_log2, flag);
+    if (blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0) {
+        hdr[2] = (uint32_t)S;
+        hdr[3] = (uint32_t)flag;
+    }
+    if (flag != CBG_FLAG_OK) return;   // (uniform over the launch)
+    for (int j = threadIdx.x; j < (k << rlog2); j += CB_THREADS) bins[j] = 0ull;
+
+    const int lane = threadIdx.x & 63;
+    const int rep = lane & ((1 << rlog2) - 1);
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const long long blk = blockIdx.x;
+    float gv[MT][E];
+    bool incol[E];
+#pragma unroll
+    for (int e = 0; e < E; ++e) {
+        const long long col = (blk * E + e) * 64 + lane;
+        incol[e] = col < ncols;
+#pragma unroll
+        for (int r = 0; r < MT; ++r) gv[r][e] = (r < m && incol[e]) ? g[(long long)r * ncols + col] : 0.0f;
+    }
+
+    const long long g_lo = (long long)blockIdx.y * rows_per_group, g_hi = std::min(kdim, g_lo + rows_per_group);
+    const long long per_wave = (g_hi - g_lo + CB_WAVES - 1) / CB_WAVES;
+    const long long i0 = std::min(g_hi, g_lo + wave * per_wave), i1 = std::min(g_hi, i0 + per_wave);
+    unsigned long long skip = 0;   // the images of the lane's skipped weights: bin z
+    __syncthreads();
+
+    uint64_t wn;
+    long long cn;
+    sg_batch<E>(bitmap, lo, hi, segs, blk, i0, i1, lane, wn, cn);
+    for (long long ib = i0; ib < i1; ib += RB) {
+        const uint64_t wl = wn;
+        const long long cl = cn;
+        if (ib + RB < i1) sg_batch<E>(bitmap, lo, hi, segs, blk, ib + RB, i1, lane, wn, cn);   // the next batch in flight
+        const int nb = (int)std::min((long long)RB, i1 - ib);
+        for (int u0 = 0; u0 < nb; u0 += UR) {
+            // x[r, i] of the UR rows: lane f holds x[f / UR, ib + u0 + f % UR] (f < MT * UR <= 64), broadcast by v_readlane
+            float xa;
+            {
+                const int r0 = lane / UR;
+                const long long i = ib + u0 + lane % UR;
+                xa = (r0 < m && i < i1) ? x[(long long)r0 * kdim + i] : 0.0f;
+            }
+            uint32_t bits[UR][E], sv[UR][E];
+            sg_symbols<LT, E, UR>(wl, cl, u0, lane, sym, nnz, bits, sv);
+#pragma unroll
+            for (int u = 0; u < UR; ++u) {
+                if (u0 + u >= nb) break;   // (uniform)
+                float xv[MT];
+#pragma unroll
+                for (int r = 0; r < MT; ++r) xv[r] = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, xa), r * UR + u));
+#pragma unroll
+                for (int e = 0; e < E; ++e) {
+                    float d = 0.0f;
+#pragma unroll
+                    for (int r = 0; r < MT; ++r) d = __builtin_fmaf(xv[r], gv[r][e], d);   // dW[i, o], r ascending (k_cbdc_stream)
+                    const unsigned long long img = cbdc_fix(d, S);
+                    if (bits[u][e]) {
+                        if (sv[u][e] < (uint32_t)k) atomicAdd(&bins[(sv[u][e] << rlog2) + rep], img);
+                    } else if (incol[e]) {
+                        skip += img;
+                    }
+                }
+            }
+        }
+    }
+    if (z < k && skip) atomicAdd(&bins[((uint32_t)z << rlog2) + rep], skip);
+    cbdc_flush(bins, k, rlog2, sums);
+}
+
+// ------------------------------------------------------------------ dc, m > 16
+// grid (ncols tiles * kdim tiles, splits of m), 256 threads; the tiles and the FMA of k_cbdc_tiled, so the same 64 values per
+// thread; their labels come from the bitmap: a thread's 8 columns tx*8.. lie in one segment.
+template <typename LT>
+__global__ __launch_bounds__(256) void k_cbspdc_tiled(const float *__restrict__ x, const float *__restrict__ g, long long m, long long kdim,
+                                                      const uint64_t *__restrict__ bitmap, const uint32_t *__restrict__ lo, const uint32_t *__restrict__ hi,
+                                                      const LT *__restrict__ sym, long long nnz, long long ncols, long long segs, int k, int z, int rlog2,
+                                                      int terms_log2, long long col_tiles, long long rows_per_split, uint32_t *__restrict__ hdr,
+                                                      unsigned long long *__restrict__ sums)
+{
+    extern __shared__ float smem[];
+    float *xs = smem;                      // [TB_K][TB_M]: x[r, i0 + i]
+    float *gs = xs + TB_K * TB_M;          // [TB_K][TB_N]: g[r, o0 + o]
+    unsigned long long *bins = reinterpret_cast<unsigned long long *>(gs + TB_K * TB_N);
+    int flag;
+    const int S = cbdc_shift(hdr, m, terms_log2, flag);
+    if (blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0) {
+        hdr[2] = (uint32_t)S;
+        hdr[3] = (uint32_t)flag;
+    }
+    if (flag != CBG_FLAG_OK) return;
+    for (int j = threadIdx.x; j < (k << rlog2); j += 256) bins[j] = 0ull;
+
+    const int t = threadIdx.x, tx = t & 15, ty = t >> 4;
+    const long long o0 = (blockIdx.x % col_tiles) * TB_N, i0 = (blockIdx.x / col_tiles) * TB_M;
+    const long long r_lo = (long long)blockIdx.y * rows_per_split, r_hi = std::min(m, r_lo + rows_per_split);
+    float acc[8][8];
+#pragma unroll
+    for (int a = 0; a < 8; ++a)
+#pragma unroll
+        for (int b = 0; b < 8; ++b) acc[a][b] = 0.0f;
+
+    const int lk = t >> 5, lc = (t & 31) * 4;   // both tiles: row r = rb + lk, columns lc..lc+3 (coalesced)
+    for (long long rb = r_lo; rb < r_hi; rb += TB_K) {
+        __syncthreads();
+        {
+            const long long r = rb + lk;
+            const bool in_r = r < r_hi;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const long long ii = i0 + lc + j, oo = o0 + lc + j;
+                xs[lk * TB_M + lc + j] = (in_r && ii < kdim) ? x[r * kdim + ii] : 0.0f;
+                gs[lk * TB_N + lc + j] = (in_r && oo < ncols) ? g[r * ncols + oo] : 0.0f;
+            }
+        }
+        __syncthreads();
+        tb_tile_fma(xs, gs, tx, ty, acc);
+    }
+    const int rep = t & ((1 << rlog2) - 1);
+    const long long ob = o0 + tx * 8, sg = ob >> 6;
+    const int b0 = (int)(ob & 63);
+    unsigned long long skip = 0;   // the images of the thread's skipped weights: bin z
+#pragma unroll
+    for (int a = 0; a < 8; ++a) {
+        const long long i = i0 + ty * 8 + a;
+        if (i >= kdim || ob >= ncols) continue;
+        const long long gi = i * segs;
+        const uint64_t word = bitmap[gi + sg];
+        long long pos = sp_count(lo[gi + sg], lo[gi], hi[i]) + __popcll(word & ((1ULL << b0) - 1));
+#pragma unroll
+        for (int b = 0; b < 8; ++b) {
+            if (ob + b >= ncols) continue;
+            const unsigned long long img = cbdc_fix(acc[a][b], S);
+            if ((word >> (b0 + b)) & 1) {
+                const uint32_t l = pos < nnz ? (uint32_t)sym[pos] : (uint32_t)z;   // (past nnz: skipped, as nnc_cbsp_unpack reads it)
+                ++pos;
+                if (l < (uint32_t)k) atomicAdd(&bins[(l << rlog2) + rep], img);
+            } else {
+                skip += img;
+            }
+        }
+    }
+    if (z < k && skip) atomicAdd(&bins[((uint32_t)z << rlog2) + rep], skip);
+    cbdc_flush(bins, k, rlog2, sums);
+}
+
+// ------------------------------------------------------------------ C ABI
+static int sg_check(const char *fn, int64_t m, int64_t kdim, int64_t ncols, int label_bytes, int32_t k)
+{
+    const std::string f(fn);
+    if (m < 0 || kdim < 0 || ncols < 0) return fail(NNC_EINVAL, f + ": negative size");
+    if (label_bytes != 1 && label_bytes != 2) return fail(NNC_EINVAL, f + ": label_bytes must be 1 or 2");
+    if (k < 1 || k > NNC_KMAX) return fail(NNC_EINVAL, f + ": k outside 1..NNC_KMAX");
+    if (label_bytes == 1 && k > 256) return fail(NNC_EINVAL, f + ": k > 256 needs 2-byte labels");
+    if (m > (1LL << 40) || !sp_size_ok(kdim, ncols))
+        return fail(NNC_EINVAL, f + ": size too large (m <= 2^40, ncols < 2^32, kdim * ceil(ncols / 64) <= 2^40)");
+    return NNC_OK;
+}
+
+// the arguments both calls share: the form (nnz, size, alignment), the skipped symbol
+static int sg_check_form(const char *fn, int64_t m, int64_t kdim, int64_t ncols, int label_bytes, int32_t z, int64_t nnz, const void *packed,
+                         int64_t packed_bytes)
+{
+    int rc = sp_check_z(fn, z, label_bytes);
+    if (rc != NNC_OK) return rc;
+    const std::string f(fn);
+    if (nnz < 0 || nnz > kdim * ncols) return fail(NNC_EINVAL, f + ": nnz outside 0..kdim * ncols");
+    if (packed_bytes < sp_layout(kdim, ncols, label_bytes, nnz).bytes)
+        return fail(NNC_EINVAL, f + ": packed buffer smaller than nnc_cbsp_pack_bytes(kdim, ncols, label_bytes, nnz)");
+    if (m > 0 && kdim > 0 && ncols > 0 && !packed) return fail(NNC_EINVAL, f + ": packed is NULL");
+    if (m > 0 && kdim > 0 && ncols > 0 && reinterpret_cast<uintptr_t>(packed) % 256) return fail(NNC_EINVAL, f + ": packed must be 256-byte aligned");
+    return NNC_OK;
+}
+
+template <typename LT, int MT>
+static void launch_sg_dx(dim3 grid, size_t lds, hipStream_t s, const float *g, int m, long long kdim, const unsigned char *base, const SpLayout &L,
+                         long long nnz, long long ncols, const float *centers, int k, int z, const SgPlan &p, int direct, float *out)
+{
+    hipLaunchKernelGGL((k_cbspdx_stream<LT, MT>), grid, dim3(CB_THREADS), lds, s, g, m, kdim, reinterpret_cast<const uint64_t *>(base),
+                       reinterpret_cast<const uint32_t *>(base + L.off_lo), reinterpret_cast<const uint32_t *>(base + L.off_hi),
+                       reinterpret_cast<const LT *>(base + L.off_sym), nnz, ncols, L.segs, centers, k, z, p.entries, p.cshift, p.rows_per_group, direct,
+                       out);
+}
+
+template <typename LT, int MT>
+static void launch_sg_dc(dim3 grid, size_t lds, hipStream_t s, const float *x, const float *g, int m, long long kdim, const unsigned char *base,
+                         const SpLayout &L, long long nnz, long long ncols, int k, int z, const SgPlan &p, uint32_t *hdr, unsigned long long *sums)
+{
+    hipLaunchKernelGGL((k_cbspdc_stream<LT, MT>), grid, dim3(CB_THREADS), lds, s, x, g, m, kdim, reinterpret_cast<const uint64_t *>(base),
+                       reinterpret_cast<const uint32_t *>(base + L.off_lo), reinterpret_cast<const uint32_t *>(base + L.off_hi),
+                       reinterpret_cast<const LT *>(base + L.off_sym), nnz, ncols, L.segs, k, z, p.rlog2, p.terms_log2, p.rows_per_group, hdr, sums);
+}
+
+// every stream instantiation there is; the plans are checked against this table, and the launches go through it
+using SgDxLaunch = void (*)(dim3, size_t, hipStream_t, const float *, int, long long, const unsigned char *, const SpLayout &, long long, long long,
+                            const float *, int, int, const SgPlan &, int, float *);
+using SgDcLaunch = void (*)(dim3, size_t, hipStream_t, const float *, const float *, int, long long, const unsigned char *, const SpLayout &, long long,
+                            long long, int, int, const SgPlan &, uint32_t *, unsigned long long *);
+struct SgCase {
+    int lb, mt;
+    SgDxLaunch dx;
+    SgDcLaunch dc;
+};
+#define SG_CASE(LT, LB, MT) {LB, MT, launch_sg_dx<LT, MT>, launch_sg_dc<LT, MT>}
+static const SgCase kSgCases[] = {
+    SG_CASE(uint8_t, 1, 1),  SG_CASE(uint8_t, 1, 2),  SG_CASE(uint8_t, 1, 4),  SG_CASE(uint8_t, 1, 8),  SG_CASE(uint8_t, 1, 16),
+    SG_CASE(uint16_t, 2, 1), SG_CASE(uint16_t, 2, 2), SG_CASE(uint16_t, 2, 4), SG_CASE(uint16_t, 2, 8), SG_CASE(uint16_t, 2, 16),
+};
+#undef SG_CASE
+
+static const SgCase *find_sg_case(int lb, int mt)
+{
+    for (const SgCase &c : kSgCases)
+        if (c.lb == lb && c.mt == mt) return &c;
+    return nullptr;
+}
+
+static int no_sg_case(const char *fn, int lb, int mt)
+{
+    return fail(NNC_EINVAL, std::string(fn) + ": no stream instantiation for label_bytes " + std::to_string(lb) + ", mt " + std::to_string(mt));
+}
+
+static int sg_plan_out(const char *fn, const SgPlan &p, int lb, int32_t cus, int64_t *out)
+{
+    if (cus < 1) return fail(NNC_EINVAL, std::string(fn) + ": cus < 1");
+    if (!out) return fail(NNC_EINVAL, std::string(fn) + ": out is NULL");
+    if (p.path == NNC_CBMM_STREAM && !find_sg_case(lb, p.mt)) return no_sg_case(fn, lb, p.mt);
+    return NNC_OK;
+}
+
+extern "C" int64_t nnc_cbsp_dx_workspace_bytes(int64_t m, int64_t kdim, int64_t ncols, int label_bytes)
+{
+    if (sg_check("nnc_cbsp_dx_workspace_bytes", m, kdim, ncols, label_bytes, 1) != NNC_OK) return 0;
+    return sg_dx_ws_bytes(sg_dx_plan(m, kdim, ncols, label_bytes, 1, CB_PLAN_CUS), m, kdim);
+}
+
+extern "C" int nnc_cbsp_dx_plan(int64_t m, int64_t kdim, int64_t ncols, int label_bytes, int32_t k, int32_t cus, int64_t *out)
+{
+    int rc = sg_check("nnc_cbsp_dx_plan", m, kdim, ncols, label_bytes, k);
+    if (rc != NNC_OK) return rc;
+    const SgPlan p = sg_dx_plan(m, kdim, ncols, label_bytes, k, cus);
+    if ((rc = sg_plan_out("nnc_cbsp_dx_plan", p, label_bytes, cus, out)) != NNC_OK) return rc;
+    const int64_t v[NNC_CBSPDX_PLAN_LEN] = {p.path, p.mt, p.segs, p.path == NNC_CBMM_STREAM ? 1LL << p.cshift : (p.entries ? 1 : 0), p.entries,
+                                            p.splits, p.per_split, p.lds, p.col_tiles, p.row_tiles, sg_dx_ws_bytes(p, m, kdim)};
+    for (int i = 0; i < NNC_CBSPDX_PLAN_LEN; ++i) out[i] = v[i];
+    return NNC_OK;
+}
+
+extern "C" int nnc_cbsp_dx_f32(const float *g, int64_t m, int64_t kdim, const void *packed, int64_t packed_bytes, int label_bytes, int64_t ncols,
+                               int32_t zero_symbol, int64_t nnz, const float *centers_dev, int32_t k, float *dx, void *workspace, int64_t workspace_bytes,
+                               void *stream)
+{
+    const char *fn = "nnc_cbsp_dx_f32";
+    int rc = sg_check(fn, m, kdim, ncols, label_bytes, k);
+    if (rc != NNC_OK) return rc;
+    if ((rc = sg_check_form(fn, m, kdim, ncols, label_bytes, zero_symbol, nnz, packed, packed_bytes)) != NNC_OK) return rc;
+    if (!centers_dev) return fail(NNC_EINVAL, "nnc_cbsp_dx_f32: centers is NULL");
+    if (m > 0 && kdim > 0 && !dx) return fail(NNC_EINVAL, "nnc_cbsp_dx_f32: dx is NULL");
+    if (m > 0 && kdim > 0 && ncols > 0 && !g) return fail(NNC_EINVAL, "nnc_cbsp_dx_f32: g is NULL");
+    if (workspace_bytes < 0) return fail(NNC_EINVAL, "nnc_cbsp_dx_f32: negative workspace size");
+    const int64_t need = nnc_cbsp_dx_workspace_bytes(m, kdim, ncols, label_bytes);
+    if (workspace_bytes < need) return fail(NNC_ENOSPACE, "nnc_cbsp_dx_f32: workspace smaller than nnc_cbsp_dx_workspace_bytes()");
+    if (need > 0 && !workspace) return fail(NNC_EINVAL, "nnc_cbsp_dx_f32: workspace is NULL");
+    if (need > 0 && reinterpret_cast<uintptr_t>(workspace) % 4) return fail(NNC_EINVAL, "nnc_cbsp_dx_f32: workspace must be 4-byte aligned");
+    const SgPlan p = sg_dx_plan(m, kdim, ncols, label_bytes, k, cu_count());
+    const SgCase *sc = p.path == NNC_CBMM_STREAM ? find_sg_case(label_bytes, p.mt) : nullptr;
+    if (p.path == NNC_CBMM_STREAM && !sc) return no_sg_case(fn, label_bytes, p.mt);
+    if (p.path == NNC_CBMM_NONE) return NNC_OK;
+
+    hipStream_t s = S(stream);
+    if (p.path == NNC_CBMM_ZERO) {
+        HIPCHK(hipMemsetAsync(dx, 0, (size_t)(m * kdim) * 4, s));
+        return NNC_OK;
+    }
+    const SpLayout L = sp_layout(kdim, ncols, label_bytes, nnz);
+    const unsigned char *base = reinterpret_cast<const unsigned char *>(packed);
+    const int direct = p.splits == 1;
+    float *part = reinterpret_cast<float *>(workspace);
+    float *rs = reinterpret_cast<float *>(reinterpret_cast<unsigned char *>(workspace) + sg_part_bytes(p, m, kdim));
+    float *out = direct ? dx : part;
+    if ((rc = cbsp_rowsum(g, m, ncols, rs, s)) != NNC_OK) return rc;
+    if (p.path == NNC_CBMM_STREAM) {
+        sc->dx(dim3((unsigned)p.col_tiles, (unsigned)p.row_tiles), (size_t)p.lds, s, g, (int)m, kdim, base, L, nnz, ncols, centers_dev, k, zero_symbol, p,
+               direct, out);
+        LAUNCHCHK("k_cbspdx_stream");
+    } else {
+        const dim3 grid((unsigned)(p.col_tiles * p.row_tiles), (unsigned)p.splits);
+        const uint64_t *bm = reinterpret_cast<const uint64_t *>(base);
+        const uint32_t *lo = reinterpret_cast<const uint32_t *>(base + L.off_lo), *hi = reinterpret_cast<const uint32_t *>(base + L.off_hi);
+        if (label_bytes == 1)
+            hipLaunchKernelGGL(k_cbspdx_tiled<uint8_t>, grid, dim3(256), (size_t)p.lds, s, g, (long long)m, (long long)kdim, bm, lo, hi,
+                               reinterpret_cast<const uint8_t *>(base + L.off_sym), (long long)nnz, (long long)ncols, L.segs, centers_dev, (int)k,
+                               (int)zero_symbol, p.col_tiles, p.per_split, direct, out);
+        else
+            hipLaunchKernelGGL(k_cbspdx_tiled<uint16_t>, grid, dim3(256), (size_t)p.lds, s, g, (long long)m, (long long)kdim, bm, lo, hi,
+                               reinterpret_cast<const uint16_t *>(base + L.off_sym), (long long)nnz, (long long)ncols, L.segs, centers_dev, (int)k,
+                               (int)zero_symbol, p.col_tiles, p.per_split, direct, out);
+        LAUNCHCHK("k_cbspdx_tiled");
+    }
+    if (!direct && (rc = cbgrad_reduce(part, p.splits, m * kdim, dx, s)) != NNC_OK) return rc;
+    const int rgrid = (int)std::max(1LL, std::min(cdiv(m * kdim, 256), 8192LL));
+    hipLaunchKernelGGL(k_cbspdx_rank1, dim3(rgrid), dim3(256), 0, s, dx, (long long)m, (long long)kdim, rs, centers_dev, (int)k, (int)zero_symbol);
+    LAUNCHCHK("k_cbspdx_rank1");
+    return NNC_OK;
+}
+
+extern "C" int64_t nnc_cbsp_dc_workspace_bytes(int64_t m, int64_t kdim, int64_t ncols, int label_bytes, int32_t k)
+{
+    if (sg_check("nnc_cbsp_dc_workspace_bytes", m, kdim, ncols, label_bytes, k) != NNC_OK) return 0;
+    SgPlan p;
+    if (sg_dc_plan(m, kdim, ncols, label_bytes, k, CB_PLAN_CUS, p) != NNC_OK) return 0;
+    return sg_dc_ws_bytes(p, k);
+}
+
+extern "C" int nnc_cbsp_dc_plan(int64_t m, int64_t kdim, int64_t ncols, int label_bytes, int32_t k, int32_t cus, int64_t *out)
+{
+    int rc = sg_check("nnc_cbsp_dc_plan", m, kdim, ncols, label_bytes, k);
+    if (rc != NNC_OK) return rc;
+    SgPlan p;
+    if ((rc = sg_dc_plan(m, kdim, ncols, label_bytes, k, cus, p)) != NNC_OK) return rc;
+    if ((rc = sg_plan_out("nnc_cbsp_dc_plan", p, label_bytes, cus, out)) != NNC_OK) return rc;
+    const int64_t v[NNC_CBSPDC_PLAN_LEN] = {p.path, p.mt, p.segs, p.path == NNC_CBMM_ZERO ? 0 : 1LL << p.rlog2, p.splits, p.per_split, p.lds,
+                                            p.col_tiles, p.row_tiles, p.terms_log2, sg_dc_ws_bytes(p, k)};
+    for (int i = 0; i < NNC_CBSPDC_PLAN_LEN; ++i) out[i] = v[i];
+    return NNC_OK;
+}
+
+extern "C" int nnc_cbsp_dc_f32(const float *x, const float *g, int64_t m, int64_t kdim, const void *packed, int64_t packed_bytes, int label_bytes,
+                               int64_t ncols, int32_t zero_symbol, int64_t nnz, int32_t k, void *dc, int32_t out_f64, void *workspace,
+                               int64_t workspace_bytes, void *stream)
+{
+    const char *fn = "nnc_cbsp_dc_f32";
+    int rc = sg_check(fn, m, kdim, ncols, label_bytes, k);
+    if (rc != NNC_OK) return rc;
+    if ((rc = sg_check_form(fn, m, kdim, ncols, label_bytes, zero_symbol, nnz, packed, packed_bytes)) != NNC_OK) return rc;
+    if (!dc) return fail(NNC_EINVAL, "nnc_cbsp_dc_f32: dc is NULL");
+    if (m > 0 && kdim > 0 && ncols > 0 && (!x || !g)) return fail(NNC_EINVAL, "nnc_cbsp_dc_f32: x or g is NULL");
+    if (workspace_bytes < 0) return fail(NNC_EINVAL, "nnc_cbsp_dc_f32: negative workspace size");
+    const int64_t need = nnc_cbsp_dc_workspace_bytes(m, kdim, ncols, label_bytes, k);
+    if (workspace_bytes < need) return fail(NNC_ENOSPACE, "nnc_cbsp_dc_f32: workspace smaller than nnc_cbsp_dc_workspace_bytes()");
+    if (need > 0 && !workspace) return fail(NNC_EINVAL, "nnc_cbsp_dc_f32: workspace is NULL");
+    if (need > 0 && reinterpret_cast<uintptr_t>(workspace) % 8 != 0) return fail(NNC_EINVAL, "nnc_cbsp_dc_f32: workspace not 8-byte aligned");
+    SgPlan p;
+    if ((rc = sg_dc_plan(m, kdim, ncols, label_bytes, k, cu_count(), p)) != NNC_OK) return rc;
+    const SgCase *sc = p.path == NNC_CBMM_STREAM ? find_sg_case(label_bytes, p.mt) : nullptr;
+    if (p.path == NNC_CBMM_STREAM && !sc) return no_sg_case(fn, label_bytes, p.mt);
+
+    hipStream_t s = S(stream);
+    const size_t esz = out_f64 ? 8 : 4;
+    if (p.path == NNC_CBMM_ZERO) {
+        HIPCHK(hipMemsetAsync(dc, 0, (size_t)k * esz, s));
+        return NNC_OK;
+    }
+    const SpLayout L = sp_layout(kdim, ncols, label_bytes, nnz);
+    const unsigned char *base = reinterpret_cast<const unsigned char *>(packed);
+    uint32_t *hdr = reinterpret_cast<uint32_t *>(workspace);
+    unsigned long long *sums = reinterpret_cast<unsigned long long *>(reinterpret_cast<char *>(workspace) + CBG_HDR_BYTES);
+    HIPCHK(hipMemsetAsync(workspace, 0, (size_t)need, s));
+    if ((rc = cbgrad_absmax(x, m * kdim, g, m * ncols, hdr, s)) != NNC_OK) return rc;
+    if (p.path == NNC_CBMM_STREAM) {
+        sc->dc(dim3((unsigned)p.col_tiles, (unsigned)p.row_tiles), (size_t)p.lds, s, x, g, (int)m, kdim, base, L, nnz, ncols, k, zero_symbol, p, hdr, sums);
+        LAUNCHCHK("k_cbspdc_stream");
+    } else {
+        const dim3 grid((unsigned)(p.col_tiles * p.row_tiles), (unsigned)p.splits);
+        const uint64_t *bm = reinterpret_cast<const uint64_t *>(base);
+        const uint32_t *lo = reinterpret_cast<const uint32_t *>(base + L.off_lo), *hi = reinterpret_cast<const uint32_t *>(base + L.off_hi);
+        if (label_bytes == 1)
+            hipLaunchKernelGGL(k_cbspdc_tiled<uint8_t>, grid, dim3(256), (size_t)p.lds, s, x, g, (long long)m, (long long)kdim, bm, lo, hi,
+                               reinterpret_cast<const uint8_t *>(base + L.off_sym), (long long)nnz, (long long)ncols, L.segs, (int)k, (int)zero_symbol,
+                               p.rlog2, p.terms_log2, p.col_tiles, p.per_split, hdr, sums);
+        else
+            hipLaunchKernelGGL(k_cbspdc_tiled<uint16_t>, grid, dim3(256), (size_t)p.lds, s, x, g, (long long)m, (long long)kdim, bm, lo, hi,
+                               reinterpret_cast<const uint16_t *>(base + L.off_sym), (long long)nnz, (long long)ncols, L.segs, (int)k, (int)zero_symbol,
+                               p.rlog2, p.terms_log2, p.col_tiles, p.per_split, hdr, sums);
+        LAUNCHCHK("k_cbspdc_tiled");
+    }
+    return cbdc_finish(hdr, reinterpret_cast<const long long *>(sums), (int)k, (int)(out_f64 != 0), dc, s);
+}

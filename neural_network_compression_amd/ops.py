@@ -576,6 +576,116 @@ def cbsp_plan(m: int, kdim: int, ncols: int, label_bytes: int, k: int, cus: int)
     return dict(zip(nat.CBSP_PLAN_FIELDS, (int(v) for v in out)))
 
 
+def _sparse_grad_args(g: torch.Tensor, codes: SparseCodes):
+    _require_cuda(g, "g", torch.float32)
+    if not isinstance(codes, SparseCodes):
+        raise TypeError("codes must be a SparseCodes (ops.pack_sparse_codes)")
+    if g.dim() < 1 or g.shape[-1] != codes.ncols:
+        raise ValueError(f"g must have shape (..., {codes.ncols}), got {tuple(g.shape)}")
+    lead = tuple(g.shape[:-1])
+    return lead, (int(np.prod(lead)) if lead else 1)
+
+
+def sparse_codebook_matmul_dx(g: torch.Tensor, codes: SparseCodes, centers: torch.Tensor) -> torch.Tensor:
+    """dx = g @ W^T from the bitmap-sparse form (include/nnc.h, nnc_cbsp_dx_f32): c_z * sum_o g[., o] + the stored weights'
+    g[., o] * (centers[label] - c_z), the input gradient of sparse_codebook_matmul with its conventions (with centers[zero_symbol]
+    == 0 a skipped weight forms no product).  g: float32 (..., ncols); centers: float32[codes.k].  Returns float32 (..., kdim).
+    Split partials are summed in a fixed order: the same call gives the same bits.  No host read."""
+    _require_cuda(centers, "centers", torch.float32)
+    lead, m = _sparse_grad_args(g, codes)
+    if centers.numel() != codes.k:
+        raise ValueError(f"centers must hold k = {codes.k} values, got {centers.numel()}")
+    if len({g.device, codes.device, centers.device}) != 1:
+        raise ValueError("g, codes and centers must be on one device")
+    L = nat.load()
+    kdim, ncols, lb = codes.kdim, codes.ncols, codes.label_bytes
+    dx = torch.empty(lead + (kdim,), dtype=torch.float32, device=g.device)
+    ws_bytes = int(L.nnc_cbsp_dx_workspace_bytes(m, kdim, ncols, lb))
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=g.device) if ws_bytes else None
+    nat.check(L.nnc_cbsp_dx_f32(_ptr(g), m, kdim, _ptr(codes.buf), codes.nbytes(), lb, ncols, codes.zero_symbol, codes.nnz, _ptr(centers),
+                                centers.numel(), _ptr(dx), _ptr(ws), ws_bytes, _stream(g)))
+    return dx
+
+
+def sparse_codebook_centroid_grad(x: torch.Tensor, g: torch.Tensor, codes: SparseCodes, dtype=torch.float64) -> torch.Tensor:
+    """dc[j] = sum over the (i, o) whose label is j of (x^T g)[i, o], the skipped positions counted under zero_symbol
+    (include/nnc.h, nnc_cbsp_dc_f32): bit for bit codebook_centroid_grad(x, g, codes.to_dense(), codes.k, ...), the indices
+    never unpacked and dW never written.  x: float32 (..., kdim), g: float32 (..., ncols) with the same leading shape.  Returns
+    ``dtype`` (float64 or float32) [codes.k].  No host read."""
+    _require_cuda(x, "x", torch.float32)
+    lead, m = _sparse_grad_args(g, codes)
+    kdim, ncols, k, lb = codes.kdim, codes.ncols, codes.k, codes.label_bytes
+    if x.dim() < 1 or x.shape[-1] != kdim or tuple(x.shape[:-1]) != lead:
+        raise ValueError(f"x must have shape {lead + (kdim,)}, got {tuple(x.shape)}")
+    if len({x.device, g.device, codes.device}) != 1:
+        raise ValueError("x, g and codes must be on one device")
+    if dtype not in (torch.float64, torch.float32):
+        raise TypeError("dtype must be torch.float64 or torch.float32")
+    L = nat.load()
+    dc = torch.empty(k, dtype=dtype, device=x.device)
+    ws_bytes = int(L.nnc_cbsp_dc_workspace_bytes(m, kdim, ncols, lb, k))
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=x.device) if ws_bytes else None
+    nat.check(L.nnc_cbsp_dc_f32(_ptr(x), _ptr(g), m, kdim, _ptr(codes.buf), codes.nbytes(), lb, ncols, codes.zero_symbol, codes.nnz, k, _ptr(dc),
+                                1 if dtype == torch.float64 else 0, _ptr(ws), ws_bytes, _stream(x)))
+    return dc
+
+
+def cbsp_dx_plan(m: int, kdim: int, ncols: int, label_bytes: int, k: int, cus: int) -> dict:
+    """Host: the plan nnc_cbsp_dx_f32 follows on a device with ``cus`` compute units (include/nnc.h, nnc_cbsp_dx_plan), as a dict
+    keyed by _native.CBSPDX_PLAN_FIELDS.  No device needed."""
+    L = nat.load()
+    out = (ctypes.c_int64 * nat.CBSPDX_PLAN_LEN)()
+    nat.check(L.nnc_cbsp_dx_plan(int(m), int(kdim), int(ncols), int(label_bytes), int(k), int(cus), out))
+    return dict(zip(nat.CBSPDX_PLAN_FIELDS, (int(v) for v in out)))
+
+
+def cbsp_dc_plan(m: int, kdim: int, ncols: int, label_bytes: int, k: int, cus: int) -> dict:
+    """Host: the plan nnc_cbsp_dc_f32 follows on a device with ``cus`` compute units (include/nnc.h, nnc_cbsp_dc_plan), as a dict
+    keyed by _native.CBSPDC_PLAN_FIELDS.  No device needed."""
+    L = nat.load()
+    out = (ctypes.c_int64 * nat.CBSPDC_PLAN_LEN)()
+    nat.check(L.nnc_cbsp_dc_plan(int(m), int(kdim), int(ncols), int(label_bytes), int(k), int(cus), out))
+    return dict(zip(nat.CBSPDC_PLAN_FIELDS, (int(v) for v in out)))
+
+
+class _SparseCodebookLinear(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, codes, centers, bias, relu):
+        with torch.no_grad():
+            y = sparse_codebook_matmul(x.contiguous(), codes, centers, bias=bias, relu=relu)
+        ctx.codes, ctx.relu = codes, relu
+        ctx.save_for_backward(x, centers, y if relu else None)
+        return y
+
+    @staticmethod
+    def backward(ctx, gy):
+        x, centers, y = ctx.saved_tensors
+        codes = ctx.codes
+        g = gy.contiguous()
+        if ctx.relu:   # as torch.relu's backward: the gradient passes where y > 0 only (a NaN or negative output gets 0)
+            g = torch.where(y > 0, g, torch.zeros((), dtype=g.dtype, device=g.device))
+        g2 = g.reshape(-1, codes.ncols)
+        dx = dc = db = None
+        if ctx.needs_input_grad[0]:
+            dx = sparse_codebook_matmul_dx(g2, codes, centers).view(x.shape)
+        if ctx.needs_input_grad[2]:
+            dc = sparse_codebook_centroid_grad(x.contiguous().reshape(-1, codes.kdim), g2, codes, dtype=torch.float32)
+        if ctx.needs_input_grad[3]:
+            db = g2.sum(0)
+        return dx, None, dc, db, None
+
+
+def sparse_codebook_linear(x: torch.Tensor, codes: SparseCodes, centers: torch.Tensor, bias: torch.Tensor | None = None,
+                           relu: bool = False) -> torch.Tensor:
+    """sparse_codebook_matmul with gradients for x, centers and bias (an autograd Function shaped like codebook_linear).  The
+    forward is the same nnc_cbsp_f32 call (under no_grad the bits of sparse_codebook_matmul); the backward runs
+    sparse_codebook_matmul_dx only if x needs a gradient and sparse_codebook_centroid_grad (float32) only if centers does, masks a
+    fused ReLU as torch does and sums the bias gradient over the rows.  The indices get no gradient.  No host read."""
+    if not isinstance(codes, SparseCodes):
+        raise TypeError("codes must be a SparseCodes (ops.pack_sparse_codes)")
+    return _SparseCodebookLinear.apply(x, codes, centers, bias, bool(relu))
+
+
 def huffman_lengths(counts) -> tuple:
     """Host: (lengths uint8[k], hist int64[max_len+1], total_bits) from an index histogram."""
     L = nat.load()
