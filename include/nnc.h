@@ -527,11 +527,14 @@ int nnc_kmeanspp_seed_f32(const float *x, int64_t n, float x_mean, int32_t k, in
  * nnc_centroid_grad_f32: sums_dev[k] (int64, zeroed here) = sum of rint(grad * 2^fix_shift) per centroid index
  *   (fix_shift = nnc_fix_shift(max |grad|, n): exact integer sums, independent of order and of GPU count -- a sharded
  *   caller all-reduces them); counts_dev[k] (may be NULL) = members per index.  dL/dC_k = ldexp(sums[k], -fix_shift).
+ *   nonfinite_dev[1] (int64, zeroed here) becomes non-zero if any of grad[0, n) is NaN or +-Inf, whatever its index: then
+ *   every dL/dC_k is NaN (the convention of nnc_cbmm_dc_f32), and the sums are to be ignored.  A sharded caller reduces it
+ *   with the sums (it may be sums_dev[k] of a k + 1 buffer, so that one sum all-reduce carries both).
  * nnc_gather_f32: out[i] = centers_dev[labels[i]], the decode step cluster_centers_[labels_] (common/utility.py:239), for
  *   writing updated centroids back into the layer.
  * ---------------------------------------------------------------------------------- */
 int nnc_centroid_grad_f32(const float *grad, const void *labels, int label_bytes, int64_t n, int32_t k, int32_t fix_shift,
-                          int64_t *sums_dev, int64_t *counts_dev, void *stream);
+                          int64_t *sums_dev, int64_t *counts_dev, int64_t *nonfinite_dev, void *stream);
 int nnc_gather_f32(const float *centers_dev, int32_t k, const void *labels, int label_bytes, int64_t n, float *out, void *stream);
 
 /* ------------------------------------------------------------------------------------
@@ -587,12 +590,15 @@ int nnc_cbmm_f32(const float *x, int64_t m, int64_t kdim, const void *labels, in
  *                   partials are summed in split order (k_cbgrad_reduce).  An index >= k reads 0.
  * nnc_cbmm_dc_f32   dc[k] = sum over (i, o) with labels[i, o] = k of dW[i, o], dW = x^T g (x float32[m, kdim]), written as
  *                   float64[k] (out_f64 != 0) or float32[k]; dW itself is never stored.  dW[i, o] is formed in float32 (r
- *                   ascending; for m > 16 one value per split of m, k_cbdc_tiled) and binned as the exact integer
+ *                   ascending; for m > 16 one value per split of m, k_cbdc_tiled) from x and g scaled as they are loaded by the
+ *                   powers of two that bring max|x| and max|g| to [0.5, 1) (exact: dW is formed in float32's normal range, and
+ *                   wherever the unscaled products are normal the value is the unscaled one), and binned as the exact integer
  *                       rint(dW * 2^S),   S = 62 - T - P,   T = ceil(log2(kdim * ncols * splits)),   2^P > m * max|x| * max|g|
  *                   (max|x|, max|g| reduced on the device; the kernel derives S itself and keeps it in the workspace): every
  *                   image is at most 2^(62 - T) (1 + 2^-24)^m in magnitude, so the int64 sum stays below 2^63 for m <= 2^23; it is exact and
  *                   independent of order -- the result depends on the shape and the data only.  dc = ldexp(sum, -S): each term
- *                   is off by at most 2^(-S-1).  dc is all NaN if x or g holds Inf / NaN or P > 127; an index >= k falls into
+ *                   is off by at most 2^(-S-1); the error bound of DESIGN.md section 12 holds for every finite x and g, subnormal
+ *                   ones included.  dc is all NaN if x or g holds Inf / NaN or P > 127; an index >= k falls into
  *                   no bin.  splits is NNC_CBDC_P_SPLITS of the plan (1 for m <= 16).
  * No host read and no float atomics in either; the same call gives the same bits.  m = 0 or kdim = 0: dx is empty (a no-op);
  * ncols = 0: dx = 0.  No terms (m, kdim or ncols = 0): dc = 0.
@@ -711,7 +717,7 @@ int nnc_cbsp_f32(const float *x, int64_t m, int64_t kdim, const void *packed, in
  *                   count that depends on the shape alone); the split partials are summed in split order (k_cbgrad_reduce), then
  *                   c_z times the fixed-order row sums of g is added.
  * nnc_cbsp_dc_f32   dc[k] as nnc_cbmm_dc_f32 on the unpacked labels, bit for bit: every dW[i, o] is formed in float32 as that call
- *                   forms it and binned as rint(dW * 2^S) with the same S (SPLITS and TERMS_LOG2 are nnc_cbmm_dc_plan's for the
+ *                   forms it (from the same scaled x and g) and binned as rint(dW * 2^S) with the same S (SPLITS and TERMS_LOG2 are nnc_cbmm_dc_plan's for the
  *                   shape); a skipped (i, o) falls into bin z (none if z >= k), a stored index >= k into none.  A stored
  *                   weight's image goes into LDS bins, a skipped one's into a register flushed once per thread.  The all-NaN rule,
  *                   dc = 0 for a zero maximum, float64 / float32 output: as nnc_cbmm_dc_f32.

@@ -161,7 +161,7 @@ SIGNATURES = {
     "nnc_kmeanspp_trials": (c_i32, [c_i32]),
     "nnc_kmeanspp_workspace_bytes": (c_size, [c_i64, c_i32]),
     "nnc_kmeanspp_seed_f32": (c_int, [c_void_p, c_i64, c_f32, c_i32, c_i64, c_void_p, c_void_p, c_void_p, c_void_p, c_size, c_void_p]),
-    "nnc_centroid_grad_f32": (c_int, [c_void_p, c_void_p, c_int, c_i64, c_i32, c_i32, c_void_p, c_void_p, c_void_p]),
+    "nnc_centroid_grad_f32": (c_int, [c_void_p, c_void_p, c_int, c_i64, c_i32, c_i32, c_void_p, c_void_p, c_void_p, c_void_p]),
     "nnc_gather_f32": (c_int, [c_void_p, c_i32, c_void_p, c_int, c_i64, c_void_p, c_void_p]),
     "nnc_cbmm_workspace_bytes": (c_i64, [c_i64, c_i64, c_i64, c_int]),
     "nnc_cbmm_plan": (c_int, [c_i64, c_i64, c_i64, c_int, c_i32, c_i32, ctypes.c_uint64, ctypes.POINTER(c_i64)]),

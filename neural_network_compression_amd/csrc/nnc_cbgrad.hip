@@ -12,9 +12,10 @@
 //                  row-major indices, then the register-blocked FMA of k_cbmm_tiled.  ncols is split by a count that depends on the
 //                  shape alone; the partials go through k_cbgrad_reduce.
 //   k_cbdc_stream  m <= 16.  A lane holds g[0..m-1, o] for its columns; x[r, i] is broadcast by v_readlane; dW[i, o] is formed in
-//                  float32 with r ascending and binned at once.
+//                  float32 with r ascending and binned at once.  Both dc kernels scale x by 2^scx and g by 2^scg as they load
+//                  them (cbdc_scales: the maxima to [0.5, 1)), so dW' = dW * 2^(scx + scg) stays in float32's normal range.
 //   k_cbdc_tiled   m > 16.  128 (i) x 128 (o) tiles of x^T g, the reduction over m split by a count that depends on the shape alone.
-//   Binning: every dW (or every m-split's partial) becomes rint(v * 2^S) in int64 and is added into K LDS bins (replicated across
+//   Binning: every dW' (or every m-split's partial) becomes rint(v * 2^(S - scx - scg)) = rint(dW * 2^S) in int64 and is added into K LDS bins (replicated across
 //   banks) with integer atomics, then into a global int64[K] with integer atomics: exact, so the result depends on the shape and the
 //   data only.  S = 62 - ceil(log2(terms)) - P, 2^P > m * max|x| * max|g|, terms = kdim * ncols * splits; max|x| and max|g| come
 //   from k_cbgrad_absmax on the device, the dc kernel derives S itself and writes it next to the sums, and k_cbdc_finish writes
@@ -318,6 +319,9 @@ __global__ __launch_bounds__(CB_THREADS) void k_cbdc_stream(const float *__restr
         hdr[3] = (uint32_t)flag;
     }
     if (flag != CBG_FLAG_OK) return;   // (uniform over the launch)
+    int scx, scg;
+    cbdc_scales(hdr, scx, scg);
+    const int Sw = S - scx - scg;      // the shift of dW' = dW * 2^(scx + scg)
     for (int j = threadIdx.x; j < (k << rlog2); j += CB_THREADS) bins[j] = 0ull;
 
     const int lane = threadIdx.x & 63;
@@ -330,7 +334,12 @@ __global__ __launch_bounds__(CB_THREADS) void k_cbdc_stream(const float *__restr
 #pragma unroll
     for (int r = 0; r < MT; ++r)
 #pragma unroll
-        for (int e = 0; e < E; ++e) gv[r][e] = (r < m && e < ne) ? g[(long long)r * ncols + c0 + e] : 0.0f;
+        for (int e = 0; e < E; ++e) gv[r][e] = g[cbdc_idx((long long)r * ncols + c0 + e, r < m && e < ne)];
+    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+    for (int r = 0; r < MT; ++r)
+#pragma unroll
+        for (int e = 0; e < E; ++e) gv[r][e] = cbdc_scaled(gv[r][e], r < m && e < ne, scg);
 
     const long long g_lo = (long long)blockIdx.y * rows_per_group, g_hi = std::min(kdim, g_lo + rows_per_group);
     const long long per_wave = (g_hi - g_lo + CB_WAVES - 1) / CB_WAVES;
@@ -359,8 +368,8 @@ __global__ __launch_bounds__(CB_THREADS) void k_cbdc_stream(const float *__restr
     auto load_x = [&](long long i, int U, float &xa, float &xb) {
         const int f0 = lane, f1 = lane + 64;
         const int r0 = f0 / U, r1 = f1 / U;
-        xa = r0 < m ? x[(long long)r0 * kdim + i + f0 % U] : 0.0f;
-        xb = (MT * CB_UNROLL > 64 && r1 < m) ? x[(long long)r1 * kdim + i + f1 % U] : 0.0f;
+        xa = cbdc_scaled(x[cbdc_idx((long long)r0 * kdim + i + f0 % U, r0 < m)], r0 < m, scx);
+        xb = MT * CB_UNROLL > 64 ? cbdc_scaled(x[cbdc_idx((long long)r1 * kdim + i + f1 % U, r1 < m)], r1 < m, scx) : 0.0f;
     };
     auto consume = [&](const uint32_t *w, uint32_t s, float xa, float xb, int u, int U) {
         float xv[MT];
@@ -381,8 +390,8 @@ __global__ __launch_bounds__(CB_THREADS) void k_cbdc_stream(const float *__restr
             const uint32_t l = (o[e / PER] >> (8 * LB * (e % PER))) & (LB == 1 ? 0xFFu : 0xFFFFu);
             float d = 0.0f;
 #pragma unroll
-            for (int r = 0; r < MT; ++r) d = __builtin_fmaf(xv[r], gv[r][e], d);   // dW[i, o], r ascending
-            if (e < ne && l < (uint32_t)k) atomicAdd(&bins[(l << rlog2) + rep], cbdc_fix(d, S));
+            for (int r = 0; r < MT; ++r) d = __builtin_fmaf(xv[r], gv[r][e], d);   // dW'[i, o], r ascending
+            if (e < ne && l < (uint32_t)k) atomicAdd(&bins[(l << rlog2) + rep], cbdc_fix(d, Sw));
         }
     };
 
@@ -426,6 +435,9 @@ __global__ __launch_bounds__(256) void k_cbdc_tiled(const float *__restrict__ x,
         hdr[3] = (uint32_t)flag;
     }
     if (flag != CBG_FLAG_OK) return;
+    int scx, scg;
+    cbdc_scales(hdr, scx, scg);
+    const int Sw = S - scx - scg;
     for (int j = threadIdx.x; j < (k << rlog2); j += 256) bins[j] = 0ull;
 
     const int t = threadIdx.x, tx = t & 15, ty = t >> 4;
@@ -443,11 +455,19 @@ __global__ __launch_bounds__(256) void k_cbdc_tiled(const float *__restrict__ x,
         {
             const long long r = rb + lk;
             const bool in_r = r < r_hi;
+            float xv[4], gv[4];
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
                 const long long ii = i0 + lc + j, oo = o0 + lc + j;
-                xs[lk * TB_M + lc + j] = (in_r && ii < kdim) ? x[r * kdim + ii] : 0.0f;
-                gs[lk * TB_N + lc + j] = (in_r && oo < ncols) ? g[r * ncols + oo] : 0.0f;
+                xv[j] = x[cbdc_idx(r * kdim + ii, in_r && ii < kdim)];
+                gv[j] = g[cbdc_idx(r * ncols + oo, in_r && oo < ncols)];
+            }
+            __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const long long ii = i0 + lc + j, oo = o0 + lc + j;
+                xs[lk * TB_M + lc + j] = cbdc_scaled(xv[j], in_r && ii < kdim, scx);
+                gs[lk * TB_N + lc + j] = cbdc_scaled(gv[j], in_r && oo < ncols, scg);
             }
         }
         __syncthreads();
@@ -462,7 +482,7 @@ __global__ __launch_bounds__(256) void k_cbdc_tiled(const float *__restrict__ x,
             const long long o = o0 + tx * 8 + b;
             if (i >= kdim || o >= ncols) continue;
             const uint32_t l = (uint32_t)labels[i * ncols + o];
-            if (l < (uint32_t)k) atomicAdd(&bins[(l << rlog2) + rep], cbdc_fix(acc[a][b], S));
+            if (l < (uint32_t)k) atomicAdd(&bins[(l << rlog2) + rep], cbdc_fix(acc[a][b], Sw));
         }
     }
     cbdc_flush(bins, k, rlog2, sums);

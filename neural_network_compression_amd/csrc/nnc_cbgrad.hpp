@@ -1,6 +1,6 @@
 // nnc_cbgrad.hpp -- what the backward pass of the codebook matmul (nnc_cbgrad.hip) shares with that of its bitmap-sparse sibling
-// (nnc_cbspgrad.hip): the fixed-order wave reduction of the dx stream kernels, the fixed-point binning of dc (DESIGN.md section
-// 12) and the launches of the kernels both use (defined in nnc_cbgrad.hip).
+// (nnc_cbspgrad.hip): the fixed-order wave reduction of the dx stream kernels, the scaling and fixed-point binning of dc (DESIGN.md
+// section 12) and the launches of the kernels both use (defined in nnc_cbgrad.hip).
 #pragma once
 #include "nnc_cbmm.hpp"
 
@@ -57,6 +57,30 @@ __device__ __forceinline__ int cbdc_shift(const uint32_t *amax, long long m, int
     }
     return 62 - terms_log2 - P;
 }
+
+// e with |v| = f * 2^e, f in [0.5, 1), of a finite non-zero |v| given as bits (subnormals included)
+__device__ __forceinline__ int cbdc_exp(uint32_t bits)
+{
+    const int E = (int)(bits >> 23);
+    return E ? E - 126 : (32 - __clz((int)bits)) - 149;
+}
+
+// The exponents scx, scg that bring max |x| and max |g| (k_cbgrad_absmax's bits, finite and non-zero: CBG_FLAG_OK) to [0.5, 1).
+// The dc kernels scale every x by 2^scx and every g by 2^scg as they load them (v_ldexp_f32: exact, a float32 multiplier cannot
+// hold 2^+-149), so dW' = dW * 2^(scx + scg) is formed in float32's normal range whatever the magnitudes; they bin
+// rint(dW' * 2^(S - scx - scg)).
+__device__ __forceinline__ void cbdc_scales(const uint32_t *amax, int &scx, int &scg)
+{
+    scx = -cbdc_exp(amax[0]);
+    scg = -cbdc_exp(amax[1]);
+}
+
+// The loads of the dc kernels are made whatever the guard says (of v[0], which they always have, finite, where it is false) and
+// cbdc_scaled(value, guard, s) is value * 2^s, or +-0 (the value * 2^-512) where the guard is false: a guarded load followed by
+// the scaling compiles to a branch that waits for each load in turn.  A batch of loads goes first, then a sched_barrier, then
+// the scaling, so that the loads of the batch are in flight together.
+__device__ __forceinline__ long long cbdc_idx(long long idx, bool ok) { return ok ? idx : 0; }
+__device__ __forceinline__ float cbdc_scaled(float v, bool ok, int s) { return ldexpf(v, ok ? s : -512); }
 
 // the fixed-point image of one dW: exact scaling by 2^S (|v * 2^S| < 2^63), nearest integer, ties to even
 __device__ __forceinline__ unsigned long long cbdc_fix(float v, int S) { return (unsigned long long)(long long)rintf(ldexpf(v, S)); }

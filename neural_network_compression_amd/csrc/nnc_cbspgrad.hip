@@ -5,7 +5,8 @@
 //   dx[r, i] = c_z * sum_o g[r, o] + sum over the stored (i, o) of g[r, o] * d[L[i, o]]   the Jacobian of nnc_cbsp_f32; with
 //                                                                                        c_z == 0 the rank-1 term is dropped
 //   dc[k]    = nnc_cbmm_dc_f32 on the unpacked labels, bit for bit: every dW[i, o] is formed in float32 as k_cbdc_stream /
-//              k_cbdc_tiled form it and binned as rint(dW * 2^S) with the same S (the same splits of m and T); a skipped (i, o)
+//              k_cbdc_tiled form it (from x and g scaled by the same powers of two) and binned as rint(dW * 2^S) with the same S
+//              (the same splits of m and T); a skipped (i, o)
 //              falls into bin z (none if z >= K).  Integer sums do not depend on order.
 //
 //   k_cbspdx_stream  m <= 16.  A workgroup owns a block of E segments (64 lanes x E columns of g in registers, E * MT <= 32) and
@@ -342,6 +343,9 @@ __global__ __launch_bounds__(CB_THREADS) void k_cbspdc_stream(const float *__res
         hdr[3] = (uint32_t)flag;
     }
     if (flag != CBG_FLAG_OK) return;   // (uniform over the launch)
+    int scx, scg;
+    cbdc_scales(hdr, scx, scg);
+    const int Sw = S - scx - scg;      // the shift of dW' = dW * 2^(scx + scg)
     for (int j = threadIdx.x; j < (k << rlog2); j += CB_THREADS) bins[j] = 0ull;
 
     const int lane = threadIdx.x & 63;
@@ -355,8 +359,13 @@ __global__ __launch_bounds__(CB_THREADS) void k_cbspdc_stream(const float *__res
         const long long col = (blk * E + e) * 64 + lane;
         incol[e] = col < ncols;
 #pragma unroll
-        for (int r = 0; r < MT; ++r) gv[r][e] = (r < m && incol[e]) ? g[(long long)r * ncols + col] : 0.0f;
+        for (int r = 0; r < MT; ++r) gv[r][e] = g[cbdc_idx((long long)r * ncols + col, r < m && incol[e])];
     }
+    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+    for (int e = 0; e < E; ++e)
+#pragma unroll
+        for (int r = 0; r < MT; ++r) gv[r][e] = cbdc_scaled(gv[r][e], r < m && incol[e], scg);
 
     const long long g_lo = (long long)blockIdx.y * rows_per_group, g_hi = std::min(kdim, g_lo + rows_per_group);
     const long long per_wave = (g_hi - g_lo + CB_WAVES - 1) / CB_WAVES;
@@ -378,7 +387,7 @@ __global__ __launch_bounds__(CB_THREADS) void k_cbspdc_stream(const float *__res
             {
                 const int r0 = lane / UR;
                 const long long i = ib + u0 + lane % UR;
-                xa = (r0 < m && i < i1) ? x[(long long)r0 * kdim + i] : 0.0f;
+                xa = cbdc_scaled(x[cbdc_idx((long long)r0 * kdim + i, r0 < m && i < i1)], r0 < m && i < i1, scx);
             }
             uint32_t bits[UR][E], sv[UR][E];
             sg_symbols<LT, E, UR>(wl, cl, u0, lane, sym, nnz, bits, sv);
@@ -392,8 +401,8 @@ __global__ __launch_bounds__(CB_THREADS) void k_cbspdc_stream(const float *__res
                 for (int e = 0; e < E; ++e) {
                     float d = 0.0f;
 #pragma unroll
-                    for (int r = 0; r < MT; ++r) d = __builtin_fmaf(xv[r], gv[r][e], d);   // dW[i, o], r ascending (k_cbdc_stream)
-                    const unsigned long long img = cbdc_fix(d, S);
+                    for (int r = 0; r < MT; ++r) d = __builtin_fmaf(xv[r], gv[r][e], d);   // dW'[i, o], r ascending (k_cbdc_stream)
+                    const unsigned long long img = cbdc_fix(d, Sw);
                     if (bits[u][e]) {
                         if (sv[u][e] < (uint32_t)k) atomicAdd(&bins[(sv[u][e] << rlog2) + rep], img);
                     } else if (incol[e]) {
@@ -428,6 +437,9 @@ __global__ __launch_bounds__(256) void k_cbspdc_tiled(const float *__restrict__ 
         hdr[3] = (uint32_t)flag;
     }
     if (flag != CBG_FLAG_OK) return;
+    int scx, scg;
+    cbdc_scales(hdr, scx, scg);
+    const int Sw = S - scx - scg;
     for (int j = threadIdx.x; j < (k << rlog2); j += 256) bins[j] = 0ull;
 
     const int t = threadIdx.x, tx = t & 15, ty = t >> 4;
@@ -445,11 +457,19 @@ __global__ __launch_bounds__(256) void k_cbspdc_tiled(const float *__restrict__ 
         {
             const long long r = rb + lk;
             const bool in_r = r < r_hi;
+            float xv[4], gv[4];
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
                 const long long ii = i0 + lc + j, oo = o0 + lc + j;
-                xs[lk * TB_M + lc + j] = (in_r && ii < kdim) ? x[r * kdim + ii] : 0.0f;
-                gs[lk * TB_N + lc + j] = (in_r && oo < ncols) ? g[r * ncols + oo] : 0.0f;
+                xv[j] = x[cbdc_idx(r * kdim + ii, in_r && ii < kdim)];
+                gv[j] = g[cbdc_idx(r * ncols + oo, in_r && oo < ncols)];
+            }
+            __builtin_amdgcn_sched_barrier(0);   // (as k_cbdc_tiled)
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const long long ii = i0 + lc + j, oo = o0 + lc + j;
+                xs[lk * TB_M + lc + j] = cbdc_scaled(xv[j], in_r && ii < kdim, scx);
+                gs[lk * TB_N + lc + j] = cbdc_scaled(gv[j], in_r && oo < ncols, scg);
             }
         }
         __syncthreads();
@@ -469,7 +489,7 @@ __global__ __launch_bounds__(256) void k_cbspdc_tiled(const float *__restrict__ 
 #pragma unroll
         for (int b = 0; b < 8; ++b) {
             if (ob + b >= ncols) continue;
-            const unsigned long long img = cbdc_fix(acc[a][b], S);
+            const unsigned long long img = cbdc_fix(acc[a][b], Sw);
             if ((word >> (b0 + b)) & 1) {
                 const uint32_t l = pos < nnz ? (uint32_t)sym[pos] : (uint32_t)z;   // (past nnz: skipped, as nnc_cbsp_unpack reads it)
                 ++pos;

@@ -299,12 +299,14 @@ extern "C" int nnc_kmeanspp_seed_f32(const float *x, int64_t n, float x_mean, in
 // the reference describes it and leaves it out because scanning all gradients for every batch on the host was too slow,
 // papers/lat/report.tex:149-158).  A segmented reduction by centroid index: the same shape as the M-step, on the original
 // (unsorted) order, so the sums go through LDS accumulators.  Gradients enter as fixed-point images rint(g * 2^S)
-// (S = nnc_fix_shift(max |g|, n)), so the result is independent of summation order and of the number of GPUs.
+// (S = nnc_fix_shift(max |g|, n)), so the result is independent of summation order and of the number of GPUs.  A NaN or Inf
+// anywhere in g sets the flag word (its image would be garbage), and the caller makes every dL/dC_k NaN.
 // Also the decode step itself, cluster_centers_[labels_] (utility.py:239), for writing fine-tuned centroids back.
 // ======================================================================================
 template <typename LT>
 __global__ __launch_bounds__(256) void k_centroid_grad(const float *__restrict__ g, const LT *__restrict__ labels, long long n, int k, int Sft,
-                                                       int rlog2, unsigned long long *__restrict__ sums, unsigned long long *__restrict__ counts)
+                                                       int rlog2, unsigned long long *__restrict__ sums, unsigned long long *__restrict__ counts,
+                                                       unsigned long long *__restrict__ nonfinite)
 {
     extern __shared__ unsigned long long acc[]; // [k][R] sums, then [k][R] counts (as 32-bit)
     const int R = 1 << rlog2;
@@ -313,14 +315,18 @@ __global__ __launch_bounds__(256) void k_centroid_grad(const float *__restrict__
     __syncthreads();
     const int rep = threadIdx.x & (R - 1);
     const long long tid = (long long)blockIdx.x * blockDim.x + threadIdx.x, nthreads = (long long)gridDim.x * blockDim.x;
+    bool bad = false;
     for (long long i = tid; i < n; i += nthreads) {
         const int l = (int)labels[i];
+        const float v = g[i];
+        bad |= !__builtin_isfinite(v);
         if (l < k) {
-            const long long q = (long long)(int)rintf(ldexpf(g[i], Sft));
+            const long long q = (long long)(int)rintf(ldexpf(v, Sft));
             atomicAdd(&acc[(l << rlog2) + rep], (unsigned long long)q);
             atomicAdd(&cnt[(l << rlog2) + rep], 1u);
         }
     }
+    if (bad) atomicOr(nonfinite, 1ull);
     __syncthreads();
     for (int j = threadIdx.x; j < k; j += 256) {
         unsigned long long s = 0, c = 0;
@@ -330,25 +336,27 @@ __global__ __launch_bounds__(256) void k_centroid_grad(const float *__restrict__
 }
 
 extern "C" int nnc_centroid_grad_f32(const float *grad, const void *labels, int label_bytes, int64_t n, int32_t k, int32_t fix_shift,
-                                     int64_t *sums_dev, int64_t *counts_dev, void *stream)
+                                     int64_t *sums_dev, int64_t *counts_dev, int64_t *nonfinite_dev, void *stream)
 {
-    if (n < 0 || k < 1 || k > NNC_KMAX || !sums_dev || (n > 0 && (!grad || !labels)) || (label_bytes != 1 && label_bytes != 2))
+    if (n < 0 || k < 1 || k > NNC_KMAX || !sums_dev || !nonfinite_dev || (n > 0 && (!grad || !labels)) || (label_bytes != 1 && label_bytes != 2))
         return nnc_set_error_(NNC_EINVAL, "nnc_centroid_grad_f32: bad argument");
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     if (hipMemsetAsync(sums_dev, 0, (size_t)k * 8, s) != hipSuccess) return nnc_set_error_(NNC_EHIP, "nnc_centroid_grad_f32: memset");
     if (counts_dev && hipMemsetAsync(counts_dev, 0, (size_t)k * 8, s) != hipSuccess) return nnc_set_error_(NNC_EHIP, "nnc_centroid_grad_f32: memset");
+    if (hipMemsetAsync(nonfinite_dev, 0, 8, s) != hipSuccess) return nnc_set_error_(NNC_EHIP, "nnc_centroid_grad_f32: memset");
     if (n == 0) return NNC_OK;
     int rlog2 = k <= 64 ? 5 : (k <= 256 ? 3 : 1);
     int cus = 256;
     nnc_device_info(nullptr, 0, &cus);
     const int grid = (int)std::max<long long>(1, std::min<long long>((n + 2047) / 2048, (long long)cus * 4));
     const size_t lds = ((size_t)k << rlog2) * 12;
+    unsigned long long *nf = reinterpret_cast<unsigned long long *>(nonfinite_dev);
     if (label_bytes == 1)
         hipLaunchKernelGGL((k_centroid_grad<uint8_t>), dim3(grid), dim3(256), lds, s, grad, reinterpret_cast<const uint8_t *>(labels), (long long)n, (int)k,
-                           (int)fix_shift, rlog2, reinterpret_cast<unsigned long long *>(sums_dev), reinterpret_cast<unsigned long long *>(counts_dev));
+                           (int)fix_shift, rlog2, reinterpret_cast<unsigned long long *>(sums_dev), reinterpret_cast<unsigned long long *>(counts_dev), nf);
     else
         hipLaunchKernelGGL((k_centroid_grad<uint16_t>), dim3(grid), dim3(256), lds, s, grad, reinterpret_cast<const uint16_t *>(labels), (long long)n, (int)k,
-                           (int)fix_shift, rlog2, reinterpret_cast<unsigned long long *>(sums_dev), reinterpret_cast<unsigned long long *>(counts_dev));
+                           (int)fix_shift, rlog2, reinterpret_cast<unsigned long long *>(sums_dev), reinterpret_cast<unsigned long long *>(counts_dev), nf);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return nnc_set_error_(NNC_EHIP, hipGetErrorString(e));
     return NNC_OK;

@@ -247,7 +247,8 @@ def centroid_gradient(grad: torch.Tensor, labels: torch.Tensor, k: int, group=No
     """dL/dC_j = sum of dL/dW over the weights whose centroid index is j (Deep Compression's centroid fine-tuning,
     described but left out by the reference, papers/lat/report.tex:149-158) -> float64[k] on the device.
     Exact fixed-point sums (include/nnc.h, nnc_centroid_grad_f32): independent of order and, with ``group`` (every rank
-    holds a shard of the layer), of the number of GPUs.  One host read (max |grad|) sizes the fixed point."""
+    holds a shard of the layer), of the number of GPUs.  One host read (max |grad|) sizes the fixed point.  A NaN or Inf
+    anywhere in ``grad`` (on any rank) makes every entry NaN, as codebook_centroid_grad does."""
     _require_cuda(grad, "grad", torch.float32)
     _require_cuda(labels, "labels")
     g = grad.reshape(-1)
@@ -266,13 +267,15 @@ def centroid_gradient(grad: torch.Tensor, labels: torch.Tensor, k: int, group=No
         n_total = sharding.total_count(n, g.device, group)
     host = mm.cpu().numpy()
     S = fix_shift(float(max(abs(host[0]), abs(host[1]))), n_total)
-    sums = torch.empty(int(k), dtype=torch.int64, device=g.device)
-    nat.check(L.nnc_centroid_grad_f32(_ptr(g), _ptr(labels), _label_bytes(labels), n, int(k), S, _ptr(sums), 0, _stream(g)))
+    buf = torch.empty(int(k) + 1, dtype=torch.int64, device=g.device)   # the k sums, then the non-finite flag
+    sums, nonfinite = buf[: int(k)], buf[int(k):]
+    nat.check(L.nnc_centroid_grad_f32(_ptr(g), _ptr(labels), _label_bytes(labels), n, int(k), S, _ptr(sums), 0, _ptr(nonfinite), _stream(g)))
     if group is not None:
         from . import sharding
 
-        sharding.allreduce_sum_(sums, group)
-    return torch.ldexp(sums.to(torch.float64), torch.tensor(-S, device=g.device))
+        sharding.allreduce_sum_(buf, group)   # the flags of every rank with the sums
+    out = torch.ldexp(sums.to(torch.float64), torch.tensor(-S, device=g.device))
+    return out.masked_fill_(nonfinite != 0, float("nan"))
 
 
 def gather(centers: torch.Tensor, labels: torch.Tensor) -> torch.Tensor:

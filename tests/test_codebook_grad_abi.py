@@ -203,3 +203,13 @@ def test_trainable_needs_the_dense_form():
         compressed.compress_network(None, {}, sparse=True, trainable=True)
     with pytest.raises(ValueError, match="sparse"):
         compressed.compress_network(None, {}, sparse="auto", trainable=True)
+
+
+def test_centroid_grad_takes_a_non_finite_flag_and_checks_its_arguments(lib):
+    """nnc_centroid_grad_f32 (the backward of a quantized bias and of Trainer.fine_tune_centroids): the non-finite flag word is a
+    required argument; argument errors come before any HIP call."""
+    assert len(nat.SIGNATURES["nnc_centroid_grad_f32"][1]) == 10
+    ok = dict(grad=P, labels=P, lb=1, n=10, k=4, S=0, sums=P, counts=0, nonfinite=P)
+    assert lib.nnc_centroid_grad_f32(*(dict(ok, nonfinite=0).values()), None) == NNC_EINVAL
+    for bad in (dict(sums=0), dict(k=0), dict(lb=3), dict(n=-1), dict(grad=0), dict(labels=0)):
+        assert lib.nnc_centroid_grad_f32(*(dict(ok, **bad).values()), None) == NNC_EINVAL, bad
