@@ -707,6 +707,70 @@ int nnc_cbsp_f32(const float *x, int64_t m, int64_t kdim, const void *packed, in
                  int64_t workspace_bytes, void *stream);
 
 /* ------------------------------------------------------------------------------------
+ * The quantized layer of at most 16 centres run from 2- or 4-bit packed indices (csrc/nnc_cbpk.hip): a
+ * third resident form of the (kdim, ncols) index matrix, row-major as nnc_cbmm_f32 reads it, beside the byte form and the
+ * bitmap-sparse form.  bits is 2 or 4, every label < 2^bits, 1 <= k <= 2^bits.  One buffer, no other metadata:
+ *   row_bytes = 16 * ceil(ncols * bits / 128): every row starts on a 16-byte boundary (the buffer itself on one too; the Python
+ *               layer allocates it 256-byte aligned)
+ *   label (i, o) in byte i * row_bytes + (o * bits) / 8 at bit (o * bits) % 8, low bits first; the fields past ncols are 0
+ *   size kdim * row_bytes
+ * nnc_cbpk_row_bytes, nnc_cbpk_pack_bytes   host: the row pitch and the buffer size (0 for bad arguments).
+ * nnc_cbpk_pack      labels (1 or 2 bytes wide, any storage offset; 2-byte aligned for uint16) -> packed, padding included, in one
+ *                    pass with whole-dword stores and no per-weight temporary.  *bad_count_dev (one device word, set by the call;
+ *                    may be NULL) = the number of labels >= 2^bits; such a label is stored as its low bits and the caller must
+ *                    treat a non-zero count as an error.
+ * nnc_cbpk_unpack    the inverse: labels_out[kdim * ncols], label_bytes_out wide.
+ * nnc_cbpk_f32       y[m, ncols] = x[m, kdim] @ W + bias, then ReLU (v < 0 ? 0 : v: NaN kept) if relu != 0, W[i, o] =
+ *                    centers_dev[label (i, o)], an index >= k reads 0: the contract of nnc_cbmm_f32 on the unpacked labels.
+ *                    Nothing is skipped: Inf or NaN in x behaves as in the byte form (Inf * 0 is NaN).  m <= 16: k_cbpk_stream;
+ *                    m > 16: k_cbpk_tiled; split-K partials go to the workspace and are summed in split order by k_cbmm_reduce:
+ *                    no float atomics, the splits depend on the shape and the CU count alone, the same call gives the same
+ *                    bits.  m or ncols = 0 is a no-op; kdim = 0 writes y = bias (or 0).
+ * nnc_cbpk_workspace_bytes   what nnc_cbpk_f32 needs for that shape (host arithmetic, plans for 256 CUs; the plan's splits never
+ *                    shrink with more CUs and stop growing there).
+ * nnc_cbpk_plan      host: the plan nnc_cbpk_f32 follows on a device with `cus` CUs, NNC_CBPK_PLAN_LEN values indexed by
+ *                    NNC_CBPK_P_*:
+ *   PATH       NNC_CBMM_NONE / _STREAM / _TILED / _BIAS
+ *   VB, MT     stream: packed bytes per lane per row (16, 8, 4, 2 or 1), rows of x per launch (a power of two >= m)
+ *   COLS       stream: columns per lane per row (8 * VB / bits); XROWS rows of x per pass over the indices (= MT: one pass);
+ *              COLS * XROWS accumulators per lane, at most 64
+ *   TABLE      the lookup table's layout (NNC_CBPK_TABLE_BANKED: 2^bits floats, centres then zeros, COPIES per-bank copies,
+ *              entry j of lane l at word j * COPIES + l % COPIES; the tiled kernel keeps one copy), COPIES, ENTRIES
+ *   SPLITS, RPS, LDS, COL_TILES, ROW_TILES, WORKSPACE   as nnc_cbmm_plan
+ * NNC_EINVAL for bits not 2 or 4, k < 1 or k > 2^bits, a packed_bytes that is not nnc_cbpk_pack_bytes(kdim, ncols, bits), a
+ * packed not on a 16-byte boundary, NULL where a pointer is needed, negative sizes, cus < 1, or a plan with no kernel
+ * instantiation; NNC_ENOSPACE for a short workspace.  All of them are returned before any HIP call.
+ * ---------------------------------------------------------------------------------- */
+#define NNC_CBPK_TABLE_NONE 0
+#define NNC_CBPK_TABLE_BANKED 1
+#define NNC_CBPK_P_PATH 0
+#define NNC_CBPK_P_VB 1
+#define NNC_CBPK_P_MT 2
+#define NNC_CBPK_P_COLS 3
+#define NNC_CBPK_P_XROWS 4
+#define NNC_CBPK_P_TABLE 5
+#define NNC_CBPK_P_COPIES 6
+#define NNC_CBPK_P_ENTRIES 7
+#define NNC_CBPK_P_SPLITS 8
+#define NNC_CBPK_P_RPS 9
+#define NNC_CBPK_P_LDS 10
+#define NNC_CBPK_P_COL_TILES 11
+#define NNC_CBPK_P_ROW_TILES 12
+#define NNC_CBPK_P_WORKSPACE 13
+#define NNC_CBPK_PLAN_LEN 14
+int64_t nnc_cbpk_row_bytes(int64_t ncols, int bits);
+int64_t nnc_cbpk_pack_bytes(int64_t kdim, int64_t ncols, int bits);
+int nnc_cbpk_pack(const void *labels, int label_bytes, int64_t kdim, int64_t ncols, int bits, void *packed, int64_t packed_bytes,
+                  uint32_t *bad_count_dev, void *stream);
+int nnc_cbpk_unpack(const void *packed, int64_t packed_bytes, int bits, int64_t kdim, int64_t ncols, void *labels_out, int label_bytes_out,
+                    void *stream);
+int64_t nnc_cbpk_workspace_bytes(int64_t m, int64_t kdim, int64_t ncols, int bits);
+int nnc_cbpk_plan(int64_t m, int64_t kdim, int64_t ncols, int bits, int32_t k, int32_t cus, int64_t *out);
+int nnc_cbpk_f32(const float *x, int64_t m, int64_t kdim, const void *packed, int64_t packed_bytes, int bits, int64_t ncols,
+                 const float *centers_dev, int32_t k, const float *bias_dev, int32_t relu, float *y, void *workspace, int64_t workspace_bytes,
+                 void *stream);
+
+/* ------------------------------------------------------------------------------------
  * The backward pass of nnc_cbsp_f32 from the same packed form, the indices never unpacked and W never decoded
  * (csrc/nnc_cbspgrad.hip).  The form, z, c_z and d are nnc_cbsp_f32's; g = dL/dy float32[m, ncols].
  * nnc_cbsp_dx_f32   dx[m, kdim] = c_z * sum_o g[r, o] + sum over the stored (i, o) of g[r, o] * d[labels[i, o]]: the Jacobian of

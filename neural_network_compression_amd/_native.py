@@ -36,6 +36,9 @@ CBDC_PLAN_FIELDS = ("path", "vb", "mt", "copies", "splits", "rps", "aligned", "l
 CBSP_ROWSUM_NONE, CBSP_ROWSUM_FUSED, CBSP_ROWSUM_PASS = 0, 1, 2   # nnc_cbsp_plan: how the row sums of x are formed (include/nnc.h)
 CBSP_PLAN_LEN = 11
 CBSP_PLAN_FIELDS = ("path", "mt", "copies", "entries", "splits", "rps", "rowsum", "lds", "col_tiles", "row_tiles", "workspace")
+CBPK_TABLE_NONE, CBPK_TABLE_BANKED = 0, 1   # nnc_cbpk_plan: the layout of the lookup table (include/nnc.h)
+CBPK_PLAN_LEN = 14
+CBPK_PLAN_FIELDS = ("path", "vb", "mt", "cols", "xrows", "table", "copies", "entries", "splits", "rps", "lds", "col_tiles", "row_tiles", "workspace")
 CBSPDX_PLAN_LEN = 11   # nnc_cbsp_dx_plan / nnc_cbsp_dc_plan (include/nnc.h)
 CBSPDX_PLAN_FIELDS = ("path", "mt", "segs", "copies", "entries", "splits", "cps", "lds", "col_tiles", "row_tiles", "workspace")
 CBSPDC_PLAN_LEN = 11
@@ -187,6 +190,14 @@ SIGNATURES = {
     "nnc_cbsp_dc_plan": (c_int, [c_i64, c_i64, c_i64, c_int, c_i32, c_i32, ctypes.POINTER(c_i64)]),
     "nnc_cbsp_dc_f32": (c_int, [c_void_p, c_void_p, c_i64, c_i64, c_void_p, c_i64, c_int, c_i64, c_i32, c_i64, c_i32, c_void_p, c_i32, c_void_p,
                                 c_i64, c_void_p]),
+    "nnc_cbpk_row_bytes": (c_i64, [c_i64, c_int]),
+    "nnc_cbpk_pack_bytes": (c_i64, [c_i64, c_i64, c_int]),
+    "nnc_cbpk_pack": (c_int, [c_void_p, c_int, c_i64, c_i64, c_int, c_void_p, c_i64, c_void_p, c_void_p]),
+    "nnc_cbpk_unpack": (c_int, [c_void_p, c_i64, c_int, c_i64, c_i64, c_void_p, c_int, c_void_p]),
+    "nnc_cbpk_workspace_bytes": (c_i64, [c_i64, c_i64, c_i64, c_int]),
+    "nnc_cbpk_plan": (c_int, [c_i64, c_i64, c_i64, c_int, c_i32, c_i32, ctypes.POINTER(c_i64)]),
+    "nnc_cbpk_f32": (c_int, [c_void_p, c_i64, c_i64, c_void_p, c_i64, c_int, c_i64, c_void_p, c_i32, c_void_p, c_i32, c_void_p, c_void_p, c_i64,
+                             c_void_p]),
     "nnc_huffman_codes": (c_int, [ctypes.POINTER(ctypes.c_uint8), c_i32, ctypes.POINTER(ctypes.c_uint32)]),
     "nnc_codec_chunks": (c_size, [c_i64]),
     "nnc_huffman_chunk_offsets": (c_int, [c_void_p, c_int, c_i64, c_void_p, c_i32, c_void_p, c_void_p]),

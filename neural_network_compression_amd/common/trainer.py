@@ -225,17 +225,19 @@ class Trainer(ABC):
                 layer.set_weights(tensors)
         return accuracies
 
-    def compressed_network(self, sparse=False, trainable=False) -> torch.nn.Module:
+    def compressed_network(self, sparse=False, trainable=False, packed=False) -> torch.nn.Module:
         """A copy of the network whose quantized layers run from their codebooks and centroid indices (compressed.py; the
         float32 weights are never rebuilt), with the centres as they stand (after fine_tune_centroids, the tuned ones).
         ``sparse``: False, True (the indices in the bitmap-sparse form) or "auto" (per layer, the smaller form).
-        ``trainable=True`` (with sparse=False only): the layers' centres are parameters with a backward pass."""
+        ``packed``: False, True (2- or 4-bit packed indices for every layer of at most 16 centres) or "auto" (per layer, the smallest
+        form).
+        ``trainable=True`` (with sparse=False and packed=False only): the layers' centres are parameters with a backward pass."""
         models = getattr(self, "quantized_models_by_layer", None)
         if not models:
             raise RuntimeError("compressed_network needs a quantized network: call quantize first")
         from .. import compressed
 
-        return compressed.compress_network(self.neural_network, models, sparse=sparse, trainable=trainable)
+        return compressed.compress_network(self.neural_network, models, sparse=sparse, trainable=trainable, packed=packed)
 
     def _discard_quantization(self) -> None:
         """The weights are about to change: the centroid indices of ``quantize`` no longer describe them, so nothing may store, run

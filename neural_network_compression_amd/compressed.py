@@ -7,14 +7,22 @@ tensor is never rebuilt.  Biases (one value per output column) are decoded once 
 
     CompressedDense.from_dense(dense, weight_model, bias_model)
     CompressedConv2D.from_conv(conv, weight_model, bias_model)     stride 1, padding "valid" | "same", NHWC in and out
-    compress_network(network, models_by_layer, sparse=False, trainable=False)   a deep copy with the quantized layers replaced
-    load_network(path, network, sparse=False)                      the same from a ``weights.nnc`` (Trainer.store_report)
+    compress_network(network, models_by_layer, sparse=False, trainable=False, packed=False)   a deep copy with the quantized layers replaced
+    load_network(path, network, sparse=False, packed=False)        the same from a ``weights.nnc`` (Trainer.store_report)
     compressed_nbytes(network)                                     resident bytes of the layers' tensors
 
 A pruned layer can instead keep its indices in the bitmap-sparse form (ops.pack_sparse_codes, csrc/nnc_cbsp.hip, DESIGN.md
 section 11): one bit per weight, a count per 64 columns, and only the indices that are not the skipped (pruned) cluster's.
 ``SparseCompressedDense`` / ``SparseCompressedConv2D``; ``sparse=True`` in compress_network / load_network /
 Trainer.compressed_network takes it for every quantized layer, ``sparse="auto"`` for each layer whose sparse form is smaller.
+
+A layer of at most 16 centres can keep its indices at 2 or 4 bits each (ops.pack_codes, csrc/nnc_cbpk.hip, DESIGN.md section
+14): rows of whole 16-byte groups, a half or a quarter of the byte form.  ``PackedCompressedDense`` / ``PackedCompressedConv2D``;
+``packed=True`` in compress_network / load_network / Trainer.compressed_network takes it for every layer it can hold (K <= 16:
+it is the number of centres that decides, not the ``bits`` of the fit), ``packed="auto"`` where it is the smallest.  Per layer
+the candidates are the byte form (unless ``sparse is True``, or ``packed is True`` and K <= 16), the bitmap-sparse form (if
+``sparse`` is not False) and the packed form (if ``packed`` is not False and K <= 16); the one with the fewest resident bytes is
+kept, on equal bytes the earlier in this list.  The selection is by bytes, not by speed.  Inference only: no trainable variant yet.
 
 These layers are inference only: under autograd, with an input that needs a gradient, they raise instead of returning a result
 that silently has none.  ``trainable=True`` in compress_network / Trainer.compressed_network gives the trainable variants instead
@@ -456,6 +464,104 @@ def _trainable_sparse(layer, weight_model, bias_model):
     raise TypeError(f"no compressed form of {type(layer).__name__}")
 
 
+class _PackedCodebookLayer(nn.Module):
+    """The indices in the 2- or 4-bit packed form (ops.PackedCodes: its buffer is the module's ``packed`` buffer), centers
+    float32[K <= 2^bits], bias float32[ncols] or None.  No kdim * ncols tensor stays resident."""
+
+    def __init__(self, codes: ops.PackedCodes, centers: torch.Tensor, bias: torch.Tensor | None, activation=None):
+        super().__init__()
+        self.kdim, self.ncols, self.bits, self.k = codes.kdim, codes.ncols, codes.bits, codes.k
+        if centers.numel() != codes.k:
+            raise ValueError(f"{centers.numel()} centres for indices into a codebook of {codes.k}")
+        self.register_buffer("packed", codes.packed)
+        self.register_buffer("centers", centers.reshape(-1).to(torch.float32).contiguous())
+        self.register_buffer("bias", None if bias is None else bias.reshape(-1).to(torch.float32).contiguous())
+        self.activation = activation
+        self._fused_relu = activation is torch.relu
+
+    @property
+    def codes(self) -> ops.PackedCodes:
+        return ops.PackedCodes(self.packed, self.kdim, self.ncols, self.bits, self.k)
+
+    def _matmul(self, x: torch.Tensor) -> torch.Tensor:
+        y = ops.packed_codebook_matmul(x, self.codes, self.centers, bias=self.bias, relu=self._fused_relu)
+        if self.activation is not None and not self._fused_relu:
+            y = self.activation(y)
+        return y
+
+    def get_weights(self):
+        return []
+
+    def nbytes(self) -> int:
+        return sum(t.numel() * t.element_size() for t in (self.packed, self.centers, self.bias) if t is not None)
+
+
+class PackedCompressedDense(_PackedCodebookLayer):
+    """Dense run from its codebook and the 2- or 4-bit packed form of its (in, out) indices."""
+
+    @classmethod
+    def from_dense(cls, dense, weight_model, bias_model=None, bits=None) -> "PackedCompressedDense":
+        if weight_model is None:
+            raise ValueError("the kernel was not quantized (no fitted model): keep the float32 layer")
+        kin, kout = dense.kernel.shape
+        centers, labels = _codes(weight_model, dense.kernel.device)
+        return cls.from_codes(kin, kout, labels, centers, _decoded_bias(dense.bias, bias_model), dense.activation, bits)
+
+    @classmethod
+    def from_codes(cls, kdim, ncols, labels, centers, bias, activation, bits=None) -> "PackedCompressedDense":
+        return cls(ops.pack_codes(labels, kdim, ncols, centers.numel(), bits), centers, bias, activation)
+
+    def forward(self, x: torch.Tensor) -> torch.Tensor:
+        return self._matmul(x.contiguous())
+
+
+class PackedCompressedConv2D(_PackedCodebookLayer):
+    """Conv2D (stride 1, NHWC) run from its codebook and the packed form of its indices, packed after the rows were put in
+    unfold order (keras_rows_for_unfold); patch chunking and the empty batch as CompressedConv2D."""
+
+    def __init__(self, kernel_size: int, cin: int, pad: int, codes: ops.PackedCodes, centers: torch.Tensor, bias: torch.Tensor | None,
+                 activation=None):
+        if codes.kdim != kernel_size * kernel_size * cin:
+            raise ValueError(f"{codes.kdim} index rows for a {kernel_size} x {kernel_size} x {cin} kernel")
+        super().__init__(codes, centers, bias, activation)
+        self.kernel_size, self.cin, self.pad = int(kernel_size), int(cin), int(pad)
+
+    @classmethod
+    def from_conv(cls, conv, weight_model, bias_model=None, bits=None) -> "PackedCompressedConv2D":
+        if weight_model is None:
+            raise ValueError("the kernel was not quantized (no fitted model): keep the float32 layer")
+        h, w, cin, cout = conv.kernel.shape
+        if h != w:
+            raise ValueError("square kernels only (as layers.Conv2D)")
+        centers, labels = _codes(weight_model, conv.kernel.device)
+        return cls.from_codes(h, cin, cout, conv.pad, labels, centers, _decoded_bias(conv.bias, bias_model), conv.activation, bits)
+
+    @classmethod
+    def from_codes(cls, kernel_size, cin, cout, pad, labels, centers, bias, activation, bits=None) -> "PackedCompressedConv2D":
+        """labels in the Keras order of the (h, w, in, out) kernel."""
+        ops.packed_bits(centers.numel(), bits)   # a codebook that does not fit raises before the unfold
+        unf = _unfold_labels(kernel_size, cin, cout, labels)
+        codes = ops.pack_codes(unf, kernel_size * kernel_size * cin, cout, centers.numel(), bits)
+        del unf
+        return cls(kernel_size, cin, pad, codes, centers, bias, activation)
+
+    def forward(self, x: torch.Tensor) -> torch.Tensor:   # x: (N, H, W, C)
+        return _conv_forward(self, x)
+
+
+PACKED_MAX_K = 16   # the packed form holds at most 4-bit indices
+
+
+def _check_packed(packed, sparse=False, trainable=False):
+    if packed not in (False, True, "auto"):
+        raise ValueError(f"packed must be False, True or 'auto', got {packed!r}")
+    if packed is True and sparse is True:
+        raise ValueError("sparse=True and packed=True both ask for every layer: take one, or 'auto' for either")
+    if trainable and packed is not False:
+        raise ValueError("trainable=True needs packed=False: the packed layers are inference only (there is no backward pass from "
+                         "2- and 4-bit packed indices yet)")
+
+
 def _check_sparse(sparse):
     if sparse not in (False, True, "auto"):
         raise ValueError(f"sparse must be False, True or 'auto', got {sparse!r}")
@@ -472,23 +578,48 @@ def _pick(dense_layer, make_sparse, sparse):
     return sp if sp.nbytes() < de.nbytes() else de
 
 
-def _from_codes(layer, shape, labels, centers, bias, sparse):
+def _pick3(k, make_byte, make_sparse, make_packed, sparse, packed):
+    """The candidates in the order byte form (unless ``sparse is True``, or ``packed is True`` and K <= 16), bitmap-sparse form (if
+    ``sparse`` is not False), packed form (if ``packed`` is not False and K <= 16); the one with the fewest resident bytes, on
+    equal bytes the earliest."""
+    fits = k <= PACKED_MAX_K
+    makers = []
+    if sparse is not True and not (packed is True and fits):
+        makers.append(make_byte)
+    if sparse is not False:
+        makers.append(make_sparse)
+    if packed is not False and fits:
+        makers.append(make_packed)
+    best = None
+    for make in makers:
+        cand = make()
+        if best is None or cand.nbytes() < best.nbytes():
+            best = cand
+    return best
+
+
+def _from_codes(layer, shape, labels, centers, bias, sparse, packed=False):
     from .neural_networks.layers import Conv2D, Dense
 
     if isinstance(layer, Dense):
-        return _pick(lambda: CompressedDense(shape[0], shape[1], labels, centers, bias, layer.activation),
-                     lambda: SparseCompressedDense.from_codes(shape[0], shape[1], labels, centers, bias, layer.activation), sparse)
-    if isinstance(layer, Conv2D):
-        return _pick(lambda: CompressedConv2D.from_codes(shape[0], shape[2], shape[3], layer.pad, labels, centers, bias, layer.activation),
-                     lambda: SparseCompressedConv2D.from_codes(shape[0], shape[2], shape[3], layer.pad, labels, centers, bias, layer.activation),
-                     sparse)
-    raise TypeError(f"no compressed form of {type(layer).__name__}")
+        args = (shape[0], shape[1], labels, centers, bias, layer.activation)
+        make_byte, make_sparse, make_packed = (lambda: CompressedDense(*args), lambda: SparseCompressedDense.from_codes(*args),
+                                               lambda: PackedCompressedDense.from_codes(*args))
+    elif isinstance(layer, Conv2D):
+        args = (shape[0], shape[2], shape[3], layer.pad, labels, centers, bias, layer.activation)
+        make_byte, make_sparse, make_packed = (lambda: CompressedConv2D.from_codes(*args), lambda: SparseCompressedConv2D.from_codes(*args),
+                                               lambda: PackedCompressedConv2D.from_codes(*args))
+    else:
+        raise TypeError(f"no compressed form of {type(layer).__name__}")
+    if packed is False:
+        return _pick(make_byte, make_sparse, sparse)
+    return _pick3(centers.numel(), make_byte, make_sparse, make_packed, sparse, packed)
 
 
-def _replace(layer, weight_model, bias_model, sparse=False):
+def _replace(layer, weight_model, bias_model, sparse=False, packed=False):
     from .neural_networks.layers import Conv2D, Dense
 
-    if sparse is False:
+    if sparse is False and packed is False:
         if isinstance(layer, Dense):
             return CompressedDense.from_dense(layer, weight_model, bias_model)
         if isinstance(layer, Conv2D):
@@ -497,23 +628,26 @@ def _replace(layer, weight_model, bias_model, sparse=False):
     if not isinstance(layer, (Dense, Conv2D)):
         raise TypeError(f"no compressed form of {type(layer).__name__}")
     centers, labels = _codes(weight_model, layer.kernel.device)
-    return _from_codes(layer, tuple(layer.kernel.shape), labels, centers, _decoded_bias(layer.bias, bias_model), sparse)
+    return _from_codes(layer, tuple(layer.kernel.shape), labels, centers, _decoded_bias(layer.bias, bias_model), sparse, packed)
 
 
-def compress_network(network: nn.Module, models_by_layer, sparse=False, trainable=False) -> nn.Module:
+def compress_network(network: nn.Module, models_by_layer, sparse=False, trainable=False, packed=False) -> nn.Module:
     """A deep copy of ``network`` whose quantized layers (``models_by_layer``: layer -> [kernel model, bias model], as
     Trainer.quantized_models_by_layer) run from their codebooks.  Layers are replaced by the attribute names of
     ``get_config()``; a layer whose kernel passed through unquantized (model None) stays float32.  ``sparse``: False (the
     indices as they are), True (the bitmap-sparse form, skipping the most frequent index), "auto" (per layer, the smaller).
+    ``packed``: False, True (2- or 4-bit packed indices for every layer of at most 16 centres, the others in the byte form) or
+    "auto"; with ``sparse`` it decides per layer by resident bytes as the module's docstring tells.
     ``trainable=True`` (dense indices only): TrainableCompressedDense / TrainableCompressedConv2D, centres as parameters;
     compress_network_trainable gives the bitmap-sparse trainable layers too."""
     _check_sparse(sparse)
+    _check_packed(packed, sparse, trainable)
     if trainable and sparse is not False:
         raise ValueError("trainable=True needs sparse=False here: use compress_network_trainable(..., sparse=...) for trainable "
                          "bitmap-sparse layers")
     if trainable:
         return compress_network_trainable(network, models_by_layer)
-    return _compress_each(network, models_by_layer, lambda layer, wm, bm: _replace(layer, wm, bm, sparse))
+    return _compress_each(network, models_by_layer, lambda layer, wm, bm: _replace(layer, wm, bm, sparse, packed))
 
 
 def compress_network_trainable(network: nn.Module, models_by_layer, sparse=False) -> nn.Module:
@@ -539,13 +673,14 @@ def _compress_each(network: nn.Module, models_by_layer, make) -> nn.Module:
     return out
 
 
-def load_network(path: str, network: nn.Module, device=None, sparse=False) -> nn.Module:
+def load_network(path: str, network: nn.Module, device=None, sparse=False, packed=False) -> nn.Module:
     """``compress_network`` from a stored network (storage.save_compressed, as Trainer.store_report writes it: records
     "{layer}.weights" / "{layer}.biases").  ``network`` gives the architecture; layers stored raw get the stored float32 values.
-    ``sparse`` as in compress_network."""
+    ``sparse`` and ``packed`` as in compress_network: the stored format is the same, the indices are packed after loading."""
     from . import storage
 
     _check_sparse(sparse)
+    _check_packed(packed, sparse)
     device = next(network.parameters()).device if device is None else device
     codes = storage.load_compressed_codes(path, device)
     out = copy.deepcopy(network)
@@ -567,17 +702,17 @@ def load_network(path: str, network: nn.Module, device=None, sparse=False) -> nn
             target.set_weights([went.reshape(target.kernel.shape)] + ([bias.reshape(target.bias.shape)] if bias is not None else []))
             continue
         shape, centers, labels = went
-        setattr(out, name, _from_codes(layer, tuple(shape), labels, centers, bias, sparse))
+        setattr(out, name, _from_codes(layer, tuple(shape), labels, centers, bias, sparse, packed))
     return out
 
 
 def compressed_nbytes(network: nn.Module) -> int:
-    """Resident bytes of the tensors of ``network``'s layers (or of one layer): indices (or their bitmap-sparse form) + codebook +
+    """Resident bytes of the tensors of ``network``'s layers (or of one layer): indices (or their bitmap-sparse or packed form) + codebook +
     decoded bias for the compressed ones, the float32 parameters for the others."""
     layers = network.get_config().values() if hasattr(network, "get_config") else [network]
     total = 0
     for layer in layers:
-        if isinstance(layer, (_CodebookLayer, _SparseCodebookLayer, _TrainableCentres)):
+        if isinstance(layer, (_CodebookLayer, _SparseCodebookLayer, _PackedCodebookLayer, _TrainableCentres)):
             total += layer.nbytes()
         else:
             total += sum(p.numel() * p.element_size() for p in layer.parameters())

@@ -315,6 +315,14 @@ __global__ __launch_bounds__(256) void k_cbmm_reduce(const float *__restrict__ p
     }
 }
 
+int cbmm_reduce(const float *part, long long splits, long long mn, long long ncols, const float *bias, int relu, float *y, hipStream_t s)
+{
+    const int rgrid = (int)std::max(1LL, std::min(cdiv(mn, 64), 8192LL));
+    hipLaunchKernelGGL(k_cbmm_reduce, dim3(rgrid), dim3(256), 0, s, part, splits, mn, ncols, bias, relu, y);
+    LAUNCHCHK("k_cbmm_reduce");
+    return NNC_OK;
+}
+
 // ------------------------------------------------------------------ C ABI
 static int cb_check(int64_t m, int64_t kdim, int64_t ncols, int label_bytes, int32_t k)
 {
@@ -409,12 +417,9 @@ extern "C" int nnc_cbmm_f32(const float *x, int64_t m, int64_t kdim, const void 
 
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     const long long mn = m * ncols;
-    const int rgrid = (int)std::max(1LL, std::min(cdiv(mn, 64), 8192LL));
     const CbPlan p = cb_plan(m, kdim, ncols, label_bytes, k, cu_count(), reinterpret_cast<uintptr_t>(labels));
     if (p.path == NNC_CBMM_BIAS) {   // kdim = 0: y = bias (zeros without one)
-        hipLaunchKernelGGL(k_cbmm_reduce, dim3(rgrid), dim3(256), 0, s, (const float *)nullptr, 0LL, mn, (long long)ncols, bias_dev, (int)relu, y);
-        LAUNCHCHK("k_cbmm_reduce");
-        return NNC_OK;
+        return cbmm_reduce(nullptr, 0, mn, ncols, bias_dev, relu, y, s);
     }
     const int direct = p.splits == 1;
     float *out = direct ? y : reinterpret_cast<float *>(workspace);
@@ -434,9 +439,7 @@ extern "C" int nnc_cbmm_f32(const float *x, int64_t m, int64_t kdim, const void 
         LAUNCHCHK("k_cbmm_tiled");
     }
     if (!direct) {
-        hipLaunchKernelGGL(k_cbmm_reduce, dim3(rgrid), dim3(256), 0, s, reinterpret_cast<const float *>(workspace), (long long)p.splits, mn, (long long)ncols,
-                           bias_dev, (int)relu, y);
-        LAUNCHCHK("k_cbmm_reduce");
+        return cbmm_reduce(reinterpret_cast<const float *>(workspace), p.splits, mn, ncols, bias_dev, relu, y, s);
     }
     return NNC_OK;
 }

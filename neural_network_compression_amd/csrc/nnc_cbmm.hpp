@@ -1,6 +1,7 @@
 // nnc_cbmm.hpp -- what the codebook matmul (nnc_cbmm.hip), its bitmap-sparse sibling (nnc_cbsp.hip) and its backward pass
 // (nnc_cbgrad.hip) share: the launch constants, the per-bank LDS codebook layout, the label-row loads of the stream kernels and the
-// register-blocked FMA step of the tiled kernels.
+// register-blocked FMA step of the tiled kernels.  The 2- and 4-bit packed form (nnc_cbpk.hip) takes cb_fill, tb_tile_fma and
+// the split-K combine from here.
 #pragma once
 #include "nnc_common.hpp"
 
@@ -16,6 +17,10 @@
 #define TB_K 8
 
 static inline long long cdiv(long long a, long long b) { return (a + b - 1) / b; }
+
+// y[idx] = the split-K partials part[s][idx], s < splits, summed in an order that depends on `splits` alone, + bias[idx % ncols],
+// ReLU (k_cbmm_reduce, nnc_cbmm.hip; splits = 0: y = bias or 0), launched on `s`: NNC_OK or the launch error
+int cbmm_reduce(const float *part, long long splits, long long mn, long long ncols, const float *bias, int relu, float *y, hipStream_t s);
 
 // the per-bank table: entry j of lane l at word j * copies + (l mod copies), copies = 1 << cshift
 template <typename LT> struct CbTable;

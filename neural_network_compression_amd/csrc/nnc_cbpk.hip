@@ -1,0 +1,532 @@
+// nnc_cbpk.hip -- the quantized layer of at most 16 centres run from 2- or 4-bit packed indices (include/nnc.h, nnc_cbpk_*;
+// DESIGN.md section 14).
+//
+// The form of a (kdim, ncols) index matrix at `bits` = 2 or 4: one buffer of kdim rows of row_bytes = 16 * ceil(ncols * bits /
+// 128) bytes; label (i, o) in byte i * row_bytes + o * bits / 8 at bit o * bits % 8, low bits first; the fields past ncols are 0.
+// Every row starts on a 16-byte boundary: a lane's load of 1..16 bytes is aligned and never leaves the buffer.
+//
+// Kernels:
+//   k_cbpk_pack / k_cbpk_unpack   one pass each, a thread per dword of the packed form (8 or 16 labels), whole-dword stores on
+//                  the packed side; the pack counts the labels >= 2^bits (an integer atomic per wave that saw one).
+//   k_cbpk_stream  m <= 16: k_cbmm_stream without its unaligned half.  A wave owns 64 lanes x VB bytes of a packed row (VB = 16
+//                  .. 1: at most the load whose 8 * VB / BITS columns times the MT rows of x stay within 64 accumulators per
+//                  lane; narrower where the shape leaves wide lanes idle or the device short of workgroups, see pk_plan), 8 rows in flight (4 of 16-byte loads) straight to VGPRs, x[r, i] broadcast by vector load + v_readlane.  The table:
+//                  2^BITS floats (centres, then zeros) with 32 per-bank copies, 2 KiB or 512 B of LDS, one ds_read_b32 per
+//                  weight at byte (label << 7 | (lane & 31) << 2): a shift and an and-or per lookup, no bank conflict.  The 4
+//                  waves of a workgroup split its rows and are summed in LDS in wave order; workgroups split K.
+//   k_cbpk_tiled   m > 16: the 128 x 128 tile of k_cbmm_tiled; a thread decodes 4 columns of a tile row from the packed dword
+//                  that holds them into the LDS W tile, then tb_tile_fma.
+//   the split-K partials are summed by k_cbmm_reduce (cbmm_reduce) in split order.  No float atomics anywhere.
+// An index >= K reads 0 (the table's zero entries).  Columns past ncols are computed from the padding and never stored.
+#include "nnc_cbmm.hpp"
+
+#define PK_COPIES 32              // per-bank copies of the table
+#define PK_CSHIFT 5
+#define PK_ACC 64                 // accumulators per lane: columns per lane per row x rows of x
+
+// ------------------------------------------------------------------ the layout (host)
+static inline bool pk_bits_ok(int bits) { return bits == 2 || bits == 4; }
+static inline long long pk_row_bytes(long long ncols, int bits) { return 16 * cdiv(ncols * bits, 128); }
+static inline bool pk_size_ok(int64_t kdim, int64_t ncols) { return kdim <= (1LL << 40) && ncols <= (1LL << 40) && (ncols == 0 || kdim <= (1LL << 44) / cdiv(ncols, 2)); }
+
+extern "C" int64_t nnc_cbpk_row_bytes(int64_t ncols, int bits)
+{
+    if (ncols < 0 || ncols > (1LL << 40) || !pk_bits_ok(bits)) return 0;
+    return pk_row_bytes(ncols, bits);
+}
+
+extern "C" int64_t nnc_cbpk_pack_bytes(int64_t kdim, int64_t ncols, int bits)
+{
+    if (kdim < 0 || ncols < 0 || !pk_bits_ok(bits) || !pk_size_ok(kdim, ncols)) return 0;
+    return kdim * pk_row_bytes(ncols, bits);
+}
+
+// ------------------------------------------------------------------ pack / unpack
+__device__ __forceinline__ uint32_t pk_label(const unsigned char *labels, int lb, long long idx)
+{
+    return lb == 1 ? (uint32_t)labels[idx] : (uint32_t)reinterpret_cast<const uint16_t *>(labels)[idx];
+}
+
+// thread -> dword d of row i: the labels of columns d * PER .. d * PER + PER - 1 (0 past ncols)
+template <int BITS>
+__global__ __launch_bounds__(256) void k_cbpk_pack(const unsigned char *__restrict__ labels, int lb, long long kdim, long long ncols, long long row_dwords,
+                                                   uint32_t *__restrict__ packed, unsigned int *__restrict__ bad)
+{
+    constexpr int PER = 32 / BITS;
+    constexpr uint32_t MASK = (1u << BITS) - 1;
+    const long long total = kdim * row_dwords;
+    uint32_t nbad = 0;
+    for (long long t = (long long)blockIdx.x * 256 + threadIdx.x; t < total; t += (long long)gridDim.x * 256) {
+        const long long i = t / row_dwords, c0 = (t - i * row_dwords) * PER;
+        uint32_t word = 0;
+#pragma unroll
+        for (int f = 0; f < PER; ++f) {
+            if (c0 + f < ncols) {
+                const uint32_t l = pk_label(labels, lb, i * ncols + c0 + f);
+                nbad += l > MASK;
+                word |= (l & MASK) << (BITS * f);
+            }
+        }
+        packed[t] = word;
+    }
+    if (bad && __any(nbad != 0)) {
+        for (int o = 32; o > 0; o >>= 1) nbad += __shfl_down(nbad, o);
+        if ((threadIdx.x & 63) == 0) atomicAdd(bad, nbad);
+    }
+}
+
+template <int BITS>
+__global__ __launch_bounds__(256) void k_cbpk_unpack(const uint32_t *__restrict__ packed, long long kdim, long long ncols, long long row_dwords, int lb,
+                                                     unsigned char *__restrict__ labels)
+{
+    constexpr int PER = 32 / BITS;
+    constexpr uint32_t MASK = (1u << BITS) - 1;
+    const long long total = kdim * row_dwords;
+    for (long long t = (long long)blockIdx.x * 256 + threadIdx.x; t < total; t += (long long)gridDim.x * 256) {
+        const long long i = t / row_dwords, c0 = (t - i * row_dwords) * PER;
+        if (c0 >= ncols) continue;
+        const uint32_t word = packed[t];
+#pragma unroll
+        for (int f = 0; f < PER; ++f) {
+            if (c0 + f < ncols) {
+                const uint32_t l = (word >> (BITS * f)) & MASK;
+                if (lb == 1) labels[i * ncols + c0 + f] = (unsigned char)l;
+                else reinterpret_cast<uint16_t *>(labels)[i * ncols + c0 + f] = (uint16_t)l;
+            }
+        }
+    }
+}
+
+static int pk_check_form(const char *fn, int64_t kdim, int64_t ncols, int bits)
+{
+    if (kdim < 0 || ncols < 0) return fail(NNC_EINVAL, std::string(fn) + ": negative size");
+    if (!pk_bits_ok(bits)) return fail(NNC_EINVAL, std::string(fn) + ": bits must be 2 or 4");
+    if (!pk_size_ok(kdim, ncols)) return fail(NNC_EINVAL, std::string(fn) + ": size too large");
+    return NNC_OK;
+}
+
+static int pk_check_buffer(const char *fn, const void *packed, int64_t packed_bytes, int64_t kdim, int64_t ncols, int bits)
+{
+    if (packed_bytes != kdim * pk_row_bytes(ncols, bits)) return fail(NNC_EINVAL, std::string(fn) + ": packed_bytes is not nnc_cbpk_pack_bytes(kdim, ncols, bits)");
+    if (packed_bytes > 0 && !packed) return fail(NNC_EINVAL, std::string(fn) + ": packed is NULL");
+    if (reinterpret_cast<uintptr_t>(packed) % 16) return fail(NNC_EINVAL, std::string(fn) + ": packed must be 16-byte aligned");
+    return NNC_OK;
+}
+
+static int pk_check_labels(const char *fn, const void *labels, int label_bytes, int64_t kdim, int64_t ncols)
+{
+    if (label_bytes != 1 && label_bytes != 2) return fail(NNC_EINVAL, std::string(fn) + ": label_bytes must be 1 or 2");
+    if (kdim > 0 && ncols > 0 && !labels) return fail(NNC_EINVAL, std::string(fn) + ": labels is NULL");
+    if (label_bytes == 2 && reinterpret_cast<uintptr_t>(labels) % 2) return fail(NNC_EINVAL, std::string(fn) + ": 2-byte labels must be 2-byte aligned");
+    return NNC_OK;
+}
+
+static int pk_grid(long long dwords) { return (int)std::max(1LL, std::min(cdiv(dwords, 256), 65536LL)); }
+
+extern "C" int nnc_cbpk_pack(const void *labels, int label_bytes, int64_t kdim, int64_t ncols, int bits, void *packed, int64_t packed_bytes,
+                             uint32_t *bad_count_dev, void *stream)
+{
+    int rc = pk_check_form("nnc_cbpk_pack", kdim, ncols, bits);
+    if (rc != NNC_OK) return rc;
+    if ((rc = pk_check_labels("nnc_cbpk_pack", labels, label_bytes, kdim, ncols)) != NNC_OK) return rc;
+    if ((rc = pk_check_buffer("nnc_cbpk_pack", packed, packed_bytes, kdim, ncols, bits)) != NNC_OK) return rc;
+    if (reinterpret_cast<uintptr_t>(bad_count_dev) % 4) return fail(NNC_EINVAL, "nnc_cbpk_pack: bad_count_dev must be 4-byte aligned");
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    if (bad_count_dev) HIPCHK(hipMemsetAsync(bad_count_dev, 0, 4, s));
+    if (packed_bytes == 0) return NNC_OK;
+    const long long rd = pk_row_bytes(ncols, bits) / 4;
+    const unsigned char *lab = reinterpret_cast<const unsigned char *>(labels);
+    if (bits == 4)
+        hipLaunchKernelGGL(k_cbpk_pack<4>, dim3(pk_grid(kdim * rd)), dim3(256), 0, s, lab, label_bytes, (long long)kdim, (long long)ncols, rd,
+                           reinterpret_cast<uint32_t *>(packed), bad_count_dev);
+    else
+        hipLaunchKernelGGL(k_cbpk_pack<2>, dim3(pk_grid(kdim * rd)), dim3(256), 0, s, lab, label_bytes, (long long)kdim, (long long)ncols, rd,
+                           reinterpret_cast<uint32_t *>(packed), bad_count_dev);
+    LAUNCHCHK("k_cbpk_pack");
+    return NNC_OK;
+}
+
+extern "C" int nnc_cbpk_unpack(const void *packed, int64_t packed_bytes, int bits, int64_t kdim, int64_t ncols, void *labels_out, int label_bytes_out,
+                               void *stream)
+{
+    int rc = pk_check_form("nnc_cbpk_unpack", kdim, ncols, bits);
+    if (rc != NNC_OK) return rc;
+    if ((rc = pk_check_labels("nnc_cbpk_unpack", labels_out, label_bytes_out, kdim, ncols)) != NNC_OK) return rc;
+    if ((rc = pk_check_buffer("nnc_cbpk_unpack", packed, packed_bytes, kdim, ncols, bits)) != NNC_OK) return rc;
+    if (packed_bytes == 0) return NNC_OK;
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    const long long rd = pk_row_bytes(ncols, bits) / 4;
+    if (bits == 4)
+        hipLaunchKernelGGL(k_cbpk_unpack<4>, dim3(pk_grid(kdim * rd)), dim3(256), 0, s, reinterpret_cast<const uint32_t *>(packed), (long long)kdim,
+                           (long long)ncols, rd, label_bytes_out, reinterpret_cast<unsigned char *>(labels_out));
+    else
+        hipLaunchKernelGGL(k_cbpk_unpack<2>, dim3(pk_grid(kdim * rd)), dim3(256), 0, s, reinterpret_cast<const uint32_t *>(packed), (long long)kdim,
+                           (long long)ncols, rd, label_bytes_out, reinterpret_cast<unsigned char *>(labels_out));
+    LAUNCHCHK("k_cbpk_unpack");
+    return NNC_OK;
+}
+
+// ------------------------------------------------------------------ the plan (host)
+// Every decision nnc_cbpk_f32 takes before it launches; nnc_cbpk_plan reports it.
+struct PkPlan {
+    int path;                // NNC_CBMM_NONE / _STREAM / _TILED / _BIAS
+    int vb, mt;              // stream: packed bytes per lane per row, rows of x per launch (a power of two >= m)
+    int cols, xrows;         // stream: columns per lane per row (8 * vb / bits), rows of x per pass over the indices (= mt: one pass)
+    int table, copies, entries;
+    long long col_tiles, row_tiles;
+    long long splits, rows_per_split;
+    long long lds;
+};
+
+static PkPlan pk_plan(long long m, long long kdim, long long ncols, int bits, int cus)
+{
+    PkPlan p{};
+    if (m == 0 || ncols == 0) return p;
+    if (kdim == 0) {
+        p.path = NNC_CBMM_BIAS;
+        return p;
+    }
+    cus = std::max(1, std::min(cus, CB_PLAN_CUS));
+    p.table = NNC_CBPK_TABLE_BANKED;
+    p.entries = 1 << bits;
+    long long s;
+    if (m <= CB_SKINNY_M) {
+        p.path = NNC_CBMM_STREAM;
+        p.mt = m <= 1 ? 1 : (m <= 2 ? 2 : (m <= 4 ? 4 : (m <= 8 ? 8 : 16)));
+        p.xrows = p.mt;
+        // every wave keeps at least one batch of rows; the partials (splits x m x ncols x 4 B) stay within the packed index
+        // stream (kdim x ncols x bits / 8 B)
+        const long long s_max = std::max(1LL, std::min(kdim / (CB_WAVES * CB_UNROLL), kdim * bits / (32 * m)));
+        // bytes per lane: at most a 16-byte load and PK_ACC accumulators; from there down to 4 bytes, the widest load that
+        // keeps four lanes in five on a column (the last column tile may be nearly empty) and gives every CU of the planning
+        // device a workgroup; else the narrowest.  Shape alone decides, so the splits below never shrink with more CUs.
+        const int cap = std::min(128 / bits, PK_ACC / p.mt);
+        p.cols = cap;
+        for (int c = cap; c * bits >= 32; c /= 2) {
+            p.cols = c;
+            const long long tiles = cdiv(ncols, 64LL * c);
+            if (tiles * 64 * c * 4 <= ncols * 5 && tiles * s_max >= CB_PLAN_CUS) break;
+        }
+        p.vb = p.cols * bits / 8;
+        p.copies = PK_COPIES;
+        p.row_tiles = 1;
+        p.col_tiles = cdiv(ncols, 64LL * p.cols);
+        s = std::min(cdiv(2LL * cus, p.col_tiles), s_max);          // enough workgroups for two per CU
+        p.lds = ((long long)p.entries * p.copies + (long long)p.mt * p.cols * 64 + p.entries) * 4;
+    } else {
+        p.path = NNC_CBMM_TILED;
+        p.copies = 1;
+        p.col_tiles = cdiv(ncols, TB_N);
+        p.row_tiles = cdiv(m, TB_M);
+        s = std::min({cdiv(2LL * cus, p.col_tiles * p.row_tiles), kdim / (16 * TB_K), 16LL});
+        p.lds = (long long)(TB_K * TB_M + TB_K * TB_N + p.entries) * 4;
+    }
+    s = std::max(1LL, s);
+    p.rows_per_split = cdiv(kdim, s);
+    p.splits = cdiv(kdim, p.rows_per_split);
+    return p;
+}
+
+static int64_t pk_ws_bytes(const PkPlan &p, long long m, long long ncols) { return p.splits > 1 ? (int64_t)p.splits * m * ncols * 4 : 0; }
+
+// ------------------------------------------------------------------ skinny: m <= 16
+template <int VB>
+__device__ __forceinline__ void pk_load(const unsigned char *p, uint32_t *w)
+{
+    if constexpr (VB == 1) w[0] = *p;
+    else if constexpr (VB == 2) w[0] = *reinterpret_cast<const uint16_t *>(p);
+    else load_chunk<VB>(p, w);
+}
+
+// grid (col_tiles, splits), CB_THREADS threads.  `out` is y (splits == 1: + bias, ReLU here) or the partials [split][m][ncols].
+template <int BITS, int VB, int MT>
+__global__ __launch_bounds__(CB_THREADS, 2) void k_cbpk_stream(const float *__restrict__ x, int m, long long kdim, const unsigned char *__restrict__ packed,
+                                                            long long row_bytes, long long ncols, const float *__restrict__ centers, int k,
+                                                            long long rows_per_split, const float *__restrict__ bias, int relu, int direct,
+                                                            float *__restrict__ out)
+{
+    constexpr int E = 8 * VB / BITS, N = VB >= 4 ? VB / 4 : 1, PER = 32 / BITS, ENTRIES = 1 << BITS;
+    constexpr uint32_t MASK = (1u << BITS) - 1;
+    constexpr int U = E >= 32 ? 4 : CB_UNROLL;          // rows in flight: a 16-byte row keeps a lane busy for 32 or 64 lookups
+    static_assert(E * MT <= PK_ACC, "accumulators per lane");
+    extern __shared__ float smem[];
+    float *cb = smem;                                   // [ENTRIES][PK_COPIES]
+    float *red = smem + ENTRIES * PK_COPIES;            // [MT * E][64]
+    float *stage = red + MT * E * 64;
+    cb_fill(cb, stage, centers, k, ENTRIES, PK_CSHIFT);
+
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const long long c0 = (long long)blockIdx.x * (64 * E) + lane * E;
+    const bool active = c0 < ncols;                     // then the lane's VB bytes lie inside the padded row
+    const long long s_lo = (long long)blockIdx.y * rows_per_split, s_hi = std::min(kdim, s_lo + rows_per_split);
+    const long long per_wave = (s_hi - s_lo + CB_WAVES - 1) / CB_WAVES;
+    const long long i0 = std::min(s_hi, s_lo + wave * per_wave), i1 = std::min(s_hi, i0 + per_wave);
+    const unsigned char *mine = packed + (active ? (long long)blockIdx.x * (64 * VB) + lane * VB : 0LL);
+    const char *tab = reinterpret_cast<const char *>(cb) + ((lane & (PK_COPIES - 1)) << 2);
+
+    float acc[MT][E];
+#pragma unroll
+    for (int r = 0; r < MT; ++r)
+#pragma unroll
+        for (int e = 0; e < E; ++e) acc[r][e] = 0.0f;
+    __syncthreads();
+
+    // x[r, i + u] of a batch of U rows: lane f holds value f = r * U + u (and f + 64), broadcast by v_readlane
+    auto load_x = [&](long long i, int U, float &xa, float &xb) {
+        const int f0 = lane, f1 = lane + 64;
+        const int r0 = f0 / U, r1 = f1 / U;
+        xa = r0 < m ? x[(long long)r0 * kdim + i + f0 % U] : 0.0f;
+        xb = (MT * U > 64 && r1 < m) ? x[(long long)r1 * kdim + i + f1 % U] : 0.0f;
+    };
+    auto consume = [&](const uint32_t *w, float xa, float xb, int u, int U) {
+        float xv[MT];
+#pragma unroll
+        for (int r = 0; r < MT; ++r) {
+            const int f = r * U + u;
+            xv[r] = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, f < 64 ? xa : xb), f & 63));
+        }
+#pragma unroll
+        for (int e = 0; e < E; ++e) {
+            constexpr int SH = 7;                                        // entry l of this lane's copy at byte l << 7
+            const int bit = BITS * (e % PER);
+            const uint32_t d = w[e / PER];
+            const uint32_t a = (bit >= SH ? d >> (bit - SH) : d << (SH - bit)) & (MASK << SH);
+            const float wv = *reinterpret_cast<const float *>(tab + a);
+#pragma unroll
+            for (int r = 0; r < MT; ++r) acc[r][e] = __builtin_fmaf(xv[r], wv, acc[r][e]);
+        }
+    };
+
+    long long i = i0;
+    for (; i + U <= i1; i += U) {
+        uint32_t w[U][N];
+        float xa, xb;
+#pragma unroll
+        for (int u = 0; u < U; ++u) pk_load<VB>(mine + (i + u) * row_bytes, w[u]);
+        load_x(i, U, xa, xb);
+#pragma unroll
+        for (int u = 0; u < U; ++u) consume(w[u], xa, xb, u, U);
+    }
+    for (; i < i1; ++i) {
+        uint32_t w[N];
+        float xa, xb;
+        pk_load<VB>(mine + i * row_bytes, w);
+        load_x(i, 1, xa, xb);
+        consume(w, xa, xb, 0, 1);
+    }
+
+    // the waves' sums, added to wave 0's in wave order
+    for (int src = 1; src < CB_WAVES; ++src) {
+        __syncthreads();
+        if (wave == src) {
+#pragma unroll
+            for (int r = 0; r < MT; ++r)
+#pragma unroll
+                for (int e = 0; e < E; ++e) red[(r * E + e) * 64 + lane] = acc[r][e];
+        }
+        __syncthreads();
+        if (wave == 0) {
+#pragma unroll
+            for (int r = 0; r < MT; ++r)
+#pragma unroll
+                for (int e = 0; e < E; ++e) acc[r][e] += red[(r * E + e) * 64 + lane];
+        }
+    }
+    if (wave != 0 || !active) return;
+#pragma unroll
+    for (int r = 0; r < MT; ++r) {
+#pragma unroll
+        for (int e = 0; e < E; ++e) {
+            const long long c = c0 + e;
+            if (r >= m || c >= ncols) continue;
+            float v = acc[r][e];
+            if (direct) {
+                if (bias) v += bias[c];
+                if (relu) v = v < 0.0f ? 0.0f : v;   // NaN stays NaN, as torch.relu
+                out[(long long)r * ncols + c] = v;
+            } else {
+                out[((long long)blockIdx.y * m + r) * ncols + c] = v;
+            }
+        }
+    }
+}
+
+// ------------------------------------------------------------------ tiled: m > 16
+// grid (col_tiles * row_tiles, splits), 256 threads, thread (tx, ty) as in k_cbmm_tiled.  The W tile of a TB_K step is TB_K rows
+// of TB_N * BITS / 32 packed dwords (a tile starts on a dword: 128 columns are 64 or 32 bytes).  Thread t decodes columns
+// (t % 32) * 4 .. + 3 of row t / 32 from the dword that holds them: the 2 (4 bits) or 4 (2 bits) threads of a dword load the same
+// address, one request, and all 256 threads share the lookups and the LDS stores.
+template <int BITS>
+__global__ __launch_bounds__(256) void k_cbpk_tiled(const float *__restrict__ x, long long m, long long kdim, const unsigned char *__restrict__ packed,
+                                                    long long row_bytes, long long ncols, const float *__restrict__ centers, int k, long long col_tiles,
+                                                    long long rows_per_split, const float *__restrict__ bias, int relu, int direct, float *__restrict__ out)
+{
+    constexpr int ENTRIES = 1 << BITS;
+    constexpr uint32_t MASK = (1u << BITS) - 1;
+    extern __shared__ float smem[];
+    float *xs = smem;                      // [TB_K][TB_M]
+    float *ws = xs + TB_K * TB_M;          // [TB_K][TB_N]
+    float *cb = ws + TB_K * TB_N;          // 2^BITS entries (zeros from k on)
+    for (int j = threadIdx.x; j < ENTRIES; j += 256) cb[j] = j < k ? centers[j] : 0.0f;
+
+    const int t = threadIdx.x, tx = t & 15, ty = t >> 4;
+    const long long n0 = (blockIdx.x % col_tiles) * TB_N, m0 = (blockIdx.x / col_tiles) * TB_M;
+    const long long k_lo = (long long)blockIdx.y * rows_per_split, k_hi = std::min(kdim, k_lo + rows_per_split);
+    float acc[8][8];
+#pragma unroll
+    for (int a = 0; a < 8; ++a)
+#pragma unroll
+        for (int b = 0; b < 8; ++b) acc[a][b] = 0.0f;
+
+    const int xr = t >> 1, xk = (t & 1) * 4;       // x tile: row xr, k xk..xk+3
+    const int wk = t >> 5, wc = (t & 31) * 4;      // W tile: k wk, columns wc..wc+3
+    const long long wbyte = n0 * BITS / 8 + (wc * BITS / 32) * 4;
+    const int wshift = wc * BITS % 32;
+    for (long long kb = k_lo; kb < k_hi; kb += TB_K) {
+        __syncthreads();
+        {
+            const long long gr = m0 + xr;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const long long gk = kb + xk + j;
+                xs[(xk + j) * TB_M + xr] = (gr < m && gk < k_hi) ? x[gr * kdim + gk] : 0.0f;
+            }
+            const long long gk = kb + wk;
+            const bool live = gk < k_hi && wbyte < row_bytes;
+            const uint32_t word = live ? *reinterpret_cast<const uint32_t *>(packed + gk * row_bytes + wbyte) >> wshift : 0u;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) ws[wk * TB_N + wc + j] = live ? cb[(word >> (BITS * j)) & MASK] : 0.0f;
+        }
+        __syncthreads();
+        tb_tile_fma(xs, ws, tx, ty, acc);
+    }
+#pragma unroll
+    for (int a = 0; a < 8; ++a) {
+        const long long r = m0 + ty * 8 + a;
+#pragma unroll
+        for (int b = 0; b < 8; ++b) {
+            const long long c = n0 + tx * 8 + b;
+            if (r >= m || c >= ncols) continue;
+            float v = acc[a][b];
+            if (direct) {
+                if (bias) v += bias[c];
+                if (relu) v = v < 0.0f ? 0.0f : v;   // NaN stays NaN, as torch.relu
+                out[r * ncols + c] = v;
+            } else {
+                out[((long long)blockIdx.y * m + r) * ncols + c] = v;
+            }
+        }
+    }
+}
+
+// ------------------------------------------------------------------ C ABI
+static int pk_check(const char *fn, int64_t m, int64_t kdim, int64_t ncols, int bits, int32_t k)
+{
+    if (m < 0) return fail(NNC_EINVAL, std::string(fn) + ": negative size");
+    const int rc = pk_check_form(fn, kdim, ncols, bits);
+    if (rc != NNC_OK) return rc;
+    if (k < 1 || k > (1 << bits)) return fail(NNC_EINVAL, std::string(fn) + ": k outside 1..2^bits");
+    if (m > (1LL << 40)) return fail(NNC_EINVAL, std::string(fn) + ": size too large");
+    return NNC_OK;
+}
+
+extern "C" int64_t nnc_cbpk_workspace_bytes(int64_t m, int64_t kdim, int64_t ncols, int bits)
+{
+    if (m <= 0 || kdim <= 0 || ncols <= 0 || pk_check("nnc_cbpk_workspace_bytes", m, kdim, ncols, bits, 1) != NNC_OK) return 0;
+    return pk_ws_bytes(pk_plan(m, kdim, ncols, bits, CB_PLAN_CUS), m, ncols);
+}
+
+template <int BITS, int VB, int MT>
+static void launch_pk_stream(dim3 grid, size_t lds, hipStream_t s, const float *x, int m, long long kdim, const unsigned char *packed, long long row_bytes,
+                             long long ncols, const float *centers, int k, long long rps, const float *bias, int relu, int direct, float *out)
+{
+    hipLaunchKernelGGL((k_cbpk_stream<BITS, VB, MT>), grid, dim3(CB_THREADS), lds, s, x, m, kdim, packed, row_bytes, ncols, centers, k, rps, bias, relu,
+                       direct, out);
+}
+
+// every k_cbpk_stream instantiation there is; the plan is checked against this table, and the launch goes through it
+using PkStreamLaunch = void (*)(dim3, size_t, hipStream_t, const float *, int, long long, const unsigned char *, long long, long long, const float *, int,
+                                long long, const float *, int, int, float *);
+struct PkStreamCase {
+    int bits, vb, mt;
+    PkStreamLaunch fn;
+};
+#define PK_CASE(B, V, M) {B, V, M, launch_pk_stream<B, V, M>}
+static const PkStreamCase kPkStreamCases[] = {
+    PK_CASE(4, 16, 1), PK_CASE(4, 16, 2), PK_CASE(4, 8, 1), PK_CASE(4, 8, 2), PK_CASE(4, 8, 4), PK_CASE(4, 4, 1), PK_CASE(4, 4, 2),
+    PK_CASE(4, 4, 4),  PK_CASE(4, 4, 8),  PK_CASE(4, 2, 16),
+    PK_CASE(2, 16, 1), PK_CASE(2, 8, 1),  PK_CASE(2, 8, 2), PK_CASE(2, 4, 1), PK_CASE(2, 4, 2), PK_CASE(2, 4, 4), PK_CASE(2, 2, 8),
+    PK_CASE(2, 1, 16),
+};
+
+static PkStreamLaunch find_pk_stream(int bits, int vb, int mt)
+{
+    for (const PkStreamCase &c : kPkStreamCases)
+        if (c.bits == bits && c.vb == vb && c.mt == mt) return c.fn;
+    return nullptr;
+}
+
+static int no_pk_stream_case(int bits, int vb, int mt)
+{
+    return fail(NNC_EINVAL, "nnc_cbpk: no k_cbpk_stream instantiation for bits " + std::to_string(bits) + ", vb " + std::to_string(vb) + ", mt " +
+                                std::to_string(mt));
+}
+
+extern "C" int nnc_cbpk_plan(int64_t m, int64_t kdim, int64_t ncols, int bits, int32_t k, int32_t cus, int64_t *out)
+{
+    const int rc = pk_check("nnc_cbpk_plan", m, kdim, ncols, bits, k);
+    if (rc != NNC_OK) return rc;
+    if (cus < 1) return fail(NNC_EINVAL, "nnc_cbpk_plan: cus < 1");
+    if (!out) return fail(NNC_EINVAL, "nnc_cbpk_plan: out is NULL");
+    const PkPlan p = pk_plan(m, kdim, ncols, bits, cus);
+    if (p.path == NNC_CBMM_STREAM && !find_pk_stream(bits, p.vb, p.mt)) return no_pk_stream_case(bits, p.vb, p.mt);
+    const int64_t v[NNC_CBPK_PLAN_LEN] = {p.path, p.vb, p.mt, p.cols, p.xrows, p.table, p.copies, p.entries, p.splits, p.rows_per_split,
+                                          p.lds, p.col_tiles, p.row_tiles, pk_ws_bytes(p, m, ncols)};
+    for (int i = 0; i < NNC_CBPK_PLAN_LEN; ++i) out[i] = v[i];
+    return NNC_OK;
+}
+
+extern "C" int nnc_cbpk_f32(const float *x, int64_t m, int64_t kdim, const void *packed, int64_t packed_bytes, int bits, int64_t ncols,
+                            const float *centers_dev, int32_t k, const float *bias_dev, int32_t relu, float *y, void *workspace, int64_t workspace_bytes,
+                            void *stream)
+{
+    int rc = pk_check("nnc_cbpk_f32", m, kdim, ncols, bits, k);
+    if (rc != NNC_OK) return rc;
+    if ((rc = pk_check_buffer("nnc_cbpk_f32", packed, packed_bytes, kdim, ncols, bits)) != NNC_OK) return rc;
+    if (!centers_dev) return fail(NNC_EINVAL, "nnc_cbpk_f32: centers is NULL");
+    if (m > 0 && ncols > 0 && !y) return fail(NNC_EINVAL, "nnc_cbpk_f32: y is NULL");
+    if (m > 0 && ncols > 0 && kdim > 0 && !x) return fail(NNC_EINVAL, "nnc_cbpk_f32: x is NULL");
+    if (workspace_bytes < 0) return fail(NNC_EINVAL, "nnc_cbpk_f32: negative workspace size");
+    const int64_t need = nnc_cbpk_workspace_bytes(m, kdim, ncols, bits);
+    if (workspace_bytes < need) return fail(NNC_ENOSPACE, "nnc_cbpk_f32: workspace smaller than nnc_cbpk_workspace_bytes()");
+    if (need > 0 && !workspace) return fail(NNC_EINVAL, "nnc_cbpk_f32: workspace is NULL");
+    if (m == 0 || ncols == 0) return NNC_OK;
+
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    const long long mn = m * ncols;
+    const PkPlan p = pk_plan(m, kdim, ncols, bits, cu_count());
+    if (p.path == NNC_CBMM_BIAS) return cbmm_reduce(nullptr, 0, mn, ncols, bias_dev, relu, y, s);   // kdim = 0: y = bias (zeros without one)
+    const int direct = p.splits == 1;
+    float *out = direct ? y : reinterpret_cast<float *>(workspace);
+    const unsigned char *pk = reinterpret_cast<const unsigned char *>(packed);
+    const long long row_bytes = pk_row_bytes(ncols, bits);
+    if (p.path == NNC_CBMM_STREAM) {
+        const PkStreamLaunch fn = find_pk_stream(bits, p.vb, p.mt);
+        if (!fn) return no_pk_stream_case(bits, p.vb, p.mt);
+        fn(dim3((unsigned)p.col_tiles, (unsigned)p.splits), (size_t)p.lds, s, x, (int)m, kdim, pk, row_bytes, ncols, centers_dev, k, p.rows_per_split,
+           bias_dev, relu, direct, out);
+        LAUNCHCHK("k_cbpk_stream");
+    } else {
+        const dim3 grid((unsigned)(p.col_tiles * p.row_tiles), (unsigned)p.splits);
+        if (bits == 4)
+            hipLaunchKernelGGL(k_cbpk_tiled<4>, grid, dim3(256), (size_t)p.lds, s, x, (long long)m, (long long)kdim, pk, row_bytes, (long long)ncols,
+                               centers_dev, (int)k, p.col_tiles, p.rows_per_split, bias_dev, (int)relu, direct, out);
+        else
+            hipLaunchKernelGGL(k_cbpk_tiled<2>, grid, dim3(256), (size_t)p.lds, s, x, (long long)m, (long long)kdim, pk, row_bytes, (long long)ncols,
+                               centers_dev, (int)k, p.col_tiles, p.rows_per_split, bias_dev, (int)relu, direct, out);
+        LAUNCHCHK("k_cbpk_tiled");
+    }
+    if (!direct) return cbmm_reduce(reinterpret_cast<const float *>(workspace), p.splits, mn, ncols, bias_dev, relu, y, s);
+    return NNC_OK;
+}

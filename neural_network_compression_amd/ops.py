@@ -689,6 +689,124 @@ def sparse_codebook_linear(x: torch.Tensor, codes: SparseCodes, centers: torch.T
     return _SparseCodebookLinear.apply(x, codes, centers, bias, bool(relu))
 
 
+class PackedCodes:
+    """The 2- or 4-bit packed form of one (kdim, ncols) index matrix of a codebook of ``k`` <= 2^bits centres (include/nnc.h,
+    nnc_cbpk_*): ``packed``, one 256-byte aligned uint8 device buffer of kdim rows of nnc_cbpk_row_bytes(ncols, bits) bytes, and
+    the metadata a product needs."""
+
+    def __init__(self, packed: torch.Tensor, kdim: int, ncols: int, bits: int, k: int):
+        self.packed, self.kdim, self.ncols, self.bits, self.k = packed, int(kdim), int(ncols), int(bits), int(k)
+
+    @property
+    def device(self):
+        return self.packed.device
+
+    @property
+    def nbytes(self) -> int:
+        """Resident bytes of the form (the buffer)."""
+        return self.packed.numel()
+
+    def to_dense(self) -> torch.Tensor:
+        """The kdim * ncols labels again (uint8), by nnc_cbpk_unpack."""
+        L = nat.load()
+        out = torch.empty(self.kdim * self.ncols, dtype=torch.uint8, device=self.packed.device)
+        nat.check(L.nnc_cbpk_unpack(_ptr(self.packed), self.nbytes, self.bits, self.kdim, self.ncols, _ptr(out), 1, _stream(self.packed)))
+        return out
+
+    def __repr__(self):
+        return f"PackedCodes(kdim={self.kdim}, ncols={self.ncols}, bits={self.bits}, k={self.k}, nbytes={self.nbytes})"
+
+
+def packed_bits(k: int, bits: int | None = None) -> int:
+    """The width the packed form takes for a codebook of ``k`` centres: the smaller of 2 and 4 that holds k, or ``bits`` once
+    checked.  ValueError for k > 16, a width other than 2 or 4, or k > 2^bits."""
+    k = int(k)
+    if k < 1:
+        raise ValueError(f"k = {k} is not a codebook size")
+    if k > 16:
+        raise ValueError(f"k = {k} centres do not fit 4-bit indices (the packed form holds at most 16; use the byte form)")
+    if bits is None:
+        return 2 if k <= 4 else 4
+    bits = int(bits)
+    if bits not in (2, 4):
+        raise ValueError(f"bits must be 2 or 4, got {bits}")
+    if k > 1 << bits:
+        raise ValueError(f"k = {k} centres do not fit {bits}-bit indices")
+    return bits
+
+
+def packed_nbytes(kdim: int, ncols: int, bits: int) -> int:
+    """Host: the bytes of the packed form of a (kdim, ncols) index matrix (nnc_cbpk_pack_bytes)."""
+    return int(nat.load().nnc_cbpk_pack_bytes(int(kdim), int(ncols), int(bits)))
+
+
+def pack_codes(labels: torch.Tensor, kdim: int, ncols: int, k: int, bits: int | None = None) -> PackedCodes:
+    """The (kdim, ncols) labels (uint8 / 16-bit, any storage offset) of a codebook of ``k`` <= 16 centres -> PackedCodes on their
+    device (nnc_cbpk_pack: one pass, no per-weight temporary).  ``bits``: 2 or 4, by default the smaller that holds k.
+    ValueError (before any launch) for k > 16 or k > 2^bits, and for a label >= 2^bits (one host read of the pack's count)."""
+    kdim, ncols, k = int(kdim), int(ncols), int(k)
+    bits = packed_bits(k, bits)
+    _require_cuda(labels, "labels")
+    lb = _label_bytes(labels)
+    if labels.numel() != kdim * ncols:
+        raise ValueError(f"labels must hold kdim * ncols = {kdim * ncols} indices, got {labels.numel()}")
+    labels = labels.reshape(-1)
+    L = nat.load()
+    total = int(L.nnc_cbpk_pack_bytes(kdim, ncols, bits))
+    if total == 0 and kdim * ncols > 0:
+        raise ValueError(f"no packed form for a {kdim} x {ncols} matrix")
+    buf = _aligned_bytes(total, labels.device)
+    bad = torch.empty(1, dtype=torch.int32, device=labels.device)
+    nat.check(L.nnc_cbpk_pack(_ptr(labels), lb, kdim, ncols, bits, _ptr(buf), total, _ptr(bad), _stream(labels)))
+    nbad = int(bad.item())
+    if nbad:
+        raise ValueError(f"{nbad} labels are >= 2^{bits}: they do not fit the packed form")
+    return PackedCodes(buf, kdim, ncols, bits, k)
+
+
+def packed_codebook_matmul(x: torch.Tensor, codes: PackedCodes, centers: torch.Tensor, bias: torch.Tensor | None = None,
+                           relu: bool = False) -> torch.Tensor:
+    """y = x @ W + bias (then ReLU) with W[i, o] = centers[label (i, o)] read from the 2- or 4-bit packed indices (include/nnc.h,
+    nnc_cbpk_f32): codebook_matmul on the unpacked labels, from a half or a quarter of the index bytes.  x: float32 (..., kdim);
+    centers: float32[codes.k]; bias: float32[ncols] or None.  Returns float32 (..., ncols).  Inference only, as codebook_matmul."""
+    _require_cuda(x, "x", torch.float32)
+    _require_cuda(centers, "centers", torch.float32)
+    if bias is not None:
+        _require_cuda(bias, "bias", torch.float32)
+    if not isinstance(codes, PackedCodes):
+        raise TypeError("codes must be a PackedCodes (ops.pack_codes)")
+    if torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (x, centers, bias)):
+        raise RuntimeError("packed_codebook_matmul is inference only: it computes no gradient (run it under torch.no_grad())")
+    devs = {t.device for t in (x, codes.packed, centers, bias) if t is not None}
+    if len(devs) != 1:
+        raise ValueError("x, codes, centers and bias must be on one device")
+    kdim, ncols = codes.kdim, codes.ncols
+    if x.dim() < 1 or x.shape[-1] != kdim:
+        raise ValueError(f"x must have shape (..., {kdim}), got {tuple(x.shape)}")
+    if centers.numel() != codes.k:
+        raise ValueError(f"centers must hold k = {codes.k} values, got {centers.numel()}")
+    if bias is not None and bias.numel() != ncols:
+        raise ValueError(f"bias must hold ncols = {ncols} values, got {bias.numel()}")
+    L = nat.load()
+    lead = tuple(x.shape[:-1])
+    m = int(np.prod(lead)) if lead else 1
+    y = torch.empty(lead + (ncols,), dtype=torch.float32, device=x.device)
+    ws_bytes = int(L.nnc_cbpk_workspace_bytes(m, kdim, ncols, codes.bits))
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=x.device) if ws_bytes else None
+    nat.check(L.nnc_cbpk_f32(_ptr(x), m, kdim, _ptr(codes.packed), codes.nbytes, codes.bits, ncols, _ptr(centers), centers.numel(), _ptr(bias),
+                             1 if relu else 0, _ptr(y), _ptr(ws), ws_bytes, _stream(x)))
+    return y
+
+
+def cbpk_plan(m: int, kdim: int, ncols: int, bits: int, k: int, cus: int) -> dict:
+    """Host: the plan nnc_cbpk_f32 follows on a device with ``cus`` compute units (include/nnc.h, nnc_cbpk_plan), as a dict keyed
+    by _native.CBPK_PLAN_FIELDS.  No device needed."""
+    L = nat.load()
+    out = (ctypes.c_int64 * nat.CBPK_PLAN_LEN)()
+    nat.check(L.nnc_cbpk_plan(int(m), int(kdim), int(ncols), int(bits), int(k), int(cus), out))
+    return dict(zip(nat.CBPK_PLAN_FIELDS, (int(v) for v in out)))
+
+
 def huffman_lengths(counts) -> tuple:
     """Host: (lengths uint8[k], hist int64[max_len+1], total_bits) from an index histogram."""
     L = nat.load()
