@@ -835,6 +835,73 @@ int nnc_cbsp_dc_f32(const float *x, const float *g, int64_t m, int64_t kdim, con
                     int32_t zero_symbol, int64_t nnz, int32_t k, void *dc, int32_t out_f64, void *workspace, int64_t workspace_bytes, void *stream);
 
 /* ------------------------------------------------------------------------------------
+ * The backward pass of nnc_cbpk_f32 from the same 2- or 4-bit packed form, the indices never unpacked and W never decoded
+ * (csrc/nnc_cbpkgrad.hip).  The form, bits and k are nnc_cbpk_f32's; g = dL/dy float32[m, ncols].
+ * nnc_cbpk_dx_f32   dx[m, kdim] = sum_o g[r, o] * centers_dev[label (i, o)] with the conventions of nnc_cbmm_dx_f32: an index >= k
+ *                   reads 0 and a column past ncols forms no product (the padding fields hold label 0 and never meet g,
+ *                   whatever centers_dev[0] is).  m <= 16 streams the packed rows (k_cbpkdx_stream: 64 lanes x COLS columns of g
+ *                   in registers per workgroup, aligned loads of VB bytes, the 2^bits-entry per-bank table, a wave reduction in
+ *                   a fixed order per index row, one split per column block), larger m decodes W^T tiles into LDS from packed
+ *                   dwords (k_cbpkdx_tiled, ncols split into multiples of 16 columns by a count that depends on the shape
+ *                   alone); the split partials are summed in split order (k_cbgrad_reduce).
+ * nnc_cbpk_dc_f32   dc[k] as nnc_cbmm_dc_f32 on the unpacked uint8 labels, bit for bit: every dW[i, o] is formed in float32 as
+ *                   that call forms it (from the same scaled x and g, r ascending) and binned as rint(dW * 2^S) with the same S
+ *                   (SPLITS and TERMS_LOG2 are nnc_cbmm_dc_plan's for the shape at label_bytes = 1); an index >= k falls into
+ *                   no bin and a padding field is never binned.  Every lane adds into its own copy of the LDS bins (COPIES =
+ *                   64).  The all-NaN rule, dc = 0 for a zero maximum, float64 / float32 output: as nnc_cbmm_dc_f32.
+ * No host read and no float atomics in either; the same call gives the same bits.  m = 0 or kdim = 0: dx is empty (a no-op);
+ * ncols = 0: dx = 0.  No terms (m, kdim or ncols = 0): dc = 0.  Limits as nnc_cbpk_f32, and m * kdim <= 2^44.
+ * *_workspace_bytes: what the call needs for that shape (0 for none; host arithmetic only): dx the split partials, 4-byte
+ * aligned; dc 64 bytes of header and k int64 sums, 8-byte aligned.  Argument errors (NNC_EINVAL as nnc_cbpk_f32: bits, k,
+ * packed_bytes, the 16-byte alignment of packed, NULL pointers; NNC_ENOSPACE for a short workspace) are returned before any
+ * HIP call.
+ * *_plan: host arithmetic only, the plan the call follows on a device with `cus` compute units.  The splits depend on the shape
+ * alone (planned for 256 CUs); `cus` changes only the number of row groups.  NNC_EINVAL as the call, for cus < 1, out NULL, or a
+ * plan with no kernel instantiation.
+ *   dx (NNC_CBPKDX_P_*): PATH (NNC_CBMM_NONE: nothing written, _STREAM, _TILED, _ZERO: dx = 0), VB and MT (stream: packed bytes
+ *       per lane per row, rows of g per launch), COLS (stream: columns per lane, 8 * VB / bits; COLS * MT <= 64 values of g per
+ *       lane), COPIES and ENTRIES of the LDS table, SPLITS of ncols and CPS columns per split, LDS, COL_TILES x ROW_TILES
+ *       (stream: column blocks x row groups; tiled: kdim tiles x m tiles), WORKSPACE.
+ *   dc (NNC_CBPKDC_P_*): PATH (_STREAM, _TILED, _ZERO: dc = 0), VB, MT, COLS, COPIES of every LDS bin, SPLITS of m and RPS rows
+ *       of m per split, LDS, COL_TILES x ROW_TILES (stream: column blocks x row groups; tiled: ncols tiles x kdim tiles),
+ *       TERMS_LOG2, WORKSPACE.
+ * ---------------------------------------------------------------------------------- */
+#define NNC_CBPKDX_P_PATH 0
+#define NNC_CBPKDX_P_VB 1
+#define NNC_CBPKDX_P_MT 2
+#define NNC_CBPKDX_P_COLS 3
+#define NNC_CBPKDX_P_COPIES 4
+#define NNC_CBPKDX_P_ENTRIES 5
+#define NNC_CBPKDX_P_SPLITS 6
+#define NNC_CBPKDX_P_CPS 7
+#define NNC_CBPKDX_P_LDS 8
+#define NNC_CBPKDX_P_COL_TILES 9
+#define NNC_CBPKDX_P_ROW_TILES 10
+#define NNC_CBPKDX_P_WORKSPACE 11
+#define NNC_CBPKDX_PLAN_LEN 12
+#define NNC_CBPKDC_P_PATH 0
+#define NNC_CBPKDC_P_VB 1
+#define NNC_CBPKDC_P_MT 2
+#define NNC_CBPKDC_P_COLS 3
+#define NNC_CBPKDC_P_COPIES 4
+#define NNC_CBPKDC_P_SPLITS 5
+#define NNC_CBPKDC_P_RPS 6
+#define NNC_CBPKDC_P_LDS 7
+#define NNC_CBPKDC_P_COL_TILES 8
+#define NNC_CBPKDC_P_ROW_TILES 9
+#define NNC_CBPKDC_P_TERMS_LOG2 10
+#define NNC_CBPKDC_P_WORKSPACE 11
+#define NNC_CBPKDC_PLAN_LEN 12
+int64_t nnc_cbpk_dx_workspace_bytes(int64_t m, int64_t kdim, int64_t ncols, int bits);
+int nnc_cbpk_dx_plan(int64_t m, int64_t kdim, int64_t ncols, int bits, int32_t k, int32_t cus, int64_t *out);
+int nnc_cbpk_dx_f32(const float *g, int64_t m, int64_t kdim, const void *packed, int64_t packed_bytes, int bits, int64_t ncols,
+                    const float *centers_dev, int32_t k, float *dx, void *workspace, int64_t workspace_bytes, void *stream);
+int64_t nnc_cbpk_dc_workspace_bytes(int64_t m, int64_t kdim, int64_t ncols, int bits, int32_t k);
+int nnc_cbpk_dc_plan(int64_t m, int64_t kdim, int64_t ncols, int bits, int32_t k, int32_t cus, int64_t *out);
+int nnc_cbpk_dc_f32(const float *x, const float *g, int64_t m, int64_t kdim, const void *packed, int64_t packed_bytes, int bits,
+                    int64_t ncols, int32_t k, void *dc, int32_t out_f64, void *workspace, int64_t workspace_bytes, void *stream);
+
+/* ------------------------------------------------------------------------------------
  * Multi-GPU: the vector is sharded across one process per GPU (contiguous shards starting on multiples of
  * NNC_CHUNK elements); the exchange per Lloyd iteration is one all-reduce (SUM) of the 2K int64 sums / counts over
  * RCCL / xGMI, enqueued by the library on the caller's stream between its own kernels.  The reference has no

@@ -39,6 +39,10 @@ CBSP_PLAN_FIELDS = ("path", "mt", "copies", "entries", "splits", "rps", "rowsum"
 CBPK_TABLE_NONE, CBPK_TABLE_BANKED = 0, 1   # nnc_cbpk_plan: the layout of the lookup table (include/nnc.h)
 CBPK_PLAN_LEN = 14
 CBPK_PLAN_FIELDS = ("path", "vb", "mt", "cols", "xrows", "table", "copies", "entries", "splits", "rps", "lds", "col_tiles", "row_tiles", "workspace")
+CBPKDX_PLAN_LEN = 12   # nnc_cbpk_dx_plan / nnc_cbpk_dc_plan (include/nnc.h)
+CBPKDX_PLAN_FIELDS = ("path", "vb", "mt", "cols", "copies", "entries", "splits", "cps", "lds", "col_tiles", "row_tiles", "workspace")
+CBPKDC_PLAN_LEN = 12
+CBPKDC_PLAN_FIELDS = ("path", "vb", "mt", "cols", "copies", "splits", "rps", "lds", "col_tiles", "row_tiles", "terms_log2", "workspace")
 CBSPDX_PLAN_LEN = 11   # nnc_cbsp_dx_plan / nnc_cbsp_dc_plan (include/nnc.h)
 CBSPDX_PLAN_FIELDS = ("path", "mt", "segs", "copies", "entries", "splits", "cps", "lds", "col_tiles", "row_tiles", "workspace")
 CBSPDC_PLAN_LEN = 11
@@ -198,6 +202,12 @@ SIGNATURES = {
     "nnc_cbpk_plan": (c_int, [c_i64, c_i64, c_i64, c_int, c_i32, c_i32, ctypes.POINTER(c_i64)]),
     "nnc_cbpk_f32": (c_int, [c_void_p, c_i64, c_i64, c_void_p, c_i64, c_int, c_i64, c_void_p, c_i32, c_void_p, c_i32, c_void_p, c_void_p, c_i64,
                              c_void_p]),
+    "nnc_cbpk_dx_workspace_bytes": (c_i64, [c_i64, c_i64, c_i64, c_int]),
+    "nnc_cbpk_dx_plan": (c_int, [c_i64, c_i64, c_i64, c_int, c_i32, c_i32, ctypes.POINTER(c_i64)]),
+    "nnc_cbpk_dx_f32": (c_int, [c_void_p, c_i64, c_i64, c_void_p, c_i64, c_int, c_i64, c_void_p, c_i32, c_void_p, c_void_p, c_i64, c_void_p]),
+    "nnc_cbpk_dc_workspace_bytes": (c_i64, [c_i64, c_i64, c_i64, c_int, c_i32]),
+    "nnc_cbpk_dc_plan": (c_int, [c_i64, c_i64, c_i64, c_int, c_i32, c_i32, ctypes.POINTER(c_i64)]),
+    "nnc_cbpk_dc_f32": (c_int, [c_void_p, c_void_p, c_i64, c_i64, c_void_p, c_i64, c_int, c_i64, c_i32, c_void_p, c_i32, c_void_p, c_i64, c_void_p]),
     "nnc_huffman_codes": (c_int, [ctypes.POINTER(ctypes.c_uint8), c_i32, ctypes.POINTER(ctypes.c_uint32)]),
     "nnc_codec_chunks": (c_size, [c_i64]),
     "nnc_huffman_chunk_offsets": (c_int, [c_void_p, c_int, c_i64, c_void_p, c_i32, c_void_p, c_void_p]),

@@ -170,12 +170,14 @@ class Trainer(ABC):
         return accuracies
 
     def fine_tune_compressed(self, train_dataset: LeNetDataset, test_dataset: LeNetDataset, epochs: int,
-                             learning_rate: float = 1e-3, sparse=False) -> List[float]:
-        """fine_tune_centroids' algorithm run on ``compressed.compress_network_trainable(..., sparse=sparse)`` (sparse=False: the
-        network of ``compressed_network(trainable=True)``; True or "auto": the bitmap-sparse trainable layers, for every
-        quantized layer or where that form is smaller): the indices stay fixed and per batch every quantized tensor's centres
-        take the plain step c -= learning_rate * dc, dc formed from the codebook and the indices (dense or packed) by the
-        backward of ops.codebook_linear / ops.sparse_codebook_linear (DESIGN.md sections 12, 13; neither W nor dW is built).
+                             learning_rate: float = 1e-3, sparse=False, packed=False) -> List[float]:
+        """fine_tune_centroids' algorithm run on ``compressed.compress_network_trainable(..., sparse=sparse, packed=packed)``
+        (both False: the network of ``compressed_network(trainable=True)``; sparse True or "auto": the bitmap-sparse trainable
+        layers, for every quantized layer or where that form is smaller; packed True or "auto": the 2- or 4-bit packed trainable
+        layers for the layers of at most 16 centres, or where that form is the smallest): the indices stay fixed and per batch
+        every quantized tensor's centres take the plain step c -= learning_rate * dc, dc formed from the codebook and the indices
+        (byte, bitmap-sparse or packed) by the backward of ops.codebook_linear / ops.sparse_codebook_linear /
+        ops.packed_codebook_linear (DESIGN.md sections 12, 13, 15; neither W nor dW is built).
         Tensors that passed through unquantized stay frozen.  At the end the tuned centres go into ``quantized_models_by_layer``
         and the float layers are re-decoded from them (ops.gather), as after fine_tune_centroids.  Returns the accuracy per epoch
         (of the trainable network)."""
@@ -184,7 +186,7 @@ class Trainer(ABC):
             raise RuntimeError("fine_tune_compressed needs a quantized network: call quantize first")
         from .. import compressed
 
-        net = compressed.compress_network_trainable(self.neural_network, models, sparse=sparse)
+        net = compressed.compress_network_trainable(self.neural_network, models, sparse=sparse, packed=packed)
         for p in net.parameters():
             p.requires_grad_(False)
         tuned = {}   # layer name -> trainable layer
@@ -231,7 +233,8 @@ class Trainer(ABC):
         ``sparse``: False, True (the indices in the bitmap-sparse form) or "auto" (per layer, the smaller form).
         ``packed``: False, True (2- or 4-bit packed indices for every layer of at most 16 centres) or "auto" (per layer, the smallest
         form).
-        ``trainable=True`` (with sparse=False and packed=False only): the layers' centres are parameters with a backward pass."""
+        ``trainable=True`` (with sparse=False and packed=False only): the layers' centres are parameters with a backward pass (DESIGN.md
+        section 12); fine_tune_compressed(..., sparse=..., packed=...) trains the other two forms."""
         models = getattr(self, "quantized_models_by_layer", None)
         if not models:
             raise RuntimeError("compressed_network needs a quantized network: call quantize first")

@@ -22,7 +22,7 @@ A layer of at most 16 centres can keep its indices at 2 or 4 bits each (ops.pack
 it is the number of centres that decides, not the ``bits`` of the fit), ``packed="auto"`` where it is the smallest.  Per layer
 the candidates are the byte form (unless ``sparse is True``, or ``packed is True`` and K <= 16), the bitmap-sparse form (if
 ``sparse`` is not False) and the packed form (if ``packed`` is not False and K <= 16); the one with the fewest resident bytes is
-kept, on equal bytes the earlier in this list.  The selection is by bytes, not by speed.  Inference only: no trainable variant yet.
+kept, on equal bytes the earlier in this list.  The selection is by bytes, not by speed.
 
 These layers are inference only: under autograd, with an input that needs a gradient, they raise instead of returning a result
 that silently has none.  ``trainable=True`` in compress_network / Trainer.compressed_network gives the trainable variants instead
@@ -31,13 +31,19 @@ forward goes through ops.codebook_linear, whose backward forms dx and the centro
 (csrc/nnc_cbgrad.hip) -- W and dW are never built.  A quantized bias keeps its indices and a ``bias_centers`` parameter; a raw bias
 stays frozen.  ``kernel_sq_sum()`` gives the trainers' L2 term without W.  Trainer.fine_tune_compressed trains them.
 
-    compress_network_trainable(network, models_by_layer, sparse=False)   the trainable layers, dense, bitmap-sparse or per layer
+    compress_network_trainable(network, models_by_layer, sparse=False, packed=False)   the trainable layers, byte, bitmap-sparse, packed or per layer
 
 The bitmap-sparse layers train too (``TrainableSparseCompressedDense`` / ``TrainableSparseCompressedConv2D``, DESIGN.md section
 13): ops.sparse_codebook_linear's backward forms dx and the centroid gradient from the packed form (csrc/nnc_cbspgrad.hip), and
 the centroid gradient is the dense trainable layer's bit for bit -- the same function, stored differently.
 compress_network_trainable(..., sparse=True | "auto") and Trainer.fine_tune_compressed(..., sparse=...) give them;
 compress_network(..., trainable=True) stays the dense form.
+
+So do the packed layers (``TrainablePackedCompressedDense`` / ``TrainablePackedCompressedConv2D``):
+ops.packed_codebook_linear's backward forms dx and the centroid gradient from the 2- or 4-bit packed rows (csrc/nnc_cbpkgrad.hip),
+the centroid gradient again the byte layer's bit for bit, and no byte-per-weight tensor stays resident while training.
+compress_network_trainable(..., packed=True | "auto") and Trainer.fine_tune_compressed(..., packed=...) give them, chosen per
+layer by the rule above applied to the trainable forms.
 """
 from __future__ import annotations
 
@@ -549,6 +555,92 @@ class PackedCompressedConv2D(_PackedCodebookLayer):
         return _conv_forward(self, x)
 
 
+class _TrainablePackedCodebookLayer(_TrainableCentres):
+    """The indices in the 2- or 4-bit packed form (the ``packed`` buffer, as _PackedCodebookLayer) with the centres, counts and bias
+    of _TrainableCentres; the forward goes through ops.packed_codebook_linear, whose backward forms dx and the centroid gradient
+    from the packed rows (csrc/nnc_cbpkgrad.hip).  ``counts`` is taken from the labels before packing, so kernel_sq_sum() is the
+    byte trainable layer's bit for bit.  No kdim * ncols tensor stays resident."""
+
+    def __init__(self, codes: ops.PackedCodes, labels: torch.Tensor, centers: torch.Tensor, bias: torch.Tensor | None = None,
+                 bias_codes=None, activation=None):
+        super().__init__()
+        if centers.numel() != codes.k:
+            raise ValueError(f"{centers.numel()} centres for indices into a codebook of {codes.k}")
+        if labels.numel() != codes.kdim * codes.ncols:
+            raise ValueError(f"{labels.numel()} indices for a {codes.kdim} x {codes.ncols} weight matrix")
+        self.kdim, self.ncols, self.bits, self.k = codes.kdim, codes.ncols, codes.bits, codes.k
+        self.register_buffer("packed", codes.packed)
+        self._init_centres(labels.reshape(-1), centers, codes.ncols, bias, bias_codes, activation)
+
+    codes = _PackedCodebookLayer.codes
+
+    def _matmul(self, x: torch.Tensor) -> torch.Tensor:
+        return self._activate(ops.packed_codebook_linear(x, self.codes, self.centers, bias=self.current_bias(), relu=self._fused_relu))
+
+    def nbytes(self) -> int:
+        return self._nbytes(self.packed)
+
+
+class TrainablePackedCompressedDense(_TrainablePackedCodebookLayer):
+    """PackedCompressedDense with trainable centres (ops.packed_codebook_linear)."""
+
+    @classmethod
+    def from_dense(cls, dense, weight_model, bias_model=None, bits=None) -> "TrainablePackedCompressedDense":
+        centers, labels, bias, bias_codes = _trainable_codes(dense, weight_model, bias_model)
+        kin, kout = dense.kernel.shape
+        return cls.from_codes(kin, kout, labels, centers, bias, bias_codes, dense.activation, bits)
+
+    @classmethod
+    def from_codes(cls, kdim, ncols, labels, centers, bias=None, bias_codes=None, activation=None, bits=None) -> "TrainablePackedCompressedDense":
+        return cls(ops.pack_codes(labels, kdim, ncols, centers.numel(), bits), labels, centers, bias, bias_codes, activation)
+
+    def forward(self, x: torch.Tensor) -> torch.Tensor:
+        return self._matmul(x.contiguous())
+
+
+class TrainablePackedCompressedConv2D(_TrainablePackedCodebookLayer):
+    """PackedCompressedConv2D with trainable centres: the patches (chunked as CompressedConv2D) through
+    ops.packed_codebook_linear; autograd carries the patch gradients back through the unfold."""
+
+    def __init__(self, kernel_size: int, cin: int, pad: int, codes: ops.PackedCodes, labels: torch.Tensor, centers: torch.Tensor, bias=None,
+                 bias_codes=None, activation=None):
+        if codes.kdim != kernel_size * kernel_size * cin:
+            raise ValueError(f"{codes.kdim} index rows for a {kernel_size} x {kernel_size} x {cin} kernel")
+        super().__init__(codes, labels, centers, bias, bias_codes, activation)
+        self.kernel_size, self.cin, self.pad = int(kernel_size), int(cin), int(pad)
+
+    @classmethod
+    def from_conv(cls, conv, weight_model, bias_model=None, bits=None) -> "TrainablePackedCompressedConv2D":
+        h, w, cin, cout = conv.kernel.shape
+        if h != w:
+            raise ValueError("square kernels only (as layers.Conv2D)")
+        centers, labels, bias, bias_codes = _trainable_codes(conv, weight_model, bias_model)
+        return cls.from_codes(h, cin, cout, conv.pad, labels, centers, bias, bias_codes, conv.activation, bits)
+
+    @classmethod
+    def from_codes(cls, kernel_size, cin, cout, pad, labels, centers, bias=None, bias_codes=None, activation=None,
+                   bits=None) -> "TrainablePackedCompressedConv2D":
+        """labels in the Keras order of the (h, w, in, out) kernel (the counts are the same in either order)."""
+        ops.packed_bits(centers.numel(), bits)   # a codebook that does not fit raises before the unfold
+        unf = _unfold_labels(kernel_size, cin, cout, labels)
+        codes = ops.pack_codes(unf, kernel_size * kernel_size * cin, cout, centers.numel(), bits)
+        del unf
+        return cls(kernel_size, cin, pad, codes, labels, centers, bias, bias_codes, activation)
+
+    def forward(self, x: torch.Tensor) -> torch.Tensor:   # x: (N, H, W, C)
+        return _conv_forward(self, x)
+
+
+def _trainable_packed(layer, weight_model, bias_model):
+    from .neural_networks.layers import Conv2D, Dense
+
+    if isinstance(layer, Dense):
+        return TrainablePackedCompressedDense.from_dense(layer, weight_model, bias_model)
+    if isinstance(layer, Conv2D):
+        return TrainablePackedCompressedConv2D.from_conv(layer, weight_model, bias_model)
+    raise TypeError(f"no compressed form of {type(layer).__name__}")
+
+
 PACKED_MAX_K = 16   # the packed form holds at most 4-bit indices
 
 
@@ -558,8 +650,8 @@ def _check_packed(packed, sparse=False, trainable=False):
     if packed is True and sparse is True:
         raise ValueError("sparse=True and packed=True both ask for every layer: take one, or 'auto' for either")
     if trainable and packed is not False:
-        raise ValueError("trainable=True needs packed=False: the packed layers are inference only (there is no backward pass from "
-                         "2- and 4-bit packed indices yet)")
+        raise ValueError("trainable=True needs packed=False here: the packed layers of compress_network are inference only; use "
+                         "compress_network_trainable(..., packed=...) for trainable 2- and 4-bit packed layers")
 
 
 def _check_sparse(sparse):
@@ -639,7 +731,7 @@ def compress_network(network: nn.Module, models_by_layer, sparse=False, trainabl
     ``packed``: False, True (2- or 4-bit packed indices for every layer of at most 16 centres, the others in the byte form) or
     "auto"; with ``sparse`` it decides per layer by resident bytes as the module's docstring tells.
     ``trainable=True`` (dense indices only): TrainableCompressedDense / TrainableCompressedConv2D, centres as parameters;
-    compress_network_trainable gives the bitmap-sparse trainable layers too."""
+    compress_network_trainable gives the bitmap-sparse and the packed trainable layers too."""
     _check_sparse(sparse)
     _check_packed(packed, sparse, trainable)
     if trainable and sparse is not False:
@@ -650,15 +742,23 @@ def compress_network(network: nn.Module, models_by_layer, sparse=False, trainabl
     return _compress_each(network, models_by_layer, lambda layer, wm, bm: _replace(layer, wm, bm, sparse, packed))
 
 
-def compress_network_trainable(network: nn.Module, models_by_layer, sparse=False) -> nn.Module:
+def compress_network_trainable(network: nn.Module, models_by_layer, sparse=False, packed=False) -> nn.Module:
     """compress_network with the centres (and quantized biases' centres) as nn.Parameters.  ``sparse``: False
     (TrainableCompressedDense / TrainableCompressedConv2D, the layers of compress_network(..., trainable=True)), True
     (TrainableSparseCompressedDense / TrainableSparseCompressedConv2D: the indices in the bitmap-sparse form, skipping the most
-    frequent one) or "auto" (per layer, the form with fewer resident bytes).  Both train the same function: the sparse layer's
-    centroid gradient is the dense one's bit for bit."""
+    frequent one) or "auto" (per layer, the form with fewer resident bytes).  ``packed``: False, True
+    (TrainablePackedCompressedDense / TrainablePackedCompressedConv2D for every layer of at most 16 centres, the others in the
+    byte form) or "auto"; with ``sparse`` it decides per layer by resident bytes as the module's docstring tells.  All train the
+    same function: the sparse and the packed layer's centroid gradient is the byte one's bit for bit (DESIGN.md sections 13, 15)."""
     _check_sparse(sparse)
+    _check_packed(packed, sparse)
+    if packed is False:
+        return _compress_each(network, models_by_layer,
+                              lambda layer, wm, bm: _pick(lambda: _trainable(layer, wm, bm), lambda: _trainable_sparse(layer, wm, bm), sparse))
     return _compress_each(network, models_by_layer,
-                          lambda layer, wm, bm: _pick(lambda: _trainable(layer, wm, bm), lambda: _trainable_sparse(layer, wm, bm), sparse))
+                          lambda layer, wm, bm: _pick3(wm.cluster_centers_.size, lambda: _trainable(layer, wm, bm),
+                                                       lambda: _trainable_sparse(layer, wm, bm), lambda: _trainable_packed(layer, wm, bm),
+                                                       sparse, packed))
 
 
 def _compress_each(network: nn.Module, models_by_layer, make) -> nn.Module:

@@ -1,5 +1,5 @@
-// nnc_cbgrad.hpp -- what the backward pass of the codebook matmul (nnc_cbgrad.hip) shares with that of its bitmap-sparse sibling
-// (nnc_cbspgrad.hip): the fixed-order wave reduction of the dx stream kernels, the scaling and fixed-point binning of dc (DESIGN.md
+// nnc_cbgrad.hpp -- what the backward pass of the codebook matmul (nnc_cbgrad.hip) shares with those of its bitmap-sparse and
+// packed siblings (nnc_cbspgrad.hip, nnc_cbpkgrad.hip): the fixed-order wave reduction of the dx stream kernels, the scaling and fixed-point binning of dc (DESIGN.md
 // section 12) and the launches of the kernels both use (defined in nnc_cbgrad.hip).
 #pragma once
 #include "nnc_cbmm.hpp"

@@ -18,17 +18,9 @@
 //                  that holds them into the LDS W tile, then tb_tile_fma.
 //   the split-K partials are summed by k_cbmm_reduce (cbmm_reduce) in split order.  No float atomics anywhere.
 // An index >= K reads 0 (the table's zero entries).  Columns past ncols are computed from the padding and never stored.
-#include "nnc_cbmm.hpp"
+#include "nnc_cbpk.hpp"
 
-#define PK_COPIES 32              // per-bank copies of the table
-#define PK_CSHIFT 5
-#define PK_ACC 64                 // accumulators per lane: columns per lane per row x rows of x
-
-// ------------------------------------------------------------------ the layout (host)
-static inline bool pk_bits_ok(int bits) { return bits == 2 || bits == 4; }
-static inline long long pk_row_bytes(long long ncols, int bits) { return 16 * cdiv(ncols * bits, 128); }
-static inline bool pk_size_ok(int64_t kdim, int64_t ncols) { return kdim <= (1LL << 40) && ncols <= (1LL << 40) && (ncols == 0 || kdim <= (1LL << 44) / cdiv(ncols, 2)); }
-
+// ------------------------------------------------------------------ the layout (host; the arithmetic is nnc_cbpk.hpp's)
 extern "C" int64_t nnc_cbpk_row_bytes(int64_t ncols, int bits)
 {
     if (ncols < 0 || ncols > (1LL << 40) || !pk_bits_ok(bits)) return 0;
@@ -95,22 +87,6 @@ __global__ __launch_bounds__(256) void k_cbpk_unpack(const uint32_t *__restrict_
             }
         }
     }
-}
-
-static int pk_check_form(const char *fn, int64_t kdim, int64_t ncols, int bits)
-{
-    if (kdim < 0 || ncols < 0) return fail(NNC_EINVAL, std::string(fn) + ": negative size");
-    if (!pk_bits_ok(bits)) return fail(NNC_EINVAL, std::string(fn) + ": bits must be 2 or 4");
-    if (!pk_size_ok(kdim, ncols)) return fail(NNC_EINVAL, std::string(fn) + ": size too large");
-    return NNC_OK;
-}
-
-static int pk_check_buffer(const char *fn, const void *packed, int64_t packed_bytes, int64_t kdim, int64_t ncols, int bits)
-{
-    if (packed_bytes != kdim * pk_row_bytes(ncols, bits)) return fail(NNC_EINVAL, std::string(fn) + ": packed_bytes is not nnc_cbpk_pack_bytes(kdim, ncols, bits)");
-    if (packed_bytes > 0 && !packed) return fail(NNC_EINVAL, std::string(fn) + ": packed is NULL");
-    if (reinterpret_cast<uintptr_t>(packed) % 16) return fail(NNC_EINVAL, std::string(fn) + ": packed must be 16-byte aligned");
-    return NNC_OK;
 }
 
 static int pk_check_labels(const char *fn, const void *labels, int label_bytes, int64_t kdim, int64_t ncols)
@@ -230,14 +206,6 @@ static PkPlan pk_plan(long long m, long long kdim, long long ncols, int bits, in
 static int64_t pk_ws_bytes(const PkPlan &p, long long m, long long ncols) { return p.splits > 1 ? (int64_t)p.splits * m * ncols * 4 : 0; }
 
 // ------------------------------------------------------------------ skinny: m <= 16
-template <int VB>
-__device__ __forceinline__ void pk_load(const unsigned char *p, uint32_t *w)
-{
-    if constexpr (VB == 1) w[0] = *p;
-    else if constexpr (VB == 2) w[0] = *reinterpret_cast<const uint16_t *>(p);
-    else load_chunk<VB>(p, w);
-}
-
 // grid (col_tiles, splits), CB_THREADS threads.  `out` is y (splits == 1: + bias, ReLU here) or the partials [split][m][ncols].
 template <int BITS, int VB, int MT>
 __global__ __launch_bounds__(CB_THREADS, 2) void k_cbpk_stream(const float *__restrict__ x, int m, long long kdim, const unsigned char *__restrict__ packed,
@@ -421,16 +389,6 @@ __global__ __launch_bounds__(256) void k_cbpk_tiled(const float *__restrict__ x,
 }
 
 // ------------------------------------------------------------------ C ABI
-static int pk_check(const char *fn, int64_t m, int64_t kdim, int64_t ncols, int bits, int32_t k)
-{
-    if (m < 0) return fail(NNC_EINVAL, std::string(fn) + ": negative size");
-    const int rc = pk_check_form(fn, kdim, ncols, bits);
-    if (rc != NNC_OK) return rc;
-    if (k < 1 || k > (1 << bits)) return fail(NNC_EINVAL, std::string(fn) + ": k outside 1..2^bits");
-    if (m > (1LL << 40)) return fail(NNC_EINVAL, std::string(fn) + ": size too large");
-    return NNC_OK;
-}
-
 extern "C" int64_t nnc_cbpk_workspace_bytes(int64_t m, int64_t kdim, int64_t ncols, int bits)
 {
     if (m <= 0 || kdim <= 0 || ncols <= 0 || pk_check("nnc_cbpk_workspace_bytes", m, kdim, ncols, bits, 1) != NNC_OK) return 0;

@@ -1,0 +1,643 @@
+// nnc_cbpkgrad.hip -- the backward pass of the 2- and 4-bit packed codebook matmul (nnc_cbpk.hip) from the packed indices: they
+// are never unpacked and W is never decoded (include/nnc.h, nnc_cbpk_dx_f32 / nnc_cbpk_dc_f32).  With
+// W[i, o] = c[L[i, o]] (a label >= K reads 0), y = x @ W and g = dL/dy:
+//
+//   dx[r, i] = sum_o g[r, o] * c[L[i, o]]     the conventions of nnc_cbmm_dx_f32: a label >= K reads 0, a column past ncols forms no
+//                                             product (the padding fields hold label 0 and meet a 0, never g)
+//   dc[k]    = nnc_cbmm_dc_f32 on the unpacked labels, bit for bit: every dW[i, o] is formed in float32 as k_cbdc_stream /
+//              k_cbdc_tiled form it (from x and g scaled by the same powers of two, r ascending) and binned as rint(dW * 2^S)
+//              with the same S (the same splits of m and T).  Integer sums do not depend on order.  A label >= K falls into no
+//              bin; a padding field is never binned.
+//
+//   k_cbpkdx_stream  m <= 16.  A workgroup owns 64 lanes x E columns of g (E = 8 * VB / BITS, held in registers) and a group of
+//                    packed rows; a wave takes one row at a time (CB_UNROLL rows in flight, k_cbpk_stream's aligned 1- to 16-byte
+//                    loads), looks its columns up in the 2^BITS-entry per-bank table and reduces its m partials over the 64 lanes
+//                    in a fixed order (pg_reduce_rows).  Column blocks are the splits, summed in block order by k_cbgrad_reduce.
+//   k_cbpkdx_tiled   m > 16.  k_cbdx_tiled with the W^T tile decoded from packed dwords: all 256 threads decode 4 columns each.
+//   k_cbpkdc_stream  m <= 16.  The grid and loads of k_cbpkdx_stream; x[r, i] by vector load + v_readlane; dW'[i, o] as
+//                    k_cbdc_stream forms it; the image goes into the lane's own copy of the K <= 16 LDS bins (64 copies: no two
+//                    lanes of a wave ever meet on an address).
+//   k_cbpkdc_tiled   m > 16.  k_cbdc_tiled's tiles and splits of m; a thread's 8 consecutive columns of a row come from one packed
+//                    dword, loaded once.
+// k_cbgrad_absmax, k_cbdc_finish and k_cbgrad_reduce are nnc_cbgrad.hip's.  No float atomics; no host read.
+#include "nnc_cbgrad.hpp"
+#include "nnc_cbpk.hpp"
+
+#define PKG_RLOG2 6               // dc: 64 copies of every LDS bin, one per lane (K <= 16: at most 8 KiB)
+#define PKG_G 64                  // stream: g values a lane keeps (columns per lane x rows of m), at most
+
+// ------------------------------------------------------------------ plans (host)
+struct PgPlan {
+    int path;                 // NNC_CBMM_NONE / _STREAM / _TILED / _ZERO
+    int vb, mt, cols;         // stream: packed bytes per lane per row, rows of m per launch (a power of two >= m), 8 * vb / bits
+    int entries, copies;      // dx: the LDS table; dc: the copies of every LDS bin
+    long long col_tiles, row_tiles;   // stream: column blocks x row groups; tiled: tiles
+    long long splits, per_split;      // dx: splits of ncols (columns per split); dc: splits of m (rows of m per split)
+    long long rows_per_group;         // stream: packed rows per workgroup
+    int terms_log2;                   // dc: T of nnc_cbmm_dc_plan
+    long long lds;
+};
+
+static int pg_mt(long long m) { return m <= 1 ? 1 : (m <= 2 ? 2 : (m <= 4 ? 4 : (m <= 8 ? 8 : 16))); }
+
+// The stream geometry both directions share.  Columns per lane: at most a 16-byte load and PKG_G values of g; from there down to a
+// 4-byte load, the widest that keeps four lanes in five on a column (the last column block may be nearly empty) and leaves the
+// 256-CU planning device two workgroups per CU (column blocks x the most row groups kdim allows); else the narrowest.  The shape
+// alone decides, so the column blocks (the splits of dx) never change with the device; row groups for two workgroups per CU.
+static void pg_stream_grid(PgPlan &p, long long m, long long kdim, long long ncols, int bits, int cus)
+{
+    cus = std::max(1, std::min(cus, CB_PLAN_CUS));
+    p.path = NNC_CBMM_STREAM;
+    p.mt = pg_mt(m);
+    const long long max_groups = cdiv(kdim, (long long)CB_WAVES * CB_UNROLL);   // every wave keeps a batch of rows
+    const int cap = std::min(128 / bits, PKG_G / p.mt);
+    p.cols = cap;
+    for (int c = cap; c * bits >= 32; c /= 2) {
+        p.cols = c;
+        const long long tiles = cdiv(ncols, 64LL * c);
+        if (tiles * 64 * c * 4 <= ncols * 5 && tiles * max_groups >= 2LL * CB_PLAN_CUS) break;
+    }
+    p.vb = p.cols * bits / 8;
+    p.col_tiles = cdiv(ncols, 64LL * p.cols);
+    const long long groups = std::max(1LL, std::min(cdiv(2LL * cus, p.col_tiles), max_groups));
+    p.rows_per_group = cdiv(kdim, groups);
+    p.row_tiles = cdiv(kdim, p.rows_per_group);
+}
+
+static PgPlan pg_dx_plan(long long m, long long kdim, long long ncols, int bits, int cus)
+{
+    PgPlan p{};
+    if (m == 0 || kdim == 0) return p;                       // NNC_CBMM_NONE: dx is empty
+    if (ncols == 0) {                                        // dx = 0
+        p.path = NNC_CBMM_ZERO;
+        return p;
+    }
+    p.entries = 1 << bits;
+    if (m <= CB_SKINNY_M) {
+        pg_stream_grid(p, m, kdim, ncols, bits, cus);
+        p.splits = p.col_tiles;                              // one split per column block
+        p.per_split = 64LL * p.cols;
+        p.copies = PK_COPIES;
+        p.lds = ((long long)p.entries * PK_COPIES + p.entries) * 4;
+    } else {
+        p.path = NNC_CBMM_TILED;
+        p.copies = 1;
+        p.col_tiles = cdiv(kdim, TB_N);
+        p.row_tiles = cdiv(m, TB_M);
+        long long s = std::min({cdiv(2LL * CB_PLAN_CUS, p.col_tiles * p.row_tiles), ncols / (16 * TB_K), 16LL});
+        s = std::max(1LL, s);
+        p.per_split = cdiv(cdiv(ncols, s), 16) * 16;         // whole dwords at either width: a thread's 4 columns lie in one
+        p.splits = cdiv(ncols, p.per_split);
+        p.lds = (long long)(TB_K * TB_M + TB_K * TB_N + p.entries) * 4;
+    }
+    return p;
+}
+
+static int64_t pg_dx_ws_bytes(const PgPlan &p, long long m, long long kdim) { return p.splits > 1 ? (int64_t)p.splits * m * kdim * 4 : 0; }
+
+// The splits of m and T are nnc_cbmm_dc_plan's for the same shape at label_bytes = 1 (so S, every image and every sum are the byte
+// form's).  NNC_OK, or that plan's error.
+static int pg_dc_plan(long long m, long long kdim, long long ncols, int bits, int k, int cus, PgPlan &p)
+{
+    p = PgPlan{};
+    if (m == 0 || kdim == 0 || ncols == 0) {                 // no terms: dc = 0
+        p.path = NNC_CBMM_ZERO;
+        return NNC_OK;
+    }
+    int64_t d[NNC_CBDC_PLAN_LEN];
+    const int rc = nnc_cbmm_dc_plan(m, kdim, ncols, 1, k, CB_PLAN_CUS, 0, d);
+    if (rc != NNC_OK) return rc;
+    p.splits = d[NNC_CBDC_P_SPLITS];
+    p.per_split = d[NNC_CBDC_P_RPS];
+    p.terms_log2 = (int)d[NNC_CBDC_P_TERMS_LOG2];
+    p.copies = 1 << PKG_RLOG2;
+    const long long bins = ((long long)k << PKG_RLOG2) * 8;
+    if (m <= CB_SKINNY_M) {
+        pg_stream_grid(p, m, kdim, ncols, bits, cus);
+        p.lds = bins;
+    } else {
+        p.path = NNC_CBMM_TILED;
+        p.col_tiles = cdiv(ncols, TB_N);
+        p.row_tiles = cdiv(kdim, TB_M);
+        p.lds = (long long)(TB_K * TB_M + TB_K * TB_N) * 4 + bins;
+    }
+    return NNC_OK;
+}
+
+static int64_t pg_dc_ws_bytes(const PgPlan &p, int k) { return p.path == NNC_CBMM_STREAM || p.path == NNC_CBMM_TILED ? CBG_HDR_BYTES + 8LL * k : 0; }
+
+// ------------------------------------------------------------------ dx, m <= 16
+// wave_reduce_rows (nnc_cbgrad.hpp: the same exchanges and the same additions in the same order) with both candidates of every
+// exchange read into values before the select.  A select between two elements of the array is a select between two addresses to the
+// compiler, which at N = 16 keeps the array in scratch (80 bytes per lane in k_cbdx_stream); this form stays in registers.
+template <int N>
+__device__ __forceinline__ float pg_reduce_rows(float (&v)[N], int lane, int &row)
+{
+    row = 0;
+#pragma unroll
+    for (int t = 0; (N >> t) > 1; ++t) {
+        const int half = N >> (t + 1), bit = 32 >> t;
+        const bool up = (lane & bit) != 0;
+#pragma unroll
+        for (int j = 0; j < half; ++j) {
+            const float a = v[j], b = v[j + half];
+            v[j] = (up ? b : a) + __shfl_xor(up ? a : b, bit);
+        }
+        row += up ? half : 0;
+    }
+    float s = v[0];
+#pragma unroll
+    for (int bit = 64 / N / 2; bit >= 1; bit >>= 1) s += __shfl_xor(s, bit);
+    return s;
+}
+
+// grid (column blocks, row groups), CB_THREADS threads.  out: dx (one column block) or the partials [block][m][kdim].
+template <int BITS, int VB, int MT>
+__global__ __launch_bounds__(CB_THREADS) void k_cbpkdx_stream(const float *__restrict__ g, int m, long long kdim, const unsigned char *__restrict__ packed,
+                                                              long long row_bytes, long long ncols, const float *__restrict__ centers, int k,
+                                                              long long rows_per_group, int direct, float *__restrict__ out)
+{
+    constexpr int E = 8 * VB / BITS, N = VB >= 4 ? VB / 4 : 1, PER = 32 / BITS, ENTRIES = 1 << BITS;
+    constexpr uint32_t MASK = (1u << BITS) - 1;
+    static_assert(E * MT <= PKG_G, "g values per lane");
+    extern __shared__ float smem[];
+    float *cb = smem;                                   // [ENTRIES][PK_COPIES]
+    float *stage = smem + ENTRIES * PK_COPIES;
+    cb_fill(cb, stage, centers, k, ENTRIES, PK_CSHIFT);
+
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const long long c0 = (long long)blockIdx.x * (64 * E) + lane * E;
+    const bool active = c0 < ncols;                     // then the lane's VB bytes lie inside the padded row
+    const int ne = (int)std::max(0LL, std::min((long long)E, ncols - c0));   // the lane's columns inside the matrix
+    float gv[MT][E];
+#pragma unroll
+    for (int r = 0; r < MT; ++r)
+#pragma unroll
+        for (int e = 0; e < E; ++e) gv[r][e] = (r < m && e < ne) ? g[(long long)r * ncols + c0 + e] : 0.0f;
+
+    const long long g_lo = (long long)blockIdx.y * rows_per_group, g_hi = std::min(kdim, g_lo + rows_per_group);
+    const long long per_wave = (g_hi - g_lo + CB_WAVES - 1) / CB_WAVES;
+    const long long i0 = std::min(g_hi, g_lo + wave * per_wave), i1 = std::min(g_hi, i0 + per_wave);
+    const unsigned char *mine = packed + (active ? (long long)blockIdx.x * (64 * VB) + lane * VB : 0LL);
+    const char *tab = reinterpret_cast<const char *>(cb) + ((lane & (PK_COPIES - 1)) << 2);
+    float *dst = direct ? out : out + (long long)blockIdx.x * m * kdim;
+    __syncthreads();
+
+    auto consume = [&](const uint32_t *w, long long i) {
+        float p[MT];
+#pragma unroll
+        for (int r = 0; r < MT; ++r) p[r] = 0.0f;
+#pragma unroll
+        for (int e = 0; e < E; ++e) {
+            constexpr int SH = 7;                                        // entry l of this lane's copy at byte l << 7
+            const int bit = BITS * (e % PER);
+            const uint32_t d = w[e / PER];
+            const uint32_t a = (bit >= SH ? d >> (bit - SH) : d << (SH - bit)) & (MASK << SH);
+            const float wv = e < ne ? *reinterpret_cast<const float *>(tab + a) : 0.0f;   // (columns past the row: no Inf * 0)
+#pragma unroll
+            for (int r = 0; r < MT; ++r) p[r] = __builtin_fmaf(gv[r][e], wv, p[r]);
+        }
+        int row;
+        const float v = pg_reduce_rows<MT>(p, lane, row);
+        if ((lane & (64 / MT - 1)) == 0 && row < m) dst[(long long)row * kdim + i] = v;
+    };
+
+    long long i = i0;
+    for (; i + CB_UNROLL <= i1; i += CB_UNROLL) {
+        uint32_t w[CB_UNROLL][N];
+#pragma unroll
+        for (int u = 0; u < CB_UNROLL; ++u) pk_load<VB>(mine + (i + u) * row_bytes, w[u]);
+#pragma unroll
+        for (int u = 0; u < CB_UNROLL; ++u) consume(w[u], i + u);
+    }
+    for (; i < i1; ++i) {
+        uint32_t w[N];
+        pk_load<VB>(mine + i * row_bytes, w);
+        consume(w, i);
+    }
+}
+
+// ------------------------------------------------------------------ dx, m > 16
+// grid (kdim tiles * m tiles, splits of ncols), 256 threads; thread (tx, ty) owns rows ty*8.. (of g) and columns tx*8.. (i) of the
+// tile.  Thread t decodes columns ob + (t & 1) * 4 .. + 3 of index row n0 + t / 2 from the dword that holds them (a split starts on a
+// multiple of 16 columns, so the 4 fields never straddle two dwords); the two threads of a row load the same address.
+template <int BITS>
+__global__ __launch_bounds__(256) void k_cbpkdx_tiled(const float *__restrict__ g, long long m, long long kdim, const unsigned char *__restrict__ packed,
+                                                      long long row_bytes, long long ncols, const float *__restrict__ centers, int k, long long col_tiles,
+                                                      long long cols_per_split, int direct, float *__restrict__ out)
+{
+    constexpr int ENTRIES = 1 << BITS;
+    constexpr uint32_t MASK = (1u << BITS) - 1;
+    extern __shared__ float smem[];
+    float *gs = smem;                      // [TB_K][TB_M]: g[m0 + r, o]
+    float *ws = gs + TB_K * TB_M;          // [TB_K][TB_N]: W^T[o, n0 + i] = c[L[n0 + i, o]]
+    float *cb = ws + TB_K * TB_N;          // 2^BITS entries (zeros from k on)
+    for (int j = threadIdx.x; j < ENTRIES; j += 256) cb[j] = j < k ? centers[j] : 0.0f;
+
+    const int t = threadIdx.x, tx = t & 15, ty = t >> 4;
+    const long long n0 = (blockIdx.x % col_tiles) * TB_N, m0 = (blockIdx.x / col_tiles) * TB_M;
+    const long long o_lo = (long long)blockIdx.y * cols_per_split, o_hi = std::min(ncols, o_lo + cols_per_split);
+    float acc[8][8];
+#pragma unroll
+    for (int a = 0; a < 8; ++a)
+#pragma unroll
+        for (int b = 0; b < 8; ++b) acc[a][b] = 0.0f;
+
+    const int lr = t >> 1, lo = (t & 1) * 4;   // g tile: row lr, o lo..lo+3; W^T tile: index row n0 + lr, o lo..lo+3
+    for (long long ob = o_lo; ob < o_hi; ob += TB_K) {
+        __syncthreads();
+        {
+            const long long gr = m0 + lr, wi = n0 + lr;
+            const long long bitpos = (ob + lo) * BITS;
+            const bool live = wi < kdim && ob + lo < o_hi;                 // then the dword lies inside the padded row
+            const uint32_t word = live ? *reinterpret_cast<const uint32_t *>(packed + wi * row_bytes + ((bitpos >> 5) << 2)) >> (bitpos & 31) : 0u;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const long long go = ob + lo + j;
+                const bool in_o = go < o_hi;
+                gs[(lo + j) * TB_M + lr] = (gr < m && in_o) ? g[gr * ncols + go] : 0.0f;
+                ws[(lo + j) * TB_N + lr] = (live && in_o) ? cb[(word >> (BITS * j)) & MASK] : 0.0f;
+            }
+        }
+        __syncthreads();
+        tb_tile_fma(gs, ws, tx, ty, acc);
+    }
+    float *dst = direct ? out : out + (long long)blockIdx.y * m * kdim;
+#pragma unroll
+    for (int a = 0; a < 8; ++a) {
+        const long long r = m0 + ty * 8 + a;
+#pragma unroll
+        for (int b = 0; b < 8; ++b) {
+            const long long c = n0 + tx * 8 + b;
+            if (r < m && c < kdim) dst[r * kdim + c] = acc[a][b];
+        }
+    }
+}
+
+// ------------------------------------------------------------------ dc, m <= 16
+// grid (column blocks, row groups), CB_THREADS threads.  LDS: the bins, [k][64] int64, copy `lane` of every bin this lane's own.
+template <int BITS, int VB, int MT>
+__global__ __launch_bounds__(CB_THREADS) void k_cbpkdc_stream(const float *__restrict__ x, const float *__restrict__ g, int m, long long kdim,
+                                                              const unsigned char *__restrict__ packed, long long row_bytes, long long ncols, int k,
+                                                              int terms_log2, long long rows_per_group, uint32_t *__restrict__ hdr,
+                                                              unsigned long long *__restrict__ sums)
+{
+    constexpr int E = 8 * VB / BITS, N = VB >= 4 ? VB / 4 : 1, PER = 32 / BITS;
+    constexpr uint32_t MASK = (1u << BITS) - 1;
+    static_assert(E * MT <= PKG_G, "g values per lane");
+    extern __shared__ unsigned long long bins[];
+    int flag;
+    const int S = cbdc_shift(hdr, m, terms_log2, flag);
+    if (blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0) {
+        hdr[2] = (uint32_t)S;
+        hdr[3] = (uint32_t)flag;
+    }
+    if (flag != CBG_FLAG_OK) return;   // (uniform over the launch)
+    int scx, scg;
+    cbdc_scales(hdr, scx, scg);
+    const int Sw = S - scx - scg;      // the shift of dW' = dW * 2^(scx + scg)
+    for (int j = threadIdx.x; j < (k << PKG_RLOG2); j += CB_THREADS) bins[j] = 0ull;
+
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const long long c0 = (long long)blockIdx.x * (64 * E) + lane * E;
+    const bool active = c0 < ncols;
+    const int ne = (int)std::max(0LL, std::min((long long)E, ncols - c0));
+    float gv[MT][E];
+#pragma unroll
+    for (int r = 0; r < MT; ++r)
+#pragma unroll
+        for (int e = 0; e < E; ++e) gv[r][e] = g[cbdc_idx((long long)r * ncols + c0 + e, r < m && e < ne)];
+    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+    for (int r = 0; r < MT; ++r)
+#pragma unroll
+        for (int e = 0; e < E; ++e) gv[r][e] = cbdc_scaled(gv[r][e], r < m && e < ne, scg);
+
+    const long long g_lo = (long long)blockIdx.y * rows_per_group, g_hi = std::min(kdim, g_lo + rows_per_group);
+    const long long per_wave = (g_hi - g_lo + CB_WAVES - 1) / CB_WAVES;
+    const long long i0 = std::min(g_hi, g_lo + wave * per_wave), i1 = std::min(g_hi, i0 + per_wave);
+    const unsigned char *mine = packed + (active ? (long long)blockIdx.x * (64 * VB) + lane * VB : 0LL);
+    unsigned long long *mybins = bins + lane;
+    __syncthreads();
+
+    // x[r, i + u] of a batch of U rows: lane f holds value f = r * U + u (and f + 64), broadcast by v_readlane (as k_cbdc_stream)
+    auto load_x = [&](long long i, int U, float &xa, float &xb) {
+        const int f0 = lane, f1 = lane + 64;
+        const int r0 = f0 / U, r1 = f1 / U;
+        xa = cbdc_scaled(x[cbdc_idx((long long)r0 * kdim + i + f0 % U, r0 < m)], r0 < m, scx);
+        xb = MT * CB_UNROLL > 64 ? cbdc_scaled(x[cbdc_idx((long long)r1 * kdim + i + f1 % U, r1 < m)], r1 < m, scx) : 0.0f;
+    };
+    auto consume = [&](const uint32_t *w, float xa, float xb, int u, int U) {
+        float xv[MT];
+#pragma unroll
+        for (int r = 0; r < MT; ++r) {
+            const int f = r * U + u;
+            xv[r] = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, f < 64 ? xa : xb), f & 63));
+        }
+#pragma unroll
+        for (int e = 0; e < E; ++e) {
+            const uint32_t l = (w[e / PER] >> (BITS * (e % PER))) & MASK;
+            float d = 0.0f;
+#pragma unroll
+            for (int r = 0; r < MT; ++r) d = __builtin_fmaf(xv[r], gv[r][e], d);   // dW'[i, o], r ascending
+            if (e < ne && l < (uint32_t)k) atomicAdd(&mybins[l << PKG_RLOG2], cbdc_fix(d, Sw));
+        }
+    };
+
+    long long i = i0;
+    for (; i + CB_UNROLL <= i1; i += CB_UNROLL) {
+        uint32_t w[CB_UNROLL][N];
+        float xa, xb;
+#pragma unroll
+        for (int u = 0; u < CB_UNROLL; ++u) pk_load<VB>(mine + (i + u) * row_bytes, w[u]);
+        load_x(i, CB_UNROLL, xa, xb);
+#pragma unroll
+        for (int u = 0; u < CB_UNROLL; ++u) consume(w[u], xa, xb, u, CB_UNROLL);
+    }
+    for (; i < i1; ++i) {
+        uint32_t w[N];
+        float xa, xb;
+        pk_load<VB>(mine + i * row_bytes, w);
+        load_x(i, 1, xa, xb);
+        consume(w, xa, xb, 0, 1);
+    }
+    cbdc_flush(bins, k, PKG_RLOG2, sums);
+}
+
+// ------------------------------------------------------------------ dc, m > 16
+// grid (ncols tiles * kdim tiles, splits of m), 256 threads; thread (tx, ty) forms dW for index rows ty*8.. and columns tx*8.. of the
+// 128 x 128 tile over its split's rows of m, then bins the 64 values: the 8 labels of a row are 8 * BITS bits of one packed dword
+// (a tile starts on a multiple of 128 columns).
+template <int BITS>
+__global__ __launch_bounds__(256) void k_cbpkdc_tiled(const float *__restrict__ x, const float *__restrict__ g, long long m, long long kdim,
+                                                      const unsigned char *__restrict__ packed, long long row_bytes, long long ncols, int k, int terms_log2,
+                                                      long long col_tiles, long long rows_per_split, uint32_t *__restrict__ hdr,
+                                                      unsigned long long *__restrict__ sums)
+{
+    constexpr uint32_t MASK = (1u << BITS) - 1;
+    extern __shared__ float smem[];
+    float *xs = smem;                      // [TB_K][TB_M]: x[r, i0 + i]
+    float *gs = xs + TB_K * TB_M;          // [TB_K][TB_N]: g[r, o0 + o]
+    unsigned long long *bins = reinterpret_cast<unsigned long long *>(gs + TB_K * TB_N);
+    int flag;
+    const int S = cbdc_shift(hdr, m, terms_log2, flag);
+    if (blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0) {
+        hdr[2] = (uint32_t)S;
+        hdr[3] = (uint32_t)flag;
+    }
+    if (flag != CBG_FLAG_OK) return;
+    int scx, scg;
+    cbdc_scales(hdr, scx, scg);
+    const int Sw = S - scx - scg;
+    for (int j = threadIdx.x; j < (k << PKG_RLOG2); j += 256) bins[j] = 0ull;
+
+    const int t = threadIdx.x, tx = t & 15, ty = t >> 4;
+    const long long o0 = (blockIdx.x % col_tiles) * TB_N, i0 = (blockIdx.x / col_tiles) * TB_M;
+    const long long r_lo = (long long)blockIdx.y * rows_per_split, r_hi = std::min(m, r_lo + rows_per_split);
+    float acc[8][8];
+#pragma unroll
+    for (int a = 0; a < 8; ++a)
+#pragma unroll
+        for (int b = 0; b < 8; ++b) acc[a][b] = 0.0f;
+
+    const int lk = t >> 5, lc = (t & 31) * 4;   // both tiles: row r = rb + lk, columns lc..lc+3 (coalesced)
+    for (long long rb = r_lo; rb < r_hi; rb += TB_K) {
+        __syncthreads();
+        {
+            const long long r = rb + lk;
+            const bool in_r = r < r_hi;
+            float xv[4], gv[4];
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const long long ii = i0 + lc + j, oo = o0 + lc + j;
+                xv[j] = x[cbdc_idx(r * kdim + ii, in_r && ii < kdim)];
+                gv[j] = g[cbdc_idx(r * ncols + oo, in_r && oo < ncols)];
+            }
+            __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const long long ii = i0 + lc + j, oo = o0 + lc + j;
+                xs[lk * TB_M + lc + j] = cbdc_scaled(xv[j], in_r && ii < kdim, scx);
+                gs[lk * TB_N + lc + j] = cbdc_scaled(gv[j], in_r && oo < ncols, scg);
+            }
+        }
+        __syncthreads();
+        tb_tile_fma(xs, gs, tx, ty, acc);
+    }
+    unsigned long long *mybins = bins + (t & ((1 << PKG_RLOG2) - 1));
+    const long long oc = o0 + tx * 8, bitpos = oc * BITS;
+#pragma unroll
+    for (int a = 0; a < 8; ++a) {
+        const long long i = i0 + ty * 8 + a;
+        if (i >= kdim || oc >= ncols) continue;                           // (then the dword lies inside the padded row)
+        const uint32_t word = *reinterpret_cast<const uint32_t *>(packed + i * row_bytes + ((bitpos >> 5) << 2)) >> (bitpos & 31);
+#pragma unroll
+        for (int b = 0; b < 8; ++b) {
+            if (oc + b >= ncols) continue;
+            const uint32_t l = (word >> (BITS * b)) & MASK;
+            if (l < (uint32_t)k) atomicAdd(&mybins[l << PKG_RLOG2], cbdc_fix(acc[a][b], Sw));
+        }
+    }
+    cbdc_flush(bins, k, PKG_RLOG2, sums);
+}
+
+// ------------------------------------------------------------------ C ABI
+static int pg_check(const char *fn, int64_t m, int64_t kdim, int64_t ncols, int bits, int32_t k)
+{
+    const int rc = pk_check(fn, m, kdim, ncols, bits, k);
+    if (rc != NNC_OK) return rc;
+    if (m > 0 && kdim > (1LL << 44) / m) return fail(NNC_EINVAL, std::string(fn) + ": size too large");
+    return NNC_OK;
+}
+
+template <int BITS, int VB, int MT>
+static void launch_pg_dx(dim3 grid, size_t lds, hipStream_t s, const float *g, int m, long long kdim, const unsigned char *packed, long long row_bytes,
+                         long long ncols, const float *centers, int k, long long rpg, int direct, float *out)
+{
+    hipLaunchKernelGGL((k_cbpkdx_stream<BITS, VB, MT>), grid, dim3(CB_THREADS), lds, s, g, m, kdim, packed, row_bytes, ncols, centers, k, rpg, direct, out);
+}
+
+template <int BITS, int VB, int MT>
+static void launch_pg_dc(dim3 grid, size_t lds, hipStream_t s, const float *x, const float *g, int m, long long kdim, const unsigned char *packed,
+                         long long row_bytes, long long ncols, int k, int tl, long long rpg, uint32_t *hdr, unsigned long long *sums)
+{
+    hipLaunchKernelGGL((k_cbpkdc_stream<BITS, VB, MT>), grid, dim3(CB_THREADS), lds, s, x, g, m, kdim, packed, row_bytes, ncols, k, tl, rpg, hdr, sums);
+}
+
+// every stream instantiation there is; the plans are checked against this table, and the launches go through it
+using PgDxLaunch = void (*)(dim3, size_t, hipStream_t, const float *, int, long long, const unsigned char *, long long, long long, const float *, int,
+                            long long, int, float *);
+using PgDcLaunch = void (*)(dim3, size_t, hipStream_t, const float *, const float *, int, long long, const unsigned char *, long long, long long, int, int,
+                            long long, uint32_t *, unsigned long long *);
+struct PgCase {
+    int bits, vb, mt;
+    PgDxLaunch dx;
+    PgDcLaunch dc;
+};
+#define PG_CASE(B, V, M) {B, V, M, launch_pg_dx<B, V, M>, launch_pg_dc<B, V, M>}
+static const PgCase kPgCases[] = {
+    PG_CASE(4, 16, 1), PG_CASE(4, 8, 1), PG_CASE(4, 4, 1), PG_CASE(4, 16, 2), PG_CASE(4, 8, 2), PG_CASE(4, 4, 2), PG_CASE(4, 8, 4),
+    PG_CASE(4, 4, 4),  PG_CASE(4, 4, 8), PG_CASE(4, 2, 16),
+    PG_CASE(2, 16, 1), PG_CASE(2, 8, 1), PG_CASE(2, 4, 1), PG_CASE(2, 8, 2),  PG_CASE(2, 4, 2), PG_CASE(2, 4, 4), PG_CASE(2, 2, 8),
+    PG_CASE(2, 1, 16),
+};
+#undef PG_CASE
+
+static const PgCase *find_pg_case(int bits, int vb, int mt)
+{
+    for (const PgCase &c : kPgCases)
+        if (c.bits == bits && c.vb == vb && c.mt == mt) return &c;
+    return nullptr;
+}
+
+static int no_pg_case(const char *fn, int bits, int vb, int mt)
+{
+    return fail(NNC_EINVAL, std::string(fn) + ": no stream instantiation for bits " + std::to_string(bits) + ", vb " + std::to_string(vb) + ", mt " +
+                                std::to_string(mt));
+}
+
+static int pg_plan_out(const char *fn, const PgPlan &p, int bits, int32_t cus, int64_t *out)
+{
+    if (cus < 1) return fail(NNC_EINVAL, std::string(fn) + ": cus < 1");
+    if (!out) return fail(NNC_EINVAL, std::string(fn) + ": out is NULL");
+    if (p.path == NNC_CBMM_STREAM && !find_pg_case(bits, p.vb, p.mt)) return no_pg_case(fn, bits, p.vb, p.mt);
+    return NNC_OK;
+}
+
+extern "C" int64_t nnc_cbpk_dx_workspace_bytes(int64_t m, int64_t kdim, int64_t ncols, int bits)
+{
+    if (pg_check("nnc_cbpk_dx_workspace_bytes", m, kdim, ncols, bits, 1) != NNC_OK) return 0;
+    return pg_dx_ws_bytes(pg_dx_plan(m, kdim, ncols, bits, CB_PLAN_CUS), m, kdim);
+}
+
+extern "C" int nnc_cbpk_dx_plan(int64_t m, int64_t kdim, int64_t ncols, int bits, int32_t k, int32_t cus, int64_t *out)
+{
+    int rc = pg_check("nnc_cbpk_dx_plan", m, kdim, ncols, bits, k);
+    if (rc != NNC_OK) return rc;
+    const PgPlan p = pg_dx_plan(m, kdim, ncols, bits, std::max(cus, 1));
+    if ((rc = pg_plan_out("nnc_cbpk_dx_plan", p, bits, cus, out)) != NNC_OK) return rc;
+    const int64_t v[NNC_CBPKDX_PLAN_LEN] = {p.path, p.vb, p.mt, p.cols, p.copies, p.entries, p.splits, p.per_split, p.lds, p.col_tiles, p.row_tiles,
+                                            pg_dx_ws_bytes(p, m, kdim)};
+    for (int i = 0; i < NNC_CBPKDX_PLAN_LEN; ++i) out[i] = v[i];
+    return NNC_OK;
+}
+
+extern "C" int nnc_cbpk_dx_f32(const float *g, int64_t m, int64_t kdim, const void *packed, int64_t packed_bytes, int bits, int64_t ncols,
+                               const float *centers_dev, int32_t k, float *dx, void *workspace, int64_t workspace_bytes, void *stream)
+{
+    const char *fn = "nnc_cbpk_dx_f32";
+    int rc = pg_check(fn, m, kdim, ncols, bits, k);
+    if (rc != NNC_OK) return rc;
+    if ((rc = pk_check_buffer(fn, packed, packed_bytes, kdim, ncols, bits)) != NNC_OK) return rc;
+    if (!centers_dev) return fail(NNC_EINVAL, "nnc_cbpk_dx_f32: centers is NULL");
+    if (m > 0 && kdim > 0 && !dx) return fail(NNC_EINVAL, "nnc_cbpk_dx_f32: dx is NULL");
+    if (m > 0 && kdim > 0 && ncols > 0 && !g) return fail(NNC_EINVAL, "nnc_cbpk_dx_f32: g is NULL");
+    if (workspace_bytes < 0) return fail(NNC_EINVAL, "nnc_cbpk_dx_f32: negative workspace size");
+    const int64_t need = nnc_cbpk_dx_workspace_bytes(m, kdim, ncols, bits);
+    if (workspace_bytes < need) return fail(NNC_ENOSPACE, "nnc_cbpk_dx_f32: workspace smaller than nnc_cbpk_dx_workspace_bytes()");
+    if (need > 0 && !workspace) return fail(NNC_EINVAL, "nnc_cbpk_dx_f32: workspace is NULL");
+    if (need > 0 && reinterpret_cast<uintptr_t>(workspace) % 4) return fail(NNC_EINVAL, "nnc_cbpk_dx_f32: workspace must be 4-byte aligned");
+    PgPlan p = pg_dx_plan(m, kdim, ncols, bits, CB_PLAN_CUS);
+    const PgCase *pc = p.path == NNC_CBMM_STREAM ? find_pg_case(bits, p.vb, p.mt) : nullptr;
+    if (p.path == NNC_CBMM_STREAM && !pc) return no_pg_case(fn, bits, p.vb, p.mt);
+    if (p.path == NNC_CBMM_NONE) return NNC_OK;
+
+    hipStream_t s = S(stream);
+    p = pg_dx_plan(m, kdim, ncols, bits, cu_count());        // (the row groups of this device)
+    if (p.path == NNC_CBMM_ZERO) {
+        HIPCHK(hipMemsetAsync(dx, 0, (size_t)(m * kdim) * 4, s));
+        return NNC_OK;
+    }
+    const int direct = p.splits == 1;
+    float *out = direct ? dx : reinterpret_cast<float *>(workspace);
+    const unsigned char *pk = reinterpret_cast<const unsigned char *>(packed);
+    const long long row_bytes = pk_row_bytes(ncols, bits);
+    if (p.path == NNC_CBMM_STREAM) {
+        pc->dx(dim3((unsigned)p.col_tiles, (unsigned)p.row_tiles), (size_t)p.lds, s, g, (int)m, kdim, pk, row_bytes, ncols, centers_dev, k, p.rows_per_group,
+               direct, out);
+        LAUNCHCHK("k_cbpkdx_stream");
+    } else {
+        const dim3 grid((unsigned)(p.col_tiles * p.row_tiles), (unsigned)p.splits);
+        if (bits == 4)
+            hipLaunchKernelGGL(k_cbpkdx_tiled<4>, grid, dim3(256), (size_t)p.lds, s, g, (long long)m, (long long)kdim, pk, row_bytes, (long long)ncols,
+                               centers_dev, (int)k, p.col_tiles, p.per_split, direct, out);
+        else
+            hipLaunchKernelGGL(k_cbpkdx_tiled<2>, grid, dim3(256), (size_t)p.lds, s, g, (long long)m, (long long)kdim, pk, row_bytes, (long long)ncols,
+                               centers_dev, (int)k, p.col_tiles, p.per_split, direct, out);
+        LAUNCHCHK("k_cbpkdx_tiled");
+    }
+    if (!direct) return cbgrad_reduce(reinterpret_cast<const float *>(workspace), p.splits, m * kdim, dx, s);
+    return NNC_OK;
+}
+
+extern "C" int64_t nnc_cbpk_dc_workspace_bytes(int64_t m, int64_t kdim, int64_t ncols, int bits, int32_t k)
+{
+    if (pg_check("nnc_cbpk_dc_workspace_bytes", m, kdim, ncols, bits, k) != NNC_OK) return 0;
+    PgPlan p;
+    if (pg_dc_plan(m, kdim, ncols, bits, k, CB_PLAN_CUS, p) != NNC_OK) return 0;
+    return pg_dc_ws_bytes(p, k);
+}
+
+extern "C" int nnc_cbpk_dc_plan(int64_t m, int64_t kdim, int64_t ncols, int bits, int32_t k, int32_t cus, int64_t *out)
+{
+    int rc = pg_check("nnc_cbpk_dc_plan", m, kdim, ncols, bits, k);
+    if (rc != NNC_OK) return rc;
+    PgPlan p;
+    if ((rc = pg_dc_plan(m, kdim, ncols, bits, k, std::max(cus, 1), p)) != NNC_OK) return rc;
+    if ((rc = pg_plan_out("nnc_cbpk_dc_plan", p, bits, cus, out)) != NNC_OK) return rc;
+    const int64_t v[NNC_CBPKDC_PLAN_LEN] = {p.path, p.vb, p.mt, p.cols, p.path == NNC_CBMM_ZERO ? 0 : p.copies, p.splits, p.per_split, p.lds,
+                                            p.col_tiles, p.row_tiles, p.terms_log2, pg_dc_ws_bytes(p, k)};
+    for (int i = 0; i < NNC_CBPKDC_PLAN_LEN; ++i) out[i] = v[i];
+    return NNC_OK;
+}
+
+extern "C" int nnc_cbpk_dc_f32(const float *x, const float *g, int64_t m, int64_t kdim, const void *packed, int64_t packed_bytes, int bits,
+                               int64_t ncols, int32_t k, void *dc, int32_t out_f64, void *workspace, int64_t workspace_bytes, void *stream)
+{
+    const char *fn = "nnc_cbpk_dc_f32";
+    int rc = pg_check(fn, m, kdim, ncols, bits, k);
+    if (rc != NNC_OK) return rc;
+    if ((rc = pk_check_buffer(fn, packed, packed_bytes, kdim, ncols, bits)) != NNC_OK) return rc;
+    if (!dc) return fail(NNC_EINVAL, "nnc_cbpk_dc_f32: dc is NULL");
+    if (m > 0 && kdim > 0 && ncols > 0 && (!x || !g)) return fail(NNC_EINVAL, "nnc_cbpk_dc_f32: x or g is NULL");
+    if (workspace_bytes < 0) return fail(NNC_EINVAL, "nnc_cbpk_dc_f32: negative workspace size");
+    PgPlan p;
+    if ((rc = pg_dc_plan(m, kdim, ncols, bits, k, CB_PLAN_CUS, p)) != NNC_OK) return rc;
+    const int64_t need = pg_dc_ws_bytes(p, k);
+    if (workspace_bytes < need) return fail(NNC_ENOSPACE, "nnc_cbpk_dc_f32: workspace smaller than nnc_cbpk_dc_workspace_bytes()");
+    if (need > 0 && !workspace) return fail(NNC_EINVAL, "nnc_cbpk_dc_f32: workspace is NULL");
+    if (need > 0 && reinterpret_cast<uintptr_t>(workspace) % 8 != 0) return fail(NNC_EINVAL, "nnc_cbpk_dc_f32: workspace not 8-byte aligned");
+    const PgCase *pc = p.path == NNC_CBMM_STREAM ? find_pg_case(bits, p.vb, p.mt) : nullptr;
+    if (p.path == NNC_CBMM_STREAM && !pc) return no_pg_case(fn, bits, p.vb, p.mt);
+
+    hipStream_t s = S(stream);
+    const size_t esz = out_f64 ? 8 : 4;
+    if (p.path == NNC_CBMM_ZERO) {
+        HIPCHK(hipMemsetAsync(dc, 0, (size_t)k * esz, s));
+        return NNC_OK;
+    }
+    if ((rc = pg_dc_plan(m, kdim, ncols, bits, k, cu_count(), p)) != NNC_OK) return rc;   // (the row groups of this device)
+    const unsigned char *pk = reinterpret_cast<const unsigned char *>(packed);
+    const long long row_bytes = pk_row_bytes(ncols, bits);
+    uint32_t *hdr = reinterpret_cast<uint32_t *>(workspace);
+    unsigned long long *sums = reinterpret_cast<unsigned long long *>(reinterpret_cast<char *>(workspace) + CBG_HDR_BYTES);
+    HIPCHK(hipMemsetAsync(workspace, 0, (size_t)need, s));
+    if ((rc = cbgrad_absmax(x, m * kdim, g, m * ncols, hdr, s)) != NNC_OK) return rc;
+    if (p.path == NNC_CBMM_STREAM) {
+        pc->dc(dim3((unsigned)p.col_tiles, (unsigned)p.row_tiles), (size_t)p.lds, s, x, g, (int)m, kdim, pk, row_bytes, ncols, k, p.terms_log2,
+               p.rows_per_group, hdr, sums);
+        LAUNCHCHK("k_cbpkdc_stream");
+    } else {
+        const dim3 grid((unsigned)(p.col_tiles * p.row_tiles), (unsigned)p.splits);
+        if (bits == 4)
+            hipLaunchKernelGGL(k_cbpkdc_tiled<4>, grid, dim3(256), (size_t)p.lds, s, x, g, (long long)m, (long long)kdim, pk, row_bytes, (long long)ncols,
+                               (int)k, p.terms_log2, p.col_tiles, p.per_split, hdr, sums);
+        else
+            hipLaunchKernelGGL(k_cbpkdc_tiled<2>, grid, dim3(256), (size_t)p.lds, s, x, g, (long long)m, (long long)kdim, pk, row_bytes, (long long)ncols,
+                               (int)k, p.terms_log2, p.col_tiles, p.per_split, hdr, sums);
+        LAUNCHCHK("k_cbpkdc_tiled");
+    }
+    return cbdc_finish(hdr, reinterpret_cast<const long long *>(sums), (int)k, (int)(out_f64 != 0), dc, s);
+}

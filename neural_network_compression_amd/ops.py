@@ -807,6 +807,116 @@ def cbpk_plan(m: int, kdim: int, ncols: int, bits: int, k: int, cus: int) -> dic
     return dict(zip(nat.CBPK_PLAN_FIELDS, (int(v) for v in out)))
 
 
+def _packed_grad_args(g: torch.Tensor, codes: PackedCodes):
+    _require_cuda(g, "g", torch.float32)
+    if not isinstance(codes, PackedCodes):
+        raise TypeError("codes must be a PackedCodes (ops.pack_codes)")
+    if g.dim() < 1 or g.shape[-1] != codes.ncols:
+        raise ValueError(f"g must have shape (..., {codes.ncols}), got {tuple(g.shape)}")
+    lead = tuple(g.shape[:-1])
+    return lead, (int(np.prod(lead)) if lead else 1)
+
+
+def packed_codebook_matmul_dx(g: torch.Tensor, codes: PackedCodes, centers: torch.Tensor) -> torch.Tensor:
+    """dx = g @ W^T with W[i, o] = centers[label (i, o)] read from the 2- or 4-bit packed indices (include/nnc.h,
+    nnc_cbpk_dx_f32): the input gradient of packed_codebook_matmul with the conventions of codebook_matmul_dx (a label >= k reads 0;
+    the padding of a row forms no product).  g: float32 (..., ncols); centers: float32[codes.k].  Returns float32 (..., kdim).
+    Split partials are summed in a fixed order: the same call gives the same bits.  No host read."""
+    _require_cuda(centers, "centers", torch.float32)
+    lead, m = _packed_grad_args(g, codes)
+    if centers.numel() != codes.k:
+        raise ValueError(f"centers must hold k = {codes.k} values, got {centers.numel()}")
+    if len({g.device, codes.device, centers.device}) != 1:
+        raise ValueError("g, codes and centers must be on one device")
+    L = nat.load()
+    kdim, ncols, bits = codes.kdim, codes.ncols, codes.bits
+    dx = torch.empty(lead + (kdim,), dtype=torch.float32, device=g.device)
+    ws_bytes = int(L.nnc_cbpk_dx_workspace_bytes(m, kdim, ncols, bits))
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=g.device) if ws_bytes else None
+    nat.check(L.nnc_cbpk_dx_f32(_ptr(g), m, kdim, _ptr(codes.packed), codes.nbytes, bits, ncols, _ptr(centers), centers.numel(), _ptr(dx),
+                                _ptr(ws), ws_bytes, _stream(g)))
+    return dx
+
+
+def packed_codebook_centroid_grad(x: torch.Tensor, g: torch.Tensor, codes: PackedCodes, dtype=torch.float64) -> torch.Tensor:
+    """dc[j] = sum over the (i, o) whose label is j of (x^T g)[i, o] (include/nnc.h, nnc_cbpk_dc_f32): bit for bit
+    codebook_centroid_grad(x, g, codes.to_dense(), codes.k, ...), the indices never unpacked and dW never written.  x: float32
+    (..., kdim), g: float32 (..., ncols) with the same leading shape.  Returns ``dtype`` (float64 or float32) [codes.k].  No host
+    read."""
+    _require_cuda(x, "x", torch.float32)
+    lead, m = _packed_grad_args(g, codes)
+    kdim, ncols, k, bits = codes.kdim, codes.ncols, codes.k, codes.bits
+    if x.dim() < 1 or x.shape[-1] != kdim or tuple(x.shape[:-1]) != lead:
+        raise ValueError(f"x must have shape {lead + (kdim,)}, got {tuple(x.shape)}")
+    if len({x.device, g.device, codes.device}) != 1:
+        raise ValueError("x, g and codes must be on one device")
+    if dtype not in (torch.float64, torch.float32):
+        raise TypeError("dtype must be torch.float64 or torch.float32")
+    L = nat.load()
+    dc = torch.empty(k, dtype=dtype, device=x.device)
+    ws_bytes = int(L.nnc_cbpk_dc_workspace_bytes(m, kdim, ncols, bits, k))
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=x.device) if ws_bytes else None
+    nat.check(L.nnc_cbpk_dc_f32(_ptr(x), _ptr(g), m, kdim, _ptr(codes.packed), codes.nbytes, bits, ncols, k, _ptr(dc),
+                                1 if dtype == torch.float64 else 0, _ptr(ws), ws_bytes, _stream(x)))
+    return dc
+
+
+def cbpk_dx_plan(m: int, kdim: int, ncols: int, bits: int, k: int, cus: int) -> dict:
+    """Host: the plan nnc_cbpk_dx_f32 follows on a device with ``cus`` compute units (include/nnc.h, nnc_cbpk_dx_plan), as a dict
+    keyed by _native.CBPKDX_PLAN_FIELDS.  No device needed."""
+    L = nat.load()
+    out = (ctypes.c_int64 * nat.CBPKDX_PLAN_LEN)()
+    nat.check(L.nnc_cbpk_dx_plan(int(m), int(kdim), int(ncols), int(bits), int(k), int(cus), out))
+    return dict(zip(nat.CBPKDX_PLAN_FIELDS, (int(v) for v in out)))
+
+
+def cbpk_dc_plan(m: int, kdim: int, ncols: int, bits: int, k: int, cus: int) -> dict:
+    """Host: the plan nnc_cbpk_dc_f32 follows on a device with ``cus`` compute units (include/nnc.h, nnc_cbpk_dc_plan), as a dict
+    keyed by _native.CBPKDC_PLAN_FIELDS.  No device needed."""
+    L = nat.load()
+    out = (ctypes.c_int64 * nat.CBPKDC_PLAN_LEN)()
+    nat.check(L.nnc_cbpk_dc_plan(int(m), int(kdim), int(ncols), int(bits), int(k), int(cus), out))
+    return dict(zip(nat.CBPKDC_PLAN_FIELDS, (int(v) for v in out)))
+
+
+class _PackedCodebookLinear(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, codes, centers, bias, relu):
+        with torch.no_grad():
+            y = packed_codebook_matmul(x.contiguous(), codes, centers, bias=bias, relu=relu)
+        ctx.codes, ctx.relu = codes, relu
+        ctx.save_for_backward(x, centers, y if relu else None)
+        return y
+
+    @staticmethod
+    def backward(ctx, gy):
+        x, centers, y = ctx.saved_tensors
+        codes = ctx.codes
+        g = gy.contiguous()
+        if ctx.relu:   # as torch.relu's backward: the gradient passes where y > 0 only (a NaN or negative output gets 0)
+            g = torch.where(y > 0, g, torch.zeros((), dtype=g.dtype, device=g.device))
+        g2 = g.reshape(-1, codes.ncols)
+        dx = dc = db = None
+        if ctx.needs_input_grad[0]:
+            dx = packed_codebook_matmul_dx(g2, codes, centers).view(x.shape)
+        if ctx.needs_input_grad[2]:
+            dc = packed_codebook_centroid_grad(x.contiguous().reshape(-1, codes.kdim), g2, codes, dtype=torch.float32)
+        if ctx.needs_input_grad[3]:
+            db = g2.sum(0)
+        return dx, None, dc, db, None
+
+
+def packed_codebook_linear(x: torch.Tensor, codes: PackedCodes, centers: torch.Tensor, bias: torch.Tensor | None = None,
+                           relu: bool = False) -> torch.Tensor:
+    """packed_codebook_matmul with gradients for x, centers and bias (an autograd Function shaped like codebook_linear).  The
+    forward is the same nnc_cbpk_f32 call (under no_grad the bits of packed_codebook_matmul); the backward runs
+    packed_codebook_matmul_dx only if x needs a gradient and packed_codebook_centroid_grad (float32) only if centers does, masks a
+    fused ReLU as torch does and sums the bias gradient over the rows.  The indices get no gradient.  No host read."""
+    if not isinstance(codes, PackedCodes):
+        raise TypeError("codes must be a PackedCodes (ops.pack_codes)")
+    return _PackedCodebookLinear.apply(x, codes, centers, bias, bool(relu))
+
+
 def huffman_lengths(counts) -> tuple:
     """Host: (lengths uint8[k], hist int64[max_len+1], total_bits) from an index histogram."""
     L = nat.load()
