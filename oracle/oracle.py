@@ -323,6 +323,12 @@ def lloyd_iter(xc, c_old, accum="A", S=0, want_labels=True, reloc=None, info=Non
             info["reloc_multi"] = info.get("reloc_multi", 0) + (n_empty > 1)
             if n_empty < d.size and ds[-n_empty] == ds[-n_empty - 1] and ds[-n_empty] != 0:
                 info["reloc_ties"] = info.get("reloc_ties", 0) + 1
+                # ... of which the ties that can matter: the two samples either side of the cut, in the order "descending distance, equal
+                # distances by descending value", differ in VALUE (samples equal in both get the same index and leave the same sums behind
+                # whichever of them goes: the zeros of a pruned tensor are the common case).  What the device reports (nnc_kmeans_status).
+                o = np.lexsort((xc, d))
+                if xc[o[-n_empty]] != xc[o[-n_empty - 1]]:
+                    info["reloc_ties_distinct"] = info.get("reloc_ties_distinct", 0) + 1
         if reloc == "argpartition":
             # scikit-learn: whatever order numpy.argpartition leaves the top n_empty indices in
             far = np.argpartition(d, -n_empty)[: -n_empty - 1 : -1].astype(np.int32)
