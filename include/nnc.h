@@ -582,6 +582,39 @@ int nnc_cbmm_f32(const float *x, int64_t m, int64_t kdim, const void *labels, in
                  const float *bias_dev, int32_t relu, float *y, void *workspace, int64_t workspace_bytes, void *stream);
 
 /* ------------------------------------------------------------------------------------
+ * The same layer on bf16 or fp16 activations (csrc/nnc_cbmm_h16.hip), the byte form of the indices only:
+ *     y = x @ W_h + bias,   W_h[i, o] = rn_dtype(centers_dev[labels[i * ncols + o]]),   dtype = x_dtype (NNC_DT_BF16 / NNC_DT_F16)
+ * centers_dev  float32[k] as for nnc_cbmm_f32; every centre is rounded to dtype (to nearest even) when a kernel builds its LDS
+ *              table, so an fp16 centre beyond 65504 acts as Inf.  An index >= k reads 0.
+ * products     x[., i] * W_h[i, .] of two bf16 or two fp16 values: exact in float32.
+ * sums         float32, in an order fixed by the shape and the CU count alone: no float atomics, split-K partials are float32 in the
+ *              workspace and summed in split order by k_cbmm_reduce; the same call gives the same bits.
+ * bias, ReLU   bias_dev float32[ncols] or NULL, added in float32; relu != 0: v < 0 ? 0 : v, so NaN is kept.
+ * y            y_dtype = NNC_DT_F32, or x_dtype: the float32 value rounded once to nearest even.
+ * x            contiguous (m, kdim) of x_dtype on any 2-byte aligned address; labels uint8 / uint16 on any storage offset, row-major
+ *              (kdim, ncols), as nnc_cbmm_f32.  m or ncols = 0 is a no-op; kdim = 0 writes y = bias (or 0).
+ * m <= 16 runs k_cbmm_stream with x read as dtype and widened (the float32 fmaf chain of nnc_cbmm_f32 on half the x bytes);
+ * m > 16 runs k_cbmm_mfma: 128 x 128 output tiles, the W tile looked up through the LDS table into a dtype LDS image, and
+ * v_mfma_f32_32x32x16_{bf16,f16} on it and the x tile; rows of x are loaded as 16-byte fragments where x is 16-byte aligned and kdim
+ * a multiple of 8, element by element otherwise.  Inference only.  nnc_cbmm_h16_workspace_bytes: what the call needs (host
+ * arithmetic).  nnc_cbmm_h16_plan: as nnc_cbmm_plan, NNC_CBMM_H16_PLAN_LEN values: the NNC_CBMM_P_* fields (PATH is NNC_CBMM_MFMA
+ * for m > 16; splits follow nnc_cbmm_plan's rule: from the shape and the CU count, never shrinking with more CUs, the query
+ * planning for 256), then NNC_CBMM_H16_P_DTYPE.  Argument errors (NNC_EINVAL: also an x_dtype that is not BF16 / F16, a y_dtype
+ * that is neither NNC_DT_F32 nor x_dtype, an odd x or half y address, a plan with no kernel instantiation; NNC_ENOSPACE for a short
+ * workspace) are returned before any HIP call.
+ * ---------------------------------------------------------------------------------- */
+#define NNC_DT_F32 0
+#define NNC_DT_BF16 1
+#define NNC_DT_F16 2
+#define NNC_CBMM_MFMA 5
+#define NNC_CBMM_H16_P_DTYPE 12
+#define NNC_CBMM_H16_PLAN_LEN 13
+int64_t nnc_cbmm_h16_workspace_bytes(int64_t m, int64_t kdim, int64_t ncols, int label_bytes);
+int nnc_cbmm_h16_plan(int x_dtype, int64_t m, int64_t kdim, int64_t ncols, int label_bytes, int32_t k, int32_t cus, uint64_t labels_addr, int64_t *out);
+int nnc_cbmm_h16(const void *x, int x_dtype, int64_t m, int64_t kdim, const void *labels, int label_bytes, int64_t ncols, const float *centers_dev,
+                 int32_t k, const float *bias_dev, int32_t relu, void *y, int y_dtype, void *workspace, int64_t workspace_bytes, void *stream);
+
+/* ------------------------------------------------------------------------------------
  * The backward pass of nnc_cbmm_f32 from the same codebook and indices, W never decoded (csrc/nnc_cbgrad.hip, DESIGN.md section
  * 12).  W[i, o] = centers[labels[i * ncols + o]] as above (same label widths, any storage offset); g = dL/dy float32[m, ncols].
  * nnc_cbmm_dx_f32   dx[m, kdim] = g @ W^T: dx[r, i] = sum_o g[r, o] * W[i, o].  m <= 16 streams the index rows (k_cbdx_stream: a

@@ -24,6 +24,14 @@ the candidates are the byte form (unless ``sparse is True``, or ``packed is True
 ``sparse`` is not False) and the packed form (if ``packed`` is not False and K <= 16); the one with the fewest resident bytes is
 kept, on equal bytes the earlier in this list.  The selection is by bytes, not by speed.
 
+``CompressedDense`` / ``CompressedConv2D`` also run on bfloat16 and float16 inputs (ops.codebook_matmul -> nnc_cbmm_h16,
+csrc/nnc_cbmm_h16.hip): the path is chosen by the input's dtype and the output has that dtype, so a chain
+of compressed layers stays in half.  ``centers`` and ``bias`` stay float32 buffers (each centre is rounded to the input's dtype
+inside the kernel, the bias is added in float32): feed half inputs, leave the module float32.  A module cast with ``.half()`` /
+``.bfloat16()`` turns those buffers into half tensors, and the layer then raises the dtype ``TypeError`` of ops.codebook_matmul.
+Half inputs are for the byte form only: the bitmap-sparse, the packed and every trainable layer raise ``TypeError`` on them, and
+``torch.autocast`` is not registered.
+
 These layers are inference only: under autograd, with an input that needs a gradient, they raise instead of returning a result
 that silently has none.  ``trainable=True`` in compress_network / Trainer.compressed_network gives the trainable variants instead
 (``TrainableCompressedDense`` / ``TrainableCompressedConv2D``): their ``centers`` is an nn.Parameter and the
@@ -72,7 +80,9 @@ def _decoded_bias(raw: torch.Tensor, bias_model) -> torch.Tensor:
 
 
 class _CodebookLayer(nn.Module):
-    """labels (kdim * ncols indices, row-major (kdim, ncols)), centers float32[K], bias float32[ncols] or None."""
+    """labels (kdim * ncols indices, row-major (kdim, ncols)), centers float32[K], bias float32[ncols] or None.  A bfloat16 or
+    float16 input gives an output of that dtype (ops.codebook_matmul); centers and bias stay float32: feed half inputs, leave the
+    module float32 (after ``.half()`` / ``.bfloat16()`` on the module the forward raises ops.codebook_matmul's dtype TypeError)."""
 
     def __init__(self, kdim: int, ncols: int, labels: torch.Tensor, centers: torch.Tensor, bias: torch.Tensor | None, activation=None):
         super().__init__()
@@ -160,7 +170,7 @@ def _conv_forward(layer, x: torch.Tensor) -> torch.Tensor:
     """The patches of NHWC x, at most _PATCH_BYTES of them at a time, through layer._matmul -> (N, Ho, Wo, ncols)."""
     n, hh, ww, _ = x.shape
     ho, wo = hh + 2 * layer.pad - layer.kernel_size + 1, ww + 2 * layer.pad - layer.kernel_size + 1
-    per = max(1, _PATCH_BYTES // max(1, ho * wo * layer.kdim * 4))
+    per = max(1, _PATCH_BYTES // max(1, ho * wo * layer.kdim * x.element_size()))
     outs = [layer._matmul(conv_patches(x[i: i + per], layer.kernel_size, layer.pad).contiguous()) for i in range(0, n, per)]
     if not outs:   # an empty batch: the (0, kdim) product, as F.conv2d gives an empty result
         outs = [layer._matmul(x.new_empty((0, layer.kdim)))]

@@ -1,7 +1,8 @@
 // nnc_cbmm.hip -- the quantized layer run from its codebook and centroid indices: y[m, ncols] = x[m, kdim] @ W + bias (then
 // ReLU if asked), W[i, o] = centers[labels[i * ncols + o]], the fp32 W never stored (include/nnc.h, nnc_cbmm_f32).
 //
-// Two regimes ("Running the compressed layer"):
+// Two regimes ("Running the compressed layer"); the plan and k_cbmm_stream are in nnc_cbmm.hpp, shared with the
+// bf16 / fp16 unit nnc_cbmm_h16.hip:
 //   k_cbmm_stream  m <= 16: bound by the index stream.  A wave owns 64 lanes x VB bytes of a label row (VB = 16, 8 or 4: the
 //                  widest load that keeps the m x (VB / label_bytes) accumulators of a lane within 64 registers), loaded straight
 //                  to VGPRs, CB_UNROLL rows in flight; x[r, i] is uniform over the wave (vector load + v_readlane).  The codebook sits in LDS
@@ -17,207 +18,6 @@
 // one byte of the tensor lies in the tensor's page, so no load leaves the allocation; lanes past the last column load their
 // row's first chunk and store nothing.  An index >= K reads 0, as nnc_gather_f32 does.
 #include "nnc_cbmm.hpp"
-
-// ------------------------------------------------------------------ the plan (host)
-// Every decision nnc_cbmm_f32 takes before it launches: which kernel, its instantiation, the LDS table, the grid and the K
-// splits.  nnc_cbmm_plan reports it (include/nnc.h), so the tests can see which regime a call hits.
-struct CbPlan {
-    int path;                // NNC_CBMM_NONE / _STREAM / _TILED / _BIAS
-    int vb, mt;              // stream: bytes per lane per row, rows of x per launch (a power of two >= m)
-    int entries, cshift;     // the LDS codebook: entries (centres, then zeros) x (1 << cshift) copies
-    int aligned;             // stream: every label row starts on a VB-byte boundary (no funnel shift)
-    long long col_tiles, row_tiles;
-    long long splits, rows_per_split;
-    long long lds;           // dynamic LDS bytes of the main kernel
-};
-
-// the splits and tiles (m >= 1, kdim >= 1, ncols >= 1)
-static void cb_grid(CbPlan &p, long long m, long long kdim, long long ncols, int lb, int cus)
-{
-    cus = std::max(1, std::min(cus, CB_PLAN_CUS));
-    long long s;
-    if (m <= CB_SKINNY_M) {
-        p.path = NNC_CBMM_STREAM;
-        p.mt = m <= 1 ? 1 : (m <= 2 ? 2 : (m <= 4 ? 4 : (m <= 8 ? 8 : 16)));
-        const int e_max = 64 / p.mt;                                 // accumulators per lane <= 64
-        p.vb = std::min(16, e_max * lb);
-        p.row_tiles = 1;
-        p.col_tiles = cdiv(ncols, 64LL * (p.vb / lb));
-        // enough workgroups for two per CU; every wave keeps at least one batch of rows; the partials (splits x m x ncols x 4 B)
-        // stay within a quarter of the index stream
-        s = std::min({cdiv(2LL * cus, p.col_tiles), kdim / (CB_WAVES * CB_UNROLL), kdim * lb / (16 * m)});
-    } else {
-        p.path = NNC_CBMM_TILED;
-        p.col_tiles = cdiv(ncols, TB_N);
-        p.row_tiles = cdiv(m, TB_M);
-        s = std::min({cdiv(2LL * cus, p.col_tiles * p.row_tiles), kdim / (16 * TB_K), 16LL});
-    }
-    s = std::max(1LL, s);
-    p.rows_per_split = cdiv(kdim, s);
-    p.splits = cdiv(kdim, p.rows_per_split);
-}
-
-static CbPlan cb_plan(long long m, long long kdim, long long ncols, int lb, int k, int cus, uintptr_t labels)
-{
-    CbPlan p{};
-    if (m == 0 || ncols == 0) return p;                              // NNC_CBMM_NONE: nothing to write
-    if (kdim == 0) {                                                 // y = bias (zeros without one), by k_cbmm_reduce
-        p.path = NNC_CBMM_BIAS;
-        return p;
-    }
-    cb_grid(p, m, kdim, ncols, lb, cus);
-    if (p.path == NNC_CBMM_STREAM) {
-        if (lb == 1) {
-            p.entries = 256;
-            p.cshift = __builtin_ctz(CB_U8_COPIES);
-        } else {
-            p.entries = k + 1;
-            while ((1 << p.cshift) < CB_U8_COPIES && (long long)p.entries << (p.cshift + 1) <= CB_U16_WORDS) ++p.cshift;
-        }
-        p.aligned = labels % p.vb == 0 && (ncols * lb) % p.vb == 0;
-        p.lds = ((long long)p.entries << p.cshift) * 4 + (long long)p.mt * (p.vb / lb) * 64 * 4 + (long long)p.entries * 4;
-    } else {
-        p.entries = k + 1;
-        p.lds = (long long)(TB_K * TB_M + TB_K * TB_N + k + 1) * 4;
-    }
-    return p;
-}
-
-static int64_t cb_ws_bytes(const CbPlan &p, long long m, long long ncols) { return p.splits > 1 ? (int64_t)p.splits * m * ncols * 4 : 0; }
-
-// ------------------------------------------------------------------ skinny: m <= 16
-// grid (col_tiles, splits), CB_THREADS threads.  `out` is y (splits == 1: + bias, ReLU here) or the partials [split][m][ncols].
-template <typename LT, int VB, int MT, bool ALIGNED>
-__global__ __launch_bounds__(CB_THREADS) void k_cbmm_stream(const float *__restrict__ x, int m, long long kdim, const unsigned char *__restrict__ labels,
-                                                            long long ncols, const float *__restrict__ centers, int k, int entries, int cshift,
-                                                            long long rows_per_split, const float *__restrict__ bias, int relu, int direct,
-                                                            float *__restrict__ out)
-{
-    constexpr int LB = sizeof(LT), E = VB / LB, N = VB / 4, PER = 32 / (8 * LB) /* labels per dword */;
-    extern __shared__ float smem[];
-    float *cb = smem;
-    float *red = smem + (entries << cshift);
-    float *stage = red + MT * E * 64;
-    cb_fill(cb, stage, centers, k, entries, cshift);
-
-    const int lane = threadIdx.x & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const long long c0 = (long long)blockIdx.x * (64 * E) + lane * E;
-    const bool active = c0 < ncols;
-    const long long s_lo = (long long)blockIdx.y * rows_per_split, s_hi = std::min(kdim, s_lo + rows_per_split);
-    const long long per_wave = (s_hi - s_lo + CB_WAVES - 1) / CB_WAVES;
-    const long long i0 = std::min(s_hi, s_lo + wave * per_wave), i1 = std::min(s_hi, i0 + per_wave);
-    const uintptr_t base = reinterpret_cast<uintptr_t>(labels);
-    const long long row_bytes = ncols * LB;
-    const long long lane_off = (long long)blockIdx.x * (64 * VB) + lane * VB;   // byte offset of the lane's window in its row
-
-    float acc[MT][E];
-#pragma unroll
-    for (int r = 0; r < MT; ++r)
-#pragma unroll
-        for (int e = 0; e < E; ++e) acc[r][e] = 0.0f;
-    __syncthreads();
-
-    auto row_words = [&](long long i, uint32_t *w, uint32_t &s) {
-        const uintptr_t row = base + (uintptr_t)(i * row_bytes);
-        if constexpr (ALIGNED) {
-            s = 0;
-            load_chunk<VB>(reinterpret_cast<const unsigned char *>(active ? row + lane_off : row), w);
-        } else {
-            const uintptr_t first = row & ~(uintptr_t)(VB - 1);          // the chunk that holds the row's first byte
-            s = (uint32_t)(__builtin_amdgcn_readfirstlane((uint32_t)((row + blockIdx.x * (64 * VB)) & (VB - 1))));
-            const uintptr_t a = ((row + lane_off) & ~(uintptr_t)(VB - 1));
-            const uintptr_t a0 = active ? a : first;
-            const uintptr_t a1 = (active && a + VB < row + row_bytes) ? a + VB : a0;
-            load_chunk<VB>(reinterpret_cast<const unsigned char *>(a0), w);
-            load_chunk<VB>(reinterpret_cast<const unsigned char *>(a1), w + N);
-        }
-    };
-    // x[r, i + u] of a batch of U rows: lane f holds value f = r * U + u (and f + 64), broadcast by v_readlane.  Vector loads
-    // keep the x reads off the LGKM counter that every LDS lookup waits on.
-    auto load_x = [&](long long i, int U, float &xa, float &xb) {
-        const int f0 = lane, f1 = lane + 64;
-        const int r0 = f0 / U, r1 = f1 / U;
-        xa = r0 < m ? x[(long long)r0 * kdim + i + f0 % U] : 0.0f;
-        xb = (MT * CB_UNROLL > 64 && r1 < m) ? x[(long long)r1 * kdim + i + f1 % U] : 0.0f;
-    };
-    auto consume = [&](const uint32_t *w, uint32_t s, float xa, float xb, int u, int U) {
-        float xv[MT];
-#pragma unroll
-        for (int r = 0; r < MT; ++r) {
-            const int f = r * U + u;
-            xv[r] = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, f < 64 ? xa : xb), f & 63));
-        }
-        uint32_t o[N];
-        if constexpr (ALIGNED) {
-#pragma unroll
-            for (int d = 0; d < N; ++d) o[d] = w[d];
-        } else {
-            funnel<N>(w, s, o);
-        }
-#pragma unroll
-        for (int e = 0; e < E; ++e) {
-            const uint32_t l = (o[e / PER] >> (8 * LB * (e % PER))) & (LB == 1 ? 0xFFu : 0xFFFFu);
-            const float wv = cb[CbTable<LT>::index(l, k, cshift, lane)];
-#pragma unroll
-            for (int r = 0; r < MT; ++r) acc[r][e] = __builtin_fmaf(xv[r], wv, acc[r][e]);
-        }
-    };
-
-    constexpr int WN = ALIGNED ? N : 2 * N;
-    long long i = i0;
-    for (; i + CB_UNROLL <= i1; i += CB_UNROLL) {
-        uint32_t w[CB_UNROLL][WN], s[CB_UNROLL];
-        float xa, xb;
-#pragma unroll
-        for (int u = 0; u < CB_UNROLL; ++u) row_words(i + u, w[u], s[u]);
-        load_x(i, CB_UNROLL, xa, xb);
-#pragma unroll
-        for (int u = 0; u < CB_UNROLL; ++u) consume(w[u], s[u], xa, xb, u, CB_UNROLL);
-    }
-    for (; i < i1; ++i) {
-        uint32_t w[WN], s;
-        float xa, xb;
-        row_words(i, w, s);
-        load_x(i, 1, xa, xb);
-        consume(w, s, xa, xb, 0, 1);
-    }
-
-    // the waves' sums, added to wave 0's in wave order
-    for (int src = 1; src < CB_WAVES; ++src) {
-        __syncthreads();
-        if (wave == src) {
-#pragma unroll
-            for (int r = 0; r < MT; ++r)
-#pragma unroll
-                for (int e = 0; e < E; ++e) red[(r * E + e) * 64 + lane] = acc[r][e];
-        }
-        __syncthreads();
-        if (wave == 0) {
-#pragma unroll
-            for (int r = 0; r < MT; ++r)
-#pragma unroll
-                for (int e = 0; e < E; ++e) acc[r][e] += red[(r * E + e) * 64 + lane];
-        }
-    }
-    if (wave != 0 || !active) return;
-#pragma unroll
-    for (int r = 0; r < MT; ++r) {
-#pragma unroll
-        for (int e = 0; e < E; ++e) {
-            const long long c = c0 + e;
-            if (r >= m || c >= ncols) continue;
-            float v = acc[r][e];
-            if (direct) {
-                if (bias) v += bias[c];
-                if (relu) v = v < 0.0f ? 0.0f : v;   // NaN stays NaN, as torch.relu
-                out[(long long)r * ncols + c] = v;
-            } else {
-                out[((long long)blockIdx.y * m + r) * ncols + c] = v;
-            }
-        }
-    }
-}
 
 // ------------------------------------------------------------------ tiled: m > 16
 // grid (col_tiles * row_tiles, splits), 256 threads; thread (tx, ty) = (t % 16, t / 16) owns rows ty*8.. and columns tx*8.. of
@@ -287,9 +87,11 @@ __global__ __launch_bounds__(256) void k_cbmm_tiled(const float *__restrict__ x,
 // ------------------------------------------------------------------ split-K combine
 // y = ((q0 + q1) + q2) + q3 + bias, q = the in-order sum of a quarter of the splits: 64 outputs per workgroup, a quarter per wave
 // (one thread per output summing all splits serially was 25-37 us at m = 1 with ~100 splits).  The order depends on `splits` only.
+// OT = float, or bf16_t / f16_t for nnc_cbmm_h16: the float32 value rounded once.
 #define RED_Q 4
+template <typename OT>
 __global__ __launch_bounds__(256) void k_cbmm_reduce(const float *__restrict__ part, long long splits, long long mn, long long ncols,
-                                                     const float *__restrict__ bias, int relu, float *__restrict__ y)
+                                                     const float *__restrict__ bias, int relu, OT *__restrict__ y)
 {
     __shared__ float qs[RED_Q - 1][64];
     const int o = threadIdx.x & 63, q = threadIdx.x >> 6;
@@ -310,17 +112,29 @@ __global__ __launch_bounds__(256) void k_cbmm_reduce(const float *__restrict__ p
             for (int j = 0; j < RED_Q - 1; ++j) v += qs[j][o];
             if (bias) v += bias[idx % ncols];
             if (relu) v = v < 0.0f ? 0.0f : v;   // NaN stays NaN, as torch.relu
-            y[idx] = v;
+            y[idx] = (OT)v;
         }
     }
 }
 
-int cbmm_reduce(const float *part, long long splits, long long mn, long long ncols, const float *bias, int relu, float *y, hipStream_t s)
+int cbmm_reduce_dt(const float *part, long long splits, long long mn, long long ncols, const float *bias, int relu, void *y, int y_dtype, hipStream_t s)
 {
     const int rgrid = (int)std::max(1LL, std::min(cdiv(mn, 64), 8192LL));
-    hipLaunchKernelGGL(k_cbmm_reduce, dim3(rgrid), dim3(256), 0, s, part, splits, mn, ncols, bias, relu, y);
+    if (y_dtype == NNC_DT_F32)
+        hipLaunchKernelGGL(k_cbmm_reduce<float>, dim3(rgrid), dim3(256), 0, s, part, splits, mn, ncols, bias, relu, reinterpret_cast<float *>(y));
+    else if (y_dtype == NNC_DT_BF16)
+        hipLaunchKernelGGL(k_cbmm_reduce<bf16_t>, dim3(rgrid), dim3(256), 0, s, part, splits, mn, ncols, bias, relu, reinterpret_cast<bf16_t *>(y));
+    else if (y_dtype == NNC_DT_F16)
+        hipLaunchKernelGGL(k_cbmm_reduce<f16_t>, dim3(rgrid), dim3(256), 0, s, part, splits, mn, ncols, bias, relu, reinterpret_cast<f16_t *>(y));
+    else
+        return fail(NNC_EINVAL, "k_cbmm_reduce: no instantiation for output dtype " + std::to_string(y_dtype));
     LAUNCHCHK("k_cbmm_reduce");
     return NNC_OK;
+}
+
+int cbmm_reduce(const float *part, long long splits, long long mn, long long ncols, const float *bias, int relu, float *y, hipStream_t s)
+{
+    return cbmm_reduce_dt(part, splits, mn, ncols, bias, relu, y, NNC_DT_F32, s);
 }
 
 // ------------------------------------------------------------------ C ABI
@@ -346,9 +160,9 @@ static void launch_stream(bool aligned, dim3 grid, size_t lds, hipStream_t s, co
 {
     const unsigned char *lab = reinterpret_cast<const unsigned char *>(labels);
     if (aligned)
-        hipLaunchKernelGGL((k_cbmm_stream<LT, VB, MT, true>), grid, dim3(CB_THREADS), lds, s, x, m, kdim, lab, ncols, centers, k, entries, cshift, rps, bias, relu, direct, out);
+        hipLaunchKernelGGL((k_cbmm_stream<float, LT, VB, MT, true>), grid, dim3(CB_THREADS), lds, s, x, m, kdim, lab, ncols, centers, k, entries, cshift, rps, bias, relu, direct, out);
     else
-        hipLaunchKernelGGL((k_cbmm_stream<LT, VB, MT, false>), grid, dim3(CB_THREADS), lds, s, x, m, kdim, lab, ncols, centers, k, entries, cshift, rps, bias, relu, direct, out);
+        hipLaunchKernelGGL((k_cbmm_stream<float, LT, VB, MT, false>), grid, dim3(CB_THREADS), lds, s, x, m, kdim, lab, ncols, centers, k, entries, cshift, rps, bias, relu, direct, out);
 }
 
 // every k_cbmm_stream instantiation there is; the plan is checked against this table, and the launch goes through it

@@ -1,9 +1,11 @@
 // nnc_cbmm.hpp -- what the codebook matmul (nnc_cbmm.hip), its bitmap-sparse sibling (nnc_cbsp.hip) and its backward pass
 // (nnc_cbgrad.hip) share: the launch constants, the per-bank LDS codebook layout, the label-row loads of the stream kernels and the
 // register-blocked FMA step of the tiled kernels.  The 2- and 4-bit packed form (nnc_cbpk.hip) takes cb_fill, tb_tile_fma and
-// the split-K combine from here.
+// the split-K combine from here.  The plan (cb_plan) and the stream kernel k_cbmm_stream itself live here too, templated on the
+// type of x: nnc_cbmm.hip instantiates them for float32, nnc_cbmm_h16.hip for bf16 / fp16 activations.
 #pragma once
 #include "nnc_common.hpp"
+#include <type_traits>
 
 #define CB_WAVES 4
 #define CB_THREADS (CB_WAVES * WAVE)
@@ -16,11 +18,102 @@
 #define TB_N 128
 #define TB_K 8
 
+using bf16_t = __bf16;      // the 2-byte activation types of nnc_cbmm_h16 (NNC_DT_BF16, NNC_DT_F16)
+using f16_t = _Float16;
+
+#define HM_BM 128                 // k_cbmm_mfma (nnc_cbmm_h16.hip): the output tile of a workgroup,
+#define HM_BN 128
+#define HM_BK 32                  // its k step,
+#define HM_LD 40                  // and the 2-byte elements per row of its LDS images: HM_BK of k and 16 bytes of padding
+
 static inline long long cdiv(long long a, long long b) { return (a + b - 1) / b; }
+// k_cbmm_mfma's table and its staging row, in float32 words, rounded up so that the images behind them start on 16 bytes
+__host__ __device__ static inline int hm_table_words(int entries, int cshift) { return ((entries << cshift) + entries + 3) & ~3; }
 
 // y[idx] = the split-K partials part[s][idx], s < splits, summed in an order that depends on `splits` alone, + bias[idx % ncols],
 // ReLU (k_cbmm_reduce, nnc_cbmm.hip; splits = 0: y = bias or 0), launched on `s`: NNC_OK or the launch error
 int cbmm_reduce(const float *part, long long splits, long long mn, long long ncols, const float *bias, int relu, float *y, hipStream_t s);
+// the same sums written as y_dtype (NNC_DT_*): float32, or bf16 / fp16 with one rounding to nearest even of the float32 value
+int cbmm_reduce_dt(const float *part, long long splits, long long mn, long long ncols, const float *bias, int relu, void *y, int y_dtype, hipStream_t s);
+
+// ------------------------------------------------------------------ the plan (host)
+// Every decision nnc_cbmm_f32 (and nnc_cbmm_h16, `mfma`: its m > 16 kernel is k_cbmm_mfma, nnc_cbmm_h16.hip) takes before it
+// launches: which kernel, its instantiation, the LDS table, the grid and the K splits.  nnc_cbmm_plan / nnc_cbmm_h16_plan report
+// it (include/nnc.h), so the tests can see which regime a call hits.
+struct CbPlan {
+    int path;                // NNC_CBMM_NONE / _STREAM / _TILED / _BIAS / _MFMA
+    int vb, mt;              // stream: bytes per lane per row, rows of x per launch (a power of two >= m)
+    int entries, cshift;     // the LDS codebook: entries (centres, then zeros) x (1 << cshift) copies
+    int aligned;             // stream: every label row starts on a VB-byte boundary (no funnel shift)
+    long long col_tiles, row_tiles;
+    long long splits, rows_per_split;
+    long long lds;           // dynamic LDS bytes of the main kernel
+};
+
+// the splits and tiles (m >= 1, kdim >= 1, ncols >= 1)
+static inline void cb_grid(CbPlan &p, long long m, long long kdim, long long ncols, int lb, int cus, bool mfma)
+{
+    cus = std::max(1, std::min(cus, CB_PLAN_CUS));
+    long long s;
+    if (m <= CB_SKINNY_M) {
+        p.path = NNC_CBMM_STREAM;
+        p.mt = m <= 1 ? 1 : (m <= 2 ? 2 : (m <= 4 ? 4 : (m <= 8 ? 8 : 16)));
+        const int e_max = 64 / p.mt;                                 // accumulators per lane <= 64
+        p.vb = std::min(16, e_max * lb);
+        p.row_tiles = 1;
+        p.col_tiles = cdiv(ncols, 64LL * (p.vb / lb));
+        // enough workgroups for two per CU; every wave keeps at least one batch of rows; the partials (splits x m x ncols x 4 B)
+        // stay within a quarter of the index stream
+        s = std::min({cdiv(2LL * cus, p.col_tiles), kdim / (CB_WAVES * CB_UNROLL), kdim * lb / (16 * m)});
+    } else if (mfma) {
+        p.path = NNC_CBMM_MFMA;
+        p.col_tiles = cdiv(ncols, HM_BN);
+        p.row_tiles = cdiv(m, HM_BM);
+        // two workgroups per CU; every split keeps at least two HM_BK steps
+        s = std::min({cdiv(2LL * cus, p.col_tiles * p.row_tiles), kdim / (2 * HM_BK), 16LL});
+    } else {
+        p.path = NNC_CBMM_TILED;
+        p.col_tiles = cdiv(ncols, TB_N);
+        p.row_tiles = cdiv(m, TB_M);
+        s = std::min({cdiv(2LL * cus, p.col_tiles * p.row_tiles), kdim / (16 * TB_K), 16LL});
+    }
+    s = std::max(1LL, s);
+    p.rows_per_split = cdiv(kdim, s);
+    if (p.path == NNC_CBMM_MFMA) p.rows_per_split = cdiv(p.rows_per_split, HM_BK) * HM_BK;   // every split starts on a whole k step
+    p.splits = cdiv(kdim, p.rows_per_split);
+}
+
+static inline CbPlan cb_plan(long long m, long long kdim, long long ncols, int lb, int k, int cus, uintptr_t labels, bool mfma = false)
+{
+    CbPlan p{};
+    if (m == 0 || ncols == 0) return p;                              // NNC_CBMM_NONE: nothing to write
+    if (kdim == 0) {                                                 // y = bias (zeros without one), by k_cbmm_reduce
+        p.path = NNC_CBMM_BIAS;
+        return p;
+    }
+    cb_grid(p, m, kdim, ncols, lb, cus, mfma);
+    if (p.path != NNC_CBMM_TILED) {   // the per-bank table of the stream kernels; k_cbmm_mfma looks its W tile up in the same one
+        if (lb == 1) {
+            p.entries = 256;
+            p.cshift = __builtin_ctz(CB_U8_COPIES);
+        } else {
+            p.entries = k + 1;
+            while ((1 << p.cshift) < CB_U8_COPIES && (long long)p.entries << (p.cshift + 1) <= CB_U16_WORDS) ++p.cshift;
+        }
+        if (p.path == NNC_CBMM_MFMA) {
+            p.lds = (long long)hm_table_words(p.entries, p.cshift) * 4 + (long long)(HM_BM + HM_BN) * HM_LD * 2;
+        } else {
+            p.aligned = labels % p.vb == 0 && (ncols * lb) % p.vb == 0;
+            p.lds = ((long long)p.entries << p.cshift) * 4 + (long long)p.mt * (p.vb / lb) * 64 * 4 + (long long)p.entries * 4;
+        }
+    } else {
+        p.entries = k + 1;
+        p.lds = (long long)(TB_K * TB_M + TB_K * TB_N + k + 1) * 4;
+    }
+    return p;
+}
+
+static inline int64_t cb_ws_bytes(const CbPlan &p, long long m, long long ncols) { return p.splits > 1 ? (int64_t)p.splits * m * ncols * 4 : 0; }
 
 // the per-bank table: entry j of lane l at word j * copies + (l mod copies), copies = 1 << cshift
 template <typename LT> struct CbTable;
@@ -56,9 +149,11 @@ __device__ __forceinline__ void tb_tile_fma(const float *xs, const float *ws, in
 // the table: `entries` values (centers, then zeros), `1 << cshift` copies of each, copy c of entry j at j * copies + c.  The
 // centres come from global memory once per workgroup into `stage`; the copies are made from LDS (a loop of global loads per copy
 // was a chain of L2 round trips in front of every workgroup).
+// RT = bf16_t / f16_t: every centre rounded to RT (to nearest even, as torch's .to(dtype)) and widened back.
+template <typename RT = float>
 __device__ __forceinline__ void cb_fill(float *cb, float *stage, const float *__restrict__ centers, int k, int entries, int cshift)
 {
-    for (int j = threadIdx.x; j < entries; j += blockDim.x) stage[j] = j < k ? centers[j] : 0.0f;
+    for (int j = threadIdx.x; j < entries; j += blockDim.x) stage[j] = j < k ? (float)(RT)centers[j] : 0.0f;
     __syncthreads();
     const int words = entries << cshift;
 #pragma unroll 8
@@ -92,4 +187,145 @@ __device__ __forceinline__ void funnel(const uint32_t *w, uint32_t s, uint32_t *
     }
 #pragma unroll
     for (int d = 0; d < N; ++d) o[d] = __builtin_amdgcn_alignbyte(v[d + 1], v[d], r);
+}
+
+// ------------------------------------------------------------------ skinny: m <= 16
+// grid (col_tiles, splits), CB_THREADS threads.  `out` is y (direct != 0: + bias, ReLU here) or the float32 partials
+// [split][m][ncols].  XT = float is nnc_cbmm_f32's kernel (nnc_cbmm.hip).  XT = bf16_t / f16_t is nnc_cbmm_h16's (nnc_cbmm_h16.hip):
+// x is read as XT and widened (exact), the table holds the centres rounded to XT and widened, the arithmetic is the same float32
+// fmaf chain, and direct = 2 stores y as XT (one rounding) where direct = 1 stores float32.
+template <typename XT, typename LT, int VB, int MT, bool ALIGNED>
+__global__ __launch_bounds__(CB_THREADS) void k_cbmm_stream(const XT *__restrict__ x, int m, long long kdim, const unsigned char *__restrict__ labels,
+                                                            long long ncols, const float *__restrict__ centers, int k, int entries, int cshift,
+                                                            long long rows_per_split, const float *__restrict__ bias, int relu, int direct,
+                                                            void *__restrict__ out_)
+{
+    constexpr int LB = sizeof(LT), E = VB / LB, N = VB / 4, PER = 32 / (8 * LB) /* labels per dword */;
+    extern __shared__ float smem[];
+    float *cb = smem;
+    float *red = smem + (entries << cshift);
+    float *stage = red + MT * E * 64;
+    float *out = reinterpret_cast<float *>(out_);
+    cb_fill<XT>(cb, stage, centers, k, entries, cshift);
+
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const long long c0 = (long long)blockIdx.x * (64 * E) + lane * E;
+    const bool active = c0 < ncols;
+    const long long s_lo = (long long)blockIdx.y * rows_per_split, s_hi = std::min(kdim, s_lo + rows_per_split);
+    const long long per_wave = (s_hi - s_lo + CB_WAVES - 1) / CB_WAVES;
+    const long long i0 = std::min(s_hi, s_lo + wave * per_wave), i1 = std::min(s_hi, i0 + per_wave);
+    const uintptr_t base = reinterpret_cast<uintptr_t>(labels);
+    const long long row_bytes = ncols * LB;
+    const long long lane_off = (long long)blockIdx.x * (64 * VB) + lane * VB;   // byte offset of the lane's window in its row
+
+    float acc[MT][E];
+#pragma unroll
+    for (int r = 0; r < MT; ++r)
+#pragma unroll
+        for (int e = 0; e < E; ++e) acc[r][e] = 0.0f;
+    __syncthreads();
+
+    auto row_words = [&](long long i, uint32_t *w, uint32_t &s) {
+        const uintptr_t row = base + (uintptr_t)(i * row_bytes);
+        if constexpr (ALIGNED) {
+            s = 0;
+            load_chunk<VB>(reinterpret_cast<const unsigned char *>(active ? row + lane_off : row), w);
+        } else {
+            const uintptr_t first = row & ~(uintptr_t)(VB - 1);          // the chunk that holds the row's first byte
+            s = (uint32_t)(__builtin_amdgcn_readfirstlane((uint32_t)((row + blockIdx.x * (64 * VB)) & (VB - 1))));
+            const uintptr_t a = ((row + lane_off) & ~(uintptr_t)(VB - 1));
+            const uintptr_t a0 = active ? a : first;
+            const uintptr_t a1 = (active && a + VB < row + row_bytes) ? a + VB : a0;
+            load_chunk<VB>(reinterpret_cast<const unsigned char *>(a0), w);
+            load_chunk<VB>(reinterpret_cast<const unsigned char *>(a1), w + N);
+        }
+    };
+    // x[r, i + u] of a batch of U rows: lane f holds value f = r * U + u (and f + 64), broadcast by v_readlane.  Vector loads
+    // keep the x reads off the LGKM counter that every LDS lookup waits on.
+    auto load_x = [&](long long i, int U, float &xa, float &xb) {
+        const int f0 = lane, f1 = lane + 64;
+        const int r0 = f0 / U, r1 = f1 / U;
+        xa = r0 < m ? (float)x[(long long)r0 * kdim + i + f0 % U] : 0.0f;
+        xb = (MT * CB_UNROLL > 64 && r1 < m) ? (float)x[(long long)r1 * kdim + i + f1 % U] : 0.0f;
+    };
+    auto consume = [&](const uint32_t *w, uint32_t s, float xa, float xb, int u, int U) {
+        float xv[MT];
+#pragma unroll
+        for (int r = 0; r < MT; ++r) {
+            const int f = r * U + u;
+            xv[r] = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, f < 64 ? xa : xb), f & 63));
+        }
+        uint32_t o[N];
+        if constexpr (ALIGNED) {
+#pragma unroll
+            for (int d = 0; d < N; ++d) o[d] = w[d];
+        } else {
+            funnel<N>(w, s, o);
+        }
+#pragma unroll
+        for (int e = 0; e < E; ++e) {
+            const uint32_t l = (o[e / PER] >> (8 * LB * (e % PER))) & (LB == 1 ? 0xFFu : 0xFFFFu);
+            const float wv = cb[CbTable<LT>::index(l, k, cshift, lane)];
+#pragma unroll
+            for (int r = 0; r < MT; ++r) acc[r][e] = __builtin_fmaf(xv[r], wv, acc[r][e]);
+        }
+    };
+
+    constexpr int WN = ALIGNED ? N : 2 * N;
+    long long i = i0;
+    for (; i + CB_UNROLL <= i1; i += CB_UNROLL) {
+        uint32_t w[CB_UNROLL][WN], s[CB_UNROLL];
+        float xa, xb;
+#pragma unroll
+        for (int u = 0; u < CB_UNROLL; ++u) row_words(i + u, w[u], s[u]);
+        load_x(i, CB_UNROLL, xa, xb);
+#pragma unroll
+        for (int u = 0; u < CB_UNROLL; ++u) consume(w[u], s[u], xa, xb, u, CB_UNROLL);
+    }
+    for (; i < i1; ++i) {
+        uint32_t w[WN], s;
+        float xa, xb;
+        row_words(i, w, s);
+        load_x(i, 1, xa, xb);
+        consume(w, s, xa, xb, 0, 1);
+    }
+
+    // the waves' sums, added to wave 0's in wave order
+    for (int src = 1; src < CB_WAVES; ++src) {
+        __syncthreads();
+        if (wave == src) {
+#pragma unroll
+            for (int r = 0; r < MT; ++r)
+#pragma unroll
+                for (int e = 0; e < E; ++e) red[(r * E + e) * 64 + lane] = acc[r][e];
+        }
+        __syncthreads();
+        if (wave == 0) {
+#pragma unroll
+            for (int r = 0; r < MT; ++r)
+#pragma unroll
+                for (int e = 0; e < E; ++e) acc[r][e] += red[(r * E + e) * 64 + lane];
+        }
+    }
+    if (wave != 0 || !active) return;
+#pragma unroll
+    for (int r = 0; r < MT; ++r) {
+#pragma unroll
+        for (int e = 0; e < E; ++e) {
+            const long long c = c0 + e;
+            if (r >= m || c >= ncols) continue;
+            float v = acc[r][e];
+            if (direct) {
+                if (bias) v += bias[c];
+                if (relu) v = v < 0.0f ? 0.0f : v;   // NaN stays NaN, as torch.relu
+                if (!std::is_same<XT, float>::value && direct == 2)
+                    reinterpret_cast<XT *>(out_)[(long long)r * ncols + c] = (XT)v;
+                else
+                    out[(long long)r * ncols + c] = v;
+            } else {
+                out[((long long)blockIdx.y * m + r) * ncols + c] = v;
+            }
+        }
+    }
 }

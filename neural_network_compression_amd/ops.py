@@ -26,6 +26,13 @@ def _require_cuda(t: torch.Tensor, name: str, dtype=None):
         raise ValueError(f"{name} must be contiguous")
 
 
+def _require_f32_x(x, who: str):
+    """The entry points that have no half-precision kernels: a bfloat16 / float16 x names the one form that has."""
+    if isinstance(x, torch.Tensor) and x.dtype in (torch.bfloat16, torch.float16):
+        raise TypeError(f"{who} takes float32 activations, got {x.dtype}: bfloat16 and float16 inputs run on the byte form only "
+                        "(ops.codebook_matmul, CompressedDense / CompressedConv2D), inference only")
+
+
 def _stream(t: torch.Tensor) -> int:
     return torch.cuda.current_stream(t.device).cuda_stream
 
@@ -288,13 +295,28 @@ def gather(centers: torch.Tensor, labels: torch.Tensor) -> torch.Tensor:
     return out
 
 
+_H16_DT = {torch.bfloat16: nat.DT_BF16, torch.float16: nat.DT_F16}   # the half activation types of nnc_cbmm_h16
+
+
 def codebook_matmul(x: torch.Tensor, labels: torch.Tensor, centers: torch.Tensor, kdim: int, ncols: int,
-                    bias: torch.Tensor | None = None, relu: bool = False) -> torch.Tensor:
+                    bias: torch.Tensor | None = None, relu: bool = False, out_dtype=None) -> torch.Tensor:
     """y = x @ W + bias (then ReLU) with W[i, o] = centers[labels[i * ncols + o]] read from the indices, never decoded to float32
     (include/nnc.h, nnc_cbmm_f32).  x: float32 (..., kdim); labels: the kdim * ncols uint8 / 16-bit indices (QuantizedModel.
     labels_compact_, any storage offset); centers: float32[K]; bias: float32[ncols] or None.  Returns float32 (..., ncols).
+    A bfloat16 or float16 x takes nnc_cbmm_h16: centers and bias stay float32, every centre is rounded to
+    x's dtype as ``centers.to(x.dtype)`` does, the products are exact and the sums float32; the result has ``out_dtype``: None
+    (x's dtype, the float32 value rounded once) or torch.float32.  A float32 x takes no ``out_dtype`` but None or torch.float32.
     Inference only: with autograd recording a tensor that needs a gradient it raises instead of returning a result without one."""
-    _require_cuda(x, "x", torch.float32)
+    if isinstance(x, torch.Tensor) and x.dtype in _H16_DT:
+        _require_cuda(x, "x")
+        if out_dtype not in (None, torch.float32):
+            raise TypeError(f"out_dtype must be None ({x.dtype}) or torch.float32 for x of {x.dtype}, got {out_dtype}")
+        y_dtype = x.dtype if out_dtype is None else out_dtype
+    else:
+        _require_cuda(x, "x", torch.float32)
+        if out_dtype not in (None, torch.float32):
+            raise TypeError(f"out_dtype must be None or torch.float32 for a float32 x, got {out_dtype}")
+        y_dtype = torch.float32
     _require_cuda(labels, "labels")
     _require_cuda(centers, "centers", torch.float32)
     if bias is not None:
@@ -314,8 +336,14 @@ def codebook_matmul(x: torch.Tensor, labels: torch.Tensor, centers: torch.Tensor
     L = nat.load()
     lead = tuple(x.shape[:-1])
     m = int(np.prod(lead)) if lead else 1
-    y = torch.empty(lead + (ncols,), dtype=torch.float32, device=x.device)
+    y = torch.empty(lead + (ncols,), dtype=y_dtype, device=x.device)
     lb = _label_bytes(labels)
+    if x.dtype in _H16_DT:
+        ws_bytes = int(L.nnc_cbmm_h16_workspace_bytes(m, kdim, ncols, lb))
+        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=x.device) if ws_bytes else None
+        nat.check(L.nnc_cbmm_h16(_ptr(x), _H16_DT[x.dtype], m, kdim, _ptr(labels), lb, ncols, _ptr(centers), centers.numel(), _ptr(bias),
+                                 1 if relu else 0, _ptr(y), _H16_DT.get(y_dtype, nat.DT_F32), _ptr(ws), ws_bytes, _stream(x)))
+        return y
     ws_bytes = int(L.nnc_cbmm_workspace_bytes(m, kdim, ncols, lb))
     ws = torch.empty(ws_bytes, dtype=torch.uint8, device=x.device) if ws_bytes else None
     nat.check(L.nnc_cbmm_f32(_ptr(x), m, kdim, _ptr(labels), lb, ncols, _ptr(centers), centers.numel(), _ptr(bias), 1 if relu else 0,
@@ -330,6 +358,17 @@ def cbmm_plan(m: int, kdim: int, ncols: int, label_bytes: int, k: int, cus: int,
     out = (ctypes.c_int64 * nat.CBMM_PLAN_LEN)()
     nat.check(L.nnc_cbmm_plan(int(m), int(kdim), int(ncols), int(label_bytes), int(k), int(cus), int(labels_addr), out))
     return dict(zip(nat.CBMM_PLAN_FIELDS, (int(v) for v in out)))
+
+
+def cbmm_h16_plan(dtype, m: int, kdim: int, ncols: int, label_bytes: int, k: int, cus: int, labels_addr: int = 0) -> dict:
+    """Host: the plan nnc_cbmm_h16 follows for x of ``dtype`` (torch.bfloat16 / torch.float16) on a device with ``cus`` compute
+    units (include/nnc.h, nnc_cbmm_h16_plan), as a dict keyed by _native.CBMM_H16_PLAN_FIELDS.  No device needed."""
+    if dtype not in _H16_DT:
+        raise TypeError(f"dtype must be torch.bfloat16 or torch.float16, got {dtype}")
+    L = nat.load()
+    out = (ctypes.c_int64 * nat.CBMM_H16_PLAN_LEN)()
+    nat.check(L.nnc_cbmm_h16_plan(_H16_DT[dtype], int(m), int(kdim), int(ncols), int(label_bytes), int(k), int(cus), int(labels_addr), out))
+    return dict(zip(nat.CBMM_H16_PLAN_FIELDS, (int(v) for v in out)))
 
 
 def _grad_args(g: torch.Tensor, labels: torch.Tensor, kdim: int, ncols: int, k: int):
@@ -460,6 +499,7 @@ def codebook_linear(x: torch.Tensor, labels: torch.Tensor, centers: torch.Tensor
     (under no_grad the bits of codebook_matmul); the backward runs codebook_matmul_dx only if x needs a gradient and
     codebook_centroid_grad (float32) only if centers does, masks a fused ReLU as torch does and sums the bias gradient over the
     rows.  The indices get no gradient.  No host read."""
+    _require_f32_x(x, "codebook_linear")
     return _CodebookLinear.apply(x, labels, centers, int(kdim), int(ncols), bias, bool(relu))
 
 
@@ -541,6 +581,7 @@ def sparse_codebook_matmul(x: torch.Tensor, codes: SparseCodes, centers: torch.T
     centers[labels[i, o]] read from the bitmap-sparse form (include/nnc.h, nnc_cbsp_f32).  With centers[zero_symbol] == 0 the
     skipped weights are absent (an Inf in x meets no 0).  x: float32 (..., kdim); centers: float32[codes.k]; bias: float32[ncols]
     or None.  Returns float32 (..., ncols).  Inference only, as codebook_matmul."""
+    _require_f32_x(x, "sparse_codebook_matmul")
     _require_cuda(x, "x", torch.float32)
     _require_cuda(centers, "centers", torch.float32)
     if bias is not None:
@@ -686,6 +727,7 @@ def sparse_codebook_linear(x: torch.Tensor, codes: SparseCodes, centers: torch.T
     fused ReLU as torch does and sums the bias gradient over the rows.  The indices get no gradient.  No host read."""
     if not isinstance(codes, SparseCodes):
         raise TypeError("codes must be a SparseCodes (ops.pack_sparse_codes)")
+    _require_f32_x(x, "sparse_codebook_linear")
     return _SparseCodebookLinear.apply(x, codes, centers, bias, bool(relu))
 
 
@@ -769,6 +811,7 @@ def packed_codebook_matmul(x: torch.Tensor, codes: PackedCodes, centers: torch.T
     """y = x @ W + bias (then ReLU) with W[i, o] = centers[label (i, o)] read from the 2- or 4-bit packed indices (include/nnc.h,
     nnc_cbpk_f32): codebook_matmul on the unpacked labels, from a half or a quarter of the index bytes.  x: float32 (..., kdim);
     centers: float32[codes.k]; bias: float32[ncols] or None.  Returns float32 (..., ncols).  Inference only, as codebook_matmul."""
+    _require_f32_x(x, "packed_codebook_matmul")
     _require_cuda(x, "x", torch.float32)
     _require_cuda(centers, "centers", torch.float32)
     if bias is not None:
@@ -914,6 +957,7 @@ def packed_codebook_linear(x: torch.Tensor, codes: PackedCodes, centers: torch.T
     fused ReLU as torch does and sums the bias gradient over the rows.  The indices get no gradient.  No host read."""
     if not isinstance(codes, PackedCodes):
         raise TypeError("codes must be a PackedCodes (ops.pack_codes)")
+    _require_f32_x(x, "packed_codebook_linear")
     return _PackedCodebookLinear.apply(x, codes, centers, bias, bool(relu))
 
 
