@@ -615,6 +615,38 @@ int nnc_cbmm_h16(const void *x, int x_dtype, int64_t m, int64_t kdim, const void
                  int32_t k, const float *bias_dev, int32_t relu, void *y, int y_dtype, void *workspace, int64_t workspace_bytes, void *stream);
 
 /* ------------------------------------------------------------------------------------
+ * The same layer with one codebook per block of input rows (csrc/nnc_cbmm_grouped.hip):
+ *     y = x @ W + bias (then ReLU),   W[i, o] = centers_dev[i / group_rows][labels[i * ncols + o]]
+ * centers_dev  float32[G][k], contiguous, G = ceil(kdim / group_rows), 1 <= k <= 256.
+ * labels       the kdim * ncols uint8 indices, row-major (kdim, ncols), on any storage offset.  There is no 2-byte form: a group
+ *              holds group_rows * ncols weights and group codebooks are for small k, so k > 256 is NNC_EINVAL.
+ * group_rows   a positive multiple of 32 (anything else is NNC_EINVAL); the last group may be short; group_rows >= kdim is one
+ *              group, and the result then equals nnc_cbmm_f32 / nnc_cbmm_h16 bit for bit.
+ * x            x_dtype = NNC_DT_F32, NNC_DT_BF16 or NNC_DT_F16, aligned to its element size.  Half x follows nnc_cbmm_h16: every
+ *              centre is rounded to the dtype, the products are exact, the sums are float32, y_dtype is NNC_DT_F32 or x_dtype (one
+ *              rounding).  A float32 x takes y_dtype = NNC_DT_F32 only.
+ * Everything else is nnc_cbmm_f32's contract: an index >= k reads 0; split-K partials are float32 in the workspace and are summed
+ * in split order by k_cbmm_reduce; no float atomics, the same call gives the same bits; ReLU keeps NaN; m or ncols = 0 is a no-op;
+ * kdim = 0 writes y = bias (or 0); argument errors come back before any HIP call.
+ * The plan is the ungrouped one: PATH, VB, MT, COL_TILES, ROW_TILES, SPLITS and RPS are what nnc_cbmm_plan (float32 x) or
+ * nnc_cbmm_h16_plan (half x) give for (m, kdim, ncols, label_bytes 1, k, cus), so the workspace keeps the ungrouped bound
+ * (nnc_cbmm_grouped_workspace_bytes is nnc_cbmm_workspace_bytes / nnc_cbmm_h16_workspace_bytes at label_bytes 1).  A workgroup walks
+ * through the groups inside its split and changes its LDS table on the way: k_cbmm_stream_grouped keeps its four waves inside one
+ * group at a time, k_cbmm_tiled_grouped holds two tables (COPIES = 2, LDS one table larger than nnc_cbmm_plan's) because a TB_K
+ * step can lie across a boundary, k_cbmm_mfma_grouped changes tables between k steps of 32.
+ * nnc_cbmm_grouped_plan writes NNC_CBMM_GROUPED_PLAN_LEN values: the NNC_CBMM_P_* fields, NNC_CBMM_H16_P_DTYPE, then GROUP_ROWS,
+ * GROUPS (G) and MAX_GROUPS_PER_SPLIT (the most groups the rows of one split lie in).
+ * ---------------------------------------------------------------------------------- */
+#define NNC_CBMM_GROUPED_P_GROUP_ROWS 13
+#define NNC_CBMM_GROUPED_P_GROUPS 14
+#define NNC_CBMM_GROUPED_P_MAX_GROUPS_PER_SPLIT 15
+#define NNC_CBMM_GROUPED_PLAN_LEN 16
+int64_t nnc_cbmm_grouped_workspace_bytes(int x_dtype, int64_t m, int64_t kdim, int64_t ncols);
+int nnc_cbmm_grouped_plan(int x_dtype, int64_t m, int64_t kdim, int64_t ncols, int32_t k, int64_t group_rows, int32_t cus, uint64_t labels_addr, int64_t *out);
+int nnc_cbmm_grouped(const void *x, int x_dtype, int64_t m, int64_t kdim, const void *labels, int64_t ncols, const float *centers_dev, int32_t k,
+                     int64_t group_rows, const float *bias_dev, int32_t relu, void *y, int y_dtype, void *workspace, int64_t workspace_bytes, void *stream);
+
+/* ------------------------------------------------------------------------------------
  * The backward pass of nnc_cbmm_f32 from the same codebook and indices, W never decoded (csrc/nnc_cbgrad.hip, DESIGN.md section
  * 12).  W[i, o] = centers[labels[i * ncols + o]] as above (same label widths, any storage offset); g = dL/dy float32[m, ncols].
  * nnc_cbmm_dx_f32   dx[m, kdim] = g @ W^T: dx[r, i] = sum_o g[r, o] * W[i, o].  m <= 16 streams the index rows (k_cbdx_stream: a

@@ -33,6 +33,8 @@ CBMM_MFMA = 5   # nnc_cbmm_h16_plan: m > 16 runs k_cbmm_mfma
 DT_F32, DT_BF16, DT_F16 = 0, 1, 2   # NNC_DT_*: the activation / output types of nnc_cbmm_h16
 CBMM_H16_PLAN_LEN = 13
 CBMM_H16_PLAN_FIELDS = CBMM_PLAN_FIELDS + ("dtype",)
+CBMM_GROUPED_PLAN_LEN = 16   # nnc_cbmm_grouped_plan: the h16 fields, then the groups
+CBMM_GROUPED_PLAN_FIELDS = CBMM_H16_PLAN_FIELDS + ("group_rows", "groups", "max_groups_per_split")
 CBDX_PLAN_LEN = 12
 CBDX_PLAN_FIELDS = ("path", "vb", "mt", "copies", "entries", "splits", "cps", "aligned", "lds", "col_tiles", "row_tiles", "workspace")
 CBDC_PLAN_LEN = 12
@@ -181,6 +183,10 @@ SIGNATURES = {
     "nnc_cbmm_h16_plan": (c_int, [c_int, c_i64, c_i64, c_i64, c_int, c_i32, c_i32, ctypes.c_uint64, ctypes.POINTER(c_i64)]),
     "nnc_cbmm_h16": (c_int, [c_void_p, c_int, c_i64, c_i64, c_void_p, c_int, c_i64, c_void_p, c_i32, c_void_p, c_i32, c_void_p, c_int, c_void_p, c_i64,
                              c_void_p]),
+    "nnc_cbmm_grouped_workspace_bytes": (c_i64, [c_int, c_i64, c_i64, c_i64]),
+    "nnc_cbmm_grouped_plan": (c_int, [c_int, c_i64, c_i64, c_i64, c_i32, c_i64, c_i32, ctypes.c_uint64, ctypes.POINTER(c_i64)]),
+    "nnc_cbmm_grouped": (c_int, [c_void_p, c_int, c_i64, c_i64, c_void_p, c_i64, c_void_p, c_i32, c_i64, c_void_p, c_i32, c_void_p, c_int, c_void_p, c_i64,
+                                 c_void_p]),
     "nnc_cbmm_dx_workspace_bytes": (c_i64, [c_i64, c_i64, c_i64, c_int]),
     "nnc_cbmm_dx_plan": (c_int, [c_i64, c_i64, c_i64, c_int, c_i32, c_i32, ctypes.c_uint64, ctypes.POINTER(c_i64)]),
     "nnc_cbmm_dx_f32": (c_int, [c_void_p, c_i64, c_i64, c_void_p, c_int, c_i64, c_void_p, c_i32, c_void_p, c_void_p, c_i64, c_void_p]),

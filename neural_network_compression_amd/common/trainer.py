@@ -82,12 +82,20 @@ class Trainer(ABC):
 
     # ------------------------------------------------------------------ the hot path
     def quantize(self, test_dataset: LeNetDataset, with_cumulative_weight_distribution: bool,
-                 maximum_centroid_bits: int, k_means_initialization_mode: str, *, arith: str = "auto", reloc: str = "auto") -> float:
+                 maximum_centroid_bits: int, k_means_initialization_mode: str, *, arith: str = "auto", reloc: str = "auto",
+                 group_rows: int | None = None) -> float:
         """The reference's signature (common/trainer.py:42-48) plus two keywords that select its own arithmetic where identity
         with it is wanted (utility.get_quantized_weight): ``arith="reference"`` = scikit-learn's float32 running sums in sample
         order on tensors of any length (centres, indices and n_iter_ then equal the reference's on one thread bit for bit; slower:
         a host round trip per Lloyd iteration beyond 4096 weights), ``reloc="reference"`` = numpy.argpartition's own choice of the
-        far samples at an empty-cluster event.  The defaults are the order-independent exact sums and the on-device selection."""
+        far samples at an empty-cluster event.  The defaults are the order-independent exact sums and the on-device selection.
+        ``group_rows`` (None: one codebook per tensor, as ever): every 2-D Dense kernel gets one codebook per block of that many
+        input rows (a positive multiple of 32; utility.get_quantized_weight_grouped): its model is a
+        utility.GroupedModel and compressed_network() runs it as a GroupedCompressedDense.  Conv2D kernels (their rows in unfold
+        order are not contiguous in the Keras kernel) and biases are fitted as without it.  A group too small for the number of
+        centroids, or more than 256 of them, is a ValueError before any fit."""
+        from ..neural_networks.layers import Dense
+
         self.quantized_models_by_layer = {}   # layer -> [fitted model or None per tensor]: what fine_tune_centroids needs
         layers = [layer for _layer_name, layer in self.neural_network.get_config().items()]
         # The tensors of the network are independent: where the init draws nothing from NumPy's global generator (linear,
@@ -97,6 +105,12 @@ class Trainer(ABC):
         # Everything else -- forgy / kmeans++ (global generator, in layer order), tensors too short for the number of centroids
         # (the reference's "not enough bits" pass-through), the error cases -- takes the reference's own sequence of calls.
         mode, bits = k_means_initialization_mode, maximum_centroid_bits
+        # (layer index, tensor index) -> the row ranges of the groups of a Dense kernel; checked for every kernel before the first fit
+        grouped = {}
+        if group_rows is not None:
+            for li, layer in enumerate(layers):
+                if isinstance(layer, Dense):
+                    grouped[(li, 0)] = utility.grouped_slices(tuple(layer.kernel.shape), group_rows, bits, mode)
         batched = {}
         if (arith, reloc) == ("auto", "auto") and mode in ("linear", "density") and (mode != "density" or with_cumulative_weight_distribution) and isinstance(bits, int) and 1 <= bits <= 10:
             from .. import pipeline
@@ -104,17 +118,32 @@ class Trainer(ABC):
             todo = [(li, ti, params) for li, layer in enumerate(layers) for ti, params in enumerate(layer.get_weights())
                     if isinstance(params, torch.Tensor) and params.is_cuda and params.dtype == torch.float32 and params.is_contiguous()
                     and params.numel() >= 2 ** bits + 1]
-            if todo:
-                res = pipeline.compress_layers([p.reshape(-1) for _, _, p in todo], workers=8, q=None, bits=bits, mode=mode,
-                                               with_cdf=(mode == "density"), huffman=True, want_values=True)
-                for (li, ti, p), r in zip(todo, res):
-                    batched[(li, ti)] = (r.values.view(p.shape), r.model)
+            # a grouped kernel goes in as its groups' slices (contiguous: the kernel is row-major), each a tensor of the batch
+            parts = []
+            for li, ti, p in todo:
+                parts += [p[lo:hi] for lo, hi in grouped[(li, ti)]] if (li, ti) in grouped else [p]
+            if parts:
+                res = iter(pipeline.compress_layers([p.reshape(-1) for p in parts], workers=8, q=None, bits=bits, mode=mode,
+                                                    with_cdf=(mode == "density"), huffman=True, want_values=True))
+                for li, ti, p in todo:
+                    if (li, ti) in grouped:
+                        rs = [next(res) for _ in grouped[(li, ti)]]
+                        batched[(li, ti)] = (torch.cat([r.values for r in rs]).view(p.shape), utility.GroupedModel(group_rows, [r.model for r in rs]))
+                    else:
+                        r = next(res)
+                        batched[(li, ti)] = (r.values.view(p.shape), r.model)
         for li, layer in enumerate(layers):
             quantized_weights_and_bias = []
             models = []
             for ti, params in enumerate(layer.get_weights()):
                 if (li, ti) in batched:
                     quantized, model = batched[(li, ti)]
+                elif (li, ti) in grouped:
+                    cdfs = None
+                    if with_cumulative_weight_distribution:
+                        cdfs = [utility.get_weight_distribution(params[lo:hi], skip_zeros=True) for lo, hi in grouped[(li, ti)]]
+                    quantized, model = utility.get_quantized_weight_grouped(params, group_rows, bits=bits, mode=mode, cdfs_by_group=cdfs,
+                                                                            arith=arith, reloc=reloc)
                 else:
                     cdfs = None
                     if with_cumulative_weight_distribution:
@@ -140,6 +169,9 @@ class Trainer(ABC):
         models = getattr(self, "quantized_models_by_layer", None)
         if not models:
             raise RuntimeError("fine_tune_centroids needs a quantized network: call quantize first")
+        for name, layer in self.neural_network.get_config().items():
+            if any(hasattr(m, "group_rows") for m in models.get(layer, [])):
+                raise NotImplementedError(f"layer {name!r} has group-wise codebooks (group_rows): fine_tune_centroids is not implemented for it")
         x = self._to_device(train_dataset.input_data).float()
         y = self._to_device(train_dataset.output_data).float()
         centers = {}
@@ -234,7 +266,9 @@ class Trainer(ABC):
         ``packed``: False, True (2- or 4-bit packed indices for every layer of at most 16 centres) or "auto" (per layer, the smallest
         form).
         ``trainable=True`` (with sparse=False and packed=False only): the layers' centres are parameters with a backward pass (DESIGN.md
-        section 12); fine_tune_compressed(..., sparse=..., packed=...) trains the other two forms."""
+        section 12); fine_tune_compressed(..., sparse=..., packed=...) trains the other two forms.
+        A layer quantized with ``group_rows`` becomes a GroupedCompressedDense; it has the byte form only, so any of the three
+        options raises NotImplementedError with the layer's name."""
         models = getattr(self, "quantized_models_by_layer", None)
         if not models:
             raise RuntimeError("compressed_network needs a quantized network: call quantize first")
@@ -314,7 +348,9 @@ class Trainer(ABC):
         """The quantized network in its stored form (storage.save_compressed: codebook + Huffman-coded centroid indices, dense or
         relative-index sparse, whichever is smaller per tensor -> ``weights.nnc``); appends to ``report.txt`` what Deep Compression
         reports: bits per weight of every tensor and the compression ratio against 32-bit weights.  Needs ``quantize`` with no
-        retraining since (the indices must describe the weights).  Returns storage.save_compressed's report."""
+        retraining since (the indices must describe the weights).  A kernel with group-wise codebooks (quantize(..., group_rows=))
+        is stored as one ordinary record per group, "{layer}.weights#g{g}" of shape (rows of the group, out); compressed.load_network
+        puts them together again.  Returns storage.save_compressed's report."""
         models = getattr(self, "quantized_models_by_layer", None)
         if not models:
             raise RuntimeError("store_compressed needs a quantized network: call quantize first (retraining discards it)")
@@ -326,6 +362,11 @@ class Trainer(ABC):
             if layer not in models:
                 continue
             for kind, t, m in zip(("weights", "biases"), layer.get_weights(), models[layer]):
+                if hasattr(m, "group_rows"):   # group-wise codebooks: one ordinary record per group, "{layer}.weights#g{g}"
+                    for g, gm in enumerate(m.models):
+                        rows = min(m.group_rows, t.shape[0] - g * m.group_rows)
+                        stored[f"{layer_name}.{kind}#g{g}"] = ((rows, t.shape[1]), gm, None)
+                    continue
                 stored[f"{layer_name}.{kind}"] = (tuple(t.shape), m, t if m is None else None)
         rep = {}
         storage.save_compressed(f"{directory}/weights.nnc", stored, report=rep)

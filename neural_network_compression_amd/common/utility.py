@@ -242,3 +242,59 @@ def get_quantized_weight(layer_weight, bits=4, mode="linear", cdfs=None, group=N
     if was_numpy:
         return values.cpu().numpy().reshape(shape), model
     return values.view(shape), model
+
+
+class GroupedModel:
+    """The fit of a Dense kernel with one codebook per block of ``group_rows`` input rows (get_quantized_weight_grouped):
+    ``models`` the per-group fitted models in group order, ``cluster_centers_`` float32 (G, K), ``labels_compact_`` the groups'
+    uint8 indices one after the other (row-major (in, out), what ops.grouped_codebook_matmul reads), ``n_iter_`` per group."""
+
+    def __init__(self, group_rows: int, models):
+        self.group_rows = int(group_rows)
+        self.models = list(models)
+        k = max(int(m.cluster_centers_.size) for m in self.models)
+        # (a fit that ends with fewer centres than its neighbours is padded with zeros no index of its group refers to)
+        self.cluster_centers_ = np.stack([np.pad(np.asarray(m.cluster_centers_, dtype=np.float32).ravel(), (0, k - int(m.cluster_centers_.size)))
+                                          for m in self.models])
+        self.labels_compact_ = torch.cat([m.labels_compact_.reshape(-1) for m in self.models])
+        self.n_iter_ = [m.n_iter_ for m in self.models]
+
+
+def grouped_slices(shape, group_rows: int, bits: int, mode: str):
+    """The row ranges [(lo, hi)] of the groups of a 2-D kernel of ``shape``, after the checks that need no fit: ValueError for a
+    kernel that is not 2-D, a group_rows that is no positive multiple of 32, more than 256 centres per group, or a group (the
+    short last one, usually) of fewer than 2**bits + 1 weights."""
+    if len(shape) != 2:
+        raise ValueError(f"group-wise codebooks take a 2-D Dense kernel (in, out), got shape {tuple(shape)}")
+    if not isinstance(group_rows, (int, np.integer)) or group_rows < 32 or group_rows % 32:
+        raise ValueError(f"group_rows must be a positive multiple of 32, got {group_rows!r}")
+    k = 2 ** bits + (1 if mode == "density" else 0)
+    if k > 256:
+        raise ValueError(f"{k} centres per group: group-wise codebooks hold at most 256 (uint8 indices)")
+    rows, ncols = int(shape[0]), int(shape[1])
+    slices = [(lo, min(rows, lo + int(group_rows))) for lo in range(0, rows, int(group_rows))]
+    for lo, hi in slices:
+        if (hi - lo) * ncols < 2 ** bits + 1:
+            raise ValueError(f"rows {lo}..{hi - 1} hold {(hi - lo) * ncols} weights, fewer than the 2**bits + 1 = {2 ** bits + 1} a group needs")
+    if not slices:
+        raise ValueError("an empty kernel has no groups")
+    return slices
+
+
+def get_quantized_weight_grouped(kernel, group_rows, bits=4, mode="linear", cdfs_by_group=None, arith="auto", reloc="auto"):
+    """get_quantized_weight per block of ``group_rows`` rows of a 2-D Dense kernel (in, out): group g is fitted exactly as
+    ``get_quantized_weight(kernel[g * group_rows:(g + 1) * group_rows], bits, mode, cdfs_by_group[g], arith=, reloc=)`` fits that
+    slice (a contiguous one: the kernel is row-major), in group order, so the modes that draw from NumPy's global generator see
+    the draws in that order.  Returns ``(quantized kernel, GroupedModel)``.  ``cdfs_by_group``: one get_weight_distribution
+    result per group for ``density``.  The ValueErrors of grouped_slices are raised before any fit."""
+    slices = grouped_slices(tuple(kernel.shape), group_rows, bits, mode)
+    if cdfs_by_group is not None and len(cdfs_by_group) != len(slices):
+        raise ValueError(f"cdfs_by_group holds {len(cdfs_by_group)} entries for {len(slices)} groups")
+    values, models = [], []
+    for g, (lo, hi) in enumerate(slices):
+        v, m = get_quantized_weight(kernel[lo:hi], bits=bits, mode=mode, cdfs=None if cdfs_by_group is None else cdfs_by_group[g],
+                                    arith=arith, reloc=reloc)
+        values.append(v)
+        models.append(m)
+    quantized = np.concatenate(values, axis=0) if isinstance(values[0], np.ndarray) else torch.cat(values, dim=0)
+    return quantized, GroupedModel(group_rows, models)

@@ -32,6 +32,12 @@ inside the kernel, the bias is added in float32): feed half inputs, leave the mo
 Half inputs are for the byte form only: the bitmap-sparse, the packed and every trainable layer raise ``TypeError`` on them, and
 ``torch.autocast`` is not registered.
 
+``GroupedCompressedDense`` runs a Dense layer whose kernel has one codebook per block of ``group_rows`` input rows
+(utility.get_quantized_weight_grouped, Trainer.quantize(..., group_rows=); ops.grouped_codebook_matmul, csrc/nnc_cbmm_grouped.hip,
+DESIGN.md section 17), on float32, bfloat16 and float16 inputs as ``CompressedDense`` does.  compress_network and load_network
+build it for a layer fitted that way; it has a byte form only, so ``sparse``, ``packed`` and ``trainable`` raise
+``NotImplementedError`` naming the layer.
+
 These layers are inference only: under autograd, with an input that needs a gradient, they raise instead of returning a result
 that silently has none.  ``trainable=True`` in compress_network / Trainer.compressed_network gives the trainable variants instead
 (``TrainableCompressedDense`` / ``TrainableCompressedConv2D``): their ``centers`` is an nn.Parameter and the
@@ -121,6 +127,64 @@ class CompressedDense(_CodebookLayer):
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:
         return self._matmul(x.contiguous())
+
+
+class GroupedCompressedDense(nn.Module):
+    """Dense run from one codebook per block of ``group_rows`` input rows: labels (kdim * ncols uint8 indices, row-major),
+    centers float32 (G, K), G = ceil(kdim / group_rows), bias float32[ncols] or None.  The path follows the input's dtype as in
+    CompressedDense (float32, bfloat16, float16; the output has the input's dtype); centers and bias stay float32."""
+
+    def __init__(self, kdim: int, ncols: int, group_rows: int, labels: torch.Tensor, centers: torch.Tensor, bias: torch.Tensor | None,
+                 activation=None):
+        super().__init__()
+        if labels.numel() != kdim * ncols:
+            raise ValueError(f"{labels.numel()} indices for a {kdim} x {ncols} weight matrix")
+        if labels.dtype != torch.uint8:
+            raise TypeError(f"group-wise codebooks take uint8 indices, got {labels.dtype}")
+        groups = max(1, -(-int(kdim) // int(group_rows)))
+        if centers.dim() != 2 or centers.shape[0] != groups:
+            raise ValueError(f"centers must have shape ({groups}, K) for {kdim} rows in groups of {group_rows}, got {tuple(centers.shape)}")
+        self.kdim, self.ncols, self.group_rows = int(kdim), int(ncols), int(group_rows)
+        self.register_buffer("labels", labels.reshape(-1))
+        self.register_buffer("centers", centers.to(torch.float32).contiguous())
+        self.register_buffer("bias", None if bias is None else bias.reshape(-1).to(torch.float32).contiguous())
+        self.activation = activation
+        self._fused_relu = activation is torch.relu
+
+    @classmethod
+    def from_dense(cls, dense, weight_model, bias_model=None) -> "GroupedCompressedDense":
+        """From a Dense layer and the GroupedModel of its kernel (utility.get_quantized_weight_grouped)."""
+        if weight_model is None:
+            raise ValueError("the kernel was not quantized (no fitted model): keep the float32 layer")
+        kin, kout = dense.kernel.shape
+        centers = torch.from_numpy(np.ascontiguousarray(weight_model.cluster_centers_, dtype=np.float32)).to(dense.kernel.device)
+        return cls(kin, kout, weight_model.group_rows, weight_model.labels_compact_, centers, _decoded_bias(dense.bias, bias_model), dense.activation)
+
+    @classmethod
+    def from_codes(cls, kdim, ncols, group_rows, labels, centers, bias, activation) -> "GroupedCompressedDense":
+        return cls(kdim, ncols, group_rows, labels, centers, bias, activation)
+
+    def forward(self, x: torch.Tensor) -> torch.Tensor:
+        y = ops.grouped_codebook_matmul(x.contiguous(), self.labels, self.centers, self.kdim, self.ncols, self.group_rows, bias=self.bias,
+                                        relu=self._fused_relu)
+        if self.activation is not None and not self._fused_relu:
+            y = self.activation(y)
+        return y
+
+    def get_weights(self):
+        return []
+
+    def nbytes(self) -> int:
+        return sum(t.numel() * t.element_size() for t in (self.labels, self.centers, self.bias) if t is not None)
+
+
+def _is_grouped(model) -> bool:
+    return hasattr(model, "group_rows")
+
+
+def _grouped_only_byte_form(name, what):
+    raise NotImplementedError(f"layer {name!r} has group-wise codebooks (group_rows): {what} is not implemented for it; "
+                              "it runs in the byte form only (GroupedCompressedDense)")
 
 
 def keras_rows_for_unfold(h: int, w: int, cin: int) -> np.ndarray:
@@ -741,7 +805,9 @@ def compress_network(network: nn.Module, models_by_layer, sparse=False, trainabl
     ``packed``: False, True (2- or 4-bit packed indices for every layer of at most 16 centres, the others in the byte form) or
     "auto"; with ``sparse`` it decides per layer by resident bytes as the module's docstring tells.
     ``trainable=True`` (dense indices only): TrainableCompressedDense / TrainableCompressedConv2D, centres as parameters;
-    compress_network_trainable gives the bitmap-sparse and the packed trainable layers too."""
+    compress_network_trainable gives the bitmap-sparse and the packed trainable layers too.
+    A layer whose kernel model is a utility.GroupedModel (one codebook per block of input rows) becomes a GroupedCompressedDense;
+    with ``sparse``, ``packed`` or ``trainable`` set it raises NotImplementedError and names the layer."""
     _check_sparse(sparse)
     _check_packed(packed, sparse, trainable)
     if trainable and sparse is not False:
@@ -749,7 +815,8 @@ def compress_network(network: nn.Module, models_by_layer, sparse=False, trainabl
                          "bitmap-sparse layers")
     if trainable:
         return compress_network_trainable(network, models_by_layer)
-    return _compress_each(network, models_by_layer, lambda layer, wm, bm: _replace(layer, wm, bm, sparse, packed))
+    what = "sparse=" + repr(sparse) if sparse is not False else ("packed=" + repr(packed) if packed is not False else None)
+    return _compress_each(network, models_by_layer, lambda layer, wm, bm: _replace(layer, wm, bm, sparse, packed), grouped=what)
 
 
 def compress_network_trainable(network: nn.Module, models_by_layer, sparse=False, packed=False) -> nn.Module:
@@ -764,28 +831,36 @@ def compress_network_trainable(network: nn.Module, models_by_layer, sparse=False
     _check_packed(packed, sparse)
     if packed is False:
         return _compress_each(network, models_by_layer,
-                              lambda layer, wm, bm: _pick(lambda: _trainable(layer, wm, bm), lambda: _trainable_sparse(layer, wm, bm), sparse))
+                              lambda layer, wm, bm: _pick(lambda: _trainable(layer, wm, bm), lambda: _trainable_sparse(layer, wm, bm), sparse),
+                              grouped="trainable=True")
     return _compress_each(network, models_by_layer,
                           lambda layer, wm, bm: _pick3(wm.cluster_centers_.size, lambda: _trainable(layer, wm, bm),
                                                        lambda: _trainable_sparse(layer, wm, bm), lambda: _trainable_packed(layer, wm, bm),
-                                                       sparse, packed))
+                                                       sparse, packed), grouped="trainable=True")
 
 
-def _compress_each(network: nn.Module, models_by_layer, make) -> nn.Module:
-    """A deep copy of ``network`` with every quantized layer replaced by make(layer, kernel model, bias model)."""
-    out = copy.deepcopy(network)
+def _compress_each(network: nn.Module, models_by_layer, make, grouped=None) -> nn.Module:
+    """A deep copy of ``network`` with every quantized layer replaced by make(layer, kernel model, bias model).  A layer fitted
+    with group-wise codebooks becomes a GroupedCompressedDense; ``grouped`` names the option that has no grouped form (None: the
+    plain byte form was asked for) and then raises NotImplementedError with the layer's name, before anything is built."""
+    todo = []
     for name, layer in network.get_config().items():
         models = models_by_layer.get(layer)
         if not models or models[0] is None:
             continue
-        bias_model = models[1] if len(models) > 1 else None
-        setattr(out, name, make(layer, models[0], bias_model))
+        if _is_grouped(models[0]) and grouped is not None:
+            _grouped_only_byte_form(name, grouped)
+        todo.append((name, layer, models[0], models[1] if len(models) > 1 else None))
+    out = copy.deepcopy(network)
+    for name, layer, wm, bm in todo:
+        setattr(out, name, GroupedCompressedDense.from_dense(layer, wm, bm) if _is_grouped(wm) else make(layer, wm, bm))
     return out
 
 
 def load_network(path: str, network: nn.Module, device=None, sparse=False, packed=False) -> nn.Module:
     """``compress_network`` from a stored network (storage.save_compressed, as Trainer.store_report writes it: records
-    "{layer}.weights" / "{layer}.biases").  ``network`` gives the architecture; layers stored raw get the stored float32 values.
+    "{layer}.weights" / "{layer}.biases", or "{layer}.weights#g{g}" per group of a kernel with group-wise codebooks, whose
+    ``group_rows`` is the row count of the first).  ``network`` gives the architecture; layers stored raw get the stored float32 values.
     ``sparse`` and ``packed`` as in compress_network: the stored format is the same, the indices are packed after loading."""
     from . import storage
 
@@ -803,6 +878,18 @@ def load_network(path: str, network: nn.Module, device=None, sparse=False, packe
 
     for name, layer in network.get_config().items():
         wkey, bkey = f"{name}.weights", f"{name}.biases"
+        if f"{wkey}#g0" in codes:   # a kernel with group-wise codebooks: one record per group (Trainer.store_compressed)
+            if sparse is not False or packed is not False:
+                _grouped_only_byte_form(name, "sparse=" + repr(sparse) if sparse is not False else "packed=" + repr(packed))
+            parts = []
+            while f"{wkey}#g{len(parts)}" in codes:
+                parts.append(codes[f"{wkey}#g{len(parts)}"])
+            (rows0, ncols), kdim = parts[0][0], sum(shape[0] for shape, _, _ in parts)
+            bias = tensor_of(codes[bkey]) if bkey in codes else None
+            group_rows = rows0 if len(parts) > 1 else -(-rows0 // 32) * 32   # one group: any multiple of 32 that holds every row
+            setattr(out, name, GroupedCompressedDense(kdim, ncols, group_rows, torch.cat([lab.reshape(-1) for _, _, lab in parts]),
+                                                      torch.stack([cen for _, cen, _ in parts]), bias, layer.activation))
+            continue
         if wkey not in codes:
             continue
         went = codes[wkey]
@@ -822,7 +909,7 @@ def compressed_nbytes(network: nn.Module) -> int:
     layers = network.get_config().values() if hasattr(network, "get_config") else [network]
     total = 0
     for layer in layers:
-        if isinstance(layer, (_CodebookLayer, _SparseCodebookLayer, _PackedCodebookLayer, _TrainableCentres)):
+        if isinstance(layer, (_CodebookLayer, GroupedCompressedDense, _SparseCodebookLayer, _PackedCodebookLayer, _TrainableCentres)):
             total += layer.nbytes()
         else:
             total += sum(p.numel() * p.element_size() for p in layer.parameters())

@@ -2,7 +2,9 @@
 // (nnc_cbgrad.hip) share: the launch constants, the per-bank LDS codebook layout, the label-row loads of the stream kernels and the
 // register-blocked FMA step of the tiled kernels.  The 2- and 4-bit packed form (nnc_cbpk.hip) takes cb_fill, tb_tile_fma and
 // the split-K combine from here.  The plan (cb_plan) and the stream kernel k_cbmm_stream itself live here too, templated on the
-// type of x: nnc_cbmm.hip instantiates them for float32, nnc_cbmm_h16.hip for bf16 / fp16 activations.
+// type of x: nnc_cbmm.hip instantiates them for float32, nnc_cbmm_h16.hip for bf16 / fp16 activations.  The group-wise unit
+// (nnc_cbmm_grouped.hip: one codebook per block of rows) follows the same plan and takes cb_fill, cb_refill, the label-row loads,
+// tb_tile_fma and HFrag from here.
 #pragma once
 #include "nnc_common.hpp"
 #include <type_traits>
@@ -24,7 +26,21 @@ using f16_t = _Float16;
 #define HM_BM 128                 // k_cbmm_mfma (nnc_cbmm_h16.hip): the output tile of a workgroup,
 #define HM_BN 128
 #define HM_BK 32                  // its k step,
-#define HM_LD 40                  // and the 2-byte elements per row of its LDS images: HM_BK of k and 16 bytes of padding
+#define HM_LD 40                  // the 2-byte elements per row of its LDS images: HM_BK of k and 16 bytes of padding,
+#define HM_THREADS 256            // and its threads
+
+// the MFMA of the two 2-byte types: 8 values of A and of B per lane, a 32 x 32 float32 tile of 16 registers
+template <typename XT> struct HFrag;
+template <> struct HFrag<bf16_t> {
+    typedef bf16_t V __attribute__((ext_vector_type(8)));
+    typedef float C __attribute__((ext_vector_type(16)));
+    __device__ static __forceinline__ C mfma(V a, V b, C c) { return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0); }
+};
+template <> struct HFrag<f16_t> {
+    typedef f16_t V __attribute__((ext_vector_type(8)));
+    typedef float C __attribute__((ext_vector_type(16)));
+    __device__ static __forceinline__ C mfma(V a, V b, C c) { return __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, c, 0, 0, 0); }
+};
 
 static inline long long cdiv(long long a, long long b) { return (a + b - 1) / b; }
 // k_cbmm_mfma's table and its staging row, in float32 words, rounded up so that the images behind them start on 16 bytes
@@ -158,6 +174,16 @@ __device__ __forceinline__ void cb_fill(float *cb, float *stage, const float *__
     const int words = entries << cshift;
 #pragma unroll 8
     for (int w = threadIdx.x; w < words; w += blockDim.x) cb[w] = stage[w >> cshift];
+}
+
+// the grouped layers (nnc_cbmm_grouped.hip) change tables on the way through a split: the copies of the first k entries
+// rewritten from another group's centres (the zeros behind them stay).  The caller's barriers keep readers of the old table out.
+template <typename RT = float>
+__device__ __forceinline__ void cb_refill(float *cb, const float *__restrict__ centers, int k, int cshift)
+{
+    const int words = k << cshift;
+#pragma unroll 8
+    for (int w = threadIdx.x; w < words; w += blockDim.x) cb[w] = (float)(RT)centers[w >> cshift];
 }
 
 template <int VB> struct Chunk;

@@ -15,20 +15,6 @@
 //   k_cbmm_reduce      the split-K partials (float32) in split order, + bias, ReLU, rounded once to the output type.
 #include "nnc_cbmm.hpp"
 
-#define HM_THREADS 256
-
-template <typename XT> struct HFrag;
-template <> struct HFrag<bf16_t> {
-    typedef bf16_t V __attribute__((ext_vector_type(8)));
-    typedef float C __attribute__((ext_vector_type(16)));
-    __device__ static __forceinline__ C mfma(V a, V b, C c) { return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0); }
-};
-template <> struct HFrag<f16_t> {
-    typedef f16_t V __attribute__((ext_vector_type(8)));
-    typedef float C __attribute__((ext_vector_type(16)));
-    __device__ static __forceinline__ C mfma(V a, V b, C c) { return __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, c, 0, 0, 0); }
-};
-
 // grid (col_tiles * row_tiles, splits), HM_THREADS threads.  `out` is y (direct 1: float32, 2: XT; + bias, ReLU here) or the float32
 // partials [split][m][ncols] (direct 0).  rows_per_split is a multiple of HM_BK.
 template <typename XT, typename LT, bool XVEC>

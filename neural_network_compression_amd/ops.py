@@ -371,6 +371,67 @@ def cbmm_h16_plan(dtype, m: int, kdim: int, ncols: int, label_bytes: int, k: int
     return dict(zip(nat.CBMM_H16_PLAN_FIELDS, (int(v) for v in out)))
 
 
+_X_DT = {torch.float32: nat.DT_F32, **_H16_DT}   # the activation types of nnc_cbmm_grouped
+
+
+def grouped_codebook_matmul(x: torch.Tensor, labels: torch.Tensor, centers: torch.Tensor, kdim: int, ncols: int, group_rows: int,
+                            bias: torch.Tensor | None = None, relu: bool = False, out_dtype=None) -> torch.Tensor:
+    """y = x @ W + bias (then ReLU) with one codebook per block of ``group_rows`` input rows: W[i, o] = centers[i // group_rows]
+    [labels[i * ncols + o]] (include/nnc.h, nnc_cbmm_grouped; DESIGN.md section 17).  x: float32, bfloat16 or float16 (..., kdim);
+    labels: the kdim * ncols uint8 indices (any storage offset); centers: float32 (G, K), G = ceil(kdim / group_rows), K <= 256;
+    group_rows: a positive multiple of 32; bias: float32[ncols] or None.  ``out_dtype`` and half x are as for codebook_matmul,
+    and with one group (group_rows >= kdim) so is every bit of the result.  Inference only: it raises under autograd."""
+    if not isinstance(x, torch.Tensor) or x.dtype not in _X_DT:
+        raise TypeError(f"x must be a float32, bfloat16 or float16 tensor, got {getattr(x, 'dtype', type(x))}")
+    _require_cuda(x, "x")
+    if out_dtype not in (None, torch.float32):
+        raise TypeError(f"out_dtype must be None ({x.dtype}) or torch.float32, got {out_dtype}")
+    y_dtype = x.dtype if out_dtype is None else out_dtype
+    _require_cuda(labels, "labels")
+    if labels.dtype != torch.uint8:
+        raise TypeError(f"grouped_codebook_matmul takes uint8 labels (K <= 256 per group), got {labels.dtype}")
+    _require_cuda(centers, "centers", torch.float32)
+    if bias is not None:
+        _require_cuda(bias, "bias", torch.float32)
+    kdim, ncols, group_rows = int(kdim), int(ncols), int(group_rows)
+    if torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (x, centers, bias)):
+        raise RuntimeError("grouped_codebook_matmul is inference only: it computes no gradient (run it under torch.no_grad())")
+    devs = {t.device for t in (x, labels, centers, bias) if t is not None}
+    if len(devs) != 1:
+        raise ValueError("x, labels, centers and bias must be on one device")
+    if group_rows < 32 or group_rows % 32:
+        raise ValueError(f"group_rows must be a positive multiple of 32, got {group_rows}")
+    groups = -(-kdim // group_rows)
+    if centers.dim() != 2 or centers.shape[0] != max(groups, 1) or not 1 <= centers.shape[1] <= 256:
+        raise ValueError(f"centers must have shape ({max(groups, 1)}, K <= 256) for kdim {kdim} and group_rows {group_rows}, got {tuple(centers.shape)}")
+    if x.dim() < 1 or x.shape[-1] != kdim:
+        raise ValueError(f"x must have shape (..., {kdim}), got {tuple(x.shape)}")
+    if labels.numel() != kdim * ncols:
+        raise ValueError(f"labels must hold kdim * ncols = {kdim * ncols} indices, got {labels.numel()}")
+    if bias is not None and bias.numel() != ncols:
+        raise ValueError(f"bias must hold ncols = {ncols} values, got {bias.numel()}")
+    L = nat.load()
+    lead = tuple(x.shape[:-1])
+    m = int(np.prod(lead)) if lead else 1
+    y = torch.empty(lead + (ncols,), dtype=y_dtype, device=x.device)
+    ws_bytes = int(L.nnc_cbmm_grouped_workspace_bytes(_X_DT[x.dtype], m, kdim, ncols))
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=x.device) if ws_bytes else None
+    nat.check(L.nnc_cbmm_grouped(_ptr(x), _X_DT[x.dtype], m, kdim, _ptr(labels), ncols, _ptr(centers), int(centers.shape[1]), group_rows, _ptr(bias),
+                                 1 if relu else 0, _ptr(y), _X_DT[y_dtype], _ptr(ws), ws_bytes, _stream(x)))
+    return y
+
+
+def cbmm_grouped_plan(dtype, m: int, kdim: int, ncols: int, k: int, group_rows: int, cus: int, labels_addr: int = 0) -> dict:
+    """Host: the plan nnc_cbmm_grouped follows for x of ``dtype`` (torch.float32 / bfloat16 / float16) on a device with ``cus``
+    compute units (include/nnc.h, nnc_cbmm_grouped_plan), as a dict keyed by _native.CBMM_GROUPED_PLAN_FIELDS.  No device needed."""
+    if dtype not in _X_DT:
+        raise TypeError(f"dtype must be torch.float32, torch.bfloat16 or torch.float16, got {dtype}")
+    L = nat.load()
+    out = (ctypes.c_int64 * nat.CBMM_GROUPED_PLAN_LEN)()
+    nat.check(L.nnc_cbmm_grouped_plan(_X_DT[dtype], int(m), int(kdim), int(ncols), int(k), int(group_rows), int(cus), int(labels_addr), out))
+    return dict(zip(nat.CBMM_GROUPED_PLAN_FIELDS, (int(v) for v in out)))
+
+
 def _grad_args(g: torch.Tensor, labels: torch.Tensor, kdim: int, ncols: int, k: int):
     _require_cuda(g, "g", torch.float32)
     _require_cuda(labels, "labels")
