@@ -10,18 +10,19 @@
 //                  are summed in block order by k_cbgrad_reduce.
 //   k_cbdx_tiled   m > 16.  128 (r) x 128 (i) output tiles; the W^T tile (128 rows i x TB_K columns o) is decoded into LDS from the
 //                  row-major indices, then the register-blocked FMA of k_cbmm_tiled.  ncols is split by a count that depends on the
-//                  shape alone; the partials go through k_cbgrad_reduce.
+//                  shape alone; the partials go through k_cbgrad_reduce.  Around the decode: the tile skeleton of nnc_cbtile.hpp.
 //   k_cbdc_stream  m <= 16.  A lane holds g[0..m-1, o] for its columns; x[r, i] is broadcast by v_readlane; dW[i, o] is formed in
 //                  float32 with r ascending and binned at once.  Both dc kernels scale x by 2^scx and g by 2^scg as they load
 //                  them (cbdc_scales: the maxima to [0.5, 1)), so dW' = dW * 2^(scx + scg) stays in float32's normal range.
-//   k_cbdc_tiled   m > 16.  128 (i) x 128 (o) tiles of x^T g, the reduction over m split by a count that depends on the shape alone.
+//   k_cbdc_tiled   m > 16.  128 (i) x 128 (o) tiles of x^T g, the reduction over m split by a count that depends on the shape alone:
+//                  the prologue, the tile fill and the binning loop of nnc_cbtile.hpp with the label read labels[i * ncols + o].
 //   Binning: every dW' (or every m-split's partial) becomes rint(v * 2^(S - scx - scg)) = rint(dW * 2^S) in int64 and is added into K LDS bins (replicated across
 //   banks) with integer atomics, then into a global int64[K] with integer atomics: exact, so the result depends on the shape and the
 //   data only.  S = 62 - ceil(log2(terms)) - P, 2^P > m * max|x| * max|g|, terms = kdim * ncols * splits; max|x| and max|g| come
 //   from k_cbgrad_absmax on the device, the dc kernel derives S itself and writes it next to the sums, and k_cbdc_finish writes
 //   dc = ldexp(sum, -S).  No host read anywhere.
 // An index >= K reads 0 in dx and falls into no bin in dc, as in the forward pass.  No float atomics.
-#include "nnc_cbgrad.hpp"
+#include "nnc_cbtile.hpp"
 
 // ------------------------------------------------------------------ plans (host)
 struct CgPlan {
@@ -37,8 +38,6 @@ struct CgPlan {
     long long lds;
 };
 
-static int mt_of(long long m) { return m <= 1 ? 1 : (m <= 2 ? 2 : (m <= 4 ? 4 : (m <= 8 ? 8 : 16))); }
-
 static int ceil_log2(long long v)
 {
     int l = 0;
@@ -51,7 +50,7 @@ static void cg_stream_grid(CgPlan &p, long long m, long long kdim, long long nco
 {
     cus = std::max(1, std::min(cus, CB_PLAN_CUS));
     p.path = NNC_CBMM_STREAM;
-    p.mt = mt_of(m);
+    p.mt = cb_mt(m);
     p.vb = std::min(16, (64 / p.mt) * lb);
     p.col_tiles = cdiv(ncols, 64LL * (p.vb / lb));
     const long long groups = std::max(1LL, std::min(cdiv(2LL * cus, p.col_tiles), cdiv(kdim, (long long)CB_WAVES * CB_UNROLL)));
@@ -123,9 +122,6 @@ static CgPlan dc_plan(long long m, long long kdim, long long ncols, int lb, int 
     p.terms_log2 = ceil_log2(kdim * ncols * p.splits);
     return p;
 }
-
-static int64_t dx_ws_bytes(const CgPlan &p, long long m, long long kdim) { return p.splits > 1 ? (int64_t)p.splits * m * kdim * 4 : 0; }
-static int64_t dc_ws_bytes(const CgPlan &p, int k) { return p.path == NNC_CBMM_STREAM || p.path == NNC_CBMM_TILED ? CBG_HDR_BYTES + 8LL * k : 0; }
 
 // ------------------------------------------------------------------ max |x|, max |g|
 // amax[0] = bits of max |x|, amax[1] = bits of max |g| (zeroed by the caller).  |v| as a bit pattern orders as the value; a NaN
@@ -256,41 +252,27 @@ __global__ __launch_bounds__(256) void k_cbdx_tiled(const float *__restrict__ g,
     float *cb = ws + TB_K * TB_N;          // k + 1 entries (entry k = 0)
     for (int j = threadIdx.x; j <= k; j += 256) cb[j] = j < k ? centers[j] : 0.0f;
 
-    const int t = threadIdx.x, tx = t & 15, ty = t >> 4;
-    const long long n0 = (blockIdx.x % col_tiles) * TB_N, m0 = (blockIdx.x / col_tiles) * TB_M;
-    const long long o_lo = (long long)blockIdx.y * cols_per_split, o_hi = std::min(ncols, o_lo + cols_per_split);
+    const TbTile T = tb_tile(col_tiles, cols_per_split, ncols);
     float acc[8][8];
+    tb_clear(acc);
+
+    const int lr = threadIdx.x >> 1, lo = (threadIdx.x & 1) * 4;   // W^T tile: index row n0 + lr, o lo..lo+3 (as the g tile: row lr, o lo..lo+3)
+    for (long long ob = T.lo; ob < T.hi; ob += TB_K) {
+        __syncthreads();
+        tb_load_rows(gs, g, m, ncols, T.m0, ob, T.hi);
+        const long long wi = T.n0 + lr;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const long long go = ob + lo + j;
+            ws[(lo + j) * TB_N + lr] = (wi < kdim && go < T.hi) ? cb[std::min((uint32_t)labels[wi * ncols + go], (uint32_t)k)] : 0.0f;
+        }
+        __syncthreads();
+        tb_tile_fma(gs, ws, T.tx, T.ty, acc);
+    }
 #pragma unroll
     for (int a = 0; a < 8; ++a)
 #pragma unroll
-        for (int b = 0; b < 8; ++b) acc[a][b] = 0.0f;
-
-    const int lr = t >> 1, lo = (t & 1) * 4;   // g tile: row lr, o lo..lo+3; W^T tile: index row n0 + lr, o lo..lo+3
-    for (long long ob = o_lo; ob < o_hi; ob += TB_K) {
-        __syncthreads();
-        {
-            const long long gr = m0 + lr, wi = n0 + lr;
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const long long go = ob + lo + j;
-                const bool in_o = go < o_hi;
-                gs[(lo + j) * TB_M + lr] = (gr < m && in_o) ? g[gr * ncols + go] : 0.0f;
-                ws[(lo + j) * TB_N + lr] = (wi < kdim && in_o) ? cb[std::min((uint32_t)labels[wi * ncols + go], (uint32_t)k)] : 0.0f;
-            }
-        }
-        __syncthreads();
-        tb_tile_fma(gs, ws, tx, ty, acc);
-    }
-    float *dst = direct ? out : out + (long long)blockIdx.y * m * kdim;
-#pragma unroll
-    for (int a = 0; a < 8; ++a) {
-        const long long r = m0 + ty * 8 + a;
-#pragma unroll
-        for (int b = 0; b < 8; ++b) {
-            const long long c = n0 + tx * 8 + b;
-            if (r < m && c < kdim) dst[r * kdim + c] = acc[a][b];
-        }
-    }
+        for (int b = 0; b < 8; ++b) tb_store_dx(acc[a][b], T.m0 + T.ty * 8 + a, T.n0 + T.tx * 8 + b, m, kdim, direct, out);
 }
 
 // ------------------------------------------------------------------ the split partials, summed in split order
@@ -428,63 +410,20 @@ __global__ __launch_bounds__(256) void k_cbdc_tiled(const float *__restrict__ x,
     float *xs = smem;                      // [TB_K][TB_M]: x[r, i0 + i]
     float *gs = xs + TB_K * TB_M;          // [TB_K][TB_N]: g[r, o0 + o]
     unsigned long long *bins = reinterpret_cast<unsigned long long *>(gs + TB_K * TB_N);
-    int flag;
-    const int S = cbdc_shift(hdr, m, terms_log2, flag);
-    if (blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0) {
-        hdr[2] = (uint32_t)S;
-        hdr[3] = (uint32_t)flag;
-    }
-    if (flag != CBG_FLAG_OK) return;
-    int scx, scg;
-    cbdc_scales(hdr, scx, scg);
-    const int Sw = S - scx - scg;
-    for (int j = threadIdx.x; j < (k << rlog2); j += 256) bins[j] = 0ull;
+    int scx, scg, Sw;
+    if (!cbdc_begin(hdr, m, terms_log2, bins, k << rlog2, scx, scg, Sw)) return;
 
-    const int t = threadIdx.x, tx = t & 15, ty = t >> 4;
-    const long long o0 = (blockIdx.x % col_tiles) * TB_N, i0 = (blockIdx.x / col_tiles) * TB_M;
-    const long long r_lo = (long long)blockIdx.y * rows_per_split, r_hi = std::min(m, r_lo + rows_per_split);
+    const TbTile T = tb_tile(col_tiles, rows_per_split, m);   // n0: the first column o, m0: the first index row i
     float acc[8][8];
-#pragma unroll
-    for (int a = 0; a < 8; ++a)
-#pragma unroll
-        for (int b = 0; b < 8; ++b) acc[a][b] = 0.0f;
-
-    const int lk = t >> 5, lc = (t & 31) * 4;   // both tiles: row r = rb + lk, columns lc..lc+3 (coalesced)
-    for (long long rb = r_lo; rb < r_hi; rb += TB_K) {
+    tb_clear(acc);
+    for (long long rb = T.lo; rb < T.hi; rb += TB_K) {
         __syncthreads();
-        {
-            const long long r = rb + lk;
-            const bool in_r = r < r_hi;
-            float xv[4], gv[4];
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const long long ii = i0 + lc + j, oo = o0 + lc + j;
-                xv[j] = x[cbdc_idx(r * kdim + ii, in_r && ii < kdim)];
-                gv[j] = g[cbdc_idx(r * ncols + oo, in_r && oo < ncols)];
-            }
-            __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const long long ii = i0 + lc + j, oo = o0 + lc + j;
-                xs[lk * TB_M + lc + j] = cbdc_scaled(xv[j], in_r && ii < kdim, scx);
-                gs[lk * TB_N + lc + j] = cbdc_scaled(gv[j], in_r && oo < ncols, scg);
-            }
-        }
+        cbdc_load_tiles(xs, gs, x, g, kdim, ncols, T.m0, T.n0, rb, T.hi, scx, scg);
         __syncthreads();
-        tb_tile_fma(xs, gs, tx, ty, acc);
+        tb_tile_fma(xs, gs, T.tx, T.ty, acc);
     }
-    const int rep = t & ((1 << rlog2) - 1);
-#pragma unroll
-    for (int a = 0; a < 8; ++a) {
-        const long long i = i0 + ty * 8 + a;
-#pragma unroll
-        for (int b = 0; b < 8; ++b) {
-            const long long o = o0 + tx * 8 + b;
-            if (i >= kdim || o >= ncols) continue;
-            const uint32_t l = (uint32_t)labels[i * ncols + o];
-            if (l < (uint32_t)k) atomicAdd(&bins[(l << rlog2) + rep], cbdc_fix(acc[a][b], Sw));
-        }
-    }
+    cbdc_bin_tile(acc, T, kdim, ncols, k, Sw, bins, rlog2, threadIdx.x & ((1 << rlog2) - 1),
+                  [&](long long i, long long o) { return (uint32_t)labels[i * ncols + o]; });
     cbdc_flush(bins, k, rlog2, sums);
 }
 
@@ -600,7 +539,7 @@ static int plan_out(const char *fn, const CgPlan &p, int lb, int32_t cus, int64_
 extern "C" int64_t nnc_cbmm_dx_workspace_bytes(int64_t m, int64_t kdim, int64_t ncols, int label_bytes)
 {
     if (cg_check("nnc_cbmm_dx_workspace_bytes", m, kdim, ncols, label_bytes, 1) != NNC_OK) return 0;
-    return dx_ws_bytes(dx_plan(m, kdim, ncols, label_bytes, 1, CB_PLAN_CUS, 0), m, kdim);
+    return cbg_dx_ws_bytes(dx_plan(m, kdim, ncols, label_bytes, 1, CB_PLAN_CUS, 0).splits, m, kdim);
 }
 
 extern "C" int nnc_cbmm_dx_plan(int64_t m, int64_t kdim, int64_t ncols, int label_bytes, int32_t k, int32_t cus, uint64_t labels_addr, int64_t *out)
@@ -610,7 +549,7 @@ extern "C" int nnc_cbmm_dx_plan(int64_t m, int64_t kdim, int64_t ncols, int labe
     const CgPlan p = dx_plan(m, kdim, ncols, label_bytes, k, cus, (uintptr_t)labels_addr);
     if ((rc = plan_out("nnc_cbmm_dx_plan", p, label_bytes, cus, out)) != NNC_OK) return rc;
     const int64_t v[NNC_CBDX_PLAN_LEN] = {p.path, p.vb, p.mt, p.path == NNC_CBMM_STREAM ? 1LL << p.cshift : (p.entries ? 1 : 0), p.entries, p.splits,
-                                          p.per_split, p.aligned, p.lds, p.col_tiles, p.row_tiles, dx_ws_bytes(p, m, kdim)};
+                                          p.per_split, p.aligned, p.lds, p.col_tiles, p.row_tiles, cbg_dx_ws_bytes(p.splits, m, kdim)};
     for (int i = 0; i < NNC_CBDX_PLAN_LEN; ++i) out[i] = v[i];
     return NNC_OK;
 }
@@ -623,10 +562,8 @@ extern "C" int nnc_cbmm_dx_f32(const float *g, int64_t m, int64_t kdim, const vo
     if (!centers_dev) return fail(NNC_EINVAL, "nnc_cbmm_dx_f32: centers is NULL");
     if (m > 0 && kdim > 0 && !dx) return fail(NNC_EINVAL, "nnc_cbmm_dx_f32: dx is NULL");
     if (m > 0 && kdim > 0 && ncols > 0 && (!g || !labels)) return fail(NNC_EINVAL, "nnc_cbmm_dx_f32: g or labels is NULL");
-    if (workspace_bytes < 0) return fail(NNC_EINVAL, "nnc_cbmm_dx_f32: negative workspace size");
     const int64_t need = nnc_cbmm_dx_workspace_bytes(m, kdim, ncols, label_bytes);
-    if (workspace_bytes < need) return fail(NNC_ENOSPACE, "nnc_cbmm_dx_f32: workspace smaller than nnc_cbmm_dx_workspace_bytes()");
-    if (need > 0 && !workspace) return fail(NNC_EINVAL, "nnc_cbmm_dx_f32: workspace is NULL");
+    if ((rc = cb_check_workspace("nnc_cbmm_dx_f32", "nnc_cbmm_dx_workspace_bytes", workspace, workspace_bytes, need)) != NNC_OK) return rc;
     const CgPlan p = dx_plan(m, kdim, ncols, label_bytes, k, cu_count(), reinterpret_cast<uintptr_t>(labels));
     const GradCase *gc = p.path == NNC_CBMM_STREAM ? find_grad_case(label_bytes, p.vb, p.mt) : nullptr;
     if (p.path == NNC_CBMM_STREAM && !gc) return no_grad_case("nnc_cbmm_dx_f32", label_bytes, p.vb, p.mt);
@@ -660,7 +597,7 @@ extern "C" int nnc_cbmm_dx_f32(const float *g, int64_t m, int64_t kdim, const vo
 extern "C" int64_t nnc_cbmm_dc_workspace_bytes(int64_t m, int64_t kdim, int64_t ncols, int label_bytes, int32_t k)
 {
     if (cg_check("nnc_cbmm_dc_workspace_bytes", m, kdim, ncols, label_bytes, k) != NNC_OK) return 0;
-    return dc_ws_bytes(dc_plan(m, kdim, ncols, label_bytes, k, CB_PLAN_CUS, 0), k);
+    return cbg_dc_ws_bytes(dc_plan(m, kdim, ncols, label_bytes, k, CB_PLAN_CUS, 0).path, k);
 }
 
 extern "C" int nnc_cbmm_dc_plan(int64_t m, int64_t kdim, int64_t ncols, int label_bytes, int32_t k, int32_t cus, uint64_t labels_addr, int64_t *out)
@@ -670,7 +607,7 @@ extern "C" int nnc_cbmm_dc_plan(int64_t m, int64_t kdim, int64_t ncols, int labe
     const CgPlan p = dc_plan(m, kdim, ncols, label_bytes, k, cus, (uintptr_t)labels_addr);
     if ((rc = plan_out("nnc_cbmm_dc_plan", p, label_bytes, cus, out)) != NNC_OK) return rc;
     const int64_t v[NNC_CBDC_PLAN_LEN] = {p.path, p.vb, p.mt, p.path == NNC_CBMM_ZERO ? 0 : 1LL << p.rlog2, p.splits, p.per_split, p.aligned, p.lds,
-                                          p.col_tiles, p.row_tiles, p.terms_log2, dc_ws_bytes(p, k)};
+                                          p.col_tiles, p.row_tiles, p.terms_log2, cbg_dc_ws_bytes(p.path, k)};
     for (int i = 0; i < NNC_CBDC_PLAN_LEN; ++i) out[i] = v[i];
     return NNC_OK;
 }
@@ -682,11 +619,8 @@ extern "C" int nnc_cbmm_dc_f32(const float *x, const float *g, int64_t m, int64_
     if (rc != NNC_OK) return rc;
     if (!dc) return fail(NNC_EINVAL, "nnc_cbmm_dc_f32: dc is NULL");
     if (m > 0 && kdim > 0 && ncols > 0 && (!x || !g || !labels)) return fail(NNC_EINVAL, "nnc_cbmm_dc_f32: x, g or labels is NULL");
-    if (workspace_bytes < 0) return fail(NNC_EINVAL, "nnc_cbmm_dc_f32: negative workspace size");
     const int64_t need = nnc_cbmm_dc_workspace_bytes(m, kdim, ncols, label_bytes, k);
-    if (workspace_bytes < need) return fail(NNC_ENOSPACE, "nnc_cbmm_dc_f32: workspace smaller than nnc_cbmm_dc_workspace_bytes()");
-    if (need > 0 && !workspace) return fail(NNC_EINVAL, "nnc_cbmm_dc_f32: workspace is NULL");
-    if (need > 0 && reinterpret_cast<uintptr_t>(workspace) % 8 != 0) return fail(NNC_EINVAL, "nnc_cbmm_dc_f32: workspace not 8-byte aligned");
+    if ((rc = cb_check_workspace("nnc_cbmm_dc_f32", "nnc_cbmm_dc_workspace_bytes", workspace, workspace_bytes, need, 8, "workspace not 8-byte aligned")) != NNC_OK) return rc;
     const CgPlan p = dc_plan(m, kdim, ncols, label_bytes, k, cu_count(), reinterpret_cast<uintptr_t>(labels));
     const GradCase *gc = p.path == NNC_CBMM_STREAM ? find_grad_case(label_bytes, p.vb, p.mt) : nullptr;
     if (p.path == NNC_CBMM_STREAM && !gc) return no_grad_case("nnc_cbmm_dc_f32", label_bytes, p.vb, p.mt);

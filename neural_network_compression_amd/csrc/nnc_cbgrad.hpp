@@ -1,6 +1,7 @@
 // nnc_cbgrad.hpp -- what the backward pass of the codebook matmul (nnc_cbgrad.hip) shares with those of its bitmap-sparse and
 // packed siblings (nnc_cbspgrad.hip, nnc_cbpkgrad.hip): the fixed-order wave reduction of the dx stream kernels, the scaling and fixed-point binning of dc (DESIGN.md
-// section 12) and the launches of the kernels both use (defined in nnc_cbgrad.hip).
+// section 12), the workspace sizes and the launches of the kernels both use (defined in nnc_cbgrad.hip).  The tiled kernels' shared
+// text is in nnc_cbtile.hpp.
 #pragma once
 #include "nnc_cbmm.hpp"
 
@@ -12,7 +13,8 @@
 // The m partials of every lane summed over the wave: a reduce-scatter (at lane bit 32 >> t the lanes with the bit set keep the upper
 // half of the rows they hold and take their partner's; then the rest of the butterfly on one value).  N + log2(64 / N) shuffles
 // instead of 6 N; every pair adds in a fixed order, so the sum depends on the data only.  Returns the total of row `row`, the
-// same on every lane of a group of 64 / N lanes.
+// same on every lane of a group of 64 / N lanes.  Both candidates of an exchange are read into values before the select: a select
+// between two elements of the array is a select between two addresses to the compiler, which at N = 16 keeps the array in scratch.
 template <int N>
 __device__ __forceinline__ float wave_reduce_rows(float (&v)[N], int lane, int &row)
 {
@@ -23,9 +25,8 @@ __device__ __forceinline__ float wave_reduce_rows(float (&v)[N], int lane, int &
         const bool up = (lane & bit) != 0;
 #pragma unroll
         for (int j = 0; j < half; ++j) {
-            const float send = up ? v[j] : v[j + half];
-            const float keep = up ? v[j + half] : v[j];
-            v[j] = keep + __shfl_xor(send, bit);
+            const float a = v[j], b = v[j + half];
+            v[j] = (up ? b : a) + __shfl_xor(up ? a : b, bit);
         }
         row += up ? half : 0;
     }
@@ -34,6 +35,10 @@ __device__ __forceinline__ float wave_reduce_rows(float (&v)[N], int lane, int &
     for (int bit = 64 / N / 2; bit >= 1; bit >>= 1) s += __shfl_xor(s, bit);
     return s;
 }
+
+// the workspaces of the backward entry points: dx, the partials [splits][m][kdim] when ncols is split; dc, the header and int64 sums[k]
+static inline int64_t cbg_dx_ws_bytes(long long splits, long long m, long long kdim) { return splits > 1 ? (int64_t)splits * m * kdim * 4 : 0; }
+static inline int64_t cbg_dc_ws_bytes(int path, int k) { return path == NNC_CBMM_STREAM || path == NNC_CBMM_TILED ? CBG_HDR_BYTES + 8LL * k : 0; }
 
 // S of the dc sums from the maxima k_cbgrad_absmax left (uniform over the launch); flag as CBG_FLAG_*
 __device__ __forceinline__ int cbdc_shift(const uint32_t *amax, long long m, int terms_log2, int &flag)

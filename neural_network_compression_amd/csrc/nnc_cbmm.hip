@@ -10,14 +10,16 @@
 //                  lane always hits its own bank, 2 LDS cycles per 64 lookups), fewer copies for K > 256.  The 4 waves of a
 //                  workgroup split its rows and are summed in LDS in wave order; workgroups split K.
 //   k_cbmm_tiled   m > 16: bound by compute.  128 x 128 output tiles, the W tile dequantized from its indices into LDS once per
-//                  workgroup and reused by all 128 rows of x (register-blocked FMA, 8 x 8 outputs per thread).
+//                  workgroup and reused by all 128 rows of x (register-blocked FMA, 8 x 8 outputs per thread).  The kernel is
+//                  the decode; the tile coordinates, the x tile load and the store are nnc_cbtile.hpp's, as for every tiled
+//                  kernel of the other forms.
 //   k_cbmm_reduce  the split-K partials summed in split order, + bias, ReLU.  No float atomics anywhere: the number of splits
 //                  depends only on the shape and the CU count, so the same call gives the same bits.
 // Label rows need not be aligned (any ncols, any storage offset): a lane loads the two aligned VB-byte chunks around its window
 // and funnel-shifts them (v_alignbyte) by the row's misalignment, which is uniform over the wave.  An aligned chunk that holds
 // one byte of the tensor lies in the tensor's page, so no load leaves the allocation; lanes past the last column load their
 // row's first chunk and store nothing.  An index >= K reads 0, as nnc_gather_f32 does.
-#include "nnc_cbmm.hpp"
+#include "nnc_cbtile.hpp"
 
 // ------------------------------------------------------------------ tiled: m > 16
 // grid (col_tiles * row_tiles, splits), 256 threads; thread (tx, ty) = (t % 16, t / 16) owns rows ty*8.. and columns tx*8.. of
@@ -33,55 +35,29 @@ __global__ __launch_bounds__(256) void k_cbmm_tiled(const float *__restrict__ x,
     float *cb = ws + TB_K * TB_N;          // k + 1 entries (entry k = 0)
     for (int j = threadIdx.x; j <= k; j += 256) cb[j] = j < k ? centers[j] : 0.0f;
 
-    const int t = threadIdx.x, tx = t & 15, ty = t >> 4;
-    const long long n0 = (blockIdx.x % col_tiles) * TB_N, m0 = (blockIdx.x / col_tiles) * TB_M;
-    const long long k_lo = (long long)blockIdx.y * rows_per_split, k_hi = std::min(kdim, k_lo + rows_per_split);
+    const TbTile T = tb_tile(col_tiles, rows_per_split, kdim);
     float acc[8][8];
+    tb_clear(acc);
+
+    const int wk = threadIdx.x >> 5, wc = (threadIdx.x & 31) * 4;      // W tile: k wk, columns wc..wc+3
+    for (long long kb = T.lo; kb < T.hi; kb += TB_K) {
+        __syncthreads();
+        tb_load_rows(xs, x, m, kdim, T.m0, kb, T.hi);
+        const long long gk = kb + wk;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const long long gc = T.n0 + wc + j;
+            float v = 0.0f;
+            if (gk < T.hi && gc < ncols) v = cb[std::min((uint32_t)labels[gk * ncols + gc], (uint32_t)k)];
+            ws[wk * TB_N + wc + j] = v;
+        }
+        __syncthreads();
+        tb_tile_fma(xs, ws, T.tx, T.ty, acc);
+    }
 #pragma unroll
     for (int a = 0; a < 8; ++a)
 #pragma unroll
-        for (int b = 0; b < 8; ++b) acc[a][b] = 0.0f;
-
-    const int xr = t >> 1, xk = (t & 1) * 4;       // x tile: row xr, k xk..xk+3
-    const int wk = t >> 5, wc = (t & 31) * 4;      // W tile: k wk, columns wc..wc+3
-    for (long long kb = k_lo; kb < k_hi; kb += TB_K) {
-        __syncthreads();
-        {
-            const long long gr = m0 + xr;
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const long long gk = kb + xk + j;
-                xs[(xk + j) * TB_M + xr] = (gr < m && gk < k_hi) ? x[gr * kdim + gk] : 0.0f;
-            }
-            const long long gk = kb + wk;
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const long long gc = n0 + wc + j;
-                float v = 0.0f;
-                if (gk < k_hi && gc < ncols) v = cb[std::min((uint32_t)labels[gk * ncols + gc], (uint32_t)k)];
-                ws[wk * TB_N + wc + j] = v;
-            }
-        }
-        __syncthreads();
-        tb_tile_fma(xs, ws, tx, ty, acc);
-    }
-#pragma unroll
-    for (int a = 0; a < 8; ++a) {
-        const long long r = m0 + ty * 8 + a;
-#pragma unroll
-        for (int b = 0; b < 8; ++b) {
-            const long long c = n0 + tx * 8 + b;
-            if (r >= m || c >= ncols) continue;
-            float v = acc[a][b];
-            if (direct) {
-                if (bias) v += bias[c];
-                if (relu) v = v < 0.0f ? 0.0f : v;   // NaN stays NaN, as torch.relu
-                out[r * ncols + c] = v;
-            } else {
-                out[((long long)blockIdx.y * m + r) * ncols + c] = v;
-            }
-        }
-    }
+        for (int b = 0; b < 8; ++b) tb_store_y(acc[a][b], T.m0 + T.ty * 8 + a, T.n0 + T.tx * 8 + b, m, ncols, bias, relu, direct, out);
 }
 
 // ------------------------------------------------------------------ split-K combine
@@ -223,10 +199,8 @@ extern "C" int nnc_cbmm_f32(const float *x, int64_t m, int64_t kdim, const void 
     if (!centers_dev) return nnc_set_error_(NNC_EINVAL, "nnc_cbmm_f32: centers is NULL");
     if (m > 0 && ncols > 0 && !y) return nnc_set_error_(NNC_EINVAL, "nnc_cbmm_f32: y is NULL");
     if (m > 0 && ncols > 0 && kdim > 0 && (!x || !labels)) return nnc_set_error_(NNC_EINVAL, "nnc_cbmm_f32: x or labels is NULL");
-    if (workspace_bytes < 0) return nnc_set_error_(NNC_EINVAL, "nnc_cbmm_f32: negative workspace size");
     const int64_t need = nnc_cbmm_workspace_bytes(m, kdim, ncols, label_bytes);
-    if (workspace_bytes < need) return nnc_set_error_(NNC_ENOSPACE, "nnc_cbmm_f32: workspace smaller than nnc_cbmm_workspace_bytes()");
-    if (need > 0 && !workspace) return nnc_set_error_(NNC_EINVAL, "nnc_cbmm_f32: workspace is NULL");
+    if ((rc = cb_check_workspace("nnc_cbmm_f32", "nnc_cbmm_workspace_bytes", workspace, workspace_bytes, need)) != NNC_OK) return rc;
     if (m == 0 || ncols == 0) return NNC_OK;
 
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);

@@ -4,7 +4,7 @@
 // the split-K combine from here.  The plan (cb_plan) and the stream kernel k_cbmm_stream itself live here too, templated on the
 // type of x: nnc_cbmm.hip instantiates them for float32, nnc_cbmm_h16.hip for bf16 / fp16 activations.  The group-wise unit
 // (nnc_cbmm_grouped.hip: one codebook per block of rows) follows the same plan and takes cb_fill, cb_refill, the label-row loads,
-// tb_tile_fma and HFrag from here.
+// tb_tile_fma and HFrag from here.  cb_mt and cb_check_workspace serve every entry point of the nnc_cb*.hip units.
 #pragma once
 #include "nnc_common.hpp"
 #include <type_traits>
@@ -43,6 +43,8 @@ template <> struct HFrag<f16_t> {
 };
 
 static inline long long cdiv(long long a, long long b) { return (a + b - 1) / b; }
+// the rows of x (of g in the backward pass) a stream kernel is instantiated for: the power of two >= m (m <= CB_SKINNY_M)
+static inline int cb_mt(long long m) { return m <= 1 ? 1 : (m <= 2 ? 2 : (m <= 4 ? 4 : (m <= 8 ? 8 : 16))); }
 // k_cbmm_mfma's table and its staging row, in float32 words, rounded up so that the images behind them start on 16 bytes
 __host__ __device__ static inline int hm_table_words(int entries, int cshift) { return ((entries << cshift) + entries + 3) & ~3; }
 
@@ -73,7 +75,7 @@ static inline void cb_grid(CbPlan &p, long long m, long long kdim, long long nco
     long long s;
     if (m <= CB_SKINNY_M) {
         p.path = NNC_CBMM_STREAM;
-        p.mt = m <= 1 ? 1 : (m <= 2 ? 2 : (m <= 4 ? 4 : (m <= 8 ? 8 : 16)));
+        p.mt = cb_mt(m);
         const int e_max = 64 / p.mt;                                 // accumulators per lane <= 64
         p.vb = std::min(16, e_max * lb);
         p.row_tiles = 1;
@@ -130,6 +132,20 @@ static inline CbPlan cb_plan(long long m, long long kdim, long long ncols, int l
 }
 
 static inline int64_t cb_ws_bytes(const CbPlan &p, long long m, long long ncols) { return p.splits > 1 ? (int64_t)p.splits * m * ncols * 4 : 0; }
+
+// The workspace checks of an entry point `fn` whose query `query` answered `need`, in the order every entry point makes them: a
+// negative size (NNC_EINVAL), less than `need` (NNC_ENOSPACE), a NULL or, with `align` > 0, a misaligned pointer where bytes are
+// needed (NNC_EINVAL; `misaligned` is the entry point's wording of the last).  NNC_OK otherwise.
+static inline int cb_check_workspace(const char *fn, const char *query, const void *workspace, int64_t workspace_bytes, int64_t need, int align = 0,
+                                     const char *misaligned = "")
+{
+    const std::string f(fn);
+    if (workspace_bytes < 0) return fail(NNC_EINVAL, f + ": negative workspace size");
+    if (workspace_bytes < need) return fail(NNC_ENOSPACE, f + ": workspace smaller than " + query + "()");
+    if (need > 0 && !workspace) return fail(NNC_EINVAL, f + ": workspace is NULL");
+    if (need > 0 && align > 0 && reinterpret_cast<uintptr_t>(workspace) % align) return fail(NNC_EINVAL, f + ": " + misaligned);
+    return NNC_OK;
+}
 
 // the per-bank table: entry j of lane l at word j * copies + (l mod copies), copies = 1 << cshift
 template <typename LT> struct CbTable;

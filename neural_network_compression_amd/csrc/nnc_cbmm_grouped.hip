@@ -4,12 +4,13 @@
 // The plan is the ungrouped one (cb_plan, nnc_cbmm.hpp) for the same shape, so the splits, the workspace and the summation order are
 // those of nnc_cbmm_f32 / nnc_cbmm_h16.  The kernels are the ungrouped ones with one addition: a workgroup that walks from one group's
 // rows into the next changes its LDS table.  They are kernels of their own and not instantiations of a body shared with the
-// ungrouped ones: called through a device function, k_cbmm_stream compiles to another instruction stream.
+// ungrouped ones: called through a device function, k_cbmm_stream compiles to another instruction stream.  The tiled one is, like
+// k_cbmm_tiled, the tile skeleton of nnc_cbtile.hpp around its decode.
 //   k_cbmm_stream_grouped  m <= 16: the split is walked group by group, the four waves share each stretch and the table.
 //   k_cbmm_tiled_grouped   m > 16, float32 x: two small tables in LDS, a TB_K step may lie across a boundary.
 //   k_cbmm_mfma_grouped    m > 16, bf16 / fp16 x: a k step of HM_BK never lies across a boundary (group_rows is a multiple of 32).
 // With one group every kernel computes what its ungrouped counterpart computes, bit for bit.
-#include "nnc_cbmm.hpp"
+#include "nnc_cbtile.hpp"
 
 // ------------------------------------------------------------------ skinny: m <= 16
 // k_cbmm_stream (nnc_cbmm.hpp) with uint8 labels and centers[groups][k]: grid (col_tiles, splits), CB_THREADS threads, the same
@@ -189,57 +190,31 @@ __global__ __launch_bounds__(256) void k_cbmm_tiled_grouped(const float *__restr
     long long g_top = (long long)blockIdx.y * rows_per_split / group_rows;   // the last group whose table is in LDS
     table(g_top);
 
-    const int t = threadIdx.x, tx = t & 15, ty = t >> 4;
-    const long long n0 = (blockIdx.x % col_tiles) * TB_N, m0 = (blockIdx.x / col_tiles) * TB_M;
-    const long long k_lo = (long long)blockIdx.y * rows_per_split, k_hi = std::min(kdim, k_lo + rows_per_split);
+    const TbTile T = tb_tile(col_tiles, rows_per_split, kdim);
     float acc[8][8];
+    tb_clear(acc);
+
+    const int wk = threadIdx.x >> 5, wc = (threadIdx.x & 31) * 4;      // W tile: k wk, columns wc..wc+3
+    for (long long kb = T.lo; kb < T.hi; kb += TB_K) {
+        if (std::min(kb + TB_K, T.hi) > (g_top + 1) * group_rows) table(++g_top);   // the step's last row opens a group
+        __syncthreads();
+        tb_load_rows(xs, x, m, kdim, T.m0, kb, T.hi);
+        const long long gk = kb + wk;
+        const float *tab = cb + ((gk >= g_top * group_rows ? g_top : g_top - 1) & 1) * (k + 1);   // a step's rows lie in g_top - 1 and g_top
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const long long gc = T.n0 + wc + j;
+            float v = 0.0f;
+            if (gk < T.hi && gc < ncols) v = tab[std::min((uint32_t)labels[gk * ncols + gc], (uint32_t)k)];
+            ws[wk * TB_N + wc + j] = v;
+        }
+        __syncthreads();
+        tb_tile_fma(xs, ws, T.tx, T.ty, acc);
+    }
 #pragma unroll
     for (int a = 0; a < 8; ++a)
 #pragma unroll
-        for (int b = 0; b < 8; ++b) acc[a][b] = 0.0f;
-
-    const int xr = t >> 1, xk = (t & 1) * 4;       // x tile: row xr, k xk..xk+3
-    const int wk = t >> 5, wc = (t & 31) * 4;      // W tile: k wk, columns wc..wc+3
-    for (long long kb = k_lo; kb < k_hi; kb += TB_K) {
-        if (std::min(kb + TB_K, k_hi) > (g_top + 1) * group_rows) table(++g_top);   // the step's last row opens a group
-        __syncthreads();
-        {
-            const long long gr = m0 + xr;
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const long long gk = kb + xk + j;
-                xs[(xk + j) * TB_M + xr] = (gr < m && gk < k_hi) ? x[gr * kdim + gk] : 0.0f;
-            }
-            const long long gk = kb + wk;
-            const float *tab = cb + ((gk >= g_top * group_rows ? g_top : g_top - 1) & 1) * (k + 1);   // a step's rows lie in g_top - 1 and g_top
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const long long gc = n0 + wc + j;
-                float v = 0.0f;
-                if (gk < k_hi && gc < ncols) v = tab[std::min((uint32_t)labels[gk * ncols + gc], (uint32_t)k)];
-                ws[wk * TB_N + wc + j] = v;
-            }
-        }
-        __syncthreads();
-        tb_tile_fma(xs, ws, tx, ty, acc);
-    }
-#pragma unroll
-    for (int a = 0; a < 8; ++a) {
-        const long long r = m0 + ty * 8 + a;
-#pragma unroll
-        for (int b = 0; b < 8; ++b) {
-            const long long c = n0 + tx * 8 + b;
-            if (r >= m || c >= ncols) continue;
-            float v = acc[a][b];
-            if (direct) {
-                if (bias) v += bias[c];
-                if (relu) v = v < 0.0f ? 0.0f : v;   // NaN stays NaN, as torch.relu
-                out[r * ncols + c] = v;
-            } else {
-                out[((long long)blockIdx.y * m + r) * ncols + c] = v;
-            }
-        }
-    }
+        for (int b = 0; b < 8; ++b) tb_store_y(acc[a][b], T.m0 + T.ty * 8 + a, T.n0 + T.tx * 8 + b, m, ncols, bias, relu, direct, out);
 }
 
 // ------------------------------------------------------------------ MFMA tile: m > 16, bf16 / fp16 x
@@ -499,10 +474,8 @@ extern "C" int nnc_cbmm_grouped(const void *x, int x_dtype, int64_t m, int64_t k
     const int xb = x_dtype == NNC_DT_F32 ? 4 : 2, yb = y_dtype == NNC_DT_F32 ? 4 : 2;
     if (reinterpret_cast<uintptr_t>(x) % xb || reinterpret_cast<uintptr_t>(y) % yb)
         return nnc_set_error_(NNC_EINVAL, "nnc_cbmm_grouped: x or y is not aligned to its element size");
-    if (workspace_bytes < 0) return nnc_set_error_(NNC_EINVAL, "nnc_cbmm_grouped: negative workspace size");
     const int64_t need = nnc_cbmm_grouped_workspace_bytes(x_dtype, m, kdim, ncols);
-    if (workspace_bytes < need) return nnc_set_error_(NNC_ENOSPACE, "nnc_cbmm_grouped: workspace smaller than nnc_cbmm_grouped_workspace_bytes()");
-    if (need > 0 && !workspace) return nnc_set_error_(NNC_EINVAL, "nnc_cbmm_grouped: workspace is NULL");
+    if ((rc = cb_check_workspace("nnc_cbmm_grouped", "nnc_cbmm_grouped_workspace_bytes", workspace, workspace_bytes, need)) != NNC_OK) return rc;
     if (m == 0 || ncols == 0) return NNC_OK;
 
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);

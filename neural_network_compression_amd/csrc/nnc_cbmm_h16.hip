@@ -268,10 +268,8 @@ extern "C" int nnc_cbmm_h16(const void *x, int x_dtype, int64_t m, int64_t kdim,
     if (m > 0 && ncols > 0 && kdim > 0 && (!x || !labels)) return nnc_set_error_(NNC_EINVAL, "nnc_cbmm_h16: x or labels is NULL");
     if (reinterpret_cast<uintptr_t>(x) % 2 || reinterpret_cast<uintptr_t>(y) % (y_dtype == NNC_DT_F32 ? 4 : 2))
         return nnc_set_error_(NNC_EINVAL, "nnc_cbmm_h16: x or y is not aligned to its element size");
-    if (workspace_bytes < 0) return nnc_set_error_(NNC_EINVAL, "nnc_cbmm_h16: negative workspace size");
     const int64_t need = nnc_cbmm_h16_workspace_bytes(m, kdim, ncols, label_bytes);
-    if (workspace_bytes < need) return nnc_set_error_(NNC_ENOSPACE, "nnc_cbmm_h16: workspace smaller than nnc_cbmm_h16_workspace_bytes()");
-    if (need > 0 && !workspace) return nnc_set_error_(NNC_EINVAL, "nnc_cbmm_h16: workspace is NULL");
+    if ((rc = cb_check_workspace("nnc_cbmm_h16", "nnc_cbmm_h16_workspace_bytes", workspace, workspace_bytes, need)) != NNC_OK) return rc;
     if (m == 0 || ncols == 0) return NNC_OK;
 
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);

@@ -14,11 +14,12 @@
 //                  2^BITS floats (centres, then zeros) with 32 per-bank copies, 2 KiB or 512 B of LDS, one ds_read_b32 per
 //                  weight at byte (label << 7 | (lane & 31) << 2): a shift and an and-or per lookup, no bank conflict.  The 4
 //                  waves of a workgroup split its rows and are summed in LDS in wave order; workgroups split K.
-//   k_cbpk_tiled   m > 16: the 128 x 128 tile of k_cbmm_tiled; a thread decodes 4 columns of a tile row from the packed dword
-//                  that holds them into the LDS W tile, then tb_tile_fma.
+//   k_cbpk_tiled   m > 16: the 128 x 128 tile of k_cbmm_tiled (the tile skeleton of nnc_cbtile.hpp); a thread decodes 4 columns
+//                  of a tile row from the packed dword that holds them into the LDS W tile, then tb_tile_fma.
 //   the split-K partials are summed by k_cbmm_reduce (cbmm_reduce) in split order.  No float atomics anywhere.
 // An index >= K reads 0 (the table's zero entries).  Columns past ncols are computed from the padding and never stored.
 #include "nnc_cbpk.hpp"
+#include "nnc_cbtile.hpp"
 
 // ------------------------------------------------------------------ the layout (host; the arithmetic is nnc_cbpk.hpp's)
 extern "C" int64_t nnc_cbpk_row_bytes(int64_t ncols, int bits)
@@ -168,7 +169,7 @@ static PkPlan pk_plan(long long m, long long kdim, long long ncols, int bits, in
     long long s;
     if (m <= CB_SKINNY_M) {
         p.path = NNC_CBMM_STREAM;
-        p.mt = m <= 1 ? 1 : (m <= 2 ? 2 : (m <= 4 ? 4 : (m <= 8 ? 8 : 16)));
+        p.mt = cb_mt(m);
         p.xrows = p.mt;
         // every wave keeps at least one batch of rows; the partials (splits x m x ncols x 4 B) stay within the packed index
         // stream (kdim x ncols x bits / 8 B)
@@ -338,54 +339,28 @@ __global__ __launch_bounds__(256) void k_cbpk_tiled(const float *__restrict__ x,
     float *cb = ws + TB_K * TB_N;          // 2^BITS entries (zeros from k on)
     for (int j = threadIdx.x; j < ENTRIES; j += 256) cb[j] = j < k ? centers[j] : 0.0f;
 
-    const int t = threadIdx.x, tx = t & 15, ty = t >> 4;
-    const long long n0 = (blockIdx.x % col_tiles) * TB_N, m0 = (blockIdx.x / col_tiles) * TB_M;
-    const long long k_lo = (long long)blockIdx.y * rows_per_split, k_hi = std::min(kdim, k_lo + rows_per_split);
+    const TbTile T = tb_tile(col_tiles, rows_per_split, kdim);
     float acc[8][8];
+    tb_clear(acc);
+
+    const int wk = threadIdx.x >> 5, wc = (threadIdx.x & 31) * 4;      // W tile: k wk, columns wc..wc+3
+    const long long wbyte = T.n0 * BITS / 8 + (wc * BITS / 32) * 4;
+    const int wshift = wc * BITS % 32;
+    for (long long kb = T.lo; kb < T.hi; kb += TB_K) {
+        __syncthreads();
+        tb_load_rows(xs, x, m, kdim, T.m0, kb, T.hi);
+        const long long gk = kb + wk;
+        const bool live = gk < T.hi && wbyte < row_bytes;
+        const uint32_t word = live ? *reinterpret_cast<const uint32_t *>(packed + gk * row_bytes + wbyte) >> wshift : 0u;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) ws[wk * TB_N + wc + j] = live ? cb[(word >> (BITS * j)) & MASK] : 0.0f;
+        __syncthreads();
+        tb_tile_fma(xs, ws, T.tx, T.ty, acc);
+    }
 #pragma unroll
     for (int a = 0; a < 8; ++a)
 #pragma unroll
-        for (int b = 0; b < 8; ++b) acc[a][b] = 0.0f;
-
-    const int xr = t >> 1, xk = (t & 1) * 4;       // x tile: row xr, k xk..xk+3
-    const int wk = t >> 5, wc = (t & 31) * 4;      // W tile: k wk, columns wc..wc+3
-    const long long wbyte = n0 * BITS / 8 + (wc * BITS / 32) * 4;
-    const int wshift = wc * BITS % 32;
-    for (long long kb = k_lo; kb < k_hi; kb += TB_K) {
-        __syncthreads();
-        {
-            const long long gr = m0 + xr;
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const long long gk = kb + xk + j;
-                xs[(xk + j) * TB_M + xr] = (gr < m && gk < k_hi) ? x[gr * kdim + gk] : 0.0f;
-            }
-            const long long gk = kb + wk;
-            const bool live = gk < k_hi && wbyte < row_bytes;
-            const uint32_t word = live ? *reinterpret_cast<const uint32_t *>(packed + gk * row_bytes + wbyte) >> wshift : 0u;
-#pragma unroll
-            for (int j = 0; j < 4; ++j) ws[wk * TB_N + wc + j] = live ? cb[(word >> (BITS * j)) & MASK] : 0.0f;
-        }
-        __syncthreads();
-        tb_tile_fma(xs, ws, tx, ty, acc);
-    }
-#pragma unroll
-    for (int a = 0; a < 8; ++a) {
-        const long long r = m0 + ty * 8 + a;
-#pragma unroll
-        for (int b = 0; b < 8; ++b) {
-            const long long c = n0 + tx * 8 + b;
-            if (r >= m || c >= ncols) continue;
-            float v = acc[a][b];
-            if (direct) {
-                if (bias) v += bias[c];
-                if (relu) v = v < 0.0f ? 0.0f : v;   // NaN stays NaN, as torch.relu
-                out[r * ncols + c] = v;
-            } else {
-                out[((long long)blockIdx.y * m + r) * ncols + c] = v;
-            }
-        }
-    }
+        for (int b = 0; b < 8; ++b) tb_store_y(acc[a][b], T.m0 + T.ty * 8 + a, T.n0 + T.tx * 8 + b, m, ncols, bias, relu, direct, out);
 }
 
 // ------------------------------------------------------------------ C ABI
@@ -455,10 +430,8 @@ extern "C" int nnc_cbpk_f32(const float *x, int64_t m, int64_t kdim, const void 
     if (!centers_dev) return fail(NNC_EINVAL, "nnc_cbpk_f32: centers is NULL");
     if (m > 0 && ncols > 0 && !y) return fail(NNC_EINVAL, "nnc_cbpk_f32: y is NULL");
     if (m > 0 && ncols > 0 && kdim > 0 && !x) return fail(NNC_EINVAL, "nnc_cbpk_f32: x is NULL");
-    if (workspace_bytes < 0) return fail(NNC_EINVAL, "nnc_cbpk_f32: negative workspace size");
     const int64_t need = nnc_cbpk_workspace_bytes(m, kdim, ncols, bits);
-    if (workspace_bytes < need) return fail(NNC_ENOSPACE, "nnc_cbpk_f32: workspace smaller than nnc_cbpk_workspace_bytes()");
-    if (need > 0 && !workspace) return fail(NNC_EINVAL, "nnc_cbpk_f32: workspace is NULL");
+    if ((rc = cb_check_workspace("nnc_cbpk_f32", "nnc_cbpk_workspace_bytes", workspace, workspace_bytes, need)) != NNC_OK) return rc;
     if (m == 0 || ncols == 0) return NNC_OK;
 
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);

@@ -12,16 +12,17 @@
 //   k_cbpkdx_stream  m <= 16.  A workgroup owns 64 lanes x E columns of g (E = 8 * VB / BITS, held in registers) and a group of
 //                    packed rows; a wave takes one row at a time (CB_UNROLL rows in flight, k_cbpk_stream's aligned 1- to 16-byte
 //                    loads), looks its columns up in the 2^BITS-entry per-bank table and reduces its m partials over the 64 lanes
-//                    in a fixed order (pg_reduce_rows).  Column blocks are the splits, summed in block order by k_cbgrad_reduce.
+//                    in a fixed order (wave_reduce_rows).  Column blocks are the splits, summed in block order by k_cbgrad_reduce.
 //   k_cbpkdx_tiled   m > 16.  k_cbdx_tiled with the W^T tile decoded from packed dwords: all 256 threads decode 4 columns each.
+//                    Both tiled kernels are the tile skeleton of nnc_cbtile.hpp around their label reads.
 //   k_cbpkdc_stream  m <= 16.  The grid and loads of k_cbpkdx_stream; x[r, i] by vector load + v_readlane; dW'[i, o] as
 //                    k_cbdc_stream forms it; the image goes into the lane's own copy of the K <= 16 LDS bins (64 copies: no two
 //                    lanes of a wave ever meet on an address).
 //   k_cbpkdc_tiled   m > 16.  k_cbdc_tiled's tiles and splits of m; a thread's 8 consecutive columns of a row come from one packed
 //                    dword, loaded once.
 // k_cbgrad_absmax, k_cbdc_finish and k_cbgrad_reduce are nnc_cbgrad.hip's.  No float atomics; no host read.
-#include "nnc_cbgrad.hpp"
 #include "nnc_cbpk.hpp"
+#include "nnc_cbtile.hpp"
 
 #define PKG_RLOG2 6               // dc: 64 copies of every LDS bin, one per lane (K <= 16: at most 8 KiB)
 #define PKG_G 64                  // stream: g values a lane keeps (columns per lane x rows of m), at most
@@ -38,8 +39,6 @@ struct PgPlan {
     long long lds;
 };
 
-static int pg_mt(long long m) { return m <= 1 ? 1 : (m <= 2 ? 2 : (m <= 4 ? 4 : (m <= 8 ? 8 : 16))); }
-
 // The stream geometry both directions share.  Columns per lane: at most a 16-byte load and PKG_G values of g; from there down to a
 // 4-byte load, the widest that keeps four lanes in five on a column (the last column block may be nearly empty) and leaves the
 // 256-CU planning device two workgroups per CU (column blocks x the most row groups kdim allows); else the narrowest.  The shape
@@ -48,7 +47,7 @@ static void pg_stream_grid(PgPlan &p, long long m, long long kdim, long long nco
 {
     cus = std::max(1, std::min(cus, CB_PLAN_CUS));
     p.path = NNC_CBMM_STREAM;
-    p.mt = pg_mt(m);
+    p.mt = cb_mt(m);
     const long long max_groups = cdiv(kdim, (long long)CB_WAVES * CB_UNROLL);   // every wave keeps a batch of rows
     const int cap = std::min(128 / bits, PKG_G / p.mt);
     p.cols = cap;
@@ -93,8 +92,6 @@ static PgPlan pg_dx_plan(long long m, long long kdim, long long ncols, int bits,
     return p;
 }
 
-static int64_t pg_dx_ws_bytes(const PgPlan &p, long long m, long long kdim) { return p.splits > 1 ? (int64_t)p.splits * m * kdim * 4 : 0; }
-
 // The splits of m and T are nnc_cbmm_dc_plan's for the same shape at label_bytes = 1 (so S, every image and every sum are the byte
 // form's).  NNC_OK, or that plan's error.
 static int pg_dc_plan(long long m, long long kdim, long long ncols, int bits, int k, int cus, PgPlan &p)
@@ -124,33 +121,7 @@ static int pg_dc_plan(long long m, long long kdim, long long ncols, int bits, in
     return NNC_OK;
 }
 
-static int64_t pg_dc_ws_bytes(const PgPlan &p, int k) { return p.path == NNC_CBMM_STREAM || p.path == NNC_CBMM_TILED ? CBG_HDR_BYTES + 8LL * k : 0; }
-
 // ------------------------------------------------------------------ dx, m <= 16
-// wave_reduce_rows (nnc_cbgrad.hpp: the same exchanges and the same additions in the same order) with both candidates of every
-// exchange read into values before the select.  A select between two elements of the array is a select between two addresses to the
-// compiler, which at N = 16 keeps the array in scratch (80 bytes per lane in k_cbdx_stream); this form stays in registers.
-template <int N>
-__device__ __forceinline__ float pg_reduce_rows(float (&v)[N], int lane, int &row)
-{
-    row = 0;
-#pragma unroll
-    for (int t = 0; (N >> t) > 1; ++t) {
-        const int half = N >> (t + 1), bit = 32 >> t;
-        const bool up = (lane & bit) != 0;
-#pragma unroll
-        for (int j = 0; j < half; ++j) {
-            const float a = v[j], b = v[j + half];
-            v[j] = (up ? b : a) + __shfl_xor(up ? a : b, bit);
-        }
-        row += up ? half : 0;
-    }
-    float s = v[0];
-#pragma unroll
-    for (int bit = 64 / N / 2; bit >= 1; bit >>= 1) s += __shfl_xor(s, bit);
-    return s;
-}
-
 // grid (column blocks, row groups), CB_THREADS threads.  out: dx (one column block) or the partials [block][m][kdim].
 template <int BITS, int VB, int MT>
 __global__ __launch_bounds__(CB_THREADS) void k_cbpkdx_stream(const float *__restrict__ g, int m, long long kdim, const unsigned char *__restrict__ packed,
@@ -199,7 +170,7 @@ __global__ __launch_bounds__(CB_THREADS) void k_cbpkdx_stream(const float *__res
             for (int r = 0; r < MT; ++r) p[r] = __builtin_fmaf(gv[r][e], wv, p[r]);
         }
         int row;
-        const float v = pg_reduce_rows<MT>(p, lane, row);
+        const float v = wave_reduce_rows<MT>(p, lane, row);
         if ((lane & (64 / MT - 1)) == 0 && row < m) dst[(long long)row * kdim + i] = v;
     };
 
@@ -235,44 +206,27 @@ __global__ __launch_bounds__(256) void k_cbpkdx_tiled(const float *__restrict__ 
     float *cb = ws + TB_K * TB_N;          // 2^BITS entries (zeros from k on)
     for (int j = threadIdx.x; j < ENTRIES; j += 256) cb[j] = j < k ? centers[j] : 0.0f;
 
-    const int t = threadIdx.x, tx = t & 15, ty = t >> 4;
-    const long long n0 = (blockIdx.x % col_tiles) * TB_N, m0 = (blockIdx.x / col_tiles) * TB_M;
-    const long long o_lo = (long long)blockIdx.y * cols_per_split, o_hi = std::min(ncols, o_lo + cols_per_split);
+    const TbTile T = tb_tile(col_tiles, cols_per_split, ncols);
     float acc[8][8];
+    tb_clear(acc);
+
+    const int lr = threadIdx.x >> 1, lo = (threadIdx.x & 1) * 4;   // W^T tile: index row n0 + lr, o lo..lo+3 (as the g tile: row lr, o lo..lo+3)
+    for (long long ob = T.lo; ob < T.hi; ob += TB_K) {
+        __syncthreads();
+        tb_load_rows(gs, g, m, ncols, T.m0, ob, T.hi);
+        const long long wi = T.n0 + lr;
+        const long long bitpos = (ob + lo) * BITS;
+        const bool live = wi < kdim && ob + lo < T.hi;                 // then the dword lies inside the padded row
+        const uint32_t word = live ? *reinterpret_cast<const uint32_t *>(packed + wi * row_bytes + ((bitpos >> 5) << 2)) >> (bitpos & 31) : 0u;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) ws[(lo + j) * TB_N + lr] = (live && ob + lo + j < T.hi) ? cb[(word >> (BITS * j)) & MASK] : 0.0f;
+        __syncthreads();
+        tb_tile_fma(gs, ws, T.tx, T.ty, acc);
+    }
 #pragma unroll
     for (int a = 0; a < 8; ++a)
 #pragma unroll
-        for (int b = 0; b < 8; ++b) acc[a][b] = 0.0f;
-
-    const int lr = t >> 1, lo = (t & 1) * 4;   // g tile: row lr, o lo..lo+3; W^T tile: index row n0 + lr, o lo..lo+3
-    for (long long ob = o_lo; ob < o_hi; ob += TB_K) {
-        __syncthreads();
-        {
-            const long long gr = m0 + lr, wi = n0 + lr;
-            const long long bitpos = (ob + lo) * BITS;
-            const bool live = wi < kdim && ob + lo < o_hi;                 // then the dword lies inside the padded row
-            const uint32_t word = live ? *reinterpret_cast<const uint32_t *>(packed + wi * row_bytes + ((bitpos >> 5) << 2)) >> (bitpos & 31) : 0u;
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const long long go = ob + lo + j;
-                const bool in_o = go < o_hi;
-                gs[(lo + j) * TB_M + lr] = (gr < m && in_o) ? g[gr * ncols + go] : 0.0f;
-                ws[(lo + j) * TB_N + lr] = (live && in_o) ? cb[(word >> (BITS * j)) & MASK] : 0.0f;
-            }
-        }
-        __syncthreads();
-        tb_tile_fma(gs, ws, tx, ty, acc);
-    }
-    float *dst = direct ? out : out + (long long)blockIdx.y * m * kdim;
-#pragma unroll
-    for (int a = 0; a < 8; ++a) {
-        const long long r = m0 + ty * 8 + a;
-#pragma unroll
-        for (int b = 0; b < 8; ++b) {
-            const long long c = n0 + tx * 8 + b;
-            if (r < m && c < kdim) dst[r * kdim + c] = acc[a][b];
-        }
-    }
+        for (int b = 0; b < 8; ++b) tb_store_dx(acc[a][b], T.m0 + T.ty * 8 + a, T.n0 + T.tx * 8 + b, m, kdim, direct, out);
 }
 
 // ------------------------------------------------------------------ dc, m <= 16
@@ -381,65 +335,25 @@ __global__ __launch_bounds__(256) void k_cbpkdc_tiled(const float *__restrict__ 
     float *xs = smem;                      // [TB_K][TB_M]: x[r, i0 + i]
     float *gs = xs + TB_K * TB_M;          // [TB_K][TB_N]: g[r, o0 + o]
     unsigned long long *bins = reinterpret_cast<unsigned long long *>(gs + TB_K * TB_N);
-    int flag;
-    const int S = cbdc_shift(hdr, m, terms_log2, flag);
-    if (blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0) {
-        hdr[2] = (uint32_t)S;
-        hdr[3] = (uint32_t)flag;
-    }
-    if (flag != CBG_FLAG_OK) return;
-    int scx, scg;
-    cbdc_scales(hdr, scx, scg);
-    const int Sw = S - scx - scg;
-    for (int j = threadIdx.x; j < (k << PKG_RLOG2); j += 256) bins[j] = 0ull;
+    int scx, scg, Sw;
+    if (!cbdc_begin(hdr, m, terms_log2, bins, k << PKG_RLOG2, scx, scg, Sw)) return;
 
-    const int t = threadIdx.x, tx = t & 15, ty = t >> 4;
-    const long long o0 = (blockIdx.x % col_tiles) * TB_N, i0 = (blockIdx.x / col_tiles) * TB_M;
-    const long long r_lo = (long long)blockIdx.y * rows_per_split, r_hi = std::min(m, r_lo + rows_per_split);
+    const TbTile T = tb_tile(col_tiles, rows_per_split, m);   // n0: the first column o, m0: the first index row i
     float acc[8][8];
-#pragma unroll
-    for (int a = 0; a < 8; ++a)
-#pragma unroll
-        for (int b = 0; b < 8; ++b) acc[a][b] = 0.0f;
-
-    const int lk = t >> 5, lc = (t & 31) * 4;   // both tiles: row r = rb + lk, columns lc..lc+3 (coalesced)
-    for (long long rb = r_lo; rb < r_hi; rb += TB_K) {
+    tb_clear(acc);
+    for (long long rb = T.lo; rb < T.hi; rb += TB_K) {
         __syncthreads();
-        {
-            const long long r = rb + lk;
-            const bool in_r = r < r_hi;
-            float xv[4], gv[4];
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const long long ii = i0 + lc + j, oo = o0 + lc + j;
-                xv[j] = x[cbdc_idx(r * kdim + ii, in_r && ii < kdim)];
-                gv[j] = g[cbdc_idx(r * ncols + oo, in_r && oo < ncols)];
-            }
-            __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const long long ii = i0 + lc + j, oo = o0 + lc + j;
-                xs[lk * TB_M + lc + j] = cbdc_scaled(xv[j], in_r && ii < kdim, scx);
-                gs[lk * TB_N + lc + j] = cbdc_scaled(gv[j], in_r && oo < ncols, scg);
-            }
-        }
+        cbdc_load_tiles(xs, gs, x, g, kdim, ncols, T.m0, T.n0, rb, T.hi, scx, scg);
         __syncthreads();
-        tb_tile_fma(xs, gs, tx, ty, acc);
+        tb_tile_fma(xs, gs, T.tx, T.ty, acc);
     }
-    unsigned long long *mybins = bins + (t & ((1 << PKG_RLOG2) - 1));
-    const long long oc = o0 + tx * 8, bitpos = oc * BITS;
-#pragma unroll
-    for (int a = 0; a < 8; ++a) {
-        const long long i = i0 + ty * 8 + a;
-        if (i >= kdim || oc >= ncols) continue;                           // (then the dword lies inside the padded row)
+    // the 8 labels of a thread's row are 8 * BITS bits of one packed dword (a tile starts on a multiple of 128 columns), which
+    // lies inside the padded row when its first column lies inside the matrix
+    cbdc_bin_tile(acc, T, kdim, ncols, k, Sw, bins, PKG_RLOG2, threadIdx.x & ((1 << PKG_RLOG2) - 1), [&](long long i, long long o) {
+        const long long bitpos = (o & ~7LL) * BITS;
         const uint32_t word = *reinterpret_cast<const uint32_t *>(packed + i * row_bytes + ((bitpos >> 5) << 2)) >> (bitpos & 31);
-#pragma unroll
-        for (int b = 0; b < 8; ++b) {
-            if (oc + b >= ncols) continue;
-            const uint32_t l = (word >> (BITS * b)) & MASK;
-            if (l < (uint32_t)k) atomicAdd(&mybins[l << PKG_RLOG2], cbdc_fix(acc[a][b], Sw));
-        }
-    }
+        return (word >> (BITS * (o & 7))) & MASK;
+    });
     cbdc_flush(bins, k, PKG_RLOG2, sums);
 }
 
@@ -509,7 +423,7 @@ static int pg_plan_out(const char *fn, const PgPlan &p, int bits, int32_t cus, i
 extern "C" int64_t nnc_cbpk_dx_workspace_bytes(int64_t m, int64_t kdim, int64_t ncols, int bits)
 {
     if (pg_check("nnc_cbpk_dx_workspace_bytes", m, kdim, ncols, bits, 1) != NNC_OK) return 0;
-    return pg_dx_ws_bytes(pg_dx_plan(m, kdim, ncols, bits, CB_PLAN_CUS), m, kdim);
+    return cbg_dx_ws_bytes(pg_dx_plan(m, kdim, ncols, bits, CB_PLAN_CUS).splits, m, kdim);
 }
 
 extern "C" int nnc_cbpk_dx_plan(int64_t m, int64_t kdim, int64_t ncols, int bits, int32_t k, int32_t cus, int64_t *out)
@@ -519,7 +433,7 @@ extern "C" int nnc_cbpk_dx_plan(int64_t m, int64_t kdim, int64_t ncols, int bits
     const PgPlan p = pg_dx_plan(m, kdim, ncols, bits, std::max(cus, 1));
     if ((rc = pg_plan_out("nnc_cbpk_dx_plan", p, bits, cus, out)) != NNC_OK) return rc;
     const int64_t v[NNC_CBPKDX_PLAN_LEN] = {p.path, p.vb, p.mt, p.cols, p.copies, p.entries, p.splits, p.per_split, p.lds, p.col_tiles, p.row_tiles,
-                                            pg_dx_ws_bytes(p, m, kdim)};
+                                            cbg_dx_ws_bytes(p.splits, m, kdim)};
     for (int i = 0; i < NNC_CBPKDX_PLAN_LEN; ++i) out[i] = v[i];
     return NNC_OK;
 }
@@ -534,11 +448,8 @@ extern "C" int nnc_cbpk_dx_f32(const float *g, int64_t m, int64_t kdim, const vo
     if (!centers_dev) return fail(NNC_EINVAL, "nnc_cbpk_dx_f32: centers is NULL");
     if (m > 0 && kdim > 0 && !dx) return fail(NNC_EINVAL, "nnc_cbpk_dx_f32: dx is NULL");
     if (m > 0 && kdim > 0 && ncols > 0 && !g) return fail(NNC_EINVAL, "nnc_cbpk_dx_f32: g is NULL");
-    if (workspace_bytes < 0) return fail(NNC_EINVAL, "nnc_cbpk_dx_f32: negative workspace size");
     const int64_t need = nnc_cbpk_dx_workspace_bytes(m, kdim, ncols, bits);
-    if (workspace_bytes < need) return fail(NNC_ENOSPACE, "nnc_cbpk_dx_f32: workspace smaller than nnc_cbpk_dx_workspace_bytes()");
-    if (need > 0 && !workspace) return fail(NNC_EINVAL, "nnc_cbpk_dx_f32: workspace is NULL");
-    if (need > 0 && reinterpret_cast<uintptr_t>(workspace) % 4) return fail(NNC_EINVAL, "nnc_cbpk_dx_f32: workspace must be 4-byte aligned");
+    if ((rc = cb_check_workspace(fn, "nnc_cbpk_dx_workspace_bytes", workspace, workspace_bytes, need, 4, "workspace must be 4-byte aligned")) != NNC_OK) return rc;
     PgPlan p = pg_dx_plan(m, kdim, ncols, bits, CB_PLAN_CUS);
     const PgCase *pc = p.path == NNC_CBMM_STREAM ? find_pg_case(bits, p.vb, p.mt) : nullptr;
     if (p.path == NNC_CBMM_STREAM && !pc) return no_pg_case(fn, bits, p.vb, p.mt);
@@ -577,7 +488,7 @@ extern "C" int64_t nnc_cbpk_dc_workspace_bytes(int64_t m, int64_t kdim, int64_t 
     if (pg_check("nnc_cbpk_dc_workspace_bytes", m, kdim, ncols, bits, k) != NNC_OK) return 0;
     PgPlan p;
     if (pg_dc_plan(m, kdim, ncols, bits, k, CB_PLAN_CUS, p) != NNC_OK) return 0;
-    return pg_dc_ws_bytes(p, k);
+    return cbg_dc_ws_bytes(p.path, k);
 }
 
 extern "C" int nnc_cbpk_dc_plan(int64_t m, int64_t kdim, int64_t ncols, int bits, int32_t k, int32_t cus, int64_t *out)
@@ -588,7 +499,7 @@ extern "C" int nnc_cbpk_dc_plan(int64_t m, int64_t kdim, int64_t ncols, int bits
     if ((rc = pg_dc_plan(m, kdim, ncols, bits, k, std::max(cus, 1), p)) != NNC_OK) return rc;
     if ((rc = pg_plan_out("nnc_cbpk_dc_plan", p, bits, cus, out)) != NNC_OK) return rc;
     const int64_t v[NNC_CBPKDC_PLAN_LEN] = {p.path, p.vb, p.mt, p.cols, p.path == NNC_CBMM_ZERO ? 0 : p.copies, p.splits, p.per_split, p.lds,
-                                            p.col_tiles, p.row_tiles, p.terms_log2, pg_dc_ws_bytes(p, k)};
+                                            p.col_tiles, p.row_tiles, p.terms_log2, cbg_dc_ws_bytes(p.path, k)};
     for (int i = 0; i < NNC_CBPKDC_PLAN_LEN; ++i) out[i] = v[i];
     return NNC_OK;
 }
@@ -602,13 +513,10 @@ extern "C" int nnc_cbpk_dc_f32(const float *x, const float *g, int64_t m, int64_
     if ((rc = pk_check_buffer(fn, packed, packed_bytes, kdim, ncols, bits)) != NNC_OK) return rc;
     if (!dc) return fail(NNC_EINVAL, "nnc_cbpk_dc_f32: dc is NULL");
     if (m > 0 && kdim > 0 && ncols > 0 && (!x || !g)) return fail(NNC_EINVAL, "nnc_cbpk_dc_f32: x or g is NULL");
-    if (workspace_bytes < 0) return fail(NNC_EINVAL, "nnc_cbpk_dc_f32: negative workspace size");
     PgPlan p;
     if ((rc = pg_dc_plan(m, kdim, ncols, bits, k, CB_PLAN_CUS, p)) != NNC_OK) return rc;
-    const int64_t need = pg_dc_ws_bytes(p, k);
-    if (workspace_bytes < need) return fail(NNC_ENOSPACE, "nnc_cbpk_dc_f32: workspace smaller than nnc_cbpk_dc_workspace_bytes()");
-    if (need > 0 && !workspace) return fail(NNC_EINVAL, "nnc_cbpk_dc_f32: workspace is NULL");
-    if (need > 0 && reinterpret_cast<uintptr_t>(workspace) % 8 != 0) return fail(NNC_EINVAL, "nnc_cbpk_dc_f32: workspace not 8-byte aligned");
+    const int64_t need = cbg_dc_ws_bytes(p.path, k);
+    if ((rc = cb_check_workspace(fn, "nnc_cbpk_dc_workspace_bytes", workspace, workspace_bytes, need, 8, "workspace not 8-byte aligned")) != NNC_OK) return rc;
     const PgCase *pc = p.path == NNC_CBMM_STREAM ? find_pg_case(bits, p.vb, p.mt) : nullptr;
     if (p.path == NNC_CBMM_STREAM && !pc) return no_pg_case(fn, bits, p.vb, p.mt);
 

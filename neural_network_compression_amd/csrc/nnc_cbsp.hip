@@ -22,10 +22,12 @@
 //                  count + v_mbcnt(word); the d table sits in LDS with one copy per bank (CbTable); x[r, i] is broadcast by
 //                  v_readlane; the symbol loads of CB_UNROLL rows are in flight together.  The row sums of x are kept on the
 //                  side (one add per lane per CB_UNROLL rows) and combined in a fixed order.
-//   k_cbsp_tiled   m > 16: the W tile decoded from bitmap and symbols into LDS, then the FMA step of k_cbmm_tiled.
+//   k_cbsp_tiled   m > 16: the W tile decoded from bitmap and symbols into LDS, then the FMA step of k_cbmm_tiled; the tile
+//                  coordinates and the x tile load are nnc_cbtile.hpp's, the kept mask, the masked step and the store its own.
 //   k_cbsp_rowsum  m > 16: sum_i x[r, i], one workgroup per row, in a fixed order.
 //   k_cbsp_reduce  the split-K partials in split order, + c_z * row sum, + bias, ReLU.  No float atomics anywhere.
 #include "nnc_cbsp.hpp"
+#include "nnc_cbtile.hpp"
 
 #define SP_ROWS 64                // rows whose bitmap words one vector load brings to a wave
 #define SP_PLAN_LEN NNC_CBSP_PLAN_LEN
@@ -174,7 +176,7 @@ static SpPlan sp_plan(long long m, long long kdim, long long ncols, int lb, int 
     if (m <= CB_SKINNY_M) {
         p.path = NNC_CBMM_STREAM;
         p.rowsum = NNC_CBSP_ROWSUM_FUSED;
-        p.mt = m <= 1 ? 1 : (m <= 2 ? 2 : (m <= 4 ? 4 : (m <= 8 ? 8 : 16)));
+        p.mt = cb_mt(m);
         p.col_tiles = cdiv(ncols, 64);
         p.row_tiles = 1;
         // four workgroups per CU; every wave keeps at least one batch of SP_ROWS rows; the partials (splits x m x ncols x 4 B)
@@ -363,68 +365,51 @@ __global__ __launch_bounds__(256) void k_cbsp_tiled(const float *__restrict__ x,
     const float cz = sp_cz(centers, k, z);
     for (int j = threadIdx.x; j <= k; j += 256) tab[j] = (j < k ? centers[j] : 0.0f) - cz;
 
-    const int t = threadIdx.x, tx = t & 15, ty = t >> 4;
-    const long long n0 = (blockIdx.x % col_tiles) * TB_N, m0 = (blockIdx.x / col_tiles) * TB_M;
-    const long long k_lo = (long long)blockIdx.y * rows_per_split, k_hi = std::min(kdim, k_lo + rows_per_split);
+    const TbTile T = tb_tile(col_tiles, rows_per_split, kdim);
     float acc[8][8];
-#pragma unroll
-    for (int a = 0; a < 8; ++a)
-#pragma unroll
-        for (int b = 0; b < 8; ++b) acc[a][b] = 0.0f;
+    tb_clear(acc);
 
-    const int xr = t >> 1, xk = (t & 1) * 4;
-    const int wk = t >> 5, wc = (t & 31) * 4;
-    const long long gc = n0 + wc, gs = gc >> 6;
+    const int wk = threadIdx.x >> 5, wc = (threadIdx.x & 31) * 4;
+    const long long gc = T.n0 + wc, gs = gc >> 6;
     const int b0 = (int)(gc & 63);
-    int nonfinite = 0;
-    for (long long kb = k_lo; kb < k_hi; kb += TB_K) {
+    for (long long kb = T.lo; kb < T.hi; kb += TB_K) {
         __syncthreads();
-        {
-            const long long gr = m0 + xr;
+        const int nonfinite = tb_load_rows(xs, x, m, kdim, T.m0, kb, T.hi);
+        const long long gk = kb + wk;
+        float v[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+        uint32_t keep = 0;
+        if (gk < T.hi && gc < ncols) {
+            const long long gi = gk * segs;
+            const uint64_t word = bitmap[gi + gs];
+            long long pos = sp_count(lo[gi + gs], lo[gi], hi[gk]) + __popcll(word & ((1ULL << b0) - 1));
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
-                const long long gk = kb + xk + j;
-                const float xv = (gr < m && gk < k_hi) ? x[gr * kdim + gk] : 0.0f;
-                nonfinite |= !__builtin_isfinite(xv);
-                xs[(xk + j) * TB_M + xr] = xv;
-            }
-            const long long gk = kb + wk;
-            float v[4] = {0.0f, 0.0f, 0.0f, 0.0f};
-            uint32_t keep = 0;
-            if (gk < k_hi && gc < ncols) {
-                const long long gi = gk * segs;
-                const uint64_t word = bitmap[gi + gs];
-                long long pos = sp_count(lo[gi + gs], lo[gi], hi[gk]) + __popcll(word & ((1ULL << b0) - 1));
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    if ((word >> (b0 + j)) & 1) {
-                        const uint32_t l = pos < nnz ? (uint32_t)sym[pos] : (uint32_t)k;
-                        v[j] = tab[std::min(l, (uint32_t)k)];
-                        keep |= 1u << j;
-                        ++pos;
-                    }
+                if ((word >> (b0 + j)) & 1) {
+                    const uint32_t l = pos < nnz ? (uint32_t)sym[pos] : (uint32_t)k;
+                    v[j] = tab[std::min(l, (uint32_t)k)];
+                    keep |= 1u << j;
+                    ++pos;
                 }
             }
+        }
 #pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                ws[wk * TB_N + wc + j] = v[j];
-                kept[wk * TB_N + wc + j] = (unsigned char)((keep >> j) & 1);
-            }
+        for (int j = 0; j < 4; ++j) {
+            ws[wk * TB_N + wc + j] = v[j];
+            kept[wk * TB_N + wc + j] = (unsigned char)((keep >> j) & 1);
         }
         // a skipped weight is absent: where the x tile holds an Inf or NaN the FMA must not form x * 0 at a skipped position
         // (rare, so the whole workgroup takes the masked step for that tile only)
-        if (__syncthreads_or(nonfinite)) tb_tile_fma_masked(xs, ws, kept, tx, ty, acc);
-        else tb_tile_fma(xs, ws, tx, ty, acc);
-        nonfinite = 0;
+        if (__syncthreads_or(nonfinite)) tb_tile_fma_masked(xs, ws, kept, T.tx, T.ty, acc);
+        else tb_tile_fma(xs, ws, T.tx, T.ty, acc);
     }
 #pragma unroll
     for (int a = 0; a < 8; ++a) {
-        const long long r = m0 + ty * 8 + a;
+        const long long r = T.m0 + T.ty * 8 + a;
         if (r >= m) continue;
         const float rs = direct ? rowsum[r] : 0.0f;
 #pragma unroll
         for (int b = 0; b < 8; ++b) {
-            const long long c = n0 + tx * 8 + b;
+            const long long c = T.n0 + T.tx * 8 + b;
             if (c >= ncols) continue;
             if (direct) out[r * ncols + c] = sp_epilogue(acc[a][b], cz, rs, bias, c, relu);
             else out[((long long)blockIdx.y * m + r) * ncols + c] = acc[a][b];
@@ -652,10 +637,8 @@ extern "C" int nnc_cbsp_f32(const float *x, int64_t m, int64_t kdim, const void 
     if (m > 0 && ncols > 0 && !y) return fail(NNC_EINVAL, "nnc_cbsp_f32: y is NULL");
     if (m > 0 && ncols > 0 && kdim > 0 && (!x || !packed)) return fail(NNC_EINVAL, "nnc_cbsp_f32: x or packed is NULL");
     if (m > 0 && ncols > 0 && kdim > 0 && reinterpret_cast<uintptr_t>(packed) % 256) return fail(NNC_EINVAL, "nnc_cbsp_f32: packed must be 256-byte aligned");
-    if (workspace_bytes < 0) return fail(NNC_EINVAL, "nnc_cbsp_f32: negative workspace size");
     const int64_t need = nnc_cbsp_workspace_bytes(m, kdim, ncols, label_bytes);
-    if (workspace_bytes < need) return fail(NNC_ENOSPACE, "nnc_cbsp_f32: workspace smaller than nnc_cbsp_workspace_bytes()");
-    if (need > 0 && !workspace) return fail(NNC_EINVAL, "nnc_cbsp_f32: workspace is NULL");
+    if ((rc = cb_check_workspace("nnc_cbsp_f32", "nnc_cbsp_workspace_bytes", workspace, workspace_bytes, need)) != NNC_OK) return rc;
     if (m > 0 && ncols > 0 && kdim > 0 && reinterpret_cast<uintptr_t>(workspace) % 4) return fail(NNC_EINVAL, "nnc_cbsp_f32: workspace must be 4-byte aligned");
     if (m == 0 || ncols == 0) return NNC_OK;
 

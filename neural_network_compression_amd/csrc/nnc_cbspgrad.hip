@@ -17,16 +17,18 @@
 //                    product.  Column blocks are the splits, summed in block order by k_cbgrad_reduce.
 //   k_cbspdx_tiled   m > 16.  128 (r) x 128 (i) output tiles; the W^T tile is decoded into LDS from bitmap and symbols (d where
 //                    stored, 0 where skipped), then tb_tile_fma (the masked step for a g tile holding Inf / NaN).  ncols is split
-//                    into whole segments by a count that depends on the shape alone.
+//                    into whole segments by a count that depends on the shape alone.  The tile coordinates, the g tile load
+//                    and the store are nnc_cbtile.hpp's.
 //   k_cbspdx_rank1   dx += c_z * sum_o g[r, o], the row sums of g in a fixed order (k_cbsp_rowsum); nothing when c_z == 0.
 //   k_cbspdc_stream  m <= 16.  The grid and loads of k_cbspdx_stream; x[r, i] by v_readlane; dW[i, o] as k_cbdc_stream forms it.
 //                    A stored weight's image goes into the replicated LDS bins (64-bit integer atomics), a skipped one's into a
 //                    per-lane int64 register for bin z, flushed once per lane at the end.
-//   k_cbspdc_tiled   m > 16.  k_cbdc_tiled's tiles and splits of m; each of a thread's 64 values takes its label from the bitmap
-//                    word, the count and the popcount; the skipped ones are summed in a register.
+//   k_cbspdc_tiled   m > 16.  k_cbdc_tiled's tiles and splits of m (the prologue and tile fill of nnc_cbtile.hpp); each of a
+//                    thread's 64 values takes its label from the bitmap word, the count and the popcount; the skipped ones are
+//                    summed in a register.
 // k_cbgrad_absmax, k_cbdc_finish and k_cbgrad_reduce are nnc_cbgrad.hip's.  No float atomics; no host read.
-#include "nnc_cbgrad.hpp"
 #include "nnc_cbsp.hpp"
+#include "nnc_cbtile.hpp"
 
 // ------------------------------------------------------------------ plans (host)
 struct SgPlan {
@@ -41,16 +43,14 @@ struct SgPlan {
     long long lds;
 };
 
-static int sg_mt(long long m) { return m <= 1 ? 1 : (m <= 2 ? 2 : (m <= 4 ? 4 : (m <= 8 ? 8 : 16))); }
-
-// segments per column block: at most 32 g values per lane (the MT = 16 instantiation of k_cbdx_stream keeps 64 and spills)
+// segments per column block: at most 32 g values per lane
 __host__ __device__ constexpr int sg_segs(int mt) { return mt <= 4 ? 8 : 32 / mt; }
 
 static void sg_stream_grid(SgPlan &p, long long m, long long kdim, long long ncols, int cus)
 {
     cus = std::max(1, std::min(cus, CB_PLAN_CUS));
     p.path = NNC_CBMM_STREAM;
-    p.mt = sg_mt(m);
+    p.mt = cb_mt(m);
     p.segs = sg_segs(p.mt);
     p.col_tiles = cdiv(cdiv(ncols, 64), p.segs);
     const long long batch = 64 / p.segs;   // index rows per batch of a wave
@@ -128,8 +128,6 @@ static int sg_dc_plan(long long m, long long kdim, long long ncols, int lb, int 
     }
     return NNC_OK;
 }
-
-static int64_t sg_dc_ws_bytes(const SgPlan &p, int k) { return p.path == NNC_CBMM_STREAM || p.path == NNC_CBMM_TILED ? CBG_HDR_BYTES + 8LL * k : 0; }
 
 // ------------------------------------------------------------------ device helpers
 // The words and counts of a batch of 64 / E rows x E segments: lane l holds those of row ib + l / E, segment blk * E + l % E
@@ -252,66 +250,46 @@ __global__ __launch_bounds__(256) void k_cbspdx_tiled(const float *__restrict__ 
     const float cz = sp_cz(centers, k, z);
     for (int j = threadIdx.x; j <= k; j += 256) tab[j] = (j < k ? centers[j] : 0.0f) - cz;
 
-    const int t = threadIdx.x, tx = t & 15, ty = t >> 4;
-    const long long n0 = (blockIdx.x % col_tiles) * TB_N, m0 = (blockIdx.x / col_tiles) * TB_M;
-    const long long o_lo = (long long)blockIdx.y * cols_per_split, o_hi = std::min(ncols, o_lo + cols_per_split);
+    const TbTile T = tb_tile(col_tiles, cols_per_split, ncols);
     float acc[8][8];
+    tb_clear(acc);
+
+    const int lr = threadIdx.x >> 1, lq = (threadIdx.x & 1) * 4;   // W^T tile: index row n0 + lr, o lq..lq+3 (one segment), as the g tile
+    for (long long ob = T.lo; ob < T.hi; ob += TB_K) {
+        __syncthreads();
+        const int nonfinite = tb_load_rows(gs, g, m, ncols, T.m0, ob, T.hi);
+        const long long wi = T.n0 + lr, go = ob + lq;
+        float v[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+        uint32_t keep = 0;
+        if (wi < kdim && go < T.hi) {   // (bits past ncols are 0; a split ends on a segment boundary)
+            const long long gi = wi * segs, sg = go >> 6;
+            const int b0 = (int)(go & 63);
+            const uint64_t word = bitmap[gi + sg];
+            long long pos = sp_count(lo[gi + sg], lo[gi], hi[wi]) + __popcll(word & ((1ULL << b0) - 1));
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                if ((word >> (b0 + j)) & 1) {
+                    if (pos < nnz) {
+                        v[j] = tab[std::min((uint32_t)sym[pos], (uint32_t)k)];
+                        keep |= 1u << j;
+                    }
+                    ++pos;
+                }
+            }
+        }
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            ws[(lq + j) * TB_N + lr] = v[j];
+            kept[(lq + j) * TB_N + lr] = (unsigned char)((keep >> j) & 1);
+        }
+        // a skipped weight is absent: where the g tile holds an Inf or NaN the FMA must not form g * 0 at a skipped position
+        if (__syncthreads_or(nonfinite)) tb_tile_fma_masked(gs, ws, kept, T.tx, T.ty, acc);
+        else tb_tile_fma(gs, ws, T.tx, T.ty, acc);
+    }
 #pragma unroll
     for (int a = 0; a < 8; ++a)
 #pragma unroll
-        for (int b = 0; b < 8; ++b) acc[a][b] = 0.0f;
-
-    const int lr = t >> 1, lq = (t & 1) * 4;   // g tile: row lr, o lq..lq+3; W^T tile: index row n0 + lr, o lq..lq+3 (one segment)
-    int nonfinite = 0;
-    for (long long ob = o_lo; ob < o_hi; ob += TB_K) {
-        __syncthreads();
-        {
-            const long long gr = m0 + lr, wi = n0 + lr, go = ob + lq;
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const float gv = (gr < m && go + j < o_hi) ? g[gr * ncols + go + j] : 0.0f;
-                nonfinite |= !__builtin_isfinite(gv);
-                gs[(lq + j) * TB_M + lr] = gv;
-            }
-            float v[4] = {0.0f, 0.0f, 0.0f, 0.0f};
-            uint32_t keep = 0;
-            if (wi < kdim && go < o_hi) {   // (bits past ncols are 0; a split ends on a segment boundary)
-                const long long gi = wi * segs, sg = go >> 6;
-                const int b0 = (int)(go & 63);
-                const uint64_t word = bitmap[gi + sg];
-                long long pos = sp_count(lo[gi + sg], lo[gi], hi[wi]) + __popcll(word & ((1ULL << b0) - 1));
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    if ((word >> (b0 + j)) & 1) {
-                        if (pos < nnz) {
-                            v[j] = tab[std::min((uint32_t)sym[pos], (uint32_t)k)];
-                            keep |= 1u << j;
-                        }
-                        ++pos;
-                    }
-                }
-            }
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                ws[(lq + j) * TB_N + lr] = v[j];
-                kept[(lq + j) * TB_N + lr] = (unsigned char)((keep >> j) & 1);
-            }
-        }
-        // a skipped weight is absent: where the g tile holds an Inf or NaN the FMA must not form g * 0 at a skipped position
-        if (__syncthreads_or(nonfinite)) tb_tile_fma_masked(gs, ws, kept, tx, ty, acc);
-        else tb_tile_fma(gs, ws, tx, ty, acc);
-        nonfinite = 0;
-    }
-    float *dst = direct ? out : out + (long long)blockIdx.y * m * kdim;
-#pragma unroll
-    for (int a = 0; a < 8; ++a) {
-        const long long r = m0 + ty * 8 + a;
-#pragma unroll
-        for (int b = 0; b < 8; ++b) {
-            const long long c = n0 + tx * 8 + b;
-            if (r < m && c < kdim) dst[r * kdim + c] = acc[a][b];
-        }
-    }
+        for (int b = 0; b < 8; ++b) tb_store_dx(acc[a][b], T.m0 + T.ty * 8 + a, T.n0 + T.tx * 8 + b, m, kdim, direct, out);
 }
 
 // ------------------------------------------------------------------ dx += c_z * row sums of g (as sp_epilogue adds its rank-1 term)
@@ -430,58 +408,27 @@ __global__ __launch_bounds__(256) void k_cbspdc_tiled(const float *__restrict__ 
     float *xs = smem;                      // [TB_K][TB_M]: x[r, i0 + i]
     float *gs = xs + TB_K * TB_M;          // [TB_K][TB_N]: g[r, o0 + o]
     unsigned long long *bins = reinterpret_cast<unsigned long long *>(gs + TB_K * TB_N);
-    int flag;
-    const int S = cbdc_shift(hdr, m, terms_log2, flag);
-    if (blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0) {
-        hdr[2] = (uint32_t)S;
-        hdr[3] = (uint32_t)flag;
-    }
-    if (flag != CBG_FLAG_OK) return;
-    int scx, scg;
-    cbdc_scales(hdr, scx, scg);
-    const int Sw = S - scx - scg;
-    for (int j = threadIdx.x; j < (k << rlog2); j += 256) bins[j] = 0ull;
+    int scx, scg, Sw;
+    if (!cbdc_begin(hdr, m, terms_log2, bins, k << rlog2, scx, scg, Sw)) return;
 
-    const int t = threadIdx.x, tx = t & 15, ty = t >> 4;
-    const long long o0 = (blockIdx.x % col_tiles) * TB_N, i0 = (blockIdx.x / col_tiles) * TB_M;
-    const long long r_lo = (long long)blockIdx.y * rows_per_split, r_hi = std::min(m, r_lo + rows_per_split);
+    const TbTile T = tb_tile(col_tiles, rows_per_split, m);   // n0: the first column o, m0: the first index row i
     float acc[8][8];
-#pragma unroll
-    for (int a = 0; a < 8; ++a)
-#pragma unroll
-        for (int b = 0; b < 8; ++b) acc[a][b] = 0.0f;
-
-    const int lk = t >> 5, lc = (t & 31) * 4;   // both tiles: row r = rb + lk, columns lc..lc+3 (coalesced)
-    for (long long rb = r_lo; rb < r_hi; rb += TB_K) {
+    tb_clear(acc);
+    for (long long rb = T.lo; rb < T.hi; rb += TB_K) {
         __syncthreads();
-        {
-            const long long r = rb + lk;
-            const bool in_r = r < r_hi;
-            float xv[4], gv[4];
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const long long ii = i0 + lc + j, oo = o0 + lc + j;
-                xv[j] = x[cbdc_idx(r * kdim + ii, in_r && ii < kdim)];
-                gv[j] = g[cbdc_idx(r * ncols + oo, in_r && oo < ncols)];
-            }
-            __builtin_amdgcn_sched_barrier(0);   // (as k_cbdc_tiled)
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const long long ii = i0 + lc + j, oo = o0 + lc + j;
-                xs[lk * TB_M + lc + j] = cbdc_scaled(xv[j], in_r && ii < kdim, scx);
-                gs[lk * TB_N + lc + j] = cbdc_scaled(gv[j], in_r && oo < ncols, scg);
-            }
-        }
+        cbdc_load_tiles(xs, gs, x, g, kdim, ncols, T.m0, T.n0, rb, T.hi, scx, scg);
         __syncthreads();
-        tb_tile_fma(xs, gs, tx, ty, acc);
+        tb_tile_fma(xs, gs, T.tx, T.ty, acc);
     }
-    const int rep = t & ((1 << rlog2) - 1);
-    const long long ob = o0 + tx * 8, sg = ob >> 6;
+    // the binning is not cbdc_bin_tile's: a row's labels are read off one running position, and the skipped weights go to bin z
+    // through a register, not one atomic each
+    const int rep = threadIdx.x & ((1 << rlog2) - 1);
+    const long long ob = T.n0 + T.tx * 8, sg = ob >> 6;
     const int b0 = (int)(ob & 63);
     unsigned long long skip = 0;   // the images of the thread's skipped weights: bin z
 #pragma unroll
     for (int a = 0; a < 8; ++a) {
-        const long long i = i0 + ty * 8 + a;
+        const long long i = T.m0 + T.ty * 8 + a;
         if (i >= kdim || ob >= ncols) continue;
         const long long gi = i * segs;
         const uint64_t word = bitmap[gi + sg];
@@ -616,11 +563,8 @@ extern "C" int nnc_cbsp_dx_f32(const float *g, int64_t m, int64_t kdim, const vo
     if (!centers_dev) return fail(NNC_EINVAL, "nnc_cbsp_dx_f32: centers is NULL");
     if (m > 0 && kdim > 0 && !dx) return fail(NNC_EINVAL, "nnc_cbsp_dx_f32: dx is NULL");
     if (m > 0 && kdim > 0 && ncols > 0 && !g) return fail(NNC_EINVAL, "nnc_cbsp_dx_f32: g is NULL");
-    if (workspace_bytes < 0) return fail(NNC_EINVAL, "nnc_cbsp_dx_f32: negative workspace size");
     const int64_t need = nnc_cbsp_dx_workspace_bytes(m, kdim, ncols, label_bytes);
-    if (workspace_bytes < need) return fail(NNC_ENOSPACE, "nnc_cbsp_dx_f32: workspace smaller than nnc_cbsp_dx_workspace_bytes()");
-    if (need > 0 && !workspace) return fail(NNC_EINVAL, "nnc_cbsp_dx_f32: workspace is NULL");
-    if (need > 0 && reinterpret_cast<uintptr_t>(workspace) % 4) return fail(NNC_EINVAL, "nnc_cbsp_dx_f32: workspace must be 4-byte aligned");
+    if ((rc = cb_check_workspace(fn, "nnc_cbsp_dx_workspace_bytes", workspace, workspace_bytes, need, 4, "workspace must be 4-byte aligned")) != NNC_OK) return rc;
     const SgPlan p = sg_dx_plan(m, kdim, ncols, label_bytes, k, cu_count());
     const SgCase *sc = p.path == NNC_CBMM_STREAM ? find_sg_case(label_bytes, p.mt) : nullptr;
     if (p.path == NNC_CBMM_STREAM && !sc) return no_sg_case(fn, label_bytes, p.mt);
@@ -668,7 +612,7 @@ extern "C" int64_t nnc_cbsp_dc_workspace_bytes(int64_t m, int64_t kdim, int64_t 
     if (sg_check("nnc_cbsp_dc_workspace_bytes", m, kdim, ncols, label_bytes, k) != NNC_OK) return 0;
     SgPlan p;
     if (sg_dc_plan(m, kdim, ncols, label_bytes, k, CB_PLAN_CUS, p) != NNC_OK) return 0;
-    return sg_dc_ws_bytes(p, k);
+    return cbg_dc_ws_bytes(p.path, k);
 }
 
 extern "C" int nnc_cbsp_dc_plan(int64_t m, int64_t kdim, int64_t ncols, int label_bytes, int32_t k, int32_t cus, int64_t *out)
@@ -679,7 +623,7 @@ extern "C" int nnc_cbsp_dc_plan(int64_t m, int64_t kdim, int64_t ncols, int labe
     if ((rc = sg_dc_plan(m, kdim, ncols, label_bytes, k, cus, p)) != NNC_OK) return rc;
     if ((rc = sg_plan_out("nnc_cbsp_dc_plan", p, label_bytes, cus, out)) != NNC_OK) return rc;
     const int64_t v[NNC_CBSPDC_PLAN_LEN] = {p.path, p.mt, p.segs, p.path == NNC_CBMM_ZERO ? 0 : 1LL << p.rlog2, p.splits, p.per_split, p.lds,
-                                            p.col_tiles, p.row_tiles, p.terms_log2, sg_dc_ws_bytes(p, k)};
+                                            p.col_tiles, p.row_tiles, p.terms_log2, cbg_dc_ws_bytes(p.path, k)};
     for (int i = 0; i < NNC_CBSPDC_PLAN_LEN; ++i) out[i] = v[i];
     return NNC_OK;
 }
@@ -694,11 +638,8 @@ extern "C" int nnc_cbsp_dc_f32(const float *x, const float *g, int64_t m, int64_
     if ((rc = sg_check_form(fn, m, kdim, ncols, label_bytes, zero_symbol, nnz, packed, packed_bytes)) != NNC_OK) return rc;
     if (!dc) return fail(NNC_EINVAL, "nnc_cbsp_dc_f32: dc is NULL");
     if (m > 0 && kdim > 0 && ncols > 0 && (!x || !g)) return fail(NNC_EINVAL, "nnc_cbsp_dc_f32: x or g is NULL");
-    if (workspace_bytes < 0) return fail(NNC_EINVAL, "nnc_cbsp_dc_f32: negative workspace size");
     const int64_t need = nnc_cbsp_dc_workspace_bytes(m, kdim, ncols, label_bytes, k);
-    if (workspace_bytes < need) return fail(NNC_ENOSPACE, "nnc_cbsp_dc_f32: workspace smaller than nnc_cbsp_dc_workspace_bytes()");
-    if (need > 0 && !workspace) return fail(NNC_EINVAL, "nnc_cbsp_dc_f32: workspace is NULL");
-    if (need > 0 && reinterpret_cast<uintptr_t>(workspace) % 8 != 0) return fail(NNC_EINVAL, "nnc_cbsp_dc_f32: workspace not 8-byte aligned");
+    if ((rc = cb_check_workspace(fn, "nnc_cbsp_dc_workspace_bytes", workspace, workspace_bytes, need, 8, "workspace not 8-byte aligned")) != NNC_OK) return rc;
     SgPlan p;
     if ((rc = sg_dc_plan(m, kdim, ncols, label_bytes, k, cu_count(), p)) != NNC_OK) return rc;
     const SgCase *sc = p.path == NNC_CBMM_STREAM ? find_sg_case(label_bytes, p.mt) : nullptr;
