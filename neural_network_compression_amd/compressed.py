@@ -58,6 +58,14 @@ ops.packed_codebook_linear's backward forms dx and the centroid gradient from th
 the centroid gradient again the byte layer's bit for bit, and no byte-per-weight tensor stays resident while training.
 compress_network_trainable(..., packed=True | "auto") and Trainer.fine_tune_compressed(..., packed=...) give them, chosen per
 layer by the rule above applied to the trainable forms.
+
+How the classes are laid out: ``_Activated`` (the activation behind the product, ``get_weights``) is the root of
+``_InferenceLayer`` (the float32 ``centers`` / ``bias`` buffers behind the family's index buffer, ``nbytes``) and of
+``_TrainableCentres`` (the ``centers`` parameter, ``counts``, the three kinds of bias).  A family -- ``_CodebookLayer``,
+``GroupedCompressedDense``, ``_SparseCodebookLayer``, ``_PackedCodebookLayer`` and the three trainable ones -- adds its index
+buffer and the one ops call of ``_matmul``; ``_SparseForm`` / ``_PackedForm`` hold what the inference and the trainable layer of
+a form share (the ``packed`` buffer, the metadata, ``codes``).  ``_DenseHalf`` and ``_Conv2DHalf`` are the two forwards over
+``_matmul``; a public class is one of them on a family, with the constructors of its own signature.
 """
 from __future__ import annotations
 
@@ -85,7 +93,89 @@ def _decoded_bias(raw: torch.Tensor, bias_model) -> torch.Tensor:
     return ops.gather(centers, labels)
 
 
-class _CodebookLayer(nn.Module):
+def _require_model(weight_model):
+    if weight_model is None:
+        raise ValueError("the kernel was not quantized (no fitted model): keep the float32 layer")
+
+
+def _conv_shape(conv):
+    """(h, in, out) of a Keras (h, w, in, out) kernel, which has to be square."""
+    h, w, cin, cout = conv.kernel.shape
+    if h != w:
+        raise ValueError("square kernels only (as layers.Conv2D)")
+    return h, cin, cout
+
+
+def _inference_codes(layer, weight_model, bias_model):
+    """What from_dense / from_conv of the inference layers start from: (labels, centers, decoded bias), in the order the
+    from_codes take them."""
+    _require_model(weight_model)
+    centers, labels = _codes(weight_model, layer.kernel.device)
+    return labels, centers, _decoded_bias(layer.bias, bias_model)
+
+
+def _trainable_codes(layer, weight_model, bias_model):
+    """(labels, centers, raw bias, bias codes) of a trainable layer: a quantized bias keeps its codes, a raw one stays frozen."""
+    _require_model(weight_model)
+    centers, labels = _codes(weight_model, layer.kernel.device)
+    bias, bias_codes = (None, _codes(bias_model, layer.kernel.device)) if bias_model is not None else (layer.bias, None)
+    return labels, centers, bias, bias_codes
+
+
+def _tensor_bytes(*tensors) -> int:
+    return sum(t.numel() * t.element_size() for t in tensors if t is not None)
+
+
+class _Activated(nn.Module):
+    """What every layer here does behind its product: the activation (a ReLU is fused into the kernel, any other applied to
+    its result) and the empty Keras weight list."""
+
+    def _set_activation(self, activation):
+        self.activation = activation
+        self._fused_relu = activation is torch.relu
+
+    def _activate(self, y: torch.Tensor) -> torch.Tensor:
+        if self.activation is not None and not self._fused_relu:
+            y = self.activation(y)
+        return y
+
+    def get_weights(self):
+        return []
+
+
+class _InferenceLayer(_Activated):
+    """The base of the four inference families: behind the index buffer ``_INDEX`` names (registered first by the family), the
+    float32 buffers centers and bias (or None)."""
+
+    _INDEX = "labels"
+
+    def _init_codebook(self, centers: torch.Tensor, bias: torch.Tensor | None, activation):
+        self.register_buffer("centers", centers.to(torch.float32).contiguous())
+        self.register_buffer("bias", None if bias is None else bias.reshape(-1).to(torch.float32).contiguous())
+        self._set_activation(activation)
+
+    def nbytes(self) -> int:
+        return _tensor_bytes(getattr(self, self._INDEX), self.centers, self.bias)
+
+
+class _DenseHalf:
+    """A Dense layer's forward over a family's ``_matmul``."""
+
+    def forward(self, x: torch.Tensor) -> torch.Tensor:
+        return self._matmul(x.contiguous())
+
+
+class _Conv2DHalf:
+    """A Conv2D layer's geometry and forward over a family's ``_matmul``."""
+
+    def _set_conv(self, kernel_size: int, cin: int, pad: int):
+        self.kernel_size, self.cin, self.pad = int(kernel_size), int(cin), int(pad)
+
+    def forward(self, x: torch.Tensor) -> torch.Tensor:   # x: (N, H, W, C)
+        return _conv_forward(self, x)
+
+
+class _CodebookLayer(_InferenceLayer):
     """labels (kdim * ncols indices, row-major (kdim, ncols)), centers float32[K], bias float32[ncols] or None.  A bfloat16 or
     float16 input gives an output of that dtype (ops.codebook_matmul); centers and bias stay float32: feed half inputs, leave the
     module float32 (after ``.half()`` / ``.bfloat16()`` on the module the forward raises ops.codebook_matmul's dtype TypeError)."""
@@ -96,40 +186,23 @@ class _CodebookLayer(nn.Module):
             raise ValueError(f"{labels.numel()} indices for a {kdim} x {ncols} weight matrix")
         self.kdim, self.ncols = int(kdim), int(ncols)
         self.register_buffer("labels", labels.reshape(-1))
-        self.register_buffer("centers", centers.reshape(-1).to(torch.float32).contiguous())
-        self.register_buffer("bias", None if bias is None else bias.reshape(-1).to(torch.float32).contiguous())
-        self.activation = activation
-        self._fused_relu = activation is torch.relu
+        self._init_codebook(centers.reshape(-1), bias, activation)
 
     def _matmul(self, x: torch.Tensor) -> torch.Tensor:
-        y = ops.codebook_matmul(x, self.labels, self.centers, self.kdim, self.ncols, bias=self.bias, relu=self._fused_relu)
-        if self.activation is not None and not self._fused_relu:
-            y = self.activation(y)
-        return y
-
-    def get_weights(self):
-        return []
-
-    def nbytes(self) -> int:
-        return sum(t.numel() * t.element_size() for t in (self.labels, self.centers, self.bias) if t is not None)
+        return self._activate(ops.codebook_matmul(x, self.labels, self.centers, self.kdim, self.ncols, bias=self.bias, relu=self._fused_relu))
 
 
-class CompressedDense(_CodebookLayer):
+class CompressedDense(_DenseHalf, _CodebookLayer):
     """Dense run from its codebook: y = act(x @ kernel + bias), kernel (in, out) as Keras stores it (kdim = in, ncols = out)."""
 
     @classmethod
     def from_dense(cls, dense, weight_model, bias_model=None) -> "CompressedDense":
-        if weight_model is None:
-            raise ValueError("the kernel was not quantized (no fitted model): keep the float32 layer")
+        codes = _inference_codes(dense, weight_model, bias_model)
         kin, kout = dense.kernel.shape
-        centers, labels = _codes(weight_model, dense.kernel.device)
-        return cls(kin, kout, labels, centers, _decoded_bias(dense.bias, bias_model), dense.activation)
-
-    def forward(self, x: torch.Tensor) -> torch.Tensor:
-        return self._matmul(x.contiguous())
+        return cls(kin, kout, *codes, dense.activation)
 
 
-class GroupedCompressedDense(nn.Module):
+class GroupedCompressedDense(_DenseHalf, _InferenceLayer):
     """Dense run from one codebook per block of ``group_rows`` input rows: labels (kdim * ncols uint8 indices, row-major),
     centers float32 (G, K), G = ceil(kdim / group_rows), bias float32[ncols] or None.  The path follows the input's dtype as in
     CompressedDense (float32, bfloat16, float16; the output has the input's dtype); centers and bias stay float32."""
@@ -146,16 +219,12 @@ class GroupedCompressedDense(nn.Module):
             raise ValueError(f"centers must have shape ({groups}, K) for {kdim} rows in groups of {group_rows}, got {tuple(centers.shape)}")
         self.kdim, self.ncols, self.group_rows = int(kdim), int(ncols), int(group_rows)
         self.register_buffer("labels", labels.reshape(-1))
-        self.register_buffer("centers", centers.to(torch.float32).contiguous())
-        self.register_buffer("bias", None if bias is None else bias.reshape(-1).to(torch.float32).contiguous())
-        self.activation = activation
-        self._fused_relu = activation is torch.relu
+        self._init_codebook(centers, bias, activation)
 
     @classmethod
     def from_dense(cls, dense, weight_model, bias_model=None) -> "GroupedCompressedDense":
         """From a Dense layer and the GroupedModel of its kernel (utility.get_quantized_weight_grouped)."""
-        if weight_model is None:
-            raise ValueError("the kernel was not quantized (no fitted model): keep the float32 layer")
+        _require_model(weight_model)
         kin, kout = dense.kernel.shape
         centers = torch.from_numpy(np.ascontiguousarray(weight_model.cluster_centers_, dtype=np.float32)).to(dense.kernel.device)
         return cls(kin, kout, weight_model.group_rows, weight_model.labels_compact_, centers, _decoded_bias(dense.bias, bias_model), dense.activation)
@@ -164,18 +233,9 @@ class GroupedCompressedDense(nn.Module):
     def from_codes(cls, kdim, ncols, group_rows, labels, centers, bias, activation) -> "GroupedCompressedDense":
         return cls(kdim, ncols, group_rows, labels, centers, bias, activation)
 
-    def forward(self, x: torch.Tensor) -> torch.Tensor:
-        y = ops.grouped_codebook_matmul(x.contiguous(), self.labels, self.centers, self.kdim, self.ncols, self.group_rows, bias=self.bias,
-                                        relu=self._fused_relu)
-        if self.activation is not None and not self._fused_relu:
-            y = self.activation(y)
-        return y
-
-    def get_weights(self):
-        return []
-
-    def nbytes(self) -> int:
-        return sum(t.numel() * t.element_size() for t in (self.labels, self.centers, self.bias) if t is not None)
+    def _matmul(self, x: torch.Tensor) -> torch.Tensor:
+        return self._activate(ops.grouped_codebook_matmul(x, self.labels, self.centers, self.kdim, self.ncols, self.group_rows, bias=self.bias,
+                                                          relu=self._fused_relu))
 
 
 def _is_grouped(model) -> bool:
@@ -202,32 +262,25 @@ def conv_patches(x: torch.Tensor, kernel_size: int, pad: int) -> torch.Tensor:
     return p.transpose(1, 2)
 
 
-class CompressedConv2D(_CodebookLayer):
+class CompressedConv2D(_Conv2DHalf, _CodebookLayer):
     """Conv2D (stride 1, NHWC) run from its codebook: the patches of x times the kernel read from its indices, whose rows are
     put in unfold order once at construction (keras_rows_for_unfold)."""
 
     def __init__(self, kernel_size: int, cin: int, cout: int, pad: int, labels_unfold: torch.Tensor, centers: torch.Tensor,
                  bias: torch.Tensor | None, activation=None):
         super().__init__(kernel_size * kernel_size * cin, cout, labels_unfold, centers, bias, activation)
-        self.kernel_size, self.cin, self.pad = int(kernel_size), int(cin), int(pad)
+        self._set_conv(kernel_size, cin, pad)
 
     @classmethod
     def from_conv(cls, conv, weight_model, bias_model=None) -> "CompressedConv2D":
-        if weight_model is None:
-            raise ValueError("the kernel was not quantized (no fitted model): keep the float32 layer")
-        h, w, cin, cout = conv.kernel.shape
-        if h != w:
-            raise ValueError("square kernels only (as layers.Conv2D)")
-        centers, labels = _codes(weight_model, conv.kernel.device)
-        return cls.from_codes(h, cin, cout, conv.pad, labels, centers, _decoded_bias(conv.bias, bias_model), conv.activation)
+        codes = _inference_codes(conv, weight_model, bias_model)
+        h, cin, cout = _conv_shape(conv)
+        return cls.from_codes(h, cin, cout, conv.pad, *codes, conv.activation)
 
     @classmethod
     def from_codes(cls, kernel_size, cin, cout, pad, labels, centers, bias, activation) -> "CompressedConv2D":
         """labels in the Keras order of the (h, w, in, out) kernel."""
         return cls(kernel_size, cin, cout, pad, _unfold_labels(kernel_size, cin, cout, labels), centers, bias, activation)
-
-    def forward(self, x: torch.Tensor) -> torch.Tensor:   # x: (N, H, W, C)
-        return _conv_forward(self, x)
 
 
 def _conv_forward(layer, x: torch.Tensor) -> torch.Tensor:
@@ -248,6 +301,17 @@ def _unfold_labels(kernel_size: int, cin: int, cout: int, labels: torch.Tensor) 
     return labels.reshape(-1, cout)[rows].contiguous()
 
 
+def _unfold_then_pack(pack, kernel_size: int, cin: int, cout: int, labels: torch.Tensor, k: int, option):
+    """The codes of a Conv2D layer: ``pack`` (ops.pack_sparse_codes with its zero_symbol, ops.pack_codes with its bits) over the
+    labels in unfold order, which are dropped once packed."""
+    return pack(_unfold_labels(kernel_size, cin, cout, labels), kernel_size * kernel_size * cin, cout, k, option)
+
+
+def _check_conv_rows(codes, kernel_size: int, cin: int):
+    if codes.kdim != kernel_size * kernel_size * cin:
+        raise ValueError(f"{codes.kdim} index rows for a {kernel_size} x {kernel_size} x {cin} kernel")
+
+
 class _GatherCenters(torch.autograd.Function):
     """centers[labels] (ops.gather) with the centroid gradient of the result (ops.centroid_gradient) as the backward."""
 
@@ -263,7 +327,7 @@ class _GatherCenters(torch.autograd.Function):
         return ops.centroid_gradient(grad.contiguous(), labels, ctx.k).to(torch.float32), None
 
 
-class _TrainableCentres(nn.Module):
+class _TrainableCentres(_Activated):
     """What the trainable layers share: centers a float32[K] nn.Parameter, counts (the histogram of the kdim * ncols indices, for
     kernel_sq_sum) a buffer, and the bias: a quantized one (bias_labels buffer + bias_centers parameter), a frozen raw one (bias
     buffer) or None."""
@@ -282,29 +346,19 @@ class _TrainableCentres(nn.Module):
             self.register_buffer("bias_labels", None)
             self.bias_centers = None
             self.register_buffer("bias", None if bias is None else bias.detach().reshape(-1).to(torch.float32).clone())
-        self.activation = activation
-        self._fused_relu = activation is torch.relu
+        self._set_activation(activation)
 
     def current_bias(self) -> torch.Tensor | None:
         if self.bias_centers is not None:
             return _GatherCenters.apply(self.bias_centers, self.bias_labels)
         return self.bias
 
-    def _activate(self, y: torch.Tensor) -> torch.Tensor:
-        if self.activation is not None and not self._fused_relu:
-            y = self.activation(y)
-        return y
-
     def kernel_sq_sum(self) -> torch.Tensor:
         """sum of kernel^2 = sum_k count_k * c_k^2, differentiable in the centres, without W."""
         return (self.counts.to(torch.float32) * self.centers ** 2).sum()
 
-    def get_weights(self):
-        return []
-
     def _nbytes(self, indices: torch.Tensor) -> int:
-        ts = (indices, self.centers, self.bias, self.bias_labels, self.bias_centers)
-        return sum(t.numel() * t.element_size() for t in ts if t is not None)
+        return _tensor_bytes(indices, self.centers, self.bias, self.bias_labels, self.bias_centers)
 
 
 class _TrainableCodebookLayer(_TrainableCentres):
@@ -327,392 +381,284 @@ class _TrainableCodebookLayer(_TrainableCentres):
         return self._nbytes(self.labels)
 
 
-class TrainableCompressedDense(_TrainableCodebookLayer):
+class TrainableCompressedDense(_DenseHalf, _TrainableCodebookLayer):
     """CompressedDense with trainable centres (ops.codebook_linear)."""
 
-    def forward(self, x: torch.Tensor) -> torch.Tensor:
-        return self._matmul(x.contiguous())
 
-
-class TrainableCompressedConv2D(_TrainableCodebookLayer):
+class TrainableCompressedConv2D(_Conv2DHalf, _TrainableCodebookLayer):
     """CompressedConv2D with trainable centres: the patches (F.unfold, chunked as CompressedConv2D) through ops.codebook_linear;
     autograd carries the patch gradients back through the unfold."""
 
     def __init__(self, kernel_size: int, cin: int, cout: int, pad: int, labels_unfold: torch.Tensor, centers: torch.Tensor, bias=None,
                  bias_codes=None, activation=None):
         super().__init__(kernel_size * kernel_size * cin, cout, labels_unfold, centers, bias, bias_codes, activation)
-        self.kernel_size, self.cin, self.pad = int(kernel_size), int(cin), int(pad)
-
-    def forward(self, x: torch.Tensor) -> torch.Tensor:   # x: (N, H, W, C)
-        return _conv_forward(self, x)
+        self._set_conv(kernel_size, cin, pad)
 
 
-def _trainable_codes(layer, weight_model, bias_model):
-    """(centers, labels, raw bias, bias codes) of a trainable layer: a quantized bias keeps its codes, a raw one stays frozen."""
-    if weight_model is None:
-        raise ValueError("the kernel was not quantized (no fitted model): keep the float32 layer")
-    centers, labels = _codes(weight_model, layer.kernel.device)
-    bias, bias_codes = (None, _codes(bias_model, layer.kernel.device)) if bias_model is not None else (layer.bias, None)
-    return centers, labels, bias, bias_codes
-
-
-def _trainable(layer, weight_model, bias_model):
+def _trainable(layer, weight_model, bias_model, dense_cls=None, conv_cls=None):
+    """The trainable layer of ``layer``, the one Dense / Conv2D dispatch of the trainable forms: through from_dense / from_conv
+    of ``dense_cls`` / ``conv_cls`` (the bitmap-sparse or the packed pair), or, without them, the byte classes built here."""
     from .neural_networks.layers import Conv2D, Dense
 
-    centers, labels, bias, bias_codes = _trainable_codes(layer, weight_model, bias_model)
+    if dense_cls is None:   # the byte form takes its codes before it looks at the layer's type, as it always did
+        labels, centers, bias, bias_codes = _trainable_codes(layer, weight_model, bias_model)
     if isinstance(layer, Dense):
+        if dense_cls is not None:
+            return dense_cls.from_dense(layer, weight_model, bias_model)
         kin, kout = layer.kernel.shape
         return TrainableCompressedDense(kin, kout, labels, centers, bias, bias_codes, layer.activation)
     if isinstance(layer, Conv2D):
-        h, w, cin, cout = layer.kernel.shape
-        if h != w:
-            raise ValueError("square kernels only (as layers.Conv2D)")
+        if conv_cls is not None:
+            return conv_cls.from_conv(layer, weight_model, bias_model)
+        h, cin, cout = _conv_shape(layer)
         return TrainableCompressedConv2D(h, cin, cout, layer.pad, _unfold_labels(h, cin, cout, labels), centers, bias, bias_codes,
                                          layer.activation)
     raise TypeError(f"no compressed form of {type(layer).__name__}")
 
 
-class _SparseCodebookLayer(nn.Module):
-    """The indices in the bitmap-sparse form (ops.SparseCodes: its buffer is the module's ``packed`` buffer), centers float32[K],
-    bias float32[ncols] or None.  No kdim * ncols tensor stays resident."""
+class _SparseForm:
+    """What the inference and the trainable bitmap-sparse layers keep of an ops.SparseCodes: its buffer as the module's ``packed``
+    buffer and its metadata as attributes, from which ``codes`` is the same SparseCodes again."""
 
-    def __init__(self, codes: ops.SparseCodes, centers: torch.Tensor, bias: torch.Tensor | None, activation=None):
-        super().__init__()
+    _INDEX = "packed"
+    _product, _linear = staticmethod(ops.sparse_codebook_matmul), staticmethod(ops.sparse_codebook_linear)
+
+    def _take_codes(self, codes: ops.SparseCodes):
         self.kdim, self.ncols = codes.kdim, codes.ncols
         self.k, self.zero_symbol, self.label_bytes, self.nnz = codes.k, codes.zero_symbol, codes.label_bytes, codes.nnz
-        if centers.numel() != codes.k:
-            raise ValueError(f"{centers.numel()} centres for indices into a codebook of {codes.k}")
         self.register_buffer("packed", codes.buf)
-        self.register_buffer("centers", centers.reshape(-1).to(torch.float32).contiguous())
-        self.register_buffer("bias", None if bias is None else bias.reshape(-1).to(torch.float32).contiguous())
-        self.activation = activation
-        self._fused_relu = activation is torch.relu
 
     @property
     def codes(self) -> ops.SparseCodes:
         return ops.SparseCodes(self.packed, self.kdim, self.ncols, self.k, self.zero_symbol, self.label_bytes, self.nnz)
 
+
+class _PackedForm:
+    """What the inference and the trainable packed layers keep of an ops.PackedCodes: its buffer as the module's ``packed``
+    buffer and its metadata as attributes, from which ``codes`` is the same PackedCodes again."""
+
+    _INDEX = "packed"
+    _product, _linear = staticmethod(ops.packed_codebook_matmul), staticmethod(ops.packed_codebook_linear)
+
+    def _take_codes(self, codes: ops.PackedCodes):
+        self.kdim, self.ncols, self.bits, self.k = codes.kdim, codes.ncols, codes.bits, codes.k
+        self.register_buffer("packed", codes.packed)
+
+    @property
+    def codes(self) -> ops.PackedCodes:
+        return ops.PackedCodes(self.packed, self.kdim, self.ncols, self.bits, self.k)
+
+
+class _CodesLayer(_InferenceLayer):
+    """An inference layer over a form's codes (_SparseForm, _PackedForm): centers float32[K], bias float32[ncols] or None.  No
+    kdim * ncols tensor stays resident."""
+
+    def __init__(self, codes, centers: torch.Tensor, bias: torch.Tensor | None, activation=None):
+        super().__init__()
+        self._take_codes(codes)
+        if centers.numel() != codes.k:
+            raise ValueError(f"{centers.numel()} centres for indices into a codebook of {codes.k}")
+        self._init_codebook(centers.reshape(-1), bias, activation)
+
     def _matmul(self, x: torch.Tensor) -> torch.Tensor:
-        y = ops.sparse_codebook_matmul(x, self.codes, self.centers, bias=self.bias, relu=self._fused_relu)
-        if self.activation is not None and not self._fused_relu:
-            y = self.activation(y)
-        return y
-
-    def get_weights(self):
-        return []
-
-    def nbytes(self) -> int:
-        return sum(t.numel() * t.element_size() for t in (self.packed, self.centers, self.bias) if t is not None)
+        return self._activate(self._product(x, self.codes, self.centers, bias=self.bias, relu=self._fused_relu))
 
 
-class SparseCompressedDense(_SparseCodebookLayer):
-    """Dense run from its codebook and the bitmap-sparse form of its (in, out) indices."""
+class _TrainableCodesLayer(_TrainableCentres):
+    """A trainable layer over a form's codes: the ``packed`` buffer with the centres, counts and bias of _TrainableCentres; the
+    forward goes through the form's ops.*_codebook_linear, whose backward forms dx and the centroid gradient from the stored form.
+    ``counts`` is taken from the labels before packing, so kernel_sq_sum() is the byte trainable layer's bit for bit.  No
+    kdim * ncols tensor stays resident."""
 
-    @classmethod
-    def from_dense(cls, dense, weight_model, bias_model=None, zero_symbol=None) -> "SparseCompressedDense":
-        if weight_model is None:
-            raise ValueError("the kernel was not quantized (no fitted model): keep the float32 layer")
-        kin, kout = dense.kernel.shape
-        centers, labels = _codes(weight_model, dense.kernel.device)
-        return cls.from_codes(kin, kout, labels, centers, _decoded_bias(dense.bias, bias_model), dense.activation, zero_symbol)
-
-    @classmethod
-    def from_codes(cls, kdim, ncols, labels, centers, bias, activation, zero_symbol=None) -> "SparseCompressedDense":
-        return cls(ops.pack_sparse_codes(labels, kdim, ncols, centers.numel(), zero_symbol), centers, bias, activation)
-
-    def forward(self, x: torch.Tensor) -> torch.Tensor:
-        return self._matmul(x.contiguous())
-
-
-class SparseCompressedConv2D(_SparseCodebookLayer):
-    """Conv2D (stride 1, NHWC) run from its codebook and the bitmap-sparse form of its indices, packed after the rows were put
-    in unfold order (keras_rows_for_unfold); patch chunking and the empty batch as CompressedConv2D."""
-
-    def __init__(self, kernel_size: int, cin: int, pad: int, codes: ops.SparseCodes, centers: torch.Tensor, bias: torch.Tensor | None,
-                 activation=None):
-        if codes.kdim != kernel_size * kernel_size * cin:
-            raise ValueError(f"{codes.kdim} index rows for a {kernel_size} x {kernel_size} x {cin} kernel")
-        super().__init__(codes, centers, bias, activation)
-        self.kernel_size, self.cin, self.pad = int(kernel_size), int(cin), int(pad)
-
-    @classmethod
-    def from_conv(cls, conv, weight_model, bias_model=None, zero_symbol=None) -> "SparseCompressedConv2D":
-        if weight_model is None:
-            raise ValueError("the kernel was not quantized (no fitted model): keep the float32 layer")
-        h, w, cin, cout = conv.kernel.shape
-        if h != w:
-            raise ValueError("square kernels only (as layers.Conv2D)")
-        centers, labels = _codes(weight_model, conv.kernel.device)
-        return cls.from_codes(h, cin, cout, conv.pad, labels, centers, _decoded_bias(conv.bias, bias_model), conv.activation, zero_symbol)
-
-    @classmethod
-    def from_codes(cls, kernel_size, cin, cout, pad, labels, centers, bias, activation, zero_symbol=None) -> "SparseCompressedConv2D":
-        """labels in the Keras order of the (h, w, in, out) kernel."""
-        unf = _unfold_labels(kernel_size, cin, cout, labels)
-        codes = ops.pack_sparse_codes(unf, kernel_size * kernel_size * cin, cout, centers.numel(), zero_symbol)
-        del unf
-        return cls(kernel_size, cin, pad, codes, centers, bias, activation)
-
-    def forward(self, x: torch.Tensor) -> torch.Tensor:   # x: (N, H, W, C)
-        return _conv_forward(self, x)
-
-
-class _TrainableSparseCodebookLayer(_TrainableCentres):
-    """The indices in the bitmap-sparse form (the ``packed`` buffer, as _SparseCodebookLayer) with the centres, counts and bias of
-    _TrainableCentres; the forward goes through ops.sparse_codebook_linear, whose backward forms dx and the centroid gradient
-    from the packed form (csrc/nnc_cbspgrad.hip).  ``counts`` is taken from the labels before packing, so kernel_sq_sum() is the
-    dense trainable layer's bit for bit.  No kdim * ncols tensor stays resident."""
-
-    def __init__(self, codes: ops.SparseCodes, labels: torch.Tensor, centers: torch.Tensor, bias: torch.Tensor | None = None,
-                 bias_codes=None, activation=None):
+    def __init__(self, codes, labels: torch.Tensor, centers: torch.Tensor, bias: torch.Tensor | None = None, bias_codes=None, activation=None):
         super().__init__()
         if centers.numel() != codes.k:
             raise ValueError(f"{centers.numel()} centres for indices into a codebook of {codes.k}")
         if labels.numel() != codes.kdim * codes.ncols:
             raise ValueError(f"{labels.numel()} indices for a {codes.kdim} x {codes.ncols} weight matrix")
-        self.kdim, self.ncols = codes.kdim, codes.ncols
-        self.k, self.zero_symbol, self.label_bytes, self.nnz = codes.k, codes.zero_symbol, codes.label_bytes, codes.nnz
-        self.register_buffer("packed", codes.buf)
+        self._take_codes(codes)
         self._init_centres(labels.reshape(-1), centers, codes.ncols, bias, bias_codes, activation)
 
-    codes = _SparseCodebookLayer.codes
-
     def _matmul(self, x: torch.Tensor) -> torch.Tensor:
-        return self._activate(ops.sparse_codebook_linear(x, self.codes, self.centers, bias=self.current_bias(), relu=self._fused_relu))
+        return self._activate(self._linear(x, self.codes, self.centers, bias=self.current_bias(), relu=self._fused_relu))
 
     def nbytes(self) -> int:
         return self._nbytes(self.packed)
 
 
-class TrainableSparseCompressedDense(_TrainableSparseCodebookLayer):
+class _SparseCodebookLayer(_SparseForm, _CodesLayer):
+    """The indices in the bitmap-sparse form (ops.SparseCodes: its buffer is the module's ``packed`` buffer), centers float32[K],
+    bias float32[ncols] or None.  No kdim * ncols tensor stays resident."""
+
+
+class SparseCompressedDense(_DenseHalf, _SparseCodebookLayer):
+    """Dense run from its codebook and the bitmap-sparse form of its (in, out) indices."""
+
+    @classmethod
+    def from_dense(cls, dense, weight_model, bias_model=None, zero_symbol=None) -> "SparseCompressedDense":
+        codes = _inference_codes(dense, weight_model, bias_model)
+        kin, kout = dense.kernel.shape
+        return cls.from_codes(kin, kout, *codes, dense.activation, zero_symbol)
+
+    @classmethod
+    def from_codes(cls, kdim, ncols, labels, centers, bias, activation, zero_symbol=None) -> "SparseCompressedDense":
+        return cls(ops.pack_sparse_codes(labels, kdim, ncols, centers.numel(), zero_symbol), centers, bias, activation)
+
+
+class SparseCompressedConv2D(_Conv2DHalf, _SparseCodebookLayer):
+    """Conv2D (stride 1, NHWC) run from its codebook and the bitmap-sparse form of its indices, packed after the rows were put
+    in unfold order (keras_rows_for_unfold); patch chunking and the empty batch as CompressedConv2D."""
+
+    def __init__(self, kernel_size: int, cin: int, pad: int, codes: ops.SparseCodes, centers: torch.Tensor, bias: torch.Tensor | None,
+                 activation=None):
+        _check_conv_rows(codes, kernel_size, cin)
+        super().__init__(codes, centers, bias, activation)
+        self._set_conv(kernel_size, cin, pad)
+
+    @classmethod
+    def from_conv(cls, conv, weight_model, bias_model=None, zero_symbol=None) -> "SparseCompressedConv2D":
+        codes = _inference_codes(conv, weight_model, bias_model)
+        h, cin, cout = _conv_shape(conv)
+        return cls.from_codes(h, cin, cout, conv.pad, *codes, conv.activation, zero_symbol)
+
+    @classmethod
+    def from_codes(cls, kernel_size, cin, cout, pad, labels, centers, bias, activation, zero_symbol=None) -> "SparseCompressedConv2D":
+        """labels in the Keras order of the (h, w, in, out) kernel."""
+        codes = _unfold_then_pack(ops.pack_sparse_codes, kernel_size, cin, cout, labels, centers.numel(), zero_symbol)
+        return cls(kernel_size, cin, pad, codes, centers, bias, activation)
+
+
+class _TrainableSparseCodebookLayer(_SparseForm, _TrainableCodesLayer):
+    """The indices in the bitmap-sparse form (the ``packed`` buffer, as _SparseCodebookLayer) with the centres, counts and bias of
+    _TrainableCentres; the forward goes through ops.sparse_codebook_linear, whose backward forms dx and the centroid gradient
+    from the packed form (csrc/nnc_cbspgrad.hip).  ``counts`` is taken from the labels before packing, so kernel_sq_sum() is the
+    dense trainable layer's bit for bit.  No kdim * ncols tensor stays resident."""
+
+
+class TrainableSparseCompressedDense(_DenseHalf, _TrainableSparseCodebookLayer):
     """SparseCompressedDense with trainable centres (ops.sparse_codebook_linear)."""
 
     @classmethod
     def from_dense(cls, dense, weight_model, bias_model=None, zero_symbol=None) -> "TrainableSparseCompressedDense":
-        centers, labels, bias, bias_codes = _trainable_codes(dense, weight_model, bias_model)
+        codes = _trainable_codes(dense, weight_model, bias_model)
         kin, kout = dense.kernel.shape
-        return cls.from_codes(kin, kout, labels, centers, bias, bias_codes, dense.activation, zero_symbol)
+        return cls.from_codes(kin, kout, *codes, dense.activation, zero_symbol)
 
     @classmethod
     def from_codes(cls, kdim, ncols, labels, centers, bias=None, bias_codes=None, activation=None,
                    zero_symbol=None) -> "TrainableSparseCompressedDense":
         return cls(ops.pack_sparse_codes(labels, kdim, ncols, centers.numel(), zero_symbol), labels, centers, bias, bias_codes, activation)
 
-    def forward(self, x: torch.Tensor) -> torch.Tensor:
-        return self._matmul(x.contiguous())
 
-
-class TrainableSparseCompressedConv2D(_TrainableSparseCodebookLayer):
+class TrainableSparseCompressedConv2D(_Conv2DHalf, _TrainableSparseCodebookLayer):
     """SparseCompressedConv2D with trainable centres: the patches (chunked as CompressedConv2D) through
     ops.sparse_codebook_linear; autograd carries the patch gradients back through the unfold."""
 
     def __init__(self, kernel_size: int, cin: int, pad: int, codes: ops.SparseCodes, labels: torch.Tensor, centers: torch.Tensor, bias=None,
                  bias_codes=None, activation=None):
-        if codes.kdim != kernel_size * kernel_size * cin:
-            raise ValueError(f"{codes.kdim} index rows for a {kernel_size} x {kernel_size} x {cin} kernel")
+        _check_conv_rows(codes, kernel_size, cin)
         super().__init__(codes, labels, centers, bias, bias_codes, activation)
-        self.kernel_size, self.cin, self.pad = int(kernel_size), int(cin), int(pad)
+        self._set_conv(kernel_size, cin, pad)
 
     @classmethod
     def from_conv(cls, conv, weight_model, bias_model=None, zero_symbol=None) -> "TrainableSparseCompressedConv2D":
-        h, w, cin, cout = conv.kernel.shape
-        if h != w:
-            raise ValueError("square kernels only (as layers.Conv2D)")
-        centers, labels, bias, bias_codes = _trainable_codes(conv, weight_model, bias_model)
-        return cls.from_codes(h, cin, cout, conv.pad, labels, centers, bias, bias_codes, conv.activation, zero_symbol)
+        h, cin, cout = _conv_shape(conv)
+        return cls.from_codes(h, cin, cout, conv.pad, *_trainable_codes(conv, weight_model, bias_model), conv.activation, zero_symbol)
 
     @classmethod
     def from_codes(cls, kernel_size, cin, cout, pad, labels, centers, bias=None, bias_codes=None, activation=None,
                    zero_symbol=None) -> "TrainableSparseCompressedConv2D":
         """labels in the Keras order of the (h, w, in, out) kernel (the counts are the same in either order)."""
-        unf = _unfold_labels(kernel_size, cin, cout, labels)
-        codes = ops.pack_sparse_codes(unf, kernel_size * kernel_size * cin, cout, centers.numel(), zero_symbol)
-        del unf
+        codes = _unfold_then_pack(ops.pack_sparse_codes, kernel_size, cin, cout, labels, centers.numel(), zero_symbol)
         return cls(kernel_size, cin, pad, codes, labels, centers, bias, bias_codes, activation)
 
-    def forward(self, x: torch.Tensor) -> torch.Tensor:   # x: (N, H, W, C)
-        return _conv_forward(self, x)
 
-
-def _trainable_sparse(layer, weight_model, bias_model):
-    from .neural_networks.layers import Conv2D, Dense
-
-    if isinstance(layer, Dense):
-        return TrainableSparseCompressedDense.from_dense(layer, weight_model, bias_model)
-    if isinstance(layer, Conv2D):
-        return TrainableSparseCompressedConv2D.from_conv(layer, weight_model, bias_model)
-    raise TypeError(f"no compressed form of {type(layer).__name__}")
-
-
-class _PackedCodebookLayer(nn.Module):
+class _PackedCodebookLayer(_PackedForm, _CodesLayer):
     """The indices in the 2- or 4-bit packed form (ops.PackedCodes: its buffer is the module's ``packed`` buffer), centers
     float32[K <= 2^bits], bias float32[ncols] or None.  No kdim * ncols tensor stays resident."""
 
-    def __init__(self, codes: ops.PackedCodes, centers: torch.Tensor, bias: torch.Tensor | None, activation=None):
-        super().__init__()
-        self.kdim, self.ncols, self.bits, self.k = codes.kdim, codes.ncols, codes.bits, codes.k
-        if centers.numel() != codes.k:
-            raise ValueError(f"{centers.numel()} centres for indices into a codebook of {codes.k}")
-        self.register_buffer("packed", codes.packed)
-        self.register_buffer("centers", centers.reshape(-1).to(torch.float32).contiguous())
-        self.register_buffer("bias", None if bias is None else bias.reshape(-1).to(torch.float32).contiguous())
-        self.activation = activation
-        self._fused_relu = activation is torch.relu
 
-    @property
-    def codes(self) -> ops.PackedCodes:
-        return ops.PackedCodes(self.packed, self.kdim, self.ncols, self.bits, self.k)
-
-    def _matmul(self, x: torch.Tensor) -> torch.Tensor:
-        y = ops.packed_codebook_matmul(x, self.codes, self.centers, bias=self.bias, relu=self._fused_relu)
-        if self.activation is not None and not self._fused_relu:
-            y = self.activation(y)
-        return y
-
-    def get_weights(self):
-        return []
-
-    def nbytes(self) -> int:
-        return sum(t.numel() * t.element_size() for t in (self.packed, self.centers, self.bias) if t is not None)
-
-
-class PackedCompressedDense(_PackedCodebookLayer):
+class PackedCompressedDense(_DenseHalf, _PackedCodebookLayer):
     """Dense run from its codebook and the 2- or 4-bit packed form of its (in, out) indices."""
 
     @classmethod
     def from_dense(cls, dense, weight_model, bias_model=None, bits=None) -> "PackedCompressedDense":
-        if weight_model is None:
-            raise ValueError("the kernel was not quantized (no fitted model): keep the float32 layer")
+        codes = _inference_codes(dense, weight_model, bias_model)
         kin, kout = dense.kernel.shape
-        centers, labels = _codes(weight_model, dense.kernel.device)
-        return cls.from_codes(kin, kout, labels, centers, _decoded_bias(dense.bias, bias_model), dense.activation, bits)
+        return cls.from_codes(kin, kout, *codes, dense.activation, bits)
 
     @classmethod
     def from_codes(cls, kdim, ncols, labels, centers, bias, activation, bits=None) -> "PackedCompressedDense":
         return cls(ops.pack_codes(labels, kdim, ncols, centers.numel(), bits), centers, bias, activation)
 
-    def forward(self, x: torch.Tensor) -> torch.Tensor:
-        return self._matmul(x.contiguous())
 
-
-class PackedCompressedConv2D(_PackedCodebookLayer):
+class PackedCompressedConv2D(_Conv2DHalf, _PackedCodebookLayer):
     """Conv2D (stride 1, NHWC) run from its codebook and the packed form of its indices, packed after the rows were put in
     unfold order (keras_rows_for_unfold); patch chunking and the empty batch as CompressedConv2D."""
 
     def __init__(self, kernel_size: int, cin: int, pad: int, codes: ops.PackedCodes, centers: torch.Tensor, bias: torch.Tensor | None,
                  activation=None):
-        if codes.kdim != kernel_size * kernel_size * cin:
-            raise ValueError(f"{codes.kdim} index rows for a {kernel_size} x {kernel_size} x {cin} kernel")
+        _check_conv_rows(codes, kernel_size, cin)
         super().__init__(codes, centers, bias, activation)
-        self.kernel_size, self.cin, self.pad = int(kernel_size), int(cin), int(pad)
+        self._set_conv(kernel_size, cin, pad)
 
     @classmethod
     def from_conv(cls, conv, weight_model, bias_model=None, bits=None) -> "PackedCompressedConv2D":
-        if weight_model is None:
-            raise ValueError("the kernel was not quantized (no fitted model): keep the float32 layer")
-        h, w, cin, cout = conv.kernel.shape
-        if h != w:
-            raise ValueError("square kernels only (as layers.Conv2D)")
-        centers, labels = _codes(weight_model, conv.kernel.device)
-        return cls.from_codes(h, cin, cout, conv.pad, labels, centers, _decoded_bias(conv.bias, bias_model), conv.activation, bits)
+        codes = _inference_codes(conv, weight_model, bias_model)
+        h, cin, cout = _conv_shape(conv)
+        return cls.from_codes(h, cin, cout, conv.pad, *codes, conv.activation, bits)
 
     @classmethod
     def from_codes(cls, kernel_size, cin, cout, pad, labels, centers, bias, activation, bits=None) -> "PackedCompressedConv2D":
         """labels in the Keras order of the (h, w, in, out) kernel."""
         ops.packed_bits(centers.numel(), bits)   # a codebook that does not fit raises before the unfold
-        unf = _unfold_labels(kernel_size, cin, cout, labels)
-        codes = ops.pack_codes(unf, kernel_size * kernel_size * cin, cout, centers.numel(), bits)
-        del unf
+        codes = _unfold_then_pack(ops.pack_codes, kernel_size, cin, cout, labels, centers.numel(), bits)
         return cls(kernel_size, cin, pad, codes, centers, bias, activation)
 
-    def forward(self, x: torch.Tensor) -> torch.Tensor:   # x: (N, H, W, C)
-        return _conv_forward(self, x)
 
-
-class _TrainablePackedCodebookLayer(_TrainableCentres):
+class _TrainablePackedCodebookLayer(_PackedForm, _TrainableCodesLayer):
     """The indices in the 2- or 4-bit packed form (the ``packed`` buffer, as _PackedCodebookLayer) with the centres, counts and bias
     of _TrainableCentres; the forward goes through ops.packed_codebook_linear, whose backward forms dx and the centroid gradient
     from the packed rows (csrc/nnc_cbpkgrad.hip).  ``counts`` is taken from the labels before packing, so kernel_sq_sum() is the
     byte trainable layer's bit for bit.  No kdim * ncols tensor stays resident."""
 
-    def __init__(self, codes: ops.PackedCodes, labels: torch.Tensor, centers: torch.Tensor, bias: torch.Tensor | None = None,
-                 bias_codes=None, activation=None):
-        super().__init__()
-        if centers.numel() != codes.k:
-            raise ValueError(f"{centers.numel()} centres for indices into a codebook of {codes.k}")
-        if labels.numel() != codes.kdim * codes.ncols:
-            raise ValueError(f"{labels.numel()} indices for a {codes.kdim} x {codes.ncols} weight matrix")
-        self.kdim, self.ncols, self.bits, self.k = codes.kdim, codes.ncols, codes.bits, codes.k
-        self.register_buffer("packed", codes.packed)
-        self._init_centres(labels.reshape(-1), centers, codes.ncols, bias, bias_codes, activation)
 
-    codes = _PackedCodebookLayer.codes
-
-    def _matmul(self, x: torch.Tensor) -> torch.Tensor:
-        return self._activate(ops.packed_codebook_linear(x, self.codes, self.centers, bias=self.current_bias(), relu=self._fused_relu))
-
-    def nbytes(self) -> int:
-        return self._nbytes(self.packed)
-
-
-class TrainablePackedCompressedDense(_TrainablePackedCodebookLayer):
+class TrainablePackedCompressedDense(_DenseHalf, _TrainablePackedCodebookLayer):
     """PackedCompressedDense with trainable centres (ops.packed_codebook_linear)."""
 
     @classmethod
     def from_dense(cls, dense, weight_model, bias_model=None, bits=None) -> "TrainablePackedCompressedDense":
-        centers, labels, bias, bias_codes = _trainable_codes(dense, weight_model, bias_model)
+        codes = _trainable_codes(dense, weight_model, bias_model)
         kin, kout = dense.kernel.shape
-        return cls.from_codes(kin, kout, labels, centers, bias, bias_codes, dense.activation, bits)
+        return cls.from_codes(kin, kout, *codes, dense.activation, bits)
 
     @classmethod
     def from_codes(cls, kdim, ncols, labels, centers, bias=None, bias_codes=None, activation=None, bits=None) -> "TrainablePackedCompressedDense":
         return cls(ops.pack_codes(labels, kdim, ncols, centers.numel(), bits), labels, centers, bias, bias_codes, activation)
 
-    def forward(self, x: torch.Tensor) -> torch.Tensor:
-        return self._matmul(x.contiguous())
 
-
-class TrainablePackedCompressedConv2D(_TrainablePackedCodebookLayer):
+class TrainablePackedCompressedConv2D(_Conv2DHalf, _TrainablePackedCodebookLayer):
     """PackedCompressedConv2D with trainable centres: the patches (chunked as CompressedConv2D) through
     ops.packed_codebook_linear; autograd carries the patch gradients back through the unfold."""
 
     def __init__(self, kernel_size: int, cin: int, pad: int, codes: ops.PackedCodes, labels: torch.Tensor, centers: torch.Tensor, bias=None,
                  bias_codes=None, activation=None):
-        if codes.kdim != kernel_size * kernel_size * cin:
-            raise ValueError(f"{codes.kdim} index rows for a {kernel_size} x {kernel_size} x {cin} kernel")
+        _check_conv_rows(codes, kernel_size, cin)
         super().__init__(codes, labels, centers, bias, bias_codes, activation)
-        self.kernel_size, self.cin, self.pad = int(kernel_size), int(cin), int(pad)
+        self._set_conv(kernel_size, cin, pad)
 
     @classmethod
     def from_conv(cls, conv, weight_model, bias_model=None, bits=None) -> "TrainablePackedCompressedConv2D":
-        h, w, cin, cout = conv.kernel.shape
-        if h != w:
-            raise ValueError("square kernels only (as layers.Conv2D)")
-        centers, labels, bias, bias_codes = _trainable_codes(conv, weight_model, bias_model)
-        return cls.from_codes(h, cin, cout, conv.pad, labels, centers, bias, bias_codes, conv.activation, bits)
+        h, cin, cout = _conv_shape(conv)
+        return cls.from_codes(h, cin, cout, conv.pad, *_trainable_codes(conv, weight_model, bias_model), conv.activation, bits)
 
     @classmethod
     def from_codes(cls, kernel_size, cin, cout, pad, labels, centers, bias=None, bias_codes=None, activation=None,
                    bits=None) -> "TrainablePackedCompressedConv2D":
         """labels in the Keras order of the (h, w, in, out) kernel (the counts are the same in either order)."""
         ops.packed_bits(centers.numel(), bits)   # a codebook that does not fit raises before the unfold
-        unf = _unfold_labels(kernel_size, cin, cout, labels)
-        codes = ops.pack_codes(unf, kernel_size * kernel_size * cin, cout, centers.numel(), bits)
-        del unf
+        codes = _unfold_then_pack(ops.pack_codes, kernel_size, cin, cout, labels, centers.numel(), bits)
         return cls(kernel_size, cin, pad, codes, labels, centers, bias, bias_codes, activation)
-
-    def forward(self, x: torch.Tensor) -> torch.Tensor:   # x: (N, H, W, C)
-        return _conv_forward(self, x)
-
-
-def _trainable_packed(layer, weight_model, bias_model):
-    from .neural_networks.layers import Conv2D, Dense
-
-    if isinstance(layer, Dense):
-        return TrainablePackedCompressedDense.from_dense(layer, weight_model, bias_model)
-    if isinstance(layer, Conv2D):
-        return TrainablePackedCompressedConv2D.from_conv(layer, weight_model, bias_model)
-    raise TypeError(f"no compressed form of {type(layer).__name__}")
 
 
 PACKED_MAX_K = 16   # the packed form holds at most 4-bit indices
@@ -829,14 +775,14 @@ def compress_network_trainable(network: nn.Module, models_by_layer, sparse=False
     same function: the sparse and the packed layer's centroid gradient is the byte one's bit for bit (DESIGN.md sections 13, 15)."""
     _check_sparse(sparse)
     _check_packed(packed, sparse)
-    if packed is False:
-        return _compress_each(network, models_by_layer,
-                              lambda layer, wm, bm: _pick(lambda: _trainable(layer, wm, bm), lambda: _trainable_sparse(layer, wm, bm), sparse),
-                              grouped="trainable=True")
-    return _compress_each(network, models_by_layer,
-                          lambda layer, wm, bm: _pick3(wm.cluster_centers_.size, lambda: _trainable(layer, wm, bm),
-                                                       lambda: _trainable_sparse(layer, wm, bm), lambda: _trainable_packed(layer, wm, bm),
-                                                       sparse, packed), grouped="trainable=True")
+
+    def make(layer, wm, bm):
+        byte, sp, pk = (lambda: _trainable(layer, wm, bm),
+                        lambda: _trainable(layer, wm, bm, TrainableSparseCompressedDense, TrainableSparseCompressedConv2D),
+                        lambda: _trainable(layer, wm, bm, TrainablePackedCompressedDense, TrainablePackedCompressedConv2D))
+        return _pick(byte, sp, sparse) if packed is False else _pick3(wm.cluster_centers_.size, byte, sp, pk, sparse, packed)
+
+    return _compress_each(network, models_by_layer, make, grouped="trainable=True")
 
 
 def _compress_each(network: nn.Module, models_by_layer, make, grouped=None) -> nn.Module:
@@ -909,7 +855,7 @@ def compressed_nbytes(network: nn.Module) -> int:
     layers = network.get_config().values() if hasattr(network, "get_config") else [network]
     total = 0
     for layer in layers:
-        if isinstance(layer, (_CodebookLayer, GroupedCompressedDense, _SparseCodebookLayer, _PackedCodebookLayer, _TrainableCentres)):
+        if isinstance(layer, (_InferenceLayer, _TrainableCentres)):
             total += layer.nbytes()
         else:
             total += sum(p.numel() * p.element_size() for p in layer.parameters())

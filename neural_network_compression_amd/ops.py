@@ -295,6 +295,63 @@ def gather(centers: torch.Tensor, labels: torch.Tensor) -> torch.Tensor:
     return out
 
 
+# ------------------------------------------------------------------ codebook products: the steps every index form shares
+# The byte, grouped, bitmap-sparse and packed wrappers below run these in the same order; what differs per form (the dtype
+# rule of x, the checks of the indices, the native call) stays in the form's own function, between them.
+def _workspace(nbytes: int, dev) -> torch.Tensor | None:
+    """The uint8 scratch of ``nbytes`` a native call asked for, or None when it needs none."""
+    return torch.empty(nbytes, dtype=torch.uint8, device=dev) if nbytes else None
+
+
+def _rows(t: torch.Tensor, name: str, last: int):
+    """(lead, m) of ``t`` read as m rows of ``last`` values: its leading shape and their product, the last dimension checked."""
+    if t.dim() < 1 or t.shape[-1] != last:
+        raise ValueError(f"{name} must have shape (..., {last}), got {tuple(t.shape)}")
+    lead = tuple(t.shape[:-1])
+    return lead, (int(np.prod(lead)) if lead else 1)
+
+
+def _require_centers_bias(centers, bias):
+    _require_cuda(centers, "centers", torch.float32)
+    if bias is not None:
+        _require_cuda(bias, "bias", torch.float32)
+
+
+def _one_device(names: str, *tensors):
+    if len({t.device for t in tensors if t is not None}) != 1:
+        raise ValueError(f"{names} must be on one device")
+
+
+def _inference_only(who: str, names: str, x, index, centers, bias):
+    """The forward products compute no gradient: refuse to record one, then hold the operands to one device."""
+    if torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (x, centers, bias)):
+        raise RuntimeError(f"{who} is inference only: it computes no gradient (run it under torch.no_grad())")
+    _one_device(names, x, index, centers, bias)
+
+
+def _empty_y(x: torch.Tensor, lead: tuple, ncols: int, bias, dtype) -> torch.Tensor:
+    """The (..., ncols) result on x's device, once the bias is known to hold a value per column."""
+    if bias is not None and bias.numel() != ncols:
+        raise ValueError(f"bias must hold ncols = {ncols} values, got {bias.numel()}")
+    return torch.empty(lead + (ncols,), dtype=dtype, device=x.device)
+
+
+def _dc_args(x: torch.Tensor, lead: tuple, kdim: int, names: str, index, g: torch.Tensor, dtype):
+    """The centroid gradients' checks behind those of g: x row for row with g, one device, a float result type."""
+    if x.dim() < 1 or x.shape[-1] != kdim or tuple(x.shape[:-1]) != lead:
+        raise ValueError(f"x must have shape {lead + (kdim,)}, got {tuple(x.shape)}")
+    _one_device(names, x, g, index)
+    if dtype not in (torch.float64, torch.float32):
+        raise TypeError("dtype must be torch.float64 or torch.float32")
+
+
+def _plan(entry, fields: tuple, *args) -> dict:
+    """Host: one nnc_*_plan entry point called with the integer ``args`` -> its int64 record as a dict keyed by ``fields``."""
+    out = (ctypes.c_int64 * len(fields))()
+    nat.check(entry(*(int(a) for a in args), out))
+    return dict(zip(fields, (int(v) for v in out)))
+
+
 _H16_DT = {torch.bfloat16: nat.DT_BF16, torch.float16: nat.DT_F16}   # the half activation types of nnc_cbmm_h16
 
 
@@ -318,34 +375,23 @@ def codebook_matmul(x: torch.Tensor, labels: torch.Tensor, centers: torch.Tensor
             raise TypeError(f"out_dtype must be None or torch.float32 for a float32 x, got {out_dtype}")
         y_dtype = torch.float32
     _require_cuda(labels, "labels")
-    _require_cuda(centers, "centers", torch.float32)
-    if bias is not None:
-        _require_cuda(bias, "bias", torch.float32)
+    _require_centers_bias(centers, bias)
     kdim, ncols = int(kdim), int(ncols)
-    if torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (x, centers, bias)):
-        raise RuntimeError("codebook_matmul is inference only: it computes no gradient (run it under torch.no_grad())")
-    devs = {t.device for t in (x, labels, centers, bias) if t is not None}
-    if len(devs) != 1:
-        raise ValueError("x, labels, centers and bias must be on one device")
-    if x.dim() < 1 or x.shape[-1] != kdim:
-        raise ValueError(f"x must have shape (..., {kdim}), got {tuple(x.shape)}")
+    _inference_only("codebook_matmul", "x, labels, centers and bias", x, labels, centers, bias)
+    lead, m = _rows(x, "x", kdim)
     if labels.numel() != kdim * ncols:
         raise ValueError(f"labels must hold kdim * ncols = {kdim * ncols} indices, got {labels.numel()}")
-    if bias is not None and bias.numel() != ncols:
-        raise ValueError(f"bias must hold ncols = {ncols} values, got {bias.numel()}")
+    y = _empty_y(x, lead, ncols, bias, y_dtype)
     L = nat.load()
-    lead = tuple(x.shape[:-1])
-    m = int(np.prod(lead)) if lead else 1
-    y = torch.empty(lead + (ncols,), dtype=y_dtype, device=x.device)
     lb = _label_bytes(labels)
     if x.dtype in _H16_DT:
         ws_bytes = int(L.nnc_cbmm_h16_workspace_bytes(m, kdim, ncols, lb))
-        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=x.device) if ws_bytes else None
+        ws = _workspace(ws_bytes, x.device)
         nat.check(L.nnc_cbmm_h16(_ptr(x), _H16_DT[x.dtype], m, kdim, _ptr(labels), lb, ncols, _ptr(centers), centers.numel(), _ptr(bias),
                                  1 if relu else 0, _ptr(y), _H16_DT.get(y_dtype, nat.DT_F32), _ptr(ws), ws_bytes, _stream(x)))
         return y
     ws_bytes = int(L.nnc_cbmm_workspace_bytes(m, kdim, ncols, lb))
-    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=x.device) if ws_bytes else None
+    ws = _workspace(ws_bytes, x.device)
     nat.check(L.nnc_cbmm_f32(_ptr(x), m, kdim, _ptr(labels), lb, ncols, _ptr(centers), centers.numel(), _ptr(bias), 1 if relu else 0,
                              _ptr(y), _ptr(ws), ws_bytes, _stream(x)))
     return y
@@ -354,10 +400,7 @@ def codebook_matmul(x: torch.Tensor, labels: torch.Tensor, centers: torch.Tensor
 def cbmm_plan(m: int, kdim: int, ncols: int, label_bytes: int, k: int, cus: int, labels_addr: int = 0) -> dict:
     """Host: the plan nnc_cbmm_f32 follows for this call on a device with ``cus`` compute units (include/nnc.h, nnc_cbmm_plan),
     as a dict keyed by _native.CBMM_PLAN_FIELDS.  No device needed."""
-    L = nat.load()
-    out = (ctypes.c_int64 * nat.CBMM_PLAN_LEN)()
-    nat.check(L.nnc_cbmm_plan(int(m), int(kdim), int(ncols), int(label_bytes), int(k), int(cus), int(labels_addr), out))
-    return dict(zip(nat.CBMM_PLAN_FIELDS, (int(v) for v in out)))
+    return _plan(nat.load().nnc_cbmm_plan, nat.CBMM_PLAN_FIELDS, m, kdim, ncols, label_bytes, k, cus, labels_addr)
 
 
 def cbmm_h16_plan(dtype, m: int, kdim: int, ncols: int, label_bytes: int, k: int, cus: int, labels_addr: int = 0) -> dict:
@@ -365,10 +408,7 @@ def cbmm_h16_plan(dtype, m: int, kdim: int, ncols: int, label_bytes: int, k: int
     units (include/nnc.h, nnc_cbmm_h16_plan), as a dict keyed by _native.CBMM_H16_PLAN_FIELDS.  No device needed."""
     if dtype not in _H16_DT:
         raise TypeError(f"dtype must be torch.bfloat16 or torch.float16, got {dtype}")
-    L = nat.load()
-    out = (ctypes.c_int64 * nat.CBMM_H16_PLAN_LEN)()
-    nat.check(L.nnc_cbmm_h16_plan(_H16_DT[dtype], int(m), int(kdim), int(ncols), int(label_bytes), int(k), int(cus), int(labels_addr), out))
-    return dict(zip(nat.CBMM_H16_PLAN_FIELDS, (int(v) for v in out)))
+    return _plan(nat.load().nnc_cbmm_h16_plan, nat.CBMM_H16_PLAN_FIELDS, _H16_DT[dtype], m, kdim, ncols, label_bytes, k, cus, labels_addr)
 
 
 _X_DT = {torch.float32: nat.DT_F32, **_H16_DT}   # the activation types of nnc_cbmm_grouped
@@ -390,32 +430,21 @@ def grouped_codebook_matmul(x: torch.Tensor, labels: torch.Tensor, centers: torc
     _require_cuda(labels, "labels")
     if labels.dtype != torch.uint8:
         raise TypeError(f"grouped_codebook_matmul takes uint8 labels (K <= 256 per group), got {labels.dtype}")
-    _require_cuda(centers, "centers", torch.float32)
-    if bias is not None:
-        _require_cuda(bias, "bias", torch.float32)
+    _require_centers_bias(centers, bias)
     kdim, ncols, group_rows = int(kdim), int(ncols), int(group_rows)
-    if torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (x, centers, bias)):
-        raise RuntimeError("grouped_codebook_matmul is inference only: it computes no gradient (run it under torch.no_grad())")
-    devs = {t.device for t in (x, labels, centers, bias) if t is not None}
-    if len(devs) != 1:
-        raise ValueError("x, labels, centers and bias must be on one device")
+    _inference_only("grouped_codebook_matmul", "x, labels, centers and bias", x, labels, centers, bias)
     if group_rows < 32 or group_rows % 32:
         raise ValueError(f"group_rows must be a positive multiple of 32, got {group_rows}")
     groups = -(-kdim // group_rows)
     if centers.dim() != 2 or centers.shape[0] != max(groups, 1) or not 1 <= centers.shape[1] <= 256:
         raise ValueError(f"centers must have shape ({max(groups, 1)}, K <= 256) for kdim {kdim} and group_rows {group_rows}, got {tuple(centers.shape)}")
-    if x.dim() < 1 or x.shape[-1] != kdim:
-        raise ValueError(f"x must have shape (..., {kdim}), got {tuple(x.shape)}")
+    lead, m = _rows(x, "x", kdim)
     if labels.numel() != kdim * ncols:
         raise ValueError(f"labels must hold kdim * ncols = {kdim * ncols} indices, got {labels.numel()}")
-    if bias is not None and bias.numel() != ncols:
-        raise ValueError(f"bias must hold ncols = {ncols} values, got {bias.numel()}")
+    y = _empty_y(x, lead, ncols, bias, y_dtype)
     L = nat.load()
-    lead = tuple(x.shape[:-1])
-    m = int(np.prod(lead)) if lead else 1
-    y = torch.empty(lead + (ncols,), dtype=y_dtype, device=x.device)
     ws_bytes = int(L.nnc_cbmm_grouped_workspace_bytes(_X_DT[x.dtype], m, kdim, ncols))
-    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=x.device) if ws_bytes else None
+    ws = _workspace(ws_bytes, x.device)
     nat.check(L.nnc_cbmm_grouped(_ptr(x), _X_DT[x.dtype], m, kdim, _ptr(labels), ncols, _ptr(centers), int(centers.shape[1]), group_rows, _ptr(bias),
                                  1 if relu else 0, _ptr(y), _X_DT[y_dtype], _ptr(ws), ws_bytes, _stream(x)))
     return y
@@ -426,23 +455,19 @@ def cbmm_grouped_plan(dtype, m: int, kdim: int, ncols: int, k: int, group_rows: 
     compute units (include/nnc.h, nnc_cbmm_grouped_plan), as a dict keyed by _native.CBMM_GROUPED_PLAN_FIELDS.  No device needed."""
     if dtype not in _X_DT:
         raise TypeError(f"dtype must be torch.float32, torch.bfloat16 or torch.float16, got {dtype}")
-    L = nat.load()
-    out = (ctypes.c_int64 * nat.CBMM_GROUPED_PLAN_LEN)()
-    nat.check(L.nnc_cbmm_grouped_plan(_X_DT[dtype], int(m), int(kdim), int(ncols), int(k), int(group_rows), int(cus), int(labels_addr), out))
-    return dict(zip(nat.CBMM_GROUPED_PLAN_FIELDS, (int(v) for v in out)))
+    return _plan(nat.load().nnc_cbmm_grouped_plan, nat.CBMM_GROUPED_PLAN_FIELDS, _X_DT[dtype], m, kdim, ncols, k, group_rows, cus, labels_addr)
 
 
 def _grad_args(g: torch.Tensor, labels: torch.Tensor, kdim: int, ncols: int, k: int):
+    """The byte form's checks of g and the indices -> (lead, m) of g."""
     _require_cuda(g, "g", torch.float32)
     _require_cuda(labels, "labels")
     if labels.numel() != kdim * ncols:
         raise ValueError(f"labels must hold kdim * ncols = {kdim * ncols} indices, got {labels.numel()}")
-    if g.dim() < 1 or g.shape[-1] != ncols:
-        raise ValueError(f"g must have shape (..., {ncols}), got {tuple(g.shape)}")
+    lead_m = _rows(g, "g", ncols)
     if not 1 <= k <= nat.NNC_KMAX:
         raise ValueError(f"k = {k} outside 1..{nat.NNC_KMAX}")
-    lead = tuple(g.shape[:-1])
-    return lead, (int(np.prod(lead)) if lead else 1)
+    return lead_m
 
 
 def codebook_matmul_dx(g: torch.Tensor, labels: torch.Tensor, centers: torch.Tensor, kdim: int, ncols: int) -> torch.Tensor:
@@ -452,13 +477,12 @@ def codebook_matmul_dx(g: torch.Tensor, labels: torch.Tensor, centers: torch.Ten
     kdim, ncols = int(kdim), int(ncols)
     _require_cuda(centers, "centers", torch.float32)
     lead, m = _grad_args(g, labels, kdim, ncols, centers.numel())
-    if len({g.device, labels.device, centers.device}) != 1:
-        raise ValueError("g, labels and centers must be on one device")
+    _one_device("g, labels and centers", g, labels, centers)
     L = nat.load()
     dx = torch.empty(lead + (kdim,), dtype=torch.float32, device=g.device)
     lb = _label_bytes(labels)
     ws_bytes = int(L.nnc_cbmm_dx_workspace_bytes(m, kdim, ncols, lb))
-    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=g.device) if ws_bytes else None
+    ws = _workspace(ws_bytes, g.device)
     nat.check(L.nnc_cbmm_dx_f32(_ptr(g), m, kdim, _ptr(labels), lb, ncols, _ptr(centers), centers.numel(), _ptr(dx), _ptr(ws), ws_bytes, _stream(g)))
     return dx
 
@@ -472,19 +496,14 @@ def codebook_centroid_grad(x: torch.Tensor, g: torch.Tensor, labels: torch.Tenso
     kdim, ncols, k = int(kdim), int(ncols), int(k)
     _require_cuda(x, "x", torch.float32)
     lead, m = _grad_args(g, labels, kdim, ncols, k)
-    if x.dim() < 1 or x.shape[-1] != kdim or tuple(x.shape[:-1]) != lead:
-        raise ValueError(f"x must have shape {lead + (kdim,)}, got {tuple(x.shape)}")
-    if len({x.device, g.device, labels.device}) != 1:
-        raise ValueError("x, g and labels must be on one device")
-    if dtype not in (torch.float64, torch.float32):
-        raise TypeError("dtype must be torch.float64 or torch.float32")
+    _dc_args(x, lead, kdim, "x, g and labels", labels, g, dtype)
     L = nat.load()
     lb = _label_bytes(labels)
     if lb == 1 and k > 256:
         raise ValueError("k > 256 needs 16-bit labels")
     dc = torch.empty(k, dtype=dtype, device=x.device)
     ws_bytes = int(L.nnc_cbmm_dc_workspace_bytes(m, kdim, ncols, lb, k))
-    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=x.device) if ws_bytes else None
+    ws = _workspace(ws_bytes, x.device)
     nat.check(L.nnc_cbmm_dc_f32(_ptr(x), _ptr(g), m, kdim, _ptr(labels), lb, ncols, k, _ptr(dc), 1 if dtype == torch.float64 else 0,
                                 _ptr(ws), ws_bytes, _stream(x)))
     return dc
@@ -493,19 +512,13 @@ def codebook_centroid_grad(x: torch.Tensor, g: torch.Tensor, labels: torch.Tenso
 def cbmm_dx_plan(m: int, kdim: int, ncols: int, label_bytes: int, k: int, cus: int, labels_addr: int = 0) -> dict:
     """Host: the plan nnc_cbmm_dx_f32 follows on a device with ``cus`` compute units (include/nnc.h, nnc_cbmm_dx_plan), as a dict
     keyed by _native.CBDX_PLAN_FIELDS.  No device needed."""
-    L = nat.load()
-    out = (ctypes.c_int64 * nat.CBDX_PLAN_LEN)()
-    nat.check(L.nnc_cbmm_dx_plan(int(m), int(kdim), int(ncols), int(label_bytes), int(k), int(cus), int(labels_addr), out))
-    return dict(zip(nat.CBDX_PLAN_FIELDS, (int(v) for v in out)))
+    return _plan(nat.load().nnc_cbmm_dx_plan, nat.CBDX_PLAN_FIELDS, m, kdim, ncols, label_bytes, k, cus, labels_addr)
 
 
 def cbmm_dc_plan(m: int, kdim: int, ncols: int, label_bytes: int, k: int, cus: int, labels_addr: int = 0) -> dict:
     """Host: the plan nnc_cbmm_dc_f32 follows on a device with ``cus`` compute units (include/nnc.h, nnc_cbmm_dc_plan), as a dict
     keyed by _native.CBDC_PLAN_FIELDS.  No device needed."""
-    L = nat.load()
-    out = (ctypes.c_int64 * nat.CBDC_PLAN_LEN)()
-    nat.check(L.nnc_cbmm_dc_plan(int(m), int(kdim), int(ncols), int(label_bytes), int(k), int(cus), int(labels_addr), out))
-    return dict(zip(nat.CBDC_PLAN_FIELDS, (int(v) for v in out)))
+    return _plan(nat.load().nnc_cbmm_dc_plan, nat.CBDC_PLAN_FIELDS, m, kdim, ncols, label_bytes, k, cus, labels_addr)
 
 
 CBGRAD_OK, CBGRAD_NONFINITE, CBGRAD_ZERO = 0, 1, 2
@@ -528,30 +541,36 @@ def cbgrad_shift(m: int, absmax_x: float, absmax_g: float, terms_log2: int):
 
 
 class _CodebookLinear(torch.autograd.Function):
+    """The one autograd Function of the three trainable forms.  ``index`` is what the form keeps of the indices (the labels
+    tensor, a SparseCodes, a PackedCodes); ``fwd(x, index, centers, bias, relu)``, ``dx(g, index, centers)`` and
+    ``dc(x, g, index, centers)`` are the form's products on (m, kdim) / (m, ncols) rows."""
+
     @staticmethod
-    def forward(ctx, x, labels, centers, kdim, ncols, bias, relu):
+    def forward(ctx, x, index, centers, bias, relu, kdim, ncols, fwd, dx, dc):
         with torch.no_grad():
-            y = codebook_matmul(x.contiguous(), labels, centers, kdim, ncols, bias=bias, relu=relu)
-        ctx.kdim, ctx.ncols, ctx.relu = kdim, ncols, relu
-        ctx.save_for_backward(x, labels, centers, y if relu else None)
+            y = fwd(x.contiguous(), index, centers, bias, relu)
+        ctx.kdim, ctx.ncols, ctx.relu, ctx.dx, ctx.dc = kdim, ncols, relu, dx, dc
+        held = isinstance(index, torch.Tensor)   # a labels tensor is saved with the others, a codes object kept as it is
+        ctx.index = None if held else index
+        ctx.save_for_backward(x, centers, y if relu else None, index if held else None)
         return y
 
     @staticmethod
     def backward(ctx, gy):
-        x, labels, centers, y = ctx.saved_tensors
-        kdim, ncols = ctx.kdim, ctx.ncols
+        x, centers, y, labels = ctx.saved_tensors
+        index = labels if ctx.index is None else ctx.index
         g = gy.contiguous()
         if ctx.relu:   # as torch.relu's backward: the gradient passes where y > 0 only (a NaN or negative output gets 0)
             g = torch.where(y > 0, g, torch.zeros((), dtype=g.dtype, device=g.device))
-        g2 = g.reshape(-1, ncols)
+        g2 = g.reshape(-1, ctx.ncols)
         dx = dc = db = None
         if ctx.needs_input_grad[0]:
-            dx = codebook_matmul_dx(g2, labels, centers, kdim, ncols).view(x.shape)
+            dx = ctx.dx(g2, index, centers).view(x.shape)
         if ctx.needs_input_grad[2]:
-            dc = codebook_centroid_grad(x.contiguous().reshape(-1, kdim), g2, labels, centers.numel(), kdim, ncols, dtype=torch.float32)
-        if ctx.needs_input_grad[5]:
+            dc = ctx.dc(x.contiguous().reshape(-1, ctx.kdim), g2, index, centers)
+        if ctx.needs_input_grad[3]:
             db = g2.sum(0)
-        return dx, None, dc, None, None, db, None
+        return dx, None, dc, db, None, None, None, None, None, None
 
 
 def codebook_linear(x: torch.Tensor, labels: torch.Tensor, centers: torch.Tensor, kdim: int, ncols: int, bias: torch.Tensor | None = None,
@@ -561,7 +580,12 @@ def codebook_linear(x: torch.Tensor, labels: torch.Tensor, centers: torch.Tensor
     codebook_centroid_grad (float32) only if centers does, masks a fused ReLU as torch does and sums the bias gradient over the
     rows.  The indices get no gradient.  No host read."""
     _require_f32_x(x, "codebook_linear")
-    return _CodebookLinear.apply(x, labels, centers, int(kdim), int(ncols), bias, bool(relu))
+    kdim, ncols = int(kdim), int(ncols)
+    return _CodebookLinear.apply(
+        x, labels, centers, bias, bool(relu), kdim, ncols,
+        lambda x2, lab, c, b, r: codebook_matmul(x2, lab, c, kdim, ncols, bias=b, relu=r),
+        lambda g2, lab, c: codebook_matmul_dx(g2, lab, c, kdim, ncols),
+        lambda x2, g2, lab, c: codebook_centroid_grad(x2, g2, lab, c.numel(), kdim, ncols, dtype=torch.float32))
 
 
 class SparseCodes:
@@ -644,29 +668,18 @@ def sparse_codebook_matmul(x: torch.Tensor, codes: SparseCodes, centers: torch.T
     or None.  Returns float32 (..., ncols).  Inference only, as codebook_matmul."""
     _require_f32_x(x, "sparse_codebook_matmul")
     _require_cuda(x, "x", torch.float32)
-    _require_cuda(centers, "centers", torch.float32)
-    if bias is not None:
-        _require_cuda(bias, "bias", torch.float32)
+    _require_centers_bias(centers, bias)
     if not isinstance(codes, SparseCodes):
         raise TypeError("codes must be a SparseCodes (ops.pack_sparse_codes)")
-    if torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (x, centers, bias)):
-        raise RuntimeError("sparse_codebook_matmul is inference only: it computes no gradient (run it under torch.no_grad())")
-    devs = {t.device for t in (x, codes.buf, centers, bias) if t is not None}
-    if len(devs) != 1:
-        raise ValueError("x, codes, centers and bias must be on one device")
+    _inference_only("sparse_codebook_matmul", "x, codes, centers and bias", x, codes.buf, centers, bias)
     kdim, ncols = codes.kdim, codes.ncols
-    if x.dim() < 1 or x.shape[-1] != kdim:
-        raise ValueError(f"x must have shape (..., {kdim}), got {tuple(x.shape)}")
+    lead, m = _rows(x, "x", kdim)
     if centers.numel() != codes.k:
         raise ValueError(f"centers must hold k = {codes.k} values, got {centers.numel()}")
-    if bias is not None and bias.numel() != ncols:
-        raise ValueError(f"bias must hold ncols = {ncols} values, got {bias.numel()}")
+    y = _empty_y(x, lead, ncols, bias, torch.float32)
     L = nat.load()
-    lead = tuple(x.shape[:-1])
-    m = int(np.prod(lead)) if lead else 1
-    y = torch.empty(lead + (ncols,), dtype=torch.float32, device=x.device)
     ws_bytes = int(L.nnc_cbsp_workspace_bytes(m, kdim, ncols, codes.label_bytes))
-    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=x.device) if ws_bytes else None
+    ws = _workspace(ws_bytes, x.device)
     nat.check(L.nnc_cbsp_f32(_ptr(x), m, kdim, _ptr(codes.buf), codes.nbytes(), codes.label_bytes, ncols, codes.zero_symbol, codes.nnz,
                              _ptr(centers), centers.numel(), _ptr(bias), 1 if relu else 0, _ptr(y), _ptr(ws), ws_bytes, _stream(x)))
     return y
@@ -675,20 +688,7 @@ def sparse_codebook_matmul(x: torch.Tensor, codes: SparseCodes, centers: torch.T
 def cbsp_plan(m: int, kdim: int, ncols: int, label_bytes: int, k: int, cus: int) -> dict:
     """Host: the plan nnc_cbsp_f32 follows on a device with ``cus`` compute units (include/nnc.h, nnc_cbsp_plan), as a dict keyed
     by _native.CBSP_PLAN_FIELDS.  No device needed."""
-    L = nat.load()
-    out = (ctypes.c_int64 * nat.CBSP_PLAN_LEN)()
-    nat.check(L.nnc_cbsp_plan(int(m), int(kdim), int(ncols), int(label_bytes), int(k), int(cus), out))
-    return dict(zip(nat.CBSP_PLAN_FIELDS, (int(v) for v in out)))
-
-
-def _sparse_grad_args(g: torch.Tensor, codes: SparseCodes):
-    _require_cuda(g, "g", torch.float32)
-    if not isinstance(codes, SparseCodes):
-        raise TypeError("codes must be a SparseCodes (ops.pack_sparse_codes)")
-    if g.dim() < 1 or g.shape[-1] != codes.ncols:
-        raise ValueError(f"g must have shape (..., {codes.ncols}), got {tuple(g.shape)}")
-    lead = tuple(g.shape[:-1])
-    return lead, (int(np.prod(lead)) if lead else 1)
+    return _plan(nat.load().nnc_cbsp_plan, nat.CBSP_PLAN_FIELDS, m, kdim, ncols, label_bytes, k, cus)
 
 
 def sparse_codebook_matmul_dx(g: torch.Tensor, codes: SparseCodes, centers: torch.Tensor) -> torch.Tensor:
@@ -697,16 +697,18 @@ def sparse_codebook_matmul_dx(g: torch.Tensor, codes: SparseCodes, centers: torc
     == 0 a skipped weight forms no product).  g: float32 (..., ncols); centers: float32[codes.k].  Returns float32 (..., kdim).
     Split partials are summed in a fixed order: the same call gives the same bits.  No host read."""
     _require_cuda(centers, "centers", torch.float32)
-    lead, m = _sparse_grad_args(g, codes)
+    _require_cuda(g, "g", torch.float32)
+    if not isinstance(codes, SparseCodes):
+        raise TypeError("codes must be a SparseCodes (ops.pack_sparse_codes)")
+    lead, m = _rows(g, "g", codes.ncols)
     if centers.numel() != codes.k:
         raise ValueError(f"centers must hold k = {codes.k} values, got {centers.numel()}")
-    if len({g.device, codes.device, centers.device}) != 1:
-        raise ValueError("g, codes and centers must be on one device")
+    _one_device("g, codes and centers", g, codes.buf, centers)
     L = nat.load()
     kdim, ncols, lb = codes.kdim, codes.ncols, codes.label_bytes
     dx = torch.empty(lead + (kdim,), dtype=torch.float32, device=g.device)
     ws_bytes = int(L.nnc_cbsp_dx_workspace_bytes(m, kdim, ncols, lb))
-    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=g.device) if ws_bytes else None
+    ws = _workspace(ws_bytes, g.device)
     nat.check(L.nnc_cbsp_dx_f32(_ptr(g), m, kdim, _ptr(codes.buf), codes.nbytes(), lb, ncols, codes.zero_symbol, codes.nnz, _ptr(centers),
                                 centers.numel(), _ptr(dx), _ptr(ws), ws_bytes, _stream(g)))
     return dx
@@ -718,18 +720,16 @@ def sparse_codebook_centroid_grad(x: torch.Tensor, g: torch.Tensor, codes: Spars
     never unpacked and dW never written.  x: float32 (..., kdim), g: float32 (..., ncols) with the same leading shape.  Returns
     ``dtype`` (float64 or float32) [codes.k].  No host read."""
     _require_cuda(x, "x", torch.float32)
-    lead, m = _sparse_grad_args(g, codes)
+    _require_cuda(g, "g", torch.float32)
+    if not isinstance(codes, SparseCodes):
+        raise TypeError("codes must be a SparseCodes (ops.pack_sparse_codes)")
     kdim, ncols, k, lb = codes.kdim, codes.ncols, codes.k, codes.label_bytes
-    if x.dim() < 1 or x.shape[-1] != kdim or tuple(x.shape[:-1]) != lead:
-        raise ValueError(f"x must have shape {lead + (kdim,)}, got {tuple(x.shape)}")
-    if len({x.device, g.device, codes.device}) != 1:
-        raise ValueError("x, g and codes must be on one device")
-    if dtype not in (torch.float64, torch.float32):
-        raise TypeError("dtype must be torch.float64 or torch.float32")
+    lead, m = _rows(g, "g", ncols)
+    _dc_args(x, lead, kdim, "x, g and codes", codes.buf, g, dtype)
     L = nat.load()
     dc = torch.empty(k, dtype=dtype, device=x.device)
     ws_bytes = int(L.nnc_cbsp_dc_workspace_bytes(m, kdim, ncols, lb, k))
-    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=x.device) if ws_bytes else None
+    ws = _workspace(ws_bytes, x.device)
     nat.check(L.nnc_cbsp_dc_f32(_ptr(x), _ptr(g), m, kdim, _ptr(codes.buf), codes.nbytes(), lb, ncols, codes.zero_symbol, codes.nnz, k, _ptr(dc),
                                 1 if dtype == torch.float64 else 0, _ptr(ws), ws_bytes, _stream(x)))
     return dc
@@ -738,46 +738,13 @@ def sparse_codebook_centroid_grad(x: torch.Tensor, g: torch.Tensor, codes: Spars
 def cbsp_dx_plan(m: int, kdim: int, ncols: int, label_bytes: int, k: int, cus: int) -> dict:
     """Host: the plan nnc_cbsp_dx_f32 follows on a device with ``cus`` compute units (include/nnc.h, nnc_cbsp_dx_plan), as a dict
     keyed by _native.CBSPDX_PLAN_FIELDS.  No device needed."""
-    L = nat.load()
-    out = (ctypes.c_int64 * nat.CBSPDX_PLAN_LEN)()
-    nat.check(L.nnc_cbsp_dx_plan(int(m), int(kdim), int(ncols), int(label_bytes), int(k), int(cus), out))
-    return dict(zip(nat.CBSPDX_PLAN_FIELDS, (int(v) for v in out)))
+    return _plan(nat.load().nnc_cbsp_dx_plan, nat.CBSPDX_PLAN_FIELDS, m, kdim, ncols, label_bytes, k, cus)
 
 
 def cbsp_dc_plan(m: int, kdim: int, ncols: int, label_bytes: int, k: int, cus: int) -> dict:
     """Host: the plan nnc_cbsp_dc_f32 follows on a device with ``cus`` compute units (include/nnc.h, nnc_cbsp_dc_plan), as a dict
     keyed by _native.CBSPDC_PLAN_FIELDS.  No device needed."""
-    L = nat.load()
-    out = (ctypes.c_int64 * nat.CBSPDC_PLAN_LEN)()
-    nat.check(L.nnc_cbsp_dc_plan(int(m), int(kdim), int(ncols), int(label_bytes), int(k), int(cus), out))
-    return dict(zip(nat.CBSPDC_PLAN_FIELDS, (int(v) for v in out)))
-
-
-class _SparseCodebookLinear(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, x, codes, centers, bias, relu):
-        with torch.no_grad():
-            y = sparse_codebook_matmul(x.contiguous(), codes, centers, bias=bias, relu=relu)
-        ctx.codes, ctx.relu = codes, relu
-        ctx.save_for_backward(x, centers, y if relu else None)
-        return y
-
-    @staticmethod
-    def backward(ctx, gy):
-        x, centers, y = ctx.saved_tensors
-        codes = ctx.codes
-        g = gy.contiguous()
-        if ctx.relu:   # as torch.relu's backward: the gradient passes where y > 0 only (a NaN or negative output gets 0)
-            g = torch.where(y > 0, g, torch.zeros((), dtype=g.dtype, device=g.device))
-        g2 = g.reshape(-1, codes.ncols)
-        dx = dc = db = None
-        if ctx.needs_input_grad[0]:
-            dx = sparse_codebook_matmul_dx(g2, codes, centers).view(x.shape)
-        if ctx.needs_input_grad[2]:
-            dc = sparse_codebook_centroid_grad(x.contiguous().reshape(-1, codes.kdim), g2, codes, dtype=torch.float32)
-        if ctx.needs_input_grad[3]:
-            db = g2.sum(0)
-        return dx, None, dc, db, None
+    return _plan(nat.load().nnc_cbsp_dc_plan, nat.CBSPDC_PLAN_FIELDS, m, kdim, ncols, label_bytes, k, cus)
 
 
 def sparse_codebook_linear(x: torch.Tensor, codes: SparseCodes, centers: torch.Tensor, bias: torch.Tensor | None = None,
@@ -789,7 +756,8 @@ def sparse_codebook_linear(x: torch.Tensor, codes: SparseCodes, centers: torch.T
     if not isinstance(codes, SparseCodes):
         raise TypeError("codes must be a SparseCodes (ops.pack_sparse_codes)")
     _require_f32_x(x, "sparse_codebook_linear")
-    return _SparseCodebookLinear.apply(x, codes, centers, bias, bool(relu))
+    return _CodebookLinear.apply(x, codes, centers, bias, bool(relu), codes.kdim, codes.ncols, sparse_codebook_matmul, sparse_codebook_matmul_dx,
+                                 lambda x2, g2, cd, c: sparse_codebook_centroid_grad(x2, g2, cd, dtype=torch.float32))
 
 
 class PackedCodes:
@@ -874,29 +842,18 @@ def packed_codebook_matmul(x: torch.Tensor, codes: PackedCodes, centers: torch.T
     centers: float32[codes.k]; bias: float32[ncols] or None.  Returns float32 (..., ncols).  Inference only, as codebook_matmul."""
     _require_f32_x(x, "packed_codebook_matmul")
     _require_cuda(x, "x", torch.float32)
-    _require_cuda(centers, "centers", torch.float32)
-    if bias is not None:
-        _require_cuda(bias, "bias", torch.float32)
+    _require_centers_bias(centers, bias)
     if not isinstance(codes, PackedCodes):
         raise TypeError("codes must be a PackedCodes (ops.pack_codes)")
-    if torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (x, centers, bias)):
-        raise RuntimeError("packed_codebook_matmul is inference only: it computes no gradient (run it under torch.no_grad())")
-    devs = {t.device for t in (x, codes.packed, centers, bias) if t is not None}
-    if len(devs) != 1:
-        raise ValueError("x, codes, centers and bias must be on one device")
+    _inference_only("packed_codebook_matmul", "x, codes, centers and bias", x, codes.packed, centers, bias)
     kdim, ncols = codes.kdim, codes.ncols
-    if x.dim() < 1 or x.shape[-1] != kdim:
-        raise ValueError(f"x must have shape (..., {kdim}), got {tuple(x.shape)}")
+    lead, m = _rows(x, "x", kdim)
     if centers.numel() != codes.k:
         raise ValueError(f"centers must hold k = {codes.k} values, got {centers.numel()}")
-    if bias is not None and bias.numel() != ncols:
-        raise ValueError(f"bias must hold ncols = {ncols} values, got {bias.numel()}")
+    y = _empty_y(x, lead, ncols, bias, torch.float32)
     L = nat.load()
-    lead = tuple(x.shape[:-1])
-    m = int(np.prod(lead)) if lead else 1
-    y = torch.empty(lead + (ncols,), dtype=torch.float32, device=x.device)
     ws_bytes = int(L.nnc_cbpk_workspace_bytes(m, kdim, ncols, codes.bits))
-    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=x.device) if ws_bytes else None
+    ws = _workspace(ws_bytes, x.device)
     nat.check(L.nnc_cbpk_f32(_ptr(x), m, kdim, _ptr(codes.packed), codes.nbytes, codes.bits, ncols, _ptr(centers), centers.numel(), _ptr(bias),
                              1 if relu else 0, _ptr(y), _ptr(ws), ws_bytes, _stream(x)))
     return y
@@ -905,20 +862,7 @@ def packed_codebook_matmul(x: torch.Tensor, codes: PackedCodes, centers: torch.T
 def cbpk_plan(m: int, kdim: int, ncols: int, bits: int, k: int, cus: int) -> dict:
     """Host: the plan nnc_cbpk_f32 follows on a device with ``cus`` compute units (include/nnc.h, nnc_cbpk_plan), as a dict keyed
     by _native.CBPK_PLAN_FIELDS.  No device needed."""
-    L = nat.load()
-    out = (ctypes.c_int64 * nat.CBPK_PLAN_LEN)()
-    nat.check(L.nnc_cbpk_plan(int(m), int(kdim), int(ncols), int(bits), int(k), int(cus), out))
-    return dict(zip(nat.CBPK_PLAN_FIELDS, (int(v) for v in out)))
-
-
-def _packed_grad_args(g: torch.Tensor, codes: PackedCodes):
-    _require_cuda(g, "g", torch.float32)
-    if not isinstance(codes, PackedCodes):
-        raise TypeError("codes must be a PackedCodes (ops.pack_codes)")
-    if g.dim() < 1 or g.shape[-1] != codes.ncols:
-        raise ValueError(f"g must have shape (..., {codes.ncols}), got {tuple(g.shape)}")
-    lead = tuple(g.shape[:-1])
-    return lead, (int(np.prod(lead)) if lead else 1)
+    return _plan(nat.load().nnc_cbpk_plan, nat.CBPK_PLAN_FIELDS, m, kdim, ncols, bits, k, cus)
 
 
 def packed_codebook_matmul_dx(g: torch.Tensor, codes: PackedCodes, centers: torch.Tensor) -> torch.Tensor:
@@ -927,16 +871,18 @@ def packed_codebook_matmul_dx(g: torch.Tensor, codes: PackedCodes, centers: torc
     the padding of a row forms no product).  g: float32 (..., ncols); centers: float32[codes.k].  Returns float32 (..., kdim).
     Split partials are summed in a fixed order: the same call gives the same bits.  No host read."""
     _require_cuda(centers, "centers", torch.float32)
-    lead, m = _packed_grad_args(g, codes)
+    _require_cuda(g, "g", torch.float32)
+    if not isinstance(codes, PackedCodes):
+        raise TypeError("codes must be a PackedCodes (ops.pack_codes)")
+    lead, m = _rows(g, "g", codes.ncols)
     if centers.numel() != codes.k:
         raise ValueError(f"centers must hold k = {codes.k} values, got {centers.numel()}")
-    if len({g.device, codes.device, centers.device}) != 1:
-        raise ValueError("g, codes and centers must be on one device")
+    _one_device("g, codes and centers", g, codes.packed, centers)
     L = nat.load()
     kdim, ncols, bits = codes.kdim, codes.ncols, codes.bits
     dx = torch.empty(lead + (kdim,), dtype=torch.float32, device=g.device)
     ws_bytes = int(L.nnc_cbpk_dx_workspace_bytes(m, kdim, ncols, bits))
-    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=g.device) if ws_bytes else None
+    ws = _workspace(ws_bytes, g.device)
     nat.check(L.nnc_cbpk_dx_f32(_ptr(g), m, kdim, _ptr(codes.packed), codes.nbytes, bits, ncols, _ptr(centers), centers.numel(), _ptr(dx),
                                 _ptr(ws), ws_bytes, _stream(g)))
     return dx
@@ -948,18 +894,16 @@ def packed_codebook_centroid_grad(x: torch.Tensor, g: torch.Tensor, codes: Packe
     (..., kdim), g: float32 (..., ncols) with the same leading shape.  Returns ``dtype`` (float64 or float32) [codes.k].  No host
     read."""
     _require_cuda(x, "x", torch.float32)
-    lead, m = _packed_grad_args(g, codes)
+    _require_cuda(g, "g", torch.float32)
+    if not isinstance(codes, PackedCodes):
+        raise TypeError("codes must be a PackedCodes (ops.pack_codes)")
     kdim, ncols, k, bits = codes.kdim, codes.ncols, codes.k, codes.bits
-    if x.dim() < 1 or x.shape[-1] != kdim or tuple(x.shape[:-1]) != lead:
-        raise ValueError(f"x must have shape {lead + (kdim,)}, got {tuple(x.shape)}")
-    if len({x.device, g.device, codes.device}) != 1:
-        raise ValueError("x, g and codes must be on one device")
-    if dtype not in (torch.float64, torch.float32):
-        raise TypeError("dtype must be torch.float64 or torch.float32")
+    lead, m = _rows(g, "g", ncols)
+    _dc_args(x, lead, kdim, "x, g and codes", codes.packed, g, dtype)
     L = nat.load()
     dc = torch.empty(k, dtype=dtype, device=x.device)
     ws_bytes = int(L.nnc_cbpk_dc_workspace_bytes(m, kdim, ncols, bits, k))
-    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=x.device) if ws_bytes else None
+    ws = _workspace(ws_bytes, x.device)
     nat.check(L.nnc_cbpk_dc_f32(_ptr(x), _ptr(g), m, kdim, _ptr(codes.packed), codes.nbytes, bits, ncols, k, _ptr(dc),
                                 1 if dtype == torch.float64 else 0, _ptr(ws), ws_bytes, _stream(x)))
     return dc
@@ -968,46 +912,13 @@ def packed_codebook_centroid_grad(x: torch.Tensor, g: torch.Tensor, codes: Packe
 def cbpk_dx_plan(m: int, kdim: int, ncols: int, bits: int, k: int, cus: int) -> dict:
     """Host: the plan nnc_cbpk_dx_f32 follows on a device with ``cus`` compute units (include/nnc.h, nnc_cbpk_dx_plan), as a dict
     keyed by _native.CBPKDX_PLAN_FIELDS.  No device needed."""
-    L = nat.load()
-    out = (ctypes.c_int64 * nat.CBPKDX_PLAN_LEN)()
-    nat.check(L.nnc_cbpk_dx_plan(int(m), int(kdim), int(ncols), int(bits), int(k), int(cus), out))
-    return dict(zip(nat.CBPKDX_PLAN_FIELDS, (int(v) for v in out)))
+    return _plan(nat.load().nnc_cbpk_dx_plan, nat.CBPKDX_PLAN_FIELDS, m, kdim, ncols, bits, k, cus)
 
 
 def cbpk_dc_plan(m: int, kdim: int, ncols: int, bits: int, k: int, cus: int) -> dict:
     """Host: the plan nnc_cbpk_dc_f32 follows on a device with ``cus`` compute units (include/nnc.h, nnc_cbpk_dc_plan), as a dict
     keyed by _native.CBPKDC_PLAN_FIELDS.  No device needed."""
-    L = nat.load()
-    out = (ctypes.c_int64 * nat.CBPKDC_PLAN_LEN)()
-    nat.check(L.nnc_cbpk_dc_plan(int(m), int(kdim), int(ncols), int(bits), int(k), int(cus), out))
-    return dict(zip(nat.CBPKDC_PLAN_FIELDS, (int(v) for v in out)))
-
-
-class _PackedCodebookLinear(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, x, codes, centers, bias, relu):
-        with torch.no_grad():
-            y = packed_codebook_matmul(x.contiguous(), codes, centers, bias=bias, relu=relu)
-        ctx.codes, ctx.relu = codes, relu
-        ctx.save_for_backward(x, centers, y if relu else None)
-        return y
-
-    @staticmethod
-    def backward(ctx, gy):
-        x, centers, y = ctx.saved_tensors
-        codes = ctx.codes
-        g = gy.contiguous()
-        if ctx.relu:   # as torch.relu's backward: the gradient passes where y > 0 only (a NaN or negative output gets 0)
-            g = torch.where(y > 0, g, torch.zeros((), dtype=g.dtype, device=g.device))
-        g2 = g.reshape(-1, codes.ncols)
-        dx = dc = db = None
-        if ctx.needs_input_grad[0]:
-            dx = packed_codebook_matmul_dx(g2, codes, centers).view(x.shape)
-        if ctx.needs_input_grad[2]:
-            dc = packed_codebook_centroid_grad(x.contiguous().reshape(-1, codes.kdim), g2, codes, dtype=torch.float32)
-        if ctx.needs_input_grad[3]:
-            db = g2.sum(0)
-        return dx, None, dc, db, None
+    return _plan(nat.load().nnc_cbpk_dc_plan, nat.CBPKDC_PLAN_FIELDS, m, kdim, ncols, bits, k, cus)
 
 
 def packed_codebook_linear(x: torch.Tensor, codes: PackedCodes, centers: torch.Tensor, bias: torch.Tensor | None = None,
@@ -1019,7 +930,8 @@ def packed_codebook_linear(x: torch.Tensor, codes: PackedCodes, centers: torch.T
     if not isinstance(codes, PackedCodes):
         raise TypeError("codes must be a PackedCodes (ops.pack_codes)")
     _require_f32_x(x, "packed_codebook_linear")
-    return _PackedCodebookLinear.apply(x, codes, centers, bias, bool(relu))
+    return _CodebookLinear.apply(x, codes, centers, bias, bool(relu), codes.kdim, codes.ncols, packed_codebook_matmul, packed_codebook_matmul_dx,
+                                 lambda x2, g2, cd, c: packed_codebook_centroid_grad(x2, g2, cd, dtype=torch.float32))
 
 
 def huffman_lengths(counts) -> tuple:
