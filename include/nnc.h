@@ -836,6 +836,42 @@ int nnc_cbpk_f32(const float *x, int64_t m, int64_t kdim, const void *packed, in
                  void *stream);
 
 /* ------------------------------------------------------------------------------------
+ * The group-wise layer (nnc_cbmm_grouped) on the 2- or 4-bit packed indices of nnc_cbpk_* (csrc/nnc_cbpk_grouped.hip, DESIGN.md
+ * section 18):
+ *     y = x @ W + bias (then ReLU),   W[i, o] = centers_dev[i / group_rows][label (i, o)]
+ * packed       the packed form of the whole row-major (kdim, ncols) index matrix, as nnc_cbpk_pack writes it: a grouped kernel has no
+ *              form of its own.  bits is 2 or 4; packed_bytes = nnc_cbpk_pack_bytes(kdim, ncols, bits); 16-byte aligned.
+ * centers_dev  float32[G][k], contiguous, G = ceil(kdim / group_rows), 1 <= k <= 2^bits.  An index >= k reads 0.
+ * group_rows   a positive multiple of 32; the last group may be short; group_rows >= kdim is one group, and for float32 x the
+ *              result then equals nnc_cbpk_f32 bit for bit.
+ * x            x_dtype = NNC_DT_F32, NNC_DT_BF16 or NNC_DT_F16, aligned to its element size.  Half x follows nnc_cbmm_h16: every
+ *              centre is rounded to the dtype, the products are exact, the sums are float32.  y_dtype is NNC_DT_F32 or x_dtype
+ *              (one rounding).
+ * Everything else is nnc_cbpk_f32's and nnc_cbmm_grouped's contract: split-K partials are float32 in the workspace and are summed in
+ * split order by k_cbmm_reduce; no float atomics, the same call gives the same bits; ReLU keeps NaN; m or ncols = 0 is a no-op;
+ * kdim = 0 writes y = bias (or 0); argument errors (those of nnc_cbpk_f32 and of nnc_cbmm_grouped) come back before any HIP call.
+ * The plan: m <= 16 (k_cbpk_stream_grouped, any x_dtype) and m > 16 with float32 x (k_cbpk_tiled_grouped) follow nnc_cbpk_plan for
+ * (m, kdim, ncols, bits, k, cus): PATH, VB, MT, COLS, XROWS, SPLITS, RPS, the tiles and the workspace are its values.  Half x at
+ * m > 16 (k_cbpk_mfma_grouped, PATH = NNC_CBMM_MFMA) takes the grid nnc_cbmm_grouped takes: the tiled path's tile counts, splits of
+ * whole k steps of 32.  The stream kernel keeps a table per wave (TABLES = 4) and changes it without a workgroup barrier, the
+ * tiled kernel two tables (a TB_K step can lie across a boundary), the MFMA tile one.
+ * nnc_cbpk_grouped_plan writes NNC_CBPK_GROUPED_PLAN_LEN values: the NNC_CBPK_P_* fields, then DTYPE, GROUP_ROWS, GROUPS (G),
+ * MAX_GROUPS_PER_SPLIT (the most groups the rows of one split lie in) and TABLES (the tables held in LDS; each has ENTRIES x COPIES
+ * words).  nnc_cbpk_grouped_workspace_bytes plans for 256 CUs; the splits never shrink with more CUs.
+ * ---------------------------------------------------------------------------------- */
+#define NNC_CBPK_GROUPED_P_DTYPE 14
+#define NNC_CBPK_GROUPED_P_GROUP_ROWS 15
+#define NNC_CBPK_GROUPED_P_GROUPS 16
+#define NNC_CBPK_GROUPED_P_MAX_GROUPS_PER_SPLIT 17
+#define NNC_CBPK_GROUPED_P_TABLES 18
+#define NNC_CBPK_GROUPED_PLAN_LEN 19
+int64_t nnc_cbpk_grouped_workspace_bytes(int x_dtype, int64_t m, int64_t kdim, int64_t ncols, int bits);
+int nnc_cbpk_grouped_plan(int x_dtype, int64_t m, int64_t kdim, int64_t ncols, int bits, int32_t k, int64_t group_rows, int32_t cus, int64_t *out);
+int nnc_cbpk_grouped(const void *x, int x_dtype, int64_t m, int64_t kdim, const void *packed, int64_t packed_bytes, int bits, int64_t ncols,
+                     const float *centers_dev, int32_t k, int64_t group_rows, const float *bias_dev, int32_t relu, void *y, int y_dtype,
+                     void *workspace, int64_t workspace_bytes, void *stream);
+
+/* ------------------------------------------------------------------------------------
  * The backward pass of nnc_cbsp_f32 from the same packed form, the indices never unpacked and W never decoded
  * (csrc/nnc_cbspgrad.hip).  The form, z, c_z and d are nnc_cbsp_f32's; g = dL/dy float32[m, ncols].
  * nnc_cbsp_dx_f32   dx[m, kdim] = c_z * sum_o g[r, o] + sum over the stored (i, o) of g[r, o] * d[labels[i, o]]: the Jacobian of

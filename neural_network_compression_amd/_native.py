@@ -45,6 +45,8 @@ CBSP_PLAN_FIELDS = ("path", "mt", "copies", "entries", "splits", "rps", "rowsum"
 CBPK_TABLE_NONE, CBPK_TABLE_BANKED = 0, 1   # nnc_cbpk_plan: the layout of the lookup table (include/nnc.h)
 CBPK_PLAN_LEN = 14
 CBPK_PLAN_FIELDS = ("path", "vb", "mt", "cols", "xrows", "table", "copies", "entries", "splits", "rps", "lds", "col_tiles", "row_tiles", "workspace")
+CBPK_GROUPED_PLAN_LEN = 19   # nnc_cbpk_grouped_plan: the packed fields, then the dtype, the groups and the tables in LDS
+CBPK_GROUPED_PLAN_FIELDS = CBPK_PLAN_FIELDS + ("dtype", "group_rows", "groups", "max_groups_per_split", "tables")
 CBPKDX_PLAN_LEN = 12   # nnc_cbpk_dx_plan / nnc_cbpk_dc_plan (include/nnc.h)
 CBPKDX_PLAN_FIELDS = ("path", "vb", "mt", "cols", "copies", "entries", "splits", "cps", "lds", "col_tiles", "row_tiles", "workspace")
 CBPKDC_PLAN_LEN = 12
@@ -216,6 +218,10 @@ SIGNATURES = {
     "nnc_cbpk_plan": (c_int, [c_i64, c_i64, c_i64, c_int, c_i32, c_i32, ctypes.POINTER(c_i64)]),
     "nnc_cbpk_f32": (c_int, [c_void_p, c_i64, c_i64, c_void_p, c_i64, c_int, c_i64, c_void_p, c_i32, c_void_p, c_i32, c_void_p, c_void_p, c_i64,
                              c_void_p]),
+    "nnc_cbpk_grouped_workspace_bytes": (c_i64, [c_int, c_i64, c_i64, c_i64, c_int]),
+    "nnc_cbpk_grouped_plan": (c_int, [c_int, c_i64, c_i64, c_i64, c_int, c_i32, c_i64, c_i32, ctypes.POINTER(c_i64)]),
+    "nnc_cbpk_grouped": (c_int, [c_void_p, c_int, c_i64, c_i64, c_void_p, c_i64, c_int, c_i64, c_void_p, c_i32, c_i64, c_void_p, c_i32, c_void_p, c_int,
+                                 c_void_p, c_i64, c_void_p]),
     "nnc_cbpk_dx_workspace_bytes": (c_i64, [c_i64, c_i64, c_i64, c_int]),
     "nnc_cbpk_dx_plan": (c_int, [c_i64, c_i64, c_i64, c_int, c_i32, c_i32, ctypes.POINTER(c_i64)]),
     "nnc_cbpk_dx_f32": (c_int, [c_void_p, c_i64, c_i64, c_void_p, c_i64, c_int, c_i64, c_void_p, c_i32, c_void_p, c_void_p, c_i64, c_void_p]),

@@ -267,8 +267,9 @@ class Trainer(ABC):
         form).
         ``trainable=True`` (with sparse=False and packed=False only): the layers' centres are parameters with a backward pass (DESIGN.md
         section 12); fine_tune_compressed(..., sparse=..., packed=...) trains the other two forms.
-        A layer quantized with ``group_rows`` becomes a GroupedCompressedDense; it has the byte form only, so any of the three
-        options raises NotImplementedError with the layer's name."""
+        A layer quantized with ``group_rows`` becomes a GroupedCompressedDense; with it any of the three options raises
+        NotImplementedError with the layer's name (compressed.pack_grouped_layers packs the grouped layers of the result, DESIGN.md
+        section 18)."""
         models = getattr(self, "quantized_models_by_layer", None)
         if not models:
             raise RuntimeError("compressed_network needs a quantized network: call quantize first")

@@ -9,6 +9,7 @@ tensor is never rebuilt.  Biases (one value per output column) are decoded once 
     CompressedConv2D.from_conv(conv, weight_model, bias_model)     stride 1, padding "valid" | "same", NHWC in and out
     compress_network(network, models_by_layer, sparse=False, trainable=False, packed=False)   a deep copy with the quantized layers replaced
     load_network(path, network, sparse=False, packed=False)        the same from a ``weights.nnc`` (Trainer.store_report)
+    pack_grouped_layers(network, packed=True)                      a deep copy with the grouped layers' indices packed to 2 or 4 bits
     compressed_nbytes(network)                                     resident bytes of the layers' tensors
 
 A pruned layer can instead keep its indices in the bitmap-sparse form (ops.pack_sparse_codes, csrc/nnc_cbsp.hip, DESIGN.md
@@ -35,8 +36,10 @@ Half inputs are for the byte form only: the bitmap-sparse, the packed and every 
 ``GroupedCompressedDense`` runs a Dense layer whose kernel has one codebook per block of ``group_rows`` input rows
 (utility.get_quantized_weight_grouped, Trainer.quantize(..., group_rows=); ops.grouped_codebook_matmul, csrc/nnc_cbmm_grouped.hip,
 DESIGN.md section 17), on float32, bfloat16 and float16 inputs as ``CompressedDense`` does.  compress_network and load_network
-build it for a layer fitted that way; it has a byte form only, so ``sparse``, ``packed`` and ``trainable`` raise
-``NotImplementedError`` naming the layer.
+build it for a layer fitted that way; there ``sparse``, ``packed`` and ``trainable`` raise ``NotImplementedError`` naming the
+layer.  ``pack_grouped_layers(network, packed=True | "auto")`` is the way to the 2- and 4-bit packed form of grouped layers of at
+most 16 centres per group: ``GroupedPackedCompressedDense`` (ops.grouped_packed_codebook_matmul, csrc/nnc_cbpk_grouped.hip,
+DESIGN.md section 18), the same function from a half or a quarter of the index bytes, on the same three input dtypes.
 
 These layers are inference only: under autograd, with an input that needs a gradient, they raise instead of returning a result
 that silently has none.  ``trainable=True`` in compress_network / Trainer.compressed_network gives the trainable variants instead
@@ -62,7 +65,7 @@ layer by the rule above applied to the trainable forms.
 How the classes are laid out: ``_Activated`` (the activation behind the product, ``get_weights``) is the root of
 ``_InferenceLayer`` (the float32 ``centers`` / ``bias`` buffers behind the family's index buffer, ``nbytes``) and of
 ``_TrainableCentres`` (the ``centers`` parameter, ``counts``, the three kinds of bias).  A family -- ``_CodebookLayer``,
-``GroupedCompressedDense``, ``_SparseCodebookLayer``, ``_PackedCodebookLayer`` and the three trainable ones -- adds its index
+``GroupedCompressedDense``, ``GroupedPackedCompressedDense``, ``_SparseCodebookLayer``, ``_PackedCodebookLayer`` and the three trainable ones -- adds its index
 buffer and the one ops call of ``_matmul``; ``_SparseForm`` / ``_PackedForm`` hold what the inference and the trainable layer of
 a form share (the ``packed`` buffer, the metadata, ``codes``).  ``_DenseHalf`` and ``_Conv2DHalf`` are the two forwards over
 ``_matmul``; a public class is one of them on a family, with the constructors of its own signature.
@@ -244,7 +247,7 @@ def _is_grouped(model) -> bool:
 
 def _grouped_only_byte_form(name, what):
     raise NotImplementedError(f"layer {name!r} has group-wise codebooks (group_rows): {what} is not implemented for it; "
-                              "it runs in the byte form only (GroupedCompressedDense)")
+                              "build it in the byte form (GroupedCompressedDense); pack_grouped_layers packs its indices afterwards")
 
 
 def keras_rows_for_unfold(h: int, w: int, cin: int) -> np.ndarray:
@@ -661,6 +664,47 @@ class TrainablePackedCompressedConv2D(_Conv2DHalf, _TrainablePackedCodebookLayer
         return cls(kernel_size, cin, pad, codes, labels, centers, bias, bias_codes, activation)
 
 
+class GroupedPackedCompressedDense(_DenseHalf, _PackedForm, _InferenceLayer):
+    """Dense run from one codebook per block of ``group_rows`` input rows and the 2- or 4-bit packed form of its (in, out) indices
+    (ops.grouped_packed_codebook_matmul): packed (the ordinary packed buffer of the whole index matrix),
+    centers float32 (G, K <= 2^bits), G = ceil(kdim / group_rows), bias float32[ncols] or None.  The path follows the input's
+    dtype as in GroupedCompressedDense (float32, bfloat16, float16; the output has the input's dtype); centers and bias stay
+    float32.  No kdim * ncols tensor stays resident."""
+
+    def __init__(self, codes: ops.PackedCodes, group_rows: int, centers: torch.Tensor, bias: torch.Tensor | None, activation=None):
+        super().__init__()
+        groups = max(1, -(-codes.kdim // int(group_rows)))
+        if centers.dim() != 2 or tuple(centers.shape) != (groups, codes.k):
+            raise ValueError(f"centers must have shape ({groups}, {codes.k}) for {codes.kdim} rows in groups of {group_rows} and indices into "
+                             f"codebooks of {codes.k}, got {tuple(centers.shape)}")
+        self._take_codes(codes)
+        self.group_rows = int(group_rows)
+        self._init_codebook(centers, bias, activation)
+
+    @classmethod
+    def from_dense(cls, dense, grouped_model, bias_model=None, bits=None) -> "GroupedPackedCompressedDense":
+        """From a Dense layer and the GroupedModel of its kernel (utility.get_quantized_weight_grouped), K <= 16."""
+        _require_model(grouped_model)
+        kin, kout = dense.kernel.shape
+        centers = torch.from_numpy(np.ascontiguousarray(grouped_model.cluster_centers_, dtype=np.float32)).to(dense.kernel.device)
+        return cls.from_codes(kin, kout, grouped_model.group_rows, grouped_model.labels_compact_, centers, _decoded_bias(dense.bias, bias_model),
+                              dense.activation, bits)
+
+    @classmethod
+    def from_codes(cls, kdim, ncols, group_rows, labels, centers, bias, activation, bits=None) -> "GroupedPackedCompressedDense":
+        if centers.dim() != 2:
+            raise ValueError(f"centers must have shape (G, K), got {tuple(centers.shape)}")
+        return cls(ops.pack_codes(labels, kdim, ncols, centers.shape[1], bits), group_rows, centers, bias, activation)
+
+    @classmethod
+    def from_grouped(cls, layer: GroupedCompressedDense, bits=None) -> "GroupedPackedCompressedDense":
+        """The same layer from the packed form of a GroupedCompressedDense's indices: the same function, bit for bit."""
+        return cls.from_codes(layer.kdim, layer.ncols, layer.group_rows, layer.labels, layer.centers, layer.bias, layer.activation, bits)
+
+    def _matmul(self, x: torch.Tensor) -> torch.Tensor:
+        return self._activate(ops.grouped_packed_codebook_matmul(x, self.codes, self.centers, self.group_rows, bias=self.bias, relu=self._fused_relu))
+
+
 PACKED_MAX_K = 16   # the packed form holds at most 4-bit indices
 
 
@@ -753,7 +797,8 @@ def compress_network(network: nn.Module, models_by_layer, sparse=False, trainabl
     ``trainable=True`` (dense indices only): TrainableCompressedDense / TrainableCompressedConv2D, centres as parameters;
     compress_network_trainable gives the bitmap-sparse and the packed trainable layers too.
     A layer whose kernel model is a utility.GroupedModel (one codebook per block of input rows) becomes a GroupedCompressedDense;
-    with ``sparse``, ``packed`` or ``trainable`` set it raises NotImplementedError and names the layer."""
+    with ``sparse``, ``packed`` or ``trainable`` set it raises NotImplementedError and names the layer (pack_grouped_layers packs
+    the grouped layers of the result)."""
     _check_sparse(sparse)
     _check_packed(packed, sparse, trainable)
     if trainable and sparse is not False:
@@ -807,7 +852,8 @@ def load_network(path: str, network: nn.Module, device=None, sparse=False, packe
     """``compress_network`` from a stored network (storage.save_compressed, as Trainer.store_report writes it: records
     "{layer}.weights" / "{layer}.biases", or "{layer}.weights#g{g}" per group of a kernel with group-wise codebooks, whose
     ``group_rows`` is the row count of the first).  ``network`` gives the architecture; layers stored raw get the stored float32 values.
-    ``sparse`` and ``packed`` as in compress_network: the stored format is the same, the indices are packed after loading."""
+    ``sparse`` and ``packed`` as in compress_network: the stored format is the same, the indices are packed after loading.  A
+    kernel with group-wise codebooks raises NotImplementedError for either; pack_grouped_layers packs it after loading."""
     from . import storage
 
     _check_sparse(sparse)
@@ -846,6 +892,25 @@ def load_network(path: str, network: nn.Module, device=None, sparse=False, packe
             continue
         shape, centers, labels = went
         setattr(out, name, _from_codes(layer, tuple(shape), labels, centers, bias, sparse, packed))
+    return out
+
+
+def pack_grouped_layers(network: nn.Module, packed=True) -> nn.Module:
+    """A deep copy of a compressed ``network`` (compress_network, Trainer.compressed_network() or load_network) whose
+    GroupedCompressedDense layers keep their indices in the 2- or 4-bit packed form (GroupedPackedCompressedDense, DESIGN.md section
+    18).  ``packed``: True (every grouped layer of at most 16 centres per group) or "auto" (a layer only where the packed form
+    holds fewer resident bytes; on equal bytes the byte form stays); anything else is a ValueError.  Grouped layers of more than
+    16 centres and all other layers are left as they are.  Every replaced layer computes what it computed before, bit for bit."""
+    if packed is not True and packed != "auto":
+        raise ValueError(f"packed must be True or 'auto', got {packed!r}")
+    out = copy.deepcopy(network)
+    for name, layer in out.get_config().items():
+        if not isinstance(layer, GroupedCompressedDense) or layer.centers.shape[1] > PACKED_MAX_K:
+            continue
+        bits = ops.packed_bits(layer.centers.shape[1])
+        if packed == "auto" and ops.packed_nbytes(layer.kdim, layer.ncols, bits) >= layer.labels.numel():
+            continue
+        setattr(out, name, GroupedPackedCompressedDense.from_grouped(layer))
     return out
 
 

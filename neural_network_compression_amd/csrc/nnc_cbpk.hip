@@ -143,69 +143,6 @@ extern "C" int nnc_cbpk_unpack(const void *packed, int64_t packed_bytes, int bit
     return NNC_OK;
 }
 
-// ------------------------------------------------------------------ the plan (host)
-// Every decision nnc_cbpk_f32 takes before it launches; nnc_cbpk_plan reports it.
-struct PkPlan {
-    int path;                // NNC_CBMM_NONE / _STREAM / _TILED / _BIAS
-    int vb, mt;              // stream: packed bytes per lane per row, rows of x per launch (a power of two >= m)
-    int cols, xrows;         // stream: columns per lane per row (8 * vb / bits), rows of x per pass over the indices (= mt: one pass)
-    int table, copies, entries;
-    long long col_tiles, row_tiles;
-    long long splits, rows_per_split;
-    long long lds;
-};
-
-static PkPlan pk_plan(long long m, long long kdim, long long ncols, int bits, int cus)
-{
-    PkPlan p{};
-    if (m == 0 || ncols == 0) return p;
-    if (kdim == 0) {
-        p.path = NNC_CBMM_BIAS;
-        return p;
-    }
-    cus = std::max(1, std::min(cus, CB_PLAN_CUS));
-    p.table = NNC_CBPK_TABLE_BANKED;
-    p.entries = 1 << bits;
-    long long s;
-    if (m <= CB_SKINNY_M) {
-        p.path = NNC_CBMM_STREAM;
-        p.mt = cb_mt(m);
-        p.xrows = p.mt;
-        // every wave keeps at least one batch of rows; the partials (splits x m x ncols x 4 B) stay within the packed index
-        // stream (kdim x ncols x bits / 8 B)
-        const long long s_max = std::max(1LL, std::min(kdim / (CB_WAVES * CB_UNROLL), kdim * bits / (32 * m)));
-        // bytes per lane: at most a 16-byte load and PK_ACC accumulators; from there down to 4 bytes, the widest load that
-        // keeps four lanes in five on a column (the last column tile may be nearly empty) and gives every CU of the planning
-        // device a workgroup; else the narrowest.  Shape alone decides, so the splits below never shrink with more CUs.
-        const int cap = std::min(128 / bits, PK_ACC / p.mt);
-        p.cols = cap;
-        for (int c = cap; c * bits >= 32; c /= 2) {
-            p.cols = c;
-            const long long tiles = cdiv(ncols, 64LL * c);
-            if (tiles * 64 * c * 4 <= ncols * 5 && tiles * s_max >= CB_PLAN_CUS) break;
-        }
-        p.vb = p.cols * bits / 8;
-        p.copies = PK_COPIES;
-        p.row_tiles = 1;
-        p.col_tiles = cdiv(ncols, 64LL * p.cols);
-        s = std::min(cdiv(2LL * cus, p.col_tiles), s_max);          // enough workgroups for two per CU
-        p.lds = ((long long)p.entries * p.copies + (long long)p.mt * p.cols * 64 + p.entries) * 4;
-    } else {
-        p.path = NNC_CBMM_TILED;
-        p.copies = 1;
-        p.col_tiles = cdiv(ncols, TB_N);
-        p.row_tiles = cdiv(m, TB_M);
-        s = std::min({cdiv(2LL * cus, p.col_tiles * p.row_tiles), kdim / (16 * TB_K), 16LL});
-        p.lds = (long long)(TB_K * TB_M + TB_K * TB_N + p.entries) * 4;
-    }
-    s = std::max(1LL, s);
-    p.rows_per_split = cdiv(kdim, s);
-    p.splits = cdiv(kdim, p.rows_per_split);
-    return p;
-}
-
-static int64_t pk_ws_bytes(const PkPlan &p, long long m, long long ncols) { return p.splits > 1 ? (int64_t)p.splits * m * ncols * 4 : 0; }
-
 // ------------------------------------------------------------------ skinny: m <= 16
 // grid (col_tiles, splits), CB_THREADS threads.  `out` is y (splits == 1: + bias, ReLU here) or the partials [split][m][ncols].
 template <int BITS, int VB, int MT>

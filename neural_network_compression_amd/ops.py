@@ -296,7 +296,7 @@ def gather(centers: torch.Tensor, labels: torch.Tensor) -> torch.Tensor:
 
 
 # ------------------------------------------------------------------ codebook products: the steps every index form shares
-# The byte, grouped, bitmap-sparse and packed wrappers below run these in the same order; what differs per form (the dtype
+# The byte, grouped, bitmap-sparse, packed and grouped packed wrappers below run these in the same order; what differs per form (the dtype
 # rule of x, the checks of the indices, the native call) stays in the form's own function, between them.
 def _workspace(nbytes: int, dev) -> torch.Tensor | None:
     """The uint8 scratch of ``nbytes`` a native call asked for, or None when it needs none."""
@@ -863,6 +863,50 @@ def cbpk_plan(m: int, kdim: int, ncols: int, bits: int, k: int, cus: int) -> dic
     """Host: the plan nnc_cbpk_f32 follows on a device with ``cus`` compute units (include/nnc.h, nnc_cbpk_plan), as a dict keyed
     by _native.CBPK_PLAN_FIELDS.  No device needed."""
     return _plan(nat.load().nnc_cbpk_plan, nat.CBPK_PLAN_FIELDS, m, kdim, ncols, bits, k, cus)
+
+
+def grouped_packed_codebook_matmul(x: torch.Tensor, codes: PackedCodes, centers: torch.Tensor, group_rows: int, bias: torch.Tensor | None = None,
+                                   relu: bool = False, out_dtype=None) -> torch.Tensor:
+    """y = x @ W + bias (then ReLU) with one codebook per block of ``group_rows`` input rows, W[i, o] = centers[i // group_rows]
+    [label (i, o)] read from the 2- or 4-bit packed indices (include/nnc.h, nnc_cbpk_grouped):
+    grouped_codebook_matmul on the unpacked labels, bit for bit, from a half or a quarter of the index bytes.  x: float32, bfloat16
+    or float16 (..., kdim); codes: the PackedCodes of the whole (kdim, ncols) index matrix (ops.pack_codes); centers: float32
+    (G, K), G = ceil(kdim / group_rows), K = codes.k <= 2^bits; group_rows: a positive multiple of 32; bias: float32[ncols] or None.
+    ``out_dtype`` and half x are as for grouped_codebook_matmul.  Inference only: it raises under autograd."""
+    if not isinstance(x, torch.Tensor) or x.dtype not in _X_DT:
+        raise TypeError(f"x must be a float32, bfloat16 or float16 tensor, got {getattr(x, 'dtype', type(x))}")
+    _require_cuda(x, "x")
+    if out_dtype not in (None, torch.float32):
+        raise TypeError(f"out_dtype must be None ({x.dtype}) or torch.float32, got {out_dtype}")
+    y_dtype = x.dtype if out_dtype is None else out_dtype
+    if not isinstance(codes, PackedCodes):
+        raise TypeError("codes must be a PackedCodes (ops.pack_codes)")
+    _require_centers_bias(centers, bias)
+    group_rows = int(group_rows)
+    _inference_only("grouped_packed_codebook_matmul", "x, codes, centers and bias", x, codes.packed, centers, bias)
+    if group_rows < 32 or group_rows % 32:
+        raise ValueError(f"group_rows must be a positive multiple of 32, got {group_rows}")
+    kdim, ncols = codes.kdim, codes.ncols
+    groups = max(-(-kdim // group_rows), 1)
+    if centers.dim() != 2 or tuple(centers.shape) != (groups, codes.k):
+        raise ValueError(f"centers must have shape ({groups}, {codes.k}) for kdim {kdim}, group_rows {group_rows} and codes of k = {codes.k}, "
+                         f"got {tuple(centers.shape)}")
+    lead, m = _rows(x, "x", kdim)
+    y = _empty_y(x, lead, ncols, bias, y_dtype)
+    L = nat.load()
+    ws_bytes = int(L.nnc_cbpk_grouped_workspace_bytes(_X_DT[x.dtype], m, kdim, ncols, codes.bits))
+    ws = _workspace(ws_bytes, x.device)
+    nat.check(L.nnc_cbpk_grouped(_ptr(x), _X_DT[x.dtype], m, kdim, _ptr(codes.packed), codes.nbytes, codes.bits, ncols, _ptr(centers), codes.k, group_rows,
+                                 _ptr(bias), 1 if relu else 0, _ptr(y), _X_DT[y_dtype], _ptr(ws), ws_bytes, _stream(x)))
+    return y
+
+
+def cbpk_grouped_plan(dtype, m: int, kdim: int, ncols: int, bits: int, k: int, group_rows: int, cus: int) -> dict:
+    """Host: the plan nnc_cbpk_grouped follows for x of ``dtype`` (torch.float32 / bfloat16 / float16) on a device with ``cus``
+    compute units (include/nnc.h, nnc_cbpk_grouped_plan), as a dict keyed by _native.CBPK_GROUPED_PLAN_FIELDS.  No device needed."""
+    if dtype not in _X_DT:
+        raise TypeError(f"dtype must be torch.float32, torch.bfloat16 or torch.float16, got {dtype}")
+    return _plan(nat.load().nnc_cbpk_grouped_plan, nat.CBPK_GROUPED_PLAN_FIELDS, _X_DT[dtype], m, kdim, ncols, bits, k, group_rows, cus)
 
 
 def packed_codebook_matmul_dx(g: torch.Tensor, codes: PackedCodes, centers: torch.Tensor) -> torch.Tensor:
