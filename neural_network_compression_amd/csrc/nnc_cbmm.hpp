@@ -4,7 +4,9 @@
 // the split-K combine from here.  The plan (cb_plan) and the stream kernel k_cbmm_stream itself live here too, templated on the
 // type of x: nnc_cbmm.hip instantiates them for float32, nnc_cbmm_h16.hip for bf16 / fp16 activations.  The group-wise unit
 // (nnc_cbmm_grouped.hip: one codebook per block of rows) follows the same plan and takes cb_fill, cb_refill, the label-row loads,
-// tb_tile_fma and HFrag from here.  cb_mt and cb_check_workspace serve every entry point of the nnc_cb*.hip units.
+// tb_tile_fma and HFrag from here.  cb_mt and cb_check_workspace serve every entry point of the nnc_cb*.hip units; cb_check_operands,
+// cb_direct and cb_finish the three that take half x (nnc_cbmm_h16, nnc_cbmm_grouped, nnc_cbpk_grouped).  The MFMA tile of those
+// three is nnc_cbmfma.hpp.
 #pragma once
 #include "nnc_common.hpp"
 #include <type_traits>
@@ -145,6 +147,42 @@ static inline int cb_check_workspace(const char *fn, const char *query, const vo
     if (need > 0 && !workspace) return fail(NNC_EINVAL, f + ": workspace is NULL");
     if (need > 0 && align > 0 && reinterpret_cast<uintptr_t>(workspace) % align) return fail(NNC_EINVAL, f + ": " + misaligned);
     return NNC_OK;
+}
+
+// The operand checks of a forward entry point `fn` (nnc_cbmm_h16, nnc_cbmm_grouped, nnc_cbpk_grouped) behind its size checks, in
+// the order each makes them: y_dtype is float32 or x's type, centers, y where there is an output, the inputs where there is a
+// product (`inputs_missing`, worded `inputs`: "x or labels", "x"), x and y aligned to their element size.  NNC_EINVAL or NNC_OK.
+static inline int cb_check_operands(const char *fn, const void *x, int x_dtype, const void *y, int y_dtype, const void *centers, int64_t m, int64_t kdim,
+                                    int64_t ncols, bool inputs_missing, const char *inputs)
+{
+    const std::string f(fn);
+    if (y_dtype != NNC_DT_F32 && y_dtype != x_dtype) return fail(NNC_EINVAL, f + ": y_dtype must be NNC_DT_F32 or x_dtype");
+    if (!centers) return fail(NNC_EINVAL, f + ": centers is NULL");
+    if (m > 0 && ncols > 0 && !y) return fail(NNC_EINVAL, f + ": y is NULL");
+    if (m > 0 && ncols > 0 && kdim > 0 && inputs_missing) return fail(NNC_EINVAL, f + ": " + inputs + " is NULL");
+    const int xb = x_dtype == NNC_DT_F32 ? 4 : 2, yb = y_dtype == NNC_DT_F32 ? 4 : 2;
+    if (reinterpret_cast<uintptr_t>(x) % xb || reinterpret_cast<uintptr_t>(y) % yb) return fail(NNC_EINVAL, f + ": x or y is not aligned to its element size");
+    return NNC_OK;
+}
+
+// what the main kernel of such an entry point writes: y itself with one split (direct 1: float32, 2: x's type), else (0) the float32
+// partials into the workspace, which cb_finish then sums into y (k_cbmm_reduce)
+static inline int cb_direct(long long splits, int y_dtype) { return splits == 1 ? (y_dtype == NNC_DT_F32 ? 1 : 2) : 0; }
+static inline int cb_finish(int direct, const void *workspace, long long splits, long long mn, long long ncols, const float *bias, int relu, void *y,
+                            int y_dtype, hipStream_t s)
+{
+    return direct ? NNC_OK : cbmm_reduce_dt(reinterpret_cast<const float *>(workspace), splits, mn, ncols, bias, relu, y, y_dtype, s);
+}
+
+// the most groups of group_rows rows that the rows of one split lie in (the group-wise units report it in their plans)
+static inline long long max_groups_per_split(long long splits, long long rows_per_split, long long kdim, long long group_rows)
+{
+    long long most = 0;
+    for (long long s = 0; s < splits; ++s) {
+        const long long lo = s * rows_per_split, hi = std::min(kdim, lo + rows_per_split);
+        most = std::max(most, (hi - 1) / group_rows - lo / group_rows + 1);
+    }
+    return most;
 }
 
 // the per-bank table: entry j of lane l at word j * copies + (l mod copies), copies = 1 << cshift

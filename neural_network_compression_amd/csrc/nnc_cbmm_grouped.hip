@@ -5,11 +5,13 @@
 // those of nnc_cbmm_f32 / nnc_cbmm_h16.  The kernels are the ungrouped ones with one addition: a workgroup that walks from one group's
 // rows into the next changes its LDS table.  They are kernels of their own and not instantiations of a body shared with the
 // ungrouped ones: called through a device function, k_cbmm_stream compiles to another instruction stream.  The tiled one is, like
-// k_cbmm_tiled, the tile skeleton of nnc_cbtile.hpp around its decode.
+// k_cbmm_tiled, the tile skeleton of nnc_cbtile.hpp around its decode; the MFMA one is, like k_cbmm_mfma, the tile of nnc_cbmfma.hpp
+// around its table (cb_fill, cb_refill where a step opens a group), its label load and its lookup.
 //   k_cbmm_stream_grouped  m <= 16: the split is walked group by group, the four waves share each stretch and the table.
 //   k_cbmm_tiled_grouped   m > 16, float32 x: two small tables in LDS, a TB_K step may lie across a boundary.
 //   k_cbmm_mfma_grouped    m > 16, bf16 / fp16 x: a k step of HM_BK never lies across a boundary (group_rows is a multiple of 32).
 // With one group every kernel computes what its ungrouped counterpart computes, bit for bit.
+#include "nnc_cbmfma.hpp"
 #include "nnc_cbtile.hpp"
 
 // ------------------------------------------------------------------ skinny: m <= 16
@@ -218,7 +220,8 @@ __global__ __launch_bounds__(256) void k_cbmm_tiled_grouped(const float *__restr
 }
 
 // ------------------------------------------------------------------ MFMA tile: m > 16, bf16 / fp16 x
-// k_cbmm_mfma (nnc_cbmm_h16.hip) with uint8 labels and centers[groups][k]: the same grid, images and MFMA order.  Splits start on
+// k_cbmm_mfma (nnc_cbmm_h16.hip) with uint8 labels and centers[groups][k]: the same grid and the same tile (nnc_cbmfma.hpp: images,
+// MFMA order, epilogue); its own are the group walk, the label load and the lookup.  Splits start on
 // whole k steps of HM_BK = 32 and group_rows is a multiple of 32, so a step lies in one group.  A step that opens a group rewrites
 // the first k table entries ahead of its first barrier: the lookups of the step before ended at that step's second barrier.
 template <typename XT, bool XVEC>
@@ -228,9 +231,6 @@ __global__ __launch_bounds__(HM_THREADS) void k_cbmm_mfma_grouped(const XT *__re
                                                                   const float *__restrict__ bias, int relu, int direct, void *__restrict__ out_)
 {
     using LT = uint8_t;
-    using F = HFrag<XT>;
-    using V = typename F::V;
-    using C = typename F::C;
     extern __shared__ __attribute__((aligned(16))) float hm_smem[];
     float *cb = hm_smem;                                // entries << cshift
     float *stage = cb + (entries << cshift);            // entries
@@ -239,118 +239,42 @@ __global__ __launch_bounds__(HM_THREADS) void k_cbmm_mfma_grouped(const XT *__re
     long long group = (long long)blockIdx.y * rows_per_split / group_rows;
     cb_fill<XT>(cb, stage, centers + group * k, k, entries, cshift);
 
-    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
-    const long long n0 = (blockIdx.x % col_tiles) * HM_BN, m0 = (blockIdx.x / col_tiles) * HM_BM;
-    const long long k_lo = (long long)blockIdx.y * rows_per_split, k_hi = std::min(kdim, k_lo + rows_per_split);
-
-    // W: thread t owns column wc of the tile and its 16 rows wk0 .. wk0 + 15 of the k step
-    const int wc = t & (HM_BN - 1), wk0 = (t >> 7) * 16;
-    const long long gc = n0 + wc;
+    const HmTile T = hm_tile(col_tiles, rows_per_split, kdim);
+    const long long gc = T.n0 + T.wc;
     const bool col_ok = gc < ncols;
-    // x: fragments f = t and t + 256 of the 128 rows x 4 fragments of 8
     uint32_t lab[16];
     uint4 xf[2];
 
     auto load = [&](long long kb) {
 #pragma unroll
         for (int j = 0; j < 16; ++j) {
-            const long long gk = kb + wk0 + j;
-            lab[j] = (col_ok && gk < k_hi) ? (uint32_t)labels[gk * ncols + gc] : 0u;
+            const long long gk = kb + T.wk0 + j;
+            lab[j] = (col_ok && gk < T.k_hi) ? (uint32_t)labels[gk * ncols + gc] : 0u;
         }
 #pragma unroll
-        for (int i = 0; i < 2; ++i) {
-            const int f = t + i * HM_THREADS;
-            const long long gr = m0 + (f >> 2), gk = kb + (f & 3) * 8;
-            xf[i] = make_uint4(0u, 0u, 0u, 0u);
-            if (gr < m) {
-                if constexpr (XVEC) {   // kdim, k_lo and gk are multiples of 8: the fragment lies wholly before k_hi or wholly past it
-                    if (gk < k_hi) xf[i] = *reinterpret_cast<const uint4 *>(x + gr * kdim + gk);
-                } else {
-                    const unsigned short *xr = reinterpret_cast<const unsigned short *>(x + gr * kdim);
-                    uint32_t h[8];
-#pragma unroll
-                    for (int e = 0; e < 8; ++e) h[e] = gk + e < k_hi ? (uint32_t)xr[gk + e] : 0u;
-                    xf[i] = make_uint4(h[0] | h[1] << 16, h[2] | h[3] << 16, h[4] | h[5] << 16, h[6] | h[7] << 16);
-                }
-            }
-        }
+        for (int i = 0; i < 2; ++i) xf[i] = hm_load_x<XT, XVEC>(x, m, kdim, T.m0, kb, T.k_hi, T.t + i * HM_THREADS);
     };
     auto store = [&](long long kb) {
-        V w0, w1;
+        float w[16];
 #pragma unroll
-        for (int j = 0; j < 16; ++j) {
-            const float v = (col_ok && kb + wk0 + j < k_hi) ? cb[CbTable<LT>::index(lab[j], k, cshift, lane)] : 0.0f;
-            if (j < 8) w0[j] = (XT)v;   // exact: the table holds values of XT
-            else w1[j - 8] = (XT)v;
-        }
-        *reinterpret_cast<V *>(ws + wc * HM_LD + wk0) = w0;
-        *reinterpret_cast<V *>(ws + wc * HM_LD + wk0 + 8) = w1;
+        for (int j = 0; j < 16; ++j) w[j] = (col_ok && kb + T.wk0 + j < T.k_hi) ? cb[CbTable<LT>::index(lab[j], k, cshift, T.lane)] : 0.0f;
+        hm_store_w(ws, T.wc, T.wk0, w);
 #pragma unroll
-        for (int i = 0; i < 2; ++i) {
-            const int f = t + i * HM_THREADS;
-            *reinterpret_cast<uint4 *>(xs + (f >> 2) * HM_LD + (f & 3) * 8) = xf[i];
-        }
+        for (int i = 0; i < 2; ++i) hm_store_x(xs, T.t + i * HM_THREADS, xf[i]);
     };
 
-    C acc[2][2];
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.0f;
-
-    // lane l of a 32x32x16 MFMA holds A[row l & 31][k = 8 (l >> 5) + e] and B[k = 8 (l >> 5) + e][col l & 31], e = 0..7
-    const int wm = (wave >> 1) * 64, wn = (wave & 1) * 64, fr = lane & 31, fh = (lane >> 5) * 8;
-    load(k_lo);
-    for (long long kb = k_lo; kb < k_hi; kb += HM_BK) {
+    typename HFrag<XT>::C acc[2][2];
+    hm_clear<XT>(acc);
+    load(T.k_lo);
+    for (long long kb = T.k_lo; kb < T.k_hi; kb += HM_BK) {
         if (kb >= (group + 1) * group_rows) cb_refill<XT>(cb, centers + ++group * k, k, cshift);   // this step opens a group
         __syncthreads();   // the table is filled (first step); the images of the step before have been read
         store(kb);
         __syncthreads();
-        if (kb + HM_BK < k_hi) load(kb + HM_BK);
-#pragma unroll
-        for (int s = 0; s < HM_BK; s += 16) {
-            V a[2], b[2];
-#pragma unroll
-            for (int i = 0; i < 2; ++i) {
-                a[i] = *reinterpret_cast<const V *>(xs + (wm + i * 32 + fr) * HM_LD + s + fh);
-                b[i] = *reinterpret_cast<const V *>(ws + (wn + i * 32 + fr) * HM_LD + s + fh);
-            }
-#pragma unroll
-            for (int i = 0; i < 2; ++i)
-#pragma unroll
-                for (int j = 0; j < 2; ++j) acc[i][j] = F::mfma(a[i], b[j], acc[i][j]);
-        }
+        if (kb + HM_BK < T.k_hi) load(kb + HM_BK);
+        hm_step(xs, ws, T.wm, T.wn, T.fr, T.fh, acc);
     }
-
-    // C / D: register r of lane l is row (r & 3) + 8 (r >> 2) + 4 (l >> 5), column l & 31
-    float *outf = reinterpret_cast<float *>(out_);
-#pragma unroll
-    for (int i = 0; i < 2; ++i) {
-#pragma unroll
-        for (int j = 0; j < 2; ++j) {
-            const long long c = n0 + wn + j * 32 + fr;
-            if (c >= ncols) continue;
-            const float bv = (direct && bias) ? bias[c] : 0.0f;
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const long long row = m0 + wm + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
-                if (row >= m) continue;
-                float v = acc[i][j][r];
-                if (direct) {
-                    if (bias) v += bv;
-                    if (relu) v = v < 0.0f ? 0.0f : v;   // NaN stays NaN, as torch.relu
-                    if (direct == 2)
-                        reinterpret_cast<XT *>(out_)[row * ncols + c] = (XT)v;
-                    else
-                        outf[row * ncols + c] = v;
-                } else {
-                    outf[((long long)blockIdx.y * m + row) * ncols + c] = v;
-                }
-            }
-        }
-    }
+    hm_store_y<XT>(acc, T.n0, T.m0, T.wm, T.wn, T.lane, m, ncols, bias, relu, direct, out_);
 }
 
 // ------------------------------------------------------------------ launches
@@ -368,16 +292,12 @@ static void launch_stream(bool aligned, dim3 grid, size_t lds, hipStream_t s, co
 }
 
 template <typename XT>
-static void launch_mfma(bool xvec, dim3 grid, size_t lds, hipStream_t s, const void *x, long long m, long long kdim, const void *labels, long long ncols,
+static void launch_mfma(dim3 grid, size_t lds, hipStream_t s, const void *x, long long m, long long kdim, const void *labels, long long ncols,
                         const float *centers, int k, int entries, int cshift, long long col_tiles, long long rps, long long group_rows, const float *bias,
                         int relu, int direct, void *out)
 {
-    const XT *xp = reinterpret_cast<const XT *>(x);
-    const uint8_t *lab = reinterpret_cast<const uint8_t *>(labels);
-    if (xvec)
-        hipLaunchKernelGGL((k_cbmm_mfma_grouped<XT, true>), grid, dim3(HM_THREADS), lds, s, xp, m, kdim, lab, ncols, centers, k, entries, cshift, col_tiles, rps, group_rows, bias, relu, direct, out);
-    else
-        hipLaunchKernelGGL((k_cbmm_mfma_grouped<XT, false>), grid, dim3(HM_THREADS), lds, s, xp, m, kdim, lab, ncols, centers, k, entries, cshift, col_tiles, rps, group_rows, bias, relu, direct, out);
+    hm_launch(x, kdim, k_cbmm_mfma_grouped<XT, true>, k_cbmm_mfma_grouped<XT, false>, grid, lds, s, reinterpret_cast<const XT *>(x), m, kdim,
+              reinterpret_cast<const uint8_t *>(labels), ncols, centers, k, entries, cshift, col_tiles, rps, group_rows, bias, relu, direct, out);
 }
 
 // every stream instantiation of this unit; the plan is checked against this table, and the launch goes through it
@@ -428,17 +348,6 @@ static CbPlan grouped_plan(int x_dtype, long long m, long long kdim, long long n
     return p;
 }
 
-// the most groups a split's rows lie in
-static long long max_groups_per_split(const CbPlan &p, long long kdim, long long group_rows)
-{
-    long long most = 0;
-    for (long long s = 0; s < p.splits; ++s) {
-        const long long lo = s * p.rows_per_split, hi = std::min(kdim, lo + p.rows_per_split);
-        most = std::max(most, (hi - 1) / group_rows - lo / group_rows + 1);
-    }
-    return most;
-}
-
 extern "C" int64_t nnc_cbmm_grouped_workspace_bytes(int x_dtype, int64_t m, int64_t kdim, int64_t ncols)
 {
     return x_dtype == NNC_DT_F32 ? nnc_cbmm_workspace_bytes(m, kdim, ncols, 1) : nnc_cbmm_h16_workspace_bytes(m, kdim, ncols, 1);
@@ -456,7 +365,7 @@ extern "C" int nnc_cbmm_grouped_plan(int x_dtype, int64_t m, int64_t kdim, int64
     if (rc != NNC_OK) return rc;
     const int64_t v[NNC_CBMM_GROUPED_PLAN_LEN] = {p.path, p.vb, p.mt, p.path == NNC_CBMM_TILED ? 2 : (p.entries ? 1LL << p.cshift : 0), p.entries, p.splits,
                                                   p.rows_per_split, p.aligned, p.lds, p.col_tiles, p.row_tiles, cb_ws_bytes(p, m, ncols), x_dtype, group_rows,
-                                                  kdim > 0 ? cdiv(kdim, group_rows) : 0, p.splits > 0 ? max_groups_per_split(p, kdim, group_rows) : 0};
+                                                  kdim > 0 ? cdiv(kdim, group_rows) : 0, p.splits > 0 ? max_groups_per_split(p.splits, p.rows_per_split, kdim, group_rows) : 0};
     for (int i = 0; i < NNC_CBMM_GROUPED_PLAN_LEN; ++i) out[i] = v[i];
     return NNC_OK;
 }
@@ -467,13 +376,7 @@ extern "C" int nnc_cbmm_grouped(const void *x, int x_dtype, int64_t m, int64_t k
 {
     int rc = grouped_check(x_dtype, m, kdim, ncols, k, group_rows);
     if (rc != NNC_OK) return rc;
-    if (y_dtype != NNC_DT_F32 && y_dtype != x_dtype) return nnc_set_error_(NNC_EINVAL, "nnc_cbmm_grouped: y_dtype must be NNC_DT_F32 or x_dtype");
-    if (!centers_dev) return nnc_set_error_(NNC_EINVAL, "nnc_cbmm_grouped: centers is NULL");
-    if (m > 0 && ncols > 0 && !y) return nnc_set_error_(NNC_EINVAL, "nnc_cbmm_grouped: y is NULL");
-    if (m > 0 && ncols > 0 && kdim > 0 && (!x || !labels)) return nnc_set_error_(NNC_EINVAL, "nnc_cbmm_grouped: x or labels is NULL");
-    const int xb = x_dtype == NNC_DT_F32 ? 4 : 2, yb = y_dtype == NNC_DT_F32 ? 4 : 2;
-    if (reinterpret_cast<uintptr_t>(x) % xb || reinterpret_cast<uintptr_t>(y) % yb)
-        return nnc_set_error_(NNC_EINVAL, "nnc_cbmm_grouped: x or y is not aligned to its element size");
+    if ((rc = cb_check_operands("nnc_cbmm_grouped", x, x_dtype, y, y_dtype, centers_dev, m, kdim, ncols, !x || !labels, "x or labels")) != NNC_OK) return rc;
     const int64_t need = nnc_cbmm_grouped_workspace_bytes(x_dtype, m, kdim, ncols);
     if ((rc = cb_check_workspace("nnc_cbmm_grouped", "nnc_cbmm_grouped_workspace_bytes", workspace, workspace_bytes, need)) != NNC_OK) return rc;
     if (m == 0 || ncols == 0) return NNC_OK;
@@ -484,7 +387,7 @@ extern "C" int nnc_cbmm_grouped(const void *x, int x_dtype, int64_t m, int64_t k
     if (p.path == NNC_CBMM_BIAS) return cbmm_reduce_dt(nullptr, 0, mn, ncols, bias_dev, relu, y, y_dtype, s);   // kdim = 0: y = bias
     rc = have_kernel(p, x_dtype);
     if (rc != NNC_OK) return rc;
-    const int direct = p.splits == 1 ? (y_dtype == NNC_DT_F32 ? 1 : 2) : 0;
+    const int direct = cb_direct(p.splits, y_dtype);
     void *out = direct ? y : workspace;
     if (p.path == NNC_CBMM_STREAM) {
         const dim3 grid((unsigned)p.col_tiles, (unsigned)p.splits);
@@ -499,11 +402,9 @@ extern "C" int nnc_cbmm_grouped(const void *x, int x_dtype, int64_t m, int64_t k
         LAUNCHCHK("k_cbmm_tiled_grouped");
     } else {
         const dim3 grid((unsigned)(p.col_tiles * p.row_tiles), (unsigned)p.splits);
-        const bool xvec = reinterpret_cast<uintptr_t>(x) % 16 == 0 && kdim % 8 == 0;
-        (x_dtype == NNC_DT_BF16 ? launch_mfma<bf16_t> : launch_mfma<f16_t>)(xvec, grid, (size_t)p.lds, s, x, m, kdim, labels, ncols, centers_dev, k, p.entries,
-                                                                            p.cshift, p.col_tiles, p.rows_per_split, group_rows, bias_dev, relu, direct, out);
+        (x_dtype == NNC_DT_BF16 ? launch_mfma<bf16_t> : launch_mfma<f16_t>)(grid, (size_t)p.lds, s, x, m, kdim, labels, ncols, centers_dev, k, p.entries, p.cshift,
+                                                                            p.col_tiles, p.rows_per_split, group_rows, bias_dev, relu, direct, out);
         LAUNCHCHK("k_cbmm_mfma_grouped");
     }
-    if (!direct) return cbmm_reduce_dt(reinterpret_cast<const float *>(workspace), p.splits, mn, ncols, bias_dev, relu, y, y_dtype, s);
-    return NNC_OK;
+    return cb_finish(direct, workspace, p.splits, mn, ncols, bias_dev, relu, y, y_dtype, s);
 }

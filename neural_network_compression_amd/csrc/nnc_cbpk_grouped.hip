@@ -4,16 +4,19 @@
 //
 // The plan is the ungrouped packed one (pk_plan, nnc_cbpk.hpp) for the stream and the tiled kernel, and the MFMA grid of cb_grid
 // (nnc_cbmm.hpp) for half x at m > 16, so the splits, the workspace and the summation order are those of nnc_cbpk_f32 (of
-// nnc_cbmm_grouped for the MFMA tile).  The kernels are copies of their ungrouped counterparts with the walk through the groups
-// added, not instantiations of a shared body (DESIGN.md section 17 records why):
+// nnc_cbmm_grouped for the MFMA tile).  The stream kernel is a copy of its ungrouped counterpart with the walk through the groups
+// added, not an instantiation of a shared body (DESIGN.md section 17 records why); the tiled one is the tile skeleton of
+// nnc_cbtile.hpp, the MFMA one the tile of nnc_cbmfma.hpp, each around its own tables, label decode and group walk:
 //   k_cbpk_stream_grouped  m <= 16: k_cbpk_stream with x of type XT.  Every wave owns a table (2^BITS entries x 32 per-bank copies:
 //                          2 KiB or 512 B), walks its own rows group by group and rewrites its table at a boundary from the K
 //                          centres it loaded, one per lane, while the stretch before ran: no workgroup barrier, no exposed load.
 //   k_cbpk_tiled_grouped   m > 16, float32 x: k_cbpk_tiled with two tables in LDS, group g in slot g & 1 (a TB_K step may lie
 //                          across a boundary).
-//   k_cbpk_mfma_grouped    m > 16, bf16 / fp16 x: k_cbmm_mfma_grouped with the label of (gk, gc) taken from the packed row.
+//   k_cbpk_mfma_grouped    m > 16, bf16 / fp16 x: k_cbmm_mfma_grouped's walk and the shared tile, the label of (gk, gc) taken from
+//                          the packed row: on the same x and centres, the bits of nnc_cbmm_grouped on the unpacked labels.
 // With one group the stream and the tiled kernel compute what k_cbpk_stream / k_cbpk_tiled compute, bit for bit.
 #include "nnc_cbpk.hpp"
+#include "nnc_cbmfma.hpp"
 #include "nnc_cbtile.hpp"
 
 // ------------------------------------------------------------------ skinny: m <= 16
@@ -217,11 +220,11 @@ __global__ __launch_bounds__(256) void k_cbpk_tiled_grouped(const float *__restr
 }
 
 // ------------------------------------------------------------------ MFMA tile: m > 16, bf16 / fp16 x
-// k_cbmm_mfma_grouped (nnc_cbmm_grouped.hip) with the label of (gk, gc) taken from the packed row: the same grid, images and MFMA
-// order, the per-bank table of 2^BITS entries (the centres rounded to XT, zeros from k on).  Thread t owns column wc of the tile
-// and 16 rows of the k step: 16 byte loads, the threads of neighbouring columns reading the same byte.  Splits start on whole k
-// steps of HM_BK = 32 and group_rows is a multiple of 32, so a step lies in one group; a step that opens a group rewrites the first
-// k table entries ahead of its first barrier: the lookups of the step before ended at that step's second barrier.
+// k_cbmm_mfma_grouped (nnc_cbmm_grouped.hip) with the label of (gk, gc) taken from the packed row: the same grid and the same tile
+// (nnc_cbmfma.hpp), the per-bank table of 2^BITS entries (the centres rounded to XT, zeros from k on).  Thread t owns column wc of
+// the tile and 16 rows of the k step: 16 byte loads, the threads of neighbouring columns reading the same byte.  Splits start on
+// whole k steps of HM_BK = 32 and group_rows is a multiple of 32, so a step lies in one group; a step that opens a group rewrites
+// the first k table entries ahead of its first barrier: the lookups of the step before ended at that step's second barrier.
 template <typename XT, int BITS, bool XVEC>
 __global__ __launch_bounds__(HM_THREADS) void k_cbpk_mfma_grouped(const XT *__restrict__ x, long long m, long long kdim,
                                                                   const unsigned char *__restrict__ packed, long long row_bytes, long long ncols,
@@ -229,9 +232,6 @@ __global__ __launch_bounds__(HM_THREADS) void k_cbpk_mfma_grouped(const XT *__re
                                                                   long long group_rows, const float *__restrict__ bias, int relu, int direct,
                                                                   void *__restrict__ out_)
 {
-    using F = HFrag<XT>;
-    using V = typename F::V;
-    using C = typename F::C;
     constexpr int ENTRIES = 1 << BITS;
     constexpr uint32_t MASK = (1u << BITS) - 1;
     extern __shared__ __attribute__((aligned(16))) float hm_smem[];
@@ -242,120 +242,44 @@ __global__ __launch_bounds__(HM_THREADS) void k_cbpk_mfma_grouped(const XT *__re
     long long group = (long long)blockIdx.y * rows_per_split / group_rows;
     cb_fill<XT>(cb, stage, centers + group * k, k, ENTRIES, PK_CSHIFT);
 
-    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
-    const long long n0 = (blockIdx.x % col_tiles) * HM_BN, m0 = (blockIdx.x / col_tiles) * HM_BM;
-    const long long k_lo = (long long)blockIdx.y * rows_per_split, k_hi = std::min(kdim, k_lo + rows_per_split);
-
-    // W: thread t owns column wc of the tile and its 16 rows wk0 .. wk0 + 15 of the k step
-    const int wc = t & (HM_BN - 1), wk0 = (t >> 7) * 16;
-    const long long gc = n0 + wc;
+    const HmTile T = hm_tile(col_tiles, rows_per_split, kdim);
+    const long long gc = T.n0 + T.wc;
     const bool col_ok = gc < ncols;                     // then byte gc * BITS / 8 lies inside the row
     const long long cbyte = col_ok ? gc * BITS / 8 : 0;
     const int cshift = (int)(gc * BITS % 8);
-    // x: fragments f = t and t + 256 of the 128 rows x 4 fragments of 8
     uint32_t lab[16];
     uint4 xf[2];
 
     auto load = [&](long long kb) {
 #pragma unroll
         for (int j = 0; j < 16; ++j) {
-            const long long gk = kb + wk0 + j;
-            lab[j] = (col_ok && gk < k_hi) ? ((uint32_t)packed[gk * row_bytes + cbyte] >> cshift) & MASK : 0u;
+            const long long gk = kb + T.wk0 + j;
+            lab[j] = (col_ok && gk < T.k_hi) ? ((uint32_t)packed[gk * row_bytes + cbyte] >> cshift) & MASK : 0u;
         }
 #pragma unroll
-        for (int i = 0; i < 2; ++i) {
-            const int f = t + i * HM_THREADS;
-            const long long gr = m0 + (f >> 2), gk = kb + (f & 3) * 8;
-            xf[i] = make_uint4(0u, 0u, 0u, 0u);
-            if (gr < m) {
-                if constexpr (XVEC) {   // kdim, k_lo and gk are multiples of 8: the fragment lies wholly before k_hi or wholly past it
-                    if (gk < k_hi) xf[i] = *reinterpret_cast<const uint4 *>(x + gr * kdim + gk);
-                } else {
-                    const unsigned short *xr = reinterpret_cast<const unsigned short *>(x + gr * kdim);
-                    uint32_t h[8];
-#pragma unroll
-                    for (int e = 0; e < 8; ++e) h[e] = gk + e < k_hi ? (uint32_t)xr[gk + e] : 0u;
-                    xf[i] = make_uint4(h[0] | h[1] << 16, h[2] | h[3] << 16, h[4] | h[5] << 16, h[6] | h[7] << 16);
-                }
-            }
-        }
+        for (int i = 0; i < 2; ++i) xf[i] = hm_load_x<XT, XVEC>(x, m, kdim, T.m0, kb, T.k_hi, T.t + i * HM_THREADS);
     };
     auto store = [&](long long kb) {
-        V w0, w1;
+        float w[16];
 #pragma unroll
-        for (int j = 0; j < 16; ++j) {
-            const float v = (col_ok && kb + wk0 + j < k_hi) ? cb[(lab[j] << PK_CSHIFT) | (lane & (PK_COPIES - 1))] : 0.0f;
-            if (j < 8) w0[j] = (XT)v;   // exact: the table holds values of XT
-            else w1[j - 8] = (XT)v;
-        }
-        *reinterpret_cast<V *>(ws + wc * HM_LD + wk0) = w0;
-        *reinterpret_cast<V *>(ws + wc * HM_LD + wk0 + 8) = w1;
+        for (int j = 0; j < 16; ++j) w[j] = (col_ok && kb + T.wk0 + j < T.k_hi) ? cb[(lab[j] << PK_CSHIFT) | (T.lane & (PK_COPIES - 1))] : 0.0f;
+        hm_store_w(ws, T.wc, T.wk0, w);
 #pragma unroll
-        for (int i = 0; i < 2; ++i) {
-            const int f = t + i * HM_THREADS;
-            *reinterpret_cast<uint4 *>(xs + (f >> 2) * HM_LD + (f & 3) * 8) = xf[i];
-        }
+        for (int i = 0; i < 2; ++i) hm_store_x(xs, T.t + i * HM_THREADS, xf[i]);
     };
 
-    C acc[2][2];
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.0f;
-
-    // lane l of a 32x32x16 MFMA holds A[row l & 31][k = 8 (l >> 5) + e] and B[k = 8 (l >> 5) + e][col l & 31], e = 0..7
-    const int wm = (wave >> 1) * 64, wn = (wave & 1) * 64, fr = lane & 31, fh = (lane >> 5) * 8;
-    load(k_lo);
-    for (long long kb = k_lo; kb < k_hi; kb += HM_BK) {
+    typename HFrag<XT>::C acc[2][2];
+    hm_clear<XT>(acc);
+    load(T.k_lo);
+    for (long long kb = T.k_lo; kb < T.k_hi; kb += HM_BK) {
         if (kb >= (group + 1) * group_rows) cb_refill<XT>(cb, centers + ++group * k, k, PK_CSHIFT);   // this step opens a group
         __syncthreads();   // the table is filled (first step); the images of the step before have been read
         store(kb);
         __syncthreads();
-        if (kb + HM_BK < k_hi) load(kb + HM_BK);
-#pragma unroll
-        for (int s = 0; s < HM_BK; s += 16) {
-            V a[2], b[2];
-#pragma unroll
-            for (int i = 0; i < 2; ++i) {
-                a[i] = *reinterpret_cast<const V *>(xs + (wm + i * 32 + fr) * HM_LD + s + fh);
-                b[i] = *reinterpret_cast<const V *>(ws + (wn + i * 32 + fr) * HM_LD + s + fh);
-            }
-#pragma unroll
-            for (int i = 0; i < 2; ++i)
-#pragma unroll
-                for (int j = 0; j < 2; ++j) acc[i][j] = F::mfma(a[i], b[j], acc[i][j]);
-        }
+        if (kb + HM_BK < T.k_hi) load(kb + HM_BK);
+        hm_step(xs, ws, T.wm, T.wn, T.fr, T.fh, acc);
     }
-
-    // C / D: register r of lane l is row (r & 3) + 8 (r >> 2) + 4 (l >> 5), column l & 31
-    float *outf = reinterpret_cast<float *>(out_);
-#pragma unroll
-    for (int i = 0; i < 2; ++i) {
-#pragma unroll
-        for (int j = 0; j < 2; ++j) {
-            const long long c = n0 + wn + j * 32 + fr;
-            if (c >= ncols) continue;
-            const float bv = (direct && bias) ? bias[c] : 0.0f;
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const long long row = m0 + wm + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
-                if (row >= m) continue;
-                float v = acc[i][j][r];
-                if (direct) {
-                    if (bias) v += bv;
-                    if (relu) v = v < 0.0f ? 0.0f : v;   // NaN stays NaN, as torch.relu
-                    if (direct == 2)
-                        reinterpret_cast<XT *>(out_)[row * ncols + c] = (XT)v;
-                    else
-                        outf[row * ncols + c] = v;
-                } else {
-                    outf[((long long)blockIdx.y * m + row) * ncols + c] = v;
-                }
-            }
-        }
-    }
+    hm_store_y<XT>(acc, T.n0, T.m0, T.wm, T.wn, T.lane, m, ncols, bias, relu, direct, out_);
 }
 
 // ------------------------------------------------------------------ launches
@@ -368,15 +292,12 @@ static void launch_stream(dim3 grid, size_t lds, hipStream_t s, const void *x, i
 }
 
 template <typename XT, int BITS>
-static void launch_mfma(bool xvec, dim3 grid, size_t lds, hipStream_t s, const void *x, long long m, long long kdim, const unsigned char *packed,
-                        long long row_bytes, long long ncols, const float *centers, int k, long long col_tiles, long long rps, long long group_rows,
-                        const float *bias, int relu, int direct, void *out)
+static void launch_mfma(dim3 grid, size_t lds, hipStream_t s, const void *x, long long m, long long kdim, const unsigned char *packed, long long row_bytes,
+                        long long ncols, const float *centers, int k, long long col_tiles, long long rps, long long group_rows, const float *bias, int relu,
+                        int direct, void *out)
 {
-    const XT *xp = reinterpret_cast<const XT *>(x);
-    if (xvec)
-        hipLaunchKernelGGL((k_cbpk_mfma_grouped<XT, BITS, true>), grid, dim3(HM_THREADS), lds, s, xp, m, kdim, packed, row_bytes, ncols, centers, k, col_tiles, rps, group_rows, bias, relu, direct, out);
-    else
-        hipLaunchKernelGGL((k_cbpk_mfma_grouped<XT, BITS, false>), grid, dim3(HM_THREADS), lds, s, xp, m, kdim, packed, row_bytes, ncols, centers, k, col_tiles, rps, group_rows, bias, relu, direct, out);
+    hm_launch(x, kdim, k_cbpk_mfma_grouped<XT, BITS, true>, k_cbpk_mfma_grouped<XT, BITS, false>, grid, lds, s, reinterpret_cast<const XT *>(x), m, kdim,
+              packed, row_bytes, ncols, centers, k, col_tiles, rps, group_rows, bias, relu, direct, out);
 }
 
 // every stream instantiation of this unit: the (bits, vb, mt) of nnc_cbpk.hip's table for each type of x.  The plan is checked
@@ -441,17 +362,6 @@ static int have_kernel(const PkPlan &p, int dt, int bits)
     return NNC_OK;
 }
 
-// the most groups a split's rows lie in
-static long long max_groups_per_split(const PkPlan &p, long long kdim, long long group_rows)
-{
-    long long most = 0;
-    for (long long s = 0; s < p.splits; ++s) {
-        const long long lo = s * p.rows_per_split, hi = std::min(kdim, lo + p.rows_per_split);
-        most = std::max(most, (hi - 1) / group_rows - lo / group_rows + 1);
-    }
-    return most;
-}
-
 // ------------------------------------------------------------------ C ABI
 static int grouped_check(const char *fn, int x_dtype, int64_t m, int64_t kdim, int64_t ncols, int bits, int32_t k, int64_t group_rows)
 {
@@ -481,7 +391,7 @@ extern "C" int nnc_cbpk_grouped_plan(int x_dtype, int64_t m, int64_t kdim, int64
     if ((rc = have_kernel(p, x_dtype, bits)) != NNC_OK) return rc;
     const int64_t v[NNC_CBPK_GROUPED_PLAN_LEN] = {p.path, p.vb, p.mt, p.cols, p.xrows, p.table, p.copies, p.entries, p.splits, p.rows_per_split, p.lds,
                                                   p.col_tiles, p.row_tiles, pk_ws_bytes(p, m, ncols), x_dtype, group_rows,
-                                                  kdim > 0 ? cdiv(kdim, group_rows) : 0, p.splits > 0 ? max_groups_per_split(p, kdim, group_rows) : 0,
+                                                  kdim > 0 ? cdiv(kdim, group_rows) : 0, p.splits > 0 ? max_groups_per_split(p.splits, p.rows_per_split, kdim, group_rows) : 0,
                                                   g.tables};
     for (int i = 0; i < NNC_CBPK_GROUPED_PLAN_LEN; ++i) out[i] = v[i];
     return NNC_OK;
@@ -494,13 +404,7 @@ extern "C" int nnc_cbpk_grouped(const void *x, int x_dtype, int64_t m, int64_t k
     int rc = grouped_check("nnc_cbpk_grouped", x_dtype, m, kdim, ncols, bits, k, group_rows);
     if (rc != NNC_OK) return rc;
     if ((rc = pk_check_buffer("nnc_cbpk_grouped", packed, packed_bytes, kdim, ncols, bits)) != NNC_OK) return rc;
-    if (y_dtype != NNC_DT_F32 && y_dtype != x_dtype) return fail(NNC_EINVAL, "nnc_cbpk_grouped: y_dtype must be NNC_DT_F32 or x_dtype");
-    if (!centers_dev) return fail(NNC_EINVAL, "nnc_cbpk_grouped: centers is NULL");
-    if (m > 0 && ncols > 0 && !y) return fail(NNC_EINVAL, "nnc_cbpk_grouped: y is NULL");
-    if (m > 0 && ncols > 0 && kdim > 0 && !x) return fail(NNC_EINVAL, "nnc_cbpk_grouped: x is NULL");
-    const int xb = x_dtype == NNC_DT_F32 ? 4 : 2, yb = y_dtype == NNC_DT_F32 ? 4 : 2;
-    if (reinterpret_cast<uintptr_t>(x) % xb || reinterpret_cast<uintptr_t>(y) % yb)
-        return fail(NNC_EINVAL, "nnc_cbpk_grouped: x or y is not aligned to its element size");
+    if ((rc = cb_check_operands("nnc_cbpk_grouped", x, x_dtype, y, y_dtype, centers_dev, m, kdim, ncols, !x, "x")) != NNC_OK) return rc;
     const int64_t need = nnc_cbpk_grouped_workspace_bytes(x_dtype, m, kdim, ncols, bits);
     if ((rc = cb_check_workspace("nnc_cbpk_grouped", "nnc_cbpk_grouped_workspace_bytes", workspace, workspace_bytes, need)) != NNC_OK) return rc;
     if (m == 0 || ncols == 0) return NNC_OK;
@@ -510,7 +414,7 @@ extern "C" int nnc_cbpk_grouped(const void *x, int x_dtype, int64_t m, int64_t k
     const PkPlan p = pkg_plan(x_dtype, m, kdim, ncols, bits, cu_count()).p;
     if (p.path == NNC_CBMM_BIAS) return cbmm_reduce_dt(nullptr, 0, mn, ncols, bias_dev, relu, y, y_dtype, s);   // kdim = 0: y = bias
     if ((rc = have_kernel(p, x_dtype, bits)) != NNC_OK) return rc;
-    const int direct = p.splits == 1 ? (y_dtype == NNC_DT_F32 ? 1 : 2) : 0;
+    const int direct = cb_direct(p.splits, y_dtype);
     void *out = direct ? y : workspace;
     const unsigned char *pk = reinterpret_cast<const unsigned char *>(packed);
     const long long row_bytes = pk_row_bytes(ncols, bits);
@@ -531,11 +435,9 @@ extern "C" int nnc_cbpk_grouped(const void *x, int x_dtype, int64_t m, int64_t k
         LAUNCHCHK("k_cbpk_tiled_grouped");
     } else {
         const dim3 grid((unsigned)(p.col_tiles * p.row_tiles), (unsigned)p.splits);
-        const bool xvec = reinterpret_cast<uintptr_t>(x) % 16 == 0 && kdim % 8 == 0;
         auto fn = x_dtype == NNC_DT_BF16 ? (bits == 4 ? launch_mfma<bf16_t, 4> : launch_mfma<bf16_t, 2>) : (bits == 4 ? launch_mfma<f16_t, 4> : launch_mfma<f16_t, 2>);
-        fn(xvec, grid, (size_t)p.lds, s, x, m, kdim, pk, row_bytes, ncols, centers_dev, k, p.col_tiles, p.rows_per_split, group_rows, bias_dev, relu, direct, out);
+        fn(grid, (size_t)p.lds, s, x, m, kdim, pk, row_bytes, ncols, centers_dev, k, p.col_tiles, p.rows_per_split, group_rows, bias_dev, relu, direct, out);
         LAUNCHCHK("k_cbpk_mfma_grouped");
     }
-    if (!direct) return cbmm_reduce_dt(reinterpret_cast<const float *>(workspace), p.splits, mn, ncols, bias_dev, relu, y, y_dtype, s);
-    return NNC_OK;
+    return cb_finish(direct, workspace, p.splits, mn, ncols, bias_dev, relu, y, y_dtype, s);
 }

@@ -190,6 +190,37 @@ def test_case(env, case_data, ci, dtype):
         assert torch.equal(ybits, _call(env, xf_t, dtype, m, kdim, pk_t, bits, ncols, cf_t, k, rows, bf_t, False, half_out)[1])
 
 
+# ------------------------------------------------------------------ the MFMA tile: the packed and the byte form share it
+@pytest.mark.parametrize("dtype", ["bf16", "fp16"])
+def test_mfma_tile_gives_the_byte_forms_bits_on_float_data(env, case_data, dtype):
+    """Half x at m > 16: nnc_cbpk_grouped and nnc_cbmm_grouped take the same grid (cb_grid), the same rounded table values and the
+    same 128 x 128 MFMA tile (csrc/nnc_cbmfma.hpp), so on float data (grouped_ref.float_data) too, not only on exact data,
+    ops.grouped_packed_codebook_matmul on the packed labels gives the bits of ops.grouped_codebook_matmul on the unpacked ones:
+    every case whose plan here is the MFMA tile, half and float32 output, with and without ReLU."""
+    _, ops, cus = env
+    tdt = _tdt(dtype)
+    ran = set()
+    for c, d in zip(CASES, case_data):
+        m, kdim, ncols, k, rows = c["m"], c["kdim"], c["ncols"], c["k"], c["group_rows"]
+        p = _plan(env, c, dtype)
+        if p["path"] != gp.PATH_MFMA:
+            continue
+        pb = ops.cbmm_grouped_plan(tdt, m, kdim, ncols, k, rows, cus)
+        assert (pb["path"], pb["splits"], pb["rps"]) == (gp.PATH_MFMA, p["splits"], p["rps"]), (c, p, pb)
+        lab_t = _dev_labels(d["lab"])
+        codes = ops.pack_codes(lab_t, kdim, ncols, k)
+        x_t, cen_t = _dev(_round(d["xf"], dtype), tdt, c["x_view"]), _dev(d["cf"], torch.float32)
+        bias_t = None if d["bf"] is None else _dev(d["bf"], torch.float32, c["bias_view"])
+        for out_dtype in (None, torch.float32):
+            for relu in (False, True):
+                got = ops.grouped_packed_codebook_matmul(x_t, codes, cen_t, rows, bias=bias_t, relu=relu, out_dtype=out_dtype)
+                want = ops.grouped_codebook_matmul(x_t, lab_t, cen_t, kdim, ncols, rows, bias=bias_t, relu=relu, out_dtype=out_dtype)
+                assert got.dtype == want.dtype == (tdt if out_dtype is None else torch.float32) and got.shape == want.shape == (m, ncols)
+                assert torch.equal(got.reshape(-1).view(torch.int16), want.reshape(-1).view(torch.int16)), (c, dtype, out_dtype, relu)
+        ran.add((c["bits"], "split" if p["splits"] > 1 else "direct"))
+    assert ran == {(2, "direct"), (2, "split"), (4, "direct"), (4, "split")}, sorted(ran)
+
+
 # ------------------------------------------------------------------ one group is the ungrouped packed call
 def test_one_group_equals_packed_codebook_matmul(env):
     """group_rows >= kdim, float32, on every case of packed_ref.PACKED_REGIME_CASES, float data, bias, ReLU, x and bias as views:
