@@ -715,6 +715,10 @@ int nnc_cbmm_dc_plan(int64_t m, int64_t kdim, int64_t ncols, int label_bytes, in
 int nnc_cbmm_dc_f32(const float *x, const float *g, int64_t m, int64_t kdim, const void *labels, int label_bytes, int64_t ncols, int32_t k, void *dc,
                     int32_t out_f64, void *workspace, int64_t workspace_bytes, void *stream);
 
+/* The backward pass of nnc_cbmm_grouped from the same codebooks and indices (csrc/nnc_cbgrad_grouped.hip):
+ * the dx / dc entry points of the group-wise layer, their workspace queries and plans.  A header of its own, part of this ABI. */
+#include "nnc_cbgrad_grouped.h"
+
 /* ------------------------------------------------------------------------------------
  * The pruned quantized layer run from a bitmap-sparse form of its indices (csrc/nnc_cbsp.hip).  The
  * (kdim, ncols) index matrix, row-major as nnc_cbmm_f32 reads it, and a skipped symbol z (by default the most frequent index)

@@ -39,6 +39,10 @@ CBDX_PLAN_LEN = 12
 CBDX_PLAN_FIELDS = ("path", "vb", "mt", "copies", "entries", "splits", "cps", "aligned", "lds", "col_tiles", "row_tiles", "workspace")
 CBDC_PLAN_LEN = 12
 CBDC_PLAN_FIELDS = ("path", "vb", "mt", "copies", "splits", "rps", "aligned", "lds", "col_tiles", "row_tiles", "terms_log2", "workspace")
+CBGRAD_GROUPED_PLAN_LEN = 16   # nnc_cbmm_grouped_dx_plan / nnc_cbmm_grouped_dc_plan: the ungrouped fields, then the groups
+_CBGRAD_GROUPED_TAIL = ("group_rows", "groups", "rows_per_group", "max_groups_per_workgroup")
+CBDX_GROUPED_PLAN_FIELDS = CBDX_PLAN_FIELDS + _CBGRAD_GROUPED_TAIL
+CBDC_GROUPED_PLAN_FIELDS = CBDC_PLAN_FIELDS + _CBGRAD_GROUPED_TAIL
 CBSP_ROWSUM_NONE, CBSP_ROWSUM_FUSED, CBSP_ROWSUM_PASS = 0, 1, 2   # nnc_cbsp_plan: how the row sums of x are formed (include/nnc.h)
 CBSP_PLAN_LEN = 11
 CBSP_PLAN_FIELDS = ("path", "mt", "copies", "entries", "splits", "rps", "rowsum", "lds", "col_tiles", "row_tiles", "workspace")
@@ -256,6 +260,17 @@ SIGNATURES = {
     "nnc_huffman_lengths": (c_int, [ctypes.POINTER(c_i64), c_i32, ctypes.POINTER(ctypes.c_uint8), ctypes.POINTER(c_i64), ctypes.POINTER(c_i64)]),
 }
 
+# name -> (restype, argtypes); every symbol include/nnc_cbgrad_grouped.h declares (the part of the ABI nnc.h includes from a header
+# of its own: the backward pass of the group-wise layer).  Required and bound by load() as SIGNATURES are.
+GROUPED_GRAD_SIGNATURES = {
+    "nnc_cbmm_grouped_dx_workspace_bytes": (c_i64, [c_i64, c_i64, c_i64]),
+    "nnc_cbmm_grouped_dx_plan": (c_int, [c_i64, c_i64, c_i64, c_i32, c_i64, c_i32, ctypes.c_uint64, ctypes.POINTER(c_i64)]),
+    "nnc_cbmm_grouped_dx_f32": (c_int, [c_void_p, c_i64, c_i64, c_void_p, c_i64, c_void_p, c_i32, c_i64, c_void_p, c_void_p, c_i64, c_void_p]),
+    "nnc_cbmm_grouped_dc_workspace_bytes": (c_i64, [c_i64, c_i64, c_i64, c_i32, c_i64]),
+    "nnc_cbmm_grouped_dc_plan": (c_int, [c_i64, c_i64, c_i64, c_i32, c_i64, c_i32, ctypes.c_uint64, ctypes.POINTER(c_i64)]),
+    "nnc_cbmm_grouped_dc_f32": (c_int, [c_void_p, c_void_p, c_i64, c_i64, c_void_p, c_i64, c_i32, c_i64, c_void_p, c_i32, c_void_p, c_i64, c_void_p]),
+}
+
 # exported only by the diagnostics build (NNC_DIAG=1: libnnc_hip_diag.so, see build.py); bound when present
 DIAG_SIGNATURES = {
     "nnc_debug_set_ablation": (c_int, [c_int]),
@@ -288,7 +303,7 @@ def load():
         L = ctypes.CDLL(path)
     except OSError as e:  # pragma: no cover - depends on the machine
         raise NativeLibraryError(f"cannot load {path}: {e}; there is no CPU fallback") from e
-    for name, (res, args) in SIGNATURES.items():
+    for name, (res, args) in list(SIGNATURES.items()) + list(GROUPED_GRAD_SIGNATURES.items()):
         try:
             fn = getattr(L, name)
         except AttributeError as e:

@@ -219,6 +219,28 @@ class Trainer(ABC):
         from .. import compressed
 
         net = compressed.compress_network_trainable(self.neural_network, models, sparse=sparse, packed=packed)
+        return self._tune_centres(net, models, train_dataset, test_dataset, epochs, learning_rate)
+
+    def fine_tune_grouped(self, train_dataset: LeNetDataset, test_dataset: LeNetDataset, epochs: int, learning_rate: float = 1e-3) -> List[float]:
+        """fine_tune_compressed's loop on ``compressed.compress_network_trainable_grouped``: the Dense layers quantized with
+        ``group_rows`` train their (G, K) centres through ops.grouped_codebook_linear (neither W nor dW is
+        built), every other quantized tensor trains as in fine_tune_compressed(sparse=False, packed=False).  At the end a
+        GroupedModel's ``cluster_centers_`` gets the tuned (G, K), each of its ``models[q].cluster_centers_`` the first entries that
+        are that group's own (not the zero padding of a shorter codebook), and the float kernel is re-decoded group by group, so
+        compressed_network(), store_report and load_network see the tuned centres.  Returns the accuracy per epoch."""
+        models = getattr(self, "quantized_models_by_layer", None)
+        if not models:
+            raise RuntimeError("fine_tune_grouped needs a quantized network: call quantize first")
+        from .. import compressed
+
+        net = compressed.compress_network_trainable_grouped(self.neural_network, models)
+        return self._tune_centres(net, models, train_dataset, test_dataset, epochs, learning_rate)
+
+    def _tune_centres(self, net, models, train_dataset, test_dataset, epochs, learning_rate) -> List[float]:
+        """The loop of fine_tune_compressed / fine_tune_grouped on the trainable network ``net`` of this trainer's quantized
+        network: plain steps on the centres, then the tuned centres into ``models`` and the float layers re-decoded from them."""
+        from .. import compressed
+
         for p in net.parameters():
             p.requires_grad_(False)
         tuned = {}   # layer name -> trainable layer
@@ -254,6 +276,15 @@ class Trainer(ABC):
                     if c is None or ti >= len(ms) or ms[ti] is None:
                         continue
                     c = c.detach().contiguous()
+                    if hasattr(ms[ti], "group_rows"):   # group-wise codebooks: (G, K) back, each group's own entries into its model
+                        ms[ti].cluster_centers_ = c.cpu().numpy()
+                        parts = []
+                        for q, gm in enumerate(ms[ti].models):
+                            size = int(gm.cluster_centers_.size)
+                            gm.cluster_centers_ = ms[ti].cluster_centers_[q, :size].reshape(-1, 1).copy()
+                            parts.append(ops.gather(c[q].contiguous(), gm.labels_compact_))
+                        tensors[ti] = torch.cat(parts).view(tensors[ti].shape)
+                        continue
                     ms[ti].cluster_centers_ = c.cpu().numpy().reshape(-1, 1)
                     tensors[ti] = ops.gather(c, ms[ti].labels_compact_).view(tensors[ti].shape)
                 layer.set_weights(tensors)

@@ -62,6 +62,14 @@ the centroid gradient again the byte layer's bit for bit, and no byte-per-weight
 compress_network_trainable(..., packed=True | "auto") and Trainer.fine_tune_compressed(..., packed=...) give them, chosen per
 layer by the rule above applied to the trainable forms.
 
+A grouped Dense layer trains too (``TrainableGroupedCompressedDense``): ops.grouped_codebook_linear's
+backward forms dx and the (G, K) centroid gradient from the codebooks and the byte indices (csrc/nnc_cbgrad_grouped.hip).  The
+options above keep refusing grouped layers; the way in is
+
+    compress_network_trainable_grouped(network, models_by_layer)   the byte trainable layers, grouped Dense layers included
+
+and Trainer.fine_tune_grouped trains it.  The packed and the bitmap-sparse grouped forms and grouped Conv2D do not train.
+
 How the classes are laid out: ``_Activated`` (the activation behind the product, ``get_weights``) is the root of
 ``_InferenceLayer`` (the float32 ``centers`` / ``bias`` buffers behind the family's index buffer, ``nbytes``) and of
 ``_TrainableCentres`` (the ``centers`` parameter, ``counts``, the three kinds of bias).  A family -- ``_CodebookLayer``,
@@ -335,9 +343,11 @@ class _TrainableCentres(_Activated):
     kernel_sq_sum) a buffer, and the bias: a quantized one (bias_labels buffer + bias_centers parameter), a frozen raw one (bias
     buffer) or None."""
 
-    def _init_centres(self, labels: torch.Tensor, centers: torch.Tensor, ncols: int, bias, bias_codes, activation):
-        self.centers = nn.Parameter(centers.detach().reshape(-1).to(torch.float32).clone())
-        self.register_buffer("counts", ops.bincount(labels, self.centers.numel()))
+    def _init_centres(self, labels: torch.Tensor, centers: torch.Tensor, ncols: int, bias, bias_codes, activation, counts=None):
+        """``counts`` given (the grouped layer: a histogram per group): the centres keep their shape, which is that of counts."""
+        flat = centers.detach().to(torch.float32)
+        self.centers = nn.Parameter((flat.reshape(-1) if counts is None else flat).clone())
+        self.register_buffer("counts", ops.bincount(labels, self.centers.numel()) if counts is None else counts)
         if bias_codes is not None:
             bcenters, blabels = bias_codes
             if blabels.numel() != ncols:
@@ -396,6 +406,55 @@ class TrainableCompressedConv2D(_Conv2DHalf, _TrainableCodebookLayer):
                  bias_codes=None, activation=None):
         super().__init__(kernel_size * kernel_size * cin, cout, labels_unfold, centers, bias, bias_codes, activation)
         self._set_conv(kernel_size, cin, pad)
+
+
+class TrainableGroupedCompressedDense(_DenseHalf, _TrainableCentres):
+    """GroupedCompressedDense with trainable centres (ops.grouped_codebook_linear): labels (kdim * ncols uint8
+    indices, row-major) a buffer, centers a float32 (G, K) nn.Parameter, counts the (G, K) histogram of every group's indices, so
+    kernel_sq_sum() = sum counts * centers^2; the bias of _TrainableCentres.  The backward forms dx and the (G, K) centroid
+    gradient from the codebooks and the indices (csrc/nnc_cbgrad_grouped.hip): W and dW are never built.  float32 inputs only."""
+
+    def __init__(self, kdim: int, ncols: int, group_rows: int, labels: torch.Tensor, centers: torch.Tensor, bias: torch.Tensor | None = None,
+                 bias_codes=None, activation=None):
+        super().__init__()
+        if labels.numel() != kdim * ncols:
+            raise ValueError(f"{labels.numel()} indices for a {kdim} x {ncols} weight matrix")
+        if labels.dtype != torch.uint8:
+            raise TypeError(f"group-wise codebooks take uint8 indices, got {labels.dtype}")
+        groups = max(1, -(-int(kdim) // int(group_rows)))
+        if centers.dim() != 2 or centers.shape[0] != groups:
+            raise ValueError(f"centers must have shape ({groups}, K) for {kdim} rows in groups of {group_rows}, got {tuple(centers.shape)}")
+        self.kdim, self.ncols, self.group_rows = int(kdim), int(ncols), int(group_rows)
+        self.register_buffer("labels", labels.reshape(-1))
+        per = self.group_rows * self.ncols   # a group's indices lie one after the other
+        counts = torch.stack([ops.bincount(self.labels[q * per: (q + 1) * per], centers.shape[1]) for q in range(groups)])
+        self._init_centres(self.labels, centers, ncols, bias, bias_codes, activation, counts=counts)
+
+    @classmethod
+    def from_dense(cls, dense, grouped_model, bias_model=None) -> "TrainableGroupedCompressedDense":
+        """From a Dense layer and the GroupedModel of its kernel; a quantized bias keeps its codes, a raw one stays frozen."""
+        _require_model(grouped_model)
+        kin, kout = dense.kernel.shape
+        dev = dense.kernel.device
+        centers = torch.from_numpy(np.ascontiguousarray(grouped_model.cluster_centers_, dtype=np.float32)).to(dev)
+        bias, bias_codes = (None, _codes(bias_model, dev)) if bias_model is not None else (dense.bias, None)
+        return cls(kin, kout, grouped_model.group_rows, grouped_model.labels_compact_, centers, bias, bias_codes, dense.activation)
+
+    @classmethod
+    def from_codes(cls, kdim, ncols, group_rows, labels, centers, bias=None, bias_codes=None, activation=None) -> "TrainableGroupedCompressedDense":
+        return cls(kdim, ncols, group_rows, labels, centers, bias, bias_codes, activation)
+
+    @classmethod
+    def from_grouped(cls, layer: GroupedCompressedDense) -> "TrainableGroupedCompressedDense":
+        """The trainable layer of a GroupedCompressedDense: the same indices and centres, its decoded bias frozen."""
+        return cls(layer.kdim, layer.ncols, layer.group_rows, layer.labels, layer.centers, layer.bias, None, layer.activation)
+
+    def _matmul(self, x: torch.Tensor) -> torch.Tensor:
+        return self._activate(ops.grouped_codebook_linear(x, self.labels, self.centers, self.kdim, self.ncols, self.group_rows,
+                                                          bias=self.current_bias(), relu=self._fused_relu))
+
+    def nbytes(self) -> int:
+        return self._nbytes(self.labels)
 
 
 def _trainable(layer, weight_model, bias_model, dense_cls=None, conv_cls=None):
@@ -830,10 +889,18 @@ def compress_network_trainable(network: nn.Module, models_by_layer, sparse=False
     return _compress_each(network, models_by_layer, make, grouped="trainable=True")
 
 
-def _compress_each(network: nn.Module, models_by_layer, make, grouped=None) -> nn.Module:
+def compress_network_trainable_grouped(network: nn.Module, models_by_layer) -> nn.Module:
+    """compress_network_trainable(network, models_by_layer) -- the byte forms -- in which every layer whose kernel model is a
+    utility.GroupedModel becomes a TrainableGroupedCompressedDense instead of raising.  On a network
+    without grouped layers it returns what compress_network_trainable returns.  Trainer.fine_tune_grouped trains it."""
+    return _compress_each(network, models_by_layer, lambda layer, wm, bm: _trainable(layer, wm, bm),
+                          make_grouped=TrainableGroupedCompressedDense.from_dense)
+
+
+def _compress_each(network: nn.Module, models_by_layer, make, grouped=None, make_grouped=GroupedCompressedDense.from_dense) -> nn.Module:
     """A deep copy of ``network`` with every quantized layer replaced by make(layer, kernel model, bias model).  A layer fitted
-    with group-wise codebooks becomes a GroupedCompressedDense; ``grouped`` names the option that has no grouped form (None: the
-    plain byte form was asked for) and then raises NotImplementedError with the layer's name, before anything is built."""
+    with group-wise codebooks becomes make_grouped(...), a GroupedCompressedDense; ``grouped`` names the option that has no grouped
+    form (None: there is one) and then raises NotImplementedError with the layer's name, before anything is built."""
     todo = []
     for name, layer in network.get_config().items():
         models = models_by_layer.get(layer)
@@ -844,7 +911,7 @@ def _compress_each(network: nn.Module, models_by_layer, make, grouped=None) -> n
         todo.append((name, layer, models[0], models[1] if len(models) > 1 else None))
     out = copy.deepcopy(network)
     for name, layer, wm, bm in todo:
-        setattr(out, name, GroupedCompressedDense.from_dense(layer, wm, bm) if _is_grouped(wm) else make(layer, wm, bm))
+        setattr(out, name, make_grouped(layer, wm, bm) if _is_grouped(wm) else make(layer, wm, bm))
     return out
 
 

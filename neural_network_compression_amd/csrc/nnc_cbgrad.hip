@@ -22,106 +22,8 @@
 //   from k_cbgrad_absmax on the device, the dc kernel derives S itself and writes it next to the sums, and k_cbdc_finish writes
 //   dc = ldexp(sum, -S).  No host read anywhere.
 // An index >= K reads 0 in dx and falls into no bin in dc, as in the forward pass.  No float atomics.
+// The plans (CgPlan, dx_plan, dc_plan) and cg_check are in nnc_cbgrad.hpp, where nnc_cbgrad_grouped.hip finds them too.
 #include "nnc_cbtile.hpp"
-
-// ------------------------------------------------------------------ plans (host)
-struct CgPlan {
-    int path;                 // NNC_CBMM_NONE / _STREAM / _TILED / _ZERO
-    int vb, mt;               // stream: bytes per lane per row, rows of m per launch (a power of two >= m)
-    int entries, cshift;      // dx stream: the LDS codebook (entries x (1 << cshift) copies); tiled: k + 1 entries
-    int rlog2;                // dc: 1 << rlog2 copies of every LDS bin
-    int aligned;
-    long long col_tiles, row_tiles;   // stream: column blocks x row groups; tiled: tiles
-    long long splits, per_split;      // dx: splits of ncols (columns per split); dc: splits of m (rows of m per split)
-    long long rows_per_group;         // stream: label rows per workgroup
-    int terms_log2;                   // dc: ceil(log2(kdim * ncols * splits))
-    long long lds;
-};
-
-static int ceil_log2(long long v)
-{
-    int l = 0;
-    while (l < 62 && (1LL << l) < v) ++l;
-    return l;
-}
-
-// the stream geometry both directions share: a column block of 64 lanes x E labels, row groups for two workgroups per CU
-static void cg_stream_grid(CgPlan &p, long long m, long long kdim, long long ncols, int lb, int cus, uintptr_t labels)
-{
-    cus = std::max(1, std::min(cus, CB_PLAN_CUS));
-    p.path = NNC_CBMM_STREAM;
-    p.mt = cb_mt(m);
-    p.vb = std::min(16, (64 / p.mt) * lb);
-    p.col_tiles = cdiv(ncols, 64LL * (p.vb / lb));
-    const long long groups = std::max(1LL, std::min(cdiv(2LL * cus, p.col_tiles), cdiv(kdim, (long long)CB_WAVES * CB_UNROLL)));
-    p.rows_per_group = cdiv(kdim, groups);
-    p.row_tiles = cdiv(kdim, p.rows_per_group);
-    p.aligned = labels % p.vb == 0 && (ncols * lb) % p.vb == 0;
-}
-
-static CgPlan dx_plan(long long m, long long kdim, long long ncols, int lb, int k, int cus, uintptr_t labels)
-{
-    CgPlan p{};
-    if (m == 0 || kdim == 0) return p;                       // NNC_CBMM_NONE: dx is empty
-    if (ncols == 0) {                                        // dx = 0
-        p.path = NNC_CBMM_ZERO;
-        return p;
-    }
-    if (m <= CB_SKINNY_M) {
-        cg_stream_grid(p, m, kdim, ncols, lb, cus, labels);
-        p.splits = p.col_tiles;                              // one split per column block
-        p.per_split = 64LL * (p.vb / lb);
-        if (lb == 1) {
-            p.entries = 256;
-            p.cshift = __builtin_ctz(CB_U8_COPIES);
-        } else {
-            p.entries = k + 1;
-            while ((1 << p.cshift) < CB_U8_COPIES && (long long)p.entries << (p.cshift + 1) <= CB_U16_WORDS) ++p.cshift;
-        }
-        p.lds = ((long long)p.entries << p.cshift) * 4 + (long long)p.entries * 4;
-    } else {
-        p.path = NNC_CBMM_TILED;
-        p.col_tiles = cdiv(kdim, TB_N);
-        p.row_tiles = cdiv(m, TB_M);
-        long long s = std::min({cdiv(2LL * CB_PLAN_CUS, p.col_tiles * p.row_tiles), ncols / (16 * TB_K), 16LL});
-        s = std::max(1LL, s);
-        p.per_split = cdiv(ncols, s);
-        p.splits = cdiv(ncols, p.per_split);
-        p.entries = k + 1;
-        p.lds = (long long)(TB_K * TB_M + TB_K * TB_N + k + 1) * 4;
-    }
-    return p;
-}
-
-static int dc_rlog2(int k) { return k <= 64 ? 5 : (k <= 256 ? 3 : 1); }   // as k_centroid_grad: K x copies x 8 B <= 16.3 KiB
-
-static CgPlan dc_plan(long long m, long long kdim, long long ncols, int lb, int k, int cus, uintptr_t labels)
-{
-    CgPlan p{};
-    if (m == 0 || kdim == 0 || ncols == 0) {                 // no terms: dc = 0
-        p.path = NNC_CBMM_ZERO;
-        return p;
-    }
-    p.rlog2 = dc_rlog2(k);
-    const long long bins = ((long long)k << p.rlog2) * 8;
-    if (m <= CB_SKINNY_M) {
-        cg_stream_grid(p, m, kdim, ncols, lb, cus, labels);
-        p.splits = 1;
-        p.per_split = m;
-        p.lds = bins;
-    } else {
-        p.path = NNC_CBMM_TILED;
-        p.col_tiles = cdiv(ncols, TB_N);
-        p.row_tiles = cdiv(kdim, TB_M);
-        long long s = std::min({cdiv(2LL * CB_PLAN_CUS, p.col_tiles * p.row_tiles), m / (16 * TB_K), 16LL});
-        s = std::max(1LL, s);
-        p.per_split = cdiv(m, s);
-        p.splits = cdiv(m, p.per_split);
-        p.lds = (long long)(TB_K * TB_M + TB_K * TB_N) * 4 + bins;
-    }
-    p.terms_log2 = ceil_log2(kdim * ncols * p.splits);
-    return p;
-}
 
 // ------------------------------------------------------------------ max |x|, max |g|
 // amax[0] = bits of max |x|, amax[1] = bits of max |g| (zeroed by the caller).  |v| as a bit pattern orders as the value; a NaN
@@ -463,19 +365,6 @@ int cbdc_finish(const uint32_t *hdr, const long long *sums, int k, int f64, void
 }
 
 // ------------------------------------------------------------------ C ABI
-static int cg_check(const char *fn, int64_t m, int64_t kdim, int64_t ncols, int label_bytes, int32_t k)
-{
-    const std::string f(fn);
-    if (m < 0 || kdim < 0 || ncols < 0) return fail(NNC_EINVAL, f + ": negative size");
-    if (label_bytes != 1 && label_bytes != 2) return fail(NNC_EINVAL, f + ": label_bytes must be 1 or 2");
-    if (k < 1 || k > NNC_KMAX) return fail(NNC_EINVAL, f + ": k outside 1..NNC_KMAX");
-    if (label_bytes == 1 && k > 256) return fail(NNC_EINVAL, f + ": k > 256 needs 2-byte labels");
-    if (m > (1LL << 40) || kdim > (1LL << 40) || ncols > (1LL << 40)) return fail(NNC_EINVAL, f + ": size too large");
-    if (m > 0 && kdim > 0 && ncols > 0 && (kdim > (1LL << 62) / ncols || kdim * ncols > (1LL << 62) / (16 * TB_K)))
-        return fail(NNC_EINVAL, f + ": kdim * ncols too large");
-    return NNC_OK;
-}
-
 template <typename LT, int VB, int MT>
 static void launch_dx_stream(bool aligned, dim3 grid, size_t lds, hipStream_t s, const float *g, int m, long long kdim, const void *labels, long long ncols,
                              const float *centers, int k, int entries, int cshift, long long rpg, int direct, float *out)

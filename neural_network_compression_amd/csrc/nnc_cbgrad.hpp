@@ -1,7 +1,8 @@
 // nnc_cbgrad.hpp -- what the backward pass of the codebook matmul (nnc_cbgrad.hip) shares with those of its bitmap-sparse and
 // packed siblings (nnc_cbspgrad.hip, nnc_cbpkgrad.hip): the fixed-order wave reduction of the dx stream kernels, the scaling and fixed-point binning of dc (DESIGN.md
 // section 12), the workspace sizes and the launches of the kernels both use (defined in nnc_cbgrad.hip).  The tiled kernels' shared
-// text is in nnc_cbtile.hpp.
+// text is in nnc_cbtile.hpp.  The host plans of the byte form (CgPlan, dx_plan, dc_plan) and its argument checks (cg_check) are here
+// too: the group-wise backward pass (nnc_cbgrad_grouped.hip) follows the same plans.
 #pragma once
 #include "nnc_cbmm.hpp"
 
@@ -100,6 +101,119 @@ __device__ __forceinline__ void cbdc_flush(const unsigned long long *bins, int k
         for (int r = 0; r < R; ++r) s += bins[(j << rlog2) + r];
         if (s) atomicAdd(&sums[j], s);
     }
+}
+
+// ------------------------------------------------------------------ plans (host)
+struct CgPlan {
+    int path;                 // NNC_CBMM_NONE / _STREAM / _TILED / _ZERO
+    int vb, mt;               // stream: bytes per lane per row, rows of m per launch (a power of two >= m)
+    int entries, cshift;      // dx stream: the LDS codebook (entries x (1 << cshift) copies); tiled: k + 1 entries
+    int rlog2;                // dc: 1 << rlog2 copies of every LDS bin
+    int aligned;
+    long long col_tiles, row_tiles;   // stream: column blocks x row groups; tiled: tiles
+    long long splits, per_split;      // dx: splits of ncols (columns per split); dc: splits of m (rows of m per split)
+    long long rows_per_group;         // stream: label rows per workgroup
+    int terms_log2;                   // dc: ceil(log2(kdim * ncols * splits))
+    long long lds;
+};
+
+static int ceil_log2(long long v)
+{
+    int l = 0;
+    while (l < 62 && (1LL << l) < v) ++l;
+    return l;
+}
+
+// the stream geometry both directions share: a column block of 64 lanes x E labels, row groups for two workgroups per CU
+static void cg_stream_grid(CgPlan &p, long long m, long long kdim, long long ncols, int lb, int cus, uintptr_t labels)
+{
+    cus = std::max(1, std::min(cus, CB_PLAN_CUS));
+    p.path = NNC_CBMM_STREAM;
+    p.mt = cb_mt(m);
+    p.vb = std::min(16, (64 / p.mt) * lb);
+    p.col_tiles = cdiv(ncols, 64LL * (p.vb / lb));
+    const long long groups = std::max(1LL, std::min(cdiv(2LL * cus, p.col_tiles), cdiv(kdim, (long long)CB_WAVES * CB_UNROLL)));
+    p.rows_per_group = cdiv(kdim, groups);
+    p.row_tiles = cdiv(kdim, p.rows_per_group);
+    p.aligned = labels % p.vb == 0 && (ncols * lb) % p.vb == 0;
+}
+
+static CgPlan dx_plan(long long m, long long kdim, long long ncols, int lb, int k, int cus, uintptr_t labels)
+{
+    CgPlan p{};
+    if (m == 0 || kdim == 0) return p;                       // NNC_CBMM_NONE: dx is empty
+    if (ncols == 0) {                                        // dx = 0
+        p.path = NNC_CBMM_ZERO;
+        return p;
+    }
+    if (m <= CB_SKINNY_M) {
+        cg_stream_grid(p, m, kdim, ncols, lb, cus, labels);
+        p.splits = p.col_tiles;                              // one split per column block
+        p.per_split = 64LL * (p.vb / lb);
+        if (lb == 1) {
+            p.entries = 256;
+            p.cshift = __builtin_ctz(CB_U8_COPIES);
+        } else {
+            p.entries = k + 1;
+            while ((1 << p.cshift) < CB_U8_COPIES && (long long)p.entries << (p.cshift + 1) <= CB_U16_WORDS) ++p.cshift;
+        }
+        p.lds = ((long long)p.entries << p.cshift) * 4 + (long long)p.entries * 4;
+    } else {
+        p.path = NNC_CBMM_TILED;
+        p.col_tiles = cdiv(kdim, TB_N);
+        p.row_tiles = cdiv(m, TB_M);
+        long long s = std::min({cdiv(2LL * CB_PLAN_CUS, p.col_tiles * p.row_tiles), ncols / (16 * TB_K), 16LL});
+        s = std::max(1LL, s);
+        p.per_split = cdiv(ncols, s);
+        p.splits = cdiv(ncols, p.per_split);
+        p.entries = k + 1;
+        p.lds = (long long)(TB_K * TB_M + TB_K * TB_N + k + 1) * 4;
+    }
+    return p;
+}
+
+static int dc_rlog2(int k) { return k <= 64 ? 5 : (k <= 256 ? 3 : 1); }   // as k_centroid_grad: K x copies x 8 B <= 16.3 KiB
+
+static CgPlan dc_plan(long long m, long long kdim, long long ncols, int lb, int k, int cus, uintptr_t labels)
+{
+    CgPlan p{};
+    if (m == 0 || kdim == 0 || ncols == 0) {                 // no terms: dc = 0
+        p.path = NNC_CBMM_ZERO;
+        return p;
+    }
+    p.rlog2 = dc_rlog2(k);
+    const long long bins = ((long long)k << p.rlog2) * 8;
+    if (m <= CB_SKINNY_M) {
+        cg_stream_grid(p, m, kdim, ncols, lb, cus, labels);
+        p.splits = 1;
+        p.per_split = m;
+        p.lds = bins;
+    } else {
+        p.path = NNC_CBMM_TILED;
+        p.col_tiles = cdiv(ncols, TB_N);
+        p.row_tiles = cdiv(kdim, TB_M);
+        long long s = std::min({cdiv(2LL * CB_PLAN_CUS, p.col_tiles * p.row_tiles), m / (16 * TB_K), 16LL});
+        s = std::max(1LL, s);
+        p.per_split = cdiv(m, s);
+        p.splits = cdiv(m, p.per_split);
+        p.lds = (long long)(TB_K * TB_M + TB_K * TB_N) * 4 + bins;
+    }
+    p.terms_log2 = ceil_log2(kdim * ncols * p.splits);
+    return p;
+}
+
+// the argument checks of the byte form's backward entry points (NNC_EINVAL, or NNC_OK)
+static int cg_check(const char *fn, int64_t m, int64_t kdim, int64_t ncols, int label_bytes, int32_t k)
+{
+    const std::string f(fn);
+    if (m < 0 || kdim < 0 || ncols < 0) return fail(NNC_EINVAL, f + ": negative size");
+    if (label_bytes != 1 && label_bytes != 2) return fail(NNC_EINVAL, f + ": label_bytes must be 1 or 2");
+    if (k < 1 || k > NNC_KMAX) return fail(NNC_EINVAL, f + ": k outside 1..NNC_KMAX");
+    if (label_bytes == 1 && k > 256) return fail(NNC_EINVAL, f + ": k > 256 needs 2-byte labels");
+    if (m > (1LL << 40) || kdim > (1LL << 40) || ncols > (1LL << 40)) return fail(NNC_EINVAL, f + ": size too large");
+    if (m > 0 && kdim > 0 && ncols > 0 && (kdim > (1LL << 62) / ncols || kdim * ncols > (1LL << 62) / (16 * TB_K)))
+        return fail(NNC_EINVAL, f + ": kdim * ncols too large");
+    return NNC_OK;
 }
 
 // the shared kernels of nnc_cbgrad.hip, launched on `s` (NNC_OK, or the launch error):

@@ -1,0 +1,535 @@
+// nnc_cbgrad_grouped.hip -- the backward pass of the group-wise codebook matmul (nnc_cbmm_grouped.hip) from the codebooks and the
+// indices, W never decoded (include/nnc.h, nnc_cbmm_grouped_dx_f32 / nnc_cbmm_grouped_dc_f32).
+// W[i, o] = c[i / group_rows][L[i, o]], uint8 labels, y = x @ W, g = dL/dy:
+//
+//   dx[r, i]  = sum_o g[r, o] * c[i / group_rows][L[i, o]]                          a row i of dx reads one table only
+//   dc[q, k]  = sum_{(i, o): i / group_rows = q, L[i, o] = k} sum_r x[r, i] * g[r, o]   G x K bins
+//
+// The plans are the ungrouped ones (dx_plan, dc_plan of nnc_cbgrad.hpp at label_bytes 1), so the path, the grids, the splits, the
+// order in which every sum is formed and the shift S of the dc sums are those of nnc_cbmm_dx_f32 / nnc_cbmm_dc_f32 on the same
+// shape.  The kernels are the ungrouped ones (nnc_cbgrad.hip) with one addition each; they are kernels of their own for the reason
+// nnc_cbmm_grouped.hip gives (a shared body changes the instruction streams of the old instantiations).
+//   k_cbdx_stream_grouped  m <= 16.  k_cbdx_stream; the workgroup's label rows are walked group by group as k_cbmm_stream_grouped
+//                          walks a split: each stretch is divided among the four waves, the table is rewritten between two barriers.
+//   k_cbdx_tiled_grouped   m > 16.  k_cbdx_tiled; an output tile's 128 index rows lie in at most four groups, whose tables are
+//                          loaded once (they do not change along the o loop); a thread decodes one row, so it keeps one table.
+//   k_cbdc_stream_grouped  m <= 16.  k_cbdc_stream with the same walk; the LDS bins are one group's, flushed into sums + q * k and
+//                          cleared at every boundary.
+//   k_cbdc_tiled_grouped   m > 16.  k_cbdc_tiled; a wave's 32 index rows lie in one group (group_rows is a multiple of 32), so the
+//                          LDS bins are cut into one set per group of the tile with the copies divided among the sets: the LDS
+//                          and the lanes per copy of k_cbdc_tiled, one binning pass, one flush per set.
+// The integer sums are exact, so neither walk changes a bit of dc; which wave takes a row changes no bit of dx.  Everything that
+// steers a walk comes from blockIdx and the wave number (a scalar): every wave of a workgroup reaches every barrier.
+// k_cbgrad_absmax, k_cbgrad_reduce and k_cbdc_finish (over G * K bins) are nnc_cbgrad.hip's.
+#include "nnc_cbtile.hpp"
+
+// the most groups the 128 index rows of a tile lie in: tiles start on multiples of 128, group_rows is a multiple of 32
+static int tile_groups(long long group_rows) { return group_rows % 128 == 0 ? 1 : (group_rows == 32 ? 4 : 2); }
+
+// ------------------------------------------------------------------ dx, m <= 16
+// k_cbdx_stream<uint8_t> with centers[groups][k]: grid (column blocks, row groups), CB_THREADS threads, the same `out`.
+template <int VB, int MT, bool ALIGNED>
+__global__ __launch_bounds__(CB_THREADS) void k_cbdx_stream_grouped(const float *__restrict__ g, int m, long long kdim, const unsigned char *__restrict__ labels,
+                                                                    long long ncols, const float *__restrict__ centers, int k, int entries, int cshift,
+                                                                    long long rows_per_group, long long group_rows, int direct, float *__restrict__ out)
+{
+    using LT = uint8_t;
+    constexpr int LB = sizeof(LT), E = VB / LB, N = VB / 4, PER = 32 / (8 * LB);
+    extern __shared__ float smem[];
+    float *cb = smem;
+    float *stage = smem + (entries << cshift);
+    long long group = (long long)blockIdx.y * rows_per_group / group_rows;
+    cb_fill(cb, stage, centers + group * k, k, entries, cshift);
+
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const long long c0 = (long long)blockIdx.x * (64 * E) + lane * E;
+    const bool active = c0 < ncols;
+    const int ne = (int)std::max(0LL, std::min((long long)E, ncols - c0));   // the lane's columns inside the matrix
+    float gv[MT][E];
+#pragma unroll
+    for (int r = 0; r < MT; ++r)
+#pragma unroll
+        for (int e = 0; e < E; ++e) gv[r][e] = (r < m && e < ne) ? g[(long long)r * ncols + c0 + e] : 0.0f;
+
+    const long long s_lo = (long long)blockIdx.y * rows_per_group, s_hi = std::min(kdim, s_lo + rows_per_group);
+    long long g_lo = s_lo, g_hi = std::min(s_hi, (group + 1) * group_rows);   // the rows of the workgroup that lie in `group`
+    long long per_wave = (g_hi - g_lo + CB_WAVES - 1) / CB_WAVES;
+    long long i0 = std::min(g_hi, g_lo + wave * per_wave), i1 = std::min(g_hi, i0 + per_wave);
+    const uintptr_t base = reinterpret_cast<uintptr_t>(labels);
+    const long long row_bytes = ncols * LB;
+    const long long lane_off = (long long)blockIdx.x * (64 * VB) + lane * VB;
+    float *dst = direct ? out : out + (long long)blockIdx.x * m * kdim;
+    __syncthreads();
+
+    auto row_words = [&](long long i, uint32_t *w, uint32_t &s) {
+        const uintptr_t row = base + (uintptr_t)(i * row_bytes);
+        if constexpr (ALIGNED) {
+            s = 0;
+            load_chunk<VB>(reinterpret_cast<const unsigned char *>(active ? row + lane_off : row), w);
+        } else {
+            const uintptr_t first = row & ~(uintptr_t)(VB - 1);
+            s = (uint32_t)(__builtin_amdgcn_readfirstlane((uint32_t)((row + blockIdx.x * (64 * VB)) & (VB - 1))));
+            const uintptr_t a = ((row + lane_off) & ~(uintptr_t)(VB - 1));
+            const uintptr_t a0 = active ? a : first;
+            const uintptr_t a1 = (active && a + VB < row + row_bytes) ? a + VB : a0;
+            load_chunk<VB>(reinterpret_cast<const unsigned char *>(a0), w);
+            load_chunk<VB>(reinterpret_cast<const unsigned char *>(a1), w + N);
+        }
+    };
+    auto consume = [&](const uint32_t *w, uint32_t s, long long i) {
+        uint32_t o[N];
+        if constexpr (ALIGNED) {
+#pragma unroll
+            for (int d = 0; d < N; ++d) o[d] = w[d];
+        } else {
+            funnel<N>(w, s, o);
+        }
+        float p[MT];
+#pragma unroll
+        for (int r = 0; r < MT; ++r) p[r] = 0.0f;
+#pragma unroll
+        for (int e = 0; e < E; ++e) {
+            const uint32_t l = (o[e / PER] >> (8 * LB * (e % PER))) & 0xFFu;
+            const float wv = e < ne ? cb[CbTable<LT>::index(l, k, cshift, lane)] : 0.0f;   // (columns past the row: no Inf * 0)
+#pragma unroll
+            for (int r = 0; r < MT; ++r) p[r] = __builtin_fmaf(gv[r][e], wv, p[r]);
+        }
+        int row;
+        const float v = wave_reduce_rows<MT>(p, lane, row);
+        if ((lane & (64 / MT - 1)) == 0 && row < m) dst[(long long)row * kdim + i] = v;
+    };
+
+    constexpr int WN = ALIGNED ? N : 2 * N;
+    for (;;) {
+        long long i = i0;
+        for (; i + CB_UNROLL <= i1; i += CB_UNROLL) {
+            uint32_t w[CB_UNROLL][WN], s[CB_UNROLL];
+#pragma unroll
+            for (int u = 0; u < CB_UNROLL; ++u) row_words(i + u, w[u], s[u]);
+#pragma unroll
+            for (int u = 0; u < CB_UNROLL; ++u) consume(w[u], s[u], i + u);
+        }
+        for (; i < i1; ++i) {
+            uint32_t w[WN], s;
+            row_words(i, w, s);
+            consume(w, s, i);
+        }
+        if (g_hi >= s_hi) break;
+        // on to the next group's rows, divided among the waves as the whole range is
+        g_lo = g_hi;
+        g_hi = std::min(s_hi, (++group + 1) * group_rows);
+        per_wave = (g_hi - g_lo + CB_WAVES - 1) / CB_WAVES;
+        i0 = std::min(g_hi, g_lo + wave * per_wave), i1 = std::min(g_hi, i0 + per_wave);
+        __syncthreads();   // every wave has left the rows of the group before
+        cb_refill(cb, centers + group * k, k, cshift);
+        __syncthreads();
+    }
+}
+
+// ------------------------------------------------------------------ dx, m > 16
+// k_cbdx_tiled<uint8_t> with centers[groups][k]: the same grid, tile and FMA order.  LDS holds `tables` tables of k + 1 entries
+// (entry k = 0), table t that of group n0 / group_rows + t; index row n0 + lr reads the one its group has.
+__global__ __launch_bounds__(256) void k_cbdx_tiled_grouped(const float *__restrict__ g, long long m, long long kdim, const uint8_t *__restrict__ labels,
+                                                            long long ncols, const float *__restrict__ centers, int k, long long col_tiles,
+                                                            long long cols_per_split, long long group_rows, int tables, int direct, float *__restrict__ out)
+{
+    extern __shared__ float smem[];
+    float *gs = smem;                      // [TB_K][TB_M]: g[m0 + r, o]
+    float *ws = gs + TB_K * TB_M;          // [TB_K][TB_N]: W^T[o, n0 + i] = c[group of n0 + i][L[n0 + i, o]]
+    float *cb = ws + TB_K * TB_N;          // [tables][k + 1]
+
+    const TbTile T = tb_tile(col_tiles, cols_per_split, ncols);
+    const long long q0 = T.n0 / group_rows, groups = (kdim + group_rows - 1) / group_rows;
+    for (int j = threadIdx.x; j < tables * (k + 1); j += 256) {
+        const int t = j / (k + 1), e = j - t * (k + 1);
+        cb[j] = (e < k && q0 + t < groups) ? centers[(q0 + t) * k + e] : 0.0f;
+    }
+    float acc[8][8];
+    tb_clear(acc);
+
+    const int lr = threadIdx.x >> 1, lo = (threadIdx.x & 1) * 4;   // W^T tile: index row n0 + lr, o lo..lo+3 (as the g tile: row lr, o lo..lo+3)
+    const long long wi = T.n0 + lr;
+    const float *tab = cb + std::min((long long)tables - 1, wi / group_rows - q0) * (k + 1);
+    for (long long ob = T.lo; ob < T.hi; ob += TB_K) {
+        __syncthreads();
+        tb_load_rows(gs, g, m, ncols, T.m0, ob, T.hi);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const long long go = ob + lo + j;
+            ws[(lo + j) * TB_N + lr] = (wi < kdim && go < T.hi) ? tab[std::min((uint32_t)labels[wi * ncols + go], (uint32_t)k)] : 0.0f;
+        }
+        __syncthreads();
+        tb_tile_fma(gs, ws, T.tx, T.ty, acc);
+    }
+#pragma unroll
+    for (int a = 0; a < 8; ++a)
+#pragma unroll
+        for (int b = 0; b < 8; ++b) tb_store_dx(acc[a][b], T.m0 + T.ty * 8 + a, T.n0 + T.tx * 8 + b, m, kdim, direct, out);
+}
+
+// ------------------------------------------------------------------ dc, m <= 16
+// k_cbdc_stream<uint8_t> with sums[groups][k]: grid (column blocks, row groups), CB_THREADS threads.  LDS: one group's bins,
+// [k][1 << rlog2] int64.  The walk is k_cbdx_stream_grouped's; at a boundary the bins go into the group's sums and are cleared by
+// the threads that have just read them, ahead of the barrier that opens the next stretch.
+template <int VB, int MT, bool ALIGNED>
+__global__ __launch_bounds__(CB_THREADS) void k_cbdc_stream_grouped(const float *__restrict__ x, const float *__restrict__ g, int m, long long kdim,
+                                                                    const unsigned char *__restrict__ labels, long long ncols, int k, int rlog2, int terms_log2,
+                                                                    long long rows_per_group, long long group_rows, uint32_t *__restrict__ hdr,
+                                                                    unsigned long long *__restrict__ sums)
+{
+    using LT = uint8_t;
+    constexpr int LB = sizeof(LT), E = VB / LB, N = VB / 4, PER = 32 / (8 * LB);
+    extern __shared__ unsigned long long bins[];
+    int flag;
+    const int S = cbdc_shift(hdr, m, terms_log2, flag);
+    if (blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0) {
+        hdr[2] = (uint32_t)S;
+        hdr[3] = (uint32_t)flag;
+    }
+    if (flag != CBG_FLAG_OK) return;   // (uniform over the launch)
+    int scx, scg;
+    cbdc_scales(hdr, scx, scg);
+    const int Sw = S - scx - scg;      // the shift of dW' = dW * 2^(scx + scg)
+    for (int j = threadIdx.x; j < (k << rlog2); j += CB_THREADS) bins[j] = 0ull;
+
+    const int lane = threadIdx.x & 63;
+    const int rep = lane & ((1 << rlog2) - 1);
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const long long c0 = (long long)blockIdx.x * (64 * E) + lane * E;
+    const bool active = c0 < ncols;
+    const int ne = (int)std::max(0LL, std::min((long long)E, ncols - c0));
+    float gv[MT][E];
+#pragma unroll
+    for (int r = 0; r < MT; ++r)
+#pragma unroll
+        for (int e = 0; e < E; ++e) gv[r][e] = g[cbdc_idx((long long)r * ncols + c0 + e, r < m && e < ne)];
+    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+    for (int r = 0; r < MT; ++r)
+#pragma unroll
+        for (int e = 0; e < E; ++e) gv[r][e] = cbdc_scaled(gv[r][e], r < m && e < ne, scg);
+
+    long long group = (long long)blockIdx.y * rows_per_group / group_rows;
+    const long long s_lo = (long long)blockIdx.y * rows_per_group, s_hi = std::min(kdim, s_lo + rows_per_group);
+    long long g_lo = s_lo, g_hi = std::min(s_hi, (group + 1) * group_rows);   // the rows of the workgroup that lie in `group`
+    long long per_wave = (g_hi - g_lo + CB_WAVES - 1) / CB_WAVES;
+    long long i0 = std::min(g_hi, g_lo + wave * per_wave), i1 = std::min(g_hi, i0 + per_wave);
+    const uintptr_t base = reinterpret_cast<uintptr_t>(labels);
+    const long long row_bytes = ncols * LB;
+    const long long lane_off = (long long)blockIdx.x * (64 * VB) + lane * VB;
+    __syncthreads();
+
+    auto row_words = [&](long long i, uint32_t *w, uint32_t &s) {
+        const uintptr_t row = base + (uintptr_t)(i * row_bytes);
+        if constexpr (ALIGNED) {
+            s = 0;
+            load_chunk<VB>(reinterpret_cast<const unsigned char *>(active ? row + lane_off : row), w);
+        } else {
+            const uintptr_t first = row & ~(uintptr_t)(VB - 1);
+            s = (uint32_t)(__builtin_amdgcn_readfirstlane((uint32_t)((row + blockIdx.x * (64 * VB)) & (VB - 1))));
+            const uintptr_t a = ((row + lane_off) & ~(uintptr_t)(VB - 1));
+            const uintptr_t a0 = active ? a : first;
+            const uintptr_t a1 = (active && a + VB < row + row_bytes) ? a + VB : a0;
+            load_chunk<VB>(reinterpret_cast<const unsigned char *>(a0), w);
+            load_chunk<VB>(reinterpret_cast<const unsigned char *>(a1), w + N);
+        }
+    };
+    // x[r, i + u] of a batch of U rows: lane f holds value f = r * U + u (and f + 64), broadcast by v_readlane (as k_cbmm_stream)
+    auto load_x = [&](long long i, int U, float &xa, float &xb) {
+        const int f0 = lane, f1 = lane + 64;
+        const int r0 = f0 / U, r1 = f1 / U;
+        xa = cbdc_scaled(x[cbdc_idx((long long)r0 * kdim + i + f0 % U, r0 < m)], r0 < m, scx);
+        xb = MT * CB_UNROLL > 64 ? cbdc_scaled(x[cbdc_idx((long long)r1 * kdim + i + f1 % U, r1 < m)], r1 < m, scx) : 0.0f;
+    };
+    auto consume = [&](const uint32_t *w, uint32_t s, float xa, float xb, int u, int U) {
+        float xv[MT];
+#pragma unroll
+        for (int r = 0; r < MT; ++r) {
+            const int f = r * U + u;
+            xv[r] = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, f < 64 ? xa : xb), f & 63));
+        }
+        uint32_t o[N];
+        if constexpr (ALIGNED) {
+#pragma unroll
+            for (int d = 0; d < N; ++d) o[d] = w[d];
+        } else {
+            funnel<N>(w, s, o);
+        }
+#pragma unroll
+        for (int e = 0; e < E; ++e) {
+            const uint32_t l = (o[e / PER] >> (8 * LB * (e % PER))) & 0xFFu;
+            float d = 0.0f;
+#pragma unroll
+            for (int r = 0; r < MT; ++r) d = __builtin_fmaf(xv[r], gv[r][e], d);   // dW'[i, o], r ascending
+            if (e < ne && l < (uint32_t)k) atomicAdd(&bins[(l << rlog2) + rep], cbdc_fix(d, Sw));
+        }
+    };
+
+    constexpr int WN = ALIGNED ? N : 2 * N;
+    for (;;) {
+        long long i = i0;
+        for (; i + CB_UNROLL <= i1; i += CB_UNROLL) {
+            uint32_t w[CB_UNROLL][WN], s[CB_UNROLL];
+            float xa, xb;
+#pragma unroll
+            for (int u = 0; u < CB_UNROLL; ++u) row_words(i + u, w[u], s[u]);
+            load_x(i, CB_UNROLL, xa, xb);
+#pragma unroll
+            for (int u = 0; u < CB_UNROLL; ++u) consume(w[u], s[u], xa, xb, u, CB_UNROLL);
+        }
+        for (; i < i1; ++i) {
+            uint32_t w[WN], s;
+            float xa, xb;
+            row_words(i, w, s);
+            load_x(i, 1, xa, xb);
+            consume(w, s, xa, xb, 0, 1);
+        }
+        cbdc_flush(bins, k, rlog2, sums + group * k);   // (begins with a barrier: every wave has left the group's rows)
+        if (g_hi >= s_hi) break;
+        for (int j = threadIdx.x; j < k; j += CB_THREADS)   // the copies this thread has just summed
+            for (int r = 0; r < (1 << rlog2); ++r) bins[(j << rlog2) + r] = 0ull;
+        g_lo = g_hi;
+        g_hi = std::min(s_hi, (++group + 1) * group_rows);
+        per_wave = (g_hi - g_lo + CB_WAVES - 1) / CB_WAVES;
+        i0 = std::min(g_hi, g_lo + wave * per_wave), i1 = std::min(g_hi, i0 + per_wave);
+        __syncthreads();
+    }
+}
+
+// ------------------------------------------------------------------ dc, m > 16
+// k_cbdc_tiled<uint8_t> with sums[groups][k]: the same grid, tiles and FMA order.  The k << rlog2 LDS bins are cut into
+// 1 << sets_log2 sets of k << (rlog2 - sets_log2), set t for group m0 / group_rows + t.  Thread (tx, ty) bins index rows
+// m0 + ty * 8 .. + 7, which lie in one group, into that group's set; every set then goes into its group's sums.
+__global__ __launch_bounds__(256) void k_cbdc_tiled_grouped(const float *__restrict__ x, const float *__restrict__ g, long long m, long long kdim,
+                                                            const uint8_t *__restrict__ labels, long long ncols, int k, int rlog2, int sets_log2,
+                                                            int terms_log2, long long col_tiles, long long rows_per_split, long long group_rows,
+                                                            uint32_t *__restrict__ hdr, unsigned long long *__restrict__ sums)
+{
+    extern __shared__ float smem[];
+    float *xs = smem;                      // [TB_K][TB_M]: x[r, i0 + i]
+    float *gs = xs + TB_K * TB_M;          // [TB_K][TB_N]: g[r, o0 + o]
+    unsigned long long *bins = reinterpret_cast<unsigned long long *>(gs + TB_K * TB_N);
+    int scx, scg, Sw;
+    if (!cbdc_begin(hdr, m, terms_log2, bins, k << rlog2, scx, scg, Sw)) return;
+
+    const TbTile T = tb_tile(col_tiles, rows_per_split, m);   // n0: the first column o, m0: the first index row i
+    float acc[8][8];
+    tb_clear(acc);
+    for (long long rb = T.lo; rb < T.hi; rb += TB_K) {
+        __syncthreads();
+        cbdc_load_tiles(xs, gs, x, g, kdim, ncols, T.m0, T.n0, rb, T.hi, scx, scg);
+        __syncthreads();
+        tb_tile_fma(xs, gs, T.tx, T.ty, acc);
+    }
+    const int rl = rlog2 - sets_log2, sets = 1 << sets_log2;
+    const long long q0 = T.m0 / group_rows, groups = (kdim + group_rows - 1) / group_rows;
+    const int set = (int)std::min((long long)sets - 1, (T.m0 + T.ty * 8) / group_rows - q0);
+    cbdc_bin_tile(acc, T, kdim, ncols, k, Sw, bins + ((long long)set * k << rl), rl, threadIdx.x & ((1 << rl) - 1),
+                  [&](long long i, long long o) { return (uint32_t)labels[i * ncols + o]; });
+    for (int t = 0; t < sets && q0 + t < groups; ++t) cbdc_flush(bins + ((long long)t * k << rl), k, rl, sums + (q0 + t) * k);
+}
+
+// ------------------------------------------------------------------ launches
+template <int VB, int MT>
+static void launch_dx_stream(bool aligned, dim3 grid, size_t lds, hipStream_t s, const float *g, int m, long long kdim, const void *labels, long long ncols,
+                             const float *centers, int k, int entries, int cshift, long long rpg, long long group_rows, int direct, float *out)
+{
+    const unsigned char *lab = reinterpret_cast<const unsigned char *>(labels);
+    if (aligned)
+        hipLaunchKernelGGL((k_cbdx_stream_grouped<VB, MT, true>), grid, dim3(CB_THREADS), lds, s, g, m, kdim, lab, ncols, centers, k, entries, cshift, rpg, group_rows, direct, out);
+    else
+        hipLaunchKernelGGL((k_cbdx_stream_grouped<VB, MT, false>), grid, dim3(CB_THREADS), lds, s, g, m, kdim, lab, ncols, centers, k, entries, cshift, rpg, group_rows, direct, out);
+}
+
+template <int VB, int MT>
+static void launch_dc_stream(bool aligned, dim3 grid, size_t lds, hipStream_t s, const float *x, const float *g, int m, long long kdim, const void *labels,
+                             long long ncols, int k, int rlog2, int tl, long long rpg, long long group_rows, uint32_t *hdr, unsigned long long *sums)
+{
+    const unsigned char *lab = reinterpret_cast<const unsigned char *>(labels);
+    if (aligned)
+        hipLaunchKernelGGL((k_cbdc_stream_grouped<VB, MT, true>), grid, dim3(CB_THREADS), lds, s, x, g, m, kdim, lab, ncols, k, rlog2, tl, rpg, group_rows, hdr, sums);
+    else
+        hipLaunchKernelGGL((k_cbdc_stream_grouped<VB, MT, false>), grid, dim3(CB_THREADS), lds, s, x, g, m, kdim, lab, ncols, k, rlog2, tl, rpg, group_rows, hdr, sums);
+}
+
+// every stream instantiation of this unit (those of nnc_cbgrad.hip for uint8 labels); the plans are checked against this table
+using DxLaunch = void (*)(bool, dim3, size_t, hipStream_t, const float *, int, long long, const void *, long long, const float *, int, int, int, long long,
+                          long long, int, float *);
+using DcLaunch = void (*)(bool, dim3, size_t, hipStream_t, const float *, const float *, int, long long, const void *, long long, int, int, int, long long,
+                          long long, uint32_t *, unsigned long long *);
+struct GradCase {
+    int vb, mt;
+    DxLaunch dx;
+    DcLaunch dc;
+};
+#define GRAD_CASE(VB, MT) {VB, MT, launch_dx_stream<VB, MT>, launch_dc_stream<VB, MT>}
+static const GradCase kGradCases[] = {GRAD_CASE(16, 1), GRAD_CASE(16, 2), GRAD_CASE(16, 4), GRAD_CASE(8, 8), GRAD_CASE(4, 16)};
+#undef GRAD_CASE
+
+static const GradCase *find_grad_case(int vb, int mt)
+{
+    for (const GradCase &c : kGradCases)
+        if (c.vb == vb && c.mt == mt) return &c;
+    return nullptr;
+}
+
+static int no_grad_case(const char *fn, int vb, int mt)
+{
+    return fail(NNC_EINVAL, std::string(fn) + ": no grouped stream instantiation for vb " + std::to_string(vb) + ", mt " + std::to_string(mt));
+}
+
+// ------------------------------------------------------------------ C ABI
+// G as the layers count it: centers and dc have a row even where kdim = 0
+static long long gg_groups(long long kdim, long long group_rows) { return std::max(1LL, cdiv(kdim, group_rows)); }
+
+// cg_check's checks at label_bytes 1, then those nnc_cbmm_grouped makes of k and group_rows
+static int gg_check(const char *fn, int64_t m, int64_t kdim, int64_t ncols, int32_t k, int64_t group_rows)
+{
+    const std::string f(fn);
+    if (k > 256) return fail(NNC_EINVAL, f + ": k outside 1..256 (group codebooks take uint8 labels only)");
+    const int rc = cg_check(fn, m, kdim, ncols, 1, k);
+    if (rc != NNC_OK) return rc;
+    if (group_rows < 32 || group_rows % 32) return fail(NNC_EINVAL, f + ": group_rows must be a positive multiple of 32");
+    if (group_rows > (1LL << 40)) return fail(NNC_EINVAL, f + ": size too large");
+    if (gg_groups(kdim, group_rows) * k > (1LL << 30)) return fail(NNC_EINVAL, f + ": more than 2^30 bins (groups * k)");
+    return NNC_OK;
+}
+
+// the four values a grouped plan adds to the ungrouped record
+static void gg_plan_tail(const CgPlan &p, long long kdim, long long group_rows, int64_t *out)
+{
+    const bool stream = p.path == NNC_CBMM_STREAM, tiled = p.path == NNC_CBMM_TILED;
+    out[0] = group_rows;
+    out[1] = kdim > 0 ? cdiv(kdim, group_rows) : 0;
+    out[2] = stream ? p.rows_per_group : 0;
+    out[3] = stream ? max_groups_per_split(p.row_tiles, p.rows_per_group, kdim, group_rows)
+                    : (tiled ? max_groups_per_split(cdiv(kdim, 128), 128, kdim, group_rows) : 0);
+}
+
+static int gg_plan_out(const char *fn, const CgPlan &p, int32_t cus, const int64_t *out)
+{
+    if (cus < 1) return fail(NNC_EINVAL, std::string(fn) + ": cus < 1");
+    if (!out) return fail(NNC_EINVAL, std::string(fn) + ": out is NULL");
+    if (p.path == NNC_CBMM_STREAM && !find_grad_case(p.vb, p.mt)) return no_grad_case(fn, p.vb, p.mt);
+    return NNC_OK;
+}
+
+extern "C" int64_t nnc_cbmm_grouped_dx_workspace_bytes(int64_t m, int64_t kdim, int64_t ncols)
+{
+    if (cg_check("nnc_cbmm_grouped_dx_workspace_bytes", m, kdim, ncols, 1, 1) != NNC_OK) return 0;
+    return cbg_dx_ws_bytes(dx_plan(m, kdim, ncols, 1, 1, CB_PLAN_CUS, 0).splits, m, kdim);
+}
+
+extern "C" int nnc_cbmm_grouped_dx_plan(int64_t m, int64_t kdim, int64_t ncols, int32_t k, int64_t group_rows, int32_t cus, uint64_t labels_addr,
+                                        int64_t *out)
+{
+    int rc = gg_check("nnc_cbmm_grouped_dx_plan", m, kdim, ncols, k, group_rows);
+    if (rc != NNC_OK) return rc;
+    const CgPlan p = dx_plan(m, kdim, ncols, 1, k, cus, (uintptr_t)labels_addr);
+    if ((rc = gg_plan_out("nnc_cbmm_grouped_dx_plan", p, cus, out)) != NNC_OK) return rc;
+    const bool tiled = p.path == NNC_CBMM_TILED;
+    const int tables = tile_groups(group_rows);
+    const int64_t v[NNC_CBDX_PLAN_LEN] = {p.path, p.vb, p.mt, p.path == NNC_CBMM_STREAM ? 1LL << p.cshift : (tiled ? tables : 0), p.entries, p.splits,
+                                          p.per_split, p.aligned, p.lds + (tiled ? (long long)(tables - 1) * (k + 1) * 4 : 0), p.col_tiles, p.row_tiles,
+                                          cbg_dx_ws_bytes(p.splits, m, kdim)};
+    for (int i = 0; i < NNC_CBDX_PLAN_LEN; ++i) out[i] = v[i];
+    gg_plan_tail(p, kdim, group_rows, out + NNC_CBDX_PLAN_LEN);
+    return NNC_OK;
+}
+
+extern "C" int nnc_cbmm_grouped_dx_f32(const float *g, int64_t m, int64_t kdim, const void *labels, int64_t ncols, const float *centers_dev, int32_t k,
+                                       int64_t group_rows, float *dx, void *workspace, int64_t workspace_bytes, void *stream)
+{
+    int rc = gg_check("nnc_cbmm_grouped_dx_f32", m, kdim, ncols, k, group_rows);
+    if (rc != NNC_OK) return rc;
+    if (!centers_dev) return fail(NNC_EINVAL, "nnc_cbmm_grouped_dx_f32: centers is NULL");
+    if (m > 0 && kdim > 0 && !dx) return fail(NNC_EINVAL, "nnc_cbmm_grouped_dx_f32: dx is NULL");
+    if (m > 0 && kdim > 0 && ncols > 0 && (!g || !labels)) return fail(NNC_EINVAL, "nnc_cbmm_grouped_dx_f32: g or labels is NULL");
+    const int64_t need = nnc_cbmm_grouped_dx_workspace_bytes(m, kdim, ncols);
+    if ((rc = cb_check_workspace("nnc_cbmm_grouped_dx_f32", "nnc_cbmm_grouped_dx_workspace_bytes", workspace, workspace_bytes, need)) != NNC_OK) return rc;
+    const CgPlan p = dx_plan(m, kdim, ncols, 1, k, cu_count(), reinterpret_cast<uintptr_t>(labels));
+    const GradCase *gc = p.path == NNC_CBMM_STREAM ? find_grad_case(p.vb, p.mt) : nullptr;
+    if (p.path == NNC_CBMM_STREAM && !gc) return no_grad_case("nnc_cbmm_grouped_dx_f32", p.vb, p.mt);
+    if (p.path == NNC_CBMM_NONE) return NNC_OK;
+
+    hipStream_t s = S(stream);
+    if (p.path == NNC_CBMM_ZERO) {
+        HIPCHK(hipMemsetAsync(dx, 0, (size_t)(m * kdim) * 4, s));
+        return NNC_OK;
+    }
+    const int direct = p.splits == 1;
+    float *out = direct ? dx : reinterpret_cast<float *>(workspace);
+    if (p.path == NNC_CBMM_STREAM) {
+        gc->dx(p.aligned != 0, dim3((unsigned)p.col_tiles, (unsigned)p.row_tiles), (size_t)p.lds, s, g, (int)m, kdim, labels, ncols, centers_dev, k, p.entries,
+               p.cshift, p.rows_per_group, group_rows, direct, out);
+        LAUNCHCHK("k_cbdx_stream_grouped");
+    } else {
+        const int tables = tile_groups(group_rows);
+        const dim3 grid((unsigned)(p.col_tiles * p.row_tiles), (unsigned)p.splits);
+        hipLaunchKernelGGL(k_cbdx_tiled_grouped, grid, dim3(256), (size_t)(p.lds + (long long)(tables - 1) * (k + 1) * 4), s, g, (long long)m, (long long)kdim,
+                           reinterpret_cast<const uint8_t *>(labels), (long long)ncols, centers_dev, (int)k, p.col_tiles, p.per_split, (long long)group_rows,
+                           tables, direct, out);
+        LAUNCHCHK("k_cbdx_tiled_grouped");
+    }
+    if (!direct) return cbgrad_reduce(reinterpret_cast<const float *>(workspace), p.splits, m * kdim, dx, s);
+    return NNC_OK;
+}
+
+extern "C" int64_t nnc_cbmm_grouped_dc_workspace_bytes(int64_t m, int64_t kdim, int64_t ncols, int32_t k, int64_t group_rows)
+{
+    if (gg_check("nnc_cbmm_grouped_dc_workspace_bytes", m, kdim, ncols, k, group_rows) != NNC_OK) return 0;
+    return cbg_dc_ws_bytes(dc_plan(m, kdim, ncols, 1, k, CB_PLAN_CUS, 0).path, (int)(gg_groups(kdim, group_rows) * k));
+}
+
+extern "C" int nnc_cbmm_grouped_dc_plan(int64_t m, int64_t kdim, int64_t ncols, int32_t k, int64_t group_rows, int32_t cus, uint64_t labels_addr,
+                                        int64_t *out)
+{
+    int rc = gg_check("nnc_cbmm_grouped_dc_plan", m, kdim, ncols, k, group_rows);
+    if (rc != NNC_OK) return rc;
+    const CgPlan p = dc_plan(m, kdim, ncols, 1, k, cus, (uintptr_t)labels_addr);
+    if ((rc = gg_plan_out("nnc_cbmm_grouped_dc_plan", p, cus, out)) != NNC_OK) return rc;
+    const int sets_log2 = p.path == NNC_CBMM_TILED ? __builtin_ctz(tile_groups(group_rows)) : 0;
+    const int64_t v[NNC_CBDC_PLAN_LEN] = {p.path, p.vb, p.mt, p.path == NNC_CBMM_ZERO ? 0 : 1LL << (p.rlog2 - sets_log2), p.splits, p.per_split, p.aligned, p.lds,
+                                          p.col_tiles, p.row_tiles, p.terms_log2, cbg_dc_ws_bytes(p.path, (int)(gg_groups(kdim, group_rows) * k))};
+    for (int i = 0; i < NNC_CBDC_PLAN_LEN; ++i) out[i] = v[i];
+    gg_plan_tail(p, kdim, group_rows, out + NNC_CBDC_PLAN_LEN);
+    return NNC_OK;
+}
+
+extern "C" int nnc_cbmm_grouped_dc_f32(const float *x, const float *g, int64_t m, int64_t kdim, const void *labels, int64_t ncols, int32_t k,
+                                       int64_t group_rows, void *dc, int32_t out_f64, void *workspace, int64_t workspace_bytes, void *stream)
+{
+    int rc = gg_check("nnc_cbmm_grouped_dc_f32", m, kdim, ncols, k, group_rows);
+    if (rc != NNC_OK) return rc;
+    if (!dc) return fail(NNC_EINVAL, "nnc_cbmm_grouped_dc_f32: dc is NULL");
+    if (m > 0 && kdim > 0 && ncols > 0 && (!x || !g || !labels)) return fail(NNC_EINVAL, "nnc_cbmm_grouped_dc_f32: x, g or labels is NULL");
+    const int64_t need = nnc_cbmm_grouped_dc_workspace_bytes(m, kdim, ncols, k, group_rows);
+    if ((rc = cb_check_workspace("nnc_cbmm_grouped_dc_f32", "nnc_cbmm_grouped_dc_workspace_bytes", workspace, workspace_bytes, need, 8, "workspace not 8-byte aligned")) != NNC_OK) return rc;
+    const CgPlan p = dc_plan(m, kdim, ncols, 1, k, cu_count(), reinterpret_cast<uintptr_t>(labels));
+    const GradCase *gc = p.path == NNC_CBMM_STREAM ? find_grad_case(p.vb, p.mt) : nullptr;
+    if (p.path == NNC_CBMM_STREAM && !gc) return no_grad_case("nnc_cbmm_grouped_dc_f32", p.vb, p.mt);
+
+    hipStream_t s = S(stream);
+    const int nbins = (int)(gg_groups(kdim, group_rows) * k);
+    if (p.path == NNC_CBMM_ZERO) {
+        HIPCHK(hipMemsetAsync(dc, 0, (size_t)nbins * (out_f64 ? 8 : 4), s));
+        return NNC_OK;
+    }
+    uint32_t *hdr = reinterpret_cast<uint32_t *>(workspace);
+    unsigned long long *sums = reinterpret_cast<unsigned long long *>(reinterpret_cast<char *>(workspace) + CBG_HDR_BYTES);
+    HIPCHK(hipMemsetAsync(workspace, 0, (size_t)need, s));
+    if ((rc = cbgrad_absmax(x, m * kdim, g, m * ncols, hdr, s)) != NNC_OK) return rc;
+    if (p.path == NNC_CBMM_STREAM) {
+        gc->dc(p.aligned != 0, dim3((unsigned)p.col_tiles, (unsigned)p.row_tiles), (size_t)p.lds, s, x, g, (int)m, kdim, labels, ncols, k, p.rlog2,
+               p.terms_log2, p.rows_per_group, group_rows, hdr, sums);
+        LAUNCHCHK("k_cbdc_stream_grouped");
+    } else {
+        const dim3 grid((unsigned)(p.col_tiles * p.row_tiles), (unsigned)p.splits);
+        hipLaunchKernelGGL(k_cbdc_tiled_grouped, grid, dim3(256), (size_t)p.lds, s, x, g, (long long)m, (long long)kdim, reinterpret_cast<const uint8_t *>(labels),
+                           (long long)ncols, (int)k, p.rlog2, __builtin_ctz(tile_groups(group_rows)), p.terms_log2, p.col_tiles, p.per_split,
+                           (long long)group_rows, hdr, sums);
+        LAUNCHCHK("k_cbdc_tiled_grouped");
+    }
+    return cbdc_finish(hdr, reinterpret_cast<const long long *>(sums), nbins, (int)(out_f64 != 0), dc, s);
+}

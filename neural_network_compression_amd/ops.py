@@ -588,6 +588,90 @@ def codebook_linear(x: torch.Tensor, labels: torch.Tensor, centers: torch.Tensor
         lambda x2, g2, lab, c: codebook_centroid_grad(x2, g2, lab, c.numel(), kdim, ncols, dtype=torch.float32))
 
 
+def _grouped_grad_args(who: str, g: torch.Tensor, labels: torch.Tensor, kdim: int, ncols: int, k: int, group_rows: int):
+    """The grouped form's checks of g, the indices and the groups -> (lead, m, G) of g, G as the layers count it (>= 1)."""
+    _require_cuda(g, "g", torch.float32)
+    _require_cuda(labels, "labels")
+    if labels.dtype != torch.uint8:
+        raise TypeError(f"{who} takes uint8 labels (K <= 256 per group), got {labels.dtype}")
+    if group_rows < 32 or group_rows % 32:
+        raise ValueError(f"group_rows must be a positive multiple of 32, got {group_rows}")
+    if not 1 <= k <= 256:
+        raise ValueError(f"k = {k} outside 1..256")
+    if labels.numel() != kdim * ncols:
+        raise ValueError(f"labels must hold kdim * ncols = {kdim * ncols} indices, got {labels.numel()}")
+    lead, m = _rows(g, "g", ncols)
+    return lead, m, max(-(-kdim // group_rows), 1)
+
+
+def grouped_codebook_matmul_dx(g: torch.Tensor, labels: torch.Tensor, centers: torch.Tensor, kdim: int, ncols: int, group_rows: int) -> torch.Tensor:
+    """dx = g @ W^T with W[i, o] = centers[i // group_rows][labels[i * ncols + o]] (include/nnc.h, nnc_cbmm_grouped_dx_f32; DESIGN.md
+    section 19): the input gradient of grouped_codebook_matmul.  g: float32 (..., ncols); labels, centers (G, K) and group_rows as
+    grouped_codebook_matmul.  Returns float32 (..., kdim); the columns of a group are, bit for bit, those codebook_matmul_dx gives
+    with that group's table.  No host read."""
+    kdim, ncols, group_rows = int(kdim), int(ncols), int(group_rows)
+    _require_cuda(centers, "centers", torch.float32)
+    k = int(centers.shape[1]) if centers.dim() == 2 and 1 <= centers.shape[1] <= 256 else 0
+    lead, m, groups = _grouped_grad_args("grouped_codebook_matmul_dx", g, labels, kdim, ncols, k or 1, group_rows)
+    if not k or centers.shape[0] != groups:
+        raise ValueError(f"centers must have shape ({groups}, K <= 256) for kdim {kdim} and group_rows {group_rows}, got {tuple(centers.shape)}")
+    _one_device("g, labels and centers", g, labels, centers)
+    L = nat.load()
+    dx = torch.empty(lead + (kdim,), dtype=torch.float32, device=g.device)
+    ws_bytes = int(L.nnc_cbmm_grouped_dx_workspace_bytes(m, kdim, ncols))
+    ws = _workspace(ws_bytes, g.device)
+    nat.check(L.nnc_cbmm_grouped_dx_f32(_ptr(g), m, kdim, _ptr(labels), ncols, _ptr(centers), k, group_rows, _ptr(dx), _ptr(ws), ws_bytes, _stream(g)))
+    return dx
+
+
+def grouped_codebook_centroid_grad(x: torch.Tensor, g: torch.Tensor, labels: torch.Tensor, k: int, kdim: int, ncols: int, group_rows: int,
+                                   dtype=torch.float64) -> torch.Tensor:
+    """dc[q, j] = sum over the (i, o) with i // group_rows = q and labels[i * ncols + o] = j of (x^T g)[i, o] (include/nnc.h,
+    nnc_cbmm_grouped_dc_f32): the centroid gradient of grouped_codebook_matmul, the kdim x ncols dW never written.  x: float32
+    (..., kdim), g: float32 (..., ncols) with the same leading shape.  Exact fixed-point sums with the shift of the ungrouped call
+    (cbgrad_shift on the plan's terms_log2).  Returns ``dtype`` (float64 or float32) (G, k).  No host read."""
+    kdim, ncols, k, group_rows = int(kdim), int(ncols), int(k), int(group_rows)
+    _require_cuda(x, "x", torch.float32)
+    lead, m, groups = _grouped_grad_args("grouped_codebook_centroid_grad", g, labels, kdim, ncols, k, group_rows)
+    _dc_args(x, lead, kdim, "x, g and labels", labels, g, dtype)
+    L = nat.load()
+    dc = torch.empty((groups, k), dtype=dtype, device=x.device)
+    ws_bytes = int(L.nnc_cbmm_grouped_dc_workspace_bytes(m, kdim, ncols, k, group_rows))
+    ws = _workspace(ws_bytes, x.device)
+    nat.check(L.nnc_cbmm_grouped_dc_f32(_ptr(x), _ptr(g), m, kdim, _ptr(labels), ncols, k, group_rows, _ptr(dc), 1 if dtype == torch.float64 else 0,
+                                        _ptr(ws), ws_bytes, _stream(x)))
+    return dc
+
+
+def cbmm_grouped_dx_plan(m: int, kdim: int, ncols: int, k: int, group_rows: int, cus: int, labels_addr: int = 0) -> dict:
+    """Host: the plan nnc_cbmm_grouped_dx_f32 follows on a device with ``cus`` compute units (include/nnc.h,
+    nnc_cbmm_grouped_dx_plan), as a dict keyed by _native.CBDX_GROUPED_PLAN_FIELDS.  No device needed."""
+    return _plan(nat.load().nnc_cbmm_grouped_dx_plan, nat.CBDX_GROUPED_PLAN_FIELDS, m, kdim, ncols, k, group_rows, cus, labels_addr)
+
+
+def cbmm_grouped_dc_plan(m: int, kdim: int, ncols: int, k: int, group_rows: int, cus: int, labels_addr: int = 0) -> dict:
+    """Host: the plan nnc_cbmm_grouped_dc_f32 follows on a device with ``cus`` compute units (include/nnc.h,
+    nnc_cbmm_grouped_dc_plan), as a dict keyed by _native.CBDC_GROUPED_PLAN_FIELDS.  No device needed."""
+    return _plan(nat.load().nnc_cbmm_grouped_dc_plan, nat.CBDC_GROUPED_PLAN_FIELDS, m, kdim, ncols, k, group_rows, cus, labels_addr)
+
+
+def grouped_codebook_linear(x: torch.Tensor, labels: torch.Tensor, centers: torch.Tensor, kdim: int, ncols: int, group_rows: int,
+                            bias: torch.Tensor | None = None, relu: bool = False) -> torch.Tensor:
+    """grouped_codebook_matmul with gradients for x, centers (G, K) and bias, through the autograd Function of codebook_linear.
+    The forward is the same float32 nnc_cbmm_grouped call (under no_grad the bits of grouped_codebook_matmul); the backward runs
+    grouped_codebook_matmul_dx only if x needs a gradient and grouped_codebook_centroid_grad (float32) only if centers does.  The
+    ReLU mask and the bias gradient are codebook_linear's.  No host read."""
+    _require_f32_x(x, "grouped_codebook_linear")
+    if isinstance(labels, torch.Tensor) and labels.dtype != torch.uint8:
+        raise TypeError(f"grouped_codebook_linear takes uint8 labels (K <= 256 per group), got {labels.dtype}")
+    kdim, ncols, group_rows = int(kdim), int(ncols), int(group_rows)
+    return _CodebookLinear.apply(
+        x, labels, centers, bias, bool(relu), kdim, ncols,
+        lambda x2, lab, c, b, r: grouped_codebook_matmul(x2, lab, c, kdim, ncols, group_rows, bias=b, relu=r),
+        lambda g2, lab, c: grouped_codebook_matmul_dx(g2, lab, c, kdim, ncols, group_rows),
+        lambda x2, g2, lab, c: grouped_codebook_centroid_grad(x2, g2, lab, c.shape[1], kdim, ncols, group_rows, dtype=torch.float32))
+
+
 class SparseCodes:
     """The bitmap-sparse form of one (kdim, ncols) index matrix (include/nnc.h, nnc_cbsp_*): one 256-byte aligned uint8 device
     buffer holding the bitmap, the symbol counts and the ``nnz`` stored symbols, plus the metadata a product needs.  ``k`` is the
