@@ -1006,6 +1006,10 @@ int nnc_cbpk_dc_plan(int64_t m, int64_t kdim, int64_t ncols, int bits, int32_t k
 int nnc_cbpk_dc_f32(const float *x, const float *g, int64_t m, int64_t kdim, const void *packed, int64_t packed_bytes, int bits,
                     int64_t ncols, int32_t k, void *dc, int32_t out_f64, void *workspace, int64_t workspace_bytes, void *stream);
 
+/* The backward pass of the group-wise packed layer from the same codebooks and packed indices (csrc/nnc_cbpkgrad_grouped.hip,
+ * DESIGN.md section 20): six entry points, declared in a header of their own. */
+#include "nnc_cbpkgrad_grouped.h"
+
 /* ------------------------------------------------------------------------------------
  * Multi-GPU: the vector is sharded across one process per GPU (contiguous shards starting on multiples of
  * NNC_CHUNK elements); the exchange per Lloyd iteration is one all-reduce (SUM) of the 2K int64 sums / counts over

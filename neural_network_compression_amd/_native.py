@@ -55,6 +55,10 @@ CBPKDX_PLAN_LEN = 12   # nnc_cbpk_dx_plan / nnc_cbpk_dc_plan (include/nnc.h)
 CBPKDX_PLAN_FIELDS = ("path", "vb", "mt", "cols", "copies", "entries", "splits", "cps", "lds", "col_tiles", "row_tiles", "workspace")
 CBPKDC_PLAN_LEN = 12
 CBPKDC_PLAN_FIELDS = ("path", "vb", "mt", "cols", "copies", "splits", "rps", "lds", "col_tiles", "row_tiles", "terms_log2", "workspace")
+CBPKGRAD_GROUPED_PLAN_LEN = 17   # nnc_cbpk_grouped_dx_plan / nnc_cbpk_grouped_dc_plan: the ungrouped packed fields, then the groups
+_CBPKGRAD_GROUPED_TAIL = _CBGRAD_GROUPED_TAIL + ("held",)   # dx: the tables held in LDS; dc: the per-group sets of bins
+CBPKDX_GROUPED_PLAN_FIELDS = CBPKDX_PLAN_FIELDS + _CBPKGRAD_GROUPED_TAIL
+CBPKDC_GROUPED_PLAN_FIELDS = CBPKDC_PLAN_FIELDS + _CBPKGRAD_GROUPED_TAIL
 CBSPDX_PLAN_LEN = 11   # nnc_cbsp_dx_plan / nnc_cbsp_dc_plan (include/nnc.h)
 CBSPDX_PLAN_FIELDS = ("path", "mt", "segs", "copies", "entries", "splits", "cps", "lds", "col_tiles", "row_tiles", "workspace")
 CBSPDC_PLAN_LEN = 11
@@ -271,6 +275,18 @@ GROUPED_GRAD_SIGNATURES = {
     "nnc_cbmm_grouped_dc_f32": (c_int, [c_void_p, c_void_p, c_i64, c_i64, c_void_p, c_i64, c_i32, c_i64, c_void_p, c_i32, c_void_p, c_i64, c_void_p]),
 }
 
+# name -> (restype, argtypes); every symbol include/nnc_cbpkgrad_grouped.h declares (the backward pass of the group-wise packed layer,
+# again a header of its own that nnc.h includes).  Required and bound by load() as SIGNATURES are.
+GROUPED_PACKED_GRAD_SIGNATURES = {
+    "nnc_cbpk_grouped_dx_workspace_bytes": (c_i64, [c_i64, c_i64, c_i64, c_int]),
+    "nnc_cbpk_grouped_dx_plan": (c_int, [c_i64, c_i64, c_i64, c_int, c_i32, c_i64, c_i32, ctypes.POINTER(c_i64)]),
+    "nnc_cbpk_grouped_dx_f32": (c_int, [c_void_p, c_i64, c_i64, c_void_p, c_i64, c_int, c_i64, c_void_p, c_i32, c_i64, c_void_p, c_void_p, c_i64, c_void_p]),
+    "nnc_cbpk_grouped_dc_workspace_bytes": (c_i64, [c_i64, c_i64, c_i64, c_int, c_i32, c_i64]),
+    "nnc_cbpk_grouped_dc_plan": (c_int, [c_i64, c_i64, c_i64, c_int, c_i32, c_i64, c_i32, ctypes.POINTER(c_i64)]),
+    "nnc_cbpk_grouped_dc_f32": (c_int, [c_void_p, c_void_p, c_i64, c_i64, c_void_p, c_i64, c_int, c_i64, c_i32, c_i64, c_void_p, c_i32, c_void_p, c_i64,
+                                        c_void_p]),
+}
+
 # exported only by the diagnostics build (NNC_DIAG=1: libnnc_hip_diag.so, see build.py); bound when present
 DIAG_SIGNATURES = {
     "nnc_debug_set_ablation": (c_int, [c_int]),
@@ -303,7 +319,7 @@ def load():
         L = ctypes.CDLL(path)
     except OSError as e:  # pragma: no cover - depends on the machine
         raise NativeLibraryError(f"cannot load {path}: {e}; there is no CPU fallback") from e
-    for name, (res, args) in list(SIGNATURES.items()) + list(GROUPED_GRAD_SIGNATURES.items()):
+    for name, (res, args) in list(SIGNATURES.items()) + list(GROUPED_GRAD_SIGNATURES.items()) + list(GROUPED_PACKED_GRAD_SIGNATURES.items()):
         try:
             fn = getattr(L, name)
         except AttributeError as e:

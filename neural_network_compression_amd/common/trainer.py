@@ -221,10 +221,13 @@ class Trainer(ABC):
         net = compressed.compress_network_trainable(self.neural_network, models, sparse=sparse, packed=packed)
         return self._tune_centres(net, models, train_dataset, test_dataset, epochs, learning_rate)
 
-    def fine_tune_grouped(self, train_dataset: LeNetDataset, test_dataset: LeNetDataset, epochs: int, learning_rate: float = 1e-3) -> List[float]:
-        """fine_tune_compressed's loop on ``compressed.compress_network_trainable_grouped``: the Dense layers quantized with
-        ``group_rows`` train their (G, K) centres through ops.grouped_codebook_linear (neither W nor dW is
-        built), every other quantized tensor trains as in fine_tune_compressed(sparse=False, packed=False).  At the end a
+    def fine_tune_grouped(self, train_dataset: LeNetDataset, test_dataset: LeNetDataset, epochs: int, learning_rate: float = 1e-3,
+                          packed=False) -> List[float]:
+        """fine_tune_compressed's loop on ``compressed.compress_network_trainable_grouped(..., packed=packed)``: the Dense layers
+        quantized with ``group_rows`` train their (G, K) centres through ops.grouped_codebook_linear (neither W
+        nor dW is built), every other quantized tensor trains as in fine_tune_compressed(sparse=False, packed=False).  ``packed``
+        True or "auto": the grouped layers of at most 16 centres per group train from their 2- or 4-bit packed indices instead
+        (ops.grouped_packed_codebook_linear), every one or where that form is smaller.  At the end a
         GroupedModel's ``cluster_centers_`` gets the tuned (G, K), each of its ``models[q].cluster_centers_`` the first entries that
         are that group's own (not the zero padding of a shorter codebook), and the float kernel is re-decoded group by group, so
         compressed_network(), store_report and load_network see the tuned centres.  Returns the accuracy per epoch."""
@@ -233,7 +236,7 @@ class Trainer(ABC):
             raise RuntimeError("fine_tune_grouped needs a quantized network: call quantize first")
         from .. import compressed
 
-        net = compressed.compress_network_trainable_grouped(self.neural_network, models)
+        net = compressed.compress_network_trainable_grouped(self.neural_network, models, packed=packed)
         return self._tune_centres(net, models, train_dataset, test_dataset, epochs, learning_rate)
 
     def _tune_centres(self, net, models, train_dataset, test_dataset, epochs, learning_rate) -> List[float]:

@@ -66,14 +66,18 @@ A grouped Dense layer trains too (``TrainableGroupedCompressedDense``, DESIGN.md
 backward forms dx and the (G, K) centroid gradient from the codebooks and the byte indices (csrc/nnc_cbgrad_grouped.hip).  The
 options above keep refusing grouped layers; the way in is
 
-    compress_network_trainable_grouped(network, models_by_layer)   the byte trainable layers, grouped Dense layers included
+    compress_network_trainable_grouped(network, models_by_layer, packed=False)   the byte trainable layers, grouped Dense layers included
 
-and Trainer.fine_tune_grouped trains it.  The packed and the bitmap-sparse grouped forms and grouped Conv2D do not train.
+and Trainer.fine_tune_grouped trains it.  With ``packed=True | "auto"`` there a grouped layer of at most 16 centres per group
+trains from its 2- or 4-bit packed indices (``TrainableGroupedPackedCompressedDense``):
+ops.grouped_packed_codebook_linear's backward forms dx and the (G, K) centroid gradient from the packed rows
+(csrc/nnc_cbpkgrad_grouped.hip), the centroid gradient the byte grouped layer's bit for bit, and no byte-per-weight tensor stays
+resident while training.  The bitmap-sparse grouped form and grouped Conv2D do not train.
 
 How the classes are laid out: ``_Activated`` (the activation behind the product, ``get_weights``) is the root of
 ``_InferenceLayer`` (the float32 ``centers`` / ``bias`` buffers behind the family's index buffer, ``nbytes``) and of
 ``_TrainableCentres`` (the ``centers`` parameter, ``counts``, the three kinds of bias).  A family -- ``_CodebookLayer``,
-``GroupedCompressedDense``, ``GroupedPackedCompressedDense``, ``_SparseCodebookLayer``, ``_PackedCodebookLayer`` and the three trainable ones -- adds its index
+``GroupedCompressedDense``, ``GroupedPackedCompressedDense``, ``_SparseCodebookLayer``, ``_PackedCodebookLayer`` and the trainable ones -- adds its index
 buffer and the one ops call of ``_matmul``; ``_SparseForm`` / ``_PackedForm`` hold what the inference and the trainable layer of
 a form share (the ``packed`` buffer, the metadata, ``codes``).  ``_DenseHalf`` and ``_Conv2DHalf`` are the two forwards over
 ``_matmul``; a public class is one of them on a family, with the constructors of its own signature.
@@ -408,6 +412,11 @@ class TrainableCompressedConv2D(_Conv2DHalf, _TrainableCodebookLayer):
         self._set_conv(kernel_size, cin, pad)
 
 
+def _group_counts(labels: torch.Tensor, per: int, groups: int, k: int) -> torch.Tensor:
+    """The (G, K) histogram of every group's indices: a group's ``per`` = group_rows * ncols indices lie one after the other."""
+    return torch.stack([ops.bincount(labels[q * per: (q + 1) * per], k) for q in range(groups)])
+
+
 class TrainableGroupedCompressedDense(_DenseHalf, _TrainableCentres):
     """GroupedCompressedDense with trainable centres (ops.grouped_codebook_linear): labels (kdim * ncols uint8
     indices, row-major) a buffer, centers a float32 (G, K) nn.Parameter, counts the (G, K) histogram of every group's indices, so
@@ -426,8 +435,7 @@ class TrainableGroupedCompressedDense(_DenseHalf, _TrainableCentres):
             raise ValueError(f"centers must have shape ({groups}, K) for {kdim} rows in groups of {group_rows}, got {tuple(centers.shape)}")
         self.kdim, self.ncols, self.group_rows = int(kdim), int(ncols), int(group_rows)
         self.register_buffer("labels", labels.reshape(-1))
-        per = self.group_rows * self.ncols   # a group's indices lie one after the other
-        counts = torch.stack([ops.bincount(self.labels[q * per: (q + 1) * per], centers.shape[1]) for q in range(groups)])
+        counts = _group_counts(self.labels, self.group_rows * self.ncols, groups, centers.shape[1])
         self._init_centres(self.labels, centers, ncols, bias, bias_codes, activation, counts=counts)
 
     @classmethod
@@ -764,6 +772,64 @@ class GroupedPackedCompressedDense(_DenseHalf, _PackedForm, _InferenceLayer):
         return self._activate(ops.grouped_packed_codebook_matmul(x, self.codes, self.centers, self.group_rows, bias=self.bias, relu=self._fused_relu))
 
 
+class TrainableGroupedPackedCompressedDense(_DenseHalf, _PackedForm, _TrainableCentres):
+    """GroupedPackedCompressedDense with trainable centres (ops.grouped_packed_codebook_linear): packed (the
+    ordinary 2- or 4-bit packed buffer of the whole index matrix) the only index buffer, centers a float32 (G, K <= 2^bits)
+    nn.Parameter, counts the (G, K) histogram of every group's indices taken from the labels before packing, so kernel_sq_sum() is
+    TrainableGroupedCompressedDense's bit for bit; the bias of _TrainableCentres.  The backward forms dx and the (G, K) centroid
+    gradient from the codebooks and the packed rows (csrc/nnc_cbpkgrad_grouped.hip): the indices are never unpacked, W and dW never
+    built, and no byte-per-weight tensor stays resident while training.  float32 inputs only."""
+
+    def __init__(self, codes: ops.PackedCodes, group_rows: int, labels: torch.Tensor, centers: torch.Tensor, bias: torch.Tensor | None = None,
+                 bias_codes=None, activation=None):
+        super().__init__()
+        groups = max(1, -(-codes.kdim // int(group_rows)))
+        if centers.dim() != 2 or tuple(centers.shape) != (groups, codes.k):
+            raise ValueError(f"centers must have shape ({groups}, {codes.k}) for {codes.kdim} rows in groups of {group_rows} and indices into "
+                             f"codebooks of {codes.k}, got {tuple(centers.shape)}")
+        if labels.numel() != codes.kdim * codes.ncols:
+            raise ValueError(f"{labels.numel()} indices for a {codes.kdim} x {codes.ncols} weight matrix")
+        self._take_codes(codes)
+        self.group_rows = int(group_rows)
+        counts = _group_counts(labels.reshape(-1), self.group_rows * self.ncols, groups, codes.k)
+        self._init_centres(None, centers, codes.ncols, bias, bias_codes, activation, counts=counts)
+
+    @classmethod
+    def from_dense(cls, dense, grouped_model, bias_model=None, bits=None) -> "TrainableGroupedPackedCompressedDense":
+        """From a Dense layer and the GroupedModel of its kernel, K <= 16; a quantized bias keeps its codes, a raw one stays frozen."""
+        _require_model(grouped_model)
+        kin, kout = dense.kernel.shape
+        dev = dense.kernel.device
+        centers = torch.from_numpy(np.ascontiguousarray(grouped_model.cluster_centers_, dtype=np.float32)).to(dev)
+        bias, bias_codes = (None, _codes(bias_model, dev)) if bias_model is not None else (dense.bias, None)
+        return cls.from_codes(kin, kout, grouped_model.group_rows, grouped_model.labels_compact_, centers, bias, bias_codes, dense.activation, bits)
+
+    @classmethod
+    def from_codes(cls, kdim, ncols, group_rows, labels, centers, bias=None, bias_codes=None, activation=None,
+                   bits=None) -> "TrainableGroupedPackedCompressedDense":
+        if centers.dim() != 2:
+            raise ValueError(f"centers must have shape (G, K), got {tuple(centers.shape)}")
+        return cls(ops.pack_codes(labels, kdim, ncols, centers.shape[1], bits), group_rows, labels, centers, bias, bias_codes, activation)
+
+    @classmethod
+    def from_grouped(cls, layer: GroupedCompressedDense, bits=None) -> "TrainableGroupedPackedCompressedDense":
+        """The trainable packed layer of a GroupedCompressedDense: its indices packed, the same centres, its decoded bias frozen."""
+        return cls.from_codes(layer.kdim, layer.ncols, layer.group_rows, layer.labels, layer.centers, layer.bias, None, layer.activation, bits)
+
+    @classmethod
+    def from_grouped_packed(cls, layer: GroupedPackedCompressedDense) -> "TrainableGroupedPackedCompressedDense":
+        """The trainable layer of a GroupedPackedCompressedDense on the same packed buffer; the counts come from a temporary unpack
+        (nnc_cbpk_unpack), which is dropped afterwards."""
+        return cls(layer.codes, layer.group_rows, layer.codes.to_dense(), layer.centers, layer.bias, None, layer.activation)
+
+    def _matmul(self, x: torch.Tensor) -> torch.Tensor:
+        return self._activate(ops.grouped_packed_codebook_linear(x, self.codes, self.centers, self.group_rows, bias=self.current_bias(),
+                                                                 relu=self._fused_relu))
+
+    def nbytes(self) -> int:
+        return self._nbytes(self.packed)
+
+
 PACKED_MAX_K = 16   # the packed form holds at most 4-bit indices
 
 
@@ -889,12 +955,25 @@ def compress_network_trainable(network: nn.Module, models_by_layer, sparse=False
     return _compress_each(network, models_by_layer, make, grouped="trainable=True")
 
 
-def compress_network_trainable_grouped(network: nn.Module, models_by_layer) -> nn.Module:
+def compress_network_trainable_grouped(network: nn.Module, models_by_layer, packed=False) -> nn.Module:
     """compress_network_trainable(network, models_by_layer) -- the byte forms -- in which every layer whose kernel model is a
     utility.GroupedModel becomes a TrainableGroupedCompressedDense instead of raising.  On a network
-    without grouped layers it returns what compress_network_trainable returns.  Trainer.fine_tune_grouped trains it."""
-    return _compress_each(network, models_by_layer, lambda layer, wm, bm: _trainable(layer, wm, bm),
-                          make_grouped=TrainableGroupedCompressedDense.from_dense)
+    without grouped layers it returns what compress_network_trainable returns.  ``packed``: False (the byte grouped layers), True
+    (a TrainableGroupedPackedCompressedDense, DESIGN.md section 20, for every grouped layer of at most 16 centres per group) or
+    "auto" (that class only where the packed form holds fewer resident bytes; on equal bytes the byte form stays); anything else
+    is a ValueError.  Ungrouped layers stay in the byte trainable forms either way.  Trainer.fine_tune_grouped trains it."""
+    if packed is False:
+        make_grouped = TrainableGroupedCompressedDense.from_dense
+    elif packed is True or packed == "auto":
+        def make_grouped(layer, wm, bm):
+            k = wm.cluster_centers_.shape[1]
+            kin, kout = layer.kernel.shape
+            if k > PACKED_MAX_K or (packed == "auto" and ops.packed_nbytes(kin, kout, ops.packed_bits(k)) >= kin * kout):
+                return TrainableGroupedCompressedDense.from_dense(layer, wm, bm)
+            return TrainableGroupedPackedCompressedDense.from_dense(layer, wm, bm)
+    else:
+        raise ValueError(f"packed must be False, True or 'auto', got {packed!r}")
+    return _compress_each(network, models_by_layer, lambda layer, wm, bm: _trainable(layer, wm, bm), make_grouped=make_grouped)
 
 
 def _compress_each(network: nn.Module, models_by_layer, make, grouped=None, make_grouped=GroupedCompressedDense.from_dense) -> nn.Module:

@@ -216,6 +216,13 @@ static int cg_check(const char *fn, int64_t m, int64_t kdim, int64_t ncols, int 
     return NNC_OK;
 }
 
+// ------------------------------------------------------------------ groups (host): the group-wise backward passes (nnc_cbgrad_grouped.hip, nnc_cbpkgrad_grouped.hip)
+// the most groups the 128 index rows of a tile lie in: tiles start on multiples of 128, group_rows is a multiple of 32
+static inline int tile_groups(long long group_rows) { return group_rows % 128 == 0 ? 1 : (group_rows == 32 ? 4 : 2); }
+
+// G as the layers count it: centers and dc have a row even where kdim = 0
+static inline long long gg_groups(long long kdim, long long group_rows) { return std::max(1LL, cdiv(kdim, group_rows)); }
+
 // the shared kernels of nnc_cbgrad.hip, launched on `s` (NNC_OK, or the launch error):
 //   cbgrad_absmax  amax[0..1] = bits of max |x[0, nx)|, max |g[0, ng)| (amax zeroed by the caller)   k_cbgrad_absmax
 //   cbgrad_reduce  out[idx] = sum over s < splits of part[s * mn + idx], in split order                k_cbgrad_reduce

@@ -23,9 +23,6 @@
 // k_cbgrad_absmax, k_cbgrad_reduce and k_cbdc_finish (over G * K bins) are nnc_cbgrad.hip's.
 #include "nnc_cbtile.hpp"
 
-// the most groups the 128 index rows of a tile lie in: tiles start on multiples of 128, group_rows is a multiple of 32
-static int tile_groups(long long group_rows) { return group_rows % 128 == 0 ? 1 : (group_rows == 32 ? 4 : 2); }
-
 // ------------------------------------------------------------------ dx, m <= 16
 // k_cbdx_stream<uint8_t> with centers[groups][k]: grid (column blocks, row groups), CB_THREADS threads, the same `out`.
 template <int VB, int MT, bool ALIGNED>
@@ -380,9 +377,6 @@ static int no_grad_case(const char *fn, int vb, int mt)
 }
 
 // ------------------------------------------------------------------ C ABI
-// G as the layers count it: centers and dc have a row even where kdim = 0
-static long long gg_groups(long long kdim, long long group_rows) { return std::max(1LL, cdiv(kdim, group_rows)); }
-
 // cg_check's checks at label_bytes 1, then those nnc_cbmm_grouped makes of k and group_rows
 static int gg_check(const char *fn, int64_t m, int64_t kdim, int64_t ncols, int32_t k, int64_t group_rows)
 {

@@ -21,105 +21,7 @@
 //   k_cbpkdc_tiled   m > 16.  k_cbdc_tiled's tiles and splits of m; a thread's 8 consecutive columns of a row come from one packed
 //                    dword, loaded once.
 // k_cbgrad_absmax, k_cbdc_finish and k_cbgrad_reduce are nnc_cbgrad.hip's.  No float atomics; no host read.
-#include "nnc_cbpk.hpp"
-#include "nnc_cbtile.hpp"
-
-#define PKG_RLOG2 6               // dc: 64 copies of every LDS bin, one per lane (K <= 16: at most 8 KiB)
-#define PKG_G 64                  // stream: g values a lane keeps (columns per lane x rows of m), at most
-
-// ------------------------------------------------------------------ plans (host)
-struct PgPlan {
-    int path;                 // NNC_CBMM_NONE / _STREAM / _TILED / _ZERO
-    int vb, mt, cols;         // stream: packed bytes per lane per row, rows of m per launch (a power of two >= m), 8 * vb / bits
-    int entries, copies;      // dx: the LDS table; dc: the copies of every LDS bin
-    long long col_tiles, row_tiles;   // stream: column blocks x row groups; tiled: tiles
-    long long splits, per_split;      // dx: splits of ncols (columns per split); dc: splits of m (rows of m per split)
-    long long rows_per_group;         // stream: packed rows per workgroup
-    int terms_log2;                   // dc: T of nnc_cbmm_dc_plan
-    long long lds;
-};
-
-// The stream geometry both directions share.  Columns per lane: at most a 16-byte load and PKG_G values of g; from there down to a
-// 4-byte load, the widest that keeps four lanes in five on a column (the last column block may be nearly empty) and leaves the
-// 256-CU planning device two workgroups per CU (column blocks x the most row groups kdim allows); else the narrowest.  The shape
-// alone decides, so the column blocks (the splits of dx) never change with the device; row groups for two workgroups per CU.
-static void pg_stream_grid(PgPlan &p, long long m, long long kdim, long long ncols, int bits, int cus)
-{
-    cus = std::max(1, std::min(cus, CB_PLAN_CUS));
-    p.path = NNC_CBMM_STREAM;
-    p.mt = cb_mt(m);
-    const long long max_groups = cdiv(kdim, (long long)CB_WAVES * CB_UNROLL);   // every wave keeps a batch of rows
-    const int cap = std::min(128 / bits, PKG_G / p.mt);
-    p.cols = cap;
-    for (int c = cap; c * bits >= 32; c /= 2) {
-        p.cols = c;
-        const long long tiles = cdiv(ncols, 64LL * c);
-        if (tiles * 64 * c * 4 <= ncols * 5 && tiles * max_groups >= 2LL * CB_PLAN_CUS) break;
-    }
-    p.vb = p.cols * bits / 8;
-    p.col_tiles = cdiv(ncols, 64LL * p.cols);
-    const long long groups = std::max(1LL, std::min(cdiv(2LL * cus, p.col_tiles), max_groups));
-    p.rows_per_group = cdiv(kdim, groups);
-    p.row_tiles = cdiv(kdim, p.rows_per_group);
-}
-
-static PgPlan pg_dx_plan(long long m, long long kdim, long long ncols, int bits, int cus)
-{
-    PgPlan p{};
-    if (m == 0 || kdim == 0) return p;                       // NNC_CBMM_NONE: dx is empty
-    if (ncols == 0) {                                        // dx = 0
-        p.path = NNC_CBMM_ZERO;
-        return p;
-    }
-    p.entries = 1 << bits;
-    if (m <= CB_SKINNY_M) {
-        pg_stream_grid(p, m, kdim, ncols, bits, cus);
-        p.splits = p.col_tiles;                              // one split per column block
-        p.per_split = 64LL * p.cols;
-        p.copies = PK_COPIES;
-        p.lds = ((long long)p.entries * PK_COPIES + p.entries) * 4;
-    } else {
-        p.path = NNC_CBMM_TILED;
-        p.copies = 1;
-        p.col_tiles = cdiv(kdim, TB_N);
-        p.row_tiles = cdiv(m, TB_M);
-        long long s = std::min({cdiv(2LL * CB_PLAN_CUS, p.col_tiles * p.row_tiles), ncols / (16 * TB_K), 16LL});
-        s = std::max(1LL, s);
-        p.per_split = cdiv(cdiv(ncols, s), 16) * 16;         // whole dwords at either width: a thread's 4 columns lie in one
-        p.splits = cdiv(ncols, p.per_split);
-        p.lds = (long long)(TB_K * TB_M + TB_K * TB_N + p.entries) * 4;
-    }
-    return p;
-}
-
-// The splits of m and T are nnc_cbmm_dc_plan's for the same shape at label_bytes = 1 (so S, every image and every sum are the byte
-// form's).  NNC_OK, or that plan's error.
-static int pg_dc_plan(long long m, long long kdim, long long ncols, int bits, int k, int cus, PgPlan &p)
-{
-    p = PgPlan{};
-    if (m == 0 || kdim == 0 || ncols == 0) {                 // no terms: dc = 0
-        p.path = NNC_CBMM_ZERO;
-        return NNC_OK;
-    }
-    int64_t d[NNC_CBDC_PLAN_LEN];
-    const int rc = nnc_cbmm_dc_plan(m, kdim, ncols, 1, k, CB_PLAN_CUS, 0, d);
-    if (rc != NNC_OK) return rc;
-    p.splits = d[NNC_CBDC_P_SPLITS];
-    p.per_split = d[NNC_CBDC_P_RPS];
-    p.terms_log2 = (int)d[NNC_CBDC_P_TERMS_LOG2];
-    p.copies = 1 << PKG_RLOG2;
-    const long long bins = ((long long)k << PKG_RLOG2) * 8;
-    if (m <= CB_SKINNY_M) {
-        pg_stream_grid(p, m, kdim, ncols, bits, cus);
-        p.lds = bins;
-    } else {
-        p.path = NNC_CBMM_TILED;
-        p.col_tiles = cdiv(ncols, TB_N);
-        p.row_tiles = cdiv(kdim, TB_M);
-        p.lds = (long long)(TB_K * TB_M + TB_K * TB_N) * 4 + bins;
-    }
-    return NNC_OK;
-}
+#include "nnc_cbpkgrad.hpp"
 
 // ------------------------------------------------------------------ dx, m <= 16
 // grid (column blocks, row groups), CB_THREADS threads.  out: dx (one column block) or the partials [block][m][kdim].
@@ -358,14 +260,6 @@ __global__ __launch_bounds__(256) void k_cbpkdc_tiled(const float *__restrict__ 
 }
 
 // ------------------------------------------------------------------ C ABI
-static int pg_check(const char *fn, int64_t m, int64_t kdim, int64_t ncols, int bits, int32_t k)
-{
-    const int rc = pk_check(fn, m, kdim, ncols, bits, k);
-    if (rc != NNC_OK) return rc;
-    if (m > 0 && kdim > (1LL << 44) / m) return fail(NNC_EINVAL, std::string(fn) + ": size too large");
-    return NNC_OK;
-}
-
 template <int BITS, int VB, int MT>
 static void launch_pg_dx(dim3 grid, size_t lds, hipStream_t s, const float *g, int m, long long kdim, const unsigned char *packed, long long row_bytes,
                          long long ncols, const float *centers, int k, long long rpg, int direct, float *out)

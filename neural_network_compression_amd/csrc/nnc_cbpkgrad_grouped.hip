@@ -1,0 +1,550 @@
+// nnc_cbpkgrad_grouped.hip -- the backward pass of the group-wise codebook matmul on 2- and 4-bit packed indices (nnc_cbpk_grouped.hip)
+// from the (G, K) codebooks and the packed buffer of the whole index matrix: the indices are never unpacked, W and dW never built
+// (include/nnc_cbpkgrad_grouped.h, nnc_cbpk_grouped_dx_f32 / nnc_cbpk_grouped_dc_f32).
+// W[i, o] = c[i / group_rows][L[i, o]], L read from the packed rows, y = x @ W, g = dL/dy:
+//
+//   dx[r, i]  = sum_o g[r, o] * c[i / group_rows][L[i, o]]       a label >= K reads 0; a column past ncols forms no product
+//   dc[q, k]  = sum_{(i, o): i / group_rows = q, L[i, o] = k} sum_r x[r, i] * g[r, o]   G x K bins; a padding field falls into none
+//
+// The plans are the ungrouped packed ones (pg_dx_plan, pg_dc_plan of nnc_cbpkgrad.hpp), so the path, the grids, the splits, the
+// order in which every sum is formed and the shift S of the dc sums are those of nnc_cbpk_dx_f32 / nnc_cbpk_dc_f32 on the same
+// shape.  The kernels are the ungrouped ones (nnc_cbpkgrad.hip) with the walk through the groups added; they are kernels of their
+// own for the reason nnc_cbmm_grouped.hip gives (a shared body changes the instruction streams of the old instantiations).
+//   k_cbpkdx_stream_grouped  m <= 16.  k_cbpkdx_stream with the per-wave table of k_cbpk_stream_grouped: every wave walks its own
+//                            rows in stretches cut at the group's end and rewrites its table from the centres its lanes hold,
+//                            loaded while the stretch before ran.  No workgroup barrier.
+//   k_cbpkdx_tiled_grouped   m > 16.  k_cbpkdx_tiled with the up to four tables of the groups a 128-row tile lies in, loaded
+//                            once; a thread decodes one index row throughout, so it keeps a pointer to that row's table.
+//   k_cbpkdc_stream_grouped  m <= 16.  k_cbpkdc_stream with the workgroup walk of k_cbdc_stream_grouped: the [K][64] bins are
+//                            one group's, flushed into sums + q * K and cleared at every boundary.
+//   k_cbpkdc_tiled_grouped   m > 16.  k_cbpkdc_tiled with the per-group sets of k_cbdc_tiled_grouped: a wave's 32 index rows lie
+//                            in one group, one binning pass, one flush per set; LDS unchanged.
+// The integer sums are exact, so neither walk changes a bit of dc; which wave takes a row changes no bit of dx.  Everything that
+// steers a walk comes from blockIdx, the kernel arguments and the readfirstlane'd wave number: every wave of a workgroup reaches
+// every barrier, and no cross-lane read sits in a lane-dependent branch.
+// k_cbgrad_absmax, k_cbgrad_reduce and k_cbdc_finish (over G * K bins) are nnc_cbgrad.hip's.  No float atomics; no host read.
+#include "nnc_cbpkgrad.hpp"
+
+// ------------------------------------------------------------------ dx, m <= 16
+// k_cbpkdx_stream with centers[groups][k]: grid (column blocks, row groups), CB_THREADS threads, the same `out`.  LDS: one table
+// per wave, [CB_WAVES][2^BITS][PK_COPIES].  A wave's rows (the share k_cbpkdx_stream gives it) are walked in stretches cut at the
+// group's end, each a run of batches of CB_UNROLL rows and then single rows: a row's sum does not depend on the batch it is in.
+template <int BITS, int VB, int MT>
+__global__ __launch_bounds__(CB_THREADS) void k_cbpkdx_stream_grouped(const float *__restrict__ g, int m, long long kdim, const unsigned char *__restrict__ packed,
+                                                                      long long row_bytes, long long ncols, const float *__restrict__ centers, int k,
+                                                                      long long rows_per_group, long long group_rows, int direct, float *__restrict__ out)
+{
+    constexpr int E = 8 * VB / BITS, N = VB >= 4 ? VB / 4 : 1, PER = 32 / BITS, ENTRIES = 1 << BITS;
+    constexpr uint32_t MASK = (1u << BITS) - 1;
+    static_assert(E * MT <= PKG_G, "g values per lane");
+    extern __shared__ float smem[];
+
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    float *cb = smem + wave * (ENTRIES * PK_COPIES);    // this wave's table: [ENTRIES][PK_COPIES]
+    const long long c0 = (long long)blockIdx.x * (64 * E) + lane * E;
+    const bool active = c0 < ncols;                     // then the lane's VB bytes lie inside the padded row
+    const int ne = (int)std::max(0LL, std::min((long long)E, ncols - c0));   // the lane's columns inside the matrix
+    float gv[MT][E];
+#pragma unroll
+    for (int r = 0; r < MT; ++r)
+#pragma unroll
+        for (int e = 0; e < E; ++e) gv[r][e] = (r < m && e < ne) ? g[(long long)r * ncols + c0 + e] : 0.0f;
+
+    const long long g_lo = (long long)blockIdx.y * rows_per_group, g_hi = std::min(kdim, g_lo + rows_per_group);
+    const long long per_wave = (g_hi - g_lo + CB_WAVES - 1) / CB_WAVES;
+    const long long i0 = std::min(g_hi, g_lo + wave * per_wave), i1 = std::min(g_hi, i0 + per_wave);
+    const unsigned char *mine = packed + (active ? (long long)blockIdx.x * (64 * VB) + lane * VB : 0LL);
+    const char *tab = reinterpret_cast<const char *>(cb) + ((lane & (PK_COPIES - 1)) << 2);
+    float *dst = direct ? out : out + (long long)blockIdx.x * m * kdim;
+
+    // lane j holds centre j of group q; 0 from k on
+    auto centre = [&](long long q) {
+        const float c = centers[q * k + std::min(lane, k - 1)];
+        return lane < k ? c : 0.0f;
+    };
+    // the wave's table from the centres its lanes hold: word t * 64 + lane is copy lane & 31 of entry 2 t + (lane >> 5)
+    auto fill = [&](float cv) {
+#pragma unroll
+        for (int t = 0; t < ENTRIES / 2; ++t) {
+            const int lo = __builtin_amdgcn_readlane(__builtin_bit_cast(int, cv), 2 * t);
+            const int hi = __builtin_amdgcn_readlane(__builtin_bit_cast(int, cv), 2 * t + 1);
+            cb[t * 64 + lane] = __builtin_bit_cast(float, lane < 32 ? lo : hi);
+        }
+        __builtin_amdgcn_wave_barrier();                // the lookups below read what other lanes of this wave wrote
+    };
+    auto consume = [&](const uint32_t *w, long long i) {
+        float p[MT];
+#pragma unroll
+        for (int r = 0; r < MT; ++r) p[r] = 0.0f;
+#pragma unroll
+        for (int e = 0; e < E; ++e) {
+            constexpr int SH = 7;                                        // entry l of this lane's copy at byte l << 7
+            const int bit = BITS * (e % PER);
+            const uint32_t d = w[e / PER];
+            const uint32_t a = (bit >= SH ? d >> (bit - SH) : d << (SH - bit)) & (MASK << SH);
+            const float wv = e < ne ? *reinterpret_cast<const float *>(tab + a) : 0.0f;   // (columns past the row: no Inf * 0)
+#pragma unroll
+            for (int r = 0; r < MT; ++r) p[r] = __builtin_fmaf(gv[r][e], wv, p[r]);
+        }
+        int row;
+        const float v = wave_reduce_rows<MT>(p, lane, row);
+        if ((lane & (64 / MT - 1)) == 0 && row < m) dst[(long long)row * kdim + i] = v;
+    };
+
+    if (i0 >= i1) return;                               // uniform over the wave; the kernel has no workgroup barrier
+    long long group = i0 / group_rows;
+    float cv = centre(group);
+    long long i = i0;
+    for (;;) {
+        const long long e1 = std::min(i1, (group + 1) * group_rows);   // the end of the stretch: the group's or the wave's
+        fill(cv);                                       // the lookups of the stretch before were issued ahead of these writes
+        if (e1 < i1) cv = centre(group + 1);            // the next group's centres arrive while this stretch runs
+        for (; i + CB_UNROLL <= e1; i += CB_UNROLL) {
+            uint32_t w[CB_UNROLL][N];
+#pragma unroll
+            for (int u = 0; u < CB_UNROLL; ++u) pk_load<VB>(mine + (i + u) * row_bytes, w[u]);
+#pragma unroll
+            for (int u = 0; u < CB_UNROLL; ++u) consume(w[u], i + u);
+        }
+        for (; i < e1; ++i) {
+            uint32_t w[N];
+            pk_load<VB>(mine + i * row_bytes, w);
+            consume(w, i);
+        }
+        if (e1 >= i1) break;
+        ++group;
+        __builtin_amdgcn_wave_barrier();                // the stretch's lookups stay ahead of the next fill
+    }
+}
+
+// ------------------------------------------------------------------ dx, m > 16
+// k_cbpkdx_tiled with centers[groups][k]: the same grid, tile, decode and FMA order.  LDS holds `tables` tables of 2^BITS entries
+// (zeros from k on), table t that of group n0 / group_rows + t; index row n0 + lr reads the one its group has.
+template <int BITS>
+__global__ __launch_bounds__(256) void k_cbpkdx_tiled_grouped(const float *__restrict__ g, long long m, long long kdim, const unsigned char *__restrict__ packed,
+                                                              long long row_bytes, long long ncols, const float *__restrict__ centers, int k,
+                                                              long long col_tiles, long long cols_per_split, long long group_rows, int tables, int direct,
+                                                              float *__restrict__ out)
+{
+    constexpr int ENTRIES = 1 << BITS;
+    constexpr uint32_t MASK = (1u << BITS) - 1;
+    extern __shared__ float smem[];
+    float *gs = smem;                      // [TB_K][TB_M]: g[m0 + r, o]
+    float *ws = gs + TB_K * TB_M;          // [TB_K][TB_N]: W^T[o, n0 + i] = c[group of n0 + i][L[n0 + i, o]]
+    float *cb = ws + TB_K * TB_N;          // [tables][2^BITS]
+
+    const TbTile T = tb_tile(col_tiles, cols_per_split, ncols);
+    const long long q0 = T.n0 / group_rows, groups = (kdim + group_rows - 1) / group_rows;
+    for (int j = threadIdx.x; j < tables * ENTRIES; j += 256) {
+        const int t = j / ENTRIES, e = j % ENTRIES;
+        cb[j] = (e < k && q0 + t < groups) ? centers[(q0 + t) * k + e] : 0.0f;
+    }
+    float acc[8][8];
+    tb_clear(acc);
+
+    const int lr = threadIdx.x >> 1, lo = (threadIdx.x & 1) * 4;   // W^T tile: index row n0 + lr, o lo..lo+3 (as the g tile: row lr, o lo..lo+3)
+    const long long wi = T.n0 + lr;
+    const float *tab = cb + std::min((long long)tables - 1, wi / group_rows - q0) * ENTRIES;
+    for (long long ob = T.lo; ob < T.hi; ob += TB_K) {
+        __syncthreads();
+        tb_load_rows(gs, g, m, ncols, T.m0, ob, T.hi);
+        const long long bitpos = (ob + lo) * BITS;
+        const bool live = wi < kdim && ob + lo < T.hi;                 // then the dword lies inside the padded row
+        const uint32_t word = live ? *reinterpret_cast<const uint32_t *>(packed + wi * row_bytes + ((bitpos >> 5) << 2)) >> (bitpos & 31) : 0u;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) ws[(lo + j) * TB_N + lr] = (live && ob + lo + j < T.hi) ? tab[(word >> (BITS * j)) & MASK] : 0.0f;
+        __syncthreads();
+        tb_tile_fma(gs, ws, T.tx, T.ty, acc);
+    }
+#pragma unroll
+    for (int a = 0; a < 8; ++a)
+#pragma unroll
+        for (int b = 0; b < 8; ++b) tb_store_dx(acc[a][b], T.m0 + T.ty * 8 + a, T.n0 + T.tx * 8 + b, m, kdim, direct, out);
+}
+
+// ------------------------------------------------------------------ dc, m <= 16
+// k_cbpkdc_stream with sums[groups][k]: grid (column blocks, row groups), CB_THREADS threads.  LDS: one group's bins, [k][64]
+// int64, copy `lane` of every bin this lane's own.  The workgroup's rows are walked group by group as k_cbdc_stream_grouped walks
+// them: each stretch is divided among the four waves; at a boundary the bins go into the group's sums and are cleared by the
+// threads that have just read them, ahead of the barrier that opens the next stretch.  Every wave reaches every barrier.
+template <int BITS, int VB, int MT>
+__global__ __launch_bounds__(CB_THREADS) void k_cbpkdc_stream_grouped(const float *__restrict__ x, const float *__restrict__ g, int m, long long kdim,
+                                                                      const unsigned char *__restrict__ packed, long long row_bytes, long long ncols, int k,
+                                                                      int terms_log2, long long rows_per_group, long long group_rows,
+                                                                      uint32_t *__restrict__ hdr, unsigned long long *__restrict__ sums)
+{
+    constexpr int E = 8 * VB / BITS, N = VB >= 4 ? VB / 4 : 1, PER = 32 / BITS;
+    constexpr uint32_t MASK = (1u << BITS) - 1;
+    static_assert(E * MT <= PKG_G, "g values per lane");
+    extern __shared__ unsigned long long bins[];
+    int flag;
+    const int S = cbdc_shift(hdr, m, terms_log2, flag);
+    if (blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0) {
+        hdr[2] = (uint32_t)S;
+        hdr[3] = (uint32_t)flag;
+    }
+    if (flag != CBG_FLAG_OK) return;   // (uniform over the launch)
+    int scx, scg;
+    cbdc_scales(hdr, scx, scg);
+    const int Sw = S - scx - scg;      // the shift of dW' = dW * 2^(scx + scg)
+    for (int j = threadIdx.x; j < (k << PKG_RLOG2); j += CB_THREADS) bins[j] = 0ull;
+
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const long long c0 = (long long)blockIdx.x * (64 * E) + lane * E;
+    const bool active = c0 < ncols;
+    const int ne = (int)std::max(0LL, std::min((long long)E, ncols - c0));
+    float gv[MT][E];
+#pragma unroll
+    for (int r = 0; r < MT; ++r)
+#pragma unroll
+        for (int e = 0; e < E; ++e) gv[r][e] = g[cbdc_idx((long long)r * ncols + c0 + e, r < m && e < ne)];
+    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+    for (int r = 0; r < MT; ++r)
+#pragma unroll
+        for (int e = 0; e < E; ++e) gv[r][e] = cbdc_scaled(gv[r][e], r < m && e < ne, scg);
+
+    long long group = (long long)blockIdx.y * rows_per_group / group_rows;
+    const long long s_lo = (long long)blockIdx.y * rows_per_group, s_hi = std::min(kdim, s_lo + rows_per_group);
+    long long g_lo = s_lo, g_hi = std::min(s_hi, (group + 1) * group_rows);   // the rows of the workgroup that lie in `group`
+    long long per_wave = (g_hi - g_lo + CB_WAVES - 1) / CB_WAVES;
+    long long i0 = std::min(g_hi, g_lo + wave * per_wave), i1 = std::min(g_hi, i0 + per_wave);
+    const unsigned char *mine = packed + (active ? (long long)blockIdx.x * (64 * VB) + lane * VB : 0LL);
+    unsigned long long *mybins = bins + lane;
+    __syncthreads();
+
+    // x[r, i + u] of a batch of U rows: lane f holds value f = r * U + u (and f + 64), broadcast by v_readlane (as k_cbdc_stream)
+    auto load_x = [&](long long i, int U, float &xa, float &xb) {
+        const int f0 = lane, f1 = lane + 64;
+        const int r0 = f0 / U, r1 = f1 / U;
+        xa = cbdc_scaled(x[cbdc_idx((long long)r0 * kdim + i + f0 % U, r0 < m)], r0 < m, scx);
+        xb = MT * CB_UNROLL > 64 ? cbdc_scaled(x[cbdc_idx((long long)r1 * kdim + i + f1 % U, r1 < m)], r1 < m, scx) : 0.0f;
+    };
+    auto consume = [&](const uint32_t *w, float xa, float xb, int u, int U) {
+        float xv[MT];
+#pragma unroll
+        for (int r = 0; r < MT; ++r) {
+            const int f = r * U + u;
+            xv[r] = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, f < 64 ? xa : xb), f & 63));
+        }
+#pragma unroll
+        for (int e = 0; e < E; ++e) {
+            const uint32_t l = (w[e / PER] >> (BITS * (e % PER))) & MASK;
+            float d = 0.0f;
+#pragma unroll
+            for (int r = 0; r < MT; ++r) d = __builtin_fmaf(xv[r], gv[r][e], d);   // dW'[i, o], r ascending
+            if (e < ne && l < (uint32_t)k) atomicAdd(&mybins[l << PKG_RLOG2], cbdc_fix(d, Sw));
+        }
+    };
+
+    for (;;) {
+        long long i = i0;
+        for (; i + CB_UNROLL <= i1; i += CB_UNROLL) {
+            uint32_t w[CB_UNROLL][N];
+            float xa, xb;
+#pragma unroll
+            for (int u = 0; u < CB_UNROLL; ++u) pk_load<VB>(mine + (i + u) * row_bytes, w[u]);
+            load_x(i, CB_UNROLL, xa, xb);
+#pragma unroll
+            for (int u = 0; u < CB_UNROLL; ++u) consume(w[u], xa, xb, u, CB_UNROLL);
+        }
+        for (; i < i1; ++i) {
+            uint32_t w[N];
+            float xa, xb;
+            pk_load<VB>(mine + i * row_bytes, w);
+            load_x(i, 1, xa, xb);
+            consume(w, xa, xb, 0, 1);
+        }
+        cbdc_flush(bins, k, PKG_RLOG2, sums + group * k);   // (begins with a barrier: every wave has left the group's rows)
+        if (g_hi >= s_hi) break;                            // (s_hi and g_hi are the workgroup's: uniform)
+        for (int j = threadIdx.x; j < k; j += CB_THREADS)   // the copies this thread has just summed
+            for (int r = 0; r < (1 << PKG_RLOG2); ++r) bins[(j << PKG_RLOG2) + r] = 0ull;
+        g_lo = g_hi;
+        g_hi = std::min(s_hi, (++group + 1) * group_rows);
+        per_wave = (g_hi - g_lo + CB_WAVES - 1) / CB_WAVES;
+        i0 = std::min(g_hi, g_lo + wave * per_wave), i1 = std::min(g_hi, i0 + per_wave);
+        __syncthreads();
+    }
+}
+
+// ------------------------------------------------------------------ dc, m > 16
+// k_cbpkdc_tiled with sums[groups][k]: the same grid, tiles and FMA order.  The k << PKG_RLOG2 LDS bins are cut into
+// 1 << sets_log2 sets of k << (PKG_RLOG2 - sets_log2), set t for group m0 / group_rows + t.  Thread (tx, ty) bins index rows
+// m0 + ty * 8 .. + 7, which lie in one group, into that group's set; every set then goes into its group's sums.
+template <int BITS>
+__global__ __launch_bounds__(256) void k_cbpkdc_tiled_grouped(const float *__restrict__ x, const float *__restrict__ g, long long m, long long kdim,
+                                                              const unsigned char *__restrict__ packed, long long row_bytes, long long ncols, int k,
+                                                              int sets_log2, int terms_log2, long long col_tiles, long long rows_per_split,
+                                                              long long group_rows, uint32_t *__restrict__ hdr, unsigned long long *__restrict__ sums)
+{
+    constexpr uint32_t MASK = (1u << BITS) - 1;
+    extern __shared__ float smem[];
+    float *xs = smem;                      // [TB_K][TB_M]: x[r, i0 + i]
+    float *gs = xs + TB_K * TB_M;          // [TB_K][TB_N]: g[r, o0 + o]
+    unsigned long long *bins = reinterpret_cast<unsigned long long *>(gs + TB_K * TB_N);
+    int scx, scg, Sw;
+    if (!cbdc_begin(hdr, m, terms_log2, bins, k << PKG_RLOG2, scx, scg, Sw)) return;
+
+    const TbTile T = tb_tile(col_tiles, rows_per_split, m);   // n0: the first column o, m0: the first index row i
+    float acc[8][8];
+    tb_clear(acc);
+    for (long long rb = T.lo; rb < T.hi; rb += TB_K) {
+        __syncthreads();
+        cbdc_load_tiles(xs, gs, x, g, kdim, ncols, T.m0, T.n0, rb, T.hi, scx, scg);
+        __syncthreads();
+        tb_tile_fma(xs, gs, T.tx, T.ty, acc);
+    }
+    const int rl = PKG_RLOG2 - sets_log2, sets = 1 << sets_log2;
+    const long long q0 = T.m0 / group_rows, groups = (kdim + group_rows - 1) / group_rows;
+    const int set = (int)std::min((long long)sets - 1, (T.m0 + T.ty * 8) / group_rows - q0);
+    // the 8 labels of a thread's row are 8 * BITS bits of one packed dword (a tile starts on a multiple of 128 columns), which
+    // lies inside the padded row when its first column lies inside the matrix
+    cbdc_bin_tile(acc, T, kdim, ncols, k, Sw, bins + ((long long)set * k << rl), rl, threadIdx.x & ((1 << rl) - 1), [&](long long i, long long o) {
+        const long long bitpos = (o & ~7LL) * BITS;
+        const uint32_t word = *reinterpret_cast<const uint32_t *>(packed + i * row_bytes + ((bitpos >> 5) << 2)) >> (bitpos & 31);
+        return (word >> (BITS * (o & 7))) & MASK;
+    });
+    for (int t = 0; t < sets && q0 + t < groups; ++t) cbdc_flush(bins + ((long long)t * k << rl), k, rl, sums + (q0 + t) * k);
+}
+
+// ------------------------------------------------------------------ launches
+template <int BITS, int VB, int MT>
+static void launch_pgg_dx(dim3 grid, size_t lds, hipStream_t s, const float *g, int m, long long kdim, const unsigned char *packed, long long row_bytes,
+                          long long ncols, const float *centers, int k, long long rpg, long long group_rows, int direct, float *out)
+{
+    hipLaunchKernelGGL((k_cbpkdx_stream_grouped<BITS, VB, MT>), grid, dim3(CB_THREADS), lds, s, g, m, kdim, packed, row_bytes, ncols, centers, k, rpg, group_rows,
+                       direct, out);
+}
+
+template <int BITS, int VB, int MT>
+static void launch_pgg_dc(dim3 grid, size_t lds, hipStream_t s, const float *x, const float *g, int m, long long kdim, const unsigned char *packed,
+                          long long row_bytes, long long ncols, int k, int tl, long long rpg, long long group_rows, uint32_t *hdr, unsigned long long *sums)
+{
+    hipLaunchKernelGGL((k_cbpkdc_stream_grouped<BITS, VB, MT>), grid, dim3(CB_THREADS), lds, s, x, g, m, kdim, packed, row_bytes, ncols, k, tl, rpg, group_rows,
+                       hdr, sums);
+}
+
+// every stream instantiation of this unit: the (bits, vb, mt) of nnc_cbpkgrad.hip's table, so the plan leaves no shape out
+using PggDxLaunch = void (*)(dim3, size_t, hipStream_t, const float *, int, long long, const unsigned char *, long long, long long, const float *, int,
+                             long long, long long, int, float *);
+using PggDcLaunch = void (*)(dim3, size_t, hipStream_t, const float *, const float *, int, long long, const unsigned char *, long long, long long, int, int,
+                             long long, long long, uint32_t *, unsigned long long *);
+struct PggCase {
+    int bits, vb, mt;
+    PggDxLaunch dx;
+    PggDcLaunch dc;
+};
+#define PGG_CASE(B, V, M) {B, V, M, launch_pgg_dx<B, V, M>, launch_pgg_dc<B, V, M>}
+static const PggCase kPggCases[] = {
+    PGG_CASE(4, 16, 1), PGG_CASE(4, 8, 1), PGG_CASE(4, 4, 1), PGG_CASE(4, 16, 2), PGG_CASE(4, 8, 2), PGG_CASE(4, 4, 2), PGG_CASE(4, 8, 4),
+    PGG_CASE(4, 4, 4),  PGG_CASE(4, 4, 8), PGG_CASE(4, 2, 16),
+    PGG_CASE(2, 16, 1), PGG_CASE(2, 8, 1), PGG_CASE(2, 4, 1), PGG_CASE(2, 8, 2),  PGG_CASE(2, 4, 2), PGG_CASE(2, 4, 4), PGG_CASE(2, 2, 8),
+    PGG_CASE(2, 1, 16),
+};
+#undef PGG_CASE
+
+static const PggCase *find_pgg_case(int bits, int vb, int mt)
+{
+    for (const PggCase &c : kPggCases)
+        if (c.bits == bits && c.vb == vb && c.mt == mt) return &c;
+    return nullptr;
+}
+
+static int no_pgg_case(const char *fn, int bits, int vb, int mt)
+{
+    return fail(NNC_EINVAL, std::string(fn) + ": no grouped stream instantiation for bits " + std::to_string(bits) + ", vb " + std::to_string(vb) + ", mt " +
+                                std::to_string(mt));
+}
+
+// ------------------------------------------------------------------ C ABI
+// pg_check's checks, then those nnc_cbpk_grouped makes of group_rows and the bound on the G * k bins
+static int pgg_check(const char *fn, int64_t m, int64_t kdim, int64_t ncols, int bits, int32_t k, int64_t group_rows)
+{
+    const int rc = pg_check(fn, m, kdim, ncols, bits, k);
+    if (rc != NNC_OK) return rc;
+    if (group_rows < 32 || group_rows % 32) return fail(NNC_EINVAL, std::string(fn) + ": group_rows must be a positive multiple of 32");
+    if (group_rows > (1LL << 40)) return fail(NNC_EINVAL, std::string(fn) + ": size too large");
+    if (gg_groups(kdim, group_rows) * k > (1LL << 30)) return fail(NNC_EINVAL, std::string(fn) + ": more than 2^30 bins (groups * k)");
+    return NNC_OK;
+}
+
+// the dx LDS: one table per wave (stream), or the tile's images and one table per group of the tile (tiled)
+static void pgg_dx_lds(PgPlan &p, long long group_rows, int &tables)
+{
+    tables = 0;
+    if (p.path == NNC_CBMM_STREAM) {
+        tables = CB_WAVES;
+        p.lds = (long long)CB_WAVES * p.entries * PK_COPIES * 4;
+    } else if (p.path == NNC_CBMM_TILED) {
+        tables = tile_groups(group_rows);
+        p.lds += (long long)(tables - 1) * p.entries * 4;
+    }
+}
+
+// the five values a grouped plan adds to the ungrouped record
+static void pgg_plan_tail(const PgPlan &p, long long kdim, long long group_rows, int held, int64_t *out)
+{
+    const bool stream = p.path == NNC_CBMM_STREAM, tiled = p.path == NNC_CBMM_TILED;
+    out[0] = group_rows;
+    out[1] = kdim > 0 ? cdiv(kdim, group_rows) : 0;
+    out[2] = stream ? p.rows_per_group : 0;
+    out[3] = stream ? max_groups_per_split(p.row_tiles, p.rows_per_group, kdim, group_rows)
+                    : (tiled ? max_groups_per_split(cdiv(kdim, 128), 128, kdim, group_rows) : 0);
+    out[4] = held;
+}
+
+static int pgg_plan_out(const char *fn, const PgPlan &p, int bits, int32_t cus, const int64_t *out)
+{
+    if (cus < 1) return fail(NNC_EINVAL, std::string(fn) + ": cus < 1");
+    if (!out) return fail(NNC_EINVAL, std::string(fn) + ": out is NULL");
+    if (p.path == NNC_CBMM_STREAM && !find_pgg_case(bits, p.vb, p.mt)) return no_pgg_case(fn, bits, p.vb, p.mt);
+    return NNC_OK;
+}
+
+extern "C" int64_t nnc_cbpk_grouped_dx_workspace_bytes(int64_t m, int64_t kdim, int64_t ncols, int bits)
+{
+    if (pg_check("nnc_cbpk_grouped_dx_workspace_bytes", m, kdim, ncols, bits, 1) != NNC_OK) return 0;
+    return cbg_dx_ws_bytes(pg_dx_plan(m, kdim, ncols, bits, CB_PLAN_CUS).splits, m, kdim);
+}
+
+extern "C" int nnc_cbpk_grouped_dx_plan(int64_t m, int64_t kdim, int64_t ncols, int bits, int32_t k, int64_t group_rows, int32_t cus, int64_t *out)
+{
+    const char *fn = "nnc_cbpk_grouped_dx_plan";
+    int rc = pgg_check(fn, m, kdim, ncols, bits, k, group_rows);
+    if (rc != NNC_OK) return rc;
+    PgPlan p = pg_dx_plan(m, kdim, ncols, bits, std::max(cus, 1));
+    if ((rc = pgg_plan_out(fn, p, bits, cus, out)) != NNC_OK) return rc;
+    int tables;
+    pgg_dx_lds(p, group_rows, tables);
+    const int64_t v[NNC_CBPKDX_PLAN_LEN] = {p.path, p.vb, p.mt, p.cols, p.copies, p.entries, p.splits, p.per_split, p.lds, p.col_tiles, p.row_tiles,
+                                            cbg_dx_ws_bytes(p.splits, m, kdim)};
+    for (int i = 0; i < NNC_CBPKDX_PLAN_LEN; ++i) out[i] = v[i];
+    pgg_plan_tail(p, kdim, group_rows, tables, out + NNC_CBPKDX_PLAN_LEN);
+    return NNC_OK;
+}
+
+extern "C" int nnc_cbpk_grouped_dx_f32(const float *g, int64_t m, int64_t kdim, const void *packed, int64_t packed_bytes, int bits, int64_t ncols,
+                                       const float *centers_dev, int32_t k, int64_t group_rows, float *dx, void *workspace, int64_t workspace_bytes,
+                                       void *stream)
+{
+    const char *fn = "nnc_cbpk_grouped_dx_f32";
+    int rc = pgg_check(fn, m, kdim, ncols, bits, k, group_rows);
+    if (rc != NNC_OK) return rc;
+    if ((rc = pk_check_buffer(fn, packed, packed_bytes, kdim, ncols, bits)) != NNC_OK) return rc;
+    if (!centers_dev) return fail(NNC_EINVAL, "nnc_cbpk_grouped_dx_f32: centers is NULL");
+    if (m > 0 && kdim > 0 && !dx) return fail(NNC_EINVAL, "nnc_cbpk_grouped_dx_f32: dx is NULL");
+    if (m > 0 && kdim > 0 && ncols > 0 && !g) return fail(NNC_EINVAL, "nnc_cbpk_grouped_dx_f32: g is NULL");
+    const int64_t need = nnc_cbpk_grouped_dx_workspace_bytes(m, kdim, ncols, bits);
+    if ((rc = cb_check_workspace(fn, "nnc_cbpk_grouped_dx_workspace_bytes", workspace, workspace_bytes, need, 4, "workspace must be 4-byte aligned")) != NNC_OK)
+        return rc;
+    PgPlan p = pg_dx_plan(m, kdim, ncols, bits, CB_PLAN_CUS);
+    const PggCase *pc = p.path == NNC_CBMM_STREAM ? find_pgg_case(bits, p.vb, p.mt) : nullptr;
+    if (p.path == NNC_CBMM_STREAM && !pc) return no_pgg_case(fn, bits, p.vb, p.mt);
+    if (p.path == NNC_CBMM_NONE) return NNC_OK;
+
+    hipStream_t s = S(stream);
+    p = pg_dx_plan(m, kdim, ncols, bits, cu_count());        // (the row groups of this device)
+    if (p.path == NNC_CBMM_ZERO) {
+        HIPCHK(hipMemsetAsync(dx, 0, (size_t)(m * kdim) * 4, s));
+        return NNC_OK;
+    }
+    int tables;
+    pgg_dx_lds(p, group_rows, tables);
+    const int direct = p.splits == 1;
+    float *out = direct ? dx : reinterpret_cast<float *>(workspace);
+    const unsigned char *pk = reinterpret_cast<const unsigned char *>(packed);
+    const long long row_bytes = pk_row_bytes(ncols, bits);
+    if (p.path == NNC_CBMM_STREAM) {
+        pc->dx(dim3((unsigned)p.col_tiles, (unsigned)p.row_tiles), (size_t)p.lds, s, g, (int)m, kdim, pk, row_bytes, ncols, centers_dev, k, p.rows_per_group,
+               group_rows, direct, out);
+        LAUNCHCHK("k_cbpkdx_stream_grouped");
+    } else {
+        const dim3 grid((unsigned)(p.col_tiles * p.row_tiles), (unsigned)p.splits);
+        if (bits == 4)
+            hipLaunchKernelGGL(k_cbpkdx_tiled_grouped<4>, grid, dim3(256), (size_t)p.lds, s, g, (long long)m, (long long)kdim, pk, row_bytes, (long long)ncols,
+                               centers_dev, (int)k, p.col_tiles, p.per_split, (long long)group_rows, tables, direct, out);
+        else
+            hipLaunchKernelGGL(k_cbpkdx_tiled_grouped<2>, grid, dim3(256), (size_t)p.lds, s, g, (long long)m, (long long)kdim, pk, row_bytes, (long long)ncols,
+                               centers_dev, (int)k, p.col_tiles, p.per_split, (long long)group_rows, tables, direct, out);
+        LAUNCHCHK("k_cbpkdx_tiled_grouped");
+    }
+    if (!direct) return cbgrad_reduce(reinterpret_cast<const float *>(workspace), p.splits, m * kdim, dx, s);
+    return NNC_OK;
+}
+
+extern "C" int64_t nnc_cbpk_grouped_dc_workspace_bytes(int64_t m, int64_t kdim, int64_t ncols, int bits, int32_t k, int64_t group_rows)
+{
+    if (pgg_check("nnc_cbpk_grouped_dc_workspace_bytes", m, kdim, ncols, bits, k, group_rows) != NNC_OK) return 0;
+    PgPlan p;
+    if (pg_dc_plan(m, kdim, ncols, bits, k, CB_PLAN_CUS, p) != NNC_OK) return 0;
+    return cbg_dc_ws_bytes(p.path, (int)(gg_groups(kdim, group_rows) * k));
+}
+
+extern "C" int nnc_cbpk_grouped_dc_plan(int64_t m, int64_t kdim, int64_t ncols, int bits, int32_t k, int64_t group_rows, int32_t cus, int64_t *out)
+{
+    const char *fn = "nnc_cbpk_grouped_dc_plan";
+    int rc = pgg_check(fn, m, kdim, ncols, bits, k, group_rows);
+    if (rc != NNC_OK) return rc;
+    PgPlan p;
+    if ((rc = pg_dc_plan(m, kdim, ncols, bits, k, std::max(cus, 1), p)) != NNC_OK) return rc;
+    if ((rc = pgg_plan_out(fn, p, bits, cus, out)) != NNC_OK) return rc;
+    const bool tiled = p.path == NNC_CBMM_TILED;
+    const int sets = tiled ? tile_groups(group_rows) : (p.path == NNC_CBMM_STREAM ? 1 : 0);
+    const int64_t v[NNC_CBPKDC_PLAN_LEN] = {p.path, p.vb, p.mt, p.cols, p.path == NNC_CBMM_ZERO ? 0 : p.copies / std::max(sets, 1), p.splits, p.per_split,
+                                            p.lds, p.col_tiles, p.row_tiles, p.terms_log2,
+                                            cbg_dc_ws_bytes(p.path, (int)(gg_groups(kdim, group_rows) * k))};
+    for (int i = 0; i < NNC_CBPKDC_PLAN_LEN; ++i) out[i] = v[i];
+    pgg_plan_tail(p, kdim, group_rows, sets, out + NNC_CBPKDC_PLAN_LEN);
+    return NNC_OK;
+}
+
+extern "C" int nnc_cbpk_grouped_dc_f32(const float *x, const float *g, int64_t m, int64_t kdim, const void *packed, int64_t packed_bytes, int bits,
+                                       int64_t ncols, int32_t k, int64_t group_rows, void *dc, int32_t out_f64, void *workspace, int64_t workspace_bytes,
+                                       void *stream)
+{
+    const char *fn = "nnc_cbpk_grouped_dc_f32";
+    int rc = pgg_check(fn, m, kdim, ncols, bits, k, group_rows);
+    if (rc != NNC_OK) return rc;
+    if ((rc = pk_check_buffer(fn, packed, packed_bytes, kdim, ncols, bits)) != NNC_OK) return rc;
+    if (!dc) return fail(NNC_EINVAL, "nnc_cbpk_grouped_dc_f32: dc is NULL");
+    if (m > 0 && kdim > 0 && ncols > 0 && (!x || !g)) return fail(NNC_EINVAL, "nnc_cbpk_grouped_dc_f32: x or g is NULL");
+    PgPlan p;
+    if ((rc = pg_dc_plan(m, kdim, ncols, bits, k, CB_PLAN_CUS, p)) != NNC_OK) return rc;
+    const int nbins = (int)(gg_groups(kdim, group_rows) * k);
+    const int64_t need = cbg_dc_ws_bytes(p.path, nbins);
+    if ((rc = cb_check_workspace(fn, "nnc_cbpk_grouped_dc_workspace_bytes", workspace, workspace_bytes, need, 8, "workspace not 8-byte aligned")) != NNC_OK)
+        return rc;
+    const PggCase *pc = p.path == NNC_CBMM_STREAM ? find_pgg_case(bits, p.vb, p.mt) : nullptr;
+    if (p.path == NNC_CBMM_STREAM && !pc) return no_pgg_case(fn, bits, p.vb, p.mt);
+
+    hipStream_t s = S(stream);
+    if (p.path == NNC_CBMM_ZERO) {
+        HIPCHK(hipMemsetAsync(dc, 0, (size_t)nbins * (out_f64 ? 8 : 4), s));
+        return NNC_OK;
+    }
+    if ((rc = pg_dc_plan(m, kdim, ncols, bits, k, cu_count(), p)) != NNC_OK) return rc;   // (the row groups of this device)
+    const unsigned char *pk = reinterpret_cast<const unsigned char *>(packed);
+    const long long row_bytes = pk_row_bytes(ncols, bits);
+    uint32_t *hdr = reinterpret_cast<uint32_t *>(workspace);
+    unsigned long long *sums = reinterpret_cast<unsigned long long *>(reinterpret_cast<char *>(workspace) + CBG_HDR_BYTES);
+    HIPCHK(hipMemsetAsync(workspace, 0, (size_t)need, s));
+    if ((rc = cbgrad_absmax(x, m * kdim, g, m * ncols, hdr, s)) != NNC_OK) return rc;
+    if (p.path == NNC_CBMM_STREAM) {
+        pc->dc(dim3((unsigned)p.col_tiles, (unsigned)p.row_tiles), (size_t)p.lds, s, x, g, (int)m, kdim, pk, row_bytes, ncols, k, p.terms_log2,
+               p.rows_per_group, group_rows, hdr, sums);
+        LAUNCHCHK("k_cbpkdc_stream_grouped");
+    } else {
+        const int sets_log2 = __builtin_ctz(tile_groups(group_rows));
+        const dim3 grid((unsigned)(p.col_tiles * p.row_tiles), (unsigned)p.splits);
+        if (bits == 4)
+            hipLaunchKernelGGL(k_cbpkdc_tiled_grouped<4>, grid, dim3(256), (size_t)p.lds, s, x, g, (long long)m, (long long)kdim, pk, row_bytes, (long long)ncols,
+                               (int)k, sets_log2, p.terms_log2, p.col_tiles, p.per_split, (long long)group_rows, hdr, sums);
+        else
+            hipLaunchKernelGGL(k_cbpkdc_tiled_grouped<2>, grid, dim3(256), (size_t)p.lds, s, x, g, (long long)m, (long long)kdim, pk, row_bytes, (long long)ncols,
+                               (int)k, sets_log2, p.terms_log2, p.col_tiles, p.per_split, (long long)group_rows, hdr, sums);
+        LAUNCHCHK("k_cbpkdc_tiled_grouped");
+    }
+    return cbdc_finish(hdr, reinterpret_cast<const long long *>(sums), nbins, (int)(out_f64 != 0), dc, s);
+}

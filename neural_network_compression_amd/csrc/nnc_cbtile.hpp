@@ -1,7 +1,7 @@
 // nnc_cbtile.hpp -- what every tiled (m > 16) float32 codebook kernel repeats, written once: the byte form (k_cbmm_tiled,
 // k_cbdx_tiled, k_cbdc_tiled), the packed form (k_cbpk_tiled, k_cbpkdx_tiled, k_cbpkdc_tiled), the bitmap-sparse form
 // (k_cbsp_tiled, k_cbspdx_tiled, k_cbspdc_tiled), the group-wise forward pass (k_cbmm_tiled_grouped) and the group-wise backward
-// pass (k_cbdx_tiled_grouped, k_cbdc_tiled_grouped).  A kernel keeps its
+// passes (k_cbdx_tiled_grouped, k_cbdc_tiled_grouped; k_cbpkdx_tiled_grouped, k_cbpkdc_tiled_grouped).  A kernel keeps its
 // LDS layout, its table and the decode of its W tile (where a weight's label comes from) and calls these for the rest: the
 // tile coordinates, the x / g tile loads, the dc prologue and scaled tile fill, the stores and the dc binning loop.  The FMA
 // step itself is tb_tile_fma (nnc_cbmm.hpp).  256 threads; grid (column tiles * row tiles, splits).  The sparse kernels keep

@@ -1062,6 +1062,92 @@ def packed_codebook_linear(x: torch.Tensor, codes: PackedCodes, centers: torch.T
                                  lambda x2, g2, cd, c: packed_codebook_centroid_grad(x2, g2, cd, dtype=torch.float32))
 
 
+def _grouped_packed_args(codes, centers: torch.Tensor, group_rows: int) -> int:
+    """The grouped packed form's checks of the codes, the (G, K) centres and group_rows -> G, as the layers count it (>= 1)."""
+    if not isinstance(codes, PackedCodes):
+        raise TypeError("codes must be a PackedCodes (ops.pack_codes)")
+    if group_rows < 32 or group_rows % 32:
+        raise ValueError(f"group_rows must be a positive multiple of 32, got {group_rows}")
+    groups = max(-(-codes.kdim // group_rows), 1)
+    if centers is not None and (centers.dim() != 2 or tuple(centers.shape) != (groups, codes.k)):
+        raise ValueError(f"centers must have shape ({groups}, {codes.k}) for kdim {codes.kdim}, group_rows {group_rows} and codes of k = {codes.k}, "
+                         f"got {tuple(centers.shape)}")
+    return groups
+
+
+def grouped_packed_codebook_matmul_dx(g: torch.Tensor, codes: PackedCodes, centers: torch.Tensor, group_rows: int) -> torch.Tensor:
+    """dx = g @ W^T with W[i, o] = centers[i // group_rows][label (i, o)] read from the 2- or 4-bit packed indices
+    (include/nnc_cbpkgrad_grouped.h, nnc_cbpk_grouped_dx_f32): the input gradient of
+    grouped_packed_codebook_matmul.  g: float32 (..., ncols); codes, centers (G, K) and group_rows as grouped_packed_codebook_matmul.
+    Returns float32 (..., kdim); the columns of a group are, bit for bit, those packed_codebook_matmul_dx gives with that group's
+    table.  No host read."""
+    group_rows = int(group_rows)
+    _require_cuda(centers, "centers", torch.float32)
+    _require_cuda(g, "g", torch.float32)
+    _grouped_packed_args(codes, centers, group_rows)
+    lead, m = _rows(g, "g", codes.ncols)
+    _one_device("g, codes and centers", g, codes.packed, centers)
+    L = nat.load()
+    kdim, ncols, bits = codes.kdim, codes.ncols, codes.bits
+    dx = torch.empty(lead + (kdim,), dtype=torch.float32, device=g.device)
+    ws_bytes = int(L.nnc_cbpk_grouped_dx_workspace_bytes(m, kdim, ncols, bits))
+    ws = _workspace(ws_bytes, g.device)
+    nat.check(L.nnc_cbpk_grouped_dx_f32(_ptr(g), m, kdim, _ptr(codes.packed), codes.nbytes, bits, ncols, _ptr(centers), codes.k, group_rows, _ptr(dx),
+                                        _ptr(ws), ws_bytes, _stream(g)))
+    return dx
+
+
+def grouped_packed_codebook_centroid_grad(x: torch.Tensor, g: torch.Tensor, codes: PackedCodes, group_rows: int, dtype=torch.float64) -> torch.Tensor:
+    """dc[q, j] = sum over the (i, o) with i // group_rows = q whose label is j of (x^T g)[i, o] (include/nnc_cbpkgrad_grouped.h,
+    nnc_cbpk_grouped_dc_f32): bit for bit grouped_codebook_centroid_grad(x, g, codes.to_dense(), codes.k, ...), the indices never
+    unpacked and dW never written.  x: float32 (..., kdim), g: float32 (..., ncols) with the same leading shape.  Returns ``dtype``
+    (float64 or float32) (G, codes.k).  No host read."""
+    group_rows = int(group_rows)
+    _require_cuda(x, "x", torch.float32)
+    _require_cuda(g, "g", torch.float32)
+    groups = _grouped_packed_args(codes, None, group_rows)
+    kdim, ncols, k, bits = codes.kdim, codes.ncols, codes.k, codes.bits
+    lead, m = _rows(g, "g", ncols)
+    _dc_args(x, lead, kdim, "x, g and codes", codes.packed, g, dtype)
+    L = nat.load()
+    dc = torch.empty((groups, k), dtype=dtype, device=x.device)
+    ws_bytes = int(L.nnc_cbpk_grouped_dc_workspace_bytes(m, kdim, ncols, bits, k, group_rows))
+    ws = _workspace(ws_bytes, x.device)
+    nat.check(L.nnc_cbpk_grouped_dc_f32(_ptr(x), _ptr(g), m, kdim, _ptr(codes.packed), codes.nbytes, bits, ncols, k, group_rows, _ptr(dc),
+                                        1 if dtype == torch.float64 else 0, _ptr(ws), ws_bytes, _stream(x)))
+    return dc
+
+
+def cbpk_grouped_dx_plan(m: int, kdim: int, ncols: int, bits: int, k: int, group_rows: int, cus: int) -> dict:
+    """Host: the plan nnc_cbpk_grouped_dx_f32 follows on a device with ``cus`` compute units (include/nnc_cbpkgrad_grouped.h,
+    nnc_cbpk_grouped_dx_plan), as a dict keyed by _native.CBPKDX_GROUPED_PLAN_FIELDS.  No device needed."""
+    return _plan(nat.load().nnc_cbpk_grouped_dx_plan, nat.CBPKDX_GROUPED_PLAN_FIELDS, m, kdim, ncols, bits, k, group_rows, cus)
+
+
+def cbpk_grouped_dc_plan(m: int, kdim: int, ncols: int, bits: int, k: int, group_rows: int, cus: int) -> dict:
+    """Host: the plan nnc_cbpk_grouped_dc_f32 follows on a device with ``cus`` compute units (include/nnc_cbpkgrad_grouped.h,
+    nnc_cbpk_grouped_dc_plan), as a dict keyed by _native.CBPKDC_GROUPED_PLAN_FIELDS.  No device needed."""
+    return _plan(nat.load().nnc_cbpk_grouped_dc_plan, nat.CBPKDC_GROUPED_PLAN_FIELDS, m, kdim, ncols, bits, k, group_rows, cus)
+
+
+def grouped_packed_codebook_linear(x: torch.Tensor, codes: PackedCodes, centers: torch.Tensor, group_rows: int, bias: torch.Tensor | None = None,
+                                   relu: bool = False) -> torch.Tensor:
+    """grouped_packed_codebook_matmul with gradients for x, centers (G, K) and bias, through the autograd Function of codebook_linear.
+    The forward is the same float32 nnc_cbpk_grouped call (under no_grad the bits of grouped_packed_codebook_matmul, which stays
+    inference only); the backward runs grouped_packed_codebook_matmul_dx only if x needs a gradient and
+    grouped_packed_codebook_centroid_grad (float32) only if centers does.  The ReLU mask and the bias gradient are codebook_linear's.
+    The indices get no gradient.  No host read."""
+    if not isinstance(codes, PackedCodes):
+        raise TypeError("codes must be a PackedCodes (ops.pack_codes)")
+    _require_f32_x(x, "grouped_packed_codebook_linear")
+    group_rows = int(group_rows)
+    return _CodebookLinear.apply(
+        x, codes, centers, bias, bool(relu), codes.kdim, codes.ncols,
+        lambda x2, cd, c, b, r: grouped_packed_codebook_matmul(x2, cd, c, group_rows, bias=b, relu=r),
+        lambda g2, cd, c: grouped_packed_codebook_matmul_dx(g2, cd, c, group_rows),
+        lambda x2, g2, cd, c: grouped_packed_codebook_centroid_grad(x2, g2, cd, group_rows, dtype=torch.float32))
+
+
 def huffman_lengths(counts) -> tuple:
     """Host: (lengths uint8[k], hist int64[max_len+1], total_bits) from an index histogram."""
     L = nat.load()
