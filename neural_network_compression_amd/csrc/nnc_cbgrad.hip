@@ -22,7 +22,9 @@
 //   from k_cbgrad_absmax on the device, the dc kernel derives S itself and writes it next to the sums, and k_cbdc_finish writes
 //   dc = ldexp(sum, -S).  No host read anywhere.
 // An index >= K reads 0 in dx and falls into no bin in dc, as in the forward pass.  No float atomics.
-// The plans (CgPlan, dx_plan, dc_plan) and cg_check are in nnc_cbgrad.hpp, where nnc_cbgrad_grouped.hip finds them too.
+// The plans (CgPlan, dx_plan, dc_plan) and cg_check are in nnc_cbgrad.hpp, where nnc_cbgrad_grouped.hip finds them too; so are the
+// sequences of HIP calls of the two entry points (cbg_run_dx, cbg_run_dc) and the list of stream instantiations.  The label row
+// loads (cb_row_words) are nnc_cbmm.hpp's, the x load of k_cbdc_stream (cbdc_load_x) nnc_cbgrad.hpp's.
 #include "nnc_cbtile.hpp"
 
 // ------------------------------------------------------------------ max |x|, max |g|
@@ -87,21 +89,7 @@ __global__ __launch_bounds__(CB_THREADS) void k_cbdx_stream(const float *__restr
     float *dst = direct ? out : out + (long long)blockIdx.x * m * kdim;
     __syncthreads();
 
-    auto row_words = [&](long long i, uint32_t *w, uint32_t &s) {
-        const uintptr_t row = base + (uintptr_t)(i * row_bytes);
-        if constexpr (ALIGNED) {
-            s = 0;
-            load_chunk<VB>(reinterpret_cast<const unsigned char *>(active ? row + lane_off : row), w);
-        } else {
-            const uintptr_t first = row & ~(uintptr_t)(VB - 1);
-            s = (uint32_t)(__builtin_amdgcn_readfirstlane((uint32_t)((row + blockIdx.x * (64 * VB)) & (VB - 1))));
-            const uintptr_t a = ((row + lane_off) & ~(uintptr_t)(VB - 1));
-            const uintptr_t a0 = active ? a : first;
-            const uintptr_t a1 = (active && a + VB < row + row_bytes) ? a + VB : a0;
-            load_chunk<VB>(reinterpret_cast<const unsigned char *>(a0), w);
-            load_chunk<VB>(reinterpret_cast<const unsigned char *>(a1), w + N);
-        }
-    };
+    auto row_words = [&](long long i, uint32_t *w, uint32_t &s) { cb_row_words<VB, ALIGNED>(base, row_bytes, lane_off, active, i, w, s); };
     auto consume = [&](const uint32_t *w, uint32_t s, long long i) {
         uint32_t o[N];
         if constexpr (ALIGNED) {
@@ -233,28 +221,8 @@ __global__ __launch_bounds__(CB_THREADS) void k_cbdc_stream(const float *__restr
     const long long lane_off = (long long)blockIdx.x * (64 * VB) + lane * VB;
     __syncthreads();
 
-    auto row_words = [&](long long i, uint32_t *w, uint32_t &s) {
-        const uintptr_t row = base + (uintptr_t)(i * row_bytes);
-        if constexpr (ALIGNED) {
-            s = 0;
-            load_chunk<VB>(reinterpret_cast<const unsigned char *>(active ? row + lane_off : row), w);
-        } else {
-            const uintptr_t first = row & ~(uintptr_t)(VB - 1);
-            s = (uint32_t)(__builtin_amdgcn_readfirstlane((uint32_t)((row + blockIdx.x * (64 * VB)) & (VB - 1))));
-            const uintptr_t a = ((row + lane_off) & ~(uintptr_t)(VB - 1));
-            const uintptr_t a0 = active ? a : first;
-            const uintptr_t a1 = (active && a + VB < row + row_bytes) ? a + VB : a0;
-            load_chunk<VB>(reinterpret_cast<const unsigned char *>(a0), w);
-            load_chunk<VB>(reinterpret_cast<const unsigned char *>(a1), w + N);
-        }
-    };
-    // x[r, i + u] of a batch of U rows: lane f holds value f = r * U + u (and f + 64), broadcast by v_readlane (as k_cbmm_stream)
-    auto load_x = [&](long long i, int U, float &xa, float &xb) {
-        const int f0 = lane, f1 = lane + 64;
-        const int r0 = f0 / U, r1 = f1 / U;
-        xa = cbdc_scaled(x[cbdc_idx((long long)r0 * kdim + i + f0 % U, r0 < m)], r0 < m, scx);
-        xb = MT * CB_UNROLL > 64 ? cbdc_scaled(x[cbdc_idx((long long)r1 * kdim + i + f1 % U, r1 < m)], r1 < m, scx) : 0.0f;
-    };
+    auto row_words = [&](long long i, uint32_t *w, uint32_t &s) { cb_row_words<VB, ALIGNED>(base, row_bytes, lane_off, active, i, w, s); };
+    auto load_x = [&](long long i, int U, float &xa, float &xb) { cbdc_load_x<MT>(x, kdim, m, scx, lane, i, U, xa, xb); };
     auto consume = [&](const uint32_t *w, uint32_t s, float xa, float xb, int u, int U) {
         float xv[MT];
 #pragma unroll
@@ -340,7 +308,7 @@ __global__ __launch_bounds__(256) void k_cbdc_finish(const uint32_t *__restrict_
     }
 }
 
-// ------------------------------------------------------------------ the launches nnc_cbspgrad.hip shares (nnc_cbgrad.hpp)
+// ------------------------------------------------------------------ the launches every backward unit shares (nnc_cbgrad.hpp)
 int cbgrad_absmax(const float *x, long long nx, const float *g, long long ng, uint32_t *amax, hipStream_t s)
 {
     const int agrid = (int)std::max(1LL, std::min(cdiv(std::max(nx, ng), 256 * 8), 4LL * cu_count()));
@@ -387,43 +355,22 @@ static void launch_dc_stream(bool aligned, dim3 grid, size_t lds, hipStream_t s,
         hipLaunchKernelGGL((k_cbdc_stream<LT, VB, MT, false>), grid, dim3(CB_THREADS), lds, s, x, g, m, kdim, lab, ncols, k, rlog2, tl, rpg, hdr, sums);
 }
 
-// every stream instantiation there is; the plans are checked against this table, and the launches go through it
+// every stream instantiation there is (the lists of nnc_cbgrad.hpp); the plans are checked against this table, and the launches go through it
 using DxLaunch = void (*)(bool, dim3, size_t, hipStream_t, const float *, int, long long, const void *, long long, const float *, int, int, int, long long,
                           int, float *);
 using DcLaunch = void (*)(bool, dim3, size_t, hipStream_t, const float *, const float *, int, long long, const void *, long long, int, int, int, long long,
                           uint32_t *, unsigned long long *);
 struct GradCase {
-    int lb, vb, mt;
+    int a, vb, mt;            // a: label_bytes
     DxLaunch dx;
     DcLaunch dc;
 };
-#define GRAD_CASE(LT, LB, VB, MT) {LB, VB, MT, launch_dx_stream<LT, VB, MT>, launch_dc_stream<LT, VB, MT>}
-static const GradCase kGradCases[] = {
-    GRAD_CASE(uint8_t, 1, 16, 1),  GRAD_CASE(uint8_t, 1, 16, 2),  GRAD_CASE(uint8_t, 1, 16, 4),  GRAD_CASE(uint8_t, 1, 8, 8),   GRAD_CASE(uint8_t, 1, 4, 16),
-    GRAD_CASE(uint16_t, 2, 16, 1), GRAD_CASE(uint16_t, 2, 16, 2), GRAD_CASE(uint16_t, 2, 16, 4), GRAD_CASE(uint16_t, 2, 16, 8), GRAD_CASE(uint16_t, 2, 8, 16),
-};
-#undef GRAD_CASE
-
-static const GradCase *find_grad_case(int lb, int vb, int mt)
-{
-    for (const GradCase &c : kGradCases)
-        if (c.lb == lb && c.vb == vb && c.mt == mt) return &c;
-    return nullptr;
-}
-
-static int no_grad_case(const char *fn, int lb, int vb, int mt)
-{
-    return fail(NNC_EINVAL, std::string(fn) + ": no stream instantiation for label_bytes " + std::to_string(lb) + ", vb " + std::to_string(vb) + ", mt " +
-                                std::to_string(mt));
-}
-
-static int plan_out(const char *fn, const CgPlan &p, int lb, int32_t cus, int64_t *out)
-{
-    if (cus < 1) return fail(NNC_EINVAL, std::string(fn) + ": cus < 1");
-    if (!out) return fail(NNC_EINVAL, std::string(fn) + ": out is NULL");
-    if (p.path == NNC_CBMM_STREAM && !find_grad_case(lb, p.vb, p.mt)) return no_grad_case(fn, lb, p.vb, p.mt);
-    return NNC_OK;
-}
+#define U8_CASE(VB, MT) {1, VB, MT, launch_dx_stream<uint8_t, VB, MT>, launch_dc_stream<uint8_t, VB, MT>},
+#define U16_CASE(VB, MT) {2, VB, MT, launch_dx_stream<uint16_t, VB, MT>, launch_dc_stream<uint16_t, VB, MT>},
+static const GradCase kGradCases[] = {CBG_U8_STREAM_CASES(U8_CASE) CBG_U16_STREAM_CASES(U16_CASE)};
+#undef U8_CASE
+#undef U16_CASE
+static const CbgCaseNames kGradNames = {false, "label_bytes", true};
 
 extern "C" int64_t nnc_cbmm_dx_workspace_bytes(int64_t m, int64_t kdim, int64_t ncols, int label_bytes)
 {
@@ -436,7 +383,7 @@ extern "C" int nnc_cbmm_dx_plan(int64_t m, int64_t kdim, int64_t ncols, int labe
     int rc = cg_check("nnc_cbmm_dx_plan", m, kdim, ncols, label_bytes, k);
     if (rc != NNC_OK) return rc;
     const CgPlan p = dx_plan(m, kdim, ncols, label_bytes, k, cus, (uintptr_t)labels_addr);
-    if ((rc = plan_out("nnc_cbmm_dx_plan", p, label_bytes, cus, out)) != NNC_OK) return rc;
+    if ((rc = cbg_plan_out("nnc_cbmm_dx_plan", kGradCases, kGradNames, p.path, label_bytes, p.vb, p.mt, cus, out)) != NNC_OK) return rc;
     const int64_t v[NNC_CBDX_PLAN_LEN] = {p.path, p.vb, p.mt, p.path == NNC_CBMM_STREAM ? 1LL << p.cshift : (p.entries ? 1 : 0), p.entries, p.splits,
                                           p.per_split, p.aligned, p.lds, p.col_tiles, p.row_tiles, cbg_dx_ws_bytes(p.splits, m, kdim)};
     for (int i = 0; i < NNC_CBDX_PLAN_LEN; ++i) out[i] = v[i];
@@ -454,33 +401,26 @@ extern "C" int nnc_cbmm_dx_f32(const float *g, int64_t m, int64_t kdim, const vo
     const int64_t need = nnc_cbmm_dx_workspace_bytes(m, kdim, ncols, label_bytes);
     if ((rc = cb_check_workspace("nnc_cbmm_dx_f32", "nnc_cbmm_dx_workspace_bytes", workspace, workspace_bytes, need)) != NNC_OK) return rc;
     const CgPlan p = dx_plan(m, kdim, ncols, label_bytes, k, cu_count(), reinterpret_cast<uintptr_t>(labels));
-    const GradCase *gc = p.path == NNC_CBMM_STREAM ? find_grad_case(label_bytes, p.vb, p.mt) : nullptr;
-    if (p.path == NNC_CBMM_STREAM && !gc) return no_grad_case("nnc_cbmm_dx_f32", label_bytes, p.vb, p.mt);
-    if (p.path == NNC_CBMM_NONE) return NNC_OK;
-
+    const GradCase *gc;
+    if ((rc = cbg_stream_case("nnc_cbmm_dx_f32", kGradCases, kGradNames, p.path, label_bytes, p.vb, p.mt, gc)) != NNC_OK) return rc;
     hipStream_t s = S(stream);
-    if (p.path == NNC_CBMM_ZERO) {
-        HIPCHK(hipMemsetAsync(dx, 0, (size_t)(m * kdim) * 4, s));
+    return cbg_run_dx(p.path, p.splits, m, kdim, dx, workspace, s, [&](int direct, float *out) {
+        if (p.path == NNC_CBMM_STREAM) {
+            gc->dx(p.aligned != 0, dim3((unsigned)p.col_tiles, (unsigned)p.row_tiles), (size_t)p.lds, s, g, (int)m, kdim, labels, ncols, centers_dev, k,
+                   p.entries, p.cshift, p.rows_per_group, direct, out);
+            LAUNCHCHK("k_cbdx_stream");
+        } else {
+            const dim3 grid((unsigned)(p.col_tiles * p.row_tiles), (unsigned)p.splits);
+            if (label_bytes == 1)
+                hipLaunchKernelGGL(k_cbdx_tiled<uint8_t>, grid, dim3(256), (size_t)p.lds, s, g, (long long)m, (long long)kdim,
+                                   reinterpret_cast<const uint8_t *>(labels), (long long)ncols, centers_dev, (int)k, p.col_tiles, p.per_split, direct, out);
+            else
+                hipLaunchKernelGGL(k_cbdx_tiled<uint16_t>, grid, dim3(256), (size_t)p.lds, s, g, (long long)m, (long long)kdim,
+                                   reinterpret_cast<const uint16_t *>(labels), (long long)ncols, centers_dev, (int)k, p.col_tiles, p.per_split, direct, out);
+            LAUNCHCHK("k_cbdx_tiled");
+        }
         return NNC_OK;
-    }
-    const int direct = p.splits == 1;
-    float *out = direct ? dx : reinterpret_cast<float *>(workspace);
-    if (p.path == NNC_CBMM_STREAM) {
-        gc->dx(p.aligned != 0, dim3((unsigned)p.col_tiles, (unsigned)p.row_tiles), (size_t)p.lds, s, g, (int)m, kdim, labels, ncols, centers_dev, k, p.entries,
-               p.cshift, p.rows_per_group, direct, out);
-        LAUNCHCHK("k_cbdx_stream");
-    } else {
-        const dim3 grid((unsigned)(p.col_tiles * p.row_tiles), (unsigned)p.splits);
-        if (label_bytes == 1)
-            hipLaunchKernelGGL(k_cbdx_tiled<uint8_t>, grid, dim3(256), (size_t)p.lds, s, g, (long long)m, (long long)kdim, reinterpret_cast<const uint8_t *>(labels),
-                               (long long)ncols, centers_dev, (int)k, p.col_tiles, p.per_split, direct, out);
-        else
-            hipLaunchKernelGGL(k_cbdx_tiled<uint16_t>, grid, dim3(256), (size_t)p.lds, s, g, (long long)m, (long long)kdim, reinterpret_cast<const uint16_t *>(labels),
-                               (long long)ncols, centers_dev, (int)k, p.col_tiles, p.per_split, direct, out);
-        LAUNCHCHK("k_cbdx_tiled");
-    }
-    if (!direct) return cbgrad_reduce(reinterpret_cast<const float *>(workspace), p.splits, m * kdim, dx, s);
-    return NNC_OK;
+    });
 }
 
 extern "C" int64_t nnc_cbmm_dc_workspace_bytes(int64_t m, int64_t kdim, int64_t ncols, int label_bytes, int32_t k)
@@ -494,7 +434,7 @@ extern "C" int nnc_cbmm_dc_plan(int64_t m, int64_t kdim, int64_t ncols, int labe
     int rc = cg_check("nnc_cbmm_dc_plan", m, kdim, ncols, label_bytes, k);
     if (rc != NNC_OK) return rc;
     const CgPlan p = dc_plan(m, kdim, ncols, label_bytes, k, cus, (uintptr_t)labels_addr);
-    if ((rc = plan_out("nnc_cbmm_dc_plan", p, label_bytes, cus, out)) != NNC_OK) return rc;
+    if ((rc = cbg_plan_out("nnc_cbmm_dc_plan", kGradCases, kGradNames, p.path, label_bytes, p.vb, p.mt, cus, out)) != NNC_OK) return rc;
     const int64_t v[NNC_CBDC_PLAN_LEN] = {p.path, p.vb, p.mt, p.path == NNC_CBMM_ZERO ? 0 : 1LL << p.rlog2, p.splits, p.per_split, p.aligned, p.lds,
                                           p.col_tiles, p.row_tiles, p.terms_log2, cbg_dc_ws_bytes(p.path, k)};
     for (int i = 0; i < NNC_CBDC_PLAN_LEN; ++i) out[i] = v[i];
@@ -511,32 +451,24 @@ extern "C" int nnc_cbmm_dc_f32(const float *x, const float *g, int64_t m, int64_
     const int64_t need = nnc_cbmm_dc_workspace_bytes(m, kdim, ncols, label_bytes, k);
     if ((rc = cb_check_workspace("nnc_cbmm_dc_f32", "nnc_cbmm_dc_workspace_bytes", workspace, workspace_bytes, need, 8, "workspace not 8-byte aligned")) != NNC_OK) return rc;
     const CgPlan p = dc_plan(m, kdim, ncols, label_bytes, k, cu_count(), reinterpret_cast<uintptr_t>(labels));
-    const GradCase *gc = p.path == NNC_CBMM_STREAM ? find_grad_case(label_bytes, p.vb, p.mt) : nullptr;
-    if (p.path == NNC_CBMM_STREAM && !gc) return no_grad_case("nnc_cbmm_dc_f32", label_bytes, p.vb, p.mt);
-
+    const GradCase *gc;
+    if ((rc = cbg_stream_case("nnc_cbmm_dc_f32", kGradCases, kGradNames, p.path, label_bytes, p.vb, p.mt, gc)) != NNC_OK) return rc;
     hipStream_t s = S(stream);
-    const size_t esz = out_f64 ? 8 : 4;
-    if (p.path == NNC_CBMM_ZERO) {
-        HIPCHK(hipMemsetAsync(dc, 0, (size_t)k * esz, s));
+    return cbg_run_dc(p.path, x, g, m, kdim, ncols, (int)k, dc, out_f64, workspace, need, s, [&](uint32_t *hdr, unsigned long long *sums) {
+        if (p.path == NNC_CBMM_STREAM) {
+            gc->dc(p.aligned != 0, dim3((unsigned)p.col_tiles, (unsigned)p.row_tiles), (size_t)p.lds, s, x, g, (int)m, kdim, labels, ncols, k, p.rlog2,
+                   p.terms_log2, p.rows_per_group, hdr, sums);
+            LAUNCHCHK("k_cbdc_stream");
+        } else {
+            const dim3 grid((unsigned)(p.col_tiles * p.row_tiles), (unsigned)p.splits);
+            if (label_bytes == 1)
+                hipLaunchKernelGGL(k_cbdc_tiled<uint8_t>, grid, dim3(256), (size_t)p.lds, s, x, g, (long long)m, (long long)kdim,
+                                   reinterpret_cast<const uint8_t *>(labels), (long long)ncols, (int)k, p.rlog2, p.terms_log2, p.col_tiles, p.per_split, hdr, sums);
+            else
+                hipLaunchKernelGGL(k_cbdc_tiled<uint16_t>, grid, dim3(256), (size_t)p.lds, s, x, g, (long long)m, (long long)kdim,
+                                   reinterpret_cast<const uint16_t *>(labels), (long long)ncols, (int)k, p.rlog2, p.terms_log2, p.col_tiles, p.per_split, hdr, sums);
+            LAUNCHCHK("k_cbdc_tiled");
+        }
         return NNC_OK;
-    }
-    uint32_t *hdr = reinterpret_cast<uint32_t *>(workspace);
-    unsigned long long *sums = reinterpret_cast<unsigned long long *>(reinterpret_cast<char *>(workspace) + CBG_HDR_BYTES);
-    HIPCHK(hipMemsetAsync(workspace, 0, (size_t)need, s));
-    if ((rc = cbgrad_absmax(x, m * kdim, g, m * ncols, hdr, s)) != NNC_OK) return rc;
-    if (p.path == NNC_CBMM_STREAM) {
-        gc->dc(p.aligned != 0, dim3((unsigned)p.col_tiles, (unsigned)p.row_tiles), (size_t)p.lds, s, x, g, (int)m, kdim, labels, ncols, k, p.rlog2,
-               p.terms_log2, p.rows_per_group, hdr, sums);
-        LAUNCHCHK("k_cbdc_stream");
-    } else {
-        const dim3 grid((unsigned)(p.col_tiles * p.row_tiles), (unsigned)p.splits);
-        if (label_bytes == 1)
-            hipLaunchKernelGGL(k_cbdc_tiled<uint8_t>, grid, dim3(256), (size_t)p.lds, s, x, g, (long long)m, (long long)kdim,
-                               reinterpret_cast<const uint8_t *>(labels), (long long)ncols, (int)k, p.rlog2, p.terms_log2, p.col_tiles, p.per_split, hdr, sums);
-        else
-            hipLaunchKernelGGL(k_cbdc_tiled<uint16_t>, grid, dim3(256), (size_t)p.lds, s, x, g, (long long)m, (long long)kdim,
-                               reinterpret_cast<const uint16_t *>(labels), (long long)ncols, (int)k, p.rlog2, p.terms_log2, p.col_tiles, p.per_split, hdr, sums);
-        LAUNCHCHK("k_cbdc_tiled");
-    }
-    return cbdc_finish(hdr, reinterpret_cast<const long long *>(sums), (int)k, (int)(out_f64 != 0), dc, s);
+    });
 }

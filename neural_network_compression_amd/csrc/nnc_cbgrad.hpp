@@ -1,8 +1,13 @@
-// nnc_cbgrad.hpp -- what the backward pass of the codebook matmul (nnc_cbgrad.hip) shares with those of its bitmap-sparse and
-// packed siblings (nnc_cbspgrad.hip, nnc_cbpkgrad.hip): the fixed-order wave reduction of the dx stream kernels, the scaling and fixed-point binning of dc (DESIGN.md
-// section 12), the workspace sizes and the launches of the kernels both use (defined in nnc_cbgrad.hip).  The tiled kernels' shared
-// text is in nnc_cbtile.hpp.  The host plans of the byte form (CgPlan, dx_plan, dc_plan) and its argument checks (cg_check) are here
-// too: the group-wise backward pass (nnc_cbgrad_grouped.hip) follows the same plans.
+// nnc_cbgrad.hpp -- what the five backward units of the codebook matmul share (nnc_cbgrad.hip, nnc_cbgrad_grouped.hip,
+// nnc_cbspgrad.hip, nnc_cbpkgrad.hip, nnc_cbpkgrad_grouped.hip).  Device side: the fixed-order wave
+// reduction of the dx stream kernels, the scaling and fixed-point binning of dc and the x load of the dc
+// stream kernels (cbdc_load_x).  Host side: the plans of the byte form (CgPlan, dx_plan, dc_plan) and its argument checks
+// (cg_check), which the group-wise unit follows too; the list of the uint8 and uint16 stream instantiations; and the glue every
+// backward entry point runs, written once: the lookup in a unit's table of stream instantiations and its error (cbg_stream_case),
+// the checks of a plan call (cbg_plan_out), the tail of a grouped plan record (cbg_grouped_plan_tail) and the two sequences of
+// HIP calls (cbg_run_dx, cbg_run_dc), which take the unit's own launch as a callable.  The kernels both directions of every unit
+// launch (k_cbgrad_absmax, k_cbgrad_reduce, k_cbdc_finish) are defined in nnc_cbgrad.hip.  The tiled kernels' shared text is in
+// nnc_cbtile.hpp, the label row loads and the group step of the stream kernels in nnc_cbmm.hpp.
 #pragma once
 #include "nnc_cbmm.hpp"
 
@@ -87,6 +92,17 @@ __device__ __forceinline__ void cbdc_scales(const uint32_t *amax, int &scx, int 
 // the scaling, so that the loads of the batch are in flight together.
 __device__ __forceinline__ long long cbdc_idx(long long idx, bool ok) { return ok ? idx : 0; }
 __device__ __forceinline__ float cbdc_scaled(float v, bool ok, int s) { return ldexpf(v, ok ? s : -512); }
+
+// x[r, i + u] of a batch of U rows of a dc stream kernel, scaled by 2^scx: lane f holds value f = r * U + u (and f + 64),
+// broadcast later by v_readlane (as k_cbmm_stream's cb_load_x)
+template <int MT>
+__device__ __forceinline__ void cbdc_load_x(const float *__restrict__ x, long long kdim, int m, int scx, int lane, long long i, int U, float &xa, float &xb)
+{
+    const int f0 = lane, f1 = lane + 64;
+    const int r0 = f0 / U, r1 = f1 / U;
+    xa = cbdc_scaled(x[cbdc_idx((long long)r0 * kdim + i + f0 % U, r0 < m)], r0 < m, scx);
+    xb = MT * CB_UNROLL > 64 ? cbdc_scaled(x[cbdc_idx((long long)r1 * kdim + i + f1 % U, r1 < m)], r1 < m, scx) : 0.0f;
+}
 
 // the fixed-point image of one dW: exact scaling by 2^S (|v * 2^S| < 2^63), nearest integer, ties to even
 __device__ __forceinline__ unsigned long long cbdc_fix(float v, int S) { return (unsigned long long)(long long)rintf(ldexpf(v, S)); }
@@ -218,10 +234,8 @@ static int cg_check(const char *fn, int64_t m, int64_t kdim, int64_t ncols, int 
 
 // ------------------------------------------------------------------ groups (host): the group-wise backward passes (nnc_cbgrad_grouped.hip, nnc_cbpkgrad_grouped.hip)
 // the most groups the 128 index rows of a tile lie in: tiles start on multiples of 128, group_rows is a multiple of 32
+// (gg_groups, the count of groups, and the group_rows checks are nnc_cbmm.hpp's)
 static inline int tile_groups(long long group_rows) { return group_rows % 128 == 0 ? 1 : (group_rows == 32 ? 4 : 2); }
-
-// G as the layers count it: centers and dc have a row even where kdim = 0
-static inline long long gg_groups(long long kdim, long long group_rows) { return std::max(1LL, cdiv(kdim, group_rows)); }
 
 // the shared kernels of nnc_cbgrad.hip, launched on `s` (NNC_OK, or the launch error):
 //   cbgrad_absmax  amax[0..1] = bits of max |x[0, nx)|, max |g[0, ng)| (amax zeroed by the caller)   k_cbgrad_absmax
@@ -230,3 +244,92 @@ static inline long long gg_groups(long long kdim, long long group_rows) { return
 int cbgrad_absmax(const float *x, long long nx, const float *g, long long ng, uint32_t *amax, hipStream_t s);
 int cbgrad_reduce(const float *part, long long splits, long long mn, float *out, hipStream_t s);
 int cbdc_finish(const uint32_t *hdr, const long long *sums, int k, int f64, void *out, hipStream_t s);
+
+// ------------------------------------------------------------------ the host glue of every backward entry point
+// The (vb, mt) of the stream kernels the byte-form plans (cg_stream_grid) can ask for, per label width, written once: the tables
+// of nnc_cbgrad.hip (both widths) and of nnc_cbgrad_grouped.hip (uint8) are made from these lists, so the grouped unit cannot miss
+// a case the plan produces.  The packed list is PKG_STREAM_CASES (nnc_cbpkgrad.hpp).
+#define CBG_U8_STREAM_CASES(X) X(16, 1) X(16, 2) X(16, 4) X(8, 8) X(4, 16)
+#define CBG_U16_STREAM_CASES(X) X(16, 1) X(16, 2) X(16, 4) X(16, 8) X(8, 16)
+
+// How a unit words a missing stream instantiation: "<fn>: no [grouped ]stream instantiation for [<first> a, ][vb v, ]mt m".  Its
+// table entries begin with the three ints {a, vb, mt}: a = label_bytes or bits (0 where `first` is NULL), vb = 0 without `vb`.
+struct CbgCaseNames {
+    bool grouped;
+    const char *first;
+    bool vb;
+};
+
+// The stream instantiation a plan asks for: c = the entry {a, vb, mt} of `cases` where the path is NNC_CBMM_STREAM (NNC_EINVAL
+// and the unit's message if the table has none), NULL on every other path.
+template <typename Case, size_t N>
+static int cbg_stream_case(const char *fn, const Case (&cases)[N], const CbgCaseNames &n, int path, int a, int vb, int mt, const Case *&c)
+{
+    c = nullptr;
+    if (path != NNC_CBMM_STREAM) return NNC_OK;
+    for (const Case &e : cases)
+        if (e.a == a && e.vb == vb && e.mt == mt) c = &e;
+    if (c) return NNC_OK;
+    return fail(NNC_EINVAL, std::string(fn) + ": no " + (n.grouped ? "grouped " : "") + "stream instantiation for " +
+                                (n.first ? n.first + (" " + std::to_string(a)) + ", " : std::string()) + (n.vb ? "vb " + std::to_string(vb) + ", " : std::string()) +
+                                "mt " + std::to_string(mt));
+}
+
+// the checks of a plan call behind its plan: cus, out, then the stream instantiation
+template <typename Case, size_t N>
+static int cbg_plan_out(const char *fn, const Case (&cases)[N], const CbgCaseNames &n, int path, int a, int vb, int mt, int32_t cus, const int64_t *out)
+{
+    if (cus < 1) return fail(NNC_EINVAL, std::string(fn) + ": cus < 1");
+    if (!out) return fail(NNC_EINVAL, std::string(fn) + ": out is NULL");
+    const Case *c;
+    return cbg_stream_case(fn, cases, n, path, a, vb, mt, c);
+}
+
+// the four values a grouped plan adds to the ungrouped record (the packed one adds a fifth of its own behind them)
+static inline void cbg_grouped_plan_tail(int path, long long row_tiles, long long rows_per_group, long long kdim, long long group_rows, int64_t *out)
+{
+    const bool stream = path == NNC_CBMM_STREAM, tiled = path == NNC_CBMM_TILED;
+    out[0] = group_rows;
+    out[1] = kdim > 0 ? cdiv(kdim, group_rows) : 0;
+    out[2] = stream ? rows_per_group : 0;
+    out[3] = stream ? max_groups_per_split(row_tiles, rows_per_group, kdim, group_rows)
+                    : (tiled ? max_groups_per_split(cdiv(kdim, 128), 128, kdim, group_rows) : 0);
+}
+
+// What every *_dx_f32 does on the stream behind its checks and its plan: nothing (NNC_CBMM_NONE); dx = 0 (NNC_CBMM_ZERO); else
+// the unit's stream or tiled kernel -- launch(direct, out) launches it and returns its status -- into dx itself with one split
+// (direct), or into the partials at the head of the workspace, which k_cbgrad_reduce then sums into dx in split order.
+template <typename Launch>
+static int cbg_run_dx(int path, long long splits, long long m, long long kdim, float *dx, void *workspace, hipStream_t s, Launch launch)
+{
+    if (path == NNC_CBMM_NONE) return NNC_OK;
+    if (path == NNC_CBMM_ZERO) {
+        HIPCHK(hipMemsetAsync(dx, 0, (size_t)(m * kdim) * 4, s));
+        return NNC_OK;
+    }
+    const int direct = splits == 1;
+    const int rc = launch(direct, direct ? dx : reinterpret_cast<float *>(workspace));
+    if (rc != NNC_OK) return rc;
+    if (!direct) return cbgrad_reduce(reinterpret_cast<const float *>(workspace), splits, m * kdim, dx, s);
+    return NNC_OK;
+}
+
+// What every *_dc_f32 does on the stream behind its checks and its plan: dc = 0 over the nbins bins (NNC_CBMM_ZERO); else the
+// workspace (`need` bytes: the header, then int64 sums[nbins]) zeroed, k_cbgrad_absmax into the header, the unit's stream or
+// tiled kernel -- launch(hdr, sums) launches it and returns its status -- and k_cbdc_finish from the sums into dc.
+template <typename Launch>
+static int cbg_run_dc(int path, const float *x, const float *g, long long m, long long kdim, long long ncols, int nbins, void *dc, int out_f64,
+                      void *workspace, int64_t need, hipStream_t s, Launch launch)
+{
+    if (path == NNC_CBMM_ZERO) {
+        HIPCHK(hipMemsetAsync(dc, 0, (size_t)nbins * (out_f64 ? 8 : 4), s));
+        return NNC_OK;
+    }
+    uint32_t *hdr = reinterpret_cast<uint32_t *>(workspace);
+    unsigned long long *sums = reinterpret_cast<unsigned long long *>(reinterpret_cast<char *>(workspace) + CBG_HDR_BYTES);
+    HIPCHK(hipMemsetAsync(workspace, 0, (size_t)need, s));
+    int rc = cbgrad_absmax(x, m * kdim, g, m * ncols, hdr, s);
+    if (rc != NNC_OK) return rc;
+    if ((rc = launch(hdr, sums)) != NNC_OK) return rc;
+    return cbdc_finish(hdr, reinterpret_cast<const long long *>(sums), nbins, (int)(out_f64 != 0), dc, s);
+}

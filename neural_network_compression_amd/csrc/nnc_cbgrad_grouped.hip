@@ -21,6 +21,11 @@
 // The integer sums are exact, so neither walk changes a bit of dc; which wave takes a row changes no bit of dx.  Everything that
 // steers a walk comes from blockIdx and the wave number (a scalar): every wave of a workgroup reaches every barrier.
 // k_cbgrad_absmax, k_cbgrad_reduce and k_cbdc_finish (over G * K bins) are nnc_cbgrad.hip's.
+// What the kernels share with the ungrouped ones without changing an instruction of either is written once (DESIGN.md section
+// 21): the label row loads (cb_row_words) and the step to the next group's rows (cb_group_step) in nnc_cbmm.hpp, the x load of the
+// dc kernel (cbdc_load_x) in nnc_cbgrad.hpp.  So is the host side: the sequences of HIP calls of the two entry points
+// (cbg_run_dx, cbg_run_dc), the lookup in the table of stream instantiations, the list that table is made from, the plan checks
+// and the tail of the plan record (nnc_cbgrad.hpp), the group_rows checks (cb_check_group_rows, nnc_cbmm.hpp).
 #include "nnc_cbtile.hpp"
 
 // ------------------------------------------------------------------ dx, m <= 16
@@ -50,30 +55,15 @@ __global__ __launch_bounds__(CB_THREADS) void k_cbdx_stream_grouped(const float 
         for (int e = 0; e < E; ++e) gv[r][e] = (r < m && e < ne) ? g[(long long)r * ncols + c0 + e] : 0.0f;
 
     const long long s_lo = (long long)blockIdx.y * rows_per_group, s_hi = std::min(kdim, s_lo + rows_per_group);
-    long long g_lo = s_lo, g_hi = std::min(s_hi, (group + 1) * group_rows);   // the rows of the workgroup that lie in `group`
-    long long per_wave = (g_hi - g_lo + CB_WAVES - 1) / CB_WAVES;
-    long long i0 = std::min(g_hi, g_lo + wave * per_wave), i1 = std::min(g_hi, i0 + per_wave);
+    long long g_lo = s_lo, g_hi, i0, i1;   // the rows of the workgroup that lie in `group`, and the wave's share of them
+    cb_group_step(group, group_rows, g_lo, s_hi, wave, g_hi, i0, i1);
     const uintptr_t base = reinterpret_cast<uintptr_t>(labels);
     const long long row_bytes = ncols * LB;
     const long long lane_off = (long long)blockIdx.x * (64 * VB) + lane * VB;
     float *dst = direct ? out : out + (long long)blockIdx.x * m * kdim;
     __syncthreads();
 
-    auto row_words = [&](long long i, uint32_t *w, uint32_t &s) {
-        const uintptr_t row = base + (uintptr_t)(i * row_bytes);
-        if constexpr (ALIGNED) {
-            s = 0;
-            load_chunk<VB>(reinterpret_cast<const unsigned char *>(active ? row + lane_off : row), w);
-        } else {
-            const uintptr_t first = row & ~(uintptr_t)(VB - 1);
-            s = (uint32_t)(__builtin_amdgcn_readfirstlane((uint32_t)((row + blockIdx.x * (64 * VB)) & (VB - 1))));
-            const uintptr_t a = ((row + lane_off) & ~(uintptr_t)(VB - 1));
-            const uintptr_t a0 = active ? a : first;
-            const uintptr_t a1 = (active && a + VB < row + row_bytes) ? a + VB : a0;
-            load_chunk<VB>(reinterpret_cast<const unsigned char *>(a0), w);
-            load_chunk<VB>(reinterpret_cast<const unsigned char *>(a1), w + N);
-        }
-    };
+    auto row_words = [&](long long i, uint32_t *w, uint32_t &s) { cb_row_words<VB, ALIGNED>(base, row_bytes, lane_off, active, i, w, s); };
     auto consume = [&](const uint32_t *w, uint32_t s, long long i) {
         uint32_t o[N];
         if constexpr (ALIGNED) {
@@ -115,9 +105,7 @@ __global__ __launch_bounds__(CB_THREADS) void k_cbdx_stream_grouped(const float 
         if (g_hi >= s_hi) break;
         // on to the next group's rows, divided among the waves as the whole range is
         g_lo = g_hi;
-        g_hi = std::min(s_hi, (++group + 1) * group_rows);
-        per_wave = (g_hi - g_lo + CB_WAVES - 1) / CB_WAVES;
-        i0 = std::min(g_hi, g_lo + wave * per_wave), i1 = std::min(g_hi, i0 + per_wave);
+        cb_group_step(++group, group_rows, g_lo, s_hi, wave, g_hi, i0, i1);
         __syncthreads();   // every wave has left the rows of the group before
         cb_refill(cb, centers + group * k, k, cshift);
         __syncthreads();
@@ -209,36 +197,15 @@ __global__ __launch_bounds__(CB_THREADS) void k_cbdc_stream_grouped(const float 
 
     long long group = (long long)blockIdx.y * rows_per_group / group_rows;
     const long long s_lo = (long long)blockIdx.y * rows_per_group, s_hi = std::min(kdim, s_lo + rows_per_group);
-    long long g_lo = s_lo, g_hi = std::min(s_hi, (group + 1) * group_rows);   // the rows of the workgroup that lie in `group`
-    long long per_wave = (g_hi - g_lo + CB_WAVES - 1) / CB_WAVES;
-    long long i0 = std::min(g_hi, g_lo + wave * per_wave), i1 = std::min(g_hi, i0 + per_wave);
+    long long g_lo = s_lo, g_hi, i0, i1;   // the rows of the workgroup that lie in `group`, and the wave's share of them
+    cb_group_step(group, group_rows, g_lo, s_hi, wave, g_hi, i0, i1);
     const uintptr_t base = reinterpret_cast<uintptr_t>(labels);
     const long long row_bytes = ncols * LB;
     const long long lane_off = (long long)blockIdx.x * (64 * VB) + lane * VB;
     __syncthreads();
 
-    auto row_words = [&](long long i, uint32_t *w, uint32_t &s) {
-        const uintptr_t row = base + (uintptr_t)(i * row_bytes);
-        if constexpr (ALIGNED) {
-            s = 0;
-            load_chunk<VB>(reinterpret_cast<const unsigned char *>(active ? row + lane_off : row), w);
-        } else {
-            const uintptr_t first = row & ~(uintptr_t)(VB - 1);
-            s = (uint32_t)(__builtin_amdgcn_readfirstlane((uint32_t)((row + blockIdx.x * (64 * VB)) & (VB - 1))));
-            const uintptr_t a = ((row + lane_off) & ~(uintptr_t)(VB - 1));
-            const uintptr_t a0 = active ? a : first;
-            const uintptr_t a1 = (active && a + VB < row + row_bytes) ? a + VB : a0;
-            load_chunk<VB>(reinterpret_cast<const unsigned char *>(a0), w);
-            load_chunk<VB>(reinterpret_cast<const unsigned char *>(a1), w + N);
-        }
-    };
-    // x[r, i + u] of a batch of U rows: lane f holds value f = r * U + u (and f + 64), broadcast by v_readlane (as k_cbmm_stream)
-    auto load_x = [&](long long i, int U, float &xa, float &xb) {
-        const int f0 = lane, f1 = lane + 64;
-        const int r0 = f0 / U, r1 = f1 / U;
-        xa = cbdc_scaled(x[cbdc_idx((long long)r0 * kdim + i + f0 % U, r0 < m)], r0 < m, scx);
-        xb = MT * CB_UNROLL > 64 ? cbdc_scaled(x[cbdc_idx((long long)r1 * kdim + i + f1 % U, r1 < m)], r1 < m, scx) : 0.0f;
-    };
+    auto row_words = [&](long long i, uint32_t *w, uint32_t &s) { cb_row_words<VB, ALIGNED>(base, row_bytes, lane_off, active, i, w, s); };
+    auto load_x = [&](long long i, int U, float &xa, float &xb) { cbdc_load_x<MT>(x, kdim, m, scx, lane, i, U, xa, xb); };
     auto consume = [&](const uint32_t *w, uint32_t s, float xa, float xb, int u, int U) {
         float xv[MT];
 #pragma unroll
@@ -287,9 +254,7 @@ __global__ __launch_bounds__(CB_THREADS) void k_cbdc_stream_grouped(const float 
         for (int j = threadIdx.x; j < k; j += CB_THREADS)   // the copies this thread has just summed
             for (int r = 0; r < (1 << rlog2); ++r) bins[(j << rlog2) + r] = 0ull;
         g_lo = g_hi;
-        g_hi = std::min(s_hi, (++group + 1) * group_rows);
-        per_wave = (g_hi - g_lo + CB_WAVES - 1) / CB_WAVES;
-        i0 = std::min(g_hi, g_lo + wave * per_wave), i1 = std::min(g_hi, i0 + per_wave);
+        cb_group_step(++group, group_rows, g_lo, s_hi, wave, g_hi, i0, i1);
         __syncthreads();
     }
 }
@@ -350,63 +315,29 @@ static void launch_dc_stream(bool aligned, dim3 grid, size_t lds, hipStream_t s,
         hipLaunchKernelGGL((k_cbdc_stream_grouped<VB, MT, false>), grid, dim3(CB_THREADS), lds, s, x, g, m, kdim, lab, ncols, k, rlog2, tl, rpg, group_rows, hdr, sums);
 }
 
-// every stream instantiation of this unit (those of nnc_cbgrad.hip for uint8 labels); the plans are checked against this table
+// every stream instantiation of this unit: the uint8 list of nnc_cbgrad.hpp, which nnc_cbgrad.hip's table is made from too
 using DxLaunch = void (*)(bool, dim3, size_t, hipStream_t, const float *, int, long long, const void *, long long, const float *, int, int, int, long long,
                           long long, int, float *);
 using DcLaunch = void (*)(bool, dim3, size_t, hipStream_t, const float *, const float *, int, long long, const void *, long long, int, int, int, long long,
                           long long, uint32_t *, unsigned long long *);
 struct GradCase {
-    int vb, mt;
+    int a, vb, mt;            // a: 0 (uint8 labels only)
     DxLaunch dx;
     DcLaunch dc;
 };
-#define GRAD_CASE(VB, MT) {VB, MT, launch_dx_stream<VB, MT>, launch_dc_stream<VB, MT>}
-static const GradCase kGradCases[] = {GRAD_CASE(16, 1), GRAD_CASE(16, 2), GRAD_CASE(16, 4), GRAD_CASE(8, 8), GRAD_CASE(4, 16)};
+#define GRAD_CASE(VB, MT) {0, VB, MT, launch_dx_stream<VB, MT>, launch_dc_stream<VB, MT>},
+static const GradCase kGradCases[] = {CBG_U8_STREAM_CASES(GRAD_CASE)};
 #undef GRAD_CASE
-
-static const GradCase *find_grad_case(int vb, int mt)
-{
-    for (const GradCase &c : kGradCases)
-        if (c.vb == vb && c.mt == mt) return &c;
-    return nullptr;
-}
-
-static int no_grad_case(const char *fn, int vb, int mt)
-{
-    return fail(NNC_EINVAL, std::string(fn) + ": no grouped stream instantiation for vb " + std::to_string(vb) + ", mt " + std::to_string(mt));
-}
+static const CbgCaseNames kGradNames = {true, nullptr, true};
 
 // ------------------------------------------------------------------ C ABI
 // cg_check's checks at label_bytes 1, then those nnc_cbmm_grouped makes of k and group_rows
 static int gg_check(const char *fn, int64_t m, int64_t kdim, int64_t ncols, int32_t k, int64_t group_rows)
 {
-    const std::string f(fn);
-    if (k > 256) return fail(NNC_EINVAL, f + ": k outside 1..256 (group codebooks take uint8 labels only)");
+    if (k > 256) return fail(NNC_EINVAL, std::string(fn) + ": k outside 1..256 (group codebooks take uint8 labels only)");
     const int rc = cg_check(fn, m, kdim, ncols, 1, k);
     if (rc != NNC_OK) return rc;
-    if (group_rows < 32 || group_rows % 32) return fail(NNC_EINVAL, f + ": group_rows must be a positive multiple of 32");
-    if (group_rows > (1LL << 40)) return fail(NNC_EINVAL, f + ": size too large");
-    if (gg_groups(kdim, group_rows) * k > (1LL << 30)) return fail(NNC_EINVAL, f + ": more than 2^30 bins (groups * k)");
-    return NNC_OK;
-}
-
-// the four values a grouped plan adds to the ungrouped record
-static void gg_plan_tail(const CgPlan &p, long long kdim, long long group_rows, int64_t *out)
-{
-    const bool stream = p.path == NNC_CBMM_STREAM, tiled = p.path == NNC_CBMM_TILED;
-    out[0] = group_rows;
-    out[1] = kdim > 0 ? cdiv(kdim, group_rows) : 0;
-    out[2] = stream ? p.rows_per_group : 0;
-    out[3] = stream ? max_groups_per_split(p.row_tiles, p.rows_per_group, kdim, group_rows)
-                    : (tiled ? max_groups_per_split(cdiv(kdim, 128), 128, kdim, group_rows) : 0);
-}
-
-static int gg_plan_out(const char *fn, const CgPlan &p, int32_t cus, const int64_t *out)
-{
-    if (cus < 1) return fail(NNC_EINVAL, std::string(fn) + ": cus < 1");
-    if (!out) return fail(NNC_EINVAL, std::string(fn) + ": out is NULL");
-    if (p.path == NNC_CBMM_STREAM && !find_grad_case(p.vb, p.mt)) return no_grad_case(fn, p.vb, p.mt);
-    return NNC_OK;
+    return cb_check_group_rows(fn, kdim, group_rows, k);
 }
 
 extern "C" int64_t nnc_cbmm_grouped_dx_workspace_bytes(int64_t m, int64_t kdim, int64_t ncols)
@@ -421,14 +352,14 @@ extern "C" int nnc_cbmm_grouped_dx_plan(int64_t m, int64_t kdim, int64_t ncols, 
     int rc = gg_check("nnc_cbmm_grouped_dx_plan", m, kdim, ncols, k, group_rows);
     if (rc != NNC_OK) return rc;
     const CgPlan p = dx_plan(m, kdim, ncols, 1, k, cus, (uintptr_t)labels_addr);
-    if ((rc = gg_plan_out("nnc_cbmm_grouped_dx_plan", p, cus, out)) != NNC_OK) return rc;
+    if ((rc = cbg_plan_out("nnc_cbmm_grouped_dx_plan", kGradCases, kGradNames, p.path, 0, p.vb, p.mt, cus, out)) != NNC_OK) return rc;
     const bool tiled = p.path == NNC_CBMM_TILED;
     const int tables = tile_groups(group_rows);
     const int64_t v[NNC_CBDX_PLAN_LEN] = {p.path, p.vb, p.mt, p.path == NNC_CBMM_STREAM ? 1LL << p.cshift : (tiled ? tables : 0), p.entries, p.splits,
                                           p.per_split, p.aligned, p.lds + (tiled ? (long long)(tables - 1) * (k + 1) * 4 : 0), p.col_tiles, p.row_tiles,
                                           cbg_dx_ws_bytes(p.splits, m, kdim)};
     for (int i = 0; i < NNC_CBDX_PLAN_LEN; ++i) out[i] = v[i];
-    gg_plan_tail(p, kdim, group_rows, out + NNC_CBDX_PLAN_LEN);
+    cbg_grouped_plan_tail(p.path, p.row_tiles, p.rows_per_group, kdim, group_rows, out + NNC_CBDX_PLAN_LEN);
     return NNC_OK;
 }
 
@@ -443,31 +374,24 @@ extern "C" int nnc_cbmm_grouped_dx_f32(const float *g, int64_t m, int64_t kdim, 
     const int64_t need = nnc_cbmm_grouped_dx_workspace_bytes(m, kdim, ncols);
     if ((rc = cb_check_workspace("nnc_cbmm_grouped_dx_f32", "nnc_cbmm_grouped_dx_workspace_bytes", workspace, workspace_bytes, need)) != NNC_OK) return rc;
     const CgPlan p = dx_plan(m, kdim, ncols, 1, k, cu_count(), reinterpret_cast<uintptr_t>(labels));
-    const GradCase *gc = p.path == NNC_CBMM_STREAM ? find_grad_case(p.vb, p.mt) : nullptr;
-    if (p.path == NNC_CBMM_STREAM && !gc) return no_grad_case("nnc_cbmm_grouped_dx_f32", p.vb, p.mt);
-    if (p.path == NNC_CBMM_NONE) return NNC_OK;
-
+    const GradCase *gc;
+    if ((rc = cbg_stream_case("nnc_cbmm_grouped_dx_f32", kGradCases, kGradNames, p.path, 0, p.vb, p.mt, gc)) != NNC_OK) return rc;
     hipStream_t s = S(stream);
-    if (p.path == NNC_CBMM_ZERO) {
-        HIPCHK(hipMemsetAsync(dx, 0, (size_t)(m * kdim) * 4, s));
+    return cbg_run_dx(p.path, p.splits, m, kdim, dx, workspace, s, [&](int direct, float *out) {
+        if (p.path == NNC_CBMM_STREAM) {
+            gc->dx(p.aligned != 0, dim3((unsigned)p.col_tiles, (unsigned)p.row_tiles), (size_t)p.lds, s, g, (int)m, kdim, labels, ncols, centers_dev, k,
+                   p.entries, p.cshift, p.rows_per_group, group_rows, direct, out);
+            LAUNCHCHK("k_cbdx_stream_grouped");
+        } else {
+            const int tables = tile_groups(group_rows);
+            const dim3 grid((unsigned)(p.col_tiles * p.row_tiles), (unsigned)p.splits);
+            hipLaunchKernelGGL(k_cbdx_tiled_grouped, grid, dim3(256), (size_t)(p.lds + (long long)(tables - 1) * (k + 1) * 4), s, g, (long long)m,
+                               (long long)kdim, reinterpret_cast<const uint8_t *>(labels), (long long)ncols, centers_dev, (int)k, p.col_tiles, p.per_split,
+                               (long long)group_rows, tables, direct, out);
+            LAUNCHCHK("k_cbdx_tiled_grouped");
+        }
         return NNC_OK;
-    }
-    const int direct = p.splits == 1;
-    float *out = direct ? dx : reinterpret_cast<float *>(workspace);
-    if (p.path == NNC_CBMM_STREAM) {
-        gc->dx(p.aligned != 0, dim3((unsigned)p.col_tiles, (unsigned)p.row_tiles), (size_t)p.lds, s, g, (int)m, kdim, labels, ncols, centers_dev, k, p.entries,
-               p.cshift, p.rows_per_group, group_rows, direct, out);
-        LAUNCHCHK("k_cbdx_stream_grouped");
-    } else {
-        const int tables = tile_groups(group_rows);
-        const dim3 grid((unsigned)(p.col_tiles * p.row_tiles), (unsigned)p.splits);
-        hipLaunchKernelGGL(k_cbdx_tiled_grouped, grid, dim3(256), (size_t)(p.lds + (long long)(tables - 1) * (k + 1) * 4), s, g, (long long)m, (long long)kdim,
-                           reinterpret_cast<const uint8_t *>(labels), (long long)ncols, centers_dev, (int)k, p.col_tiles, p.per_split, (long long)group_rows,
-                           tables, direct, out);
-        LAUNCHCHK("k_cbdx_tiled_grouped");
-    }
-    if (!direct) return cbgrad_reduce(reinterpret_cast<const float *>(workspace), p.splits, m * kdim, dx, s);
-    return NNC_OK;
+    });
 }
 
 extern "C" int64_t nnc_cbmm_grouped_dc_workspace_bytes(int64_t m, int64_t kdim, int64_t ncols, int32_t k, int64_t group_rows)
@@ -482,12 +406,12 @@ extern "C" int nnc_cbmm_grouped_dc_plan(int64_t m, int64_t kdim, int64_t ncols, 
     int rc = gg_check("nnc_cbmm_grouped_dc_plan", m, kdim, ncols, k, group_rows);
     if (rc != NNC_OK) return rc;
     const CgPlan p = dc_plan(m, kdim, ncols, 1, k, cus, (uintptr_t)labels_addr);
-    if ((rc = gg_plan_out("nnc_cbmm_grouped_dc_plan", p, cus, out)) != NNC_OK) return rc;
+    if ((rc = cbg_plan_out("nnc_cbmm_grouped_dc_plan", kGradCases, kGradNames, p.path, 0, p.vb, p.mt, cus, out)) != NNC_OK) return rc;
     const int sets_log2 = p.path == NNC_CBMM_TILED ? __builtin_ctz(tile_groups(group_rows)) : 0;
     const int64_t v[NNC_CBDC_PLAN_LEN] = {p.path, p.vb, p.mt, p.path == NNC_CBMM_ZERO ? 0 : 1LL << (p.rlog2 - sets_log2), p.splits, p.per_split, p.aligned, p.lds,
                                           p.col_tiles, p.row_tiles, p.terms_log2, cbg_dc_ws_bytes(p.path, (int)(gg_groups(kdim, group_rows) * k))};
     for (int i = 0; i < NNC_CBDC_PLAN_LEN; ++i) out[i] = v[i];
-    gg_plan_tail(p, kdim, group_rows, out + NNC_CBDC_PLAN_LEN);
+    cbg_grouped_plan_tail(p.path, p.row_tiles, p.rows_per_group, kdim, group_rows, out + NNC_CBDC_PLAN_LEN);
     return NNC_OK;
 }
 
@@ -501,29 +425,22 @@ extern "C" int nnc_cbmm_grouped_dc_f32(const float *x, const float *g, int64_t m
     const int64_t need = nnc_cbmm_grouped_dc_workspace_bytes(m, kdim, ncols, k, group_rows);
     if ((rc = cb_check_workspace("nnc_cbmm_grouped_dc_f32", "nnc_cbmm_grouped_dc_workspace_bytes", workspace, workspace_bytes, need, 8, "workspace not 8-byte aligned")) != NNC_OK) return rc;
     const CgPlan p = dc_plan(m, kdim, ncols, 1, k, cu_count(), reinterpret_cast<uintptr_t>(labels));
-    const GradCase *gc = p.path == NNC_CBMM_STREAM ? find_grad_case(p.vb, p.mt) : nullptr;
-    if (p.path == NNC_CBMM_STREAM && !gc) return no_grad_case("nnc_cbmm_grouped_dc_f32", p.vb, p.mt);
-
+    const GradCase *gc;
+    if ((rc = cbg_stream_case("nnc_cbmm_grouped_dc_f32", kGradCases, kGradNames, p.path, 0, p.vb, p.mt, gc)) != NNC_OK) return rc;
     hipStream_t s = S(stream);
     const int nbins = (int)(gg_groups(kdim, group_rows) * k);
-    if (p.path == NNC_CBMM_ZERO) {
-        HIPCHK(hipMemsetAsync(dc, 0, (size_t)nbins * (out_f64 ? 8 : 4), s));
+    return cbg_run_dc(p.path, x, g, m, kdim, ncols, nbins, dc, out_f64, workspace, need, s, [&](uint32_t *hdr, unsigned long long *sums) {
+        if (p.path == NNC_CBMM_STREAM) {
+            gc->dc(p.aligned != 0, dim3((unsigned)p.col_tiles, (unsigned)p.row_tiles), (size_t)p.lds, s, x, g, (int)m, kdim, labels, ncols, k, p.rlog2,
+                   p.terms_log2, p.rows_per_group, group_rows, hdr, sums);
+            LAUNCHCHK("k_cbdc_stream_grouped");
+        } else {
+            const dim3 grid((unsigned)(p.col_tiles * p.row_tiles), (unsigned)p.splits);
+            hipLaunchKernelGGL(k_cbdc_tiled_grouped, grid, dim3(256), (size_t)p.lds, s, x, g, (long long)m, (long long)kdim,
+                               reinterpret_cast<const uint8_t *>(labels), (long long)ncols, (int)k, p.rlog2, __builtin_ctz(tile_groups(group_rows)), p.terms_log2,
+                               p.col_tiles, p.per_split, (long long)group_rows, hdr, sums);
+            LAUNCHCHK("k_cbdc_tiled_grouped");
+        }
         return NNC_OK;
-    }
-    uint32_t *hdr = reinterpret_cast<uint32_t *>(workspace);
-    unsigned long long *sums = reinterpret_cast<unsigned long long *>(reinterpret_cast<char *>(workspace) + CBG_HDR_BYTES);
-    HIPCHK(hipMemsetAsync(workspace, 0, (size_t)need, s));
-    if ((rc = cbgrad_absmax(x, m * kdim, g, m * ncols, hdr, s)) != NNC_OK) return rc;
-    if (p.path == NNC_CBMM_STREAM) {
-        gc->dc(p.aligned != 0, dim3((unsigned)p.col_tiles, (unsigned)p.row_tiles), (size_t)p.lds, s, x, g, (int)m, kdim, labels, ncols, k, p.rlog2,
-               p.terms_log2, p.rows_per_group, group_rows, hdr, sums);
-        LAUNCHCHK("k_cbdc_stream_grouped");
-    } else {
-        const dim3 grid((unsigned)(p.col_tiles * p.row_tiles), (unsigned)p.splits);
-        hipLaunchKernelGGL(k_cbdc_tiled_grouped, grid, dim3(256), (size_t)p.lds, s, x, g, (long long)m, (long long)kdim, reinterpret_cast<const uint8_t *>(labels),
-                           (long long)ncols, (int)k, p.rlog2, __builtin_ctz(tile_groups(group_rows)), p.terms_log2, p.col_tiles, p.per_split,
-                           (long long)group_rows, hdr, sums);
-        LAUNCHCHK("k_cbdc_tiled_grouped");
-    }
-    return cbdc_finish(hdr, reinterpret_cast<const long long *>(sums), nbins, (int)(out_f64 != 0), dc, s);
+    });
 }

@@ -174,6 +174,21 @@ static inline int cb_finish(int direct, const void *workspace, long long splits,
     return direct ? NNC_OK : cbmm_reduce_dt(reinterpret_cast<const float *>(workspace), splits, mn, ncols, bias, relu, y, y_dtype, s);
 }
 
+// G as the group-wise layers count it: centers and dc have a row even where kdim = 0
+static inline long long gg_groups(long long kdim, long long group_rows) { return std::max(1LL, cdiv(kdim, group_rows)); }
+
+// The group_rows checks of every group-wise entry point `fn`, forward and backward, in the order each makes them: a multiple of
+// 32 and at least 32; at most 2^40; and, where the caller keeps bins (bins_k = its k > 0: the dc sums of the backward units), at
+// most 2^30 of them.  NNC_EINVAL or NNC_OK.
+static inline int cb_check_group_rows(const char *fn, int64_t kdim, int64_t group_rows, int32_t bins_k = 0)
+{
+    const std::string f(fn);
+    if (group_rows < 32 || group_rows % 32) return fail(NNC_EINVAL, f + ": group_rows must be a positive multiple of 32");
+    if (group_rows > (1LL << 40)) return fail(NNC_EINVAL, f + ": size too large");
+    if (bins_k > 0 && gg_groups(kdim, group_rows) * bins_k > (1LL << 30)) return fail(NNC_EINVAL, f + ": more than 2^30 bins (groups * k)");
+    return NNC_OK;
+}
+
 // the most groups of group_rows rows that the rows of one split lie in (the group-wise units report it in their plans)
 static inline long long max_groups_per_split(long long splits, long long rows_per_split, long long kdim, long long group_rows)
 {
@@ -269,6 +284,54 @@ __device__ __forceinline__ void funnel(const uint32_t *w, uint32_t s, uint32_t *
     for (int d = 0; d < N; ++d) o[d] = __builtin_amdgcn_alignbyte(v[d + 1], v[d], r);
 }
 
+// The label row loads of the byte-form stream kernels, forward and backward: the lane's VB bytes of label
+// row i into w (s = 0) where every row starts on a VB-byte boundary; else the two aligned chunks that hold them into the 2N-dword
+// window w, and the byte offset s of the lane's bytes in it (uniform over the wave: funnel() shifts by it).  `base` the labels,
+// `lane_off` the byte offset of the lane's window in its row; a lane past the row (`active` false) reads the row's first chunk.
+template <int VB, bool ALIGNED>
+__device__ __forceinline__ void cb_row_words(uintptr_t base, long long row_bytes, long long lane_off, bool active, long long i, uint32_t *w, uint32_t &s)
+{
+    constexpr int N = VB / 4;
+    const uintptr_t row = base + (uintptr_t)(i * row_bytes);
+    if constexpr (ALIGNED) {
+        s = 0;
+        load_chunk<VB>(reinterpret_cast<const unsigned char *>(active ? row + lane_off : row), w);
+    } else {
+        const uintptr_t first = row & ~(uintptr_t)(VB - 1);          // the chunk that holds the row's first byte
+        s = (uint32_t)(__builtin_amdgcn_readfirstlane((uint32_t)((row + blockIdx.x * (64 * VB)) & (VB - 1))));
+        const uintptr_t a = ((row + lane_off) & ~(uintptr_t)(VB - 1));
+        const uintptr_t a0 = active ? a : first;
+        const uintptr_t a1 = (active && a + VB < row + row_bytes) ? a + VB : a0;
+        load_chunk<VB>(reinterpret_cast<const unsigned char *>(a0), w);
+        load_chunk<VB>(reinterpret_cast<const unsigned char *>(a1), w + N);
+    }
+}
+
+// x[r, i + u] of a batch of U rows of a forward stream kernel: lane f holds value f = r * U + u (and f + 64), broadcast later by
+// v_readlane.  Vector loads keep the x reads off the LGKM counter that every LDS lookup waits on.  The second value exists only
+// where a batch holds more than 64 (MT * CB_UNROLL > 64: MT = 16 at U = CB_UNROLL).  A shorter batch of an MT = 16 kernel (U = 1, or
+// the U = 4 of the packed kernels) passes that guard too and still loads nothing: its row r1 = (lane + 64) / U >= 16 >= m, m <= 16
+// on every stream path.
+template <int MT, typename XT>
+__device__ __forceinline__ void cb_load_x(const XT *__restrict__ x, long long kdim, int m, int lane, long long i, int U, float &xa, float &xb)
+{
+    const int f0 = lane, f1 = lane + 64;
+    const int r0 = f0 / U, r1 = f1 / U;
+    xa = r0 < m ? (float)x[(long long)r0 * kdim + i + f0 % U] : 0.0f;
+    xb = (MT * CB_UNROLL > 64 && r1 < m) ? (float)x[(long long)r1 * kdim + i + f1 % U] : 0.0f;
+}
+
+// The step of a group-wise stream kernel that walks its workgroup's rows [.., s_hi) group by group: the rows from g_lo on that
+// lie in `group` end at g_hi (the group's end or the workgroup's), and wave `wave` takes [i0, i1) of them, divided among the
+// CB_WAVES waves as an ungrouped kernel divides its whole range.
+__device__ __forceinline__ void cb_group_step(long long group, long long group_rows, long long g_lo, long long s_hi, int wave, long long &g_hi, long long &i0,
+                                              long long &i1)
+{
+    g_hi = std::min(s_hi, (group + 1) * group_rows);
+    const long long per_wave = (g_hi - g_lo + CB_WAVES - 1) / CB_WAVES;
+    i0 = std::min(g_hi, g_lo + wave * per_wave), i1 = std::min(g_hi, i0 + per_wave);
+}
+
 // ------------------------------------------------------------------ skinny: m <= 16
 // grid (col_tiles, splits), CB_THREADS threads.  `out` is y (direct != 0: + bias, ReLU here) or the float32 partials
 // [split][m][ncols].  XT = float is nnc_cbmm_f32's kernel (nnc_cbmm.hip).  XT = bf16_t / f16_t is nnc_cbmm_h16's (nnc_cbmm_h16.hip):
@@ -306,29 +369,8 @@ __global__ __launch_bounds__(CB_THREADS) void k_cbmm_stream(const XT *__restrict
         for (int e = 0; e < E; ++e) acc[r][e] = 0.0f;
     __syncthreads();
 
-    auto row_words = [&](long long i, uint32_t *w, uint32_t &s) {
-        const uintptr_t row = base + (uintptr_t)(i * row_bytes);
-        if constexpr (ALIGNED) {
-            s = 0;
-            load_chunk<VB>(reinterpret_cast<const unsigned char *>(active ? row + lane_off : row), w);
-        } else {
-            const uintptr_t first = row & ~(uintptr_t)(VB - 1);          // the chunk that holds the row's first byte
-            s = (uint32_t)(__builtin_amdgcn_readfirstlane((uint32_t)((row + blockIdx.x * (64 * VB)) & (VB - 1))));
-            const uintptr_t a = ((row + lane_off) & ~(uintptr_t)(VB - 1));
-            const uintptr_t a0 = active ? a : first;
-            const uintptr_t a1 = (active && a + VB < row + row_bytes) ? a + VB : a0;
-            load_chunk<VB>(reinterpret_cast<const unsigned char *>(a0), w);
-            load_chunk<VB>(reinterpret_cast<const unsigned char *>(a1), w + N);
-        }
-    };
-    // x[r, i + u] of a batch of U rows: lane f holds value f = r * U + u (and f + 64), broadcast by v_readlane.  Vector loads
-    // keep the x reads off the LGKM counter that every LDS lookup waits on.
-    auto load_x = [&](long long i, int U, float &xa, float &xb) {
-        const int f0 = lane, f1 = lane + 64;
-        const int r0 = f0 / U, r1 = f1 / U;
-        xa = r0 < m ? (float)x[(long long)r0 * kdim + i + f0 % U] : 0.0f;
-        xb = (MT * CB_UNROLL > 64 && r1 < m) ? (float)x[(long long)r1 * kdim + i + f1 % U] : 0.0f;
-    };
+    auto row_words = [&](long long i, uint32_t *w, uint32_t &s) { cb_row_words<VB, ALIGNED>(base, row_bytes, lane_off, active, i, w, s); };
+    auto load_x = [&](long long i, int U, float &xa, float &xb) { cb_load_x<MT>(x, kdim, m, lane, i, U, xa, xb); };
     auto consume = [&](const uint32_t *w, uint32_t s, float xa, float xb, int u, int U) {
         float xv[MT];
 #pragma unroll

@@ -42,9 +42,8 @@ __global__ __launch_bounds__(CB_THREADS) void k_cbmm_stream_grouped(const XT *__
     const long long c0 = (long long)blockIdx.x * (64 * E) + lane * E;
     const bool active = c0 < ncols;
     const long long s_lo = (long long)blockIdx.y * rows_per_split, s_hi = std::min(kdim, s_lo + rows_per_split);
-    long long g_lo = s_lo, g_hi = std::min(s_hi, (group + 1) * group_rows);   // the rows of the split that lie in `group`
-    long long per_wave = (g_hi - g_lo + CB_WAVES - 1) / CB_WAVES;
-    long long i0 = std::min(g_hi, g_lo + wave * per_wave), i1 = std::min(g_hi, i0 + per_wave);
+    long long g_lo = s_lo, g_hi, i0, i1;   // the rows of the split that lie in `group`, and the wave's share of them
+    cb_group_step(group, group_rows, g_lo, s_hi, wave, g_hi, i0, i1);
     const uintptr_t base = reinterpret_cast<uintptr_t>(labels);
     const long long row_bytes = ncols * LB;
     const long long lane_off = (long long)blockIdx.x * (64 * VB) + lane * VB;   // byte offset of the lane's window in its row
@@ -56,29 +55,8 @@ __global__ __launch_bounds__(CB_THREADS) void k_cbmm_stream_grouped(const XT *__
         for (int e = 0; e < E; ++e) acc[r][e] = 0.0f;
     __syncthreads();
 
-    auto row_words = [&](long long i, uint32_t *w, uint32_t &s) {
-        const uintptr_t row = base + (uintptr_t)(i * row_bytes);
-        if constexpr (ALIGNED) {
-            s = 0;
-            load_chunk<VB>(reinterpret_cast<const unsigned char *>(active ? row + lane_off : row), w);
-        } else {
-            const uintptr_t first = row & ~(uintptr_t)(VB - 1);          // the chunk that holds the row's first byte
-            s = (uint32_t)(__builtin_amdgcn_readfirstlane((uint32_t)((row + blockIdx.x * (64 * VB)) & (VB - 1))));
-            const uintptr_t a = ((row + lane_off) & ~(uintptr_t)(VB - 1));
-            const uintptr_t a0 = active ? a : first;
-            const uintptr_t a1 = (active && a + VB < row + row_bytes) ? a + VB : a0;
-            load_chunk<VB>(reinterpret_cast<const unsigned char *>(a0), w);
-            load_chunk<VB>(reinterpret_cast<const unsigned char *>(a1), w + N);
-        }
-    };
-    // x[r, i + u] of a batch of U rows: lane f holds value f = r * U + u (and f + 64), broadcast by v_readlane.  Vector loads
-    // keep the x reads off the LGKM counter that every LDS lookup waits on.
-    auto load_x = [&](long long i, int U, float &xa, float &xb) {
-        const int f0 = lane, f1 = lane + 64;
-        const int r0 = f0 / U, r1 = f1 / U;
-        xa = r0 < m ? (float)x[(long long)r0 * kdim + i + f0 % U] : 0.0f;
-        xb = (MT * CB_UNROLL > 64 && r1 < m) ? (float)x[(long long)r1 * kdim + i + f1 % U] : 0.0f;
-    };
+    auto row_words = [&](long long i, uint32_t *w, uint32_t &s) { cb_row_words<VB, ALIGNED>(base, row_bytes, lane_off, active, i, w, s); };
+    auto load_x = [&](long long i, int U, float &xa, float &xb) { cb_load_x<MT>(x, kdim, m, lane, i, U, xa, xb); };
     auto consume = [&](const uint32_t *w, uint32_t s, float xa, float xb, int u, int U) {
         float xv[MT];
 #pragma unroll
@@ -124,9 +102,7 @@ __global__ __launch_bounds__(CB_THREADS) void k_cbmm_stream_grouped(const XT *__
         if (g_hi >= s_hi) break;
         // on to the next group's rows, divided among the waves as a whole split is
         g_lo = g_hi;
-        g_hi = std::min(s_hi, (++group + 1) * group_rows);
-        per_wave = (g_hi - g_lo + CB_WAVES - 1) / CB_WAVES;
-        i0 = std::min(g_hi, g_lo + wave * per_wave), i1 = std::min(g_hi, i0 + per_wave);
+        cb_group_step(++group, group_rows, g_lo, s_hi, wave, g_hi, i0, i1);
         __syncthreads();   // every wave has left the rows of the group before
         cb_refill<XT>(cb, centers + group * k, k, cshift);
         __syncthreads();
@@ -335,9 +311,9 @@ static int grouped_check(int x_dtype, int64_t m, int64_t kdim, int64_t ncols, in
         return nnc_set_error_(NNC_EINVAL, "nnc_cbmm_grouped: x_dtype must be NNC_DT_F32, NNC_DT_BF16 or NNC_DT_F16");
     if (m < 0 || kdim < 0 || ncols < 0) return nnc_set_error_(NNC_EINVAL, "nnc_cbmm_grouped: negative size");
     if (k < 1 || k > 256) return nnc_set_error_(NNC_EINVAL, "nnc_cbmm_grouped: k outside 1..256 (group codebooks take uint8 labels only)");
-    if (group_rows < 32 || group_rows % 32) return nnc_set_error_(NNC_EINVAL, "nnc_cbmm_grouped: group_rows must be a positive multiple of 32");
-    if (m > (1LL << 40) || kdim > (1LL << 40) || ncols > (1LL << 40) || group_rows > (1LL << 40))
-        return nnc_set_error_(NNC_EINVAL, "nnc_cbmm_grouped: size too large");
+    const int rc = cb_check_group_rows("nnc_cbmm_grouped", kdim, group_rows);
+    if (rc != NNC_OK) return rc;
+    if (m > (1LL << 40) || kdim > (1LL << 40) || ncols > (1LL << 40)) return nnc_set_error_(NNC_EINVAL, "nnc_cbmm_grouped: size too large");
     return NNC_OK;
 }
 

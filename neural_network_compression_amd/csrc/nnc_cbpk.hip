@@ -178,13 +178,7 @@ __global__ __launch_bounds__(CB_THREADS, 2) void k_cbpk_stream(const float *__re
         for (int e = 0; e < E; ++e) acc[r][e] = 0.0f;
     __syncthreads();
 
-    // x[r, i + u] of a batch of U rows: lane f holds value f = r * U + u (and f + 64), broadcast by v_readlane
-    auto load_x = [&](long long i, int U, float &xa, float &xb) {
-        const int f0 = lane, f1 = lane + 64;
-        const int r0 = f0 / U, r1 = f1 / U;
-        xa = r0 < m ? x[(long long)r0 * kdim + i + f0 % U] : 0.0f;
-        xb = (MT * U > 64 && r1 < m) ? x[(long long)r1 * kdim + i + f1 % U] : 0.0f;
-    };
+    auto load_x = [&](long long i, int U, float &xa, float &xb) { cb_load_x<MT>(x, kdim, m, lane, i, U, xa, xb); };
     auto consume = [&](const uint32_t *w, float xa, float xb, int u, int U) {
         float xv[MT];
 #pragma unroll

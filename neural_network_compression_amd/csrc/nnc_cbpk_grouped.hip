@@ -73,13 +73,7 @@ __global__ __launch_bounds__(CB_THREADS, 2) void k_cbpk_stream_grouped(const XT 
         }
         __builtin_amdgcn_wave_barrier();                // the lookups below read what other lanes of this wave wrote
     };
-    // x[r, i + u] of a batch of U rows: lane f holds value f = r * U + u (and f + 64), broadcast by v_readlane
-    auto load_x = [&](long long i, int U, float &xa, float &xb) {
-        const int f0 = lane, f1 = lane + 64;
-        const int r0 = f0 / U, r1 = f1 / U;
-        xa = r0 < m ? (float)x[(long long)r0 * kdim + i + f0 % U] : 0.0f;
-        xb = (MT * U > 64 && r1 < m) ? (float)x[(long long)r1 * kdim + i + f1 % U] : 0.0f;
-    };
+    auto load_x = [&](long long i, int U, float &xa, float &xb) { cb_load_x<MT>(x, kdim, m, lane, i, U, xa, xb); };
     auto consume = [&](const uint32_t *w, float xa, float xb, int u, int U) {
         float xv[MT];
 #pragma unroll
@@ -369,9 +363,7 @@ static int grouped_check(const char *fn, int x_dtype, int64_t m, int64_t kdim, i
         return fail(NNC_EINVAL, std::string(fn) + ": x_dtype must be NNC_DT_F32, NNC_DT_BF16 or NNC_DT_F16");
     const int rc = pk_check(fn, m, kdim, ncols, bits, k);
     if (rc != NNC_OK) return rc;
-    if (group_rows < 32 || group_rows % 32) return fail(NNC_EINVAL, std::string(fn) + ": group_rows must be a positive multiple of 32");
-    if (group_rows > (1LL << 40)) return fail(NNC_EINVAL, std::string(fn) + ": size too large");
-    return NNC_OK;
+    return cb_check_group_rows(fn, kdim, group_rows);
 }
 
 extern "C" int64_t nnc_cbpk_grouped_workspace_bytes(int x_dtype, int64_t m, int64_t kdim, int64_t ncols, int bits)

@@ -21,6 +21,8 @@
 //   k_cbpkdc_tiled   m > 16.  k_cbdc_tiled's tiles and splits of m; a thread's 8 consecutive columns of a row come from one packed
 //                    dword, loaded once.
 // k_cbgrad_absmax, k_cbdc_finish and k_cbgrad_reduce are nnc_cbgrad.hip's.  No float atomics; no host read.
+// The sequences of HIP calls of the two entry points (cbg_run_dx, cbg_run_dc), the lookup in the table of stream instantiations and
+// the x load of k_cbpkdc_stream (cbdc_load_x) are nnc_cbgrad.hpp's; the list the table is made from is nnc_cbpkgrad.hpp's.
 #include "nnc_cbpkgrad.hpp"
 
 // ------------------------------------------------------------------ dx, m <= 16
@@ -178,13 +180,7 @@ __global__ __launch_bounds__(CB_THREADS) void k_cbpkdc_stream(const float *__res
     unsigned long long *mybins = bins + lane;
     __syncthreads();
 
-    // x[r, i + u] of a batch of U rows: lane f holds value f = r * U + u (and f + 64), broadcast by v_readlane (as k_cbdc_stream)
-    auto load_x = [&](long long i, int U, float &xa, float &xb) {
-        const int f0 = lane, f1 = lane + 64;
-        const int r0 = f0 / U, r1 = f1 / U;
-        xa = cbdc_scaled(x[cbdc_idx((long long)r0 * kdim + i + f0 % U, r0 < m)], r0 < m, scx);
-        xb = MT * CB_UNROLL > 64 ? cbdc_scaled(x[cbdc_idx((long long)r1 * kdim + i + f1 % U, r1 < m)], r1 < m, scx) : 0.0f;
-    };
+    auto load_x = [&](long long i, int U, float &xa, float &xb) { cbdc_load_x<MT>(x, kdim, m, scx, lane, i, U, xa, xb); };
     auto consume = [&](const uint32_t *w, float xa, float xb, int u, int U) {
         float xv[MT];
 #pragma unroll
@@ -274,45 +270,20 @@ static void launch_pg_dc(dim3 grid, size_t lds, hipStream_t s, const float *x, c
     hipLaunchKernelGGL((k_cbpkdc_stream<BITS, VB, MT>), grid, dim3(CB_THREADS), lds, s, x, g, m, kdim, packed, row_bytes, ncols, k, tl, rpg, hdr, sums);
 }
 
-// every stream instantiation there is; the plans are checked against this table, and the launches go through it
+// every stream instantiation there is (the list of nnc_cbpkgrad.hpp); the plans are checked against this table, and the launches go through it
 using PgDxLaunch = void (*)(dim3, size_t, hipStream_t, const float *, int, long long, const unsigned char *, long long, long long, const float *, int,
                             long long, int, float *);
 using PgDcLaunch = void (*)(dim3, size_t, hipStream_t, const float *, const float *, int, long long, const unsigned char *, long long, long long, int, int,
                             long long, uint32_t *, unsigned long long *);
 struct PgCase {
-    int bits, vb, mt;
+    int a, vb, mt;            // a: bits
     PgDxLaunch dx;
     PgDcLaunch dc;
 };
-#define PG_CASE(B, V, M) {B, V, M, launch_pg_dx<B, V, M>, launch_pg_dc<B, V, M>}
-static const PgCase kPgCases[] = {
-    PG_CASE(4, 16, 1), PG_CASE(4, 8, 1), PG_CASE(4, 4, 1), PG_CASE(4, 16, 2), PG_CASE(4, 8, 2), PG_CASE(4, 4, 2), PG_CASE(4, 8, 4),
-    PG_CASE(4, 4, 4),  PG_CASE(4, 4, 8), PG_CASE(4, 2, 16),
-    PG_CASE(2, 16, 1), PG_CASE(2, 8, 1), PG_CASE(2, 4, 1), PG_CASE(2, 8, 2),  PG_CASE(2, 4, 2), PG_CASE(2, 4, 4), PG_CASE(2, 2, 8),
-    PG_CASE(2, 1, 16),
-};
+#define PG_CASE(B, V, M) {B, V, M, launch_pg_dx<B, V, M>, launch_pg_dc<B, V, M>},
+static const PgCase kPgCases[] = {PKG_STREAM_CASES(PG_CASE)};
 #undef PG_CASE
-
-static const PgCase *find_pg_case(int bits, int vb, int mt)
-{
-    for (const PgCase &c : kPgCases)
-        if (c.bits == bits && c.vb == vb && c.mt == mt) return &c;
-    return nullptr;
-}
-
-static int no_pg_case(const char *fn, int bits, int vb, int mt)
-{
-    return fail(NNC_EINVAL, std::string(fn) + ": no stream instantiation for bits " + std::to_string(bits) + ", vb " + std::to_string(vb) + ", mt " +
-                                std::to_string(mt));
-}
-
-static int pg_plan_out(const char *fn, const PgPlan &p, int bits, int32_t cus, int64_t *out)
-{
-    if (cus < 1) return fail(NNC_EINVAL, std::string(fn) + ": cus < 1");
-    if (!out) return fail(NNC_EINVAL, std::string(fn) + ": out is NULL");
-    if (p.path == NNC_CBMM_STREAM && !find_pg_case(bits, p.vb, p.mt)) return no_pg_case(fn, bits, p.vb, p.mt);
-    return NNC_OK;
-}
+static const CbgCaseNames kPgNames = {false, "bits", true};
 
 extern "C" int64_t nnc_cbpk_dx_workspace_bytes(int64_t m, int64_t kdim, int64_t ncols, int bits)
 {
@@ -325,7 +296,7 @@ extern "C" int nnc_cbpk_dx_plan(int64_t m, int64_t kdim, int64_t ncols, int bits
     int rc = pg_check("nnc_cbpk_dx_plan", m, kdim, ncols, bits, k);
     if (rc != NNC_OK) return rc;
     const PgPlan p = pg_dx_plan(m, kdim, ncols, bits, std::max(cus, 1));
-    if ((rc = pg_plan_out("nnc_cbpk_dx_plan", p, bits, cus, out)) != NNC_OK) return rc;
+    if ((rc = cbg_plan_out("nnc_cbpk_dx_plan", kPgCases, kPgNames, p.path, bits, p.vb, p.mt, cus, out)) != NNC_OK) return rc;
     const int64_t v[NNC_CBPKDX_PLAN_LEN] = {p.path, p.vb, p.mt, p.cols, p.copies, p.entries, p.splits, p.per_split, p.lds, p.col_tiles, p.row_tiles,
                                             cbg_dx_ws_bytes(p.splits, m, kdim)};
     for (int i = 0; i < NNC_CBPKDX_PLAN_LEN; ++i) out[i] = v[i];
@@ -345,36 +316,29 @@ extern "C" int nnc_cbpk_dx_f32(const float *g, int64_t m, int64_t kdim, const vo
     const int64_t need = nnc_cbpk_dx_workspace_bytes(m, kdim, ncols, bits);
     if ((rc = cb_check_workspace(fn, "nnc_cbpk_dx_workspace_bytes", workspace, workspace_bytes, need, 4, "workspace must be 4-byte aligned")) != NNC_OK) return rc;
     PgPlan p = pg_dx_plan(m, kdim, ncols, bits, CB_PLAN_CUS);
-    const PgCase *pc = p.path == NNC_CBMM_STREAM ? find_pg_case(bits, p.vb, p.mt) : nullptr;
-    if (p.path == NNC_CBMM_STREAM && !pc) return no_pg_case(fn, bits, p.vb, p.mt);
-    if (p.path == NNC_CBMM_NONE) return NNC_OK;
-
+    const PgCase *pc;
+    if ((rc = cbg_stream_case(fn, kPgCases, kPgNames, p.path, bits, p.vb, p.mt, pc)) != NNC_OK) return rc;
     hipStream_t s = S(stream);
-    p = pg_dx_plan(m, kdim, ncols, bits, cu_count());        // (the row groups of this device)
-    if (p.path == NNC_CBMM_ZERO) {
-        HIPCHK(hipMemsetAsync(dx, 0, (size_t)(m * kdim) * 4, s));
-        return NNC_OK;
-    }
-    const int direct = p.splits == 1;
-    float *out = direct ? dx : reinterpret_cast<float *>(workspace);
+    if (p.path != NNC_CBMM_NONE) p = pg_dx_plan(m, kdim, ncols, bits, cu_count());        // (the row groups of this device)
     const unsigned char *pk = reinterpret_cast<const unsigned char *>(packed);
     const long long row_bytes = pk_row_bytes(ncols, bits);
-    if (p.path == NNC_CBMM_STREAM) {
-        pc->dx(dim3((unsigned)p.col_tiles, (unsigned)p.row_tiles), (size_t)p.lds, s, g, (int)m, kdim, pk, row_bytes, ncols, centers_dev, k, p.rows_per_group,
-               direct, out);
-        LAUNCHCHK("k_cbpkdx_stream");
-    } else {
-        const dim3 grid((unsigned)(p.col_tiles * p.row_tiles), (unsigned)p.splits);
-        if (bits == 4)
-            hipLaunchKernelGGL(k_cbpkdx_tiled<4>, grid, dim3(256), (size_t)p.lds, s, g, (long long)m, (long long)kdim, pk, row_bytes, (long long)ncols,
-                               centers_dev, (int)k, p.col_tiles, p.per_split, direct, out);
-        else
-            hipLaunchKernelGGL(k_cbpkdx_tiled<2>, grid, dim3(256), (size_t)p.lds, s, g, (long long)m, (long long)kdim, pk, row_bytes, (long long)ncols,
-                               centers_dev, (int)k, p.col_tiles, p.per_split, direct, out);
-        LAUNCHCHK("k_cbpkdx_tiled");
-    }
-    if (!direct) return cbgrad_reduce(reinterpret_cast<const float *>(workspace), p.splits, m * kdim, dx, s);
-    return NNC_OK;
+    return cbg_run_dx(p.path, p.splits, m, kdim, dx, workspace, s, [&](int direct, float *out) {
+        if (p.path == NNC_CBMM_STREAM) {
+            pc->dx(dim3((unsigned)p.col_tiles, (unsigned)p.row_tiles), (size_t)p.lds, s, g, (int)m, kdim, pk, row_bytes, ncols, centers_dev, k,
+                   p.rows_per_group, direct, out);
+            LAUNCHCHK("k_cbpkdx_stream");
+        } else {
+            const dim3 grid((unsigned)(p.col_tiles * p.row_tiles), (unsigned)p.splits);
+            if (bits == 4)
+                hipLaunchKernelGGL(k_cbpkdx_tiled<4>, grid, dim3(256), (size_t)p.lds, s, g, (long long)m, (long long)kdim, pk, row_bytes, (long long)ncols,
+                                   centers_dev, (int)k, p.col_tiles, p.per_split, direct, out);
+            else
+                hipLaunchKernelGGL(k_cbpkdx_tiled<2>, grid, dim3(256), (size_t)p.lds, s, g, (long long)m, (long long)kdim, pk, row_bytes, (long long)ncols,
+                                   centers_dev, (int)k, p.col_tiles, p.per_split, direct, out);
+            LAUNCHCHK("k_cbpkdx_tiled");
+        }
+        return NNC_OK;
+    });
 }
 
 extern "C" int64_t nnc_cbpk_dc_workspace_bytes(int64_t m, int64_t kdim, int64_t ncols, int bits, int32_t k)
@@ -391,7 +355,7 @@ extern "C" int nnc_cbpk_dc_plan(int64_t m, int64_t kdim, int64_t ncols, int bits
     if (rc != NNC_OK) return rc;
     PgPlan p;
     if ((rc = pg_dc_plan(m, kdim, ncols, bits, k, std::max(cus, 1), p)) != NNC_OK) return rc;
-    if ((rc = pg_plan_out("nnc_cbpk_dc_plan", p, bits, cus, out)) != NNC_OK) return rc;
+    if ((rc = cbg_plan_out("nnc_cbpk_dc_plan", kPgCases, kPgNames, p.path, bits, p.vb, p.mt, cus, out)) != NNC_OK) return rc;
     const int64_t v[NNC_CBPKDC_PLAN_LEN] = {p.path, p.vb, p.mt, p.cols, p.path == NNC_CBMM_ZERO ? 0 : p.copies, p.splits, p.per_split, p.lds,
                                             p.col_tiles, p.row_tiles, p.terms_log2, cbg_dc_ws_bytes(p.path, k)};
     for (int i = 0; i < NNC_CBPKDC_PLAN_LEN; ++i) out[i] = v[i];
@@ -411,35 +375,27 @@ extern "C" int nnc_cbpk_dc_f32(const float *x, const float *g, int64_t m, int64_
     if ((rc = pg_dc_plan(m, kdim, ncols, bits, k, CB_PLAN_CUS, p)) != NNC_OK) return rc;
     const int64_t need = cbg_dc_ws_bytes(p.path, k);
     if ((rc = cb_check_workspace(fn, "nnc_cbpk_dc_workspace_bytes", workspace, workspace_bytes, need, 8, "workspace not 8-byte aligned")) != NNC_OK) return rc;
-    const PgCase *pc = p.path == NNC_CBMM_STREAM ? find_pg_case(bits, p.vb, p.mt) : nullptr;
-    if (p.path == NNC_CBMM_STREAM && !pc) return no_pg_case(fn, bits, p.vb, p.mt);
-
+    const PgCase *pc;
+    if ((rc = cbg_stream_case(fn, kPgCases, kPgNames, p.path, bits, p.vb, p.mt, pc)) != NNC_OK) return rc;
     hipStream_t s = S(stream);
-    const size_t esz = out_f64 ? 8 : 4;
-    if (p.path == NNC_CBMM_ZERO) {
-        HIPCHK(hipMemsetAsync(dc, 0, (size_t)k * esz, s));
-        return NNC_OK;
-    }
-    if ((rc = pg_dc_plan(m, kdim, ncols, bits, k, cu_count(), p)) != NNC_OK) return rc;   // (the row groups of this device)
+    if (p.path != NNC_CBMM_ZERO && (rc = pg_dc_plan(m, kdim, ncols, bits, k, cu_count(), p)) != NNC_OK) return rc;   // (the row groups of this device)
     const unsigned char *pk = reinterpret_cast<const unsigned char *>(packed);
     const long long row_bytes = pk_row_bytes(ncols, bits);
-    uint32_t *hdr = reinterpret_cast<uint32_t *>(workspace);
-    unsigned long long *sums = reinterpret_cast<unsigned long long *>(reinterpret_cast<char *>(workspace) + CBG_HDR_BYTES);
-    HIPCHK(hipMemsetAsync(workspace, 0, (size_t)need, s));
-    if ((rc = cbgrad_absmax(x, m * kdim, g, m * ncols, hdr, s)) != NNC_OK) return rc;
-    if (p.path == NNC_CBMM_STREAM) {
-        pc->dc(dim3((unsigned)p.col_tiles, (unsigned)p.row_tiles), (size_t)p.lds, s, x, g, (int)m, kdim, pk, row_bytes, ncols, k, p.terms_log2,
-               p.rows_per_group, hdr, sums);
-        LAUNCHCHK("k_cbpkdc_stream");
-    } else {
-        const dim3 grid((unsigned)(p.col_tiles * p.row_tiles), (unsigned)p.splits);
-        if (bits == 4)
-            hipLaunchKernelGGL(k_cbpkdc_tiled<4>, grid, dim3(256), (size_t)p.lds, s, x, g, (long long)m, (long long)kdim, pk, row_bytes, (long long)ncols,
-                               (int)k, p.terms_log2, p.col_tiles, p.per_split, hdr, sums);
-        else
-            hipLaunchKernelGGL(k_cbpkdc_tiled<2>, grid, dim3(256), (size_t)p.lds, s, x, g, (long long)m, (long long)kdim, pk, row_bytes, (long long)ncols,
-                               (int)k, p.terms_log2, p.col_tiles, p.per_split, hdr, sums);
-        LAUNCHCHK("k_cbpkdc_tiled");
-    }
-    return cbdc_finish(hdr, reinterpret_cast<const long long *>(sums), (int)k, (int)(out_f64 != 0), dc, s);
+    return cbg_run_dc(p.path, x, g, m, kdim, ncols, (int)k, dc, out_f64, workspace, need, s, [&](uint32_t *hdr, unsigned long long *sums) {
+        if (p.path == NNC_CBMM_STREAM) {
+            pc->dc(dim3((unsigned)p.col_tiles, (unsigned)p.row_tiles), (size_t)p.lds, s, x, g, (int)m, kdim, pk, row_bytes, ncols, k, p.terms_log2,
+                   p.rows_per_group, hdr, sums);
+            LAUNCHCHK("k_cbpkdc_stream");
+        } else {
+            const dim3 grid((unsigned)(p.col_tiles * p.row_tiles), (unsigned)p.splits);
+            if (bits == 4)
+                hipLaunchKernelGGL(k_cbpkdc_tiled<4>, grid, dim3(256), (size_t)p.lds, s, x, g, (long long)m, (long long)kdim, pk, row_bytes, (long long)ncols,
+                                   (int)k, p.terms_log2, p.col_tiles, p.per_split, hdr, sums);
+            else
+                hipLaunchKernelGGL(k_cbpkdc_tiled<2>, grid, dim3(256), (size_t)p.lds, s, x, g, (long long)m, (long long)kdim, pk, row_bytes, (long long)ncols,
+                                   (int)k, p.terms_log2, p.col_tiles, p.per_split, hdr, sums);
+            LAUNCHCHK("k_cbpkdc_tiled");
+        }
+        return NNC_OK;
+    });
 }

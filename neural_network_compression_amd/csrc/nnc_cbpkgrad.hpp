@@ -1,6 +1,7 @@
 // nnc_cbpkgrad.hpp -- the host side the backward pass of the packed codebook matmul (nnc_cbpkgrad.hip) shares with that of the
-// group-wise packed form (nnc_cbpkgrad_grouped.hip): the plans of both directions, the argument check and
-// the two constants of the kernels.  The grouped unit follows these plans unchanged, so the path, the grids, the splits and the
+// group-wise packed form (nnc_cbpkgrad_grouped.hip): the plans of both directions, the argument check,
+// the two constants of the kernels and the list of their stream instantiations.  The glue of the entry points (the lookup in that
+// list, the plan checks, the sequences of HIP calls) is nnc_cbgrad.hpp's, shared with the other backward units.  The grouped unit follows these plans unchanged, so the path, the grids, the splits and the
 // order of every sum are those of nnc_cbpk_dx_f32 / nnc_cbpk_dc_f32 on the same shape.
 #pragma once
 #include "nnc_cbpk.hpp"
@@ -8,6 +9,12 @@
 
 #define PKG_RLOG2 6               // dc: 64 copies of every LDS bin, one per lane (K <= 16: at most 8 KiB)
 #define PKG_G 64                  // stream: g values a lane keeps (columns per lane x rows of m), at most
+
+// The (bits, vb, mt) of the stream kernels pg_stream_grid can ask for, written once: the tables of nnc_cbpkgrad.hip and of
+// nnc_cbpkgrad_grouped.hip are both made from this list, so the grouped unit cannot miss a case the plan produces.
+#define PKG_STREAM_CASES(X)                                                                                                  \
+    X(4, 16, 1) X(4, 8, 1) X(4, 4, 1) X(4, 16, 2) X(4, 8, 2) X(4, 4, 2) X(4, 8, 4) X(4, 4, 4) X(4, 4, 8) X(4, 2, 16)          \
+    X(2, 16, 1) X(2, 8, 1) X(2, 4, 1) X(2, 8, 2) X(2, 4, 2) X(2, 4, 4) X(2, 2, 8) X(2, 1, 16)
 
 // ------------------------------------------------------------------ plans (host)
 struct PgPlan {

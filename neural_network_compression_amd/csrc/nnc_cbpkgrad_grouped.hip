@@ -23,6 +23,11 @@
 // steers a walk comes from blockIdx, the kernel arguments and the readfirstlane'd wave number: every wave of a workgroup reaches
 // every barrier, and no cross-lane read sits in a lane-dependent branch.
 // k_cbgrad_absmax, k_cbgrad_reduce and k_cbdc_finish (over G * K bins) are nnc_cbgrad.hip's.  No float atomics; no host read.
+// What the kernels share with the other units without changing an instruction of any is written once: the
+// step to the next group's rows (cb_group_step, nnc_cbmm.hpp) and the x load of the dc kernel (cbdc_load_x, nnc_cbgrad.hpp).  So
+// is the host side: the sequences of HIP calls of the two entry points (cbg_run_dx, cbg_run_dc), the lookup in the table of
+// stream instantiations, the plan checks and the tail of the plan record (nnc_cbgrad.hpp), the list that table is made from
+// (nnc_cbpkgrad.hpp), the group_rows checks (cb_check_group_rows, nnc_cbmm.hpp).
 #include "nnc_cbpkgrad.hpp"
 
 // ------------------------------------------------------------------ dx, m <= 16
@@ -208,20 +213,13 @@ __global__ __launch_bounds__(CB_THREADS) void k_cbpkdc_stream_grouped(const floa
 
     long long group = (long long)blockIdx.y * rows_per_group / group_rows;
     const long long s_lo = (long long)blockIdx.y * rows_per_group, s_hi = std::min(kdim, s_lo + rows_per_group);
-    long long g_lo = s_lo, g_hi = std::min(s_hi, (group + 1) * group_rows);   // the rows of the workgroup that lie in `group`
-    long long per_wave = (g_hi - g_lo + CB_WAVES - 1) / CB_WAVES;
-    long long i0 = std::min(g_hi, g_lo + wave * per_wave), i1 = std::min(g_hi, i0 + per_wave);
+    long long g_lo = s_lo, g_hi, i0, i1;   // the rows of the workgroup that lie in `group`, and the wave's share of them
+    cb_group_step(group, group_rows, g_lo, s_hi, wave, g_hi, i0, i1);
     const unsigned char *mine = packed + (active ? (long long)blockIdx.x * (64 * VB) + lane * VB : 0LL);
     unsigned long long *mybins = bins + lane;
     __syncthreads();
 
-    // x[r, i + u] of a batch of U rows: lane f holds value f = r * U + u (and f + 64), broadcast by v_readlane (as k_cbdc_stream)
-    auto load_x = [&](long long i, int U, float &xa, float &xb) {
-        const int f0 = lane, f1 = lane + 64;
-        const int r0 = f0 / U, r1 = f1 / U;
-        xa = cbdc_scaled(x[cbdc_idx((long long)r0 * kdim + i + f0 % U, r0 < m)], r0 < m, scx);
-        xb = MT * CB_UNROLL > 64 ? cbdc_scaled(x[cbdc_idx((long long)r1 * kdim + i + f1 % U, r1 < m)], r1 < m, scx) : 0.0f;
-    };
+    auto load_x = [&](long long i, int U, float &xa, float &xb) { cbdc_load_x<MT>(x, kdim, m, scx, lane, i, U, xa, xb); };
     auto consume = [&](const uint32_t *w, float xa, float xb, int u, int U) {
         float xv[MT];
 #pragma unroll
@@ -262,9 +260,7 @@ __global__ __launch_bounds__(CB_THREADS) void k_cbpkdc_stream_grouped(const floa
         for (int j = threadIdx.x; j < k; j += CB_THREADS)   // the copies this thread has just summed
             for (int r = 0; r < (1 << PKG_RLOG2); ++r) bins[(j << PKG_RLOG2) + r] = 0ull;
         g_lo = g_hi;
-        g_hi = std::min(s_hi, (++group + 1) * group_rows);
-        per_wave = (g_hi - g_lo + CB_WAVES - 1) / CB_WAVES;
-        i0 = std::min(g_hi, g_lo + wave * per_wave), i1 = std::min(g_hi, i0 + per_wave);
+        cb_group_step(++group, group_rows, g_lo, s_hi, wave, g_hi, i0, i1);
         __syncthreads();
     }
 }
@@ -326,37 +322,20 @@ static void launch_pgg_dc(dim3 grid, size_t lds, hipStream_t s, const float *x, 
                        hdr, sums);
 }
 
-// every stream instantiation of this unit: the (bits, vb, mt) of nnc_cbpkgrad.hip's table, so the plan leaves no shape out
+// every stream instantiation of this unit: the list of nnc_cbpkgrad.hpp, which nnc_cbpkgrad.hip's table is made from too
 using PggDxLaunch = void (*)(dim3, size_t, hipStream_t, const float *, int, long long, const unsigned char *, long long, long long, const float *, int,
                              long long, long long, int, float *);
 using PggDcLaunch = void (*)(dim3, size_t, hipStream_t, const float *, const float *, int, long long, const unsigned char *, long long, long long, int, int,
                              long long, long long, uint32_t *, unsigned long long *);
 struct PggCase {
-    int bits, vb, mt;
+    int a, vb, mt;            // a: bits
     PggDxLaunch dx;
     PggDcLaunch dc;
 };
-#define PGG_CASE(B, V, M) {B, V, M, launch_pgg_dx<B, V, M>, launch_pgg_dc<B, V, M>}
-static const PggCase kPggCases[] = {
-    PGG_CASE(4, 16, 1), PGG_CASE(4, 8, 1), PGG_CASE(4, 4, 1), PGG_CASE(4, 16, 2), PGG_CASE(4, 8, 2), PGG_CASE(4, 4, 2), PGG_CASE(4, 8, 4),
-    PGG_CASE(4, 4, 4),  PGG_CASE(4, 4, 8), PGG_CASE(4, 2, 16),
-    PGG_CASE(2, 16, 1), PGG_CASE(2, 8, 1), PGG_CASE(2, 4, 1), PGG_CASE(2, 8, 2),  PGG_CASE(2, 4, 2), PGG_CASE(2, 4, 4), PGG_CASE(2, 2, 8),
-    PGG_CASE(2, 1, 16),
-};
+#define PGG_CASE(B, V, M) {B, V, M, launch_pgg_dx<B, V, M>, launch_pgg_dc<B, V, M>},
+static const PggCase kPggCases[] = {PKG_STREAM_CASES(PGG_CASE)};
 #undef PGG_CASE
-
-static const PggCase *find_pgg_case(int bits, int vb, int mt)
-{
-    for (const PggCase &c : kPggCases)
-        if (c.bits == bits && c.vb == vb && c.mt == mt) return &c;
-    return nullptr;
-}
-
-static int no_pgg_case(const char *fn, int bits, int vb, int mt)
-{
-    return fail(NNC_EINVAL, std::string(fn) + ": no grouped stream instantiation for bits " + std::to_string(bits) + ", vb " + std::to_string(vb) + ", mt " +
-                                std::to_string(mt));
-}
+static const CbgCaseNames kPggNames = {true, "bits", true};
 
 // ------------------------------------------------------------------ C ABI
 // pg_check's checks, then those nnc_cbpk_grouped makes of group_rows and the bound on the G * k bins
@@ -364,10 +343,7 @@ static int pgg_check(const char *fn, int64_t m, int64_t kdim, int64_t ncols, int
 {
     const int rc = pg_check(fn, m, kdim, ncols, bits, k);
     if (rc != NNC_OK) return rc;
-    if (group_rows < 32 || group_rows % 32) return fail(NNC_EINVAL, std::string(fn) + ": group_rows must be a positive multiple of 32");
-    if (group_rows > (1LL << 40)) return fail(NNC_EINVAL, std::string(fn) + ": size too large");
-    if (gg_groups(kdim, group_rows) * k > (1LL << 30)) return fail(NNC_EINVAL, std::string(fn) + ": more than 2^30 bins (groups * k)");
-    return NNC_OK;
+    return cb_check_group_rows(fn, kdim, group_rows, k);
 }
 
 // the dx LDS: one table per wave (stream), or the tile's images and one table per group of the tile (tiled)
@@ -383,26 +359,6 @@ static void pgg_dx_lds(PgPlan &p, long long group_rows, int &tables)
     }
 }
 
-// the five values a grouped plan adds to the ungrouped record
-static void pgg_plan_tail(const PgPlan &p, long long kdim, long long group_rows, int held, int64_t *out)
-{
-    const bool stream = p.path == NNC_CBMM_STREAM, tiled = p.path == NNC_CBMM_TILED;
-    out[0] = group_rows;
-    out[1] = kdim > 0 ? cdiv(kdim, group_rows) : 0;
-    out[2] = stream ? p.rows_per_group : 0;
-    out[3] = stream ? max_groups_per_split(p.row_tiles, p.rows_per_group, kdim, group_rows)
-                    : (tiled ? max_groups_per_split(cdiv(kdim, 128), 128, kdim, group_rows) : 0);
-    out[4] = held;
-}
-
-static int pgg_plan_out(const char *fn, const PgPlan &p, int bits, int32_t cus, const int64_t *out)
-{
-    if (cus < 1) return fail(NNC_EINVAL, std::string(fn) + ": cus < 1");
-    if (!out) return fail(NNC_EINVAL, std::string(fn) + ": out is NULL");
-    if (p.path == NNC_CBMM_STREAM && !find_pgg_case(bits, p.vb, p.mt)) return no_pgg_case(fn, bits, p.vb, p.mt);
-    return NNC_OK;
-}
-
 extern "C" int64_t nnc_cbpk_grouped_dx_workspace_bytes(int64_t m, int64_t kdim, int64_t ncols, int bits)
 {
     if (pg_check("nnc_cbpk_grouped_dx_workspace_bytes", m, kdim, ncols, bits, 1) != NNC_OK) return 0;
@@ -415,13 +371,14 @@ extern "C" int nnc_cbpk_grouped_dx_plan(int64_t m, int64_t kdim, int64_t ncols, 
     int rc = pgg_check(fn, m, kdim, ncols, bits, k, group_rows);
     if (rc != NNC_OK) return rc;
     PgPlan p = pg_dx_plan(m, kdim, ncols, bits, std::max(cus, 1));
-    if ((rc = pgg_plan_out(fn, p, bits, cus, out)) != NNC_OK) return rc;
+    if ((rc = cbg_plan_out(fn, kPggCases, kPggNames, p.path, bits, p.vb, p.mt, cus, out)) != NNC_OK) return rc;
     int tables;
     pgg_dx_lds(p, group_rows, tables);
     const int64_t v[NNC_CBPKDX_PLAN_LEN] = {p.path, p.vb, p.mt, p.cols, p.copies, p.entries, p.splits, p.per_split, p.lds, p.col_tiles, p.row_tiles,
                                             cbg_dx_ws_bytes(p.splits, m, kdim)};
     for (int i = 0; i < NNC_CBPKDX_PLAN_LEN; ++i) out[i] = v[i];
-    pgg_plan_tail(p, kdim, group_rows, tables, out + NNC_CBPKDX_PLAN_LEN);
+    cbg_grouped_plan_tail(p.path, p.row_tiles, p.rows_per_group, kdim, group_rows, out + NNC_CBPKDX_PLAN_LEN);
+    out[NNC_CBPKDX_PLAN_LEN + 4] = tables;
     return NNC_OK;
 }
 
@@ -440,38 +397,31 @@ extern "C" int nnc_cbpk_grouped_dx_f32(const float *g, int64_t m, int64_t kdim, 
     if ((rc = cb_check_workspace(fn, "nnc_cbpk_grouped_dx_workspace_bytes", workspace, workspace_bytes, need, 4, "workspace must be 4-byte aligned")) != NNC_OK)
         return rc;
     PgPlan p = pg_dx_plan(m, kdim, ncols, bits, CB_PLAN_CUS);
-    const PggCase *pc = p.path == NNC_CBMM_STREAM ? find_pgg_case(bits, p.vb, p.mt) : nullptr;
-    if (p.path == NNC_CBMM_STREAM && !pc) return no_pgg_case(fn, bits, p.vb, p.mt);
-    if (p.path == NNC_CBMM_NONE) return NNC_OK;
-
+    const PggCase *pc;
+    if ((rc = cbg_stream_case(fn, kPggCases, kPggNames, p.path, bits, p.vb, p.mt, pc)) != NNC_OK) return rc;
     hipStream_t s = S(stream);
-    p = pg_dx_plan(m, kdim, ncols, bits, cu_count());        // (the row groups of this device)
-    if (p.path == NNC_CBMM_ZERO) {
-        HIPCHK(hipMemsetAsync(dx, 0, (size_t)(m * kdim) * 4, s));
-        return NNC_OK;
-    }
+    if (p.path != NNC_CBMM_NONE) p = pg_dx_plan(m, kdim, ncols, bits, cu_count());        // (the row groups of this device)
     int tables;
     pgg_dx_lds(p, group_rows, tables);
-    const int direct = p.splits == 1;
-    float *out = direct ? dx : reinterpret_cast<float *>(workspace);
     const unsigned char *pk = reinterpret_cast<const unsigned char *>(packed);
     const long long row_bytes = pk_row_bytes(ncols, bits);
-    if (p.path == NNC_CBMM_STREAM) {
-        pc->dx(dim3((unsigned)p.col_tiles, (unsigned)p.row_tiles), (size_t)p.lds, s, g, (int)m, kdim, pk, row_bytes, ncols, centers_dev, k, p.rows_per_group,
-               group_rows, direct, out);
-        LAUNCHCHK("k_cbpkdx_stream_grouped");
-    } else {
-        const dim3 grid((unsigned)(p.col_tiles * p.row_tiles), (unsigned)p.splits);
-        if (bits == 4)
-            hipLaunchKernelGGL(k_cbpkdx_tiled_grouped<4>, grid, dim3(256), (size_t)p.lds, s, g, (long long)m, (long long)kdim, pk, row_bytes, (long long)ncols,
-                               centers_dev, (int)k, p.col_tiles, p.per_split, (long long)group_rows, tables, direct, out);
-        else
-            hipLaunchKernelGGL(k_cbpkdx_tiled_grouped<2>, grid, dim3(256), (size_t)p.lds, s, g, (long long)m, (long long)kdim, pk, row_bytes, (long long)ncols,
-                               centers_dev, (int)k, p.col_tiles, p.per_split, (long long)group_rows, tables, direct, out);
-        LAUNCHCHK("k_cbpkdx_tiled_grouped");
-    }
-    if (!direct) return cbgrad_reduce(reinterpret_cast<const float *>(workspace), p.splits, m * kdim, dx, s);
-    return NNC_OK;
+    return cbg_run_dx(p.path, p.splits, m, kdim, dx, workspace, s, [&](int direct, float *out) {
+        if (p.path == NNC_CBMM_STREAM) {
+            pc->dx(dim3((unsigned)p.col_tiles, (unsigned)p.row_tiles), (size_t)p.lds, s, g, (int)m, kdim, pk, row_bytes, ncols, centers_dev, k,
+                   p.rows_per_group, group_rows, direct, out);
+            LAUNCHCHK("k_cbpkdx_stream_grouped");
+        } else {
+            const dim3 grid((unsigned)(p.col_tiles * p.row_tiles), (unsigned)p.splits);
+            if (bits == 4)
+                hipLaunchKernelGGL(k_cbpkdx_tiled_grouped<4>, grid, dim3(256), (size_t)p.lds, s, g, (long long)m, (long long)kdim, pk, row_bytes,
+                                   (long long)ncols, centers_dev, (int)k, p.col_tiles, p.per_split, (long long)group_rows, tables, direct, out);
+            else
+                hipLaunchKernelGGL(k_cbpkdx_tiled_grouped<2>, grid, dim3(256), (size_t)p.lds, s, g, (long long)m, (long long)kdim, pk, row_bytes,
+                                   (long long)ncols, centers_dev, (int)k, p.col_tiles, p.per_split, (long long)group_rows, tables, direct, out);
+            LAUNCHCHK("k_cbpkdx_tiled_grouped");
+        }
+        return NNC_OK;
+    });
 }
 
 extern "C" int64_t nnc_cbpk_grouped_dc_workspace_bytes(int64_t m, int64_t kdim, int64_t ncols, int bits, int32_t k, int64_t group_rows)
@@ -489,14 +439,15 @@ extern "C" int nnc_cbpk_grouped_dc_plan(int64_t m, int64_t kdim, int64_t ncols, 
     if (rc != NNC_OK) return rc;
     PgPlan p;
     if ((rc = pg_dc_plan(m, kdim, ncols, bits, k, std::max(cus, 1), p)) != NNC_OK) return rc;
-    if ((rc = pgg_plan_out(fn, p, bits, cus, out)) != NNC_OK) return rc;
+    if ((rc = cbg_plan_out(fn, kPggCases, kPggNames, p.path, bits, p.vb, p.mt, cus, out)) != NNC_OK) return rc;
     const bool tiled = p.path == NNC_CBMM_TILED;
     const int sets = tiled ? tile_groups(group_rows) : (p.path == NNC_CBMM_STREAM ? 1 : 0);
     const int64_t v[NNC_CBPKDC_PLAN_LEN] = {p.path, p.vb, p.mt, p.cols, p.path == NNC_CBMM_ZERO ? 0 : p.copies / std::max(sets, 1), p.splits, p.per_split,
                                             p.lds, p.col_tiles, p.row_tiles, p.terms_log2,
                                             cbg_dc_ws_bytes(p.path, (int)(gg_groups(kdim, group_rows) * k))};
     for (int i = 0; i < NNC_CBPKDC_PLAN_LEN; ++i) out[i] = v[i];
-    pgg_plan_tail(p, kdim, group_rows, sets, out + NNC_CBPKDC_PLAN_LEN);
+    cbg_grouped_plan_tail(p.path, p.row_tiles, p.rows_per_group, kdim, group_rows, out + NNC_CBPKDC_PLAN_LEN);
+    out[NNC_CBPKDC_PLAN_LEN + 4] = sets;
     return NNC_OK;
 }
 
@@ -516,35 +467,28 @@ extern "C" int nnc_cbpk_grouped_dc_f32(const float *x, const float *g, int64_t m
     const int64_t need = cbg_dc_ws_bytes(p.path, nbins);
     if ((rc = cb_check_workspace(fn, "nnc_cbpk_grouped_dc_workspace_bytes", workspace, workspace_bytes, need, 8, "workspace not 8-byte aligned")) != NNC_OK)
         return rc;
-    const PggCase *pc = p.path == NNC_CBMM_STREAM ? find_pgg_case(bits, p.vb, p.mt) : nullptr;
-    if (p.path == NNC_CBMM_STREAM && !pc) return no_pgg_case(fn, bits, p.vb, p.mt);
-
+    const PggCase *pc;
+    if ((rc = cbg_stream_case(fn, kPggCases, kPggNames, p.path, bits, p.vb, p.mt, pc)) != NNC_OK) return rc;
     hipStream_t s = S(stream);
-    if (p.path == NNC_CBMM_ZERO) {
-        HIPCHK(hipMemsetAsync(dc, 0, (size_t)nbins * (out_f64 ? 8 : 4), s));
-        return NNC_OK;
-    }
-    if ((rc = pg_dc_plan(m, kdim, ncols, bits, k, cu_count(), p)) != NNC_OK) return rc;   // (the row groups of this device)
+    if (p.path != NNC_CBMM_ZERO && (rc = pg_dc_plan(m, kdim, ncols, bits, k, cu_count(), p)) != NNC_OK) return rc;   // (the row groups of this device)
     const unsigned char *pk = reinterpret_cast<const unsigned char *>(packed);
     const long long row_bytes = pk_row_bytes(ncols, bits);
-    uint32_t *hdr = reinterpret_cast<uint32_t *>(workspace);
-    unsigned long long *sums = reinterpret_cast<unsigned long long *>(reinterpret_cast<char *>(workspace) + CBG_HDR_BYTES);
-    HIPCHK(hipMemsetAsync(workspace, 0, (size_t)need, s));
-    if ((rc = cbgrad_absmax(x, m * kdim, g, m * ncols, hdr, s)) != NNC_OK) return rc;
-    if (p.path == NNC_CBMM_STREAM) {
-        pc->dc(dim3((unsigned)p.col_tiles, (unsigned)p.row_tiles), (size_t)p.lds, s, x, g, (int)m, kdim, pk, row_bytes, ncols, k, p.terms_log2,
-               p.rows_per_group, group_rows, hdr, sums);
-        LAUNCHCHK("k_cbpkdc_stream_grouped");
-    } else {
-        const int sets_log2 = __builtin_ctz(tile_groups(group_rows));
-        const dim3 grid((unsigned)(p.col_tiles * p.row_tiles), (unsigned)p.splits);
-        if (bits == 4)
-            hipLaunchKernelGGL(k_cbpkdc_tiled_grouped<4>, grid, dim3(256), (size_t)p.lds, s, x, g, (long long)m, (long long)kdim, pk, row_bytes, (long long)ncols,
-                               (int)k, sets_log2, p.terms_log2, p.col_tiles, p.per_split, (long long)group_rows, hdr, sums);
-        else
-            hipLaunchKernelGGL(k_cbpkdc_tiled_grouped<2>, grid, dim3(256), (size_t)p.lds, s, x, g, (long long)m, (long long)kdim, pk, row_bytes, (long long)ncols,
-                               (int)k, sets_log2, p.terms_log2, p.col_tiles, p.per_split, (long long)group_rows, hdr, sums);
-        LAUNCHCHK("k_cbpkdc_tiled_grouped");
-    }
-    return cbdc_finish(hdr, reinterpret_cast<const long long *>(sums), nbins, (int)(out_f64 != 0), dc, s);
+    return cbg_run_dc(p.path, x, g, m, kdim, ncols, nbins, dc, out_f64, workspace, need, s, [&](uint32_t *hdr, unsigned long long *sums) {
+        if (p.path == NNC_CBMM_STREAM) {
+            pc->dc(dim3((unsigned)p.col_tiles, (unsigned)p.row_tiles), (size_t)p.lds, s, x, g, (int)m, kdim, pk, row_bytes, ncols, k, p.terms_log2,
+                   p.rows_per_group, group_rows, hdr, sums);
+            LAUNCHCHK("k_cbpkdc_stream_grouped");
+        } else {
+            const int sets_log2 = __builtin_ctz(tile_groups(group_rows));
+            const dim3 grid((unsigned)(p.col_tiles * p.row_tiles), (unsigned)p.splits);
+            if (bits == 4)
+                hipLaunchKernelGGL(k_cbpkdc_tiled_grouped<4>, grid, dim3(256), (size_t)p.lds, s, x, g, (long long)m, (long long)kdim, pk, row_bytes,
+                                   (long long)ncols, (int)k, sets_log2, p.terms_log2, p.col_tiles, p.per_split, (long long)group_rows, hdr, sums);
+            else
+                hipLaunchKernelGGL(k_cbpkdc_tiled_grouped<2>, grid, dim3(256), (size_t)p.lds, s, x, g, (long long)m, (long long)kdim, pk, row_bytes,
+                                   (long long)ncols, (int)k, sets_log2, p.terms_log2, p.col_tiles, p.per_split, (long long)group_rows, hdr, sums);
+            LAUNCHCHK("k_cbpkdc_tiled_grouped");
+        }
+        return NNC_OK;
+    });
 }

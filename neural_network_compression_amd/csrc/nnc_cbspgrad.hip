@@ -27,6 +27,8 @@
 //                    thread's 64 values takes its label from the bitmap word, the count and the popcount; the skipped ones are
 //                    summed in a register.
 // k_cbgrad_absmax, k_cbdc_finish and k_cbgrad_reduce are nnc_cbgrad.hip's.  No float atomics; no host read.
+// The sequences of HIP calls of the two entry points (cbg_run_dx, cbg_run_dc) and the lookup in the table of stream instantiations
+// are nnc_cbgrad.hpp's; the row sums and the rank-1 term of dx stay here, around that sequence.
 #include "nnc_cbsp.hpp"
 #include "nnc_cbtile.hpp"
 
@@ -503,36 +505,17 @@ using SgDxLaunch = void (*)(dim3, size_t, hipStream_t, const float *, int, long 
 using SgDcLaunch = void (*)(dim3, size_t, hipStream_t, const float *, const float *, int, long long, const unsigned char *, const SpLayout &, long long,
                             long long, int, int, const SgPlan &, uint32_t *, unsigned long long *);
 struct SgCase {
-    int lb, mt;
+    int a, vb, mt;            // a: label_bytes; vb: 0 (a lane's columns are fixed by mt)
     SgDxLaunch dx;
     SgDcLaunch dc;
 };
-#define SG_CASE(LT, LB, MT) {LB, MT, launch_sg_dx<LT, MT>, launch_sg_dc<LT, MT>}
+#define SG_CASE(LT, LB, MT) {LB, 0, MT, launch_sg_dx<LT, MT>, launch_sg_dc<LT, MT>}
 static const SgCase kSgCases[] = {
     SG_CASE(uint8_t, 1, 1),  SG_CASE(uint8_t, 1, 2),  SG_CASE(uint8_t, 1, 4),  SG_CASE(uint8_t, 1, 8),  SG_CASE(uint8_t, 1, 16),
     SG_CASE(uint16_t, 2, 1), SG_CASE(uint16_t, 2, 2), SG_CASE(uint16_t, 2, 4), SG_CASE(uint16_t, 2, 8), SG_CASE(uint16_t, 2, 16),
 };
 #undef SG_CASE
-
-static const SgCase *find_sg_case(int lb, int mt)
-{
-    for (const SgCase &c : kSgCases)
-        if (c.lb == lb && c.mt == mt) return &c;
-    return nullptr;
-}
-
-static int no_sg_case(const char *fn, int lb, int mt)
-{
-    return fail(NNC_EINVAL, std::string(fn) + ": no stream instantiation for label_bytes " + std::to_string(lb) + ", mt " + std::to_string(mt));
-}
-
-static int sg_plan_out(const char *fn, const SgPlan &p, int lb, int32_t cus, int64_t *out)
-{
-    if (cus < 1) return fail(NNC_EINVAL, std::string(fn) + ": cus < 1");
-    if (!out) return fail(NNC_EINVAL, std::string(fn) + ": out is NULL");
-    if (p.path == NNC_CBMM_STREAM && !find_sg_case(lb, p.mt)) return no_sg_case(fn, lb, p.mt);
-    return NNC_OK;
-}
+static const CbgCaseNames kSgNames = {false, "label_bytes", false};
 
 extern "C" int64_t nnc_cbsp_dx_workspace_bytes(int64_t m, int64_t kdim, int64_t ncols, int label_bytes)
 {
@@ -545,7 +528,7 @@ extern "C" int nnc_cbsp_dx_plan(int64_t m, int64_t kdim, int64_t ncols, int labe
     int rc = sg_check("nnc_cbsp_dx_plan", m, kdim, ncols, label_bytes, k);
     if (rc != NNC_OK) return rc;
     const SgPlan p = sg_dx_plan(m, kdim, ncols, label_bytes, k, cus);
-    if ((rc = sg_plan_out("nnc_cbsp_dx_plan", p, label_bytes, cus, out)) != NNC_OK) return rc;
+    if ((rc = cbg_plan_out("nnc_cbsp_dx_plan", kSgCases, kSgNames, p.path, label_bytes, 0, p.mt, cus, out)) != NNC_OK) return rc;
     const int64_t v[NNC_CBSPDX_PLAN_LEN] = {p.path, p.mt, p.segs, p.path == NNC_CBMM_STREAM ? 1LL << p.cshift : (p.entries ? 1 : 0), p.entries,
                                             p.splits, p.per_split, p.lds, p.col_tiles, p.row_tiles, sg_dx_ws_bytes(p, m, kdim)};
     for (int i = 0; i < NNC_CBSPDX_PLAN_LEN; ++i) out[i] = v[i];
@@ -566,41 +549,37 @@ extern "C" int nnc_cbsp_dx_f32(const float *g, int64_t m, int64_t kdim, const vo
     const int64_t need = nnc_cbsp_dx_workspace_bytes(m, kdim, ncols, label_bytes);
     if ((rc = cb_check_workspace(fn, "nnc_cbsp_dx_workspace_bytes", workspace, workspace_bytes, need, 4, "workspace must be 4-byte aligned")) != NNC_OK) return rc;
     const SgPlan p = sg_dx_plan(m, kdim, ncols, label_bytes, k, cu_count());
-    const SgCase *sc = p.path == NNC_CBMM_STREAM ? find_sg_case(label_bytes, p.mt) : nullptr;
-    if (p.path == NNC_CBMM_STREAM && !sc) return no_sg_case(fn, label_bytes, p.mt);
-    if (p.path == NNC_CBMM_NONE) return NNC_OK;
-
+    const SgCase *sc;
+    if ((rc = cbg_stream_case(fn, kSgCases, kSgNames, p.path, label_bytes, 0, p.mt, sc)) != NNC_OK) return rc;
     hipStream_t s = S(stream);
-    if (p.path == NNC_CBMM_ZERO) {
-        HIPCHK(hipMemsetAsync(dx, 0, (size_t)(m * kdim) * 4, s));
-        return NNC_OK;
-    }
     const SpLayout L = sp_layout(kdim, ncols, label_bytes, nnz);
     const unsigned char *base = reinterpret_cast<const unsigned char *>(packed);
-    const int direct = p.splits == 1;
-    float *part = reinterpret_cast<float *>(workspace);
-    float *rs = reinterpret_cast<float *>(reinterpret_cast<unsigned char *>(workspace) + sg_part_bytes(p, m, kdim));
-    float *out = direct ? dx : part;
-    if ((rc = cbsp_rowsum(g, m, ncols, rs, s)) != NNC_OK) return rc;
-    if (p.path == NNC_CBMM_STREAM) {
-        sc->dx(dim3((unsigned)p.col_tiles, (unsigned)p.row_tiles), (size_t)p.lds, s, g, (int)m, kdim, base, L, nnz, ncols, centers_dev, k, zero_symbol, p,
-               direct, out);
-        LAUNCHCHK("k_cbspdx_stream");
-    } else {
-        const dim3 grid((unsigned)(p.col_tiles * p.row_tiles), (unsigned)p.splits);
-        const uint64_t *bm = reinterpret_cast<const uint64_t *>(base);
-        const uint32_t *lo = reinterpret_cast<const uint32_t *>(base + L.off_lo), *hi = reinterpret_cast<const uint32_t *>(base + L.off_hi);
-        if (label_bytes == 1)
-            hipLaunchKernelGGL(k_cbspdx_tiled<uint8_t>, grid, dim3(256), (size_t)p.lds, s, g, (long long)m, (long long)kdim, bm, lo, hi,
-                               reinterpret_cast<const uint8_t *>(base + L.off_sym), (long long)nnz, (long long)ncols, L.segs, centers_dev, (int)k,
-                               (int)zero_symbol, p.col_tiles, p.per_split, direct, out);
-        else
-            hipLaunchKernelGGL(k_cbspdx_tiled<uint16_t>, grid, dim3(256), (size_t)p.lds, s, g, (long long)m, (long long)kdim, bm, lo, hi,
-                               reinterpret_cast<const uint16_t *>(base + L.off_sym), (long long)nnz, (long long)ncols, L.segs, centers_dev, (int)k,
-                               (int)zero_symbol, p.col_tiles, p.per_split, direct, out);
-        LAUNCHCHK("k_cbspdx_tiled");
-    }
-    if (!direct && (rc = cbgrad_reduce(part, p.splits, m * kdim, dx, s)) != NNC_OK) return rc;
+    float *rs = reinterpret_cast<float *>(reinterpret_cast<unsigned char *>(workspace) + sg_part_bytes(p, m, kdim));   // behind the partials
+    // the row sums of g ahead of the kernel, the rank-1 term behind the reduce: the two steps the other forms do not have
+    rc = cbg_run_dx(p.path, p.splits, m, kdim, dx, workspace, s, [&](int direct, float *out) {
+        const int rr = cbsp_rowsum(g, m, ncols, rs, s);
+        if (rr != NNC_OK) return rr;
+        if (p.path == NNC_CBMM_STREAM) {
+            sc->dx(dim3((unsigned)p.col_tiles, (unsigned)p.row_tiles), (size_t)p.lds, s, g, (int)m, kdim, base, L, nnz, ncols, centers_dev, k, zero_symbol, p,
+                   direct, out);
+            LAUNCHCHK("k_cbspdx_stream");
+        } else {
+            const dim3 grid((unsigned)(p.col_tiles * p.row_tiles), (unsigned)p.splits);
+            const uint64_t *bm = reinterpret_cast<const uint64_t *>(base);
+            const uint32_t *lo = reinterpret_cast<const uint32_t *>(base + L.off_lo), *hi = reinterpret_cast<const uint32_t *>(base + L.off_hi);
+            if (label_bytes == 1)
+                hipLaunchKernelGGL(k_cbspdx_tiled<uint8_t>, grid, dim3(256), (size_t)p.lds, s, g, (long long)m, (long long)kdim, bm, lo, hi,
+                                   reinterpret_cast<const uint8_t *>(base + L.off_sym), (long long)nnz, (long long)ncols, L.segs, centers_dev, (int)k,
+                                   (int)zero_symbol, p.col_tiles, p.per_split, direct, out);
+            else
+                hipLaunchKernelGGL(k_cbspdx_tiled<uint16_t>, grid, dim3(256), (size_t)p.lds, s, g, (long long)m, (long long)kdim, bm, lo, hi,
+                                   reinterpret_cast<const uint16_t *>(base + L.off_sym), (long long)nnz, (long long)ncols, L.segs, centers_dev, (int)k,
+                                   (int)zero_symbol, p.col_tiles, p.per_split, direct, out);
+            LAUNCHCHK("k_cbspdx_tiled");
+        }
+        return NNC_OK;
+    });
+    if (rc != NNC_OK || (p.path != NNC_CBMM_STREAM && p.path != NNC_CBMM_TILED)) return rc;
     const int rgrid = (int)std::max(1LL, std::min(cdiv(m * kdim, 256), 8192LL));
     hipLaunchKernelGGL(k_cbspdx_rank1, dim3(rgrid), dim3(256), 0, s, dx, (long long)m, (long long)kdim, rs, centers_dev, (int)k, (int)zero_symbol);
     LAUNCHCHK("k_cbspdx_rank1");
@@ -621,7 +600,7 @@ extern "C" int nnc_cbsp_dc_plan(int64_t m, int64_t kdim, int64_t ncols, int labe
     if (rc != NNC_OK) return rc;
     SgPlan p;
     if ((rc = sg_dc_plan(m, kdim, ncols, label_bytes, k, cus, p)) != NNC_OK) return rc;
-    if ((rc = sg_plan_out("nnc_cbsp_dc_plan", p, label_bytes, cus, out)) != NNC_OK) return rc;
+    if ((rc = cbg_plan_out("nnc_cbsp_dc_plan", kSgCases, kSgNames, p.path, label_bytes, 0, p.mt, cus, out)) != NNC_OK) return rc;
     const int64_t v[NNC_CBSPDC_PLAN_LEN] = {p.path, p.mt, p.segs, p.path == NNC_CBMM_ZERO ? 0 : 1LL << p.rlog2, p.splits, p.per_split, p.lds,
                                             p.col_tiles, p.row_tiles, p.terms_log2, cbg_dc_ws_bytes(p.path, k)};
     for (int i = 0; i < NNC_CBSPDC_PLAN_LEN; ++i) out[i] = v[i];
@@ -642,37 +621,29 @@ extern "C" int nnc_cbsp_dc_f32(const float *x, const float *g, int64_t m, int64_
     if ((rc = cb_check_workspace(fn, "nnc_cbsp_dc_workspace_bytes", workspace, workspace_bytes, need, 8, "workspace not 8-byte aligned")) != NNC_OK) return rc;
     SgPlan p;
     if ((rc = sg_dc_plan(m, kdim, ncols, label_bytes, k, cu_count(), p)) != NNC_OK) return rc;
-    const SgCase *sc = p.path == NNC_CBMM_STREAM ? find_sg_case(label_bytes, p.mt) : nullptr;
-    if (p.path == NNC_CBMM_STREAM && !sc) return no_sg_case(fn, label_bytes, p.mt);
-
+    const SgCase *sc;
+    if ((rc = cbg_stream_case(fn, kSgCases, kSgNames, p.path, label_bytes, 0, p.mt, sc)) != NNC_OK) return rc;
     hipStream_t s = S(stream);
-    const size_t esz = out_f64 ? 8 : 4;
-    if (p.path == NNC_CBMM_ZERO) {
-        HIPCHK(hipMemsetAsync(dc, 0, (size_t)k * esz, s));
-        return NNC_OK;
-    }
     const SpLayout L = sp_layout(kdim, ncols, label_bytes, nnz);
     const unsigned char *base = reinterpret_cast<const unsigned char *>(packed);
-    uint32_t *hdr = reinterpret_cast<uint32_t *>(workspace);
-    unsigned long long *sums = reinterpret_cast<unsigned long long *>(reinterpret_cast<char *>(workspace) + CBG_HDR_BYTES);
-    HIPCHK(hipMemsetAsync(workspace, 0, (size_t)need, s));
-    if ((rc = cbgrad_absmax(x, m * kdim, g, m * ncols, hdr, s)) != NNC_OK) return rc;
-    if (p.path == NNC_CBMM_STREAM) {
-        sc->dc(dim3((unsigned)p.col_tiles, (unsigned)p.row_tiles), (size_t)p.lds, s, x, g, (int)m, kdim, base, L, nnz, ncols, k, zero_symbol, p, hdr, sums);
-        LAUNCHCHK("k_cbspdc_stream");
-    } else {
-        const dim3 grid((unsigned)(p.col_tiles * p.row_tiles), (unsigned)p.splits);
-        const uint64_t *bm = reinterpret_cast<const uint64_t *>(base);
-        const uint32_t *lo = reinterpret_cast<const uint32_t *>(base + L.off_lo), *hi = reinterpret_cast<const uint32_t *>(base + L.off_hi);
-        if (label_bytes == 1)
-            hipLaunchKernelGGL(k_cbspdc_tiled<uint8_t>, grid, dim3(256), (size_t)p.lds, s, x, g, (long long)m, (long long)kdim, bm, lo, hi,
-                               reinterpret_cast<const uint8_t *>(base + L.off_sym), (long long)nnz, (long long)ncols, L.segs, (int)k, (int)zero_symbol,
-                               p.rlog2, p.terms_log2, p.col_tiles, p.per_split, hdr, sums);
-        else
-            hipLaunchKernelGGL(k_cbspdc_tiled<uint16_t>, grid, dim3(256), (size_t)p.lds, s, x, g, (long long)m, (long long)kdim, bm, lo, hi,
-                               reinterpret_cast<const uint16_t *>(base + L.off_sym), (long long)nnz, (long long)ncols, L.segs, (int)k, (int)zero_symbol,
-                               p.rlog2, p.terms_log2, p.col_tiles, p.per_split, hdr, sums);
-        LAUNCHCHK("k_cbspdc_tiled");
-    }
-    return cbdc_finish(hdr, reinterpret_cast<const long long *>(sums), (int)k, (int)(out_f64 != 0), dc, s);
+    return cbg_run_dc(p.path, x, g, m, kdim, ncols, (int)k, dc, out_f64, workspace, need, s, [&](uint32_t *hdr, unsigned long long *sums) {
+        if (p.path == NNC_CBMM_STREAM) {
+            sc->dc(dim3((unsigned)p.col_tiles, (unsigned)p.row_tiles), (size_t)p.lds, s, x, g, (int)m, kdim, base, L, nnz, ncols, k, zero_symbol, p, hdr, sums);
+            LAUNCHCHK("k_cbspdc_stream");
+        } else {
+            const dim3 grid((unsigned)(p.col_tiles * p.row_tiles), (unsigned)p.splits);
+            const uint64_t *bm = reinterpret_cast<const uint64_t *>(base);
+            const uint32_t *lo = reinterpret_cast<const uint32_t *>(base + L.off_lo), *hi = reinterpret_cast<const uint32_t *>(base + L.off_hi);
+            if (label_bytes == 1)
+                hipLaunchKernelGGL(k_cbspdc_tiled<uint8_t>, grid, dim3(256), (size_t)p.lds, s, x, g, (long long)m, (long long)kdim, bm, lo, hi,
+                                   reinterpret_cast<const uint8_t *>(base + L.off_sym), (long long)nnz, (long long)ncols, L.segs, (int)k, (int)zero_symbol,
+                                   p.rlog2, p.terms_log2, p.col_tiles, p.per_split, hdr, sums);
+            else
+                hipLaunchKernelGGL(k_cbspdc_tiled<uint16_t>, grid, dim3(256), (size_t)p.lds, s, x, g, (long long)m, (long long)kdim, bm, lo, hi,
+                                   reinterpret_cast<const uint16_t *>(base + L.off_sym), (long long)nnz, (long long)ncols, L.segs, (int)k, (int)zero_symbol,
+                                   p.rlog2, p.terms_log2, p.col_tiles, p.per_split, hdr, sums);
+            LAUNCHCHK("k_cbspdc_tiled");
+        }
+        return NNC_OK;
+    });
 }

@@ -6,7 +6,9 @@
 // tile coordinates, the x / g tile loads, the dc prologue and scaled tile fill, the stores and the dc binning loop.  The FMA
 // step itself is tb_tile_fma (nnc_cbmm.hpp).  256 threads; grid (column tiles * row tiles, splits).  The sparse kernels keep
 // their kept mask, the masked FMA step, the sp_epilogue store and the binning of k_cbspdc_tiled (a running symbol position and
-// a register for the skipped weights: more than a label per (i, o)).
+// a register for the skipped weights: more than a label per (i, o)).  What the stream (m <= 16) kernels share is elsewhere: the
+// label row loads, the forward x load and the group step in nnc_cbmm.hpp, the dc x load in nnc_cbgrad.hpp.
+// cbdc_begin stays the tiled kernels' alone: the dc stream kernels compile to other instructions around it (same section).
 #pragma once
 #include "nnc_cbgrad.hpp"
 
