@@ -718,6 +718,7 @@ int nnc_cbmm_dc_f32(const float *x, const float *g, int64_t m, int64_t kdim, con
 /* The backward pass of nnc_cbmm_grouped from the same codebooks and indices (csrc/nnc_cbgrad_grouped.hip):
  * the dx / dc entry points of the group-wise layer, their workspace queries and plans.  A header of its own, part of this ABI. */
 #include "nnc_cbgrad_grouped.h"
+#include "nnc_cbgrad_h16.h"
 
 /* ------------------------------------------------------------------------------------
  * The pruned quantized layer run from a bitmap-sparse form of its indices (csrc/nnc_cbsp.hip).  The

@@ -43,6 +43,9 @@ CBGRAD_GROUPED_PLAN_LEN = 16   # nnc_cbmm_grouped_dx_plan / nnc_cbmm_grouped_dc_
 _CBGRAD_GROUPED_TAIL = ("group_rows", "groups", "rows_per_group", "max_groups_per_workgroup")
 CBDX_GROUPED_PLAN_FIELDS = CBDX_PLAN_FIELDS + _CBGRAD_GROUPED_TAIL
 CBDC_GROUPED_PLAN_FIELDS = CBDC_PLAN_FIELDS + _CBGRAD_GROUPED_TAIL
+CBGRAD_H16_PLAN_LEN = 13   # nnc_cbmm_dx_h16_plan / nnc_cbmm_dc_h16_plan: the float32 fields, then the dtype
+CBDX_H16_PLAN_FIELDS = CBDX_PLAN_FIELDS + ("dtype",)
+CBDC_H16_PLAN_FIELDS = CBDC_PLAN_FIELDS + ("dtype",)
 CBSP_ROWSUM_NONE, CBSP_ROWSUM_FUSED, CBSP_ROWSUM_PASS = 0, 1, 2   # nnc_cbsp_plan: how the row sums of x are formed (include/nnc.h)
 CBSP_PLAN_LEN = 11
 CBSP_PLAN_FIELDS = ("path", "mt", "copies", "entries", "splits", "rps", "rowsum", "lds", "col_tiles", "row_tiles", "workspace")
@@ -275,6 +278,17 @@ GROUPED_GRAD_SIGNATURES = {
     "nnc_cbmm_grouped_dc_f32": (c_int, [c_void_p, c_void_p, c_i64, c_i64, c_void_p, c_i64, c_i32, c_i64, c_void_p, c_i32, c_void_p, c_i64, c_void_p]),
 }
 
+# name -> (restype, argtypes); every symbol include/nnc_cbgrad_h16.h declares (the backward pass of the byte form on bf16 / fp16
+# activations, a header of its own that nnc.h includes).  Required and bound by load() as SIGNATURES are.
+H16_GRAD_SIGNATURES = {
+    "nnc_cbmm_dx_h16_workspace_bytes": (c_i64, [c_i64, c_i64, c_i64, c_int]),
+    "nnc_cbmm_dx_h16_plan": (c_int, [c_int, c_i64, c_i64, c_i64, c_int, c_i32, c_i32, ctypes.c_uint64, ctypes.POINTER(c_i64)]),
+    "nnc_cbmm_dx_h16": (c_int, [c_void_p, c_int, c_i64, c_i64, c_void_p, c_int, c_i64, c_void_p, c_i32, c_void_p, c_int, c_void_p, c_i64, c_void_p]),
+    "nnc_cbmm_dc_h16_workspace_bytes": (c_i64, [c_i64, c_i64, c_i64, c_int, c_i32]),
+    "nnc_cbmm_dc_h16_plan": (c_int, [c_int, c_i64, c_i64, c_i64, c_int, c_i32, c_i32, ctypes.c_uint64, ctypes.POINTER(c_i64)]),
+    "nnc_cbmm_dc_h16": (c_int, [c_void_p, c_void_p, c_int, c_i64, c_i64, c_void_p, c_int, c_i64, c_i32, c_void_p, c_i32, c_void_p, c_i64, c_void_p]),
+}
+
 # name -> (restype, argtypes); every symbol include/nnc_cbpkgrad_grouped.h declares (the backward pass of the group-wise packed layer,
 # again a header of its own that nnc.h includes).  Required and bound by load() as SIGNATURES are.
 GROUPED_PACKED_GRAD_SIGNATURES = {
@@ -319,7 +333,7 @@ def load():
         L = ctypes.CDLL(path)
     except OSError as e:  # pragma: no cover - depends on the machine
         raise NativeLibraryError(f"cannot load {path}: {e}; there is no CPU fallback") from e
-    for name, (res, args) in list(SIGNATURES.items()) + list(GROUPED_GRAD_SIGNATURES.items()) + list(GROUPED_PACKED_GRAD_SIGNATURES.items()):
+    for name, (res, args) in list(SIGNATURES.items()) + list(GROUPED_GRAD_SIGNATURES.items()) + list(H16_GRAD_SIGNATURES.items()) + list(GROUPED_PACKED_GRAD_SIGNATURES.items()):
         try:
             fn = getattr(L, name)
         except AttributeError as e:

@@ -51,6 +51,24 @@ def kernel_l2(layer) -> torch.Tensor:
     return (layer.kernel ** 2).sum() / 2
 
 
+class _HalfActivations(torch.nn.Module):
+    """A trainable codebook network run on half activations: the input cast to ``dtype``, the output back to float32 (before the
+    loss).  Everything else -- get_config, the layers by name, the parameters -- is the wrapped network's."""
+
+    def __init__(self, network: torch.nn.Module, dtype):
+        super().__init__()
+        self.network, self.dtype = network, dtype
+
+    def __getattr__(self, name):
+        try:
+            return super().__getattr__(name)
+        except AttributeError:
+            return getattr(super().__getattr__("network"), name)
+
+    def forward(self, x, *args, **kwargs):
+        return self.network(x.to(self.dtype), *args, **kwargs).to(torch.float32)
+
+
 class Trainer(ABC):
     neural_network: torch.nn.Module
     optimizer: torch.optim.Optimizer
@@ -202,7 +220,7 @@ class Trainer(ABC):
         return accuracies
 
     def fine_tune_compressed(self, train_dataset: LeNetDataset, test_dataset: LeNetDataset, epochs: int,
-                             learning_rate: float = 1e-3, sparse=False, packed=False) -> List[float]:
+                             learning_rate: float = 1e-3, sparse=False, packed=False, activation_dtype=None) -> List[float]:
         """fine_tune_centroids' algorithm run on ``compressed.compress_network_trainable(..., sparse=sparse, packed=packed)``
         (both False: the network of ``compressed_network(trainable=True)``; sparse True or "auto": the bitmap-sparse trainable
         layers, for every quantized layer or where that form is smaller; packed True or "auto": the 2- or 4-bit packed trainable
@@ -212,14 +230,30 @@ class Trainer(ABC):
         ops.packed_codebook_linear (DESIGN.md sections 12, 13, 15; neither W nor dW is built).
         Tensors that passed through unquantized stay frozen.  At the end the tuned centres go into ``quantized_models_by_layer``
         and the float layers are re-decoded from them (ops.gather), as after fine_tune_centroids.  Returns the accuracy per epoch
-        (of the trainable network)."""
+        (of the trainable network).
+        ``activation_dtype``: None (float32), torch.bfloat16 or torch.float16 (sparse=False and packed=False
+        only, else ValueError): the trainable network is built with half_inputs=True, its input is cast to the dtype and its output
+        back to float32 before the loss, so the centres are tuned in the arithmetic the compressed network runs inference in.  The
+        centres, their steps and the L2 term stay float32.  Every weighted layer then has to be a byte-form trainable layer: one that
+        passed through unquantized raises a ValueError that names it."""
         models = getattr(self, "quantized_models_by_layer", None)
         if not models:
             raise RuntimeError("fine_tune_compressed needs a quantized network: call quantize first")
         from .. import compressed
 
-        net = compressed.compress_network_trainable(self.neural_network, models, sparse=sparse, packed=packed)
-        return self._tune_centres(net, models, train_dataset, test_dataset, epochs, learning_rate)
+        if activation_dtype is None:
+            net = compressed.compress_network_trainable(self.neural_network, models, sparse=sparse, packed=packed)
+            return self._tune_centres(net, models, train_dataset, test_dataset, epochs, learning_rate)
+        if activation_dtype not in (torch.bfloat16, torch.float16):
+            raise ValueError(f"activation_dtype must be None, torch.bfloat16 or torch.float16, got {activation_dtype}")
+        if sparse is not False or packed is not False:
+            raise ValueError("activation_dtype needs sparse=False and packed=False: only the byte form trains on bfloat16 / float16 inputs")
+        net = compressed.compress_network_trainable(self.neural_network, models, half_inputs=True)
+        for name, layer in net.get_config().items():
+            if not isinstance(layer, compressed._TrainableCodebookLayer) and (hasattr(layer, "kernel") or next(layer.parameters(), None) is not None):
+                raise ValueError(f"activation_dtype={activation_dtype}: layer {name!r} ({type(layer).__name__}) is not a byte-form trainable "
+                                 "layer (its kernel passed through unquantized, or it has no half-precision backward pass)")
+        return self._tune_centres(_HalfActivations(net, activation_dtype), models, train_dataset, test_dataset, epochs, learning_rate)
 
     def fine_tune_grouped(self, train_dataset: LeNetDataset, test_dataset: LeNetDataset, epochs: int, learning_rate: float = 1e-3,
                           packed=False) -> List[float]:
@@ -293,14 +327,15 @@ class Trainer(ABC):
                 layer.set_weights(tensors)
         return accuracies
 
-    def compressed_network(self, sparse=False, trainable=False, packed=False) -> torch.nn.Module:
+    def compressed_network(self, sparse=False, trainable=False, packed=False, half_inputs=False) -> torch.nn.Module:
         """A copy of the network whose quantized layers run from their codebooks and centroid indices (compressed.py; the
         float32 weights are never rebuilt), with the centres as they stand (after fine_tune_centroids, the tuned ones).
         ``sparse``: False, True (the indices in the bitmap-sparse form) or "auto" (per layer, the smaller form).
         ``packed``: False, True (2- or 4-bit packed indices for every layer of at most 16 centres) or "auto" (per layer, the smallest
         form).
         ``trainable=True`` (with sparse=False and packed=False only): the layers' centres are parameters with a backward pass (DESIGN.md
-        section 12); fine_tune_compressed(..., sparse=..., packed=...) trains the other two forms.
+        section 12); fine_tune_compressed(..., sparse=..., packed=...) trains the other two forms.  ``half_inputs=True`` with it:
+        those layers train on bfloat16 / float16 inputs too.
         A layer quantized with ``group_rows`` becomes a GroupedCompressedDense; with it any of the three options raises
         NotImplementedError with the layer's name (compressed.pack_grouped_layers packs the grouped layers of the result, DESIGN.md
         section 18)."""
@@ -309,7 +344,7 @@ class Trainer(ABC):
             raise RuntimeError("compressed_network needs a quantized network: call quantize first")
         from .. import compressed
 
-        return compressed.compress_network(self.neural_network, models, sparse=sparse, trainable=trainable, packed=packed)
+        return compressed.compress_network(self.neural_network, models, sparse=sparse, trainable=trainable, packed=packed, half_inputs=half_inputs)
 
     def _discard_quantization(self) -> None:
         """The weights are about to change: the centroid indices of ``quantize`` no longer describe them, so nothing may store, run

@@ -30,7 +30,8 @@ csrc/nnc_cbmm_h16.hip): the path is chosen by the input's 
 of compressed layers stays in half.  ``centers`` and ``bias`` stay float32 buffers (each centre is rounded to the input's dtype
 inside the kernel, the bias is added in float32): feed half inputs, leave the module float32.  A module cast with ``.half()`` /
 ``.bfloat16()`` turns those buffers into half tensors, and the layer then raises the dtype ``TypeError`` of ops.codebook_matmul.
-Half inputs are for the byte form only: the bitmap-sparse, the packed and every trainable layer raise ``TypeError`` on them, and
+Half inputs are for the byte form only: the bitmap-sparse, the packed and every trainable layer raise ``TypeError`` on them (the
+trainable byte layers train on them when built with ``half_inputs=True``), and
 ``torch.autocast`` is not registered.
 
 ``GroupedCompressedDense`` runs a Dense layer whose kernel has one codebook per block of ``group_rows`` input rows
@@ -379,18 +380,25 @@ class _TrainableCentres(_Activated):
 
 
 class _TrainableCodebookLayer(_TrainableCentres):
-    """labels (kdim * ncols indices, row-major (kdim, ncols)) a buffer; the centres, counts and bias of _TrainableCentres."""
+    """labels (kdim * ncols indices, row-major (kdim, ncols)) a buffer; the centres, counts and bias of _TrainableCentres.
+    ``half_inputs=True`` lets the layer train on bfloat16 / float16 inputs (ops.codebook_linear): the output and
+    the input gradient have the input's dtype, centres and bias stay float32 parameters with float32 gradients.  Without it a half
+    input raises ``TypeError``: training in half is a numerics decision the caller makes knowingly."""
 
     def __init__(self, kdim: int, ncols: int, labels: torch.Tensor, centers: torch.Tensor, bias: torch.Tensor | None = None,
-                 bias_codes=None, activation=None):
+                 bias_codes=None, activation=None, half_inputs: bool = False):
         super().__init__()
         if labels.numel() != kdim * ncols:
             raise ValueError(f"{labels.numel()} indices for a {kdim} x {ncols} weight matrix")
         self.kdim, self.ncols = int(kdim), int(ncols)
+        self.half_inputs = bool(half_inputs)
         self.register_buffer("labels", labels.reshape(-1))
         self._init_centres(self.labels, centers, ncols, bias, bias_codes, activation)
 
     def _matmul(self, x: torch.Tensor) -> torch.Tensor:
+        if not self.half_inputs and x.dtype in (torch.bfloat16, torch.float16):
+            raise TypeError(f"{type(self).__name__} takes float32 activations, got {x.dtype}: a trainable layer of the byte form trains on "
+                            "bfloat16 and float16 inputs only when built with half_inputs=True")
         return self._activate(ops.codebook_linear(x, self.labels, self.centers, self.kdim, self.ncols, bias=self.current_bias(),
                                                   relu=self._fused_relu))
 
@@ -407,8 +415,8 @@ class TrainableCompressedConv2D(_Conv2DHalf, _TrainableCodebookLayer):
     autograd carries the patch gradients back through the unfold."""
 
     def __init__(self, kernel_size: int, cin: int, cout: int, pad: int, labels_unfold: torch.Tensor, centers: torch.Tensor, bias=None,
-                 bias_codes=None, activation=None):
-        super().__init__(kernel_size * kernel_size * cin, cout, labels_unfold, centers, bias, bias_codes, activation)
+                 bias_codes=None, activation=None, half_inputs: bool = False):
+        super().__init__(kernel_size * kernel_size * cin, cout, labels_unfold, centers, bias, bias_codes, activation, half_inputs)
         self._set_conv(kernel_size, cin, pad)
 
 
@@ -465,9 +473,10 @@ class TrainableGroupedCompressedDense(_DenseHalf, _TrainableCentres):
         return self._nbytes(self.labels)
 
 
-def _trainable(layer, weight_model, bias_model, dense_cls=None, conv_cls=None):
+def _trainable(layer, weight_model, bias_model, dense_cls=None, conv_cls=None, half_inputs=False):
     """The trainable layer of ``layer``, the one Dense / Conv2D dispatch of the trainable forms: through from_dense / from_conv
-    of ``dense_cls`` / ``conv_cls`` (the bitmap-sparse or the packed pair), or, without them, the byte classes built here."""
+    of ``dense_cls`` / ``conv_cls`` (the bitmap-sparse or the packed pair), or, without them, the byte classes built here
+    (``half_inputs``: theirs alone)."""
     from .neural_networks.layers import Conv2D, Dense
 
     if dense_cls is None:   # the byte form takes its codes before it looks at the layer's type, as it always did
@@ -476,13 +485,13 @@ def _trainable(layer, weight_model, bias_model, dense_cls=None, conv_cls=None):
         if dense_cls is not None:
             return dense_cls.from_dense(layer, weight_model, bias_model)
         kin, kout = layer.kernel.shape
-        return TrainableCompressedDense(kin, kout, labels, centers, bias, bias_codes, layer.activation)
+        return TrainableCompressedDense(kin, kout, labels, centers, bias, bias_codes, layer.activation, half_inputs)
     if isinstance(layer, Conv2D):
         if conv_cls is not None:
             return conv_cls.from_conv(layer, weight_model, bias_model)
         h, cin, cout = _conv_shape(layer)
         return TrainableCompressedConv2D(h, cin, cout, layer.pad, _unfold_labels(h, cin, cout, labels), centers, bias, bias_codes,
-                                         layer.activation)
+                                         layer.activation, half_inputs)
     raise TypeError(f"no compressed form of {type(layer).__name__}")
 
 
@@ -912,7 +921,17 @@ def _replace(layer, weight_model, bias_model, sparse=False, packed=False):
     return _from_codes(layer, tuple(layer.kernel.shape), labels, centers, _decoded_bias(layer.bias, bias_model), sparse, packed)
 
 
-def compress_network(network: nn.Module, models_by_layer, sparse=False, trainable=False, packed=False) -> nn.Module:
+def _check_half_inputs(half_inputs, sparse, packed, trainable=True):
+    if not half_inputs:
+        return
+    if not trainable:
+        raise ValueError("half_inputs=True is an option of the trainable layers (trainable=True): the inference layers of the byte form "
+                         "take bfloat16 and float16 inputs as they are")
+    if sparse is not False or packed is not False:
+        raise ValueError("half_inputs=True needs sparse=False and packed=False: only the byte form trains on bfloat16 / float16 inputs")
+
+
+def compress_network(network: nn.Module, models_by_layer, sparse=False, trainable=False, packed=False, half_inputs=False) -> nn.Module:
     """A deep copy of ``network`` whose quantized layers (``models_by_layer``: layer -> [kernel model, bias model], as
     Trainer.quantized_models_by_layer) run from their codebooks.  Layers are replaced by the attribute names of
     ``get_config()``; a layer whose kernel passed through unquantized (model None) stays float32.  ``sparse``: False (the
@@ -920,34 +939,39 @@ def compress_network(network: nn.Module, models_by_layer, sparse=False, trainabl
     ``packed``: False, True (2- or 4-bit packed indices for every layer of at most 16 centres, the others in the byte form) or
     "auto"; with ``sparse`` it decides per layer by resident bytes as the module's docstring tells.
     ``trainable=True`` (dense indices only): TrainableCompressedDense / TrainableCompressedConv2D, centres as parameters;
-    compress_network_trainable gives the bitmap-sparse and the packed trainable layers too.
+    compress_network_trainable gives the bitmap-sparse and the packed trainable layers too.  ``half_inputs=True`` (with
+    trainable=True, sparse=False and packed=False only, else ValueError): those layers train on bfloat16 / float16 inputs too.
     A layer whose kernel model is a utility.GroupedModel (one codebook per block of input rows) becomes a GroupedCompressedDense;
     with ``sparse``, ``packed`` or ``trainable`` set it raises NotImplementedError and names the layer (pack_grouped_layers packs
     the grouped layers of the result)."""
     _check_sparse(sparse)
     _check_packed(packed, sparse, trainable)
+    _check_half_inputs(half_inputs, sparse, packed, trainable)
     if trainable and sparse is not False:
         raise ValueError("trainable=True needs sparse=False here: use compress_network_trainable(..., sparse=...) for trainable "
                          "bitmap-sparse layers")
     if trainable:
-        return compress_network_trainable(network, models_by_layer)
+        return compress_network_trainable(network, models_by_layer, half_inputs=half_inputs)
     what = "sparse=" + repr(sparse) if sparse is not False else ("packed=" + repr(packed) if packed is not False else None)
     return _compress_each(network, models_by_layer, lambda layer, wm, bm: _replace(layer, wm, bm, sparse, packed), grouped=what)
 
 
-def compress_network_trainable(network: nn.Module, models_by_layer, sparse=False, packed=False) -> nn.Module:
+def compress_network_trainable(network: nn.Module, models_by_layer, sparse=False, packed=False, half_inputs=False) -> nn.Module:
     """compress_network with the centres (and quantized biases' centres) as nn.Parameters.  ``sparse``: False
     (TrainableCompressedDense / TrainableCompressedConv2D, the layers of compress_network(..., trainable=True)), True
     (TrainableSparseCompressedDense / TrainableSparseCompressedConv2D: the indices in the bitmap-sparse form, skipping the most
     frequent one) or "auto" (per layer, the form with fewer resident bytes).  ``packed``: False, True
     (TrainablePackedCompressedDense / TrainablePackedCompressedConv2D for every layer of at most 16 centres, the others in the
     byte form) or "auto"; with ``sparse`` it decides per layer by resident bytes as the module's docstring tells.  All train the
-    same function: the sparse and the packed layer's centroid gradient is the byte one's bit for bit (DESIGN.md sections 13, 15)."""
+    same function: the sparse and the packed layer's centroid gradient is the byte one's bit for bit (DESIGN.md sections 13, 15).
+    ``half_inputs=True`` (sparse=False and packed=False only, else ValueError): the byte layers built with half_inputs=True, which
+    train on bfloat16 / float16 inputs."""
     _check_sparse(sparse)
     _check_packed(packed, sparse)
+    _check_half_inputs(half_inputs, sparse, packed)
 
     def make(layer, wm, bm):
-        byte, sp, pk = (lambda: _trainable(layer, wm, bm),
+        byte, sp, pk = (lambda: _trainable(layer, wm, bm, half_inputs=half_inputs),
                         lambda: _trainable(layer, wm, bm, TrainableSparseCompressedDense, TrainableSparseCompressedConv2D),
                         lambda: _trainable(layer, wm, bm, TrainablePackedCompressedDense, TrainablePackedCompressedConv2D))
         return _pick(byte, sp, sparse) if packed is False else _pick3(wm.cluster_centers_.size, byte, sp, pk, sparse, packed)

@@ -22,112 +22,12 @@
 //   from k_cbgrad_absmax on the device, the dc kernel derives S itself and writes it next to the sums, and k_cbdc_finish writes
 //   dc = ldexp(sum, -S).  No host read anywhere.
 // An index >= K reads 0 in dx and falls into no bin in dc, as in the forward pass.  No float atomics.
+// The two stream kernels, k_cbgrad_absmax and k_cbgrad_reduce are templates in nnc_cbgrad.hpp (the element type of x and g: this unit
+// instantiates them for float32, nnc_cbgrad_h16.hip for bf16 / fp16).
 // The plans (CgPlan, dx_plan, dc_plan) and cg_check are in nnc_cbgrad.hpp, where nnc_cbgrad_grouped.hip finds them too; so are the
 // sequences of HIP calls of the two entry points (cbg_run_dx, cbg_run_dc) and the list of stream instantiations.  The label row
 // loads (cb_row_words) are nnc_cbmm.hpp's, the x load of k_cbdc_stream (cbdc_load_x) nnc_cbgrad.hpp's.
 #include "nnc_cbtile.hpp"
-
-// ------------------------------------------------------------------ max |x|, max |g|
-// amax[0] = bits of max |x|, amax[1] = bits of max |g| (zeroed by the caller).  |v| as a bit pattern orders as the value; a NaN
-// orders above Inf, so amax >= 0x7F800000 means "not finite".
-__global__ __launch_bounds__(256) void k_cbgrad_absmax(const float *__restrict__ x, long long nx, const float *__restrict__ g, long long ng,
-                                                       uint32_t *__restrict__ amax)
-{
-    __shared__ uint32_t wmax[2][4];
-    uint32_t a = 0, b = 0;
-    const long long tid = (long long)blockIdx.x * blockDim.x + threadIdx.x, nth = (long long)gridDim.x * blockDim.x;
-    for (long long i = tid; i < nx; i += nth) a = std::max(a, __float_as_uint(x[i]) & 0x7FFFFFFFu);
-    for (long long i = tid; i < ng; i += nth) b = std::max(b, __float_as_uint(g[i]) & 0x7FFFFFFFu);
-#pragma unroll
-    for (int bit = 32; bit >= 1; bit >>= 1) {
-        a = std::max(a, (uint32_t)__shfl_xor((int)a, bit));
-        b = std::max(b, (uint32_t)__shfl_xor((int)b, bit));
-    }
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    if (lane == 0) {
-        wmax[0][wave] = a;
-        wmax[1][wave] = b;
-    }
-    __syncthreads();
-    if (threadIdx.x < 2) {
-        uint32_t v = 0;
-        for (int w = 0; w < (int)(blockDim.x >> 6); ++w) v = std::max(v, wmax[threadIdx.x][w]);
-        if (v) atomicMax(&amax[threadIdx.x], v);
-    }
-}
-
-// ------------------------------------------------------------------ dx, m <= 16
-// grid (column blocks, row groups), CB_THREADS threads.  out: dx (one column block) or the partials [block][m][kdim].
-template <typename LT, int VB, int MT, bool ALIGNED>
-__global__ __launch_bounds__(CB_THREADS) void k_cbdx_stream(const float *__restrict__ g, int m, long long kdim, const unsigned char *__restrict__ labels,
-                                                            long long ncols, const float *__restrict__ centers, int k, int entries, int cshift,
-                                                            long long rows_per_group, int direct, float *__restrict__ out)
-{
-    constexpr int LB = sizeof(LT), E = VB / LB, N = VB / 4, PER = 32 / (8 * LB);
-    extern __shared__ float smem[];
-    float *cb = smem;
-    float *stage = smem + (entries << cshift);
-    cb_fill(cb, stage, centers, k, entries, cshift);
-
-    const int lane = threadIdx.x & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const long long c0 = (long long)blockIdx.x * (64 * E) + lane * E;
-    const bool active = c0 < ncols;
-    const int ne = (int)std::max(0LL, std::min((long long)E, ncols - c0));   // the lane's columns inside the matrix
-    float gv[MT][E];
-#pragma unroll
-    for (int r = 0; r < MT; ++r)
-#pragma unroll
-        for (int e = 0; e < E; ++e) gv[r][e] = (r < m && e < ne) ? g[(long long)r * ncols + c0 + e] : 0.0f;
-
-    const long long g_lo = (long long)blockIdx.y * rows_per_group, g_hi = std::min(kdim, g_lo + rows_per_group);
-    const long long per_wave = (g_hi - g_lo + CB_WAVES - 1) / CB_WAVES;
-    const long long i0 = std::min(g_hi, g_lo + wave * per_wave), i1 = std::min(g_hi, i0 + per_wave);
-    const uintptr_t base = reinterpret_cast<uintptr_t>(labels);
-    const long long row_bytes = ncols * LB;
-    const long long lane_off = (long long)blockIdx.x * (64 * VB) + lane * VB;
-    float *dst = direct ? out : out + (long long)blockIdx.x * m * kdim;
-    __syncthreads();
-
-    auto row_words = [&](long long i, uint32_t *w, uint32_t &s) { cb_row_words<VB, ALIGNED>(base, row_bytes, lane_off, active, i, w, s); };
-    auto consume = [&](const uint32_t *w, uint32_t s, long long i) {
-        uint32_t o[N];
-        if constexpr (ALIGNED) {
-#pragma unroll
-            for (int d = 0; d < N; ++d) o[d] = w[d];
-        } else {
-            funnel<N>(w, s, o);
-        }
-        float p[MT];
-#pragma unroll
-        for (int r = 0; r < MT; ++r) p[r] = 0.0f;
-#pragma unroll
-        for (int e = 0; e < E; ++e) {
-            const uint32_t l = (o[e / PER] >> (8 * LB * (e % PER))) & (LB == 1 ? 0xFFu : 0xFFFFu);
-            const float wv = e < ne ? cb[CbTable<LT>::index(l, k, cshift, lane)] : 0.0f;   // (columns past the row: no Inf * 0)
-#pragma unroll
-            for (int r = 0; r < MT; ++r) p[r] = __builtin_fmaf(gv[r][e], wv, p[r]);
-        }
-        int row;
-        const float v = wave_reduce_rows<MT>(p, lane, row);
-        if ((lane & (64 / MT - 1)) == 0 && row < m) dst[(long long)row * kdim + i] = v;
-    };
-
-    constexpr int WN = ALIGNED ? N : 2 * N;
-    long long i = i0;
-    for (; i + CB_UNROLL <= i1; i += CB_UNROLL) {
-        uint32_t w[CB_UNROLL][WN], s[CB_UNROLL];
-#pragma unroll
-        for (int u = 0; u < CB_UNROLL; ++u) row_words(i + u, w[u], s[u]);
-#pragma unroll
-        for (int u = 0; u < CB_UNROLL; ++u) consume(w[u], s[u], i + u);
-    }
-    for (; i < i1; ++i) {
-        uint32_t w[WN], s;
-        row_words(i, w, s);
-        consume(w, s, i);
-    }
-}
 
 // ------------------------------------------------------------------ dx, m > 16
 // grid (kdim tiles * m tiles, splits of ncols), 256 threads; thread (tx, ty) owns rows ty*8.. (of g) and columns tx*8.. (i) of the tile.
@@ -163,109 +63,6 @@ __global__ __launch_bounds__(256) void k_cbdx_tiled(const float *__restrict__ g,
     for (int a = 0; a < 8; ++a)
 #pragma unroll
         for (int b = 0; b < 8; ++b) tb_store_dx(acc[a][b], T.m0 + T.ty * 8 + a, T.n0 + T.tx * 8 + b, m, kdim, direct, out);
-}
-
-// ------------------------------------------------------------------ the split partials, summed in split order
-__global__ __launch_bounds__(256) void k_cbgrad_reduce(const float *__restrict__ part, long long splits, long long mn, float *__restrict__ out)
-{
-    for (long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x; idx < mn; idx += (long long)gridDim.x * blockDim.x) {
-        float v = part[idx];
-        for (long long s = 1; s < splits; ++s) v += part[s * mn + idx];
-        out[idx] = v;
-    }
-}
-
-// ------------------------------------------------------------------ dc, m <= 16
-// grid (column blocks, row groups), CB_THREADS threads.  LDS: the bins, [k][1 << rlog2] int64.
-template <typename LT, int VB, int MT, bool ALIGNED>
-__global__ __launch_bounds__(CB_THREADS) void k_cbdc_stream(const float *__restrict__ x, const float *__restrict__ g, int m, long long kdim,
-                                                            const unsigned char *__restrict__ labels, long long ncols, int k, int rlog2, int terms_log2,
-                                                            long long rows_per_group, uint32_t *__restrict__ hdr, unsigned long long *__restrict__ sums)
-{
-    constexpr int LB = sizeof(LT), E = VB / LB, N = VB / 4, PER = 32 / (8 * LB);
-    extern __shared__ unsigned long long bins[];
-    int flag;
-    const int S = cbdc_shift(hdr, m, terms_log2, flag);
-    if (blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0) {
-        hdr[2] = (uint32_t)S;
-        hdr[3] = (uint32_t)flag;
-    }
-    if (flag != CBG_FLAG_OK) return;   // (uniform over the launch)
-    int scx, scg;
-    cbdc_scales(hdr, scx, scg);
-    const int Sw = S - scx - scg;      // the shift of dW' = dW * 2^(scx + scg)
-    for (int j = threadIdx.x; j < (k << rlog2); j += CB_THREADS) bins[j] = 0ull;
-
-    const int lane = threadIdx.x & 63;
-    const int rep = lane & ((1 << rlog2) - 1);
-    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const long long c0 = (long long)blockIdx.x * (64 * E) + lane * E;
-    const bool active = c0 < ncols;
-    const int ne = (int)std::max(0LL, std::min((long long)E, ncols - c0));
-    float gv[MT][E];
-#pragma unroll
-    for (int r = 0; r < MT; ++r)
-#pragma unroll
-        for (int e = 0; e < E; ++e) gv[r][e] = g[cbdc_idx((long long)r * ncols + c0 + e, r < m && e < ne)];
-    __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-    for (int r = 0; r < MT; ++r)
-#pragma unroll
-        for (int e = 0; e < E; ++e) gv[r][e] = cbdc_scaled(gv[r][e], r < m && e < ne, scg);
-
-    const long long g_lo = (long long)blockIdx.y * rows_per_group, g_hi = std::min(kdim, g_lo + rows_per_group);
-    const long long per_wave = (g_hi - g_lo + CB_WAVES - 1) / CB_WAVES;
-    const long long i0 = std::min(g_hi, g_lo + wave * per_wave), i1 = std::min(g_hi, i0 + per_wave);
-    const uintptr_t base = reinterpret_cast<uintptr_t>(labels);
-    const long long row_bytes = ncols * LB;
-    const long long lane_off = (long long)blockIdx.x * (64 * VB) + lane * VB;
-    __syncthreads();
-
-    auto row_words = [&](long long i, uint32_t *w, uint32_t &s) { cb_row_words<VB, ALIGNED>(base, row_bytes, lane_off, active, i, w, s); };
-    auto load_x = [&](long long i, int U, float &xa, float &xb) { cbdc_load_x<MT>(x, kdim, m, scx, lane, i, U, xa, xb); };
-    auto consume = [&](const uint32_t *w, uint32_t s, float xa, float xb, int u, int U) {
-        float xv[MT];
-#pragma unroll
-        for (int r = 0; r < MT; ++r) {
-            const int f = r * U + u;
-            xv[r] = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, f < 64 ? xa : xb), f & 63));
-        }
-        uint32_t o[N];
-        if constexpr (ALIGNED) {
-#pragma unroll
-            for (int d = 0; d < N; ++d) o[d] = w[d];
-        } else {
-            funnel<N>(w, s, o);
-        }
-#pragma unroll
-        for (int e = 0; e < E; ++e) {
-            const uint32_t l = (o[e / PER] >> (8 * LB * (e % PER))) & (LB == 1 ? 0xFFu : 0xFFFFu);
-            float d = 0.0f;
-#pragma unroll
-            for (int r = 0; r < MT; ++r) d = __builtin_fmaf(xv[r], gv[r][e], d);   // dW'[i, o], r ascending
-            if (e < ne && l < (uint32_t)k) atomicAdd(&bins[(l << rlog2) + rep], cbdc_fix(d, Sw));
-        }
-    };
-
-    constexpr int WN = ALIGNED ? N : 2 * N;
-    long long i = i0;
-    for (; i + CB_UNROLL <= i1; i += CB_UNROLL) {
-        uint32_t w[CB_UNROLL][WN], s[CB_UNROLL];
-        float xa, xb;
-#pragma unroll
-        for (int u = 0; u < CB_UNROLL; ++u) row_words(i + u, w[u], s[u]);
-        load_x(i, CB_UNROLL, xa, xb);
-#pragma unroll
-        for (int u = 0; u < CB_UNROLL; ++u) consume(w[u], s[u], xa, xb, u, CB_UNROLL);
-    }
-    for (; i < i1; ++i) {
-        uint32_t w[WN], s;
-        float xa, xb;
-        row_words(i, w, s);
-        load_x(i, 1, xa, xb);
-        consume(w, s, xa, xb, 0, 1);
-    }
-    cbdc_flush(bins, k, rlog2, sums);
 }
 
 // ------------------------------------------------------------------ dc, m > 16
@@ -309,18 +106,28 @@ __global__ __launch_bounds__(256) void k_cbdc_finish(const uint32_t *__restrict_
 }
 
 // ------------------------------------------------------------------ the launches every backward unit shares (nnc_cbgrad.hpp)
-int cbgrad_absmax(const float *x, long long nx, const float *g, long long ng, uint32_t *amax, hipStream_t s)
+template <typename XT>
+static void launch_absmax(int agrid, hipStream_t s, const void *x, long long nx, const void *g, long long ng, uint32_t *amax)
+{
+    hipLaunchKernelGGL(k_cbgrad_absmax<XT>, dim3(agrid), dim3(256), 0, s, reinterpret_cast<const XT *>(x), nx, reinterpret_cast<const XT *>(g), ng, amax);
+}
+
+int cbgrad_absmax_dt(const void *x, long long nx, const void *g, long long ng, int dtype, uint32_t *amax, hipStream_t s)
 {
     const int agrid = (int)std::max(1LL, std::min(cdiv(std::max(nx, ng), 256 * 8), 4LL * cu_count()));
-    hipLaunchKernelGGL(k_cbgrad_absmax, dim3(agrid), dim3(256), 0, s, x, nx, g, ng, amax);
+    if (dtype == NNC_DT_BF16) launch_absmax<bf16_t>(agrid, s, x, nx, g, ng, amax);
+    else if (dtype == NNC_DT_F16) launch_absmax<f16_t>(agrid, s, x, nx, g, ng, amax);
+    else launch_absmax<float>(agrid, s, x, nx, g, ng, amax);
     LAUNCHCHK("k_cbgrad_absmax");
     return NNC_OK;
 }
 
-int cbgrad_reduce(const float *part, long long splits, long long mn, float *out, hipStream_t s)
+int cbgrad_reduce_dt(const float *part, long long splits, long long mn, void *out, int out_dtype, hipStream_t s)
 {
     const int rgrid = (int)std::max(1LL, std::min(cdiv(mn, 256), 8192LL));
-    hipLaunchKernelGGL(k_cbgrad_reduce, dim3(rgrid), dim3(256), 0, s, part, splits, mn, out);
+    if (out_dtype == NNC_DT_BF16) hipLaunchKernelGGL(k_cbgrad_reduce<bf16_t>, dim3(rgrid), dim3(256), 0, s, part, splits, mn, reinterpret_cast<bf16_t *>(out));
+    else if (out_dtype == NNC_DT_F16) hipLaunchKernelGGL(k_cbgrad_reduce<f16_t>, dim3(rgrid), dim3(256), 0, s, part, splits, mn, reinterpret_cast<f16_t *>(out));
+    else hipLaunchKernelGGL(k_cbgrad_reduce<float>, dim3(rgrid), dim3(256), 0, s, part, splits, mn, reinterpret_cast<float *>(out));
     LAUNCHCHK("k_cbgrad_reduce");
     return NNC_OK;
 }
@@ -339,9 +146,9 @@ static void launch_dx_stream(bool aligned, dim3 grid, size_t lds, hipStream_t s,
 {
     const unsigned char *lab = reinterpret_cast<const unsigned char *>(labels);
     if (aligned)
-        hipLaunchKernelGGL((k_cbdx_stream<LT, VB, MT, true>), grid, dim3(CB_THREADS), lds, s, g, m, kdim, lab, ncols, centers, k, entries, cshift, rpg, direct, out);
+        hipLaunchKernelGGL((k_cbdx_stream<float, LT, VB, MT, true>), grid, dim3(CB_THREADS), lds, s, g, m, kdim, lab, ncols, centers, k, entries, cshift, rpg, direct, out);
     else
-        hipLaunchKernelGGL((k_cbdx_stream<LT, VB, MT, false>), grid, dim3(CB_THREADS), lds, s, g, m, kdim, lab, ncols, centers, k, entries, cshift, rpg, direct, out);
+        hipLaunchKernelGGL((k_cbdx_stream<float, LT, VB, MT, false>), grid, dim3(CB_THREADS), lds, s, g, m, kdim, lab, ncols, centers, k, entries, cshift, rpg, direct, out);
 }
 
 template <typename LT, int VB, int MT>
@@ -350,9 +157,9 @@ static void launch_dc_stream(bool aligned, dim3 grid, size_t lds, hipStream_t s,
 {
     const unsigned char *lab = reinterpret_cast<const unsigned char *>(labels);
     if (aligned)
-        hipLaunchKernelGGL((k_cbdc_stream<LT, VB, MT, true>), grid, dim3(CB_THREADS), lds, s, x, g, m, kdim, lab, ncols, k, rlog2, tl, rpg, hdr, sums);
+        hipLaunchKernelGGL((k_cbdc_stream<float, LT, VB, MT, true>), grid, dim3(CB_THREADS), lds, s, x, g, m, kdim, lab, ncols, k, rlog2, tl, rpg, hdr, sums);
     else
-        hipLaunchKernelGGL((k_cbdc_stream<LT, VB, MT, false>), grid, dim3(CB_THREADS), lds, s, x, g, m, kdim, lab, ncols, k, rlog2, tl, rpg, hdr, sums);
+        hipLaunchKernelGGL((k_cbdc_stream<float, LT, VB, MT, false>), grid, dim3(CB_THREADS), lds, s, x, g, m, kdim, lab, ncols, k, rlog2, tl, rpg, hdr, sums);
 }
 
 // every stream instantiation there is (the lists of nnc_cbgrad.hpp); the plans are checked against this table, and the launches go through it

@@ -103,6 +103,19 @@ static inline void cb_grid(CbPlan &p, long long m, long long kdim, long long nco
     p.splits = cdiv(kdim, p.rows_per_split);
 }
 
+// the per-bank LDS table of a label width: its entries (uint8: 256, zero-padded; uint16: k + 1, entry k the out-of-range value) and
+// the log2 of its copies (cshift zero on entry)
+static inline void cb_table_shape(int lb, int k, int &entries, int &cshift)
+{
+    if (lb == 1) {
+        entries = 256;
+        cshift = __builtin_ctz(CB_U8_COPIES);
+    } else {
+        entries = k + 1;
+        while ((1 << cshift) < CB_U8_COPIES && (long long)entries << (cshift + 1) <= CB_U16_WORDS) ++cshift;
+    }
+}
+
 static inline CbPlan cb_plan(long long m, long long kdim, long long ncols, int lb, int k, int cus, uintptr_t labels, bool mfma = false)
 {
     CbPlan p{};
@@ -113,13 +126,7 @@ static inline CbPlan cb_plan(long long m, long long kdim, long long ncols, int l
     }
     cb_grid(p, m, kdim, ncols, lb, cus, mfma);
     if (p.path != NNC_CBMM_TILED) {   // the per-bank table of the stream kernels; k_cbmm_mfma looks its W tile up in the same one
-        if (lb == 1) {
-            p.entries = 256;
-            p.cshift = __builtin_ctz(CB_U8_COPIES);
-        } else {
-            p.entries = k + 1;
-            while ((1 << p.cshift) < CB_U8_COPIES && (long long)p.entries << (p.cshift + 1) <= CB_U16_WORDS) ++p.cshift;
-        }
+        cb_table_shape(lb, k, p.entries, p.cshift);
         if (p.path == NNC_CBMM_MFMA) {
             p.lds = (long long)hm_table_words(p.entries, p.cshift) * 4 + (long long)(HM_BM + HM_BN) * HM_LD * 2;
         } else {

@@ -30,7 +30,8 @@ def _require_f32_x(x, who: str):
     """The entry points that have no half-precision kernels: a bfloat16 / float16 x names the one form that has."""
     if isinstance(x, torch.Tensor) and x.dtype in (torch.bfloat16, torch.float16):
         raise TypeError(f"{who} takes float32 activations, got {x.dtype}: bfloat16 and float16 inputs run on the byte form only "
-                        "(ops.codebook_matmul, CompressedDense / CompressedConv2D), inference only")
+                        "(ops.codebook_matmul and ops.codebook_linear; CompressedDense / CompressedConv2D, and their trainable "
+                        "layers built with half_inputs=True)")
 
 
 def _stream(t: torch.Tensor) -> int:
@@ -459,8 +460,8 @@ def cbmm_grouped_plan(dtype, m: int, kdim: int, ncols: int, k: int, group_rows: 
 
 
 def _grad_args(g: torch.Tensor, labels: torch.Tensor, kdim: int, ncols: int, k: int):
-    """The byte form's checks of g and the indices -> (lead, m) of g."""
-    _require_cuda(g, "g", torch.float32)
+    """The byte form's checks of g and the indices -> (lead, m) of g.  g: float32, or bfloat16 / float16."""
+    _require_cuda(g, "g", g.dtype if isinstance(g, torch.Tensor) and g.dtype in _H16_DT else torch.float32)
     _require_cuda(labels, "labels")
     if labels.numel() != kdim * ncols:
         raise ValueError(f"labels must hold kdim * ncols = {kdim * ncols} indices, got {labels.numel()}")
@@ -470,15 +471,29 @@ def _grad_args(g: torch.Tensor, labels: torch.Tensor, kdim: int, ncols: int, k: 
     return lead_m
 
 
-def codebook_matmul_dx(g: torch.Tensor, labels: torch.Tensor, centers: torch.Tensor, kdim: int, ncols: int) -> torch.Tensor:
+def codebook_matmul_dx(g: torch.Tensor, labels: torch.Tensor, centers: torch.Tensor, kdim: int, ncols: int, out_dtype=None) -> torch.Tensor:
     """dx = g @ W^T with W[i, o] = centers[labels[i * ncols + o]] read from the indices (include/nnc.h, nnc_cbmm_dx_f32): the input
     gradient of codebook_matmul.  g: float32 (..., ncols); labels, centers as codebook_matmul.  Returns float32 (..., kdim).  Split
-    partials are summed in a fixed order: the same call gives the same bits.  No host read."""
+    partials are summed in a fixed order: the same call gives the same bits.  No host read.
+    A bfloat16 or float16 g takes nnc_cbmm_dx_h16: centers stay float32 and are rounded to g's dtype as the
+    forward rounds them, the products are exact, the sums float32; the result has ``out_dtype``: None (g's dtype, the float32 value
+    rounded once) or torch.float32.  A float32 g takes no ``out_dtype`` but None or torch.float32."""
     kdim, ncols = int(kdim), int(ncols)
     _require_cuda(centers, "centers", torch.float32)
     lead, m = _grad_args(g, labels, kdim, ncols, centers.numel())
     _one_device("g, labels and centers", g, labels, centers)
+    if out_dtype not in (None, torch.float32):
+        raise TypeError(f"out_dtype must be None or torch.float32, got {out_dtype}")
     L = nat.load()
+    if g.dtype in _H16_DT:
+        dx_dtype = g.dtype if out_dtype is None else out_dtype
+        dx = torch.empty(lead + (kdim,), dtype=dx_dtype, device=g.device)
+        lb = _label_bytes(labels)
+        ws_bytes = int(L.nnc_cbmm_dx_h16_workspace_bytes(m, kdim, ncols, lb))
+        ws = _workspace(ws_bytes, g.device)
+        nat.check(L.nnc_cbmm_dx_h16(_ptr(g), _H16_DT[g.dtype], m, kdim, _ptr(labels), lb, ncols, _ptr(centers), centers.numel(), _ptr(dx),
+                                    _H16_DT.get(dx_dtype, nat.DT_F32), _ptr(ws), ws_bytes, _stream(g)))
+        return dx
     dx = torch.empty(lead + (kdim,), dtype=torch.float32, device=g.device)
     lb = _label_bytes(labels)
     ws_bytes = int(L.nnc_cbmm_dx_workspace_bytes(m, kdim, ncols, lb))
@@ -492,9 +507,13 @@ def codebook_centroid_grad(x: torch.Tensor, g: torch.Tensor, labels: torch.Tenso
     """dc[j] = sum over the (i, o) with labels[i * ncols + o] = j of (x^T g)[i, o] (include/nnc.h, nnc_cbmm_dc_f32): the centroid
     gradient of codebook_matmul, the kdim x ncols dW never written.  x: float32 (..., kdim), g: float32 (..., ncols) with the same
     leading shape.  Exact fixed-point sums (S from max|x| and max|g| on the device, cbgrad_shift): the result depends on the shape
-    and the data only.  Returns ``dtype`` (float64 or float32) [k].  No host read."""
+    and the data only.  Returns ``dtype`` (float64 or float32) [k].  No host read.
+    x and g both bfloat16 or both float16 take nnc_cbmm_dc_h16: the products are exact, dW is formed in float32
+    and binned by the same rule; the result is the gradient with respect to the float32 centres."""
     kdim, ncols, k = int(kdim), int(ncols), int(k)
-    _require_cuda(x, "x", torch.float32)
+    if isinstance(x, torch.Tensor) and isinstance(g, torch.Tensor) and x.dtype != g.dtype and (x.dtype in _H16_DT or g.dtype in _H16_DT):
+        raise TypeError(f"x and g must have one dtype, got {x.dtype} and {g.dtype}")
+    _require_cuda(x, "x", x.dtype if isinstance(x, torch.Tensor) and x.dtype in _H16_DT else torch.float32)
     lead, m = _grad_args(g, labels, kdim, ncols, k)
     _dc_args(x, lead, kdim, "x, g and labels", labels, g, dtype)
     L = nat.load()
@@ -502,6 +521,12 @@ def codebook_centroid_grad(x: torch.Tensor, g: torch.Tensor, labels: torch.Tenso
     if lb == 1 and k > 256:
         raise ValueError("k > 256 needs 16-bit labels")
     dc = torch.empty(k, dtype=dtype, device=x.device)
+    if x.dtype in _H16_DT:
+        ws_bytes = int(L.nnc_cbmm_dc_h16_workspace_bytes(m, kdim, ncols, lb, k))
+        ws = _workspace(ws_bytes, x.device)
+        nat.check(L.nnc_cbmm_dc_h16(_ptr(x), _ptr(g), _H16_DT[x.dtype], m, kdim, _ptr(labels), lb, ncols, k, _ptr(dc), 1 if dtype == torch.float64 else 0,
+                                    _ptr(ws), ws_bytes, _stream(x)))
+        return dc
     ws_bytes = int(L.nnc_cbmm_dc_workspace_bytes(m, kdim, ncols, lb, k))
     ws = _workspace(ws_bytes, x.device)
     nat.check(L.nnc_cbmm_dc_f32(_ptr(x), _ptr(g), m, kdim, _ptr(labels), lb, ncols, k, _ptr(dc), 1 if dtype == torch.float64 else 0,
@@ -519,6 +544,24 @@ def cbmm_dc_plan(m: int, kdim: int, ncols: int, label_bytes: int, k: int, cus: i
     """Host: the plan nnc_cbmm_dc_f32 follows on a device with ``cus`` compute units (include/nnc.h, nnc_cbmm_dc_plan), as a dict
     keyed by _native.CBDC_PLAN_FIELDS.  No device needed."""
     return _plan(nat.load().nnc_cbmm_dc_plan, nat.CBDC_PLAN_FIELDS, m, kdim, ncols, label_bytes, k, cus, labels_addr)
+
+
+def _h16_dt(dtype) -> int:
+    if dtype not in _H16_DT:
+        raise TypeError(f"dtype must be torch.bfloat16 or torch.float16, got {dtype}")
+    return _H16_DT[dtype]
+
+
+def cbmm_dx_h16_plan(dtype, m: int, kdim: int, ncols: int, label_bytes: int, k: int, cus: int, labels_addr: int = 0) -> dict:
+    """Host: the plan nnc_cbmm_dx_h16 follows for g of ``dtype`` (torch.bfloat16 / torch.float16) on a device with ``cus`` compute
+    units (include/nnc_cbgrad_h16.h), as a dict keyed by _native.CBDX_H16_PLAN_FIELDS.  No device needed."""
+    return _plan(nat.load().nnc_cbmm_dx_h16_plan, nat.CBDX_H16_PLAN_FIELDS, _h16_dt(dtype), m, kdim, ncols, label_bytes, k, cus, labels_addr)
+
+
+def cbmm_dc_h16_plan(dtype, m: int, kdim: int, ncols: int, label_bytes: int, k: int, cus: int, labels_addr: int = 0) -> dict:
+    """Host: the plan nnc_cbmm_dc_h16 follows for x and g of ``dtype`` (include/nnc_cbgrad_h16.h), as a dict keyed by
+    _native.CBDC_H16_PLAN_FIELDS.  No device needed."""
+    return _plan(nat.load().nnc_cbmm_dc_h16_plan, nat.CBDC_H16_PLAN_FIELDS, _h16_dt(dtype), m, kdim, ncols, label_bytes, k, cus, labels_addr)
 
 
 CBGRAD_OK, CBGRAD_NONFINITE, CBGRAD_ZERO = 0, 1, 2
@@ -569,7 +612,7 @@ class _CodebookLinear(torch.autograd.Function):
         if ctx.needs_input_grad[2]:
             dc = ctx.dc(x.contiguous().reshape(-1, ctx.kdim), g2, index, centers)
         if ctx.needs_input_grad[3]:
-            db = g2.sum(0)
+            db = g2.sum(0, dtype=torch.float32)   # (a float32 g: the same bits; a half g: the float32 bias's gradient)
         return dx, None, dc, db, None, None, None, None, None, None
 
 
@@ -578,9 +621,12 @@ def codebook_linear(x: torch.Tensor, labels: torch.Tensor, centers: torch.Tensor
     """codebook_matmul with gradients for x, centers and bias (an autograd Function).  The forward is the same nnc_cbmm_f32 call
     (under no_grad the bits of codebook_matmul); the backward runs codebook_matmul_dx only if x needs a gradient and
     codebook_centroid_grad (float32) only if centers does, masks a fused ReLU as torch does and sums the bias gradient over the
-    rows.  The indices get no gradient.  No host read."""
-    _require_f32_x(x, "codebook_linear")
+    rows.  The indices get no gradient.  No host read.
+    A bfloat16 or float16 x: the forward is nnc_cbmm_h16 with x's dtype out, dx has x's dtype, the gradients
+    of the float32 centers and bias are float32.  A half ``centers`` or ``bias`` raises ``TypeError``."""
     kdim, ncols = int(kdim), int(ncols)
+    if isinstance(x, torch.Tensor) and x.dtype in _H16_DT:
+        _require_centers_bias(centers, bias)
     return _CodebookLinear.apply(
         x, labels, centers, bias, bool(relu), kdim, ncols,
         lambda x2, lab, c, b, r: codebook_matmul(x2, lab, c, kdim, ncols, bias=b, relu=r),
