@@ -776,6 +776,10 @@ int nnc_cbsp_f32(const float *x, int64_t m, int64_t kdim, const void *packed, in
                  int64_t nnz, const float *centers_dev, int32_t k, const float *bias_dev, int32_t relu, float *y, void *workspace,
                  int64_t workspace_bytes, void *stream);
 
+/* The same layer on bf16 / fp16 activations (csrc/nnc_cbsp_h16.hip): nnc_cbsp_h16, its workspace query and
+ * its plan.  A header of its own, part of this ABI. */
+#include "nnc_cbsp_h16.h"
+
 /* ------------------------------------------------------------------------------------
  * The quantized layer of at most 16 centres run from 2- or 4-bit packed indices (csrc/nnc_cbpk.hip): a
  * third resident form of the (kdim, ncols) index matrix, row-major as nnc_cbmm_f32 reads it, beside the byte form and the

@@ -327,7 +327,7 @@ class Trainer(ABC):
                 layer.set_weights(tensors)
         return accuracies
 
-    def compressed_network(self, sparse=False, trainable=False, packed=False, half_inputs=False) -> torch.nn.Module:
+    def compressed_network(self, sparse=False, trainable=False, packed=False, half_inputs=False, sparse_half_inputs=False) -> torch.nn.Module:
         """A copy of the network whose quantized layers run from their codebooks and centroid indices (compressed.py; the
         float32 weights are never rebuilt), with the centres as they stand (after fine_tune_centroids, the tuned ones).
         ``sparse``: False, True (the indices in the bitmap-sparse form) or "auto" (per layer, the smaller form).
@@ -335,7 +335,8 @@ class Trainer(ABC):
         form).
         ``trainable=True`` (with sparse=False and packed=False only): the layers' centres are parameters with a backward pass (DESIGN.md
         section 12); fine_tune_compressed(..., sparse=..., packed=...) trains the other two forms.  ``half_inputs=True`` with it:
-        those layers train on bfloat16 / float16 inputs too.
+        those layers train on bfloat16 / float16 inputs too.  ``sparse_half_inputs=True`` (with ``sparse`` True or
+        "auto", not trainable): the bitmap-sparse layers run on bfloat16 / float16 inputs.
         A layer quantized with ``group_rows`` becomes a GroupedCompressedDense; with it any of the three options raises
         NotImplementedError with the layer's name (compressed.pack_grouped_layers packs the grouped layers of the result, DESIGN.md
         section 18)."""
@@ -344,7 +345,8 @@ class Trainer(ABC):
             raise RuntimeError("compressed_network needs a quantized network: call quantize first")
         from .. import compressed
 
-        return compressed.compress_network(self.neural_network, models, sparse=sparse, trainable=trainable, packed=packed, half_inputs=half_inputs)
+        return compressed.compress_network(self.neural_network, models, sparse=sparse, trainable=trainable, packed=packed, half_inputs=half_inputs,
+                                            sparse_half_inputs=sparse_half_inputs)
 
     def _discard_quantization(self) -> None:
         """The weights are about to change: the centroid indices of ``quantize`` no longer describe them, so nothing may store, run

@@ -30,9 +30,11 @@ csrc/nnc_cbmm_h16.hip): the path is chosen by the input's 
 of compressed layers stays in half.  ``centers`` and ``bias`` stay float32 buffers (each centre is rounded to the input's dtype
 inside the kernel, the bias is added in float32): feed half inputs, leave the module float32.  A module cast with ``.half()`` /
 ``.bfloat16()`` turns those buffers into half tensors, and the layer then raises the dtype ``TypeError`` of ops.codebook_matmul.
-Half inputs are for the byte form only: the bitmap-sparse, the packed and every trainable layer raise ``TypeError`` on them (the
-trainable byte layers train on them when built with ``half_inputs=True``), and
-``torch.autocast`` is not registered.
+Half inputs are for the byte form unless a layer is built for them: the bitmap-sparse, the packed and every trainable layer raise
+``TypeError`` on them (the trainable byte layers train on them when built with ``half_inputs=True``), and
+``torch.autocast`` is not registered.  ``SparseCompressedDense`` / ``SparseCompressedConv2D`` built with ``half_inputs=True``
+(``sparse_half_inputs=True`` in compress_network / load_network / Trainer.compressed_network) run on them too
+(ops.sparse_codebook_matmul -> nnc_cbsp_h16, csrc/nnc_cbsp_h16.hip), path and output dtype by the input's dtype.
 
 ``GroupedCompressedDense`` runs a Dense layer whose kernel has one codebook per block of ``group_rows`` input rows
 (utility.get_quantized_weight_grouped, Trainer.quantize(..., group_rows=); ops.grouped_codebook_matmul, csrc/nnc_cbmm_grouped.hip,
@@ -567,21 +569,34 @@ class _TrainableCodesLayer(_TrainableCentres):
 
 class _SparseCodebookLayer(_SparseForm, _CodesLayer):
     """The indices in the bitmap-sparse form (ops.SparseCodes: its buffer is the module's ``packed`` buffer), centers float32[K],
-    bias float32[ncols] or None.  No kdim * ncols tensor stays resident."""
+    bias float32[ncols] or None.  No kdim * ncols tensor stays resident.  ``half_inputs=True`` lets the layer run on bfloat16 /
+    float16 inputs (ops.sparse_codebook_matmul -> nnc_cbsp_h16): the path is chosen by the input's dtype and the
+    output has that dtype; centers and bias stay float32.  Without it a half input raises TypeError, as it always did."""
+
+    def __init__(self, codes, centers: torch.Tensor, bias: torch.Tensor | None, activation=None, half_inputs: bool = False):
+        super().__init__(codes, centers, bias, activation)
+        self.half_inputs = bool(half_inputs)
+
+    def _matmul(self, x: torch.Tensor) -> torch.Tensor:
+        if not self.half_inputs and x.dtype in (torch.bfloat16, torch.float16):
+            raise TypeError(f"{type(self).__name__} takes float32 activations, got {x.dtype}: bfloat16 and float16 inputs run on the byte form "
+                            "(CompressedDense / CompressedConv2D), and on a bitmap-sparse inference layer only when it is built with "
+                            "half_inputs=True")
+        return super()._matmul(x)
 
 
 class SparseCompressedDense(_DenseHalf, _SparseCodebookLayer):
     """Dense run from its codebook and the bitmap-sparse form of its (in, out) indices."""
 
     @classmethod
-    def from_dense(cls, dense, weight_model, bias_model=None, zero_symbol=None) -> "SparseCompressedDense":
+    def from_dense(cls, dense, weight_model, bias_model=None, zero_symbol=None, half_inputs: bool = False) -> "SparseCompressedDense":
         codes = _inference_codes(dense, weight_model, bias_model)
         kin, kout = dense.kernel.shape
-        return cls.from_codes(kin, kout, *codes, dense.activation, zero_symbol)
+        return cls.from_codes(kin, kout, *codes, dense.activation, zero_symbol, half_inputs)
 
     @classmethod
-    def from_codes(cls, kdim, ncols, labels, centers, bias, activation, zero_symbol=None) -> "SparseCompressedDense":
-        return cls(ops.pack_sparse_codes(labels, kdim, ncols, centers.numel(), zero_symbol), centers, bias, activation)
+    def from_codes(cls, kdim, ncols, labels, centers, bias, activation, zero_symbol=None, half_inputs: bool = False) -> "SparseCompressedDense":
+        return cls(ops.pack_sparse_codes(labels, kdim, ncols, centers.numel(), zero_symbol), centers, bias, activation, half_inputs)
 
 
 class SparseCompressedConv2D(_Conv2DHalf, _SparseCodebookLayer):
@@ -589,22 +604,23 @@ class SparseCompressedConv2D(_Conv2DHalf, _SparseCodebookLayer):
     in unfold order (keras_rows_for_unfold); patch chunking and the empty batch as CompressedConv2D."""
 
     def __init__(self, kernel_size: int, cin: int, pad: int, codes: ops.SparseCodes, centers: torch.Tensor, bias: torch.Tensor | None,
-                 activation=None):
+                 activation=None, half_inputs: bool = False):
         _check_conv_rows(codes, kernel_size, cin)
-        super().__init__(codes, centers, bias, activation)
+        super().__init__(codes, centers, bias, activation, half_inputs)
         self._set_conv(kernel_size, cin, pad)
 
     @classmethod
-    def from_conv(cls, conv, weight_model, bias_model=None, zero_symbol=None) -> "SparseCompressedConv2D":
+    def from_conv(cls, conv, weight_model, bias_model=None, zero_symbol=None, half_inputs: bool = False) -> "SparseCompressedConv2D":
         codes = _inference_codes(conv, weight_model, bias_model)
         h, cin, cout = _conv_shape(conv)
-        return cls.from_codes(h, cin, cout, conv.pad, *codes, conv.activation, zero_symbol)
+        return cls.from_codes(h, cin, cout, conv.pad, *codes, conv.activation, zero_symbol, half_inputs)
 
     @classmethod
-    def from_codes(cls, kernel_size, cin, cout, pad, labels, centers, bias, activation, zero_symbol=None) -> "SparseCompressedConv2D":
+    def from_codes(cls, kernel_size, cin, cout, pad, labels, centers, bias, activation, zero_symbol=None,
+                   half_inputs: bool = False) -> "SparseCompressedConv2D":
         """labels in the Keras order of the (h, w, in, out) kernel."""
         codes = _unfold_then_pack(ops.pack_sparse_codes, kernel_size, cin, cout, labels, centers.numel(), zero_symbol)
-        return cls(kernel_size, cin, pad, codes, centers, bias, activation)
+        return cls(kernel_size, cin, pad, codes, centers, bias, activation, half_inputs)
 
 
 class _TrainableSparseCodebookLayer(_SparseForm, _TrainableCodesLayer):
@@ -888,16 +904,17 @@ def _pick3(k, make_byte, make_sparse, make_packed, sparse, packed):
     return best
 
 
-def _from_codes(layer, shape, labels, centers, bias, sparse, packed=False):
+def _from_codes(layer, shape, labels, centers, bias, sparse, packed=False, sparse_half_inputs=False):
     from .neural_networks.layers import Conv2D, Dense
 
+    half = dict(half_inputs=True) if sparse_half_inputs else {}
     if isinstance(layer, Dense):
         args = (shape[0], shape[1], labels, centers, bias, layer.activation)
-        make_byte, make_sparse, make_packed = (lambda: CompressedDense(*args), lambda: SparseCompressedDense.from_codes(*args),
+        make_byte, make_sparse, make_packed = (lambda: CompressedDense(*args), lambda: SparseCompressedDense.from_codes(*args, **half),
                                                lambda: PackedCompressedDense.from_codes(*args))
     elif isinstance(layer, Conv2D):
         args = (shape[0], shape[2], shape[3], layer.pad, labels, centers, bias, layer.activation)
-        make_byte, make_sparse, make_packed = (lambda: CompressedConv2D.from_codes(*args), lambda: SparseCompressedConv2D.from_codes(*args),
+        make_byte, make_sparse, make_packed = (lambda: CompressedConv2D.from_codes(*args), lambda: SparseCompressedConv2D.from_codes(*args, **half),
                                                lambda: PackedCompressedConv2D.from_codes(*args))
     else:
         raise TypeError(f"no compressed form of {type(layer).__name__}")
@@ -906,7 +923,7 @@ def _from_codes(layer, shape, labels, centers, bias, sparse, packed=False):
     return _pick3(centers.numel(), make_byte, make_sparse, make_packed, sparse, packed)
 
 
-def _replace(layer, weight_model, bias_model, sparse=False, packed=False):
+def _replace(layer, weight_model, bias_model, sparse=False, packed=False, sparse_half_inputs=False):
     from .neural_networks.layers import Conv2D, Dense
 
     if sparse is False and packed is False:
@@ -918,7 +935,7 @@ def _replace(layer, weight_model, bias_model, sparse=False, packed=False):
     if not isinstance(layer, (Dense, Conv2D)):
         raise TypeError(f"no compressed form of {type(layer).__name__}")
     centers, labels = _codes(weight_model, layer.kernel.device)
-    return _from_codes(layer, tuple(layer.kernel.shape), labels, centers, _decoded_bias(layer.bias, bias_model), sparse, packed)
+    return _from_codes(layer, tuple(layer.kernel.shape), labels, centers, _decoded_bias(layer.bias, bias_model), sparse, packed, sparse_half_inputs)
 
 
 def _check_half_inputs(half_inputs, sparse, packed, trainable=True):
@@ -931,7 +948,19 @@ def _check_half_inputs(half_inputs, sparse, packed, trainable=True):
         raise ValueError("half_inputs=True needs sparse=False and packed=False: only the byte form trains on bfloat16 / float16 inputs")
 
 
-def compress_network(network: nn.Module, models_by_layer, sparse=False, trainable=False, packed=False, half_inputs=False) -> nn.Module:
+def _check_sparse_half_inputs(sparse_half_inputs, sparse, trainable=False):
+    if not sparse_half_inputs:
+        return
+    if trainable:
+        raise ValueError("sparse_half_inputs=True is an option of the bitmap-sparse inference layers: it needs trainable=False (the "
+                         "trainable sparse layers take float32 activations)")
+    if sparse is False:
+        raise ValueError("sparse_half_inputs=True needs sparse=True or sparse='auto': it builds the bitmap-sparse layers with "
+                         "half_inputs=True (the byte form takes bfloat16 and float16 inputs as it is)")
+
+
+def compress_network(network: nn.Module, models_by_layer, sparse=False, trainable=False, packed=False, half_inputs=False,
+                     sparse_half_inputs=False) -> nn.Module:
     """A deep copy of ``network`` whose quantized layers (``models_by_layer``: layer -> [kernel model, bias model], as
     Trainer.quantized_models_by_layer) run from their codebooks.  Layers are replaced by the attribute names of
     ``get_config()``; a layer whose kernel passed through unquantized (model None) stays float32.  ``sparse``: False (the
@@ -941,19 +970,23 @@ def compress_network(network: nn.Module, models_by_layer, sparse=False, trainabl
     ``trainable=True`` (dense indices only): TrainableCompressedDense / TrainableCompressedConv2D, centres as parameters;
     compress_network_trainable gives the bitmap-sparse and the packed trainable layers too.  ``half_inputs=True`` (with
     trainable=True, sparse=False and packed=False only, else ValueError): those layers train on bfloat16 / float16 inputs too.
+    ``sparse_half_inputs=True`` (with ``sparse`` True or "auto" and trainable=False only, else ValueError): the bitmap-sparse layers are
+    built with half_inputs=True and run on bfloat16 / float16 inputs; layers that "auto" leaves in the byte form
+    take them anyway, and what "auto" picks does not change.
     A layer whose kernel model is a utility.GroupedModel (one codebook per block of input rows) becomes a GroupedCompressedDense;
     with ``sparse``, ``packed`` or ``trainable`` set it raises NotImplementedError and names the layer (pack_grouped_layers packs
     the grouped layers of the result)."""
     _check_sparse(sparse)
     _check_packed(packed, sparse, trainable)
     _check_half_inputs(half_inputs, sparse, packed, trainable)
+    _check_sparse_half_inputs(sparse_half_inputs, sparse, trainable)
     if trainable and sparse is not False:
         raise ValueError("trainable=True needs sparse=False here: use compress_network_trainable(..., sparse=...) for trainable "
                          "bitmap-sparse layers")
     if trainable:
         return compress_network_trainable(network, models_by_layer, half_inputs=half_inputs)
     what = "sparse=" + repr(sparse) if sparse is not False else ("packed=" + repr(packed) if packed is not False else None)
-    return _compress_each(network, models_by_layer, lambda layer, wm, bm: _replace(layer, wm, bm, sparse, packed), grouped=what)
+    return _compress_each(network, models_by_layer, lambda layer, wm, bm: _replace(layer, wm, bm, sparse, packed, sparse_half_inputs), grouped=what)
 
 
 def compress_network_trainable(network: nn.Module, models_by_layer, sparse=False, packed=False, half_inputs=False) -> nn.Module:
@@ -1018,16 +1051,17 @@ def _compress_each(network: nn.Module, models_by_layer, make, grouped=None, make
     return out
 
 
-def load_network(path: str, network: nn.Module, device=None, sparse=False, packed=False) -> nn.Module:
+def load_network(path: str, network: nn.Module, device=None, sparse=False, packed=False, sparse_half_inputs=False) -> nn.Module:
     """``compress_network`` from a stored network (storage.save_compressed, as Trainer.store_report writes it: records
     "{layer}.weights" / "{layer}.biases", or "{layer}.weights#g{g}" per group of a kernel with group-wise codebooks, whose
     ``group_rows`` is the row count of the first).  ``network`` gives the architecture; layers stored raw get the stored float32 values.
-    ``sparse`` and ``packed`` as in compress_network: the stored format is the same, the indices are packed after loading.  A
+    ``sparse``, ``packed`` and ``sparse_half_inputs`` as in compress_network: the stored format is the same, the indices are packed after loading.  A
     kernel with group-wise codebooks raises NotImplementedError for either; pack_grouped_layers packs it after loading."""
     from . import storage
 
     _check_sparse(sparse)
     _check_packed(packed, sparse)
+    _check_sparse_half_inputs(sparse_half_inputs, sparse)
     device = next(network.parameters()).device if device is None else device
     codes = storage.load_compressed_codes(path, device)
     out = copy.deepcopy(network)
@@ -1061,7 +1095,7 @@ def load_network(path: str, network: nn.Module, device=None, sparse=False, packe
             target.set_weights([went.reshape(target.kernel.shape)] + ([bias.reshape(target.bias.shape)] if bias is not None else []))
             continue
         shape, centers, labels = went
-        setattr(out, name, _from_codes(layer, tuple(shape), labels, centers, bias, sparse, packed))
+        setattr(out, name, _from_codes(layer, tuple(shape), labels, centers, bias, sparse, packed, sparse_half_inputs))
     return out
 
 

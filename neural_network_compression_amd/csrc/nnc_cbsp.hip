@@ -17,7 +17,8 @@
 //   k_cbsp_bits / k_cbsp_rowscan / k_cbsp_basescan / k_cbsp_emit   the pack: ballot + popcount per segment, a scan of the
 //                  counts in each row, a scan of the row totals, the symbols emitted at count + v_mbcnt.  No per-weight temporary.
 //   k_cbsp_unpack  the inverse.
-//   k_cbsp_stream  m <= 16: a wave owns one 64-column segment (a lane a column) over a range of rows.  The bitmap words and
+//   k_cbsp_stream  (nnc_cbsp.hpp, with the plan and k_cbsp_reduce: nnc_cbsp_h16.hip instantiates them for bf16 / fp16 x; here x is
+//                  float32)  m <= 16: a wave owns one 64-column segment (a lane a column) over a range of rows.  The bitmap words and
 //                  offsets of 64 rows come in one vector load per lane and are broadcast by v_readlane; a lane's symbol is at
 //                  count + v_mbcnt(word); the d table sits in LDS with one copy per bank (CbTable); x[r, i] is broadcast by
 //                  v_readlane; the symbol loads of CB_UNROLL rows are in flight together.  The row sums of x are kept on the
@@ -29,7 +30,6 @@
 #include "nnc_cbsp.hpp"
 #include "nnc_cbtile.hpp"
 
-#define SP_ROWS 64                // rows whose bitmap words one vector load brings to a wave
 #define SP_PLAN_LEN NNC_CBSP_PLAN_LEN
 
 __device__ __forceinline__ uint32_t sp_label(const unsigned char *labels, int lb, long long idx)
@@ -154,199 +154,6 @@ __global__ __launch_bounds__(256) void k_cbsp_unpack(const uint64_t *__restrict_
     }
 }
 
-// ------------------------------------------------------------------ the plan (host)
-struct SpPlan {
-    int path;                     // NNC_CBMM_NONE / _STREAM / _TILED / _BIAS
-    int mt;                       // stream: rows of x per launch (a power of two >= m)
-    int entries, cshift;          // the LDS d table: entries x (1 << cshift) copies
-    int rowsum;                   // NNC_CBSP_ROWSUM_*
-    long long col_tiles, row_tiles, splits, rows_per_split, lds;
-};
-
-static SpPlan sp_plan(long long m, long long kdim, long long ncols, int lb, int k, int cus)
-{
-    SpPlan p{};
-    if (m == 0 || ncols == 0) return p;
-    if (kdim == 0) {
-        p.path = NNC_CBMM_BIAS;
-        return p;
-    }
-    cus = std::max(1, std::min(cus, CB_PLAN_CUS));
-    long long s;
-    if (m <= CB_SKINNY_M) {
-        p.path = NNC_CBMM_STREAM;
-        p.rowsum = NNC_CBSP_ROWSUM_FUSED;
-        p.mt = cb_mt(m);
-        p.col_tiles = cdiv(ncols, 64);
-        p.row_tiles = 1;
-        // four workgroups per CU; every wave keeps at least one batch of SP_ROWS rows; the partials (splits x m x ncols x 4 B)
-        // stay within a quarter of the bitmap
-        s = std::min({cdiv(4LL * cus, p.col_tiles), kdim / (CB_WAVES * SP_ROWS), kdim / (16 * m)});
-        if (lb == 1) {
-            p.entries = 256;
-            p.cshift = __builtin_ctz(CB_U8_COPIES);
-        } else {
-            p.entries = k + 1;
-            while ((1 << p.cshift) < CB_U8_COPIES && (long long)p.entries << (p.cshift + 1) <= CB_U16_WORDS) ++p.cshift;
-        }
-        p.lds = ((long long)p.entries << p.cshift) * 4 + (long long)p.mt * 65 * 4 + (long long)p.entries * 4;
-    } else {
-        p.path = NNC_CBMM_TILED;
-        p.rowsum = NNC_CBSP_ROWSUM_PASS;
-        p.col_tiles = cdiv(ncols, TB_N);
-        p.row_tiles = cdiv(m, TB_M);
-        s = std::min({cdiv(2LL * cus, p.col_tiles * p.row_tiles), kdim / (16 * TB_K), 16LL});
-        p.entries = k + 1;
-        p.lds = (long long)(TB_K * TB_M + TB_K * TB_N + k + 1) * 4 + TB_K * TB_N;
-    }
-    s = std::max(1LL, s);
-    p.rows_per_split = cdiv(kdim, s);
-    p.splits = cdiv(kdim, p.rows_per_split);
-    return p;
-}
-
-// the workspace: [partials: splits x m x ncols floats, when split][row sums: rsplits x m floats], 256-byte aligned parts
-static long long sp_rsplits(const SpPlan &p)
-{
-    if (p.path == NNC_CBMM_TILED) return 1;
-    return p.path == NNC_CBMM_STREAM && p.splits > 1 ? p.splits : 0;
-}
-static long long sp_part_bytes(const SpPlan &p, long long m, long long ncols)
-{
-    return p.splits > 1 ? (p.splits * m * ncols * 4 + 255) / 256 * 256 : 0;
-}
-static int64_t sp_ws_bytes(const SpPlan &p, long long m, long long ncols) { return sp_part_bytes(p, m, ncols) + sp_rsplits(p) * m * 4; }
-
-// ------------------------------------------------------------------ device helpers
-__device__ __forceinline__ float sp_epilogue(float acc, float cz, float rs, const float *__restrict__ bias, long long c, int relu)
-{
-    float v = cz != 0.0f ? cz * rs + acc : acc;
-    if (bias) v += bias[c];
-    if (relu) v = v < 0.0f ? 0.0f : v;   // NaN stays NaN, as torch.relu
-    return v;
-}
-
-// ------------------------------------------------------------------ skinny: m <= 16
-// grid (segments, splits), CB_THREADS threads.  out: y (splits == 1) or the partials [split][m][ncols]; rs_out: the row-sum
-// partials [split][m] (split only; written by the segment-0 workgroups).
-template <typename LT, int MT>
-__global__ __launch_bounds__(CB_THREADS) void k_cbsp_stream(const float *__restrict__ x, int m, long long kdim, const uint64_t *__restrict__ bitmap,
-                                                            const uint32_t *__restrict__ lo, const uint32_t *__restrict__ hi, const LT *__restrict__ sym,
-                                                            long long nnz, long long ncols, long long segs, const float *__restrict__ centers, int k,
-                                                            int z, int entries, int cshift, long long rows_per_split, const float *__restrict__ bias,
-                                                            int relu, int direct, float *__restrict__ out, float *__restrict__ rs_out)
-{
-    constexpr int U = CB_UNROLL;
-    extern __shared__ float smem[];
-    float *tab = smem;
-    float *red = smem + (entries << cshift);          // [MT][64] accumulators, then [MT] row sums
-    float *stage = red + MT * 65;
-    const float cz = sp_cz(centers, k, z);
-    sp_fill(tab, stage, centers, k, cz, entries, cshift);
-
-    const int lane = threadIdx.x & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const long long seg = blockIdx.x;
-    const long long col = seg * 64 + lane;
-    const long long s_lo = (long long)blockIdx.y * rows_per_split, s_hi = std::min(kdim, s_lo + rows_per_split);
-    const long long per_wave = (s_hi - s_lo + CB_WAVES - 1) / CB_WAVES;
-    const long long i0 = std::min(s_hi, s_lo + wave * per_wave), i1 = std::min(s_hi, i0 + per_wave);
-
-    float acc[MT];
-#pragma unroll
-    for (int r = 0; r < MT; ++r) acc[r] = 0.0f;
-    float rsa = 0.0f, rsb = 0.0f;                     // row sums: lane f holds those of x[f / U, . + f % U] (and f + 64)
-    __syncthreads();
-
-    for (long long ib = i0; ib < i1; ib += SP_ROWS) {
-        // the words and counts of rows ib .. ib + 63, one row per lane (rows past i1: an empty word)
-        const long long ir = ib + lane;
-        uint64_t wl = 0;
-        long long cl = 0;
-        if (ir < i1) {
-            const long long gi = ir * segs;
-            wl = bitmap[gi + seg];
-            cl = sp_count(lo[gi + seg], lo[gi], hi[ir]);
-        }
-        const uint32_t wlo = (uint32_t)wl, whi = (uint32_t)(wl >> 32), clo = (uint32_t)cl, chi = (uint32_t)((uint64_t)cl >> 32);
-        const int nb = (int)std::min((long long)SP_ROWS, i1 - ib);
-        for (int u0 = 0; u0 < nb; u0 += U) {
-            const long long i = ib + u0;
-            float xa, xb;
-            {
-                const int f0 = lane, f1 = lane + 64, r0 = f0 / U, r1 = f1 / U;
-                xa = (r0 < m && i + f0 % U < i1) ? x[(long long)r0 * kdim + i + f0 % U] : 0.0f;
-                xb = (MT * U > 64 && r1 < m && i + f1 % U < i1) ? x[(long long)r1 * kdim + i + f1 % U] : 0.0f;
-            }
-            uint32_t bits[U], sv[U];
-#pragma unroll
-            for (int u = 0; u < U; ++u) {   // the symbol loads of U rows in flight together
-                const uint64_t word = ((uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)whi, u0 + u) << 32) |
-                                      (uint32_t)__builtin_amdgcn_readlane((int)wlo, u0 + u);
-                const long long cnt = (long long)(((uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)chi, u0 + u) << 32) |
-                                                  (uint32_t)__builtin_amdgcn_readlane((int)clo, u0 + u));
-                bits[u] = (uint32_t)(word >> lane) & 1u;
-                const long long pos = cnt + sp_rank(word);
-                sv[u] = 0;
-                if (bits[u] && pos < nnz) sv[u] = sym[pos];
-            }
-#pragma unroll
-            for (int u = 0; u < U; ++u) {
-                const float wv = tab[CbTable<LT>::index(sv[u], k, cshift, lane)];
-#pragma unroll
-                for (int r = 0; r < MT; ++r) {
-                    const int f = r * U + u;
-                    const float xv = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, f < 64 ? xa : xb), f & 63));
-                    if (bits[u]) acc[r] = __builtin_fmaf(xv, wv, acc[r]);
-                }
-            }
-            rsa += xa;
-            rsb += xb;
-        }
-    }
-    // the wave's row sums, r's U lanes in lane order
-    float rs[MT];
-#pragma unroll
-    for (int r = 0; r < MT; ++r) {
-        float v = 0.0f;
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-            const int f = r * U + u;
-            v += __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, f < 64 ? rsa : rsb), f & 63));
-        }
-        rs[r] = v;
-    }
-    // the waves' sums, added to wave 0's in wave order
-    for (int src = 1; src < CB_WAVES; ++src) {
-        __syncthreads();
-        if (wave == src) {
-#pragma unroll
-            for (int r = 0; r < MT; ++r) red[r * 64 + lane] = acc[r];
-            if (lane == 0)
-#pragma unroll
-                for (int r = 0; r < MT; ++r) red[MT * 64 + r] = rs[r];
-        }
-        __syncthreads();
-        if (wave == 0) {
-#pragma unroll
-            for (int r = 0; r < MT; ++r) {
-                acc[r] += red[r * 64 + lane];
-                rs[r] += red[MT * 64 + r];
-            }
-        }
-    }
-    if (wave != 0) return;
-    if (!direct && seg == 0 && lane == 0)
-        for (int r = 0; r < m && r < MT; ++r) rs_out[(long long)blockIdx.y * m + r] = rs[r];
-    if (col >= ncols) return;
-#pragma unroll
-    for (int r = 0; r < MT; ++r) {
-        if (r >= m) continue;
-        if (direct) out[(long long)r * ncols + col] = sp_epilogue(acc[r], cz, rs[r], bias, col, relu);
-        else out[((long long)blockIdx.y * m + r) * ncols + col] = acc[r];
-    }
-}
-
 // ------------------------------------------------------------------ tiled: m > 16
 // grid (col_tiles * row_tiles, splits), 256 threads, as k_cbmm_tiled; the W tile is decoded from bitmap and symbols: thread t
 // decodes row t / 32 of the tile, columns (t % 32) * 4 .. + 3 (one segment, one word, one count + popcount).
@@ -432,41 +239,6 @@ __global__ __launch_bounds__(256) void k_cbsp_rowsum(const float *__restrict__ x
         }
         if (threadIdx.x == 0) rs[r] = part[0];
         __syncthreads();
-    }
-}
-
-// ------------------------------------------------------------------ split-K combine
-// the partials as k_cbmm_reduce sums them (four quarters of the splits in order, then the quarters in order); the row sum of r
-// is the sum of its rsplits partials in split order.  part == NULL (kdim = 0): y = bias.
-#define RED_Q 4
-__global__ __launch_bounds__(256) void k_cbsp_reduce(const float *__restrict__ part, long long splits, long long m, long long ncols,
-                                                     const float *__restrict__ rsp, long long rsplits, const float *__restrict__ centers, int k,
-                                                     int z, const float *__restrict__ bias, int relu, float *__restrict__ y)
-{
-    __shared__ float qs[RED_Q - 1][64];
-    const long long mn = m * ncols;
-    const float cz = sp_cz(centers, k, z);
-    const int o = threadIdx.x & 63, q = threadIdx.x >> 6;
-    const long long per_q = (splits + RED_Q - 1) / RED_Q;
-    const long long s0 = std::min(splits, q * per_q), s1 = std::min(splits, s0 + per_q);
-    for (long long base = (long long)blockIdx.x * 64; base < mn; base += (long long)gridDim.x * 64) {
-        const long long idx = base + o;
-        float v = 0.0f;
-        if (idx < mn) {
-#pragma unroll 8
-            for (long long s = s0; s < s1; ++s) v += part[s * mn + idx];
-        }
-        __syncthreads();
-        if (q > 0) qs[q - 1][o] = v;
-        __syncthreads();
-        if (q == 0 && idx < mn) {
-#pragma unroll
-            for (int j = 0; j < RED_Q - 1; ++j) v += qs[j][o];
-            const long long r = idx / ncols;
-            float rs = 0.0f;
-            for (long long s = 0; s < rsplits; ++s) rs += rsp[s * m + r];
-            y[idx] = sp_epilogue(v, cz, rs, bias, idx - r * ncols, relu);
-        }
     }
 }
 
@@ -577,7 +349,7 @@ static void launch_sp_stream(dim3 grid, size_t lds, hipStream_t s, const float *
                              long long nnz, long long ncols, const float *centers, int k, int z, const SpPlan &p, const float *bias, int relu, int direct,
                              float *out, float *rs_out)
 {
-    hipLaunchKernelGGL((k_cbsp_stream<LT, MT>), grid, dim3(CB_THREADS), lds, s, x, m, kdim, reinterpret_cast<const uint64_t *>(base),
+    hipLaunchKernelGGL((k_cbsp_stream<float, LT, MT>), grid, dim3(CB_THREADS), lds, s, x, m, kdim, reinterpret_cast<const uint64_t *>(base),
                        reinterpret_cast<const uint32_t *>(base + L.off_lo), reinterpret_cast<const uint32_t *>(base + L.off_hi),
                        reinterpret_cast<const LT *>(base + L.off_sym), nnz, ncols, L.segs, centers, k, z, p.entries, p.cshift, p.rows_per_split, bias, relu,
                        direct, out, rs_out);
@@ -647,7 +419,7 @@ extern "C" int nnc_cbsp_f32(const float *x, int64_t m, int64_t kdim, const void 
     const int rgrid = (int)std::max(1LL, std::min(cdiv(mn, 64), 8192LL));
     const SpPlan p = sp_plan(m, kdim, ncols, label_bytes, k, cu_count());
     if (p.path == NNC_CBMM_BIAS) {   // kdim = 0: y = bias (zeros without one)
-        hipLaunchKernelGGL(k_cbsp_reduce, dim3(rgrid), dim3(256), 0, s, (const float *)nullptr, 0LL, (long long)m, (long long)ncols, (const float *)nullptr,
+        hipLaunchKernelGGL((k_cbsp_reduce<float, float>), dim3(rgrid), dim3(256), 0, s, (const float *)nullptr, 0LL, (long long)m, (long long)ncols, (const float *)nullptr,
                            0LL, centers_dev, (int)k, (int)zero_symbol, bias_dev, (int)relu, y);
         LAUNCHCHK("k_cbsp_reduce");
         return NNC_OK;
@@ -679,7 +451,7 @@ extern "C" int nnc_cbsp_f32(const float *x, int64_t m, int64_t kdim, const void 
         LAUNCHCHK("k_cbsp_tiled");
     }
     if (!direct) {
-        hipLaunchKernelGGL(k_cbsp_reduce, dim3(rgrid), dim3(256), 0, s, part, (long long)p.splits, (long long)m, (long long)ncols, rsp, sp_rsplits(p),
+        hipLaunchKernelGGL((k_cbsp_reduce<float, float>), dim3(rgrid), dim3(256), 0, s, part, (long long)p.splits, (long long)m, (long long)ncols, rsp, sp_rsplits(p),
                            centers_dev, (int)k, (int)zero_symbol, bias_dev, (int)relu, y);
         LAUNCHCHK("k_cbsp_reduce");
     }

@@ -29,9 +29,9 @@ def _require_cuda(t: torch.Tensor, name: str, dtype=None):
 def _require_f32_x(x, who: str):
     """The entry points that have no half-precision kernels: a bfloat16 / float16 x names the one form that has."""
     if isinstance(x, torch.Tensor) and x.dtype in (torch.bfloat16, torch.float16):
-        raise TypeError(f"{who} takes float32 activations, got {x.dtype}: bfloat16 and float16 inputs run on the byte form only "
+        raise TypeError(f"{who} takes float32 activations, got {x.dtype}: bfloat16 and float16 inputs run on the byte form "
                         "(ops.codebook_matmul and ops.codebook_linear; CompressedDense / CompressedConv2D, and their trainable "
-                        "layers built with half_inputs=True)")
+                        "layers built with half_inputs=True) and, forward only, on the bitmap-sparse form (ops.sparse_codebook_matmul)")
 
 
 def _stream(t: torch.Tensor) -> int:
@@ -791,13 +791,27 @@ def pack_sparse_codes(labels: torch.Tensor, kdim: int, ncols: int, k: int, zero_
 
 
 def sparse_codebook_matmul(x: torch.Tensor, codes: SparseCodes, centers: torch.Tensor, bias: torch.Tensor | None = None,
-                           relu: bool = False) -> torch.Tensor:
+                           relu: bool = False, out_dtype=None) -> torch.Tensor:
     """y = c_z * sum_i x[., i] + the stored weights' x[., i] * (centers[label] - c_z) (+ bias, then ReLU): x @ W for W[i, o] =
     centers[labels[i, o]] read from the bitmap-sparse form (include/nnc.h, nnc_cbsp_f32).  With centers[zero_symbol] == 0 the
     skipped weights are absent (an Inf in x meets no 0).  x: float32 (..., kdim); centers: float32[codes.k]; bias: float32[ncols]
-    or None.  Returns float32 (..., ncols).  Inference only, as codebook_matmul."""
-    _require_f32_x(x, "sparse_codebook_matmul")
-    _require_cuda(x, "x", torch.float32)
+    or None.  Returns float32 (..., ncols).
+    A bfloat16 or float16 x takes nnc_cbsp_h16: centers and bias stay float32, every centre is rounded to x's
+    dtype as ``centers.to(x.dtype)`` does, the products are exact and the sums float32; the result has ``out_dtype``: None (x's dtype,
+    the float32 value rounded once) or torch.float32.  Up to 16 rows of x it is the float32 product of the widened x and the rounded
+    centres bit for bit; above, it is ops.codebook_matmul on ``codes.to_dense()`` bit for bit, in which a skipped weight is an entry
+    of W (an Inf in x at a skipped position gives NaN).  A float32 x takes no ``out_dtype`` but None or torch.float32.
+    Inference only, as codebook_matmul."""
+    if isinstance(x, torch.Tensor) and x.dtype in _H16_DT:
+        _require_cuda(x, "x")
+        if out_dtype not in (None, torch.float32):
+            raise TypeError(f"out_dtype must be None ({x.dtype}) or torch.float32 for x of {x.dtype}, got {out_dtype}")
+        y_dtype = x.dtype if out_dtype is None else out_dtype
+    else:
+        _require_cuda(x, "x", torch.float32)
+        if out_dtype not in (None, torch.float32):
+            raise TypeError(f"out_dtype must be None or torch.float32 for a float32 x, got {out_dtype}")
+        y_dtype = torch.float32
     _require_centers_bias(centers, bias)
     if not isinstance(codes, SparseCodes):
         raise TypeError("codes must be a SparseCodes (ops.pack_sparse_codes)")
@@ -806,8 +820,15 @@ def sparse_codebook_matmul(x: torch.Tensor, codes: SparseCodes, centers: torch.T
     lead, m = _rows(x, "x", kdim)
     if centers.numel() != codes.k:
         raise ValueError(f"centers must hold k = {codes.k} values, got {centers.numel()}")
-    y = _empty_y(x, lead, ncols, bias, torch.float32)
+    y = _empty_y(x, lead, ncols, bias, y_dtype)
     L = nat.load()
+    if x.dtype in _H16_DT:
+        ws_bytes = int(L.nnc_cbsp_h16_workspace_bytes(m, kdim, ncols, codes.label_bytes))
+        ws = _workspace(ws_bytes, x.device)
+        nat.check(L.nnc_cbsp_h16(_ptr(x), _H16_DT[x.dtype], m, kdim, _ptr(codes.buf), codes.nbytes(), codes.label_bytes, ncols, codes.zero_symbol,
+                                 codes.nnz, _ptr(centers), centers.numel(), _ptr(bias), 1 if relu else 0, _ptr(y), _H16_DT.get(y_dtype, nat.DT_F32),
+                                 _ptr(ws), ws_bytes, _stream(x)))
+        return y
     ws_bytes = int(L.nnc_cbsp_workspace_bytes(m, kdim, ncols, codes.label_bytes))
     ws = _workspace(ws_bytes, x.device)
     nat.check(L.nnc_cbsp_f32(_ptr(x), m, kdim, _ptr(codes.buf), codes.nbytes(), codes.label_bytes, ncols, codes.zero_symbol, codes.nnz,
@@ -819,6 +840,14 @@ def cbsp_plan(m: int, kdim: int, ncols: int, label_bytes: int, k: int, cus: int)
     """Host: the plan nnc_cbsp_f32 follows on a device with ``cus`` compute units (include/nnc.h, nnc_cbsp_plan), as a dict keyed
     by _native.CBSP_PLAN_FIELDS.  No device needed."""
     return _plan(nat.load().nnc_cbsp_plan, nat.CBSP_PLAN_FIELDS, m, kdim, ncols, label_bytes, k, cus)
+
+
+def cbsp_h16_plan(dtype, m: int, kdim: int, ncols: int, label_bytes: int, k: int, cus: int) -> dict:
+    """Host: the plan nnc_cbsp_h16 follows for x of ``dtype`` (torch.bfloat16 / torch.float16) on a device with ``cus`` compute units
+    (include/nnc_cbsp_h16.h, nnc_cbsp_h16_plan), as a dict keyed by _native.CBSP_H16_PLAN_FIELDS.  No device needed."""
+    if dtype not in _H16_DT:
+        raise TypeError(f"dtype must be torch.bfloat16 or torch.float16, got {dtype}")
+    return _plan(nat.load().nnc_cbsp_h16_plan, nat.CBSP_H16_PLAN_FIELDS, _H16_DT[dtype], m, kdim, ncols, label_bytes, k, cus)
 
 
 def sparse_codebook_matmul_dx(g: torch.Tensor, codes: SparseCodes, centers: torch.Tensor) -> torch.Tensor:
