@@ -113,14 +113,16 @@ int nnc_apply_mask_f32(float *x, const uint8_t *mask, int64_t n, void *stream);
 size_t nnc_minmax_workspace_bytes(int64_t n);
 /* out_dev[0] = min, out_dev[1] = max over the elements (over the non-zero ones if
  * skip_zeros: Trainer.quantize strips exact zeros first, trainer.py:55-59);
- * count_dev = number of elements considered. */
+ * count_dev = number of elements considered.  A NaN element is skipped by min and max (fminf / fmaxf) but counted in
+ * count_dev; callers that must notice NaN do so through the mean (LayerStats). */
 int nnc_minmax_f32(const float *x, int64_t n, int skip_zeros, float *out_dev, int64_t *count_dev, void *ws,
                    size_t ws_bytes, void *stream);
 
 /* One pass for everything the pipeline wants to know about a (pruned) vector: out_dev[0..1] =
  * min / max over all elements, out_dev[2..3] = min / max over the non-zero ones (+inf / -inf if
  * there are none), signs_dev[0] = #{x < 0}, signs_dev[1] = #{x == 0} (what nnc_sort_pruned_f32
- * needs).  out_dev holds 4 floats. */
+ * needs).  out_dev holds 4 floats.  A NaN element is skipped by all four minima / maxima (fminf / fmaxf) and counts as
+ * neither negative nor zero; -0.0 counts as zero, a subnormal as non-zero. */
 int nnc_minmax_signs_f32(const float *x, int64_t n, float *out_dev, int64_t *signs_dev, void *ws, size_t ws_bytes,
                          void *stream);
 
@@ -148,7 +150,9 @@ int nnc_layer_stats_f32(const float *x, int64_t n, float *out6_dev, int64_t *sig
                         void *stream);
 
 /* ranks_out_dev[i] = #{ j : x_sorted[j] < values_dev[i] } for an ascending x_sorted: the histogram of
- * get_weight_distribution (utility.py:366-372) from the value-sorted copy, as differences of the ranks of the 32 steps. */
+ * get_weight_distribution (utility.py:366-372) from the value-sorted copy, as differences of the ranks of the 32 steps.
+ * The comparison is the float32 one (-0.0 == +0.0; -inf and +inf rank as 0 and n against finite data); the rank of a NaN
+ * value is unspecified. */
 int nnc_rank_sorted_f32(const float *x_sorted, int64_t n, const float *values_dev, int32_t m, int64_t *ranks_out_dev, void *stream);
 /* counts_dev[b] += #{ i : steps[b] <= x[i] < steps[b+1] }, b = 0..30 (caller zeroes counts_dev). */
 int nnc_hist31_f32(const float *x, int64_t n, int skip_zeros, const float *steps32_dev, int64_t *counts_dev,
@@ -421,7 +425,8 @@ int nnc_ref_sums_f32(const float *x, int64_t n, float x_mean, const void *labels
                      float *sums_out_dev, int64_t *counts_out_dev, void *stream);
 int nnc_kmeans_set_done_if(void *ws, const int32_t *flag_dev, int32_t done_code, void *stream);
 
-/* counts_dev[j] += #{ i : labels[i] == j }  (caller zeroes counts_dev; int64[k]). */
+/* counts_dev[j] += #{ i : labels[i] == j }  (caller zeroes counts_dev; int64[k]).  Labels are read as unsigned; an index >= k
+ * is not counted. */
 int nnc_bincount(const void *labels, int label_bytes, int64_t n, int32_t k, int64_t *counts_dev, void *stream);
 
 /* ------------------------------------------------------------------------------------
@@ -531,7 +536,8 @@ int nnc_kmeanspp_seed_f32(const float *x, int64_t n, float x_mean, int32_t k, in
  *   every dL/dC_k is NaN (the convention of nnc_cbmm_dc_f32), and the sums are to be ignored.  A sharded caller reduces it
  *   with the sums (it may be sums_dev[k] of a k + 1 buffer, so that one sum all-reduce carries both).
  * nnc_gather_f32: out[i] = centers_dev[labels[i]], the decode step cluster_centers_[labels_] (common/utility.py:239), for
- *   writing updated centroids back into the layer.
+ *   writing updated centroids back into the layer.  The centre's bits are copied as they are; labels are read as unsigned,
+ *   and an index >= k gathers +0.0.
  * ---------------------------------------------------------------------------------- */
 int nnc_centroid_grad_f32(const float *grad, const void *labels, int label_bytes, int64_t n, int32_t k, int32_t fix_shift,
                           int64_t *sums_dev, int64_t *counts_dev, int64_t *nonfinite_dev, void *stream);
