@@ -239,7 +239,9 @@ typedef struct nnc_kmeans_status {
     int32_t n_unproven;  /* ... and the events such a chain met but could not prove (the fit then pauses with paused == 2) */
     int32_t n_in_place;  /* of n_relocated: the events settled inside an iteration's own launch (the resident loop, or the finalize
                             step of a rank-boundary pass: small events, no relocation chain needed) */
-    int32_t reserved;
+    int32_t n_reloc_null; /* empty-cluster events in which nothing was relocated: every sample sits on its centre (np.max(distances)
+                             == 0: scikit-learn returns, _k_means_common.pyx:189; duplicate initial centres on few-valued data).
+                             Such an event is no relocation: whoever counts events as they pause takes these off again */
 } nnc_kmeans_status;
 
 int32_t nnc_fix_shift(float absmax, int64_t n_total);
@@ -518,7 +520,28 @@ int nnc_host_density_init(const float *xnew300, const double *cdf300, int32_t bi
  * then -- are not reproducible by anybody).  Single GPU (the whole vector).
  *   uniforms_dev : (k - 1) * nnc_kmeanspp_trials(k) float64 in [0, 1), round-major
  *   seeds_out_dev[k] : the seeds, centred (x[id] - x_mean in float32), in the order chosen; seed_ids_out_dev[k]: their indices
- *   ws: nnc_kmeanspp_workspace_bytes(n, k) bytes, 256-byte aligned.
+ *   ws: nnc_kmeanspp_workspace_bytes(n, k) bytes, 256-byte aligned.  With nblk = ceil(n / 1024) blocks and
+ *       ngroups = ceil(nblk / 256) groups, each part rounded up to 256 bytes: the round state (120 bytes), n float32
+ *       distances, 2 * 8 arrays of nblk float64 (block sums and their in-group prefix per trial slot) and 2 * 8 arrays of
+ *       ngroups + 1 float64 (group totals and their prefix per trial slot).  Nothing outside these bytes is written.
+ * The rules of a round (tests/test_gpu_kmeanspp_edges.py; on data whose sums are exact they are scikit-learn's own results):
+ *   - a candidate is searchsorted(running sum, r = u * float64(float32 potential), side="left"): the FIRST sample whose running
+ *     sum is >= r.  r equal to a running-sum value gives the sample that reaches it; on a plateau of zero increments (the
+ *     zeros of a pruned tensor once 0 is a seed) that is the sample in front of the plateau, also across block and group borders;
+ *   - the search has three levels (group totals, block sums inside the group, samples inside the block), each with a
+ *     fallback when no entry reaches r: the last group, the group's last block, the block's last sample.  r above the total
+ *     (u = 1 - 2^-53 on a potential that float32 rounded up), r = inf and r = NaN take all three and give sample n - 1,
+ *     numpy's searchsorted clipped to n - 1.  The block fallback is only taken below the group fallback (a group's total is the
+ *     very sum its last block is compared with); the sample fallback is also taken alone, where a block's butterfly sum
+ *     reaches r and its left-to-right sum does not;
+ *   - a potential of 0 (all samples equal, or fewer distinct values than k) makes r = 0 and every later candidate, and
+ *     seed, sample 0; an inf potential (float32 overflow) makes r inf, or NaN for u = 0, and every candidate sample n - 1;
+ *   - the candidate of the smallest float32 potential wins, the first trial slot among equal ones (np.argmin), also when the
+ *     same sample was drawn twice;
+ *   - x_mean is taken as given: the distances and seeds_out are those of float32(x[i] - x_mean) whether or not x_mean is the
+ *     mean of x.
+ * Argument errors (n < 1, k < 1, k > NNC_KMAX, first_id outside [0, n), a null x / output / workspace, null uniforms with
+ * k > 1: NNC_EINVAL; ws_bytes short: NNC_ENOSPACE; ws not 256-byte aligned: NNC_EINVAL) return before any device call.
  * ---------------------------------------------------------------------------------- */
 int32_t nnc_kmeanspp_trials(int32_t k);
 size_t nnc_kmeanspp_workspace_bytes(int64_t n, int32_t k);

@@ -2263,7 +2263,7 @@ __device__ __forceinline__ void km_init_body(KmWs *ws, const nnc_kmeans_params &
     if (tid == 0) {
         ws->st.iter = 0; ws->st.done = 0; ws->st.paused = 0; ws->st.n_empty = 0;
         ws->st.shift_tot = 0.0f; ws->st.tol = p.tol; ws->st.k = p.k; ws->st.same_counts = 0;
-        ws->st.reloc_ties = 0; ws->st.reloc_multi = 0; ws->st.n_relocated = 0; ws->st.n_unproven = 0; ws->st.n_in_place = 0; ws->st.reserved = 0; ws->spec_go = 0;
+        ws->st.reloc_ties = 0; ws->st.reloc_multi = 0; ws->st.n_relocated = 0; ws->st.n_unproven = 0; ws->st.n_in_place = 0; ws->st.n_reloc_null = 0; ws->spec_go = 0;
         ws->p = p; ws->cur = 0; ws->glog2 = glog2; ws->rlog2 = rlog2; ws->inv = inv; ws->reloc_fail = 0; ws->cells_pending = 0;
     }
     for (int j = tid; j < p.k; j += KM_THREADS) {
@@ -2956,7 +2956,8 @@ __device__ void km_relocate_apply(KmWs *__restrict__ ws, const long long *__rest
     const int tid = threadIdx.x, lane = tid & 63;
     const int k = ws->p.k;
     const int m = n_empty < nkeys ? n_empty : nkeys;
-    if (m == 0 || (keys[0] >> 32) == 0) return;
+    if (m == 0) return;
+    if ((keys[0] >> 32) == 0) { if (tid == 0) ws->st.n_reloc_null += 1; return; } // (an event, but no relocation: the counts of events leave it out)
     if (tid == 0) {
         // what scikit-learn leaves to numpy.argpartition: the pairing when several clusters are empty, and WHICH samples
         // are taken when two different ones tie at the cut (the runner-up key, if the caller passed it, tells)

@@ -419,7 +419,7 @@ extern "C" int nnc_compress_layer_f32(float *x, int64_t n, const nnc_layer_param
         LCHK(nnc_kmeans_assign(x, wb + L.km_ws, &p, 0, labels_out, res->label_bytes, lp->want_values ? values_out : nullptr, nullptr, nullptr, stream));
         LCHK(nnc_kmeans_label_counts(xs, wb + L.km_ws, &p, 0, counts_d, stream));
         LCHK(read_back(back, hb + 1024, (int)al((size_t)k * 12)));
-        res->n_iter = st.iter; res->stop = st.done; res->n_relocations = nwin; res->n_reloc_windowed = nwin;
+        res->n_iter = st.iter; res->stop = st.done; res->n_relocations = nwin - st.n_reloc_null; res->n_reloc_windowed = nwin - st.n_reloc_null; // (events that moved a sample)
         res->reloc_ties = st.reloc_ties; res->reloc_multi = st.reloc_multi;
         res->arith = NNC_ARITH_FIXED;
     }

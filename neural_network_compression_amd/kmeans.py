@@ -846,7 +846,9 @@ class DeviceKMeans:
         nat.check(self.L.nnc_kmeans_label_counts(self.x_iter.data_ptr(), self.ws.data_ptr(), ctypes.byref(self.p),
                                                  1 if strict_labels is not None else 0, counts.data_ptr(), self.stream))
         host = blk.cpu().numpy()   # the one host read of the epilogue, behind everything that was enqueued
-        model = QuantizedModel(host[8 * self.k:].view(np.float32).copy(), lab, n_iter, self.n_relocations, stop)
+        # (an empty-cluster event in which every sample sat on its centre relocated nothing and is no relocation: scikit-learn returns
+        # there, the oracle and the one-launch form do not count it either)
+        model = QuantizedModel(host[8 * self.k:].view(np.float32).copy(), lab, n_iter, self.n_relocations - int(st.n_reloc_null), stop)
         model.counts_device_ = counts
         model.counts_host_ = host[: 8 * self.k].view(np.int64).copy()   # (this rank's shard of the vector)
         model.n_reloc_windowed_ = self.n_reloc_windowed   # relocation events settled without a pass over the vector
