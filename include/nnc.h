@@ -973,6 +973,10 @@ int nnc_cbsp_dc_plan(int64_t m, int64_t kdim, int64_t ncols, int label_bytes, in
 int nnc_cbsp_dc_f32(const float *x, const float *g, int64_t m, int64_t kdim, const void *packed, int64_t packed_bytes, int label_bytes, int64_t ncols,
                     int32_t zero_symbol, int64_t nnz, int32_t k, void *dc, int32_t out_f64, void *workspace, int64_t workspace_bytes, void *stream);
 
+/* The same backward pass on bf16 / fp16 activations (csrc/nnc_cbspgrad_h16.hip): nnc_cbsp_dx_h16,
+ * nnc_cbsp_dc_h16, their workspace queries and their plans. */
+#include "nnc_cbspgrad_h16.h"
+
 /* ------------------------------------------------------------------------------------
  * The backward pass of nnc_cbpk_f32 from the same 2- or 4-bit packed form, the indices never unpacked and W never decoded
  * (csrc/nnc_cbpkgrad.hip).  The form, bits and k are nnc_cbpk_f32's; g = dL/dy float32[m, ncols].

@@ -220,7 +220,8 @@ class Trainer(ABC):
         return accuracies
 
     def fine_tune_compressed(self, train_dataset: LeNetDataset, test_dataset: LeNetDataset, epochs: int,
-                             learning_rate: float = 1e-3, sparse=False, packed=False, activation_dtype=None) -> List[float]:
+                             learning_rate: float = 1e-3, sparse=False, packed=False, activation_dtype=None,
+                             sparse_half_inputs=False) -> List[float]:
         """fine_tune_centroids' algorithm run on ``compressed.compress_network_trainable(..., sparse=sparse, packed=packed)``
         (both False: the network of ``compressed_network(trainable=True)``; sparse True or "auto": the bitmap-sparse trainable
         layers, for every quantized layer or where that form is smaller; packed True or "auto": the 2- or 4-bit packed trainable
@@ -235,24 +236,39 @@ class Trainer(ABC):
         only, else ValueError): the trainable network is built with half_inputs=True, its input is cast to the dtype and its output
         back to float32 before the loss, so the centres are tuned in the arithmetic the compressed network runs inference in.  The
         centres, their steps and the L2 term stay float32.  Every weighted layer then has to be a byte-form trainable layer: one that
-        passed through unquantized raises a ValueError that names it."""
+        passed through unquantized raises a ValueError that names it.
+        ``sparse_half_inputs=True`` (with ``activation_dtype`` and ``sparse`` True or "auto", packed=False; else ValueError): the
+        pruned layers train on the half activations from their bitmap-sparse form -- the network is
+        ``compress_network_trainable(..., sparse=sparse, sparse_half_inputs=True)``, in which the layers "auto" leaves in the byte
+        form take half inputs too; a weighted layer that is neither raises the ValueError above.  Without the keyword
+        ``activation_dtype`` with ``sparse`` stays a ValueError."""
         models = getattr(self, "quantized_models_by_layer", None)
         if not models:
             raise RuntimeError("fine_tune_compressed needs a quantized network: call quantize first")
         from .. import compressed
 
+        if sparse_half_inputs and (activation_dtype is None or sparse is False or packed is not False):
+            raise ValueError("sparse_half_inputs=True needs activation_dtype=torch.bfloat16 or torch.float16, sparse=True or 'auto' and "
+                             "packed=False: it trains the bitmap-sparse layers on half activations")
         if activation_dtype is None:
             net = compressed.compress_network_trainable(self.neural_network, models, sparse=sparse, packed=packed)
             return self._tune_centres(net, models, train_dataset, test_dataset, epochs, learning_rate)
         if activation_dtype not in (torch.bfloat16, torch.float16):
             raise ValueError(f"activation_dtype must be None, torch.bfloat16 or torch.float16, got {activation_dtype}")
-        if sparse is not False or packed is not False:
-            raise ValueError("activation_dtype needs sparse=False and packed=False: only the byte form trains on bfloat16 / float16 inputs")
-        net = compressed.compress_network_trainable(self.neural_network, models, half_inputs=True)
+        if not sparse_half_inputs and (sparse is not False or packed is not False):
+            raise ValueError("activation_dtype needs sparse=False and packed=False (the byte form), or sparse=True / 'auto' with "
+                             "sparse_half_inputs=True (the bitmap-sparse form): the packed forms do not train on bfloat16 / float16 inputs")
+        if sparse_half_inputs:
+            net = compressed.compress_network_trainable(self.neural_network, models, sparse=sparse, sparse_half_inputs=True)
+        else:
+            net = compressed.compress_network_trainable(self.neural_network, models, half_inputs=True)
+        half_layers = (compressed._TrainableCodebookLayer, compressed._TrainableSparseCodebookLayer)
         for name, layer in net.get_config().items():
-            if not isinstance(layer, compressed._TrainableCodebookLayer) and (hasattr(layer, "kernel") or next(layer.parameters(), None) is not None):
-                raise ValueError(f"activation_dtype={activation_dtype}: layer {name!r} ({type(layer).__name__}) is not a byte-form trainable "
-                                 "layer (its kernel passed through unquantized, or it has no half-precision backward pass)")
+            takes_half = isinstance(layer, half_layers) and layer.half_inputs
+            if not takes_half and (hasattr(layer, "kernel") or next(layer.parameters(), None) is not None):
+                raise ValueError(f"activation_dtype={activation_dtype}: layer {name!r} ({type(layer).__name__}) is not a byte-form or "
+                                 "bitmap-sparse trainable layer built with half_inputs (its kernel passed through unquantized, or it has "
+                                 "no half-precision backward pass)")
         return self._tune_centres(_HalfActivations(net, activation_dtype), models, train_dataset, test_dataset, epochs, learning_rate)
 
     def fine_tune_grouped(self, train_dataset: LeNetDataset, test_dataset: LeNetDataset, epochs: int, learning_rate: float = 1e-3,

@@ -31,7 +31,9 @@ of compressed layers stays in half.  ``centers`` and ``bias`` stay float32 buffe
 inside the kernel, the bias is added in float32): feed half inputs, leave the module float32.  A module cast with ``.half()`` /
 ``.bfloat16()`` turns those buffers into half tensors, and the layer then raises the dtype ``TypeError`` of ops.codebook_matmul.
 Half inputs are for the byte form unless a layer is built for them: the bitmap-sparse, the packed and every trainable layer raise
-``TypeError`` on them (the trainable byte layers train on them when built with ``half_inputs=True``), and
+``TypeError`` on them (the trainable byte layers train on them when built with ``half_inputs=True``; so do
+``TrainableSparseCompressedDense`` / ``TrainableSparseCompressedConv2D``, from their bitmap-sparse form, ops.sparse_codebook_linear ->
+csrc/nnc_cbspgrad_h16.hip, DESIGN.md section 24: ``compress_network_trainable(..., sparse=..., sparse_half_inputs=True)``), and
 ``torch.autocast`` is not registered.  ``SparseCompressedDense`` / ``SparseCompressedConv2D`` built with ``half_inputs=True``
 (``sparse_half_inputs=True`` in compress_network / load_network / Trainer.compressed_network) run on them too
 (ops.sparse_codebook_matmul -> nnc_cbsp_h16, csrc/nnc_cbsp_h16.hip), path and output dtype by the input's dtype.
@@ -478,19 +480,19 @@ class TrainableGroupedCompressedDense(_DenseHalf, _TrainableCentres):
 def _trainable(layer, weight_model, bias_model, dense_cls=None, conv_cls=None, half_inputs=False):
     """The trainable layer of ``layer``, the one Dense / Conv2D dispatch of the trainable forms: through from_dense / from_conv
     of ``dense_cls`` / ``conv_cls`` (the bitmap-sparse or the packed pair), or, without them, the byte classes built here
-    (``half_inputs``: theirs alone)."""
+    (``half_inputs``: the byte classes', and the bitmap-sparse pair's from_dense / from_conv)."""
     from .neural_networks.layers import Conv2D, Dense
 
     if dense_cls is None:   # the byte form takes its codes before it looks at the layer's type, as it always did
         labels, centers, bias, bias_codes = _trainable_codes(layer, weight_model, bias_model)
     if isinstance(layer, Dense):
         if dense_cls is not None:
-            return dense_cls.from_dense(layer, weight_model, bias_model)
+            return dense_cls.from_dense(layer, weight_model, bias_model, **(dict(half_inputs=True) if half_inputs else {}))
         kin, kout = layer.kernel.shape
         return TrainableCompressedDense(kin, kout, labels, centers, bias, bias_codes, layer.activation, half_inputs)
     if isinstance(layer, Conv2D):
         if conv_cls is not None:
-            return conv_cls.from_conv(layer, weight_model, bias_model)
+            return conv_cls.from_conv(layer, weight_model, bias_model, **(dict(half_inputs=True) if half_inputs else {}))
         h, cin, cout = _conv_shape(layer)
         return TrainableCompressedConv2D(h, cin, cout, layer.pad, _unfold_labels(h, cin, cout, labels), centers, bias, bias_codes,
                                          layer.activation, half_inputs)
@@ -627,17 +629,33 @@ class _TrainableSparseCodebookLayer(_SparseForm, _TrainableCodesLayer):
     """The indices in the bitmap-sparse form (the ``packed`` buffer, as _SparseCodebookLayer) with the centres, counts and bias of
     _TrainableCentres; the forward goes through ops.sparse_codebook_linear, whose backward forms dx and the centroid gradient
     from the packed form (csrc/nnc_cbspgrad.hip).  ``counts`` is taken from the labels before packing, so kernel_sq_sum() is the
-    dense trainable layer's bit for bit.  No kdim * ncols tensor stays resident."""
+    dense trainable layer's bit for bit.  No kdim * ncols tensor stays resident.  ``half_inputs=True`` lets the layer train on
+    bfloat16 / float16 inputs (ops.sparse_codebook_linear -> nnc_cbsp_h16 and csrc/nnc_cbspgrad_h16.hip): the
+    output and the input gradient have the input's dtype, centres and bias stay float32 parameters with float32 gradients.  Without
+    it a half input raises ``TypeError``, as it always did."""
+
+    def __init__(self, codes, labels: torch.Tensor, centers: torch.Tensor, bias: torch.Tensor | None = None, bias_codes=None, activation=None,
+                 half_inputs: bool = False):
+        super().__init__(codes, labels, centers, bias, bias_codes, activation)
+        self.half_inputs = bool(half_inputs)
+
+    def _matmul(self, x: torch.Tensor) -> torch.Tensor:
+        if not self.half_inputs and x.dtype in (torch.bfloat16, torch.float16):
+            raise TypeError(f"{type(self).__name__} takes float32 activations, got {x.dtype}: bfloat16 and float16 inputs train on the byte form "
+                            "(TrainableCompressedDense / TrainableCompressedConv2D built with half_inputs=True), and on a bitmap-sparse "
+                            "trainable layer only when it is built with half_inputs=True")
+        return super()._matmul(x)
 
 
 class TrainableSparseCompressedDense(_DenseHalf, _TrainableSparseCodebookLayer):
     """SparseCompressedDense with trainable centres (ops.sparse_codebook_linear)."""
 
     @classmethod
-    def from_dense(cls, dense, weight_model, bias_model=None, zero_symbol=None) -> "TrainableSparseCompressedDense":
-        codes = _trainable_codes(dense, weight_model, bias_model)
+    def from_dense(cls, dense, weight_model, bias_model=None, zero_symbol=None, half_inputs: bool = False) -> "TrainableSparseCompressedDense":
+        labels, centers, bias, bias_codes = _trainable_codes(dense, weight_model, bias_model)
         kin, kout = dense.kernel.shape
-        return cls.from_codes(kin, kout, *codes, dense.activation, zero_symbol)
+        return cls(ops.pack_sparse_codes(labels, kin, kout, centers.numel(), zero_symbol), labels, centers, bias, bias_codes, dense.activation,
+                   half_inputs)
 
     @classmethod
     def from_codes(cls, kdim, ncols, labels, centers, bias=None, bias_codes=None, activation=None,
@@ -650,15 +668,17 @@ class TrainableSparseCompressedConv2D(_Conv2DHalf, _TrainableSparseCodebookLayer
     ops.sparse_codebook_linear; autograd carries the patch gradients back through the unfold."""
 
     def __init__(self, kernel_size: int, cin: int, pad: int, codes: ops.SparseCodes, labels: torch.Tensor, centers: torch.Tensor, bias=None,
-                 bias_codes=None, activation=None):
+                 bias_codes=None, activation=None, half_inputs: bool = False):
         _check_conv_rows(codes, kernel_size, cin)
-        super().__init__(codes, labels, centers, bias, bias_codes, activation)
+        super().__init__(codes, labels, centers, bias, bias_codes, activation, half_inputs)
         self._set_conv(kernel_size, cin, pad)
 
     @classmethod
-    def from_conv(cls, conv, weight_model, bias_model=None, zero_symbol=None) -> "TrainableSparseCompressedConv2D":
+    def from_conv(cls, conv, weight_model, bias_model=None, zero_symbol=None, half_inputs: bool = False) -> "TrainableSparseCompressedConv2D":
         h, cin, cout = _conv_shape(conv)
-        return cls.from_codes(h, cin, cout, conv.pad, *_trainable_codes(conv, weight_model, bias_model), conv.activation, zero_symbol)
+        labels, centers, bias, bias_codes = _trainable_codes(conv, weight_model, bias_model)
+        codes = _unfold_then_pack(ops.pack_sparse_codes, h, cin, cout, labels, centers.numel(), zero_symbol)
+        return cls(h, cin, conv.pad, codes, labels, centers, bias, bias_codes, conv.activation, half_inputs)
 
     @classmethod
     def from_codes(cls, kernel_size, cin, cout, pad, labels, centers, bias=None, bias_codes=None, activation=None,
@@ -952,8 +972,9 @@ def _check_sparse_half_inputs(sparse_half_inputs, sparse, trainable=False):
     if not sparse_half_inputs:
         return
     if trainable:
-        raise ValueError("sparse_half_inputs=True is an option of the bitmap-sparse inference layers: it needs trainable=False (the "
-                         "trainable sparse layers take float32 activations)")
+        raise ValueError("sparse_half_inputs=True builds the bitmap-sparse inference layers here: it needs trainable=False "
+                         "(compress_network_trainable(..., sparse=..., sparse_half_inputs=True) builds the trainable sparse layers "
+                         "that train on bfloat16 / float16 inputs)")
     if sparse is False:
         raise ValueError("sparse_half_inputs=True needs sparse=True or sparse='auto': it builds the bitmap-sparse layers with "
                          "half_inputs=True (the byte form takes bfloat16 and float16 inputs as it is)")
@@ -989,7 +1010,8 @@ def compress_network(network: nn.Module, models_by_layer, sparse=False, trainabl
     return _compress_each(network, models_by_layer, lambda layer, wm, bm: _replace(layer, wm, bm, sparse, packed, sparse_half_inputs), grouped=what)
 
 
-def compress_network_trainable(network: nn.Module, models_by_layer, sparse=False, packed=False, half_inputs=False) -> nn.Module:
+def compress_network_trainable(network: nn.Module, models_by_layer, sparse=False, packed=False, half_inputs=False,
+                               sparse_half_inputs=False) -> nn.Module:
     """compress_network with the centres (and quantized biases' centres) as nn.Parameters.  ``sparse``: False
     (TrainableCompressedDense / TrainableCompressedConv2D, the layers of compress_network(..., trainable=True)), True
     (TrainableSparseCompressedDense / TrainableSparseCompressedConv2D: the indices in the bitmap-sparse form, skipping the most
@@ -998,14 +1020,23 @@ def compress_network_trainable(network: nn.Module, models_by_layer, sparse=False
     byte form) or "auto"; with ``sparse`` it decides per layer by resident bytes as the module's docstring tells.  All train the
     same function: the sparse and the packed layer's centroid gradient is the byte one's bit for bit (DESIGN.md sections 13, 15).
     ``half_inputs=True`` (sparse=False and packed=False only, else ValueError): the byte layers built with half_inputs=True, which
-    train on bfloat16 / float16 inputs."""
+    train on bfloat16 / float16 inputs.
+    ``sparse_half_inputs=True`` (``sparse`` True or "auto" and packed=False only, else ValueError): the bitmap-sparse layers are built
+    with half_inputs=True and train on bfloat16 / float16 inputs; the layers "auto" leaves in the byte form are
+    built with it too, so the whole network trains on half inputs, and what "auto" picks does not change."""
+    if sparse_half_inputs and (sparse is False or packed is not False):
+        raise ValueError("sparse_half_inputs=True needs sparse=True or sparse='auto', and packed=False: it builds the trainable "
+                         "bitmap-sparse layers with half_inputs=True (half_inputs=True builds the byte form's; the packed layers "
+                         "take float32 activations)")
     _check_sparse(sparse)
     _check_packed(packed, sparse)
     _check_half_inputs(half_inputs, sparse, packed)
+    half = bool(half_inputs or sparse_half_inputs)
 
     def make(layer, wm, bm):
-        byte, sp, pk = (lambda: _trainable(layer, wm, bm, half_inputs=half_inputs),
-                        lambda: _trainable(layer, wm, bm, TrainableSparseCompressedDense, TrainableSparseCompressedConv2D),
+        byte, sp, pk = (lambda: _trainable(layer, wm, bm, half_inputs=half),
+                        lambda: _trainable(layer, wm, bm, TrainableSparseCompressedDense, TrainableSparseCompressedConv2D,
+                                           half_inputs=bool(sparse_half_inputs)),
                         lambda: _trainable(layer, wm, bm, TrainablePackedCompressedDense, TrainablePackedCompressedConv2D))
         return _pick(byte, sp, sparse) if packed is False else _pick3(wm.cluster_centers_.size, byte, sp, pk, sparse, packed)
 

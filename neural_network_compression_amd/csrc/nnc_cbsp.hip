@@ -225,12 +225,14 @@ __global__ __launch_bounds__(256) void k_cbsp_tiled(const float *__restrict__ x,
 }
 
 // sum_i x[r, i]: one workgroup per row, each thread a strided sum, then a fixed tree
-__global__ __launch_bounds__(256) void k_cbsp_rowsum(const float *__restrict__ x, long long m, long long kdim, float *__restrict__ rs)
+// (XT = bf16_t / f16_t, the g of nnc_cbsp_dx_h16: every element widened, the same float32 sums)
+template <typename XT>
+__global__ __launch_bounds__(256) void k_cbsp_rowsum(const XT *__restrict__ x, long long m, long long kdim, float *__restrict__ rs)
 {
     __shared__ float part[256];
     for (long long r = blockIdx.x; r < m; r += gridDim.x) {
         float v = 0.0f;
-        for (long long i = threadIdx.x; i < kdim; i += 256) v += x[r * kdim + i];
+        for (long long i = threadIdx.x; i < kdim; i += 256) v += (float)x[r * kdim + i];
         part[threadIdx.x] = v;
         __syncthreads();
         for (int h = 128; h > 0; h >>= 1) {
@@ -243,9 +245,15 @@ __global__ __launch_bounds__(256) void k_cbsp_rowsum(const float *__restrict__ x
 }
 
 // ------------------------------------------------------------------ C ABI
-int cbsp_rowsum(const float *x, long long m, long long kdim, float *rs, hipStream_t s)
+int cbsp_rowsum_dt(const void *x, int dtype, long long m, long long kdim, float *rs, hipStream_t s)
 {
-    hipLaunchKernelGGL(k_cbsp_rowsum, dim3((unsigned)std::min<long long>(m, 65536)), dim3(256), 0, s, x, m, kdim, rs);
+    const dim3 grid((unsigned)std::min<long long>(m, 65536));
+    if (dtype == NNC_DT_F32)
+        hipLaunchKernelGGL(k_cbsp_rowsum<float>, grid, dim3(256), 0, s, reinterpret_cast<const float *>(x), m, kdim, rs);
+    else if (dtype == NNC_DT_BF16)
+        hipLaunchKernelGGL(k_cbsp_rowsum<bf16_t>, grid, dim3(256), 0, s, reinterpret_cast<const bf16_t *>(x), m, kdim, rs);
+    else
+        hipLaunchKernelGGL(k_cbsp_rowsum<f16_t>, grid, dim3(256), 0, s, reinterpret_cast<const f16_t *>(x), m, kdim, rs);
     LAUNCHCHK("k_cbsp_rowsum");
     return NNC_OK;
 }

@@ -78,8 +78,10 @@ __device__ __forceinline__ void tb_tile_fma_masked(const float *xs, const float 
     }
 }
 
-// rs[r] = sum_i x[r, i] for r < m in a fixed order (k_cbsp_rowsum, nnc_cbsp.hip), launched on `s`: NNC_OK or the launch error
-int cbsp_rowsum(const float *x, long long m, long long kdim, float *rs, hipStream_t s);
+// rs[r] = sum_i x[r, i] for r < m in a fixed order (k_cbsp_rowsum, nnc_cbsp.hip), launched on `s`: NNC_OK or the launch error.  x is
+// float32, or (cbsp_rowsum_dt, dtype NNC_DT_BF16 / NNC_DT_F16) widened element by element into the same float32 sums.
+int cbsp_rowsum_dt(const void *x, int dtype, long long m, long long kdim, float *rs, hipStream_t s);
+static inline int cbsp_rowsum(const float *x, long long m, long long kdim, float *rs, hipStream_t s) { return cbsp_rowsum_dt(x, NNC_DT_F32, m, kdim, rs, s); }
 
 #define SP_ROWS 64                // rows whose bitmap words one vector load brings to a wave of k_cbsp_stream
 

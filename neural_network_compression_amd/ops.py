@@ -31,7 +31,8 @@ def _require_f32_x(x, who: str):
     if isinstance(x, torch.Tensor) and x.dtype in (torch.bfloat16, torch.float16):
         raise TypeError(f"{who} takes float32 activations, got {x.dtype}: bfloat16 and float16 inputs run on the byte form "
                         "(ops.codebook_matmul and ops.codebook_linear; CompressedDense / CompressedConv2D, and their trainable "
-                        "layers built with half_inputs=True) and, forward only, on the bitmap-sparse form (ops.sparse_codebook_matmul)")
+                        "layers built with half_inputs=True) and on the bitmap-sparse form (ops.sparse_codebook_matmul and "
+                        "ops.sparse_codebook_linear; the sparse layers built with half_inputs=True)")
 
 
 def _stream(t: torch.Tensor) -> int:
@@ -850,13 +851,21 @@ def cbsp_h16_plan(dtype, m: int, kdim: int, ncols: int, label_bytes: int, k: int
     return _plan(nat.load().nnc_cbsp_h16_plan, nat.CBSP_H16_PLAN_FIELDS, _H16_DT[dtype], m, kdim, ncols, label_bytes, k, cus)
 
 
-def sparse_codebook_matmul_dx(g: torch.Tensor, codes: SparseCodes, centers: torch.Tensor) -> torch.Tensor:
+def sparse_codebook_matmul_dx(g: torch.Tensor, codes: SparseCodes, centers: torch.Tensor, out_dtype=None) -> torch.Tensor:
     """dx = g @ W^T from the bitmap-sparse form (include/nnc.h, nnc_cbsp_dx_f32): c_z * sum_o g[., o] + the stored weights'
     g[., o] * (centers[label] - c_z), the input gradient of sparse_codebook_matmul with its conventions (with centers[zero_symbol]
     == 0 a skipped weight forms no product).  g: float32 (..., ncols); centers: float32[codes.k].  Returns float32 (..., kdim).
-    Split partials are summed in a fixed order: the same call gives the same bits.  No host read."""
+    Split partials are summed in a fixed order: the same call gives the same bits.  No host read.
+    A bfloat16 or float16 g takes nnc_cbsp_dx_h16: centers stay float32 and are rounded to g's dtype as the
+    forward rounds them, the products are exact, the sums float32; the result has ``out_dtype``: None (g's dtype, the float32 value
+    rounded once) or torch.float32.  Up to 16 rows of g it is the float32 call on the widened g and the rounded centres bit for bit;
+    above, it is ops.codebook_matmul_dx on ``codes.to_dense()`` bit for bit, in which a skipped weight is an entry of W (an Inf in g at
+    a skipped position gives NaN).  A float32 g takes no ``out_dtype`` but None or torch.float32."""
     _require_cuda(centers, "centers", torch.float32)
-    _require_cuda(g, "g", torch.float32)
+    half = isinstance(g, torch.Tensor) and g.dtype in _H16_DT
+    _require_cuda(g, "g", g.dtype if half else torch.float32)
+    if out_dtype not in (None, torch.float32):
+        raise TypeError(f"out_dtype must be None or torch.float32, got {out_dtype}")
     if not isinstance(codes, SparseCodes):
         raise TypeError("codes must be a SparseCodes (ops.pack_sparse_codes)")
     lead, m = _rows(g, "g", codes.ncols)
@@ -865,6 +874,14 @@ def sparse_codebook_matmul_dx(g: torch.Tensor, codes: SparseCodes, centers: torc
     _one_device("g, codes and centers", g, codes.buf, centers)
     L = nat.load()
     kdim, ncols, lb = codes.kdim, codes.ncols, codes.label_bytes
+    if half:
+        dx_dtype = g.dtype if out_dtype is None else out_dtype
+        dx = torch.empty(lead + (kdim,), dtype=dx_dtype, device=g.device)
+        ws_bytes = int(L.nnc_cbsp_dx_h16_workspace_bytes(m, kdim, ncols, lb))
+        ws = _workspace(ws_bytes, g.device)
+        nat.check(L.nnc_cbsp_dx_h16(_ptr(g), _H16_DT[g.dtype], m, kdim, _ptr(codes.buf), codes.nbytes(), lb, ncols, codes.zero_symbol, codes.nnz,
+                                    _ptr(centers), centers.numel(), _ptr(dx), _H16_DT.get(dx_dtype, nat.DT_F32), _ptr(ws), ws_bytes, _stream(g)))
+        return dx
     dx = torch.empty(lead + (kdim,), dtype=torch.float32, device=g.device)
     ws_bytes = int(L.nnc_cbsp_dx_workspace_bytes(m, kdim, ncols, lb))
     ws = _workspace(ws_bytes, g.device)
@@ -877,9 +894,14 @@ def sparse_codebook_centroid_grad(x: torch.Tensor, g: torch.Tensor, codes: Spars
     """dc[j] = sum over the (i, o) whose label is j of (x^T g)[i, o], the skipped positions counted under zero_symbol
     (include/nnc.h, nnc_cbsp_dc_f32): bit for bit codebook_centroid_grad(x, g, codes.to_dense(), codes.k, ...), the indices
     never unpacked and dW never written.  x: float32 (..., kdim), g: float32 (..., ncols) with the same leading shape.  Returns
-    ``dtype`` (float64 or float32) [codes.k].  No host read."""
-    _require_cuda(x, "x", torch.float32)
-    _require_cuda(g, "g", torch.float32)
+    ``dtype`` (float64 or float32) [codes.k].  No host read.
+    x and g both bfloat16 or both float16 take nnc_cbsp_dc_h16: again codebook_centroid_grad on
+    ``codes.to_dense()`` and the same half inputs bit for bit; the result is the gradient with respect to the float32 centres."""
+    if isinstance(x, torch.Tensor) and isinstance(g, torch.Tensor) and x.dtype != g.dtype and (x.dtype in _H16_DT or g.dtype in _H16_DT):
+        raise TypeError(f"x and g must have one dtype, got {x.dtype} and {g.dtype}")
+    half = isinstance(x, torch.Tensor) and x.dtype in _H16_DT
+    _require_cuda(x, "x", x.dtype if half else torch.float32)
+    _require_cuda(g, "g", x.dtype if half else torch.float32)
     if not isinstance(codes, SparseCodes):
         raise TypeError("codes must be a SparseCodes (ops.pack_sparse_codes)")
     kdim, ncols, k, lb = codes.kdim, codes.ncols, codes.k, codes.label_bytes
@@ -887,6 +909,12 @@ def sparse_codebook_centroid_grad(x: torch.Tensor, g: torch.Tensor, codes: Spars
     _dc_args(x, lead, kdim, "x, g and codes", codes.buf, g, dtype)
     L = nat.load()
     dc = torch.empty(k, dtype=dtype, device=x.device)
+    if half:
+        ws_bytes = int(L.nnc_cbsp_dc_h16_workspace_bytes(m, kdim, ncols, lb, k))
+        ws = _workspace(ws_bytes, x.device)
+        nat.check(L.nnc_cbsp_dc_h16(_ptr(x), _ptr(g), _H16_DT[x.dtype], m, kdim, _ptr(codes.buf), codes.nbytes(), lb, ncols, codes.zero_symbol,
+                                    codes.nnz, k, _ptr(dc), 1 if dtype == torch.float64 else 0, _ptr(ws), ws_bytes, _stream(x)))
+        return dc
     ws_bytes = int(L.nnc_cbsp_dc_workspace_bytes(m, kdim, ncols, lb, k))
     ws = _workspace(ws_bytes, x.device)
     nat.check(L.nnc_cbsp_dc_f32(_ptr(x), _ptr(g), m, kdim, _ptr(codes.buf), codes.nbytes(), lb, ncols, codes.zero_symbol, codes.nnz, k, _ptr(dc),
@@ -906,15 +934,30 @@ def cbsp_dc_plan(m: int, kdim: int, ncols: int, label_bytes: int, k: int, cus: i
     return _plan(nat.load().nnc_cbsp_dc_plan, nat.CBSPDC_PLAN_FIELDS, m, kdim, ncols, label_bytes, k, cus)
 
 
+def cbsp_dx_h16_plan(dtype, m: int, kdim: int, ncols: int, label_bytes: int, k: int, cus: int) -> dict:
+    """Host: the plan nnc_cbsp_dx_h16 follows for g of ``dtype`` (torch.bfloat16 / torch.float16) on a device with ``cus`` compute
+    units (include/nnc_cbspgrad_h16.h), as a dict keyed by _native.CBSPDX_H16_PLAN_FIELDS.  No device needed."""
+    return _plan(nat.load().nnc_cbsp_dx_h16_plan, nat.CBSPDX_H16_PLAN_FIELDS, _h16_dt(dtype), m, kdim, ncols, label_bytes, k, cus)
+
+
+def cbsp_dc_h16_plan(dtype, m: int, kdim: int, ncols: int, label_bytes: int, k: int, cus: int) -> dict:
+    """Host: the plan nnc_cbsp_dc_h16 follows for x and g of ``dtype`` (include/nnc_cbspgrad_h16.h), as a dict keyed by
+    _native.CBSPDC_H16_PLAN_FIELDS.  No device needed."""
+    return _plan(nat.load().nnc_cbsp_dc_h16_plan, nat.CBSPDC_H16_PLAN_FIELDS, _h16_dt(dtype), m, kdim, ncols, label_bytes, k, cus)
+
+
 def sparse_codebook_linear(x: torch.Tensor, codes: SparseCodes, centers: torch.Tensor, bias: torch.Tensor | None = None,
                            relu: bool = False) -> torch.Tensor:
     """sparse_codebook_matmul with gradients for x, centers and bias (an autograd Function shaped like codebook_linear).  The
     forward is the same nnc_cbsp_f32 call (under no_grad the bits of sparse_codebook_matmul); the backward runs
     sparse_codebook_matmul_dx only if x needs a gradient and sparse_codebook_centroid_grad (float32) only if centers does, masks a
-    fused ReLU as torch does and sums the bias gradient over the rows.  The indices get no gradient.  No host read."""
+    fused ReLU as torch does and sums the bias gradient over the rows.  The indices get no gradient.  No host read.
+    A bfloat16 or float16 x: the forward is nnc_cbsp_h16 with x's dtype out, dx has x's dtype, the gradients
+    of the float32 centers and bias are float32.  A half ``centers`` or ``bias`` raises ``TypeError``."""
     if not isinstance(codes, SparseCodes):
         raise TypeError("codes must be a SparseCodes (ops.pack_sparse_codes)")
-    _require_f32_x(x, "sparse_codebook_linear")
+    if isinstance(x, torch.Tensor) and x.dtype in _H16_DT:
+        _require_centers_bias(centers, bias)
     return _CodebookLinear.apply(x, codes, centers, bias, bool(relu), codes.kdim, codes.ncols, sparse_codebook_matmul, sparse_codebook_matmul_dx,
                                  lambda x2, g2, cd, c: sparse_codebook_centroid_grad(x2, g2, cd, dtype=torch.float32))
 
