@@ -3786,6 +3786,7 @@ extern "C" int nnc_kmeans_fit(const float *x_iter, void *ws, const nnc_kmeans_pa
     bool first_launch = true;
     int nwin = 0, nrel_seen = status_out->n_relocated, nunp_seen = status_out->n_unproven; // (a call after a full-pass relocation carries on from the last status)
     int nip_seen = status_out->n_in_place;
+    int spec_seen = 0, spec_unseen = 0;
     if (!spec_ok) { nrel_seen = 0; nunp_seen = 0; nip_seen = 0; }
     double s_prev = -1.0, s_last = -1.0;
     int i_prev = 0, i_last = 0;
@@ -3803,10 +3804,17 @@ extern "C" int nnc_kmeans_fit(const float *x_iter, void *ws, const nnc_kmeans_pa
             }
         } else if (spec) {
             if ((rc = km_set_lds_attr())) return rc;
+            // The status of a batch of chains leaves one iteration before its end (the plain batches' way, below): the round trip and
+            // the enqueuing of the next batch -- 13-15 us -- run under the last iteration and its chain.  What that iteration does the
+            // host learns at the next look-in: its events through the running counts (nrel_seen, nip_seen, nunp_seen), a pause it has
+            // to handle behind a batch of launches that return at once.
+            const int carry = batch >= 2 ? batch - 2 : batch - 1;
+            spec_seen = spec_unseen + carry + 1; // iterations whose events this look-in counts: the last batch's tail, this one's head
+            spec_unseen = batch - 1 - carry;
             for (int i = 0; i < batch; i++) {
                 if ((rc = km_launch_accumulate(x_iter, w, &p, stream))) return rc;
                 if ((rc = km_launch_finalize(w, &p, FIN_FROM_SHARDS, 0, stream, nullptr, 0, false, x_iter))) return rc; // (small events: in place)
-                if ((rc = km_launch_spec_reloc(x_iter, w, &p, reloc_scratch_dev, stream, i == batch - 1 ? sl : nullptr, ticket))) return rc;
+                if ((rc = km_launch_spec_reloc(x_iter, w, &p, reloc_scratch_dev, stream, i == carry ? sl : nullptr, ticket))) return rc;
             }
         } else {
             // The status of a plain batch leaves two iterations before its end: the round trip to the host and the enqueuing of the
@@ -3814,7 +3822,8 @@ extern "C" int nnc_kmeans_fit(const float *x_iter, void *ws, const nnc_kmeans_pa
             // host has not seen yet costs nothing but launches: every kernel of an iteration looks at the status itself and returns
             // at once when the fit is over or has paused, so a batch enqueued behind a convergence the host learns of a look-in
             // later is a row of no-ops; the trajectory is the device's alone.
-            const int lag = (!one_launch && batch >= 4) ? KM_FIT_LAG : 0;
+            // (a batch shorter than three iterations sends it from as far ahead of its end as it reaches)
+            const int lag = one_launch ? 0 : std::min(KM_FIT_LAG, batch - 1);
             if ((rc = km_iterate_publish_(x_iter, ws, &p, batch, sl, ticket, stream, spec_ok, lag))) return rc;
         }
         if ((rc = km_wait_ticket(reinterpret_cast<volatile unsigned long long *>(sl + sizeof(nnc_kmeans_status)), ticket, S(stream)))) return rc;
@@ -3834,8 +3843,9 @@ extern "C" int nnc_kmeans_fit(const float *x_iter, void *ws, const nnc_kmeans_pa
         if (spec && !st.paused) {
             // a chain that finds nothing to do still costs its five launches (about as much as the round trip it would have saved):
             // carry on only while most iterations pause
-            // (events the iterations settle in their own launch do not need one)
-            if (2 * chain_events >= batch) { batch = 4; s_prev = s_last = -1.0; continue; }
+            // (events the iterations settle in their own launch do not need one; the count is an iteration old and the runs of events
+            // thin out, so "most" is a strict majority of the iterations it covers: an idle chain costs 16 us of launches)
+            if (2 * chain_events > spec_seen) { batch = 4; s_prev = s_last = -1.0; continue; }
             spec = false; // back to plain iterations, sized by the decay of the shift
             s_prev = s_last = -1.0;
         }
@@ -3858,7 +3868,8 @@ extern "C" int nnc_kmeans_fit(const float *x_iter, void *ws, const nnc_kmeans_pa
         if (s_prev > 0.0 && s_last > 0.0 && s_prev > s_last && p.tol > 0.0f) {
             const double rate = std::log(s_prev / s_last) / std::max(1, i_last - i_prev);
             const double left = s_last > (double)p.tol ? std::log(s_last / (double)p.tol) / rate : 0.0;
-            batch = (int)std::max(1.0, std::min((double)max_batch, std::floor(left * 0.9)));
+            // (never below the lag's reach: an iteration or two that return at once cost less than a look-in on an idle device, 11 us)
+            batch = (int)std::max((double)std::min(max_batch, KM_FIT_LAG + 1), std::min((double)max_batch, std::floor(left * 0.9)));
         }
     }
     if (n_windowed_out) *n_windowed_out = nwin;

@@ -21,7 +21,6 @@ int nnc_publish_bytes_(const void *src_dev, void *dst_host_mapped, int nbytes, v
 int nnc_wait_ticket_(void *host_ticket, uint64_t ticket, void *stream);
 int nnc_sort_pruned_bounded_flagged_(const float *x, int64_t n, int64_t n_neg, int64_t n_zero, float vmin, float vmax, float thr,
                                      float *sorted_out, void *ws, size_t ws_bytes, int32_t *flag_dev, void *stream); // in nnc_sort.hip
-
 // --------------------------------------------------------------------------------------
 // host arithmetic, NumPy's way
 // --------------------------------------------------------------------------------------
@@ -119,6 +118,25 @@ extern "C" int nnc_host_density_init(const float *xnew300, const double *cdf300,
     const int k = (1 << bits) + 1;
     std::vector<double> tmp((size_t)k);
     linspace_f64(0.0, 1.0, k, tmp.data());
+    // A cdf that never falls (what nnc_host_cdf gives, bar a last-place step down where two of its segments meet) needs no search
+    // over all 300 points per target -- 77 000 comparisons at K = 257, with the device waiting for the centres.  |c - t| is a
+    // monotone function of c on either side of t, rounding included, so it falls (not strictly) up to the last c < t and rises from
+    // the first c >= t on: the first closest point is that one, or the first of the points before it that are as close as the last.
+    bool rising = true;
+    for (int j = 1; j < 300; j++) rising = rising && cdf300[j - 1] <= cdf300[j]; // (false for a NaN as well)
+    for (int t = 0; rising && t < k; t++) {
+        const int hi = (int)(std::lower_bound(cdf300, cdf300 + 300, tmp[t]) - cdf300); // first c >= t
+        int best = hi;
+        if (hi > 0) {
+            const double dl = std::fabs(cdf300[hi - 1] - tmp[t]);
+            if (hi == 300 || dl <= std::fabs(cdf300[hi] - tmp[t])) {
+                best = hi - 1;
+                while (best > 0 && std::fabs(cdf300[best - 1] - tmp[t]) == dl) best--;
+            }
+        }
+        space_out[t] = xnew300[best];
+    }
+    if (rising) return NNC_OK;
     for (int t = 0; t < k; t++) {
         int best = 0;
         double bd = std::fabs(cdf300[0] - tmp[t]);
@@ -137,16 +155,16 @@ extern "C" int nnc_host_density_init(const float *xnew300, const double *cdf300,
 static size_t al(size_t b) { return (b + 255) & ~(size_t)255; }
 
 // A second stream (and two events) per host thread: the mean / variance passes of a long tensor run beside its sort.
-struct SideStream { int dev = -1; hipStream_t stream = nullptr; hipEvent_t fork = nullptr, join = nullptr; };
+struct SideStream { int dev = -1; hipStream_t stream = nullptr; hipEvent_t fork = nullptr, sorted = nullptr, join = nullptr; };
 static int side_stream(SideStream **out)
 {
     static thread_local SideStream side;
     int dev = 0;
     if (hipGetDevice(&dev) != hipSuccess) return nnc_set_error_(NNC_EHIP, "hipGetDevice failed");
     if (side.dev != dev) {
-        if (side.stream) { (void)hipStreamDestroy(side.stream); (void)hipEventDestroy(side.fork); (void)hipEventDestroy(side.join); side = SideStream(); }
+        if (side.stream) { (void)hipStreamDestroy(side.stream); (void)hipEventDestroy(side.fork); (void)hipEventDestroy(side.sorted); (void)hipEventDestroy(side.join); side = SideStream(); }
         if (hipStreamCreateWithFlags(&side.stream, hipStreamNonBlocking) != hipSuccess || hipEventCreateWithFlags(&side.fork, hipEventDisableTiming) != hipSuccess ||
-            hipEventCreateWithFlags(&side.join, hipEventDisableTiming) != hipSuccess)
+            hipEventCreateWithFlags(&side.sorted, hipEventDisableTiming) != hipSuccess || hipEventCreateWithFlags(&side.join, hipEventDisableTiming) != hipSuccess)
             return nnc_set_error_(NNC_EHIP, "could not create the second stream");
         side.dev = dev;
     }
@@ -291,16 +309,18 @@ extern "C" int nnc_compress_layer_f32(float *x, int64_t n, const nnc_layer_param
         res->n_iter = h_res[0]; res->stop = h_res[1]; res->n_relocations = h_res[2]; res->reloc_ties = h_res[3]; res->reloc_multi = h_res[4];
         res->arith = NNC_ARITH_REFERENCE;
     } else {
-        // ---- min / max and the sign counts are read first (the sort needs the counts on the host); mean and variance -- two passes
-        // and two single-wave folds, 90 us of mostly latency -- then run on a second stream beside the sort
+        // ---- mean and variance -- two passes and two single-wave folds, 90 us of mostly latency -- need only the pruned tensor: they
+        // go to a second stream before anything is read, and run under the first round trip and beside the sort.  min / max and the
+        // sign counts are read first (the sort needs the counts on the host).
         const int64_t nch = (n + 8191) / 8192; // NumPy's summation chunk
         float *c1 = reinterpret_cast<float *>(wb + L.stats_ws), *c2 = c1 + nch;
-        LCHK(read_back(out6, hb + 512, 64));
-        const float xmin = h_f[2], xmax = h_f[3], min_nz = h_f[4], max_nz = h_f[5];
-        const int64_t n_neg = h_signs[0], n_zero = h_signs[1];
         SideStream *side = nullptr;
         LCHK(side_stream(&side));
         LHIP(hipEventRecord(side->fork, s));
+        // (the read goes out first: five launches take the host longer than the threshold pass takes the device.  From out6[2] on:
+        // the first two floats are the second stream's to write while this read is under way)
+        const uint64_t t_mm = ++(*ticket_io);
+        LCHK(nnc_publish_bytes_(out6 + 2, hb + 512 + 8, 56, h_ticket, t_mm, stream));
         LHIP(hipStreamWaitEvent(side->stream, side->fork, 0));
         // From here on work is in flight on the second stream, writing into the caller's workspace: every way out of this scope --
         // an error return included -- first makes the caller's stream wait for it (and, on an error, waits itself), so that the
@@ -321,7 +341,9 @@ extern "C" int nnc_compress_layer_f32(float *x, int64_t n, const nnc_layer_param
         const float *h_mv = reinterpret_cast<const float *>(hb + 872);
         const uint64_t t_mv = ++(*ticket_io);
         LCHK(nnc_publish_bytes_(out6, hb + 872, 8, h_ticket_side, t_mv, side->stream));
-        LHIP(hipEventRecord(side->join, side->stream));
+        LCHK(nnc_wait_ticket_(h_ticket, t_mm, stream));
+        const float xmin = h_f[2], xmax = h_f[3], min_nz = h_f[4], max_nz = h_f[5];
+        const int64_t n_neg = h_signs[0], n_zero = h_signs[1];
         float *xs = reinterpret_cast<float *>(wb + L.sorted);
         int32_t *oob_d = reinterpret_cast<int32_t *>(wb + L.stats_out + 336); // the bounded sort's verdict: a weight outside the bounds it was given
         const int32_t *h_oob = reinterpret_cast<const int32_t *>(hb + 512 + 336);
@@ -332,15 +354,13 @@ extern "C" int nnc_compress_layer_f32(float *x, int64_t n, const nnc_layer_param
             bounded = true;
         } else if (4 * n_zero >= n) LCHK(nnc_sort_pruned_f32(x, n, n_neg, n_zero, xs, wb + L.sort_ws, L.sort_ws_bytes, stream));
         else LCHK(nnc_sort_f32(x, n, xs, wb + L.sort_ws, L.sort_ws_bytes, stream));
+        LHIP(hipEventRecord(side->sorted, s)); // (the prefix build on the second stream starts here)
         const bool with_prefix = (reinterpret_cast<uintptr_t>(xs) & 15) == 0;
         int64_t *ranks_d = reinterpret_cast<int64_t *>(wb + L.stats_out + 64);
         h_ranks = reinterpret_cast<int64_t *>(hb + 512 + 64);
         float steps[32];
         if (lp->mode == NNC_INIT_DENSITY) {
             if (!std::isfinite(min_nz)) { // no non-zero weight: the reference's numpy call raises; so does the caller's own path
-                LHIP(hipStreamWaitEvent(s, side->join, 0));
-                LHIP(hipStreamSynchronize(s));
-                side_join.joined = true;
                 if (lp->prune) { res->sigma = h_prune[0]; res->threshold = h_prune[1]; res->n_zeroed = h_nz[0]; }
                 res->status = NNC_LAYER_HOST;
                 return NNC_OK;
@@ -353,8 +373,6 @@ extern "C" int nnc_compress_layer_f32(float *x, int64_t n, const nnc_layer_param
         const uint64_t t_rk = ++(*ticket_io);
         LCHK(nnc_publish_bytes_(out6 + 2, hb + 512 + 8, 56 + 33 * 8 + 16, h_ticket, t_rk, stream));
         LCHK(nnc_wait_ticket_(h_ticket_side, t_mv, side->stream));
-        LHIP(hipStreamWaitEvent(s, side->join, 0));
-        side_join.joined = true;
         const float mean = h_mv[0], var = h_mv[1];
         if (!std::isfinite(mean) || !std::isfinite(var) || !std::isfinite(xmin) || !std::isfinite(xmax)) {
             // a NaN or an infinity in the tensor: KMeans.fit raises on such input, and so does the caller's own path (from the pruned tensor)
@@ -372,13 +390,17 @@ extern "C" int nnc_compress_layer_f32(float *x, int64_t n, const nnc_layer_param
         p.fix_shift = nnc_fix_shift(std::max(std::fabs((float)lo), std::fabs((float)hi)), n);
         p.grid_log2 = 0; p.replicas_log2 = -1; p.flags = lp->km_flags & (NNC_KM_TWO_LAUNCH | NNC_KM_LOOP);
         p.x_mean = mean; p.tol = tol; p.lo = lo; p.hi = hi;
-        // the prefix sums of the sorted copy: behind the sort on the caller's stream, while the ranks travel
+        // the prefix sums of the sorted copy: on the second stream, from the end of the sort, beside the rank kernel, the read of the
+        // ranks and the fit's first finalize step (which touches neither the table nor the vector); the caller's stream takes the
+        // second stream back in front of the first iteration
         // (the pointer is set before the fit is initialised: its first finalize step then knows that the iterations will not read the
         // cell table and leaves it to the labelling pass at the end -- one launch of k_cells less)
         if (with_prefix) {
-            LCHK(nnc_kmeans_prefix_build(xs, &p, reinterpret_cast<int64_t *>(wb + L.prefix), stream));
+            LHIP(hipStreamWaitEvent(side->stream, side->sorted, 0));
+            LCHK(nnc_kmeans_prefix_build(xs, &p, reinterpret_cast<int64_t *>(wb + L.prefix), side->stream));
             p.prefix_dev = reinterpret_cast<int64_t *>(wb + L.prefix);
         }
+        LHIP(hipEventRecord(side->join, side->stream));
         LCHK(nnc_wait_ticket_(h_ticket, t_rk, stream));
         if (bounded && *h_oob) {
             // a weight outside [min, -threshold] u {0} u [threshold, max] -- a NaN, the statistics pass ignores those: the compact-key
@@ -402,6 +424,8 @@ extern "C" int nnc_compress_layer_f32(float *x, int64_t n, const nnc_layer_param
         }
         std::memcpy(h_space, space, (size_t)k * 4);
         LCHK(nnc_kmeans_init(wb + L.km_ws, L.km_ws_bytes, &p, h_space, stream));
+        LHIP(hipStreamWaitEvent(s, side->join, 0)); // the prefix sums are there: nothing is left on the second stream
+        side_join.joined = true;
         // ---- the Lloyd loop
         nnc_kmeans_status st;
         std::memset(&st, 0, sizeof(st));
@@ -412,13 +436,17 @@ extern "C" int nnc_compress_layer_f32(float *x, int64_t n, const nnc_layer_param
             res->status = NNC_LAYER_HOST;
             return NNC_OK;
         }
-        // ---- labels + decoded values from the original order, index histogram, centres: one host read
+        // ---- index histogram and centres: one host read, which leaves in front of the labelling pass (neither needs the labels: the
+        // histogram comes from one counting pass over the sorted copy) -- the Huffman lengths are worked out, and the call returns,
+        // while that pass runs; labels + decoded values from the original order stay stream-ordered behind it
         // (one after the other: beside the labelling pass the index histogram's launches take bandwidth from it -- measured: the
         // labelling pass 43.6 -> 45.5 us for 15 us saved)
         LCHK(nnc_kmeans_get_centers(wb + L.km_ws, 0, 0, centers_d, stream));
-        LCHK(nnc_kmeans_assign(x, wb + L.km_ws, &p, 0, labels_out, res->label_bytes, lp->want_values ? values_out : nullptr, nullptr, nullptr, stream));
         LCHK(nnc_kmeans_label_counts(xs, wb + L.km_ws, &p, 0, counts_d, stream));
-        LCHK(read_back(back, hb + 1024, (int)al((size_t)k * 12)));
+        const uint64_t t_back = ++(*ticket_io);
+        LCHK(nnc_publish_bytes_(back, hb + 1024, (int)al((size_t)k * 12), h_ticket, t_back, stream));
+        LCHK(nnc_kmeans_assign(x, wb + L.km_ws, &p, 0, labels_out, res->label_bytes, lp->want_values ? values_out : nullptr, nullptr, nullptr, stream));
+        LCHK(nnc_wait_ticket_(h_ticket, t_back, stream));
         res->n_iter = st.iter; res->stop = st.done; res->n_relocations = nwin - st.n_reloc_null; res->n_reloc_windowed = nwin - st.n_reloc_null; // (events that moved a sample)
         res->reloc_ties = st.reloc_ties; res->reloc_multi = st.reloc_multi;
         res->arith = NNC_ARITH_FIXED;

@@ -453,6 +453,16 @@ static unsigned host_ord(float v)
 
 static size_t al256(size_t b) { return (b + 255) & ~(size_t)255; }
 
+// The sort's bookkeeping as launches of its own stream instead of the runtime's fill and copy commands: those two waited for whatever
+// another stream of the process had in flight (the layer call's mean / variance passes on its second stream, 90 us: the sort
+// began when they were through instead of beside them).  n16: 16-byte words.
+__global__ __launch_bounds__(256) void k_os_clear(uint4 *__restrict__ p, long long n16)
+{
+    const long long stride = (long long)gridDim.x * 256;
+    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n16; i += stride) p[i] = make_uint4(0u, 0u, 0u, 0u);
+}
+__global__ void k_os_verdict(const unsigned long long *__restrict__ ctrl, int32_t *__restrict__ flag) { *flag = reinterpret_cast<const int32_t *>(ctrl)[2]; }
+
 static int os_cus()
 {
     static int cus[64] = {0};
@@ -509,9 +519,11 @@ static int os_sort(const float *x, int64_t n, bool skip_zeros, int64_t n_neg, in
     unsigned *ghist = reinterpret_cast<unsigned *>(b); b += al256((size_t)(OS_MAXPASS + 1) * OS_MAXR * 4);
     unsigned long long *status = reinterpret_cast<unsigned long long *>(b);
     hipError_t e;
-    // ctrl + histograms + status words lie side by side: one memset
+    // ctrl + histograms + status words lie side by side (256-byte aligned, a multiple of 256 bytes): one launch clears them
     const size_t zero_bytes = al256(OS_CTRL_WORDS * 8) + al256((size_t)(OS_MAXPASS + 1) * OS_MAXR * 4) + os_status_bytes(n_keys);
-    if ((e = hipMemsetAsync(ctrl, 0, zero_bytes, s)) != hipSuccess) return nnc_set_error_(NNC_EHIP, hipGetErrorString(e));
+    const long long n16 = (long long)(zero_bytes / 16);
+    hipLaunchKernelGGL(k_os_clear, dim3((unsigned)std::min<long long>((n16 + 255) / 256, 1024)), dim3(256), 0, s, reinterpret_cast<uint4 *>(ctrl), n16);
+    if ((e = hipGetLastError()) != hipSuccess) return nnc_set_error_(NNC_EHIP, hipGetErrorString(e));
     // (the zeros of a pruned vector are written by the tiles of the last pass; with no key at all there is no pass)
     if (skip_zeros && n_zero > 0 && n_keys == 0 && (e = hipMemsetAsync(sorted_out + n_neg, 0, (size_t)n_zero * 4, s)) != hipSuccess) return nnc_set_error_(NNC_EHIP, hipGetErrorString(e));
     const OsPlan pl = os_plan(bits);
@@ -548,8 +560,10 @@ static int os_sort(const float *x, int64_t n, bool skip_zeros, int64_t n_neg, in
             dst = (dst == ka) ? kb : ka;
         }
     }
-    if (flag_dev && (e = hipMemcpyAsync(flag_dev, reinterpret_cast<unsigned char *>(ctrl) + 8, 4, hipMemcpyDeviceToDevice, s)) != hipSuccess)
-        return nnc_set_error_(NNC_EHIP, hipGetErrorString(e));
+    if (flag_dev) {
+        hipLaunchKernelGGL(k_os_verdict, dim3(1), dim3(1), 0, s, (const unsigned long long *)ctrl, flag_dev);
+        if ((e = hipGetLastError()) != hipSuccess) return nnc_set_error_(NNC_EHIP, hipGetErrorString(e));
+    }
     return NNC_OK;
 }
 
