@@ -1427,7 +1427,7 @@ __device__ int km_finalize_relocate(KmWs *__restrict__ ws, const float *__restri
         const int it = min(ws->st.iter, 63);
         rt[300 + 4 * it] = (unsigned long long)hd->n_empty; rt[301 + 4 * it] = (unsigned long long)hd->nch; rt[302 + 4 * it] = (unsigned long long)hd->slow; rt[303 + 4 * it] = (unsigned long long)ku;
     }
-    if (hd->slow || hd->nch > 1024) return 0; // (beyond that the candidate list would not fit anyway: kl_relocate checks)
+    if (hd->slow || hd->nch > 1024) return 0; // (that many undecided chunks are no small event: the chain takes it)
     if constexpr (MASS) {
         if (mass) {
             __shared__ KlMass mass_s;
@@ -1442,6 +1442,7 @@ __device__ int km_finalize_relocate(KmWs *__restrict__ ws, const float *__restri
 // WAVE (NT == 64 only): the body is run by ONE wave of a larger workgroup, so it may not use workgroup barriers; the
 // wave's own lock step (plus a compiler fence) orders its LDS traffic.  Returns true if new zones were left
 // (gcell / hcell / ku_out = {ku, cur} filled), i.e. the cell table has to be rebuilt.
+#define KM_MV_MAX 8 // centres placed by a relocation that the ordering puts in by rank (more of them: the counting rank)
 template <int NT, bool ONEWAVE, bool MASS = false>
 __device__ __forceinline__ bool km_finalize_body(KmWs *__restrict__ ws, int mode, int resume, int *gcell, int *hcell, int *ku_out, const bool lazy = false,
                                                  const float *__restrict__ reloc_xs = nullptr, const long long reloc_n = 0, const int k_hint = 0)
@@ -1468,6 +1469,7 @@ __device__ __forceinline__ bool km_finalize_body(KmWs *__restrict__ ws, int mode
     __shared__ float cu[NNC_KMAX];     // distinct sorted centre values
     __shared__ uint16_t sou[NNC_KMAX]; // their (lowest) original indices
     __shared__ double wave_a[NT / 64], wave_b[NT / 64];
+    __shared__ int mv_n, mv_pos[KM_MV_MAX], mv_idx[KM_MV_MAX], mv_rank[KM_MV_MAX]; // the centres a relocation has just placed (the ordering section)
 
     const int tid = threadIdx.x;
     unsigned long long *ftr = NNC_FIN_TRACE_PTR;
@@ -1475,6 +1477,7 @@ __device__ __forceinline__ bool km_finalize_body(KmWs *__restrict__ ws, int mode
     FSTAMP(0);
     if (tid == 0) ws->cells_pending = 0;
     if (!ONEWAVE && tid < 8) fin_votes[tid] = 0; // (the barrier below is in front of the first vote)
+    if (!ONEWAVE && tid == 0) mv_n = 0;
     // ---- ONE round of loads for everything this step reads.  On an otherwise idle chip every DEPENDENT global load costs about a
     // microsecond (the lines were written by the kernel in front, on other compute units: each first touch goes to the memory side),
     // and until round 4 there were four of them one behind the other here -- the queue length, behind a barrier the header, behind
@@ -1506,7 +1509,7 @@ __device__ __forceinline__ bool km_finalize_body(KmWs *__restrict__ ws, int mode
         pc[r] = 0; c_both[r][0] = c_both[r][1] = 0.0f; pm_both[r][0] = pm_both[r][1] = pmn_both[r][0] = pmn_both[r][1] = 0;
         const int j = tid + r * NT;
         if (j < kb) {
-            if (track) pc[r] = ws->prev_counts[j];
+            if (track || resume) pc[r] = ws->prev_counts[j]; // (a resumed step: the counts the paused step saw -- zero where a centre has been placed since)
             if (mode != FIN_INIT) {
                 c_both[r][0] = ws->c[0][j]; c_both[r][1] = ws->c[1][j];
                 pm_both[r][0] = ws->tab[0].perm[j]; pm_both[r][1] = ws->tab[1].perm[j];
@@ -1556,10 +1559,12 @@ __device__ __forceinline__ bool km_finalize_body(KmWs *__restrict__ ws, int mode
     // the previous centres and the order the E-step of this iteration used
     float cold_r[RR];
     int spa[RR], spb[RR];
+    unsigned was_empty = 0u; // bit r: cluster tid + r * NT had no sample before a relocation gave it one (behind a chain: as the paused step saw it)
 #pragma unroll
     for (int r = 0; r < RR; r++) {
         const int j = tid + r * NT;
         const bool in = mode != FIN_INIT && j < k;
+        if (resume && in && pc[r] == 0) was_empty |= 1u << r;
         cold_r[r] = in ? (cur ? c_both[r][1] : c_both[r][0]) : 0.0f;
         spa[r] = in ? (int)(cur ? pm_both[r][1] : pm_both[r][0]) : 0;
         spb[r] = (in && j + 1 < k) ? (int)(cur ? pmn_both[r][1] : pmn_both[r][0]) : 0;
@@ -1631,6 +1636,8 @@ __device__ __forceinline__ bool km_finalize_body(KmWs *__restrict__ ws, int mode
             // (the same conditions under which the chain enqueued "in case" goes ahead: km_spec_decide)
             // (n_empty counts THREADS with an empty cluster here: more of them than the selection takes clusters is a mass event)
             if (n_empty > 0 && (MASS || n_empty <= KL_RM_MAX) && !resume && reloc_xs && mode == FIN_FROM_SHARDS && lazy && !(st_iter >= 1 && same_counts_now)) {
+#pragma unroll
+                for (int r = 0; r < RR; r++) if (tid + r * NT < k && cnt_o[tid + r * NT] == 0) was_empty |= 1u << r; // (before the selection fills them)
                 __syncthreads(); // (the global stores of this step so far are out before the selection reads the workspace)
                 if (ftr && tid == 0) { ftr[20] = ftr[0]; ftr[21] = __builtin_amdgcn_s_memrealtime(); }
                 const KmTab *tabc = &ws->tab[cur];
@@ -1693,6 +1700,10 @@ __device__ __forceinline__ bool km_finalize_body(KmWs *__restrict__ ws, int mode
         }
         cur ^= 1;
         for (int j = tid; j < k; j += NT) ws->c[cur][j] = cnew[j];
+        if (!ONEWAVE && (resume || settled_event)) { // (sou is free until the distinct centres are listed: by original index, was this centre placed?)
+#pragma unroll
+            for (int r = 0; r < RR; r++) if (tid + r * NT < k) sou[tid + r * NT] = (uint16_t)(was_empty >> r & 1u);
+        }
         FIN_SYNC();
     } else {
         for (int j = tid; j < k; j += NT) cnew[j] = ws->c[cur][j];
@@ -1705,29 +1716,67 @@ __device__ __forceinline__ bool km_finalize_body(KmWs *__restrict__ ws, int mode
     // the centres move little per iteration: first try the previous permutation
     int still_sorted = 0;
     if (mode != FIN_INIT) {
-        int ok = 1;
+        // Behind a relocation (this step's own, or the chain's in front of a resumed step) the placed centres are far from their old
+        // places, the others have moved as little as ever.  Where at most KM_MV_MAX were placed they are taken out of the previous order,
+        // the rest is tested and repaired as usual, and the placed ones are put in by rank (a binary search each; equal values go by
+        // original index, as the counting rank breaks them).  More of them (the mass events), or a rest that does not settle: the
+        // counting rank below, as before.
+        const bool moved_far = resume || settled_event;
+        int m_ins = 0;
+        if (!ONEWAVE && moved_far) {
 #pragma unroll
-        for (int r = 0; r < RR; r++) {
-            const int p = tid + r * NT;
-            if (p < k) {
-                const int a = spa[r];
-                so[p] = (uint16_t)a;
-                cs[p] = cnew[a];
-                if (p + 1 < k) {
-                    const int b = spb[r];
-                    const float va = cnew[a], vb = cnew[b];
-                    ok &= (va < vb) || (va == vb && a < b);
+            for (int r = 0; r < RR; r++) { // where the placed centres stood
+                const int p = tid + r * NT;
+                if (p < k && sou[spa[r]]) {
+                    const int slot = atomicAdd(&mv_n, 1);
+                    if (slot < KM_MV_MAX) { mv_pos[slot] = p; mv_idx[slot] = spa[r]; }
+                }
+            }
+            FIN_SYNC();
+            const int m = mv_n;
+            if (m >= 1 && m <= KM_MV_MAX && m < k) m_ins = m;
+        }
+        const int kk = k - m_ins; // centres the test and the repair run over
+        int ok = 1;
+        if (m_ins) {
+#pragma unroll
+            for (int r = 0; r < RR; r++) {
+                const int p = tid + r * NT;
+                if (p < k && !sou[spa[r]]) {
+                    int before = 0;
+                    for (int i = 0; i < m_ins; i++) before += mv_pos[i] < p;
+                    so[p - before] = (uint16_t)spa[r];
+                    cs[p - before] = cnew[spa[r]];
+                }
+            }
+            FIN_SYNC();
+            for (int p = tid; p + 1 < kk; p += NT) {
+                const float va = cs[p], vb = cs[p + 1];
+                ok &= (va < vb) || (va == vb && so[p] < so[p + 1]);
+            }
+        } else {
+#pragma unroll
+            for (int r = 0; r < RR; r++) {
+                const int p = tid + r * NT;
+                if (p < k) {
+                    const int a = spa[r];
+                    so[p] = (uint16_t)a;
+                    cs[p] = cnew[a];
+                    if (p + 1 < k) {
+                        const int b = spb[r];
+                        const float va = cnew[a], vb = cnew[b];
+                        ok &= (va < vb) || (va == vb && a < b);
+                    }
                 }
             }
         }
         FSTAMP(12);
         still_sorted = FIN_AND(2, ok);
         // nearly sorted (two neighbours changed places): a few odd-even transposition passes repair it
-        // (not behind a relocation: a centre that was moved to a far sample is far from its old place, the passes would be for nothing)
-        const bool moved_far = resume || settled_event;
-        for (int pass = 0; pass < 3 && !still_sorted && !moved_far; pass++) {
+        // (not with the placed centres among them: one that was moved to a far sample is far from its old place, the passes would be for nothing)
+        for (int pass = 0; pass < 3 && !still_sorted && (!moved_far || m_ins); pass++) {
             for (int parity = 0; parity < 2; parity++) {
-                for (int p = 2 * tid + parity; p + 1 < k; p += 2 * NT) {
+                for (int p = 2 * tid + parity; p + 1 < kk; p += 2 * NT) {
                     const float va = cs[p], vb = cs[p + 1];
                     const uint16_t a = so[p], b = so[p + 1];
                     if (!((va < vb) || (va == vb && a < b))) { cs[p] = vb; cs[p + 1] = va; so[p] = b; so[p + 1] = a; }
@@ -1735,11 +1784,55 @@ __device__ __forceinline__ bool km_finalize_body(KmWs *__restrict__ ws, int mode
                 FIN_SYNC();
             }
             int ok2 = 1;
-            for (int p = tid; p + 1 < k; p += NT) {
+            for (int p = tid; p + 1 < kk; p += NT) {
                 const float va = cs[p], vb = cs[p + 1];
                 ok2 &= (va < vb) || (va == vb && so[p] < so[p + 1]);
             }
             still_sorted = FIN_AND(3 + pass, ok2);
+        }
+        if (m_ins && still_sorted) {
+            // the rest is in order: every placed centre finds its rank among them (thread i < m_ins), everything moves up by the
+            // number of placed centres in front of it
+            float tv[RR];
+            int to[RR];
+#pragma unroll
+            for (int r = 0; r < RR; r++) {
+                const int p = tid + r * NT;
+                tv[r] = 0.0f; to[r] = 0;
+                if (p < kk) { tv[r] = cs[p]; to[r] = so[p]; }
+            }
+            if (tid < m_ins) {
+                const int a = mv_idx[tid];
+                const float v = cnew[a];
+                int lo = 0, hi = kk; // (at most eleven steps: kk <= NNC_KMAX)
+                while (lo < hi) {
+                    const int mid = (lo + hi) >> 1;
+                    const float u = cs[mid];
+                    if ((u < v) || (u == v && (int)so[mid] < a)) lo = mid + 1; else hi = mid;
+                }
+                mv_rank[tid] = lo;
+            }
+            FIN_SYNC();
+#pragma unroll
+            for (int r = 0; r < RR; r++) {
+                const int p = tid + r * NT;
+                if (p < kk) {
+                    int before = 0;
+                    for (int i = 0; i < m_ins; i++) before += mv_rank[i] <= p;
+                    cs[p + before] = tv[r]; so[p + before] = (uint16_t)to[r];
+                }
+            }
+            if (tid < m_ins) {
+                const int a = mv_idx[tid];
+                const float v = cnew[a];
+                int at = mv_rank[tid];
+                for (int i = 0; i < m_ins; i++) {
+                    const int b = mv_idx[i];
+                    const float u = cnew[b];
+                    at += (u < v) || (u == v && b < a);
+                }
+                cs[at] = v; so[at] = (uint16_t)a;
+            }
         }
     }
     FSTAMP(8);

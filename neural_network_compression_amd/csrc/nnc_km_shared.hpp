@@ -63,7 +63,7 @@ struct KmWs {
     int32_t wide, kl_budget;
     unsigned long long kl_trace[24]; // diagnostics build: time per phase of k_lloyd (10 ns ticks), summed over the fit
     int32_t kl_stats[8]; // [0] iterations the loop ran, [1] its launches, [2] of them with centres changing places, [3] iterations handed over, [4] iterations the wide pair ran, [5] empty-cluster events the loop settled itself
-    unsigned long long kl_keys[KL_RKEYS]; // candidate keys of such an event (kl_relocate)
+    unsigned long long kl_keys[KL_RKEYS]; // (until the candidate keys of such an event stayed in registers: kept so that the workspace layout stands)
     int32_t bnd_phi[NNC_KMAX]; // per boundary j of the last k_bounds pass: the highest centre that could still win below U_j (the finalize step labels the undecided samples of an empty-cluster event with it, km_finalize_relocate)
     unsigned long long kl_mkeys[40960]; // candidate keys of a MASS empty-cluster event settled by the finalize step (kl_relocate_mass, KL_MKEYS)
     float kl_hL[2 * NNC_KMAX], kl_hR[2 * NNC_KMAX]; // per search (two a boundary: its ranks hint_a / hint_b): the threshold the rank was found for, the local density there (samples per unit)

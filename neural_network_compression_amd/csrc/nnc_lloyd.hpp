@@ -49,8 +49,7 @@ struct KlHead {
     // relocation of empty clusters inside the loop (kl_relocate)
     int r_cnt, r_bad, r_flat, r_pad1; // (r_flat: a run of equal values was settled as a whole in this iteration, kl_chunks)
     unsigned long long r_keys[8];     // the selected keys, descending (one more than there are empty clusters)
-    unsigned long long r_wkey[2][16]; // per wave: its largest remaining key ...
-    int r_widx[2][16];                // ... and the slot that holds it
+    unsigned long long r_wlist[16][8]; // per wave: the largest keys of its threads, descending (the first n_empty + 1 are in use)
     int r_empty[8], r_old[8];         // the empty clusters (ascending index); the clusters the selected samples leave
 };
 static_assert(sizeof(KlHead) % 16 == 0, "the arrays behind the header are 16-byte aligned");
@@ -689,11 +688,10 @@ __device__ __forceinline__ void kl_label(const float *__restrict__ xs, const flo
 // candidate of every end lies STRICTLY below the cut -- the proof k_reloc_select runs on its windows, with the loop's exact ranks in
 // place of windows that must be wide enough.  Returns 1 when the event is settled (sums, counts and ws->partials edited as
 // km_relocate_apply edits them, status counters updated: the caller goes on with the averages), 0 when it is not (more than
-// KL_RM_MAX empty clusters, too many candidates, no proof, every sample on its centre, a cluster that would be left empty): nothing
+// KL_RM_MAX empty clusters, no proof, every sample on its centre, a cluster that would be left empty): nothing
 // has changed then and the caller pauses as before -- the relocation chain behind the launch, or the host, takes the event.
 #define KL_RW 8      // candidates per end of a certain stretch: the lanes of a group
 #define KL_RM_MAX 7  // empty clusters one event may have here (KL_RM_MAX + 1 keys are selected)
-#define KL_RKPT 16   // candidate keys one thread holds during the selection
 #define KL_RPASS 10  // ends of certain stretches (groups of eight lanes) one thread takes: 2 ku <= KL_RPASS * NT / 8
 template <int NT>
 __device__ __forceinline__ int kl_relocate(const float *__restrict__ xs, const long long n, KmWs *__restrict__ ws, KlHead *hd, const KlArr &L,
@@ -703,48 +701,54 @@ __device__ __forceinline__ int kl_relocate(const float *__restrict__ xs, const l
     const int ku = hd->ku, m = hd->n_empty;
     if (tid == 0 && m > ws->kl_stats[7]) ws->kl_stats[7] = m; // (diagnostics: the largest event seen, why events were passed on)
     if (m < 1 || m > KL_RM_MAX || 2 * ku > KL_RPASS * (NT / 8) || hd->r_flat) { if (tid == 0) ws->kl_stats[6] |= 1; return 0; }
-    unsigned long long *keys = ws->kl_keys;
-    const int base = 2 * KL_RW * ku;
     unsigned long long *rtr = NNC_FIN_TRACE_PTR; // diagnostics: phase stamps
 #define KRSTAMP(i) do { if (rtr && tid == 0) rtr[30 + (i)] = __builtin_amdgcn_s_memrealtime(); } while (0)
     KRSTAMP(0);
-    if (tid == 0) { hd->r_cnt = 0; hd->r_bad = 0; }
+    if (tid == 0) hd->r_bad = 0;
+    if (tid <= KL_RM_MAX) hd->r_keys[tid] = 0ull;
     __syncthreads();
-    // ---- the ends of the certain stretches: group q = (centre p, lower / upper end), one sample a lane, the outermost first
-    unsigned inner = 0u; // the largest distance of an innermost candidate that has samples behind it
-    {   // (at most KL_RPASS groups a thread; all their samples are fetched before any is looked at)
-        long long rr[KL_RPASS];
-        float xq[KL_RPASS];
-        bool deep[KL_RPASS];
+    // ---- the candidate keys stay on the chip: a key that is not among the m + 1 largest of the keys one thread makes is not among
+    // the m + 1 largest of them all, so every thread keeps a list of its m + 1 largest (descending, 0 = none; equal keys are kept as
+    // often as they occur: they are interchangeable samples) and nothing else
+    unsigned long long top[KL_RM_MAX + 1];
 #pragma unroll
-        for (int u = 0; u < KL_RPASS; u++) {
-            const int q = g + u * (NT / 8);
-            rr[u] = -1; deep[u] = false;
-            if (q < 2 * ku) {
-                const int p = q >> 1, side = q & 1;
-                const long long lo_r = p > 0 ? L.B[p - 1] : 0, hi_r = p == ku - 1 ? n : L.A[p];
-                long long r = -1;
-                if (side == 0) { r = lo_r + gl; if (r >= hi_r) r = -1; }
-                else { r = hi_r - 1 - gl; if (r < lo_r + KL_RW) r = -1; } // (a short stretch: its first KL_RW samples are the lower end's)
-                rr[u] = r;
-                deep[u] = gl == KL_RW - 1 && hi_r - lo_r > 2 * KL_RW;
-            }
+    for (int i = 0; i <= KL_RM_MAX; i++) top[i] = 0ull;
+    auto keep = [&](unsigned long long key) { // (m is the workgroup's: the steps behind it are skipped by a scalar branch)
+#pragma unroll
+        for (int i = 0; i <= KL_RM_MAX; i++) {
+            if (i > m) break;
+            const bool up = key > top[i];
+            const unsigned long long hi = up ? key : top[i];
+            key = up ? top[i] : key;
+            top[i] = hi;
         }
+    };
+    // ---- the ends of the certain stretches: group q = (centre p, lower / upper end), one sample a lane, the outermost first (at most
+    // KL_RPASS groups a thread; all their samples are fetched before any is looked at)
+    float xe[KL_RPASS];
+    unsigned have = 0u, deep = 0u; // bit u: group u of this thread has a sample; ... is the innermost of an end with samples behind it
 #pragma unroll
-        for (int u = 0; u < KL_RPASS; u++) xq[u] = rr[u] >= 0 ? xs[rr[u]] : 0.0f;
+    for (int u = 0; u < KL_RPASS; u++) {
+        const int q = g + u * (NT / 8);
+        long long r = -1;
+        if (q < 2 * ku) {
+            const int p = q >> 1, side = q & 1;
+            const long long lo_r = p > 0 ? L.B[p - 1] : 0, hi_r = p == ku - 1 ? n : L.A[p];
+            if (side == 0) { r = lo_r + gl; if (r >= hi_r) r = -1; }
+            else { r = hi_r - 1 - gl; if (r < lo_r + KL_RW) r = -1; } // (a short stretch: its first KL_RW samples are the lower end's)
+            if (gl == KL_RW - 1 && hi_r - lo_r > 2 * KL_RW) deep |= 1u << u;
+        }
+        if (r >= 0) have |= 1u << u;
+        xe[u] = r >= 0 ? xs[r] : 0.0f;
+    }
+    unsigned inner = 0u; // the largest distance of an innermost candidate that has samples behind it
 #pragma unroll
-        for (int u = 0; u < KL_RPASS; u++) {
-            const int q = g + u * (NT / 8);
-            if (q < 2 * ku) {
-                unsigned long long key = 0ull;
-                if (rr[u] >= 0) {
-                    const float dd = (xq[u] - mean) - L.cs[q >> 1];
-                    const float dv = dd * dd;
-                    key = ((unsigned long long)__float_as_uint(dv) << 32) | (unsigned long long)f32_ordered_bits(xq[u]);
-                    if (deep[u]) inner = max(inner, __float_as_uint(dv));
-                }
-                keys[q * KL_RW + gl] = key;
-            }
+    for (int u = 0; u < KL_RPASS; u++) {
+        if (have >> u & 1u) {
+            const float dd = (xe[u] - mean) - L.cs[(g + u * (NT / 8)) >> 1];
+            const float dv = dd * dd;
+            keep(((unsigned long long)__float_as_uint(dv) << 32) | (unsigned long long)f32_ordered_bits(xe[u]));
+            if (deep >> u & 1u) inner = max(inner, __float_as_uint(dv));
         }
     }
     KRSTAMP(1); // certain ends
@@ -758,10 +762,6 @@ __device__ __forceinline__ int kl_relocate(const float *__restrict__ xs, const l
         const int cs_ = phi == j + 1 ? KL_CHUNK : KL_CHUNK_CROWD;
         const long long start = s + (long long)cs_ * (c - qfirst[j]);
         const long long end = start + cs_ < e ? start + cs_ : e;
-        // (one slot range a chunk: a counter bumped once per SAMPLE -- six thousand LDS atomics on one word -- was most of this phase)
-        int cbase = 0;
-        if (gl == 0) cbase = atomicAdd(&hd->r_cnt, (int)(end - start));
-        cbase = __shfl(cbase, (int)(threadIdx.x & 63 & ~7));
         for (long long r0 = start + gl; r0 < end; r0 += 64) { // eight loads a lane in flight
             float xq[8];
 #pragma unroll
@@ -780,55 +780,46 @@ __device__ __forceinline__ int kl_relocate(const float *__restrict__ xs, const l
                     }
                     const float dd = xc - L.cs[best];
                     const float dv = dd * dd;
-                    const int slot = base + cbase + (int)(r0 + 8 * u - start);
-                    if (slot < KL_RKEYS) keys[slot] = ((unsigned long long)__float_as_uint(dv) << 32) | (unsigned long long)f32_ordered_bits(xv);
+                    keep(((unsigned long long)__float_as_uint(dv) << 32) | (unsigned long long)f32_ordered_bits(xv));
                 }
             }
         }
     }
     KRSTAMP(2); // stretch samples (this wave)
-    __syncthreads();
-    KRSTAMP(3);
-    const int N = base + hd->r_cnt;
-    if (N > KL_RKPT * NT || N > KL_RKEYS) { if (tid == 0) ws->kl_stats[6] |= 2; return 0; }
-    // ---- the m + 1 largest keys: every thread holds its share in registers, one round of workgroup maximum per key
-    unsigned long long kr[KL_RKPT];
-#pragma unroll
-    for (int i = 0; i < KL_RKPT; i++) { const int slot = tid + i * NT; kr[i] = slot < N ? keys[slot] : 0ull; }
-    KRSTAMP(4); // keys back in registers
-    if (tid <= KL_RM_MAX) hd->r_keys[tid] = 0ull;
+    // ---- the m + 1 largest of the workgroup: two stages of one piece of code (one copy: it runs once or twice a call and every copy
+    // arrives cold).  A stage is m + 1 rounds inside a wave, no barrier: the maximum over the heads of the lanes' lists, which the
+    // first lane that holds it takes off its list.  Stage 0 runs on the threads' own lists and leaves every wave's m + 1 largest,
+    // descending, in hd->r_wlist; in stage 1 lane w of every wave holds wave w's list, and the wave's result is the workgroup's
 #pragma unroll 1
-    for (int r = 0; r <= m; r++) { // (one copy of the round's code, not eight: it runs once or twice a call and every copy arrives cold)
-        {
-            unsigned long long bk = 0ull;
-            int bi = -1;
-#pragma unroll
-            for (int i = 0; i < KL_RKPT; i++) if (kr[i] > bk) { bk = kr[i]; bi = tid + i * NT; }
-#pragma unroll
-            for (int off = 32; off >= 1; off >>= 1) { // equal keys are interchangeable samples: the lower slot goes first
-                const unsigned long long ok = (unsigned long long)__shfl_xor((long long)bk, off);
-                const int oi = __shfl_xor(bi, off);
-                if (ok > bk || (ok == bk && (unsigned)oi < (unsigned)bi)) { bk = ok; bi = oi; }
-            }
-            if (lane == 0) { hd->r_wkey[r & 1][wv] = bk; hd->r_widx[r & 1][wv] = bi; }
+    for (int stage = 0; stage < 2; stage++) {
+        if (stage == 1) {
             __syncthreads();
-            bk = 0ull; bi = -1;
 #pragma unroll
-            for (int w = 0; w < NT / 64; w++) {
-                const unsigned long long ok = hd->r_wkey[r & 1][w];
-                const int oi = hd->r_widx[r & 1][w];
-                if (ok > bk || (ok == bk && (unsigned)oi < (unsigned)bi)) { bk = ok; bi = oi; }
+            for (int i = 0; i <= KL_RM_MAX; i++) top[i] = (lane < NT / 64 && i <= m) ? hd->r_wlist[lane][i] : 0ull;
+        }
+#pragma unroll 1
+        for (int r = 0; r <= m; r++) {
+            unsigned long long bk = top[0];
+#pragma unroll
+            for (int off = 32; off >= 1; off >>= 1) {
+                const unsigned long long ok = (unsigned long long)__shfl_xor((long long)bk, off);
+                bk = ok > bk ? ok : bk;
             }
-            if (tid == 0) hd->r_keys[r] = bk;
-            if (bi >= 0 && (bi % NT) == tid) {
-                const int mine = bi / NT;
+            const unsigned long long holders = __ballot(top[0] == bk);
+            if (bk != 0ull && lane == __ffsll((long long)holders) - 1) { // equal keys are interchangeable samples: one holder gives its copy
 #pragma unroll
-                for (int i = 0; i < KL_RKPT; i++) if (i == mine) kr[i] = 0ull;
+                for (int i = 0; i < KL_RM_MAX; i++) top[i] = top[i + 1];
+                top[KL_RM_MAX] = 0ull;
+            }
+            if (lane == 0) {
+                if (stage == 0) hd->r_wlist[wv][r] = bk;
+                else if (wv == 0) hd->r_keys[r] = bk;
             }
         }
+        KRSTAMP(3 + stage); // the waves' lists; the workgroup's keys
     }
     __syncthreads();
-    KRSTAMP(5); // rounds
+    KRSTAMP(5); // barrier
     // ---- is the selection right, and is there anything to move?
     const unsigned long long kcut = hd->r_keys[m - 1], ktop = hd->r_keys[0];
     int bad = 0;

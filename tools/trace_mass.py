@@ -38,6 +38,6 @@ for o in range(16):
 if t[22] > 0:
     z = float(t[20])
     r = (t[30:38].astype(np.float64) - z) * 0.01
-    print(f"last event settled in place: selection starts {(t[21] - z) * 0.01:.1f}, certain ends {r[1]:.1f}, undecided samples {r[2]:.1f}, barrier {r[3]:.1f}, keys in registers {r[4]:.1f}, "
-          f"rounds {r[5]:.1f}, proof + empties {r[6]:.1f}, old clusters + edits {r[7]:.1f}, selection done {(t[22] - z) * 0.01:.1f}; shift / tolerance {(t[23] - z) * 0.01:.1f}, centres sorted {(t[24] - z) * 0.01:.1f}, "
+    print(f"last event settled in place: selection starts {(t[21] - z) * 0.01:.1f}, certain ends {r[1]:.1f}, undecided samples {r[2]:.1f}, waves' lists {r[3]:.1f}, workgroup's keys {r[4]:.1f}, "
+          f"barrier {r[5]:.1f}, proof + empties {r[6]:.1f}, old clusters + edits {r[7]:.1f}, selection done {(t[22] - z) * 0.01:.1f}; shift / tolerance {(t[23] - z) * 0.01:.1f}, centres sorted {(t[24] - z) * 0.01:.1f}, "
           f"zones {(t[25] - z) * 0.01:.1f}, end {(t[26] - z) * 0.01:.1f} us")
