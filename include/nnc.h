@@ -1048,6 +1048,10 @@ int nnc_cbpk_dc_f32(const float *x, const float *g, int64_t m, int64_t kdim, con
  * DESIGN.md section 20): six entry points, declared in a header of their own. */
 #include "nnc_cbpkgrad_grouped.h"
 
+/* The ungrouped packed layer on bf16 / fp16 activations, forward and backward (csrc/nnc_cbpk_h16.hip):
+ * nnc_cbpk_h16, nnc_cbpk_dx_h16, nnc_cbpk_dc_h16, their workspace queries and plans, declared in a header of their own. */
+#include "nnc_cbpk_h16.h"
+
 /* ------------------------------------------------------------------------------------
  * Multi-GPU: the vector is sharded across one process per GPU (contiguous shards starting on multiples of
  * NNC_CHUNK elements); the exchange per Lloyd iteration is one all-reduce (SUM) of the 2K int64 sums / counts over

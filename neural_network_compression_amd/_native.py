@@ -71,6 +71,11 @@ CBSPDC_PLAN_FIELDS = ("path", "mt", "segs", "copies", "splits", "rps", "lds", "c
 CBSPGRAD_H16_PLAN_LEN = 12   # nnc_cbsp_dx_h16_plan / nnc_cbsp_dc_h16_plan (include/nnc_cbspgrad_h16.h): the float32 sparse fields, then the dtype
 CBSPDX_H16_PLAN_FIELDS = CBSPDX_PLAN_FIELDS + ("dtype",)
 CBSPDC_H16_PLAN_FIELDS = CBSPDC_PLAN_FIELDS + ("dtype",)
+CBPK_H16_PLAN_LEN = 15   # nnc_cbpk_h16_plan (include/nnc_cbpk_h16.h): the float32 packed fields, then the dtype; path is CBMM_MFMA for m > 16
+CBPK_H16_PLAN_FIELDS = CBPK_PLAN_FIELDS + ("dtype",)
+CBPKGRAD_H16_PLAN_LEN = 13   # nnc_cbpk_dx_h16_plan / nnc_cbpk_dc_h16_plan: the float32 packed fields, then the dtype
+CBPKDX_H16_PLAN_FIELDS = CBPKDX_PLAN_FIELDS + ("dtype",)
+CBPKDC_H16_PLAN_FIELDS = CBPKDC_PLAN_FIELDS + ("dtype",)
 
 
 class NativeLibraryError(RuntimeError):
@@ -328,6 +333,21 @@ SPARSE_H16_GRAD_SIGNATURES = {
                                 c_void_p]),
 }
 
+# name -> (restype, argtypes); every symbol include/nnc_cbpk_h16.h declares (the 2- / 4-bit packed layer on bf16 / fp16 activations, forward
+# and backward, again a header of its own that nnc.h includes).  Required and bound by load() as SIGNATURES are.
+PACKED_H16_SIGNATURES = {
+    "nnc_cbpk_h16_workspace_bytes": (c_i64, [c_i64, c_i64, c_i64, c_int]),
+    "nnc_cbpk_h16_plan": (c_int, [c_int, c_i64, c_i64, c_i64, c_int, c_i32, c_i32, ctypes.POINTER(c_i64)]),
+    "nnc_cbpk_h16": (c_int, [c_void_p, c_int, c_i64, c_i64, c_void_p, c_i64, c_int, c_i64, c_void_p, c_i32, c_void_p, c_i32, c_void_p, c_int, c_void_p, c_i64,
+                             c_void_p]),
+    "nnc_cbpk_dx_h16_workspace_bytes": (c_i64, [c_i64, c_i64, c_i64, c_int]),
+    "nnc_cbpk_dx_h16_plan": (c_int, [c_int, c_i64, c_i64, c_i64, c_int, c_i32, c_i32, ctypes.POINTER(c_i64)]),
+    "nnc_cbpk_dx_h16": (c_int, [c_void_p, c_int, c_i64, c_i64, c_void_p, c_i64, c_int, c_i64, c_void_p, c_i32, c_void_p, c_int, c_void_p, c_i64, c_void_p]),
+    "nnc_cbpk_dc_h16_workspace_bytes": (c_i64, [c_i64, c_i64, c_i64, c_int, c_i32]),
+    "nnc_cbpk_dc_h16_plan": (c_int, [c_int, c_i64, c_i64, c_i64, c_int, c_i32, c_i32, ctypes.POINTER(c_i64)]),
+    "nnc_cbpk_dc_h16": (c_int, [c_void_p, c_void_p, c_int, c_i64, c_i64, c_void_p, c_i64, c_int, c_i64, c_i32, c_void_p, c_i32, c_void_p, c_i64, c_void_p]),
+}
+
 # exported only by the diagnostics build (NNC_DIAG=1: libnnc_hip_diag.so, see build.py); bound when present
 DIAG_SIGNATURES = {
     "nnc_debug_set_ablation": (c_int, [c_int]),
@@ -360,7 +380,7 @@ def load():
         L = ctypes.CDLL(path)
     except OSError as e:  # pragma: no cover - depends on the machine
         raise NativeLibraryError(f"cannot load {path}: {e}; there is no CPU fallback") from e
-    for name, (res, args) in list(SIGNATURES.items()) + list(GROUPED_GRAD_SIGNATURES.items()) + list(H16_GRAD_SIGNATURES.items()) + list(GROUPED_PACKED_GRAD_SIGNATURES.items()) + list(SPARSE_H16_SIGNATURES.items()) + list(SPARSE_H16_GRAD_SIGNATURES.items()):
+    for name, (res, args) in list(SIGNATURES.items()) + list(GROUPED_GRAD_SIGNATURES.items()) + list(H16_GRAD_SIGNATURES.items()) + list(GROUPED_PACKED_GRAD_SIGNATURES.items()) + list(SPARSE_H16_SIGNATURES.items()) + list(SPARSE_H16_GRAD_SIGNATURES.items()) + list(PACKED_H16_SIGNATURES.items()):
         try:
             fn = getattr(L, name)
         except AttributeError as e:

@@ -221,7 +221,7 @@ class Trainer(ABC):
 
     def fine_tune_compressed(self, train_dataset: LeNetDataset, test_dataset: LeNetDataset, epochs: int,
                              learning_rate: float = 1e-3, sparse=False, packed=False, activation_dtype=None,
-                             sparse_half_inputs=False) -> List[float]:
+                             sparse_half_inputs=False, packed_half_inputs=False) -> List[float]:
         """fine_tune_centroids' algorithm run on ``compressed.compress_network_trainable(..., sparse=sparse, packed=packed)``
         (both False: the network of ``compressed_network(trainable=True)``; sparse True or "auto": the bitmap-sparse trainable
         layers, for every quantized layer or where that form is smaller; packed True or "auto": the 2- or 4-bit packed trainable
@@ -241,13 +241,21 @@ class Trainer(ABC):
         pruned layers train on the half activations from their bitmap-sparse form -- the network is
         ``compress_network_trainable(..., sparse=sparse, sparse_half_inputs=True)``, in which the layers "auto" leaves in the byte
         form take half inputs too; a weighted layer that is neither raises the ValueError above.  Without the keyword
-        ``activation_dtype`` with ``sparse`` stays a ValueError."""
+        ``activation_dtype`` with ``sparse`` stays a ValueError.
+        ``packed_half_inputs=True`` (with ``activation_dtype`` and ``packed`` True or "auto"; with ``sparse`` other than False also
+        sparse_half_inputs=True; else ValueError): the layers of at most 16 centres train on the half activations from their 2- or 4-bit
+        packed form -- the network is ``compress_network_trainable(..., packed=packed, packed_half_inputs=True)``,
+        in which the layers left in the byte form take half inputs too.  Without the keyword ``activation_dtype`` with ``packed``
+        stays a ValueError."""
         models = getattr(self, "quantized_models_by_layer", None)
         if not models:
             raise RuntimeError("fine_tune_compressed needs a quantized network: call quantize first")
         from .. import compressed
 
-        if sparse_half_inputs and (activation_dtype is None or sparse is False or packed is not False):
+        if packed_half_inputs and (activation_dtype is None or packed is False):
+            raise ValueError("packed_half_inputs=True needs activation_dtype=torch.bfloat16 or torch.float16 and packed=True or 'auto': "
+                             "it trains the 2- / 4-bit packed layers on half activations")
+        if sparse_half_inputs and (activation_dtype is None or sparse is False or (packed is not False and not packed_half_inputs)):
             raise ValueError("sparse_half_inputs=True needs activation_dtype=torch.bfloat16 or torch.float16, sparse=True or 'auto' and "
                              "packed=False: it trains the bitmap-sparse layers on half activations")
         if activation_dtype is None:
@@ -255,19 +263,23 @@ class Trainer(ABC):
             return self._tune_centres(net, models, train_dataset, test_dataset, epochs, learning_rate)
         if activation_dtype not in (torch.bfloat16, torch.float16):
             raise ValueError(f"activation_dtype must be None, torch.bfloat16 or torch.float16, got {activation_dtype}")
-        if not sparse_half_inputs and (sparse is not False or packed is not False):
+        if not sparse_half_inputs and not packed_half_inputs and (sparse is not False or packed is not False):
             raise ValueError("activation_dtype needs sparse=False and packed=False (the byte form), or sparse=True / 'auto' with "
-                             "sparse_half_inputs=True (the bitmap-sparse form): the packed forms do not train on bfloat16 / float16 inputs")
-        if sparse_half_inputs:
+                             "sparse_half_inputs=True (the bitmap-sparse form): the packed forms do not train on bfloat16 / float16 inputs "
+                             "unless packed=True / 'auto' comes with packed_half_inputs=True")
+        if packed_half_inputs:   # (sparse without sparse_half_inputs: compress_network_trainable's ValueError, which names it)
+            net = compressed.compress_network_trainable(self.neural_network, models, sparse=sparse, packed=packed,
+                                                        sparse_half_inputs=sparse_half_inputs, packed_half_inputs=True)
+        elif sparse_half_inputs:
             net = compressed.compress_network_trainable(self.neural_network, models, sparse=sparse, sparse_half_inputs=True)
         else:
             net = compressed.compress_network_trainable(self.neural_network, models, half_inputs=True)
-        half_layers = (compressed._TrainableCodebookLayer, compressed._TrainableSparseCodebookLayer)
+        half_layers = (compressed._TrainableCodebookLayer, compressed._TrainableSparseCodebookLayer, compressed._TrainablePackedCodebookLayer)
         for name, layer in net.get_config().items():
             takes_half = isinstance(layer, half_layers) and layer.half_inputs
             if not takes_half and (hasattr(layer, "kernel") or next(layer.parameters(), None) is not None):
-                raise ValueError(f"activation_dtype={activation_dtype}: layer {name!r} ({type(layer).__name__}) is not a byte-form or "
-                                 "bitmap-sparse trainable layer built with half_inputs (its kernel passed through unquantized, or it has "
+                raise ValueError(f"activation_dtype={activation_dtype}: layer {name!r} ({type(layer).__name__}) is not a byte-form, "
+                                 "bitmap-sparse or packed trainable layer built with half_inputs (its kernel passed through unquantized, or it has "
                                  "no half-precision backward pass)")
         return self._tune_centres(_HalfActivations(net, activation_dtype), models, train_dataset, test_dataset, epochs, learning_rate)
 
@@ -343,7 +355,8 @@ class Trainer(ABC):
                 layer.set_weights(tensors)
         return accuracies
 
-    def compressed_network(self, sparse=False, trainable=False, packed=False, half_inputs=False, sparse_half_inputs=False) -> torch.nn.Module:
+    def compressed_network(self, sparse=False, trainable=False, packed=False, half_inputs=False, sparse_half_inputs=False,
+                           packed_half_inputs=False) -> torch.nn.Module:
         """A copy of the network whose quantized layers run from their codebooks and centroid indices (compressed.py; the
         float32 weights are never rebuilt), with the centres as they stand (after fine_tune_centroids, the tuned ones).
         ``sparse``: False, True (the indices in the bitmap-sparse form) or "auto" (per layer, the smaller form).
@@ -353,6 +366,7 @@ class Trainer(ABC):
         section 12); fine_tune_compressed(..., sparse=..., packed=...) trains the other two forms.  ``half_inputs=True`` with it:
         those layers train on bfloat16 / float16 inputs too.  ``sparse_half_inputs=True`` (with ``sparse`` True or
         "auto", not trainable): the bitmap-sparse layers run on bfloat16 / float16 inputs.
+        ``packed_half_inputs=True`` (with ``packed`` True or "auto", not trainable): the packed layers run on them.
         A layer quantized with ``group_rows`` becomes a GroupedCompressedDense; with it any of the three options raises
         NotImplementedError with the layer's name (compressed.pack_grouped_layers packs the grouped layers of the result, DESIGN.md
         section 18)."""
@@ -362,7 +376,7 @@ class Trainer(ABC):
         from .. import compressed
 
         return compressed.compress_network(self.neural_network, models, sparse=sparse, trainable=trainable, packed=packed, half_inputs=half_inputs,
-                                            sparse_half_inputs=sparse_half_inputs)
+                                            sparse_half_inputs=sparse_half_inputs, packed_half_inputs=packed_half_inputs)
 
     def _discard_quantization(self) -> None:
         """The weights are about to change: the centroid indices of ``quantize`` no longer describe them, so nothing may store, run

@@ -37,6 +37,9 @@ csrc/nnc_cbspgrad_h16.hip, DESIGN.md section 24: ``compress_network_trainable(..
 ``torch.autocast`` is not registered.  ``SparseCompressedDense`` / ``SparseCompressedConv2D`` built with ``half_inputs=True``
 (``sparse_half_inputs=True`` in compress_network / load_network / Trainer.compressed_network) run on them too
 (ops.sparse_codebook_matmul -> nnc_cbsp_h16, csrc/nnc_cbsp_h16.hip), path and output dtype by the input's dtype.
+The four packed layers built with ``half_inputs=True`` (``packed_half_inputs=True`` in compress_network / load_network /
+Trainer.compressed_network / compress_network_trainable) run and train on them as well (ops.packed_codebook_matmul /
+ops.packed_codebook_linear -> csrc/nnc_cbpk_h16.hip); the grouped layers' backward passes stay float32.
 
 ``GroupedCompressedDense`` runs a Dense layer whose kernel has one codebook per block of ``group_rows`` input rows
 (utility.get_quantized_weight_grouped, Trainer.quantize(..., group_rows=); ops.grouped_codebook_matmul, csrc/nnc_cbmm_grouped.hip,
@@ -480,7 +483,7 @@ class TrainableGroupedCompressedDense(_DenseHalf, _TrainableCentres):
 def _trainable(layer, weight_model, bias_model, dense_cls=None, conv_cls=None, half_inputs=False):
     """The trainable layer of ``layer``, the one Dense / Conv2D dispatch of the trainable forms: through from_dense / from_conv
     of ``dense_cls`` / ``conv_cls`` (the bitmap-sparse or the packed pair), or, without them, the byte classes built here
-    (``half_inputs``: the byte classes', and the bitmap-sparse pair's from_dense / from_conv)."""
+    (``half_inputs``: the byte classes', and the bitmap-sparse and the packed pair's from_dense / from_conv)."""
     from .neural_networks.layers import Conv2D, Dense
 
     if dense_cls is None:   # the byte form takes its codes before it looks at the layer's type, as it always did
@@ -690,21 +693,32 @@ class TrainableSparseCompressedConv2D(_Conv2DHalf, _TrainableSparseCodebookLayer
 
 class _PackedCodebookLayer(_PackedForm, _CodesLayer):
     """The indices in the 2- or 4-bit packed form (ops.PackedCodes: its buffer is the module's ``packed`` buffer), centers
-    float32[K <= 2^bits], bias float32[ncols] or None.  No kdim * ncols tensor stays resident."""
+    float32[K <= 2^bits], bias float32[ncols] or None.  No kdim * ncols tensor stays resident.  ``half_inputs=True`` lets the layer run
+    on bfloat16 / float16 inputs (ops.packed_codebook_matmul -> nnc_cbpk_h16): the path is chosen by the input's
+    dtype and the output has that dtype; centers and bias stay float32.  Without it a half input raises TypeError, as it always did."""
+
+    def __init__(self, codes, centers: torch.Tensor, bias: torch.Tensor | None, activation=None, half_inputs: bool = False):
+        super().__init__(codes, centers, bias, activation)
+        self.half_inputs = bool(half_inputs)
+
+    def _matmul(self, x: torch.Tensor) -> torch.Tensor:
+        if not self.half_inputs:
+            ops._require_f32_x(x, type(self).__name__)
+        return super()._matmul(x)
 
 
 class PackedCompressedDense(_DenseHalf, _PackedCodebookLayer):
     """Dense run from its codebook and the 2- or 4-bit packed form of its (in, out) indices."""
 
     @classmethod
-    def from_dense(cls, dense, weight_model, bias_model=None, bits=None) -> "PackedCompressedDense":
+    def from_dense(cls, dense, weight_model, bias_model=None, bits=None, half_inputs: bool = False) -> "PackedCompressedDense":
         codes = _inference_codes(dense, weight_model, bias_model)
         kin, kout = dense.kernel.shape
-        return cls.from_codes(kin, kout, *codes, dense.activation, bits)
+        return cls.from_codes(kin, kout, *codes, dense.activation, bits, half_inputs)
 
     @classmethod
-    def from_codes(cls, kdim, ncols, labels, centers, bias, activation, bits=None) -> "PackedCompressedDense":
-        return cls(ops.pack_codes(labels, kdim, ncols, centers.numel(), bits), centers, bias, activation)
+    def from_codes(cls, kdim, ncols, labels, centers, bias, activation, bits=None, half_inputs: bool = False) -> "PackedCompressedDense":
+        return cls(ops.pack_codes(labels, kdim, ncols, centers.numel(), bits), centers, bias, activation, half_inputs)
 
 
 class PackedCompressedConv2D(_Conv2DHalf, _PackedCodebookLayer):
@@ -712,44 +726,58 @@ class PackedCompressedConv2D(_Conv2DHalf, _PackedCodebookLayer):
     unfold order (keras_rows_for_unfold); patch chunking and the empty batch as CompressedConv2D."""
 
     def __init__(self, kernel_size: int, cin: int, pad: int, codes: ops.PackedCodes, centers: torch.Tensor, bias: torch.Tensor | None,
-                 activation=None):
+                 activation=None, half_inputs: bool = False):
         _check_conv_rows(codes, kernel_size, cin)
-        super().__init__(codes, centers, bias, activation)
+        super().__init__(codes, centers, bias, activation, half_inputs)
         self._set_conv(kernel_size, cin, pad)
 
     @classmethod
-    def from_conv(cls, conv, weight_model, bias_model=None, bits=None) -> "PackedCompressedConv2D":
+    def from_conv(cls, conv, weight_model, bias_model=None, bits=None, half_inputs: bool = False) -> "PackedCompressedConv2D":
         codes = _inference_codes(conv, weight_model, bias_model)
         h, cin, cout = _conv_shape(conv)
-        return cls.from_codes(h, cin, cout, conv.pad, *codes, conv.activation, bits)
+        return cls.from_codes(h, cin, cout, conv.pad, *codes, conv.activation, bits, half_inputs)
 
     @classmethod
-    def from_codes(cls, kernel_size, cin, cout, pad, labels, centers, bias, activation, bits=None) -> "PackedCompressedConv2D":
+    def from_codes(cls, kernel_size, cin, cout, pad, labels, centers, bias, activation, bits=None,
+                   half_inputs: bool = False) -> "PackedCompressedConv2D":
         """labels in the Keras order of the (h, w, in, out) kernel."""
         ops.packed_bits(centers.numel(), bits)   # a codebook that does not fit raises before the unfold
         codes = _unfold_then_pack(ops.pack_codes, kernel_size, cin, cout, labels, centers.numel(), bits)
-        return cls(kernel_size, cin, pad, codes, centers, bias, activation)
+        return cls(kernel_size, cin, pad, codes, centers, bias, activation, half_inputs)
 
 
 class _TrainablePackedCodebookLayer(_PackedForm, _TrainableCodesLayer):
     """The indices in the 2- or 4-bit packed form (the ``packed`` buffer, as _PackedCodebookLayer) with the centres, counts and bias
     of _TrainableCentres; the forward goes through ops.packed_codebook_linear, whose backward forms dx and the centroid gradient
     from the packed rows (csrc/nnc_cbpkgrad.hip).  ``counts`` is taken from the labels before packing, so kernel_sq_sum() is the
-    byte trainable layer's bit for bit.  No kdim * ncols tensor stays resident."""
+    byte trainable layer's bit for bit.  No kdim * ncols tensor stays resident.  ``half_inputs=True`` lets the layer train on bfloat16 /
+    float16 inputs (csrc/nnc_cbpk_h16.hip): the output and the input gradient have the input's dtype; the centres,
+    the bias and their gradients stay float32.  Without it a half input raises TypeError, as it always did."""
+
+    def __init__(self, codes, labels: torch.Tensor, centers: torch.Tensor, bias: torch.Tensor | None = None, bias_codes=None, activation=None,
+                 half_inputs: bool = False):
+        super().__init__(codes, labels, centers, bias, bias_codes, activation)
+        self.half_inputs = bool(half_inputs)
+
+    def _matmul(self, x: torch.Tensor) -> torch.Tensor:
+        if not self.half_inputs:
+            ops._require_f32_x(x, type(self).__name__)
+        return super()._matmul(x)
 
 
 class TrainablePackedCompressedDense(_DenseHalf, _TrainablePackedCodebookLayer):
     """PackedCompressedDense with trainable centres (ops.packed_codebook_linear)."""
 
     @classmethod
-    def from_dense(cls, dense, weight_model, bias_model=None, bits=None) -> "TrainablePackedCompressedDense":
+    def from_dense(cls, dense, weight_model, bias_model=None, bits=None, half_inputs: bool = False) -> "TrainablePackedCompressedDense":
         codes = _trainable_codes(dense, weight_model, bias_model)
         kin, kout = dense.kernel.shape
-        return cls.from_codes(kin, kout, *codes, dense.activation, bits)
+        return cls.from_codes(kin, kout, *codes, dense.activation, bits, half_inputs)
 
     @classmethod
-    def from_codes(cls, kdim, ncols, labels, centers, bias=None, bias_codes=None, activation=None, bits=None) -> "TrainablePackedCompressedDense":
-        return cls(ops.pack_codes(labels, kdim, ncols, centers.numel(), bits), labels, centers, bias, bias_codes, activation)
+    def from_codes(cls, kdim, ncols, labels, centers, bias=None, bias_codes=None, activation=None, bits=None,
+                   half_inputs: bool = False) -> "TrainablePackedCompressedDense":
+        return cls(ops.pack_codes(labels, kdim, ncols, centers.numel(), bits), labels, centers, bias, bias_codes, activation, half_inputs)
 
 
 class TrainablePackedCompressedConv2D(_Conv2DHalf, _TrainablePackedCodebookLayer):
@@ -757,23 +785,23 @@ class TrainablePackedCompressedConv2D(_Conv2DHalf, _TrainablePackedCodebookLayer
     ops.packed_codebook_linear; autograd carries the patch gradients back through the unfold."""
 
     def __init__(self, kernel_size: int, cin: int, pad: int, codes: ops.PackedCodes, labels: torch.Tensor, centers: torch.Tensor, bias=None,
-                 bias_codes=None, activation=None):
+                 bias_codes=None, activation=None, half_inputs: bool = False):
         _check_conv_rows(codes, kernel_size, cin)
-        super().__init__(codes, labels, centers, bias, bias_codes, activation)
+        super().__init__(codes, labels, centers, bias, bias_codes, activation, half_inputs)
         self._set_conv(kernel_size, cin, pad)
 
     @classmethod
-    def from_conv(cls, conv, weight_model, bias_model=None, bits=None) -> "TrainablePackedCompressedConv2D":
+    def from_conv(cls, conv, weight_model, bias_model=None, bits=None, half_inputs: bool = False) -> "TrainablePackedCompressedConv2D":
         h, cin, cout = _conv_shape(conv)
-        return cls.from_codes(h, cin, cout, conv.pad, *_trainable_codes(conv, weight_model, bias_model), conv.activation, bits)
+        return cls.from_codes(h, cin, cout, conv.pad, *_trainable_codes(conv, weight_model, bias_model), conv.activation, bits, half_inputs)
 
     @classmethod
     def from_codes(cls, kernel_size, cin, cout, pad, labels, centers, bias=None, bias_codes=None, activation=None,
-                   bits=None) -> "TrainablePackedCompressedConv2D":
+                   bits=None, half_inputs: bool = False) -> "TrainablePackedCompressedConv2D":
         """labels in the Keras order of the (h, w, in, out) kernel (the counts are the same in either order)."""
         ops.packed_bits(centers.numel(), bits)   # a codebook that does not fit raises before the unfold
         codes = _unfold_then_pack(ops.pack_codes, kernel_size, cin, cout, labels, centers.numel(), bits)
-        return cls(kernel_size, cin, pad, codes, labels, centers, bias, bias_codes, activation)
+        return cls(kernel_size, cin, pad, codes, labels, centers, bias, bias_codes, activation, half_inputs)
 
 
 class GroupedPackedCompressedDense(_DenseHalf, _PackedForm, _InferenceLayer):
@@ -924,18 +952,19 @@ def _pick3(k, make_byte, make_sparse, make_packed, sparse, packed):
     return best
 
 
-def _from_codes(layer, shape, labels, centers, bias, sparse, packed=False, sparse_half_inputs=False):
+def _from_codes(layer, shape, labels, centers, bias, sparse, packed=False, sparse_half_inputs=False, packed_half_inputs=False):
     from .neural_networks.layers import Conv2D, Dense
 
     half = dict(half_inputs=True) if sparse_half_inputs else {}
+    pk_half = dict(half_inputs=True) if packed_half_inputs else {}
     if isinstance(layer, Dense):
         args = (shape[0], shape[1], labels, centers, bias, layer.activation)
         make_byte, make_sparse, make_packed = (lambda: CompressedDense(*args), lambda: SparseCompressedDense.from_codes(*args, **half),
-                                               lambda: PackedCompressedDense.from_codes(*args))
+                                               lambda: PackedCompressedDense.from_codes(*args, **pk_half))
     elif isinstance(layer, Conv2D):
         args = (shape[0], shape[2], shape[3], layer.pad, labels, centers, bias, layer.activation)
         make_byte, make_sparse, make_packed = (lambda: CompressedConv2D.from_codes(*args), lambda: SparseCompressedConv2D.from_codes(*args, **half),
-                                               lambda: PackedCompressedConv2D.from_codes(*args))
+                                               lambda: PackedCompressedConv2D.from_codes(*args, **pk_half))
     else:
         raise TypeError(f"no compressed form of {type(layer).__name__}")
     if packed is False:
@@ -943,7 +972,7 @@ def _from_codes(layer, shape, labels, centers, bias, sparse, packed=False, spars
     return _pick3(centers.numel(), make_byte, make_sparse, make_packed, sparse, packed)
 
 
-def _replace(layer, weight_model, bias_model, sparse=False, packed=False, sparse_half_inputs=False):
+def _replace(layer, weight_model, bias_model, sparse=False, packed=False, sparse_half_inputs=False, packed_half_inputs=False):
     from .neural_networks.layers import Conv2D, Dense
 
     if sparse is False and packed is False:
@@ -955,7 +984,8 @@ def _replace(layer, weight_model, bias_model, sparse=False, packed=False, sparse
     if not isinstance(layer, (Dense, Conv2D)):
         raise TypeError(f"no compressed form of {type(layer).__name__}")
     centers, labels = _codes(weight_model, layer.kernel.device)
-    return _from_codes(layer, tuple(layer.kernel.shape), labels, centers, _decoded_bias(layer.bias, bias_model), sparse, packed, sparse_half_inputs)
+    return _from_codes(layer, tuple(layer.kernel.shape), labels, centers, _decoded_bias(layer.bias, bias_model), sparse, packed, sparse_half_inputs,
+                       packed_half_inputs)
 
 
 def _check_half_inputs(half_inputs, sparse, packed, trainable=True):
@@ -980,8 +1010,23 @@ def _check_sparse_half_inputs(sparse_half_inputs, sparse, trainable=False):
                          "half_inputs=True (the byte form takes bfloat16 and float16 inputs as it is)")
 
 
+def _check_packed_half_inputs(packed_half_inputs, sparse, packed, sparse_half_inputs, trainable=False):
+    if not packed_half_inputs:
+        return
+    if trainable:
+        raise ValueError("packed_half_inputs=True builds the packed inference layers here: it needs trainable=False "
+                         "(compress_network_trainable(..., packed=..., packed_half_inputs=True) builds the trainable packed layers "
+                         "that train on bfloat16 / float16 inputs)")
+    if packed is False:
+        raise ValueError("packed_half_inputs=True needs packed=True or packed='auto': it builds the 2- / 4-bit packed layers with "
+                         "half_inputs=True")
+    if sparse is not False and not sparse_half_inputs:
+        raise ValueError("packed_half_inputs=True with sparse=True or sparse='auto' needs sparse_half_inputs=True too: a layer that "
+                         "'auto' gives to the bitmap-sparse form would refuse the bfloat16 / float16 input")
+
+
 def compress_network(network: nn.Module, models_by_layer, sparse=False, trainable=False, packed=False, half_inputs=False,
-                     sparse_half_inputs=False) -> nn.Module:
+                     sparse_half_inputs=False, packed_half_inputs=False) -> nn.Module:
     """A deep copy of ``network`` whose quantized layers (``models_by_layer``: layer -> [kernel model, bias model], as
     Trainer.quantized_models_by_layer) run from their codebooks.  Layers are replaced by the attribute names of
     ``get_config()``; a layer whose kernel passed through unquantized (model None) stays float32.  ``sparse``: False (the
@@ -994,6 +1039,9 @@ def compress_network(network: nn.Module, models_by_layer, sparse=False, trainabl
     ``sparse_half_inputs=True`` (with ``sparse`` True or "auto" and trainable=False only, else ValueError): the bitmap-sparse layers are
     built with half_inputs=True and run on bfloat16 / float16 inputs; layers that "auto" leaves in the byte form
     take them anyway, and what "auto" picks does not change.
+    ``packed_half_inputs=True`` (with ``packed`` True or "auto" and trainable=False only, and with ``sparse`` other than False only
+    together with sparse_half_inputs=True, else ValueError): the packed layers are built with half_inputs=True and run on bfloat16 /
+    float16 inputs; what "auto" picks does not change.
     A layer whose kernel model is a utility.GroupedModel (one codebook per block of input rows) becomes a GroupedCompressedDense;
     with ``sparse``, ``packed`` or ``trainable`` set it raises NotImplementedError and names the layer (pack_grouped_layers packs
     the grouped layers of the result)."""
@@ -1001,17 +1049,19 @@ def compress_network(network: nn.Module, models_by_layer, sparse=False, trainabl
     _check_packed(packed, sparse, trainable)
     _check_half_inputs(half_inputs, sparse, packed, trainable)
     _check_sparse_half_inputs(sparse_half_inputs, sparse, trainable)
+    _check_packed_half_inputs(packed_half_inputs, sparse, packed, sparse_half_inputs, trainable)
     if trainable and sparse is not False:
         raise ValueError("trainable=True needs sparse=False here: use compress_network_trainable(..., sparse=...) for trainable "
                          "bitmap-sparse layers")
     if trainable:
         return compress_network_trainable(network, models_by_layer, half_inputs=half_inputs)
     what = "sparse=" + repr(sparse) if sparse is not False else ("packed=" + repr(packed) if packed is not False else None)
-    return _compress_each(network, models_by_layer, lambda layer, wm, bm: _replace(layer, wm, bm, sparse, packed, sparse_half_inputs), grouped=what)
+    return _compress_each(network, models_by_layer, lambda layer, wm, bm: _replace(layer, wm, bm, sparse, packed, sparse_half_inputs, packed_half_inputs),
+                          grouped=what)
 
 
 def compress_network_trainable(network: nn.Module, models_by_layer, sparse=False, packed=False, half_inputs=False,
-                               sparse_half_inputs=False) -> nn.Module:
+                               sparse_half_inputs=False, packed_half_inputs=False) -> nn.Module:
     """compress_network with the centres (and quantized biases' centres) as nn.Parameters.  ``sparse``: False
     (TrainableCompressedDense / TrainableCompressedConv2D, the layers of compress_network(..., trainable=True)), True
     (TrainableSparseCompressedDense / TrainableSparseCompressedConv2D: the indices in the bitmap-sparse form, skipping the most
@@ -1023,21 +1073,26 @@ def compress_network_trainable(network: nn.Module, models_by_layer, sparse=False
     train on bfloat16 / float16 inputs.
     ``sparse_half_inputs=True`` (``sparse`` True or "auto" and packed=False only, else ValueError): the bitmap-sparse layers are built
     with half_inputs=True and train on bfloat16 / float16 inputs; the layers "auto" leaves in the byte form are
-    built with it too, so the whole network trains on half inputs, and what "auto" picks does not change."""
-    if sparse_half_inputs and (sparse is False or packed is not False):
+    built with it too, so the whole network trains on half inputs, and what "auto" picks does not change.
+    ``packed_half_inputs=True`` (``packed`` True or "auto" only, and with ``sparse`` other than False only together with
+    sparse_half_inputs=True, else ValueError): the packed layers are built with half_inputs=True and train on bfloat16 / float16 inputs
+    (DESIGN.md section 25); the layers left in the byte form are built with it too, and what "auto" picks does not change."""
+    _check_packed_half_inputs(packed_half_inputs, sparse, packed, sparse_half_inputs)
+    if sparse_half_inputs and (sparse is False or (packed is not False and not packed_half_inputs)):
         raise ValueError("sparse_half_inputs=True needs sparse=True or sparse='auto', and packed=False: it builds the trainable "
                          "bitmap-sparse layers with half_inputs=True (half_inputs=True builds the byte form's; the packed layers "
                          "take float32 activations)")
     _check_sparse(sparse)
     _check_packed(packed, sparse)
     _check_half_inputs(half_inputs, sparse, packed)
-    half = bool(half_inputs or sparse_half_inputs)
+    half = bool(half_inputs or sparse_half_inputs or packed_half_inputs)
 
     def make(layer, wm, bm):
         byte, sp, pk = (lambda: _trainable(layer, wm, bm, half_inputs=half),
                         lambda: _trainable(layer, wm, bm, TrainableSparseCompressedDense, TrainableSparseCompressedConv2D,
                                            half_inputs=bool(sparse_half_inputs)),
-                        lambda: _trainable(layer, wm, bm, TrainablePackedCompressedDense, TrainablePackedCompressedConv2D))
+                        lambda: _trainable(layer, wm, bm, TrainablePackedCompressedDense, TrainablePackedCompressedConv2D,
+                                           half_inputs=bool(packed_half_inputs)))
         return _pick(byte, sp, sparse) if packed is False else _pick3(wm.cluster_centers_.size, byte, sp, pk, sparse, packed)
 
     return _compress_each(network, models_by_layer, make, grouped="trainable=True")
@@ -1082,17 +1137,19 @@ def _compress_each(network: nn.Module, models_by_layer, make, grouped=None, make
     return out
 
 
-def load_network(path: str, network: nn.Module, device=None, sparse=False, packed=False, sparse_half_inputs=False) -> nn.Module:
+def load_network(path: str, network: nn.Module, device=None, sparse=False, packed=False, sparse_half_inputs=False,
+                 packed_half_inputs=False) -> nn.Module:
     """``compress_network`` from a stored network (storage.save_compressed, as Trainer.store_report writes it: records
     "{layer}.weights" / "{layer}.biases", or "{layer}.weights#g{g}" per group of a kernel with group-wise codebooks, whose
     ``group_rows`` is the row count of the first).  ``network`` gives the architecture; layers stored raw get the stored float32 values.
-    ``sparse``, ``packed`` and ``sparse_half_inputs`` as in compress_network: the stored format is the same, the indices are packed after loading.  A
+    ``sparse``, ``packed``, ``sparse_half_inputs`` and ``packed_half_inputs`` as in compress_network: the stored format is the same, the indices are packed after loading.  A
     kernel with group-wise codebooks raises NotImplementedError for either; pack_grouped_layers packs it after loading."""
     from . import storage
 
     _check_sparse(sparse)
     _check_packed(packed, sparse)
     _check_sparse_half_inputs(sparse_half_inputs, sparse)
+    _check_packed_half_inputs(packed_half_inputs, sparse, packed, sparse_half_inputs)
     device = next(network.parameters()).device if device is None else device
     codes = storage.load_compressed_codes(path, device)
     out = copy.deepcopy(network)
@@ -1126,7 +1183,7 @@ def load_network(path: str, network: nn.Module, device=None, sparse=False, packe
             target.set_weights([went.reshape(target.kernel.shape)] + ([bias.reshape(target.bias.shape)] if bias is not None else []))
             continue
         shape, centers, labels = went
-        setattr(out, name, _from_codes(layer, tuple(shape), labels, centers, bias, sparse, packed, sparse_half_inputs))
+        setattr(out, name, _from_codes(layer, tuple(shape), labels, centers, bias, sparse, packed, sparse_half_inputs, packed_half_inputs))
     return out
 
 

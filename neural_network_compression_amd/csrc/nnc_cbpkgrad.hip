@@ -22,76 +22,10 @@
 //                    dword, loaded once.
 // k_cbgrad_absmax, k_cbdc_finish and k_cbgrad_reduce are nnc_cbgrad.hip's.  No float atomics; no host read.
 // The sequences of HIP calls of the two entry points (cbg_run_dx, cbg_run_dc), the lookup in the table of stream instantiations and
-// the x load of k_cbpkdc_stream (cbdc_load_x) are nnc_cbgrad.hpp's; the list the table is made from is nnc_cbpkgrad.hpp's.
+// the x load of k_cbpkdc_stream (cbdc_load_x) are nnc_cbgrad.hpp's; the list the table is made from is nnc_cbpkgrad.hpp's, and so
+// are the two stream kernels, templates on the element type that this unit instantiates for float32 and nnc_cbpk_h16.hip for
+// bf16 / fp16.
 #include "nnc_cbpkgrad.hpp"
-
-// ------------------------------------------------------------------ dx, m <= 16
-// grid (column blocks, row groups), CB_THREADS threads.  out: dx (one column block) or the partials [block][m][kdim].
-template <int BITS, int VB, int MT>
-__global__ __launch_bounds__(CB_THREADS) void k_cbpkdx_stream(const float *__restrict__ g, int m, long long kdim, const unsigned char *__restrict__ packed,
-                                                              long long row_bytes, long long ncols, const float *__restrict__ centers, int k,
-                                                              long long rows_per_group, int direct, float *__restrict__ out)
-{
-    constexpr int E = 8 * VB / BITS, N = VB >= 4 ? VB / 4 : 1, PER = 32 / BITS, ENTRIES = 1 << BITS;
-    constexpr uint32_t MASK = (1u << BITS) - 1;
-    static_assert(E * MT <= PKG_G, "g values per lane");
-    extern __shared__ float smem[];
-    float *cb = smem;                                   // [ENTRIES][PK_COPIES]
-    float *stage = smem + ENTRIES * PK_COPIES;
-    cb_fill(cb, stage, centers, k, ENTRIES, PK_CSHIFT);
-
-    const int lane = threadIdx.x & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const long long c0 = (long long)blockIdx.x * (64 * E) + lane * E;
-    const bool active = c0 < ncols;                     // then the lane's VB bytes lie inside the padded row
-    const int ne = (int)std::max(0LL, std::min((long long)E, ncols - c0));   // the lane's columns inside the matrix
-    float gv[MT][E];
-#pragma unroll
-    for (int r = 0; r < MT; ++r)
-#pragma unroll
-        for (int e = 0; e < E; ++e) gv[r][e] = (r < m && e < ne) ? g[(long long)r * ncols + c0 + e] : 0.0f;
-
-    const long long g_lo = (long long)blockIdx.y * rows_per_group, g_hi = std::min(kdim, g_lo + rows_per_group);
-    const long long per_wave = (g_hi - g_lo + CB_WAVES - 1) / CB_WAVES;
-    const long long i0 = std::min(g_hi, g_lo + wave * per_wave), i1 = std::min(g_hi, i0 + per_wave);
-    const unsigned char *mine = packed + (active ? (long long)blockIdx.x * (64 * VB) + lane * VB : 0LL);
-    const char *tab = reinterpret_cast<const char *>(cb) + ((lane & (PK_COPIES - 1)) << 2);
-    float *dst = direct ? out : out + (long long)blockIdx.x * m * kdim;
-    __syncthreads();
-
-    auto consume = [&](const uint32_t *w, long long i) {
-        float p[MT];
-#pragma unroll
-        for (int r = 0; r < MT; ++r) p[r] = 0.0f;
-#pragma unroll
-        for (int e = 0; e < E; ++e) {
-            constexpr int SH = 7;                                        // entry l of this lane's copy at byte l << 7
-            const int bit = BITS * (e % PER);
-            const uint32_t d = w[e / PER];
-            const uint32_t a = (bit >= SH ? d >> (bit - SH) : d << (SH - bit)) & (MASK << SH);
-            const float wv = e < ne ? *reinterpret_cast<const float *>(tab + a) : 0.0f;   // (columns past the row: no Inf * 0)
-#pragma unroll
-            for (int r = 0; r < MT; ++r) p[r] = __builtin_fmaf(gv[r][e], wv, p[r]);
-        }
-        int row;
-        const float v = wave_reduce_rows<MT>(p, lane, row);
-        if ((lane & (64 / MT - 1)) == 0 && row < m) dst[(long long)row * kdim + i] = v;
-    };
-
-    long long i = i0;
-    for (; i + CB_UNROLL <= i1; i += CB_UNROLL) {
-        uint32_t w[CB_UNROLL][N];
-#pragma unroll
-        for (int u = 0; u < CB_UNROLL; ++u) pk_load<VB>(mine + (i + u) * row_bytes, w[u]);
-#pragma unroll
-        for (int u = 0; u < CB_UNROLL; ++u) consume(w[u], i + u);
-    }
-    for (; i < i1; ++i) {
-        uint32_t w[N];
-        pk_load<VB>(mine + i * row_bytes, w);
-        consume(w, i);
-    }
-}
 
 // ------------------------------------------------------------------ dx, m > 16
 // grid (kdim tiles * m tiles, splits of ncols), 256 threads; thread (tx, ty) owns rows ty*8.. (of g) and columns tx*8.. (i) of the
@@ -131,91 +65,6 @@ __global__ __launch_bounds__(256) void k_cbpkdx_tiled(const float *__restrict__ 
     for (int a = 0; a < 8; ++a)
 #pragma unroll
         for (int b = 0; b < 8; ++b) tb_store_dx(acc[a][b], T.m0 + T.ty * 8 + a, T.n0 + T.tx * 8 + b, m, kdim, direct, out);
-}
-
-// ------------------------------------------------------------------ dc, m <= 16
-// grid (column blocks, row groups), CB_THREADS threads.  LDS: the bins, [k][64] int64, copy `lane` of every bin this lane's own.
-template <int BITS, int VB, int MT>
-__global__ __launch_bounds__(CB_THREADS) void k_cbpkdc_stream(const float *__restrict__ x, const float *__restrict__ g, int m, long long kdim,
-                                                              const unsigned char *__restrict__ packed, long long row_bytes, long long ncols, int k,
-                                                              int terms_log2, long long rows_per_group, uint32_t *__restrict__ hdr,
-                                                              unsigned long long *__restrict__ sums)
-{
-    constexpr int E = 8 * VB / BITS, N = VB >= 4 ? VB / 4 : 1, PER = 32 / BITS;
-    constexpr uint32_t MASK = (1u << BITS) - 1;
-    static_assert(E * MT <= PKG_G, "g values per lane");
-    extern __shared__ unsigned long long bins[];
-    int flag;
-    const int S = cbdc_shift(hdr, m, terms_log2, flag);
-    if (blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0) {
-        hdr[2] = (uint32_t)S;
-        hdr[3] = (uint32_t)flag;
-    }
-    if (flag != CBG_FLAG_OK) return;   // (uniform over the launch)
-    int scx, scg;
-    cbdc_scales(hdr, scx, scg);
-    const int Sw = S - scx - scg;      // the shift of dW' = dW * 2^(scx + scg)
-    for (int j = threadIdx.x; j < (k << PKG_RLOG2); j += CB_THREADS) bins[j] = 0ull;
-
-    const int lane = threadIdx.x & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const long long c0 = (long long)blockIdx.x * (64 * E) + lane * E;
-    const bool active = c0 < ncols;
-    const int ne = (int)std::max(0LL, std::min((long long)E, ncols - c0));
-    float gv[MT][E];
-#pragma unroll
-    for (int r = 0; r < MT; ++r)
-#pragma unroll
-        for (int e = 0; e < E; ++e) gv[r][e] = g[cbdc_idx((long long)r * ncols + c0 + e, r < m && e < ne)];
-    __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-    for (int r = 0; r < MT; ++r)
-#pragma unroll
-        for (int e = 0; e < E; ++e) gv[r][e] = cbdc_scaled(gv[r][e], r < m && e < ne, scg);
-
-    const long long g_lo = (long long)blockIdx.y * rows_per_group, g_hi = std::min(kdim, g_lo + rows_per_group);
-    const long long per_wave = (g_hi - g_lo + CB_WAVES - 1) / CB_WAVES;
-    const long long i0 = std::min(g_hi, g_lo + wave * per_wave), i1 = std::min(g_hi, i0 + per_wave);
-    const unsigned char *mine = packed + (active ? (long long)blockIdx.x * (64 * VB) + lane * VB : 0LL);
-    unsigned long long *mybins = bins + lane;
-    __syncthreads();
-
-    auto load_x = [&](long long i, int U, float &xa, float &xb) { cbdc_load_x<MT>(x, kdim, m, scx, lane, i, U, xa, xb); };
-    auto consume = [&](const uint32_t *w, float xa, float xb, int u, int U) {
-        float xv[MT];
-#pragma unroll
-        for (int r = 0; r < MT; ++r) {
-            const int f = r * U + u;
-            xv[r] = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, f < 64 ? xa : xb), f & 63));
-        }
-#pragma unroll
-        for (int e = 0; e < E; ++e) {
-            const uint32_t l = (w[e / PER] >> (BITS * (e % PER))) & MASK;
-            float d = 0.0f;
-#pragma unroll
-            for (int r = 0; r < MT; ++r) d = __builtin_fmaf(xv[r], gv[r][e], d);   // dW'[i, o], r ascending
-            if (e < ne && l < (uint32_t)k) atomicAdd(&mybins[l << PKG_RLOG2], cbdc_fix(d, Sw));
-        }
-    };
-
-    long long i = i0;
-    for (; i + CB_UNROLL <= i1; i += CB_UNROLL) {
-        uint32_t w[CB_UNROLL][N];
-        float xa, xb;
-#pragma unroll
-        for (int u = 0; u < CB_UNROLL; ++u) pk_load<VB>(mine + (i + u) * row_bytes, w[u]);
-        load_x(i, CB_UNROLL, xa, xb);
-#pragma unroll
-        for (int u = 0; u < CB_UNROLL; ++u) consume(w[u], xa, xb, u, CB_UNROLL);
-    }
-    for (; i < i1; ++i) {
-        uint32_t w[N];
-        float xa, xb;
-        pk_load<VB>(mine + i * row_bytes, w);
-        load_x(i, 1, xa, xb);
-        consume(w, xa, xb, 0, 1);
-    }
-    cbdc_flush(bins, k, PKG_RLOG2, sums);
 }
 
 // ------------------------------------------------------------------ dc, m > 16
@@ -260,14 +109,15 @@ template <int BITS, int VB, int MT>
 static void launch_pg_dx(dim3 grid, size_t lds, hipStream_t s, const float *g, int m, long long kdim, const unsigned char *packed, long long row_bytes,
                          long long ncols, const float *centers, int k, long long rpg, int direct, float *out)
 {
-    hipLaunchKernelGGL((k_cbpkdx_stream<BITS, VB, MT>), grid, dim3(CB_THREADS), lds, s, g, m, kdim, packed, row_bytes, ncols, centers, k, rpg, direct, out);
+    hipLaunchKernelGGL((k_cbpkdx_stream<float, BITS, VB, MT>), grid, dim3(CB_THREADS), lds, s, g, m, kdim, packed, row_bytes, ncols, centers, k, rpg, direct,
+                       static_cast<void *>(out));
 }
 
 template <int BITS, int VB, int MT>
 static void launch_pg_dc(dim3 grid, size_t lds, hipStream_t s, const float *x, const float *g, int m, long long kdim, const unsigned char *packed,
                          long long row_bytes, long long ncols, int k, int tl, long long rpg, uint32_t *hdr, unsigned long long *sums)
 {
-    hipLaunchKernelGGL((k_cbpkdc_stream<BITS, VB, MT>), grid, dim3(CB_THREADS), lds, s, x, g, m, kdim, packed, row_bytes, ncols, k, tl, rpg, hdr, sums);
+    hipLaunchKernelGGL((k_cbpkdc_stream<float, BITS, VB, MT>), grid, dim3(CB_THREADS), lds, s, x, g, m, kdim, packed, row_bytes, ncols, k, tl, rpg, hdr, sums);
 }
 
 // every stream instantiation there is (the list of nnc_cbpkgrad.hpp); the plans are checked against this table, and the launches go through it

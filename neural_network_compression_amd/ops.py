@@ -32,7 +32,8 @@ def _require_f32_x(x, who: str):
         raise TypeError(f"{who} takes float32 activations, got {x.dtype}: bfloat16 and float16 inputs run on the byte form "
                         "(ops.codebook_matmul and ops.codebook_linear; CompressedDense / CompressedConv2D, and their trainable "
                         "layers built with half_inputs=True) and on the bitmap-sparse form (ops.sparse_codebook_matmul and "
-                        "ops.sparse_codebook_linear; the sparse layers built with half_inputs=True)")
+                        "ops.sparse_codebook_linear; the sparse layers built with half_inputs=True) and on the 2- / 4-bit packed form "
+                        "(ops.packed_codebook_matmul and ops.packed_codebook_linear; the packed layers built with half_inputs=True)")
 
 
 def _stream(t: torch.Tensor) -> int:
@@ -1038,12 +1039,26 @@ def pack_codes(labels: torch.Tensor, kdim: int, ncols: int, k: int, bits: int | 
 
 
 def packed_codebook_matmul(x: torch.Tensor, codes: PackedCodes, centers: torch.Tensor, bias: torch.Tensor | None = None,
-                           relu: bool = False) -> torch.Tensor:
+                           relu: bool = False, out_dtype=None) -> torch.Tensor:
     """y = x @ W + bias (then ReLU) with W[i, o] = centers[label (i, o)] read from the 2- or 4-bit packed indices (include/nnc.h,
     nnc_cbpk_f32): codebook_matmul on the unpacked labels, from a half or a quarter of the index bytes.  x: float32 (..., kdim);
-    centers: float32[codes.k]; bias: float32[ncols] or None.  Returns float32 (..., ncols).  Inference only, as codebook_matmul."""
-    _require_f32_x(x, "packed_codebook_matmul")
-    _require_cuda(x, "x", torch.float32)
+    centers: float32[codes.k]; bias: float32[ncols] or None.  Returns float32 (..., ncols).
+    A bfloat16 or float16 x takes nnc_cbpk_h16: centers and bias stay float32, every centre is rounded to x's
+    dtype as ``centers.to(x.dtype)`` does, the products are exact and the sums float32; the result has ``out_dtype``: None (x's dtype,
+    the float32 value rounded once) or torch.float32.  It is grouped_packed_codebook_matmul with one group bit for bit; above 16 rows
+    of x also ops.codebook_matmul on ``codes.to_dense()``, up to 16 rows with float32 output the float32 product of the widened x and
+    the rounded centres.  A float32 x takes no ``out_dtype`` but None or torch.float32.
+    Inference only, as codebook_matmul."""
+    if isinstance(x, torch.Tensor) and x.dtype in _H16_DT:
+        _require_cuda(x, "x")
+        if out_dtype not in (None, torch.float32):
+            raise TypeError(f"out_dtype must be None ({x.dtype}) or torch.float32 for x of {x.dtype}, got {out_dtype}")
+        y_dtype = x.dtype if out_dtype is None else out_dtype
+    else:
+        _require_cuda(x, "x", torch.float32)
+        if out_dtype not in (None, torch.float32):
+            raise TypeError(f"out_dtype must be None or torch.float32 for a float32 x, got {out_dtype}")
+        y_dtype = torch.float32
     _require_centers_bias(centers, bias)
     if not isinstance(codes, PackedCodes):
         raise TypeError("codes must be a PackedCodes (ops.pack_codes)")
@@ -1052,8 +1067,14 @@ def packed_codebook_matmul(x: torch.Tensor, codes: PackedCodes, centers: torch.T
     lead, m = _rows(x, "x", kdim)
     if centers.numel() != codes.k:
         raise ValueError(f"centers must hold k = {codes.k} values, got {centers.numel()}")
-    y = _empty_y(x, lead, ncols, bias, torch.float32)
+    y = _empty_y(x, lead, ncols, bias, y_dtype)
     L = nat.load()
+    if x.dtype in _H16_DT:
+        ws_bytes = int(L.nnc_cbpk_h16_workspace_bytes(m, kdim, ncols, codes.bits))
+        ws = _workspace(ws_bytes, x.device)
+        nat.check(L.nnc_cbpk_h16(_ptr(x), _H16_DT[x.dtype], m, kdim, _ptr(codes.packed), codes.nbytes, codes.bits, ncols, _ptr(centers), centers.numel(),
+                                 _ptr(bias), 1 if relu else 0, _ptr(y), _H16_DT.get(y_dtype, nat.DT_F32), _ptr(ws), ws_bytes, _stream(x)))
+        return y
     ws_bytes = int(L.nnc_cbpk_workspace_bytes(m, kdim, ncols, codes.bits))
     ws = _workspace(ws_bytes, x.device)
     nat.check(L.nnc_cbpk_f32(_ptr(x), m, kdim, _ptr(codes.packed), codes.nbytes, codes.bits, ncols, _ptr(centers), centers.numel(), _ptr(bias),
@@ -1065,6 +1086,12 @@ def cbpk_plan(m: int, kdim: int, ncols: int, bits: int, k: int, cus: int) -> dic
     """Host: the plan nnc_cbpk_f32 follows on a device with ``cus`` compute units (include/nnc.h, nnc_cbpk_plan), as a dict keyed
     by _native.CBPK_PLAN_FIELDS.  No device needed."""
     return _plan(nat.load().nnc_cbpk_plan, nat.CBPK_PLAN_FIELDS, m, kdim, ncols, bits, k, cus)
+
+
+def cbpk_h16_plan(dtype, m: int, kdim: int, ncols: int, bits: int, k: int, cus: int) -> dict:
+    """Host: the plan nnc_cbpk_h16 follows for x of ``dtype`` (torch.bfloat16 / torch.float16) on a device with ``cus`` compute units
+    (include/nnc_cbpk_h16.h, nnc_cbpk_h16_plan), as a dict keyed by _native.CBPK_H16_PLAN_FIELDS.  No device needed."""
+    return _plan(nat.load().nnc_cbpk_h16_plan, nat.CBPK_H16_PLAN_FIELDS, _h16_dt(dtype), m, kdim, ncols, bits, k, cus)
 
 
 def grouped_packed_codebook_matmul(x: torch.Tensor, codes: PackedCodes, centers: torch.Tensor, group_rows: int, bias: torch.Tensor | None = None,
@@ -1111,13 +1138,21 @@ def cbpk_grouped_plan(dtype, m: int, kdim: int, ncols: int, bits: int, k: int, g
     return _plan(nat.load().nnc_cbpk_grouped_plan, nat.CBPK_GROUPED_PLAN_FIELDS, _X_DT[dtype], m, kdim, ncols, bits, k, group_rows, cus)
 
 
-def packed_codebook_matmul_dx(g: torch.Tensor, codes: PackedCodes, centers: torch.Tensor) -> torch.Tensor:
+def packed_codebook_matmul_dx(g: torch.Tensor, codes: PackedCodes, centers: torch.Tensor, out_dtype=None) -> torch.Tensor:
     """dx = g @ W^T with W[i, o] = centers[label (i, o)] read from the 2- or 4-bit packed indices (include/nnc.h,
     nnc_cbpk_dx_f32): the input gradient of packed_codebook_matmul with the conventions of codebook_matmul_dx (a label >= k reads 0;
     the padding of a row forms no product).  g: float32 (..., ncols); centers: float32[codes.k].  Returns float32 (..., kdim).
-    Split partials are summed in a fixed order: the same call gives the same bits.  No host read."""
+    Split partials are summed in a fixed order: the same call gives the same bits.  No host read.
+    A bfloat16 or float16 g takes nnc_cbpk_dx_h16: centers stay float32 and are rounded to g's dtype as the
+    forward rounds them, the products are exact, the sums float32; the result has ``out_dtype``: None (g's dtype, the float32 value
+    rounded once) or torch.float32.  Up to 16 rows of g it is the float32 call on the widened g and the rounded centres bit for bit;
+    above, it is ops.codebook_matmul_dx on ``codes.to_dense()`` bit for bit.  A float32 g takes no ``out_dtype`` but None or
+    torch.float32."""
     _require_cuda(centers, "centers", torch.float32)
-    _require_cuda(g, "g", torch.float32)
+    half = isinstance(g, torch.Tensor) and g.dtype in _H16_DT
+    _require_cuda(g, "g", g.dtype if half else torch.float32)
+    if out_dtype not in (None, torch.float32):
+        raise TypeError(f"out_dtype must be None or torch.float32, got {out_dtype}")
     if not isinstance(codes, PackedCodes):
         raise TypeError("codes must be a PackedCodes (ops.pack_codes)")
     lead, m = _rows(g, "g", codes.ncols)
@@ -1126,6 +1161,14 @@ def packed_codebook_matmul_dx(g: torch.Tensor, codes: PackedCodes, centers: torc
     _one_device("g, codes and centers", g, codes.packed, centers)
     L = nat.load()
     kdim, ncols, bits = codes.kdim, codes.ncols, codes.bits
+    if half:
+        dx_dtype = g.dtype if out_dtype is None else out_dtype
+        dx = torch.empty(lead + (kdim,), dtype=dx_dtype, device=g.device)
+        ws_bytes = int(L.nnc_cbpk_dx_h16_workspace_bytes(m, kdim, ncols, bits))
+        ws = _workspace(ws_bytes, g.device)
+        nat.check(L.nnc_cbpk_dx_h16(_ptr(g), _H16_DT[g.dtype], m, kdim, _ptr(codes.packed), codes.nbytes, bits, ncols, _ptr(centers), centers.numel(),
+                                    _ptr(dx), _H16_DT.get(dx_dtype, nat.DT_F32), _ptr(ws), ws_bytes, _stream(g)))
+        return dx
     dx = torch.empty(lead + (kdim,), dtype=torch.float32, device=g.device)
     ws_bytes = int(L.nnc_cbpk_dx_workspace_bytes(m, kdim, ncols, bits))
     ws = _workspace(ws_bytes, g.device)
@@ -1138,9 +1181,14 @@ def packed_codebook_centroid_grad(x: torch.Tensor, g: torch.Tensor, codes: Packe
     """dc[j] = sum over the (i, o) whose label is j of (x^T g)[i, o] (include/nnc.h, nnc_cbpk_dc_f32): bit for bit
     codebook_centroid_grad(x, g, codes.to_dense(), codes.k, ...), the indices never unpacked and dW never written.  x: float32
     (..., kdim), g: float32 (..., ncols) with the same leading shape.  Returns ``dtype`` (float64 or float32) [codes.k].  No host
-    read."""
-    _require_cuda(x, "x", torch.float32)
-    _require_cuda(g, "g", torch.float32)
+    read.
+    x and g both bfloat16 or both float16 take nnc_cbpk_dc_h16: again codebook_centroid_grad on
+    ``codes.to_dense()`` and the same half inputs bit for bit; the result is the gradient with respect to the float32 centres."""
+    if isinstance(x, torch.Tensor) and isinstance(g, torch.Tensor) and x.dtype != g.dtype and (x.dtype in _H16_DT or g.dtype in _H16_DT):
+        raise TypeError(f"x and g must have one dtype, got {x.dtype} and {g.dtype}")
+    half = isinstance(x, torch.Tensor) and x.dtype in _H16_DT
+    _require_cuda(x, "x", x.dtype if half else torch.float32)
+    _require_cuda(g, "g", x.dtype if half else torch.float32)
     if not isinstance(codes, PackedCodes):
         raise TypeError("codes must be a PackedCodes (ops.pack_codes)")
     kdim, ncols, k, bits = codes.kdim, codes.ncols, codes.k, codes.bits
@@ -1148,6 +1196,12 @@ def packed_codebook_centroid_grad(x: torch.Tensor, g: torch.Tensor, codes: Packe
     _dc_args(x, lead, kdim, "x, g and codes", codes.packed, g, dtype)
     L = nat.load()
     dc = torch.empty(k, dtype=dtype, device=x.device)
+    if half:
+        ws_bytes = int(L.nnc_cbpk_dc_h16_workspace_bytes(m, kdim, ncols, bits, k))
+        ws = _workspace(ws_bytes, x.device)
+        nat.check(L.nnc_cbpk_dc_h16(_ptr(x), _ptr(g), _H16_DT[x.dtype], m, kdim, _ptr(codes.packed), codes.nbytes, bits, ncols, k, _ptr(dc),
+                                    1 if dtype == torch.float64 else 0, _ptr(ws), ws_bytes, _stream(x)))
+        return dc
     ws_bytes = int(L.nnc_cbpk_dc_workspace_bytes(m, kdim, ncols, bits, k))
     ws = _workspace(ws_bytes, x.device)
     nat.check(L.nnc_cbpk_dc_f32(_ptr(x), _ptr(g), m, kdim, _ptr(codes.packed), codes.nbytes, bits, ncols, k, _ptr(dc),
@@ -1167,15 +1221,30 @@ def cbpk_dc_plan(m: int, kdim: int, ncols: int, bits: int, k: int, cus: int) -> 
     return _plan(nat.load().nnc_cbpk_dc_plan, nat.CBPKDC_PLAN_FIELDS, m, kdim, ncols, bits, k, cus)
 
 
+def cbpk_dx_h16_plan(dtype, m: int, kdim: int, ncols: int, bits: int, k: int, cus: int) -> dict:
+    """Host: the plan nnc_cbpk_dx_h16 follows for g of ``dtype`` (torch.bfloat16 / torch.float16) on a device with ``cus`` compute
+    units (include/nnc_cbpk_h16.h), as a dict keyed by _native.CBPKDX_H16_PLAN_FIELDS.  No device needed."""
+    return _plan(nat.load().nnc_cbpk_dx_h16_plan, nat.CBPKDX_H16_PLAN_FIELDS, _h16_dt(dtype), m, kdim, ncols, bits, k, cus)
+
+
+def cbpk_dc_h16_plan(dtype, m: int, kdim: int, ncols: int, bits: int, k: int, cus: int) -> dict:
+    """Host: the plan nnc_cbpk_dc_h16 follows for x and g of ``dtype`` (include/nnc_cbpk_h16.h), as a dict keyed by
+    _native.CBPKDC_H16_PLAN_FIELDS.  No device needed."""
+    return _plan(nat.load().nnc_cbpk_dc_h16_plan, nat.CBPKDC_H16_PLAN_FIELDS, _h16_dt(dtype), m, kdim, ncols, bits, k, cus)
+
+
 def packed_codebook_linear(x: torch.Tensor, codes: PackedCodes, centers: torch.Tensor, bias: torch.Tensor | None = None,
                            relu: bool = False) -> torch.Tensor:
     """packed_codebook_matmul with gradients for x, centers and bias (an autograd Function shaped like codebook_linear).  The
     forward is the same nnc_cbpk_f32 call (under no_grad the bits of packed_codebook_matmul); the backward runs
     packed_codebook_matmul_dx only if x needs a gradient and packed_codebook_centroid_grad (float32) only if centers does, masks a
-    fused ReLU as torch does and sums the bias gradient over the rows.  The indices get no gradient.  No host read."""
+    fused ReLU as torch does and sums the bias gradient over the rows.  The indices get no gradient.  No host read.
+    A bfloat16 or float16 x: the forward is nnc_cbpk_h16 with x's dtype out, dx has x's dtype, the gradients
+    of the float32 centers and bias are float32.  A half ``centers`` or ``bias`` raises ``TypeError``."""
     if not isinstance(codes, PackedCodes):
         raise TypeError("codes must be a PackedCodes (ops.pack_codes)")
-    _require_f32_x(x, "packed_codebook_linear")
+    if isinstance(x, torch.Tensor) and x.dtype in _H16_DT:
+        _require_centers_bias(centers, bias)
     return _CodebookLinear.apply(x, codes, centers, bias, bool(relu), codes.kdim, codes.ncols, packed_codebook_matmul, packed_codebook_matmul_dx,
                                  lambda x2, g2, cd, c: packed_codebook_centroid_grad(x2, g2, cd, dtype=torch.float32))
 
