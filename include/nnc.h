@@ -1052,6 +1052,11 @@ int nnc_cbpk_dc_f32(const float *x, const float *g, int64_t m, int64_t kdim, con
  * nnc_cbpk_h16, nnc_cbpk_dx_h16, nnc_cbpk_dc_h16, their workspace queries and plans, declared in a header of their own. */
 #include "nnc_cbpk_h16.h"
 
+/* The backward pass of the group-wise layers on bf16 / fp16 activations (csrc/nnc_cbgrad_grouped_h16.hip: byte indices,
+ * csrc/nnc_cbpkgrad_grouped_h16.hip: packed indices): nnc_cbmm_grouped_dx_h16, nnc_cbmm_grouped_dc_h16 and the
+ * two of the packed form, their workspace queries and plans, declared in a header of their own. */
+#include "nnc_cbgrad_grouped_h16.h"
+
 /* ------------------------------------------------------------------------------------
  * Multi-GPU: the vector is sharded across one process per GPU (contiguous shards starting on multiples of
  * NNC_CHUNK elements); the exchange per Lloyd iteration is one all-reduce (SUM) of the 2K int64 sums / counts over

@@ -73,9 +73,16 @@ CBSPDX_H16_PLAN_FIELDS = CBSPDX_PLAN_FIELDS + ("dtype",)
 CBSPDC_H16_PLAN_FIELDS = CBSPDC_PLAN_FIELDS + ("dtype",)
 CBPK_H16_PLAN_LEN = 15   # nnc_cbpk_h16_plan (include/nnc_cbpk_h16.h): the float32 packed fields, then the dtype; path is CBMM_MFMA for m > 16
 CBPK_H16_PLAN_FIELDS = CBPK_PLAN_FIELDS + ("dtype",)
+CBGRAD_GROUPED_H16_PLAN_LEN = 18   # nnc_cbmm_grouped_*_h16_plan and nnc_cbpk_grouped_*_h16_plan: the ungrouped half fields, then the groups and the tables / sets held in LDS
+_CBGRAD_GROUPED_H16_TAIL = _CBGRAD_GROUPED_TAIL + ("held",)
+CBDX_GROUPED_H16_PLAN_FIELDS = CBDX_H16_PLAN_FIELDS + _CBGRAD_GROUPED_H16_TAIL
+CBDC_GROUPED_H16_PLAN_FIELDS = CBDC_H16_PLAN_FIELDS + _CBGRAD_GROUPED_H16_TAIL
 CBPKGRAD_H16_PLAN_LEN = 13   # nnc_cbpk_dx_h16_plan / nnc_cbpk_dc_h16_plan: the float32 packed fields, then the dtype
 CBPKDX_H16_PLAN_FIELDS = CBPKDX_PLAN_FIELDS + ("dtype",)
 CBPKDC_H16_PLAN_FIELDS = CBPKDC_PLAN_FIELDS + ("dtype",)
+# nnc_cbpk_grouped_dx_h16_plan / _dc_h16_plan: the ungrouped packed half fields, then the groups (CBGRAD_GROUPED_H16_PLAN_LEN values too)
+CBPKDX_GROUPED_H16_PLAN_FIELDS = CBPKDX_H16_PLAN_FIELDS + _CBGRAD_GROUPED_H16_TAIL
+CBPKDC_GROUPED_H16_PLAN_FIELDS = CBPKDC_H16_PLAN_FIELDS + _CBGRAD_GROUPED_H16_TAIL
 
 
 class NativeLibraryError(RuntimeError):
@@ -348,6 +355,25 @@ PACKED_H16_SIGNATURES = {
     "nnc_cbpk_dc_h16": (c_int, [c_void_p, c_void_p, c_int, c_i64, c_i64, c_void_p, c_i64, c_int, c_i64, c_i32, c_void_p, c_i32, c_void_p, c_i64, c_void_p]),
 }
 
+# name -> (restype, argtypes); every symbol include/nnc_cbgrad_grouped_h16.h declares (the backward pass of the group-wise layers, byte and
+# packed indices, on bf16 / fp16 activations, again a header of its own that nnc.h includes).  Required and bound by load() as SIGNATURES are.
+GROUPED_H16_GRAD_SIGNATURES = {
+    "nnc_cbmm_grouped_dx_h16_workspace_bytes": (c_i64, [c_i64, c_i64, c_i64]),
+    "nnc_cbmm_grouped_dx_h16_plan": (c_int, [c_int, c_i64, c_i64, c_i64, c_i32, c_i64, c_i32, ctypes.c_uint64, ctypes.POINTER(c_i64)]),
+    "nnc_cbmm_grouped_dx_h16": (c_int, [c_void_p, c_int, c_i64, c_i64, c_void_p, c_i64, c_void_p, c_i32, c_i64, c_void_p, c_int, c_void_p, c_i64, c_void_p]),
+    "nnc_cbmm_grouped_dc_h16_workspace_bytes": (c_i64, [c_i64, c_i64, c_i64, c_i32, c_i64]),
+    "nnc_cbmm_grouped_dc_h16_plan": (c_int, [c_int, c_i64, c_i64, c_i64, c_i32, c_i64, c_i32, ctypes.c_uint64, ctypes.POINTER(c_i64)]),
+    "nnc_cbmm_grouped_dc_h16": (c_int, [c_void_p, c_void_p, c_int, c_i64, c_i64, c_void_p, c_i64, c_i32, c_i64, c_void_p, c_i32, c_void_p, c_i64, c_void_p]),
+    "nnc_cbpk_grouped_dx_h16_workspace_bytes": (c_i64, [c_i64, c_i64, c_i64, c_int]),
+    "nnc_cbpk_grouped_dx_h16_plan": (c_int, [c_int, c_i64, c_i64, c_i64, c_int, c_i32, c_i64, c_i32, ctypes.POINTER(c_i64)]),
+    "nnc_cbpk_grouped_dx_h16": (c_int, [c_void_p, c_int, c_i64, c_i64, c_void_p, c_i64, c_int, c_i64, c_void_p, c_i32, c_i64, c_void_p, c_int, c_void_p, c_i64,
+                                        c_void_p]),
+    "nnc_cbpk_grouped_dc_h16_workspace_bytes": (c_i64, [c_i64, c_i64, c_i64, c_int, c_i32, c_i64]),
+    "nnc_cbpk_grouped_dc_h16_plan": (c_int, [c_int, c_i64, c_i64, c_i64, c_int, c_i32, c_i64, c_i32, ctypes.POINTER(c_i64)]),
+    "nnc_cbpk_grouped_dc_h16": (c_int, [c_void_p, c_void_p, c_int, c_i64, c_i64, c_void_p, c_i64, c_int, c_i64, c_i32, c_i64, c_void_p, c_i32, c_void_p, c_i64,
+                                        c_void_p]),
+}
+
 # exported only by the diagnostics build (NNC_DIAG=1: libnnc_hip_diag.so, see build.py); bound when present
 DIAG_SIGNATURES = {
     "nnc_debug_set_ablation": (c_int, [c_int]),
@@ -380,7 +406,7 @@ def load():
         L = ctypes.CDLL(path)
     except OSError as e:  # pragma: no cover - depends on the machine
         raise NativeLibraryError(f"cannot load {path}: {e}; there is no CPU fallback") from e
-    for name, (res, args) in list(SIGNATURES.items()) + list(GROUPED_GRAD_SIGNATURES.items()) + list(H16_GRAD_SIGNATURES.items()) + list(GROUPED_PACKED_GRAD_SIGNATURES.items()) + list(SPARSE_H16_SIGNATURES.items()) + list(SPARSE_H16_GRAD_SIGNATURES.items()) + list(PACKED_H16_SIGNATURES.items()):
+    for name, (res, args) in list(SIGNATURES.items()) + list(GROUPED_GRAD_SIGNATURES.items()) + list(H16_GRAD_SIGNATURES.items()) + list(GROUPED_PACKED_GRAD_SIGNATURES.items()) + list(SPARSE_H16_SIGNATURES.items()) + list(SPARSE_H16_GRAD_SIGNATURES.items()) + list(PACKED_H16_SIGNATURES.items()) + list(GROUPED_H16_GRAD_SIGNATURES.items()):
         try:
             fn = getattr(L, name)
         except AttributeError as e:

@@ -284,7 +284,7 @@ class Trainer(ABC):
         return self._tune_centres(_HalfActivations(net, activation_dtype), models, train_dataset, test_dataset, epochs, learning_rate)
 
     def fine_tune_grouped(self, train_dataset: LeNetDataset, test_dataset: LeNetDataset, epochs: int, learning_rate: float = 1e-3,
-                          packed=False) -> List[float]:
+                          packed=False, activation_dtype=None) -> List[float]:
         """fine_tune_compressed's loop on ``compressed.compress_network_trainable_grouped(..., packed=packed)``: the Dense layers
         quantized with ``group_rows`` train their (G, K) centres through ops.grouped_codebook_linear (neither W
         nor dW is built), every other quantized tensor trains as in fine_tune_compressed(sparse=False, packed=False).  ``packed``
@@ -292,14 +292,29 @@ class Trainer(ABC):
         (ops.grouped_packed_codebook_linear), every one or where that form is smaller.  At the end a
         GroupedModel's ``cluster_centers_`` gets the tuned (G, K), each of its ``models[q].cluster_centers_`` the first entries that
         are that group's own (not the zero padding of a shorter codebook), and the float kernel is re-decoded group by group, so
-        compressed_network(), store_report and load_network see the tuned centres.  Returns the accuracy per epoch."""
+        compressed_network(), store_report and load_network see the tuned centres.  Returns the accuracy per epoch.
+        ``activation_dtype``: None (float32), torch.bfloat16 or torch.float16 (with any ``packed``): the network is built with half_inputs=True, its input is cast to the dtype and its output back to float32 before
+        the loss, as in fine_tune_compressed; centres, bias and their gradients stay float32, and the write-back and the re-decode
+        are the same.  A layer with weights that takes no half input is a ValueError."""
         models = getattr(self, "quantized_models_by_layer", None)
         if not models:
             raise RuntimeError("fine_tune_grouped needs a quantized network: call quantize first")
         from .. import compressed
 
-        net = compressed.compress_network_trainable_grouped(self.neural_network, models, packed=packed)
-        return self._tune_centres(net, models, train_dataset, test_dataset, epochs, learning_rate)
+        if activation_dtype is None:
+            net = compressed.compress_network_trainable_grouped(self.neural_network, models, packed=packed)
+            return self._tune_centres(net, models, train_dataset, test_dataset, epochs, learning_rate)
+        if activation_dtype not in (torch.bfloat16, torch.float16):
+            raise ValueError(f"activation_dtype must be None, torch.bfloat16 or torch.float16, got {activation_dtype}")
+        net = compressed.compress_network_trainable_grouped(self.neural_network, models, packed=packed, half_inputs=True)
+        half_layers = (compressed._TrainableCodebookLayer, compressed.TrainableGroupedCompressedDense, compressed.TrainableGroupedPackedCompressedDense)
+        for name, layer in net.get_config().items():
+            takes_half = isinstance(layer, half_layers) and layer.half_inputs
+            if not takes_half and (hasattr(layer, "kernel") or next(layer.parameters(), None) is not None):
+                raise ValueError(f"activation_dtype={activation_dtype}: layer {name!r} ({type(layer).__name__}) is not a byte-form or group-wise "
+                                 "trainable layer built with half_inputs (its kernel passed through unquantized, or it has no half-precision "
+                                 "backward pass)")
+        return self._tune_centres(_HalfActivations(net, activation_dtype), models, train_dataset, test_dataset, epochs, learning_rate)
 
     def _tune_centres(self, net, models, train_dataset, test_dataset, epochs, learning_rate) -> List[float]:
         """The loop of fine_tune_compressed / fine_tune_grouped on the trainable network ``net`` of this trainer's quantized

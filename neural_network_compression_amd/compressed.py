@@ -39,7 +39,9 @@ csrc/nnc_cbspgrad_h16.hip, DESIGN.md section 24: ``compress_network_trainable(..
 (ops.sparse_codebook_matmul -> nnc_cbsp_h16, csrc/nnc_cbsp_h16.hip), path and output dtype by the input's dtype.
 The four packed layers built with ``half_inputs=True`` (``packed_half_inputs=True`` in compress_network / load_network /
 Trainer.compressed_network / compress_network_trainable) run and train on them as well (ops.packed_codebook_matmul /
-ops.packed_codebook_linear -> csrc/nnc_cbpk_h16.hip); the grouped layers' backward passes stay float32.
+ops.packed_codebook_linear -> csrc/nnc_cbpk_h16.hip).  The two grouped trainable layers built with
+``half_inputs=True`` (compress_network_trainable_grouped(..., half_inputs=True), Trainer.fine_tune_grouped(..., activation_dtype=))
+train on them too (csrc/nnc_cbgrad_grouped_h16.hip, csrc/nnc_cbpkgrad_grouped_h16.hip).
 
 ``GroupedCompressedDense`` runs a Dense layer whose kernel has one codebook per block of ``group_rows`` input rows
 (utility.get_quantized_weight_grouped, Trainer.quantize(..., group_rows=); ops.grouped_codebook_matmul, csrc/nnc_cbmm_grouped.hip,
@@ -436,10 +438,13 @@ class TrainableGroupedCompressedDense(_DenseHalf, _TrainableCentres):
     """GroupedCompressedDense with trainable centres (ops.grouped_codebook_linear): labels (kdim * ncols uint8
     indices, row-major) a buffer, centers a float32 (G, K) nn.Parameter, counts the (G, K) histogram of every group's indices, so
     kernel_sq_sum() = sum counts * centers^2; the bias of _TrainableCentres.  The backward forms dx and the (G, K) centroid
-    gradient from the codebooks and the indices (csrc/nnc_cbgrad_grouped.hip): W and dW are never built.  float32 inputs only."""
+    gradient from the codebooks and the indices (csrc/nnc_cbgrad_grouped.hip): W and dW are never built.  ``half_inputs=True`` lets
+    the layer train on bfloat16 / float16 inputs (csrc/nnc_cbgrad_grouped_h16.hip): the output and the input
+    gradient have the input's dtype, centres and bias stay float32 with float32 gradients.  Without it a half input raises
+    ``TypeError``."""
 
     def __init__(self, kdim: int, ncols: int, group_rows: int, labels: torch.Tensor, centers: torch.Tensor, bias: torch.Tensor | None = None,
-                 bias_codes=None, activation=None):
+                 bias_codes=None, activation=None, half_inputs: bool = False):
         super().__init__()
         if labels.numel() != kdim * ncols:
             raise ValueError(f"{labels.numel()} indices for a {kdim} x {ncols} weight matrix")
@@ -449,32 +454,34 @@ class TrainableGroupedCompressedDense(_DenseHalf, _TrainableCentres):
         if centers.dim() != 2 or centers.shape[0] != groups:
             raise ValueError(f"centers must have shape ({groups}, K) for {kdim} rows in groups of {group_rows}, got {tuple(centers.shape)}")
         self.kdim, self.ncols, self.group_rows = int(kdim), int(ncols), int(group_rows)
+        self.half_inputs = bool(half_inputs)
         self.register_buffer("labels", labels.reshape(-1))
         counts = _group_counts(self.labels, self.group_rows * self.ncols, groups, centers.shape[1])
         self._init_centres(self.labels, centers, ncols, bias, bias_codes, activation, counts=counts)
 
     @classmethod
-    def from_dense(cls, dense, grouped_model, bias_model=None) -> "TrainableGroupedCompressedDense":
+    def from_dense(cls, dense, grouped_model, bias_model=None, half_inputs: bool = False) -> "TrainableGroupedCompressedDense":
         """From a Dense layer and the GroupedModel of its kernel; a quantized bias keeps its codes, a raw one stays frozen."""
         _require_model(grouped_model)
         kin, kout = dense.kernel.shape
         dev = dense.kernel.device
         centers = torch.from_numpy(np.ascontiguousarray(grouped_model.cluster_centers_, dtype=np.float32)).to(dev)
         bias, bias_codes = (None, _codes(bias_model, dev)) if bias_model is not None else (dense.bias, None)
-        return cls(kin, kout, grouped_model.group_rows, grouped_model.labels_compact_, centers, bias, bias_codes, dense.activation)
+        return cls(kin, kout, grouped_model.group_rows, grouped_model.labels_compact_, centers, bias, bias_codes, dense.activation, half_inputs)
 
     @classmethod
-    def from_codes(cls, kdim, ncols, group_rows, labels, centers, bias=None, bias_codes=None, activation=None) -> "TrainableGroupedCompressedDense":
-        return cls(kdim, ncols, group_rows, labels, centers, bias, bias_codes, activation)
+    def from_codes(cls, kdim, ncols, group_rows, labels, centers, bias=None, bias_codes=None, activation=None,
+                   half_inputs: bool = False) -> "TrainableGroupedCompressedDense":
+        return cls(kdim, ncols, group_rows, labels, centers, bias, bias_codes, activation, half_inputs)
 
     @classmethod
-    def from_grouped(cls, layer: GroupedCompressedDense) -> "TrainableGroupedCompressedDense":
+    def from_grouped(cls, layer: GroupedCompressedDense, half_inputs: bool = False) -> "TrainableGroupedCompressedDense":
         """The trainable layer of a GroupedCompressedDense: the same indices and centres, its decoded bias frozen."""
-        return cls(layer.kdim, layer.ncols, layer.group_rows, layer.labels, layer.centers, layer.bias, None, layer.activation)
+        return cls(layer.kdim, layer.ncols, layer.group_rows, layer.labels, layer.centers, layer.bias, None, layer.activation, half_inputs)
 
     def _matmul(self, x: torch.Tensor) -> torch.Tensor:
         return self._activate(ops.grouped_codebook_linear(x, self.labels, self.centers, self.kdim, self.ncols, self.group_rows,
-                                                          bias=self.current_bias(), relu=self._fused_relu))
+                                                          bias=self.current_bias(), relu=self._fused_relu, half_inputs=self.half_inputs))
 
     def nbytes(self) -> int:
         return self._nbytes(self.labels)
@@ -851,11 +858,14 @@ class TrainableGroupedPackedCompressedDense(_DenseHalf, _PackedForm, _TrainableC
     nn.Parameter, counts the (G, K) histogram of every group's indices taken from the labels before packing, so kernel_sq_sum() is
     TrainableGroupedCompressedDense's bit for bit; the bias of _TrainableCentres.  The backward forms dx and the (G, K) centroid
     gradient from the codebooks and the packed rows (csrc/nnc_cbpkgrad_grouped.hip): the indices are never unpacked, W and dW never
-    built, and no byte-per-weight tensor stays resident while training.  float32 inputs only."""
+    built, and no byte-per-weight tensor stays resident while training.  ``half_inputs=True`` lets the layer train on bfloat16 /
+    float16 inputs (csrc/nnc_cbpkgrad_grouped_h16.hip), as TrainableGroupedCompressedDense; without it a half
+    input raises ``TypeError``."""
 
     def __init__(self, codes: ops.PackedCodes, group_rows: int, labels: torch.Tensor, centers: torch.Tensor, bias: torch.Tensor | None = None,
-                 bias_codes=None, activation=None):
+                 bias_codes=None, activation=None, half_inputs: bool = False):
         super().__init__()
+        self.half_inputs = bool(half_inputs)
         groups = max(1, -(-codes.kdim // int(group_rows)))
         if centers.dim() != 2 or tuple(centers.shape) != (groups, codes.k):
             raise ValueError(f"centers must have shape ({groups}, {codes.k}) for {codes.kdim} rows in groups of {group_rows} and indices into "
@@ -868,36 +878,38 @@ class TrainableGroupedPackedCompressedDense(_DenseHalf, _PackedForm, _TrainableC
         self._init_centres(None, centers, codes.ncols, bias, bias_codes, activation, counts=counts)
 
     @classmethod
-    def from_dense(cls, dense, grouped_model, bias_model=None, bits=None) -> "TrainableGroupedPackedCompressedDense":
+    def from_dense(cls, dense, grouped_model, bias_model=None, bits=None, half_inputs: bool = False) -> "TrainableGroupedPackedCompressedDense":
         """From a Dense layer and the GroupedModel of its kernel, K <= 16; a quantized bias keeps its codes, a raw one stays frozen."""
         _require_model(grouped_model)
         kin, kout = dense.kernel.shape
         dev = dense.kernel.device
         centers = torch.from_numpy(np.ascontiguousarray(grouped_model.cluster_centers_, dtype=np.float32)).to(dev)
         bias, bias_codes = (None, _codes(bias_model, dev)) if bias_model is not None else (dense.bias, None)
-        return cls.from_codes(kin, kout, grouped_model.group_rows, grouped_model.labels_compact_, centers, bias, bias_codes, dense.activation, bits)
+        return cls.from_codes(kin, kout, grouped_model.group_rows, grouped_model.labels_compact_, centers, bias, bias_codes, dense.activation, bits,
+                              half_inputs)
 
     @classmethod
     def from_codes(cls, kdim, ncols, group_rows, labels, centers, bias=None, bias_codes=None, activation=None,
-                   bits=None) -> "TrainableGroupedPackedCompressedDense":
+                   bits=None, half_inputs: bool = False) -> "TrainableGroupedPackedCompressedDense":
         if centers.dim() != 2:
             raise ValueError(f"centers must have shape (G, K), got {tuple(centers.shape)}")
-        return cls(ops.pack_codes(labels, kdim, ncols, centers.shape[1], bits), group_rows, labels, centers, bias, bias_codes, activation)
+        return cls(ops.pack_codes(labels, kdim, ncols, centers.shape[1], bits), group_rows, labels, centers, bias, bias_codes, activation, half_inputs)
 
     @classmethod
-    def from_grouped(cls, layer: GroupedCompressedDense, bits=None) -> "TrainableGroupedPackedCompressedDense":
+    def from_grouped(cls, layer: GroupedCompressedDense, bits=None, half_inputs: bool = False) -> "TrainableGroupedPackedCompressedDense":
         """The trainable packed layer of a GroupedCompressedDense: its indices packed, the same centres, its decoded bias frozen."""
-        return cls.from_codes(layer.kdim, layer.ncols, layer.group_rows, layer.labels, layer.centers, layer.bias, None, layer.activation, bits)
+        return cls.from_codes(layer.kdim, layer.ncols, layer.group_rows, layer.labels, layer.centers, layer.bias, None, layer.activation, bits,
+                              half_inputs)
 
     @classmethod
-    def from_grouped_packed(cls, layer: GroupedPackedCompressedDense) -> "TrainableGroupedPackedCompressedDense":
+    def from_grouped_packed(cls, layer: GroupedPackedCompressedDense, half_inputs: bool = False) -> "TrainableGroupedPackedCompressedDense":
         """The trainable layer of a GroupedPackedCompressedDense on the same packed buffer; the counts come from a temporary unpack
         (nnc_cbpk_unpack), which is dropped afterwards."""
-        return cls(layer.codes, layer.group_rows, layer.codes.to_dense(), layer.centers, layer.bias, None, layer.activation)
+        return cls(layer.codes, layer.group_rows, layer.codes.to_dense(), layer.centers, layer.bias, None, layer.activation, half_inputs)
 
     def _matmul(self, x: torch.Tensor) -> torch.Tensor:
         return self._activate(ops.grouped_packed_codebook_linear(x, self.codes, self.centers, self.group_rows, bias=self.current_bias(),
-                                                                 relu=self._fused_relu))
+                                                                 relu=self._fused_relu, half_inputs=self.half_inputs))
 
     def nbytes(self) -> int:
         return self._nbytes(self.packed)
@@ -1098,25 +1110,30 @@ def compress_network_trainable(network: nn.Module, models_by_layer, sparse=False
     return _compress_each(network, models_by_layer, make, grouped="trainable=True")
 
 
-def compress_network_trainable_grouped(network: nn.Module, models_by_layer, packed=False) -> nn.Module:
+def compress_network_trainable_grouped(network: nn.Module, models_by_layer, packed=False, half_inputs=False) -> nn.Module:
     """compress_network_trainable(network, models_by_layer) -- the byte forms -- in which every layer whose kernel model is a
     utility.GroupedModel becomes a TrainableGroupedCompressedDense instead of raising.  On a network
     without grouped layers it returns what compress_network_trainable returns.  ``packed``: False (the byte grouped layers), True
     (a TrainableGroupedPackedCompressedDense, DESIGN.md section 20, for every grouped layer of at most 16 centres per group) or
     "auto" (that class only where the packed form holds fewer resident bytes; on equal bytes the byte form stays); anything else
-    is a ValueError.  Ungrouped layers stay in the byte trainable forms either way.  Trainer.fine_tune_grouped trains it."""
+    is a ValueError.  Ungrouped layers stay in the byte trainable forms either way.  Trainer.fine_tune_grouped trains it.
+    ``half_inputs=True``: the grouped layers of either form and the ungrouped byte-form layers are built with half_inputs=True and
+    train on bfloat16 / float16 inputs (DESIGN.md sections 22 and 26)."""
+    half = dict(half_inputs=True) if half_inputs else {}
     if packed is False:
-        make_grouped = TrainableGroupedCompressedDense.from_dense
+        def make_grouped(layer, wm, bm):
+            return TrainableGroupedCompressedDense.from_dense(layer, wm, bm, **half)
     elif packed is True or packed == "auto":
         def make_grouped(layer, wm, bm):
             k = wm.cluster_centers_.shape[1]
             kin, kout = layer.kernel.shape
             if k > PACKED_MAX_K or (packed == "auto" and ops.packed_nbytes(kin, kout, ops.packed_bits(k)) >= kin * kout):
-                return TrainableGroupedCompressedDense.from_dense(layer, wm, bm)
-            return TrainableGroupedPackedCompressedDense.from_dense(layer, wm, bm)
+                return TrainableGroupedCompressedDense.from_dense(layer, wm, bm, **half)
+            return TrainableGroupedPackedCompressedDense.from_dense(layer, wm, bm, **half)
     else:
         raise ValueError(f"packed must be False, True or 'auto', got {packed!r}")
-    return _compress_each(network, models_by_layer, lambda layer, wm, bm: _trainable(layer, wm, bm), make_grouped=make_grouped)
+    return _compress_each(network, models_by_layer, lambda layer, wm, bm: _trainable(layer, wm, bm, half_inputs=bool(half_inputs)),
+                          make_grouped=make_grouped)
 
 
 def _compress_each(network: nn.Module, models_by_layer, make, grouped=None, make_grouped=GroupedCompressedDense.from_dense) -> nn.Module:

@@ -19,35 +19,11 @@
 //             for every element whose scaled value is a normal bf16); fp16 operands are not scaled.  The epilogue bins the
 //             accumulators: cbdc_fix, the 64-bit LDS atomicAdd into the replicated bins, cbdc_flush.
 // Everything past m, kdim, ncols and the end of a split is zero in both images, never memory.  No float atomics; no host read.
-#include "nnc_cbmfma.hpp"
+#include "nnc_cbdxm.hpp"
 #include "nnc_cbtile.hpp"
 
 // ------------------------------------------------------------------ dx, m > 16
-// The n (<= 16) labels p[0 .. n), packed as they lie in memory (little endian) into 4 * sizeof(LT) words; the absent ones 0.  p is
-// dereferenced only where n > 0.
-template <typename LT>
-__device__ __forceinline__ void dxm_load_labels(const LT *p, int n, uint32_t (&w)[4 * sizeof(LT)])
-{
-    constexpr int LB = sizeof(LT), NW = 4 * LB, PER = 4 / LB;
-    const uintptr_t a = reinterpret_cast<uintptr_t>(p);
-    if (n == 16 && a % 16 == 0) {
-#pragma unroll
-        for (int q = 0; q < LB; ++q) {
-            const uint4 v = reinterpret_cast<const uint4 *>(p)[q];
-            w[4 * q] = v.x, w[4 * q + 1] = v.y, w[4 * q + 2] = v.z, w[4 * q + 3] = v.w;
-        }
-    } else if (n == 16 && a % 4 == 0) {
-#pragma unroll
-        for (int d = 0; d < NW; ++d) w[d] = reinterpret_cast<const uint32_t *>(p)[d];
-    } else {
-#pragma unroll
-        for (int d = 0; d < NW; ++d) w[d] = 0u;
-#pragma unroll
-        for (int j = 0; j < 16; ++j)
-            if (j < n) w[j / PER] |= (uint32_t)p[j] << (8 * LB * (j % PER));
-    }
-}
-
+// (the label load, dxm_load_labels, is nnc_cbdxm.hpp's: the group-wise kernel of nnc_cbgrad_grouped_h16.hip runs it too)
 // grid (kdim tiles * m tiles, splits of ncols), HM_THREADS threads.  `out` is dx (direct 1: float32, 2: XT) or the float32 partials
 // [split][m][kdim] (direct 0).  cols_per_split is a multiple of HM_BK.
 template <typename XT, typename LT, bool XVEC>

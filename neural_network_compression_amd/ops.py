@@ -637,8 +637,9 @@ def codebook_linear(x: torch.Tensor, labels: torch.Tensor, centers: torch.Tensor
 
 
 def _grouped_grad_args(who: str, g: torch.Tensor, labels: torch.Tensor, kdim: int, ncols: int, k: int, group_rows: int):
-    """The grouped form's checks of g, the indices and the groups -> (lead, m, G) of g, G as the layers count it (>= 1)."""
-    _require_cuda(g, "g", torch.float32)
+    """The grouped form's checks of g, the indices and the groups -> (lead, m, G) of g, G as the layers count it (>= 1).  g: float32,
+    or bfloat16 / float16."""
+    _require_cuda(g, "g", g.dtype if isinstance(g, torch.Tensor) and g.dtype in _H16_DT else torch.float32)
     _require_cuda(labels, "labels")
     if labels.dtype != torch.uint8:
         raise TypeError(f"{who} takes uint8 labels (K <= 256 per group), got {labels.dtype}")
@@ -652,11 +653,16 @@ def _grouped_grad_args(who: str, g: torch.Tensor, labels: torch.Tensor, kdim: in
     return lead, m, max(-(-kdim // group_rows), 1)
 
 
-def grouped_codebook_matmul_dx(g: torch.Tensor, labels: torch.Tensor, centers: torch.Tensor, kdim: int, ncols: int, group_rows: int) -> torch.Tensor:
+def grouped_codebook_matmul_dx(g: torch.Tensor, labels: torch.Tensor, centers: torch.Tensor, kdim: int, ncols: int, group_rows: int,
+                               out_dtype=None) -> torch.Tensor:
     """dx = g @ W^T with W[i, o] = centers[i // group_rows][labels[i * ncols + o]] (include/nnc.h, nnc_cbmm_grouped_dx_f32; DESIGN.md
     section 19): the input gradient of grouped_codebook_matmul.  g: float32 (..., ncols); labels, centers (G, K) and group_rows as
     grouped_codebook_matmul.  Returns float32 (..., kdim); the columns of a group are, bit for bit, those codebook_matmul_dx gives
-    with that group's table.  No host read."""
+    with that group's table.  No host read.
+    A bfloat16 or float16 g takes nnc_cbmm_grouped_dx_h16: centers stay float32 and are rounded to g's dtype as
+    the grouped forward rounds them; the result has ``out_dtype``: None (g's dtype, the float32 value rounded once) or torch.float32,
+    and the same identity holds against the half codebook_matmul_dx.  As in codebook_matmul_dx, g's own dtype is asked for with None,
+    not by naming it: any other ``out_dtype`` than None or torch.float32 is a ``TypeError``, for a float32 g too."""
     kdim, ncols, group_rows = int(kdim), int(ncols), int(group_rows)
     _require_cuda(centers, "centers", torch.float32)
     k = int(centers.shape[1]) if centers.dim() == 2 and 1 <= centers.shape[1] <= 256 else 0
@@ -664,7 +670,17 @@ def grouped_codebook_matmul_dx(g: torch.Tensor, labels: torch.Tensor, centers: t
     if not k or centers.shape[0] != groups:
         raise ValueError(f"centers must have shape ({groups}, K <= 256) for kdim {kdim} and group_rows {group_rows}, got {tuple(centers.shape)}")
     _one_device("g, labels and centers", g, labels, centers)
+    if out_dtype not in (None, torch.float32):
+        raise TypeError(f"out_dtype must be None or torch.float32, got {out_dtype}")
     L = nat.load()
+    if g.dtype in _H16_DT:
+        dx_dtype = g.dtype if out_dtype is None else out_dtype
+        dx = torch.empty(lead + (kdim,), dtype=dx_dtype, device=g.device)
+        ws_bytes = int(L.nnc_cbmm_grouped_dx_h16_workspace_bytes(m, kdim, ncols))
+        ws = _workspace(ws_bytes, g.device)
+        nat.check(L.nnc_cbmm_grouped_dx_h16(_ptr(g), _H16_DT[g.dtype], m, kdim, _ptr(labels), ncols, _ptr(centers), k, group_rows, _ptr(dx),
+                                            _H16_DT.get(dx_dtype, nat.DT_F32), _ptr(ws), ws_bytes, _stream(g)))
+        return dx
     dx = torch.empty(lead + (kdim,), dtype=torch.float32, device=g.device)
     ws_bytes = int(L.nnc_cbmm_grouped_dx_workspace_bytes(m, kdim, ncols))
     ws = _workspace(ws_bytes, g.device)
@@ -677,13 +693,23 @@ def grouped_codebook_centroid_grad(x: torch.Tensor, g: torch.Tensor, labels: tor
     """dc[q, j] = sum over the (i, o) with i // group_rows = q and labels[i * ncols + o] = j of (x^T g)[i, o] (include/nnc.h,
     nnc_cbmm_grouped_dc_f32): the centroid gradient of grouped_codebook_matmul, the kdim x ncols dW never written.  x: float32
     (..., kdim), g: float32 (..., ncols) with the same leading shape.  Exact fixed-point sums with the shift of the ungrouped call
-    (cbgrad_shift on the plan's terms_log2).  Returns ``dtype`` (float64 or float32) (G, k).  No host read."""
+    (cbgrad_shift on the plan's terms_log2).  Returns ``dtype`` (float64 or float32) (G, k).  No host read.
+    x and g both bfloat16 or both float16 take nnc_cbmm_grouped_dc_h16: dW is formed as the half
+    codebook_centroid_grad forms it, and the result equals that call on the 16-bit labels q * k + label, bit for bit."""
     kdim, ncols, k, group_rows = int(kdim), int(ncols), int(k), int(group_rows)
-    _require_cuda(x, "x", torch.float32)
+    if isinstance(x, torch.Tensor) and isinstance(g, torch.Tensor) and x.dtype != g.dtype and (x.dtype in _H16_DT or g.dtype in _H16_DT):
+        raise TypeError(f"x and g must have one dtype, got {x.dtype} and {g.dtype}")
+    _require_cuda(x, "x", x.dtype if isinstance(x, torch.Tensor) and x.dtype in _H16_DT else torch.float32)
     lead, m, groups = _grouped_grad_args("grouped_codebook_centroid_grad", g, labels, kdim, ncols, k, group_rows)
     _dc_args(x, lead, kdim, "x, g and labels", labels, g, dtype)
     L = nat.load()
     dc = torch.empty((groups, k), dtype=dtype, device=x.device)
+    if x.dtype in _H16_DT:
+        ws_bytes = int(L.nnc_cbmm_grouped_dc_h16_workspace_bytes(m, kdim, ncols, k, group_rows))
+        ws = _workspace(ws_bytes, x.device)
+        nat.check(L.nnc_cbmm_grouped_dc_h16(_ptr(x), _ptr(g), _H16_DT[x.dtype], m, kdim, _ptr(labels), ncols, k, group_rows, _ptr(dc),
+                                            1 if dtype == torch.float64 else 0, _ptr(ws), ws_bytes, _stream(x)))
+        return dc
     ws_bytes = int(L.nnc_cbmm_grouped_dc_workspace_bytes(m, kdim, ncols, k, group_rows))
     ws = _workspace(ws_bytes, x.device)
     nat.check(L.nnc_cbmm_grouped_dc_f32(_ptr(x), _ptr(g), m, kdim, _ptr(labels), ncols, k, group_rows, _ptr(dc), 1 if dtype == torch.float64 else 0,
@@ -703,13 +729,31 @@ def cbmm_grouped_dc_plan(m: int, kdim: int, ncols: int, k: int, group_rows: int,
     return _plan(nat.load().nnc_cbmm_grouped_dc_plan, nat.CBDC_GROUPED_PLAN_FIELDS, m, kdim, ncols, k, group_rows, cus, labels_addr)
 
 
+def cbmm_grouped_dx_h16_plan(dtype, m: int, kdim: int, ncols: int, k: int, group_rows: int, cus: int, labels_addr: int = 0) -> dict:
+    """Host: the plan nnc_cbmm_grouped_dx_h16 follows for g of ``dtype`` (torch.bfloat16 / torch.float16) on a device with ``cus``
+    compute units (include/nnc_cbgrad_grouped_h16.h), as a dict keyed by _native.CBDX_GROUPED_H16_PLAN_FIELDS.  No device needed."""
+    return _plan(nat.load().nnc_cbmm_grouped_dx_h16_plan, nat.CBDX_GROUPED_H16_PLAN_FIELDS, _h16_dt(dtype), m, kdim, ncols, k, group_rows, cus, labels_addr)
+
+
+def cbmm_grouped_dc_h16_plan(dtype, m: int, kdim: int, ncols: int, k: int, group_rows: int, cus: int, labels_addr: int = 0) -> dict:
+    """Host: the plan nnc_cbmm_grouped_dc_h16 follows for x and g of ``dtype`` (include/nnc_cbgrad_grouped_h16.h), as a dict keyed by
+    _native.CBDC_GROUPED_H16_PLAN_FIELDS.  No device needed."""
+    return _plan(nat.load().nnc_cbmm_grouped_dc_h16_plan, nat.CBDC_GROUPED_H16_PLAN_FIELDS, _h16_dt(dtype), m, kdim, ncols, k, group_rows, cus, labels_addr)
+
+
 def grouped_codebook_linear(x: torch.Tensor, labels: torch.Tensor, centers: torch.Tensor, kdim: int, ncols: int, group_rows: int,
-                            bias: torch.Tensor | None = None, relu: bool = False) -> torch.Tensor:
+                            bias: torch.Tensor | None = None, relu: bool = False, half_inputs: bool = False) -> torch.Tensor:
     """grouped_codebook_matmul with gradients for x, centers (G, K) and bias, through the autograd Function of codebook_linear.
     The forward is the same float32 nnc_cbmm_grouped call (under no_grad the bits of grouped_codebook_matmul); the backward runs
     grouped_codebook_matmul_dx only if x needs a gradient and grouped_codebook_centroid_grad (float32) only if centers does.  The
-    ReLU mask and the bias gradient are codebook_linear's.  No host read."""
-    _require_f32_x(x, "grouped_codebook_linear")
+    ReLU mask and the bias gradient are codebook_linear's.  No host read.
+    ``half_inputs=True`` lets a bfloat16 or float16 x through: the forward is the grouped half forward with
+    x's dtype out, dx has x's dtype, the gradients of the float32 centers and bias are float32.  Without it a half x raises
+    ``TypeError`` as before; a half ``centers`` or ``bias`` always does."""
+    if not half_inputs:
+        _require_f32_x(x, "grouped_codebook_linear")
+    elif isinstance(x, torch.Tensor) and x.dtype in _H16_DT:
+        _require_centers_bias(centers, bias)
     if isinstance(labels, torch.Tensor) and labels.dtype != torch.uint8:
         raise TypeError(f"grouped_codebook_linear takes uint8 labels (K <= 256 per group), got {labels.dtype}")
     kdim, ncols, group_rows = int(kdim), int(ncols), int(group_rows)
@@ -1262,20 +1306,32 @@ def _grouped_packed_args(codes, centers: torch.Tensor, group_rows: int) -> int:
     return groups
 
 
-def grouped_packed_codebook_matmul_dx(g: torch.Tensor, codes: PackedCodes, centers: torch.Tensor, group_rows: int) -> torch.Tensor:
+def grouped_packed_codebook_matmul_dx(g: torch.Tensor, codes: PackedCodes, centers: torch.Tensor, group_rows: int, out_dtype=None) -> torch.Tensor:
     """dx = g @ W^T with W[i, o] = centers[i // group_rows][label (i, o)] read from the 2- or 4-bit packed indices
     (include/nnc_cbpkgrad_grouped.h, nnc_cbpk_grouped_dx_f32): the input gradient of
     grouped_packed_codebook_matmul.  g: float32 (..., ncols); codes, centers (G, K) and group_rows as grouped_packed_codebook_matmul.
     Returns float32 (..., kdim); the columns of a group are, bit for bit, those packed_codebook_matmul_dx gives with that group's
-    table.  No host read."""
+    table.  No host read.
+    A bfloat16 or float16 g takes nnc_cbpk_grouped_dx_h16: bit for bit the half grouped_codebook_matmul_dx on
+    codes.to_dense(); ``out_dtype`` as there: None (g's dtype) or torch.float32, anything else a ``TypeError``, for a float32 g too."""
     group_rows = int(group_rows)
     _require_cuda(centers, "centers", torch.float32)
-    _require_cuda(g, "g", torch.float32)
+    _require_cuda(g, "g", g.dtype if isinstance(g, torch.Tensor) and g.dtype in _H16_DT else torch.float32)
     _grouped_packed_args(codes, centers, group_rows)
     lead, m = _rows(g, "g", codes.ncols)
     _one_device("g, codes and centers", g, codes.packed, centers)
+    if out_dtype not in (None, torch.float32):
+        raise TypeError(f"out_dtype must be None or torch.float32, got {out_dtype}")
     L = nat.load()
     kdim, ncols, bits = codes.kdim, codes.ncols, codes.bits
+    if g.dtype in _H16_DT:
+        dx_dtype = g.dtype if out_dtype is None else out_dtype
+        dx = torch.empty(lead + (kdim,), dtype=dx_dtype, device=g.device)
+        ws_bytes = int(L.nnc_cbpk_grouped_dx_h16_workspace_bytes(m, kdim, ncols, bits))
+        ws = _workspace(ws_bytes, g.device)
+        nat.check(L.nnc_cbpk_grouped_dx_h16(_ptr(g), _H16_DT[g.dtype], m, kdim, _ptr(codes.packed), codes.nbytes, bits, ncols, _ptr(centers), codes.k,
+                                            group_rows, _ptr(dx), _H16_DT.get(dx_dtype, nat.DT_F32), _ptr(ws), ws_bytes, _stream(g)))
+        return dx
     dx = torch.empty(lead + (kdim,), dtype=torch.float32, device=g.device)
     ws_bytes = int(L.nnc_cbpk_grouped_dx_workspace_bytes(m, kdim, ncols, bits))
     ws = _workspace(ws_bytes, g.device)
@@ -1288,16 +1344,26 @@ def grouped_packed_codebook_centroid_grad(x: torch.Tensor, g: torch.Tensor, code
     """dc[q, j] = sum over the (i, o) with i // group_rows = q whose label is j of (x^T g)[i, o] (include/nnc_cbpkgrad_grouped.h,
     nnc_cbpk_grouped_dc_f32): bit for bit grouped_codebook_centroid_grad(x, g, codes.to_dense(), codes.k, ...), the indices never
     unpacked and dW never written.  x: float32 (..., kdim), g: float32 (..., ncols) with the same leading shape.  Returns ``dtype``
-    (float64 or float32) (G, codes.k).  No host read."""
+    (float64 or float32) (G, codes.k).  No host read.
+    x and g both bfloat16 or both float16 take nnc_cbpk_grouped_dc_h16: bit for bit the half
+    grouped_codebook_centroid_grad on codes.to_dense()."""
     group_rows = int(group_rows)
-    _require_cuda(x, "x", torch.float32)
-    _require_cuda(g, "g", torch.float32)
+    if isinstance(x, torch.Tensor) and isinstance(g, torch.Tensor) and x.dtype != g.dtype and (x.dtype in _H16_DT or g.dtype in _H16_DT):
+        raise TypeError(f"x and g must have one dtype, got {x.dtype} and {g.dtype}")
+    _require_cuda(x, "x", x.dtype if isinstance(x, torch.Tensor) and x.dtype in _H16_DT else torch.float32)
+    _require_cuda(g, "g", g.dtype if isinstance(g, torch.Tensor) and g.dtype in _H16_DT else torch.float32)
     groups = _grouped_packed_args(codes, None, group_rows)
     kdim, ncols, k, bits = codes.kdim, codes.ncols, codes.k, codes.bits
     lead, m = _rows(g, "g", ncols)
     _dc_args(x, lead, kdim, "x, g and codes", codes.packed, g, dtype)
     L = nat.load()
     dc = torch.empty((groups, k), dtype=dtype, device=x.device)
+    if x.dtype in _H16_DT:
+        ws_bytes = int(L.nnc_cbpk_grouped_dc_h16_workspace_bytes(m, kdim, ncols, bits, k, group_rows))
+        ws = _workspace(ws_bytes, x.device)
+        nat.check(L.nnc_cbpk_grouped_dc_h16(_ptr(x), _ptr(g), _H16_DT[x.dtype], m, kdim, _ptr(codes.packed), codes.nbytes, bits, ncols, k, group_rows,
+                                            _ptr(dc), 1 if dtype == torch.float64 else 0, _ptr(ws), ws_bytes, _stream(x)))
+        return dc
     ws_bytes = int(L.nnc_cbpk_grouped_dc_workspace_bytes(m, kdim, ncols, bits, k, group_rows))
     ws = _workspace(ws_bytes, x.device)
     nat.check(L.nnc_cbpk_grouped_dc_f32(_ptr(x), _ptr(g), m, kdim, _ptr(codes.packed), codes.nbytes, bits, ncols, k, group_rows, _ptr(dc),
@@ -1317,16 +1383,33 @@ def cbpk_grouped_dc_plan(m: int, kdim: int, ncols: int, bits: int, k: int, group
     return _plan(nat.load().nnc_cbpk_grouped_dc_plan, nat.CBPKDC_GROUPED_PLAN_FIELDS, m, kdim, ncols, bits, k, group_rows, cus)
 
 
+def cbpk_grouped_dx_h16_plan(dtype, m: int, kdim: int, ncols: int, bits: int, k: int, group_rows: int, cus: int) -> dict:
+    """Host: the plan nnc_cbpk_grouped_dx_h16 follows for g of ``dtype`` (torch.bfloat16 / torch.float16) on a device with ``cus``
+    compute units (include/nnc_cbgrad_grouped_h16.h), as a dict keyed by _native.CBPKDX_GROUPED_H16_PLAN_FIELDS.  No device needed."""
+    return _plan(nat.load().nnc_cbpk_grouped_dx_h16_plan, nat.CBPKDX_GROUPED_H16_PLAN_FIELDS, _h16_dt(dtype), m, kdim, ncols, bits, k, group_rows, cus)
+
+
+def cbpk_grouped_dc_h16_plan(dtype, m: int, kdim: int, ncols: int, bits: int, k: int, group_rows: int, cus: int) -> dict:
+    """Host: the plan nnc_cbpk_grouped_dc_h16 follows for x and g of ``dtype`` (include/nnc_cbgrad_grouped_h16.h), as a dict keyed by
+    _native.CBPKDC_GROUPED_H16_PLAN_FIELDS.  No device needed."""
+    return _plan(nat.load().nnc_cbpk_grouped_dc_h16_plan, nat.CBPKDC_GROUPED_H16_PLAN_FIELDS, _h16_dt(dtype), m, kdim, ncols, bits, k, group_rows, cus)
+
+
 def grouped_packed_codebook_linear(x: torch.Tensor, codes: PackedCodes, centers: torch.Tensor, group_rows: int, bias: torch.Tensor | None = None,
-                                   relu: bool = False) -> torch.Tensor:
+                                   relu: bool = False, half_inputs: bool = False) -> torch.Tensor:
     """grouped_packed_codebook_matmul with gradients for x, centers (G, K) and bias, through the autograd Function of codebook_linear.
     The forward is the same float32 nnc_cbpk_grouped call (under no_grad the bits of grouped_packed_codebook_matmul, which stays
     inference only); the backward runs grouped_packed_codebook_matmul_dx only if x needs a gradient and
     grouped_packed_codebook_centroid_grad (float32) only if centers does.  The ReLU mask and the bias gradient are codebook_linear's.
-    The indices get no gradient.  No host read."""
+    The indices get no gradient.  No host read.
+    ``half_inputs=True`` lets a bfloat16 or float16 x through, as in grouped_codebook_linear; without it a half
+    x raises ``TypeError`` as before."""
     if not isinstance(codes, PackedCodes):
         raise TypeError("codes must be a PackedCodes (ops.pack_codes)")
-    _require_f32_x(x, "grouped_packed_codebook_linear")
+    if not half_inputs:
+        _require_f32_x(x, "grouped_packed_codebook_linear")
+    elif isinstance(x, torch.Tensor) and x.dtype in _H16_DT:
+        _require_centers_bias(centers, bias)
     group_rows = int(group_rows)
     return _CodebookLinear.apply(
         x, codes, centers, bias, bool(relu), codes.kdim, codes.ncols,
