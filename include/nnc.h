@@ -141,6 +141,17 @@ const int32_t *nnc_sort_pruned_bounded_flag(void *ws, int64_t n_nonzero);
 int nnc_sort_pruned_bounded_f32(const float *x, int64_t n, int64_t n_neg, int64_t n_zero, float vmin, float vmax, float thr,
                                 float *sorted_out, void *ws, size_t ws_bytes, void *stream);
 
+/* The pruned sort with every parameter in DEVICE memory, so that it can be enqueued right behind nnc_prune_stats_f32 without a
+ * host read in between: thr_dev = the threshold (stats_dev + 1 of the prune call), signs_dev = {#negative, #zero} (its signs_dev);
+ * the number of keys is counted by the sort itself.  Keys are taken relative to the threshold: with d = bits(|x|) - bits(thr) a
+ * negative weight has the key 2^26 - 1 - d, a positive one 2^26 + d -- 27 bits, three passes of 9 -- which holds while
+ * |x| < 256 * thr.  flag_dev (a device int32 of the caller's, zeroed by the call) is non-zero afterwards iff the sorted copy is
+ * not to be used: bit 0, a weight was clamped (|x| >= 256 * thr, |x| < thr, a NaN, a threshold that is no positive float);
+ * bit 1, a look-back gave up.  Otherwise the result is that of nnc_sort_pruned_f32.  ws: sized for n keys. */
+size_t nnc_sort_threshold_keys_workspace_bytes(int64_t n);
+int nnc_sort_threshold_keys_f32(const float *x, int64_t n, const float *thr_dev, const int64_t *signs_dev, float *sorted_out,
+                                void *ws, size_t ws_bytes, int32_t *flag_dev, void *stream);
+
 /* The statistics of one whole vector by one call (what np.mean / np.var of the reference's KMeans set-up,
  * sklearn _kmeans.py:1011 / 286, and the pass above deliver one by one): out6_dev = {mean, variance (both
  * NumPy-exact float32, as nnc_chunk_sums_f32 + nnc_fold_f32), min, max, min over the non-zeros, max over the

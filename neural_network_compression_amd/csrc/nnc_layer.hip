@@ -260,6 +260,20 @@ extern "C" int nnc_compress_layer_f32(float *x, int64_t n, const nnc_layer_param
     int64_t *signs = reinterpret_cast<int64_t *>(wb + L.stats_out + 32);
     float *pstats = reinterpret_cast<float *>(wb + L.stats_out + 48);
     int64_t *nzeroed = reinterpret_cast<int64_t *>(wb + L.stats_out + 56);
+    int32_t *oob_d = reinterpret_cast<int32_t *>(wb + L.stats_out + 336); // a compact-key sort's verdict: a weight outside what its keys can hold
+    const bool short_tensor = n <= NNC_REF_NMAX && k <= NNC_REF_KMAX;
+    // From the first launch on the second stream on, work is in flight there that writes into the caller's workspace: every way out
+    // of this call -- an error return included -- first makes the caller's stream wait for it (and, on an error, waits itself), so
+    // that the caller may drop the workspace as soon as the call is back.
+    struct SideJoin {
+        SideStream *side = nullptr; hipStream_t s = nullptr; bool joined = false;
+        ~SideJoin() { if (side && !joined) { (void)hipEventRecord(side->join, side->stream); (void)hipStreamWaitEvent(s, side->join, 0); (void)hipStreamSynchronize(s); } }
+    } side_join;
+    SideStream *side = nullptr;
+    // ---- a long tensor that is pruned here: its sorted copy follows the prune pass directly (threshold-relative keys), every
+    // parameter read from device memory: no host read stands between pruning and sorting
+    bool thr_keys = lp->prune && !short_tensor && n >= 512;
+    float *xs = reinterpret_cast<float *>(wb + L.sorted);
     // ---- prune_weigth (utility.py:131-169): in place
     // ... and, in the same pass, min / max (over all and over the non-zero weights) and the sign counts of what is left:
     // out6[2..5], signs.  Without pruning: the statistics pass on its own.
@@ -267,7 +281,6 @@ extern "C" int nnc_compress_layer_f32(float *x, int64_t n, const nnc_layer_param
         LCHK(nnc_prune_stats_f32(x, n, lp->q, lp->std_smooth ? 1 : 0, mask_out, pstats, nzeroed, out6 + 2, signs, wb + L.prune_ws, L.prune_ws_bytes, stream));
     else
         LCHK(nnc_minmax_signs_f32(x, n, out6 + 2, signs, wb + L.stats_ws, L.stats_ws_bytes, stream));
-    const bool short_tensor = n <= NNC_REF_NMAX && k <= NNC_REF_KMAX;
     // (not taken here: short tensors with the density init, tensors too short for the sorted form.  The tensor is pruned
     // already; the caller's own path goes on from there, see status)
     if ((short_tensor && lp->mode != NNC_INIT_LINEAR) || (!short_tensor && n < 512)) {
@@ -311,24 +324,22 @@ extern "C" int nnc_compress_layer_f32(float *x, int64_t n, const nnc_layer_param
     } else {
         // ---- mean and variance -- two passes and two single-wave folds, 90 us of mostly latency -- need only the pruned tensor: they
         // go to a second stream before anything is read, and run under the first round trip and beside the sort.  min / max and the
-        // sign counts are read first (the sort needs the counts on the host).
+        // sign counts are read first (the host wants them for the checks behind the sort and for the histogram steps).
         const int64_t nch = (n + 8191) / 8192; // NumPy's summation chunk
         float *c1 = reinterpret_cast<float *>(wb + L.stats_ws), *c2 = c1 + nch;
-        SideStream *side = nullptr;
         LCHK(side_stream(&side));
         LHIP(hipEventRecord(side->fork, s));
         // (the read goes out first: five launches take the host longer than the threshold pass takes the device.  From out6[2] on:
         // the first two floats are the second stream's to write while this read is under way)
         const uint64_t t_mm = ++(*ticket_io);
-        LCHK(nnc_publish_bytes_(out6 + 2, hb + 512 + 8, 56, h_ticket, t_mm, stream));
+        // (behind a prune pass that is followed by the sort the read travels on the second stream, so that no launch stands between
+        // the two on the caller's: nothing else writes this ticket before the host has seen it, the next read is enqueued behind
+        // the wait below)
+        void *mm_stream = thr_keys ? (void *)side->stream : stream;
+        if (thr_keys) LCHK(nnc_sort_threshold_keys_f32(x, n, pstats + 1, signs, xs, wb + L.sort_ws, L.sort_ws_bytes, oob_d, stream));
         LHIP(hipStreamWaitEvent(side->stream, side->fork, 0));
-        // From here on work is in flight on the second stream, writing into the caller's workspace: every way out of this scope --
-        // an error return included -- first makes the caller's stream wait for it (and, on an error, waits itself), so that the
-        // caller may drop the workspace as soon as the call is back.
-        struct SideJoin {
-            SideStream *side; hipStream_t s; bool joined = false;
-            ~SideJoin() { if (!joined) { (void)hipEventRecord(side->join, side->stream); (void)hipStreamWaitEvent(s, side->join, 0); (void)hipStreamSynchronize(s); } }
-        } side_join{side, s};
+        side_join.side = side; side_join.s = s;
+        LCHK(nnc_publish_bytes_(out6 + 2, hb + 512 + 8, 56, h_ticket, t_mm, mm_stream));
         LCHK(nnc_chunk_sums_f32(x, n, 0, nullptr, c1, side->stream));
         LCHK(nnc_fold_f32(c1, nch, n, NNC_FOLD_MEAN, nullptr, out6, side->stream));           // [0] = mean
         LCHK(nnc_chunk_sums_f32(x, n, 1, out6, c2, side->stream));
@@ -341,20 +352,28 @@ extern "C" int nnc_compress_layer_f32(float *x, int64_t n, const nnc_layer_param
         const float *h_mv = reinterpret_cast<const float *>(hb + 872);
         const uint64_t t_mv = ++(*ticket_io);
         LCHK(nnc_publish_bytes_(out6, hb + 872, 8, h_ticket_side, t_mv, side->stream));
-        LCHK(nnc_wait_ticket_(h_ticket, t_mm, stream));
+        LCHK(nnc_wait_ticket_(h_ticket, t_mm, mm_stream));
         const float xmin = h_f[2], xmax = h_f[3], min_nz = h_f[4], max_nz = h_f[5];
         const int64_t n_neg = h_signs[0], n_zero = h_signs[1];
-        float *xs = reinterpret_cast<float *>(wb + L.sorted);
-        int32_t *oob_d = reinterpret_cast<int32_t *>(wb + L.stats_out + 336); // the bounded sort's verdict: a weight outside the bounds it was given
         const int32_t *h_oob = reinterpret_cast<const int32_t *>(hb + 512 + 336);
         bool bounded = false;
-        // (a pruned tensor whose threshold is known: the surviving weights span few key bits -- three radix passes instead of four)
-        if (4 * n_zero >= n && lp->prune && nnc_sort_pruned_bounded_bits(xmin, xmax, h_prune[1], n_neg, n - n_neg - n_zero) > 0) {
-            LCHK(nnc_sort_pruned_bounded_flagged_(x, n, n_neg, n_zero, xmin, xmax, h_prune[1], xs, wb + L.sort_ws, L.sort_ws_bytes, oob_d, stream));
-            bounded = true;
-        } else if (4 * n_zero >= n) LCHK(nnc_sort_pruned_f32(x, n, n_neg, n_zero, xs, wb + L.sort_ws, L.sort_ws_bytes, stream));
-        else LCHK(nnc_sort_f32(x, n, xs, wb + L.sort_ws, L.sort_ws_bytes, stream));
-        LHIP(hipEventRecord(side->sorted, s)); // (the prefix build on the second stream starts here)
+        // the sorts that take their parameters from the host (every tensor that is not pruned here; a pruned one when the
+        // threshold-relative keys do not apply or did not hold all its weights: a second sort into the same place)
+        auto sort_from_host = [&]() -> int {
+            // (a pruned tensor whose threshold is known: the surviving weights span few key bits -- three radix passes instead of four)
+            if (4 * n_zero >= n && lp->prune && nnc_sort_pruned_bounded_bits(xmin, xmax, h_prune[1], n_neg, n - n_neg - n_zero) > 0) {
+                LCHK(nnc_sort_pruned_bounded_flagged_(x, n, n_neg, n_zero, xmin, xmax, h_prune[1], xs, wb + L.sort_ws, L.sort_ws_bytes, oob_d, stream));
+                bounded = true;
+            } else if (4 * n_zero >= n) LCHK(nnc_sort_pruned_f32(x, n, n_neg, n_zero, xs, wb + L.sort_ws, L.sort_ws_bytes, stream));
+            else LCHK(nnc_sort_f32(x, n, xs, wb + L.sort_ws, L.sort_ws_bytes, stream));
+            return NNC_OK;
+        };
+        // (what the host used to check in front of the sort: too few zeros for a sort that skips them, no usable threshold or bounds)
+        if (thr_keys && !(4 * n_zero >= n && h_prune[1] > 0.0f && std::isfinite(h_prune[1]) && std::isfinite(xmin) && std::isfinite(xmax))) {
+            LHIP(hipStreamSynchronize(s));
+            thr_keys = false;
+        }
+        if (!thr_keys) LCHK(sort_from_host());
         const bool with_prefix = (reinterpret_cast<uintptr_t>(xs) & 15) == 0;
         int64_t *ranks_d = reinterpret_cast<int64_t *>(wb + L.stats_out + 64);
         h_ranks = reinterpret_cast<int64_t *>(hb + 512 + 64);
@@ -367,11 +386,17 @@ extern "C" int nnc_compress_layer_f32(float *x, int64_t n, const nnc_layer_param
             }
             LCHK(nnc_host_linspace_f32(min_nz, max_nz, 32, steps));
             std::memcpy(h_steps, steps, 128); // (read by the kernel straight from the pinned block)
-            LCHK(nnc_rank_sorted_f32(xs, n, h_steps, 32, ranks_d, stream));
         }
-        // ---- the second read (enqueued, not waited for yet): min / max, signs, the ranks, the sort's verdict
-        const uint64_t t_rk = ++(*ticket_io);
-        LCHK(nnc_publish_bytes_(out6 + 2, hb + 512 + 8, 56 + 33 * 8 + 16, h_ticket, t_rk, stream));
+        // ---- behind a sort: the ranks of the histogram steps, and the second read (enqueued, not waited for yet): min / max, signs,
+        // the ranks, the sort's verdict
+        uint64_t t_rk = 0;
+        auto behind_sort = [&]() -> int {
+            LHIP(hipEventRecord(side->sorted, s)); // (the prefix build on the second stream starts here)
+            if (lp->mode == NNC_INIT_DENSITY) LCHK(nnc_rank_sorted_f32(xs, n, h_steps, 32, ranks_d, stream));
+            t_rk = ++(*ticket_io);
+            return nnc_publish_bytes_(out6 + 2, hb + 512 + 8, 56 + 33 * 8 + 16, h_ticket, t_rk, stream);
+        };
+        LCHK(behind_sort());
         LCHK(nnc_wait_ticket_(h_ticket_side, t_mv, side->stream));
         const float mean = h_mv[0], var = h_mv[1];
         if (!std::isfinite(mean) || !std::isfinite(var) || !std::isfinite(xmin) || !std::isfinite(xmax)) {
@@ -395,13 +420,30 @@ extern "C" int nnc_compress_layer_f32(float *x, int64_t n, const nnc_layer_param
         // second stream back in front of the first iteration
         // (the pointer is set before the fit is initialised: its first finalize step then knows that the iterations will not read the
         // cell table and leaves it to the labelling pass at the end -- one launch of k_cells less)
-        if (with_prefix) {
-            LHIP(hipStreamWaitEvent(side->stream, side->sorted, 0));
-            LCHK(nnc_kmeans_prefix_build(xs, &p, reinterpret_cast<int64_t *>(wb + L.prefix), side->stream));
-            p.prefix_dev = reinterpret_cast<int64_t *>(wb + L.prefix);
-        }
-        LHIP(hipEventRecord(side->join, side->stream));
+        auto build_prefix = [&]() -> int {
+            if (with_prefix) {
+                p.prefix_dev = nullptr;
+                LHIP(hipStreamWaitEvent(side->stream, side->sorted, 0));
+                LCHK(nnc_kmeans_prefix_build(xs, &p, reinterpret_cast<int64_t *>(wb + L.prefix), side->stream));
+                p.prefix_dev = reinterpret_cast<int64_t *>(wb + L.prefix);
+            }
+            LHIP(hipEventRecord(side->join, side->stream));
+            return NNC_OK;
+        };
+        LCHK(build_prefix());
         LCHK(nnc_wait_ticket_(h_ticket, t_rk, stream));
+        if (thr_keys && *h_oob) {
+            // a weight that the threshold-relative keys do not hold (256 thresholds or more from zero): the sorted copy is not the
+            // tensor's.  The rare case pays a second sort, by the keys the host can now choose, and everything built on the first one
+            // again (the prefix build has read the copy: it is through before the copy is written again).
+            LHIP(hipStreamWaitEvent(s, side->join, 0));
+            LHIP(hipStreamSynchronize(s));
+            thr_keys = false;
+            LCHK(sort_from_host());
+            LCHK(behind_sort());
+            LCHK(build_prefix());
+            LCHK(nnc_wait_ticket_(h_ticket, t_rk, stream));
+        }
         if (bounded && *h_oob) {
             // a weight outside [min, -threshold] u {0} u [threshold, max] -- a NaN, the statistics pass ignores those: the compact-key
             // sort clamped it, so the sorted copy is not the tensor's.  The step-by-step path (general sorts) goes on from here.

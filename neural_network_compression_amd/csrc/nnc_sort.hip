@@ -12,8 +12,10 @@
 //               contiguously.  Per pass the keys are read once and written once; the last pass writes floats, for a pruned
 //               vector either side of the block of zeros, which is a memset.
 // A pruned vector whose bounds are known has keys of 26 bits at a 1-sigma threshold (three passes of 9 / 9 / 8 bits); anything
-// else takes four passes of 8 bits.  Tickets guarantee that every tile a look-back waits for belongs to a workgroup that is
-// already running; the wait is bounded all the same (a flag says so and the successors are released).
+// else takes four passes of 8 bits.  A vector pruned by a threshold that is in device memory is sorted without any number from the
+// host (nnc_sort_threshold_keys_f32: keys relative to the threshold, 27 bits, counts read by the kernels).  Tickets guarantee that
+// every tile a look-back waits for belongs to a workgroup that is already running; the wait is bounded all the same (a flag says
+// so and the successors are released).
 #include <hip/hip_runtime.h>
 #include <cmath>
 #include <cstdlib>
@@ -81,6 +83,29 @@ __device__ __forceinline__ float os_value(const OsMap &m, unsigned k)
     return f32_unord(k < m.span_neg ? k + m.lo_neg : k - m.span_neg + m.lo_pos);
 }
 
+// threshold-relative keys (a pruned vector whose threshold is in device memory): every surviving weight has |x| >= thr, so the distance
+// d = bits(|x|) - bits(thr) of the two positive floats' images is a compact key that needs neither min nor max: H - 1 - d below zero,
+// H + d above, H = 2^26 -- 27 bits, three passes of 9.  d < H while |x| < 256 * thr; anything else (|x| < thr, |x| >= 256 * thr, a
+// NaN, a threshold that is not a positive float) is clamped and reported like a value outside the bounded map's bounds.
+#define OS_THR_H (1u << 26)
+#define OS_THR_BITS 27
+__device__ __forceinline__ unsigned os_key_thr(unsigned tb, float e, bool &outside)
+{
+    const unsigned b = __float_as_uint(e), ab = b & 0x7FFFFFFFu;
+    unsigned d = ab - tb;
+    outside |= (ab < tb) | (d >= OS_THR_H) | (ab > 0x7F800000u);
+    d = ab < tb ? 0u : (d >= OS_THR_H ? OS_THR_H - 1u : d);
+    return (b >> 31) ? OS_THR_H - 1u - d : OS_THR_H + d;
+}
+__device__ __forceinline__ float os_value_thr(unsigned tb, unsigned k)
+{
+    return __uint_as_float(k < OS_THR_H ? ((tb + (OS_THR_H - 1u - k)) | 0x80000000u) : tb + (k - OS_THR_H));
+}
+
+// what a sort that takes its parameters from device memory reads there (the DEV instances of the kernels): the sign counts that
+// k_minmax_final wrote ({#negative, #zero}), the threshold, the caller's verdict word (bits as in ctrl[1]), the whole vector's length
+struct OsDev { const long long *signs; const float *thr; int *flag; long long n_total; };
+
 // ctrl block of a sort (device): [0] keys written by k_os_prep, [1] flags (1 = a value outside the bounds, 2 = a look-back gave up),
 // [2..3] tile tickets of the passes (32 bits each)
 #define OS_CTRL_WORDS 4
@@ -89,10 +114,13 @@ __device__ __forceinline__ float os_value(const OsMap &m, unsigned k)
 // out the output ranges a tile at a time; the tile is compacted in LDS and leaves in whole lines).  Digit histogram of the FIRST pass
 // (LDS atomics retire about one lane a clock on gfx950: one histogram costs a pass's worth of them, so every radix pass makes the
 // histogram of the next one while it has the keys in registers, and this kernel only the first).
-template <bool SKIPZ>
+// THR: threshold-relative keys, the threshold read from dv.thr; the verdict goes to dv.flag as well.
+template <bool SKIPZ, bool THR = false>
 __global__ __launch_bounds__(OSP_THREADS) void k_os_prep(const float *__restrict__ x, long long n, unsigned *__restrict__ keys,
-                                                         unsigned long long *__restrict__ ctrl, long long cap, OsMap km, int rb0, unsigned *__restrict__ ghist)
+                                                         unsigned long long *__restrict__ ctrl, long long cap, OsMap km, int rb0, unsigned *__restrict__ ghist, OsDev dv)
 {
+    unsigned tb = 0u;
+    if (THR) tb = __float_as_uint(*dv.thr);
     __shared__ unsigned comp_s[SKIPZ ? OSP_TILE : 1];
     __shared__ unsigned hist_s[OS_MAXR];
     __shared__ unsigned wave_tot[OSP_THREADS / 64];
@@ -139,7 +167,7 @@ __global__ __launch_bounds__(OSP_THREADS) void k_os_prep(const float *__restrict
             bool ok = SKIPZ ? !(e[j] == 0.0f) : true;
             if (!SKIPZ && !fast) ok = tile0 + (long long)j * OSP_THREADS + tid < n; // (positions beyond the end read as zero above: not keys)
             key[j] = 0u;
-            if (ok) { key[j] = os_key(km, e[j], outside); take |= 1u << j; }
+            if (ok) { key[j] = THR ? os_key_thr(tb, e[j], outside) : os_key(km, e[j], outside); take |= 1u << j; }
         }
 #pragma unroll
         for (int j = 0; j < OSP_PER; j++)
@@ -165,6 +193,7 @@ __global__ __launch_bounds__(OSP_THREADS) void k_os_prep(const float *__restrict
         }
     }
     if (outside) atomicOr(ctrl + 1, 1ull);
+    if (THR && outside) atomicOr(dv.flag, 1);
     __syncthreads();
     for (int i = tid; i < OS_MAXR; i += OSP_THREADS) {
         const unsigned v = hist_s[i];
@@ -218,11 +247,25 @@ __device__ __forceinline__ void os_peers(unsigned d, bool valid, unsigned &plo, 
 // One digit pass.  RB: bits of the digit.  SRC 0: unsigned keys; 1: floats (keys are their ordered images: the first pass of an unpruned
 // vector reads it directly).  DST 0: unsigned keys; 1: floats (the last pass): key k of rank r goes to out[r + (r >= n_neg ? n_zero : 0)]
 // as its value.  nrb > 0: the pass also makes the digit histogram of the next pass (digit = (key >> (shift + RB)) & (2^nrb - 1)).
-template <int RB, int SRC, int DST>
-__global__ __launch_bounds__(OS_THREADS, OS_BLOCKS_PER_CU * OS_THREADS / 256) void k_os_pass(const void *__restrict__ in_, void *__restrict__ out_, long long n, int shift, int pass, int nrb,
+// DEV: the sort's parameters come from device memory -- `n_` is only the capacity of the key buffers, the number of keys is what
+// k_os_prep counted (ctrl[0]), n_neg / n_zero are dv.signs, the keys are threshold-relative (dv.thr).  The grid is sized for the
+// capacity; a workgroup whose ticket lies past the tiles there are leaves.  With no key at all the last pass writes the zeros.
+template <int RB, int SRC, int DST, bool DEV = false>
+__global__ __launch_bounds__(OS_THREADS, OS_BLOCKS_PER_CU * OS_THREADS / 256) void k_os_pass(const void *__restrict__ in_, void *__restrict__ out_, long long n_, int shift, int pass, int nrb,
                                                            const unsigned *__restrict__ ghist, unsigned *__restrict__ ghist_next, unsigned long long *__restrict__ status,
-                                                           unsigned long long *__restrict__ ctrl, OsMap km, long long n_neg, long long n_zero, int abl)
+                                                           unsigned long long *__restrict__ ctrl, OsMap km, long long n_neg_, long long n_zero_, int abl, OsDev dv)
 {
+    long long n = n_, n_neg = n_neg_, n_zero = n_zero_;
+    unsigned tb = 0u;
+    bool bad_counts = false;
+    if (DEV) {
+        const long long have = (long long)ctrl[0];
+        n = have < n_ ? have : n_;
+        n_neg = dv.signs[0]; n_zero = dv.signs[1];
+        tb = __float_as_uint(*dv.thr);
+        // (counts that do not fit the vector -- never, they come from the same pass as the keys: nothing is written out of range all the same)
+        if (n_neg < 0 || n_zero < 0 || n_neg > n || n + n_zero > dv.n_total) { n_neg = n; n_zero = 0; bad_counts = true; }
+    }
     constexpr int R = 1 << RB;
     constexpr unsigned MASK = (unsigned)R - 1u;
     constexpr int DPT = (R + OS_THREADS - 1) / OS_THREADS; // digits per thread: thread t owns digits t * DPT .. t * DPT + DPT - 1
@@ -261,6 +304,9 @@ __global__ __launch_bounds__(OS_THREADS, OS_BLOCKS_PER_CU * OS_THREADS / 256) vo
     }
     const long long ntiles = (n + OS_TILE - 1) / OS_TILE;
     bool gave_up = false;
+    if (DEV && DST == 1 && ntiles == 0) { // everything pruned: no tile, so no tile's slice of the zeros
+        for (long long i = (long long)blockIdx.x * OS_THREADS + t; i < n_zero; i += (long long)gridDim.x * OS_THREADS) out_f[n_neg + i] = 0.0f;
+    }
     for (;;) {
         if (t == 0) tile_s = (long long)atomicAdd(ticket, 1u);
         for (int d = t; d < R; d += OS_THREADS) {
@@ -428,7 +474,7 @@ __global__ __launch_bounds__(OS_THREADS, OS_BLOCKS_PER_CU * OS_THREADS / 256) vo
             const unsigned r = gpos[d] + (unsigned)j;
             if ((long long)r < n && !(abl & 4)) { // (always, unless the caller's counts were wrong: then garbage, never a fault)
                 if (DST == 0) out_k[r] = kv;
-                else out_f[(long long)r + ((long long)r >= n_neg ? n_zero : 0)] = os_value(km, kv);
+                else out_f[(long long)r + ((long long)r >= n_neg ? n_zero : 0)] = DEV ? os_value_thr(tb, kv) : os_value(km, kv);
             }
         }
         OS_STAMP(6);
@@ -436,6 +482,7 @@ __global__ __launch_bounds__(OS_THREADS, OS_BLOCKS_PER_CU * OS_THREADS / 256) vo
         OS_STAMP(7);
     }
     if (gave_up) atomicOr(ctrl + 1, 2ull);
+    if (DEV && (gave_up || (bad_counts && blockIdx.x == 0 && t == 0))) atomicOr(dv.flag, 2);
     if (nrb > 0) { // (every thread is past the loop's last barrier: the workgroup's histogram is complete)
         for (int i = t; i <= (int)nmask; i += OS_THREADS) {
             const unsigned v = nhist[i];
@@ -456,8 +503,9 @@ static size_t al256(size_t b) { return (b + 255) & ~(size_t)255; }
 // The sort's bookkeeping as launches of its own stream instead of the runtime's fill and copy commands: those two waited for whatever
 // another stream of the process had in flight (the layer call's mean / variance passes on its second stream, 90 us: the sort
 // began when they were through instead of beside them).  n16: 16-byte words.
-__global__ __launch_bounds__(256) void k_os_clear(uint4 *__restrict__ p, long long n16)
+__global__ __launch_bounds__(256) void k_os_clear(uint4 *__restrict__ p, long long n16, int *__restrict__ flag)
 {
+    if (flag && blockIdx.x == 0 && threadIdx.x == 0) *flag = 0; // (the verdict word of a sort that keeps it outside its workspace)
     const long long stride = (long long)gridDim.x * 256;
     for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n16; i += stride) p[i] = make_uint4(0u, 0u, 0u, 0u);
 }
@@ -503,6 +551,26 @@ static size_t os_ws_bytes(int64_t n_keys)
     return 2 * al256((size_t)n_keys * 4 + 16) + al256(OS_CTRL_WORDS * 8) + al256((size_t)(OS_MAXPASS + 1) * OS_MAXR * 4) + os_status_bytes(n_keys) + 256;
 }
 static unsigned char *os_ws_base(void *ws) { return reinterpret_cast<unsigned char *>((reinterpret_cast<uintptr_t>(ws) + 255) & ~(uintptr_t)255); }
+struct OsWs { unsigned *ka, *kb; unsigned long long *ctrl; unsigned *ghist; unsigned long long *status; size_t zero_bytes; };
+static OsWs os_ws_carve(void *ws, int64_t n_keys)
+{
+    OsWs w;
+    unsigned char *b = os_ws_base(ws);
+    w.ka = reinterpret_cast<unsigned *>(b); b += al256((size_t)n_keys * 4 + 16);
+    w.kb = reinterpret_cast<unsigned *>(b); b += al256((size_t)n_keys * 4 + 16);
+    w.ctrl = reinterpret_cast<unsigned long long *>(b); b += al256(OS_CTRL_WORDS * 8);
+    w.ghist = reinterpret_cast<unsigned *>(b); b += al256((size_t)(OS_MAXPASS + 1) * OS_MAXR * 4);
+    w.status = reinterpret_cast<unsigned long long *>(b);
+    // ctrl + histograms + status words lie side by side (256-byte aligned, a multiple of 256 bytes): one launch clears them
+    w.zero_bytes = al256(OS_CTRL_WORDS * 8) + al256((size_t)(OS_MAXPASS + 1) * OS_MAXR * 4) + os_status_bytes(n_keys);
+    return w;
+}
+static hipError_t os_clear(const OsWs &w, int32_t *flag_dev, hipStream_t s)
+{
+    const long long n16 = (long long)(w.zero_bytes / 16);
+    hipLaunchKernelGGL(k_os_clear, dim3((unsigned)std::min<long long>((n16 + 255) / 256, 1024)), dim3(256), 0, s, reinterpret_cast<uint4 *>(w.ctrl), n16, reinterpret_cast<int *>(flag_dev));
+    return hipGetLastError();
+}
 
 // The whole sort.  skip_zeros: only the non-zero weights are keys (n_neg negative ones, n_zero zeros: the caller's counts), the zeros
 // come back as one block between the negative and the positive values.  bits: significant bits of the keys under `km`.
@@ -512,18 +580,11 @@ static int os_sort(const float *x, int64_t n, bool skip_zeros, int64_t n_neg, in
     const int64_t n_keys = skip_zeros ? n - n_zero : n;
     if (!ws || ws_bytes < os_ws_bytes(n_keys)) return nnc_set_error_(NNC_ENOSPACE, (std::string(who) + ": workspace too small").c_str());
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    unsigned char *b = os_ws_base(ws);
-    unsigned *ka = reinterpret_cast<unsigned *>(b); b += al256((size_t)n_keys * 4 + 16);
-    unsigned *kb = reinterpret_cast<unsigned *>(b); b += al256((size_t)n_keys * 4 + 16);
-    unsigned long long *ctrl = reinterpret_cast<unsigned long long *>(b); b += al256(OS_CTRL_WORDS * 8);
-    unsigned *ghist = reinterpret_cast<unsigned *>(b); b += al256((size_t)(OS_MAXPASS + 1) * OS_MAXR * 4);
-    unsigned long long *status = reinterpret_cast<unsigned long long *>(b);
+    const OsWs w = os_ws_carve(ws, n_keys);
+    unsigned *ka = w.ka, *kb = w.kb, *ghist = w.ghist;
+    unsigned long long *ctrl = w.ctrl, *status = w.status;
     hipError_t e;
-    // ctrl + histograms + status words lie side by side (256-byte aligned, a multiple of 256 bytes): one launch clears them
-    const size_t zero_bytes = al256(OS_CTRL_WORDS * 8) + al256((size_t)(OS_MAXPASS + 1) * OS_MAXR * 4) + os_status_bytes(n_keys);
-    const long long n16 = (long long)(zero_bytes / 16);
-    hipLaunchKernelGGL(k_os_clear, dim3((unsigned)std::min<long long>((n16 + 255) / 256, 1024)), dim3(256), 0, s, reinterpret_cast<uint4 *>(ctrl), n16);
-    if ((e = hipGetLastError()) != hipSuccess) return nnc_set_error_(NNC_EHIP, hipGetErrorString(e));
+    if ((e = os_clear(w, nullptr, s)) != hipSuccess) return nnc_set_error_(NNC_EHIP, hipGetErrorString(e));
     // (the zeros of a pruned vector are written by the tiles of the last pass; with no key at all there is no pass)
     if (skip_zeros && n_zero > 0 && n_keys == 0 && (e = hipMemsetAsync(sorted_out + n_neg, 0, (size_t)n_zero * 4, s)) != hipSuccess) return nnc_set_error_(NNC_EHIP, hipGetErrorString(e));
     const OsPlan pl = os_plan(bits);
@@ -534,8 +595,8 @@ static int os_sort(const float *x, int64_t n, bool skip_zeros, int64_t n_neg, in
     if (n_keys > 0) {
         const long long ptiles = (n + OSP_TILE - 1) / OSP_TILE;
         const int pgrid = (int)std::min<long long>(std::max<long long>(ptiles, 1), 2LL * os_cus());
-        if (skip_zeros) hipLaunchKernelGGL((k_os_prep<true>), dim3(pgrid), dim3(OSP_THREADS), 0, s, x, (long long)n, ka, ctrl, (long long)n_keys, km, pl.rb[0], ghist);
-        else hipLaunchKernelGGL((k_os_prep<false>), dim3(pgrid), dim3(OSP_THREADS), 0, s, x, (long long)n, (unsigned *)nullptr, ctrl, (long long)n_keys, km, pl.rb[0], ghist);
+        if (skip_zeros) hipLaunchKernelGGL((k_os_prep<true>), dim3(pgrid), dim3(OSP_THREADS), 0, s, x, (long long)n, ka, ctrl, (long long)n_keys, km, pl.rb[0], ghist, OsDev());
+        else hipLaunchKernelGGL((k_os_prep<false>), dim3(pgrid), dim3(OSP_THREADS), 0, s, x, (long long)n, (unsigned *)nullptr, ctrl, (long long)n_keys, km, pl.rb[0], ghist, OsDev());
         if ((e = hipGetLastError()) != hipSuccess) return nnc_set_error_(NNC_EHIP, hipGetErrorString(e));
         const long long ntiles = (n_keys + OS_TILE - 1) / OS_TILE;
         const int grid = (int)std::min<long long>(ntiles, (long long)OS_BLOCKS_PER_CU * os_cus());
@@ -546,9 +607,9 @@ static int os_sort(const float *x, int64_t n, bool skip_zeros, int64_t n_neg, in
             void *o = last ? (void *)sorted_out : (void *)dst;
 #define OS_LAUNCH(SRC, DST) do { \
                 if (pl.rb[p] == 9) hipLaunchKernelGGL((k_os_pass<9, SRC, DST>), dim3(grid), dim3(OS_THREADS), 0, s, src, o, (long long)n_keys, pl.shift[p], p, last ? 0 : pl.rb[p + 1], \
-                                                      ghist + (size_t)p * OS_MAXR, ghist + (size_t)(p + 1) * OS_MAXR, status, ctrl, km, (long long)(skip_zeros ? n_neg : n_keys), (long long)(skip_zeros ? n_zero : 0), abl); \
+                                                      ghist + (size_t)p * OS_MAXR, ghist + (size_t)(p + 1) * OS_MAXR, status, ctrl, km, (long long)(skip_zeros ? n_neg : n_keys), (long long)(skip_zeros ? n_zero : 0), abl, OsDev()); \
                 else hipLaunchKernelGGL((k_os_pass<8, SRC, DST>), dim3(grid), dim3(OS_THREADS), 0, s, src, o, (long long)n_keys, pl.shift[p], p, last ? 0 : pl.rb[p + 1], \
-                                        ghist + (size_t)p * OS_MAXR, ghist + (size_t)(p + 1) * OS_MAXR, status, ctrl, km, (long long)(skip_zeros ? n_neg : n_keys), (long long)(skip_zeros ? n_zero : 0), abl); \
+                                        ghist + (size_t)p * OS_MAXR, ghist + (size_t)(p + 1) * OS_MAXR, status, ctrl, km, (long long)(skip_zeros ? n_neg : n_keys), (long long)(skip_zeros ? n_zero : 0), abl, OsDev()); \
             } while (0)
             if (first_f && last) OS_LAUNCH(1, 1);
             else if (first_f) OS_LAUNCH(1, 0);
@@ -677,4 +738,63 @@ int nnc_sort_pruned_bounded_flagged_(const float *x, int64_t n, int64_t n_neg, i
     const int bits = n_nz > 0 ? rs_bounds(vmin, vmax, thr, n_neg, n_pos, &bd) : 1;
     if (bits == 0) return nnc_set_error_(NNC_EINVAL, "nnc_sort_pruned_bounded_f32: bounds do not apply (see nnc_sort_pruned_bounded_bits)");
     return os_sort(x, n, true, n_neg, n_zero, bd, bits, sorted_out, ws, ws_bytes, flag_dev, "nnc_sort_pruned_bounded_f32", stream);
+}
+
+// --------------------------------------------------------------------------------------
+// The sort of a PRUNED vector that takes everything it needs from device memory: the threshold from the prune pass's statistics
+// block, the number of keys from k_os_prep's own counter, #negative / #zero from the signs block of k_minmax_final.  Nothing of it
+// waits for the host: the keys are threshold-relative (os_key_thr) and the workspace, the status words and the grid are sized
+// for the upper bound n.  flag_dev (zeroed by the clear) is non-zero afterwards iff the sorted copy is not to be used: bit 0, a
+// weight with |x| >= 256 * thr (or below thr, or a NaN, or a threshold that is not a positive float); bit 1, a look-back gave up.
+// (The clear is a launch in line: on a second stream beside the sigma passes it measured no better, the join costs what it saves.)
+// --------------------------------------------------------------------------------------
+extern "C" size_t nnc_sort_threshold_keys_workspace_bytes(int64_t n) { return n <= 0 ? 0 : os_ws_bytes(n); }
+
+static int sort_threshold_keys_clear(void *ws, size_t ws_bytes, int64_t n, int32_t *flag_dev, void *stream)
+{
+    if (n < 1 || n >= ((int64_t)1 << 31) || !flag_dev) return nnc_set_error_(NNC_EINVAL, "nnc_sort_threshold_keys_f32: bad argument");
+    if (!ws || ws_bytes < os_ws_bytes(n)) return nnc_set_error_(NNC_ENOSPACE, "nnc_sort_threshold_keys_f32: workspace too small");
+    const hipError_t e = os_clear(os_ws_carve(ws, n), flag_dev, reinterpret_cast<hipStream_t>(stream));
+    return e == hipSuccess ? NNC_OK : nnc_set_error_(NNC_EHIP, hipGetErrorString(e));
+}
+
+static int sort_threshold_keys_run(const float *x, int64_t n, const float *thr_dev, const int64_t *signs_dev, float *sorted_out, void *ws, size_t ws_bytes,
+                                 int32_t *flag_dev, void *stream)
+{
+    if (n < 1 || n >= ((int64_t)1 << 31) || !x || !sorted_out || !thr_dev || !signs_dev || !flag_dev) return nnc_set_error_(NNC_EINVAL, "nnc_sort_threshold_keys_f32: bad argument");
+    if (!ws || ws_bytes < os_ws_bytes(n)) return nnc_set_error_(NNC_ENOSPACE, "nnc_sort_threshold_keys_f32: workspace too small");
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    const OsWs w = os_ws_carve(ws, n);
+    OsDev dv;
+    dv.signs = reinterpret_cast<const long long *>(signs_dev); dv.thr = thr_dev; dv.flag = reinterpret_cast<int *>(flag_dev); dv.n_total = (long long)n;
+    const OsPlan pl = os_plan(OS_THR_BITS);
+    const OsMap km = os_identity(); // (unused by the THR / DEV instances)
+    hipError_t e;
+    const long long ptiles = (n + OSP_TILE - 1) / OSP_TILE;
+    const int pgrid = (int)std::min<long long>(ptiles, 2LL * os_cus());
+    hipLaunchKernelGGL((k_os_prep<true, true>), dim3(pgrid), dim3(OSP_THREADS), 0, s, x, (long long)n, w.ka, w.ctrl, (long long)n, km, pl.rb[0], w.ghist, dv);
+    if ((e = hipGetLastError()) != hipSuccess) return nnc_set_error_(NNC_EHIP, hipGetErrorString(e));
+    const long long ntiles = (n + OS_TILE - 1) / OS_TILE; // (as many as there can be: the kernels know how many there are)
+    const int grid = (int)std::min<long long>(ntiles, (long long)OS_BLOCKS_PER_CU * os_cus());
+    const unsigned *src = w.ka;
+    unsigned *dst = w.kb;
+    for (int p = 0; p < pl.passes; p++) {
+        const bool last = (p == pl.passes - 1);
+        static_assert(OS_THR_BITS > 24 && OS_THR_BITS <= 27, "three passes of nine bits");
+        if (last) hipLaunchKernelGGL((k_os_pass<9, 0, 1, true>), dim3(grid), dim3(OS_THREADS), 0, s, (const void *)src, (void *)sorted_out, (long long)n, pl.shift[p], p, 0,
+                                     w.ghist + (size_t)p * OS_MAXR, w.ghist + (size_t)(p + 1) * OS_MAXR, w.status, w.ctrl, km, 0ll, 0ll, 0, dv);
+        else hipLaunchKernelGGL((k_os_pass<9, 0, 0, true>), dim3(grid), dim3(OS_THREADS), 0, s, (const void *)src, (void *)dst, (long long)n, pl.shift[p], p, pl.rb[p + 1],
+                                w.ghist + (size_t)p * OS_MAXR, w.ghist + (size_t)(p + 1) * OS_MAXR, w.status, w.ctrl, km, 0ll, 0ll, 0, dv);
+        if ((e = hipGetLastError()) != hipSuccess) return nnc_set_error_(NNC_EHIP, hipGetErrorString(e));
+        src = dst;
+        dst = (dst == w.ka) ? w.kb : w.ka;
+    }
+    return NNC_OK;
+}
+
+extern "C" int nnc_sort_threshold_keys_f32(const float *x, int64_t n, const float *thr_dev, const int64_t *signs_dev, float *sorted_out, void *ws,
+                                           size_t ws_bytes, int32_t *flag_dev, void *stream)
+{
+    const int rc = sort_threshold_keys_clear(ws, ws_bytes, n, flag_dev, stream);
+    return rc ? rc : sort_threshold_keys_run(x, n, thr_dev, signs_dev, sorted_out, ws, ws_bytes, flag_dev, stream);
 }
