@@ -3,7 +3,8 @@
 // element type of g and x as the ungrouped ones of nnc_cbgrad.hpp are, and the argument checks both units make.  XT = float is
 // nnc_cbmm_grouped_dx_f32's / nnc_cbmm_grouped_dc_f32's kernel, instruction for instruction what it was in nnc_cbgrad_grouped.hip;
 // XT = bf16_t / f16_t reads g and x as XT and widens them, and the dx tables hold the centres rounded to XT and widened.  The fmaf
-// chains, the walk through the groups and the barriers do not depend on XT.
+// chains, the walk through the groups and the barriers do not depend on XT.  Also here: which table or set of bins an index row of an
+// MFMA tile uses (tile_group_of), for the MFMA kernels of both group-wise half units (the packed one too, section 27).
 #pragma once
 #include "nnc_cbtile.hpp"
 
@@ -203,6 +204,28 @@ __global__ __launch_bounds__(CB_THREADS) void k_cbdc_stream_grouped(const XT *__
         __syncthreads();
     }
 }
+
+// ------------------------------------------------------------------ the groups of an MFMA tile, m > 16 (both group-wise half units)
+// The 128 index rows of a tile that starts at row i0 lie in the groups q0, q0 + 1, ... of the layer's `groups`; a kernel holds `held`
+// (tile_groups: 1, 2 or 4) tables (dx) or sets of bins (dc) for them, one past the last group being unread.
+struct TileGroups {
+    long long q0, groups;
+};
+
+__device__ __forceinline__ TileGroups tile_groups_at(long long i0, long long kdim, long long group_rows)
+{
+    return {i0 / group_rows, (kdim + group_rows - 1) / group_rows};
+}
+
+// the table or set of index row i
+__device__ __forceinline__ long long tile_group_of(const TileGroups &G, long long i, long long group_rows, int held)
+{
+    return std::min((long long)held - 1, i / group_rows - G.q0);
+}
+
+// dc: the first index row of the wave's quarter of the tile, T.m0 + T.wm, as a scalar.  The 32 rows of accumulator row a start at
+// + 32 a and lie in one group (group_rows is a multiple of 32), so their set is a scalar too.
+__device__ __forceinline__ long long tile_wave_row0(long long m0) { return m0 + __builtin_amdgcn_readfirstlane(threadIdx.x >> 7) * 64; }
 
 // ------------------------------------------------------------------ the checks of both units (host)
 // cg_check's checks at label_bytes 1, then those nnc_cbmm_grouped makes of k and group_rows

@@ -3,9 +3,11 @@
 // W_h[i, o] = the centre centers[i / group_rows][labels[i, o]] rounded to the type of g, exactly the grouped forward's; products
 // are exact in float32, every sum is float32, dc is binned as section 12's exact integers into G x K bins.
 //
-// The plans are the ungrouped half ones (nnc_cbmm_dx_h16_plan / nnc_cbmm_dc_h16_plan at label_bytes 1) plus the group fields, as
-// section 19 took the float32 ones: the path, the tiles, the splits, the order of every sum and the shift S of the dc sums are those
-// of nnc_cbmm_dx_h16 / nnc_cbmm_dc_h16 on the same shape.
+// The plans are the ungrouped half ones at label_bytes 1 (section 12's stream plans; nnc_cbh16plan.hpp's tiles and splits with the
+// byte form's table and bins at m > 16) plus the group fields, as section 19 took the float32 ones: the path, the tiles, the splits,
+// the order of every sum and the shift S of the dc sums are those of nnc_cbmm_dx_h16 / nnc_cbmm_dc_h16 on the same shape.  The
+// two main loops are the ungrouped kernels' (dxm_accumulate, dcm_accumulate), the pick of a row's table or set tile_group_of
+// (nnc_cbgrad_grouped.hpp).
 //   m <= 16   k_cbdx_stream_grouped<XT> / k_cbdc_stream_grouped<XT> of nnc_cbgrad_grouped.hpp: section 19's kernels with g and x
 //             widened as they are loaded and, for dx, the tables of the rounded centres.
 //   k_cbdx_mfma_grouped  m > 16.  k_cbdx_mfma (nnc_cbgrad_h16.hip) with the tables of the up to four groups the tile's 128 index rows
@@ -22,6 +24,7 @@
 #include "nnc_cbdxm.hpp"
 #include "nnc_cbgrad_grouped.hpp"
 #include "nnc_cbgrad_h16.hpp"
+#include "nnc_cbh16plan.hpp"
 
 // ------------------------------------------------------------------ dx, m > 16
 // grid (kdim tiles * m tiles, splits of ncols), HM_THREADS threads; `out` and cols_per_split as k_cbdx_mfma.  LDS: 1 << tlog2 tables
@@ -41,26 +44,23 @@ __global__ __launch_bounds__(HM_THREADS) void k_cbdx_mfma_grouped(const XT *__re
 
     const HmTile T = hm_tile(col_tiles, cols_per_split, ncols);   // n0: the first index row i, m0: the first row of g, [k_lo, k_hi): columns o
     const int tcs = cshift - tlog2, tables = 1 << tlog2;          // the copies of one table (log2)
-    const long long q0 = T.n0 / group_rows, groups = (kdim + group_rows - 1) / group_rows;
+    const TileGroups G = tile_groups_at(T.n0, kdim, group_rows);
     for (int t = 0; t < tables; ++t) {                  // (uniform over the workgroup; a table past the last group repeats it, unread)
         if (t) __syncthreads();                         // the staging row of the table before has been copied
-        cb_fill<XT>(cb + (long long)t * (entries << tcs), stage, centers + std::min(q0 + t, groups - 1) * k, k, entries, tcs);
+        cb_fill<XT>(cb + (long long)t * (entries << tcs), stage, centers + std::min(G.q0 + t, G.groups - 1) * k, k, entries, tcs);
     }
 
     const long long gi = T.n0 + T.wc;
     const bool row_ok = gi < kdim;
     const uint8_t *lrow = labels + gi * ncols;
-    const float *tab = cb + std::min((long long)tables - 1, gi / group_rows - q0) * (entries << tcs) + (T.lane & ((1 << tcs) - 1));
+    const float *tab = cb + tile_group_of(G, gi, group_rows, tables) * (entries << tcs) + (T.lane & ((1 << tcs) - 1));
     uint32_t lw[4];
-    uint4 gf[2];
 
-    auto load = [&](long long ob) {
+    auto load_w = [&](long long ob) {
         const long long left = T.k_hi - (ob + T.wk0);
         dxm_load_labels<uint8_t>(lrow + ob + T.wk0, row_ok ? (int)std::max(0LL, std::min(16LL, left)) : 0, lw);
-#pragma unroll
-        for (int i = 0; i < 2; ++i) gf[i] = hm_load_x<XT, XVEC>(g, m, ncols, T.m0, ob, T.k_hi, T.t + i * HM_THREADS);
     };
-    auto store = [&](long long ob) {
+    auto store_w = [&](long long ob) {
         float w[16];
 #pragma unroll
         for (int j = 0; j < 16; ++j) {
@@ -68,20 +68,10 @@ __global__ __launch_bounds__(HM_THREADS) void k_cbdx_mfma_grouped(const XT *__re
             w[j] = (row_ok && ob + T.wk0 + j < T.k_hi) ? tab[l << tcs] : 0.0f;
         }
         hm_store_w(ws, T.wc, T.wk0, w);
-#pragma unroll
-        for (int i = 0; i < 2; ++i) hm_store_x(gs, T.t + i * HM_THREADS, gf[i]);
     };
 
     typename HFrag<XT>::C acc[2][2];
-    hm_clear<XT>(acc);
-    load(T.k_lo);
-    for (long long ob = T.k_lo; ob < T.k_hi; ob += HM_BK) {
-        __syncthreads();   // the tables are filled (first step); the images of the step before have been read
-        store(ob);
-        __syncthreads();
-        if (ob + HM_BK < T.k_hi) load(ob + HM_BK);
-        hm_step(gs, ws, T.wm, T.wn, T.fr, T.fh, acc);
-    }
+    dxm_accumulate<XT, XVEC>(g, m, ncols, T, gs, ws, acc, load_w, store_w);
     hm_store_y<XT>(acc, T.n0, T.m0, T.wm, T.wn, T.lane, m, kdim, nullptr, 0, direct, out_);
 }
 
@@ -106,64 +96,51 @@ __global__ __launch_bounds__(HM_THREADS) void k_cbdc_mfma_grouped(const XT *__re
     typename HFrag<XT>::C acc[2][2];
     dcm_accumulate<XT, XVEC>(x, g, kdim, ncols, T, scx, scg, xs, gs, acc);
 
-    // register r of lane l of accumulator (a, b) is dW'[i = m0 + wm + 32 a + (r & 3) + 8 (r >> 2) + 4 (l >> 5)][o = n0 + wn + 32 b + (l & 31)]:
-    // the 32 rows of (a, b) start on a multiple of 32 and lie in one group, whose set is a scalar
+    // accumulator (a, b) holds dW'[i][o] (hm_acc_row, hm_acc_col): its 32 rows lie in one group, whose set is a scalar
     const int rl = rlog2 - sets_log2, sets = 1 << sets_log2;
-    const long long q0 = T.m0 / group_rows, groups = (kdim + group_rows - 1) / group_rows;
-    const int wm = __builtin_amdgcn_readfirstlane(threadIdx.x >> 7) * 64;   // T.wm, as a scalar
+    const TileGroups G = tile_groups_at(T.m0, kdim, group_rows);
+    const long long row0 = tile_wave_row0(T.m0);
     const int rep = T.t & ((1 << rl) - 1);
 #pragma unroll
     for (int a = 0; a < 2; ++a) {
-        const int set = (int)std::min((long long)sets - 1, (T.m0 + wm + a * 32) / group_rows - q0);
+        const int set = (int)tile_group_of(G, row0 + a * 32, group_rows, sets);
         unsigned long long *sb = bins + ((long long)set * k << rl);
 #pragma unroll
         for (int b = 0; b < 2; ++b) {
-            const long long o = T.n0 + T.wn + b * 32 + T.fr;
+            const long long o = hm_acc_col(T.n0 + T.wn, b, T.lane);
             if (o >= ncols) continue;
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
-                const long long i = T.m0 + T.wm + a * 32 + (r & 3) + 8 * (r >> 2) + 4 * (T.lane >> 5);
+                const long long i = hm_acc_row(T.m0 + T.wm, a, r, T.lane);
                 if (i >= kdim) continue;
                 const uint32_t l = (uint32_t)labels[i * ncols + o];
                 if (l < (uint32_t)k) atomicAdd(&sb[(l << rl) + rep], cbdc_fix(acc[a][b][r], Sw));
             }
         }
     }
-    for (int t = 0; t < sets && q0 + t < groups; ++t) cbdc_flush(bins + ((long long)t * k << rl), k, rl, sums + (q0 + t) * k);
+    for (int t = 0; t < sets && G.q0 + t < G.groups; ++t) cbdc_flush(bins + ((long long)t * k << rl), k, rl, sums + (G.q0 + t) * k);
 }
 
 // ------------------------------------------------------------------ plans (host)
-// m <= 16 and the empty shapes: section 12's plans at label_bytes 1 (what nnc_cbmm_dx_h16_plan / nnc_cbmm_dc_h16_plan report there,
-// with the rows per workgroup their records leave out).  m > 16: the record of the ungrouped half plan itself.
-static int gh_dx_plan(const char *fn, int dt, int64_t m, int64_t kdim, int64_t ncols, int32_t k, int32_t cus, uintptr_t labels, CgPlan &p)
+// nnc_cbmm_dx_h16's / nnc_cbmm_dc_h16's plans at label_bytes 1.  m <= 16 and the empty shapes: section 12's plans (dx_plan, dc_plan).
+// m > 16: nnc_cbh16plan.hpp's tiles and splits with the LDS of k_cbdx_mfma / k_cbdc_mfma, which the tables / sets of a tile divide.
+static CgPlan gh_dx_plan(int64_t m, int64_t kdim, int64_t ncols, int32_t k, int32_t cus, uintptr_t labels)
 {
-    p = dx_plan(m, kdim, ncols, 1, k, cus, labels);
-    if (p.path != NNC_CBMM_TILED) return NNC_OK;
-    int64_t r[NNC_CBDX_H16_PLAN_LEN];
-    const int rc = nnc_cbmm_dx_h16_plan(dt, m, kdim, ncols, 1, k, cus, (uint64_t)labels, r);
-    if (rc != NNC_OK) return rc;
-    if (r[0] != NNC_CBMM_MFMA) return fail(NNC_EINVAL, std::string(fn) + ": the half plan of m > 16 is not the MFMA path");
-    p = CgPlan{};
-    p.path = (int)r[0], p.entries = (int)r[4], p.cshift = __builtin_ctzll((unsigned long long)r[3]);
-    p.splits = r[5], p.per_split = r[6], p.lds = r[8], p.col_tiles = r[9], p.row_tiles = r[10];
-    return NNC_OK;
+    if (!h16_mfma_shape(m, kdim, ncols)) return dx_plan(m, kdim, ncols, 1, k, cus, labels);
+    int entries = 0, cshift = 0;   // (cb_table_shape counts cshift up from 0)
+    cb_table_shape(1, k, entries, cshift);
+    CgPlan p = h16_mfma_plan<CgPlan>(h16_dx_tiles(m, kdim, ncols), (long long)hm_table_words(entries, cshift) * 4);
+    p.entries = entries, p.cshift = cshift;
+    return p;
 }
 
-static int gh_dc_plan(const char *fn, int dt, int64_t m, int64_t kdim, int64_t ncols, int32_t k, int32_t cus, uintptr_t labels, CgPlan &p)
+static CgPlan gh_dc_plan(int64_t m, int64_t kdim, int64_t ncols, int32_t k, int32_t cus, uintptr_t labels)
 {
-    p = dc_plan(m, kdim, ncols, 1, k, cus, labels);
-    if (p.path != NNC_CBMM_TILED) return NNC_OK;
-    int64_t r[NNC_CBDC_H16_PLAN_LEN];
-    const int rc = nnc_cbmm_dc_h16_plan(dt, m, kdim, ncols, 1, k, cus, (uint64_t)labels, r);
-    if (rc != NNC_OK) return rc;
-    if (r[0] != NNC_CBMM_MFMA) return fail(NNC_EINVAL, std::string(fn) + ": the half plan of m > 16 is not the MFMA path");
-    p = CgPlan{};
-    p.path = (int)r[0], p.rlog2 = __builtin_ctzll((unsigned long long)r[3]);
-    p.splits = r[4], p.per_split = r[5], p.lds = r[7], p.col_tiles = r[8], p.row_tiles = r[9], p.terms_log2 = (int)r[10];
-    return NNC_OK;
+    if (!h16_mfma_shape(m, kdim, ncols)) return dc_plan(m, kdim, ncols, 1, k, cus, labels);
+    CgPlan p = h16_mfma_plan<CgPlan>(h16_dc_tiles(m, kdim, ncols), ((long long)k << dc_rlog2(k)) * 8);
+    p.rlog2 = dc_rlog2(k);
+    return p;
 }
-
-static inline int64_t gh_dc_ws_bytes(int path, long long nbins) { return path == NNC_CBMM_ZERO ? 0 : CBG_HDR_BYTES + 8LL * nbins; }
 
 // ------------------------------------------------------------------ launches
 template <typename XT, int VB, int MT>
@@ -224,7 +201,7 @@ struct GradCase {
     DcLaunch dc;
 };
 struct MfmaCase {
-    int dt;
+    int dt, a;                // a: 0 (uint8 labels only)
     DxMfma dx;
     DcMfma dc;
 };
@@ -234,21 +211,17 @@ static const GradCase kBf16Cases[] = {CBG_U8_STREAM_CASES(BF_CASE)};
 static const GradCase kF16Cases[] = {CBG_U8_STREAM_CASES(HF_CASE)};
 #undef BF_CASE
 #undef HF_CASE
-static_assert(sizeof(kBf16Cases) == sizeof(kF16Cases), "one stream table per dtype, the same cases");
 static const MfmaCase kMfmaCases[] = {
-    {NNC_DT_BF16, launch_dx_mfma<bf16_t>, launch_dc_mfma<bf16_t>},
-    {NNC_DT_F16, launch_dx_mfma<f16_t>, launch_dc_mfma<f16_t>},
+    {NNC_DT_BF16, 0, launch_dx_mfma<bf16_t>, launch_dc_mfma<bf16_t>},
+    {NNC_DT_F16, 0, launch_dx_mfma<f16_t>, launch_dc_mfma<f16_t>},
 };
 static const CbgCaseNames kGradNames = {true, nullptr, true};
-
-static inline const GradCase (&stream_cases(int dt))[sizeof(kBf16Cases) / sizeof(GradCase)] { return dt == NNC_DT_BF16 ? kBf16Cases : kF16Cases; }
-static inline const MfmaCase &mfma_case(int dt) { return kMfmaCases[dt == NNC_DT_BF16 ? 0 : 1]; }
 
 // ------------------------------------------------------------------ C ABI
 static int gh_check(const char *fn, int x_dtype, int64_t m, int64_t kdim, int64_t ncols, int32_t k, int64_t group_rows)
 {
-    if (x_dtype != NNC_DT_BF16 && x_dtype != NNC_DT_F16) return fail(NNC_EINVAL, std::string(fn) + ": x_dtype must be NNC_DT_BF16 or NNC_DT_F16");
-    return gg_check(fn, m, kdim, ncols, k, group_rows);
+    const int rc = h16_check_dtype(fn, x_dtype);
+    return rc != NNC_OK ? rc : gg_check(fn, m, kdim, ncols, k, group_rows);
 }
 
 // the group fields behind the record of the ungrouped half plan (`rec`: its NNC_CBDX_H16_PLAN_LEN = NNC_CBDC_H16_PLAN_LEN values)
@@ -272,9 +245,8 @@ extern "C" int nnc_cbmm_grouped_dx_h16_plan(int x_dtype, int64_t m, int64_t kdim
     if (rc != NNC_OK) return rc;
     if (cus < 1) return fail(NNC_EINVAL, std::string(fn) + ": cus < 1");
     if (!out) return fail(NNC_EINVAL, std::string(fn) + ": out is NULL");
-    CgPlan p;
-    if ((rc = gh_dx_plan(fn, x_dtype, m, kdim, ncols, k, cus, (uintptr_t)labels_addr, p)) != NNC_OK) return rc;
-    if ((rc = cbg_plan_out(fn, stream_cases(x_dtype), kGradNames, p.path, 0, p.vb, p.mt, cus, out)) != NNC_OK) return rc;
+    const CgPlan p = gh_dx_plan(m, kdim, ncols, k, cus, (uintptr_t)labels_addr);
+    if ((rc = cbg_plan_out(fn, h16_cases(x_dtype, kBf16Cases, kF16Cases), kGradNames, p.path, 0, p.vb, p.mt, cus, out)) != NNC_OK) return rc;
     if ((rc = nnc_cbmm_dx_h16_plan(x_dtype, m, kdim, ncols, 1, k, cus, labels_addr, out)) != NNC_OK) return rc;   // the shared fields: the ungrouped record
     gh_plan_tail(p, kdim, group_rows, out + NNC_CBDX_H16_PLAN_LEN);
     return NNC_OK;
@@ -294,10 +266,11 @@ extern "C" int nnc_cbmm_grouped_dx_h16(const void *g, int x_dtype, int64_t m, in
         return fail(NNC_EINVAL, "nnc_cbmm_grouped_dx_h16: g or dx is not aligned to its element size");
     const int64_t need = nnc_cbmm_grouped_dx_h16_workspace_bytes(m, kdim, ncols);
     if ((rc = cb_check_workspace(fn, "nnc_cbmm_grouped_dx_h16_workspace_bytes", workspace, workspace_bytes, need, 4, "workspace not 4-byte aligned")) != NNC_OK) return rc;
-    CgPlan p;
-    if ((rc = gh_dx_plan(fn, x_dtype, m, kdim, ncols, k, cu_count(), reinterpret_cast<uintptr_t>(labels), p)) != NNC_OK) return rc;
+    const CgPlan p = gh_dx_plan(m, kdim, ncols, k, cu_count(), reinterpret_cast<uintptr_t>(labels));
     const GradCase *gc;
-    if ((rc = cbg_stream_case(fn, stream_cases(x_dtype), kGradNames, p.path, 0, p.vb, p.mt, gc)) != NNC_OK) return rc;
+    if ((rc = cbg_stream_case(fn, h16_cases(x_dtype, kBf16Cases, kF16Cases), kGradNames, p.path, 0, p.vb, p.mt, gc)) != NNC_OK) return rc;
+    const MfmaCase *mc;
+    if ((rc = h16_mfma_case(fn, kMfmaCases, kGradNames, p.path, x_dtype, 0, mc)) != NNC_OK) return rc;
     hipStream_t s = S(stream);
     return cbg_run_dx(p.path, p.splits, m, kdim, dx, dx_dtype, workspace, s, [&](int direct, void *out) {
         if (p.path == NNC_CBMM_STREAM) {
@@ -305,7 +278,7 @@ extern "C" int nnc_cbmm_grouped_dx_h16(const void *g, int x_dtype, int64_t m, in
                    p.entries, p.cshift, p.rows_per_group, group_rows, direct, out);
             LAUNCHCHK("k_cbdx_stream_grouped (h16)");
         } else {
-            mfma_case(x_dtype).dx(dim3((unsigned)(p.col_tiles * p.row_tiles), (unsigned)p.splits), (size_t)p.lds, s, g, m, kdim, labels, ncols, centers_dev, k,
+            mc->dx(dim3((unsigned)(p.col_tiles * p.row_tiles), (unsigned)p.splits), (size_t)p.lds, s, g, m, kdim, labels, ncols, centers_dev, k,
                                   p.entries, p.cshift, __builtin_ctz(tile_groups(group_rows)), p.col_tiles, p.per_split, group_rows, direct, out);
             LAUNCHCHK("k_cbdx_mfma_grouped");
         }
@@ -316,7 +289,7 @@ extern "C" int nnc_cbmm_grouped_dx_h16(const void *g, int x_dtype, int64_t m, in
 extern "C" int64_t nnc_cbmm_grouped_dc_h16_workspace_bytes(int64_t m, int64_t kdim, int64_t ncols, int32_t k, int64_t group_rows)
 {
     if (gg_check("nnc_cbmm_grouped_dc_h16_workspace_bytes", m, kdim, ncols, k, group_rows) != NNC_OK) return 0;
-    return gh_dc_ws_bytes(dc_plan(m, kdim, ncols, 1, k, CB_PLAN_CUS, 0).path, gg_groups(kdim, group_rows) * k);
+    return h16_dc_ws_bytes(dc_plan(m, kdim, ncols, 1, k, CB_PLAN_CUS, 0).path, gg_groups(kdim, group_rows) * k);
 }
 
 extern "C" int nnc_cbmm_grouped_dc_h16_plan(int x_dtype, int64_t m, int64_t kdim, int64_t ncols, int32_t k, int64_t group_rows, int32_t cus,
@@ -327,11 +300,10 @@ extern "C" int nnc_cbmm_grouped_dc_h16_plan(int x_dtype, int64_t m, int64_t kdim
     if (rc != NNC_OK) return rc;
     if (cus < 1) return fail(NNC_EINVAL, std::string(fn) + ": cus < 1");
     if (!out) return fail(NNC_EINVAL, std::string(fn) + ": out is NULL");
-    CgPlan p;
-    if ((rc = gh_dc_plan(fn, x_dtype, m, kdim, ncols, k, cus, (uintptr_t)labels_addr, p)) != NNC_OK) return rc;
-    if ((rc = cbg_plan_out(fn, stream_cases(x_dtype), kGradNames, p.path, 0, p.vb, p.mt, cus, out)) != NNC_OK) return rc;
+    const CgPlan p = gh_dc_plan(m, kdim, ncols, k, cus, (uintptr_t)labels_addr);
+    if ((rc = cbg_plan_out(fn, h16_cases(x_dtype, kBf16Cases, kF16Cases), kGradNames, p.path, 0, p.vb, p.mt, cus, out)) != NNC_OK) return rc;
     if ((rc = nnc_cbmm_dc_h16_plan(x_dtype, m, kdim, ncols, 1, k, cus, labels_addr, out)) != NNC_OK) return rc;   // the shared fields: the ungrouped record
-    out[11] = gh_dc_ws_bytes(p.path, gg_groups(kdim, group_rows) * k);                                            // (NNC_CBDC_P_WORKSPACE: G * k bins)
+    out[NNC_CBDC_P_WORKSPACE] = h16_dc_ws_bytes(p.path, gg_groups(kdim, group_rows) * k);                                            // (G * k bins)
     gh_plan_tail(p, kdim, group_rows, out + NNC_CBDC_H16_PLAN_LEN);
     return NNC_OK;
 }
@@ -348,10 +320,11 @@ extern "C" int nnc_cbmm_grouped_dc_h16(const void *x, const void *g, int x_dtype
         return fail(NNC_EINVAL, "nnc_cbmm_grouped_dc_h16: x or g is not aligned to its element size");
     const int64_t need = nnc_cbmm_grouped_dc_h16_workspace_bytes(m, kdim, ncols, k, group_rows);
     if ((rc = cb_check_workspace(fn, "nnc_cbmm_grouped_dc_h16_workspace_bytes", workspace, workspace_bytes, need, 8, "workspace not 8-byte aligned")) != NNC_OK) return rc;
-    CgPlan p;
-    if ((rc = gh_dc_plan(fn, x_dtype, m, kdim, ncols, k, cu_count(), reinterpret_cast<uintptr_t>(labels), p)) != NNC_OK) return rc;
+    const CgPlan p = gh_dc_plan(m, kdim, ncols, k, cu_count(), reinterpret_cast<uintptr_t>(labels));
     const GradCase *gc;
-    if ((rc = cbg_stream_case(fn, stream_cases(x_dtype), kGradNames, p.path, 0, p.vb, p.mt, gc)) != NNC_OK) return rc;
+    if ((rc = cbg_stream_case(fn, h16_cases(x_dtype, kBf16Cases, kF16Cases), kGradNames, p.path, 0, p.vb, p.mt, gc)) != NNC_OK) return rc;
+    const MfmaCase *mc;
+    if ((rc = h16_mfma_case(fn, kMfmaCases, kGradNames, p.path, x_dtype, 0, mc)) != NNC_OK) return rc;
     hipStream_t s = S(stream);
     const int nbins = (int)(gg_groups(kdim, group_rows) * k);
     return cbg_run_dc(p.path, x, g, x_dtype, m, kdim, ncols, nbins, dc, out_f64, workspace, need, s, [&](uint32_t *hdr, unsigned long long *sums) {
@@ -360,7 +333,7 @@ extern "C" int nnc_cbmm_grouped_dc_h16(const void *x, const void *g, int x_dtype
                    p.terms_log2, p.rows_per_group, group_rows, hdr, sums);
             LAUNCHCHK("k_cbdc_stream_grouped (h16)");
         } else {
-            mfma_case(x_dtype).dc(dim3((unsigned)(p.col_tiles * p.row_tiles), (unsigned)p.splits), (size_t)p.lds, s, x, g, m, kdim, labels, ncols, k, p.rlog2,
+            mc->dc(dim3((unsigned)(p.col_tiles * p.row_tiles), (unsigned)p.splits), (size_t)p.lds, s, x, g, m, kdim, labels, ncols, k, p.rlog2,
                                   __builtin_ctz(tile_groups(group_rows)), p.terms_log2, p.col_tiles, p.per_split, group_rows, hdr, sums);
             LAUNCHCHK("k_cbdc_mfma_grouped");
         }

@@ -19,11 +19,15 @@
 //             for every element whose scaled value is a normal bf16); fp16 operands are not scaled.  The epilogue bins the
 //             accumulators: cbdc_fix, the 64-bit LDS atomicAdd into the replicated bins, cbdc_flush.
 // Everything past m, kdim, ncols and the end of a split is zero in both images, never memory.  No float atomics; no host read.
+// The two main loops are shared with the other four half backward units (section 27): dxm_accumulate (nnc_cbdxm.hpp) around this
+// form's label load and lookup, dcm_accumulate (nnc_cbgrad_h16.hpp) in front of this form's epilogue; the tiles and splits of the
+// MFMA plan and the half glue of the entry points are nnc_cbh16plan.hpp's.
 #include "nnc_cbdxm.hpp"
-#include "nnc_cbtile.hpp"
+#include "nnc_cbgrad_h16.hpp"
+#include "nnc_cbh16plan.hpp"
 
 // ------------------------------------------------------------------ dx, m > 16
-// (the label load, dxm_load_labels, is nnc_cbdxm.hpp's: the group-wise kernel of nnc_cbgrad_grouped_h16.hip runs it too)
+// (the main loop, dxm_accumulate, and the label load, dxm_load_labels, are nnc_cbdxm.hpp's)
 // grid (kdim tiles * m tiles, splits of ncols), HM_THREADS threads.  `out` is dx (direct 1: float32, 2: XT) or the float32 partials
 // [split][m][kdim] (direct 0).  cols_per_split is a multiple of HM_BK.
 template <typename XT, typename LT, bool XVEC>
@@ -44,15 +48,12 @@ __global__ __launch_bounds__(HM_THREADS) void k_cbdx_mfma(const XT *__restrict__
     const bool row_ok = gi < kdim;
     const LT *lrow = labels + gi * ncols;
     uint32_t lw[4 * LB];
-    uint4 gf[2];
 
-    auto load = [&](long long ob) {
+    auto load_w = [&](long long ob) {
         const long long left = T.k_hi - (ob + T.wk0);
         dxm_load_labels<LT>(lrow + ob + T.wk0, row_ok ? (int)std::max(0LL, std::min(16LL, left)) : 0, lw);
-#pragma unroll
-        for (int i = 0; i < 2; ++i) gf[i] = hm_load_x<XT, XVEC>(g, m, ncols, T.m0, ob, T.k_hi, T.t + i * HM_THREADS);
     };
-    auto store = [&](long long ob) {
+    auto store_w = [&](long long ob) {
         float w[16];
 #pragma unroll
         for (int j = 0; j < 16; ++j) {
@@ -60,40 +61,14 @@ __global__ __launch_bounds__(HM_THREADS) void k_cbdx_mfma(const XT *__restrict__
             w[j] = (row_ok && ob + T.wk0 + j < T.k_hi) ? cb[CbTable<LT>::index(l, k, cshift, T.lane)] : 0.0f;
         }
         hm_store_w(ws, T.wc, T.wk0, w);
-#pragma unroll
-        for (int i = 0; i < 2; ++i) hm_store_x(gs, T.t + i * HM_THREADS, gf[i]);
     };
 
     typename HFrag<XT>::C acc[2][2];
-    hm_clear<XT>(acc);
-    load(T.k_lo);
-    for (long long ob = T.k_lo; ob < T.k_hi; ob += HM_BK) {
-        __syncthreads();   // the table is filled (first step); the images of the step before have been read
-        store(ob);
-        __syncthreads();
-        if (ob + HM_BK < T.k_hi) load(ob + HM_BK);
-        hm_step(gs, ws, T.wm, T.wn, T.fr, T.fh, acc);
-    }
+    dxm_accumulate<XT, XVEC>(g, m, ncols, T, gs, ws, acc, load_w, store_w);
     hm_store_y<XT>(acc, T.n0, T.m0, T.wm, T.wn, T.lane, m, kdim, nullptr, 0, direct, out_);
 }
 
 // ------------------------------------------------------------------ dc, m > 16
-// the value of the 16 bits `h` as XT, scaled by 2^sc (bf16; fp16 is staged as it is: sc = 0), as the float32 hm_store_w rounds back
-template <typename XT> __device__ __forceinline__ float dcm_staged(uint32_t h, int sc)
-{
-    const float v = (float)__builtin_bit_cast(XT, (unsigned short)h);
-    return std::is_same<XT, bf16_t>::value ? ldexpf(v, sc) : v;
-}
-
-// 8 values of consecutive r into column `col` of an image [128][HM_LD] at r offset k0 (a multiple of 8): one 16-byte store
-template <typename XT> __device__ __forceinline__ void dcm_store8(XT *img, int col, int k0, const float (&w)[8])
-{
-    typename HFrag<XT>::V v;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) v[j] = (XT)w[j];
-    *reinterpret_cast<typename HFrag<XT>::V *>(img + col * HM_LD + k0) = v;
-}
-
 // grid (ncols tiles * kdim tiles, splits of m), HM_THREADS threads.  LDS: the two images, then the bins [k][1 << rlog2] int64.
 // rows_per_split is a multiple of HM_BK.  XVEC: x and g 4-byte aligned, kdim and ncols even.
 template <typename XT, typename LT, bool XVEC>
@@ -108,86 +83,23 @@ __global__ __launch_bounds__(HM_THREADS) void k_cbdc_mfma(const XT *__restrict__
     unsigned long long *bins = reinterpret_cast<unsigned long long *>(gs + HM_BN * HM_LD);
     int scx, scg, Sw;
     if (!cbdc_begin(hdr, m, terms_log2, bins, k << rlog2, scx, scg, Sw)) return;   // (uniform over the launch)
-    if (!std::is_same<XT, bf16_t>::value) {             // fp16: every product and sum is a normal float32 as it is
-        Sw += scx + scg;
-        scx = scg = 0;
-    }
+    dcm_scales<XT>(scx, scg, Sw);
 
     const HmTile T = hm_tile(col_tiles, rows_per_split, m);   // n0: the first column o, m0: the first index row i, [k_lo, k_hi): rows r
-    const unsigned short *x16 = reinterpret_cast<const unsigned short *>(x), *g16 = reinterpret_cast<const unsigned short *>(g);
-    // element arm: column wc of both tiles, rows wk0 .. wk0 + 15, two values per word; XVEC: columns 2 pc, 2 pc + 1, rows pk0 .. pk0 + 7,
-    // a word per row (the two columns)
-    const int pc = T.t & 63, pk0 = (T.t >> 6) * 8;
-    uint32_t xw[8], gw[8];
-
-    auto load = [&](long long rb) {
-        if constexpr (XVEC) {
-            const long long ii = T.m0 + 2 * pc, oo = T.n0 + 2 * pc;
-#pragma unroll
-            for (int j = 0; j < 8; ++j) {
-                const long long r = rb + pk0 + j;
-                xw[j] = (r < T.k_hi && ii < kdim) ? *reinterpret_cast<const uint32_t *>(x16 + r * kdim + ii) : 0u;
-                gw[j] = (r < T.k_hi && oo < ncols) ? *reinterpret_cast<const uint32_t *>(g16 + r * ncols + oo) : 0u;
-            }
-        } else {
-            const long long ii = T.m0 + T.wc, oo = T.n0 + T.wc;
-#pragma unroll
-            for (int j = 0; j < 8; ++j) {
-                const long long r = rb + T.wk0 + 2 * j;
-                const uint32_t x0 = (r < T.k_hi && ii < kdim) ? x16[r * kdim + ii] : 0u, x1 = (r + 1 < T.k_hi && ii < kdim) ? x16[(r + 1) * kdim + ii] : 0u;
-                const uint32_t g0 = (r < T.k_hi && oo < ncols) ? g16[r * ncols + oo] : 0u, g1 = (r + 1 < T.k_hi && oo < ncols) ? g16[(r + 1) * ncols + oo] : 0u;
-                xw[j] = x0 | x1 << 16;
-                gw[j] = g0 | g1 << 16;
-            }
-        }
-    };
-    auto store = [&]() {
-        if constexpr (XVEC) {
-            float a0[8], a1[8], b0[8], b1[8];
-#pragma unroll
-            for (int j = 0; j < 8; ++j) {
-                a0[j] = dcm_staged<XT>(xw[j] & 0xFFFFu, scx), a1[j] = dcm_staged<XT>(xw[j] >> 16, scx);
-                b0[j] = dcm_staged<XT>(gw[j] & 0xFFFFu, scg), b1[j] = dcm_staged<XT>(gw[j] >> 16, scg);
-            }
-            dcm_store8(xs, 2 * pc, pk0, a0);
-            dcm_store8(xs, 2 * pc + 1, pk0, a1);
-            dcm_store8(gs, 2 * pc, pk0, b0);
-            dcm_store8(gs, 2 * pc + 1, pk0, b1);
-        } else {
-            float a[16], b[16];
-#pragma unroll
-            for (int j = 0; j < 8; ++j) {
-                a[2 * j] = dcm_staged<XT>(xw[j] & 0xFFFFu, scx), a[2 * j + 1] = dcm_staged<XT>(xw[j] >> 16, scx);
-                b[2 * j] = dcm_staged<XT>(gw[j] & 0xFFFFu, scg), b[2 * j + 1] = dcm_staged<XT>(gw[j] >> 16, scg);
-            }
-            hm_store_w(xs, T.wc, T.wk0, a);
-            hm_store_w(gs, T.wc, T.wk0, b);
-        }
-    };
-
     typename HFrag<XT>::C acc[2][2];
-    hm_clear<XT>(acc);
-    load(T.k_lo);
-    for (long long rb = T.k_lo; rb < T.k_hi; rb += HM_BK) {
-        __syncthreads();   // the bins are cleared (first step); the images of the step before have been read
-        store();
-        __syncthreads();
-        if (rb + HM_BK < T.k_hi) load(rb + HM_BK);
-        hm_step(xs, gs, T.wm, T.wn, T.fr, T.fh, acc);
-    }
+    dcm_accumulate<XT, XVEC>(x, g, kdim, ncols, T, scx, scg, xs, gs, acc);
 
-    // register r of lane l of accumulator (a, b) is dW'[i = m0 + wm + 32 a + (r & 3) + 8 (r >> 2) + 4 (l >> 5)][o = n0 + wn + 32 b + (l & 31)];
-    // the label loads are coalesced over the 32 lanes of a row
+    // accumulator (a, b) holds dW'[i][o] (hm_acc_row, hm_acc_col); the label loads are coalesced over the 32 lanes of a row
     const int rep = T.t & ((1 << rlog2) - 1);
 #pragma unroll
     for (int a = 0; a < 2; ++a) {
 #pragma unroll
         for (int b = 0; b < 2; ++b) {
-            const long long o = T.n0 + T.wn + b * 32 + T.fr;
+            const long long o = hm_acc_col(T.n0 + T.wn, b, T.lane);
             if (o >= ncols) continue;
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
-                const long long i = T.m0 + T.wm + a * 32 + (r & 3) + 8 * (r >> 2) + 4 * (T.lane >> 5);
+                const long long i = hm_acc_row(T.m0 + T.wm, a, r, T.lane);
                 if (i >= kdim) continue;
                 const uint32_t l = (uint32_t)labels[i * ncols + o];
                 if (l < (uint32_t)k) atomicAdd(&bins[(l << rlog2) + rep], cbdc_fix(acc[a][b][r], Sw));
@@ -198,43 +110,25 @@ __global__ __launch_bounds__(HM_THREADS) void k_cbdc_mfma(const XT *__restrict__
 }
 
 // ------------------------------------------------------------------ plans (host)
-// m <= 16 and the empty shapes: section 12's plans (dx_plan, dc_plan) field for field.  m > 16: the MFMA tile, the reduced dimension
-// split by section 16's rule for CB_PLAN_CUS compute units whatever the device (cus changes the stream grid only).
-static long long h16_splits(long long tiles, long long extent, long long &per_split)
-{
-    const long long s = std::max(1LL, std::min({cdiv(2LL * CB_PLAN_CUS, tiles), extent / (2 * HM_BK), 16LL}));
-    per_split = cdiv(cdiv(extent, s), HM_BK) * HM_BK;   // every split starts on a whole step
-    return cdiv(extent, per_split);
-}
-
+// m <= 16 and the empty shapes: section 12's plans (dx_plan, dc_plan) field for field.  m > 16: nnc_cbh16plan.hpp's tiles and splits
+// with the per-bank table of k_cbmm_mfma (dx) or the replicated bins (dc).
 static CgPlan dx_plan_h16(long long m, long long kdim, long long ncols, int lb, int k, int cus, uintptr_t labels)
 {
-    if (m == 0 || kdim == 0 || ncols == 0 || m <= CB_SKINNY_M) return dx_plan(m, kdim, ncols, lb, k, cus, labels);
-    CgPlan p{};
-    p.path = NNC_CBMM_MFMA;
-    p.col_tiles = cdiv(kdim, HM_BN);
-    p.row_tiles = cdiv(m, HM_BM);
-    p.splits = h16_splits(p.col_tiles * p.row_tiles, ncols, p.per_split);
-    cb_table_shape(lb, k, p.entries, p.cshift);   // the per-bank table of k_cbmm_mfma
-    p.lds = (long long)hm_table_words(p.entries, p.cshift) * 4 + (long long)(HM_BM + HM_BN) * HM_LD * 2;
+    if (!h16_mfma_shape(m, kdim, ncols)) return dx_plan(m, kdim, ncols, lb, k, cus, labels);
+    int entries = 0, cshift = 0;   // (cb_table_shape counts cshift up from 0)
+    cb_table_shape(lb, k, entries, cshift);
+    CgPlan p = h16_mfma_plan<CgPlan>(h16_dx_tiles(m, kdim, ncols), (long long)hm_table_words(entries, cshift) * 4);
+    p.entries = entries, p.cshift = cshift;
     return p;
 }
 
 static CgPlan dc_plan_h16(long long m, long long kdim, long long ncols, int lb, int k, int cus, uintptr_t labels)
 {
-    if (m == 0 || kdim == 0 || ncols == 0 || m <= CB_SKINNY_M) return dc_plan(m, kdim, ncols, lb, k, cus, labels);
-    CgPlan p{};
-    p.path = NNC_CBMM_MFMA;
+    if (!h16_mfma_shape(m, kdim, ncols)) return dc_plan(m, kdim, ncols, lb, k, cus, labels);
+    CgPlan p = h16_mfma_plan<CgPlan>(h16_dc_tiles(m, kdim, ncols), ((long long)k << dc_rlog2(k)) * 8);
     p.rlog2 = dc_rlog2(k);
-    p.col_tiles = cdiv(ncols, HM_BN);
-    p.row_tiles = cdiv(kdim, HM_BM);
-    p.splits = h16_splits(p.col_tiles * p.row_tiles, m, p.per_split);
-    p.lds = (long long)(HM_BM + HM_BN) * HM_LD * 2 + ((long long)k << p.rlog2) * 8;
-    p.terms_log2 = ceil_log2(kdim * ncols * p.splits);
     return p;
 }
-
-static inline int64_t dc_ws_bytes_h16(int path, int k) { return path == NNC_CBMM_ZERO ? 0 : CBG_HDR_BYTES + 8LL * k; }
 
 // ------------------------------------------------------------------ launches
 template <typename XT, typename LT, int VB, int MT>
@@ -273,8 +167,7 @@ template <typename XT, typename LT>
 static void launch_dc_mfma(dim3 grid, size_t lds, hipStream_t s, const void *x, const void *g, long long m, long long kdim, const void *labels,
                            long long ncols, int k, int rlog2, int tl, long long col_tiles, long long rps, uint32_t *hdr, unsigned long long *sums)
 {
-    const bool xvec = reinterpret_cast<uintptr_t>(x) % 4 == 0 && reinterpret_cast<uintptr_t>(g) % 4 == 0 && kdim % 2 == 0 && ncols % 2 == 0;
-    hipLaunchKernelGGL((xvec ? k_cbdc_mfma<XT, LT, true> : k_cbdc_mfma<XT, LT, false>), grid, dim3(HM_THREADS), lds, s, reinterpret_cast<const XT *>(x),
+    hipLaunchKernelGGL((dcm_xvec(x, g, kdim, ncols) ? k_cbdc_mfma<XT, LT, true> : k_cbdc_mfma<XT, LT, false>), grid, dim3(HM_THREADS), lds, s, reinterpret_cast<const XT *>(x),
                        reinterpret_cast<const XT *>(g), m, kdim, reinterpret_cast<const LT *>(labels), ncols, k, rlog2, tl, col_tiles, rps, hdr, sums);
 }
 
@@ -294,7 +187,7 @@ struct GradCase {
     DcLaunch dc;
 };
 struct MfmaCase {
-    int dt, lb;
+    int dt, a;                // a: label_bytes
     DxMfma dx;
     DcMfma dc;
 };
@@ -308,31 +201,17 @@ static const GradCase kF16Cases[] = {CBG_U8_STREAM_CASES(HF_U8) CBG_U16_STREAM_C
 #undef BF_U16
 #undef HF_U8
 #undef HF_U16
-static_assert(sizeof(kBf16Cases) == sizeof(kF16Cases), "one stream table per dtype, the same cases");
 static const MfmaCase kMfmaCases[] = {
     {NNC_DT_BF16, 1, launch_dx_mfma<bf16_t, uint8_t>, launch_dc_mfma<bf16_t, uint8_t>}, {NNC_DT_BF16, 2, launch_dx_mfma<bf16_t, uint16_t>, launch_dc_mfma<bf16_t, uint16_t>},
     {NNC_DT_F16, 1, launch_dx_mfma<f16_t, uint8_t>, launch_dc_mfma<f16_t, uint8_t>},   {NNC_DT_F16, 2, launch_dx_mfma<f16_t, uint16_t>, launch_dc_mfma<f16_t, uint16_t>},
 };
 static const CbgCaseNames kGradNames = {false, "label_bytes", true};
 
-static inline const GradCase (&stream_cases(int dt))[sizeof(kBf16Cases) / sizeof(GradCase)] { return dt == NNC_DT_BF16 ? kBf16Cases : kF16Cases; }
-
-// the MFMA instantiation of (dt, lb), or NNC_EINVAL in the wording of cbg_stream_case
-static int mfma_case(const char *fn, int path, int dt, int lb, const MfmaCase *&c)
-{
-    c = nullptr;
-    if (path != NNC_CBMM_MFMA) return NNC_OK;
-    for (const MfmaCase &e : kMfmaCases)
-        if (e.dt == dt && e.lb == lb) c = &e;
-    if (c) return NNC_OK;
-    return fail(NNC_EINVAL, std::string(fn) + ": no MFMA instantiation for dtype " + std::to_string(dt) + ", label_bytes " + std::to_string(lb));
-}
-
 // ------------------------------------------------------------------ C ABI
 static int h16_check(const char *fn, int x_dtype, int64_t m, int64_t kdim, int64_t ncols, int label_bytes, int32_t k)
 {
-    if (x_dtype != NNC_DT_BF16 && x_dtype != NNC_DT_F16) return fail(NNC_EINVAL, std::string(fn) + ": x_dtype must be NNC_DT_BF16 or NNC_DT_F16");
-    return cg_check(fn, m, kdim, ncols, label_bytes, k);
+    const int rc = h16_check_dtype(fn, x_dtype);
+    return rc != NNC_OK ? rc : cg_check(fn, m, kdim, ncols, label_bytes, k);
 }
 
 extern "C" int64_t nnc_cbmm_dx_h16_workspace_bytes(int64_t m, int64_t kdim, int64_t ncols, int label_bytes)
@@ -347,9 +226,9 @@ extern "C" int nnc_cbmm_dx_h16_plan(int x_dtype, int64_t m, int64_t kdim, int64_
     int rc = h16_check("nnc_cbmm_dx_h16_plan", x_dtype, m, kdim, ncols, label_bytes, k);
     if (rc != NNC_OK) return rc;
     const CgPlan p = dx_plan_h16(m, kdim, ncols, label_bytes, k, cus, (uintptr_t)labels_addr);
-    if ((rc = cbg_plan_out("nnc_cbmm_dx_h16_plan", stream_cases(x_dtype), kGradNames, p.path, label_bytes, p.vb, p.mt, cus, out)) != NNC_OK) return rc;
+    if ((rc = cbg_plan_out("nnc_cbmm_dx_h16_plan", h16_cases(x_dtype, kBf16Cases, kF16Cases), kGradNames, p.path, label_bytes, p.vb, p.mt, cus, out)) != NNC_OK) return rc;
     const MfmaCase *mc;
-    if ((rc = mfma_case("nnc_cbmm_dx_h16_plan", p.path, x_dtype, label_bytes, mc)) != NNC_OK) return rc;
+    if ((rc = h16_mfma_case("nnc_cbmm_dx_h16_plan", kMfmaCases, kGradNames, p.path, x_dtype, label_bytes, mc)) != NNC_OK) return rc;
     const int64_t v[NNC_CBDX_H16_PLAN_LEN] = {p.path, p.vb, p.mt, p.path == NNC_CBMM_STREAM || p.path == NNC_CBMM_MFMA ? 1LL << p.cshift : 0, p.entries,
                                               p.splits, p.per_split, p.aligned, p.lds, p.col_tiles, p.row_tiles, cbg_dx_ws_bytes(p.splits, m, kdim), x_dtype};
     for (int i = 0; i < NNC_CBDX_H16_PLAN_LEN; ++i) out[i] = v[i];
@@ -373,9 +252,9 @@ extern "C" int nnc_cbmm_dx_h16(const void *g, int x_dtype, int64_t m, int64_t kd
     if ((rc = cb_check_workspace(fn, "nnc_cbmm_dx_h16_workspace_bytes", workspace, workspace_bytes, need, 4, "workspace not 4-byte aligned")) != NNC_OK) return rc;
     const CgPlan p = dx_plan_h16(m, kdim, ncols, label_bytes, k, cu_count(), reinterpret_cast<uintptr_t>(labels));
     const GradCase *gc;
-    if ((rc = cbg_stream_case(fn, stream_cases(x_dtype), kGradNames, p.path, label_bytes, p.vb, p.mt, gc)) != NNC_OK) return rc;
+    if ((rc = cbg_stream_case(fn, h16_cases(x_dtype, kBf16Cases, kF16Cases), kGradNames, p.path, label_bytes, p.vb, p.mt, gc)) != NNC_OK) return rc;
     const MfmaCase *mc;
-    if ((rc = mfma_case(fn, p.path, x_dtype, label_bytes, mc)) != NNC_OK) return rc;
+    if ((rc = h16_mfma_case(fn, kMfmaCases, kGradNames, p.path, x_dtype, label_bytes, mc)) != NNC_OK) return rc;
     hipStream_t s = S(stream);
     return cbg_run_dx(p.path, p.splits, m, kdim, dx, dx_dtype, workspace, s, [&](int direct, void *out) {
         if (p.path == NNC_CBMM_STREAM) {
@@ -394,7 +273,7 @@ extern "C" int nnc_cbmm_dx_h16(const void *g, int x_dtype, int64_t m, int64_t kd
 extern "C" int64_t nnc_cbmm_dc_h16_workspace_bytes(int64_t m, int64_t kdim, int64_t ncols, int label_bytes, int32_t k)
 {
     if (cg_check("nnc_cbmm_dc_h16_workspace_bytes", m, kdim, ncols, label_bytes, k) != NNC_OK) return 0;
-    return dc_ws_bytes_h16(dc_plan_h16(m, kdim, ncols, label_bytes, k, CB_PLAN_CUS, 0).path, k);
+    return h16_dc_ws_bytes(dc_plan_h16(m, kdim, ncols, label_bytes, k, CB_PLAN_CUS, 0).path, k);
 }
 
 extern "C" int nnc_cbmm_dc_h16_plan(int x_dtype, int64_t m, int64_t kdim, int64_t ncols, int label_bytes, int32_t k, int32_t cus, uint64_t labels_addr,
@@ -403,11 +282,11 @@ extern "C" int nnc_cbmm_dc_h16_plan(int x_dtype, int64_t m, int64_t kdim, int64_
     int rc = h16_check("nnc_cbmm_dc_h16_plan", x_dtype, m, kdim, ncols, label_bytes, k);
     if (rc != NNC_OK) return rc;
     const CgPlan p = dc_plan_h16(m, kdim, ncols, label_bytes, k, cus, (uintptr_t)labels_addr);
-    if ((rc = cbg_plan_out("nnc_cbmm_dc_h16_plan", stream_cases(x_dtype), kGradNames, p.path, label_bytes, p.vb, p.mt, cus, out)) != NNC_OK) return rc;
+    if ((rc = cbg_plan_out("nnc_cbmm_dc_h16_plan", h16_cases(x_dtype, kBf16Cases, kF16Cases), kGradNames, p.path, label_bytes, p.vb, p.mt, cus, out)) != NNC_OK) return rc;
     const MfmaCase *mc;
-    if ((rc = mfma_case("nnc_cbmm_dc_h16_plan", p.path, x_dtype, label_bytes, mc)) != NNC_OK) return rc;
+    if ((rc = h16_mfma_case("nnc_cbmm_dc_h16_plan", kMfmaCases, kGradNames, p.path, x_dtype, label_bytes, mc)) != NNC_OK) return rc;
     const int64_t v[NNC_CBDC_H16_PLAN_LEN] = {p.path, p.vb, p.mt, p.path == NNC_CBMM_ZERO ? 0 : 1LL << p.rlog2, p.splits, p.per_split, p.aligned, p.lds,
-                                              p.col_tiles, p.row_tiles, p.terms_log2, dc_ws_bytes_h16(p.path, k), x_dtype};
+                                              p.col_tiles, p.row_tiles, p.terms_log2, h16_dc_ws_bytes(p.path, k), x_dtype};
     for (int i = 0; i < NNC_CBDC_H16_PLAN_LEN; ++i) out[i] = v[i];
     return NNC_OK;
 }
@@ -426,9 +305,9 @@ extern "C" int nnc_cbmm_dc_h16(const void *x, const void *g, int x_dtype, int64_
     if ((rc = cb_check_workspace(fn, "nnc_cbmm_dc_h16_workspace_bytes", workspace, workspace_bytes, need, 8, "workspace not 8-byte aligned")) != NNC_OK) return rc;
     const CgPlan p = dc_plan_h16(m, kdim, ncols, label_bytes, k, cu_count(), reinterpret_cast<uintptr_t>(labels));
     const GradCase *gc;
-    if ((rc = cbg_stream_case(fn, stream_cases(x_dtype), kGradNames, p.path, label_bytes, p.vb, p.mt, gc)) != NNC_OK) return rc;
+    if ((rc = cbg_stream_case(fn, h16_cases(x_dtype, kBf16Cases, kF16Cases), kGradNames, p.path, label_bytes, p.vb, p.mt, gc)) != NNC_OK) return rc;
     const MfmaCase *mc;
-    if ((rc = mfma_case(fn, p.path, x_dtype, label_bytes, mc)) != NNC_OK) return rc;
+    if ((rc = h16_mfma_case(fn, kMfmaCases, kGradNames, p.path, x_dtype, label_bytes, mc)) != NNC_OK) return rc;
     hipStream_t s = S(stream);
     return cbg_run_dc(p.path, x, g, x_dtype, m, kdim, ncols, (int)k, dc, out_f64, workspace, need, s, [&](uint32_t *hdr, unsigned long long *sums) {
         if (p.path == NNC_CBMM_STREAM) {

@@ -1,10 +1,8 @@
-// nnc_cbgrad_h16.hpp -- the main loop of a dc MFMA kernel on bf16 / fp16 activations as a function: the 128 (i) x 128 (o) tile of
-// dW = x^T g from two transposed LDS images.  It is k_cbdc_mfma's loop (nnc_cbgrad_h16.hip, the byte form)
-// statement for statement, and k_cbspdc_mfma (nnc_cbspgrad_h16.hip, the bitmap-sparse form, section 24) runs it; the two kernels
-// differ only in where the label of an accumulator comes from.  k_cbdc_mfma itself still carries its own copy of this text: calling
-// the function from it changed the order of its instructions (not their kind), and section 24's gate keeps every kernel of
-// nnc_cbgrad_h16.hip to the instruction stream it had.  A kernel keeps its signature, its LDS carve-up, cbdc_begin and the epilogue;
-// dcm_scales and dcm_accumulate are the rest.
+// nnc_cbgrad_h16.hpp -- the main loop of the dc MFMA kernels on bf16 / fp16 activations, written once: the
+// 128 (i) x 128 (o) tile of dW = x^T g from two transposed LDS images.  All five kernels run it (k_cbdc_mfma, k_cbspdc_mfma,
+// k_cbpkdc_mfma, k_cbdc_mfma_grouped, k_cbpkdc_mfma_grouped), so they hold the same accumulators and differ only in where the
+// label of an accumulator comes from.  A kernel keeps its signature, its LDS carve-up, cbdc_begin and the epilogue; dcm_scales and
+// dcm_accumulate are the rest.
 #pragma once
 #include "nnc_cbmfma.hpp"
 #include "nnc_cbtile.hpp"

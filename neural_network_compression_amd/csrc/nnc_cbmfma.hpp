@@ -4,7 +4,8 @@
 // kernel keeps its signature, its LDS carve-up, its table (cb_fill, and cb_refill on the walk through the groups), its label load
 // (a byte, two bytes, a packed field) and its table lookup, and calls these for the rest: the tile coordinates, the x fragments,
 // the two LDS images, the k step and the C / D epilogue.  The barriers, the load-next-before-MFMA order and the loop over the
-// k steps stay in the kernels, as the decode of the tiled float32 kernels does around nnc_cbtile.hpp.
+// k steps stay in these forward kernels, as the decode of the tiled float32 kernels does around nnc_cbtile.hpp; the backward kernels
+// on the same tile share theirs (dxm_accumulate of nnc_cbdxm.hpp, dcm_accumulate of nnc_cbgrad_h16.hpp).
 #pragma once
 #include "nnc_cbmm.hpp"
 
@@ -34,6 +35,12 @@ __device__ __forceinline__ HmTile hm_tile(long long col_tiles, long long rows_pe
     T.fh = (T.lane >> 5) * 8;
     return T;
 }
+
+// C / D: register r of lane l of a 32 x 32 accumulator is row (r & 3) + 8 (r >> 2) + 4 (l >> 5), column l & 31, and accumulator
+// (a, b) of a wave starts at (wm + 32 a, wn + 32 b).  The row and the column of the matrix, from those of the wave's quarter
+// (row0 = m0 + wm, col0 = n0 + wn):
+__device__ __forceinline__ long long hm_acc_row(long long row0, int a, int r, int lane) { return row0 + a * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5); }
+__device__ __forceinline__ long long hm_acc_col(long long col0, int b, int lane) { return col0 + b * 32 + (lane & 31); }
 
 // Fragment f (of the 128 rows x 4 fragments of 8; a thread loads f = t and t + HM_THREADS) of the x image of the step at kb: x[m0 +
 // f / 4, kb + 8 (f % 4) .. + 7], zero past m and past k_hi, never memory: a NaN there would reach valid outputs as NaN * 0.  XVEC:
@@ -108,24 +115,23 @@ __device__ __forceinline__ void hm_step(const XT *xs, const XT *ws, int wm, int 
     }
 }
 
-// C / D: register r of lane l is row (r & 3) + 8 (r >> 2) + 4 (l >> 5), column l & 31.  `out` is y (direct 1: float32, 2: XT; +
-// bias, ReLU here) or the float32 partials [split][m][ncols] (direct 0).
+// C / D (hm_acc_row, hm_acc_col).  `out` is y (direct 1: float32, 2: XT; + bias, ReLU here) or the float32 partials
+// [split][m][ncols] (direct 0).
 template <typename XT>
 __device__ __forceinline__ void hm_store_y(const typename HFrag<XT>::C (&acc)[2][2], long long n0, long long m0, int wm, int wn, int lane, long long m,
                                            long long ncols, const float *__restrict__ bias, int relu, int direct, void *__restrict__ out_)
 {
     float *outf = reinterpret_cast<float *>(out_);
-    const int fr = lane & 31;
 #pragma unroll
     for (int i = 0; i < 2; ++i) {
 #pragma unroll
         for (int j = 0; j < 2; ++j) {
-            const long long c = n0 + wn + j * 32 + fr;
+            const long long c = hm_acc_col(n0 + wn, j, lane);
             if (c >= ncols) continue;
             const float bv = (direct && bias) ? bias[c] : 0.0f;
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
-                const long long row = m0 + wm + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
+                const long long row = hm_acc_row(m0 + wm, i, r, lane);
                 if (row >= m) continue;
                 float v = acc[i][j][r];
                 if (direct) {

@@ -7,18 +7,21 @@
 //   m <= 16   k_cbpkdx_stream<XT> / k_cbpkdc_stream<XT> of nnc_cbpkgrad.hpp: section 15's stream plans and kernels with g and x
 //             widened as they are loaded and, for dx, the table of the rounded centres.  Bit for bit the float32 entry points on
 //             the widened inputs.
-//   k_cbpkdx_mfma  m > 16.  k_cbdx_mfma's tile, plan and splits (nnc_cbgrad_h16.hip); g is the A operand (hm_load_x / hm_store_x).
+//   k_cbpkdx_mfma  m > 16.  k_cbdx_mfma's tile, main loop (dxm_accumulate, nnc_cbdxm.hpp), tiles and splits (nnc_cbh16plan.hpp); g is
+//             the A operand (hm_load_x / hm_store_x).
 //             The B operand W^T: thread t owns index row n0 + (t mod 128) and the 16 consecutive o of its half of the k step, which
 //             are 8 bytes (4 bits) or 4 bytes (2 bits) of the packed row: naturally aligned (a row starts on 16 bytes, a split on
 //             a multiple of 32 columns) and inside the row (32 fields are at most one 16-byte granule).  One load, the fields looked
 //             up in the 2^BITS-entry per-bank table, hm_store_w.  A column at or past ncols is 0 in the image, not table[0]: the
 //             padding fields hold label 0, and a centre that rounds to Inf would otherwise meet the zero of the g image.
-//   k_cbpkdc_mfma  m > 16.  k_cbdc_mfma's main loop (nnc_cbgrad_h16.hpp), so the same accumulators; in the epilogue the 32 lanes of
+//   k_cbpkdc_mfma  m > 16.  k_cbdc_mfma's main loop (dcm_accumulate, nnc_cbgrad_h16.hpp), so the same accumulators; in the epilogue the 32 lanes of
 //             an accumulator row read 32 consecutive fields of one packed row (16 or 8 bytes): a lane loads the dword that holds
 //             its field, shifts and masks.  Every lane adds into its own copy of the K <= 16 bins (64 copies, at most 8 KiB).
 // No load leaves the packed buffer: rows past kdim and columns past the split (dx) or past ncols (dc) load nothing.  Everything past
 // m, kdim, ncols and the end of a split is zero in the images, never memory.  No float atomics; no host read.
+#include "nnc_cbdxm.hpp"
 #include "nnc_cbgrad_h16.hpp"
+#include "nnc_cbh16plan.hpp"
 #include "nnc_cbpkgrad.hpp"
 
 // ------------------------------------------------------------------ dx, m > 16
@@ -42,9 +45,8 @@ __global__ __launch_bounds__(HM_THREADS) void k_cbpkdx_mfma(const XT *__restrict
     const bool row_ok = gi < kdim;
     const unsigned char *prow = packed + (row_ok ? gi * row_bytes : 0LL);
     uint32_t lw[NW];
-    uint4 gf[2];
 
-    auto load = [&](long long ob) {
+    auto load_w = [&](long long ob) {
         const long long o0 = ob + T.wk0;                // a multiple of 16: the 16 fields are 16 * BITS / 8 aligned bytes
 #pragma unroll
         for (int d = 0; d < NW; ++d) lw[d] = 0u;
@@ -57,10 +59,8 @@ __global__ __launch_bounds__(HM_THREADS) void k_cbpkdx_mfma(const XT *__restrict
                 lw[0] = *reinterpret_cast<const uint32_t *>(p);
             }
         }
-#pragma unroll
-        for (int i = 0; i < 2; ++i) gf[i] = hm_load_x<XT, XVEC>(g, m, ncols, T.m0, ob, T.k_hi, T.t + i * HM_THREADS);
     };
-    auto store = [&](long long ob) {
+    auto store_w = [&](long long ob) {
         float w[16];
 #pragma unroll
         for (int j = 0; j < 16; ++j) {
@@ -69,20 +69,10 @@ __global__ __launch_bounds__(HM_THREADS) void k_cbpkdx_mfma(const XT *__restrict
             w[j] = (row_ok && ob + T.wk0 + j < T.k_hi) ? cb[(l << PK_CSHIFT) | (T.lane & (PK_COPIES - 1))] : 0.0f;
         }
         hm_store_w(ws, T.wc, T.wk0, w);
-#pragma unroll
-        for (int i = 0; i < 2; ++i) hm_store_x(gs, T.t + i * HM_THREADS, gf[i]);
     };
 
     typename HFrag<XT>::C acc[2][2];
-    hm_clear<XT>(acc);
-    load(T.k_lo);
-    for (long long ob = T.k_lo; ob < T.k_hi; ob += HM_BK) {
-        __syncthreads();   // the table is filled (first step); the images of the step before have been read
-        store(ob);
-        __syncthreads();
-        if (ob + HM_BK < T.k_hi) load(ob + HM_BK);
-        hm_step(gs, ws, T.wm, T.wn, T.fr, T.fh, acc);
-    }
+    dxm_accumulate<XT, XVEC>(g, m, ncols, T, gs, ws, acc, load_w, store_w);
     hm_store_y<XT>(acc, T.n0, T.m0, T.wm, T.wn, T.lane, m, kdim, nullptr, 0, direct, out_);
 }
 
@@ -108,22 +98,21 @@ __global__ __launch_bounds__(HM_THREADS) void k_cbpkdc_mfma(const XT *__restrict
     typename HFrag<XT>::C acc[2][2];
     dcm_accumulate<XT, XVEC>(x, g, kdim, ncols, T, scx, scg, xs, gs, acc);
 
-    // register r of lane l of accumulator (a, b) is dW'[i = m0 + wm + 32 a + (r & 3) + 8 (r >> 2) + 4 (l >> 5)][o = n0 + wn + 32 b + (l & 31)]:
-    // the 32 lanes of a row read 32 consecutive fields of packed row i, which start on a multiple of 32 columns; a lane's dword lies
-    // inside the padded row when its column lies inside the matrix
+    // accumulator (a, b) holds dW'[i][o] (hm_acc_row, hm_acc_col): the 32 lanes of a row read 32 consecutive fields of packed row i,
+    // which start on a multiple of 32 columns; a lane's dword lies inside the padded row when its column lies inside the matrix
     unsigned long long *mybins = bins + T.lane;
 #pragma unroll
     for (int a = 0; a < 2; ++a) {
 #pragma unroll
         for (int b = 0; b < 2; ++b) {
-            const long long o = T.n0 + T.wn + b * 32 + T.fr;
+            const long long o = hm_acc_col(T.n0 + T.wn, b, T.lane);
             if (o >= ncols) continue;
             const long long bitpos = o * BITS;
             const unsigned char *pcol = packed + ((bitpos >> 5) << 2);
             const int sh = (int)(bitpos & 31);
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
-                const long long i = T.m0 + T.wm + a * 32 + (r & 3) + 8 * (r >> 2) + 4 * (T.lane >> 5);
+                const long long i = hm_acc_row(T.m0 + T.wm, a, r, T.lane);
                 if (i >= kdim) continue;
                 const uint32_t l = (*reinterpret_cast<const uint32_t *>(pcol + i * row_bytes) >> sh) & MASK;
                 if (l < (uint32_t)k) atomicAdd(&mybins[l << PKG_RLOG2], cbdc_fix(acc[a][b][r], Sw));
@@ -134,50 +123,25 @@ __global__ __launch_bounds__(HM_THREADS) void k_cbpkdc_mfma(const XT *__restrict
 }
 
 // ------------------------------------------------------------------ plans (host)
-// m <= 16 and the empty shapes: section 15's plans (pg_dx_plan, pg_dc_plan) field for field.  m > 16: the byte form's half plans
-// (nnc_cbmm_dx_h16_plan / nnc_cbmm_dc_h16_plan at label_bytes = 1) in every field the records share, so the tiles, the splits, S and
-// every image are that call's; the table is the packed form's (2^bits entries x PK_COPIES), the bins one copy per lane.  NNC_OK, or
-// that plan's error.
-static int h16_dx_plan(int dt, long long m, long long kdim, long long ncols, int bits, int k, int cus, PgPlan &p)
+// m <= 16 and the empty shapes: section 15's plans (pg_dx_plan, pg_dc_plan) field for field.  m > 16: nnc_cbh16plan.hpp's tiles and
+// splits, so the tiles, the splits, S and every image are the byte form's; the table is the packed form's (2^bits entries x
+// PK_COPIES), the bins one copy per lane.
+static PgPlan h16_dx_plan(long long m, long long kdim, long long ncols, int bits, int cus)
 {
-    if (m == 0 || kdim == 0 || ncols == 0 || m <= CB_SKINNY_M) {
-        p = pg_dx_plan(m, kdim, ncols, bits, cus);
-        return NNC_OK;
-    }
-    p = PgPlan{};
-    int64_t d[NNC_CBDX_H16_PLAN_LEN];
-    const int rc = nnc_cbmm_dx_h16_plan(dt, m, kdim, ncols, 1, k, CB_PLAN_CUS, 0, d);
-    if (rc != NNC_OK) return rc;
-    p.path = (int)d[NNC_CBDX_P_PATH];
+    if (!h16_mfma_shape(m, kdim, ncols)) return pg_dx_plan(m, kdim, ncols, bits, cus);
+    PgPlan p = h16_mfma_plan<PgPlan>(h16_dx_tiles(m, kdim, ncols), (long long)hm_table_words(1 << bits, PK_CSHIFT) * 4);
     p.entries = 1 << bits;
     p.copies = PK_COPIES;
-    p.splits = d[NNC_CBDX_P_SPLITS];
-    p.per_split = d[NNC_CBDX_P_CPS];
-    p.col_tiles = d[NNC_CBDX_P_COL_TILES];
-    p.row_tiles = d[NNC_CBDX_P_ROW_TILES];
-    p.lds = (long long)hm_table_words(p.entries, PK_CSHIFT) * 4 + (long long)(HM_BM + HM_BN) * HM_LD * 2;
-    return NNC_OK;
+    return p;
 }
 
-static int h16_dc_plan(int dt, long long m, long long kdim, long long ncols, int bits, int k, int cus, PgPlan &p)
+static int h16_dc_plan(long long m, long long kdim, long long ncols, int bits, int k, int cus, PgPlan &p)
 {
-    if (m == 0 || kdim == 0 || ncols == 0 || m <= CB_SKINNY_M) return pg_dc_plan(m, kdim, ncols, bits, k, cus, p);
-    p = PgPlan{};
-    int64_t d[NNC_CBDC_H16_PLAN_LEN];
-    const int rc = nnc_cbmm_dc_h16_plan(dt, m, kdim, ncols, 1, k, CB_PLAN_CUS, 0, d);
-    if (rc != NNC_OK) return rc;
-    p.path = (int)d[NNC_CBDC_P_PATH];
+    if (!h16_mfma_shape(m, kdim, ncols)) return pg_dc_plan(m, kdim, ncols, bits, k, cus, p);
+    p = h16_mfma_plan<PgPlan>(h16_dc_tiles(m, kdim, ncols), ((long long)k << PKG_RLOG2) * 8);
     p.copies = 1 << PKG_RLOG2;
-    p.splits = d[NNC_CBDC_P_SPLITS];
-    p.per_split = d[NNC_CBDC_P_RPS];
-    p.col_tiles = d[NNC_CBDC_P_COL_TILES];
-    p.row_tiles = d[NNC_CBDC_P_ROW_TILES];
-    p.terms_log2 = (int)d[NNC_CBDC_P_TERMS_LOG2];
-    p.lds = (long long)(HM_BM + HM_BN) * HM_LD * 2 + ((long long)k << PKG_RLOG2) * 8;
     return NNC_OK;
 }
-
-static inline int64_t h16_dc_ws_bytes(int path, int k) { return path == NNC_CBMM_ZERO ? 0 : CBG_HDR_BYTES + 8LL * k; }
 
 // ------------------------------------------------------------------ launches
 template <typename XT, int BITS, int VB, int MT>
@@ -228,7 +192,7 @@ struct StreamCase {
     DcStream dc;
 };
 struct MfmaCase {
-    int dt, bits;
+    int dt, a;                // a: bits
     DxMfma dx;
     DcMfma dc;
 };
@@ -238,31 +202,17 @@ static const StreamCase kBf16Cases[] = {PKG_STREAM_CASES(BF_CASE)};
 static const StreamCase kF16Cases[] = {PKG_STREAM_CASES(HF_CASE)};
 #undef BF_CASE
 #undef HF_CASE
-static_assert(sizeof(kBf16Cases) == sizeof(kF16Cases), "one stream table per dtype, the same cases");
 static const MfmaCase kMfmaCases[] = {
     {NNC_DT_BF16, 4, launch_dx_mfma<bf16_t, 4>, launch_dc_mfma<bf16_t, 4>}, {NNC_DT_BF16, 2, launch_dx_mfma<bf16_t, 2>, launch_dc_mfma<bf16_t, 2>},
     {NNC_DT_F16, 4, launch_dx_mfma<f16_t, 4>, launch_dc_mfma<f16_t, 4>},   {NNC_DT_F16, 2, launch_dx_mfma<f16_t, 2>, launch_dc_mfma<f16_t, 2>},
 };
 static const CbgCaseNames kPkNames = {false, "bits", true};
 
-static inline const StreamCase (&stream_cases(int dt))[sizeof(kBf16Cases) / sizeof(StreamCase)] { return dt == NNC_DT_BF16 ? kBf16Cases : kF16Cases; }
-
-// the MFMA instantiation of (dt, bits), or NNC_EINVAL in the wording of cbg_stream_case
-static int mfma_case(const char *fn, int path, int dt, int bits, const MfmaCase *&c)
-{
-    c = nullptr;
-    if (path != NNC_CBMM_MFMA) return NNC_OK;
-    for (const MfmaCase &e : kMfmaCases)
-        if (e.dt == dt && e.bits == bits) c = &e;
-    if (c) return NNC_OK;
-    return fail(NNC_EINVAL, std::string(fn) + ": no MFMA instantiation for dtype " + std::to_string(dt) + ", bits " + std::to_string(bits));
-}
-
 // ------------------------------------------------------------------ C ABI
 static int h16_check(const char *fn, int x_dtype, int64_t m, int64_t kdim, int64_t ncols, int bits, int32_t k)
 {
-    if (x_dtype != NNC_DT_BF16 && x_dtype != NNC_DT_F16) return fail(NNC_EINVAL, std::string(fn) + ": x_dtype must be NNC_DT_BF16 or NNC_DT_F16");
-    return pg_check(fn, m, kdim, ncols, bits, k);
+    const int rc = h16_check_dtype(fn, x_dtype);
+    return rc != NNC_OK ? rc : pg_check(fn, m, kdim, ncols, bits, k);
 }
 
 // the one group of the forward call: every index row of the layer, as a multiple of 32
@@ -310,9 +260,7 @@ extern "C" int nnc_cbpk_h16(const void *x, int x_dtype, int64_t m, int64_t kdim,
 extern "C" int64_t nnc_cbpk_dx_h16_workspace_bytes(int64_t m, int64_t kdim, int64_t ncols, int bits)
 {
     if (pg_check("nnc_cbpk_dx_h16_workspace_bytes", m, kdim, ncols, bits, 1) != NNC_OK) return 0;
-    PgPlan p;
-    if (h16_dx_plan(NNC_DT_BF16, m, kdim, ncols, bits, 1, CB_PLAN_CUS, p) != NNC_OK) return 0;
-    return cbg_dx_ws_bytes(p.splits, m, kdim);
+    return cbg_dx_ws_bytes(h16_dx_plan(m, kdim, ncols, bits, CB_PLAN_CUS).splits, m, kdim);
 }
 
 extern "C" int nnc_cbpk_dx_h16_plan(int x_dtype, int64_t m, int64_t kdim, int64_t ncols, int bits, int32_t k, int32_t cus, int64_t *out)
@@ -320,11 +268,10 @@ extern "C" int nnc_cbpk_dx_h16_plan(int x_dtype, int64_t m, int64_t kdim, int64_
     const char *fn = "nnc_cbpk_dx_h16_plan";
     int rc = h16_check(fn, x_dtype, m, kdim, ncols, bits, k);
     if (rc != NNC_OK) return rc;
-    PgPlan p;
-    if ((rc = h16_dx_plan(x_dtype, m, kdim, ncols, bits, k, std::max(cus, 1), p)) != NNC_OK) return rc;
-    if ((rc = cbg_plan_out(fn, stream_cases(x_dtype), kPkNames, p.path, bits, p.vb, p.mt, cus, out)) != NNC_OK) return rc;
+    const PgPlan p = h16_dx_plan(m, kdim, ncols, bits, std::max(cus, 1));
+    if ((rc = cbg_plan_out(fn, h16_cases(x_dtype, kBf16Cases, kF16Cases), kPkNames, p.path, bits, p.vb, p.mt, cus, out)) != NNC_OK) return rc;
     const MfmaCase *mc;
-    if ((rc = mfma_case(fn, p.path, x_dtype, bits, mc)) != NNC_OK) return rc;
+    if ((rc = h16_mfma_case(fn, kMfmaCases, kPkNames, p.path, x_dtype, bits, mc)) != NNC_OK) return rc;
     const int64_t v[NNC_CBPKDX_H16_PLAN_LEN] = {p.path, p.vb, p.mt, p.cols, p.copies, p.entries, p.splits, p.per_split, p.lds, p.col_tiles, p.row_tiles,
                                                 cbg_dx_ws_bytes(p.splits, m, kdim), x_dtype};
     for (int i = 0; i < NNC_CBPKDX_H16_PLAN_LEN; ++i) out[i] = v[i];
@@ -346,12 +293,11 @@ extern "C" int nnc_cbpk_dx_h16(const void *g, int x_dtype, int64_t m, int64_t kd
         return fail(NNC_EINVAL, "nnc_cbpk_dx_h16: g or dx is not aligned to its element size");
     const int64_t need = nnc_cbpk_dx_h16_workspace_bytes(m, kdim, ncols, bits);
     if ((rc = cb_check_workspace(fn, "nnc_cbpk_dx_h16_workspace_bytes", workspace, workspace_bytes, need, 4, "workspace must be 4-byte aligned")) != NNC_OK) return rc;
-    PgPlan p;
-    if ((rc = h16_dx_plan(x_dtype, m, kdim, ncols, bits, k, CB_PLAN_CUS, p)) != NNC_OK) return rc;
+    PgPlan p = h16_dx_plan(m, kdim, ncols, bits, CB_PLAN_CUS);
     const StreamCase *sc;
-    if ((rc = cbg_stream_case(fn, stream_cases(x_dtype), kPkNames, p.path, bits, p.vb, p.mt, sc)) != NNC_OK) return rc;
+    if ((rc = cbg_stream_case(fn, h16_cases(x_dtype, kBf16Cases, kF16Cases), kPkNames, p.path, bits, p.vb, p.mt, sc)) != NNC_OK) return rc;
     const MfmaCase *mc;
-    if ((rc = mfma_case(fn, p.path, x_dtype, bits, mc)) != NNC_OK) return rc;
+    if ((rc = h16_mfma_case(fn, kMfmaCases, kPkNames, p.path, x_dtype, bits, mc)) != NNC_OK) return rc;
     hipStream_t s = S(stream);
     if (p.path == NNC_CBMM_STREAM) p = pg_dx_plan(m, kdim, ncols, bits, cu_count());      // (the row groups of this device)
     const unsigned char *pk = reinterpret_cast<const unsigned char *>(packed);
@@ -374,7 +320,7 @@ extern "C" int64_t nnc_cbpk_dc_h16_workspace_bytes(int64_t m, int64_t kdim, int6
 {
     if (pg_check("nnc_cbpk_dc_h16_workspace_bytes", m, kdim, ncols, bits, k) != NNC_OK) return 0;
     PgPlan p;
-    if (h16_dc_plan(NNC_DT_BF16, m, kdim, ncols, bits, k, CB_PLAN_CUS, p) != NNC_OK) return 0;
+    if (h16_dc_plan(m, kdim, ncols, bits, k, CB_PLAN_CUS, p) != NNC_OK) return 0;
     return h16_dc_ws_bytes(p.path, k);
 }
 
@@ -384,10 +330,10 @@ extern "C" int nnc_cbpk_dc_h16_plan(int x_dtype, int64_t m, int64_t kdim, int64_
     int rc = h16_check(fn, x_dtype, m, kdim, ncols, bits, k);
     if (rc != NNC_OK) return rc;
     PgPlan p;
-    if ((rc = h16_dc_plan(x_dtype, m, kdim, ncols, bits, k, std::max(cus, 1), p)) != NNC_OK) return rc;
-    if ((rc = cbg_plan_out(fn, stream_cases(x_dtype), kPkNames, p.path, bits, p.vb, p.mt, cus, out)) != NNC_OK) return rc;
+    if ((rc = h16_dc_plan(m, kdim, ncols, bits, k, std::max(cus, 1), p)) != NNC_OK) return rc;
+    if ((rc = cbg_plan_out(fn, h16_cases(x_dtype, kBf16Cases, kF16Cases), kPkNames, p.path, bits, p.vb, p.mt, cus, out)) != NNC_OK) return rc;
     const MfmaCase *mc;
-    if ((rc = mfma_case(fn, p.path, x_dtype, bits, mc)) != NNC_OK) return rc;
+    if ((rc = h16_mfma_case(fn, kMfmaCases, kPkNames, p.path, x_dtype, bits, mc)) != NNC_OK) return rc;
     const int64_t v[NNC_CBPKDC_H16_PLAN_LEN] = {p.path, p.vb, p.mt, p.cols, p.path == NNC_CBMM_ZERO ? 0 : p.copies, p.splits, p.per_split, p.lds, p.col_tiles,
                                                 p.row_tiles, p.terms_log2, h16_dc_ws_bytes(p.path, k), x_dtype};
     for (int i = 0; i < NNC_CBPKDC_H16_PLAN_LEN; ++i) out[i] = v[i];
@@ -405,13 +351,13 @@ extern "C" int nnc_cbpk_dc_h16(const void *x, const void *g, int x_dtype, int64_
     if (m > 0 && kdim > 0 && ncols > 0 && (!x || !g)) return fail(NNC_EINVAL, "nnc_cbpk_dc_h16: x or g is NULL");
     if (reinterpret_cast<uintptr_t>(x) % 2 || reinterpret_cast<uintptr_t>(g) % 2) return fail(NNC_EINVAL, "nnc_cbpk_dc_h16: x or g is not aligned to its element size");
     PgPlan p;
-    if ((rc = h16_dc_plan(x_dtype, m, kdim, ncols, bits, k, CB_PLAN_CUS, p)) != NNC_OK) return rc;
+    if ((rc = h16_dc_plan(m, kdim, ncols, bits, k, CB_PLAN_CUS, p)) != NNC_OK) return rc;
     const int64_t need = h16_dc_ws_bytes(p.path, k);
     if ((rc = cb_check_workspace(fn, "nnc_cbpk_dc_h16_workspace_bytes", workspace, workspace_bytes, need, 8, "workspace not 8-byte aligned")) != NNC_OK) return rc;
     const StreamCase *sc;
-    if ((rc = cbg_stream_case(fn, stream_cases(x_dtype), kPkNames, p.path, bits, p.vb, p.mt, sc)) != NNC_OK) return rc;
+    if ((rc = cbg_stream_case(fn, h16_cases(x_dtype, kBf16Cases, kF16Cases), kPkNames, p.path, bits, p.vb, p.mt, sc)) != NNC_OK) return rc;
     const MfmaCase *mc;
-    if ((rc = mfma_case(fn, p.path, x_dtype, bits, mc)) != NNC_OK) return rc;
+    if ((rc = h16_mfma_case(fn, kMfmaCases, kPkNames, p.path, x_dtype, bits, mc)) != NNC_OK) return rc;
     hipStream_t s = S(stream);
     if (p.path == NNC_CBMM_STREAM && (rc = pg_dc_plan(m, kdim, ncols, bits, k, cu_count(), p)) != NNC_OK) return rc;   // (the row groups of this device)
     const unsigned char *pk = reinterpret_cast<const unsigned char *>(packed);

@@ -3,8 +3,10 @@
 // W_h[i, o] = the centre centers[i / group_rows][label (i, o)] rounded to the type of g, a label >= K reading 0 and a padding field
 // past ncols forming no product; products are exact in float32, every sum is float32, dc is binned into G x K exact integers.
 //
-// The plans are the ungrouped packed half ones (nnc_cbpk_dx_h16_plan / nnc_cbpk_dc_h16_plan) plus the group fields, as section 20
-// took the float32 ones: the path, the tiles, the splits, the order of every sum and S are those of nnc_cbpk_dx_h16 / nnc_cbpk_dc_h16.
+// The plans are the ungrouped packed half ones (section 15's stream plans; nnc_cbh16plan.hpp's tiles and splits at m > 16) plus the
+// group fields, as section 20 took the float32 ones: the path, the tiles, the splits, the order of every sum and S are those of
+// nnc_cbpk_dx_h16 / nnc_cbpk_dc_h16.  The two main loops are the ungrouped kernels' (dxm_accumulate, dcm_accumulate), the pick of a
+// row's table or set tile_group_of (nnc_cbgrad_grouped.hpp).
 //   m <= 16   k_cbpkdx_stream_grouped<XT> / k_cbpkdc_stream_grouped<XT> of nnc_cbpkgrad_grouped.hpp: section 20's kernels with g and
 //             x widened as they are loaded and, for dx, the per-wave tables of the rounded centres.
 //   k_cbpkdx_mfma_grouped  m > 16.  k_cbpkdx_mfma (nnc_cbpk_h16.hip) with one whole per-bank table (2^BITS entries x PK_COPIES: 2 KiB
@@ -13,7 +15,10 @@
 //   k_cbpkdc_mfma_grouped  m > 16.  dcm_accumulate unchanged, then k_cbpkdc_mfma's epilogue with one set of [K][64] bins per group of
 //             the tile: the 32 rows of an accumulator lie in one group, so the set is a scalar; one cbdc_flush per set.
 // No load leaves the packed buffer; everything past m, kdim, ncols and the end of a split is zero in the images, never memory.
+#include "nnc_cbdxm.hpp"
+#include "nnc_cbgrad_grouped.hpp"
 #include "nnc_cbgrad_h16.hpp"
+#include "nnc_cbh16plan.hpp"
 #include "nnc_cbpkgrad_grouped.hpp"
 
 // ------------------------------------------------------------------ dx, m > 16
@@ -35,10 +40,10 @@ __global__ __launch_bounds__(HM_THREADS) void k_cbpkdx_mfma_grouped(const XT *__
     XT *ws = gs + HM_BM * HM_LD;                        // [HM_BN][HM_LD]: W^T tile, [i][o]
 
     const HmTile T = hm_tile(col_tiles, cols_per_split, ncols);   // n0: the first index row i, m0: the first row of g, [k_lo, k_hi): columns o
-    const long long q0 = T.n0 / group_rows, groups = (kdim + group_rows - 1) / group_rows;
+    const TileGroups G = tile_groups_at(T.n0, kdim, group_rows);
     for (int j = threadIdx.x; j < all; j += HM_THREADS) {          // (a table past the last group repeats it, unread)
         const int t = j / ENTRIES, e = j % ENTRIES;
-        stage[j] = e < k ? (float)(XT)centers[std::min(q0 + t, groups - 1) * k + e] : 0.0f;
+        stage[j] = e < k ? (float)(XT)centers[std::min(G.q0 + t, G.groups - 1) * k + e] : 0.0f;
     }
     __syncthreads();
     for (int w = threadIdx.x; w < (all << PK_CSHIFT); w += HM_THREADS) cb[w] = stage[w >> PK_CSHIFT];
@@ -46,11 +51,10 @@ __global__ __launch_bounds__(HM_THREADS) void k_cbpkdx_mfma_grouped(const XT *__
     const long long gi = T.n0 + T.wc;
     const bool row_ok = gi < kdim;
     const unsigned char *prow = packed + (row_ok ? gi * row_bytes : 0LL);
-    const float *tab = cb + std::min((long long)tables - 1, gi / group_rows - q0) * (ENTRIES * PK_COPIES) + (T.lane & (PK_COPIES - 1));
+    const float *tab = cb + tile_group_of(G, gi, group_rows, tables) * (ENTRIES * PK_COPIES) + (T.lane & (PK_COPIES - 1));
     uint32_t lw[NW];
-    uint4 gf[2];
 
-    auto load = [&](long long ob) {
+    auto load_w = [&](long long ob) {
         const long long o0 = ob + T.wk0;                // a multiple of 16: the 16 fields are 16 * BITS / 8 aligned bytes
 #pragma unroll
         for (int d = 0; d < NW; ++d) lw[d] = 0u;
@@ -63,10 +67,8 @@ __global__ __launch_bounds__(HM_THREADS) void k_cbpkdx_mfma_grouped(const XT *__
                 lw[0] = *reinterpret_cast<const uint32_t *>(p);
             }
         }
-#pragma unroll
-        for (int i = 0; i < 2; ++i) gf[i] = hm_load_x<XT, XVEC>(g, m, ncols, T.m0, ob, T.k_hi, T.t + i * HM_THREADS);
     };
-    auto store = [&](long long ob) {
+    auto store_w = [&](long long ob) {
         float w[16];
 #pragma unroll
         for (int j = 0; j < 16; ++j) {
@@ -75,20 +77,10 @@ __global__ __launch_bounds__(HM_THREADS) void k_cbpkdx_mfma_grouped(const XT *__
             w[j] = (row_ok && ob + T.wk0 + j < T.k_hi) ? tab[l << PK_CSHIFT] : 0.0f;
         }
         hm_store_w(ws, T.wc, T.wk0, w);
-#pragma unroll
-        for (int i = 0; i < 2; ++i) hm_store_x(gs, T.t + i * HM_THREADS, gf[i]);
     };
 
     typename HFrag<XT>::C acc[2][2];
-    hm_clear<XT>(acc);
-    load(T.k_lo);
-    for (long long ob = T.k_lo; ob < T.k_hi; ob += HM_BK) {
-        __syncthreads();   // the tables are filled (first step); the images of the step before have been read
-        store(ob);
-        __syncthreads();
-        if (ob + HM_BK < T.k_hi) load(ob + HM_BK);
-        hm_step(gs, ws, T.wm, T.wn, T.fr, T.fh, acc);
-    }
+    dxm_accumulate<XT, XVEC>(g, m, ncols, T, gs, ws, acc, load_w, store_w);
     hm_store_y<XT>(acc, T.n0, T.m0, T.wm, T.wn, T.lane, m, kdim, nullptr, 0, direct, out_);
 }
 
@@ -114,74 +106,68 @@ __global__ __launch_bounds__(HM_THREADS) void k_cbpkdc_mfma_grouped(const XT *__
     typename HFrag<XT>::C acc[2][2];
     dcm_accumulate<XT, XVEC>(x, g, kdim, ncols, T, scx, scg, xs, gs, acc);
 
-    // register r of lane l of accumulator (a, b) is dW'[i = m0 + wm + 32 a + (r & 3) + 8 (r >> 2) + 4 (l >> 5)][o = n0 + wn + 32 b + (l & 31)]:
-    // the 32 rows of (a, b) start on a multiple of 32 and lie in one group, whose set is a scalar; the 32 lanes of a row read 32
-    // consecutive fields of packed row i, and a lane's dword lies inside the padded row when its column lies inside the matrix
-    const long long q0 = T.m0 / group_rows, groups = (kdim + group_rows - 1) / group_rows;
-    const int wm = __builtin_amdgcn_readfirstlane(threadIdx.x >> 7) * 64;   // T.wm, as a scalar
+    // accumulator (a, b) holds dW'[i][o] (hm_acc_row, hm_acc_col): its 32 rows lie in one group, whose set is a scalar; the 32 lanes
+    // of a row read 32 consecutive fields of packed row i, and a lane's dword lies inside the padded row when its column lies inside
+    // the matrix
+    const TileGroups G = tile_groups_at(T.m0, kdim, group_rows);
+    const long long row0 = tile_wave_row0(T.m0);
 #pragma unroll
     for (int a = 0; a < 2; ++a) {
-        const int set = (int)std::min((long long)sets - 1, (T.m0 + wm + a * 32) / group_rows - q0);
+        const int set = (int)tile_group_of(G, row0 + a * 32, group_rows, sets);
         unsigned long long *mybins = bins + (((long long)set * k) << PKG_RLOG2) + T.lane;
 #pragma unroll
         for (int b = 0; b < 2; ++b) {
-            const long long o = T.n0 + T.wn + b * 32 + T.fr;
+            const long long o = hm_acc_col(T.n0 + T.wn, b, T.lane);
             if (o >= ncols) continue;
             const long long bitpos = o * BITS;
             const unsigned char *pcol = packed + ((bitpos >> 5) << 2);
             const int sh = (int)(bitpos & 31);
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
-                const long long i = T.m0 + T.wm + a * 32 + (r & 3) + 8 * (r >> 2) + 4 * (T.lane >> 5);
+                const long long i = hm_acc_row(T.m0 + T.wm, a, r, T.lane);
                 if (i >= kdim) continue;
                 const uint32_t l = (*reinterpret_cast<const uint32_t *>(pcol + i * row_bytes) >> sh) & MASK;
                 if (l < (uint32_t)k) atomicAdd(&mybins[l << PKG_RLOG2], cbdc_fix(acc[a][b][r], Sw));
             }
         }
     }
-    for (int t = 0; t < sets && q0 + t < groups; ++t) cbdc_flush(bins + (((long long)t * k) << PKG_RLOG2), k, PKG_RLOG2, sums + (q0 + t) * k);
+    for (int t = 0; t < sets && G.q0 + t < G.groups; ++t) cbdc_flush(bins + (((long long)t * k) << PKG_RLOG2), k, PKG_RLOG2, sums + (G.q0 + t) * k);
 }
 
 // ------------------------------------------------------------------ plans (host)
-// m <= 16 and the empty shapes: section 15's plans (pg_dx_plan, pg_dc_plan) with section 20's per-wave tables.  m > 16: the record
-// of the ungrouped packed half plan, with the LDS of the tables / sets of the tile's groups.
-static int pgh_dx_plan(const char *fn, int dt, int64_t m, int64_t kdim, int64_t ncols, int bits, int32_t k, int64_t group_rows, int cus, PgPlan &p, int &tables)
+// m <= 16 and the empty shapes: section 15's plans (pg_dx_plan, pg_dc_plan) with section 20's per-wave tables.  m > 16:
+// nnc_cbh16plan.hpp's tiles and splits, so those of nnc_cbpk_dx_h16 / nnc_cbpk_dc_h16, with the LDS of the tables / sets of the
+// tile's groups.
+static PgPlan pgh_dx_plan(int64_t m, int64_t kdim, int64_t ncols, int bits, int64_t group_rows, int cus, int &tables)
 {
-    p = pg_dx_plan(m, kdim, ncols, bits, cus);
+    if (h16_mfma_shape(m, kdim, ncols)) {
+        tables = tile_groups(group_rows);
+        PgPlan p = h16_mfma_plan<PgPlan>(h16_dx_tiles(m, kdim, ncols), (long long)hm_table_words(tables << bits, PK_CSHIFT) * 4);
+        p.entries = 1 << bits;
+        p.copies = PK_COPIES;
+        return p;
+    }
+    PgPlan p = pg_dx_plan(m, kdim, ncols, bits, cus);
     tables = 0;
     if (p.path == NNC_CBMM_STREAM) {
         tables = CB_WAVES;
         p.lds = (long long)CB_WAVES * p.entries * PK_COPIES * 4;
     }
-    if (p.path != NNC_CBMM_TILED) return NNC_OK;
-    int64_t r[NNC_CBPKDX_H16_PLAN_LEN];
-    const int rc = nnc_cbpk_dx_h16_plan(dt, m, kdim, ncols, bits, k, std::max(cus, 1), r);
-    if (rc != NNC_OK) return rc;
-    if (r[0] != NNC_CBMM_MFMA) return fail(NNC_EINVAL, std::string(fn) + ": the half plan of m > 16 is not the MFMA path");
-    p = PgPlan{};
-    tables = tile_groups(group_rows);
-    p.path = (int)r[0], p.copies = (int)r[4], p.entries = (int)r[5], p.splits = r[6], p.per_split = r[7], p.col_tiles = r[9], p.row_tiles = r[10];
-    p.lds = (long long)hm_table_words(tables * p.entries, PK_CSHIFT) * 4 + (long long)(HM_BM + HM_BN) * HM_LD * 2;
-    return NNC_OK;
+    return p;
 }
 
-static int pgh_dc_plan(const char *fn, int dt, int64_t m, int64_t kdim, int64_t ncols, int bits, int32_t k, int64_t group_rows, int cus, PgPlan &p, int &sets)
+static int pgh_dc_plan(int64_t m, int64_t kdim, int64_t ncols, int bits, int32_t k, int64_t group_rows, int cus, PgPlan &p, int &sets)
 {
-    int rc = pg_dc_plan(m, kdim, ncols, bits, k, cus, p);
-    if (rc != NNC_OK) return rc;
+    if (h16_mfma_shape(m, kdim, ncols)) {
+        sets = tile_groups(group_rows);
+        p = h16_mfma_plan<PgPlan>(h16_dc_tiles(m, kdim, ncols), (((long long)sets * k) << PKG_RLOG2) * 8);
+        p.copies = 1 << PKG_RLOG2;
+        return NNC_OK;
+    }
+    const int rc = pg_dc_plan(m, kdim, ncols, bits, k, cus, p);
     sets = p.path == NNC_CBMM_STREAM ? 1 : 0;
-    if (p.path != NNC_CBMM_TILED) return NNC_OK;
-    int64_t r[NNC_CBPKDC_H16_PLAN_LEN];
-    if ((rc = nnc_cbpk_dc_h16_plan(dt, m, kdim, ncols, bits, k, std::max(cus, 1), r)) != NNC_OK) return rc;
-    if (r[0] != NNC_CBMM_MFMA) return fail(NNC_EINVAL, std::string(fn) + ": the half plan of m > 16 is not the MFMA path");
-    p = PgPlan{};
-    sets = tile_groups(group_rows);
-    p.path = (int)r[0], p.copies = (int)r[4], p.splits = r[5], p.per_split = r[6], p.col_tiles = r[8], p.row_tiles = r[9], p.terms_log2 = (int)r[10];
-    p.lds = (long long)(HM_BM + HM_BN) * HM_LD * 2 + (((long long)sets * k) << PKG_RLOG2) * 8;
-    return NNC_OK;
+    return rc;
 }
-
-static inline int64_t pgh_dc_ws_bytes(int path, long long nbins) { return path == NNC_CBMM_ZERO ? 0 : CBG_HDR_BYTES + 8LL * nbins; }
 
 // ------------------------------------------------------------------ launches
 template <typename XT, int BITS, int VB, int MT>
@@ -234,7 +220,7 @@ struct StreamCase {
     DcStream dc;
 };
 struct MfmaCase {
-    int dt, bits;
+    int dt, a;                // a: bits
     DxMfma dx;
     DcMfma dc;
 };
@@ -244,27 +230,17 @@ static const StreamCase kBf16Cases[] = {PKG_STREAM_CASES(BF_CASE)};
 static const StreamCase kF16Cases[] = {PKG_STREAM_CASES(HF_CASE)};
 #undef BF_CASE
 #undef HF_CASE
-static_assert(sizeof(kBf16Cases) == sizeof(kF16Cases), "one stream table per dtype, the same cases");
 static const MfmaCase kMfmaCases[] = {
     {NNC_DT_BF16, 4, launch_dx_mfma<bf16_t, 4>, launch_dc_mfma<bf16_t, 4>}, {NNC_DT_BF16, 2, launch_dx_mfma<bf16_t, 2>, launch_dc_mfma<bf16_t, 2>},
     {NNC_DT_F16, 4, launch_dx_mfma<f16_t, 4>, launch_dc_mfma<f16_t, 4>},   {NNC_DT_F16, 2, launch_dx_mfma<f16_t, 2>, launch_dc_mfma<f16_t, 2>},
 };
 static const CbgCaseNames kPkNames = {true, "bits", true};
 
-static inline const StreamCase (&stream_cases(int dt))[sizeof(kBf16Cases) / sizeof(StreamCase)] { return dt == NNC_DT_BF16 ? kBf16Cases : kF16Cases; }
-
-static const MfmaCase &mfma_case(int dt, int bits)
-{
-    for (const MfmaCase &e : kMfmaCases)
-        if (e.dt == dt && e.bits == bits) return e;
-    return kMfmaCases[0];     // (dt and bits were checked: not reached)
-}
-
 // ------------------------------------------------------------------ C ABI
 static int pgh_check(const char *fn, int x_dtype, int64_t m, int64_t kdim, int64_t ncols, int bits, int32_t k, int64_t group_rows)
 {
-    if (x_dtype != NNC_DT_BF16 && x_dtype != NNC_DT_F16) return fail(NNC_EINVAL, std::string(fn) + ": x_dtype must be NNC_DT_BF16 or NNC_DT_F16");
-    return pgg_check(fn, m, kdim, ncols, bits, k, group_rows);
+    const int rc = h16_check_dtype(fn, x_dtype);
+    return rc != NNC_OK ? rc : pgg_check(fn, m, kdim, ncols, bits, k, group_rows);
 }
 
 static void pgh_plan_tail(const PgPlan &p, int64_t kdim, int64_t group_rows, int held, int64_t *out)
@@ -288,10 +264,10 @@ extern "C" int nnc_cbpk_grouped_dx_h16_plan(int x_dtype, int64_t m, int64_t kdim
     if (!out) return fail(NNC_EINVAL, std::string(fn) + ": out is NULL");
     PgPlan p;
     int tables;
-    if ((rc = pgh_dx_plan(fn, x_dtype, m, kdim, ncols, bits, k, group_rows, cus, p, tables)) != NNC_OK) return rc;
-    if ((rc = cbg_plan_out(fn, stream_cases(x_dtype), kPkNames, p.path, bits, p.vb, p.mt, cus, out)) != NNC_OK) return rc;
+    p = pgh_dx_plan(m, kdim, ncols, bits, group_rows, cus, tables);
+    if ((rc = cbg_plan_out(fn, h16_cases(x_dtype, kBf16Cases, kF16Cases), kPkNames, p.path, bits, p.vb, p.mt, cus, out)) != NNC_OK) return rc;
     if ((rc = nnc_cbpk_dx_h16_plan(x_dtype, m, kdim, ncols, bits, k, cus, out)) != NNC_OK) return rc;   // the shared fields: the ungrouped record
-    out[8] = p.lds;                                                                                    // (NNC_CBPKDX_P_LDS: the tables of the groups)
+    out[NNC_CBPKDX_P_LDS] = p.lds;                                                                     // (the tables of the groups)
     pgh_plan_tail(p, kdim, group_rows, tables, out + NNC_CBPKDX_H16_PLAN_LEN);
     return NNC_OK;
 }
@@ -315,12 +291,13 @@ extern "C" int nnc_cbpk_grouped_dx_h16(const void *g, int x_dtype, int64_t m, in
         return rc;
     PgPlan p;
     int tables;
-    if ((rc = pgh_dx_plan(fn, x_dtype, m, kdim, ncols, bits, k, group_rows, CB_PLAN_CUS, p, tables)) != NNC_OK) return rc;
+    p = pgh_dx_plan(m, kdim, ncols, bits, group_rows, CB_PLAN_CUS, tables);
     const StreamCase *sc;
-    if ((rc = cbg_stream_case(fn, stream_cases(x_dtype), kPkNames, p.path, bits, p.vb, p.mt, sc)) != NNC_OK) return rc;
+    if ((rc = cbg_stream_case(fn, h16_cases(x_dtype, kBf16Cases, kF16Cases), kPkNames, p.path, bits, p.vb, p.mt, sc)) != NNC_OK) return rc;
+    const MfmaCase *mc;
+    if ((rc = h16_mfma_case(fn, kMfmaCases, kPkNames, p.path, x_dtype, bits, mc)) != NNC_OK) return rc;
     hipStream_t s = S(stream);
-    if (p.path == NNC_CBMM_STREAM && (rc = pgh_dx_plan(fn, x_dtype, m, kdim, ncols, bits, k, group_rows, cu_count(), p, tables)) != NNC_OK)
-        return rc;                                                                        // (the row groups of this device)
+    if (p.path == NNC_CBMM_STREAM) p = pgh_dx_plan(m, kdim, ncols, bits, group_rows, cu_count(), tables);   // (the row groups of this device)
     const unsigned char *pk = reinterpret_cast<const unsigned char *>(packed);
     const long long row_bytes = pk_row_bytes(ncols, bits);
     return cbg_run_dx(p.path, p.splits, m, kdim, dx, dx_dtype, workspace, s, [&](int direct, void *out) {
@@ -329,7 +306,7 @@ extern "C" int nnc_cbpk_grouped_dx_h16(const void *g, int x_dtype, int64_t m, in
                    group_rows, direct, out);
             LAUNCHCHK("k_cbpkdx_stream_grouped (h16)");
         } else {
-            mfma_case(x_dtype, bits).dx(dim3((unsigned)(p.col_tiles * p.row_tiles), (unsigned)p.splits), (size_t)p.lds, s, g, m, kdim, pk, row_bytes, ncols,
+            mc->dx(dim3((unsigned)(p.col_tiles * p.row_tiles), (unsigned)p.splits), (size_t)p.lds, s, g, m, kdim, pk, row_bytes, ncols,
                                         centers_dev, k, tables, p.col_tiles, p.per_split, group_rows, direct, out);
             LAUNCHCHK("k_cbpkdx_mfma_grouped");
         }
@@ -340,7 +317,7 @@ extern "C" int nnc_cbpk_grouped_dx_h16(const void *g, int x_dtype, int64_t m, in
 extern "C" int64_t nnc_cbpk_grouped_dc_h16_workspace_bytes(int64_t m, int64_t kdim, int64_t ncols, int bits, int32_t k, int64_t group_rows)
 {
     if (pgg_check("nnc_cbpk_grouped_dc_h16_workspace_bytes", m, kdim, ncols, bits, k, group_rows) != NNC_OK) return 0;
-    return pgh_dc_ws_bytes(m == 0 || kdim == 0 || ncols == 0 ? NNC_CBMM_ZERO : NNC_CBMM_STREAM, gg_groups(kdim, group_rows) * k);
+    return h16_dc_ws_bytes(m == 0 || kdim == 0 || ncols == 0 ? NNC_CBMM_ZERO : NNC_CBMM_STREAM, gg_groups(kdim, group_rows) * k);
 }
 
 extern "C" int nnc_cbpk_grouped_dc_h16_plan(int x_dtype, int64_t m, int64_t kdim, int64_t ncols, int bits, int32_t k, int64_t group_rows, int32_t cus,
@@ -353,11 +330,11 @@ extern "C" int nnc_cbpk_grouped_dc_h16_plan(int x_dtype, int64_t m, int64_t kdim
     if (!out) return fail(NNC_EINVAL, std::string(fn) + ": out is NULL");
     PgPlan p;
     int sets;
-    if ((rc = pgh_dc_plan(fn, x_dtype, m, kdim, ncols, bits, k, group_rows, cus, p, sets)) != NNC_OK) return rc;
-    if ((rc = cbg_plan_out(fn, stream_cases(x_dtype), kPkNames, p.path, bits, p.vb, p.mt, cus, out)) != NNC_OK) return rc;
+    if ((rc = pgh_dc_plan(m, kdim, ncols, bits, k, group_rows, cus, p, sets)) != NNC_OK) return rc;
+    if ((rc = cbg_plan_out(fn, h16_cases(x_dtype, kBf16Cases, kF16Cases), kPkNames, p.path, bits, p.vb, p.mt, cus, out)) != NNC_OK) return rc;
     if ((rc = nnc_cbpk_dc_h16_plan(x_dtype, m, kdim, ncols, bits, k, cus, out)) != NNC_OK) return rc;   // the shared fields: the ungrouped record
-    out[7] = p.lds;                                                                                    // (NNC_CBPKDC_P_LDS: a set of bins per group)
-    out[11] = pgh_dc_ws_bytes(p.path, gg_groups(kdim, group_rows) * k);                                // (NNC_CBPKDC_P_WORKSPACE: G * k bins)
+    out[NNC_CBPKDC_P_LDS] = p.lds;                                                                     // (a set of bins per group)
+    out[NNC_CBPKDC_P_WORKSPACE] = h16_dc_ws_bytes(p.path, gg_groups(kdim, group_rows) * k);            // (G * k bins)
     pgh_plan_tail(p, kdim, group_rows, sets, out + NNC_CBPKDC_H16_PLAN_LEN);
     return NNC_OK;
 }
@@ -376,15 +353,17 @@ extern "C" int nnc_cbpk_grouped_dc_h16(const void *x, const void *g, int x_dtype
         return fail(NNC_EINVAL, "nnc_cbpk_grouped_dc_h16: x or g is not aligned to its element size");
     PgPlan p;
     int sets;
-    if ((rc = pgh_dc_plan(fn, x_dtype, m, kdim, ncols, bits, k, group_rows, CB_PLAN_CUS, p, sets)) != NNC_OK) return rc;
+    if ((rc = pgh_dc_plan(m, kdim, ncols, bits, k, group_rows, CB_PLAN_CUS, p, sets)) != NNC_OK) return rc;
     const int nbins = (int)(gg_groups(kdim, group_rows) * k);
-    const int64_t need = pgh_dc_ws_bytes(p.path, nbins);
+    const int64_t need = h16_dc_ws_bytes(p.path, nbins);
     if ((rc = cb_check_workspace(fn, "nnc_cbpk_grouped_dc_h16_workspace_bytes", workspace, workspace_bytes, need, 8, "workspace not 8-byte aligned")) != NNC_OK)
         return rc;
     const StreamCase *sc;
-    if ((rc = cbg_stream_case(fn, stream_cases(x_dtype), kPkNames, p.path, bits, p.vb, p.mt, sc)) != NNC_OK) return rc;
+    if ((rc = cbg_stream_case(fn, h16_cases(x_dtype, kBf16Cases, kF16Cases), kPkNames, p.path, bits, p.vb, p.mt, sc)) != NNC_OK) return rc;
+    const MfmaCase *mc;
+    if ((rc = h16_mfma_case(fn, kMfmaCases, kPkNames, p.path, x_dtype, bits, mc)) != NNC_OK) return rc;
     hipStream_t s = S(stream);
-    if (p.path == NNC_CBMM_STREAM && (rc = pgh_dc_plan(fn, x_dtype, m, kdim, ncols, bits, k, group_rows, cu_count(), p, sets)) != NNC_OK)
+    if (p.path == NNC_CBMM_STREAM && (rc = pgh_dc_plan(m, kdim, ncols, bits, k, group_rows, cu_count(), p, sets)) != NNC_OK)
         return rc;                                                                        // (the row groups of this device)
     const unsigned char *pk = reinterpret_cast<const unsigned char *>(packed);
     const long long row_bytes = pk_row_bytes(ncols, bits);
@@ -394,7 +373,7 @@ extern "C" int nnc_cbpk_grouped_dc_h16(const void *x, const void *g, int x_dtype
                    p.rows_per_group, group_rows, hdr, sums);
             LAUNCHCHK("k_cbpkdc_stream_grouped (h16)");
         } else {
-            mfma_case(x_dtype, bits).dc(dim3((unsigned)(p.col_tiles * p.row_tiles), (unsigned)p.splits), (size_t)p.lds, s, x, g, m, kdim, pk, row_bytes, ncols, k,
+            mc->dc(dim3((unsigned)(p.col_tiles * p.row_tiles), (unsigned)p.splits), (size_t)p.lds, s, x, g, m, kdim, pk, row_bytes, ncols, k,
                                         sets, p.terms_log2, p.col_tiles, p.per_split, group_rows, hdr, sums);
             LAUNCHCHK("k_cbpkdc_mfma_grouped");
         }

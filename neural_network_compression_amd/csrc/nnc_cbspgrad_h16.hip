@@ -8,18 +8,21 @@
 //             (k_cbsp_rowsum<XT>) come first; the rank-1 term c_z * rs is added in float32 before the one rounding of a half dx, by
 //             the stream kernel itself where a single column block writes dx, by k_cbspdx_finish behind the split partials.  Bit
 //             for bit the float32 entry points on the widened inputs.
-//   k_cbspdx_mfma  m > 16.  k_cbdx_mfma's tile, table, plan and splits (nnc_cbgrad_h16.hip); g is the A operand.  The B operand W^T is
+//   k_cbspdx_mfma  m > 16.  k_cbdx_mfma's tile, table, main loop (dxm_accumulate, nnc_cbdxm.hpp), tiles and splits (nnc_cbh16plan.hpp);
+//             g is the A operand.  The B operand W^T is
 //             decoded from the form: thread t owns index row n0 + (t mod 128) and 16 consecutive o of the step, which are 16 aligned
 //             bits of one bitmap word; their stored symbols are one run of the symbol stream starting at the segment's count plus
 //             the popcount of the word below the 16 bits.  A skipped position takes the table entry of zero_symbol, so there is no
 //             rank-1 term and no row sum on this path.  The word and the count of a step are requested two steps ahead of the MFMAs
 //             that consume them, the symbols and g one.
-//   k_cbspdc_mfma  m > 16.  k_cbdc_mfma's main loop (nnc_cbgrad_h16.hpp), so the same accumulators; the epilogue takes an
+//   k_cbspdc_mfma  m > 16.  k_cbdc_mfma's main loop (dcm_accumulate, nnc_cbgrad_h16.hpp), so the same accumulators; the epilogue takes an
 //             accumulator's label from the bitmap word of its row and segment, the count and a popcount.  A stored weight's image
 //             goes into the replicated LDS bins, a skipped one's into a per-lane int64 register flushed into bin z once.
 // No load leaves the packed buffer: rows past kdim load no word, columns past the split none, a symbol is loaded only below nnz.
 // Everything past m, kdim, ncols and the end of a split is zero in the images, never memory.  No float atomics; no host read.
+#include "nnc_cbdxm.hpp"
 #include "nnc_cbgrad_h16.hpp"
+#include "nnc_cbh16plan.hpp"
 #include "nnc_cbspgrad.hpp"
 
 // ------------------------------------------------------------------ dx, m <= 16
@@ -64,10 +67,9 @@ __global__ __launch_bounds__(HM_THREADS) void k_cbspdx_mfma(const XT *__restrict
         lo0 = lo[wrow];
         hrow = hi[gi];
     }
-    uint64_t word = 0;                                  // of the step load() decodes next
+    uint64_t word = 0;                                  // of the step load_w() decodes next
     long long cnt = 0;
     uint32_t lab[16];
-    uint4 gf[2];
 
     // the word holding columns ob + wk0 .. + 15 and the count of its segment; rows past kdim and columns past the split load nothing
     auto load_words = [&](long long ob) {
@@ -80,7 +82,7 @@ __global__ __launch_bounds__(HM_THREADS) void k_cbspdx_mfma(const XT *__restrict
             cnt = sp_count(lo[wrow + sg], lo0, hrow);
         }
     };
-    auto load = [&](long long ob) {                     // from the word load_words(ob) brought
+    auto load_w = [&](long long ob) {                   // from the word load_words(ob) brought
         const int b0 = (int)((ob + T.wk0) & 63);        // 0, 16, 32 or 48: steps and splits are multiples of 32
         const uint32_t bits = (uint32_t)(word >> b0) & 0xFFFFu;
         const long long start = cnt + __popcll(word & ((1ULL << b0) - 1));
@@ -90,33 +92,17 @@ __global__ __launch_bounds__(HM_THREADS) void k_cbspdx_mfma(const XT *__restrict
             lab[j] = (uint32_t)z;                       // a skipped position (every position of an empty word)
             if (((bits >> j) & 1u) && pos < nnz) lab[j] = (uint32_t)sym[pos];
         }
-#pragma unroll
-        for (int i = 0; i < 2; ++i) gf[i] = hm_load_x<XT, XVEC>(g, m, ncols, T.m0, ob, T.k_hi, T.t + i * HM_THREADS);
     };
-    auto store = [&](long long ob) {
+    auto store_w = [&](long long ob) {
         float w[16];
 #pragma unroll
         for (int j = 0; j < 16; ++j) w[j] = (row_ok && ob + T.wk0 + j < T.k_hi) ? cb[CbTable<LT>::index(lab[j], k, cshift, T.lane)] : 0.0f;
         hm_store_w(ws, T.wc, T.wk0, w);
-#pragma unroll
-        for (int i = 0; i < 2; ++i) hm_store_x(gs, T.t + i * HM_THREADS, gf[i]);
     };
 
     typename HFrag<XT>::C acc[2][2];
-    hm_clear<XT>(acc);
     load_words(T.k_lo);
-    load(T.k_lo);
-    load_words(T.k_lo + HM_BK);
-    for (long long ob = T.k_lo; ob < T.k_hi; ob += HM_BK) {
-        __syncthreads();   // the table is filled (first step); the images of the step before have been read
-        store(ob);
-        __syncthreads();
-        if (ob + HM_BK < T.k_hi) {
-            load(ob + HM_BK);
-            load_words(ob + 2 * HM_BK);
-        }
-        hm_step(gs, ws, T.wm, T.wn, T.fr, T.fh, acc);
-    }
+    dxm_accumulate<XT, XVEC>(g, m, ncols, T, gs, ws, acc, load_w, store_w, [&](long long ob) { load_words(ob + HM_BK); });
     hm_store_y<XT>(acc, T.n0, T.m0, T.wm, T.wn, T.lane, m, kdim, nullptr, 0, direct, out_);
 }
 
@@ -141,9 +127,9 @@ __global__ __launch_bounds__(HM_THREADS) void k_cbspdc_mfma(const XT *__restrict
     typename HFrag<XT>::C acc[2][2];
     dcm_accumulate<XT, XVEC>(x, g, kdim, ncols, T, scx, scg, xs, gs, acc);
 
-    // register r of lane l of accumulator (a, b) is dW'[i = m0 + wm + 32 a + (r & 3) + 8 (r >> 2) + 4 (l >> 5)][o = n0 + wn + 32 b + (l & 31)]:
-    // the 32 lanes of a row lie in the wave's one segment (n0 + wn is a multiple of 64), so one word and one count serve each half
-    // of the wave for both b; a lane's label is the symbol at count + popcount(word below its column)
+    // accumulator (a, b) holds dW'[i][o] (hm_acc_row, hm_acc_col): the 32 lanes of a row lie in the wave's one segment (n0 + wn is a
+    // multiple of 64), so one word and one count serve each half of the wave for both b; a lane's label is the symbol at count +
+    // popcount(word below its column)
     const int rep = T.t & ((1 << rlog2) - 1);
     const long long sg = (T.n0 + T.wn) >> 6;
     const bool seg_ok = sg < segs;                      // (else every column of the wave lies past ncols)
@@ -152,14 +138,14 @@ __global__ __launch_bounds__(HM_THREADS) void k_cbspdc_mfma(const XT *__restrict
     for (int a = 0; a < 2; ++a) {
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-            const long long i = T.m0 + T.wm + a * 32 + (r & 3) + 8 * (r >> 2) + 4 * (T.lane >> 5);
+            const long long i = hm_acc_row(T.m0 + T.wm, a, r, T.lane);
             if (i >= kdim || !seg_ok) continue;
             const long long wrow = i * segs;
             const uint64_t word = bitmap[wrow + sg];
             const long long cnt = sp_count(lo[wrow + sg], lo[wrow], hi[i]);
 #pragma unroll
             for (int b = 0; b < 2; ++b) {
-                const int c = b * 32 + T.fr;            // the lane's column inside the segment
+                const int c = (int)hm_acc_col(0, b, T.lane);   // the lane's column inside the segment
                 if (T.n0 + T.wn + c >= ncols) continue;
                 const unsigned long long img = cbdc_fix(acc[a][b][r], Sw);
                 const long long pos = cnt + __popcll(word & ((1ULL << c) - 1));
@@ -177,28 +163,17 @@ __global__ __launch_bounds__(HM_THREADS) void k_cbspdc_mfma(const XT *__restrict
 }
 
 // ------------------------------------------------------------------ plans (host)
-// m <= 16 and the empty shapes: section 13's plans (sg_dx_plan, sg_dc_plan) field for field.  m > 16: the byte form's half plans
-// (nnc_cbmm_dx_h16_plan / nnc_cbmm_dc_h16_plan) in every field the two records share, so the tiles, the splits, S and every image
-// are that call's.  NNC_OK, or that plan's error.
-static int h16_dx_plan(int dt, long long m, long long kdim, long long ncols, int lb, int k, int cus, SgPlan &p)
+// m <= 16 and the empty shapes: section 13's plans (sg_dx_plan, sg_dc_plan) field for field.  m > 16: nnc_cbh16plan.hpp's tiles and
+// splits with the byte form's table and bins, so the tiles, the splits, S and every image are those of nnc_cbmm_dx_h16 /
+// nnc_cbmm_dc_h16 on the same shape.
+static SgPlan h16_dx_plan(long long m, long long kdim, long long ncols, int lb, int k, int cus)
 {
-    if (m == 0 || kdim == 0 || ncols == 0 || m <= CB_SKINNY_M) {
-        p = sg_dx_plan(m, kdim, ncols, lb, k, cus);
-        return NNC_OK;
-    }
-    p = SgPlan{};
-    int64_t d[NNC_CBDX_H16_PLAN_LEN];
-    const int rc = nnc_cbmm_dx_h16_plan(dt, m, kdim, ncols, lb, k, CB_PLAN_CUS, 0, d);
-    if (rc != NNC_OK) return rc;
-    p.path = (int)d[NNC_CBDX_P_PATH];
-    p.entries = (int)d[NNC_CBDX_P_ENTRIES];
-    p.cshift = __builtin_ctzll((unsigned long long)d[NNC_CBDX_P_COPIES]);
-    p.splits = d[NNC_CBDX_P_SPLITS];
-    p.per_split = d[NNC_CBDX_P_CPS];
-    p.lds = d[NNC_CBDX_P_LDS];
-    p.col_tiles = d[NNC_CBDX_P_COL_TILES];
-    p.row_tiles = d[NNC_CBDX_P_ROW_TILES];
-    return NNC_OK;
+    if (!h16_mfma_shape(m, kdim, ncols)) return sg_dx_plan(m, kdim, ncols, lb, k, cus);
+    int entries = 0, cshift = 0;   // (cb_table_shape counts cshift up from 0)
+    cb_table_shape(lb, k, entries, cshift);
+    SgPlan p = h16_mfma_plan<SgPlan>(h16_dx_tiles(m, kdim, ncols), (long long)hm_table_words(entries, cshift) * 4);
+    p.entries = entries, p.cshift = cshift;
+    return p;
 }
 
 static int64_t h16_dx_ws_bytes(const SgPlan &p, long long m, long long kdim)
@@ -206,25 +181,13 @@ static int64_t h16_dx_ws_bytes(const SgPlan &p, long long m, long long kdim)
     return p.path == NNC_CBMM_MFMA ? cbg_dx_ws_bytes(p.splits, m, kdim) : sg_dx_ws_bytes(p, m, kdim);
 }
 
-static int h16_dc_plan(int dt, long long m, long long kdim, long long ncols, int lb, int k, int cus, SgPlan &p)
+static int h16_dc_plan(long long m, long long kdim, long long ncols, int lb, int k, int cus, SgPlan &p)
 {
-    if (m == 0 || kdim == 0 || ncols == 0 || m <= CB_SKINNY_M) return sg_dc_plan(m, kdim, ncols, lb, k, cus, p);
-    p = SgPlan{};
-    int64_t d[NNC_CBDC_H16_PLAN_LEN];
-    const int rc = nnc_cbmm_dc_h16_plan(dt, m, kdim, ncols, lb, k, CB_PLAN_CUS, 0, d);
-    if (rc != NNC_OK) return rc;
-    p.path = (int)d[NNC_CBDC_P_PATH];
-    p.rlog2 = __builtin_ctzll((unsigned long long)d[NNC_CBDC_P_COPIES]);
-    p.splits = d[NNC_CBDC_P_SPLITS];
-    p.per_split = d[NNC_CBDC_P_RPS];
-    p.lds = d[NNC_CBDC_P_LDS];
-    p.col_tiles = d[NNC_CBDC_P_COL_TILES];
-    p.row_tiles = d[NNC_CBDC_P_ROW_TILES];
-    p.terms_log2 = (int)d[NNC_CBDC_P_TERMS_LOG2];
+    if (!h16_mfma_shape(m, kdim, ncols)) return sg_dc_plan(m, kdim, ncols, lb, k, cus, p);
+    p = h16_mfma_plan<SgPlan>(h16_dc_tiles(m, kdim, ncols), ((long long)k << dc_rlog2(k)) * 8);
+    p.rlog2 = dc_rlog2(k);
     return NNC_OK;
 }
-
-static inline int64_t h16_dc_ws_bytes(int path, int k) { return path == NNC_CBMM_ZERO ? 0 : CBG_HDR_BYTES + 8LL * k; }
 
 // ------------------------------------------------------------------ launches
 struct SgForm {   // the parts of the packed buffer
@@ -293,7 +256,7 @@ struct StreamCase {
     DcStream dc;
 };
 struct MfmaCase {
-    int dt, lb;
+    int dt, a;                // a: label_bytes
     DxMfma dx;
     DcMfma dc;
 };
@@ -312,24 +275,11 @@ static const MfmaCase kMfmaCases[] = {
 };
 static const CbgCaseNames kSgNames = {false, "label_bytes", false};
 
-static inline const StreamCase (&stream_cases(int dt))[sizeof(kBf16Cases) / sizeof(StreamCase)] { return dt == NNC_DT_BF16 ? kBf16Cases : kF16Cases; }
-
-// the MFMA instantiation of (dt, lb), or NNC_EINVAL in the wording of cbg_stream_case
-static int mfma_case(const char *fn, int path, int dt, int lb, const MfmaCase *&c)
-{
-    c = nullptr;
-    if (path != NNC_CBMM_MFMA) return NNC_OK;
-    for (const MfmaCase &e : kMfmaCases)
-        if (e.dt == dt && e.lb == lb) c = &e;
-    if (c) return NNC_OK;
-    return fail(NNC_EINVAL, std::string(fn) + ": no MFMA instantiation for dtype " + std::to_string(dt) + ", label_bytes " + std::to_string(lb));
-}
-
 // ------------------------------------------------------------------ C ABI
 static int h16_check(const char *fn, int x_dtype, int64_t m, int64_t kdim, int64_t ncols, int label_bytes, int32_t k)
 {
-    if (x_dtype != NNC_DT_BF16 && x_dtype != NNC_DT_F16) return fail(NNC_EINVAL, std::string(fn) + ": x_dtype must be NNC_DT_BF16 or NNC_DT_F16");
-    return sg_check(fn, m, kdim, ncols, label_bytes, k);
+    const int rc = h16_check_dtype(fn, x_dtype);
+    return rc != NNC_OK ? rc : sg_check(fn, m, kdim, ncols, label_bytes, k);
 }
 
 static SgForm sg_form(const void *packed, const SpLayout &L, long long nnz)
@@ -342,9 +292,7 @@ static SgForm sg_form(const void *packed, const SpLayout &L, long long nnz)
 extern "C" int64_t nnc_cbsp_dx_h16_workspace_bytes(int64_t m, int64_t kdim, int64_t ncols, int label_bytes)
 {
     if (sg_check("nnc_cbsp_dx_h16_workspace_bytes", m, kdim, ncols, label_bytes, 1) != NNC_OK) return 0;
-    SgPlan p;
-    if (h16_dx_plan(NNC_DT_BF16, m, kdim, ncols, label_bytes, 1, CB_PLAN_CUS, p) != NNC_OK) return 0;
-    return h16_dx_ws_bytes(p, m, kdim);
+    return h16_dx_ws_bytes(h16_dx_plan(m, kdim, ncols, label_bytes, 1, CB_PLAN_CUS), m, kdim);
 }
 
 extern "C" int nnc_cbsp_dx_h16_plan(int x_dtype, int64_t m, int64_t kdim, int64_t ncols, int label_bytes, int32_t k, int32_t cus, int64_t *out)
@@ -352,11 +300,10 @@ extern "C" int nnc_cbsp_dx_h16_plan(int x_dtype, int64_t m, int64_t kdim, int64_
     const char *fn = "nnc_cbsp_dx_h16_plan";
     int rc = h16_check(fn, x_dtype, m, kdim, ncols, label_bytes, k);
     if (rc != NNC_OK) return rc;
-    SgPlan p;
-    if ((rc = h16_dx_plan(x_dtype, m, kdim, ncols, label_bytes, k, cus, p)) != NNC_OK) return rc;
-    if ((rc = cbg_plan_out(fn, stream_cases(x_dtype), kSgNames, p.path, label_bytes, 0, p.mt, cus, out)) != NNC_OK) return rc;
+    const SgPlan p = h16_dx_plan(m, kdim, ncols, label_bytes, k, cus);
+    if ((rc = cbg_plan_out(fn, h16_cases(x_dtype, kBf16Cases, kF16Cases), kSgNames, p.path, label_bytes, 0, p.mt, cus, out)) != NNC_OK) return rc;
     const MfmaCase *mc;
-    if ((rc = mfma_case(fn, p.path, x_dtype, label_bytes, mc)) != NNC_OK) return rc;
+    if ((rc = h16_mfma_case(fn, kMfmaCases, kSgNames, p.path, x_dtype, label_bytes, mc)) != NNC_OK) return rc;
     const bool table = p.path == NNC_CBMM_STREAM || p.path == NNC_CBMM_MFMA;
     const int64_t v[NNC_CBSPDX_H16_PLAN_LEN] = {p.path, p.mt, p.segs, table ? 1LL << p.cshift : (p.entries ? 1 : 0), p.entries, p.splits, p.per_split, p.lds,
                                                 p.col_tiles, p.row_tiles, h16_dx_ws_bytes(p, m, kdim), x_dtype};
@@ -380,12 +327,11 @@ extern "C" int nnc_cbsp_dx_h16(const void *g, int x_dtype, int64_t m, int64_t kd
         return fail(NNC_EINVAL, "nnc_cbsp_dx_h16: g or dx is not aligned to its element size");
     const int64_t need = nnc_cbsp_dx_h16_workspace_bytes(m, kdim, ncols, label_bytes);
     if ((rc = cb_check_workspace(fn, "nnc_cbsp_dx_h16_workspace_bytes", workspace, workspace_bytes, need, 4, "workspace must be 4-byte aligned")) != NNC_OK) return rc;
-    SgPlan p;
-    if ((rc = h16_dx_plan(x_dtype, m, kdim, ncols, label_bytes, k, cu_count(), p)) != NNC_OK) return rc;
+    const SgPlan p = h16_dx_plan(m, kdim, ncols, label_bytes, k, cu_count());
     const StreamCase *sc;
-    if ((rc = cbg_stream_case(fn, stream_cases(x_dtype), kSgNames, p.path, label_bytes, 0, p.mt, sc)) != NNC_OK) return rc;
+    if ((rc = cbg_stream_case(fn, h16_cases(x_dtype, kBf16Cases, kF16Cases), kSgNames, p.path, label_bytes, 0, p.mt, sc)) != NNC_OK) return rc;
     const MfmaCase *mc;
-    if ((rc = mfma_case(fn, p.path, x_dtype, label_bytes, mc)) != NNC_OK) return rc;
+    if ((rc = h16_mfma_case(fn, kMfmaCases, kSgNames, p.path, x_dtype, label_bytes, mc)) != NNC_OK) return rc;
     hipStream_t s = S(stream);
     const SgForm f = sg_form(packed, sp_layout(kdim, ncols, label_bytes, nnz), nnz);
     if (p.path != NNC_CBMM_STREAM)   // nothing, dx = 0, or the MFMA tile: W_h holds c_z at a skipped position, so no row sums and no rank-1 term
@@ -415,7 +361,7 @@ extern "C" int64_t nnc_cbsp_dc_h16_workspace_bytes(int64_t m, int64_t kdim, int6
 {
     if (sg_check("nnc_cbsp_dc_h16_workspace_bytes", m, kdim, ncols, label_bytes, k) != NNC_OK) return 0;
     SgPlan p;
-    if (h16_dc_plan(NNC_DT_BF16, m, kdim, ncols, label_bytes, k, CB_PLAN_CUS, p) != NNC_OK) return 0;
+    if (h16_dc_plan(m, kdim, ncols, label_bytes, k, CB_PLAN_CUS, p) != NNC_OK) return 0;
     return h16_dc_ws_bytes(p.path, k);
 }
 
@@ -425,10 +371,10 @@ extern "C" int nnc_cbsp_dc_h16_plan(int x_dtype, int64_t m, int64_t kdim, int64_
     int rc = h16_check(fn, x_dtype, m, kdim, ncols, label_bytes, k);
     if (rc != NNC_OK) return rc;
     SgPlan p;
-    if ((rc = h16_dc_plan(x_dtype, m, kdim, ncols, label_bytes, k, cus, p)) != NNC_OK) return rc;
-    if ((rc = cbg_plan_out(fn, stream_cases(x_dtype), kSgNames, p.path, label_bytes, 0, p.mt, cus, out)) != NNC_OK) return rc;
+    if ((rc = h16_dc_plan(m, kdim, ncols, label_bytes, k, cus, p)) != NNC_OK) return rc;
+    if ((rc = cbg_plan_out(fn, h16_cases(x_dtype, kBf16Cases, kF16Cases), kSgNames, p.path, label_bytes, 0, p.mt, cus, out)) != NNC_OK) return rc;
     const MfmaCase *mc;
-    if ((rc = mfma_case(fn, p.path, x_dtype, label_bytes, mc)) != NNC_OK) return rc;
+    if ((rc = h16_mfma_case(fn, kMfmaCases, kSgNames, p.path, x_dtype, label_bytes, mc)) != NNC_OK) return rc;
     const int64_t v[NNC_CBSPDC_H16_PLAN_LEN] = {p.path, p.mt, p.segs, p.path == NNC_CBMM_ZERO ? 0 : 1LL << p.rlog2, p.splits, p.per_split, p.lds, p.col_tiles,
                                                 p.row_tiles, p.terms_log2, h16_dc_ws_bytes(p.path, k), x_dtype};
     for (int i = 0; i < NNC_CBSPDC_H16_PLAN_LEN; ++i) out[i] = v[i];
@@ -449,11 +395,11 @@ extern "C" int nnc_cbsp_dc_h16(const void *x, const void *g, int x_dtype, int64_
     const int64_t need = nnc_cbsp_dc_h16_workspace_bytes(m, kdim, ncols, label_bytes, k);
     if ((rc = cb_check_workspace(fn, "nnc_cbsp_dc_h16_workspace_bytes", workspace, workspace_bytes, need, 8, "workspace not 8-byte aligned")) != NNC_OK) return rc;
     SgPlan p;
-    if ((rc = h16_dc_plan(x_dtype, m, kdim, ncols, label_bytes, k, cu_count(), p)) != NNC_OK) return rc;
+    if ((rc = h16_dc_plan(m, kdim, ncols, label_bytes, k, cu_count(), p)) != NNC_OK) return rc;
     const StreamCase *sc;
-    if ((rc = cbg_stream_case(fn, stream_cases(x_dtype), kSgNames, p.path, label_bytes, 0, p.mt, sc)) != NNC_OK) return rc;
+    if ((rc = cbg_stream_case(fn, h16_cases(x_dtype, kBf16Cases, kF16Cases), kSgNames, p.path, label_bytes, 0, p.mt, sc)) != NNC_OK) return rc;
     const MfmaCase *mc;
-    if ((rc = mfma_case(fn, p.path, x_dtype, label_bytes, mc)) != NNC_OK) return rc;
+    if ((rc = h16_mfma_case(fn, kMfmaCases, kSgNames, p.path, x_dtype, label_bytes, mc)) != NNC_OK) return rc;
     hipStream_t s = S(stream);
     const SgForm f = sg_form(packed, sp_layout(kdim, ncols, label_bytes, nnz), nnz);
     return cbg_run_dc(p.path, x, g, x_dtype, m, kdim, ncols, (int)k, dc, out_f64, workspace, need, s, [&](uint32_t *hdr, unsigned long long *sums) {
