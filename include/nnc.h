@@ -820,6 +820,10 @@ int nnc_cbsp_f32(const float *x, int64_t m, int64_t kdim, const void *packed, in
  * its plan.  A header of its own, part of this ABI. */
 #include "nnc_cbsp_h16.h"
 
+/* The same form with one codebook per block of input rows, float32 x (csrc/nnc_cbsp_grouped.hip): the pack
+ * with a skipped symbol per group, nnc_cbsp_grouped_f32, its workspace query and its plan.  A header of its own, part of this ABI. */
+#include "nnc_cbsp_grouped.h"
+
 /* ------------------------------------------------------------------------------------
  * The quantized layer of at most 16 centres run from 2- or 4-bit packed indices (csrc/nnc_cbpk.hip): a
  * third resident form of the (kdim, ncols) index matrix, row-major as nnc_cbmm_f32 reads it, beside the byte form and the

@@ -49,6 +49,8 @@ CBDC_H16_PLAN_FIELDS = CBDC_PLAN_FIELDS + ("dtype",)
 CBSP_ROWSUM_NONE, CBSP_ROWSUM_FUSED, CBSP_ROWSUM_PASS = 0, 1, 2   # nnc_cbsp_plan: how the row sums of x are formed (include/nnc.h)
 CBSP_PLAN_LEN = 11
 CBSP_PLAN_FIELDS = ("path", "mt", "copies", "entries", "splits", "rps", "rowsum", "lds", "col_tiles", "row_tiles", "workspace")
+CBSP_GROUPED_PLAN_LEN = 14   # nnc_cbsp_grouped_plan (include/nnc_cbsp_grouped.h): the sparse fields, then the groups
+CBSP_GROUPED_PLAN_FIELDS = CBSP_PLAN_FIELDS + ("group_rows", "groups", "max_groups_per_split")
 CBSP_H16_PLAN_LEN = 12   # nnc_cbsp_h16_plan (include/nnc_cbsp_h16.h): path is CBMM_MFMA for m > 16
 CBSP_H16_PLAN_FIELDS = CBSP_PLAN_FIELDS + ("dtype",)
 CBPK_TABLE_NONE, CBPK_TABLE_BANKED = 0, 1   # nnc_cbpk_plan: the layout of the lookup table (include/nnc.h)
@@ -376,6 +378,17 @@ GROUPED_H16_GRAD_SIGNATURES = {
                                         c_void_p]),
 }
 
+# name -> (restype, argtypes); every symbol include/nnc_cbsp_grouped.h declares (the bitmap-sparse form of the group-wise layer, float32
+# activations, again a header of its own that nnc.h includes).  Required and bound by load() as SIGNATURES are.
+GROUPED_SPARSE_SIGNATURES = {
+    "nnc_cbsp_grouped_pack": (c_int, [c_void_p, c_i64, c_i64, c_i64, c_void_p, c_void_p, c_i64, c_void_p, c_void_p]),
+    "nnc_cbsp_grouped_unpack": (c_int, [c_void_p, c_i64, c_i64, c_i64, c_i64, c_void_p, c_i64, c_void_p, c_void_p]),
+    "nnc_cbsp_grouped_workspace_bytes": (c_i64, [c_i64, c_i64, c_i64]),
+    "nnc_cbsp_grouped_plan": (c_int, [c_i64, c_i64, c_i64, c_i32, c_i64, c_i32, ctypes.POINTER(c_i64)]),
+    "nnc_cbsp_grouped_f32": (c_int, [c_void_p, c_i64, c_i64, c_void_p, c_i64, c_i64, c_void_p, c_i64, c_void_p, c_i32, c_i64, c_void_p, c_i32, c_void_p,
+                                     c_void_p, c_i64, c_void_p]),
+}
+
 # exported only by the diagnostics build (NNC_DIAG=1: libnnc_hip_diag.so, see build.py); bound when present
 DIAG_SIGNATURES = {
     "nnc_debug_set_ablation": (c_int, [c_int]),
@@ -408,7 +421,7 @@ def load():
         L = ctypes.CDLL(path)
     except OSError as e:  # pragma: no cover - depends on the machine
         raise NativeLibraryError(f"cannot load {path}: {e}; there is no CPU fallback") from e
-    for name, (res, args) in list(SIGNATURES.items()) + list(GROUPED_GRAD_SIGNATURES.items()) + list(H16_GRAD_SIGNATURES.items()) + list(GROUPED_PACKED_GRAD_SIGNATURES.items()) + list(SPARSE_H16_SIGNATURES.items()) + list(SPARSE_H16_GRAD_SIGNATURES.items()) + list(PACKED_H16_SIGNATURES.items()) + list(GROUPED_H16_GRAD_SIGNATURES.items()):
+    for name, (res, args) in list(SIGNATURES.items()) + list(GROUPED_GRAD_SIGNATURES.items()) + list(H16_GRAD_SIGNATURES.items()) + list(GROUPED_PACKED_GRAD_SIGNATURES.items()) + list(SPARSE_H16_SIGNATURES.items()) + list(SPARSE_H16_GRAD_SIGNATURES.items()) + list(PACKED_H16_SIGNATURES.items()) + list(GROUPED_H16_GRAD_SIGNATURES.items()) + list(GROUPED_SPARSE_SIGNATURES.items()):
         try:
             fn = getattr(L, name)
         except AttributeError as e:

@@ -10,6 +10,8 @@ tensor is never rebuilt.  Biases (one value per output column) are decoded once 
     compress_network(network, models_by_layer, sparse=False, trainable=False, packed=False)   a deep copy with the quantized layers replaced
     load_network(path, network, sparse=False, packed=False)        the same from a ``weights.nnc`` (Trainer.store_report)
     pack_grouped_layers(network, packed=True)                      a deep copy with the grouped layers' indices packed to 2 or 4 bits
+    sparsify_grouped_layers(network, sparse=True)                  a deep copy with the grouped layers' indices in the bitmap-sparse form
+    smallest_grouped_layers(network)                               a deep copy with every grouped layer in the smallest of its three forms
     compressed_nbytes(network)                                     resident bytes of the layers' tensors
 
 A pruned layer can instead keep its indices in the bitmap-sparse form (ops.pack_sparse_codes, csrc/nnc_cbsp.hip, DESIGN.md
@@ -50,6 +52,10 @@ build it for a layer fitted that way; there ``sparse``, ``packed`` and ``trainab
 layer.  ``pack_grouped_layers(network, packed=True | "auto")`` is the way to the 2- and 4-bit packed form of grouped layers of at
 most 16 centres per group: ``GroupedPackedCompressedDense`` (ops.grouped_packed_codebook_matmul, csrc/nnc_cbpk_grouped.hip,
 DESIGN.md section 18), the same function from a half or a quarter of the index bytes, on the same three input dtypes.
+``sparsify_grouped_layers(network, sparse=True | "auto")`` is the way to the bitmap-sparse form of a pruned grouped layer, with one
+skipped index per group: ``GroupedSparseCompressedDense`` (ops.grouped_sparse_codebook_matmul, csrc/nnc_cbsp_grouped.hip, DESIGN.md
+section 28), on float32 inputs only; ``smallest_grouped_layers(network)`` picks per layer, by resident bytes, among the byte, the
+packed and the sparse form.
 
 These layers are inference only: under autograd, with an input that needs a gradient, they raise instead of returning a result
 that silently has none.  ``trainable=True`` in compress_network / Trainer.compressed_network gives the trainable variants instead
@@ -87,7 +93,7 @@ resident while training.  The bitmap-sparse grouped form and grouped Conv2D do n
 How the classes are laid out: ``_Activated`` (the activation behind the product, ``get_weights``) is the root of
 ``_InferenceLayer`` (the float32 ``centers`` / ``bias`` buffers behind the family's index buffer, ``nbytes``) and of
 ``_TrainableCentres`` (the ``centers`` parameter, ``counts``, the three kinds of bias).  A family -- ``_CodebookLayer``,
-``GroupedCompressedDense``, ``GroupedPackedCompressedDense``, ``_SparseCodebookLayer``, ``_PackedCodebookLayer`` and the trainable ones -- adds its index
+``GroupedCompressedDense``, ``GroupedPackedCompressedDense``, ``GroupedSparseCompressedDense``, ``_SparseCodebookLayer``, ``_PackedCodebookLayer`` and the trainable ones -- adds its index
 buffer and the one ops call of ``_matmul``; ``_SparseForm`` / ``_PackedForm`` hold what the inference and the trainable layer of
 a form share (the ``packed`` buffer, the metadata, ``codes``).  ``_DenseHalf`` and ``_Conv2DHalf`` are the two forwards over
 ``_matmul``; a public class is one of them on a family, with the constructors of its own signature.
@@ -852,6 +858,59 @@ class GroupedPackedCompressedDense(_DenseHalf, _PackedForm, _InferenceLayer):
         return self._activate(ops.grouped_packed_codebook_matmul(x, self.codes, self.centers, self.group_rows, bias=self.bias, relu=self._fused_relu))
 
 
+class GroupedSparseCompressedDense(_DenseHalf, _InferenceLayer):
+    """Dense run from one codebook per block of ``group_rows`` input rows and the bitmap-sparse form of its (in, out) indices
+    (ops.grouped_sparse_codebook_matmul): packed (the bitmap-sparse buffer of the whole index matrix, one
+    byte per stored symbol), zero_symbols (the skipped index of every group, uint8[G]), centers float32 (G, K), G = ceil(kdim /
+    group_rows), bias float32[ncols] or None.  float32 activations only: a bfloat16 or float16 input raises TypeError.  Inference
+    only.  No kdim * ncols tensor stays resident."""
+
+    _INDEX = "packed"
+
+    def __init__(self, codes: ops.GroupedSparseCodes, centers: torch.Tensor, bias: torch.Tensor | None, activation=None):
+        super().__init__()
+        groups = max(1, codes.groups)
+        if centers.dim() != 2 or tuple(centers.shape) != (groups, codes.k):
+            raise ValueError(f"centers must have shape ({groups}, {codes.k}) for {codes.kdim} rows in groups of {codes.group_rows} and indices into "
+                             f"codebooks of {codes.k}, got {tuple(centers.shape)}")
+        self.kdim, self.ncols, self.k, self.group_rows, self.nnz = codes.kdim, codes.ncols, codes.k, codes.group_rows, codes.nnz
+        self.register_buffer("packed", codes.buf)
+        self.register_buffer("zero_symbols", codes.zero_symbols)
+        self._init_codebook(centers, bias, activation)
+
+    @property
+    def codes(self) -> ops.GroupedSparseCodes:
+        return ops.GroupedSparseCodes(self.packed, self.kdim, self.ncols, self.k, self.group_rows, self.zero_symbols, self.nnz)
+
+    @classmethod
+    def from_dense(cls, dense, grouped_model, bias_model=None, zero_symbols=None) -> "GroupedSparseCompressedDense":
+        """From a Dense layer and the GroupedModel of its kernel (utility.get_quantized_weight_grouped)."""
+        _require_model(grouped_model)
+        kin, kout = dense.kernel.shape
+        centers = torch.from_numpy(np.ascontiguousarray(grouped_model.cluster_centers_, dtype=np.float32)).to(dense.kernel.device)
+        return cls.from_codes(kin, kout, grouped_model.group_rows, grouped_model.labels_compact_, centers, _decoded_bias(dense.bias, bias_model),
+                              dense.activation, zero_symbols)
+
+    @classmethod
+    def from_codes(cls, kdim, ncols, group_rows, labels, centers, bias, activation, zero_symbols=None) -> "GroupedSparseCompressedDense":
+        if centers.dim() != 2:
+            raise ValueError(f"centers must have shape (G, K), got {tuple(centers.shape)}")
+        return cls(ops.pack_grouped_sparse_codes(labels, kdim, ncols, centers.shape[1], group_rows, zero_symbols), centers, bias, activation)
+
+    @classmethod
+    def from_grouped(cls, layer: GroupedCompressedDense, zero_symbols=None) -> "GroupedSparseCompressedDense":
+        """The same layer from the bitmap-sparse form of a GroupedCompressedDense's indices: the same weights, the sums in the
+        order of DESIGN.md section 28."""
+        return cls.from_codes(layer.kdim, layer.ncols, layer.group_rows, layer.labels, layer.centers, layer.bias, layer.activation, zero_symbols)
+
+    def nbytes(self) -> int:
+        """The buffer, the G skipped symbols, the G * K centres and the bias."""
+        return super().nbytes() + _tensor_bytes(self.zero_symbols)
+
+    def _matmul(self, x: torch.Tensor) -> torch.Tensor:
+        return self._activate(ops.grouped_sparse_codebook_matmul(x, self.codes, self.centers, bias=self.bias, relu=self._fused_relu))
+
+
 class TrainableGroupedPackedCompressedDense(_DenseHalf, _PackedForm, _TrainableCentres):
     """GroupedPackedCompressedDense with trainable centres (ops.grouped_packed_codebook_linear): packed (the
     ordinary 2- or 4-bit packed buffer of the whole index matrix) the only index buffer, centers a float32 (G, K <= 2^bits)
@@ -1056,7 +1115,8 @@ def compress_network(network: nn.Module, models_by_layer, sparse=False, trainabl
     float16 inputs; what "auto" picks does not change.
     A layer whose kernel model is a utility.GroupedModel (one codebook per block of input rows) becomes a GroupedCompressedDense;
     with ``sparse``, ``packed`` or ``trainable`` set it raises NotImplementedError and names the layer (pack_grouped_layers packs
-    the grouped layers of the result)."""
+    the grouped layers of the result, sparsify_grouped_layers gives them the bitmap-sparse form, smallest_grouped_layers the
+    smallest of the three)."""
     _check_sparse(sparse)
     _check_packed(packed, sparse, trainable)
     _check_half_inputs(half_inputs, sparse, packed, trainable)
@@ -1160,7 +1220,8 @@ def load_network(path: str, network: nn.Module, device=None, sparse=False, packe
     "{layer}.weights" / "{layer}.biases", or "{layer}.weights#g{g}" per group of a kernel with group-wise codebooks, whose
     ``group_rows`` is the row count of the first).  ``network`` gives the architecture; layers stored raw get the stored float32 values.
     ``sparse``, ``packed``, ``sparse_half_inputs`` and ``packed_half_inputs`` as in compress_network: the stored format is the same, the indices are packed after loading.  A
-    kernel with group-wise codebooks raises NotImplementedError for either; pack_grouped_layers packs it after loading."""
+    kernel with group-wise codebooks raises NotImplementedError for either; pack_grouped_layers packs it after loading, and
+    sparsify_grouped_layers gives it the bitmap-sparse form."""
     from . import storage
 
     _check_sparse(sparse)
@@ -1220,6 +1281,47 @@ def pack_grouped_layers(network: nn.Module, packed=True) -> nn.Module:
         if packed == "auto" and ops.packed_nbytes(layer.kdim, layer.ncols, bits) >= layer.labels.numel():
             continue
         setattr(out, name, GroupedPackedCompressedDense.from_grouped(layer))
+    return out
+
+
+def sparsify_grouped_layers(network: nn.Module, sparse=True) -> nn.Module:
+    """A deep copy of a compressed ``network`` (compress_network, Trainer.compressed_network() or load_network) whose
+    GroupedCompressedDense layers keep their indices in the bitmap-sparse form with one skipped index per group
+    (GroupedSparseCompressedDense).  ``sparse``: True (every GroupedCompressedDense) or "auto" (a layer only
+    where the sparse form holds fewer resident bytes; on equal bytes the byte form stays); anything else is a ValueError.
+    GroupedPackedCompressedDense layers and all other layers are left as they are.  A replaced layer has the same weights and takes
+    float32 activations only; its sums run in another order (within the float bound of section 28, the same bits on exact data)."""
+    if sparse is not True and sparse != "auto":
+        raise ValueError(f"sparse must be True or 'auto', got {sparse!r}")
+    out = copy.deepcopy(network)
+    for name, layer in out.get_config().items():
+        if not isinstance(layer, GroupedCompressedDense):
+            continue
+        made = GroupedSparseCompressedDense.from_grouped(layer)
+        if sparse == "auto" and made.nbytes() >= layer.nbytes():
+            continue
+        setattr(out, name, made)
+    return out
+
+
+def smallest_grouped_layers(network: nn.Module) -> nn.Module:
+    """A deep copy of a compressed ``network`` in which every GroupedCompressedDense takes the form with the fewest resident bytes
+    (nbytes()) of the three it has: the byte form it is in, the 2- or 4-bit packed form (GroupedPackedCompressedDense, a candidate
+    only with at most 16 centres per group) and the bitmap-sparse form (GroupedSparseCompressedDense).  On equal bytes the order is
+    byte, then packed, then sparse.  All other layers are left as they are.  A layer that ends in the sparse form takes float32
+    activations only."""
+    out = copy.deepcopy(network)
+    for name, layer in out.get_config().items():
+        if not isinstance(layer, GroupedCompressedDense):
+            continue
+        best = layer
+        if layer.centers.shape[1] <= PACKED_MAX_K:
+            made = GroupedPackedCompressedDense.from_grouped(layer)
+            best = made if made.nbytes() < best.nbytes() else best
+        made = GroupedSparseCompressedDense.from_grouped(layer)
+        best = made if made.nbytes() < best.nbytes() else best
+        if best is not layer:
+            setattr(out, name, best)
     return out
 
 

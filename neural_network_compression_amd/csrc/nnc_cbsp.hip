@@ -258,6 +258,19 @@ int cbsp_rowsum_dt(const void *x, int dtype, long long m, long long kdim, float 
     return NNC_OK;
 }
 
+int cbsp_pack_scans(long long kdim, long long segs, uint32_t *lo, uint32_t *hi, long long *nnz, hipStream_t s)
+{
+    if (kdim > 0 && segs > 0) {
+        hipLaunchKernelGGL(k_cbsp_rowscan, dim3((unsigned)std::min<long long>(kdim, 65536)), dim3(256), 0, s, kdim, segs, lo, hi);
+        LAUNCHCHK("k_cbsp_rowscan");
+    }
+    if (kdim > 0 || nnz) {
+        hipLaunchKernelGGL(k_cbsp_basescan, dim3(1), dim3(256), 0, s, kdim, segs, lo, hi, nnz);
+        LAUNCHCHK("k_cbsp_basescan");
+    }
+    return NNC_OK;
+}
+
 static int sp_check_shape(const char *fn, int64_t kdim, int64_t ncols, int label_bytes)
 {
     if (kdim < 0 || ncols < 0) return fail(NNC_EINVAL, std::string(fn) + ": negative size");

@@ -83,7 +83,12 @@ __device__ __forceinline__ void tb_tile_fma_masked(const float *xs, const float 
 int cbsp_rowsum_dt(const void *x, int dtype, long long m, long long kdim, float *rs, hipStream_t s);
 static inline int cbsp_rowsum(const float *x, long long m, long long kdim, float *rs, hipStream_t s) { return cbsp_rowsum_dt(x, NNC_DT_F32, m, kdim, rs, s); }
 
-#define SP_ROWS 64                // rows whose bitmap words one vector load brings to a wave of k_cbsp_stream
+// The two scans of the pack that do not look at a label (k_cbsp_rowscan, k_cbsp_basescan, nnc_cbsp.hip), launched on `s` behind a
+// bits pass that left the popcount of every segment in lo: the counts of the form in lo and hi, the total in *nnz (may be NULL).
+// The group-wise pack (nnc_cbsp_grouped.hip) runs them between its own bits and emit passes.  NNC_OK or the launch error.
+int cbsp_pack_scans(long long kdim, long long segs, uint32_t *lo, uint32_t *hi, long long *nnz, hipStream_t s);
+
+#define SP_ROWS 64               // rows whose bitmap words one vector load brings to a wave of k_cbsp_stream
 
 // ------------------------------------------------------------------ the plan (host)
 // Every decision nnc_cbsp_f32 takes before it launches (nnc_cbsp_h16 follows the stream plan for m <= 16; its m > 16 plan is cb_plan's).

@@ -1007,6 +1007,130 @@ def sparse_codebook_linear(x: torch.Tensor, codes: SparseCodes, centers: torch.T
                                  lambda x2, g2, cd, c: sparse_codebook_centroid_grad(x2, g2, cd, dtype=torch.float32))
 
 
+class GroupedSparseCodes:
+    """The bitmap-sparse form of one (kdim, ncols) uint8 index matrix of a group-wise layer (include/nnc_cbsp_grouped.h; DESIGN.md
+    section 28): the buffer of SparseCodes at one byte per stored symbol, with one skipped symbol per block of ``group_rows`` rows,
+    ``zero_symbols`` (uint8[G] on the device).  ``k`` is the size of every group's codebook."""
+
+    def __init__(self, buf: torch.Tensor, kdim: int, ncols: int, k: int, group_rows: int, zero_symbols: torch.Tensor, nnz: int):
+        self.buf, self.kdim, self.ncols, self.k = buf, int(kdim), int(ncols), int(k)
+        self.group_rows, self.zero_symbols, self.nnz = int(group_rows), zero_symbols, int(nnz)
+
+    @property
+    def device(self):
+        return self.buf.device
+
+    @property
+    def groups(self) -> int:
+        return -(-self.kdim // self.group_rows)
+
+    def density(self) -> float:
+        n = self.kdim * self.ncols
+        return self.nnz / n if n else 0.0
+
+    def nbytes(self) -> int:
+        """Resident bytes of the form: the buffer and the G skipped symbols."""
+        return self.buf.numel() + self.zero_symbols.numel()
+
+    def to_dense(self) -> torch.Tensor:
+        """The kdim * ncols uint8 labels again, by nnc_cbsp_grouped_unpack."""
+        L = nat.load()
+        out = torch.empty(self.kdim * self.ncols, dtype=torch.uint8, device=self.buf.device)
+        nat.check(L.nnc_cbsp_grouped_unpack(_ptr(self.buf), self.buf.numel(), self.kdim, self.ncols, self.group_rows, _ptr(self.zero_symbols), self.nnz,
+                                            _ptr(out), _stream(self.buf)))
+        return out
+
+    def __repr__(self):
+        return (f"GroupedSparseCodes(kdim={self.kdim}, ncols={self.ncols}, k={self.k}, group_rows={self.group_rows}, groups={self.groups}, "
+                f"nnz={self.nnz}, nbytes={self.nbytes()})")
+
+
+def _check_group_rows(kdim: int, group_rows: int) -> int:
+    if group_rows < 32 or group_rows % 32:
+        raise ValueError(f"group_rows must be a positive multiple of 32, got {group_rows}")
+    return -(-kdim // group_rows)
+
+
+def pack_grouped_sparse_codes(labels: torch.Tensor, kdim: int, ncols: int, k: int, group_rows: int,
+                              zero_symbols: torch.Tensor | None = None) -> GroupedSparseCodes:
+    """The (kdim, ncols) uint8 labels of a group-wise layer (any storage offset) -> GroupedSparseCodes on their device
+    (nnc_cbsp_grouped_pack: bitmap, counts, symbols; no per-weight temporary).  ``zero_symbols``: the skipped index of every group
+    (uint8[G] on the device, any byte), by default the most frequent index of the group's rows (ties: the lowest), from nnc_bincount
+    on each group's slice, chosen on the device.  Two passes as pack_sparse_codes: the first returns the count of stored symbols
+    (the one host read)."""
+    _require_cuda(labels, "labels")
+    if labels.dtype != torch.uint8:
+        raise TypeError(f"pack_grouped_sparse_codes takes uint8 labels (K <= 256 per group), got {labels.dtype}")
+    kdim, ncols, k, group_rows = int(kdim), int(ncols), int(k), int(group_rows)
+    if labels.numel() != kdim * ncols:
+        raise ValueError(f"labels must hold kdim * ncols = {kdim * ncols} indices, got {labels.numel()}")
+    if not 1 <= k <= 256:
+        raise ValueError(f"k = {k} outside 1..256")
+    groups = _check_group_rows(kdim, group_rows)
+    labels = labels.reshape(-1)
+    if zero_symbols is None:
+        if groups and ncols:
+            counts = torch.stack([bincount(labels[g * group_rows * ncols: min(kdim, (g + 1) * group_rows) * ncols], k) for g in range(groups)])
+            zero_symbols = torch.argmax(counts, dim=1).to(torch.uint8)
+        else:
+            zero_symbols = torch.zeros(groups, dtype=torch.uint8, device=labels.device)
+    else:
+        _require_cuda(zero_symbols, "zero_symbols", torch.uint8)
+        _one_device("labels and zero_symbols", labels, zero_symbols)
+        if zero_symbols.numel() != groups:
+            raise ValueError(f"zero_symbols must hold one byte per group ({groups}), got {zero_symbols.numel()}")
+        zero_symbols = zero_symbols.reshape(-1)
+    L = nat.load()
+    st = _stream(labels)
+    struct_bytes = int(L.nnc_cbsp_pack_bytes(kdim, ncols, 1, 0))
+    if struct_bytes == 0 and kdim * ncols > 0:
+        raise ValueError(f"no sparse form for a {kdim} x {ncols} matrix (ncols < 2^32, kdim * ceil(ncols / 64) <= 2^40)")
+    nnz_dev = torch.zeros(1, dtype=torch.int64, device=labels.device)
+    probe = _aligned_bytes(struct_bytes, labels.device)
+    nat.check(L.nnc_cbsp_grouped_pack(_ptr(labels), kdim, ncols, group_rows, _ptr(zero_symbols), _ptr(probe), struct_bytes, _ptr(nnz_dev), st))
+    nnz = int(nnz_dev.item())
+    del probe
+    total = int(L.nnc_cbsp_pack_bytes(kdim, ncols, 1, nnz))
+    buf = _aligned_bytes(total, labels.device)
+    nat.check(L.nnc_cbsp_grouped_pack(_ptr(labels), kdim, ncols, group_rows, _ptr(zero_symbols), _ptr(buf), total, None, st))
+    return GroupedSparseCodes(buf, kdim, ncols, k, group_rows, zero_symbols, nnz)
+
+
+def grouped_sparse_codebook_matmul(x: torch.Tensor, codes: GroupedSparseCodes, centers: torch.Tensor, bias: torch.Tensor | None = None,
+                                   relu: bool = False) -> torch.Tensor:
+    """y = t + the stored weights' x[., i] * (centers[g][label] - c_{z_g}) (+ bias, then ReLU), g = i // group_rows and t =
+    sum_g c_{z_g} * (the sum of x over group g's rows): x @ W for W[i, o] = centers[i // group_rows][labels[i, o]] read from the
+    bitmap-sparse form (include/nnc_cbsp_grouped.h, nnc_cbsp_grouped_f32).  A group with c_{z_g} == 0 adds
+    nothing to t and its skipped weights are absent (an Inf in x there meets no 0).  x: float32 (..., kdim); centers: float32
+    (G, codes.k); bias: float32[ncols] or None.  Returns float32 (..., ncols).  float32 activations only: a bfloat16 or float16 x
+    raises ``TypeError``.  Inference only, as sparse_codebook_matmul: it raises under autograd."""
+    if isinstance(x, torch.Tensor) and x.dtype in _H16_DT:
+        raise TypeError(f"grouped_sparse_codebook_matmul takes float32 activations, got {x.dtype}: the group-wise layer runs bfloat16 and "
+                        "float16 inputs from its byte and packed forms (ops.grouped_codebook_matmul, ops.grouped_packed_codebook_matmul)")
+    _require_cuda(x, "x", torch.float32)
+    _require_centers_bias(centers, bias)
+    if not isinstance(codes, GroupedSparseCodes):
+        raise TypeError("codes must be a GroupedSparseCodes (ops.pack_grouped_sparse_codes)")
+    _inference_only("grouped_sparse_codebook_matmul", "x, codes, centers and bias", x, codes.buf, centers, bias)
+    kdim, ncols = codes.kdim, codes.ncols
+    lead, m = _rows(x, "x", kdim)
+    if centers.dim() != 2 or tuple(centers.shape) != (max(codes.groups, 1), codes.k):
+        raise ValueError(f"centers must have shape ({max(codes.groups, 1)}, {codes.k}), got {tuple(centers.shape)}")
+    y = _empty_y(x, lead, ncols, bias, torch.float32)
+    L = nat.load()
+    ws_bytes = int(L.nnc_cbsp_grouped_workspace_bytes(m, kdim, ncols))
+    ws = _workspace(ws_bytes, x.device)
+    nat.check(L.nnc_cbsp_grouped_f32(_ptr(x), m, kdim, _ptr(codes.buf), codes.buf.numel(), ncols, _ptr(codes.zero_symbols), codes.nnz, _ptr(centers),
+                                     codes.k, codes.group_rows, _ptr(bias), 1 if relu else 0, _ptr(y), _ptr(ws), ws_bytes, _stream(x)))
+    return y
+
+
+def cbsp_grouped_plan(m: int, kdim: int, ncols: int, k: int, group_rows: int, cus: int) -> dict:
+    """Host: the plan nnc_cbsp_grouped_f32 follows on a device with ``cus`` compute units (include/nnc_cbsp_grouped.h,
+    nnc_cbsp_grouped_plan), as a dict keyed by _native.CBSP_GROUPED_PLAN_FIELDS.  No device needed."""
+    return _plan(nat.load().nnc_cbsp_grouped_plan, nat.CBSP_GROUPED_PLAN_FIELDS, m, kdim, ncols, k, group_rows, cus)
+
+
 class PackedCodes:
     """The 2- or 4-bit packed form of one (kdim, ncols) index matrix of a codebook of ``k`` <= 2^bits centres (include/nnc.h,
     nnc_cbpk_*): ``packed``, one 256-byte aligned uint8 device buffer of kdim rows of nnc_cbpk_row_bytes(ncols, bits) bytes, and
