@@ -4,6 +4,7 @@ codebook_linear, csrc/nnc_cbgrad.hip).
 - ``dx64`` / ``dc64``: the float64 formulas of include/nnc.h (an index >= K reads 0 in dx and falls into no bin in dc).
 - ``dx_bound`` / ``dc_bound``: the float32 error bounds of DESIGN.md section 12.
 - ``REGIME_CASES`` / ``dx_regime`` / ``dc_regime``: calls that, between them, hit every regime the two plans can choose.
+- ``case_data`` and the formulas also serve tests/helpers/stream_cells_ref.py, whose cases reach every stream instantiation.
 Test infrastructure only."""
 from __future__ import annotations
 

@@ -7,6 +7,8 @@ nnc_cbmm_grouped_dc_f32, csrc/nnc_cbgrad_grouped.hip), sha
 - ``exact_data`` / ``float_data``: group q's centres are offset by 64 q (as grouped_ref), so a row read from the wrong table shows.
 - ``dx64`` / ``dc64`` and ``dx_bound`` / ``dc_bound``: cbgrad_ref's formulas and bounds, taken group by group.
 - ``labels16``: the one-codebook image of the grouped indices, q * K + label, for the identity with codebook_centroid_grad.
+- ``exact_data`` / ``labels_of`` and the formulas also serve tests/helpers/stream_cells_ref.py, whose cases reach every stream instantiation
+  (DESIGN.md section 29).
 Test infrastructure only."""
 from __future__ import annotations
 

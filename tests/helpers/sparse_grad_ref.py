@@ -6,6 +6,7 @@ sparse_codebook_centroid_grad / sparse_codebook_linear, csrc/nnc_cbspgrad.hip).
   c_z == 0).
 - ``dx_bound``: the DESIGN.md section 13 bound of |dx - g @ W^T| (W decoded, float64).
 - ``REGIME_CASES`` / ``dx_regime`` / ``dc_regime``: calls that, between them, hit every regime of the two plans.
+- ``case_data`` and ``dx64`` also serve tests/helpers/stream_cells_ref.py, whose cases reach every stream instantiation.
 Test infrastructure only."""
 from __future__ import annotations
 
