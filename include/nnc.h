@@ -824,6 +824,10 @@ int nnc_cbsp_f32(const float *x, int64_t m, int64_t kdim, const void *packed, in
  * with a skipped symbol per group, nnc_cbsp_grouped_f32, its workspace query and its plan.  A header of its own, part of this ABI. */
 #include "nnc_cbsp_grouped.h"
 
+/* The same group-wise form on bf16 / fp16 activations (csrc/nnc_cbsp_grouped_h16.hip): nnc_cbsp_grouped_h16,
+ * its workspace query and its plan.  A header of its own, part of this ABI. */
+#include "nnc_cbsp_grouped_h16.h"
+
 /* ------------------------------------------------------------------------------------
  * The quantized layer of at most 16 centres run from 2- or 4-bit packed indices (csrc/nnc_cbpk.hip): a
  * third resident form of the (kdim, ncols) index matrix, row-major as nnc_cbmm_f32 reads it, beside the byte form and the

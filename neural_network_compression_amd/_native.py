@@ -51,6 +51,8 @@ CBSP_PLAN_LEN = 11
 CBSP_PLAN_FIELDS = ("path", "mt", "copies", "entries", "splits", "rps", "rowsum", "lds", "col_tiles", "row_tiles", "workspace")
 CBSP_GROUPED_PLAN_LEN = 14   # nnc_cbsp_grouped_plan (include/nnc_cbsp_grouped.h): the sparse fields, then the groups
 CBSP_GROUPED_PLAN_FIELDS = CBSP_PLAN_FIELDS + ("group_rows", "groups", "max_groups_per_split")
+CBSP_GROUPED_H16_PLAN_LEN = 15   # nnc_cbsp_grouped_h16_plan (include/nnc_cbsp_grouped_h16.h): the grouped sparse fields, then the dtype; path is CBMM_MFMA for m > 16
+CBSP_GROUPED_H16_PLAN_FIELDS = CBSP_GROUPED_PLAN_FIELDS + ("dtype",)
 CBSP_H16_PLAN_LEN = 12   # nnc_cbsp_h16_plan (include/nnc_cbsp_h16.h): path is CBMM_MFMA for m > 16
 CBSP_H16_PLAN_FIELDS = CBSP_PLAN_FIELDS + ("dtype",)
 CBPK_TABLE_NONE, CBPK_TABLE_BANKED = 0, 1   # nnc_cbpk_plan: the layout of the lookup table (include/nnc.h)
@@ -389,6 +391,15 @@ GROUPED_SPARSE_SIGNATURES = {
                                      c_void_p, c_i64, c_void_p]),
 }
 
+# name -> (restype, argtypes); every symbol include/nnc_cbsp_grouped_h16.h declares (the bitmap-sparse form of the group-wise layer on
+# bf16 / fp16 activations, again a header of its own that nnc.h includes).  Required and bound by load() as SIGNATURES are.
+GROUPED_SPARSE_H16_SIGNATURES = {
+    "nnc_cbsp_grouped_h16_workspace_bytes": (c_i64, [c_int, c_i64, c_i64, c_i64]),
+    "nnc_cbsp_grouped_h16_plan": (c_int, [c_int, c_i64, c_i64, c_i64, c_i32, c_i64, c_i32, ctypes.POINTER(c_i64)]),
+    "nnc_cbsp_grouped_h16": (c_int, [c_void_p, c_int, c_i64, c_i64, c_void_p, c_i64, c_i64, c_void_p, c_i64, c_void_p, c_i32, c_i64, c_void_p, c_i32, c_void_p,
+                                     c_int, c_void_p, c_i64, c_void_p]),
+}
+
 # exported only by the diagnostics build (NNC_DIAG=1: libnnc_hip_diag.so, see build.py); bound when present
 DIAG_SIGNATURES = {
     "nnc_debug_set_ablation": (c_int, [c_int]),
@@ -421,7 +432,7 @@ def load():
         L = ctypes.CDLL(path)
     except OSError as e:  # pragma: no cover - depends on the machine
         raise NativeLibraryError(f"cannot load {path}: {e}; there is no CPU fallback") from e
-    for name, (res, args) in list(SIGNATURES.items()) + list(GROUPED_GRAD_SIGNATURES.items()) + list(H16_GRAD_SIGNATURES.items()) + list(GROUPED_PACKED_GRAD_SIGNATURES.items()) + list(SPARSE_H16_SIGNATURES.items()) + list(SPARSE_H16_GRAD_SIGNATURES.items()) + list(PACKED_H16_SIGNATURES.items()) + list(GROUPED_H16_GRAD_SIGNATURES.items()) + list(GROUPED_SPARSE_SIGNATURES.items()):
+    for name, (res, args) in list(SIGNATURES.items()) + list(GROUPED_GRAD_SIGNATURES.items()) + list(H16_GRAD_SIGNATURES.items()) + list(GROUPED_PACKED_GRAD_SIGNATURES.items()) + list(SPARSE_H16_SIGNATURES.items()) + list(SPARSE_H16_GRAD_SIGNATURES.items()) + list(PACKED_H16_SIGNATURES.items()) + list(GROUPED_H16_GRAD_SIGNATURES.items()) + list(GROUPED_SPARSE_SIGNATURES.items()) + list(GROUPED_SPARSE_H16_SIGNATURES.items()):
         try:
             fn = getattr(L, name)
         except AttributeError as e:

@@ -54,8 +54,9 @@ most 16 centres per group: ``GroupedPackedCompressedDense`` (ops.grouped_packed_
 DESIGN.md section 18), the same function from a half or a quarter of the index bytes, on the same three input dtypes.
 ``sparsify_grouped_layers(network, sparse=True | "auto")`` is the way to the bitmap-sparse form of a pruned grouped layer, with one
 skipped index per group: ``GroupedSparseCompressedDense`` (ops.grouped_sparse_codebook_matmul, csrc/nnc_cbsp_grouped.hip, DESIGN.md
-section 28), on float32 inputs only; ``smallest_grouped_layers(network)`` picks per layer, by resident bytes, among the byte, the
-packed and the sparse form.
+section 28), on float32 inputs, and built with ``half_inputs=True`` (a keyword of the layer and of both functions here) on bfloat16 and
+float16 inputs too (csrc/nnc_cbsp_grouped_h16.hip); ``smallest_grouped_layers(network)`` picks per layer, by
+resident bytes, among the byte, the packed and the sparse form.
 
 These layers are inference only: under autograd, with an input that needs a gradient, they raise instead of returning a result
 that silently has none.  ``trainable=True`` in compress_network / Trainer.compressed_network gives the trainable variants instead
@@ -862,13 +863,16 @@ class GroupedSparseCompressedDense(_DenseHalf, _InferenceLayer):
     """Dense run from one codebook per block of ``group_rows`` input rows and the bitmap-sparse form of its (in, out) indices
     (ops.grouped_sparse_codebook_matmul): packed (the bitmap-sparse buffer of the whole index matrix, one
     byte per stored symbol), zero_symbols (the skipped index of every group, uint8[G]), centers float32 (G, K), G = ceil(kdim /
-    group_rows), bias float32[ncols] or None.  float32 activations only: a bfloat16 or float16 input raises TypeError.  Inference
+    group_rows), bias float32[ncols] or None.  ``half_inputs=True`` lets the layer run on bfloat16 / float16 inputs
+    (ops.grouped_sparse_codebook_matmul -> nnc_cbsp_grouped_h16): the path is chosen by the input's dtype and
+    the output has that dtype; centers and bias stay float32.  Without it a half input raises TypeError, as it always did.  Inference
     only.  No kdim * ncols tensor stays resident."""
 
     _INDEX = "packed"
 
-    def __init__(self, codes: ops.GroupedSparseCodes, centers: torch.Tensor, bias: torch.Tensor | None, activation=None):
+    def __init__(self, codes: ops.GroupedSparseCodes, centers: torch.Tensor, bias: torch.Tensor | None, activation=None, half_inputs: bool = False):
         super().__init__()
+        self.half_inputs = bool(half_inputs)
         groups = max(1, codes.groups)
         if centers.dim() != 2 or tuple(centers.shape) != (groups, codes.k):
             raise ValueError(f"centers must have shape ({groups}, {codes.k}) for {codes.kdim} rows in groups of {codes.group_rows} and indices into "
@@ -883,32 +887,36 @@ class GroupedSparseCompressedDense(_DenseHalf, _InferenceLayer):
         return ops.GroupedSparseCodes(self.packed, self.kdim, self.ncols, self.k, self.group_rows, self.zero_symbols, self.nnz)
 
     @classmethod
-    def from_dense(cls, dense, grouped_model, bias_model=None, zero_symbols=None) -> "GroupedSparseCompressedDense":
+    def from_dense(cls, dense, grouped_model, bias_model=None, zero_symbols=None, half_inputs: bool = False) -> "GroupedSparseCompressedDense":
         """From a Dense layer and the GroupedModel of its kernel (utility.get_quantized_weight_grouped)."""
         _require_model(grouped_model)
         kin, kout = dense.kernel.shape
         centers = torch.from_numpy(np.ascontiguousarray(grouped_model.cluster_centers_, dtype=np.float32)).to(dense.kernel.device)
         return cls.from_codes(kin, kout, grouped_model.group_rows, grouped_model.labels_compact_, centers, _decoded_bias(dense.bias, bias_model),
-                              dense.activation, zero_symbols)
+                              dense.activation, zero_symbols, half_inputs)
 
     @classmethod
-    def from_codes(cls, kdim, ncols, group_rows, labels, centers, bias, activation, zero_symbols=None) -> "GroupedSparseCompressedDense":
+    def from_codes(cls, kdim, ncols, group_rows, labels, centers, bias, activation, zero_symbols=None,
+                   half_inputs: bool = False) -> "GroupedSparseCompressedDense":
         if centers.dim() != 2:
             raise ValueError(f"centers must have shape (G, K), got {tuple(centers.shape)}")
-        return cls(ops.pack_grouped_sparse_codes(labels, kdim, ncols, centers.shape[1], group_rows, zero_symbols), centers, bias, activation)
+        return cls(ops.pack_grouped_sparse_codes(labels, kdim, ncols, centers.shape[1], group_rows, zero_symbols), centers, bias, activation,
+                   half_inputs)
 
     @classmethod
-    def from_grouped(cls, layer: GroupedCompressedDense, zero_symbols=None) -> "GroupedSparseCompressedDense":
+    def from_grouped(cls, layer: GroupedCompressedDense, zero_symbols=None, half_inputs: bool = False) -> "GroupedSparseCompressedDense":
         """The same layer from the bitmap-sparse form of a GroupedCompressedDense's indices: the same weights, the sums in the
         order of DESIGN.md section 28."""
-        return cls.from_codes(layer.kdim, layer.ncols, layer.group_rows, layer.labels, layer.centers, layer.bias, layer.activation, zero_symbols)
+        return cls.from_codes(layer.kdim, layer.ncols, layer.group_rows, layer.labels, layer.centers, layer.bias, layer.activation, zero_symbols,
+                              half_inputs)
 
     def nbytes(self) -> int:
         """The buffer, the G skipped symbols, the G * K centres and the bias."""
         return super().nbytes() + _tensor_bytes(self.zero_symbols)
 
     def _matmul(self, x: torch.Tensor) -> torch.Tensor:
-        return self._activate(ops.grouped_sparse_codebook_matmul(x, self.codes, self.centers, bias=self.bias, relu=self._fused_relu))
+        return self._activate(ops.grouped_sparse_codebook_matmul(x, self.codes, self.centers, bias=self.bias, relu=self._fused_relu,
+                                                                 half_inputs=self.half_inputs))
 
 
 class TrainableGroupedPackedCompressedDense(_DenseHalf, _PackedForm, _TrainableCentres):
@@ -1284,32 +1292,35 @@ def pack_grouped_layers(network: nn.Module, packed=True) -> nn.Module:
     return out
 
 
-def sparsify_grouped_layers(network: nn.Module, sparse=True) -> nn.Module:
+def sparsify_grouped_layers(network: nn.Module, sparse=True, half_inputs: bool = False) -> nn.Module:
     """A deep copy of a compressed ``network`` (compress_network, Trainer.compressed_network() or load_network) whose
     GroupedCompressedDense layers keep their indices in the bitmap-sparse form with one skipped index per group
     (GroupedSparseCompressedDense).  ``sparse``: True (every GroupedCompressedDense) or "auto" (a layer only
     where the sparse form holds fewer resident bytes; on equal bytes the byte form stays); anything else is a ValueError.
-    GroupedPackedCompressedDense layers and all other layers are left as they are.  A replaced layer has the same weights and takes
-    float32 activations only; its sums run in another order (within the float bound of section 28, the same bits on exact data)."""
+    GroupedPackedCompressedDense layers and all other layers are left as they are.  A replaced layer has the same weights; its sums run
+    in another order (within the float bound of section 28, the same bits on exact data).  It takes float32 activations, and with
+    ``half_inputs=True`` bfloat16 and float16 ones too (GroupedSparseCompressedDense(half_inputs=True), DESIGN.md section 30);
+    ``half_inputs`` does not change which layers are replaced."""
     if sparse is not True and sparse != "auto":
         raise ValueError(f"sparse must be True or 'auto', got {sparse!r}")
     out = copy.deepcopy(network)
     for name, layer in out.get_config().items():
         if not isinstance(layer, GroupedCompressedDense):
             continue
-        made = GroupedSparseCompressedDense.from_grouped(layer)
+        made = GroupedSparseCompressedDense.from_grouped(layer, half_inputs=half_inputs)
         if sparse == "auto" and made.nbytes() >= layer.nbytes():
             continue
         setattr(out, name, made)
     return out
 
 
-def smallest_grouped_layers(network: nn.Module) -> nn.Module:
+def smallest_grouped_layers(network: nn.Module, half_inputs: bool = False) -> nn.Module:
     """A deep copy of a compressed ``network`` in which every GroupedCompressedDense takes the form with the fewest resident bytes
     (nbytes()) of the three it has: the byte form it is in, the 2- or 4-bit packed form (GroupedPackedCompressedDense, a candidate
     only with at most 16 centres per group) and the bitmap-sparse form (GroupedSparseCompressedDense).  On equal bytes the order is
     byte, then packed, then sparse.  All other layers are left as they are.  A layer that ends in the sparse form takes float32
-    activations only."""
+    activations, and with ``half_inputs=True`` bfloat16 and float16 ones too, as the other two forms do (DESIGN.md section 30);
+    ``half_inputs`` does not change which form is picked."""
     out = copy.deepcopy(network)
     for name, layer in out.get_config().items():
         if not isinstance(layer, GroupedCompressedDense):
@@ -1318,7 +1329,7 @@ def smallest_grouped_layers(network: nn.Module) -> nn.Module:
         if layer.centers.shape[1] <= PACKED_MAX_K:
             made = GroupedPackedCompressedDense.from_grouped(layer)
             best = made if made.nbytes() < best.nbytes() else best
-        made = GroupedSparseCompressedDense.from_grouped(layer)
+        made = GroupedSparseCompressedDense.from_grouped(layer, half_inputs=half_inputs)
         best = made if made.nbytes() < best.nbytes() else best
         if best is not layer:
             setattr(out, name, best)

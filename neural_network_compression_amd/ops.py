@@ -1097,17 +1097,35 @@ def pack_grouped_sparse_codes(labels: torch.Tensor, kdim: int, ncols: int, k: in
 
 
 def grouped_sparse_codebook_matmul(x: torch.Tensor, codes: GroupedSparseCodes, centers: torch.Tensor, bias: torch.Tensor | None = None,
-                                   relu: bool = False) -> torch.Tensor:
+                                   relu: bool = False, out_dtype=None, half_inputs: bool = False) -> torch.Tensor:
     """y = t + the stored weights' x[., i] * (centers[g][label] - c_{z_g}) (+ bias, then ReLU), g = i // group_rows and t =
     sum_g c_{z_g} * (the sum of x over group g's rows): x @ W for W[i, o] = centers[i // group_rows][labels[i, o]] read from the
     bitmap-sparse form (include/nnc_cbsp_grouped.h, nnc_cbsp_grouped_f32).  A group with c_{z_g} == 0 adds
     nothing to t and its skipped weights are absent (an Inf in x there meets no 0).  x: float32 (..., kdim); centers: float32
-    (G, codes.k); bias: float32[ncols] or None.  Returns float32 (..., ncols).  float32 activations only: a bfloat16 or float16 x
-    raises ``TypeError``.  Inference only, as sparse_codebook_matmul: it raises under autograd."""
-    if isinstance(x, torch.Tensor) and x.dtype in _H16_DT:
-        raise TypeError(f"grouped_sparse_codebook_matmul takes float32 activations, got {x.dtype}: the group-wise layer runs bfloat16 and "
-                        "float16 inputs from its byte and packed forms (ops.grouped_codebook_matmul, ops.grouped_packed_codebook_matmul)")
-    _require_cuda(x, "x", torch.float32)
+    (G, codes.k); bias: float32[ncols] or None.  Returns float32 (..., ncols).
+    With ``half_inputs=True`` a bfloat16 or float16 x takes nnc_cbsp_grouped_h16 (include/nnc_cbsp_grouped_h16.h; DESIGN.md section
+    30): centers and bias stay float32, every centre is rounded to x's dtype as ``centers.to(x.dtype)`` does, the products are exact
+    and the sums float32; the result has ``out_dtype``: None (x's dtype, the float32 value rounded once) or torch.float32.  Up to 16
+    rows of x it is the float32 product of the widened x and the rounded centres bit for bit; above, it is
+    ops.grouped_codebook_matmul on ``codes.to_dense()`` bit for bit, in which a skipped weight is an entry of W (an Inf in x at a
+    skipped position gives NaN).  Without the keyword a bfloat16 or float16 x raises ``TypeError``, as it always did; a float32 x
+    takes the same call with or without it, and no ``out_dtype`` but None or torch.float32.
+    Inference only, as sparse_codebook_matmul: it raises under autograd."""
+    half = isinstance(x, torch.Tensor) and x.dtype in _H16_DT
+    if half and not half_inputs:
+        raise TypeError(f"grouped_sparse_codebook_matmul takes float32 activations, got {x.dtype}: pass half_inputs=True to run bfloat16 and "
+                        "float16 inputs from the bitmap-sparse form (or use the byte and packed forms, ops.grouped_codebook_matmul, "
+                        "ops.grouped_packed_codebook_matmul)")
+    if half:
+        _require_cuda(x, "x")
+        if out_dtype not in (None, torch.float32):
+            raise TypeError(f"out_dtype must be None ({x.dtype}) or torch.float32 for x of {x.dtype}, got {out_dtype}")
+        y_dtype = x.dtype if out_dtype is None else out_dtype
+    else:
+        _require_cuda(x, "x", torch.float32)
+        if out_dtype not in (None, torch.float32):
+            raise TypeError(f"out_dtype must be None or torch.float32 for a float32 x, got {out_dtype}")
+        y_dtype = torch.float32
     _require_centers_bias(centers, bias)
     if not isinstance(codes, GroupedSparseCodes):
         raise TypeError("codes must be a GroupedSparseCodes (ops.pack_grouped_sparse_codes)")
@@ -1116,8 +1134,15 @@ def grouped_sparse_codebook_matmul(x: torch.Tensor, codes: GroupedSparseCodes, c
     lead, m = _rows(x, "x", kdim)
     if centers.dim() != 2 or tuple(centers.shape) != (max(codes.groups, 1), codes.k):
         raise ValueError(f"centers must have shape ({max(codes.groups, 1)}, {codes.k}), got {tuple(centers.shape)}")
-    y = _empty_y(x, lead, ncols, bias, torch.float32)
+    y = _empty_y(x, lead, ncols, bias, y_dtype)
     L = nat.load()
+    if half:
+        ws_bytes = int(L.nnc_cbsp_grouped_h16_workspace_bytes(_H16_DT[x.dtype], m, kdim, ncols))
+        ws = _workspace(ws_bytes, x.device)
+        nat.check(L.nnc_cbsp_grouped_h16(_ptr(x), _H16_DT[x.dtype], m, kdim, _ptr(codes.buf), codes.buf.numel(), ncols, _ptr(codes.zero_symbols),
+                                         codes.nnz, _ptr(centers), codes.k, codes.group_rows, _ptr(bias), 1 if relu else 0, _ptr(y),
+                                         _H16_DT.get(y_dtype, nat.DT_F32), _ptr(ws), ws_bytes, _stream(x)))
+        return y
     ws_bytes = int(L.nnc_cbsp_grouped_workspace_bytes(m, kdim, ncols))
     ws = _workspace(ws_bytes, x.device)
     nat.check(L.nnc_cbsp_grouped_f32(_ptr(x), m, kdim, _ptr(codes.buf), codes.buf.numel(), ncols, _ptr(codes.zero_symbols), codes.nnz, _ptr(centers),
@@ -1129,6 +1154,13 @@ def cbsp_grouped_plan(m: int, kdim: int, ncols: int, k: int, group_rows: int, cu
     """Host: the plan nnc_cbsp_grouped_f32 follows on a device with ``cus`` compute units (include/nnc_cbsp_grouped.h,
     nnc_cbsp_grouped_plan), as a dict keyed by _native.CBSP_GROUPED_PLAN_FIELDS.  No device needed."""
     return _plan(nat.load().nnc_cbsp_grouped_plan, nat.CBSP_GROUPED_PLAN_FIELDS, m, kdim, ncols, k, group_rows, cus)
+
+
+def cbsp_grouped_h16_plan(dtype, m: int, kdim: int, ncols: int, k: int, group_rows: int, cus: int) -> dict:
+    """Host: the plan nnc_cbsp_grouped_h16 follows for x of ``dtype`` (torch.bfloat16 / torch.float16) on a device with ``cus`` compute
+    units (include/nnc_cbsp_grouped_h16.h, nnc_cbsp_grouped_h16_plan), as a dict keyed by _native.CBSP_GROUPED_H16_PLAN_FIELDS.  No
+    device needed."""
+    return _plan(nat.load().nnc_cbsp_grouped_h16_plan, nat.CBSP_GROUPED_H16_PLAN_FIELDS, _h16_dt(dtype), m, kdim, ncols, k, group_rows, cus)
 
 
 class PackedCodes:
