@@ -6,7 +6,7 @@
 // The plans are the ungrouped half ones at label_bytes 1 (section 12's stream plans; nnc_cbh16plan.hpp's tiles and splits with the
 // byte form's table and bins at m > 16) plus the group fields, as section 19 took the float32 ones: the path, the tiles, the splits,
 // the order of every sum and the shift S of the dc sums are those of nnc_cbmm_dx_h16 / nnc_cbmm_dc_h16 on the same shape.  The
-// two main loops are the ungrouped kernels' (dxm_accumulate, dcm_accumulate), the pick of a row's table or set tile_group_of
+// two main loops are the ungrouped kernels' (hm_accumulate, dcm_accumulate), the pick of a row's table or set tile_group_of
 // (nnc_cbgrad_grouped.hpp).
 //   m <= 16   k_cbdx_stream_grouped<XT> / k_cbdc_stream_grouped<XT> of nnc_cbgrad_grouped.hpp: section 19's kernels with g and x
 //             widened as they are loaded and, for dx, the tables of the rounded centres.
@@ -71,7 +71,7 @@ __global__ __launch_bounds__(HM_THREADS) void k_cbdx_mfma_grouped(const XT *__re
     };
 
     typename HFrag<XT>::C acc[2][2];
-    dxm_accumulate<XT, XVEC>(g, m, ncols, T, gs, ws, acc, load_w, store_w);
+    hm_accumulate<XT, XVEC>(g, m, ncols, T, gs, ws, acc, load_w, store_w);
     hm_store_y<XT>(acc, T.n0, T.m0, T.wm, T.wn, T.lane, m, kdim, nullptr, 0, direct, out_);
 }
 

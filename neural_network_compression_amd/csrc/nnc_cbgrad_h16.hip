@@ -19,7 +19,7 @@
 //             for every element whose scaled value is a normal bf16); fp16 operands are not scaled.  The epilogue bins the
 //             accumulators: cbdc_fix, the 64-bit LDS atomicAdd into the replicated bins, cbdc_flush.
 // Everything past m, kdim, ncols and the end of a split is zero in both images, never memory.  No float atomics; no host read.
-// The two main loops are shared with the other four half backward units (section 27): dxm_accumulate (nnc_cbdxm.hpp) around this
+// The two main loops are shared with the other four half backward units (section 27): hm_accumulate (nnc_cbmfma.hpp) around this
 // form's label load and lookup, dcm_accumulate (nnc_cbgrad_h16.hpp) in front of this form's epilogue; the tiles and splits of the
 // MFMA plan and the half glue of the entry points are nnc_cbh16plan.hpp's.
 #include "nnc_cbdxm.hpp"
@@ -27,7 +27,7 @@
 #include "nnc_cbh16plan.hpp"
 
 // ------------------------------------------------------------------ dx, m > 16
-// (the main loop, dxm_accumulate, and the label load, dxm_load_labels, are nnc_cbdxm.hpp's)
+// (the main loop, hm_accumulate, is the tile's, nnc_cbmfma.hpp; the label load, dxm_load_labels, is nnc_cbdxm.hpp's)
 // grid (kdim tiles * m tiles, splits of ncols), HM_THREADS threads.  `out` is dx (direct 1: float32, 2: XT) or the float32 partials
 // [split][m][kdim] (direct 0).  cols_per_split is a multiple of HM_BK.
 template <typename XT, typename LT, bool XVEC>
@@ -64,7 +64,7 @@ __global__ __launch_bounds__(HM_THREADS) void k_cbdx_mfma(const XT *__restrict__
     };
 
     typename HFrag<XT>::C acc[2][2];
-    dxm_accumulate<XT, XVEC>(g, m, ncols, T, gs, ws, acc, load_w, store_w);
+    hm_accumulate<XT, XVEC>(g, m, ncols, T, gs, ws, acc, load_w, store_w);
     hm_store_y<XT>(acc, T.n0, T.m0, T.wm, T.wn, T.lane, m, kdim, nullptr, 0, direct, out_);
 }
 

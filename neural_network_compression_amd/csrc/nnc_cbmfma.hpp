@@ -1,13 +1,32 @@
-// nnc_cbmfma.hpp -- the 128 x 128 MFMA tile of the bf16 / fp16 codebook kernels at m > 16, written once: k_cbmm_mfma
-// (nnc_cbmm_h16.hip), k_cbmm_mfma_grouped (nnc_cbmm_grouped.hip) and k_cbpk_mfma_grouped (nnc_cbpk_grouped.hip).  HM_THREADS
-// threads, 4 waves, each a 64 x 64 quarter as 2 x 2 v_mfma_f32_32x32x16 accumulators; grid (column tiles * row tiles, splits).  A
-// kernel keeps its signature, its LDS carve-up, its table (cb_fill, and cb_refill on the walk through the groups), its label load
-// (a byte, two bytes, a packed field) and its table lookup, and calls these for the rest: the tile coordinates, the x fragments,
-// the two LDS images, the k step and the C / D epilogue.  The barriers, the load-next-before-MFMA order and the loop over the
-// k steps stay in these forward kernels, as the decode of the tiled float32 kernels does around nnc_cbtile.hpp; the backward kernels
-// on the same tile share theirs (dxm_accumulate of nnc_cbdxm.hpp, dcm_accumulate of nnc_cbgrad_h16.hpp).
+// nnc_cbmfma.hpp -- the 128 x 128 MFMA tile of the bf16 / fp16 codebook kernels at m > 16, written once.
+// HM_THREADS threads, 4 waves, each a 64 x 64 quarter as 2 x 2 v_mfma_f32_32x32x16 accumulators; grid (column tiles * row tiles,
+// splits).  Nine kernels run its k loop, hm_accumulate: four forward kernels (k_cbmm_mfma_grouped, k_cbpk_mfma_grouped, k_cbsp_mfma,
+// k_cbspg_mfma) and the five dx kernels (k_cbdx_mfma, k_cbspdx_mfma, k_cbpkdx_mfma, k_cbdx_mfma_grouped, k_cbpkdx_mfma_grouped);
+// k_cbmm_mfma keeps the same loop written out, because through the callables it compiled to a slower instruction stream (section
+// 31).  The dc kernels run dcm_accumulate (nnc_cbgrad_h16.hpp) on the same fragments.  A
+// kernel keeps its signature, its table (cb_fill; cb_refill on the walk through the groups, as the loop's `open`) and the load of
+// its index form (a byte, two bytes, a packed field, the bitmap-sparse decode of nnc_cbsp.hpp), and takes the rest from here: the
+// LDS carve-up, the tile coordinates, the x fragments, the two LDS images, the lookup into the W image, the barriers and the
+// load-next-before-MFMA order of the k loop, the k step and the C / D epilogue.
 #pragma once
 #include "nnc_cbmm.hpp"
+
+// the dynamic LDS of a forward kernel: the per-bank table (entries << cshift words), the stage cb_fill copies from (entries
+// words), then the two images
+template <typename XT> struct HmLds {
+    float *cb, *stage;
+    XT *xs, *ws;   // [HM_BM][HM_LD]: x tile, row-major in k; [HM_BN][HM_LD]: W tile, column-major (k contiguous)
+};
+
+template <typename XT> __device__ __forceinline__ HmLds<XT> hm_lds(float *smem, int entries, int cshift)
+{
+    HmLds<XT> L;
+    L.cb = smem;
+    L.stage = smem + (entries << cshift);
+    L.xs = reinterpret_cast<XT *>(smem + hm_table_words(entries, cshift));
+    L.ws = L.xs + HM_BM * HM_LD;
+    return L;
+}
 
 // Thread t of the tile at (m0, n0), split [k_lo, k_hi).  W image: t owns column wc and the 16 rows wk0 .. wk0 + 15 of a k step.
 // MFMA: lane l of a 32x32x16 holds A[row l & 31][k = 8 (l >> 5) + e] and B[k = 8 (l >> 5) + e][col l & 31], e = 0..7, so the
@@ -84,6 +103,18 @@ template <typename XT> __device__ __forceinline__ void hm_store_w(XT *ws, int wc
     *reinterpret_cast<typename HFrag<XT>::V *>(ws + wc * HM_LD + wk0 + 8) = w1;
 }
 
+// The W image of the step at kb from the thread's 16 labels: cb[index(lab[j])] for its rows kb + wk0 + j, and zero past k_hi and
+// where the thread's column does not exist (col_ok false), never the table: a label there is no label, and a NaN centre would reach
+// valid outputs as NaN * 0.  `index` is the kernel's table lookup (CbTable<LT>::index, or the packed form's fixed shift).
+template <typename XT, typename Index>
+__device__ __forceinline__ void hm_lookup_w(XT *ws, const float *cb, const HmTile &T, bool col_ok, long long kb, const uint32_t (&lab)[16], Index index)
+{
+    float w[16];
+#pragma unroll
+    for (int j = 0; j < 16; ++j) w[j] = (col_ok && kb + T.wk0 + j < T.k_hi) ? cb[index(lab[j])] : 0.0f;
+    hm_store_w(ws, T.wc, T.wk0, w);
+}
+
 template <typename XT> __device__ __forceinline__ void hm_clear(typename HFrag<XT>::C (&acc)[2][2])
 {
 #pragma unroll
@@ -112,6 +143,47 @@ __device__ __forceinline__ void hm_step(const XT *xs, const XT *ws, int wm, int 
         for (int i = 0; i < 2; ++i)
 #pragma unroll
             for (int j = 0; j < 2; ++j) acc[i][j] = F::mfma(a[i], b[j], acc[i][j]);
+    }
+}
+
+// The k loop of the tile: acc = the 128 x 128 tile of x W over the k range [T.k_lo, T.k_hi) of the split, in steps of HM_BK.  x has
+// m rows of length kdim and T.m0 is the tile's first; xs [HM_BM][HM_LD] is its image, row-major in k (hm_load_x / hm_store_x).
+// ws [HM_BN][HM_LD] is the W image [column][k], which the kernel's callables fill: load_w(kb) fetches what the thread needs of its
+// index form for the step at kb, one step ahead of the MFMAs that consume it, and store_w(kb) looks it up and writes the thread's 16
+// values (hm_lookup_w, hm_store_w).  ahead(kb), behind the loads of x, is for a form that requests something for the step after
+// kb there (the bitmap words of the sparse forms, which their kernels request for T.k_lo themselves in front of the call).
+// open(kb) runs at the top of every step in front of its first barrier, when the lookups of the step before have ended (at that
+// step's second barrier): the grouped kernels refill the table there when the step opens a group.  Whatever steers a callable
+// must be uniform over the workgroup: every wave reaches both barriers of every step.  The first barrier also orders what the
+// caller wrote to LDS before the call (the table).  A forward kernel passes (x, m, kdim); a dx kernel passes (g, m, ncols), its
+// tile being dx = g W^T over the columns of the split, T.n0 its first index row and ws the W^T image [i][o].
+struct HmNothing {
+    __device__ __forceinline__ void operator()(long long) const {}
+};
+
+template <typename XT, bool XVEC, typename LoadW, typename StoreW, typename Ahead = HmNothing, typename Open = HmNothing>
+__device__ __forceinline__ void hm_accumulate(const XT *x, long long m, long long kdim, const HmTile T, XT *xs, const XT *ws,
+                                              typename HFrag<XT>::C (&acc)[2][2], LoadW load_w, StoreW store_w, Ahead ahead = Ahead(), Open open = Open())
+{
+    uint4 xf[2];
+    auto load = [&](long long kb) {
+        load_w(kb);
+#pragma unroll
+        for (int i = 0; i < 2; ++i) xf[i] = hm_load_x<XT, XVEC>(x, m, kdim, T.m0, kb, T.k_hi, T.t + i * HM_THREADS);
+        ahead(kb);
+    };
+
+    hm_clear<XT>(acc);
+    load(T.k_lo);
+    for (long long kb = T.k_lo; kb < T.k_hi; kb += HM_BK) {
+        open(kb);
+        __syncthreads();   // the table is filled (first step, or refilled); the images of the step before have been read
+        store_w(kb);
+#pragma unroll
+        for (int i = 0; i < 2; ++i) hm_store_x(xs, T.t + i * HM_THREADS, xf[i]);
+        __syncthreads();
+        if (kb + HM_BK < T.k_hi) load(kb + HM_BK);
+        hm_step(xs, ws, T.wm, T.wn, T.fr, T.fh, acc);
     }
 }
 

@@ -5,8 +5,9 @@
 // type of x: nnc_cbmm.hip instantiates them for float32, nnc_cbmm_h16.hip for bf16 / fp16 activations.  The group-wise unit
 // (nnc_cbmm_grouped.hip: one codebook per block of rows) follows the same plan and takes cb_fill, cb_refill, the label-row loads,
 // tb_tile_fma and HFrag from here.  cb_mt and cb_check_workspace serve every entry point of the nnc_cb*.hip units; cb_check_operands,
-// cb_direct and cb_finish the three that take half x (nnc_cbmm_h16, nnc_cbmm_grouped, nnc_cbpk_grouped).  The MFMA tile of those
-// three is nnc_cbmfma.hpp.
+// cb_direct and cb_finish the five forward units that take half x (nnc_cbmm_h16, nnc_cbmm_grouped, nnc_cbpk_grouped, nnc_cbsp_h16,
+// nnc_cbsp_grouped_h16).  The MFMA tile and the k loop of those five, and of the dx kernels of the half backward units, is
+// nnc_cbmfma.hpp.
 #pragma once
 #include "nnc_common.hpp"
 #include <type_traits>

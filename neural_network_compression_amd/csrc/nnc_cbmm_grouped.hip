@@ -5,8 +5,8 @@
 // those of nnc_cbmm_f32 / nnc_cbmm_h16.  The kernels are the ungrouped ones with one addition: a workgroup that walks from one group's
 // rows into the next changes its LDS table.  They are kernels of their own and not instantiations of a body shared with the
 // ungrouped ones: called through a device function, k_cbmm_stream compiles to another instruction stream.  The tiled one is, like
-// k_cbmm_tiled, the tile skeleton of nnc_cbtile.hpp around its decode; the MFMA one is, like k_cbmm_mfma, the tile of nnc_cbmfma.hpp
-// around its table (cb_fill, cb_refill where a step opens a group), its label load and its lookup.
+// k_cbmm_tiled, the tile skeleton of nnc_cbtile.hpp around its decode; the MFMA one is, like k_cbmm_mfma, the tile and the k loop
+// of nnc_cbmfma.hpp around its table (cb_fill, cb_refill where a step opens a group), its label load and its lookup.
 //   k_cbmm_stream_grouped  m <= 16: the split is walked group by group, the four waves share each stretch and the table.
 //   k_cbmm_tiled_grouped   m > 16, float32 x: two small tables in LDS, a TB_K step may lie across a boundary.
 //   k_cbmm_mfma_grouped    m > 16, bf16 / fp16 x: a k step of HM_BK never lies across a boundary (group_rows is a multiple of 32).
@@ -197,9 +197,10 @@ __global__ __launch_bounds__(256) void k_cbmm_tiled_grouped(const float *__restr
 
 // ------------------------------------------------------------------ MFMA tile: m > 16, bf16 / fp16 x
 // k_cbmm_mfma (nnc_cbmm_h16.hip) with uint8 labels and centers[groups][k]: the same grid and the same tile (nnc_cbmfma.hpp: images,
-// MFMA order, epilogue); its own are the group walk, the label load and the lookup.  Splits start on
+// k loop, epilogue); its own are the group walk, the label load and the lookup.  Splits start on
 // whole k steps of HM_BK = 32 and group_rows is a multiple of 32, so a step lies in one group.  A step that opens a group rewrites
-// the first k table entries ahead of its first barrier: the lookups of the step before ended at that step's second barrier.
+// the first k table entries ahead of its first barrier (hm_accumulate's `open`): the lookups of the step before ended at that
+// step's second barrier.
 template <typename XT, bool XVEC>
 __global__ __launch_bounds__(HM_THREADS) void k_cbmm_mfma_grouped(const XT *__restrict__ x, long long m, long long kdim, const uint8_t *__restrict__ labels,
                                                                   long long ncols, const float *__restrict__ centers, int k, int entries, int cshift,
@@ -208,48 +209,32 @@ __global__ __launch_bounds__(HM_THREADS) void k_cbmm_mfma_grouped(const XT *__re
 {
     using LT = uint8_t;
     extern __shared__ __attribute__((aligned(16))) float hm_smem[];
-    float *cb = hm_smem;                                // entries << cshift
-    float *stage = cb + (entries << cshift);            // entries
-    XT *xs = reinterpret_cast<XT *>(hm_smem + hm_table_words(entries, cshift));   // [HM_BM][HM_LD]: x tile, row-major in k
-    XT *ws = xs + HM_BM * HM_LD;                        // [HM_BN][HM_LD]: W tile, column-major (k contiguous)
+    const HmLds<XT> L = hm_lds<XT>(hm_smem, entries, cshift);
     long long group = (long long)blockIdx.y * rows_per_split / group_rows;
-    cb_fill<XT>(cb, stage, centers + group * k, k, entries, cshift);
+    cb_fill<XT>(L.cb, L.stage, centers + group * k, k, entries, cshift);
 
     const HmTile T = hm_tile(col_tiles, rows_per_split, kdim);
     const long long gc = T.n0 + T.wc;
     const bool col_ok = gc < ncols;
+    const long long k_end = col_ok ? T.k_hi : T.k_lo;   // the end of the thread's label rows: none in a column past ncols
     uint32_t lab[16];
-    uint4 xf[2];
 
-    auto load = [&](long long kb) {
+    auto load_w = [&](long long kb) {
 #pragma unroll
         for (int j = 0; j < 16; ++j) {
             const long long gk = kb + T.wk0 + j;
-            lab[j] = (col_ok && gk < T.k_hi) ? (uint32_t)labels[gk * ncols + gc] : 0u;
+            lab[j] = gk < k_end ? (uint32_t)labels[gk * ncols + gc] : 0u;
         }
-#pragma unroll
-        for (int i = 0; i < 2; ++i) xf[i] = hm_load_x<XT, XVEC>(x, m, kdim, T.m0, kb, T.k_hi, T.t + i * HM_THREADS);
     };
-    auto store = [&](long long kb) {
-        float w[16];
-#pragma unroll
-        for (int j = 0; j < 16; ++j) w[j] = (col_ok && kb + T.wk0 + j < T.k_hi) ? cb[CbTable<LT>::index(lab[j], k, cshift, T.lane)] : 0.0f;
-        hm_store_w(ws, T.wc, T.wk0, w);
-#pragma unroll
-        for (int i = 0; i < 2; ++i) hm_store_x(xs, T.t + i * HM_THREADS, xf[i]);
+    auto store_w = [&](long long kb) {
+        hm_lookup_w(L.ws, L.cb, T, col_ok, kb, lab, [&](uint32_t l) { return CbTable<LT>::index(l, k, cshift, T.lane); });
+    };
+    auto open = [&](long long kb) {                     // this step opens a group
+        if (kb >= (group + 1) * group_rows) cb_refill<XT>(L.cb, centers + ++group * k, k, cshift);
     };
 
     typename HFrag<XT>::C acc[2][2];
-    hm_clear<XT>(acc);
-    load(T.k_lo);
-    for (long long kb = T.k_lo; kb < T.k_hi; kb += HM_BK) {
-        if (kb >= (group + 1) * group_rows) cb_refill<XT>(cb, centers + ++group * k, k, cshift);   // this step opens a group
-        __syncthreads();   // the table is filled (first step); the images of the step before have been read
-        store(kb);
-        __syncthreads();
-        if (kb + HM_BK < T.k_hi) load(kb + HM_BK);
-        hm_step(xs, ws, T.wm, T.wn, T.fr, T.fh, acc);
-    }
+    hm_accumulate<XT, XVEC>(x, m, kdim, T, L.xs, L.ws, acc, load_w, store_w, HmNothing(), open);
     hm_store_y<XT>(acc, T.n0, T.m0, T.wm, T.wn, T.lane, m, ncols, bias, relu, direct, out_);
 }
 

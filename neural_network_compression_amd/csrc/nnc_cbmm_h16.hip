@@ -12,9 +12,10 @@
 //                      or element by element.  A lane's A / B fragment is then one 16-byte LDS read.  The labels and x of the next
 //                      step are loaded into registers before the MFMAs of this one.  Everything past kdim (or past the split), past
 //                      m and past ncols is zero in both images, never memory: a NaN there would reach valid outputs as NaN * 0.
-//                      The tile itself (coordinates, x fragments, both image stores, the MFMA step, the C / D epilogue) is
-//                      nnc_cbmfma.hpp's, shared with the two group-wise units; the kernel keeps its table, the label load and the
-//                      lookup, the barriers and the order of a step.
+//                      The tile itself (LDS carve-up, coordinates, x fragments, both image stores, the lookup into the W image, the
+//                      MFMA step, the C / D epilogue) is nnc_cbmfma.hpp's, shared with the other four forward units and the dx
+//                      kernels; the kernel keeps its table, the label load, the lookup and, alone among them, its own copy of
+//                      the k loop (hm_accumulate's barriers and order, written out).
 //   k_cbmm_reduce      the split-K partials (float32) in split order, + bias, ReLU, rounded once to the output type.
 #include "nnc_cbmfma.hpp"
 
@@ -27,11 +28,8 @@ __global__ __launch_bounds__(HM_THREADS) void k_cbmm_mfma(const XT *__restrict__
                                                           int direct, void *__restrict__ out_)
 {
     extern __shared__ __attribute__((aligned(16))) float hm_smem[];
-    float *cb = hm_smem;                                // entries << cshift
-    float *stage = cb + (entries << cshift);            // entries
-    XT *xs = reinterpret_cast<XT *>(hm_smem + hm_table_words(entries, cshift));   // [HM_BM][HM_LD]: x tile, row-major in k
-    XT *ws = xs + HM_BM * HM_LD;                        // [HM_BN][HM_LD]: W tile, column-major (k contiguous)
-    cb_fill<XT>(cb, stage, centers, k, entries, cshift);
+    const HmLds<XT> L = hm_lds<XT>(hm_smem, entries, cshift);
+    cb_fill<XT>(L.cb, L.stage, centers, k, entries, cshift);
 
     const HmTile T = hm_tile(col_tiles, rows_per_split, kdim);
     const long long gc = T.n0 + T.wc;
@@ -49,14 +47,13 @@ __global__ __launch_bounds__(HM_THREADS) void k_cbmm_mfma(const XT *__restrict__
         for (int i = 0; i < 2; ++i) xf[i] = hm_load_x<XT, XVEC>(x, m, kdim, T.m0, kb, T.k_hi, T.t + i * HM_THREADS);
     };
     auto store = [&](long long kb) {
-        float w[16];
+        hm_lookup_w(L.ws, L.cb, T, col_ok, kb, lab, [&](uint32_t l) { return CbTable<LT>::index(l, k, cshift, T.lane); });
 #pragma unroll
-        for (int j = 0; j < 16; ++j) w[j] = (col_ok && kb + T.wk0 + j < T.k_hi) ? cb[CbTable<LT>::index(lab[j], k, cshift, T.lane)] : 0.0f;
-        hm_store_w(ws, T.wc, T.wk0, w);
-#pragma unroll
-        for (int i = 0; i < 2; ++i) hm_store_x(xs, T.t + i * HM_THREADS, xf[i]);
+        for (int i = 0; i < 2; ++i) hm_store_x(L.xs, T.t + i * HM_THREADS, xf[i]);
     };
 
+    // hm_accumulate's loop, written out: through the shared loop this kernel compiles to a slower instruction stream (DESIGN.md
+    // section 31)
     typename HFrag<XT>::C acc[2][2];
     hm_clear<XT>(acc);
     load(T.k_lo);
@@ -65,7 +62,7 @@ __global__ __launch_bounds__(HM_THREADS) void k_cbmm_mfma(const XT *__restrict__
         store(kb);
         __syncthreads();
         if (kb + HM_BK < T.k_hi) load(kb + HM_BK);
-        hm_step(xs, ws, T.wm, T.wn, T.fr, T.fh, acc);
+        hm_step(L.xs, L.ws, T.wm, T.wn, T.fr, T.fh, acc);
     }
     hm_store_y<XT>(acc, T.n0, T.m0, T.wm, T.wn, T.lane, m, ncols, bias, relu, direct, out_);
 }

@@ -214,8 +214,8 @@ __global__ __launch_bounds__(256) void k_cbpk_tiled_grouped(const float *__restr
 }
 
 // ------------------------------------------------------------------ MFMA tile: m > 16, bf16 / fp16 x
-// k_cbmm_mfma_grouped (nnc_cbmm_grouped.hip) with the label of (gk, gc) taken from the packed row: the same grid and the same tile
-// (nnc_cbmfma.hpp), the per-bank table of 2^BITS entries (the centres rounded to XT, zeros from k on).  Thread t owns column wc of
+// k_cbmm_mfma_grouped (nnc_cbmm_grouped.hip) with the label of (gk, gc) taken from the packed row: the same grid, the same tile and
+// k loop (nnc_cbmfma.hpp, the refill as hm_accumulate's `open`), the per-bank table of 2^BITS entries (the centres rounded to XT, zeros from k on).  Thread t owns column wc of
 // the tile and 16 rows of the k step: 16 byte loads, the threads of neighbouring columns reading the same byte.  Splits start on
 // whole k steps of HM_BK = 32 and group_rows is a multiple of 32, so a step lies in one group; a step that opens a group rewrites
 // the first k table entries ahead of its first barrier: the lookups of the step before ended at that step's second barrier.
@@ -229,50 +229,34 @@ __global__ __launch_bounds__(HM_THREADS) void k_cbpk_mfma_grouped(const XT *__re
     constexpr int ENTRIES = 1 << BITS;
     constexpr uint32_t MASK = (1u << BITS) - 1;
     extern __shared__ __attribute__((aligned(16))) float hm_smem[];
-    float *cb = hm_smem;                                // [ENTRIES][PK_COPIES]
-    float *stage = cb + ENTRIES * PK_COPIES;            // ENTRIES
-    XT *xs = reinterpret_cast<XT *>(hm_smem + hm_table_words(ENTRIES, PK_CSHIFT));   // [HM_BM][HM_LD]: x tile, row-major in k
-    XT *ws = xs + HM_BM * HM_LD;                        // [HM_BN][HM_LD]: W tile, column-major (k contiguous)
+    const HmLds<XT> L = hm_lds<XT>(hm_smem, ENTRIES, PK_CSHIFT);   // the table: [ENTRIES][PK_COPIES]
     long long group = (long long)blockIdx.y * rows_per_split / group_rows;
-    cb_fill<XT>(cb, stage, centers + group * k, k, ENTRIES, PK_CSHIFT);
+    cb_fill<XT>(L.cb, L.stage, centers + group * k, k, ENTRIES, PK_CSHIFT);
 
     const HmTile T = hm_tile(col_tiles, rows_per_split, kdim);
     const long long gc = T.n0 + T.wc;
     const bool col_ok = gc < ncols;                     // then byte gc * BITS / 8 lies inside the row
     const long long cbyte = col_ok ? gc * BITS / 8 : 0;
     const int cshift = (int)(gc * BITS % 8);
+    const long long k_end = col_ok ? T.k_hi : T.k_lo;   // the end of the thread's label rows: none in a column past ncols
     uint32_t lab[16];
-    uint4 xf[2];
 
-    auto load = [&](long long kb) {
+    auto load_w = [&](long long kb) {
 #pragma unroll
         for (int j = 0; j < 16; ++j) {
             const long long gk = kb + T.wk0 + j;
-            lab[j] = (col_ok && gk < T.k_hi) ? ((uint32_t)packed[gk * row_bytes + cbyte] >> cshift) & MASK : 0u;
+            lab[j] = gk < k_end ? ((uint32_t)packed[gk * row_bytes + cbyte] >> cshift) & MASK : 0u;
         }
-#pragma unroll
-        for (int i = 0; i < 2; ++i) xf[i] = hm_load_x<XT, XVEC>(x, m, kdim, T.m0, kb, T.k_hi, T.t + i * HM_THREADS);
     };
-    auto store = [&](long long kb) {
-        float w[16];
-#pragma unroll
-        for (int j = 0; j < 16; ++j) w[j] = (col_ok && kb + T.wk0 + j < T.k_hi) ? cb[(lab[j] << PK_CSHIFT) | (T.lane & (PK_COPIES - 1))] : 0.0f;
-        hm_store_w(ws, T.wc, T.wk0, w);
-#pragma unroll
-        for (int i = 0; i < 2; ++i) hm_store_x(xs, T.t + i * HM_THREADS, xf[i]);
+    auto store_w = [&](long long kb) {
+        hm_lookup_w(L.ws, L.cb, T, col_ok, kb, lab, [&](uint32_t l) { return (l << PK_CSHIFT) | (T.lane & (PK_COPIES - 1)); });
+    };
+    auto open = [&](long long kb) {                     // this step opens a group
+        if (kb >= (group + 1) * group_rows) cb_refill<XT>(L.cb, centers + ++group * k, k, PK_CSHIFT);
     };
 
     typename HFrag<XT>::C acc[2][2];
-    hm_clear<XT>(acc);
-    load(T.k_lo);
-    for (long long kb = T.k_lo; kb < T.k_hi; kb += HM_BK) {
-        if (kb >= (group + 1) * group_rows) cb_refill<XT>(cb, centers + ++group * k, k, PK_CSHIFT);   // this step opens a group
-        __syncthreads();   // the table is filled (first step); the images of the step before have been read
-        store(kb);
-        __syncthreads();
-        if (kb + HM_BK < T.k_hi) load(kb + HM_BK);
-        hm_step(xs, ws, T.wm, T.wn, T.fr, T.fh, acc);
-    }
+    hm_accumulate<XT, XVEC>(x, m, kdim, T, L.xs, L.ws, acc, load_w, store_w, HmNothing(), open);
     hm_store_y<XT>(acc, T.n0, T.m0, T.wm, T.wn, T.lane, m, ncols, bias, relu, direct, out_);
 }
 

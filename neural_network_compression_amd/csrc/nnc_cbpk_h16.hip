@@ -7,7 +7,7 @@
 //   m <= 16   k_cbpkdx_stream<XT> / k_cbpkdc_stream<XT> of nnc_cbpkgrad.hpp: section 15's stream plans and kernels with g and x
 //             widened as they are loaded and, for dx, the table of the rounded centres.  Bit for bit the float32 entry points on
 //             the widened inputs.
-//   k_cbpkdx_mfma  m > 16.  k_cbdx_mfma's tile, main loop (dxm_accumulate, nnc_cbdxm.hpp), tiles and splits (nnc_cbh16plan.hpp); g is
+//   k_cbpkdx_mfma  m > 16.  k_cbdx_mfma's tile, main loop (hm_accumulate, nnc_cbmfma.hpp), tiles and splits (nnc_cbh16plan.hpp); g is
 //             the A operand (hm_load_x / hm_store_x).
 //             The B operand W^T: thread t owns index row n0 + (t mod 128) and the 16 consecutive o of its half of the k step, which
 //             are 8 bytes (4 bits) or 4 bytes (2 bits) of the packed row: naturally aligned (a row starts on 16 bytes, a split on
@@ -19,7 +19,6 @@
 //             its field, shifts and masks.  Every lane adds into its own copy of the K <= 16 bins (64 copies, at most 8 KiB).
 // No load leaves the packed buffer: rows past kdim and columns past the split (dx) or past ncols (dc) load nothing.  Everything past
 // m, kdim, ncols and the end of a split is zero in the images, never memory.  No float atomics; no host read.
-#include "nnc_cbdxm.hpp"
 #include "nnc_cbgrad_h16.hpp"
 #include "nnc_cbh16plan.hpp"
 #include "nnc_cbpkgrad.hpp"
@@ -72,7 +71,7 @@ __global__ __launch_bounds__(HM_THREADS) void k_cbpkdx_mfma(const XT *__restrict
     };
 
     typename HFrag<XT>::C acc[2][2];
-    dxm_accumulate<XT, XVEC>(g, m, ncols, T, gs, ws, acc, load_w, store_w);
+    hm_accumulate<XT, XVEC>(g, m, ncols, T, gs, ws, acc, load_w, store_w);
     hm_store_y<XT>(acc, T.n0, T.m0, T.wm, T.wn, T.lane, m, kdim, nullptr, 0, direct, out_);
 }
 

@@ -5,7 +5,7 @@
 //
 // The plans are the ungrouped packed half ones (section 15's stream plans; nnc_cbh16plan.hpp's tiles and splits at m > 16) plus the
 // group fields, as section 20 took the float32 ones: the path, the tiles, the splits, the order of every sum and S are those of
-// nnc_cbpk_dx_h16 / nnc_cbpk_dc_h16.  The two main loops are the ungrouped kernels' (dxm_accumulate, dcm_accumulate), the pick of a
+// nnc_cbpk_dx_h16 / nnc_cbpk_dc_h16.  The two main loops are the ungrouped kernels' (hm_accumulate, dcm_accumulate), the pick of a
 // row's table or set tile_group_of (nnc_cbgrad_grouped.hpp).
 //   m <= 16   k_cbpkdx_stream_grouped<XT> / k_cbpkdc_stream_grouped<XT> of nnc_cbpkgrad_grouped.hpp: section 20's kernels with g and
 //             x widened as they are loaded and, for dx, the per-wave tables of the rounded centres.
@@ -15,7 +15,6 @@
 //   k_cbpkdc_mfma_grouped  m > 16.  dcm_accumulate unchanged, then k_cbpkdc_mfma's epilogue with one set of [K][64] bins per group of
 //             the tile: the 32 rows of an accumulator lie in one group, so the set is a scalar; one cbdc_flush per set.
 // No load leaves the packed buffer; everything past m, kdim, ncols and the end of a split is zero in the images, never memory.
-#include "nnc_cbdxm.hpp"
 #include "nnc_cbgrad_grouped.hpp"
 #include "nnc_cbgrad_h16.hpp"
 #include "nnc_cbh16plan.hpp"
@@ -80,7 +79,7 @@ __global__ __launch_bounds__(HM_THREADS) void k_cbpkdx_mfma_grouped(const XT *__
     };
 
     typename HFrag<XT>::C acc[2][2];
-    dxm_accumulate<XT, XVEC>(g, m, ncols, T, gs, ws, acc, load_w, store_w);
+    hm_accumulate<XT, XVEC>(g, m, ncols, T, gs, ws, acc, load_w, store_w);
     hm_store_y<XT>(acc, T.n0, T.m0, T.wm, T.wn, T.lane, m, kdim, nullptr, 0, direct, out_);
 }
 

@@ -2,8 +2,9 @@
 // layout and the limits of the packed form, the count and rank of a stored symbol, the d table, the masked FMA step of the tiled
 // kernels and the row-sum launch.  The plan (sp_plan), the stream kernel k_cbsp_stream and the split-K combine k_cbsp_reduce live
 // here too, templated on the type of x: nnc_cbsp.hip instantiates them for float32, nnc_cbsp_h16.hip for bf16 / fp16 activations.
+// SpTileDecode is the decode of the two forward MFMA kernels on half x (nnc_cbsp_h16.hip, nnc_cbsp_grouped_h16.hip).
 #pragma once
-#include "nnc_cbmm.hpp"
+#include "nnc_cbmfma.hpp"
 
 // ------------------------------------------------------------------ the layout (host and device)
 struct SpLayout {
@@ -45,6 +46,58 @@ __device__ __forceinline__ uint32_t sp_rank(uint64_t word)
 {
     return __builtin_amdgcn_mbcnt_hi((uint32_t)(word >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)word, 0u));
 }
+
+// ------------------------------------------------------------------ the decode of the MFMA tile (bf16 / fp16 x, m > 16)
+// What k_cbsp_mfma (nnc_cbsp_h16.hip) and k_cbspg_mfma (nnc_cbsp_grouped_h16.hip) put in front of the tile of nnc_cbmfma.hpp: the
+// labels of a thread's 16 k rows of its column, from the form.  A wave's 64 lanes own one 64-column segment (n0 is a multiple of
+// 128, wc = t & 127) and the same 16 rows of a step (wk0 = 16 (t >> 7)), so the bitmap word and the count of a row are uniform over
+// the wave: load_words(kb) has lane j < 16 load those of row kb + wk0 + j, decode() broadcasts them by v_readlane, and a lane's symbol
+// sits at count + v_mbcnt(word).  The kernels call load_words two k steps ahead of the MFMAs and decode one (hm_accumulate's `ahead`
+// and `load_w`).  No load leaves the packed buffer: rows past k_hi load no word and segments past segs nothing, so their words are
+// empty, and a symbol is loaded only where its bit is set and pos < nnz.  No readlane sits inside a lane-dependent branch.
+template <typename LT> struct SpTileDecode {
+    const uint64_t *__restrict__ bitmap;
+    const uint32_t *__restrict__ lo, *__restrict__ hi;
+    const LT *__restrict__ sym;
+    long long nnz, segs, seg, k_hi;   // seg: the wave's segment
+    int wk0, lane;                    // wk0: the wave's first k row of a step
+    bool seg_ok;
+    uint32_t wlo = 0, whi = 0, clo = 0, chi = 0;   // lane j < 16: the word and the count of row kb + wk0 + j
+
+    __device__ __forceinline__ SpTileDecode(const uint64_t *bitmap_, const uint32_t *lo_, const uint32_t *hi_, const LT *sym_, long long nnz_, long long segs_,
+                                            const HmTile &T)
+        : bitmap(bitmap_), lo(lo_), hi(hi_), sym(sym_), nnz(nnz_), segs(segs_), seg((T.n0 >> 6) + __builtin_amdgcn_readfirstlane(T.wc >> 6)), k_hi(T.k_hi),
+          wk0(__builtin_amdgcn_readfirstlane(T.wk0)), lane(T.lane), seg_ok(seg < segs_)
+    {
+    }
+
+    __device__ __forceinline__ void load_words(long long kb)
+    {
+        const long long gk = kb + wk0 + lane;
+        uint64_t w = 0;
+        long long c = 0;
+        if (lane < 16 && seg_ok && gk < k_hi) {         // rows past k_hi and segments past segs load nothing
+            const long long gi = gk * segs;
+            w = bitmap[gi + seg];
+            c = sp_count(lo[gi + seg], lo[gi], hi[gk]);
+        }
+        wlo = (uint32_t)w, whi = (uint32_t)(w >> 32), clo = (uint32_t)c, chi = (uint32_t)((uint64_t)c >> 32);
+    }
+
+    // from the words the last load_words brought; z (uniform over the wave) is the label of a skipped position
+    __device__ __forceinline__ void decode(uint32_t z, uint32_t (&lab)[16]) const
+    {
+#pragma unroll
+        for (int j = 0; j < 16; ++j) {
+            const uint64_t word = ((uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)whi, j) << 32) | (uint32_t)__builtin_amdgcn_readlane((int)wlo, j);
+            const long long cnt = (long long)(((uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)chi, j) << 32) |
+                                              (uint32_t)__builtin_amdgcn_readlane((int)clo, j));
+            const long long pos = cnt + sp_rank(word);
+            lab[j] = z;                                 // a skipped position (every position of an empty word: past k_hi, past segs)
+            if (((word >> lane) & 1) && pos < nnz) lab[j] = (uint32_t)sym[pos];
+        }
+    }
+};
 
 // ------------------------------------------------------------------ the d table
 // stage[j] = c[j] - c_z (j < k), -c_z past k; then `1 << cshift` copies of each entry as in k_cbmm_stream

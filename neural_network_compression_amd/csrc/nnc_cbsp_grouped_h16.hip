@@ -7,23 +7,22 @@
 //            nnc_cbsp_grouped_plan's stream plan (sp_plan).  x is read as XT and widened, c_{z_g} is rn(c) widened, the d table is
 //            rn(c_g[s]) - rn(c_{z_g}): section 28's float32 arithmetic on half the x bytes.  A skipped weight stays absent when
 //            rn(c_{z_g}) == 0.
-//   m > 16:  k_cbspg_mfma, the combination of k_cbsp_mfma's decode (nnc_cbsp_h16.hip: a wave owns one 64-column segment, 16 lanes
-//            load a row's bitmap word and count, v_readlane broadcasts them, a lane's symbol sits at count + v_mbcnt(word)) and
+//   m > 16:  k_cbspg_mfma, the combination of k_cbsp_mfma's decode (SpTileDecode, nnc_cbsp.hpp: a wave owns one 64-column segment, 16
+//            lanes load a row's bitmap word and count, v_readlane broadcasts them, a lane's symbol sits at count + v_mbcnt(word)) and
 //            k_cbmm_mfma_grouped's table walk (nnc_cbmm_grouped.hip: a k step of HM_BK lies in one group, the step that opens a group
-//            refills the table ahead of its first barrier), on the tile of nnc_cbmfma.hpp under the grouped byte form's half plan
-//            (cb_plan).  Its own: the skipped label changes with the group.  It is the z of the step being loaded (the next step's
+//            refills the table ahead of its first barrier), on the tile and the k loop of nnc_cbmfma.hpp under the grouped byte
+//            form's half plan (cb_plan).  Its own: the skipped label changes with the group.  It is the z of the step being loaded (the next step's
 //            group when the loop loads ahead), loaded with that step's words, made uniform over the wave by readfirstlane when the
 //            step is decoded, and looked up like any stored label after the refill: W_h holds rn(c_{z_g}) at a
 //            skipped position (0 for z_g >= k), no rank-1 term, no row sums.  k_cbmm_reduce combines the splits: y is nnc_cbmm_grouped's
 //            on the unpacked labels bit for bit.
-#include "nnc_cbmfma.hpp"
 #include "nnc_cbsp_grouped.hpp"
 
 // grid (col_tiles * row_tiles, splits), HM_THREADS threads; out, direct and rows_per_split as k_cbmm_mfma_grouped.  What steers the
 // walk (the k steps, the two group counters, z) comes from blockIdx and the arguments or is made uniform by readfirstlane; every
-// wave reaches every barrier.  No load leaves its buffer: rows past k_hi load no word and segments past segs nothing (load_words),
-// a symbol is loaded only where its bit is set and pos < nnz, and both group counters follow a k step below k_hi <= kdim, so they
-// stay at or below (kdim - 1) / group_rows = G - 1.  No readlane / readfirstlane sits inside a lane-dependent branch.
+// wave reaches every barrier.  No load leaves its buffer: SpTileDecode argues it for the form, and both group counters follow a k
+// step below k_hi <= kdim, so they stay at or below (kdim - 1) / group_rows = G - 1.  No readlane / readfirstlane sits inside a
+// lane-dependent branch.
 template <typename XT, bool XVEC>
 __global__ __launch_bounds__(HM_THREADS) void k_cbspg_mfma(const XT *__restrict__ x, long long m, long long kdim, const uint64_t *__restrict__ bitmap,
                                                            const uint32_t *__restrict__ lo, const uint32_t *__restrict__ hi, const uint8_t *__restrict__ sym,
@@ -34,79 +33,36 @@ __global__ __launch_bounds__(HM_THREADS) void k_cbspg_mfma(const XT *__restrict_
 {
     using LT = uint8_t;
     extern __shared__ __attribute__((aligned(16))) float hm_smem[];
-    float *cb = hm_smem;                                // entries << cshift
-    float *stage = cb + (entries << cshift);            // entries
-    XT *xs = reinterpret_cast<XT *>(hm_smem + hm_table_words(entries, cshift));   // [HM_BM][HM_LD]: x tile, row-major in k
-    XT *ws = xs + HM_BM * HM_LD;                        // [HM_BN][HM_LD]: W tile, column-major (k contiguous)
+    const HmLds<XT> L = hm_lds<XT>(hm_smem, entries, cshift);
     long long group = (long long)blockIdx.y * rows_per_split / group_rows;   // the group whose table is in LDS
-    cb_fill<XT>(cb, stage, centers + group * k, k, entries, cshift);
+    cb_fill<XT>(L.cb, L.stage, centers + group * k, k, entries, cshift);
 
     const HmTile T = hm_tile(col_tiles, rows_per_split, kdim);
     const bool col_ok = T.n0 + T.wc < ncols;
-    // the wave's segment and its first k row of a step: uniform over the wave (wc = t & 127, wk0 = 16 (t >> 7))
-    const long long seg = (T.n0 >> 6) + __builtin_amdgcn_readfirstlane(T.wc >> 6);
-    const int wk0 = __builtin_amdgcn_readfirstlane(T.wk0);
-    const bool seg_ok = seg < segs;
+    SpTileDecode<LT> D(bitmap, lo, hi, sym, nnz, segs, T);
     long long zgroup = group;                           // the group of the step whose words were loaded last, two steps ahead of `group`
-    uint32_t zraw = 0, z = 0;                           // its z as loaded, and the z of the step `load` decodes (uniform)
-    uint32_t wlo = 0, whi = 0, clo = 0, chi = 0;        // lane j < 16: the word and the count of row kb + wk0 + j
+    uint32_t zraw = 0;                                  // its z as loaded
     uint32_t lab[16];
-    uint4 xf[2];
 
     auto load_words = [&](long long kb) {
-        const long long gk = kb + wk0 + T.lane;
-        uint64_t w = 0;
-        long long c = 0;
-        if (T.lane < 16 && seg_ok && gk < T.k_hi) {     // rows past k_hi and segments past segs load nothing
-            const long long gi = gk * segs;
-            w = bitmap[gi + seg];
-            c = sp_count(lo[gi + seg], lo[gi], hi[gk]);
-        }
-        wlo = (uint32_t)w, whi = (uint32_t)(w >> 32), clo = (uint32_t)c, chi = (uint32_t)((uint64_t)c >> 32);
+        D.load_words(kb);
         if (kb < T.k_hi) {                              // uniform; the step's group is at most G - 1, and its z comes with its words
             if (kb >= (zgroup + 1) * group_rows) ++zgroup;
             zraw = zsym[zgroup];
         }
     };
-    auto load = [&](long long kb) {                     // kb < k_hi; from the words and the z load_words(kb) brought
-        z = (uint32_t)__builtin_amdgcn_readfirstlane((int)zraw);
-#pragma unroll
-        for (int j = 0; j < 16; ++j) {
-            const uint64_t word = ((uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)whi, j) << 32) | (uint32_t)__builtin_amdgcn_readlane((int)wlo, j);
-            const long long cnt = (long long)(((uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)chi, j) << 32) |
-                                              (uint32_t)__builtin_amdgcn_readlane((int)clo, j));
-            const long long pos = cnt + sp_rank(word);
-            lab[j] = z;                                 // a skipped position (every position of an empty word: past k_hi, past segs)
-            if (((word >> T.lane) & 1) && pos < nnz) lab[j] = (uint32_t)sym[pos];
-        }
-#pragma unroll
-        for (int i = 0; i < 2; ++i) xf[i] = hm_load_x<XT, XVEC>(x, m, kdim, T.m0, kb, T.k_hi, T.t + i * HM_THREADS);
+    // a step kb < k_hi, from the words and the z load_words(kb) brought: the z made uniform here, outside every lane-dependent branch
+    auto load_w = [&](long long) { D.decode((uint32_t)__builtin_amdgcn_readfirstlane((int)zraw), lab); };
+    auto store_w = [&](long long kb) {                  // the labels of this step, its group's z among them, in its group's table
+        hm_lookup_w(L.ws, L.cb, T, col_ok, kb, lab, [&](uint32_t l) { return CbTable<LT>::index(l, k, cshift, T.lane); });
     };
-    auto store = [&](long long kb) {
-        float w[16];
-#pragma unroll
-        for (int j = 0; j < 16; ++j) w[j] = (col_ok && kb + T.wk0 + j < T.k_hi) ? cb[CbTable<LT>::index(lab[j], k, cshift, T.lane)] : 0.0f;
-        hm_store_w(ws, T.wc, T.wk0, w);
-#pragma unroll
-        for (int i = 0; i < 2; ++i) hm_store_x(xs, T.t + i * HM_THREADS, xf[i]);
+    auto open = [&](long long kb) {                     // this step opens a group
+        if (kb >= (group + 1) * group_rows) cb_refill<XT>(L.cb, centers + ++group * k, k, cshift);
     };
 
     typename HFrag<XT>::C acc[2][2];
-    hm_clear<XT>(acc);
     load_words(T.k_lo);
-    load(T.k_lo);
-    load_words(T.k_lo + HM_BK);
-    for (long long kb = T.k_lo; kb < T.k_hi; kb += HM_BK) {
-        if (kb >= (group + 1) * group_rows) cb_refill<XT>(cb, centers + ++group * k, k, cshift);   // this step opens a group
-        __syncthreads();   // the table is filled (first step, or refilled); the images of the step before have been read
-        store(kb);         // the labels of this step, its group's z among them, in its group's table
-        __syncthreads();
-        if (kb + HM_BK < T.k_hi) {
-            load(kb + HM_BK);
-            load_words(kb + 2 * HM_BK);
-        }
-        hm_step(xs, ws, T.wm, T.wn, T.fr, T.fh, acc);
-    }
+    hm_accumulate<XT, XVEC>(x, m, kdim, T, L.xs, L.ws, acc, load_w, store_w, [&](long long kb) { load_words(kb + HM_BK); }, open);
     hm_store_y<XT>(acc, T.n0, T.m0, T.wm, T.wn, T.lane, m, ncols, bias, relu, direct, out_);
 }
 

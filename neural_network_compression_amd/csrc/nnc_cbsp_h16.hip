@@ -5,15 +5,14 @@
 //   k_cbsp_stream<XT>  m <= 16: nnc_cbsp.hpp's stream kernel with x read as XT and widened and the d table built from the rounded
 //                      centres widened: the float32 path's fmaf chain (and its plan, sp_plan) on half the x bytes.  A skipped weight
 //                      stays absent when rn(c_z) == 0.  k_cbsp_reduce<XT, YT> combines its splits.
-//   k_cbsp_mfma        m > 16: k_cbmm_mfma's tile (nnc_cbmfma.hpp), table (cb_fill<XT>, the per-bank copies) and plan (cb_plan's half
-//                      plan), with the label of a thread's 16 k rows of its column decoded from the form.  A wave's 64 lanes own one
-//                      64-column segment (n0 is a multiple of 128), so the bitmap word and the count of a row are wave-uniform: 16
-//                      lanes load one row each and v_readlane broadcasts them; a lane's symbol sits at count + v_mbcnt(word).  A
-//                      skipped position takes the table entry of zero_symbol: W_h holds c_z there, no rank-1 term, no row sums.  The
-//                      words and counts run two k steps ahead of the MFMAs, the symbols and x one.  Everything past kdim (or past
-//                      the split), past m and past ncols is zero in both images, never memory; no load leaves the packed buffer.
+//   k_cbsp_mfma        m > 16: k_cbmm_mfma's tile and k loop (nnc_cbmfma.hpp), table (cb_fill<XT>, the per-bank copies) and plan
+//                      (cb_plan's half plan), with the label of a thread's 16 k rows of its column decoded from the form by
+//                      SpTileDecode (nnc_cbsp.hpp): a wave owns one 64-column segment, 16 lanes load one row's word and count each,
+//                      v_readlane broadcasts them, a lane's symbol sits at count + v_mbcnt(word).  A skipped position takes the
+//                      table entry of zero_symbol: W_h holds c_z there, no rank-1 term, no row sums.  The words and counts run two
+//                      k steps ahead of the MFMAs (the loop's `ahead`), the symbols and x one.  Everything past kdim (or past the
+//                      split), past m and past ncols is zero in both images, never memory; no load leaves the packed buffer.
 //                      k_cbmm_reduce combines the splits: y is nnc_cbmm_h16's on the unpacked labels bit for bit.
-#include "nnc_cbmfma.hpp"
 #include "nnc_cbsp.hpp"
 
 // grid (col_tiles * row_tiles, splits), HM_THREADS threads; out, direct and rows_per_split as k_cbmm_mfma
@@ -25,70 +24,22 @@ __global__ __launch_bounds__(HM_THREADS) void k_cbsp_mfma(const XT *__restrict__
                                                           const float *__restrict__ bias, int relu, int direct, void *__restrict__ out_)
 {
     extern __shared__ __attribute__((aligned(16))) float hm_smem[];
-    float *cb = hm_smem;                                // entries << cshift
-    float *stage = cb + (entries << cshift);            // entries
-    XT *xs = reinterpret_cast<XT *>(hm_smem + hm_table_words(entries, cshift));   // [HM_BM][HM_LD]: x tile, row-major in k
-    XT *ws = xs + HM_BM * HM_LD;                        // [HM_BN][HM_LD]: W tile, column-major (k contiguous)
-    cb_fill<XT>(cb, stage, centers, k, entries, cshift);
+    const HmLds<XT> L = hm_lds<XT>(hm_smem, entries, cshift);
+    cb_fill<XT>(L.cb, L.stage, centers, k, entries, cshift);
 
     const HmTile T = hm_tile(col_tiles, rows_per_split, kdim);
     const bool col_ok = T.n0 + T.wc < ncols;
-    // the wave's segment and its first k row of a step: uniform over the wave (wc = t & 127, wk0 = 16 (t >> 7))
-    const long long seg = (T.n0 >> 6) + __builtin_amdgcn_readfirstlane(T.wc >> 6);
-    const int wk0 = __builtin_amdgcn_readfirstlane(T.wk0);
-    const bool seg_ok = seg < segs;
-    uint32_t wlo = 0, whi = 0, clo = 0, chi = 0;        // lane j < 16: the word and the count of row kb + wk0 + j
+    SpTileDecode<LT> D(bitmap, lo, hi, sym, nnz, segs, T);
     uint32_t lab[16];
-    uint4 xf[2];
 
-    auto load_words = [&](long long kb) {
-        const long long gk = kb + wk0 + T.lane;
-        uint64_t w = 0;
-        long long c = 0;
-        if (T.lane < 16 && seg_ok && gk < T.k_hi) {     // rows past k_hi and segments past segs load nothing
-            const long long gi = gk * segs;
-            w = bitmap[gi + seg];
-            c = sp_count(lo[gi + seg], lo[gi], hi[gk]);
-        }
-        wlo = (uint32_t)w, whi = (uint32_t)(w >> 32), clo = (uint32_t)c, chi = (uint32_t)((uint64_t)c >> 32);
-    };
-    auto load = [&](long long kb) {                     // from the words load_words(kb) brought
-#pragma unroll
-        for (int j = 0; j < 16; ++j) {
-            const uint64_t word = ((uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)whi, j) << 32) | (uint32_t)__builtin_amdgcn_readlane((int)wlo, j);
-            const long long cnt = (long long)(((uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)chi, j) << 32) |
-                                              (uint32_t)__builtin_amdgcn_readlane((int)clo, j));
-            const long long pos = cnt + sp_rank(word);
-            lab[j] = (uint32_t)z;                       // a skipped position (every position of an empty word: past k_hi, past segs)
-            if (((word >> T.lane) & 1) && pos < nnz) lab[j] = (uint32_t)sym[pos];
-        }
-#pragma unroll
-        for (int i = 0; i < 2; ++i) xf[i] = hm_load_x<XT, XVEC>(x, m, kdim, T.m0, kb, T.k_hi, T.t + i * HM_THREADS);
-    };
-    auto store = [&](long long kb) {
-        float w[16];
-#pragma unroll
-        for (int j = 0; j < 16; ++j) w[j] = (col_ok && kb + T.wk0 + j < T.k_hi) ? cb[CbTable<LT>::index(lab[j], k, cshift, T.lane)] : 0.0f;
-        hm_store_w(ws, T.wc, T.wk0, w);
-#pragma unroll
-        for (int i = 0; i < 2; ++i) hm_store_x(xs, T.t + i * HM_THREADS, xf[i]);
+    auto load_w = [&](long long) { D.decode((uint32_t)z, lab); };   // the step whose words load_words brought last
+    auto store_w = [&](long long kb) {
+        hm_lookup_w(L.ws, L.cb, T, col_ok, kb, lab, [&](uint32_t l) { return CbTable<LT>::index(l, k, cshift, T.lane); });
     };
 
     typename HFrag<XT>::C acc[2][2];
-    hm_clear<XT>(acc);
-    load_words(T.k_lo);
-    load(T.k_lo);
-    load_words(T.k_lo + HM_BK);
-    for (long long kb = T.k_lo; kb < T.k_hi; kb += HM_BK) {
-        __syncthreads();   // the table is filled (first step); the images of the step before have been read
-        store(kb);
-        __syncthreads();
-        if (kb + HM_BK < T.k_hi) {
-            load(kb + HM_BK);
-            load_words(kb + 2 * HM_BK);
-        }
-        hm_step(xs, ws, T.wm, T.wn, T.fr, T.fh, acc);
-    }
+    D.load_words(T.k_lo);
+    hm_accumulate<XT, XVEC>(x, m, kdim, T, L.xs, L.ws, acc, load_w, store_w, [&](long long kb) { D.load_words(kb + HM_BK); });
     hm_store_y<XT>(acc, T.n0, T.m0, T.wm, T.wn, T.lane, m, ncols, bias, relu, direct, out_);
 }
 

@@ -8,7 +8,7 @@
 //             (k_cbsp_rowsum<XT>) come first; the rank-1 term c_z * rs is added in float32 before the one rounding of a half dx, by
 //             the stream kernel itself where a single column block writes dx, by k_cbspdx_finish behind the split partials.  Bit
 //             for bit the float32 entry points on the widened inputs.
-//   k_cbspdx_mfma  m > 16.  k_cbdx_mfma's tile, table, main loop (dxm_accumulate, nnc_cbdxm.hpp), tiles and splits (nnc_cbh16plan.hpp);
+//   k_cbspdx_mfma  m > 16.  k_cbdx_mfma's tile, table, main loop (hm_accumulate, nnc_cbmfma.hpp), tiles and splits (nnc_cbh16plan.hpp);
 //             g is the A operand.  The B operand W^T is
 //             decoded from the form: thread t owns index row n0 + (t mod 128) and 16 consecutive o of the step, which are 16 aligned
 //             bits of one bitmap word; their stored symbols are one run of the symbol stream starting at the segment's count plus
@@ -20,7 +20,6 @@
 //             goes into the replicated LDS bins, a skipped one's into a per-lane int64 register flushed into bin z once.
 // No load leaves the packed buffer: rows past kdim load no word, columns past the split none, a symbol is loaded only below nnz.
 // Everything past m, kdim, ncols and the end of a split is zero in the images, never memory.  No float atomics; no host read.
-#include "nnc_cbdxm.hpp"
 #include "nnc_cbgrad_h16.hpp"
 #include "nnc_cbh16plan.hpp"
 #include "nnc_cbspgrad.hpp"
@@ -102,7 +101,7 @@ __global__ __launch_bounds__(HM_THREADS) void k_cbspdx_mfma(const XT *__restrict
 
     typename HFrag<XT>::C acc[2][2];
     load_words(T.k_lo);
-    dxm_accumulate<XT, XVEC>(g, m, ncols, T, gs, ws, acc, load_w, store_w, [&](long long ob) { load_words(ob + HM_BK); });
+    hm_accumulate<XT, XVEC>(g, m, ncols, T, gs, ws, acc, load_w, store_w, [&](long long ob) { load_words(ob + HM_BK); });
     hm_store_y<XT>(acc, T.n0, T.m0, T.wm, T.wn, T.lane, m, kdim, nullptr, 0, direct, out_);
 }
 
