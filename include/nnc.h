@@ -996,6 +996,10 @@ int nnc_cbsp_dc_f32(const float *x, const float *g, int64_t m, int64_t kdim, con
  * nnc_cbsp_dc_h16, their workspace queries and their plans. */
 #include "nnc_cbspgrad_h16.h"
 
+/* The backward pass of the group-wise layer from the same form (csrc/nnc_cbspgrad_grouped.hip):
+ * nnc_cbsp_grouped_dx_f32, nnc_cbsp_grouped_dc_f32, their workspace queries and their plans. */
+#include "nnc_cbspgrad_grouped.h"
+
 /* ------------------------------------------------------------------------------------
  * The backward pass of nnc_cbpk_f32 from the same 2- or 4-bit packed form, the indices never unpacked and W never decoded
  * (csrc/nnc_cbpkgrad.hip).  The form, bits and k are nnc_cbpk_f32's; g = dL/dy float32[m, ncols].

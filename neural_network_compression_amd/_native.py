@@ -75,6 +75,11 @@ CBSPDC_PLAN_FIELDS = ("path", "mt", "segs", "copies", "splits", "rps", "lds", "c
 CBSPGRAD_H16_PLAN_LEN = 12   # nnc_cbsp_dx_h16_plan / nnc_cbsp_dc_h16_plan (include/nnc_cbspgrad_h16.h): the float32 sparse fields, then the dtype
 CBSPDX_H16_PLAN_FIELDS = CBSPDX_PLAN_FIELDS + ("dtype",)
 CBSPDC_H16_PLAN_FIELDS = CBSPDC_PLAN_FIELDS + ("dtype",)
+# nnc_cbsp_grouped_dx_plan / nnc_cbsp_grouped_dc_plan (include/nnc_cbspgrad_grouped.h): the float32 sparse fields, then the groups
+CBSPDX_GROUPED_PLAN_LEN = 16
+CBSPDX_GROUPED_PLAN_FIELDS = CBSPDX_PLAN_FIELDS + ("group_rows", "groups", "rows_per_group", "max_groups_per_workgroup", "tables")
+CBSPDC_GROUPED_PLAN_LEN = 15
+CBSPDC_GROUPED_PLAN_FIELDS = CBSPDC_PLAN_FIELDS + ("group_rows", "groups", "rows_per_group", "max_groups_per_workgroup")
 CBPK_H16_PLAN_LEN = 15   # nnc_cbpk_h16_plan (include/nnc_cbpk_h16.h): the float32 packed fields, then the dtype; path is CBMM_MFMA for m > 16
 CBPK_H16_PLAN_FIELDS = CBPK_PLAN_FIELDS + ("dtype",)
 CBGRAD_GROUPED_H16_PLAN_LEN = 18   # nnc_cbmm_grouped_*_h16_plan and nnc_cbpk_grouped_*_h16_plan: the ungrouped half fields, then the groups and the tables / sets held in LDS
@@ -400,6 +405,19 @@ GROUPED_SPARSE_H16_SIGNATURES = {
                                      c_int, c_void_p, c_i64, c_void_p]),
 }
 
+# name -> (restype, argtypes); every symbol include/nnc_cbspgrad_grouped.h declares (the backward pass of the group-wise layer from the
+# bitmap-sparse form, float32 activations, again a header of its own that nnc.h includes).  Required and bound by load() as SIGNATURES are.
+GROUPED_SPARSE_GRAD_SIGNATURES = {
+    "nnc_cbsp_grouped_dx_workspace_bytes": (c_i64, [c_i64, c_i64, c_i64]),
+    "nnc_cbsp_grouped_dx_plan": (c_int, [c_i64, c_i64, c_i64, c_i32, c_i64, c_i32, ctypes.POINTER(c_i64)]),
+    "nnc_cbsp_grouped_dx_f32": (c_int, [c_void_p, c_i64, c_i64, c_void_p, c_i64, c_i64, c_void_p, c_i64, c_void_p, c_i32, c_i64, c_void_p, c_void_p, c_i64,
+                                        c_void_p]),
+    "nnc_cbsp_grouped_dc_workspace_bytes": (c_i64, [c_i64, c_i64, c_i64, c_i32, c_i64]),
+    "nnc_cbsp_grouped_dc_plan": (c_int, [c_i64, c_i64, c_i64, c_i32, c_i64, c_i32, ctypes.POINTER(c_i64)]),
+    "nnc_cbsp_grouped_dc_f32": (c_int, [c_void_p, c_void_p, c_i64, c_i64, c_void_p, c_i64, c_i64, c_void_p, c_i64, c_i32, c_i64, c_void_p, c_i32, c_void_p,
+                                        c_i64, c_void_p]),
+}
+
 # exported only by the diagnostics build (NNC_DIAG=1: libnnc_hip_diag.so, see build.py); bound when present
 DIAG_SIGNATURES = {
     "nnc_debug_set_ablation": (c_int, [c_int]),
@@ -432,7 +450,7 @@ def load():
         L = ctypes.CDLL(path)
     except OSError as e:  # pragma: no cover - depends on the machine
         raise NativeLibraryError(f"cannot load {path}: {e}; there is no CPU fallback") from e
-    for name, (res, args) in list(SIGNATURES.items()) + list(GROUPED_GRAD_SIGNATURES.items()) + list(H16_GRAD_SIGNATURES.items()) + list(GROUPED_PACKED_GRAD_SIGNATURES.items()) + list(SPARSE_H16_SIGNATURES.items()) + list(SPARSE_H16_GRAD_SIGNATURES.items()) + list(PACKED_H16_SIGNATURES.items()) + list(GROUPED_H16_GRAD_SIGNATURES.items()) + list(GROUPED_SPARSE_SIGNATURES.items()) + list(GROUPED_SPARSE_H16_SIGNATURES.items()):
+    for name, (res, args) in list(SIGNATURES.items()) + list(GROUPED_GRAD_SIGNATURES.items()) + list(H16_GRAD_SIGNATURES.items()) + list(GROUPED_PACKED_GRAD_SIGNATURES.items()) + list(SPARSE_H16_SIGNATURES.items()) + list(SPARSE_H16_GRAD_SIGNATURES.items()) + list(PACKED_H16_SIGNATURES.items()) + list(GROUPED_H16_GRAD_SIGNATURES.items()) + list(GROUPED_SPARSE_SIGNATURES.items()) + list(GROUPED_SPARSE_H16_SIGNATURES.items()) + list(GROUPED_SPARSE_GRAD_SIGNATURES.items()):
         try:
             fn = getattr(L, name)
         except AttributeError as e:

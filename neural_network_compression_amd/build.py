@@ -17,7 +17,7 @@ DIAG = os.environ.get("NNC_DIAG", "0") not in ("", "0")   # diagnostics build (p
 LIB = os.path.join(CSRC, "libnnc_hip_diag.so" if DIAG else "libnnc_hip.so")
 SOURCES = [os.path.join(CSRC, f) for f in ("nnc_hip.hip", "nnc_core.hip", "nnc_reduce.hip", "nnc_reffit.hip", "nnc_huffman.hip", "nnc_comm.hip", "nnc_sort.hip", "nnc_pp.hip",
                                             "nnc_codec.hip", "nnc_layer.hip", "nnc_cbmm.hip", "nnc_cbmm_h16.hip", "nnc_cbmm_grouped.hip", "nnc_cbsp.hip", "nnc_cbsp_h16.hip", "nnc_cbsp_grouped.hip", "nnc_cbsp_grouped_h16.hip",
-                                            "nnc_cbgrad.hip", "nnc_cbgrad_h16.hip", "nnc_cbgrad_grouped.hip", "nnc_cbspgrad.hip", "nnc_cbspgrad_h16.hip", "nnc_cbpk.hip", "nnc_cbpkgrad.hip", "nnc_cbpk_grouped.hip", "nnc_cbpkgrad_grouped.hip", "nnc_cbpk_h16.hip", "nnc_cbgrad_grouped_h16.hip", "nnc_cbpkgrad_grouped_h16.hip")]   # (the longest unit first: the units compile side by side)
+                                            "nnc_cbgrad.hip", "nnc_cbgrad_h16.hip", "nnc_cbgrad_grouped.hip", "nnc_cbspgrad.hip", "nnc_cbspgrad_h16.hip", "nnc_cbpk.hip", "nnc_cbpkgrad.hip", "nnc_cbpk_grouped.hip", "nnc_cbpkgrad_grouped.hip", "nnc_cbpk_h16.hip", "nnc_cbgrad_grouped_h16.hip", "nnc_cbpkgrad_grouped_h16.hip", "nnc_cbspgrad_grouped.hip")]   # (the longest unit first: the units compile side by side)
 EXTRA_LIBS: list = []
 
 
@@ -37,7 +37,7 @@ def is_stale() -> bool:
 
 
 def _headers():
-    return [os.path.join(INCLUDE, "nnc.h"), os.path.join(INCLUDE, "nnc_cbgrad_grouped.h"), os.path.join(INCLUDE, "nnc_cbgrad_h16.h"), os.path.join(INCLUDE, "nnc_cbpkgrad_grouped.h"), os.path.join(INCLUDE, "nnc_cbsp_h16.h"), os.path.join(INCLUDE, "nnc_cbsp_grouped.h"), os.path.join(INCLUDE, "nnc_cbsp_grouped_h16.h"), os.path.join(INCLUDE, "nnc_cbspgrad_h16.h"), os.path.join(INCLUDE, "nnc_cbpk_h16.h"), os.path.join(INCLUDE, "nnc_cbgrad_grouped_h16.h")] + sorted(os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".hpp"))
+    return [os.path.join(INCLUDE, "nnc.h"), os.path.join(INCLUDE, "nnc_cbgrad_grouped.h"), os.path.join(INCLUDE, "nnc_cbgrad_h16.h"), os.path.join(INCLUDE, "nnc_cbpkgrad_grouped.h"), os.path.join(INCLUDE, "nnc_cbsp_h16.h"), os.path.join(INCLUDE, "nnc_cbsp_grouped.h"), os.path.join(INCLUDE, "nnc_cbsp_grouped_h16.h"), os.path.join(INCLUDE, "nnc_cbspgrad_h16.h"), os.path.join(INCLUDE, "nnc_cbpk_h16.h"), os.path.join(INCLUDE, "nnc_cbgrad_grouped_h16.h"), os.path.join(INCLUDE, "nnc_cbspgrad_grouped.h")] + sorted(os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".hpp"))
 
 
 def _flags():

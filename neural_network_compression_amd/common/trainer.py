@@ -284,8 +284,8 @@ class Trainer(ABC):
         return self._tune_centres(_HalfActivations(net, activation_dtype), models, train_dataset, test_dataset, epochs, learning_rate)
 
     def fine_tune_grouped(self, train_dataset: LeNetDataset, test_dataset: LeNetDataset, epochs: int, learning_rate: float = 1e-3,
-                          packed=False, activation_dtype=None) -> List[float]:
-        """fine_tune_compressed's loop on ``compressed.compress_network_trainable_grouped(..., packed=packed)``: the Dense layers
+                          packed=False, sparse=False, activation_dtype=None) -> List[float]:
+        """fine_tune_compressed's loop on ``compressed.compress_network_trainable_grouped(..., packed=packed, sparse=sparse)``: the Dense layers
         quantized with ``group_rows`` train their (G, K) centres through ops.grouped_codebook_linear (neither W
         nor dW is built), every other quantized tensor trains as in fine_tune_compressed(sparse=False, packed=False).  ``packed``
         True or "auto": the grouped layers of at most 16 centres per group train from their 2- or 4-bit packed indices instead
@@ -295,14 +295,24 @@ class Trainer(ABC):
         compressed_network(), store_report and load_network see the tuned centres.  Returns the accuracy per epoch.
         ``activation_dtype``: None (float32), torch.bfloat16 or torch.float16 (with any ``packed``): the network is built with half_inputs=True, its input is cast to the dtype and its output back to float32 before
         the loss, as in fine_tune_compressed; centres, bias and their gradients stay float32, and the write-back and the re-decode
-        are the same.  A layer with weights that takes no half input is a ValueError."""
+        are the same.  A layer with weights that takes no half input is a ValueError.
+        ``sparse`` True or "auto": the grouped layers train from the bitmap-sparse form of their indices instead
+        (ops.grouped_sparse_codebook_linear), every one or where that form is smaller; with ``packed`` not False
+        a layer takes the smallest of its forms.  float32 activations only: ``sparse`` not False with ``activation_dtype`` is a
+        ValueError.  The write-back of the tuned (G, K) is unchanged."""
+        if sparse is not False and activation_dtype is not None:
+            raise ValueError("sparse needs activation_dtype=None: the trainable grouped bitmap-sparse layer takes float32 activations only "
+                             "(activation_dtype trains the byte and packed grouped forms)")
         models = getattr(self, "quantized_models_by_layer", None)
         if not models:
             raise RuntimeError("fine_tune_grouped needs a quantized network: call quantize first")
         from .. import compressed
 
+        # ``sparse`` is passed only where it is asked for: older tests replace compress_network_trainable_grouped by a recorder and
+        # pin the keywords of this call, so without ``sparse`` it stays the call it was
         if activation_dtype is None:
-            net = compressed.compress_network_trainable_grouped(self.neural_network, models, packed=packed)
+            net = compressed.compress_network_trainable_grouped(self.neural_network, models, packed=packed,
+                                                                **({} if sparse is False else dict(sparse=sparse)))
             return self._tune_centres(net, models, train_dataset, test_dataset, epochs, learning_rate)
         if activation_dtype not in (torch.bfloat16, torch.float16):
             raise ValueError(f"activation_dtype must be None, torch.bfloat16 or torch.float16, got {activation_dtype}")

@@ -89,7 +89,10 @@ and Trainer.fine_tune_grouped trains it.  With ``packed=True | "auto"`` there a 
 trains from its 2- or 4-bit packed indices (``TrainableGroupedPackedCompressedDense``):
 ops.grouped_packed_codebook_linear's backward forms dx and the (G, K) centroid gradient from the packed rows
 (csrc/nnc_cbpkgrad_grouped.hip), the centroid gradient the byte grouped layer's bit for bit, and no byte-per-weight tensor stays
-resident while training.  The bitmap-sparse grouped form and grouped Conv2D do not train.
+resident while training.  With ``sparse=True | "auto"`` there a pruned grouped layer trains from the bitmap-sparse form of its
+indices (``TrainableGroupedSparseCompressedDense``): ops.grouped_sparse_codebook_linear's backward forms dx and
+the (G, K) centroid gradient from the buffer of ``GroupedSparseCompressedDense`` (csrc/nnc_cbspgrad_grouped.hip), the centroid
+gradient again the byte grouped layer's bit for bit, on float32 activations only.  Grouped Conv2D does not train.
 
 How the classes are laid out: ``_Activated`` (the activation behind the product, ``get_weights``) is the root of
 ``_InferenceLayer`` (the float32 ``centers`` / ``bias`` buffers behind the family's index buffer, ``nbytes``) and of
@@ -982,6 +985,72 @@ class TrainableGroupedPackedCompressedDense(_DenseHalf, _PackedForm, _TrainableC
         return self._nbytes(self.packed)
 
 
+class TrainableGroupedSparseCompressedDense(_DenseHalf, _TrainableCentres):
+    """GroupedSparseCompressedDense with trainable centres (ops.grouped_sparse_codebook_linear): packed (the
+    bitmap-sparse buffer of the whole index matrix) and zero_symbols (uint8[G]) the only index buffers, centers a float32 (G, K)
+    nn.Parameter, counts the (G, K) histogram of every group's indices taken from the labels before packing, so kernel_sq_sum() is
+    TrainableGroupedCompressedDense's bit for bit; the bias of _TrainableCentres.  The backward forms dx and the (G, K) centroid
+    gradient from the codebooks and the bitmap-sparse form (csrc/nnc_cbspgrad_grouped.hip): the indices are never unpacked, W and dW
+    never built, and no byte-per-weight tensor stays resident while training.  float32 activations only: a bfloat16 or float16 input
+    raises ``TypeError``."""
+
+    def __init__(self, codes: ops.GroupedSparseCodes, labels: torch.Tensor, centers: torch.Tensor, bias: torch.Tensor | None = None,
+                 bias_codes=None, activation=None):
+        super().__init__()
+        groups = max(1, codes.groups)
+        if centers.dim() != 2 or tuple(centers.shape) != (groups, codes.k):
+            raise ValueError(f"centers must have shape ({groups}, {codes.k}) for {codes.kdim} rows in groups of {codes.group_rows} and indices into "
+                             f"codebooks of {codes.k}, got {tuple(centers.shape)}")
+        if labels.numel() != codes.kdim * codes.ncols:
+            raise ValueError(f"{labels.numel()} indices for a {codes.kdim} x {codes.ncols} weight matrix")
+        self.kdim, self.ncols, self.k, self.group_rows, self.nnz = codes.kdim, codes.ncols, codes.k, codes.group_rows, codes.nnz
+        self.register_buffer("packed", codes.buf)
+        self.register_buffer("zero_symbols", codes.zero_symbols)
+        counts = _group_counts(labels.reshape(-1), self.group_rows * self.ncols, groups, codes.k)
+        self._init_centres(None, centers, codes.ncols, bias, bias_codes, activation, counts=counts)
+
+    @property
+    def codes(self) -> ops.GroupedSparseCodes:
+        return ops.GroupedSparseCodes(self.packed, self.kdim, self.ncols, self.k, self.group_rows, self.zero_symbols, self.nnz)
+
+    @classmethod
+    def from_dense(cls, dense, grouped_model, bias_model=None, zero_symbols=None) -> "TrainableGroupedSparseCompressedDense":
+        """From a Dense layer and the GroupedModel of its kernel; a quantized bias keeps its codes, a raw one stays frozen."""
+        _require_model(grouped_model)
+        kin, kout = dense.kernel.shape
+        dev = dense.kernel.device
+        centers = torch.from_numpy(np.ascontiguousarray(grouped_model.cluster_centers_, dtype=np.float32)).to(dev)
+        bias, bias_codes = (None, _codes(bias_model, dev)) if bias_model is not None else (dense.bias, None)
+        return cls.from_codes(kin, kout, grouped_model.group_rows, grouped_model.labels_compact_, centers, bias, bias_codes, dense.activation,
+                              zero_symbols)
+
+    @classmethod
+    def from_codes(cls, kdim, ncols, group_rows, labels, centers, bias=None, bias_codes=None, activation=None,
+                   zero_symbols=None) -> "TrainableGroupedSparseCompressedDense":
+        if centers.dim() != 2:
+            raise ValueError(f"centers must have shape (G, K), got {tuple(centers.shape)}")
+        return cls(ops.pack_grouped_sparse_codes(labels, kdim, ncols, centers.shape[1], group_rows, zero_symbols), labels, centers, bias, bias_codes,
+                   activation)
+
+    @classmethod
+    def from_grouped(cls, layer: GroupedCompressedDense, zero_symbols=None) -> "TrainableGroupedSparseCompressedDense":
+        """The trainable sparse layer of a GroupedCompressedDense: its indices packed, the same centres, its decoded bias frozen."""
+        return cls.from_codes(layer.kdim, layer.ncols, layer.group_rows, layer.labels, layer.centers, layer.bias, None, layer.activation, zero_symbols)
+
+    @classmethod
+    def from_grouped_sparse(cls, layer: GroupedSparseCompressedDense) -> "TrainableGroupedSparseCompressedDense":
+        """The trainable layer of a GroupedSparseCompressedDense on the same buffer; the counts come from a temporary unpack
+        (nnc_cbsp_grouped_unpack), which is dropped afterwards."""
+        return cls(layer.codes, layer.codes.to_dense(), layer.centers, layer.bias, None, layer.activation)
+
+    def _matmul(self, x: torch.Tensor) -> torch.Tensor:
+        return self._activate(ops.grouped_sparse_codebook_linear(x, self.codes, self.centers, bias=self.current_bias(), relu=self._fused_relu))
+
+    def nbytes(self) -> int:
+        """The buffer, the G skipped symbols, the G * K centres and the bias."""
+        return self._nbytes(self.packed) + _tensor_bytes(self.zero_symbols)
+
+
 PACKED_MAX_K = 16   # the packed form holds at most 4-bit indices
 
 
@@ -1178,7 +1247,29 @@ def compress_network_trainable(network: nn.Module, models_by_layer, sparse=False
     return _compress_each(network, models_by_layer, make, grouped="trainable=True")
 
 
-def compress_network_trainable_grouped(network: nn.Module, models_by_layer, packed=False, half_inputs=False) -> nn.Module:
+def _grouped_trainable_pick(layer, wm, bm, sparse, packed):
+    """The trainable grouped layer of compress_network_trainable_grouped(sparse=, packed=) with ``sparse`` not False: the candidates in
+    the order byte form (unless ``sparse is True``, or ``packed is True`` and K <= 16), packed form (``packed`` not False and K <= 16),
+    bitmap-sparse form; the one with the fewest resident bytes, on equal bytes the earliest (smallest_grouped_layers' order).
+    The forms differ in their index bytes only (the sparse one also keeps its G skipped symbols), which are known from the labels'
+    histograms: only the winner is built."""
+    k = wm.cluster_centers_.shape[1]
+    fits = k <= PACKED_MAX_K
+    kin, kout = layer.kernel.shape
+    rows = int(wm.group_rows)
+    groups = max(1, -(-kin // rows))
+    cands = []   # (index bytes, maker), in the order of the ties
+    if sparse is not True and not (packed is True and fits):
+        cands.append((kin * kout, TrainableGroupedCompressedDense.from_dense))
+    if packed is not False and fits:
+        cands.append((ops.packed_nbytes(kin, kout, ops.packed_bits(k)), TrainableGroupedPackedCompressedDense.from_dense))
+    counts = _group_counts(wm.labels_compact_.reshape(-1), rows * kout, groups, k)
+    nnz = kin * kout - int(counts.max(dim=1).values.sum().item())   # every group skips its most frequent index
+    cands.append((int(ops.nat.load().nnc_cbsp_pack_bytes(kin, kout, 1, nnz)) + -(-kin // rows), TrainableGroupedSparseCompressedDense.from_dense))
+    return min(cands, key=lambda c: c[0])[1](layer, wm, bm)   # (min keeps the first of equals)
+
+
+def compress_network_trainable_grouped(network: nn.Module, models_by_layer, packed=False, sparse=False, half_inputs=False) -> nn.Module:
     """compress_network_trainable(network, models_by_layer) -- the byte forms -- in which every layer whose kernel model is a
     utility.GroupedModel becomes a TrainableGroupedCompressedDense instead of raising.  On a network
     without grouped layers it returns what compress_network_trainable returns.  ``packed``: False (the byte grouped layers), True
@@ -1186,9 +1277,25 @@ def compress_network_trainable_grouped(network: nn.Module, models_by_layer, pack
     "auto" (that class only where the packed form holds fewer resident bytes; on equal bytes the byte form stays); anything else
     is a ValueError.  Ungrouped layers stay in the byte trainable forms either way.  Trainer.fine_tune_grouped trains it.
     ``half_inputs=True``: the grouped layers of either form and the ungrouped byte-form layers are built with half_inputs=True and
-    train on bfloat16 / float16 inputs (DESIGN.md sections 22 and 26)."""
+    train on bfloat16 / float16 inputs (DESIGN.md sections 22 and 26).
+    ``sparse``: False (as above), True (a TrainableGroupedSparseCompressedDense, DESIGN.md section 32, for every grouped layer) or
+    "auto" (that class only where the bitmap-sparse form holds fewer resident bytes than the byte form); anything else is a
+    ValueError.  Together with ``packed`` not False a grouped layer takes the smallest of its candidates, on equal bytes in the order
+    byte, packed, sparse; ``sparse=True`` with ``packed=True`` is a ValueError (both ask for every layer).  The sparse trainable layer
+    takes float32 activations only: ``sparse`` not False with ``half_inputs=True`` is a ValueError."""
+    _check_sparse(sparse)
+    if packed not in (False, True, "auto"):
+        raise ValueError(f"packed must be False, True or 'auto', got {packed!r}")
+    if sparse is not False and half_inputs:
+        raise ValueError("sparse needs half_inputs=False here: the trainable grouped bitmap-sparse layer takes float32 activations only "
+                         "(half_inputs trains the byte and packed grouped forms)")
+    if sparse is True and packed is True:
+        raise ValueError("sparse=True and packed=True both ask for every layer: take one, or 'auto' for either")
     half = dict(half_inputs=True) if half_inputs else {}
-    if packed is False:
+    if sparse is not False:
+        def make_grouped(layer, wm, bm):
+            return _grouped_trainable_pick(layer, wm, bm, sparse, packed)
+    elif packed is False:
         def make_grouped(layer, wm, bm):
             return TrainableGroupedCompressedDense.from_dense(layer, wm, bm, **half)
     elif packed is True or packed == "auto":

@@ -1163,6 +1163,91 @@ def cbsp_grouped_h16_plan(dtype, m: int, kdim: int, ncols: int, k: int, group_ro
     return _plan(nat.load().nnc_cbsp_grouped_h16_plan, nat.CBSP_GROUPED_H16_PLAN_FIELDS, _h16_dt(dtype), m, kdim, ncols, k, group_rows, cus)
 
 
+def _grouped_sparse_grad_args(who: str, g, codes, centers=None):
+    """The checks of the grouped sparse backward ops: float32 g of (..., ncols) rows, a GroupedSparseCodes, and (dx) float32 centers
+    (G, codes.k) -> (lead, m) of g."""
+    if isinstance(g, torch.Tensor) and g.dtype in _H16_DT:
+        raise TypeError(f"{who} takes float32 activations, got {g.dtype}: the backward pass from the grouped bitmap-sparse form has no bfloat16 / "
+                        "float16 path (use the byte or packed forms, ops.grouped_codebook_linear(half_inputs=True))")
+    _require_cuda(g, "g", torch.float32)
+    if not isinstance(codes, GroupedSparseCodes):
+        raise TypeError("codes must be a GroupedSparseCodes (ops.pack_grouped_sparse_codes)")
+    _check_group_rows(codes.kdim, codes.group_rows)
+    if centers is not None:
+        _require_cuda(centers, "centers", torch.float32)
+        if centers.dim() != 2 or tuple(centers.shape) != (max(codes.groups, 1), codes.k):
+            raise ValueError(f"centers must have shape ({max(codes.groups, 1)}, {codes.k}), got {tuple(centers.shape)}")
+    return _rows(g, "g", codes.ncols)
+
+
+def grouped_sparse_codebook_matmul_dx(g: torch.Tensor, codes: GroupedSparseCodes, centers: torch.Tensor) -> torch.Tensor:
+    """dx = g @ W^T from the bitmap-sparse form of a group-wise layer (include/nnc_cbspgrad_grouped.h, nnc_cbsp_grouped_dx_f32;
+    DESIGN.md section 32): with q = i // group_rows, dx[., i] = c_{z_q} * sum_o g[., o] + the stored weights' g[., o] *
+    (centers[q][label] - c_{z_q}), the input gradient of grouped_sparse_codebook_matmul with its conventions (a group with c_{z_q} == 0
+    drops the rank-1 term, and its skipped weights form no product).  g: float32 (..., ncols); centers: float32 (G, codes.k).
+    Returns float32 (..., kdim).  The columns of group q are, bit for bit, those sparse_codebook_matmul_dx gives on the same buffer
+    read as ``SparseCodes(codes.buf, kdim, ncols, k, z_q, 1, codes.nnz)`` with the one table ``centers[q]``.  No host read."""
+    lead, m = _grouped_sparse_grad_args("grouped_sparse_codebook_matmul_dx", g, codes, centers)
+    _one_device("g, codes and centers", g, codes.buf, codes.zero_symbols, centers)
+    L = nat.load()
+    kdim, ncols = codes.kdim, codes.ncols
+    dx = torch.empty(lead + (kdim,), dtype=torch.float32, device=g.device)
+    ws_bytes = int(L.nnc_cbsp_grouped_dx_workspace_bytes(m, kdim, ncols))
+    ws = _workspace(ws_bytes, g.device)
+    nat.check(L.nnc_cbsp_grouped_dx_f32(_ptr(g), m, kdim, _ptr(codes.buf), codes.buf.numel(), ncols, _ptr(codes.zero_symbols), codes.nnz, _ptr(centers),
+                                        codes.k, codes.group_rows, _ptr(dx), _ptr(ws), ws_bytes, _stream(g)))
+    return dx
+
+
+def grouped_sparse_codebook_centroid_grad(x: torch.Tensor, g: torch.Tensor, codes: GroupedSparseCodes, dtype=torch.float64) -> torch.Tensor:
+    """dc[q, j] = sum over the (i, o) of group q whose label is j of (x^T g)[i, o], the skipped positions counted under the group's
+    zero symbol (include/nnc_cbspgrad_grouped.h, nnc_cbsp_grouped_dc_f32): bit for bit grouped_codebook_centroid_grad(x, g,
+    codes.to_dense(), ...), the indices never unpacked and dW never written.  x: float32 (..., kdim), g: float32 (..., ncols) with the
+    same leading shape.  Returns ``dtype`` (float64 or float32) (G, codes.k).  No host read."""
+    if isinstance(x, torch.Tensor) and x.dtype in _H16_DT:
+        raise TypeError(f"grouped_sparse_codebook_centroid_grad takes float32 activations, got {x.dtype}: the backward pass from the grouped "
+                        "bitmap-sparse form has no bfloat16 / float16 path")
+    lead, m = _grouped_sparse_grad_args("grouped_sparse_codebook_centroid_grad", g, codes)
+    _require_cuda(x, "x", torch.float32)
+    kdim, ncols, k = codes.kdim, codes.ncols, codes.k
+    _dc_args(x, lead, kdim, "x, g and codes", codes.buf, g, dtype)
+    L = nat.load()
+    dc = torch.empty((max(codes.groups, 1), k), dtype=dtype, device=x.device)
+    ws_bytes = int(L.nnc_cbsp_grouped_dc_workspace_bytes(m, kdim, ncols, k, codes.group_rows))
+    ws = _workspace(ws_bytes, x.device)
+    nat.check(L.nnc_cbsp_grouped_dc_f32(_ptr(x), _ptr(g), m, kdim, _ptr(codes.buf), codes.buf.numel(), ncols, _ptr(codes.zero_symbols), codes.nnz, k,
+                                        codes.group_rows, _ptr(dc), 1 if dtype == torch.float64 else 0, _ptr(ws), ws_bytes, _stream(x)))
+    return dc
+
+
+def cbsp_grouped_dx_plan(m: int, kdim: int, ncols: int, k: int, group_rows: int, cus: int) -> dict:
+    """Host: the plan nnc_cbsp_grouped_dx_f32 follows on a device with ``cus`` compute units (include/nnc_cbspgrad_grouped.h,
+    nnc_cbsp_grouped_dx_plan), as a dict keyed by _native.CBSPDX_GROUPED_PLAN_FIELDS.  No device needed."""
+    return _plan(nat.load().nnc_cbsp_grouped_dx_plan, nat.CBSPDX_GROUPED_PLAN_FIELDS, m, kdim, ncols, k, group_rows, cus)
+
+
+def cbsp_grouped_dc_plan(m: int, kdim: int, ncols: int, k: int, group_rows: int, cus: int) -> dict:
+    """Host: the plan nnc_cbsp_grouped_dc_f32 follows on a device with ``cus`` compute units (include/nnc_cbspgrad_grouped.h,
+    nnc_cbsp_grouped_dc_plan), as a dict keyed by _native.CBSPDC_GROUPED_PLAN_FIELDS.  No device needed."""
+    return _plan(nat.load().nnc_cbsp_grouped_dc_plan, nat.CBSPDC_GROUPED_PLAN_FIELDS, m, kdim, ncols, k, group_rows, cus)
+
+
+def grouped_sparse_codebook_linear(x: torch.Tensor, codes: GroupedSparseCodes, centers: torch.Tensor, bias: torch.Tensor | None = None,
+                                   relu: bool = False) -> torch.Tensor:
+    """grouped_sparse_codebook_matmul with gradients for x, centers (G, K) and bias, through the autograd Function of codebook_linear
+    (DESIGN.md section 32).  The forward is the same float32 nnc_cbsp_grouped_f32 call (under no_grad the bits of
+    grouped_sparse_codebook_matmul); the backward runs grouped_sparse_codebook_matmul_dx only if x needs a gradient and
+    grouped_sparse_codebook_centroid_grad (float32) only if centers does, masks a fused ReLU as torch does and sums the bias gradient
+    over the rows.  The indices get no gradient.  No host read.  float32 activations only: a bfloat16 or float16 x raises
+    ``TypeError``."""
+    if not isinstance(codes, GroupedSparseCodes):
+        raise TypeError("codes must be a GroupedSparseCodes (ops.pack_grouped_sparse_codes)")
+    _require_f32_x(x, "grouped_sparse_codebook_linear")
+    return _CodebookLinear.apply(x, codes, centers, bias, bool(relu), codes.kdim, codes.ncols, grouped_sparse_codebook_matmul,
+                                 grouped_sparse_codebook_matmul_dx,
+                                 lambda x2, g2, cd, c: grouped_sparse_codebook_centroid_grad(x2, g2, cd, dtype=torch.float32))
+
+
 class PackedCodes:
     """The 2- or 4-bit packed form of one (kdim, ncols) index matrix of a codebook of ``k`` <= 2^bits centres (include/nnc.h,
     nnc_cbpk_*): ``packed``, one 256-byte aligned uint8 device buffer of kdim rows of nnc_cbpk_row_bytes(ncols, bits) bytes, and
