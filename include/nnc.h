@@ -1080,6 +1080,11 @@ int nnc_cbpk_dc_f32(const float *x, const float *g, int64_t m, int64_t kdim, con
  * two of the packed form, their workspace queries and plans, declared in a header of their own. */
 #include "nnc_cbgrad_grouped_h16.h"
 
+/* The backward pass of the pruned group-wise layer on bf16 / fp16 activations from its bitmap-sparse form
+ * (csrc/nnc_cbspgrad_grouped_h16.hip): nnc_cbsp_grouped_dx_h16, nnc_cbsp_grouped_dc_h16, their workspace
+ * queries and plans, declared in a header of their own. */
+#include "nnc_cbspgrad_grouped_h16.h"
+
 /* ------------------------------------------------------------------------------------
  * Multi-GPU: the vector is sharded across one process per GPU (contiguous shards starting on multiples of
  * NNC_CHUNK elements); the exchange per Lloyd iteration is one all-reduce (SUM) of the 2K int64 sums / counts over

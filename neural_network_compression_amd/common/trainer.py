@@ -284,7 +284,7 @@ class Trainer(ABC):
         return self._tune_centres(_HalfActivations(net, activation_dtype), models, train_dataset, test_dataset, epochs, learning_rate)
 
     def fine_tune_grouped(self, train_dataset: LeNetDataset, test_dataset: LeNetDataset, epochs: int, learning_rate: float = 1e-3,
-                          packed=False, sparse=False, activation_dtype=None) -> List[float]:
+                          packed=False, sparse=False, *, sparse_half_inputs=False, activation_dtype=None) -> List[float]:
         """fine_tune_compressed's loop on ``compressed.compress_network_trainable_grouped(..., packed=packed, sparse=sparse)``: the Dense layers
         quantized with ``group_rows`` train their (G, K) centres through ops.grouped_codebook_linear (neither W
         nor dW is built), every other quantized tensor trains as in fine_tune_compressed(sparse=False, packed=False).  ``packed``
@@ -298,11 +298,15 @@ class Trainer(ABC):
         are the same.  A layer with weights that takes no half input is a ValueError.
         ``sparse`` True or "auto": the grouped layers train from the bitmap-sparse form of their indices instead
         (ops.grouped_sparse_codebook_linear), every one or where that form is smaller; with ``packed`` not False
-        a layer takes the smallest of its forms.  float32 activations only: ``sparse`` not False with ``activation_dtype`` is a
-        ValueError.  The write-back of the tuned (G, K) is unchanged."""
-        if sparse is not False and activation_dtype is not None:
+        a layer takes the smallest of its forms.  ``sparse`` not False with ``activation_dtype`` is a ValueError unless
+        ``sparse_half_inputs=True`` asks for it: then the sparse layers train on the half activations too (DESIGN.md section 35);
+        ``sparse_half_inputs=True`` without ``sparse`` is a ValueError, as in compress_network_trainable_grouped.  The write-back of the
+        tuned (G, K) is unchanged."""
+        if sparse_half_inputs and sparse is False:
+            raise ValueError("sparse_half_inputs=True needs sparse=True or 'auto': it trains the grouped bitmap-sparse layers on half activations")
+        if sparse is not False and activation_dtype is not None and not sparse_half_inputs:
             raise ValueError("sparse needs activation_dtype=None: the trainable grouped bitmap-sparse layer takes float32 activations only "
-                             "(activation_dtype trains the byte and packed grouped forms)")
+                             "(activation_dtype trains the byte and packed grouped forms) unless sparse_half_inputs=True is passed as well")
         models = getattr(self, "quantized_models_by_layer", None)
         if not models:
             raise RuntimeError("fine_tune_grouped needs a quantized network: call quantize first")
@@ -316,8 +320,10 @@ class Trainer(ABC):
             return self._tune_centres(net, models, train_dataset, test_dataset, epochs, learning_rate)
         if activation_dtype not in (torch.bfloat16, torch.float16):
             raise ValueError(f"activation_dtype must be None, torch.bfloat16 or torch.float16, got {activation_dtype}")
-        net = compressed.compress_network_trainable_grouped(self.neural_network, models, packed=packed, half_inputs=True)
-        half_layers = (compressed._TrainableCodebookLayer, compressed.TrainableGroupedCompressedDense, compressed.TrainableGroupedPackedCompressedDense)
+        net = compressed.compress_network_trainable_grouped(self.neural_network, models, packed=packed, half_inputs=True,
+                                                            **({} if sparse is False else dict(sparse=sparse, sparse_half_inputs=True)))
+        half_layers = (compressed._TrainableCodebookLayer, compressed.TrainableGroupedCompressedDense, compressed.TrainableGroupedPackedCompressedDense,
+                       compressed.TrainableGroupedSparseCompressedDense)
         for name, layer in net.get_config().items():
             takes_half = isinstance(layer, half_layers) and layer.half_inputs
             if not takes_half and (hasattr(layer, "kernel") or next(layer.parameters(), None) is not None):

@@ -24,87 +24,11 @@
 //                     group, so its one skip register goes into bin z_q of its set.
 // Everything that steers a walk comes from blockIdx, the kernel arguments and the wave number (a scalar): every wave of a workgroup
 // reaches every barrier, also one whose share of a stretch is empty, and no v_readlane stands under a lane-dependent branch.
+// The two stream kernels are nnc_cbspgrad_grouped.hpp's at XT = float (nnc_cbspgrad_grouped_h16.hip instantiates the half ones).
 // The row sums (cbsp_rowsum), k_cbgrad_absmax, k_cbgrad_reduce, k_cbdc_finish (over G * k bins) and the host sequences (cbg_run_dx,
 // cbg_run_dc) are shared with the other backward units.  No float atomics; no host read.
-#include "nnc_cbspgrad.hpp"
-#include "nnc_cbsp_grouped.hpp"
+#include "nnc_cbspgrad_grouped.hpp"
 #include "nnc_cbtile.hpp"
-
-// ------------------------------------------------------------------ dx, m <= 16
-// grid (column blocks, row groups), CB_THREADS threads; LDS as k_cbspdx_stream: the d table (entries << cshift), the staging row.
-// out: dx (one column block) or the float32 partials [block][m][kdim] (direct 0).  rows_per_group is the workgroup's index rows (the
-// plan's name), not group_rows.
-template <int MT>
-__global__ __launch_bounds__(CB_THREADS) void k_cbspgdx_stream(const float *__restrict__ g, int m, long long kdim, const uint64_t *__restrict__ bitmap,
-                                                               const uint32_t *__restrict__ lo, const uint32_t *__restrict__ hi,
-                                                               const uint8_t *__restrict__ sym, long long nnz, long long ncols, long long segs,
-                                                               const float *__restrict__ centers, int k, const uint8_t *__restrict__ zsym,
-                                                               long long group_rows, int entries, int cshift, long long rows_per_group, int direct,
-                                                               float *__restrict__ out)
-{
-    constexpr int E = sg_segs(MT), RB = 64 / E, UR = E >= 8 ? 1 : 8 / E;   // segments per block, rows per batch, rows per step
-    extern __shared__ float smem[];
-    float *tab = smem;
-    float *stage = smem + (entries << cshift);
-
-    const int lane = threadIdx.x & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const long long blk = blockIdx.x;
-    const long long s_lo = (long long)blockIdx.y * rows_per_group, s_hi = std::min(kdim, s_lo + rows_per_group);
-    long long group = s_lo / group_rows;
-    long long g_lo = s_lo, g_hi, i0, i1;   // the rows of the workgroup that lie in `group`, and the wave's share of them
-    cb_group_step(group, group_rows, g_lo, s_hi, wave, g_hi, i0, i1);
-    const int top = std::min(k, entries - 1);   // entry min(symbol, top): d of the symbol, or -c_{z_q} (k < 256: a symbol can pass k)
-    sp_fill<float>(tab, stage, centers + group * k, k, spg_cz(centers, k, zsym, group), top + 1, cshift);
-
-    float gv[MT][E];
-#pragma unroll
-    for (int e = 0; e < E; ++e) {
-        const long long col = (blk * E + e) * 64 + lane;
-#pragma unroll
-        for (int r = 0; r < MT; ++r) gv[r][e] = (r < m && col < ncols) ? g[(long long)r * ncols + col] : 0.0f;
-    }
-    float *dst = direct ? out : out + blk * m * kdim;
-    __syncthreads();
-
-    for (;;) {
-        uint64_t wn;
-        long long cn;
-        sg_batch<E>(bitmap, lo, hi, segs, blk, i0, i1, lane, wn, cn);
-        for (long long ib = i0; ib < i1; ib += RB) {
-            const uint64_t wl = wn;
-            const long long cl = cn;
-            if (ib + RB < i1) sg_batch<E>(bitmap, lo, hi, segs, blk, ib + RB, i1, lane, wn, cn);   // the next batch of the stretch in flight
-            const int nb = (int)std::min((long long)RB, i1 - ib);
-            for (int u0 = 0; u0 < nb; u0 += UR) {
-                uint32_t bits[UR][E], sv[UR][E];
-                sg_symbols<uint8_t, E, UR>(wl, cl, u0, lane, sym, nnz, bits, sv);
-#pragma unroll
-                for (int u = 0; u < UR; ++u) {
-                    float p[MT];
-#pragma unroll
-                    for (int r = 0; r < MT; ++r) p[r] = 0.0f;
-#pragma unroll
-                    for (int e = 0; e < E; ++e) {
-                        const float dv = tab[CbTable<uint8_t>::index(std::min(sv[u][e], (uint32_t)top), k, cshift, lane)];
-#pragma unroll
-                        for (int r = 0; r < MT; ++r) p[r] = bits[u][e] ? __builtin_fmaf(gv[r][e], dv, p[r]) : p[r];   // skipped: no product
-                    }
-                    int row;
-                    const float v = wave_reduce_rows<MT>(p, lane, row);
-                    if (u0 + u < nb && (lane & (64 / MT - 1)) == 0 && row < m) dst[(long long)row * kdim + ib + u0 + u] = v;
-                }
-            }
-        }
-        if (g_hi >= s_hi) break;   // (the same test for the four waves)
-        // on to the next group's rows, divided among the waves as the whole range is
-        g_lo = g_hi;
-        cb_group_step(++group, group_rows, g_lo, s_hi, wave, g_hi, i0, i1);
-        __syncthreads();   // every wave has left the rows of the group before
-        sp_fill<float>(tab, stage, centers + group * k, k, spg_cz(centers, k, zsym, group), top + 1, cshift);
-        __syncthreads();
-    }
-}
 
 // ------------------------------------------------------------------ dx, m > 16
 // k_cbspdx_tiled<uint8_t> with centers[groups][k] and zsym[groups]: the same grid, tile and FMA order.  LDS holds `tables` d tables of
@@ -185,109 +109,6 @@ __global__ __launch_bounds__(256) void k_cbspgdx_rank1(float *__restrict__ dx, l
     }
 }
 
-// ------------------------------------------------------------------ dc, m <= 16
-// grid (column blocks, row groups), CB_THREADS threads.  LDS: one group's bins, [k][1 << rlog2] int64; sums[groups][k].
-template <int MT>
-__global__ __launch_bounds__(CB_THREADS) void k_cbspgdc_stream(const float *__restrict__ x, const float *__restrict__ g, int m, long long kdim,
-                                                               const uint64_t *__restrict__ bitmap, const uint32_t *__restrict__ lo,
-                                                               const uint32_t *__restrict__ hi, const uint8_t *__restrict__ sym, long long nnz,
-                                                               long long ncols, long long segs, int k, const uint8_t *__restrict__ zsym,
-                                                               long long group_rows, int rlog2, int terms_log2, long long rows_per_group,
-                                                               uint32_t *__restrict__ hdr, unsigned long long *__restrict__ sums)
-{
-    constexpr int E = sg_segs(MT), RB = 64 / E, UR = E >= 8 ? 1 : 8 / E;
-    extern __shared__ unsigned long long bins[];
-    int flag;
-    const int S = cbdc_shift(hdr, m, terms_log2, flag);
-    if (blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0) {
-        hdr[2] = (uint32_t)S;
-        hdr[3] = (uint32_t)flag;
-    }
-    if (flag != CBG_FLAG_OK) return;   // (uniform over the launch)
-    int scx, scg;
-    cbdc_scales(hdr, scx, scg);
-    const int Sw = S - scx - scg;      // the shift of dW' = dW * 2^(scx + scg)
-    for (int j = threadIdx.x; j < (k << rlog2); j += CB_THREADS) bins[j] = 0ull;
-
-    const int lane = threadIdx.x & 63;
-    const int rep = lane & ((1 << rlog2) - 1);
-    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const long long blk = blockIdx.x;
-    float gv[MT][E];
-    bool incol[E];
-#pragma unroll
-    for (int e = 0; e < E; ++e) {
-        const long long col = (blk * E + e) * 64 + lane;
-        incol[e] = col < ncols;
-#pragma unroll
-        for (int r = 0; r < MT; ++r) gv[r][e] = g[cbdc_idx((long long)r * ncols + col, r < m && incol[e])];
-    }
-    __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-    for (int e = 0; e < E; ++e)
-#pragma unroll
-        for (int r = 0; r < MT; ++r) gv[r][e] = cbdc_scaled(gv[r][e], r < m && incol[e], scg);
-
-    const long long s_lo = (long long)blockIdx.y * rows_per_group, s_hi = std::min(kdim, s_lo + rows_per_group);
-    long long group = s_lo / group_rows;
-    long long g_lo = s_lo, g_hi, i0, i1;   // the rows of the workgroup that lie in `group`, and the wave's share of them
-    cb_group_step(group, group_rows, g_lo, s_hi, wave, g_hi, i0, i1);
-    unsigned long long skip = 0;   // the images of the lane's skipped weights in this group: bin z_q
-    __syncthreads();
-
-    for (;;) {
-        uint64_t wn;
-        long long cn;
-        sg_batch<E>(bitmap, lo, hi, segs, blk, i0, i1, lane, wn, cn);
-        for (long long ib = i0; ib < i1; ib += RB) {
-            const uint64_t wl = wn;
-            const long long cl = cn;
-            if (ib + RB < i1) sg_batch<E>(bitmap, lo, hi, segs, blk, ib + RB, i1, lane, wn, cn);   // the next batch of the stretch in flight
-            const int nb = (int)std::min((long long)RB, i1 - ib);
-            for (int u0 = 0; u0 < nb; u0 += UR) {
-                // x[r, i] of the UR rows: lane f holds x[f / UR, ib + u0 + f % UR] (f < MT * UR <= 64), broadcast by v_readlane
-                float xa;
-                {
-                    const int r0 = lane / UR;
-                    const long long i = ib + u0 + lane % UR;
-                    xa = cbdc_scaled(x[cbdc_idx((long long)r0 * kdim + i, r0 < m && i < i1)], r0 < m && i < i1, scx);
-                }
-                uint32_t bits[UR][E], sv[UR][E];
-                sg_symbols<uint8_t, E, UR>(wl, cl, u0, lane, sym, nnz, bits, sv);
-#pragma unroll
-                for (int u = 0; u < UR; ++u) {
-                    if (u0 + u >= nb) break;   // (uniform)
-                    float xv[MT];
-#pragma unroll
-                    for (int r = 0; r < MT; ++r) xv[r] = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, xa), r * UR + u));
-#pragma unroll
-                    for (int e = 0; e < E; ++e) {
-                        float d = 0.0f;
-#pragma unroll
-                        for (int r = 0; r < MT; ++r) d = __builtin_fmaf(xv[r], gv[r][e], d);   // dW'[i, o], r ascending (k_cbdc_stream)
-                        const unsigned long long img = cbdc_fix(d, Sw);
-                        if (bits[u][e]) {
-                            if (sv[u][e] < (uint32_t)k) atomicAdd(&bins[(sv[u][e] << rlog2) + rep], img);
-                        } else if (incol[e]) {
-                            skip += img;
-                        }
-                    }
-                }
-            }
-        }
-        const uint32_t z = zsym[group];   // (uniform)
-        if (z < (uint32_t)k && skip) atomicAdd(&bins[(z << rlog2) + rep], skip);
-        skip = 0;
-        cbdc_flush(bins, k, rlog2, sums + group * k);   // (begins with a barrier: every wave has left the group's rows)
-        if (g_hi >= s_hi) break;                        // (the same test for the four waves)
-        for (int j = threadIdx.x; j < k; j += CB_THREADS)   // the copies this thread has just summed
-            for (int r = 0; r < (1 << rlog2); ++r) bins[(j << rlog2) + r] = 0ull;
-        g_lo = g_hi;
-        cb_group_step(++group, group_rows, g_lo, s_hi, wave, g_hi, i0, i1);
-        __syncthreads();
-    }
-}
-
 // ------------------------------------------------------------------ dc, m > 16
 // k_cbspdc_tiled<uint8_t> with sums[groups][k]: the same grid, tiles and FMA order.  The k << rlog2 LDS bins are cut into
 // 1 << sets_log2 sets of k << (rlog2 - sets_log2), set t for group m0 / group_rows + t (k_cbdc_tiled_grouped).  Thread (tx, ty) bins
@@ -354,7 +175,7 @@ template <int MT>
 static void launch_sgg_dx(dim3 grid, size_t lds, hipStream_t s, const float *g, int m, long long kdim, const SpgForm &f, long long ncols, const float *centers,
                           int k, const SgPlan &p, int direct, float *out)
 {
-    hipLaunchKernelGGL((k_cbspgdx_stream<MT>), grid, dim3(CB_THREADS), lds, s, g, m, kdim, f.bitmap, f.lo, f.hi, f.sym, f.nnz, ncols, f.segs, centers, k, f.zsym,
+    hipLaunchKernelGGL((k_cbspgdx_stream<float, MT>), grid, dim3(CB_THREADS), lds, s, g, m, kdim, f.bitmap, f.lo, f.hi, f.sym, f.nnz, ncols, f.segs, centers, k, f.zsym,
                        f.group_rows, p.entries, p.cshift, p.rows_per_group, direct, out);
 }
 
@@ -362,7 +183,7 @@ template <int MT>
 static void launch_sgg_dc(dim3 grid, size_t lds, hipStream_t s, const float *x, const float *g, int m, long long kdim, const SpgForm &f, long long ncols, int k,
                           const SgPlan &p, uint32_t *hdr, unsigned long long *sums)
 {
-    hipLaunchKernelGGL((k_cbspgdc_stream<MT>), grid, dim3(CB_THREADS), lds, s, x, g, m, kdim, f.bitmap, f.lo, f.hi, f.sym, f.nnz, ncols, f.segs, k, f.zsym,
+    hipLaunchKernelGGL((k_cbspgdc_stream<float, MT>), grid, dim3(CB_THREADS), lds, s, x, g, m, kdim, f.bitmap, f.lo, f.hi, f.sym, f.nnz, ncols, f.segs, k, f.zsym,
                        f.group_rows, p.rlog2, p.terms_log2, p.rows_per_group, hdr, sums);
 }
 
@@ -381,29 +202,7 @@ static const SggCase kSggCases[] = {SGG_CASE(1), SGG_CASE(2), SGG_CASE(4), SGG_C
 #undef SGG_CASE
 static const CbgCaseNames kSggNames = {true, nullptr, false};
 
-// ------------------------------------------------------------------ checks (host)
-// sg_check's checks at label_bytes 1, then those the group-wise layers make of k and group_rows (the bins of dc included)
-static int sgg_check(const char *fn, int64_t m, int64_t kdim, int64_t ncols, int32_t k, int64_t group_rows)
-{
-    if (k > 256) return fail(NNC_EINVAL, std::string(fn) + ": k outside 1..256 (group codebooks take uint8 labels only)");
-    const int rc = sg_check(fn, m, kdim, ncols, 1, k);
-    if (rc != NNC_OK) return rc;
-    return cb_check_group_rows(fn, kdim, group_rows, k);
-}
-
-// the form: nnz, the size and the alignment of the buffer, the skipped symbols
-static int sgg_check_form(const char *fn, int64_t m, int64_t kdim, int64_t ncols, int64_t nnz, const void *packed, int64_t packed_bytes,
-                          const void *zero_symbols)
-{
-    const std::string f(fn);
-    if (nnz < 0 || nnz > kdim * ncols) return fail(NNC_EINVAL, f + ": nnz outside 0..kdim * ncols");
-    if (packed_bytes < sp_layout(kdim, ncols, 1, nnz).bytes)
-        return fail(NNC_EINVAL, f + ": packed buffer smaller than nnc_cbsp_pack_bytes(kdim, ncols, 1, nnz)");
-    const bool product = m > 0 && kdim > 0 && ncols > 0;
-    if (product && (!packed || !zero_symbols)) return fail(NNC_EINVAL, f + ": packed or zero_symbols is NULL");
-    if (product && reinterpret_cast<uintptr_t>(packed) % 256) return fail(NNC_EINVAL, f + ": packed must be 256-byte aligned");
-    return NNC_OK;
-}
+// (sgg_check, sgg_check_form: nnc_cbspgrad_grouped.hpp)
 
 // ------------------------------------------------------------------ C ABI
 extern "C" int64_t nnc_cbsp_grouped_dx_workspace_bytes(int64_t m, int64_t kdim, int64_t ncols)

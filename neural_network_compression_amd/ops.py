@@ -1163,13 +1163,15 @@ def cbsp_grouped_h16_plan(dtype, m: int, kdim: int, ncols: int, k: int, group_ro
     return _plan(nat.load().nnc_cbsp_grouped_h16_plan, nat.CBSP_GROUPED_H16_PLAN_FIELDS, _h16_dt(dtype), m, kdim, ncols, k, group_rows, cus)
 
 
-def _grouped_sparse_grad_args(who: str, g, codes, centers=None):
-    """The checks of the grouped sparse backward ops: float32 g of (..., ncols) rows, a GroupedSparseCodes, and (dx) float32 centers
-    (G, codes.k) -> (lead, m) of g."""
-    if isinstance(g, torch.Tensor) and g.dtype in _H16_DT:
-        raise TypeError(f"{who} takes float32 activations, got {g.dtype}: the backward pass from the grouped bitmap-sparse form has no bfloat16 / "
-                        "float16 path (use the byte or packed forms, ops.grouped_codebook_linear(half_inputs=True))")
-    _require_cuda(g, "g", torch.float32)
+def _grouped_sparse_grad_args(who: str, g, codes, centers=None, half_inputs: bool = False):
+    """The checks of the grouped sparse backward ops: float32 g (bfloat16 / float16 too with ``half_inputs``) of (..., ncols) rows, a
+    GroupedSparseCodes, and (dx) float32 centers (G, codes.k) -> (lead, m) of g."""
+    half = isinstance(g, torch.Tensor) and g.dtype in _H16_DT
+    if half and not half_inputs:
+        raise TypeError(f"{who} takes float32 activations, got {g.dtype}: pass half_inputs=True to run the backward pass from the grouped "
+                        "bitmap-sparse form on bfloat16 and float16 inputs (or use the byte or packed forms, "
+                        "ops.grouped_codebook_linear(half_inputs=True))")
+    _require_cuda(g, "g", g.dtype if half else torch.float32)
     if not isinstance(codes, GroupedSparseCodes):
         raise TypeError("codes must be a GroupedSparseCodes (ops.pack_grouped_sparse_codes)")
     _check_group_rows(codes.kdim, codes.group_rows)
@@ -1180,17 +1182,34 @@ def _grouped_sparse_grad_args(who: str, g, codes, centers=None):
     return _rows(g, "g", codes.ncols)
 
 
-def grouped_sparse_codebook_matmul_dx(g: torch.Tensor, codes: GroupedSparseCodes, centers: torch.Tensor) -> torch.Tensor:
+def grouped_sparse_codebook_matmul_dx(g: torch.Tensor, codes: GroupedSparseCodes, centers: torch.Tensor, out_dtype=None,
+                                      half_inputs: bool = False) -> torch.Tensor:
     """dx = g @ W^T from the bitmap-sparse form of a group-wise layer (include/nnc_cbspgrad_grouped.h, nnc_cbsp_grouped_dx_f32;
     DESIGN.md section 32): with q = i // group_rows, dx[., i] = c_{z_q} * sum_o g[., o] + the stored weights' g[., o] *
     (centers[q][label] - c_{z_q}), the input gradient of grouped_sparse_codebook_matmul with its conventions (a group with c_{z_q} == 0
     drops the rank-1 term, and its skipped weights form no product).  g: float32 (..., ncols); centers: float32 (G, codes.k).
     Returns float32 (..., kdim).  The columns of group q are, bit for bit, those sparse_codebook_matmul_dx gives on the same buffer
-    read as ``SparseCodes(codes.buf, kdim, ncols, k, z_q, 1, codes.nnz)`` with the one table ``centers[q]``.  No host read."""
-    lead, m = _grouped_sparse_grad_args("grouped_sparse_codebook_matmul_dx", g, codes, centers)
+    read as ``SparseCodes(codes.buf, kdim, ncols, k, z_q, 1, codes.nnz)`` with the one table ``centers[q]``.  No host read.
+    With ``half_inputs=True`` a bfloat16 or float16 g takes nnc_cbsp_grouped_dx_h16 (include/nnc_cbspgrad_grouped_h16.h; DESIGN.md
+    section 35): centers stay float32 and are rounded to g's dtype as the forward rounds them; the result has ``out_dtype``: None (g's
+    dtype, the float32 value rounded once) or torch.float32.  Above 16 rows of g it is grouped_codebook_matmul_dx on
+    ``codes.to_dense()`` bit for bit; up to 16 rows, with float32 out, this op's float32 result on ``g.float()`` and
+    ``centers.to(g.dtype).float()`` bit for bit.  Without the keyword a half g raises ``TypeError``, as it always did."""
+    lead, m = _grouped_sparse_grad_args("grouped_sparse_codebook_matmul_dx", g, codes, centers, half_inputs)
     _one_device("g, codes and centers", g, codes.buf, codes.zero_symbols, centers)
+    if out_dtype not in (None, torch.float32):
+        raise TypeError(f"out_dtype must be None or torch.float32, got {out_dtype}")
     L = nat.load()
     kdim, ncols = codes.kdim, codes.ncols
+    if g.dtype in _H16_DT:
+        dx_dtype = g.dtype if out_dtype is None else out_dtype
+        dx = torch.empty(lead + (kdim,), dtype=dx_dtype, device=g.device)
+        ws_bytes = int(L.nnc_cbsp_grouped_dx_h16_workspace_bytes(m, kdim, ncols))
+        ws = _workspace(ws_bytes, g.device)
+        nat.check(L.nnc_cbsp_grouped_dx_h16(_ptr(g), _H16_DT[g.dtype], m, kdim, _ptr(codes.buf), codes.buf.numel(), ncols, _ptr(codes.zero_symbols),
+                                            codes.nnz, _ptr(centers), codes.k, codes.group_rows, _ptr(dx), _H16_DT.get(dx_dtype, nat.DT_F32), _ptr(ws),
+                                            ws_bytes, _stream(g)))
+        return dx
     dx = torch.empty(lead + (kdim,), dtype=torch.float32, device=g.device)
     ws_bytes = int(L.nnc_cbsp_grouped_dx_workspace_bytes(m, kdim, ncols))
     ws = _workspace(ws_bytes, g.device)
@@ -1199,20 +1218,35 @@ def grouped_sparse_codebook_matmul_dx(g: torch.Tensor, codes: GroupedSparseCodes
     return dx
 
 
-def grouped_sparse_codebook_centroid_grad(x: torch.Tensor, g: torch.Tensor, codes: GroupedSparseCodes, dtype=torch.float64) -> torch.Tensor:
+def grouped_sparse_codebook_centroid_grad(x: torch.Tensor, g: torch.Tensor, codes: GroupedSparseCodes, dtype=torch.float64,
+                                          half_inputs: bool = False) -> torch.Tensor:
     """dc[q, j] = sum over the (i, o) of group q whose label is j of (x^T g)[i, o], the skipped positions counted under the group's
     zero symbol (include/nnc_cbspgrad_grouped.h, nnc_cbsp_grouped_dc_f32): bit for bit grouped_codebook_centroid_grad(x, g,
     codes.to_dense(), ...), the indices never unpacked and dW never written.  x: float32 (..., kdim), g: float32 (..., ncols) with the
-    same leading shape.  Returns ``dtype`` (float64 or float32) (G, codes.k).  No host read."""
-    if isinstance(x, torch.Tensor) and x.dtype in _H16_DT:
-        raise TypeError(f"grouped_sparse_codebook_centroid_grad takes float32 activations, got {x.dtype}: the backward pass from the grouped "
-                        "bitmap-sparse form has no bfloat16 / float16 path")
-    lead, m = _grouped_sparse_grad_args("grouped_sparse_codebook_centroid_grad", g, codes)
-    _require_cuda(x, "x", torch.float32)
+    same leading shape.  Returns ``dtype`` (float64 or float32) (G, codes.k).  No host read.
+    With ``half_inputs=True`` x and g both bfloat16 or both float16 take nnc_cbsp_grouped_dc_h16 (include/nnc_cbspgrad_grouped_h16.h;
+    DESIGN.md section 35), with the same identity against the half grouped_codebook_centroid_grad at every number of rows.  Without
+    the keyword a half x or g raises ``TypeError``, as it always did."""
+    half = isinstance(x, torch.Tensor) and x.dtype in _H16_DT
+    if not half_inputs:   # the refusals in the order they always had: a half x, then (with the checks of g) a half g
+        if half:
+            raise TypeError(f"grouped_sparse_codebook_centroid_grad takes float32 activations, got {x.dtype}: pass half_inputs=True to run the "
+                            "backward pass from the grouped bitmap-sparse form on bfloat16 and float16 inputs")
+    elif isinstance(x, torch.Tensor) and isinstance(g, torch.Tensor) and x.dtype != g.dtype and (half or g.dtype in _H16_DT):
+        raise TypeError(f"x and g must have one dtype, got {x.dtype} and {g.dtype}")
+    lead, m = _grouped_sparse_grad_args("grouped_sparse_codebook_centroid_grad", g, codes, None, half_inputs)
+    _require_cuda(x, "x", x.dtype if half else torch.float32)
     kdim, ncols, k = codes.kdim, codes.ncols, codes.k
     _dc_args(x, lead, kdim, "x, g and codes", codes.buf, g, dtype)
     L = nat.load()
     dc = torch.empty((max(codes.groups, 1), k), dtype=dtype, device=x.device)
+    if half:
+        ws_bytes = int(L.nnc_cbsp_grouped_dc_h16_workspace_bytes(m, kdim, ncols, k, codes.group_rows))
+        ws = _workspace(ws_bytes, x.device)
+        nat.check(L.nnc_cbsp_grouped_dc_h16(_ptr(x), _ptr(g), _H16_DT[x.dtype], m, kdim, _ptr(codes.buf), codes.buf.numel(), ncols,
+                                            _ptr(codes.zero_symbols), codes.nnz, k, codes.group_rows, _ptr(dc), 1 if dtype == torch.float64 else 0,
+                                            _ptr(ws), ws_bytes, _stream(x)))
+        return dc
     ws_bytes = int(L.nnc_cbsp_grouped_dc_workspace_bytes(m, kdim, ncols, k, codes.group_rows))
     ws = _workspace(ws_bytes, x.device)
     nat.check(L.nnc_cbsp_grouped_dc_f32(_ptr(x), _ptr(g), m, kdim, _ptr(codes.buf), codes.buf.numel(), ncols, _ptr(codes.zero_symbols), codes.nnz, k,
@@ -1232,20 +1266,39 @@ def cbsp_grouped_dc_plan(m: int, kdim: int, ncols: int, k: int, group_rows: int,
     return _plan(nat.load().nnc_cbsp_grouped_dc_plan, nat.CBSPDC_GROUPED_PLAN_FIELDS, m, kdim, ncols, k, group_rows, cus)
 
 
+def cbsp_grouped_dx_h16_plan(dtype, m: int, kdim: int, ncols: int, k: int, group_rows: int, cus: int) -> dict:
+    """Host: the plan nnc_cbsp_grouped_dx_h16 follows for g of ``dtype`` (torch.bfloat16 / torch.float16) on a device with ``cus``
+    compute units (include/nnc_cbspgrad_grouped_h16.h), as a dict keyed by _native.CBSPDX_GROUPED_H16_PLAN_FIELDS.  No device needed."""
+    return _plan(nat.load().nnc_cbsp_grouped_dx_h16_plan, nat.CBSPDX_GROUPED_H16_PLAN_FIELDS, _h16_dt(dtype), m, kdim, ncols, k, group_rows, cus)
+
+
+def cbsp_grouped_dc_h16_plan(dtype, m: int, kdim: int, ncols: int, k: int, group_rows: int, cus: int) -> dict:
+    """Host: the plan nnc_cbsp_grouped_dc_h16 follows for x and g of ``dtype`` (include/nnc_cbspgrad_grouped_h16.h), as a dict keyed by
+    _native.CBSPDC_GROUPED_H16_PLAN_FIELDS.  No device needed."""
+    return _plan(nat.load().nnc_cbsp_grouped_dc_h16_plan, nat.CBSPDC_GROUPED_H16_PLAN_FIELDS, _h16_dt(dtype), m, kdim, ncols, k, group_rows, cus)
+
+
 def grouped_sparse_codebook_linear(x: torch.Tensor, codes: GroupedSparseCodes, centers: torch.Tensor, bias: torch.Tensor | None = None,
-                                   relu: bool = False) -> torch.Tensor:
+                                   relu: bool = False, half_inputs: bool = False) -> torch.Tensor:
     """grouped_sparse_codebook_matmul with gradients for x, centers (G, K) and bias, through the autograd Function of codebook_linear
     (DESIGN.md section 32).  The forward is the same float32 nnc_cbsp_grouped_f32 call (under no_grad the bits of
     grouped_sparse_codebook_matmul); the backward runs grouped_sparse_codebook_matmul_dx only if x needs a gradient and
     grouped_sparse_codebook_centroid_grad (float32) only if centers does, masks a fused ReLU as torch does and sums the bias gradient
-    over the rows.  The indices get no gradient.  No host read.  float32 activations only: a bfloat16 or float16 x raises
-    ``TypeError``."""
+    over the rows.  The indices get no gradient.  No host read.
+    ``half_inputs=True`` lets a bfloat16 or float16 x through: the forward is nnc_cbsp_grouped_h16 with x's
+    dtype out, dx has x's dtype, the gradients of the float32 centers and bias are float32.  Without it a half x raises ``TypeError``
+    as before; a half ``centers`` or ``bias`` always does."""
     if not isinstance(codes, GroupedSparseCodes):
         raise TypeError("codes must be a GroupedSparseCodes (ops.pack_grouped_sparse_codes)")
-    _require_f32_x(x, "grouped_sparse_codebook_linear")
-    return _CodebookLinear.apply(x, codes, centers, bias, bool(relu), codes.kdim, codes.ncols, grouped_sparse_codebook_matmul,
-                                 grouped_sparse_codebook_matmul_dx,
-                                 lambda x2, g2, cd, c: grouped_sparse_codebook_centroid_grad(x2, g2, cd, dtype=torch.float32))
+    if not half_inputs:
+        _require_f32_x(x, "grouped_sparse_codebook_linear")
+    elif isinstance(x, torch.Tensor) and x.dtype in _H16_DT:
+        _require_centers_bias(centers, bias)
+    half_inputs = bool(half_inputs)
+    return _CodebookLinear.apply(x, codes, centers, bias, bool(relu), codes.kdim, codes.ncols,
+                                 lambda x2, cd, c, b, r: grouped_sparse_codebook_matmul(x2, cd, c, b, r, half_inputs=half_inputs),
+                                 lambda g2, cd, c: grouped_sparse_codebook_matmul_dx(g2, cd, c, half_inputs=half_inputs),
+                                 lambda x2, g2, cd, c: grouped_sparse_codebook_centroid_grad(x2, g2, cd, dtype=torch.float32, half_inputs=half_inputs))
 
 
 class PackedCodes:
