@@ -435,6 +435,20 @@ GROUPED_SPARSE_H16_GRAD_SIGNATURES = {
                                         c_void_p, c_i64, c_void_p]),
 }
 
+# name -> (restype, argtypes); every symbol include/nnc_cbwp.h declares (the 5-, 6- and 9-bit split-plane "wide packed" form of the codebook
+# layer, inference only, a header of its own that includes nnc.h).  Required and bound by load() as SIGNATURES are.
+WIDE_PACKED_SIGNATURES = {
+    "nnc_cbwp_pack_bytes": (c_i64, [c_i64, c_i64, c_int]),
+    "nnc_cbwp_pack": (c_int, [c_void_p, c_int, c_i64, c_i64, c_int, c_void_p, c_i64, c_void_p, c_void_p]),
+    "nnc_cbwp_unpack": (c_int, [c_void_p, c_i64, c_int, c_i64, c_i64, c_void_p, c_int, c_void_p]),
+    "nnc_cbwp_workspace_bytes": (c_i64, [c_int, c_i64, c_i64, c_i64, c_int]),
+    "nnc_cbwp_plan": (c_int, [c_int, c_i64, c_i64, c_i64, c_int, c_i32, c_i32, ctypes.POINTER(c_i64)]),
+    "nnc_cbwp": (c_int, [c_void_p, c_int, c_i64, c_i64, c_void_p, c_i64, c_int, c_i64, c_void_p, c_i32, c_void_p, c_i32, c_void_p, c_int, c_void_p, c_i64,
+                         c_void_p]),
+}
+# nnc_cbwp_plan (include/nnc_cbwp.h, NNC_CBWP_P_*)
+CBWP_PLAN_FIELDS = ("path", "vb", "mt", "cols", "base", "planes", "copies", "entries", "splits", "rps", "lds", "col_tiles", "row_tiles", "workspace", "dtype")
+
 # exported only by the diagnostics build (NNC_DIAG=1: libnnc_hip_diag.so, see build.py); bound when present
 DIAG_SIGNATURES = {
     "nnc_debug_set_ablation": (c_int, [c_int]),
@@ -467,7 +481,7 @@ def load():
         L = ctypes.CDLL(path)
     except OSError as e:  # pragma: no cover - depends on the machine
         raise NativeLibraryError(f"cannot load {path}: {e}; there is no CPU fallback") from e
-    for name, (res, args) in list(SIGNATURES.items()) + list(GROUPED_GRAD_SIGNATURES.items()) + list(H16_GRAD_SIGNATURES.items()) + list(GROUPED_PACKED_GRAD_SIGNATURES.items()) + list(SPARSE_H16_SIGNATURES.items()) + list(SPARSE_H16_GRAD_SIGNATURES.items()) + list(PACKED_H16_SIGNATURES.items()) + list(GROUPED_H16_GRAD_SIGNATURES.items()) + list(GROUPED_SPARSE_SIGNATURES.items()) + list(GROUPED_SPARSE_H16_SIGNATURES.items()) + list(GROUPED_SPARSE_GRAD_SIGNATURES.items()) + list(GROUPED_SPARSE_H16_GRAD_SIGNATURES.items()):
+    for name, (res, args) in list(SIGNATURES.items()) + list(GROUPED_GRAD_SIGNATURES.items()) + list(H16_GRAD_SIGNATURES.items()) + list(GROUPED_PACKED_GRAD_SIGNATURES.items()) + list(SPARSE_H16_SIGNATURES.items()) + list(SPARSE_H16_GRAD_SIGNATURES.items()) + list(PACKED_H16_SIGNATURES.items()) + list(GROUPED_H16_GRAD_SIGNATURES.items()) + list(GROUPED_SPARSE_SIGNATURES.items()) + list(GROUPED_SPARSE_H16_SIGNATURES.items()) + list(GROUPED_SPARSE_GRAD_SIGNATURES.items()) + list(GROUPED_SPARSE_H16_GRAD_SIGNATURES.items()) + list(WIDE_PACKED_SIGNATURES.items()):
         try:
             fn = getattr(L, name)
         except AttributeError as e:

@@ -12,6 +12,7 @@ tensor is never rebuilt.  Biases (one value per output column) are decoded once 
     pack_grouped_layers(network, packed=True)                      a deep copy with the grouped layers' indices packed to 2 or 4 bits
     sparsify_grouped_layers(network, sparse=True)                  a deep copy with the grouped layers' indices in the bitmap-sparse form
     smallest_grouped_layers(network)                               a deep copy with every grouped layer in the smallest of its three forms
+    widen_packed_layers(network, wide=True)                        a deep copy with the byte layers of 17 .. 512 centres at 5, 6 or 9 bits per index
     compressed_nbytes(network)                                     resident bytes of the layers' tensors
 
 A pruned layer can instead keep its indices in the bitmap-sparse form (ops.pack_sparse_codes, csrc/nnc_cbsp.hip, DESIGN.md
@@ -823,6 +824,66 @@ class TrainablePackedCompressedConv2D(_Conv2DHalf, _TrainablePackedCodebookLayer
         return cls(kernel_size, cin, pad, codes, labels, centers, bias, bias_codes, activation, half_inputs)
 
 
+class _WidePackedCodebookLayer(_CodesLayer):
+    """The indices in the 5-, 6- or 9-bit split-plane form (ops.WidePackedCodes: its buffer is the module's ``packed`` buffer, DESIGN.md
+    section 36), centers float32[16 < K <= 512], bias float32[ncols] or None.  No kdim * ncols tensor stays resident.  The path
+    follows the input's dtype as in CompressedDense (float32, bfloat16, float16; the output has the input's dtype); centers and bias
+    stay float32.  Inference only."""
+
+    _INDEX = "packed"
+    _product = staticmethod(ops.wide_packed_codebook_matmul)
+
+    def _take_codes(self, codes: ops.WidePackedCodes):
+        self.kdim, self.ncols, self.bits, self.k = codes.kdim, codes.ncols, codes.bits, codes.k
+        self.register_buffer("packed", codes.packed)
+
+    @property
+    def codes(self) -> ops.WidePackedCodes:
+        return ops.WidePackedCodes(self.packed, self.kdim, self.ncols, self.bits, self.k)
+
+
+def _pack_wide(labels, kdim, ncols, k, _option=None):
+    return ops.pack_codes_wide(labels, kdim, ncols, k)
+
+
+class WidePackedCompressedDense(_DenseHalf, _WidePackedCodebookLayer):
+    """Dense run from its codebook and the split-plane form of its (in, out) indices."""
+
+    @classmethod
+    def from_dense(cls, dense, weight_model, bias_model=None) -> "WidePackedCompressedDense":
+        codes = _inference_codes(dense, weight_model, bias_model)
+        kin, kout = dense.kernel.shape
+        return cls.from_codes(kin, kout, *codes, dense.activation)
+
+    @classmethod
+    def from_codes(cls, kdim, ncols, labels, centers, bias, activation) -> "WidePackedCompressedDense":
+        return cls(_pack_wide(labels, kdim, ncols, centers.numel()), centers, bias, activation)
+
+
+class WidePackedCompressedConv2D(_Conv2DHalf, _WidePackedCodebookLayer):
+    """Conv2D (stride 1, NHWC) run from its codebook and the split-plane form of its indices, packed after the rows were put in
+    unfold order (keras_rows_for_unfold); patch chunking and the empty batch as CompressedConv2D."""
+
+    def __init__(self, kernel_size: int, cin: int, pad: int, codes: ops.WidePackedCodes, centers: torch.Tensor, bias: torch.Tensor | None,
+                 activation=None):
+        _check_conv_rows(codes, kernel_size, cin)
+        super().__init__(codes, centers, bias, activation)
+        self._set_conv(kernel_size, cin, pad)
+
+    @classmethod
+    def from_conv(cls, conv, weight_model, bias_model=None) -> "WidePackedCompressedConv2D":
+        codes = _inference_codes(conv, weight_model, bias_model)
+        h, cin, cout = _conv_shape(conv)
+        return cls.from_codes(h, cin, cout, conv.pad, *codes, conv.activation)
+
+    @classmethod
+    def from_codes(cls, kernel_size, cin, cout, pad, labels, centers, bias, activation) -> "WidePackedCompressedConv2D":
+        """labels in the Keras order of the (h, w, in, out) kernel."""
+        ops.wide_packed_bits(centers.numel())   # a codebook that does not fit raises before the unfold
+        codes = _unfold_then_pack(_pack_wide, kernel_size, cin, cout, labels, centers.numel(), None)
+        return cls(kernel_size, cin, pad, codes, centers, bias, activation)
+
+
 class GroupedPackedCompressedDense(_DenseHalf, _PackedForm, _InferenceLayer):
     """Dense run from one codebook per block of ``group_rows`` input rows and the 2- or 4-bit packed form of its (in, out) indices
     (ops.grouped_packed_codebook_matmul): packed (the ordinary packed buffer of the whole index matrix),
@@ -1454,6 +1515,31 @@ def smallest_grouped_layers(network: nn.Module, half_inputs: bool = False) -> nn
         best = made if made.nbytes() < best.nbytes() else best
         if best is not layer:
             setattr(out, name, best)
+    return out
+
+
+def widen_packed_layers(network: nn.Module, wide=True) -> nn.Module:
+    """A deep copy of a compressed ``network`` (compress_network, Trainer.compressed_network() or load_network) whose CompressedDense /
+    CompressedConv2D layers of 16 < K <= 512 centres keep their indices in the 5-, 6- or 9-bit split-plane form
+    (WidePackedCompressedDense / WidePackedCompressedConv2D).  ``wide``: True (every such layer) or "auto" (a
+    layer only where the new form holds fewer resident bytes; on equal bytes the byte form stays); anything else is a ValueError.
+    Grouped, sparse, packed and trainable layers and all others are left as they are.  A replaced layer has the same weights; its
+    sums run in another order (within the float bound of section 36, the same bits on exact data)."""
+    if wide is not True and wide != "auto":
+        raise ValueError(f"wide must be True or 'auto', got {wide!r}")
+    out = copy.deepcopy(network)
+    for name, layer in out.get_config().items():
+        k = layer.centers.numel() if type(layer) in (CompressedDense, CompressedConv2D) else 0
+        if not 16 < k <= 512:
+            continue
+        if wide == "auto" and ops.wide_packed_nbytes(layer.kdim, layer.ncols, ops.wide_packed_bits(k)) >= _tensor_bytes(layer.labels):
+            continue
+        codes = ops.pack_codes_wide(layer.labels, layer.kdim, layer.ncols, k)   # (a Conv2D layer's labels are in unfold order already)
+        if type(layer) is CompressedDense:
+            made = WidePackedCompressedDense(codes, layer.centers, layer.bias, layer.activation)
+        else:
+            made = WidePackedCompressedConv2D(layer.kernel_size, layer.cin, layer.pad, codes, layer.centers, layer.bias, layer.activation)
+        setattr(out, name, made)
     return out
 
 

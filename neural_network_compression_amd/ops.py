@@ -1712,6 +1712,113 @@ def grouped_packed_codebook_linear(x: torch.Tensor, codes: PackedCodes, centers:
         lambda x2, g2, cd, c: grouped_packed_codebook_centroid_grad(x2, g2, cd, group_rows, dtype=torch.float32))
 
 
+# ------------------------------------------------------------------ the 5-, 6- and 9-bit split-plane ("wide packed") form
+class WidePackedCodes:
+    """The 5-, 6- or 9-bit split-plane form of one (kdim, ncols) index matrix of a codebook of 16 < ``k`` <= 512 centres
+    (include/nnc_cbwp.h): ``packed``, one 256-byte aligned uint8 device buffer of kdim rows, each a base part
+    of 4- or 8-bit fields followed by one or two bit planes, and the metadata a product needs."""
+
+    def __init__(self, packed: torch.Tensor, kdim: int, ncols: int, bits: int, k: int):
+        self.packed, self.kdim, self.ncols, self.bits, self.k = packed, int(kdim), int(ncols), int(bits), int(k)
+
+    @property
+    def device(self):
+        return self.packed.device
+
+    @property
+    def nbytes(self) -> int:
+        """Resident bytes of the form (the buffer)."""
+        return self.packed.numel()
+
+    def to_dense(self) -> torch.Tensor:
+        """The kdim * ncols labels again (uint8 at 5 and 6 bits, int16 at 9), by nnc_cbwp_unpack."""
+        dtype, lb = (torch.uint8, 1) if self.bits <= 8 else (torch.int16, 2)
+        out = torch.empty(self.kdim * self.ncols, dtype=dtype, device=self.packed.device)
+        nat.check(nat.load().nnc_cbwp_unpack(_ptr(self.packed), self.nbytes, self.bits, self.kdim, self.ncols, _ptr(out), lb, _stream(self.packed)))
+        return out
+
+    def __repr__(self):
+        return f"WidePackedCodes(kdim={self.kdim}, ncols={self.ncols}, bits={self.bits}, k={self.k}, nbytes={self.nbytes})"
+
+
+def wide_packed_bits(k: int) -> int:
+    """The width the split-plane form takes for a codebook of ``k`` centres: the smallest of 5, 6 and 9 that holds k.  ValueError
+    for k <= 16 (the 2- / 4-bit packed form serves it: ops.packed_bits) and for k > 512."""
+    k = int(k)
+    if k <= 16:
+        raise ValueError(f"k = {k} centres fit 4-bit indices: use the packed form (ops.pack_codes)")
+    if k > 512:
+        raise ValueError(f"k = {k} centres do not fit 9-bit indices (the wide packed form holds at most 512; use the byte form)")
+    return 5 if k <= 32 else (6 if k <= 64 else 9)
+
+
+def wide_packed_nbytes(kdim: int, ncols: int, bits: int) -> int:
+    """Host: the bytes of the split-plane form of a (kdim, ncols) index matrix (nnc_cbwp_pack_bytes)."""
+    return int(nat.load().nnc_cbwp_pack_bytes(int(kdim), int(ncols), int(bits)))
+
+
+def pack_codes_wide(labels: torch.Tensor, kdim: int, ncols: int, k: int) -> WidePackedCodes:
+    """The (kdim, ncols) labels (uint8 / 16-bit, any storage offset) of a codebook of 16 < ``k`` <= 512 centres -> WidePackedCodes
+    on their device (nnc_cbwp_pack: one pass, no per-weight temporary), at wide_packed_bits(k).  ValueError (before any launch)
+    for a k outside that range, and for a label >= 2^bits (one host read of the pack's count)."""
+    kdim, ncols, k = int(kdim), int(ncols), int(k)
+    bits = wide_packed_bits(k)
+    _require_cuda(labels, "labels")
+    lb = _label_bytes(labels)
+    if labels.numel() != kdim * ncols:
+        raise ValueError(f"labels must hold kdim * ncols = {kdim * ncols} indices, got {labels.numel()}")
+    labels = labels.reshape(-1)
+    L = nat.load()
+    total = int(L.nnc_cbwp_pack_bytes(kdim, ncols, bits))
+    if total == 0 and kdim * ncols > 0:
+        raise ValueError(f"no wide packed form for a {kdim} x {ncols} matrix")
+    buf = _aligned_bytes(total, labels.device)
+    bad = torch.empty(1, dtype=torch.int32, device=labels.device)
+    nat.check(L.nnc_cbwp_pack(_ptr(labels), lb, kdim, ncols, bits, _ptr(buf), total, _ptr(bad), _stream(labels)))
+    nbad = int(bad.item())
+    if nbad:
+        raise ValueError(f"{nbad} labels are >= 2^{bits}: they do not fit the wide packed form")
+    return WidePackedCodes(buf, kdim, ncols, bits, k)
+
+
+def wide_packed_codebook_matmul(x: torch.Tensor, codes: WidePackedCodes, centers: torch.Tensor, bias: torch.Tensor | None = None,
+                                relu: bool = False, out_dtype=None) -> torch.Tensor:
+    """y = x @ W + bias (then ReLU) with W[i, o] = centers[label (i, o)] read from the 5-, 6- or 9-bit split-plane indices
+    (include/nnc_cbwp.h, nnc_cbwp): codebook_matmul on the unpacked labels from 5/8, 6/8 or 9/16 of the index bytes.  x: float32,
+    bfloat16 or float16 (..., kdim); centers: float32[codes.k]; bias: float32[ncols] or None.  With half x every centre is rounded to
+    x's dtype as ``centers.to(x.dtype)`` does, the products are exact and the sums float32.  The result has ``out_dtype``: None (x's
+    dtype, the float32 value rounded once) or torch.float32.  A label >= codes.k contributes 0.  Inference only, as codebook_matmul."""
+    if not isinstance(x, torch.Tensor) or x.dtype not in _X_DT:
+        raise TypeError(f"x must be a float32, bfloat16 or float16 tensor, got {getattr(x, 'dtype', type(x))}")
+    _require_cuda(x, "x")
+    if out_dtype not in (None, torch.float32):
+        raise TypeError(f"out_dtype must be None ({x.dtype}) or torch.float32, got {out_dtype}")
+    y_dtype = x.dtype if out_dtype is None else out_dtype
+    if not isinstance(codes, WidePackedCodes):
+        raise TypeError("codes must be a WidePackedCodes (ops.pack_codes_wide)")
+    _require_centers_bias(centers, bias)
+    _inference_only("wide_packed_codebook_matmul", "x, codes, centers and bias", x, codes.packed, centers, bias)
+    kdim, ncols = codes.kdim, codes.ncols
+    lead, m = _rows(x, "x", kdim)
+    if centers.numel() != codes.k:
+        raise ValueError(f"centers must hold k = {codes.k} values, got {centers.numel()}")
+    y = _empty_y(x, lead, ncols, bias, y_dtype)
+    L = nat.load()
+    ws_bytes = int(L.nnc_cbwp_workspace_bytes(_X_DT[x.dtype], m, kdim, ncols, codes.bits))
+    ws = _workspace(ws_bytes, x.device)
+    nat.check(L.nnc_cbwp(_ptr(x), _X_DT[x.dtype], m, kdim, _ptr(codes.packed), codes.nbytes, codes.bits, ncols, _ptr(centers), codes.k, _ptr(bias),
+                         1 if relu else 0, _ptr(y), _X_DT[y_dtype], _ptr(ws), ws_bytes, _stream(x)))
+    return y
+
+
+def cbwp_plan(dtype, m: int, kdim: int, ncols: int, bits: int, k: int, cus: int) -> dict:
+    """Host: the plan nnc_cbwp follows for x of ``dtype`` (torch.float32 / bfloat16 / float16) on a device with ``cus`` compute units
+    (include/nnc_cbwp.h, nnc_cbwp_plan), as a dict keyed by _native.CBWP_PLAN_FIELDS.  No device needed."""
+    if dtype not in _X_DT:
+        raise TypeError(f"dtype must be torch.float32, torch.bfloat16 or torch.float16, got {dtype}")
+    return _plan(nat.load().nnc_cbwp_plan, nat.CBWP_PLAN_FIELDS, _X_DT[dtype], m, kdim, ncols, bits, k, cus)
+
+
 def huffman_lengths(counts) -> tuple:
     """Host: (lengths uint8[k], hist int64[max_len+1], total_bits) from an index histogram."""
     L = nat.load()
