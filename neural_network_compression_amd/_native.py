@@ -449,6 +449,20 @@ WIDE_PACKED_SIGNATURES = {
 # nnc_cbwp_plan (include/nnc_cbwp.h, NNC_CBWP_P_*)
 CBWP_PLAN_FIELDS = ("path", "vb", "mt", "cols", "base", "planes", "copies", "entries", "splits", "rps", "lds", "col_tiles", "row_tiles", "workspace", "dtype")
 
+# name -> (restype, argtypes); every symbol include/nnc_cbwpgrad.h declares (the backward pass of the split-plane form, a header of its own
+# that includes nnc_cbwp.h).  Required and bound by load() as SIGNATURES are.
+WIDE_PACKED_GRAD_SIGNATURES = {
+    "nnc_cbwp_dx_workspace_bytes": (c_i64, [c_int, c_i64, c_i64, c_i64, c_int]),
+    "nnc_cbwp_dx_plan": (c_int, [c_int, c_i64, c_i64, c_i64, c_int, c_i32, c_i32, ctypes.POINTER(c_i64)]),
+    "nnc_cbwp_dx": (c_int, [c_void_p, c_int, c_i64, c_i64, c_void_p, c_i64, c_int, c_i64, c_void_p, c_i32, c_void_p, c_int, c_void_p, c_i64, c_void_p]),
+    "nnc_cbwp_dc_workspace_bytes": (c_i64, [c_int, c_i64, c_i64, c_i64, c_int, c_i32]),
+    "nnc_cbwp_dc_plan": (c_int, [c_int, c_i64, c_i64, c_i64, c_int, c_i32, c_i32, ctypes.POINTER(c_i64)]),
+    "nnc_cbwp_dc": (c_int, [c_void_p, c_void_p, c_int, c_i64, c_i64, c_void_p, c_i64, c_int, c_i64, c_i32, c_void_p, c_i32, c_void_p, c_i64, c_void_p]),
+}
+# nnc_cbwp_dx_plan / nnc_cbwp_dc_plan (include/nnc_cbwpgrad.h, NNC_CBWPDX_P_* / NNC_CBWPDC_P_*)
+CBWPDX_PLAN_FIELDS = ("path", "vb", "mt", "cols", "base", "planes", "copies", "entries", "splits", "cps", "lds", "col_tiles", "row_tiles", "workspace", "dtype")
+CBWPDC_PLAN_FIELDS = ("path", "vb", "mt", "cols", "base", "planes", "copies", "splits", "rps", "lds", "col_tiles", "row_tiles", "terms_log2", "workspace", "dtype")
+
 # exported only by the diagnostics build (NNC_DIAG=1: libnnc_hip_diag.so, see build.py); bound when present
 DIAG_SIGNATURES = {
     "nnc_debug_set_ablation": (c_int, [c_int]),
@@ -481,7 +495,7 @@ def load():
         L = ctypes.CDLL(path)
     except OSError as e:  # pragma: no cover - depends on the machine
         raise NativeLibraryError(f"cannot load {path}: {e}; there is no CPU fallback") from e
-    for name, (res, args) in list(SIGNATURES.items()) + list(GROUPED_GRAD_SIGNATURES.items()) + list(H16_GRAD_SIGNATURES.items()) + list(GROUPED_PACKED_GRAD_SIGNATURES.items()) + list(SPARSE_H16_SIGNATURES.items()) + list(SPARSE_H16_GRAD_SIGNATURES.items()) + list(PACKED_H16_SIGNATURES.items()) + list(GROUPED_H16_GRAD_SIGNATURES.items()) + list(GROUPED_SPARSE_SIGNATURES.items()) + list(GROUPED_SPARSE_H16_SIGNATURES.items()) + list(GROUPED_SPARSE_GRAD_SIGNATURES.items()) + list(GROUPED_SPARSE_H16_GRAD_SIGNATURES.items()) + list(WIDE_PACKED_SIGNATURES.items()):
+    for name, (res, args) in list(SIGNATURES.items()) + list(GROUPED_GRAD_SIGNATURES.items()) + list(H16_GRAD_SIGNATURES.items()) + list(GROUPED_PACKED_GRAD_SIGNATURES.items()) + list(SPARSE_H16_SIGNATURES.items()) + list(SPARSE_H16_GRAD_SIGNATURES.items()) + list(PACKED_H16_SIGNATURES.items()) + list(GROUPED_H16_GRAD_SIGNATURES.items()) + list(GROUPED_SPARSE_SIGNATURES.items()) + list(GROUPED_SPARSE_H16_SIGNATURES.items()) + list(GROUPED_SPARSE_GRAD_SIGNATURES.items()) + list(GROUPED_SPARSE_H16_GRAD_SIGNATURES.items()) + list(WIDE_PACKED_SIGNATURES.items()) + list(WIDE_PACKED_GRAD_SIGNATURES.items()):
         try:
             fn = getattr(L, name)
         except AttributeError as e:

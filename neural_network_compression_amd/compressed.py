@@ -824,14 +824,12 @@ class TrainablePackedCompressedConv2D(_Conv2DHalf, _TrainablePackedCodebookLayer
         return cls(kernel_size, cin, pad, codes, labels, centers, bias, bias_codes, activation, half_inputs)
 
 
-class _WidePackedCodebookLayer(_CodesLayer):
-    """The indices in the 5-, 6- or 9-bit split-plane form (ops.WidePackedCodes: its buffer is the module's ``packed`` buffer, DESIGN.md
-    section 36), centers float32[16 < K <= 512], bias float32[ncols] or None.  No kdim * ncols tensor stays resident.  The path
-    follows the input's dtype as in CompressedDense (float32, bfloat16, float16; the output has the input's dtype); centers and bias
-    stay float32.  Inference only."""
+class _WidePackedForm:
+    """What the inference and the trainable wide layers keep of an ops.WidePackedCodes: its buffer as the module's ``packed`` buffer
+    and its metadata as attributes, from which ``codes`` is the same WidePackedCodes again."""
 
     _INDEX = "packed"
-    _product = staticmethod(ops.wide_packed_codebook_matmul)
+    _product, _linear = staticmethod(ops.wide_packed_codebook_matmul), staticmethod(ops.wide_packed_codebook_linear)
 
     def _take_codes(self, codes: ops.WidePackedCodes):
         self.kdim, self.ncols, self.bits, self.k = codes.kdim, codes.ncols, codes.bits, codes.k
@@ -840,6 +838,13 @@ class _WidePackedCodebookLayer(_CodesLayer):
     @property
     def codes(self) -> ops.WidePackedCodes:
         return ops.WidePackedCodes(self.packed, self.kdim, self.ncols, self.bits, self.k)
+
+
+class _WidePackedCodebookLayer(_WidePackedForm, _CodesLayer):
+    """The indices in the 5-, 6- or 9-bit split-plane form (ops.WidePackedCodes: its buffer is the module's ``packed`` buffer, DESIGN.md
+    section 36), centers float32[16 < K <= 512], bias float32[ncols] or None.  No kdim * ncols tensor stays resident.  The path
+    follows the input's dtype as in CompressedDense (float32, bfloat16, float16; the output has the input's dtype); centers and bias
+    stay float32.  Inference only."""
 
 
 def _pack_wide(labels, kdim, ncols, k, _option=None):
@@ -882,6 +887,52 @@ class WidePackedCompressedConv2D(_Conv2DHalf, _WidePackedCodebookLayer):
         ops.wide_packed_bits(centers.numel())   # a codebook that does not fit raises before the unfold
         codes = _unfold_then_pack(_pack_wide, kernel_size, cin, cout, labels, centers.numel(), None)
         return cls(kernel_size, cin, pad, codes, centers, bias, activation)
+
+
+class _TrainableWidePackedCodebookLayer(_WidePackedForm, _TrainableCodesLayer):
+    """The indices in the split-plane form (the ``packed`` buffer, as _WidePackedCodebookLayer) with the centres, counts and bias of
+    _TrainableCentres; the forward goes through ops.wide_packed_codebook_linear, whose backward forms dx and the centroid gradient
+    from the packed rows (csrc/nnc_cbwpgrad.hip).  ``counts`` is taken from the labels before packing, so
+    kernel_sq_sum() is the byte trainable layer's bit for bit.  No kdim * ncols tensor stays resident.  The path follows the input's
+    dtype, as in the inference wide layers: a half input gives a half output and input gradient; the centres, the bias and their
+    gradients stay float32."""
+
+
+class TrainableWidePackedCompressedDense(_DenseHalf, _TrainableWidePackedCodebookLayer):
+    """WidePackedCompressedDense with trainable centres (ops.wide_packed_codebook_linear)."""
+
+    @classmethod
+    def from_dense(cls, dense, weight_model, bias_model=None) -> "TrainableWidePackedCompressedDense":
+        kin, kout = dense.kernel.shape
+        return cls.from_codes(kin, kout, *_trainable_codes(dense, weight_model, bias_model), dense.activation)
+
+    @classmethod
+    def from_codes(cls, kdim, ncols, labels, centers, bias=None, bias_codes=None, activation=None) -> "TrainableWidePackedCompressedDense":
+        return cls(_pack_wide(labels, kdim, ncols, centers.numel()), labels, centers, bias, bias_codes, activation)
+
+
+class TrainableWidePackedCompressedConv2D(_Conv2DHalf, _TrainableWidePackedCodebookLayer):
+    """WidePackedCompressedConv2D with trainable centres: the patches (chunked as CompressedConv2D) through
+    ops.wide_packed_codebook_linear; autograd carries the patch gradients back through the unfold."""
+
+    def __init__(self, kernel_size: int, cin: int, pad: int, codes: ops.WidePackedCodes, labels: torch.Tensor, centers: torch.Tensor, bias=None,
+                 bias_codes=None, activation=None):
+        _check_conv_rows(codes, kernel_size, cin)
+        super().__init__(codes, labels, centers, bias, bias_codes, activation)
+        self._set_conv(kernel_size, cin, pad)
+
+    @classmethod
+    def from_conv(cls, conv, weight_model, bias_model=None) -> "TrainableWidePackedCompressedConv2D":
+        h, cin, cout = _conv_shape(conv)
+        return cls.from_codes(h, cin, cout, conv.pad, *_trainable_codes(conv, weight_model, bias_model), conv.activation)
+
+    @classmethod
+    def from_codes(cls, kernel_size, cin, cout, pad, labels, centers, bias=None, bias_codes=None,
+                   activation=None) -> "TrainableWidePackedCompressedConv2D":
+        """labels in the Keras order of the (h, w, in, out) kernel (the counts are the same in either order)."""
+        ops.wide_packed_bits(centers.numel())   # a codebook that does not fit raises before the unfold
+        codes = _unfold_then_pack(_pack_wide, kernel_size, cin, cout, labels, centers.numel(), None)
+        return cls(kernel_size, cin, pad, codes, labels, centers, bias, bias_codes, activation)
 
 
 class GroupedPackedCompressedDense(_DenseHalf, _PackedForm, _InferenceLayer):
@@ -1518,24 +1569,35 @@ def smallest_grouped_layers(network: nn.Module, half_inputs: bool = False) -> nn
     return out
 
 
-def widen_packed_layers(network: nn.Module, wide=True) -> nn.Module:
+def widen_packed_layers(network: nn.Module, wide=True, *, trainable=False) -> nn.Module:
     """A deep copy of a compressed ``network`` (compress_network, Trainer.compressed_network() or load_network) whose CompressedDense /
     CompressedConv2D layers of 16 < K <= 512 centres keep their indices in the 5-, 6- or 9-bit split-plane form
     (WidePackedCompressedDense / WidePackedCompressedConv2D).  ``wide``: True (every such layer) or "auto" (a
     layer only where the new form holds fewer resident bytes; on equal bytes the byte form stays); anything else is a ValueError.
-    Grouped, sparse, packed and trainable layers and all others are left as they are.  A replaced layer has the same weights; its
-    sums run in another order (within the float bound of section 36, the same bits on exact data)."""
+    ``trainable=True`` widens the TrainableCompressedDense / TrainableCompressedConv2D layers of such a codebook too
+    (TrainableWidePackedCompressedDense / TrainableWidePackedCompressedConv2D, section 37): they keep their centres, counts, bias
+    and bias codes and train from the packed rows.  Grouped, sparse, packed and, by default, trainable layers and all others are left
+    as they are.  A replaced layer has the same weights; its sums run in another order (within the float bound of section 36, the
+    same bits on exact data)."""
     if wide is not True and wide != "auto":
         raise ValueError(f"wide must be True or 'auto', got {wide!r}")
+    kinds = (CompressedDense, CompressedConv2D) + ((TrainableCompressedDense, TrainableCompressedConv2D) if trainable else ())
     out = copy.deepcopy(network)
     for name, layer in out.get_config().items():
-        k = layer.centers.numel() if type(layer) in (CompressedDense, CompressedConv2D) else 0
+        k = layer.centers.numel() if type(layer) in kinds else 0
         if not 16 < k <= 512:
             continue
         if wide == "auto" and ops.wide_packed_nbytes(layer.kdim, layer.ncols, ops.wide_packed_bits(k)) >= _tensor_bytes(layer.labels):
             continue
         codes = ops.pack_codes_wide(layer.labels, layer.kdim, layer.ncols, k)   # (a Conv2D layer's labels are in unfold order already)
-        if type(layer) is CompressedDense:
+        if isinstance(layer, _TrainableCentres):
+            bias_codes = None if layer.bias_centers is None else (layer.bias_centers, layer.bias_labels)
+            tail = (codes, layer.labels, layer.centers, layer.bias, bias_codes, layer.activation)
+            if type(layer) is TrainableCompressedDense:
+                made = TrainableWidePackedCompressedDense(*tail)
+            else:
+                made = TrainableWidePackedCompressedConv2D(layer.kernel_size, layer.cin, layer.pad, *tail)
+        elif type(layer) is CompressedDense:
             made = WidePackedCompressedDense(codes, layer.centers, layer.bias, layer.activation)
         else:
             made = WidePackedCompressedConv2D(layer.kernel_size, layer.cin, layer.pad, codes, layer.centers, layer.bias, layer.activation)

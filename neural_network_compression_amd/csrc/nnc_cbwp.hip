@@ -116,9 +116,6 @@ static int wp_check_labels(const char *fn, const void *labels, int label_bytes, 
 
 static int wp_grid(long long dwords) { return (int)std::max(1LL, std::min(cdiv(dwords, 256), 65536LL)); }
 
-// the one place that turns `bits` into <BASE, PLANES>
-#define WP_BY_BITS(bits, CALL) ((bits) == 5 ? CALL(4, 1) : (bits) == 6 ? CALL(4, 2) : CALL(8, 1))
-
 extern "C" int nnc_cbwp_pack(const void *labels, int label_bytes, int64_t kdim, int64_t ncols, int bits, void *packed, int64_t packed_bytes,
                              uint32_t *bad_count_dev, void *stream)
 {
@@ -159,23 +156,6 @@ extern "C" int nnc_cbwp_unpack(const void *packed, int64_t packed_bytes, int bit
 }
 
 // ------------------------------------------------------------------ skinny: m <= 16
-// the bits of `d` selected by `mask` at bit `from`, moved to bit `to` (both compile-time constants behind the unrolled loops)
-__device__ __forceinline__ uint32_t wp_move(uint32_t d, int from, int to, uint32_t mask)
-{
-    return (from >= to ? d >> (from - to) : d << (to - from)) & (mask << to);
-}
-
-// a lane's E plane bits: a nibble (E = 4: the lane's half of the byte), a byte, two bytes or a dword of the plane; `p` is the
-// plane's byte that holds the lane's first column, aligned to the width of the load
-template <int E>
-__device__ __forceinline__ uint32_t wp_plane_load(const unsigned char *p, int lane)
-{
-    if constexpr (E == 4) return (uint32_t)*p >> ((lane & 1) * 4);
-    else if constexpr (E == 8) return *p;
-    else if constexpr (E == 16) return *reinterpret_cast<const uint16_t *>(p);
-    else return *reinterpret_cast<const uint32_t *>(p);
-}
-
 // grid (col_tiles, splits), CB_THREADS threads.  `out` is y (direct 1: float32, 2: XT; + bias, ReLU here) or the float32 partials
 // [split][m][ncols] (direct 0).  base_bytes / plane_bytes: the parts of a row (row_bytes = base_bytes + PLANES * plane_bytes).
 template <int BASE, int PLANES, int VB, int MT, typename XT>

@@ -1,5 +1,6 @@
 // nnc_cbwp.hpp -- the host half of the 5-, 6- and 9-bit split-plane ("wide packed") codebook matmul (nnc_cbwp.hip, DESIGN.md
-// section 36): the layout arithmetic and the limits of the form, the argument checks and the plan.  The launch constants, the
+// section 36): the layout arithmetic and the limits of the form, the argument checks and the plan, and, shared with the backward
+// pass (nnc_cbwpgrad.hip, section 37), the <BASE, PLANES> dispatch and the decode of a lane's plane bits.  The launch constants, the
 // per-bank table, the tiles and the split-K combine are nnc_cbmm.hpp's; the aligned row load (pk_load), the accumulator budget
 // (PK_ACC) and the size limit (pk_size_ok) are the packed form's, nnc_cbpk.hpp.
 #pragma once
@@ -119,3 +120,24 @@ static WpPlan wp_plan(int x_dtype, long long m, long long kdim, long long ncols,
 }
 
 static int64_t wp_ws_bytes(const WpPlan &p, long long m, long long ncols) { return p.splits > 1 ? (int64_t)p.splits * m * ncols * 4 : 0; }
+
+// the one place that turns `bits` into <BASE, PLANES>
+#define WP_BY_BITS(bits, CALL) ((bits) == 5 ? CALL(4, 1) : (bits) == 6 ? CALL(4, 2) : CALL(8, 1))
+
+// ------------------------------------------------------------------ the decode the stream kernels of both directions share (device)
+// the bits of `d` selected by `mask` at bit `from`, moved to bit `to` (both compile-time constants behind the unrolled loops)
+__device__ __forceinline__ uint32_t wp_move(uint32_t d, int from, int to, uint32_t mask)
+{
+    return (from >= to ? d >> (from - to) : d << (to - from)) & (mask << to);
+}
+
+// a lane's E plane bits: a nibble (E = 4: the lane's half of the byte), a byte, two bytes or a dword of the plane; `p` is the
+// plane's byte that holds the lane's first column, aligned to the width of the load
+template <int E>
+__device__ __forceinline__ uint32_t wp_plane_load(const unsigned char *p, int lane)
+{
+    if constexpr (E == 4) return (uint32_t)*p >> ((lane & 1) * 4);
+    else if constexpr (E == 8) return *p;
+    else if constexpr (E == 16) return *reinterpret_cast<const uint16_t *>(p);
+    else return *reinterpret_cast<const uint32_t *>(p);
+}

@@ -1819,6 +1819,99 @@ def cbwp_plan(dtype, m: int, kdim: int, ncols: int, bits: int, k: int, cus: int)
     return _plan(nat.load().nnc_cbwp_plan, nat.CBWP_PLAN_FIELDS, _X_DT[dtype], m, kdim, ncols, bits, k, cus)
 
 
+def _wide_codes(codes) -> WidePackedCodes:
+    if not isinstance(codes, WidePackedCodes):
+        raise TypeError("codes must be a WidePackedCodes (ops.pack_codes_wide)")
+    return codes
+
+
+def wide_packed_codebook_matmul_dx(g: torch.Tensor, codes: WidePackedCodes, centers: torch.Tensor, out_dtype=None) -> torch.Tensor:
+    """dx = g @ W^T with W[i, o] = centers[label (i, o)] read from the 5-, 6- or 9-bit split-plane indices (include/nnc_cbwpgrad.h,
+    nnc_cbwp_dx): the input gradient of wide_packed_codebook_matmul with the conventions of codebook_matmul_dx
+    (a label >= k reads 0; the padding of a row forms no product).  g: float32, bfloat16 or float16 (..., ncols); centers:
+    float32[codes.k], rounded to a half g's dtype as the forward rounds them (exact products, float32 sums).  The result (..., kdim)
+    has ``out_dtype``: None (g's dtype, the float32 value rounded once) or torch.float32.  Above 16 rows of a half g it is
+    ops.codebook_matmul_dx on ``codes.to_dense()`` bit for bit.  Split partials are summed in a fixed order: the same call gives
+    the same bits.  No host read."""
+    if not isinstance(g, torch.Tensor) or g.dtype not in _X_DT:
+        raise TypeError(f"g must be a float32, bfloat16 or float16 tensor, got {getattr(g, 'dtype', type(g))}")
+    _require_cuda(g, "g")
+    _require_cuda(centers, "centers", torch.float32)
+    if out_dtype not in (None, torch.float32):
+        raise TypeError(f"out_dtype must be None or torch.float32, got {out_dtype}")
+    codes = _wide_codes(codes)
+    lead, m = _rows(g, "g", codes.ncols)
+    if centers.numel() != codes.k:
+        raise ValueError(f"centers must hold k = {codes.k} values, got {centers.numel()}")
+    _one_device("g, codes and centers", g, codes.packed, centers)
+    L = nat.load()
+    kdim, ncols, bits = codes.kdim, codes.ncols, codes.bits
+    dx_dtype = g.dtype if out_dtype is None else out_dtype
+    dx = torch.empty(lead + (kdim,), dtype=dx_dtype, device=g.device)
+    ws_bytes = int(L.nnc_cbwp_dx_workspace_bytes(_X_DT[g.dtype], m, kdim, ncols, bits))
+    ws = _workspace(ws_bytes, g.device)
+    nat.check(L.nnc_cbwp_dx(_ptr(g), _X_DT[g.dtype], m, kdim, _ptr(codes.packed), codes.nbytes, bits, ncols, _ptr(centers), centers.numel(), _ptr(dx),
+                            _X_DT[dx_dtype], _ptr(ws), ws_bytes, _stream(g)))
+    return dx
+
+
+def wide_packed_codebook_centroid_grad(x: torch.Tensor, g: torch.Tensor, codes: WidePackedCodes, dtype=torch.float64) -> torch.Tensor:
+    """dc[j] = sum over the (i, o) whose label is j of (x^T g)[i, o] (include/nnc_cbwpgrad.h, nnc_cbwp_dc): bit for bit
+    codebook_centroid_grad(x, g, codes.to_dense(), codes.k, ...) at every number of rows and dtype, the indices never unpacked and dW
+    never written.  x: (..., kdim), g: (..., ncols), both float32, both bfloat16 or both float16, with the same leading shape.
+    Returns ``dtype`` (float64 or float32) [codes.k], the gradient with respect to the float32 centres.  No host read."""
+    if not isinstance(x, torch.Tensor) or x.dtype not in _X_DT:
+        raise TypeError(f"x must be a float32, bfloat16 or float16 tensor, got {getattr(x, 'dtype', type(x))}")
+    if not isinstance(g, torch.Tensor) or g.dtype != x.dtype:
+        raise TypeError(f"x and g must have one dtype, got {x.dtype} and {getattr(g, 'dtype', type(g))}")
+    _require_cuda(x, "x")
+    _require_cuda(g, "g")
+    codes = _wide_codes(codes)
+    kdim, ncols, k, bits = codes.kdim, codes.ncols, codes.k, codes.bits
+    lead, m = _rows(g, "g", ncols)
+    _dc_args(x, lead, kdim, "x, g and codes", codes.packed, g, dtype)
+    L = nat.load()
+    dc = torch.empty(k, dtype=dtype, device=x.device)
+    ws_bytes = int(L.nnc_cbwp_dc_workspace_bytes(_X_DT[x.dtype], m, kdim, ncols, bits, k))
+    ws = _workspace(ws_bytes, x.device)
+    nat.check(L.nnc_cbwp_dc(_ptr(x), _ptr(g), _X_DT[x.dtype], m, kdim, _ptr(codes.packed), codes.nbytes, bits, ncols, k, _ptr(dc),
+                            1 if dtype == torch.float64 else 0, _ptr(ws), ws_bytes, _stream(x)))
+    return dc
+
+
+def _cbwp_grad_plan(entry, fields, dtype, *args) -> dict:
+    if dtype not in _X_DT:
+        raise TypeError(f"dtype must be torch.float32, torch.bfloat16 or torch.float16, got {dtype}")
+    return _plan(getattr(nat.load(), entry), fields, _X_DT[dtype], *args)
+
+
+def cbwp_dx_plan(dtype, m: int, kdim: int, ncols: int, bits: int, k: int, cus: int) -> dict:
+    """Host: the plan nnc_cbwp_dx follows for g of ``dtype`` on a device with ``cus`` compute units (include/nnc_cbwpgrad.h), as a dict
+    keyed by _native.CBWPDX_PLAN_FIELDS.  No device needed."""
+    return _cbwp_grad_plan("nnc_cbwp_dx_plan", nat.CBWPDX_PLAN_FIELDS, dtype, m, kdim, ncols, bits, k, cus)
+
+
+def cbwp_dc_plan(dtype, m: int, kdim: int, ncols: int, bits: int, k: int, cus: int) -> dict:
+    """Host: the plan nnc_cbwp_dc follows for x and g of ``dtype`` (include/nnc_cbwpgrad.h), as a dict keyed by
+    _native.CBWPDC_PLAN_FIELDS.  No device needed."""
+    return _cbwp_grad_plan("nnc_cbwp_dc_plan", nat.CBWPDC_PLAN_FIELDS, dtype, m, kdim, ncols, bits, k, cus)
+
+
+def wide_packed_codebook_linear(x: torch.Tensor, codes: WidePackedCodes, centers: torch.Tensor, bias: torch.Tensor | None = None,
+                                relu: bool = False) -> torch.Tensor:
+    """wide_packed_codebook_matmul with gradients for x, centers and bias (an autograd Function shaped like packed_codebook_linear;
+    DESIGN.md section 37).  The forward is the same nnc_cbwp call (under no_grad the bits of wide_packed_codebook_matmul); the
+    backward runs wide_packed_codebook_matmul_dx only if x needs a gradient and wide_packed_codebook_centroid_grad (float32) only if
+    centers does, masks a fused ReLU as torch does and sums the bias gradient over the rows.  The indices get no gradient.  No host
+    read.  A bfloat16 or float16 x: the output and dx have x's dtype, the float32 centers and bias get float32 gradients; a half
+    ``centers`` or ``bias`` raises ``TypeError``."""
+    codes = _wide_codes(codes)
+    if isinstance(x, torch.Tensor) and x.dtype in _H16_DT:
+        _require_centers_bias(centers, bias)
+    return _CodebookLinear.apply(x, codes, centers, bias, bool(relu), codes.kdim, codes.ncols, wide_packed_codebook_matmul, wide_packed_codebook_matmul_dx,
+                                 lambda x2, g2, cd, c: wide_packed_codebook_centroid_grad(x2, g2, cd, dtype=torch.float32))
+
+
 def huffman_lengths(counts) -> tuple:
     """Host: (lengths uint8[k], hist int64[max_len+1], total_bits) from an index histogram."""
     L = nat.load()
