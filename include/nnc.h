@@ -1085,6 +1085,10 @@ int nnc_cbpk_dc_f32(const float *x, const float *g, int64_t m, int64_t kdim, con
  * queries and plans, declared in a header of their own. */
 #include "nnc_cbspgrad_grouped_h16.h"
 
+/* The group-wise layer run from 5- and 6-bit split-plane indices (csrc/nnc_cbwp_grouped.hip): the call, its
+ * workspace query and its plan, declared in a header of their own, which brings the split-plane form's header (nnc_cbwp.h) with it. */
+#include "nnc_cbwp_grouped.h"
+
 /* ------------------------------------------------------------------------------------
  * Multi-GPU: the vector is sharded across one process per GPU (contiguous shards starting on multiples of
  * NNC_CHUNK elements); the exchange per Lloyd iteration is one all-reduce (SUM) of the 2K int64 sums / counts over

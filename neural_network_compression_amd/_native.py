@@ -463,6 +463,17 @@ WIDE_PACKED_GRAD_SIGNATURES = {
 CBWPDX_PLAN_FIELDS = ("path", "vb", "mt", "cols", "base", "planes", "copies", "entries", "splits", "cps", "lds", "col_tiles", "row_tiles", "workspace", "dtype")
 CBWPDC_PLAN_FIELDS = ("path", "vb", "mt", "cols", "base", "planes", "copies", "splits", "rps", "lds", "col_tiles", "row_tiles", "terms_log2", "workspace", "dtype")
 
+# name -> (restype, argtypes); every symbol include/nnc_cbwp_grouped.h declares (the group-wise layer on 5- and 6-bit split-plane indices,
+# inference only, a header of its own that nnc.h includes).  Required and bound by load() as SIGNATURES are.
+GROUPED_WIDE_PACKED_SIGNATURES = {
+    "nnc_cbwp_grouped_workspace_bytes": (c_i64, [c_int, c_i64, c_i64, c_i64, c_int]),
+    "nnc_cbwp_grouped_plan": (c_int, [c_int, c_i64, c_i64, c_i64, c_int, c_i32, c_i64, c_i32, ctypes.POINTER(c_i64)]),
+    "nnc_cbwp_grouped": (c_int, [c_void_p, c_int, c_i64, c_i64, c_void_p, c_i64, c_int, c_i64, c_void_p, c_i32, c_i64, c_void_p, c_i32, c_void_p, c_int,
+                                 c_void_p, c_i64, c_void_p]),
+}
+CBWP_GROUPED_PLAN_LEN = 19   # nnc_cbwp_grouped_plan (include/nnc_cbwp_grouped.h): the NNC_CBWP_P_* fields, then the groups and the tables in LDS
+CBWP_GROUPED_PLAN_FIELDS = CBWP_PLAN_FIELDS + ("group_rows", "groups", "max_groups_per_split", "tables")
+
 # exported only by the diagnostics build (NNC_DIAG=1: libnnc_hip_diag.so, see build.py); bound when present
 DIAG_SIGNATURES = {
     "nnc_debug_set_ablation": (c_int, [c_int]),
@@ -495,7 +506,7 @@ def load():
         L = ctypes.CDLL(path)
     except OSError as e:  # pragma: no cover - depends on the machine
         raise NativeLibraryError(f"cannot load {path}: {e}; there is no CPU fallback") from e
-    for name, (res, args) in list(SIGNATURES.items()) + list(GROUPED_GRAD_SIGNATURES.items()) + list(H16_GRAD_SIGNATURES.items()) + list(GROUPED_PACKED_GRAD_SIGNATURES.items()) + list(SPARSE_H16_SIGNATURES.items()) + list(SPARSE_H16_GRAD_SIGNATURES.items()) + list(PACKED_H16_SIGNATURES.items()) + list(GROUPED_H16_GRAD_SIGNATURES.items()) + list(GROUPED_SPARSE_SIGNATURES.items()) + list(GROUPED_SPARSE_H16_SIGNATURES.items()) + list(GROUPED_SPARSE_GRAD_SIGNATURES.items()) + list(GROUPED_SPARSE_H16_GRAD_SIGNATURES.items()) + list(WIDE_PACKED_SIGNATURES.items()) + list(WIDE_PACKED_GRAD_SIGNATURES.items()):
+    for name, (res, args) in list(SIGNATURES.items()) + list(GROUPED_GRAD_SIGNATURES.items()) + list(H16_GRAD_SIGNATURES.items()) + list(GROUPED_PACKED_GRAD_SIGNATURES.items()) + list(SPARSE_H16_SIGNATURES.items()) + list(SPARSE_H16_GRAD_SIGNATURES.items()) + list(PACKED_H16_SIGNATURES.items()) + list(GROUPED_H16_GRAD_SIGNATURES.items()) + list(GROUPED_SPARSE_SIGNATURES.items()) + list(GROUPED_SPARSE_H16_SIGNATURES.items()) + list(GROUPED_SPARSE_GRAD_SIGNATURES.items()) + list(GROUPED_SPARSE_H16_GRAD_SIGNATURES.items()) + list(WIDE_PACKED_SIGNATURES.items()) + list(WIDE_PACKED_GRAD_SIGNATURES.items()) + list(GROUPED_WIDE_PACKED_SIGNATURES.items()):
         try:
             fn = getattr(L, name)
         except AttributeError as e:

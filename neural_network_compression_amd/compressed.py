@@ -13,6 +13,7 @@ tensor is never rebuilt.  Biases (one value per output column) are decoded once 
     sparsify_grouped_layers(network, sparse=True)                  a deep copy with the grouped layers' indices in the bitmap-sparse form
     smallest_grouped_layers(network)                               a deep copy with every grouped layer in the smallest of its three forms
     widen_packed_layers(network, wide=True)                        a deep copy with the byte layers of 17 .. 512 centres at 5, 6 or 9 bits per index
+    widen_grouped_layers(network, wide=True)                       a deep copy with the grouped layers of 17 .. 64 centres per group at 5 or 6 bits per index
     compressed_nbytes(network)                                     resident bytes of the layers' tensors
 
 A pruned layer can instead keep its indices in the bitmap-sparse form (ops.pack_sparse_codes, csrc/nnc_cbsp.hip, DESIGN.md
@@ -976,6 +977,54 @@ class GroupedPackedCompressedDense(_DenseHalf, _PackedForm, _InferenceLayer):
         return self._activate(ops.grouped_packed_codebook_matmul(x, self.codes, self.centers, self.group_rows, bias=self.bias, relu=self._fused_relu))
 
 
+GROUPED_WIDE_MAX_K = 64   # the widest group-wise split-plane form is 6 bits: the grouped byte form is uint8, 9 bits would be larger
+
+
+class GroupedWidePackedCompressedDense(_DenseHalf, _WidePackedForm, _InferenceLayer):
+    """Dense run from one codebook per block of ``group_rows`` input rows and the 5- or 6-bit split-plane form of its (in, out)
+    indices (ops.grouped_wide_packed_codebook_matmul): packed (the ordinary split-plane buffer of the whole
+    index matrix), centers float32 (G, 16 < K <= 64), G = ceil(kdim / group_rows), bias float32[ncols] or None.  The path follows
+    the input's dtype as in GroupedCompressedDense (float32, bfloat16, float16; the output has the input's dtype); centers and bias
+    stay float32.  No kdim * ncols tensor stays resident.  Inference only."""
+
+    def __init__(self, codes: ops.WidePackedCodes, group_rows: int, centers: torch.Tensor, bias: torch.Tensor | None, activation=None):
+        super().__init__()
+        if not PACKED_MAX_K < codes.k <= GROUPED_WIDE_MAX_K:
+            raise ValueError(f"group-wise split-plane indices take 17 to {GROUPED_WIDE_MAX_K} centres per group, got {codes.k}: at most 16 fit the "
+                             "packed form (GroupedPackedCompressedDense), more than 64 stay in the byte form (GroupedCompressedDense)")
+        groups = max(1, -(-codes.kdim // int(group_rows)))
+        if centers.dim() != 2 or tuple(centers.shape) != (groups, codes.k):
+            raise ValueError(f"centers must have shape ({groups}, {codes.k}) for {codes.kdim} rows in groups of {group_rows} and indices into "
+                             f"codebooks of {codes.k}, got {tuple(centers.shape)}")
+        self._take_codes(codes)
+        self.group_rows = int(group_rows)
+        self._init_codebook(centers, bias, activation)
+
+    @classmethod
+    def from_dense(cls, dense, grouped_model, bias_model=None) -> "GroupedWidePackedCompressedDense":
+        """From a Dense layer and the GroupedModel of its kernel (utility.get_quantized_weight_grouped), 16 < K <= 64."""
+        _require_model(grouped_model)
+        kin, kout = dense.kernel.shape
+        centers = torch.from_numpy(np.ascontiguousarray(grouped_model.cluster_centers_, dtype=np.float32)).to(dense.kernel.device)
+        return cls.from_codes(kin, kout, grouped_model.group_rows, grouped_model.labels_compact_, centers, _decoded_bias(dense.bias, bias_model),
+                              dense.activation)
+
+    @classmethod
+    def from_codes(cls, kdim, ncols, group_rows, labels, centers, bias, activation) -> "GroupedWidePackedCompressedDense":
+        if centers.dim() != 2 or not PACKED_MAX_K < centers.shape[1] <= GROUPED_WIDE_MAX_K:
+            raise ValueError(f"centers must have shape (G, 17 <= K <= {GROUPED_WIDE_MAX_K}), got {tuple(centers.shape)}")
+        return cls(ops.pack_codes_wide(labels, kdim, ncols, centers.shape[1]), group_rows, centers, bias, activation)
+
+    @classmethod
+    def from_grouped(cls, layer: GroupedCompressedDense) -> "GroupedWidePackedCompressedDense":
+        """The same layer from the split-plane form of a GroupedCompressedDense's indices: the same weights."""
+        return cls.from_codes(layer.kdim, layer.ncols, layer.group_rows, layer.labels, layer.centers, layer.bias, layer.activation)
+
+    def _matmul(self, x: torch.Tensor) -> torch.Tensor:
+        return self._activate(ops.grouped_wide_packed_codebook_matmul(x, self.codes, self.centers, self.group_rows, bias=self.bias,
+                                                                      relu=self._fused_relu))
+
+
 class GroupedSparseCompressedDense(_DenseHalf, _InferenceLayer):
     """Dense run from one codebook per block of ``group_rows`` input rows and the bitmap-sparse form of its (in, out) indices
     (ops.grouped_sparse_codebook_matmul): packed (the bitmap-sparse buffer of the whole index matrix, one
@@ -1602,6 +1651,27 @@ def widen_packed_layers(network: nn.Module, wide=True, *, trainable=False) -> nn
         else:
             made = WidePackedCompressedConv2D(layer.kernel_size, layer.cin, layer.pad, codes, layer.centers, layer.bias, layer.activation)
         setattr(out, name, made)
+    return out
+
+
+def widen_grouped_layers(network: nn.Module, wide=True) -> nn.Module:
+    """A deep copy of a compressed ``network`` (compress_network, Trainer.compressed_network() or load_network) whose
+    GroupedCompressedDense layers of 16 < K <= 64 centres per group keep their indices in the 5- or 6-bit split-plane form
+    (GroupedWidePackedCompressedDense).  ``wide``: True (every such layer) or "auto" (a layer only where the
+    split-plane form holds fewer resident bytes; on equal bytes the byte form stays); anything else is a ValueError.  Grouped layers
+    of at most 16 centres (pack_grouped_layers serves them) or more than 64, and all other layers, are left as they are.  A replaced
+    layer has the same weights; its float32 sums run in another order (within the float bound of section 36, the same bits on exact
+    data), its bfloat16 / float16 products at more than 16 rows give the same bits."""
+    if wide is not True and wide != "auto":
+        raise ValueError(f"wide must be True or 'auto', got {wide!r}")
+    out = copy.deepcopy(network)
+    for name, layer in out.get_config().items():
+        if not isinstance(layer, GroupedCompressedDense) or not PACKED_MAX_K < layer.centers.shape[1] <= GROUPED_WIDE_MAX_K:
+            continue
+        bits = ops.wide_packed_bits(layer.centers.shape[1])
+        if wide == "auto" and ops.wide_packed_nbytes(layer.kdim, layer.ncols, bits) >= layer.labels.numel():
+            continue
+        setattr(out, name, GroupedWidePackedCompressedDense.from_grouped(layer))
     return out
 
 
