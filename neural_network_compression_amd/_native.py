@@ -474,6 +474,23 @@ GROUPED_WIDE_PACKED_SIGNATURES = {
 CBWP_GROUPED_PLAN_LEN = 19   # nnc_cbwp_grouped_plan (include/nnc_cbwp_grouped.h): the NNC_CBWP_P_* fields, then the groups and the tables in LDS
 CBWP_GROUPED_PLAN_FIELDS = CBWP_PLAN_FIELDS + ("group_rows", "groups", "max_groups_per_split", "tables")
 
+# name -> (restype, argtypes); every symbol include/nnc_cbwpgrad_grouped.h declares (the backward pass of the group-wise layer on 5- and
+# 6-bit split-plane indices, a header of its own that includes nnc_cbwpgrad.h and nnc_cbwp_grouped.h).  Required and bound by load().
+GROUPED_WIDE_PACKED_GRAD_SIGNATURES = {
+    "nnc_cbwp_grouped_dx_workspace_bytes": (c_i64, [c_int, c_i64, c_i64, c_i64, c_int]),
+    "nnc_cbwp_grouped_dx_plan": (c_int, [c_int, c_i64, c_i64, c_i64, c_int, c_i32, c_i64, c_i32, ctypes.POINTER(c_i64)]),
+    "nnc_cbwp_grouped_dx": (c_int, [c_void_p, c_int, c_i64, c_i64, c_void_p, c_i64, c_int, c_i64, c_void_p, c_i32, c_i64, c_void_p, c_int, c_void_p, c_i64,
+                                    c_void_p]),
+    "nnc_cbwp_grouped_dc_workspace_bytes": (c_i64, [c_int, c_i64, c_i64, c_i64, c_int, c_i32, c_i64]),
+    "nnc_cbwp_grouped_dc_plan": (c_int, [c_int, c_i64, c_i64, c_i64, c_int, c_i32, c_i64, c_i32, ctypes.POINTER(c_i64)]),
+    "nnc_cbwp_grouped_dc": (c_int, [c_void_p, c_void_p, c_int, c_i64, c_i64, c_void_p, c_i64, c_int, c_i64, c_i32, c_i64, c_void_p, c_i32, c_void_p, c_i64,
+                                    c_void_p]),
+}
+# nnc_cbwp_grouped_dx_plan / nnc_cbwp_grouped_dc_plan (include/nnc_cbwpgrad_grouped.h): the ungrouped fields, then NNC_CBWPGRAD_GROUPED_P_*
+_CBWPGRAD_GROUPED_TAIL = ("group_rows", "groups", "rows_per_group", "max_groups_per_workgroup", "held")
+CBWPDX_GROUPED_PLAN_FIELDS = CBWPDX_PLAN_FIELDS + _CBWPGRAD_GROUPED_TAIL
+CBWPDC_GROUPED_PLAN_FIELDS = CBWPDC_PLAN_FIELDS + _CBWPGRAD_GROUPED_TAIL
+
 # exported only by the diagnostics build (NNC_DIAG=1: libnnc_hip_diag.so, see build.py); bound when present
 DIAG_SIGNATURES = {
     "nnc_debug_set_ablation": (c_int, [c_int]),
@@ -506,7 +523,7 @@ def load():
         L = ctypes.CDLL(path)
     except OSError as e:  # pragma: no cover - depends on the machine
         raise NativeLibraryError(f"cannot load {path}: {e}; there is no CPU fallback") from e
-    for name, (res, args) in list(SIGNATURES.items()) + list(GROUPED_GRAD_SIGNATURES.items()) + list(H16_GRAD_SIGNATURES.items()) + list(GROUPED_PACKED_GRAD_SIGNATURES.items()) + list(SPARSE_H16_SIGNATURES.items()) + list(SPARSE_H16_GRAD_SIGNATURES.items()) + list(PACKED_H16_SIGNATURES.items()) + list(GROUPED_H16_GRAD_SIGNATURES.items()) + list(GROUPED_SPARSE_SIGNATURES.items()) + list(GROUPED_SPARSE_H16_SIGNATURES.items()) + list(GROUPED_SPARSE_GRAD_SIGNATURES.items()) + list(GROUPED_SPARSE_H16_GRAD_SIGNATURES.items()) + list(WIDE_PACKED_SIGNATURES.items()) + list(WIDE_PACKED_GRAD_SIGNATURES.items()) + list(GROUPED_WIDE_PACKED_SIGNATURES.items()):
+    for name, (res, args) in list(SIGNATURES.items()) + list(GROUPED_GRAD_SIGNATURES.items()) + list(H16_GRAD_SIGNATURES.items()) + list(GROUPED_PACKED_GRAD_SIGNATURES.items()) + list(SPARSE_H16_SIGNATURES.items()) + list(SPARSE_H16_GRAD_SIGNATURES.items()) + list(PACKED_H16_SIGNATURES.items()) + list(GROUPED_H16_GRAD_SIGNATURES.items()) + list(GROUPED_SPARSE_SIGNATURES.items()) + list(GROUPED_SPARSE_H16_SIGNATURES.items()) + list(GROUPED_SPARSE_GRAD_SIGNATURES.items()) + list(GROUPED_SPARSE_H16_GRAD_SIGNATURES.items()) + list(WIDE_PACKED_SIGNATURES.items()) + list(WIDE_PACKED_GRAD_SIGNATURES.items()) + list(GROUPED_WIDE_PACKED_SIGNATURES.items()) + list(GROUPED_WIDE_PACKED_GRAD_SIGNATURES.items()):
         try:
             fn = getattr(L, name)
         except AttributeError as e:

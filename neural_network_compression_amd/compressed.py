@@ -1148,6 +1148,68 @@ class TrainableGroupedPackedCompressedDense(_DenseHalf, _PackedForm, _TrainableC
         return self._nbytes(self.packed)
 
 
+class TrainableGroupedWidePackedCompressedDense(_DenseHalf, _WidePackedForm, _TrainableCentres):
+    """GroupedWidePackedCompressedDense with trainable centres (ops.grouped_wide_packed_codebook_linear): packed
+    (the ordinary 5- or 6-bit split-plane buffer of the whole index matrix) the only index buffer, centers a float32 (G, 17 <= K <= 64)
+    nn.Parameter, counts the (G, K) histogram of every group's indices taken from the labels before packing, so kernel_sq_sum() is
+    TrainableGroupedCompressedDense's bit for bit; the bias of _TrainableCentres.  The backward forms dx and the (G, K) centroid
+    gradient from the codebooks and the packed rows (csrc/nnc_cbwpgrad_grouped.hip): the indices are never unpacked, W and dW never
+    built, and no byte-per-weight tensor stays resident while training.  The path follows the input's dtype (float32, bfloat16,
+    float16; the output and the input gradient have it); centres and bias stay float32 with float32 gradients."""
+
+    def __init__(self, codes: ops.WidePackedCodes, group_rows: int, labels: torch.Tensor, centers: torch.Tensor, bias: torch.Tensor | None = None,
+                 bias_codes=None, activation=None):
+        super().__init__()
+        if not PACKED_MAX_K < codes.k <= GROUPED_WIDE_MAX_K:
+            raise ValueError(f"group-wise split-plane indices take 17 to {GROUPED_WIDE_MAX_K} centres per group, got {codes.k}: at most 16 fit the "
+                             "packed form (TrainableGroupedPackedCompressedDense), more than 64 stay in the byte form (TrainableGroupedCompressedDense)")
+        groups = max(1, -(-codes.kdim // int(group_rows)))
+        if centers.dim() != 2 or tuple(centers.shape) != (groups, codes.k):
+            raise ValueError(f"centers must have shape ({groups}, {codes.k}) for {codes.kdim} rows in groups of {group_rows} and indices into "
+                             f"codebooks of {codes.k}, got {tuple(centers.shape)}")
+        if labels.numel() != codes.kdim * codes.ncols:
+            raise ValueError(f"{labels.numel()} indices for a {codes.kdim} x {codes.ncols} weight matrix")
+        self._take_codes(codes)
+        self.group_rows = int(group_rows)
+        counts = _group_counts(labels.reshape(-1), self.group_rows * self.ncols, groups, codes.k)
+        self._init_centres(None, centers, codes.ncols, bias, bias_codes, activation, counts=counts)
+
+    @classmethod
+    def from_dense(cls, dense, grouped_model, bias_model=None) -> "TrainableGroupedWidePackedCompressedDense":
+        """From a Dense layer and the GroupedModel of its kernel, 16 < K <= 64; a quantized bias keeps its codes, a raw one stays frozen."""
+        _require_model(grouped_model)
+        kin, kout = dense.kernel.shape
+        dev = dense.kernel.device
+        centers = torch.from_numpy(np.ascontiguousarray(grouped_model.cluster_centers_, dtype=np.float32)).to(dev)
+        bias, bias_codes = (None, _codes(bias_model, dev)) if bias_model is not None else (dense.bias, None)
+        return cls.from_codes(kin, kout, grouped_model.group_rows, grouped_model.labels_compact_, centers, bias, bias_codes, dense.activation)
+
+    @classmethod
+    def from_codes(cls, kdim, ncols, group_rows, labels, centers, bias=None, bias_codes=None,
+                   activation=None) -> "TrainableGroupedWidePackedCompressedDense":
+        if centers.dim() != 2 or not PACKED_MAX_K < centers.shape[1] <= GROUPED_WIDE_MAX_K:
+            raise ValueError(f"centers must have shape (G, 17 <= K <= {GROUPED_WIDE_MAX_K}), got {tuple(centers.shape)}")
+        return cls(ops.pack_codes_wide(labels, kdim, ncols, centers.shape[1]), group_rows, labels, centers, bias, bias_codes, activation)
+
+    @classmethod
+    def from_grouped(cls, layer: GroupedCompressedDense) -> "TrainableGroupedWidePackedCompressedDense":
+        """The trainable split-plane layer of a GroupedCompressedDense: its indices packed, the same centres, its decoded bias frozen."""
+        return cls.from_codes(layer.kdim, layer.ncols, layer.group_rows, layer.labels, layer.centers, layer.bias, None, layer.activation)
+
+    @classmethod
+    def from_grouped_wide_packed(cls, layer: GroupedWidePackedCompressedDense) -> "TrainableGroupedWidePackedCompressedDense":
+        """The trainable layer of a GroupedWidePackedCompressedDense on the same packed buffer; the counts come from a temporary unpack
+        (nnc_cbwp_unpack), which is dropped afterwards."""
+        return cls(layer.codes, layer.group_rows, layer.codes.to_dense(), layer.centers, layer.bias, None, layer.activation)
+
+    def _matmul(self, x: torch.Tensor) -> torch.Tensor:
+        return self._activate(ops.grouped_wide_packed_codebook_linear(x, self.codes, self.centers, self.group_rows, bias=self.current_bias(),
+                                                                      relu=self._fused_relu))
+
+    def nbytes(self) -> int:
+        return self._nbytes(self.packed)
+
+
 class TrainableGroupedSparseCompressedDense(_DenseHalf, _TrainableCentres):
     """GroupedSparseCompressedDense with trainable centres (ops.grouped_sparse_codebook_linear): packed (the
     bitmap-sparse buffer of the whole index matrix) and zero_symbols (uint8[G]) the only index buffers, centers a float32 (G, K)
@@ -1654,24 +1716,34 @@ def widen_packed_layers(network: nn.Module, wide=True, *, trainable=False) -> nn
     return out
 
 
-def widen_grouped_layers(network: nn.Module, wide=True) -> nn.Module:
+def widen_grouped_layers(network: nn.Module, wide=True, *, trainable=False) -> nn.Module:
     """A deep copy of a compressed ``network`` (compress_network, Trainer.compressed_network() or load_network) whose
     GroupedCompressedDense layers of 16 < K <= 64 centres per group keep their indices in the 5- or 6-bit split-plane form
     (GroupedWidePackedCompressedDense).  ``wide``: True (every such layer) or "auto" (a layer only where the
-    split-plane form holds fewer resident bytes; on equal bytes the byte form stays); anything else is a ValueError.  Grouped layers
-    of at most 16 centres (pack_grouped_layers serves them) or more than 64, and all other layers, are left as they are.  A replaced
-    layer has the same weights; its float32 sums run in another order (within the float bound of section 36, the same bits on exact
-    data), its bfloat16 / float16 products at more than 16 rows give the same bits."""
+    split-plane form holds fewer resident bytes; on equal bytes the byte form stays); anything else is a ValueError.
+    ``trainable=True`` widens the TrainableGroupedCompressedDense layers of such codebooks too
+    (TrainableGroupedWidePackedCompressedDense, section 39): they keep their centres, counts, bias and bias codes and train from the
+    packed rows.  Grouped layers of at most 16 centres (pack_grouped_layers serves them) or more than 64, by default the trainable
+    ones, and all other layers are left as they are.  A replaced layer has the same weights; its float32 sums run in another order
+    (within the float bound of section 36, the same bits on exact data), its bfloat16 / float16 products at more than 16 rows give the
+    same bits."""
     if wide is not True and wide != "auto":
         raise ValueError(f"wide must be True or 'auto', got {wide!r}")
+    kinds = (GroupedCompressedDense,) + ((TrainableGroupedCompressedDense,) if trainable else ())
     out = copy.deepcopy(network)
     for name, layer in out.get_config().items():
-        if not isinstance(layer, GroupedCompressedDense) or not PACKED_MAX_K < layer.centers.shape[1] <= GROUPED_WIDE_MAX_K:
+        if not isinstance(layer, kinds) or not PACKED_MAX_K < layer.centers.shape[1] <= GROUPED_WIDE_MAX_K:
             continue
         bits = ops.wide_packed_bits(layer.centers.shape[1])
         if wide == "auto" and ops.wide_packed_nbytes(layer.kdim, layer.ncols, bits) >= layer.labels.numel():
             continue
-        setattr(out, name, GroupedWidePackedCompressedDense.from_grouped(layer))
+        if isinstance(layer, TrainableGroupedCompressedDense):
+            bias_codes = None if layer.bias_centers is None else (layer.bias_centers, layer.bias_labels)
+            made = TrainableGroupedWidePackedCompressedDense.from_codes(layer.kdim, layer.ncols, layer.group_rows, layer.labels, layer.centers,
+                                                                        layer.bias, bias_codes, layer.activation)
+        else:
+            made = GroupedWidePackedCompressedDense.from_grouped(layer)
+        setattr(out, name, made)
     return out
 
 

@@ -51,6 +51,20 @@ static int wp_check(const char *fn, int x_dtype, int64_t m, int64_t kdim, int64_
     return NNC_OK;
 }
 
+// the checks of the group-wise entry points, forward (nnc_cbwp_grouped.hip) and backward (nnc_cbwpgrad_grouped.hip): 5 or 6 bits and
+// 17 .. 64 centres, wp_check's, then those of group_rows (bins_k = k where the caller keeps G * k bins: cb_check_group_rows)
+static int wpg_check(const char *fn, int x_dtype, int64_t m, int64_t kdim, int64_t ncols, int bits, int32_t k, int64_t group_rows, int32_t bins_k = 0)
+{
+    const std::string f(fn);
+    if (bits == 9 || k > 64)
+        return fail(NNC_EINVAL, f + ": k > 64 (bits 9) is refused: the group-wise byte form holds uint8 labels, and 9 bits would be larger than it");
+    if (bits != 5 && bits != 6) return fail(NNC_EINVAL, f + ": bits must be 5 or 6");
+    if (k <= 16) return fail(NNC_EINVAL, f + ": k <= 16 is refused: the 2- and 4-bit packed form serves it (nnc_cbpk_grouped)");
+    const int rc = wp_check(fn, x_dtype, m, kdim, ncols, bits, k);
+    if (rc != NNC_OK) return rc;
+    return cb_check_group_rows(fn, kdim, group_rows, bins_k);
+}
+
 // ------------------------------------------------------------------ the plan (host)
 // Every decision nnc_cbwp takes before it launches; nnc_cbwp_plan reports it.
 struct WpPlan {

@@ -424,19 +424,7 @@ static WpgPlan wpg_plan(int x_dtype, long long m, long long kdim, long long ncol
     return g;
 }
 
-// ------------------------------------------------------------------ C ABI
-static int wpg_check(const char *fn, int x_dtype, int64_t m, int64_t kdim, int64_t ncols, int bits, int32_t k, int64_t group_rows)
-{
-    const std::string f(fn);
-    if (bits == 9 || k > 64)
-        return fail(NNC_EINVAL, f + ": k > 64 (bits 9) is refused: the group-wise byte form holds uint8 labels, and 9 bits would be larger than it");
-    if (bits != 5 && bits != 6) return fail(NNC_EINVAL, f + ": bits must be 5 or 6");
-    if (k <= 16) return fail(NNC_EINVAL, f + ": k <= 16 is refused: the 2- and 4-bit packed form serves it (nnc_cbpk_grouped)");
-    const int rc = wp_check(fn, x_dtype, m, kdim, ncols, bits, k);
-    if (rc != NNC_OK) return rc;
-    return cb_check_group_rows(fn, kdim, group_rows);
-}
-
+// ------------------------------------------------------------------ C ABI (wpg_check: nnc_cbwp.hpp)
 extern "C" int64_t nnc_cbwp_grouped_workspace_bytes(int x_dtype, int64_t m, int64_t kdim, int64_t ncols, int bits)
 {
     if (m <= 0 || kdim <= 0 || ncols <= 0 || wpg_check("nnc_cbwp_grouped_workspace_bytes", x_dtype, m, kdim, ncols, bits, 17, 32) != NNC_OK) return 0;

@@ -30,17 +30,6 @@
 #include "nnc_cbwpgrad.hpp"
 #include "nnc_cbgrad_h16.hpp"
 
-// label (i, o)'s base field from the dword `w` that holds it and its plane bits from the plane dwords pl[] (bit o % 32)
-template <int BASE, int PLANES>
-__device__ __forceinline__ uint32_t wg_label(uint32_t w, const uint32_t *pl, long long o)
-{
-    constexpr int PER = 32 / BASE;
-    uint32_t l = (w >> (BASE * (int)(o % PER))) & ((1u << BASE) - 1);
-#pragma unroll
-    for (int p = 0; p < PLANES; ++p) l |= ((pl[p] >> (int)(o & 31)) & 1u) << (BASE + p);
-    return l;
-}
-
 // ------------------------------------------------------------------ dx, m <= 16
 // grid (column blocks, row groups), CB_THREADS threads.  out: dx (one column block; direct 1: float32, 2: XT) or the float32 partials
 // [block][m][kdim].
@@ -403,11 +392,7 @@ __global__ __launch_bounds__(HM_THREADS) void k_cbwpdc_mfma(const XT *__restrict
 }
 
 // ------------------------------------------------------------------ launches
-// one signature per direction and path for the three dtypes: g, x and out travel as void *
-struct WgArgs {
-    const unsigned char *packed;
-    long long base_bytes, plane_bytes, ncols;
-};
+// one signature per direction and path for the three dtypes: g, x and out travel as void * (WgArgs: nnc_cbwpgrad.hpp)
 
 template <typename XT, int BASE, int PLANES, int VB, int MT>
 static void launch_dx_stream(dim3 grid, size_t lds, hipStream_t s, const void *g, int m, long long kdim, const WgArgs &w, const float *centers, int k,
@@ -483,11 +468,6 @@ static const WgStreamCase kWgF16Cases[] = {WPG_STREAM_CASES(WG_F16)};
 static const WgTileCase kWgTileCases[] = {WG_TILES(NNC_DT_F32, float), WG_TILES(NNC_DT_BF16, bf16_t), WG_TILES(NNC_DT_F16, f16_t)};
 #undef WG_TILES
 static const CbgCaseNames kWgNames = {false, "bits", true};
-
-template <size_t N> static const WgStreamCase (&wg_cases(int dt, const WgStreamCase (&f32)[N], const WgStreamCase (&bf16)[N], const WgStreamCase (&f16)[N]))[N]
-{
-    return dt == NNC_DT_F32 ? f32 : (dt == NNC_DT_BF16 ? bf16 : f16);
-}
 
 // The instantiations plan p asks for: sc on the stream path, tc on a tile path (NNC_EINVAL and a message if a table has none), both
 // NULL on the paths that launch nothing of this unit.

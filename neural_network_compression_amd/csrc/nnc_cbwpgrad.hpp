@@ -91,3 +91,27 @@ static int wg_check(const char *fn, int x_dtype, int64_t m, int64_t kdim, int64_
     if (m > 0 && kdim > (1LL << 44) / m) return fail(NNC_EINVAL, std::string(fn) + ": size too large");
     return NNC_OK;
 }
+
+// ------------------------------------------------------------------ what the group-wise unit (nnc_cbwpgrad_grouped.hip, section 39) shares
+// the packed buffer as the launches carry it
+struct WgArgs {
+    const unsigned char *packed;
+    long long base_bytes, plane_bytes, ncols;
+};
+
+// the table of a unit's stream instantiations for x_dtype: one per dtype, the same cases (N)
+template <typename Case, size_t N> static inline const Case (&wg_cases(int dt, const Case (&f32)[N], const Case (&bf16)[N], const Case (&f16)[N]))[N]
+{
+    return dt == NNC_DT_F32 ? f32 : (dt == NNC_DT_BF16 ? bf16 : f16);
+}
+
+// label (i, o)'s base field from the dword `w` that holds it and its plane bits from the plane dwords pl[] (bit o % 32)
+template <int BASE, int PLANES>
+__device__ __forceinline__ uint32_t wg_label(uint32_t w, const uint32_t *pl, long long o)
+{
+    constexpr int PER = 32 / BASE;
+    uint32_t l = (w >> (BASE * (int)(o % PER))) & ((1u << BASE) - 1);
+#pragma unroll
+    for (int p = 0; p < PLANES; ++p) l |= ((pl[p] >> (int)(o & 31)) & 1u) << (BASE + p);
+    return l;
+}

@@ -1819,6 +1819,17 @@ def cbwp_plan(dtype, m: int, kdim: int, ncols: int, bits: int, k: int, cus: int)
     return _plan(nat.load().nnc_cbwp_plan, nat.CBWP_PLAN_FIELDS, _X_DT[dtype], m, kdim, ncols, bits, k, cus)
 
 
+def _grouped_wide_args(codes: WidePackedCodes, centers, group_rows: int) -> int:
+    """The grouped split-plane form's checks of group_rows and the (G, K) centres (None: not checked) -> G, as the layers count it (>= 1)."""
+    if group_rows < 32 or group_rows % 32:
+        raise ValueError(f"group_rows must be a positive multiple of 32, got {group_rows}")
+    groups = max(-(-codes.kdim // group_rows), 1)
+    if centers is not None and (centers.dim() != 2 or tuple(centers.shape) != (groups, codes.k)):
+        raise ValueError(f"centers must have shape ({groups}, {codes.k}) for kdim {codes.kdim}, group_rows {group_rows} and codes of k = {codes.k}, "
+                         f"got {tuple(centers.shape)}")
+    return groups
+
+
 def grouped_wide_packed_codebook_matmul(x: torch.Tensor, codes: WidePackedCodes, centers: torch.Tensor, group_rows: int,
                                         bias: torch.Tensor | None = None, relu: bool = False, out_dtype=None) -> torch.Tensor:
     """y = x @ W + bias (then ReLU) with one codebook per block of ``group_rows`` input rows, W[i, o] = centers[i // group_rows]
@@ -1838,13 +1849,8 @@ def grouped_wide_packed_codebook_matmul(x: torch.Tensor, codes: WidePackedCodes,
     _require_centers_bias(centers, bias)
     group_rows = int(group_rows)
     _inference_only("grouped_wide_packed_codebook_matmul", "x, codes, centers and bias", x, codes.packed, centers, bias)
-    if group_rows < 32 or group_rows % 32:
-        raise ValueError(f"group_rows must be a positive multiple of 32, got {group_rows}")
+    _grouped_wide_args(codes, centers, group_rows)
     kdim, ncols = codes.kdim, codes.ncols
-    groups = max(-(-kdim // group_rows), 1)
-    if centers.dim() != 2 or tuple(centers.shape) != (groups, codes.k):
-        raise ValueError(f"centers must have shape ({groups}, {codes.k}) for kdim {kdim}, group_rows {group_rows} and codes of k = {codes.k}, "
-                         f"got {tuple(centers.shape)}")
     lead, m = _rows(x, "x", kdim)
     y = _empty_y(x, lead, ncols, bias, y_dtype)
     L = nat.load()
@@ -1955,6 +1961,93 @@ def wide_packed_codebook_linear(x: torch.Tensor, codes: WidePackedCodes, centers
         _require_centers_bias(centers, bias)
     return _CodebookLinear.apply(x, codes, centers, bias, bool(relu), codes.kdim, codes.ncols, wide_packed_codebook_matmul, wide_packed_codebook_matmul_dx,
                                  lambda x2, g2, cd, c: wide_packed_codebook_centroid_grad(x2, g2, cd, dtype=torch.float32))
+
+
+def grouped_wide_packed_codebook_matmul_dx(g: torch.Tensor, codes: WidePackedCodes, centers: torch.Tensor, group_rows: int, out_dtype=None) -> torch.Tensor:
+    """dx = g @ W^T with W[i, o] = centers[i // group_rows][label (i, o)] read from the 5- or 6-bit split-plane indices
+    (include/nnc_cbwpgrad_grouped.h, nnc_cbwp_grouped_dx): the input gradient of
+    grouped_wide_packed_codebook_matmul.  g: float32, bfloat16 or float16 (..., ncols); codes, centers (G, K) and group_rows as there;
+    the centres are rounded to a half g's dtype as the forward rounds them.  The result (..., kdim) has ``out_dtype``: None (g's dtype,
+    the float32 value rounded once) or torch.float32.  The columns of a group are, bit for bit, those wide_packed_codebook_matmul_dx
+    gives with that group's table up to 16 rows; above 16 rows of a half g the result is grouped_codebook_matmul_dx on
+    ``codes.to_dense()`` bit for bit.  The same call gives the same bits.  No host read."""
+    if not isinstance(g, torch.Tensor) or g.dtype not in _X_DT:
+        raise TypeError(f"g must be a float32, bfloat16 or float16 tensor, got {getattr(g, 'dtype', type(g))}")
+    _require_cuda(g, "g")
+    _require_cuda(centers, "centers", torch.float32)
+    if out_dtype not in (None, torch.float32):
+        raise TypeError(f"out_dtype must be None or torch.float32, got {out_dtype}")
+    codes, group_rows = _wide_codes(codes), int(group_rows)
+    _grouped_wide_args(codes, centers, group_rows)
+    lead, m = _rows(g, "g", codes.ncols)
+    _one_device("g, codes and centers", g, codes.packed, centers)
+    L = nat.load()
+    kdim, ncols, bits = codes.kdim, codes.ncols, codes.bits
+    dx_dtype = g.dtype if out_dtype is None else out_dtype
+    dx = torch.empty(lead + (kdim,), dtype=dx_dtype, device=g.device)
+    ws_bytes = int(L.nnc_cbwp_grouped_dx_workspace_bytes(_X_DT[g.dtype], m, kdim, ncols, bits))
+    ws = _workspace(ws_bytes, g.device)
+    nat.check(L.nnc_cbwp_grouped_dx(_ptr(g), _X_DT[g.dtype], m, kdim, _ptr(codes.packed), codes.nbytes, bits, ncols, _ptr(centers), codes.k, group_rows,
+                                    _ptr(dx), _X_DT[dx_dtype], _ptr(ws), ws_bytes, _stream(g)))
+    return dx
+
+
+def grouped_wide_packed_codebook_centroid_grad(x: torch.Tensor, g: torch.Tensor, codes: WidePackedCodes, group_rows: int,
+                                               dtype=torch.float64) -> torch.Tensor:
+    """dc[q, j] = sum over the (i, o) with i // group_rows = q whose label is j of (x^T g)[i, o] (include/nnc_cbwpgrad_grouped.h,
+    nnc_cbwp_grouped_dc): bit for bit grouped_codebook_centroid_grad(x, g, codes.to_dense(), codes.k, ...) at every number of rows and
+    dtype, the indices never unpacked and dW never written.  x: (..., kdim), g: (..., ncols), both float32, both bfloat16 or both
+    float16, with the same leading shape.  Returns ``dtype`` (float64 or float32) (G, codes.k), the gradient with respect to the
+    float32 centres.  No host read."""
+    if not isinstance(x, torch.Tensor) or x.dtype not in _X_DT:
+        raise TypeError(f"x must be a float32, bfloat16 or float16 tensor, got {getattr(x, 'dtype', type(x))}")
+    if not isinstance(g, torch.Tensor) or g.dtype != x.dtype:
+        raise TypeError(f"x and g must have one dtype, got {x.dtype} and {getattr(g, 'dtype', type(g))}")
+    _require_cuda(x, "x")
+    _require_cuda(g, "g")
+    codes, group_rows = _wide_codes(codes), int(group_rows)
+    groups = _grouped_wide_args(codes, None, group_rows)
+    kdim, ncols, k, bits = codes.kdim, codes.ncols, codes.k, codes.bits
+    lead, m = _rows(g, "g", ncols)
+    _dc_args(x, lead, kdim, "x, g and codes", codes.packed, g, dtype)
+    L = nat.load()
+    dc = torch.empty((groups, k), dtype=dtype, device=x.device)
+    ws_bytes = int(L.nnc_cbwp_grouped_dc_workspace_bytes(_X_DT[x.dtype], m, kdim, ncols, bits, k, group_rows))
+    ws = _workspace(ws_bytes, x.device)
+    nat.check(L.nnc_cbwp_grouped_dc(_ptr(x), _ptr(g), _X_DT[x.dtype], m, kdim, _ptr(codes.packed), codes.nbytes, bits, ncols, k, group_rows, _ptr(dc),
+                                    1 if dtype == torch.float64 else 0, _ptr(ws), ws_bytes, _stream(x)))
+    return dc
+
+
+def cbwp_grouped_dx_plan(dtype, m: int, kdim: int, ncols: int, bits: int, k: int, group_rows: int, cus: int) -> dict:
+    """Host: the plan nnc_cbwp_grouped_dx follows for g of ``dtype`` on a device with ``cus`` compute units
+    (include/nnc_cbwpgrad_grouped.h), as a dict keyed by _native.CBWPDX_GROUPED_PLAN_FIELDS.  No device needed."""
+    return _cbwp_grad_plan("nnc_cbwp_grouped_dx_plan", nat.CBWPDX_GROUPED_PLAN_FIELDS, dtype, m, kdim, ncols, bits, k, group_rows, cus)
+
+
+def cbwp_grouped_dc_plan(dtype, m: int, kdim: int, ncols: int, bits: int, k: int, group_rows: int, cus: int) -> dict:
+    """Host: the plan nnc_cbwp_grouped_dc follows for x and g of ``dtype`` (include/nnc_cbwpgrad_grouped.h), as a dict keyed by
+    _native.CBWPDC_GROUPED_PLAN_FIELDS.  No device needed."""
+    return _cbwp_grad_plan("nnc_cbwp_grouped_dc_plan", nat.CBWPDC_GROUPED_PLAN_FIELDS, dtype, m, kdim, ncols, bits, k, group_rows, cus)
+
+
+def grouped_wide_packed_codebook_linear(x: torch.Tensor, codes: WidePackedCodes, centers: torch.Tensor, group_rows: int,
+                                        bias: torch.Tensor | None = None, relu: bool = False) -> torch.Tensor:
+    """grouped_wide_packed_codebook_matmul with gradients for x, centers (G, K) and bias, through the autograd Function of
+    codebook_linear.  The forward is the same nnc_cbwp_grouped call (under no_grad the bits of
+    grouped_wide_packed_codebook_matmul, which stays inference only); the backward runs grouped_wide_packed_codebook_matmul_dx only if
+    x needs a gradient and grouped_wide_packed_codebook_centroid_grad (float32) only if centers does.  The ReLU mask and the bias
+    gradient are codebook_linear's.  The indices get no gradient.  No host read.  A bfloat16 or float16 x is accepted as in
+    wide_packed_codebook_linear: the output and dx have x's dtype, the float32 centers and bias get float32 gradients; a half
+    ``centers`` or ``bias`` raises ``TypeError``."""
+    codes, group_rows = _wide_codes(codes), int(group_rows)
+    if isinstance(x, torch.Tensor) and x.dtype in _H16_DT:
+        _require_centers_bias(centers, bias)
+    return _CodebookLinear.apply(
+        x, codes, centers, bias, bool(relu), codes.kdim, codes.ncols,
+        lambda x2, cd, c, b, r: grouped_wide_packed_codebook_matmul(x2, cd, c, group_rows, bias=b, relu=r),
+        lambda g2, cd, c: grouped_wide_packed_codebook_matmul_dx(g2, cd, c, group_rows),
+        lambda x2, g2, cd, c: grouped_wide_packed_codebook_centroid_grad(x2, g2, cd, group_rows, dtype=torch.float32))
 
 
 def huffman_lengths(counts) -> tuple:
